@@ -13,14 +13,27 @@ anything touches HIP, relays rank 0's JSON line and exits with the child's
 status.  --dry-run replaces the GPU engine by a host stand-in and RCCL by gloo
 so that the launcher / rank plumbing can be rehearsed on a machine without GPUs.
 
-Extra objects on the same line at N = 1 (each builds an engine of its own after the timed region, none is the headline):
+A plain run sets up, warms up (--warmup steps), times --steps steps and prints the headline line (metric, value,
+unit, higher_is_better, dtype, ms_per_step = milliseconds per timed step) and nothing else.  --dump-outputs DIR
+then writes what the last timed step computed (rank 0, float32 .npy, about 24 MB in all):
+  d_y2_losses.npy   [loss_real, loss_fake] returned by netD_y2_train
+  d_dem_losses.npy  [loss_real_dem, loss_fake_dem] returned by netD_dem_train
+  g_losses.npy      the six scalars returned by netG_train
+  {G,D_y2,D_dem}_weights.npy  every weight of the network after the step, flat, in parameter-table order
+Inputs and initial weights are seeded, so the same arguments give the same inputs in every run.
+
+--full adds everything else to the same line, measured after the timed region: the roofline of the convolution class
+(two profiled steps), the generator-forward and generator-iteration probes, the CPU baseline (run first, before the
+GPU is touched), the collective-free step at N > 1, and at N = 1 the extra objects below (each builds an engine of its
+own, none is the headline).  DEPGAN_BENCH_STEP_ONLY and DEPGAN_PROFILE_DUMP act in --full runs only.
+Extra objects on the same line at N = 1:
   config4:   BASELINE configs[3] on the bf16 matrix pipe (256x256x2, bf16 weights and activations, fp32 accumulate)
   config5:   BASELINE configs[4], the DEP-UResNet supervised step
   f32_split: the headline workload with the opt-in split-product convolutions (fp32 operands as exact sums of bf16
              terms, six / three cross products on the bf16 pipe)
   direct_conv: the headline workload with DEPGAN_WINOGRAD=0 (3x3 layers on the direct implicit-GEMM kernel)
 
-Prints ONE JSON line on rank 0 (contract in the task statement), including
+Prints ONE JSON line on rank 0; with --full it includes
   roofline:     MFMA implicit-GEMM convolution class (dominant kernels) --
                 algorithmic FLOPs / HIP-event time, measured live on extra steps
                 outside the timed region, against the 157.3 TFLOP/s fp32 matrix peak
@@ -375,6 +388,17 @@ def bench_config5(dg, torch, dev, B, steps=5):
                                      "other (batch statistics, affine / dropout passes, noise MLP)": round(parts[2][0], 3)}}
 
 
+def build_if_stale():
+    """build() takes a lock file inside the tree even when nothing is stale, and the tree that __graft_entry__.build()
+    compiled may be read-only for the process that benchmarks it: build only when libdepgan.so is missing or older
+    than a source it is built from.  Loading the library still checks its source hash (dep_gan_im_amd/_lib.py)."""
+    from dep_gan_im_amd import build as B
+    deps = [os.path.join(B.CSRC, f) for f in os.listdir(B.CSRC) if f.endswith((".hip", ".h", ".inc"))]
+    deps.append(os.path.join(ROOT, "include", "depgan.h"))
+    if not os.path.exists(B.LIB) or any(os.path.getmtime(d) > os.path.getmtime(B.LIB) for d in deps):
+        B.build()
+
+
 def launch_ranks(args, argv):
     """`python bench.py --gpus N` with no launcher around it: start N ranks as a child torch.distributed.run (this
     process has not touched HIP and never will), relay rank 0's JSON line, exit with the child's status."""
@@ -479,7 +503,15 @@ def main():
     ap.add_argument("--dry-run", action="store_true", help="no GPU: host stand-in engine + gloo (plumbing rehearsal)")
     ap.add_argument("--n1-value", type=float, default=None,
                     help="slices/s of the N=1 run, to print scaling_efficiency next to an N>1 value")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything besides the headline (roofline, probes, CPU baseline, other configs)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (float32)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if args.dump_outputs and args.dry_run:
+        ap.error("--dump-outputs needs the GPU path (a --dry-run computes nothing to dump)")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         return launch_ranks(args, sys.argv[1:])
@@ -496,13 +528,12 @@ def main():
     # The CPU leg runs FIRST, before this process touches the GPU: the GPU phase that follows is then one contiguous
     # stretch at the end of the run instead of a few seconds hidden in front of ~20 s of host work.
     cpu = None
-    if world == 1 and rank == 0 and not args.no_cpu_baseline:
+    if args.full and world == 1 and rank == 0 and not args.no_cpu_baseline:
         cpu = cpu_baseline(args.cpu_sample)
 
     import torch
     import dep_gan_im_amd as dg
-    from dep_gan_im_amd.build import build
-    build()
+    build_if_stale()
 
     # DEPGAN_BENCH_ONE_GPU=1: rehearsal of the multi-rank path on a box with ONE GPU -- every rank uses cuda:0 and the group
     # is gloo (RCCL refuses two ranks on one device); the slices/s of such a run mean nothing, the plumbing is what runs
@@ -535,9 +566,7 @@ def main():
     x, y2, z, ep = [torch.from_numpy(a).to(dev) for a in synth(1000 + rank, B)]
 
     def step():
-        tr.netD_y2_train([y2, x, z, ep])
-        tr.netD_dem_train([y2, x, z, ep])
-        tr.netG_train([x, y2, z])
+        return (tr.netD_y2_train([y2, x, z, ep]), tr.netD_dem_train([y2, x, z, ep]), tr.netG_train([x, y2, z]))
 
     def barrier():
         if dp is not None:
@@ -549,7 +578,7 @@ def main():
     barrier()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        step()
+        outs = step()
     barrier()
     dt = time.perf_counter() - t0
     if dp is not None:
@@ -558,6 +587,42 @@ def main():
         dt = float(t.item())
     ms = dt / args.steps * 1e3
     value = B * world * args.steps / dt
+    if args.dump_outputs and rank == 0:
+        # the replicas are identical after every update, so rank 0's results stand for all of them
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for name, v in zip(("d_y2_losses", "d_dem_losses", "g_losses"), outs):
+            np.save(os.path.join(args.dump_outputs, name + ".npy"), np.asarray(v, np.float32))
+        for net in ("G", "D_y2", "D_dem"):
+            w = tr.engine.get_weights(net)
+            np.save(os.path.join(args.dump_outputs, net + "_weights.npy"),
+                    np.concatenate([a.reshape(-1) for a in w.values()]).astype(np.float32))
+    line = {"metric": "2D slices/sec (G+2D+GP train step), 256x256x1 fp32", "value": round(value, 3),
+            "unit": "slices/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+            "ms_per_step": round(ms, 3), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+            "dtype": "f32", "data": "synthetic" if not one_gpu else "synthetic; REHEARSAL: all ranks on one GPU, gloo",
+            "config": {"workload": "DEP-GAN-IM twoCritics canonical train step (critic-Y2 + critic-DEM + G update, "
+                                   "WGAN-GP), batch %d per GPU, 256x256x1" % B,
+                       "per_gpu_batch": B, "global_batch": B * world, "parallelism": "dp%d" % world}}
+    if args.n1_value:
+        line["scaling_efficiency_vs_n1_value"] = round(value / (world * args.n1_value), 4)
+    eng = tr.engine
+
+    def collectives(expected):
+        return {"per_step": 3, "issued": dp.calls, "expected": expected,
+                "path": "direct RCCL: ncclAllReduce from libdepgan on the engine's stream" if dp.direct
+                        else "torch.distributed hook (%s)" % ("host staging, gloo" if one_gpu else "nccl"),
+                "rccl_nranks": eng.rccl_info()[0] if dp.direct else None,
+                "message_floats": [int(eng.arena(n, 2)[1]) + 8 for n in ("D_y2", "D_dem", "G")]}
+
+    if not args.full:
+        if rank == 0:
+            if dp is not None:
+                line["collectives"] = collectives(3 * (args.warmup + args.steps))
+            print(json.dumps(line), flush=True)
+        if dp is not None:
+            torch.distributed.destroy_process_group()
+        return 0
+
     single_ms = None
     if dp is not None and not os.environ.get("DEPGAN_BENCH_STEP_ONLY"):
         # the same step without its collectives, on an engine of its own (replicas must not diverge), max over ranks
@@ -579,7 +644,6 @@ def main():
         single_ms = float(t.item())
 
     # ---- roofline of the dominant kernel class, HIP events on the engine's stream ----
-    eng = tr.engine
     eng.profile(True)
     eng.profile_reset()
     for _ in range(2):
@@ -695,28 +759,15 @@ def main():
                               "frac": round(gf_tf / PEAK_F32_MFMA, 4), "slices_per_s": round(B / (gf_ms * 1e-3), 1)}}
 
     if rank == 0:
-        line = {"metric": "2D slices/sec (G+2D+GP train step), 256x256x1 fp32", "value": round(value, 3),
-                "unit": "slices/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-                "ms_per_step": round(ms, 3), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-                "dtype": "f32", "data": "synthetic" if not one_gpu else "synthetic; REHEARSAL: all ranks on one GPU, gloo",
-                "config": {"workload": "DEP-GAN-IM twoCritics canonical train step (critic-Y2 + critic-DEM + G update, "
-                                       "WGAN-GP), batch %d per GPU, 256x256x1" % B,
-                           "per_gpu_batch": B, "global_batch": B * world, "parallelism": "dp%d" % world},
-                "roofline": roofline}
+        line["roofline"] = roofline
         if dp is not None:
-            line["collectives"] = {"per_step": 3, "issued": dp.calls,
-                                   "expected": 3 * (args.warmup + args.steps + 2) + 2 * 12 * 3,
-                                   "path": "direct RCCL: ncclAllReduce from libdepgan on the engine's stream" if dp.direct
-                                           else "torch.distributed hook (%s)" % ("host staging, gloo" if one_gpu else "nccl"),
-                                   "rccl_nranks": eng.rccl_info()[0] if dp.direct else None,
-                                   "message_floats": [int(eng.arena(n, 2)[1]) + 8 for n in ("D_y2", "D_dem", "G")]}
+            # + the two profiled steps and the generator-iteration probes (two forms, three runs each, 12 collectives a run)
+            line["collectives"] = collectives(3 * (args.warmup + args.steps + 2) + 2 * 12 * 3)
             if single_ms is not None:
                 # self-check for the first multi-GPU run: the same step on the same GPU without the collectives (a fresh
                 # single-rank engine, max over ranks) -- weak-scaling efficiency is its ratio to the timed step
                 line["collectives"]["ms_per_step_without_collectives"] = round(single_ms, 3)
                 line["scaling_efficiency"] = round(single_ms / ms, 4)
-        if args.n1_value:
-            line["scaling_efficiency_vs_n1_value"] = round(value / (world * args.n1_value), 4)
         if config4 is not None:
             line["config4"] = config4
         if config5 is not None:

@@ -1,6 +1,6 @@
-"""Per-shape roofline table from the per-launch CSV that `DEPGAN_PROFILE_DUMP=<path> python bench.py` writes
-(depgan_profile_dump: class,label,ms,gflop for every launch of the two profiled steps; HIP events on the engine's
-stream).  The rocprofv3 kernel names merge all shapes of a template instantiation; this table is the per-layer view.
+"""Per-shape roofline table from the per-launch CSV that `DEPGAN_PROFILE_DUMP=<path> python bench.py --full`
+writes (depgan_profile_dump: class,label,ms,gflop for every launch of the two profiled steps; HIP events on the
+engine's stream).  The rocprofv3 kernel names merge all shapes of a template instantiation; this table is the per-layer view.
 
 usage: python tools/layer_table.py launches.csv [steps=2] > profiles/rNN_x_layer_table.md"""
 import collections
