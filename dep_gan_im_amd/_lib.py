@@ -22,6 +22,8 @@ EXPORTS = [
     "depgan_set_allreduce", "depgan_get_adam_step", "depgan_set_adam_step", "depgan_gen_iteration", "depgan_eval_divide",
     "depgan_source_hash", "depgan_debug_capture", "depgan_debug_tensor", "depgan_rccl_unique_id", "depgan_rccl_init",
     "depgan_rccl_broadcast", "depgan_rccl_info", "depgan_rccl_shutdown", "depgan_op_conv2d_wgrad_bf16",
+    "depgan_op_bn_moments", "depgan_op_bn_backward", "depgan_op_affine_act", "depgan_op_softmax_ce4",
+    "depgan_op_bn_rows_fwd", "depgan_op_bn_rows_bwd", "depgan_op_small_gemm",
 ]
 
 ABI_VERSION = 3          # DEPGAN_ABI_VERSION of the include/depgan.h this binding was written against
@@ -132,6 +134,14 @@ def load():
     lib.depgan_op_deconv2x2.argtypes = [vp] * 6 + [C.c_int] * 6 + [vp]
     lib.depgan_op_deconv2x2_wgrad.argtypes = [vp] * 4 + [C.c_int] * 5 + [vp]
     lib.depgan_op_conv2d_stamps.argtypes = [vp, vp, vp] + [C.c_int] * 6 + [vp, C.c_int, vp]
+    L, f, u = C.c_long, C.c_float, C.c_uint
+    lib.depgan_op_bn_moments.argtypes = [vp, L, L, L] + [C.c_int] * 4 + [vp, vp, L, vp]
+    lib.depgan_op_bn_backward.argtypes = [vp] * 3 + [L] * 3 + [C.c_int] * 4 + [vp] * 3 + [f] * 3 + [vp, vp, L, vp]
+    lib.depgan_op_affine_act.argtypes = [vp] * 4 + [L] * 3 + [vp] * 4 + [C.c_int] * 6 + [u, f, vp]
+    lib.depgan_op_softmax_ce4.argtypes = [vp] * 5 + [L, vp]
+    lib.depgan_op_bn_rows_fwd.argtypes = [vp, vp] + [C.c_int] * 3 + [vp, vp] + [f] * 3 + [vp] * 4 + [C.c_int, vp]
+    lib.depgan_op_bn_rows_bwd.argtypes = [vp] * 4 + [C.c_int] * 3 + [vp] * 5 + [vp]
+    lib.depgan_op_small_gemm.argtypes = [C.c_int] + [vp] * 4 + [C.c_int] * 3 + [vp]
     lib.depgan_uresnet_grads.argtypes = [vp, vp, vp, vp, C.c_int, C.c_uint, fp]
     lib.depgan_uresnet_step.argtypes = [vp, vp, vp, vp, C.c_int, C.c_uint, fp]
     lib.depgan_uresnet_eval.argtypes = [vp, vp, vp, vp, C.c_int, fp]

@@ -174,6 +174,7 @@ struct depgan_ctx {
   float* raw = nullptr;            // dWraw scratch (largest kernel)
   float* Sraw = nullptr;           // [256] raw column sums
   float* scratch = nullptr;        // reductions
+  size_t scratchFloats = 0;
   float* scal = nullptr;           // device scalars
   float* scal_multi = nullptr;     // 8 floats per evaluation of depgan_g_eval_multi
   float* fake_y2 = nullptr;        // [B*H*W]

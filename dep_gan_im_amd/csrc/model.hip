@@ -4,6 +4,7 @@
 // update (GT:574-598; A7-A9) and Keras Adam (A10).  The algebra follows
 // oracle/manual.py step for step.
 #include "model.h"
+#include "train_ops.h"
 
 #include <dlfcn.h>
 #include <math.h>
@@ -1380,7 +1381,8 @@ int depgan_create(const depgan_config* cfg, depgan_ctx** out) {
   if (rc == DG_OK) rc = dmalloc(c, &c->raw, (size_t)9 * 256 * 256);
   if (rc == DG_OK && !c->train_bn) rc = dmalloc(c, &c->raw_all, c->g.nTrain);
   if (rc == DG_OK) rc = dmalloc(c, &c->Sraw, 256);
-  if (rc == DG_OK) rc = dmalloc(c, &c->scratch, (size_t)(1 << 20) + (size_t)cfg->batch * 20000);
+  c->scratchFloats = (size_t)(1 << 20) + (size_t)cfg->batch * 20000;
+  if (rc == DG_OK) rc = dmalloc(c, &c->scratch, c->scratchFloats);
   if (rc == DG_OK) rc = dmalloc(c, &c->scal, 16);
   if (rc == DG_OK) rc = dmalloc(c, &c->scal_multi, 8 * DEPGAN_MAX_MULTI);
   if (rc == DG_OK) rc = dmalloc(c, &c->z_best, (size_t)cfg->batch * 32);
@@ -2017,6 +2019,136 @@ int depgan_eval_counts(const float* x, int nicg, const double* pred, const float
   }
   hipFree(dev);
   return rc;
+}
+
+
+// ---- learning-phase-1 operators (train_ops.hip), as uresnet.hip calls them; each view is NHWC with the strides
+// (sB, sY, sX) in floats and channel stride 1 ----
+static TView op_view(const float* p, long sB, long sY, long sX) {
+  TView v;
+  v.p = const_cast<float*>(p);
+  v.sB = sB;
+  v.sY = sY;
+  v.sX = sX;
+  return v;
+}
+static int op_alloc(float** p, size_t floats, const char* who) {
+  if (hipMalloc((void**)p, (floats ? floats : 1) * sizeof(float)) != hipSuccess) {
+    dg_set_error("%s: out of device memory (%zu floats)", who, floats);
+    return DG_ERR_HIP;
+  }
+  return DG_OK;
+}
+static size_t op_scratch(long scratch_floats, size_t need) { return scratch_floats > 0 ? (size_t)scratch_floats : need; }
+
+int depgan_op_bn_moments(const float* x, long sB, long sY, long sX, int B, int H, int W, int C, float* mean, float* var,
+                         long scratch_floats, void* stream) {
+  if (!x || !mean || !var || B < 1 || H < 1 || W < 1 || C < 4) { dg_set_error("op_bn_moments: bad argument"); return DG_ERR_ARG; }
+  hipStream_t st = (hipStream_t)stream;
+  const size_t cap = op_scratch(scratch_floats, dg_col_moments_scratch(B, H, W, C));
+  float* scratch = nullptr;
+  DGCHECK(op_alloc(&scratch, cap, "op_bn_moments"));
+  int rc = dg_col_moments(op_view(x, sB, sY, sX), B, H, W, C, mean, var, scratch, cap, st);
+  hipStreamSynchronize(st);
+  hipFree(scratch);
+  return rc;
+}
+
+int depgan_op_bn_backward(const float* dy, const float* raw, float* draw, long sB, long sY, long sX, int B, int H, int W,
+                          int C, const float* gamma, const float* mean, const float* var, float eps, float invN,
+                          float dyscale, float* dgamma, float* dbeta, long scratch_floats, void* stream) {
+  if (!dy || !raw || !draw || !gamma || !mean || !var || !dgamma || !dbeta || B < 1 || H < 1 || W < 1 || C < 4) {
+    dg_set_error("op_bn_backward: bad argument");
+    return DG_ERR_ARG;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  const size_t cap = op_scratch(scratch_floats, dg_colsum_pair_scratch(B, H, W, C));
+  float *scratch = nullptr, *coef = nullptr;
+  DGCHECK(op_alloc(&scratch, cap, "op_bn_backward"));
+  int rc = op_alloc(&coef, (size_t)8 * C, "op_bn_backward");
+  if (rc == DG_OK) {
+    // uresnet.hip: dg_bn_train_prepare (s, t, rstd) in the forward; dg_colsum_pair -> dg_bn_bwd_coeffs -> dg_axpby_ch
+    float *s = coef, *t = coef + C, *rstd = coef + 2 * C, *sums = coef + 3 * C, *cA = coef + 5 * C, *cB = coef + 6 * C,
+          *cC = coef + 7 * C;
+    const TView dyv = op_view(dy, sB, sY, sX), rawv = op_view(raw, sB, sY, sX), dv = op_view(draw, sB, sY, sX);
+    rc = dg_bn_train_prepare(gamma, gamma, mean, var, eps, 0.f, 0.f, nullptr, nullptr, s, t, rstd, C, st);  // t unused
+    if (rc == DG_OK) rc = dg_colsum_pair(dyv, rawv, mean, B, H, W, C, sums, scratch, cap, st);
+    if (rc == DG_OK) rc = dg_bn_bwd_coeffs(sums, mean, rstd, s, invN, dyscale, dgamma, dbeta, cA, cB, cC, C, st);
+    if (rc == DG_OK) rc = dg_axpby_ch(dyv, rawv, dv, B, H, W, C, cA, cB, cC, st);
+  }
+  hipStreamSynchronize(st);
+  hipFree(scratch);
+  hipFree(coef);
+  return rc;
+}
+
+int depgan_op_affine_act(const float* in, float* out, float* out_pre, const float* res, long sB, long sY, long sX,
+                         const float* s, const float* t, const float* film_mul, const float* film_add, int film_ld,
+                         int relu, int B, int H, int W, int C, unsigned drop_seed, float drop_rate, void* stream) {
+  if (!in || !out || !s || !t || (!film_mul != !film_add) || B < 1 || H < 1 || W < 1 || C < 4) {
+    dg_set_error("op_affine_act: bad argument");
+    return DG_ERR_ARG;
+  }
+  AffineActArgs a;
+  memset(&a, 0, sizeof(a));
+  a.in = op_view(in, sB, sY, sX);
+  a.out = op_view(out, sB, sY, sX);
+  a.out_pre = out_pre ? op_view(out_pre, sB, sY, sX) : null_view();
+  a.res = res ? op_view(res, sB, sY, sX) : null_view();
+  a.s = s;
+  a.t = t;
+  a.film_mul = film_mul;
+  a.film_add = film_add;
+  a.film_ld = film_ld;
+  a.relu = relu;
+  a.B = B; a.H = H; a.W = W; a.C = C;
+  a.drop_seed = drop_seed;
+  a.drop_rate = drop_rate;
+  return dg_affine_act(a, (hipStream_t)stream);
+}
+
+int depgan_op_softmax_ce4(const float* logits, const float* onehot, float* probs, float* dz, float* loss_sum, long P,
+                          void* stream) {
+  if (!logits || !probs || P < 1 || (onehot && (!dz || !loss_sum))) { dg_set_error("op_softmax_ce4: bad argument"); return DG_ERR_ARG; }
+  hipStream_t st = (hipStream_t)stream;
+  if (!onehot) return dg_softmax4(logits, probs, P, st);
+  float* scratch = nullptr;
+  DGCHECK(op_alloc(&scratch, 1024, "op_softmax_ce4"));
+  int rc = dg_softmax_ce4(logits, onehot, probs, dz, loss_sum, P, scratch, st);
+  hipStreamSynchronize(st);
+  hipFree(scratch);
+  return rc;
+}
+
+int depgan_op_bn_rows_fwd(const float* x, float* y, int R, int C, int ld, const float* gamma, const float* beta,
+                          float eps, float momentum, float corr, float* moving_mean, float* moving_var, float* mean,
+                          float* rstd, int relu, void* stream) {
+  if (!x || !y || !gamma || !beta || !mean || !rstd || (!moving_mean != !moving_var) || R < 1 || C < 1 || ld < C) {
+    dg_set_error("op_bn_rows_fwd: bad argument");
+    return DG_ERR_ARG;
+  }
+  return dg_bn_rows_fwd(x, y, R, C, ld, gamma, beta, eps, momentum, corr, moving_mean, moving_var, mean, rstd, relu,
+                        (hipStream_t)stream);
+}
+int depgan_op_bn_rows_bwd(const float* dy, const float* x, const float* relu_out, float* dx, int R, int C, int ld,
+                          const float* gamma, const float* mean, const float* rstd, float* dgamma, float* dbeta,
+                          void* stream) {
+  if (!dy || !x || !dx || !gamma || !mean || !rstd || !dgamma || !dbeta || R < 1 || C < 1 || ld < C) {
+    dg_set_error("op_bn_rows_bwd: bad argument");
+    return DG_ERR_ARG;
+  }
+  return dg_bn_rows_bwd(dy, x, relu_out, dx, R, C, ld, gamma, mean, rstd, dgamma, dbeta, (hipStream_t)stream);
+}
+
+int depgan_op_small_gemm(int form, const float* A, const float* Bm, const float* bias, float* Cm, int M, int K, int N,
+                         void* stream) {
+  if (!A || !Bm || !Cm || M < 1 || K < 1 || N < 1) { dg_set_error("op_small_gemm: bad argument"); return DG_ERR_ARG; }
+  hipStream_t st = (hipStream_t)stream;
+  if (form == 0) return dg_small_gemm(A, Bm, bias, Cm, M, K, N, st);
+  if (form == 1) return dg_small_gemm_at(A, Bm, Cm, M, K, N, st);
+  if (form == 2) return dg_small_gemm_bt(A, Bm, Cm, M, K, N, st);
+  dg_set_error("op_small_gemm: form %d is not 0, 1 or 2", form);
+  return DG_ERR_ARG;
 }
 
 }  // extern "C"

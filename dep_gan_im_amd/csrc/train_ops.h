@@ -3,12 +3,16 @@
 #pragma once
 #include "common.h"
 
-// per-channel batch mean and biased variance of an NHWC view (two passes: mean, then centred squares)
-// scratch: 2 * 1024 * C floats
-int dg_col_moments(TView v, int B, int H, int W, int C, float* mean, float* var, float* scratch, hipStream_t st);
-// sums[0..C) = sum_p d[p][c] ; sums[C..2C) = sum_p d[p][c] * (x[p][c] - mean[c])      scratch: 2 * 1024 * C floats
-int dg_colsum_pair(TView d, TView x, const float* mean, int B, int H, int W, int C, float* sums, float* scratch,
+// per-channel batch mean and biased variance of an NHWC view (one pass, shifted sums; C % 4 == 0, C <= 1024).
+// scratch: dg_col_moments_scratch(B, H, W, C) floats (at most 3 * 1024 * C); DG_ERR_ARG when scratch_floats is less
+int dg_col_moments(TView v, int B, int H, int W, int C, float* mean, float* var, float* scratch, size_t scratch_floats,
                    hipStream_t st);
+size_t dg_col_moments_scratch(int B, int H, int W, int C);
+// sums[0..C) = sum_p d[p][c] ; sums[C..2C) = sum_p d[p][c] * (x[p][c] - mean[c])
+// scratch: dg_colsum_pair_scratch(B, H, W, C) floats (at most 2 * 1024 * C); DG_ERR_ARG when scratch_floats is less
+int dg_colsum_pair(TView d, TView x, const float* mean, int B, int H, int W, int C, float* sums, float* scratch,
+                   size_t scratch_floats, hipStream_t st);
+size_t dg_colsum_pair_scratch(int B, int H, int W, int C);
 
 // training-mode BN bookkeeping for one layer: s = gamma*rsqrt(var+eps), t = beta - mean*s, rstd;
 // moving_mean/var <- momentum*moving + (1-momentum)*(mean, var*corr)       

@@ -88,17 +88,39 @@ __global__ void colsum2_final(const float* __restrict__ part, int nb, int C, flo
   if (threadIdx.x == 0) (j == 0 ? out0 : out1)[c] = s * scale;
 }
 
-static int colsum2_launch(int mode, TView v, TView w, const float* m, int B, int H, int W, int C, float scale,
-                          float* out0, float* out1, float* scratch, hipStream_t st) {
-  if ((C % 4) || C > 1024) {
-    dg_set_error("train colsum: C must be a multiple of 4 and <= 1024 (got %d)", C);
-    return DG_ERR_ARG;
-  }
-  const long npix = (long)B * H * W;
+// grid of the per-channel reductions over pixels: at most 1024 blocks of ppb pixels each (the last one may be short)
+static void t_pix_grid(long npix, int* nb_out, int* ppb_out) {
   int nb = (int)((npix + 255) / 256);
   if (nb > 1024) nb = 1024;
   const int ppb = (int)((npix + nb - 1) / nb);
-  nb = (int)((npix + ppb - 1) / ppb);
+  *nb_out = (int)((npix + ppb - 1) / ppb);
+  *ppb_out = ppb;
+}
+size_t dg_col_moments_scratch(int B, int H, int W, int C) {
+  int nb, ppb;
+  t_pix_grid((long)B * H * W, &nb, &ppb);
+  return (size_t)nb * 3 * C;
+}
+size_t dg_colsum_pair_scratch(int B, int H, int W, int C) {
+  int nb, ppb;
+  t_pix_grid((long)B * H * W, &nb, &ppb);
+  return (size_t)nb * 2 * C;
+}
+
+static int colsum2_launch(int mode, TView v, TView w, const float* m, int B, int H, int W, int C, float scale,
+                          float* out0, float* out1, float* scratch, size_t scratch_floats, hipStream_t st) {
+  if ((C % 4) || C > 1024 || B < 1 || H < 1 || W < 1) {
+    dg_set_error("train colsum: C must be a multiple of 4 and <= 1024, B H W >= 1 (got %d %d %d %d)", B, H, W, C);
+    return DG_ERR_ARG;
+  }
+  const long npix = (long)B * H * W;
+  int nb, ppb;
+  t_pix_grid(npix, &nb, &ppb);
+  if ((size_t)nb * 2 * C > scratch_floats) {
+    dg_set_error("train colsum: scratch holds %zu floats, %d blocks x 2 x %d channels need %zu", scratch_floats, nb, C,
+                 (size_t)nb * 2 * C);
+    return DG_ERR_ARG;
+  }
   const size_t lds = 256 * 8 * sizeof(float);
   auto is_flat = [&](const TView& t) { return !t.p || (t.sY == (long)W * t.sX && t.sB == (long)H * t.sY); };
   const bool flat = is_flat(v) && is_flat(w);
@@ -205,16 +227,20 @@ __global__ void moments_final(const float* __restrict__ part, int nb, int C, lon
   }
 }
 
-int dg_col_moments(TView v, int B, int H, int W, int C, float* mean, float* var, float* scratch, hipStream_t st) {
-  if ((C % 4) || C > 1024) {
-    dg_set_error("train moments: C must be a multiple of 4 and <= 1024 (got %d)", C);
+int dg_col_moments(TView v, int B, int H, int W, int C, float* mean, float* var, float* scratch, size_t scratch_floats,
+                   hipStream_t st) {
+  if ((C % 4) || C > 1024 || B < 1 || H < 1 || W < 1) {
+    dg_set_error("train moments: C must be a multiple of 4 and <= 1024, B H W >= 1 (got %d %d %d %d)", B, H, W, C);
     return DG_ERR_ARG;
   }
   const long npix = (long)B * H * W;
-  int nb = (int)((npix + 255) / 256);
-  if (nb > 1024) nb = 1024;
-  const int ppb = (int)((npix + nb - 1) / nb);
-  nb = (int)((npix + ppb - 1) / ppb);
+  int nb, ppb;
+  t_pix_grid(npix, &nb, &ppb);
+  if ((size_t)nb * 3 * C > scratch_floats) {
+    dg_set_error("train moments: scratch holds %zu floats, %d blocks x 3 x %d channels need %zu", scratch_floats, nb, C,
+                 (size_t)nb * 3 * C);
+    return DG_ERR_ARG;
+  }
   const size_t lds = 256 * 8 * sizeof(float);
   const bool flat = (v.sY == (long)W * v.sX && v.sB == (long)H * v.sY);
   if (flat)
@@ -227,8 +253,8 @@ int dg_col_moments(TView v, int B, int H, int W, int C, float* mean, float* var,
   return DG_OK;
 }
 int dg_colsum_pair(TView d, TView x, const float* mean, int B, int H, int W, int C, float* sums, float* scratch,
-                   hipStream_t st) {
-  return colsum2_launch(2, d, x, mean, B, H, W, C, 1.0f, sums, sums + C, scratch, st);
+                   size_t scratch_floats, hipStream_t st) {
+  return colsum2_launch(2, d, x, mean, B, H, W, C, 1.0f, sums, sums + C, scratch, scratch_floats, st);
 }
 
 __global__ void bn_train_prepare_kernel(const float* gamma, const float* beta, const float* mean, const float* var,
@@ -266,8 +292,12 @@ __device__ __forceinline__ unsigned hash_u32(unsigned i, unsigned seed) {
 }
 
 // FLAT: every view is pixel-contiguous, so pixel q of view t sits at q * t.sX -- 32-bit index arithmetic only.
+// No contraction: every step below is one correctly rounded operation (tests/test_gpu_train_ops.py replays it bitwise).
+// __fmul_rn / __fadd_rn do not ensure that: in HIP they are plain * and +, and under the default -ffp-contract=fast
+// __fadd_rn(__fmul_rn(x, s), t) compiled to one FMA.  The pragma covers the operators written in this body.
 template <bool FLAT>
 __global__ void affine_act_kernel(const AffineActArgs a, unsigned drop_thr, float drop_scale) {
+#pragma clang fp contract(off)
   const int C4 = a.C / 4;
   const size_t total = (size_t)a.B * a.H * a.W * C4;
   const unsigned HW = (unsigned)a.H * (unsigned)a.W;
@@ -299,7 +329,7 @@ __global__ void affine_act_kernel(const AffineActArgs a, unsigned drop_thr, floa
     const f32x4 sv = *reinterpret_cast<const f32x4*>(a.s + c);
     const f32x4 tv = *reinterpret_cast<const f32x4*>(a.t + c);
 #pragma unroll
-    for (int k = 0; k < 4; ++k) v[k] = __fadd_rn(__fmul_rn(v[k], sv[k]), tv[k]);
+    for (int k = 0; k < 4; ++k) v[k] = v[k] * sv[k] + tv[k];
     if (a.out_pre.p) *reinterpret_cast<f32x4*>(a.out_pre.p + o_pre + c) = v;
     if (a.film_mul) {
       const f32x4 fm = *reinterpret_cast<const f32x4*>(a.film_mul + (size_t)b * a.film_ld + c);
@@ -445,7 +475,8 @@ __global__ void softmax_ce4_kernel(const float* __restrict__ logits, const float
         const float q = p[k] / S;
         const float r = fminf(fmaxf(q, 1e-7f), 1.0f - 1e-7f);
         lsum -= t[k] * logf(r);
-        const bool in = (q > 1e-7f) && (q < 1.0f - 1e-7f);
+        // clip's gradient passes on the closed interval, bounds included (TF clip_by_value, torch.clamp)
+        const bool in = (q >= 1e-7f) && (q <= 1.0f - 1e-7f);
         gq[k] = in ? (-t[k] * invN / q) : 0.f;    // dL/dq
         dot += gq[k] * p[k];
       }

@@ -147,7 +147,8 @@ static int u_noise_bwd(depgan_ctx* c, const float* z, int n) {
 static int u_bn_act(depgan_ctx* c, GLayer& L, int Ho, int Wo, int n, unsigned drop_seed) {
   ProfScope ps(c, 2, 0.0, "bn fwd: moments + affine / act");
   const double N = (double)n * Ho * Wo;
-  DGCHECK(dg_col_moments(L.raw.view(), n, Ho, Wo, L.Cout, L.bmean, L.bvar, c->scratch, c->st));
+  DGCHECK(dg_col_moments(L.raw.view(), n, Ho, Wo, L.Cout, L.bmean, L.bvar, c->scratch, c->scratchFloats,
+                         c->st));
   DGCHECK(dg_bn_train_prepare(L.gamma, L.beta, L.bmean, L.bvar, kBnEps, kBnMomentum, (float)(N / (N - 1.0)), L.mean,
                               L.var, L.bs, L.bt, L.brstd, L.Cout, c->st));
   AffineActArgs a;
@@ -240,7 +241,8 @@ static int u_bn_bwd(depgan_ctx* c, GLayer& L, TView dy, int Ho, int Wo, int n, f
   ProfScope ps(c, 2, 0.0, "bn bwd: sums + dRAW");
   const double N = (double)n * Ho * Wo;
   *draw = make_view(c->draw_tmp.p, Ho, Wo, L.Cout);
-  DGCHECK(dg_colsum_pair(dy, L.raw.view(), L.bmean, n, Ho, Wo, L.Cout, L.sums, c->scratch, c->st));
+  DGCHECK(dg_colsum_pair(dy, L.raw.view(), L.bmean, n, Ho, Wo, L.Cout, L.sums, c->scratch, c->scratchFloats,
+                         c->st));
   DGCHECK(dg_bn_bwd_coeffs(L.sums, L.bmean, L.brstd, L.bs, (float)(1.0 / N), dyscale, L.dgamma, L.dbeta, L.cA, L.cB,
                            L.cC, L.Cout, c->st));
   return dg_axpby_ch(dy, L.raw.view(), *draw, n, Ho, Wo, L.Cout, L.cA, L.cB, L.cC, c->st);

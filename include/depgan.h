@@ -280,6 +280,40 @@ int depgan_op_deconv2x2(const float* in, const float* w_hwoi, const float* bias,
 int depgan_op_deconv2x2_wgrad(const float* in, const float* dout, float* dw_hwoi, float* colsum, int B, int H, int W,
                               int Cin, int Cout, void* hip_stream);
 
+/* Learning-phase-1 operators (the DEP-UResNet training step's batch-statistics BatchNorm, Dropout, softmax and
+ * cross-entropy), each the internal function uresnet.hip calls.  Device pointers; every NHWC view has the float strides
+ * (sB, sY, sX) and channel stride 1, so a channel slice of a wider buffer is (p + c0, H*W*Ctot, W*Ctot, Ctot).
+ * C % 4 == 0 and (moments, backward) C <= 1024.  scratch_floats: capacity of the reduction scratch the call allocates,
+ * <= 0 for what the launch needs; a capacity below that need is refused with status 1, as in the model. */
+/* mean[c] and biased var[c] over the B*H*W pixels of x */
+int depgan_op_bn_moments(const float* x, long sB, long sY, long sX, int B, int H, int W, int C, float* mean, float* var,
+                         long scratch_floats, void* hip_stream);
+/* backward of y = gamma*(raw - mean)*rsqrt(var + eps) + beta with batch statistics, for dy*dyscale:
+ * dgamma, dbeta (dbeta = sum dy*dyscale) and draw (same strides as dy and raw); invN = 1/(B*H*W) */
+int depgan_op_bn_backward(const float* dy, const float* raw, float* draw, long sB, long sY, long sX, int B, int H, int W,
+                          int C, const float* gamma, const float* mean, const float* var, float eps, float invN,
+                          float dyscale, float* dgamma, float* dbeta, long scratch_floats, void* hip_stream);
+/* out = (relu?(film(in*s + t)) dropped) + res; out_pre (optional) = in*s + t; film_mul / film_add (optional): rows of
+ * film_ld floats per sample; res (optional); drop_seed 0 = no dropout, else keep when hash >= drop_rate * 2^32 */
+int depgan_op_affine_act(const float* in, float* out, float* out_pre, const float* res, long sB, long sY, long sX,
+                         const float* s, const float* t, const float* film_mul, const float* film_add, int film_ld,
+                         int relu, int B, int H, int W, int C, unsigned drop_seed, float drop_rate, void* hip_stream);
+/* softmax over 4 logits per pixel; with onehot: dz = d(mean keras cross-entropy)/dlogits, loss_sum[0] = summed loss */
+int depgan_op_softmax_ce4(const float* logits, const float* onehot, float* probs, float* dz, float* loss_sum, long P,
+                          void* hip_stream);
+/* BatchNorm over the R rows of an [R][ld] matrix (first C columns), moving statistics updated when given:
+ * moving = momentum*moving + (1 - momentum)*(mean, var*corr) */
+int depgan_op_bn_rows_fwd(const float* x, float* y, int R, int C, int ld, const float* gamma, const float* beta,
+                          float eps, float momentum, float corr, float* moving_mean, float* moving_var, float* mean,
+                          float* rstd, int relu, void* hip_stream);
+/* its backward; relu_out (optional): the forward's ReLU output, dy is masked where it is not positive */
+int depgan_op_bn_rows_bwd(const float* dy, const float* x, const float* relu_out, float* dx, int R, int C, int ld,
+                          const float* gamma, const float* mean, const float* rstd, float* dgamma, float* dbeta,
+                          void* hip_stream);
+/* form 0: C[M][N] = A[M][K] B[K][N] (+ bias[N]); 1: C[K][N] = A[M][K]^T B[M][N]; 2: C[M][K] = A[M][N] B[K][N]^T */
+int depgan_op_small_gemm(int form, const float* A, const float* Bm, const float* bias, float* Cm, int M, int K, int N,
+                         void* hip_stream);
+
 #ifdef __cplusplus
 }
 #endif

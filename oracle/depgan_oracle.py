@@ -689,6 +689,7 @@ class OracleUResNet:
     def train_on_batch(self, inputs, labels, drop_seed=None, masks=None):
         x, z = inputs
         loss, grads, stats = uresnet_grads(self.P, x, z, labels, drop_seed, self.dtype, masks)
+        self.last_grads = grads          # the step's gradients, before Adam (tests compare them per tensor)
         self.opt.apply(self.P, grads)
         for name, (mean, var, n, fused) in stats.items():
             # moving variance: Bessel-corrected on the fused 4-D path, n/(n-(1+eps)) on the generic path

@@ -369,6 +369,12 @@ def test_config4_full_size_bf16_pipe_batch32(lib):
     np.testing.assert_allclose(acc, sums, rtol=2e-5)
 
 
+# per tensor, HIP against the fp32 oracle at 256 x 256, batch 32: measured worst 8.1e-5, all of it
+# the fp32 oracle's own error (8.0e-5 against fp64 on that tensor, HIP 1.3e-6); 2e-4 leaves room for the CPU's
+# summation order, and no more than 8 tensors may exceed 1e-4, as at 64 x 64
+FULL_GRAD_TOL = 2e-4
+
+
 def test_config5_full_size_uresnet_batch32(lib):
     """BASELINE configs[4] at its own size (DEP-UResNet, 256x256, batch 32, learning phase 1): loss, whole-gradient
     L2 and the BN moving statistics of one train_on_batch against the oracle on the full batch (batch statistics tie
@@ -394,6 +400,22 @@ def test_config5_full_size_uresnet_batch32(lib):
     ref = O.OracleUResNet({k: v.copy() for k, v in P.items()}, dtype=torch.float32)
     want = ref.train_on_batch([x, z], lab, drop_seed=77, masks=masks)
     assert abs(losses[0] - want) < 1e-3 * abs(want), (losses[0], want)
+    # the step's phase-1 gradient per tensor, against the same oracle evaluation (DESIGN.md section 2 records it next to
+    # the oracle's own fp32 against fp64 at this size, tools/uresnet_full_grads.py): the 64 x 64 bounds
+    # (the biases in front of a batch-statistics BN have an exactly zero gradient: both sides are rounding of zero there,
+    # so those are bounded against the largest gradient entry instead)
+    G = nets[0]._engine.get_grads("G")
+    zero = [k for k in G if k.endswith("/bias") and "segmentation" not in k]
+    gmax = max(float(np.abs(v).max()) for v in ref.last_grads.values())
+    for k in zero:
+        assert float(np.abs(G[k]).max()) < 1e-5 * gmax, k
+    errs = TM.tensor_errors({k: G[k] for k in G if k not in zero}, {k: v for k, v in ref.last_grads.items() if k not in zero})
+    worst = max(errs, key=errs.get)
+    print("config 5 @ 256x256 b32, phase-1 gradient under HIP's masks: worst tensor %s %.2e, %d tensors above 1e-4"
+          % (worst, errs[worst], sum(e > 1e-4 for e in errs.values())))
+    for k in errs:
+        assert errs[k] < FULL_GRAD_TOL, (k, errs[k])
+    assert sum(e > 1e-4 for e in errs.values()) <= 8, sorted(errs.items(), key=lambda kv: -kv[1])[:10]
     for k in w0:
         if k.endswith("moving_mean") or k.endswith("moving_variance"):
             np.testing.assert_allclose(w0[k], ref.P[k], rtol=1e-3, atol=1e-5, err_msg=k)

@@ -128,6 +128,63 @@ def test_phase1_gradients_under_hip_masks(lib, ds):
     eng.close()
 
 
+@pytest.mark.parametrize("n", [1, 3])
+def test_short_batch_grads_step_and_eval(lib, n):
+    """A Keras epoch can end in a short batch (n from 1 to batch): an engine of batch 4 fed n = 1 and n = 3 samples, against
+    the fp64 oracle under the HIP pass's masks -- loss, per-tensor gradients (the 64 x 64 bounds), the moving statistics of
+    every BatchNorm, the step, and the phase-0 loss after it.  At n = 1 each noise-head BatchNorm normalises one row:
+    its output is beta whatever its input, so no gradient passes into the noise MLP below it."""
+    import test_gpu_masked as TM
+    from oracle import depgan_oracle as O
+    img, B, ds = 64, 4, 77
+    P = _mg().uresnet_params(5)
+    x, z, lab = O.synth_uresnet_batch(8 + n, n, img, img)
+    eng = _engine(img, B, P)
+    loss = eng.uresnet(x, z, lab, "grads", drop_seed=ds)
+    G = eng.get_grads("G")
+    masks = TM.hip_uresnet_masks(eng, n)
+    loss64, g64, stats = O.uresnet_grads(P, x, z, lab, drop_seed=ds, dtype=torch.float64, masks=masks)
+    _, g32, _ = O.uresnet_grads(P, x, z, lab, drop_seed=ds, dtype=torch.float32, masks=masks)
+    assert abs(loss - loss64) < 1e-5 * max(1.0, abs(loss64)), (loss, loss64)
+    errs, errs32 = TM.tensor_errors(G, g64), TM.tensor_errors(g32, g64)
+    worst = max(errs, key=errs.get)
+    print("short batch n = %d: worst tensor %s %.2e (CPU fp32 %.2e there, %.2e at its worst)"
+          % (n, worst, errs[worst], errs32[worst], max(errs32.values())))
+    cap = max(1e-4, 4.0 * max(errs32.values()))
+    for k in errs:
+        assert errs[k] < cap, (k, errs[k], errs32[k])
+    assert sum(e > 1e-4 for e in errs.values()) <= 8, sorted(errs.items(), key=lambda kv: -kv[1])[:10]
+    if n == 1:
+        below = [k for k in G if k.startswith(("dense_noise_", "dense_bn_noise_1_"))]
+        assert len(below) == 8 + 2 * 14
+        for k in below:
+            assert np.all(G[k] == 0.0), (k, float(np.abs(G[k]).max()))
+    W = eng.get_weights("G")
+    for name, (mean, var, cnt, fused) in stats.items():
+        corr = cnt / (cnt - 1.0) if fused else cnt / (cnt - (1.0 + O.BN_EPS))
+        np.testing.assert_allclose(W[name + "/moving_mean"], P[name + "/moving_mean"] * 0.99 + mean.numpy() * 0.01,
+                                   rtol=1e-4, atol=1e-6, err_msg=name)
+        np.testing.assert_allclose(W[name + "/moving_variance"],
+                                   P[name + "/moving_variance"] * 0.99 + var.numpy() * corr * 0.01,
+                                   rtol=1e-4, atol=1e-6, err_msg=name)
+    # the step: Adam and the moving statistics, against the fp64 oracle's train_on_batch under the step's masks
+    eng.set_weights("G", P)
+    got = eng.uresnet(x, z, lab, "step", drop_seed=ds)
+    tr = O.OracleUResNet({k: v.copy() for k, v in P.items()}, dtype=torch.float64)
+    want = tr.train_on_batch([x, z], lab, drop_seed=ds, masks=TM.hip_uresnet_masks(eng, n))
+    assert abs(got - want) < 1e-5 * max(1.0, abs(want)), (got, want)
+    W = eng.get_weights("G")
+    for k in P:
+        if "moving_" in k:
+            np.testing.assert_allclose(W[k], tr.P[k], rtol=1e-4, atol=1e-6, err_msg=k)
+    # phase 0 after the step, on the weights the engine holds
+    ev = eng.uresnet(x, z, lab, "eval")
+    p0 = torch.from_numpy(O.uresnet_predict(W, x, z, dtype=torch.float64))
+    want0 = float(O.keras_categorical_crossentropy_t(p0, torch.from_numpy(lab).double()))
+    assert abs(ev - want0) < 1e-4 * max(1.0, abs(want0)), (ev, want0)
+    eng.close()
+
+
 def test_dropout_mask_is_the_oracles(lib):
     """drop_seed selects the same keep mask as oracle.dropout_keep_mask: with dropout on, the loss moves exactly
     as the oracle's does, and seed 0 means no dropout."""

@@ -152,3 +152,16 @@ def test_library_carries_the_hash_of_the_sources_it_was_built_from(lib, tmp_path
     monkeypatch.setattr(build, "source_hash", real)
     monkeypatch.setattr(_lib, "_lib", None)
     assert _lib.load() is not None
+
+
+def test_every_moments_and_colsum_call_passes_its_scratch_capacity():
+    """dg_col_moments / dg_colsum_pair write nb x 3 x C / nb x 2 x C floats into their scratch and refuse a smaller one:
+    every call in the model passes the capacity of the buffer it passes (the context's scratch and scratchFloats)."""
+    src = open(os.path.join(ROOT, "dep_gan_im_amd", "csrc", "uresnet.hip")).read()
+    calls = re.findall(r"\b(dg_col_moments|dg_colsum_pair)\s*\(([^;]*)\);", src)
+    assert len(calls) >= 2 and {c[0] for c in calls} == {"dg_col_moments", "dg_colsum_pair"}
+    for name, args in calls:
+        args = [a.strip() for a in args.replace("\n", " ").split(",")]
+        assert args[-3:-1] == ["c->scratch", "c->scratchFloats"], (name, args)
+    model = open(os.path.join(ROOT, "dep_gan_im_amd", "csrc", "model.hip")).read()
+    assert re.search(r"dmalloc\(c, &c->scratch, c->scratchFloats\)", model)
