@@ -24,6 +24,11 @@ EXPORTS = [
     "depgan_rccl_broadcast", "depgan_rccl_info", "depgan_rccl_shutdown", "depgan_op_conv2d_wgrad_bf16",
     "depgan_op_bn_moments", "depgan_op_bn_backward", "depgan_op_affine_act", "depgan_op_softmax_ce4",
     "depgan_op_bn_rows_fwd", "depgan_op_bn_rows_bwd", "depgan_op_small_gemm",
+    "depgan_op_unpool_mask", "depgan_op_gather_pool", "depgan_op_head", "depgan_op_critic_tail_fwd",
+    "depgan_op_critic_tail_bwd", "depgan_op_critic_tail_wgrad", "depgan_op_colsum", "depgan_op_sum",
+    "depgan_op_critic_inputs", "depgan_op_gp_u0", "depgan_op_critic_stats", "depgan_op_gloss_sums", "depgan_op_g_dpre",
+    "depgan_op_film_bwd", "depgan_op_bn_prepare_batch", "depgan_op_bn_gamma_grad_batch", "depgan_op_noise_fwd",
+    "depgan_op_noise_bwd", "depgan_op_best_noise", "depgan_op_round_bf16_masked",
 ]
 
 ABI_VERSION = 3          # DEPGAN_ABI_VERSION of the include/depgan.h this binding was written against
@@ -142,6 +147,27 @@ def load():
     lib.depgan_op_bn_rows_fwd.argtypes = [vp, vp] + [C.c_int] * 3 + [vp, vp] + [f] * 3 + [vp] * 4 + [C.c_int, vp]
     lib.depgan_op_bn_rows_bwd.argtypes = [vp] * 4 + [C.c_int] * 3 + [vp] * 5 + [vp]
     lib.depgan_op_small_gemm.argtypes = [C.c_int] + [vp] * 4 + [C.c_int] * 3 + [vp]
+    i = C.c_int
+    lib.depgan_op_unpool_mask.argtypes = [vp, L, L, L] * 4 + [i] * 4 + [vp]
+    lib.depgan_op_gather_pool.argtypes = [vp, L, L, L] * 3 + [i] * 4 + [vp]
+    lib.depgan_op_head.argtypes = [i] + [vp] * 5 + [L, i, i, vp]
+    lib.depgan_op_critic_tail_fwd.argtypes = [vp] * 7 + [i] * 3 + [vp]
+    lib.depgan_op_critic_tail_bwd.argtypes = [vp] * 4 + [i, vp] + [i] * 3 + [vp]
+    lib.depgan_op_critic_tail_wgrad.argtypes = [vp] * 5 + [i] * 3 + [vp] * 4 + [i] * 3 + [L, vp]
+    lib.depgan_op_colsum.argtypes = [vp, L, L, L] + [i] * 4 + [vp] * 3 + [i, vp, L, vp]
+    lib.depgan_op_sum.argtypes = [vp, L, vp, L, vp]
+    lib.depgan_op_critic_inputs.argtypes = [vp, vp, i] + [vp] * 3 + [i, L, i, vp]
+    lib.depgan_op_gp_u0.argtypes = [vp] * 4 + [f, i, L, L, vp]
+    lib.depgan_op_critic_stats.argtypes = [vp] * 3 + [i, vp]
+    lib.depgan_op_gloss_sums.argtypes = [vp, i, vp, vp, f, vp, L, L, vp]
+    lib.depgan_op_g_dpre.argtypes = [vp, i] + [vp] * 5 + [i, L, vp]
+    lib.depgan_op_film_bwd.argtypes = [vp] * 4 + [i] + [vp] * 3 + [i, L, i, L, vp]
+    lib.depgan_op_bn_prepare_batch.argtypes = [vp, vp, i, f, vp]
+    lib.depgan_op_bn_gamma_grad_batch.argtypes = [vp, vp, i, vp]
+    lib.depgan_op_noise_fwd.argtypes = [vp] * 6 + [i, vp]
+    lib.depgan_op_noise_bwd.argtypes = [vp] * 10 + [i, L, vp]
+    lib.depgan_op_best_noise.argtypes = [vp, i, vp, L, vp, vp, vp]
+    lib.depgan_op_round_bf16_masked.argtypes = [vp] * 3 + [L, vp]
     lib.depgan_uresnet_grads.argtypes = [vp, vp, vp, vp, C.c_int, C.c_uint, fp]
     lib.depgan_uresnet_step.argtypes = [vp, vp, vp, vp, C.c_int, C.c_uint, fp]
     lib.depgan_uresnet_eval.argtypes = [vp, vp, vp, vp, C.c_int, fp]

@@ -196,7 +196,8 @@ int deconv_wgrad_all(depgan_ctx* c, const GLayer& L, TView dsrc, int n, const fl
   }
   {
     ProfScope ps(c, 2, 0.0, "colsum");
-    DGCHECK(dg_colsum(dsrc, n, 2 * L.H, 2 * L.W, L.Cout, colscale, colout, colraw, 0, c->scratch, c->st));
+    DGCHECK(dg_colsum(dsrc, n, 2 * L.H, 2 * L.W, L.Cout, colscale, colout, colraw, 0, c->scratch, c->scratchFloats,
+                      c->st));
   }
   for (int t = 0; t < 4; ++t) {
     const size_t o = (size_t)t * L.Cout * L.Cin;
@@ -295,7 +296,8 @@ int wgrad_full(depgan_ctx* c, int KS, TView x, TView dy, int N, int H, int W, in
   // the separate streaming pass.
   if (cs && !mfma) {
     ProfScope ps(c, 2, 0.0, "colsum");
-    DGCHECK(dg_colsum(dy, cs->B, H, W, Cout, cs->scale, cs->out, cs->raw, 0, c->scratch, c->st));
+    DGCHECK(dg_colsum(dy, cs->B, H, W, Cout, cs->scale, cs->out, cs->raw, 0, c->scratch, c->scratchFloats,
+                      c->st));
   }
   if (mfma) {
     if (dg_wgrad_part_floats(KS, N, H, W, Cin, Cout) > c->partFloats) {
@@ -880,8 +882,8 @@ int g_backward(depgan_ctx* c, const float* x, const float* z, int n) {
       ProfScope ps(c, 2, 0.0, "head bwd");
       const long P = (long)n * L.H * L.W;
       // dW[c] = sum_p dpre[p] a[p][c] ; db = sum dpre
-      DGCHECK(dg_colsum_rowmul(L.in, n, L.H, L.W, L.Cin, c->dpre, L.dW, c->scratch, c->st));
-      DGCHECK(dg_sum(c->dpre, (size_t)P, L.db, c->scratch, c->st));
+      DGCHECK(dg_colsum_rowmul(L.in, n, L.H, L.W, L.Cin, c->dpre, L.dW, c->scratch, c->scratchFloats, c->st));
+      DGCHECK(dg_sum(c->dpre, (size_t)P, L.db, c->scratch, c->scratchFloats, c->st));
       DGCHECK(dg_head_bwd(c->dpre, L.Wt, L.in.p, L.din.p, P, L.Cin, c->st));
     } else if (L.kind == G_CONV) {
       DGCHECK(g_conv_bn_bwd(c, L, (size_t)i, x, L.dout, null_view(), n));
@@ -891,7 +893,7 @@ int g_backward(depgan_ctx* c, const float* x, const float* z, int n) {
         ProfScope ps(c, 2, 0.0, "film bwd");
         DGCHECK(dg_film_bwd(L.dout.p, L.u.p, c->na.heads + L.col_mul, c->na.heads + L.col_add, 1024, du.p,
                             c->dheads + L.col_mul, c->dheads + L.col_add, n, (long)L.H * L.W, L.Cout, c->scratch,
-                            c->st));
+                            c->scratchFloats, c->st));
       }
       DGCHECK(g_conv_bn_bwd(c, L, (size_t)i, x, du, L.dout, n));
     } else if (L.kind == G_POOL) {
@@ -924,7 +926,7 @@ int g_backward(depgan_ctx* c, const float* x, const float* z, int n) {
     DGCHECK(dg_bn_gamma_grad_batch(c->g_gamma_jobs, c->g_n_gamma, c->g_gamma_blocks, c->st));
   }
   ProfScope ps(c, 2, 0.0, "noise mlp bwd");
-  return dg_noise_bwd(c->np, c->ng, z, c->na, c->dheads, c->scratch, n, c->st);
+  return dg_noise_bwd(c->np, c->ng, z, c->na, c->dheads, c->scratch, c->scratchFloats, n, c->st);
 }
 
 // ---------------------------------------------------------------------------
@@ -1058,7 +1060,7 @@ static int critic_enqueue(depgan_ctx* c, int which, const float* y2, const float
   float* u0 = c->d_in + 2 * B * HW0;
   {
     ProfScope ps(c, 2, 0.0, "gp norms+u0");
-    DGCHECK(dg_gp_u0(c->g0, u0, c->norms, nullptr, c->cfg.delta, B, HW0, c->scratch, c->st));
+    DGCHECK(dg_gp_u0(c->g0, u0, c->norms, nullptr, c->cfg.delta, B, HW0, c->scratch, c->scratchFloats, c->st));
   }
   // u-forward through the masks of the mixed pass, overwriting the mixed slots
   for (int l = 0; l < 11; ++l) {
@@ -1101,9 +1103,10 @@ static int critic_enqueue(depgan_ctx* c, int which, const float* y2, const float
     const DLayer& T = c->dl[10];
     const int HW = T.H * T.W;
     DGCHECK(dg_critic_tail_wgrad(c->d_act[10].p, D.w9, D.b9, D.wd, c->coefs, B, 1, 0, D.dw9, D.db9, D.dwd, D.dbd,
-                                 c->scratch, 2 * B, HW, 256, c->st));
+                                 c->scratch, c->scratchFloats, 2 * B, HW, 256, c->st));
     DGCHECK(dg_critic_tail_wgrad(c->d_act[10].p + (size_t)2 * B * c->d_act[10].per_sample(), D.w9, D.b9, D.wd,
-                                 c->coefs + 2, B, 0, 1, D.dw9, D.db9, D.dwd, D.dbd, c->scratch, B, HW, 256, c->st));
+                                 c->coefs + 2, B, 0, 1, D.dw9, D.db9, D.dwd, D.dbd, c->scratch, c->scratchFloats, B, HW, 256,
+                                 c->st));
     DGCHECK(dg_critic_stats(c->d_out, c->norms, D.net.G + D.net.nTrain, B, c->st));
   }
   return DG_OK;
@@ -1126,7 +1129,8 @@ static int g_eval_enqueue(depgan_ctx* c, const float* x, const float* y2, const 
   {
     ProfScope ps(c, 2, 0.0, "g loss sums");
     DGCHECK(dg_sum_groups_consts(c->d_out, stats_dev, 2, B, 6, (float)B, (float)P, c->st));
-    DGCHECK(dg_gloss_sums(x, c->cfg.nicg, y2, c->attr.p, c->cfg.im_thresh, stats_dev + 2, P, c->scratch, c->st));
+    DGCHECK(dg_gloss_sums(x, c->cfg.nicg, y2, c->attr.p, c->cfg.im_thresh, stats_dev + 2, P, c->scratch,
+                                  c->scratchFloats, c->st));
   }
   if (train) {
     // d loss / d attr needs dD/dimage of both critics with upstream 1 per sample (GT:592)
@@ -2149,6 +2153,277 @@ int depgan_op_small_gemm(int form, const float* A, const float* Bm, const float*
   if (form == 2) return dg_small_gemm_bt(A, Bm, Cm, M, K, N, st);
   dg_set_error("op_small_gemm: form %d is not 0, 1 or 2", form);
   return DG_ERR_ARG;
+}
+
+
+// ---- the two-critic step's HBM-bound operators (ops.hip) and the noise MLP (noise.hip), each the dg_* function the
+// model calls; views as above, scratch_floats <= 0 for what the launch needs ----
+static TView op_view_or_null(const float* p, long sB, long sY, long sX) {
+  return p ? op_view(p, sB, sY, sX) : null_view();
+}
+extern "C++" {
+// allocate a reduction scratch of op_scratch(scratch_floats, need) floats, run the call, synchronise, free
+template <typename F>
+static int op_with_scratch(long scratch_floats, size_t need, const char* who, hipStream_t st, F&& call) {
+  const size_t cap = op_scratch(scratch_floats, need);
+  float* scratch = nullptr;
+  DGCHECK(op_alloc(&scratch, cap, who));
+  const int rc = call(scratch, cap);
+  hipStreamSynchronize(st);
+  hipFree(scratch);
+  return rc;
+}
+// a job table on the device, as the model's upload_table makes it
+template <typename T>
+static int op_upload_jobs(const std::vector<T>& jobs, T** dev, const char* who) {
+  *dev = nullptr;
+  if (hipMalloc((void**)dev, jobs.size() * sizeof(T)) != hipSuccess) { dg_set_error("%s: out of device memory", who); return DG_ERR_HIP; }
+  if (hipMemcpy(*dev, jobs.data(), jobs.size() * sizeof(T), hipMemcpyHostToDevice) != hipSuccess) {
+    dg_set_error("%s: job table upload failed", who);
+    return DG_ERR_HIP;
+  }
+  return DG_OK;
+}
+}  // extern "C++"
+
+int depgan_op_unpool_mask(const float* dpool, long dsB, long dsY, long dsX, const float* a, long asB, long asY, long asX,
+                          const float* skip, long ssB, long ssY, long ssX, float* out, long osB, long osY, long osX,
+                          int B, int Ho, int Wo, int C, void* stream) {
+  if (!dpool || !a || !out || B < 1 || Ho < 1 || Wo < 1 || C < 1) { dg_set_error("op_unpool_mask: bad argument"); return DG_ERR_ARG; }
+  return dg_unpool_mask(op_view(dpool, dsB, dsY, dsX), op_view(a, asB, asY, asX), op_view_or_null(skip, ssB, ssY, ssX),
+                        op_view(out, osB, osY, osX), B, Ho, Wo, C, (hipStream_t)stream);
+}
+int depgan_op_gather_pool(const float* u, long usB, long usY, long usX, const float* a, long asB, long asY, long asX,
+                          float* out, long osB, long osY, long osX, int B, int Ho, int Wo, int C, void* stream) {
+  if (!u || !a || !out || B < 1 || Ho < 1 || Wo < 1 || C < 1) { dg_set_error("op_gather_pool: bad argument"); return DG_ERR_ARG; }
+  return dg_gather_pool(op_view(u, usB, usY, usX), op_view(a, asB, asY, asX), op_view(out, osB, osY, osX), B, Ho, Wo, C,
+                        (hipStream_t)stream);
+}
+
+int depgan_op_head(int backward, const float* a, const float* w, const float* b, const float* dpre, float* out, long P,
+                   int C, int tanh_act, void* stream) {
+  if (!a || !w || !out || P < 1 || C < 1 || (backward ? !dpre : !b)) { dg_set_error("op_head: bad argument"); return DG_ERR_ARG; }
+  if (backward) return dg_head_bwd(dpre, w, a, out, P, C, (hipStream_t)stream);
+  return dg_head_fwd(a, w, b, out, P, C, tanh_act, (hipStream_t)stream);
+}
+
+int depgan_op_critic_tail_fwd(const float* a, const float* w9, const float* b9, const float* wd, const float* bd,
+                              float* t9, float* out, int N, int HW, int C, void* stream) {
+  if (!a || !w9 || !b9 || !wd || !bd || !t9 || !out || N < 1 || HW < 1 || C < 1) {
+    dg_set_error("op_critic_tail_fwd: bad argument");
+    return DG_ERR_ARG;
+  }
+  return dg_critic_tail_fwd(a, w9, b9, wd, bd, t9, out, N, HW, C, (hipStream_t)stream);
+}
+int depgan_op_critic_tail_bwd(const float* a, const float* w9, const float* wd, const float* coefs, int per, float* dz,
+                              int N, int HW, int C, void* stream) {
+  if (!a || !w9 || !wd || !coefs || !dz || per < 1 || N < 1 || HW < 1 || C < 4 || (C % 4)) {
+    dg_set_error("op_critic_tail_bwd: bad argument");
+    return DG_ERR_ARG;
+  }
+  return dg_critic_tail_bwd(a, w9, wd, coefs, per, dz, N, HW, C, (hipStream_t)stream);
+}
+int depgan_op_critic_tail_wgrad(const float* src, const float* w9, const float* b9, const float* wd, const float* coefs,
+                                int per, int add_bias_terms, int accumulate, float* dw9, float* db9, float* dwd,
+                                float* dbd, int N, int HW, int C, long scratch_floats, void* stream) {
+  if (!src || !w9 || !wd || !coefs || !dw9 || !dwd || per < 1 || N < 1 || HW < 1 || C < 1 ||
+      (add_bias_terms && (!b9 || !db9 || !dbd))) {
+    dg_set_error("op_critic_tail_wgrad: bad argument");
+    return DG_ERR_ARG;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  return op_with_scratch(scratch_floats, dg_critic_tail_wgrad_scratch(N, HW, C), "op_critic_tail_wgrad", st,
+                         [&](float* scratch, size_t cap) {
+                           return dg_critic_tail_wgrad(src, w9, b9, wd, coefs, per, add_bias_terms, accumulate, dw9,
+                                                       db9, dwd, dbd, scratch, cap, N, HW, C, st);
+                         });
+}
+
+int depgan_op_colsum(const float* v, long sB, long sY, long sX, int B, int H, int W, int C, const float* scale,
+                     float* out, float* raw, int accumulate, const float* rowmul, long scratch_floats, void* stream) {
+  if (!v || B < 1 || H < 1 || W < 1 || C < 1 || (!out && !raw) || (rowmul && (!out || scale || raw || accumulate))) {
+    dg_set_error("op_colsum: bad argument");
+    return DG_ERR_ARG;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  const TView vv = op_view(v, sB, sY, sX);
+  return op_with_scratch(scratch_floats, dg_colsum_scratch(B, H, W, C), "op_colsum", st, [&](float* scratch, size_t cap) {
+    if (rowmul) return dg_colsum_rowmul(vv, B, H, W, C, rowmul, out, scratch, cap, st);
+    return dg_colsum(vv, B, H, W, C, scale, out, raw, accumulate, scratch, cap, st);
+  });
+}
+int depgan_op_sum(const float* in, long n, float* out, long scratch_floats, void* stream) {
+  if (!in || !out || n < 1) { dg_set_error("op_sum: bad argument"); return DG_ERR_ARG; }
+  hipStream_t st = (hipStream_t)stream;
+  return op_with_scratch(scratch_floats, dg_sum_scratch((size_t)n), "op_sum", st, [&](float* scratch, size_t cap) {
+    return dg_sum(in, (size_t)n, out, scratch, cap, st);
+  });
+}
+
+int depgan_op_critic_inputs(const float* y2, const float* x, int nicg, const float* attr, const float* ep, float* out,
+                            int B, long HW, int which, void* stream) {
+  if (!x || !attr || !out || nicg < 1 || B < 1 || HW < 1 || which < 0 || which > 2 || (which < 2 && (!y2 || !ep))) {
+    dg_set_error("op_critic_inputs: bad argument");
+    return DG_ERR_ARG;
+  }
+  if (which == 2) return dg_add_ch0(x, nicg, attr, out, (long)B * HW, (hipStream_t)stream);
+  return dg_critic_inputs(y2, x, nicg, attr, ep, out, B, HW, which, (hipStream_t)stream);
+}
+
+int depgan_op_gp_u0(const float* g0, float* u0, float* norms, float* gp_out, float delta, int B, long HW,
+                    long scratch_floats, void* stream) {
+  if (!g0 || !u0 || !norms || B < 1 || HW < 1) { dg_set_error("op_gp_u0: bad argument"); return DG_ERR_ARG; }
+  hipStream_t st = (hipStream_t)stream;
+  return op_with_scratch(scratch_floats, dg_gp_u0_scratch(B), "op_gp_u0", st, [&](float* scratch, size_t cap) {
+    return dg_gp_u0(g0, u0, norms, gp_out, delta, B, HW, scratch, cap, st);
+  });
+}
+int depgan_op_critic_stats(const float* d_out, const float* norms, float* out, int B, void* stream) {
+  if (!d_out || !norms || !out || B < 1) { dg_set_error("op_critic_stats: bad argument"); return DG_ERR_ARG; }
+  return dg_critic_stats(d_out, norms, out, B, (hipStream_t)stream);
+}
+
+int depgan_op_gloss_sums(const float* x, int nicg, const float* y2, const float* attr, float thr, float* sums, long P,
+                         long scratch_floats, void* stream) {
+  if (!x || !y2 || !attr || !sums || nicg < 1 || P < 1) { dg_set_error("op_gloss_sums: bad argument"); return DG_ERR_ARG; }
+  hipStream_t st = (hipStream_t)stream;
+  return op_with_scratch(scratch_floats, dg_gloss_sums_scratch(P), "op_gloss_sums", st, [&](float* scratch, size_t cap) {
+    return dg_gloss_sums(x, nicg, y2, attr, thr, sums, P, scratch, cap, st);
+  });
+}
+int depgan_op_g_dpre(const float* x, int nicg, const float* y2, const float* attr, const float* g1, const float* g2,
+                     float* dpre, int B, long P, void* stream) {
+  if (!x || !y2 || !attr || !g1 || !g2 || !dpre || nicg < 1 || B < 1 || P < 1) {
+    dg_set_error("op_g_dpre: bad argument");
+    return DG_ERR_ARG;
+  }
+  return dg_g_dpre(x, nicg, y2, attr, g1, g2, dpre, B, P, (hipStream_t)stream);
+}
+
+int depgan_op_film_bwd(const float* dr, const float* u, const float* fmul, const float* fadd, int film_ld, float* du,
+                       float* dmul, float* dadd, int B, long HW, int C, long scratch_floats, void* stream) {
+  if (!dr || !u || !fmul || !fadd || !du || !dmul || !dadd || film_ld < C || B < 1 || HW < 1 || C < 1) {
+    dg_set_error("op_film_bwd: bad argument");
+    return DG_ERR_ARG;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  return op_with_scratch(scratch_floats, dg_film_bwd_scratch(B, C), "op_film_bwd", st, [&](float* scratch, size_t cap) {
+    return dg_film_bwd(dr, u, fmul, fadd, film_ld, du, dmul, dadd, B, HW, C, scratch, cap, st);
+  });
+}
+
+int depgan_op_bn_prepare_batch(void* const* ptrs, const int* C, int njobs, float eps, void* stream) {
+  if (!ptrs || !C || njobs < 1) { dg_set_error("op_bn_prepare_batch: bad argument"); return DG_ERR_ARG; }
+  std::vector<BnJob> jobs(njobs);
+  for (int j = 0; j < njobs; ++j) {
+    void* const* q = ptrs + 8 * j;
+    for (int k = 0; k < 7; ++k)   // q[7], mean_copy, is optional
+      if (!q[k] || C[j] < 1) { dg_set_error("op_bn_prepare_batch: job %d: bad argument", j); return DG_ERR_ARG; }
+    jobs[j] = {(const float*)q[0], (const float*)q[1], (const float*)q[2], (const float*)q[3], (float*)q[4],
+               (float*)q[5], (float*)q[6], (float*)q[7], C[j]};
+  }
+  hipStream_t st = (hipStream_t)stream;
+  BnJob* dev = nullptr;
+  int rc = op_upload_jobs(jobs, &dev, "op_bn_prepare_batch");
+  if (rc == DG_OK) rc = dg_bn_prepare_batch(dev, njobs, eps, st);
+  hipStreamSynchronize(st);
+  hipFree(dev);
+  return rc;
+}
+
+int depgan_op_bn_gamma_grad_batch(void* const* ptrs, const int* dims, int njobs, void* stream) {
+  if (!ptrs || !dims || njobs < 1) { dg_set_error("op_bn_gamma_grad_batch: bad argument"); return DG_ERR_ARG; }
+  std::vector<GammaJob> jobs(njobs);
+  int nblocks = 0;
+  for (int j = 0; j < njobs; ++j) {
+    void* const* q = ptrs + 7 * j;
+    const int* d = dims + 4 * j;   // K, Cout, oi, Cin
+    for (int k = 0; k < 7; ++k)
+      if (!q[k]) { dg_set_error("op_bn_gamma_grad_batch: job %d: null pointer", j); return DG_ERR_ARG; }
+    if (d[0] < 1 || d[1] < 1 || (d[2] != 0 && d[2] != 1) || (d[2] && (d[3] < 1 || d[0] % d[3]))) {
+      dg_set_error("op_bn_gamma_grad_batch: job %d: bad shape", j);
+      return DG_ERR_ARG;
+    }
+    jobs[j] = {(const float*)q[0], (const float*)q[1], (const float*)q[2], (const float*)q[3], (const float*)q[4],
+               (const float*)q[5], (float*)q[6], d[0], d[1], d[2], d[3], nblocks};
+    nblocks += d[1];   // one block per output channel, jobs back to back (the model's g_gamma_jobs)
+  }
+  hipStream_t st = (hipStream_t)stream;
+  GammaJob* dev = nullptr;
+  int rc = op_upload_jobs(jobs, &dev, "op_bn_gamma_grad_batch");
+  if (rc == DG_OK) rc = dg_bn_gamma_grad_batch(dev, njobs, nblocks, st);
+  hipStreamSynchronize(st);
+  hipFree(dev);
+  return rc;
+}
+
+// NoiseParams / NoiseGrads over packed buffers (include/depgan.h)
+static int op_noise_params(const float* trunk, const float* Wh, const float* hvec, const int* ncol, NoiseParams* P) {
+  if (!trunk || !Wh || !hvec || !ncol) { dg_set_error("op_noise: bad argument"); return DG_ERR_ARG; }
+  P->W0 = trunk; P->b0 = trunk + 32; P->s0 = trunk + 64; P->t0 = trunk + 96; P->mean0 = trunk + 128;
+  P->rstd0 = trunk + 160;
+  P->W1 = trunk + 192; P->b1 = trunk + 1216; P->s1 = trunk + 1248; P->t1 = trunk + 1280; P->mean1 = trunk + 1312;
+  P->rstd1 = trunk + 1344;
+  int col = 0;
+  size_t woff = 0;
+  for (int h = 0; h < NOISE_NHEADS; ++h) {
+    if (ncol[h] < 1) { dg_set_error("op_noise: head %d has %d columns", h, ncol[h]); return DG_ERR_ARG; }
+    P->Wh[h] = Wh + woff;
+    P->bh[h] = hvec + col;
+    P->col0[h] = col;
+    P->ncol[h] = ncol[h];
+    woff += (size_t)1024 * ncol[h];
+    col += ncol[h];
+  }
+  if (col != 1024) { dg_set_error("op_noise: head widths sum to %d, not 1024", col); return DG_ERR_ARG; }
+  P->sh = hvec + 1024; P->th = hvec + 2048; P->meanh = hvec + 3072; P->rstdh = hvec + 4096;
+  return DG_OK;
+}
+static NoiseActs op_noise_acts(float* acts, int B) {
+  const size_t n = (size_t)B * 1024;
+  NoiseActs A;
+  A.h0 = acts; A.a0 = acts + n; A.h1 = acts + 2 * n; A.a1 = acts + 3 * n; A.lin = acts + 4 * n; A.heads = acts + 5 * n;
+  return A;
+}
+
+int depgan_op_noise_fwd(const float* trunk, const float* Wh, const float* hvec, const int* ncol, const float* z,
+                        float* acts, int B, void* stream) {
+  NoiseParams P;
+  DGCHECK(op_noise_params(trunk, Wh, hvec, ncol, &P));
+  if (!z || !acts || B < 1) { dg_set_error("op_noise_fwd: bad argument"); return DG_ERR_ARG; }
+  return dg_noise_fwd(P, z, op_noise_acts(acts, B), B, (hipStream_t)stream);
+}
+int depgan_op_noise_bwd(const float* trunk, const float* Wh, const float* hvec, const int* ncol, const float* z,
+                        float* acts, const float* dheads, float* gtrunk, float* dWh, float* ghvec, int B,
+                        long scratch_floats, void* stream) {
+  NoiseParams P;
+  DGCHECK(op_noise_params(trunk, Wh, hvec, ncol, &P));
+  if (!z || !acts || !dheads || !gtrunk || !dWh || !ghvec || B < 1) { dg_set_error("op_noise_bwd: bad argument"); return DG_ERR_ARG; }
+  NoiseGrads G;
+  G.dW0 = gtrunk; G.db0 = gtrunk + 32; G.dgamma0 = gtrunk + 64; G.dbeta0 = gtrunk + 96;
+  G.dW1 = gtrunk + 128; G.db1 = gtrunk + 1152; G.dgamma1 = gtrunk + 1184; G.dbeta1 = gtrunk + 1216;
+  for (int h = 0; h < NOISE_NHEADS; ++h) {
+    G.dWh[h] = dWh + ((size_t)(P.Wh[h] - Wh));
+    G.dbh[h] = ghvec + P.col0[h];
+    G.dgamma_h[h] = ghvec + 1024 + P.col0[h];
+    G.dbeta_h[h] = ghvec + 2048 + P.col0[h];
+  }
+  hipStream_t st = (hipStream_t)stream;
+  const NoiseActs A = op_noise_acts(acts, B);
+  return op_with_scratch(scratch_floats, dg_noise_bwd_scratch(B), "op_noise_bwd", st, [&](float* scratch, size_t cap) {
+    return dg_noise_bwd(P, G, z, A, dheads, scratch, cap, B, st);
+  });
+}
+
+int depgan_op_best_noise(const float* stats, int k, const float* z_all, long zfloats, int* best, float* z_out,
+                         void* stream) {
+  if (!stats || !z_all || !best || !z_out || k < 1 || zfloats < 1) { dg_set_error("op_best_noise: bad argument"); return DG_ERR_ARG; }
+  return dg_best_noise(stats, k, z_all, zfloats, best, z_out, (hipStream_t)stream);
+}
+
+int depgan_op_round_bf16_masked(const float* src, const unsigned char* mask, float* dst, long n, void* stream) {
+  if (!src || !mask || !dst || n < 1) { dg_set_error("op_round_bf16_masked: bad argument"); return DG_ERR_ARG; }
+  return dg_round_bf16_masked(src, mask, dst, (size_t)n, (hipStream_t)stream);
 }
 
 }  // extern "C"

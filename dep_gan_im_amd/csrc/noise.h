@@ -28,9 +28,10 @@ struct NoiseGrads {
 };
 
 int dg_noise_fwd(const NoiseParams& P, const float* z, NoiseActs A, int B, hipStream_t st);
-// scratch: 4*B*1024 floats
+// scratch: dg_noise_bwd_scratch(B) = 4*B*1024 floats; DG_ERR_ARG when scratch_floats is less
 int dg_noise_bwd(const NoiseParams& P, const NoiseGrads& G, const float* z, NoiseActs A, const float* dheads,
-                 float* scratch, int B, hipStream_t st);
+                 float* scratch, size_t scratch_floats, int B, hipStream_t st);
+size_t dg_noise_bwd_scratch(int B);
 
 int dg_noise_heads_lin(const NoiseParams& P, const float* flat, float* lin, float* heads, int B, hipStream_t st);
 int dg_noise_heads_bwd_lin(const NoiseParams& P, const NoiseGrads& G, const float* flat, const float* dl, float* dflat,

@@ -233,8 +233,13 @@ __global__ __launch_bounds__(1024) void noise_trunk_bwd_kernel(NoiseParams P, No
   }
 }
 
+size_t dg_noise_bwd_scratch(int B) { return (size_t)4 * B * 1024; }
 int dg_noise_bwd(const NoiseParams& P, const NoiseGrads& G, const float* z, NoiseActs A, const float* dheads,
-                 float* scratch, int B, hipStream_t st) {
+                 float* scratch, size_t scratch_floats, int B, hipStream_t st) {
+  if (dg_noise_bwd_scratch(B) > scratch_floats) {
+    dg_set_error("dg_noise_bwd: scratch holds %zu floats, the launch needs %zu", scratch_floats, dg_noise_bwd_scratch(B));
+    return DG_ERR_ARG;
+  }
   float* dl = scratch;                         // [B][1024]
   float* dflat = scratch + (size_t)B * 1024;   // [B][1024]
   float* dl1 = scratch + (size_t)2 * B * 1024;

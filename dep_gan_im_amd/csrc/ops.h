@@ -34,13 +34,12 @@ int dg_critic_tail_bwd(const float* a, const float* w9, const float* wd, const f
 //   dw9[c] (+)= sum_{n,p} T wd[p] ; dwd[p] (+)= sum_{n,c} T w9[c] (+ b9 * sum coef if add_bias_terms)
 //   db9 (+)= sum_n coef(n) * sum_p wd[p] ; dbd (+)= sum_n coef(n)      (only if add_bias_terms)
 // accumulate = 0 overwrites the outputs, 1 adds to them
-// scratch: N*(C+HW) floats
+// scratch: dg_critic_tail_wgrad_scratch(N, HW, C) = N*(C+HW) floats; DG_ERR_ARG when scratch_floats is less
 int dg_critic_tail_wgrad(const float* src, const float* w9, const float* b9, const float* wd, const float* coefs,
                          int per, int add_bias_terms, int accumulate, float* dw9, float* db9, float* dwd, float* dbd,
-                         float* scratch, int N, int HW, int C, hipStream_t st);
+                         float* scratch, size_t scratch_floats, int N, int HW, int C, hipStream_t st);
+size_t dg_critic_tail_wgrad_scratch(int N, int HW, int C);
 
-// column sums of an NHWC view: out[c] (+)= scale[c] * sum_{b,y,x} v[b,y,x,c]; raw (optional) gets the bare sum.
-// scratch: 1024*C floats
 // one BatchNorm of a batched dg_bn_prepare_batch launch; mean_copy (optional) receives a copy of the moving mean
 struct BnJob {
   const float *gamma, *beta, *mean, *var;
@@ -56,14 +55,20 @@ struct GammaJob {
   int blk0;      // first block of this job in the batched grid
 };
 int dg_bn_gamma_grad_batch(const GammaJob* jobs_dev, int njobs, int nblocks, hipStream_t st);
-int dg_colsum(TView v, int B, int H, int W, int C, const float* scale, float* out, float* raw, int accumulate,
-              float* scratch, hipStream_t st);
 
-// out[c] = sum_{pixels q} rowmul[q] * v[q][c]   (q = dense (b,y,x) index)
+// column sums of an NHWC view: out[c] (+)= scale[c] * sum_{b,y,x} v[b,y,x,c]; raw (optional) gets the bare sum.
+// C % 4 == 0, C <= 256.  scratch: dg_colsum_scratch(B, H, W, C) floats (one row of C partials per block, at most
+// 2048 blocks); DG_ERR_ARG when scratch_floats is less
+int dg_colsum(TView v, int B, int H, int W, int C, const float* scale, float* out, float* raw, int accumulate,
+              float* scratch, size_t scratch_floats, hipStream_t st);
+size_t dg_colsum_scratch(int B, int H, int W, int C);
+
+// out[c] = sum_{pixels q} rowmul[q] * v[q][c]   (q = dense (b,y,x) index); scratch as dg_colsum
 int dg_colsum_rowmul(TView v, int B, int H, int W, int C, const float* rowmul, float* out, float* scratch,
-                     hipStream_t st);
-// out[0] = sum in[0..n)   scratch: 1024 floats
-int dg_sum(const float* in, size_t n, float* out, float* scratch, hipStream_t st);
+                     size_t scratch_floats, hipStream_t st);
+// out[0] = sum in[0..n)   scratch: dg_sum_scratch(n) floats (at most 1024)
+int dg_sum(const float* in, size_t n, float* out, float* scratch, size_t scratch_floats, hipStream_t st);
+size_t dg_sum_scratch(size_t n);
 
 // build the 3B critic input batch [real | fake | mixed] (GT:528-538, 555-557). which: 0 = Y2 critic, 1 = DEM critic
 int dg_critic_inputs(const float* y2, const float* x, int nicg, const float* attr, const float* ep, float* out, int B,
@@ -72,22 +77,26 @@ int dg_critic_inputs(const float* y2, const float* x, int nicg, const float* att
 int dg_add_ch0(const float* x, int nicg, const float* attr, float* out, long P, hipStream_t st);
 
 // gradient penalty (GT:544-545): per-sample norms of g0, GP value, and u0 = delta*(2/B)*(norm-1)/norm * g0
-// scratch: B*64 floats ; norms: B floats ; gp_out: 1 float
+// scratch: dg_gp_u0_scratch(B) = B*64 floats ; norms: B floats ; gp_out (optional): 1 float
 int dg_gp_u0(const float* g0, float* u0, float* norms, float* gp_out, float delta, int B, long HW, float* scratch,
-             hipStream_t st);
+             size_t scratch_floats, hipStream_t st);
+size_t dg_gp_u0_scratch(int B);
 
 // generator loss pieces (GT:576-589): sums[0]=sum|attr-(y2-y1)|, [1]=sum wr, [2]=sum wf, [3]=sum wr*wf
-// scratch: 1024*4 floats
+// scratch: dg_gloss_sums_scratch(P) floats (4 per block, at most 4*1024)
 int dg_gloss_sums(const float* x, int nicg, const float* y2, const float* attr, float thr, float* sums, long P,
-                  float* scratch, hipStream_t st);
+                  float* scratch, size_t scratch_floats, hipStream_t st);
+size_t dg_gloss_sums_scratch(long P);
 // dpre = ( -(g1+g2)/B + (100/P) sign(attr - (y2-y1)) ) * (1 - attr^2)      (GT:576, 592; tanh GT:495)
 int dg_g_dpre(const float* x, int nicg, const float* y2, const float* attr, const float* g1, const float* g2,
               float* dpre, int B, long P, hipStream_t st);
 
 // FiLM backward (GT:403-405): v = fmul*u + fadd; dv = dr*(v>0); du = dv*fmul;
-// dadd[b,c] = sum_hw dv ; dmul[b,c] = sum_hw dv*u.   scratch: B*64*2*C floats
+// dadd[b,c] = sum_hw dv ; dmul[b,c] = sum_hw dv*u.   C % 4 == 0, C <= 128
+// scratch: dg_film_bwd_scratch(B, C) = B*64*2*C floats
 int dg_film_bwd(const float* dr, const float* u, const float* fmul, const float* fadd, int film_ld, float* du,
-                float* dmul, float* dadd, int B, long HW, int C, float* scratch, hipStream_t st);
+                float* dmul, float* dadd, int B, long HW, int C, float* scratch, size_t scratch_floats, hipStream_t st);
+size_t dg_film_bwd_scratch(int B, int C);
 
 // BN gamma gradient from the raw weight gradient (see oracle/manual.py):
 //   dgamma[co] = rstd[co] * ( sum_k W[k,co]*dWraw[k,co] + (bias[co]-mean[co]) * S[co] )
@@ -108,8 +117,8 @@ int dg_critic_stats(const float* d_out, const float* norms, float* out, int B, h
 int dg_sum_groups_consts(const float* in, float* out, int groups, int per, int coff, float c0, float c1, hipStream_t st);
 // best-of-k noise search on the device (GT:868-877): stats = k x 8 un-normalised pieces
 // [sum D_y2(fake), sum D_dem(attr), sum|attr-real_dem|, sum wr, sum wf, sum wr*wf, n, n*H*W]; forms the k total losses
-// with the host's algebra (double, rounded to float), takes the FIRST minimum, writes its index to *best and copies
-// z_all[best] (zfloats values) to z_out
+// with the host's algebra (double, rounded to float), picks np.argmin's index (the first NaN if any total is NaN,
+// else the first minimum), writes it to *best and copies z_all[best] (zfloats values) to z_out
 int dg_best_noise(const float* stats, int k, const float* z_all, long zfloats, int* best, float* z_out, hipStream_t st);
 
 // dst[i] = mask[i] ? float(bf16_rne(src[i])) : src[i]      (bf16-weights mode: master -> compute copy)

@@ -24,6 +24,13 @@ static inline int nblk(size_t n, int cap = 2048) {
   return (int)(b > (size_t)cap ? cap : (b < 1 ? 1 : b));
 }
 
+// the reductions write their partials into a caller's scratch: refuse one smaller than the launch needs
+static int scratch_ok(const char* who, size_t need, size_t have) {
+  if (need <= have) return 1;
+  dg_set_error("%s: scratch holds %zu floats, the launch needs %zu", who, have, need);
+  return 0;
+}
+
 // ---------------------------------------------------------------------------
 // pooling
 // ---------------------------------------------------------------------------
@@ -388,8 +395,9 @@ __global__ __launch_bounds__(256) void critic_tail_wgrad_final(const float* __re
 }
 int dg_critic_tail_wgrad(const float* src, const float* w9, const float* b9, const float* wd, const float* coefs,
                          int per, int add_bias_terms, int accumulate, float* dw9, float* db9, float* dwd, float* dbd, float* scratch,
-                         int N, int HW, int C, hipStream_t st) {
+                         size_t scratch_floats, int N, int HW, int C, hipStream_t st) {
   if ((C % 4) || C > 256) { dg_set_error("dg_critic_tail_wgrad: C must be a multiple of 4 and <= 256"); return DG_ERR_ARG; }
+  if (!scratch_ok("dg_critic_tail_wgrad", dg_critic_tail_wgrad_scratch(N, HW, C), scratch_floats)) return DG_ERR_ARG;
   float* pw9 = scratch;
   float* pwd = scratch + (size_t)N * C;
   hipLaunchKernelGGL(critic_tail_wgrad_partial, dim3(N), dim3(1024), 0, st, src, w9, wd, pw9, pwd, HW, C);
@@ -399,6 +407,7 @@ int dg_critic_tail_wgrad(const float* src, const float* w9, const float* b9, con
   HIPCHECK(hipGetLastError());
   return DG_OK;
 }
+size_t dg_critic_tail_wgrad_scratch(int N, int HW, int C) { return (size_t)N * (C + HW); }
 
 // ---------------------------------------------------------------------------
 // column sums of an NHWC view
@@ -482,14 +491,27 @@ __global__ void colsum_final(const float* __restrict__ part, int nb, int C, cons
     }
   }
 }
-static int colsum_impl(TView v, int B, int H, int W, int C, const float* scale, float* out, float* raw, int accumulate,
-                       const float* rowmul, float* scratch, hipStream_t st) {
-  if ((C % 4) || C > 256) { dg_set_error("dg_colsum: C must be a multiple of 4 and <= 256"); return DG_ERR_ARG; }
-  const long npix = (long)B * H * W;
+// grid of colsum_partial: nb blocks of ppb pixels (at most 2048 blocks)
+static void colsum_grid(long npix, int* nb_out, int* ppb_out) {
   int nb = (int)((npix + 255) / 256);
   if (nb > 2048) nb = 2048;
+  if (nb < 1) nb = 1;
   const int ppb = (int)((npix + nb - 1) / nb);
-  nb = (int)((npix + ppb - 1) / ppb);
+  *nb_out = ppb > 0 ? (int)((npix + ppb - 1) / ppb) : 1;
+  *ppb_out = ppb;
+}
+size_t dg_colsum_scratch(int B, int H, int W, int C) {
+  int nb, ppb;
+  colsum_grid((long)B * H * W, &nb, &ppb);
+  return (size_t)nb * C;
+}
+static int colsum_impl(TView v, int B, int H, int W, int C, const float* scale, float* out, float* raw, int accumulate,
+                       const float* rowmul, float* scratch, size_t scratch_floats, hipStream_t st) {
+  if ((C % 4) || C > 256) { dg_set_error("dg_colsum: C must be a multiple of 4 and <= 256"); return DG_ERR_ARG; }
+  if (!scratch_ok("dg_colsum", dg_colsum_scratch(B, H, W, C), scratch_floats)) return DG_ERR_ARG;
+  const long npix = (long)B * H * W;
+  int nb, ppb;
+  colsum_grid(npix, &nb, &ppb);
   const bool flat = v.sY == (long)W * v.sX && v.sB == (long)H * v.sY;
   if (flat)
     hipLaunchKernelGGL(colsum_partial<true>, dim3(nb), dim3(256), 256 * 4 * sizeof(float), st, v, npix, H, W, C / 4,
@@ -504,12 +526,12 @@ static int colsum_impl(TView v, int B, int H, int W, int C, const float* scale, 
 }
 
 int dg_colsum(TView v, int B, int H, int W, int C, const float* scale, float* out, float* raw, int accumulate,
-              float* scratch, hipStream_t st) {
-  return colsum_impl(v, B, H, W, C, scale, out, raw, accumulate, nullptr, scratch, st);
+              float* scratch, size_t scratch_floats, hipStream_t st) {
+  return colsum_impl(v, B, H, W, C, scale, out, raw, accumulate, nullptr, scratch, scratch_floats, st);
 }
 int dg_colsum_rowmul(TView v, int B, int H, int W, int C, const float* rowmul, float* out, float* scratch,
-                     hipStream_t st) {
-  return colsum_impl(v, B, H, W, C, nullptr, out, nullptr, 0, rowmul, scratch, st);
+                     size_t scratch_floats, hipStream_t st) {
+  return colsum_impl(v, B, H, W, C, nullptr, out, nullptr, 0, rowmul, scratch, scratch_floats, st);
 }
 
 __global__ void sum_partial(const float* __restrict__ in, size_t n, float* __restrict__ part) {
@@ -526,7 +548,9 @@ __global__ void sum_final(const float* __restrict__ part, int nb, float* __restr
   acc = block_sum(acc, sh4);
   if (threadIdx.x == 0) out[0] = acc;
 }
-int dg_sum(const float* in, size_t n, float* out, float* scratch, hipStream_t st) {
+size_t dg_sum_scratch(size_t n) { return (size_t)nblk(n, 1024); }
+int dg_sum(const float* in, size_t n, float* out, float* scratch, size_t scratch_floats, hipStream_t st) {
+  if (!scratch_ok("dg_sum", dg_sum_scratch(n), scratch_floats)) return DG_ERR_ARG;
   const int nb = nblk(n, 1024);
   hipLaunchKernelGGL(sum_partial, dim3(nb), dim3(256), 0, st, in, n, scratch);
   HIPCHECK(hipGetLastError());
@@ -613,8 +637,10 @@ __global__ void gp_value_kernel(const float* __restrict__ norms, float* __restri
   acc = block_sum(acc, sh4);
   if (threadIdx.x == 0) gp_out[0] = acc / (float)B;
 }
+size_t dg_gp_u0_scratch(int B) { return (size_t)B * GP_SPLIT; }
 int dg_gp_u0(const float* g0, float* u0, float* norms, float* gp_out, float delta, int B, long HW, float* scratch,
-             hipStream_t st) {
+             size_t scratch_floats, hipStream_t st) {
+  if (!scratch_ok("dg_gp_u0", dg_gp_u0_scratch(B), scratch_floats)) return DG_ERR_ARG;
   hipLaunchKernelGGL(gp_sq_partial, dim3(B, GP_SPLIT), dim3(256), 0, st, g0, HW, scratch);
   HIPCHECK(hipGetLastError());
   hipLaunchKernelGGL(gp_scale_kernel, dim3(B, GP_SPLIT), dim3(256), 0, st, g0, u0, scratch, norms, delta, B, HW);
@@ -662,8 +688,10 @@ __global__ void gloss_final(const float* __restrict__ part, int nb, float* __res
     if (threadIdx.x == 0) sums[k] = s;
   }
 }
+size_t dg_gloss_sums_scratch(long P) { return (size_t)4 * nblk((size_t)P, 1024); }
 int dg_gloss_sums(const float* x, int nicg, const float* y2, const float* attr, float thr, float* sums, long P,
-                  float* scratch, hipStream_t st) {
+                  float* scratch, size_t scratch_floats, hipStream_t st) {
+  if (!scratch_ok("dg_gloss_sums", dg_gloss_sums_scratch(P), scratch_floats)) return DG_ERR_ARG;
   const int nb = nblk((size_t)P, 1024);
   hipLaunchKernelGGL(gloss_partial, dim3(nb), dim3(256), 0, st, x, nicg, y2, attr, thr, P, scratch);
   HIPCHECK(hipGetLastError());
@@ -749,9 +777,11 @@ __global__ void film_bwd_final(const float* __restrict__ part, float* __restrict
     dadd[(size_t)b * film_ld + c] = sa;
   }
 }
+size_t dg_film_bwd_scratch(int B, int C) { return (size_t)B * FILM_SPLIT * 2 * C; }
 int dg_film_bwd(const float* dr, const float* u, const float* fmul, const float* fadd, int film_ld, float* du,
-                float* dmul, float* dadd, int B, long HW, int C, float* scratch, hipStream_t st) {
+                float* dmul, float* dadd, int B, long HW, int C, float* scratch, size_t scratch_floats, hipStream_t st) {
   if ((C % 4) || C > 128) { dg_set_error("dg_film_bwd: C must be a multiple of 4 and <= 128"); return DG_ERR_ARG; }
+  if (!scratch_ok("dg_film_bwd", dg_film_bwd_scratch(B, C), scratch_floats)) return DG_ERR_ARG;
   hipLaunchKernelGGL(film_bwd_partial, dim3(B, FILM_SPLIT), dim3(256), 256 * 8 * sizeof(float), st, dr, u, fmul, fadd,
                      film_ld, du, scratch, HW, C / 4);
   HIPCHECK(hipGetLastError());
@@ -935,7 +965,8 @@ __global__ void best_noise_kernel(const float* __restrict__ stats, int k, const 
     float bv = g_total_loss_dev(stats);
     for (int i = 1; i < k; ++i) {
       const float v = g_total_loss_dev(stats + 8 * i);
-      if (v < bv) { bv = v; bi = i; }     // first minimum, like np.argmin; NaN never wins (as in NumPy only if first)
+      // np.argmin: the first NaN wins (NaN propagates as the minimum); without one, the first minimum
+      if (v < bv || (isnan(v) && !isnan(bv))) { bv = v; bi = i; }
     }
     sbest = bi;
     *best = bi;

@@ -297,7 +297,7 @@ static int u_backward(depgan_ctx* c, const float* x, const float* z, int n) {
         ProfScope ps(c, 2, 0.0, "film bwd");
         DGCHECK(dg_film_bwd(L.dout.p, L.u.p, c->na.heads + L.col_mul, c->na.heads + L.col_add, 1024, du.p,
                             c->dheads + L.col_mul, c->dheads + L.col_add, n, (long)L.H * L.W, L.Cout, c->scratch,
-                            c->st));
+                            c->scratchFloats, c->st));
       }
       DGCHECK(u_conv_bwd(c, L, (size_t)i, x, du, L.dout, n, 1.0f));
     } else if (L.kind == G_POOL) {

@@ -314,6 +314,78 @@ int depgan_op_bn_rows_bwd(const float* dy, const float* x, const float* relu_out
 int depgan_op_small_gemm(int form, const float* A, const float* Bm, const float* bias, float* Cm, int M, int K, int N,
                          void* hip_stream);
 
+/* The two-critic step's HBM-bound operators and the noise MLP, each the internal function the model calls.  Device
+ * pointers; views as above.  scratch_floats: capacity of the reduction scratch the call allocates, <= 0 for what the
+ * launch needs; a capacity below that need is refused with status 1. */
+/* backward of MaxPooling2D + the ReLU mask of its input a (pooled Ho x Wo, full 2Ho x 2Wo):
+ * out = ((first arg-max of the 2x2 window of a) ? dpool : 0) + skip) * (a > 0); skip optional (NULL). C % 4 == 0 */
+int depgan_op_unpool_mask(const float* dpool, long dsB, long dsY, long dsX, const float* a, long asB, long asY, long asX,
+                          const float* skip, long ssB, long ssY, long ssX, float* out, long osB, long osY, long osX,
+                          int B, int Ho, int Wo, int C, void* hip_stream);
+/* out[pooled] = u[first arg-max of the 2x2 window of a] */
+int depgan_op_gather_pool(const float* u, long usB, long usY, long usX, const float* a, long asB, long asY, long asX,
+                          float* out, long osB, long osY, long osX, int B, int Ho, int Wo, int C, void* hip_stream);
+/* generator head over [P][C] rows.  backward 0: out[p] = act(a[p] . w + b[0]), act tanh or identity;
+ * backward 1: out[p][c] = dpre[p] * w[c] * (a[p][c] > 0).  C/4 a power of two <= 64 */
+int depgan_op_head(int backward, const float* a, const float* w, const float* b, const float* dpre, float* out, long P,
+                   int C, int tanh_act, void* hip_stream);
+/* critic tail over N samples of [HW][C]: t9[n][p] = a . w9 + b9 ; out[n] = sum_p wd[p] t9[n][p] + bd */
+int depgan_op_critic_tail_fwd(const float* a, const float* w9, const float* b9, const float* wd, const float* bd,
+                              float* t9, float* out, int N, int HW, int C, void* hip_stream);
+/* dz[n][p][c] = coefs[n / per] * wd[p] * w9[c] * (a[n][p][c] > 0) */
+int depgan_op_critic_tail_bwd(const float* a, const float* w9, const float* wd, const float* coefs, int per, float* dz,
+                              int N, int HW, int C, void* hip_stream);
+/* the tail's weight gradients from coefs[n / per] * src; accumulate 1 adds to dw9 / dwd (/ db9 / dbd) */
+int depgan_op_critic_tail_wgrad(const float* src, const float* w9, const float* b9, const float* wd, const float* coefs,
+                                int per, int add_bias_terms, int accumulate, float* dw9, float* db9, float* dwd,
+                                float* dbd, int N, int HW, int C, long scratch_floats, void* hip_stream);
+/* column sums of an NHWC view: out[c] (+)= scale[c] (or 1) * sum, raw[c] = sum (out, raw optional); with rowmul:
+ * out[c] = sum_q rowmul[q] v[q][c] over the dense pixel index q (then scale, raw, accumulate must be unset).
+ * C % 4 == 0, C <= 256 */
+int depgan_op_colsum(const float* v, long sB, long sY, long sX, int B, int H, int W, int C, const float* scale,
+                     float* out, float* raw, int accumulate, const float* rowmul, long scratch_floats, void* hip_stream);
+/* out[0] = sum in[0..n) */
+int depgan_op_sum(const float* in, long n, float* out, long scratch_floats, void* hip_stream);
+/* which 0 / 1: the [real | fake | ep-mixed] input batch of the Y2 / DEM critic (3*B*HW floats);
+ * which 2: out = x[..., 0] + attr (B*HW floats; y2 and ep unused).  x has nicg interleaved channels */
+int depgan_op_critic_inputs(const float* y2, const float* x, int nicg, const float* attr, const float* ep, float* out,
+                            int B, long HW, int which, void* hip_stream);
+/* norms[b] = ||g0[b]||, u0 = delta*(2/B)*(norm-1)/norm * g0, gp_out (optional) = mean (norm-1)^2 */
+int depgan_op_gp_u0(const float* g0, float* u0, float* norms, float* gp_out, float delta, int B, long HW,
+                    long scratch_floats, void* hip_stream);
+/* out = [sum d_out[0..B), sum d_out[B..2B), sum (norms-1)^2, B] */
+int depgan_op_critic_stats(const float* d_out, const float* norms, float* out, int B, void* hip_stream);
+/* sums = [sum |attr-(y2-y1)|, #(y2 >= thr), #(y1+attr >= thr), #(both)], y1 = x[..., 0] */
+int depgan_op_gloss_sums(const float* x, int nicg, const float* y2, const float* attr, float thr, float* sums, long P,
+                         long scratch_floats, void* hip_stream);
+/* dpre = (-(g1+g2)/B + (100/P) sign(attr - (y2-y1))) * (1 - attr^2) */
+int depgan_op_g_dpre(const float* x, int nicg, const float* y2, const float* attr, const float* g1, const float* g2,
+                     float* dpre, int B, long P, void* hip_stream);
+/* FiLM backward over [B][HW][C]; fmul/fadd and dmul/dadd are rows of film_ld floats per sample.  C % 4 == 0, C <= 128 */
+int depgan_op_film_bwd(const float* dr, const float* u, const float* fmul, const float* fadd, int film_ld, float* du,
+                       float* dmul, float* dadd, int B, long HW, int C, long scratch_floats, void* hip_stream);
+/* one launch over njobs BatchNorm affines; ptrs: 8 device pointers per job (gamma, beta, mean, var, s, t, rstd,
+ * mean_copy or NULL), C: channels per job (host arrays) */
+int depgan_op_bn_prepare_batch(void* const* ptrs, const int* C, int njobs, float eps, void* hip_stream);
+/* one launch over njobs BN-gamma gradients; ptrs: 7 device pointers per job (W, dWraw, bias, mean, rstd, S, dgamma),
+ * dims: K, Cout, oi, Cin per job (host arrays); the jobs' blocks follow each other, Cout per job */
+int depgan_op_bn_gamma_grad_batch(void* const* ptrs, const int* dims, int njobs, void* hip_stream);
+/* the noise MLP with inference-mode BatchNorm.  trunk: W0, b0, s0, t0, mean0, rstd0 (32 each), W1 (32x32), b1, s1, t1,
+ * mean1, rstd1 (32 each); Wh: the 14 head kernels [1024][ncol[h]] back to back; hvec: bh, sh, th, meanh, rstdh
+ * (1024 each); ncol: 14 host ints summing to 1024; acts: h0, a0, h1, a1, lin, heads ([B][1024] each) */
+int depgan_op_noise_fwd(const float* trunk, const float* Wh, const float* hvec, const int* ncol, const float* z,
+                        float* acts, int B, void* hip_stream);
+/* its backward from dheads [B][1024]: gtrunk = dW0, db0, dgamma0, dbeta0 (32 each), dW1 (32x32), db1, dgamma1, dbeta1;
+ * dWh packed as Wh; ghvec = dbh, dgamma_h, dbeta_h (1024 each) */
+int depgan_op_noise_bwd(const float* trunk, const float* Wh, const float* hvec, const int* ncol, const float* z,
+                        float* acts, const float* dheads, float* gtrunk, float* dWh, float* ghvec, int B,
+                        long scratch_floats, void* hip_stream);
+/* best-of-k noise: k x 8 loss pieces -> *best = np.argmin of the k total losses, z_out = z_all[best] (zfloats) */
+int depgan_op_best_noise(const float* stats, int k, const float* z_all, long zfloats, int* best, float* z_out,
+                         void* hip_stream);
+/* dst[i] = mask[i] ? float(bfloat16(src[i])) : src[i] */
+int depgan_op_round_bf16_masked(const float* src, const unsigned char* mask, float* dst, long n, void* hip_stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -165,3 +165,47 @@ def test_every_moments_and_colsum_call_passes_its_scratch_capacity():
         assert args[-3:-1] == ["c->scratch", "c->scratchFloats"], (name, args)
     model = open(os.path.join(ROOT, "dep_gan_im_amd", "csrc", "model.hip")).read()
     assert re.search(r"dmalloc\(c, &c->scratch, c->scratchFloats\)", model)
+
+
+SCRATCH_REDUCTIONS = ["dg_colsum", "dg_colsum_rowmul", "dg_sum", "dg_gp_u0", "dg_gloss_sums", "dg_film_bwd",
+                      "dg_critic_tail_wgrad", "dg_noise_bwd"]
+
+
+def test_every_step_reduction_call_passes_its_scratch_capacity():
+    """The step's reductions write their partials (colsum: up to 2048 x C floats) into the context's scratch and
+    refuse a smaller capacity: every call in the model passes c->scratch together with c->scratchFloats (the
+    depgan_op_* entries: the scratch they allocate and its capacity), and each declares its capacity argument and a
+    *_scratch size helper."""
+    model_calls = set()
+    for f in ("model.hip", "uresnet.hip"):
+        src = open(os.path.join(ROOT, "dep_gan_im_amd", "csrc", f)).read()
+        for name, args in re.findall(r"\b(%s)\s*\(([^;]*)\);" % "|".join(SCRATCH_REDUCTIONS), src):
+            args = [a.strip() for a in args.replace("\n", " ").split(",")]
+            pairs = [tuple(args[i:i + 2]) for i in range(len(args) - 1)]
+            assert ("c->scratch", "c->scratchFloats") in pairs or ("scratch", "cap") in pairs, (name, args)
+            if "c->scratch" in args:
+                model_calls.add(name)
+    assert model_calls == set(SCRATCH_REDUCTIONS)
+    hdr = open(os.path.join(ROOT, "dep_gan_im_amd", "csrc", "ops.h")).read()
+    hdr += open(os.path.join(ROOT, "dep_gan_im_amd", "csrc", "noise.h")).read()
+    for name in SCRATCH_REDUCTIONS:
+        decl = re.search(r"\bint %s\(([^;]*)\);" % name, hdr).group(1)
+        assert re.search(r"float\* scratch,\s*size_t scratch_floats", decl), name
+    for helper in ("dg_colsum", "dg_sum", "dg_gp_u0", "dg_gloss_sums", "dg_film_bwd", "dg_critic_tail_wgrad",
+                   "dg_noise_bwd"):
+        assert re.search(r"\bsize_t %s_scratch\(" % helper, hdr), helper
+
+
+STEP_OPS = ["unpool_mask", "gather_pool", "head", "critic_tail_fwd", "critic_tail_bwd", "critic_tail_wgrad", "colsum",
+            "sum", "critic_inputs", "gp_u0", "critic_stats", "gloss_sums", "g_dpre", "film_bwd", "bn_prepare_batch",
+            "bn_gamma_grad_batch", "noise_fwd", "noise_bwd", "best_noise", "round_bf16_masked"]
+
+
+def test_step_operator_entries_are_exported_and_bound(lib):
+    hdr = open(os.path.join(ROOT, "include", "depgan.h")).read()
+    for op in STEP_OPS:
+        name = "depgan_op_" + op
+        assert re.search(r"\bint %s\(" % name, hdr), name
+        assert name in _lib.EXPORTS, name
+        assert hasattr(lib, name), name
+        assert getattr(lib, name).argtypes, name + " has no argtypes"
