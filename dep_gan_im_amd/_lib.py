@@ -29,6 +29,8 @@ EXPORTS = [
     "depgan_op_critic_inputs", "depgan_op_gp_u0", "depgan_op_critic_stats", "depgan_op_gloss_sums", "depgan_op_g_dpre",
     "depgan_op_film_bwd", "depgan_op_bn_prepare_batch", "depgan_op_bn_gamma_grad_batch", "depgan_op_noise_fwd",
     "depgan_op_noise_bwd", "depgan_op_best_noise", "depgan_op_round_bf16_masked",
+    "depgan_data_zscore_scratch_floats", "depgan_data_prep_zscore", "depgan_data_mask_slices", "depgan_labels_to_onehot",
+    "depgan_eval_accumulate_channels", "depgan_eval_label_counts",
 ]
 
 ABI_VERSION = 3          # DEPGAN_ABI_VERSION of the include/depgan.h this binding was written against
@@ -135,6 +137,13 @@ def load():
     lib.depgan_data_prep_scratch_floats.argtypes = [C.c_int] * 3
     lib.depgan_data_prep_scratch_floats.restype = C.c_size_t
     lib.depgan_data_prep_subject.argtypes = [vp] * 7 + [C.c_int] * 4 + [vp] * 4
+    lib.depgan_data_zscore_scratch_floats.argtypes = [C.c_int] * 3
+    lib.depgan_data_zscore_scratch_floats.restype = C.c_size_t
+    lib.depgan_data_prep_zscore.argtypes = [vp] * 3 + [C.c_int] * 3 + [vp] * 4
+    lib.depgan_data_mask_slices.argtypes = [vp] * 3 + [C.c_int] * 3 + [vp] * 2
+    lib.depgan_labels_to_onehot.argtypes = [vp, C.c_long, C.c_int, vp, vp]
+    lib.depgan_eval_accumulate_channels.argtypes = [vp, vp, vp, C.c_long, C.c_int, vp]
+    lib.depgan_eval_label_counts.argtypes = [vp, C.c_int] + [vp] * 5 + [C.c_long, vp, C.POINTER(C.c_longlong), vp]
     lib.depgan_op_maxpool.argtypes = [vp, vp] + [C.c_int] * 4 + [vp]
     lib.depgan_op_deconv2x2.argtypes = [vp] * 6 + [C.c_int] * 6 + [vp]
     lib.depgan_op_deconv2x2_wgrad.argtypes = [vp] * 4 + [C.c_int] * 5 + [vp]

@@ -10,6 +10,17 @@ Here the arithmetic of a subject runs on the GPU (`depgan_data_prep_subject`, in
 thread reads and decodes the next subject's files into pinned memory, so a training set is assembled at file-read
 speed and never exists on the host as float arrays.  Results are bit-identical to the NumPy statements
 (oracle/data_oracle.py restates them for the tests).
+
+The DEP-UResNet training script ("UT", DEP-UResNet-wNoises-training-4fold.py:434-566) prepares its inputs differently:
+four lists (`uresnet_file_lists`), FLAIR z-scored over the whole masked volume instead of mapped to [0, 1]
+(`depgan_data_prep_zscore`), the coded change map masked like the FLAIR as the target, and 4-class one-hot labels
+made from it (`to_one_hot`).  `load_uresnet_training_set` is its counterpart of `load_training_set`; `zscore_flair`
+and `mask_slices` also build every array the DEP-UResNet evaluation script ("UE") derives from its volumes.
+
+List pairing: both scripts walk their first list and read the other lists at a counter `id` that advances only for
+files that exist (GT:662-733, UT:478-526), so after a missing first-list file every later subject would be read
+together with the previous line's other files.  That drift is deliberately not reproduced: here the lists are paired
+by line, and a missing first-list file skips its whole line.
 """
 from __future__ import annotations
 
@@ -121,6 +132,30 @@ def _read_subject(files, nicg, pin):
     return out, shape
 
 
+def _prefetched(items, read, prefetch):
+    """Yields (item, read(item)) in order while a reader thread keeps `prefetch` results ahead of the consumer."""
+    q = queue.Queue(maxsize=max(1, int(prefetch)))
+
+    def reader():
+        try:
+            for s in items:
+                q.put((s, read(s)))
+            q.put(None)
+        except BaseException as e:      # surfaced on the consumer side
+            q.put(e)
+
+    th = threading.Thread(target=reader, daemon=True)
+    th.start()
+    while True:
+        item = q.get()
+        if item is None:
+            break
+        if isinstance(item, BaseException):
+            raise item
+        yield item
+    th.join()
+
+
 def load_training_set(subjects, nicg=2, device=None, prefetch=2, progress=None):
     """GT:663-733: every subject whose wmh_prob_1tp file exists, stacked along the slice axis.
     subjects: list of SubjectFiles (training_file_lists).  Returns (x (N, X, Y, nicg), y2 (N, X, Y, 1)) on `device`.
@@ -128,33 +163,14 @@ def load_training_set(subjects, nicg=2, device=None, prefetch=2, progress=None):
     import torch
     dev = torch.device(device if device is not None else "cuda:0")
     todo = [s for s in subjects if os.path.isfile(s.prob_1tp)]
-    q = queue.Queue(maxsize=max(1, int(prefetch)))
-
-    def reader():
-        try:
-            for s in todo:
-                q.put((s, _read_subject(s, nicg, pin=True)))
-            q.put(None)
-        except BaseException as e:      # surfaced on the consumer side
-            q.put(e)
-
-    th = threading.Thread(target=reader, daemon=True)
-    th.start()
     xs, ys = [], []
-    while True:
-        item = q.get()
-        if item is None:
-            break
-        if isinstance(item, BaseException):
-            raise item
-        s, (host, shape) = item
+    for s, (host, shape) in _prefetched(todo, lambda s: _read_subject(s, nicg, pin=True), prefetch):
         vols = [None if t is None else t.to(dev, non_blocking=True) for t in host]
         x, y2 = prep_subject_flat(vols, shape, nicg, dev)
         xs.append(x)
         ys.append(y2)
         if progress is not None:
             progress(s, tuple(x.shape))
-    th.join()
     if not xs:
         raise ValueError("no subject with an existing wmh_prob_1tp file")
     return torch.cat(xs, 0), torch.cat(ys, 0)
@@ -176,6 +192,172 @@ def split_and_shuffle(x, y2, rng=None):
     tv = torch.from_numpy(val.astype(np.int64)).to(x.device)
     tt = torch.from_numpy(train.astype(np.int64)).to(x.device)
     return x.index_select(0, tt), x.index_select(0, tv), y2.index_select(0, tt), y2.index_select(0, tv)
+
+
+# ---- DEP-UResNet data step (UT:434-566; the same statements in UE:496-540) ----
+
+UResNetFiles = namedtuple("UResNetFiles", "flair_1tp coded icv_1tp sl_1tp")
+
+# list-file stems, UT:446-468
+_URESNET_LISTS = (("flair_1tp", "flair_1tp"), ("coded", "wmh_subtracted_coded_2tp_1tp"), ("icv_1tp", "icv_1tp"),
+                  ("sl_1tp", "sl_cleaned_1tp"))
+
+
+def uresnet_file_lists(config_dir, fold):
+    """The four lists of UT:446-468 as one UResNetFiles per line index (FLAIR, coded change map, ICV, stroke lesions)."""
+    cols = {k: read_list(os.path.join(config_dir, "%s_fold%s.txt" % (stem, fold))) for k, stem in _URESNET_LISTS}
+    n = len(cols["flair_1tp"])
+    for k, v in cols.items():
+        if len(v) < n:
+            raise ValueError("list %s has %d entries, flair_1tp has %d" % (k, len(v), n))
+    return [UResNetFiles(*[cols[k][i] for k in UResNetFiles._fields]) for i in range(n)]
+
+
+def _p(t):
+    return C.c_void_p(t.data_ptr()) if t is not None else None
+
+
+def _stream(dev, stream):
+    import torch
+    return C.c_void_p(stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream)
+
+
+def _check_flat(vols, npix):
+    import torch
+    for v in vols:
+        if v is not None and (v.dtype != torch.float32 or v.numel() != npix or not v.is_cuda):
+            raise ValueError("volumes must be float32 CUDA tensors of X*Y*Z elements")
+
+
+def _flat_volumes(vols, device):
+    """(X, Y, Z) NumPy volumes (None allowed) -> (flat float32 CUDA tensors in file order, shape, device)."""
+    import torch
+    dev = torch.device(device if device is not None else "cuda:0")
+    shape = None
+    out = []
+    for v in vols:
+        if v is None:
+            out.append(None)
+            continue
+        if shape is None:
+            shape = tuple(np.shape(v))
+        elif tuple(np.shape(v)) != shape:
+            raise ValueError("volume shapes differ: %s vs %s" % (np.shape(v), shape))
+        out.append(torch.from_numpy(_file_order_f32(v)).to(dev, non_blocking=True))
+    return out, shape, dev
+
+
+def zscore_flair_flat(f1, icv1, sl1, shape, dev, stream=None, with_stats=False):
+    """f1 / icv1 / sl1: flat float32 CUDA tensors in file order (sl1 may be None).  Returns the z-scored brain FLAIR
+    (Z, X, Y, 1) of UT:485-512 [and the device's (mean32, std32) as a (2,) float32 CUDA tensor]."""
+    import torch
+    lib = _lib.load()
+    X, Y, Z = (int(s) for s in shape)
+    if f1 is None or icv1 is None:
+        raise ValueError("the z-score needs the FLAIR and the ICV volume")
+    _check_flat((f1, icv1, sl1), X * Y * Z)
+    out = torch.empty((Z, X, Y, 1), dtype=torch.float32, device=dev)
+    stats = torch.empty(2, dtype=torch.float32, device=dev) if with_stats else None
+    scratch = torch.empty(int(lib.depgan_data_zscore_scratch_floats(X, Y, Z)), dtype=torch.float32, device=dev)
+    _lib.check(lib.depgan_data_prep_zscore(_p(f1), _p(icv1), _p(sl1), X, Y, Z, _p(out), _p(stats), _p(scratch),
+                                           _stream(dev, stream)), "depgan_data_prep_zscore")
+    return (out, stats) if with_stats else out
+
+
+def zscore_flair(f1, icv1, sl1=None, device=None, stream=None, with_stats=False):
+    """UT:510-512 / UE:538-540 on (X, Y, Z) volumes of any dtype: brain_flair_1tp = f1*icv1 [*(1 - sl1)], then
+    nan_to_num((brain - mean) / std) over the whole volume.  Returns (Z, X, Y, 1) float32 on the GPU."""
+    vols, shape, dev = _flat_volumes((f1, icv1, sl1), device)
+    return zscore_flair_flat(*vols, shape, dev, stream, with_stats)
+
+
+def mask_slices_flat(vol, m_a, sl, shape, dev, stream=None):
+    """(vol [* m_a]) [* (1 - sl)] as (Z, X, Y, 1) slices; flat float32 CUDA tensors in file order."""
+    import torch
+    lib = _lib.load()
+    X, Y, Z = (int(s) for s in shape)
+    if vol is None:
+        raise ValueError("mask_slices needs a volume")
+    _check_flat((vol, m_a, sl), X * Y * Z)
+    out = torch.empty((Z, X, Y, 1), dtype=torch.float32, device=dev)
+    _lib.check(lib.depgan_data_mask_slices(_p(vol), _p(m_a), _p(sl), X, Y, Z, _p(out), _stream(dev, stream)),
+               "depgan_data_mask_slices")
+    return out
+
+
+def mask_slices(vol, m_a=None, sl=None, device=None, stream=None):
+    """np.multiply(vol, m_a) [then np.multiply(., 1 - sl)] on (X, Y, Z) volumes, as the reference's slices
+    (Z, X, Y, 1) float32 on the GPU.  UT brain_wsc_1tp = mask_slices(wsc, icv1, sl1); UE brain_wmh_1tp / _2tp likewise,
+    brain_cod_2tp = mask_slices(code2, icv2) (no stroke-lesion factor, UE:515), icv_and_sl_mask_1tp =
+    mask_slices(icv1, None, sl1)."""
+    vols, shape, dev = _flat_volumes((vol, m_a, sl), device)
+    return mask_slices_flat(*vols, shape, dev, stream)
+
+
+def _read_uresnet_subject(files, pin):
+    """Host side of one UT subject: [flair, coded, icv, sl or None] as flat float32 (pinned) tensors.  A missing
+    stroke-lesion file means "no mask" (UT:500: os.path.isfile)."""
+    import torch
+    out, shape = [], None
+    for key in UResNetFiles._fields:
+        path = getattr(files, key)
+        if key == "sl_1tp" and not os.path.isfile(path):
+            out.append(None)
+            continue
+        vol = nifti.load(path).image
+        if shape is None:
+            shape = vol.shape
+        elif vol.shape != shape:
+            raise ValueError("%s: shape %s differs from %s" % (path, vol.shape, shape))
+        t = torch.from_numpy(_file_order_f32(vol))
+        out.append(t.pin_memory() if pin else t)
+    return out, shape
+
+
+def load_uresnet_training_set(subjects, device=None, prefetch=2, progress=None):
+    """UT:474-531: every subject whose FLAIR file exists, stacked along the slice axis.
+    subjects: list of UResNetFiles (uresnet_file_lists).  Returns (flair (N, X, Y, 1), coded (N, X, Y, 1)) on `device`:
+    the z-scored brain FLAIR and brain_wsc_1tp = coded*icv1 [*(1 - sl1)].  split_and_shuffle takes them as they are;
+    to_one_hot makes the labels.  A reader thread keeps `prefetch` decoded subjects ahead of the GPU."""
+    import torch
+    dev = torch.device(device if device is not None else "cuda:0")
+    todo = [s for s in subjects if os.path.isfile(s.flair_1tp)]
+    fs, cs = [], []
+    for s, (host, shape) in _prefetched(todo, lambda s: _read_uresnet_subject(s, pin=True), prefetch):
+        f1, code, icv1, sl1 = [None if t is None else t.to(dev, non_blocking=True) for t in host]
+        fs.append(zscore_flair_flat(f1, icv1, sl1, shape, dev))           # UT:494-512
+        cs.append(mask_slices_flat(code, icv1, sl1, shape, dev))          # UT:494-502
+        if progress is not None:
+            progress(s, tuple(fs[-1].shape))
+    if not fs:
+        raise ValueError("no subject with an existing flair_1tp file")
+    return torch.cat(fs, 0), torch.cat(cs, 0)
+
+
+def to_one_hot(coded, n_class=4, device=None):
+    """UT:563-568: coded.astype(int) (truncation toward zero), then convert_to_1hot(., n_class) and np.squeeze.
+    coded: (N, X, Y, 1) or (N, X, Y) array / tensor.  Returns (N, X, Y, n_class) float32 on the GPU, the layout
+    Gen_UNet2D(..., nc_out=4).fit reads.  A value outside [0, n_class) raises DepganError (NumPy would wrap a
+    negative index)."""
+    if isinstance(n_class, bool) or not isinstance(n_class, (int, np.integer)) or not 1 <= int(n_class) <= 127:
+        raise ValueError("n_class must be an integer in [1, 127], got %r" % (n_class,))
+    shape = tuple(int(d) for d in (coded.shape if hasattr(coded, "shape") else np.shape(coded)))
+    if len(shape) == 4 and shape[3] == 1:
+        shape = shape[:3]
+    if len(shape) != 3:
+        raise ValueError("coded must be (N, X, Y, 1) or (N, X, Y), got shape %s" % (shape,))
+    import torch
+    lib = _lib.load()
+    if isinstance(coded, torch.Tensor):
+        dev = coded.device if device is None and coded.is_cuda else torch.device(device or "cuda:0")
+        t = coded.to(device=dev, dtype=torch.float32).contiguous()
+    else:
+        dev = torch.device(device if device is not None else "cuda:0")
+        t = torch.from_numpy(np.ascontiguousarray(np.asarray(coded), dtype=np.float32)).to(dev)
+    out = torch.empty(shape + (int(n_class),), dtype=torch.float32, device=dev)
+    _lib.check(lib.depgan_labels_to_onehot(_p(t), t.numel(), int(n_class), _p(out), _stream(dev, None)),
+               "depgan_labels_to_onehot")
+    return out
 
 
 def data_prep_save(image_data):

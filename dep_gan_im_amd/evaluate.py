@@ -9,6 +9,16 @@ The mean over the n_repeat noise draws is accumulated on the device in float64 l
 accumulator (GE:617), and the volumes / Dice figures come from one integer census kernel (exact counts) that thresholds
 that float64 mean in float64; only the two dozen integers travel to the host, where the reference's own scalar
 algebra is applied.
+
+The DEP-UResNet evaluation (DEP-UResNet_testing_4fold.py "UE":553-717) works on the C = 4 class probabilities instead:
+
+    prob = predict_mean(my_network, brain_flair_1tp, n_repeat=10, mask=icv_and_sl_mask_2tp)  # UE:553-564, (n,H,W,4)
+    m = uresnet_metrics(prob, brain_cod_2tp, icv_and_sl_mask_1tp, brain_wmh_1tp, icv_and_sl_mask_2tp, brain_wmh_2tp,
+                        voxel_volume)                                                           # UE:566-700
+    save_uresnet_maps(dirOutData, name, m["labels"], prob, affine)                              # UE:705-717
+
+The label map is np.argmax over the float64 channel means (first index on a tie), and the volumes and Dice figures
+come from an 18-count integer census of it (`depgan_eval_label_counts`).
 """
 from __future__ import annotations
 
@@ -19,6 +29,7 @@ import numpy as np
 from . import _lib
 
 NCOUNT = 20
+NCOUNT_LABEL = 18
 
 
 def _torch():
@@ -44,7 +55,11 @@ def _p(t):
 def predict_mean(netG, x, n_repeat=10, mask=None, noise_size=32, rng=None, batch_size=32):
     """Mean of n_repeat generator predictions with fresh N(0,1) noise, each multiplied by `mask` (GE:616-628).
     x: (n, H, W, nicg); mask: (n, H, W) or None.  Returns a float64 CUDA tensor (n, H, W): the reference's running
-    sum is float64 and so is the mean it thresholds (GE:617, 628)."""
+    sum is float64 and so is the mean it thresholds (GE:617, 628).
+    A model with nc_out > 1 (DEP-UResNet, UE:553-564) gets the mask broadcast over its channels and a float64 CUDA
+    tensor (n, H, W, nc_out) back."""
+    if getattr(netG, "nc_out", 1) != 1:
+        return _predict_mean_channels(netG, x, n_repeat, mask, noise_size, rng, batch_size)
     torch = _torch()
     lib = _lib.load()
     rng = rng if rng is not None else np.random
@@ -63,6 +78,32 @@ def predict_mean(netG, x, n_repeat=10, mask=None, noise_size=32, rng=None, batch
         _lib.check(lib.depgan_eval_accumulate(_p(pred), _p(md), _p(acc), acc.numel(), stream),
                    "depgan_eval_accumulate")                                          # GE:623-624
     _lib.check(lib.depgan_eval_divide(_p(acc), acc.numel(), float(n_repeat), stream), "depgan_eval_divide")  # GE:628
+    return acc
+
+
+def _predict_mean_channels(netG, x, n_repeat, mask, noise_size, rng, batch_size):
+    """UE:553-564: output_img_pred_mean (np.zeros, float64) += predict([x, noise]) * icv_and_sl_mask_2tp, the mask
+    (n, H, W[, 1]) broadcast over the C channels; then / float(n_repeat)."""
+    torch = _torch()
+    lib = _lib.load()
+    rng = rng if rng is not None else np.random
+    n = len(x)
+    eng = netG._ensure_engine(min(batch_size, n))
+    dev = eng.device
+    C_out = int(eng.nc_out)
+    xd = _dev(x, dev)
+    md = _dev(mask, dev)
+    npix = n * eng.height * eng.width
+    if md is not None and md.numel() != npix:
+        raise ValueError("mask must have one value per output pixel")
+    acc = torch.zeros((n, eng.height, eng.width, C_out), dtype=torch.float64, device=dev)        # UE:554
+    stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+    for _ in range(n_repeat):
+        noise = rng.normal(size=(n, noise_size, 1)).astype("float32")               # UE:557
+        pred = eng.g_forward(xd, noise)                                               # UE:558
+        _lib.check(lib.depgan_eval_accumulate_channels(_p(pred), _p(md), _p(acc), npix, C_out, stream),
+                   "depgan_eval_accumulate_channels")                                 # UE:559-560
+    _lib.check(lib.depgan_eval_divide(_p(acc), acc.numel(), float(n_repeat), stream), "depgan_eval_divide")  # UE:564
     return acc
 
 
@@ -128,3 +169,93 @@ def metrics_from_census(c, voxel_volume):
 def dem_metrics(x, pred, code_real, mask1, wmh1, mask2, wmh2, prob2, voxel_volume, thr):
     """All per-subject figures of GE:637-790 for one volume of slices."""
     return metrics_from_census(census(x, pred, code_real, mask1, wmh1, mask2, wmh2, prob2, thr), voxel_volume)
+
+
+# ---- DEP-UResNet evaluation (UE:566-717) ----
+
+def label_census(pred, code_real=None, mask1=None, wmh1=None, mask2=None, wmh2=None, device=None,
+                 return_labels=False):
+    """The 18 integer counts of depgan_eval_label_counts (include/depgan.h) as a Python list.
+    pred: (..., C) float64 class probabilities (predict_mean of a 4-channel model); the other arrays have one value
+    per pixel and may be None.  With return_labels the argmax label map (pred.shape[:-1], int8 CUDA tensor) comes too."""
+    torch = _torch()
+    lib = _lib.load()
+    if device is None:
+        device = pred.device if isinstance(pred, torch.Tensor) else torch.device("cuda:%d" % torch.cuda.current_device())
+    pd = _dev(pred, device, torch.float64)
+    if pd.dim() < 2:
+        raise ValueError("pred must be (..., C)")
+    n_class = int(pd.shape[-1])
+    npix = pd.numel() // n_class
+    arrs = [_dev(a, device) for a in (code_real, mask1, wmh1, mask2, wmh2)]
+    for name, a in zip(("code_real", "mask1", "wmh1", "mask2", "wmh2"), arrs):
+        if a is not None and a.numel() != npix:
+            raise ValueError("%s must have %d elements, got %d" % (name, npix, a.numel()))
+    labels = torch.empty(tuple(pd.shape[:-1]), dtype=torch.int8, device=device) if return_labels else None
+    out = (C.c_longlong * NCOUNT_LABEL)()
+    stream = C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+    _lib.check(lib.depgan_eval_label_counts(_p(pd), n_class, *[_p(a) for a in arrs], npix, _p(labels), out, stream),
+               "depgan_eval_label_counts")
+    counts = [int(v) for v in out]
+    return (counts, labels) if return_labels else counts
+
+
+def label_metrics_from_census(c, voxel_volume):
+    """UE's scalar algebra on the label census (UE:572-700); vol_dsc has GE's 18-entry row order."""
+    vol_1tp__ml = c[0] * voxel_volume / 1000                                          # UE:575-581
+    vol_2tp__ml = c[1] * voxel_volume / 1000                                          # UE:584-591
+    vol_out__ml = c[2] * voxel_volume / 1000                                          # UE:594-602
+    err_vol = vol_out__ml - vol_2tp__ml                                               # UE:606
+    mse_vol = float(np.mean((vol_2tp__ml - vol_out__ml) ** 2))                        # UE:607
+    true_pred = true_prog = true_regg = prog = regg = 0                               # UE:609-624
+    if (vol_2tp__ml - vol_1tp__ml) >= 0:
+        prog = 1
+        if vol_out__ml - vol_1tp__ml >= 0:
+            true_pred = true_prog = 1
+    else:
+        regg = 1
+        if vol_out__ml - vol_1tp__ml < 0:
+            true_pred = true_regg = 1
+    dice_1, dice_2, dice_3 = (_dice(*c[3 + 3 * k:6 + 3 * k]) for k in range(3))       # UE:636-652
+    dice_4 = _dice(*c[12:15])                                                         # UE:654-662
+    dice_5 = _dice(*c[15:18])                                                         # UE:664-679
+    dice_6 = _dice(*c[9:12])                                                          # UE:681-690 (== dice_3)
+    avg_all_dice = (dice_1 + dice_2 + dice_3) / 3.0                                   # UE:697
+    avg_dice__56 = (dice_5 + dice_6) / 2.0                                            # UE:698
+    vol_dsc = [true_pred, prog, true_prog, regg, true_regg, vol_1tp__ml, vol_2tp__ml, vol_out__ml, mse_vol, err_vol,
+               dice_5, dice_6, avg_dice__56, dice_1, dice_2, dice_3, dice_4, avg_all_dice]    # UE:699-700
+    return {"vol_dsc": vol_dsc, "vol_1tp_ml": vol_1tp__ml, "vol_2tp_ml": vol_2tp__ml, "vol_out_ml": vol_out__ml,
+            "err_vol": err_vol, "mse_vol": mse_vol, "true_pred": true_pred, "prog": prog, "true_prog": true_prog,
+            "regg": regg, "true_regg": true_regg, "dice": [dice_1, dice_2, dice_3, dice_4, dice_5, dice_6],
+            "avg_all_dice": avg_all_dice, "avg_dice_56": avg_dice__56, "census": list(c)}
+
+
+def uresnet_metrics(pred, code_real, mask1, wmh1, mask2, wmh2, voxel_volume):
+    """All per-subject figures of UE:566-700 for one volume of slices; "labels" holds the label map (int8 CUDA
+    tensor, UE:570 convert_from_1hot) for save_uresnet_maps."""
+    c, labels = label_census(pred, code_real, mask1, wmh1, mask2, wmh2, return_labels=True)
+    m = label_metrics_from_census(c, voxel_volume)
+    m["labels"] = labels
+    return m
+
+
+def save_uresnet_maps(directory, name, labels, prob_mean, affine):
+    """UE:705-717: <name>_cls_map.nii.gz (the label map, int8) and <name>_prb_map_c<c>.nii.gz (channel c of the mean
+    probabilities, float32), each through data_prep_save.  labels: (N, H, W); prob_mean: (N, H, W, C).
+    Returns the paths written."""
+    import os
+    from . import nifti
+    from .data import data_prep_save
+
+    def host(a):
+        return a.detach().cpu().numpy() if hasattr(a, "detach") else np.asarray(a)
+
+    lab, prob = host(labels), host(prob_mean)
+    paths = [os.path.join(directory, name + "_cls_map.nii.gz")]
+    nifti.save(paths[0], data_prep_save(lab).astype("int8"), affine)                                   # UE:705-708
+    N, H, W, n_class = prob.shape
+    for c in range(n_class):
+        pred_prob = prob[:, :, :, c].reshape((N, H, W, 1))                                               # UE:712-713
+        paths.append(os.path.join(directory, name + "_prb_map_c" + str(c) + ".nii.gz"))
+        nifti.save(paths[-1], data_prep_save(pred_prob).astype("float32"), affine)                      # UE:715-717
+    return paths

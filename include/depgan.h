@@ -221,6 +221,44 @@ int depgan_data_prep_subject(const float* p1_dev, const float* f1_dev, const flo
                              const float* p2_dev, const float* icv2_dev, const float* sl2_dev, int X, int Y, int Z,
                              int nicg, float* x_out_dev, float* y2_out_dev, float* scratch_dev, void* stream);
 
+/* ---- DEP-UResNet data step and evaluation (DEP-UResNet-wNoises-training-4fold.py "UT":434-566,
+ * DEP-UResNet_testing_4fold.py "UE":496-717) ----
+ * Same conventions as above: device pointers, volumes in NIfTI file order, slices out as (Z, X, Y, C), work enqueued
+ * on `stream`, int status.
+ * depgan_data_prep_zscore (UT:485-512, UE:496-540): brain = f1*icv1 [*(1 - sl1)] (float32 products in that order);
+ *   mean and population std (ddof 0) over the WHOLE volume, zeros outside the brain included, each a float64 sum in a
+ *   fixed-order two-stage reduction (no float atomics: the bits repeat from run to run), then rounded to float32;
+ *   flair_out (Z, X, Y, 1) = nan_to_num((brain - mean32) / std32) in float32 (NaN -> 0, +-inf -> +-FLT_MAX; an all-zero
+ *   volume gives zeros).  sl1 may be NULL; stats_out_dev (float[2], may be NULL) receives (mean32, std32);
+ *   scratch: depgan_data_zscore_scratch_floats(X, Y, Z) device floats, 8-byte aligned.
+ * depgan_data_mask_slices: out (Z, X, Y, 1) = (vol [* m_a]) [* (1 - sl)], m_a / sl may be NULL; bit-identical to the
+ *   NumPy statements (UT brain_wsc_1tp; UE brain_wmh_1tp / _2tp, brain_cod_2tp = code2*icv2 without sl, and
+ *   icv_and_sl_mask_1tp / _2tp with vol = icv, m_a = NULL).
+ * depgan_labels_to_onehot (UT:563-566): onehot_out (npix, C) float32, row i = one_hot(astype(int)(coded[i])) --
+ *   truncation toward zero; a value outside [0, C) (NaN included) is status 1 (reported from a device counter; its row
+ *   is all zero), not NumPy's negative-index wrap.  Synchronises `stream`.  1 <= C <= DEPGAN_MAX_CLASSES.
+ * depgan_eval_accumulate_channels (UE:553-564): acc[i*C+c] += (double)(pred[i*C+c] * mask[i]) (mask may be NULL);
+ *   depgan_eval_divide over npix*C then forms the mean.
+ * depgan_eval_label_counts (UE:570-697): label = np.argmax over the C float64 channels of pred (npix, C) -- the first
+ *   index wins a tie, so pixels the mask zeroed get label 0; labels_out (npix int8, may be NULL) receives it.
+ *   code_real / mask1 / wmh1 / mask2 / wmh2 (npix float32) may be NULL (absent).  out_host:
+ *   [0] nnz(mask1*wmh1) [1] nnz(mask2*wmh2) [2] #(label > 0) (not masked again, as UE's vol_out);
+ *   then triples (#both, #real, #fake), real = code_real compared in float: for == k, k = 1, 2, 3 at [3..11],
+ *   for > 0 at [12..14], for in {1,2} at [15..17].  Synchronises `stream`. */
+#define DEPGAN_MAX_CLASSES 127
+#define DEPGAN_EVAL_LABEL_NCOUNT 18
+size_t depgan_data_zscore_scratch_floats(int X, int Y, int Z);
+int depgan_data_prep_zscore(const float* f1_dev, const float* icv1_dev, const float* sl1_dev, int X, int Y, int Z,
+                            float* flair_out_dev, float* stats_out_dev, float* scratch_dev, void* stream);
+int depgan_data_mask_slices(const float* vol_dev, const float* m_a_dev, const float* sl_dev, int X, int Y, int Z,
+                            float* out_dev, void* stream);
+int depgan_labels_to_onehot(const float* coded_dev, long npix, int C, float* onehot_out_dev, void* stream);
+int depgan_eval_accumulate_channels(const float* pred_dev, const float* mask_dev, double* acc_dev, long npix, int C,
+                                    void* stream);
+int depgan_eval_label_counts(const double* pred_dev, int C, const float* code_real_dev, const float* mask1_dev,
+                             const float* wmh1_dev, const float* mask2_dev, const float* wmh2_dev, long npix,
+                             signed char* labels_out_dev, long long out_host[DEPGAN_EVAL_LABEL_NCOUNT], void* stream);
+
 /* ---- parity-test surface: the tensors a training closure left behind ----
  * The step functions are piecewise linear in the ReLU signs and max-pool arg-maxes of the forward passes (GT:256-309
  * activations, GT:322-335 pools; the gradient penalty of GT:543-549 differentiates through them twice).  A parity
