@@ -31,6 +31,8 @@ EXPORTS = [
     "depgan_op_noise_bwd", "depgan_op_best_noise", "depgan_op_round_bf16_masked",
     "depgan_data_zscore_scratch_floats", "depgan_data_prep_zscore", "depgan_data_mask_slices", "depgan_labels_to_onehot",
     "depgan_eval_accumulate_channels", "depgan_eval_label_counts",
+    "depgan_g_forward_bf16s", "depgan_debug_tensor_bf16s", "depgan_op_conv2d_bf16s", "depgan_op_deconv2x2_bf16s",
+    "depgan_op_edge_conv_bf16s", "depgan_op_head_bf16s",
 ]
 
 ABI_VERSION = 3          # DEPGAN_ABI_VERSION of the include/depgan.h this binding was written against
@@ -187,6 +189,13 @@ def load():
     lib.depgan_rccl_info.argtypes = [vp, ip, ip, C.POINTER(C.c_long)]
     lib.depgan_rccl_shutdown.argtypes = [vp]
     lib.depgan_debug_tensor.argtypes = [vp, C.c_char_p, vp, C.c_long, ip]
+    # generator forward with bf16 activation storage: bf16 tensors are void pointers + (sB, sY, sX) in elements
+    lib.depgan_g_forward_bf16s.argtypes = [vp, vp, vp, vp, i]
+    lib.depgan_debug_tensor_bf16s.argtypes = [vp, C.c_char_p, vp, L, ip]
+    lib.depgan_op_conv2d_bf16s.argtypes = [vp, L, L, L] + [vp] * 6 + [i] + [vp, L, L, L] * 2 + [vp] + [i] * 7 + [vp]
+    lib.depgan_op_deconv2x2_bf16s.argtypes = [vp, L, L, L] + [vp] * 4 + [vp, L, L, L] + [i] * 6 + [vp]
+    lib.depgan_op_edge_conv_bf16s.argtypes = [vp] * 5 + [vp, L, L, L] + [i] * 6 + [vp]
+    lib.depgan_op_head_bf16s.argtypes = [vp] * 4 + [L, i, i, vp]
     _lib = lib
     return lib
 

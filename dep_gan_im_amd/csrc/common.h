@@ -5,6 +5,8 @@
 // kernel serves plain tensors, channel slices of a concat buffer (reference
 // concatenate() at GT:450/465/479 is never materialised twice) and the 2x
 // strided pixel grids of the 2x2/stride-2 transposed convolution (GT:308).
+// The one exception: the opt-in generator forward with bf16 activation storage
+// (bf16s.h) keeps its inter-layer activations as NHWC bf16 behind a TViewH.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -35,6 +37,34 @@ static inline TView make_view_slice(float* p, int H, int W, int Ctot, int c0) {
 }
 static inline TView null_view() {
   TView v;
+  v.p = nullptr;
+  v.sB = v.sY = v.sX = 0;
+  return v;
+}
+
+// bf16 activation storage (generator forward of a bf16_mfma context, bf16s.h): the same three strides, counted in
+// ELEMENTS of 2 bytes; channel stride 1.  A second type next to TView, so that no fp32 call site changes.
+struct TViewH {
+  __bf16* p;
+  long sB, sY, sX;  // strides in bf16 elements; channel stride is 1
+};
+
+static inline TViewH make_view_h(__bf16* p, int H, int W, int C) {
+  TViewH v;
+  v.p = p;
+  v.sX = C;
+  v.sY = (long)W * C;
+  v.sB = (long)H * W * C;
+  return v;
+}
+// channel slice [c0, ...) of a tensor with Ctot channels
+static inline TViewH make_view_slice_h(__bf16* p, int H, int W, int Ctot, int c0) {
+  TViewH v = make_view_h(p, H, W, Ctot);
+  v.p = p + c0;
+  return v;
+}
+static inline TViewH null_view_h() {
+  TViewH v;
   v.p = nullptr;
   v.sB = v.sY = v.sX = 0;
   return v;

@@ -1,0 +1,509 @@
+// Generator forward with bf16 activation STORAGE (bf16s.h): bf16-in / bf16-out implicit GEMM on
+// v_mfma_f32_32x32x16_bf16, the fp32-in edge layer, the bf16-in head and the widening copy.
+//
+// The convolution starts from igemm_bf16_kernel<KS, TAPG> (igemm_bf16.hip): same tile (16 x 16 pixels x 32 output
+// channels per workgroup), same LDS image (80-byte rows), same XCD-aware item order, same packed panels, same K order
+// (chunk, tap, 16-channel sub-chunk) -- so its result is RNE_bf16 of what that kernel computes on the widened operands,
+// bit for bit (tests/test_gpu_bf16_store.py pins it).  What differs:
+//   * the halo tile is fetched as 16-byte pieces of 8 bf16 (half the load instructions of the fp32-input kernel for the
+//     same pixels) and copied to LDS as it is: the rounding happened when the producer stored it;
+//   * the epilogue is its own, smaller text: affine, FiLM, ReLU, bf16 residual, bf16 store, optional fused bf16 pool.
+//     A pixel's 32 channels are 64 bytes = 4 lanes x 16 bytes, so a wave covers a 16-pixel row per pass and its 4 x 16
+//     block in four passes of 16-byte stores (8-byte stores would double the issue-bound store tail).
+#include <stdlib.h>
+
+#include "bf16s.h"
+#include "epilogue.h"
+
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+typedef float f32x8 __attribute__((ext_vector_type(8), aligned(16)));   // loaded from 16-byte aligned tables
+typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+typedef int i32x4 __attribute__((ext_vector_type(4)));
+
+template <int KS, int TAPG>
+__global__ __launch_bounds__(256, 2) void igemm_bf16s_kernel(const ConvArgsH a) {
+  constexpr int NT = 32, MT = 2, CK = 32;
+  constexpr int PAD = KS / 2;
+  constexpr int TW = 16 + KS - 1;
+  constexpr int PIXT = TW * TW;
+  constexpr int NTAPS = KS * KS;
+  constexpr int NG = NTAPS / TAPG;
+  constexpr int ROWB = 80;   // bytes per LDS row: 32 bf16 + 16 bytes of padding, as igemm_bf16_kernel
+  constexpr int XV = CK / 8;  // 16-byte pieces (8 bf16) of one pixel's chunk in global memory
+  constexpr int XTOT = PIXT * XV;
+  constexpr int XPIECES = (XTOT + 255) / 256;
+  constexpr int WV = CK / 8;  // 16-byte pieces of one packed weight row
+  constexpr int WTOT = TAPG * NT * WV;
+  constexpr int WPIECES = (WTOT + 255) / 256;
+  static_assert(NTAPS % TAPG == 0, "tap grouping");
+  typedef f32x16 acc_t;
+
+  extern __shared__ __attribute__((aligned(16))) float smem[];
+  char* xs = reinterpret_cast<char*>(smem);      // [PIXT][ROWB]
+  char* ws = xs + PIXT * ROWB;                   // [TAPG][NT][ROWB]
+
+  const int tid = threadIdx.x;
+  const int tilesX = (a.W + 15) >> 4, tilesY = (a.H + 15) >> 4;
+  // work item -> (pixel tile, channel tile): the XCD-aware order of igemm_conv.hip
+  const unsigned nNTall = (unsigned)a.lgy, nPix = (unsigned)a.lgx;
+  const unsigned id = blockIdx.x;
+  int t, ntile;
+  if ((nPix & 7u) == 0) {
+    const unsigned x = id & 7u, sl = id >> 3;
+    ntile = (int)(sl % nNTall);
+    t = (int)(x * (nPix >> 3) + sl / nNTall);
+  } else {
+    t = (int)(id % nPix);
+    ntile = (int)(id / nPix);
+  }
+  const int tx0 = (t % tilesX) * 16;
+  t /= tilesX;
+  const int ty0 = (t % tilesY) * 16;
+  const int b = t / tilesY;
+  const int ngrp = a.groups > 1 ? a.groups : 1;
+  const int nNTg = (int)nNTall / ngrp;
+  const int grp = ntile / nNTg;
+  ntile -= grp * nNTg;
+  const __bf16* wbase = reinterpret_cast<const __bf16*>(a.groups > 1 ? a.w_group[grp] : a.w);
+  const long out_goff = a.groups > 1 ? a.out_group_off[grp] : 0;
+  const int n0 = ntile * NT;
+  const int nCC = (a.Cin + CK - 1) / CK;
+  const int NS = nCC * NG;
+  const __bf16* inb = a.in.p + (long)b * a.in.sB;
+
+  u32x4 xr[XPIECES];
+  u32x4 wr[WPIECES];
+  auto prefetch = [&](int s) {
+    const int cc = s / NG, tg = s - cc * NG;
+    if (tg == 0) {
+#pragma unroll
+      for (int i = 0; i < XPIECES; ++i) {
+        const int q = tid + i * 256;
+        u32x4 v = {0u, 0u, 0u, 0u};
+        if (q < XTOT) {
+          const int pix = q / XV, part = q - pix * XV;
+          const int ly = pix / TW, lx = pix - ly * TW;
+          const int iy = ty0 + ly - PAD, ix = tx0 + lx - PAD;
+          const int c = cc * CK + part * 8;
+          // Cin is a multiple of 8 (launcher): a piece is inside the channels or outside, never across the end
+          if (iy >= 0 && iy < a.H && ix >= 0 && ix < a.W && c < a.Cin)
+            v = *reinterpret_cast<const u32x4*>(inb + (long)iy * a.in.sY + (long)ix * a.in.sX + c);
+        }
+        xr[i] = v;
+      }
+    }
+    const __bf16* wsrc = wbase + ((size_t)((size_t)ntile * nCC + cc) * NTAPS + (size_t)tg * TAPG) * (NT * CK);
+#pragma unroll
+    for (int i = 0; i < WPIECES; ++i) {
+      const int q = tid + i * 256;
+      u32x4 v = {0u, 0u, 0u, 0u};
+      if (q < WTOT) v = *reinterpret_cast<const u32x4*>(wsrc + (size_t)q * 8);
+      wr[i] = v;
+    }
+  };
+  auto commit = [&](int s) {
+    const int tg = s % NG;
+    if (tg == 0) {
+#pragma unroll
+      for (int i = 0; i < XPIECES; ++i) {
+        const int q = tid + i * 256;
+        if (q < XTOT) {
+          const int pix = q / XV, part = q - pix * XV;
+          *reinterpret_cast<u32x4*>(xs + pix * ROWB + part * 16) = xr[i];   // a copy: the operand is bf16 already
+        }
+      }
+    }
+#pragma unroll
+    for (int i = 0; i < WPIECES; ++i) {
+      const int q = tid + i * 256;
+      if (q < WTOT) {
+        const int row = q / WV, part = q - row * WV;
+        *reinterpret_cast<u32x4*>(ws + row * ROWB + part * 16) = wr[i];
+      }
+    }
+  };
+
+  const int lane = tid & 63, wv = tid >> 6;
+  const int r = lane & 31, h = lane >> 5;   // h: which 8 of the 16 k-values of an MFMA this lane carries
+  int apix[MT];
+#pragma unroll
+  for (int mt = 0; mt < MT; ++mt) {
+    const int py = 4 * wv + 2 * mt + (r >> 4), px = r & 15;
+    apix[mt] = (py * TW + px) * ROWB + 16 * h;
+  }
+  const int boff = r * ROWB + 16 * h;
+
+  acc_t acc[MT];
+#pragma unroll
+  for (int mt = 0; mt < MT; ++mt)
+#pragma unroll
+    for (int j = 0; j < 16; ++j) acc[mt][j] = 0.f;
+
+  prefetch(0);
+  for (int s = 0; s < NS; ++s) {
+    __syncthreads();
+    commit(s);
+    __syncthreads();
+    if (s + 1 < NS) prefetch(s + 1);
+    const int tg = s % NG;
+#pragma unroll
+    for (int tl = 0; tl < TAPG; ++tl) {
+      const int tap = (TAPG == NTAPS) ? tl : (tg * TAPG + tl);
+      const int ty = tap / KS, tx = tap - ty * KS;
+      const int tapoff = (ty * TW + tx) * ROWB;
+#pragma unroll
+      for (int sub = 0; sub < CK / 16; ++sub) {
+        const bf16x8 bw = *reinterpret_cast<const bf16x8*>(ws + tl * (NT * ROWB) + boff + 32 * sub);
+#pragma unroll
+        for (int mt = 0; mt < MT; ++mt) {
+          const bf16x8 ax = *reinterpret_cast<const bf16x8*>(xs + apix[mt] + tapoff + 32 * sub);
+          // weight fragment first: D[channel][pixel]
+          acc[mt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(bw, ax, acc[mt], 0, 0, 0);
+        }
+      }
+    }
+  }
+
+  // ---- epilogue ----
+  // As igemm_epilogue.inc: each wave's 64 x 32 tile goes through LDS (rows of NT + 4 floats) so that a lane owns
+  // consecutive channels of one pixel; here 8 of them = 16 bytes of bf16, 4 lanes per pixel, 16 pixels (one row of the
+  // wave's 4 x 16 block) per pass.  Per view one buffer descriptor on a 64-bit base at pixel (oyw, tx0) of sample b, a
+  // per-lane 32-bit byte offset computed once and a scalar byte offset per pass: offsets stay inside four image rows.
+  __syncthreads();   // every wave is done with its fragment reads; the tile region is free
+  constexpr int CP = NT + 4;
+  float* es = smem + wv * (64 * CP);
+#pragma unroll
+  for (int mt = 0; mt < MT; ++mt)
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+      f32x4 q4;
+#pragma unroll
+      for (int k = 0; k < 4; ++k) q4[k] = acc[mt][4 * g + k];
+      *reinterpret_cast<f32x4*>(es + (32 * mt + r) * CP + 8 * g + 4 * h) = q4;
+    }
+  const int c8 = (lane & 3) * 8, pl0 = lane >> 2;
+  const int co = n0 + c8;   // < Cout: Cout is a multiple of 32 (launcher)
+  const int wvu = __builtin_amdgcn_readfirstlane(wv);
+  const EpilogueH& e = a.ep;
+  const bool affine = e.scale != nullptr, film = e.film_mul != nullptr, relu = e.relu != 0;
+  const bool has_bias = e.bias != nullptr, has_res = e.res.p != nullptr, has_pool = e.pool.p != nullptr;
+  const int oyw = ty0 + 4 * wvu;
+  const bool full = (ty0 + 16 <= a.H) && (tx0 + 16 <= a.W);
+
+  f32x8 sc8, sh8, fm8, fa8;
+#pragma unroll
+  for (int k = 0; k < 8; ++k) { sc8[k] = 1.f; sh8[k] = 0.f; fm8[k] = 1.f; fa8[k] = 0.f; }
+  if (affine) {
+    sc8 = *reinterpret_cast<const f32x8*>(e.scale + co);
+    sh8 = *reinterpret_cast<const f32x8*>(e.shift + co);
+  }
+  if (has_bias) {
+    const f32x8 bias8 = *reinterpret_cast<const f32x8*>(e.bias + co);
+    // (acc + bias) s + t as ONE fused multiply-add per value; the constant bias s + t is formed once per item
+#pragma unroll
+    for (int k = 0; k < 8; ++k) sh8[k] = fmaf(bias8[k], sc8[k], sh8[k]);
+  }
+  if (film) {
+    fm8 = *reinterpret_cast<const f32x8*>(e.film_mul + (long)b * e.film_ld + co);
+    fa8 = *reinterpret_cast<const f32x8*>(e.film_add + (long)b * e.film_ld + co);
+  }
+  auto voff = [&](const TViewH& v, int y, int x) { return (long)b * v.sB + (long)y * v.sY + (long)x * v.sX; };
+  auto mk = [&](const __bf16* p) {
+    // the descriptor must be wave-uniform: the pointer depends on the wave index
+    const unsigned long long u = (unsigned long long)p;
+    const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)u), hi = __builtin_amdgcn_readfirstlane((unsigned)(u >> 32));
+    return __builtin_amdgcn_make_buffer_rsrc((void*)(((unsigned long long)hi << 32) | lo), 0, 0x7FFFFFFF, 0x00020000);
+  };
+  const int lo_out = 2 * (pl0 * (int)a.out.sX + co);
+  const int lo_res = has_res ? 2 * (pl0 * (int)e.res.sX + co) : 0;
+  const int lo_pool = has_pool ? 2 * ((pl0 >> 1) * (int)e.pool.sX + co) : 0;
+  const __amdgpu_buffer_rsrc_t r_out = mk(a.out.p + out_goff + voff(a.out, oyw, tx0));
+  const __amdgpu_buffer_rsrc_t r_res = mk(has_res ? e.res.p + voff(e.res, oyw, tx0) : a.out.p);
+  const __amdgpu_buffer_rsrc_t r_pool = mk(has_pool ? e.pool.p + voff(e.pool, oyw >> 1, tx0 >> 1) : a.out.p);
+  const int sY_out = 2 * (int)a.out.sY, sY_res = 2 * (int)e.res.sY, sY_pool = 2 * (int)e.pool.sY;
+  f32x8 vrow;
+#pragma unroll
+  for (int k = 0; k < 8; ++k) vrow[k] = 0.f;
+#pragma unroll
+  for (int p = 0; p < 4; ++p) {
+    // pass p = row p of the wave's 4 x 16 block: the two rows of a 2x2 pool window are consecutive passes, its two
+    // columns 4 lanes apart
+    const bool ok = full || (oyw + p < a.H && tx0 + pl0 < a.W);
+    const f32x4 v0 = *reinterpret_cast<const f32x4*>(es + (p * 16 + pl0) * CP + c8);
+    const f32x4 v1 = *reinterpret_cast<const f32x4*>(es + (p * 16 + pl0) * CP + c8 + 4);
+    f32x8 v;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) { v[k] = v0[k]; v[4 + k] = v1[k]; }
+#pragma unroll
+    for (int k = 0; k < 8; ++k) v[k] = fmaf(v[k], sc8[k], sh8[k]);
+    if (film) {
+#pragma unroll
+      for (int k = 0; k < 8; ++k) v[k] = film_preact(v[k], fm8[k], fa8[k]);
+    }
+    if (relu) {
+#pragma unroll
+      for (int k = 0; k < 8; ++k) v[k] = dg_vmax(v[k], 0.f);
+    }
+    if (has_res) {
+      i32x4 rr = {0, 0, 0, 0};
+      if (ok) rr = __builtin_amdgcn_raw_buffer_load_b128(r_res, lo_res, p * sY_res, 0);
+      const f32x8 rf = __builtin_convertvector(__builtin_bit_cast(bf16x8, rr), f32x8);   // widening: exact
+#pragma unroll
+      for (int k = 0; k < 8; ++k) v[k] += rf[k];
+    }
+    // the one rounding of the storage contract: fp32 -> bf16, round to nearest even (v_cvt_pk_bf16_f32)
+    const bf16x8 o = __builtin_convertvector(v, bf16x8);
+    if (ok) __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(i32x4, o), r_out, lo_out, p * sY_out, 0);
+    if (has_pool) {
+      const f32x8 sv = __builtin_convertvector(o, f32x8);   // the STORED values
+      if ((p & 1) == 0) {
+        vrow = sv;
+      } else {
+        f32x8 m;
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+          const float t2 = dg_vmax(vrow[k], sv[k]);
+          m[k] = dg_vmax(t2, __shfl_xor(t2, 4, 64));
+        }
+        const bf16x8 mo = __builtin_convertvector(m, bf16x8);   // exact: m is one of the stored values
+        if (ok && (pl0 & 1) == 0)
+          __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(i32x4, mo), r_pool, lo_pool, (p >> 1) * sY_pool, 0);
+      }
+    }
+  }
+}
+
+template <int KS, int TAPG>
+static int launch_bf16s(const ConvArgsH& a, hipStream_t st) {
+  constexpr int TW = 16 + KS - 1;
+  constexpr size_t lds_k = (size_t)(TW * TW + TAPG * 32) * 80;
+  constexpr size_t lds_e = (size_t)4 * 64 * (32 + 4) * sizeof(float);
+  constexpr size_t lds = lds_k > lds_e ? lds_k : lds_e;
+  static DgOncePerDevice once;
+  if (once.need()) {
+    HIPCHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&igemm_bf16s_kernel<KS, TAPG>),
+                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  }
+  ConvArgsH b = a;
+  b.lgx = cdiv(a.W, 16) * cdiv(a.H, 16) * a.B;
+  b.lgy = cdiv(a.Cout, 32) * (a.groups > 1 ? a.groups : 1);
+  const long total = (long)b.lgx * b.lgy;
+  hipLaunchKernelGGL((igemm_bf16s_kernel<KS, TAPG>), dim3((unsigned)total), dim3(256), lds, st, b);
+  HIPCHECK(hipGetLastError());
+  return DG_OK;
+}
+
+static bool aligned16_h(const TViewH& v) {
+  return !v.p || (!(v.sX % 8) && !(v.sY % 8) && !(v.sB % 8) && !(((uintptr_t)v.p) & 15));
+}
+// the epilogue's per-lane and per-pass byte offsets (up to four rows and sixteen pixels from the wave's origin) are ints
+static bool offsets_fit(const TViewH& v) {
+  return !v.p || (v.sX > 0 && v.sY > 0 && v.sB >= 0 && 2 * (4 * v.sY + 16 * v.sX + 32) < 0x7FFFFFFFL);
+}
+
+const char* dg_conv_bf16s_name(int KS) { return KS == 3 ? "igemm_bf16s_kernel<3, 9>" : "igemm_bf16s_kernel<1, 1>"; }
+
+int dg_conv_bf16s(int KS, const ConvArgsH& a, hipStream_t st) {
+  if (KS != 1 && KS != 3) { dg_set_error("dg_conv_bf16s: kernel size %d (1 or 3)", KS); return DG_ERR_UNSUPPORTED; }
+  if (!a.in.p || !a.out.p || a.B < 1 || a.H < 1 || a.W < 1) { dg_set_error("dg_conv_bf16s: bad argument"); return DG_ERR_ARG; }
+  if (a.Cin < 8 || (a.Cin % 8) || a.Cout < 32 || (a.Cout % 32)) {
+    dg_set_error("dg_conv_bf16s: %d -> %d channels (Cin a multiple of 8, Cout a multiple of 32)", a.Cin, a.Cout);
+    return DG_ERR_UNSUPPORTED;
+  }
+  const int ng = a.groups > 1 ? a.groups : 1;
+  if (ng != 1 && ng != 4) { dg_set_error("dg_conv_bf16s: groups must be 0, 1 or 4"); return DG_ERR_ARG; }
+  bool al = aligned16_h(a.in) && aligned16_h(a.out) && aligned16_h(a.ep.res) && aligned16_h(a.ep.pool);
+  for (int g = 0; g < ng && ng > 1; ++g) {
+    if (!a.w_group[g]) { dg_set_error("dg_conv_bf16s: null weight panel of group %d", g); return DG_ERR_ARG; }
+    al = al && !(a.out_group_off[g] % 8);
+  }
+  if (ng == 1 && !a.w) { dg_set_error("dg_conv_bf16s: null weight panel"); return DG_ERR_ARG; }
+  if (!al) { dg_set_error("dg_conv_bf16s: every view must be 16-byte aligned (pointer, strides in multiples of 8 elements)"); return DG_ERR_ARG; }
+  if (!offsets_fit(a.in) || !offsets_fit(a.out) || !offsets_fit(a.ep.res) || !offsets_fit(a.ep.pool)) {
+    dg_set_error("dg_conv_bf16s: view strides out of range");
+    return DG_ERR_ARG;
+  }
+  if (a.ep.film_mul && (!a.ep.film_add || (a.ep.film_ld % 4))) { dg_set_error("dg_conv_bf16s: FiLM needs both vectors, ld a multiple of 4"); return DG_ERR_ARG; }
+  if ((a.ep.scale != nullptr) != (a.ep.shift != nullptr)) { dg_set_error("dg_conv_bf16s: scale and shift come together"); return DG_ERR_ARG; }
+  if (a.ep.pool.p && ((a.H | a.W) & 1)) { dg_set_error("dg_conv_bf16s: the fused pool needs even H and W"); return DG_ERR_ARG; }
+  const long total = (long)cdiv(a.W, 16) * cdiv(a.H, 16) * a.B * cdiv(a.Cout, 32) * ng;
+  if (total > 0x7FFFFFFFL) { dg_set_error("dg_conv_bf16s: %ld work items", total); return DG_ERR_UNSUPPORTED; }
+  return KS == 3 ? launch_bf16s<3, 9>(a, st) : launch_bf16s<1, 1>(a, st);
+}
+
+// ---------------------------------------------------------------------------
+// gen_0: Cin = 1 or 2 -> up to 32 channels, 3x3, fp32 in, bf16 out.  HBM-bound (the output write is the traffic that
+// matters) VALU kernel after conv_cin12_kernel (direct.hip): thread = 4 consecutive pixels x 8 consecutive output
+// channels, so that each store is 16 bytes of bf16 and the 4 lanes of a pixel fill its 64 bytes.  Block = 16 x 16 pixels.
+// ---------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void edge_conv_bf16s_kernel(const EdgeArgsH a) {
+  constexpr int KS = 3, PAD = 1, ROWS = 16;
+  constexpr int TWX = 16 + KS - 1, TWY = ROWS + KS - 1;
+  constexpr int RS = 24;   // LDS row stride (floats): 18 used + read slack
+  constexpr int CT = 32;
+  __shared__ __attribute__((aligned(16))) float xs[2 * TWY * RS];
+  __shared__ __attribute__((aligned(16))) float ws[2 * KS * KS * CT];
+
+  const int tid = threadIdx.x;
+  const int tilesX = (a.W + 15) >> 4, tilesY = (a.H + ROWS - 1) / ROWS;
+  int t = blockIdx.x;
+  const int tx0 = (t % tilesX) * 16;
+  t /= tilesX;
+  const int ty0 = (t % tilesY) * ROWS;
+  const int b = t / tilesY;
+  const int g = tid & 3, pg = tid >> 2;      // channel group of 8, pixel group
+  const int qx = (pg & 3) * 4, py = pg >> 2;
+  const float* inb = a.in + (long)b * a.H * a.W * a.Cin;
+
+  for (int q = tid; q < a.Cin * TWY * RS; q += 256) {
+    const int lx = q % RS, ly = (q / RS) % TWY, c = q / (RS * TWY);
+    const int iy = ty0 + ly - PAD, ix = tx0 + lx - PAD;
+    float v = 0.f;
+    if (lx < TWX && iy >= 0 && iy < a.H && ix >= 0 && ix < a.W) v = inb[((long)iy * a.W + ix) * a.Cin + c];
+    xs[q] = v;
+  }
+  for (int q = tid; q < a.Cin * KS * KS * CT; q += 256) {
+    const int n = q % CT, tap = (q / CT) % (KS * KS), c = q / (CT * KS * KS);
+    ws[q] = (n < a.Cout) ? a.w[((long)tap * a.Cin + c) * a.Cout + n] : 0.f;
+  }
+  __syncthreads();
+
+  f32x8 acc[4];
+#pragma unroll
+  for (int j = 0; j < 4; ++j)
+#pragma unroll
+    for (int k = 0; k < 8; ++k) acc[j][k] = 0.f;
+  // channel, tap row, tap column: a fixed order
+  for (int c = 0; c < a.Cin; ++c) {
+#pragma unroll
+    for (int ty = 0; ty < KS; ++ty) {
+      const float* row = xs + (c * TWY + py + ty) * RS + qx;
+      const f32x4 x0 = *reinterpret_cast<const f32x4*>(row);
+      const f32x4 x1 = *reinterpret_cast<const f32x4*>(row + 4);
+      const float xv[8] = {x0[0], x0[1], x0[2], x0[3], x1[0], x1[1], x1[2], x1[3]};
+#pragma unroll
+      for (int tx = 0; tx < KS; ++tx) {
+        const f32x8 w8 = *reinterpret_cast<const f32x8*>(ws + ((c * KS + ty) * KS + tx) * CT + 8 * g);
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+#pragma unroll
+          for (int k = 0; k < 8; ++k) acc[j][k] = fmaf(xv[j + tx], w8[k], acc[j][k]);
+      }
+    }
+  }
+  const int co = 8 * g;
+  const int oy = ty0 + py;
+  if (co < a.Cout && oy < a.H) {
+    f32x8 sc8, sh8;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) { sc8[k] = 1.f; sh8[k] = 0.f; }
+    if (a.scale) {
+      sc8 = *reinterpret_cast<const f32x8*>(a.scale + co);
+      sh8 = *reinterpret_cast<const f32x8*>(a.shift + co);
+    }
+    if (a.bias) {
+      const f32x8 bias8 = *reinterpret_cast<const f32x8*>(a.bias + co);
+#pragma unroll
+      for (int k = 0; k < 8; ++k) sh8[k] = fmaf(bias8[k], sc8[k], sh8[k]);
+    }
+    __bf16* orow = a.out.p + (long)b * a.out.sB + (long)oy * a.out.sY + co;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int ox = tx0 + qx + j;
+      if (ox >= a.W) continue;
+      f32x8 v;
+#pragma unroll
+      for (int k = 0; k < 8; ++k) {
+        v[k] = fmaf(acc[j][k], sc8[k], sh8[k]);
+        if (a.relu) v[k] = dg_vmax(v[k], 0.f);
+      }
+      *reinterpret_cast<bf16x8*>(orow + (long)ox * a.out.sX) = __builtin_convertvector(v, bf16x8);   // RNE
+    }
+  }
+}
+
+int dg_edge_conv_bf16s(const EdgeArgsH& a, hipStream_t st) {
+  if (!a.in || !a.w || !a.out.p || a.B < 1 || a.H < 1 || a.W < 1) { dg_set_error("dg_edge_conv_bf16s: bad argument"); return DG_ERR_ARG; }
+  if (a.Cin < 1 || a.Cin > 2 || a.Cout < 8 || a.Cout > 32 || (a.Cout % 8)) {
+    dg_set_error("dg_edge_conv_bf16s: %d -> %d channels (Cin 1 or 2, Cout 8, 16, 24 or 32)", a.Cin, a.Cout);
+    return DG_ERR_UNSUPPORTED;
+  }
+  if ((a.scale != nullptr) != (a.shift != nullptr)) { dg_set_error("dg_edge_conv_bf16s: scale and shift come together"); return DG_ERR_ARG; }
+  if (!aligned16_h(a.out)) { dg_set_error("dg_edge_conv_bf16s: the output view must be 16-byte aligned"); return DG_ERR_ARG; }
+  const long blocks = (long)cdiv(a.W, 16) * cdiv(a.H, 16) * a.B;
+  if (blocks > 0x7FFFFFFFL) { dg_set_error("dg_edge_conv_bf16s: %ld blocks", blocks); return DG_ERR_UNSUPPORTED; }
+  hipLaunchKernelGGL(edge_conv_bf16s_kernel, dim3((unsigned)blocks), dim3(256), 0, st, a);
+  HIPCHECK(hipGetLastError());
+  return DG_OK;
+}
+
+// ---------------------------------------------------------------------------
+// head: 1x1 convolution to one channel (+ tanh), bf16 in, fp32 out; C / 8 lanes per pixel, 16 bytes each
+// ---------------------------------------------------------------------------
+__global__ void head_bf16s_kernel(const __bf16* __restrict__ a, long ld, const float* __restrict__ w,
+                                  const float* __restrict__ b, float* __restrict__ out, long P, int LP, int tanh_act) {
+  const long t = blockIdx.x * (long)blockDim.x + threadIdx.x;
+  const long p = t / LP;
+  const int part = (int)(t % LP);
+  float v = 0.f;
+  if (p < P) {
+    const f32x8 av = __builtin_convertvector(*reinterpret_cast<const bf16x8*>(a + p * ld + part * 8), f32x8);
+    const f32x8 wv = *reinterpret_cast<const f32x8*>(w + part * 8);
+    v = av[0] * wv[0];
+#pragma unroll
+    for (int k = 1; k < 8; ++k) v = fmaf(av[k], wv[k], v);
+  }
+  for (int o = LP >> 1; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  if (p < P && part == 0) {
+    v += b[0];
+    out[p] = tanh_act ? tanhf(v) : v;
+  }
+}
+
+int dg_head_bf16s(const __bf16* a, long ld, const float* w, const float* b, float* out, long P, int C, int tanh_act,
+                  hipStream_t st) {
+  if (!a || !w || !b || !out || P < 1) { dg_set_error("dg_head_bf16s: bad argument"); return DG_ERR_ARG; }
+  const int LP = C / 8;
+  if (C < 8 || (C % 8) || LP > 64 || (LP & (LP - 1))) { dg_set_error("dg_head_bf16s: C/8 must be a power of two <= 64"); return DG_ERR_ARG; }
+  if (ld < C || (ld % 8) || (((uintptr_t)a) & 15) || (((uintptr_t)w) & 15)) { dg_set_error("dg_head_bf16s: the input must be 16-byte aligned, ld a multiple of 8"); return DG_ERR_ARG; }
+  const long blocks = (P * LP + 255) / 256;
+  if (blocks > 0x7FFFFFFFL) { dg_set_error("dg_head_bf16s: %ld blocks", blocks); return DG_ERR_UNSUPPORTED; }
+  hipLaunchKernelGGL(head_bf16s_kernel, dim3((unsigned)blocks), dim3(256), 0, st, a, ld, w, b, out, P, LP, tanh_act);
+  HIPCHECK(hipGetLastError());
+  return DG_OK;
+}
+
+// ---------------------------------------------------------------------------
+// bf16 view -> dense fp32 (exact), 8 channels per thread where the view allows, else one
+// ---------------------------------------------------------------------------
+__global__ void widen_bf16_kernel(TViewH s, long npix, int H, int W, int C, int vec, float* __restrict__ dst) {
+  const int per = vec ? C / 8 : C;
+  const long total = npix * per;
+  for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+    const long pix = i / per;
+    const int part = (int)(i - pix * per);
+    const int x = (int)(pix % W);
+    const long t = pix / W;
+    const int y = (int)(t % H);
+    const long b = t / H;
+    const __bf16* src = s.p + b * s.sB + (long)y * s.sY + (long)x * s.sX;
+    if (vec) {
+      const f32x8 v = __builtin_convertvector(*reinterpret_cast<const bf16x8*>(src + part * 8), f32x8);
+      *reinterpret_cast<f32x8*>(dst + pix * C + part * 8) = v;
+    } else {
+      dst[pix * C + part] = (float)src[part];
+    }
+  }
+}
+
+int dg_widen_bf16(TViewH src, int N, int H, int W, int C, float* dst, hipStream_t st) {
+  if (!src.p || !dst || N < 1 || H < 1 || W < 1 || C < 1) { dg_set_error("dg_widen_bf16: bad argument"); return DG_ERR_ARG; }
+  const int vec = (C % 8 == 0) && aligned16_h(src) && !(((uintptr_t)dst) & 31);
+  const long npix = (long)N * H * W;
+  const long total = npix * (vec ? C / 8 : C);
+  long blocks = (total + 255) / 256;
+  if (blocks > 65536) blocks = 65536;
+  hipLaunchKernelGGL(widen_bf16_kernel, dim3((unsigned)blocks), dim3(256), 0, st, src, npix, H, W, C, vec, dst);
+  HIPCHECK(hipGetLastError());
+  return DG_OK;
+}

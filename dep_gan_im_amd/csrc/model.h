@@ -9,6 +9,7 @@
 
 #include "../../include/depgan.h"
 #include "common.h"
+#include "bf16s.h"
 #include "deconv_fwd.h"
 #include "noise.h"
 #include "ops.h"
@@ -194,6 +195,12 @@ struct depgan_ctx {
   bool dbg_capture = false;
   float* dbg_mixed[11] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
   bool dbg_mixed_valid = false;
+
+  // ---- bf16 activation storage of the generator forward (model_bf16s.hip; bf16_mfma contexts) ----
+  // one view per generator layer (concat buffers shared as in the fp32 set), allocated by the first
+  // depgan_g_forward_bf16s and freed with the context; the fp32 set above is not touched by that path
+  std::vector<TViewH> h_in, h_out;
+  bool h_ready = false, h_valid = false;
 
   // ---- profiling ----
   bool prof_on = false;

@@ -1,0 +1,336 @@
+// Generator forward (Model.predict, GT:846-859; the evaluation's ten-noise mean, GE:616-628) of a bf16_mfma context
+// with every inter-layer activation STORED as bf16 (bf16s.h): the drivers, the debug surface and
+// the operator entries of the kernels in igemm_bf16s.hip.  The fp32 path (g_forward in model.hip) and its buffers are
+// not touched: this is a second, opt-in walk over the same layer table, the same packed bf16 panels (GLayer::wpf), the
+// same BN affines and the same fp32 noise MLP.
+#include "model.h"
+
+#include <stdio.h>
+#include <string.h>
+
+static TViewH strided2_h(TViewH v, int di, int dj) {   // pixel grid (2i + di, 2j + dj) of a (2H, 2W) view
+  TViewH o = v;
+  o.p = v.p + di * v.sY + dj * v.sX;
+  o.sY = 2 * v.sY;
+  o.sX = 2 * v.sX;
+  return o;
+}
+
+static int halloc(depgan_ctx* c, __bf16** p, size_t elems) {
+  void* q = nullptr;
+  const size_t bytes = (elems ? elems : 8) * sizeof(__bf16);
+  if (hipMalloc(&q, bytes) != hipSuccess) {
+    dg_set_error("depgan_g_forward_bf16s: out of device memory for the bf16 activation buffers (%zu bytes)", bytes);
+    return DG_ERR_HIP;
+  }
+  c->allocs.push_back(q);
+  HIPCHECK(hipMemset(q, 0, bytes));
+  *p = (__bf16*)q;
+  return DG_OK;
+}
+
+// what the context must be for the bf16-storage forward; no HIP call
+static int bf16s_check_ctx(const depgan_ctx* c, const char* who) {
+  if (!c->cfg.bf16_mfma || !c->cfg.bf16_weights || c->cfg.nc_out != 1) {
+    dg_set_error("%s: needs a context created with bf16_mfma = 1 (hence bf16_weights = 1, nc_out = 1); this one has "
+                 "bf16_mfma = %d, bf16_weights = %d, nc_out = %d", who, c->cfg.bf16_mfma, c->cfg.bf16_weights,
+                 c->cfg.nc_out);
+    return DG_ERR_UNSUPPORTED;
+  }
+  for (size_t i = 0; i < c->gl.size(); ++i) {
+    const GLayer& L = c->gl[i];
+    const bool conv = (L.kind == G_CONV && i > 0) || L.kind == G_FILM || L.kind == G_DECONV;
+    if (conv && (L.pf.bf16 != 1 || L.pf.variant < 100 || L.pf.variant >= 200 || !L.wpf[0] || (L.Cin % 8) || (L.Cout % 32))) {
+      dg_set_error("%s: layer %s (%d -> %d) has no bf16 plan; the storage types are not mixed", who, L.name.c_str(),
+                   L.Cin, L.Cout);
+      return DG_ERR_UNSUPPORTED;
+    }
+  }
+  if (c->gl.empty() || c->gl[0].kind != G_CONV || c->gl[0].Cin > 2 || c->gl[0].Cout != 32) {
+    dg_set_error("%s: the edge layer must be nicg -> 32", who);
+    return DG_ERR_UNSUPPORTED;
+  }
+  return DG_OK;
+}
+
+// The bf16 twin of build_generator's activation set: one buffer per layer output; a convolution that feeds a pool
+// writes into the upper channels of its concat buffer, the transposed convolution of the same level into the lower ones
+// (GT:450/465/479: [deconv | skip]).  The pairing is read off the fp32 views, which are laid out the same way.
+static int bf16s_alloc(depgan_ctx* c) {
+  if (c->h_ready) return DG_OK;
+  const int B = c->cfg.batch;
+  const size_t nl = c->gl.size();
+  std::vector<TViewH> hin(nl, null_view_h()), hout(nl, null_view_h());
+  TViewH cur = null_view_h();
+  for (size_t i = 0; i < nl; ++i) {
+    const GLayer& L = c->gl[i];
+    hin[i] = cur;
+    if (L.kind == G_CONV && i + 1 < nl && c->gl[i + 1].kind == G_POOL) {
+      // the skip convolution: find the transposed convolution that shares its concat buffer
+      int dc = -1;
+      for (size_t j = i + 1; j < nl; ++j)
+        if (c->gl[j].kind == G_DECONV && c->gl[j].out.sX == L.out.sX && L.out.p == c->gl[j].out.p + c->gl[j].Cout) dc = (int)j;
+      if (dc < 0) { dg_set_error("depgan_g_forward_bf16s: no concat partner for %s", L.name.c_str()); return DG_ERR_UNSUPPORTED; }
+      const int Ctot = c->gl[dc].Cout + L.Cout;
+      __bf16* p = nullptr;
+      DGCHECK(halloc(c, &p, (size_t)B * L.H * L.W * Ctot));
+      hout[i] = make_view_slice_h(p, L.H, L.W, Ctot, c->gl[dc].Cout);
+      hout[dc] = make_view_slice_h(p, L.H, L.W, Ctot, 0);
+      cur = hout[i];
+    } else if (L.kind == G_CONV || L.kind == G_FILM) {
+      __bf16* p = nullptr;
+      DGCHECK(halloc(c, &p, (size_t)B * L.H * L.W * L.Cout));
+      hout[i] = make_view_h(p, L.H, L.W, L.Cout);
+      cur = hout[i];
+    } else if (L.kind == G_POOL) {
+      __bf16* p = nullptr;
+      DGCHECK(halloc(c, &p, (size_t)B * (L.H / 2) * (L.W / 2) * L.Cout));
+      hout[i] = make_view_h(p, L.H / 2, L.W / 2, L.Cout);
+      cur = hout[i];
+    } else if (L.kind == G_DECONV) {
+      if (!hout[i].p) { dg_set_error("depgan_g_forward_bf16s: %s has no concat buffer", L.name.c_str()); return DG_ERR_UNSUPPORTED; }
+      cur = hout[i];   // slice 0 of the concat buffer = the whole buffer for a consumer that reads all its channels
+    }
+  }
+  c->h_in.swap(hin);
+  c->h_out.swap(hout);
+  c->h_ready = true;
+  return DG_OK;
+}
+
+// algorithmic bytes of one bf16-storage convolution launch: activations at 2 bytes per element, bf16 panels
+static double bf16s_bytes(const ConvArgsH& a, int KS) {
+  const int ng = a.groups > 1 ? a.groups : 1;
+  const double px = 2.0 * a.B * a.H * a.W;
+  return px * a.Cin + ng * (px * a.Cout * (1 + (a.ep.res.p ? 1 : 0) + (a.ep.pool.p ? 0.25 : 0)) + 2.0 * KS * KS * a.Cin * a.Cout);
+}
+
+static int conv_launch_bf16s(depgan_ctx* c, const ConvArgsH& a, int KS) {
+  const int ng = a.groups > 1 ? a.groups : 1;
+  const double fl = 2.0 * a.B * a.H * a.W * (double)a.Cin * a.Cout * KS * KS * ng;
+  char lb[56];
+  snprintf(lb, sizeof(lb), "conv(bf16s) k%d b%d %dx%d %d->%d%s", KS, a.B, a.H, a.W, a.Cin, a.Cout, ng > 1 ? " x4" : "");
+  ProfScope ps(c, 0, fl, lb, bf16s_bytes(a, KS), dg_conv_bf16s_name(KS));
+  return dg_conv_bf16s(KS, a, c->st);
+}
+
+static int g_forward_bf16s(depgan_ctx* c, const float* x, const float* z, float* out, int n) {
+  {
+    ProfScope ps(c, 2, 0.0, "noise mlp fwd");
+    DGCHECK(dg_noise_fwd(c->np, z, c->na, n, c->st));
+  }
+  bool pooled_by_conv = false;
+  for (size_t i = 0; i < c->gl.size(); ++i) {
+    const GLayer& L = c->gl[i];
+    if (L.kind == G_CONV && i == 0) {
+      EdgeArgsH e;
+      memset(&e, 0, sizeof(e));
+      e.in = x; e.w = L.Wt; e.bias = L.b; e.scale = L.s; e.shift = L.t;
+      e.out = c->h_out[i];
+      e.B = n; e.H = L.H; e.W = L.W; e.Cin = L.Cin; e.Cout = L.Cout; e.relu = 1;
+      char lb[56];
+      snprintf(lb, sizeof(lb), "edge conv(bf16s) b%d %dx%d %d->%d", n, L.H, L.W, L.Cin, L.Cout);
+      const double px = (double)n * L.H * L.W;
+      ProfScope ps(c, 2, 2.0 * px * L.Cin * L.Cout * 9, lb, px * (4.0 * L.Cin + 2.0 * L.Cout) + 36.0 * L.Cin * L.Cout);
+      DGCHECK(dg_edge_conv_bf16s(e, c->st));
+      pooled_by_conv = false;
+    } else if (L.kind == G_CONV || L.kind == G_FILM) {
+      ConvArgsH a;
+      memset(&a, 0, sizeof(a));
+      a.in = c->h_in[i];
+      a.out = c->h_out[i];
+      a.w = L.wpf[0];
+      a.B = n; a.H = L.H; a.W = L.W; a.Cin = L.Cin; a.Cout = L.Cout;
+      a.ep.bias = L.b; a.ep.scale = L.s; a.ep.shift = L.t; a.ep.relu = 1;
+      if (L.kind == G_FILM) {
+        a.ep.film_mul = c->na.heads + L.col_mul;
+        a.ep.film_add = c->na.heads + L.col_add;
+        a.ep.film_ld = 1024;
+        a.ep.res = c->h_in[i];
+      }
+      // the 2x2 max-pool that follows (gen_1 / gen_3 / gen_5) rides in this launch's epilogue
+      if (i + 1 < c->gl.size() && c->gl[i + 1].kind == G_POOL && c->gl[i + 1].skip_of == (int)i && !((L.H | L.W) & 1))
+        a.ep.pool = c->h_out[i + 1];
+      pooled_by_conv = a.ep.pool.p != nullptr;
+      DGCHECK(conv_launch_bf16s(c, a, 3));
+    } else if (L.kind == G_POOL) {
+      if (pooled_by_conv && L.skip_of == (int)i - 1) continue;
+      // height and width are multiples of 16 (depgan_create), so every pooled level is even: not reached
+      dg_set_error("depgan_g_forward_bf16s: %s is not covered by the fused pool", L.name.c_str());
+      return DG_ERR_UNSUPPORTED;
+    } else if (L.kind == G_DECONV) {
+      // four 1x1 convolutions of the same input, tap (di, dj) writing the pixel grid (2i + di, 2j + dj): one grouped launch
+      ConvArgsH a;
+      memset(&a, 0, sizeof(a));
+      a.in = c->h_in[i];
+      a.out = strided2_h(c->h_out[i], 0, 0);
+      a.B = n; a.H = L.H; a.W = L.W; a.Cin = L.Cin; a.Cout = L.Cout;
+      a.ep.bias = L.b; a.ep.scale = L.s; a.ep.shift = L.t; a.ep.relu = 1;
+      a.groups = 4;
+      for (int t = 0; t < 4; ++t) {
+        a.w_group[t] = L.wpf[t];
+        a.out_group_off[t] = strided2_h(c->h_out[i], t / 2, t % 2).p - a.out.p;
+      }
+      a.w = L.wpf[0];
+      DGCHECK(conv_launch_bf16s(c, a, 1));
+    } else if (L.kind == G_HEAD) {
+      const TViewH in = c->h_in[i];
+      const long P = (long)n * L.H * L.W;
+      ProfScope ps(c, 2, 2.0 * P * L.Cin, "head fwd(bf16s)", P * (2.0 * L.Cin + 4.0));
+      DGCHECK(dg_head_bf16s(in.p, in.sX, L.Wt, L.b, out, P, L.Cin, 1, c->st));
+    }
+  }
+  return DG_OK;
+}
+
+int depgan_g_forward_bf16s(depgan_ctx* c, const float* x, const float* z, float* out, int n) {
+  if (!c || !x || !z || !out) { dg_set_error("depgan_g_forward_bf16s: null argument"); return DG_ERR_ARG; }
+  DGCHECK(bf16s_check_ctx(c, "depgan_g_forward_bf16s"));
+  if (n < 1 || n > c->cfg.batch) { dg_set_error("depgan_g_forward_bf16s: n must be in [1, batch]"); return DG_ERR_ARG; }
+  DGCHECK(bf16s_alloc(c));
+  c->h_valid = false;
+  DGCHECK(g_forward_bf16s(c, x, z, out, n));
+  c->h_valid = true;
+  return DG_OK;
+}
+
+int depgan_debug_tensor_bf16s(depgan_ctx* c, const char* name, float* host, long cap, int shape[4]) {
+  if (!c || !name || !shape) { dg_set_error("debug_tensor_bf16s: null argument"); return DG_ERR_ARG; }
+  if (host && cap < 1) { dg_set_error("debug_tensor_bf16s: non-positive capacity"); return DG_ERR_ARG; }
+  if (strncmp(name, "g/out/", 6) != 0) {
+    dg_set_error("debug_tensor_bf16s: '%s' is not a g/out/<layer> name", name);
+    return DG_ERR_ARG;
+  }
+  if (!c->h_ready || !c->h_valid) {
+    dg_set_error("debug_tensor_bf16s: no depgan_g_forward_bf16s has run on this context");
+    return DG_ERR_ARG;
+  }
+  const std::string ln(name + 6);
+  for (size_t i = 0; i < c->gl.size(); ++i) {
+    const GLayer& L = c->gl[i];
+    if (L.name != ln) continue;
+    if (L.kind == G_HEAD) {
+      dg_set_error("debug_tensor_bf16s: %s is the fp32 output of depgan_g_forward_bf16s, not a bf16 buffer", name);
+      return DG_ERR_ARG;
+    }
+    const TViewH v = c->h_out[i];
+    const int N = c->cfg.batch, C = L.Cout;
+    const int H = L.kind == G_POOL ? L.H / 2 : (L.kind == G_DECONV ? 2 * L.H : L.H);
+    const int W = L.kind == G_POOL ? L.W / 2 : (L.kind == G_DECONV ? 2 * L.W : L.W);
+    shape[0] = N; shape[1] = H; shape[2] = W; shape[3] = C;
+    if (!host) return DG_OK;
+    const long need = (long)N * H * W * C;
+    if (cap < need) { dg_set_error("debug_tensor_bf16s: %s needs %ld floats, the buffer holds %ld", name, need, cap); return DG_ERR_ARG; }
+    float* tmp = nullptr;
+    HIPCHECK(hipMalloc((void**)&tmp, (size_t)need * sizeof(float)));
+    int rc = dg_widen_bf16(v, N, H, W, C, tmp, c->st);
+    hipError_t e = hipStreamSynchronize(c->st);
+    if (rc == DG_OK && e == hipSuccess) e = hipMemcpy(host, tmp, (size_t)need * sizeof(float), hipMemcpyDeviceToHost);
+    hipFree(tmp);
+    if (rc != DG_OK) return rc;
+    if (e != hipSuccess) { dg_set_error("debug_tensor_bf16s: copy of %s failed: %s", name, hipGetErrorString(e)); return DG_ERR_HIP; }
+    return DG_OK;
+  }
+  dg_set_error("debug_tensor_bf16s: unknown tensor '%s'", name);
+  return DG_ERR_ARG;
+}
+
+// ---- single operators (unit tests): explicit view strides in ELEMENTS, stream last, checks before any HIP call ----
+static TViewH op_view_h(const void* p, long sB, long sY, long sX) {
+  TViewH v;
+  v.p = reinterpret_cast<__bf16*>(const_cast<void*>(p));
+  v.sB = sB; v.sY = sY; v.sX = sX;
+  return v;
+}
+static bool bad_view(const void* p, long sB, long sY, long sX) { return !p || sB < 0 || sY < 1 || sX < 1; }
+
+int depgan_op_conv2d_bf16s(const void* in, long isB, long isY, long isX, const float* w_hwio, const float* bias,
+                           const float* scale, const float* shift, const float* film_mul, const float* film_add,
+                           int film_ld, const void* res, long rsB, long rsY, long rsX, void* out, long osB, long osY,
+                           long osX, void* pool, int B, int H, int W, int Cin, int Cout, int KS, int relu, void* stream) {
+  if (bad_view(in, isB, isY, isX) || bad_view(out, osB, osY, osX) || !w_hwio || B < 1 || H < 1 || W < 1 || Cin < 1 ||
+      Cout < 1 || (res && bad_view(res, rsB, rsY, rsX))) {
+    dg_set_error("op_conv2d_bf16s: null or non-positive argument");
+    return DG_ERR_ARG;
+  }
+  if (KS != 1 && KS != 3) { dg_set_error("op_conv2d_bf16s: KS must be 1 or 3"); return DG_ERR_ARG; }
+  const ConvPlan pl = dg_plan_conv_bf16(KS, Cin, Cout);
+  if (pl.bf16 != 1 || (Cin % 8)) { dg_set_error("op_conv2d_bf16s: the bf16 MFMA kernel does not cover %d -> %d", Cin, Cout); return DG_ERR_UNSUPPORTED; }
+  hipStream_t st = (hipStream_t)stream;
+  ConvArgsH a;
+  memset(&a, 0, sizeof(a));
+  a.in = op_view_h(in, isB, isY, isX);
+  a.out = op_view_h(out, osB, osY, osX);
+  a.B = B; a.H = H; a.W = W; a.Cin = Cin; a.Cout = Cout;
+  a.ep.bias = bias; a.ep.scale = scale; a.ep.shift = shift;
+  a.ep.film_mul = film_mul; a.ep.film_add = film_add; a.ep.film_ld = film_ld;
+  a.ep.res = res ? op_view_h(res, rsB, rsY, rsX) : null_view_h();
+  a.ep.relu = relu;
+  a.ep.pool = pool ? make_view_h(reinterpret_cast<__bf16*>(pool), H / 2, W / 2, Cout) : null_view_h();
+  float* wp = nullptr;
+  HIPCHECK(hipMalloc((void**)&wp, pl.packedFloats * sizeof(float)));
+  int rc = dg_pack_weights(pl, w_hwio, Cin, Cout, 0, 0, 0, nullptr, wp, st);
+  a.w = wp;
+  if (rc == DG_OK) rc = dg_conv_bf16s(KS, a, st);
+  hipStreamSynchronize(st);
+  hipFree(wp);
+  return rc;
+}
+
+int depgan_op_deconv2x2_bf16s(const void* in, long isB, long isY, long isX, const float* w_hwoi, const float* bias,
+                              const float* scale, const float* shift, void* out, long osB, long osY, long osX, int B,
+                              int H, int W, int Cin, int Cout, int relu, void* stream) {
+  if (bad_view(in, isB, isY, isX) || bad_view(out, osB, osY, osX) || !w_hwoi || B < 1 || H < 1 || W < 1 || Cin < 1 ||
+      Cout < 1) {
+    dg_set_error("op_deconv2x2_bf16s: null or non-positive argument");
+    return DG_ERR_ARG;
+  }
+  const ConvPlan pl = dg_plan_conv_bf16(1, Cin, Cout);
+  if (pl.bf16 != 1 || (Cin % 8)) { dg_set_error("op_deconv2x2_bf16s: the bf16 MFMA kernel does not cover %d -> %d", Cin, Cout); return DG_ERR_UNSUPPORTED; }
+  hipStream_t st = (hipStream_t)stream;
+  const TViewH o = op_view_h(out, osB, osY, osX);   // the (2H, 2W) output
+  ConvArgsH a;
+  memset(&a, 0, sizeof(a));
+  a.in = op_view_h(in, isB, isY, isX);
+  a.out = strided2_h(o, 0, 0);
+  a.B = B; a.H = H; a.W = W; a.Cin = Cin; a.Cout = Cout;
+  a.ep.bias = bias; a.ep.scale = scale; a.ep.shift = shift; a.ep.relu = relu;
+  a.ep.res = null_view_h();
+  a.ep.pool = null_view_h();
+  a.groups = 4;
+  float* wp = nullptr;
+  HIPCHECK(hipMalloc((void**)&wp, 4 * pl.packedFloats * sizeof(float)));
+  int rc = DG_OK;
+  for (int t = 0; t < 4 && rc == DG_OK; ++t) {
+    float* dst = wp + (size_t)t * pl.packedFloats;
+    rc = dg_pack_weights(pl, w_hwoi + (size_t)t * Cout * Cin, Cin, Cout, 1, 0, 0, nullptr, dst, st);
+    a.w_group[t] = dst;
+    a.out_group_off[t] = strided2_h(o, t / 2, t % 2).p - a.out.p;
+  }
+  a.w = wp;
+  if (rc == DG_OK) rc = dg_conv_bf16s(1, a, st);
+  hipStreamSynchronize(st);
+  hipFree(wp);
+  return rc;
+}
+
+int depgan_op_edge_conv_bf16s(const float* in, const float* w_hwio, const float* bias, const float* scale,
+                              const float* shift, void* out, long osB, long osY, long osX, int B, int H, int W, int Cin,
+                              int Cout, int relu, void* stream) {
+  if (!in || !w_hwio || bad_view(out, osB, osY, osX) || B < 1 || H < 1 || W < 1 || Cin < 1 || Cout < 1) {
+    dg_set_error("op_edge_conv_bf16s: null or non-positive argument");
+    return DG_ERR_ARG;
+  }
+  EdgeArgsH e;
+  memset(&e, 0, sizeof(e));
+  e.in = in; e.w = w_hwio; e.bias = bias; e.scale = scale; e.shift = shift;
+  e.out = op_view_h(out, osB, osY, osX);
+  e.B = B; e.H = H; e.W = W; e.Cin = Cin; e.Cout = Cout; e.relu = relu;
+  return dg_edge_conv_bf16s(e, (hipStream_t)stream);
+}
+
+int depgan_op_head_bf16s(const void* a, const float* w, const float* b, float* out, long P, int C, int tanh_act,
+                         void* stream) {
+  if (!a || !w || !b || !out || P < 1 || C < 1) { dg_set_error("op_head_bf16s: null or non-positive argument"); return DG_ERR_ARG; }
+  return dg_head_bf16s(reinterpret_cast<const __bf16*>(a), C, w, b, out, P, C, tanh_act, (hipStream_t)stream);
+}

@@ -52,6 +52,7 @@ class Engine:
         self._tables = {}
         self._ar_cb = None       # keeps the ctypes callback of set_allreduce alive
         self.world = 1
+        self._forward_storage = "float32"
 
     # ---- plumbing ----
     def _use_current_stream(self):
@@ -250,7 +251,28 @@ class Engine:
         return self.lib.depgan_arena_ptr(self.h, nid, ARENA_GRADS), self.lib.depgan_arena_floats(self.h, nid, ARENA_GRADS)
 
     # ---- forward ----
-    def g_forward(self, x, z):
+    @property
+    def forward_storage(self):
+        """How g_forward stores the activations between the generator's layers: "float32" (default) or "bfloat16"
+        (bf16_mfma engines only: BASELINE config 4 with bf16 activations, depgan_g_forward_bf16s)."""
+        return getattr(self, "_forward_storage", "float32")
+
+    @forward_storage.setter
+    def forward_storage(self, value):
+        self._forward_storage = self._check_storage(value)
+
+    def _check_storage(self, storage):
+        if storage not in ("float32", "bfloat16"):
+            raise ValueError("forward storage must be 'float32' or 'bfloat16', got %r" % (storage,))
+        if storage == "bfloat16" and not (self.cfg.bf16_mfma and self.cfg.nc_out in (0, 1)):
+            raise ValueError("bfloat16 activation storage needs an engine created with bf16_mfma=True (and nc_out=1); "
+                             "this one has bf16_mfma=%d, nc_out=%d" % (self.cfg.bf16_mfma, self.cfg.nc_out))
+        return storage
+
+    def g_forward(self, x, z, storage=None):
+        """Model.predict of the generator.  storage: None = self.forward_storage; "bfloat16" keeps every inter-layer
+        activation as bf16 (forward only; the input and the output stay float32)."""
+        storage = self.forward_storage if storage is None else self._check_storage(storage)
         torch = _torch()
         x = self._dev(x)
         z = self._dev(z).reshape(x.shape[0], -1)
@@ -262,10 +284,11 @@ class Engine:
         n = x.shape[0]
         out = torch.empty((n, self.height, self.width, self.nc_out), dtype=torch.float32, device=self.device)
         self._use_current_stream()
+        fn, what = ((self.lib.depgan_g_forward_bf16s, "depgan_g_forward_bf16s") if storage == "bfloat16"
+                    else (self.lib.depgan_g_forward, "depgan_g_forward"))
         for i in range(0, n, self.batch):
             m = min(self.batch, n - i)
-            check(self.lib.depgan_g_forward(self.h, self._p(x[i:i + m]), self._p(z[i:i + m]), self._p(out[i:i + m]), m),
-                  "depgan_g_forward")
+            check(fn(self.h, self._p(x[i:i + m]), self._p(z[i:i + m]), self._p(out[i:i + m]), m), what)
         return out
 
     def d_forward(self, net, img):
@@ -439,6 +462,15 @@ class Engine:
         out = np.empty(tuple(shape), np.float32)
         check(self.lib.depgan_debug_tensor(self.h, name.encode(), C.c_void_p(out.ctypes.data), out.size, shape),
               "depgan_debug_tensor")
+        return out
+
+    def debug_tensor_bf16s(self, name):
+        """"g/out/<layer>" of the last bfloat16-storage g_forward, widened to float32 (depgan_debug_tensor_bf16s)."""
+        shape = (C.c_int * 4)()
+        check(self.lib.depgan_debug_tensor_bf16s(self.h, name.encode(), None, 0, shape), "depgan_debug_tensor_bf16s")
+        out = np.empty(tuple(shape), np.float32)
+        check(self.lib.depgan_debug_tensor_bf16s(self.h, name.encode(), C.c_void_p(out.ctypes.data), out.size, shape),
+              "depgan_debug_tensor_bf16s")
         return out
 
     # ---- profiling ----

@@ -264,12 +264,18 @@ class GeneratorModel(_Model):
     net = "G"
     name = "Gen_UNet2D"
 
-    def __init__(self, input_shape, noiseZ_shape=(32, 1), first_fm=32, nc_out=1, seed=None):
+    def __init__(self, input_shape, noiseZ_shape=(32, 1), first_fm=32, nc_out=1, seed=None, inference_dtype="float32"):
         super().__init__(input_shape, seed)
         if tuple(noiseZ_shape) != (32, 1) or first_fm != 32:
             raise ValueError("the HIP path is built for noiseZ_shape=(32,1), first_fm=32 (GT:520)")
         if nc_out not in (1, 4):
             raise ValueError("nc_out must be 1 (DEP-GAN generator, GT:520) or 4 (DEP-UResNet, UT:583)")
+        if inference_dtype not in ("float32", "bfloat16"):
+            raise ValueError("inference_dtype must be 'float32' or 'bfloat16', got %r" % (inference_dtype,))
+        if inference_dtype == "bfloat16" and nc_out != 1:
+            raise ValueError("inference_dtype='bfloat16' (bf16 activation storage) exists for the DEP-GAN generator "
+                             "(nc_out=1) only")
+        self.inference_dtype = inference_dtype
         self.noiseZ_shape, self.first_fm, self.nc_out = tuple(noiseZ_shape), first_fm, nc_out
         if nc_out != 1:
             self.name = "DEP_UResNet"
@@ -282,6 +288,11 @@ class GeneratorModel(_Model):
 
     def _spec_engine(self, batch):
         H, W, nicg = self.input_shape
+        if self.nc_out == 1 and self.inference_dtype == "bfloat16":
+            # predict on the bf16 matrix pipe with bf16 activation storage (BASELINE config 4, forward only)
+            eng = Engine(batch, H, W, nicg, bf16_mfma=True)
+            eng.forward_storage = "bfloat16"
+            return eng
         if self.nc_out == 1:
             return Engine(batch, H, W, nicg)
         return Engine(batch, H, W, nicg, lrG=self._lr, beta1=0.9, beta2=0.999, nc_out=self.nc_out)
@@ -292,7 +303,17 @@ class GeneratorModel(_Model):
             raise ValueError("Gen_UNet2D.predict expects [images, noise]")
         x, z = inputs
         eng = self._ensure_engine(min(batch_size, max(1, len(x))))
-        return eng.g_forward(x, z).cpu().numpy()
+        return eng.g_forward(x, z, storage=self._predict_storage(eng)).cpu().numpy()
+
+    def _predict_storage(self, eng):
+        """The activation storage of predict on `eng`.  A model bound to a trainers' engine follows that engine: its
+        weights and kernels live there, so inference_dtype='bfloat16' cannot be honoured on an fp32 engine."""
+        if self.inference_dtype != "bfloat16":
+            return None                      # the engine's own forward_storage
+        if not eng.cfg.bf16_mfma:
+            raise ValueError("inference_dtype='bfloat16': this model is bound to an engine without the bf16 matrix pipe "
+                             "(build_trainers(..., activations_dtype='bfloat16') or an unbound model gives one)")
+        return "bfloat16"
 
     # ---- supervised surface of the softmax variant (DEP-UResNet, UT:427, 583-618) ----
     def _need_softmax(self, what):
@@ -410,8 +431,8 @@ class CriticModel(_Model):
         return eng.d_forward(self.net, x).cpu().numpy()
 
 
-def Gen_UNet2D(input_shape, noiseZ_shape=(32, 1), first_fm=32, nc_out=1, seed=None):
-    return GeneratorModel(input_shape, noiseZ_shape, first_fm, nc_out, seed)
+def Gen_UNet2D(input_shape, noiseZ_shape=(32, 1), first_fm=32, nc_out=1, seed=None, inference_dtype="float32"):
+    return GeneratorModel(input_shape, noiseZ_shape, first_fm, nc_out, seed, inference_dtype)
 
 
 def Dis_C2D_FCN1(input_shape, seed=None):

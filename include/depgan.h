@@ -281,6 +281,48 @@ int depgan_eval_label_counts(const double* pred_dev, int C, const float* code_re
 int depgan_debug_capture(depgan_ctx* ctx, int on);
 int depgan_debug_tensor(depgan_ctx* ctx, const char* name, float* host_dst, long cap_floats, int shape[4]);
 
+/* ---- generator forward with bf16 activation STORAGE (BASELINE config 4 as SURVEY 8d words it: bf16 weights AND bf16
+ * activations, fp32 accumulate).  Opt-in, forward only; depgan_g_forward and every training closure keep fp32 storage.
+ * Storage contract: element type bf16, NHWC, channel stride 1, strides counted in ELEMENTS.  A stored value is
+ * RNE_bf16(v) of the fp32 epilogue result v (v_cvt_pk_bf16_f32) and nothing else: no truncation, no stochastic rounding.
+ * Between the contraction and the store everything is fp32, in the order v = fma(acc, scale, bias * scale + shift),
+ * FiLM (v * mul + add, two roundings), ReLU, + residual (read as bf16, widened exactly).  A 2x2 max-pool is the max of
+ * the stored values (RNE is monotone: the same as rounding the fp32 max).  The network input x and the output stay fp32;
+ * weights are the context's bf16 panels; fp32 masters, Adam, the noise MLP and its FiLM vectors stay fp32.
+ * depgan_g_forward_bf16s: contract of depgan_g_forward (n in [1, batch], phase 0, enqueued on the context's stream).
+ *   Needs a context created with bf16_mfma = 1 (hence bf16_weights = 1, nc_out = 1); any other context gets status 3
+ *   and a message naming the settings, before any launch.  The bf16 buffers (one per generator layer output, concat
+ *   buffers shared) are allocated by the first call, kept, and freed by depgan_destroy.
+ * depgan_debug_tensor_bf16s: "g/out/<layer>" as depgan_debug_tensor resolves it, from the bf16 buffers of the last
+ *   depgan_g_forward_bf16s, widened to fp32 (exact): every conv / FiLM / deconv / pool layer, gen_17 included.
+ *   ("g/out/gen_segmentation" is the call's own fp32 output and has no bf16 buffer: status 1.) */
+int depgan_g_forward_bf16s(depgan_ctx* ctx, const float* x_dev, const float* z_dev, float* out_dev, int n);
+int depgan_debug_tensor_bf16s(depgan_ctx* ctx, const char* name, float* host_dst, long cap_floats, int shape[4]);
+
+/* Operators of that path.  bf16 tensors are void* device pointers with explicit view strides (sample, row, pixel) in
+ * ELEMENTS; every bf16 view must be 16-byte aligned (pointer, strides multiples of 8).  Status 1 for null / non-positive
+ * arguments (checked before any HIP call), 3 for shapes the kernels do not cover.
+ * depgan_op_conv2d_bf16s: KS in {1, 3}, Cin % 8 == 0, Cout % 32 == 0; HWIO fp32 weights are packed (rounded to bf16)
+ *   inside; bias, scale + shift, FiLM (mul, add: [B][ld] fp32), residual view `res` and the dense (B, H/2, W/2, Cout)
+ *   bf16 max-pool output `pool` are optional (NULL); `pool` needs even H and W.
+ * depgan_op_deconv2x2_bf16s: Conv2DTranspose(2x2, stride 2) with (kh, kw, Cout, Cin) fp32 weights as ONE grouped launch
+ *   of the same kernel; `out` is the (2H, 2W) view.
+ * depgan_op_edge_conv_bf16s: 3x3, Cin in {1, 2}, Cout in {8, 16, 24, 32}; dense fp32 input (B, H, W, Cin), bf16 output.
+ * depgan_op_head_bf16s: out[p] = act(sum_c a[p][c] w[c] + b[0]), dense bf16 a (P, C), fp32 out; act = tanh if tanh_act. */
+int depgan_op_conv2d_bf16s(const void* in, long isB, long isY, long isX, const float* w_hwio, const float* bias,
+                           const float* scale, const float* shift, const float* film_mul, const float* film_add,
+                           int film_ld, const void* res, long rsB, long rsY, long rsX, void* out, long osB, long osY,
+                           long osX, void* pool, int B, int H, int W, int Cin, int Cout, int KS, int relu,
+                           void* hip_stream);
+int depgan_op_deconv2x2_bf16s(const void* in, long isB, long isY, long isX, const float* w_hwoi, const float* bias,
+                              const float* scale, const float* shift, void* out, long osB, long osY, long osX, int B,
+                              int H, int W, int Cin, int Cout, int relu, void* hip_stream);
+int depgan_op_edge_conv_bf16s(const float* in, const float* w_hwio, const float* bias, const float* scale,
+                              const float* shift, void* out, long osB, long osY, long osX, int B, int H, int W, int Cin,
+                              int Cout, int relu, void* hip_stream);
+int depgan_op_head_bf16s(const void* a, const float* w, const float* b, float* out, long P, int C, int tanh_act,
+                         void* hip_stream);
+
 /* ---- single operators (unit-test surface; device pointers) ---- */
 /* path: 0 auto, 1 fp32 MFMA implicit GEMM, 2 direct, 3 bf16 MFMA implicit GEMM (both operands rounded to bf16, RNE),
  * 4 / 5: fp32 operands split into 2 / 3 bf16 terms, 3 / 6 products on the bf16 pipe (depgan_config.f32_split = 3 / 6),
