@@ -33,6 +33,7 @@ EXPORTS = [
     "depgan_eval_accumulate_channels", "depgan_eval_label_counts",
     "depgan_g_forward_bf16s", "depgan_debug_tensor_bf16s", "depgan_op_conv2d_bf16s", "depgan_op_deconv2x2_bf16s",
     "depgan_op_edge_conv_bf16s", "depgan_op_head_bf16s",
+    "depgan_set_fwd_only_storage", "depgan_get_fwd_only_storage", "depgan_op_conv2d_head_bf16s",
 ]
 
 ABI_VERSION = 3          # DEPGAN_ABI_VERSION of the include/depgan.h this binding was written against
@@ -196,6 +197,11 @@ def load():
     lib.depgan_op_deconv2x2_bf16s.argtypes = [vp, L, L, L] + [vp] * 4 + [vp, L, L, L] + [i] * 6 + [vp]
     lib.depgan_op_edge_conv_bf16s.argtypes = [vp] * 5 + [vp, L, L, L] + [i] * 6 + [vp]
     lib.depgan_op_head_bf16s.argtypes = [vp] * 4 + [L, i, i, vp]
+    lib.depgan_op_conv2d_head_bf16s.argtypes = ([vp, L, L, L] + [vp] * 6 + [i] + [vp, L, L, L] * 2 + [vp] + [i] * 7 +
+                                                [vp] * 3 + [i, i, vp])
+    # bf16 storage for the forward-only generator passes of the training closures
+    lib.depgan_set_fwd_only_storage.argtypes = [vp, i]
+    lib.depgan_get_fwd_only_storage.argtypes = [vp]
     _lib = lib
     return lib
 

@@ -19,6 +19,15 @@ struct EpilogueH {
   TViewH res;    // residual operand, read as bf16 and widened (exact)
   int relu;
   TViewH pool;   // non-null: the 2x2 / stride-2 max-pool of the stored output, (H/2, W/2) pixels; H and W even
+  // gen_segmentation fused (igemm_bf16s_head_kernel; KS = 3, Cout == 32, ungrouped): head_out[pixel] =
+  // act(sum_c stored[pixel][c] head_w[c] + head_b[0]), dense (B, H, W) fp32, in head_bf16s_kernel's arithmetic and order
+  // -- bit-equal to dg_head_bf16s of the stored tensor.  head_skip_out: the 16-byte stores of `out` are not issued
+  // (forward-only passes); pool and residual are unaffected.
+  const float* head_w;
+  const float* head_b;
+  float* head_out;   // non-null selects the fused-head kernel
+  int head_tanh;
+  int head_skip_out;
 };
 
 struct ConvArgsH {
@@ -37,7 +46,7 @@ struct ConvArgsH {
 // bf16-in / bf16-out implicit GEMM on v_mfma_f32_32x32x16_bf16, KS in {1, 3}; Cin % 8 == 0, Cout % 32 == 0, every view
 // 16-byte aligned (pointer and strides).  Argument checks come before the launch.
 int dg_conv_bf16s(int KS, const ConvArgsH& a, hipStream_t st);
-const char* dg_conv_bf16s_name(int KS);
+const char* dg_conv_bf16s_name(int KS, bool head = false);
 
 // gen_0: 3x3, Cin in {1, 2}, dense fp32 input, HWIO fp32 weights, affine + ReLU, bf16 output; Cout % 8 == 0, <= 32
 struct EdgeArgsH {

@@ -10,6 +10,10 @@
 //   * the epilogue is its own, smaller text: affine, FiLM, ReLU, bf16 residual, bf16 store, optional fused bf16 pool.
 //     A pixel's 32 channels are 64 bytes = 4 lanes x 16 bytes, so a wave covers a 16-pixel row per pass and its 4 x 16
 //     block in four passes of 16-byte stores (8-byte stores would double the issue-bound store tail).
+//   * igemm_bf16s_head_kernel is the same text with gen_segmentation (1x1 to one channel, + tanh) fused into the
+//     epilogue: the 4 lanes of a pixel are exactly head_bf16s_kernel's 4 lanes, so the head of the STORED values comes
+//     out bit for bit as that kernel computes it, and a forward-only pass need not store the 32-channel tensor at all.
+//     It is a sibling kernel, not a run-time branch: igemm_bf16s_kernel<3, 9> keeps its registers and occupancy.
 #include <stdlib.h>
 
 #include "bf16s.h"
@@ -20,275 +24,36 @@ typedef float f32x8 __attribute__((ext_vector_type(8), aligned(16)));   // loade
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 typedef int i32x4 __attribute__((ext_vector_type(4)));
 
-template <int KS, int TAPG>
-__global__ __launch_bounds__(256, 2) void igemm_bf16s_kernel(const ConvArgsH a) {
-  constexpr int NT = 32, MT = 2, CK = 32;
-  constexpr int PAD = KS / 2;
-  constexpr int TW = 16 + KS - 1;
-  constexpr int PIXT = TW * TW;
-  constexpr int NTAPS = KS * KS;
-  constexpr int NG = NTAPS / TAPG;
-  constexpr int ROWB = 80;   // bytes per LDS row: 32 bf16 + 16 bytes of padding, as igemm_bf16_kernel
-  constexpr int XV = CK / 8;  // 16-byte pieces (8 bf16) of one pixel's chunk in global memory
-  constexpr int XTOT = PIXT * XV;
-  constexpr int XPIECES = (XTOT + 255) / 256;
-  constexpr int WV = CK / 8;  // 16-byte pieces of one packed weight row
-  constexpr int WTOT = TAPG * NT * WV;
-  constexpr int WPIECES = (WTOT + 255) / 256;
-  static_assert(NTAPS % TAPG == 0, "tap grouping");
-  typedef f32x16 acc_t;
+#define IGEMM_BF16S_KERNEL igemm_bf16s_kernel
+#define IGEMM_BF16S_HEAD 0
+#include "igemm_bf16s_kernel.inc"
+#undef IGEMM_BF16S_KERNEL
+#undef IGEMM_BF16S_HEAD
+#define IGEMM_BF16S_KERNEL igemm_bf16s_head_kernel
+#define IGEMM_BF16S_HEAD 1
+#include "igemm_bf16s_kernel.inc"
+#undef IGEMM_BF16S_KERNEL
+#undef IGEMM_BF16S_HEAD
 
-  extern __shared__ __attribute__((aligned(16))) float smem[];
-  char* xs = reinterpret_cast<char*>(smem);      // [PIXT][ROWB]
-  char* ws = xs + PIXT * ROWB;                   // [TAPG][NT][ROWB]
-
-  const int tid = threadIdx.x;
-  const int tilesX = (a.W + 15) >> 4, tilesY = (a.H + 15) >> 4;
-  // work item -> (pixel tile, channel tile): the XCD-aware order of igemm_conv.hip
-  const unsigned nNTall = (unsigned)a.lgy, nPix = (unsigned)a.lgx;
-  const unsigned id = blockIdx.x;
-  int t, ntile;
-  if ((nPix & 7u) == 0) {
-    const unsigned x = id & 7u, sl = id >> 3;
-    ntile = (int)(sl % nNTall);
-    t = (int)(x * (nPix >> 3) + sl / nNTall);
-  } else {
-    t = (int)(id % nPix);
-    ntile = (int)(id / nPix);
-  }
-  const int tx0 = (t % tilesX) * 16;
-  t /= tilesX;
-  const int ty0 = (t % tilesY) * 16;
-  const int b = t / tilesY;
-  const int ngrp = a.groups > 1 ? a.groups : 1;
-  const int nNTg = (int)nNTall / ngrp;
-  const int grp = ntile / nNTg;
-  ntile -= grp * nNTg;
-  const __bf16* wbase = reinterpret_cast<const __bf16*>(a.groups > 1 ? a.w_group[grp] : a.w);
-  const long out_goff = a.groups > 1 ? a.out_group_off[grp] : 0;
-  const int n0 = ntile * NT;
-  const int nCC = (a.Cin + CK - 1) / CK;
-  const int NS = nCC * NG;
-  const __bf16* inb = a.in.p + (long)b * a.in.sB;
-
-  u32x4 xr[XPIECES];
-  u32x4 wr[WPIECES];
-  auto prefetch = [&](int s) {
-    const int cc = s / NG, tg = s - cc * NG;
-    if (tg == 0) {
-#pragma unroll
-      for (int i = 0; i < XPIECES; ++i) {
-        const int q = tid + i * 256;
-        u32x4 v = {0u, 0u, 0u, 0u};
-        if (q < XTOT) {
-          const int pix = q / XV, part = q - pix * XV;
-          const int ly = pix / TW, lx = pix - ly * TW;
-          const int iy = ty0 + ly - PAD, ix = tx0 + lx - PAD;
-          const int c = cc * CK + part * 8;
-          // Cin is a multiple of 8 (launcher): a piece is inside the channels or outside, never across the end
-          if (iy >= 0 && iy < a.H && ix >= 0 && ix < a.W && c < a.Cin)
-            v = *reinterpret_cast<const u32x4*>(inb + (long)iy * a.in.sY + (long)ix * a.in.sX + c);
-        }
-        xr[i] = v;
-      }
-    }
-    const __bf16* wsrc = wbase + ((size_t)((size_t)ntile * nCC + cc) * NTAPS + (size_t)tg * TAPG) * (NT * CK);
-#pragma unroll
-    for (int i = 0; i < WPIECES; ++i) {
-      const int q = tid + i * 256;
-      u32x4 v = {0u, 0u, 0u, 0u};
-      if (q < WTOT) v = *reinterpret_cast<const u32x4*>(wsrc + (size_t)q * 8);
-      wr[i] = v;
-    }
-  };
-  auto commit = [&](int s) {
-    const int tg = s % NG;
-    if (tg == 0) {
-#pragma unroll
-      for (int i = 0; i < XPIECES; ++i) {
-        const int q = tid + i * 256;
-        if (q < XTOT) {
-          const int pix = q / XV, part = q - pix * XV;
-          *reinterpret_cast<u32x4*>(xs + pix * ROWB + part * 16) = xr[i];   // a copy: the operand is bf16 already
-        }
-      }
-    }
-#pragma unroll
-    for (int i = 0; i < WPIECES; ++i) {
-      const int q = tid + i * 256;
-      if (q < WTOT) {
-        const int row = q / WV, part = q - row * WV;
-        *reinterpret_cast<u32x4*>(ws + row * ROWB + part * 16) = wr[i];
-      }
-    }
-  };
-
-  const int lane = tid & 63, wv = tid >> 6;
-  const int r = lane & 31, h = lane >> 5;   // h: which 8 of the 16 k-values of an MFMA this lane carries
-  int apix[MT];
-#pragma unroll
-  for (int mt = 0; mt < MT; ++mt) {
-    const int py = 4 * wv + 2 * mt + (r >> 4), px = r & 15;
-    apix[mt] = (py * TW + px) * ROWB + 16 * h;
-  }
-  const int boff = r * ROWB + 16 * h;
-
-  acc_t acc[MT];
-#pragma unroll
-  for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-    for (int j = 0; j < 16; ++j) acc[mt][j] = 0.f;
-
-  prefetch(0);
-  for (int s = 0; s < NS; ++s) {
-    __syncthreads();
-    commit(s);
-    __syncthreads();
-    if (s + 1 < NS) prefetch(s + 1);
-    const int tg = s % NG;
-#pragma unroll
-    for (int tl = 0; tl < TAPG; ++tl) {
-      const int tap = (TAPG == NTAPS) ? tl : (tg * TAPG + tl);
-      const int ty = tap / KS, tx = tap - ty * KS;
-      const int tapoff = (ty * TW + tx) * ROWB;
-#pragma unroll
-      for (int sub = 0; sub < CK / 16; ++sub) {
-        const bf16x8 bw = *reinterpret_cast<const bf16x8*>(ws + tl * (NT * ROWB) + boff + 32 * sub);
-#pragma unroll
-        for (int mt = 0; mt < MT; ++mt) {
-          const bf16x8 ax = *reinterpret_cast<const bf16x8*>(xs + apix[mt] + tapoff + 32 * sub);
-          // weight fragment first: D[channel][pixel]
-          acc[mt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(bw, ax, acc[mt], 0, 0, 0);
-        }
-      }
-    }
-  }
-
-  // ---- epilogue ----
-  // As igemm_epilogue.inc: each wave's 64 x 32 tile goes through LDS (rows of NT + 4 floats) so that a lane owns
-  // consecutive channels of one pixel; here 8 of them = 16 bytes of bf16, 4 lanes per pixel, 16 pixels (one row of the
-  // wave's 4 x 16 block) per pass.  Per view one buffer descriptor on a 64-bit base at pixel (oyw, tx0) of sample b, a
-  // per-lane 32-bit byte offset computed once and a scalar byte offset per pass: offsets stay inside four image rows.
-  __syncthreads();   // every wave is done with its fragment reads; the tile region is free
-  constexpr int CP = NT + 4;
-  float* es = smem + wv * (64 * CP);
-#pragma unroll
-  for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-    for (int g = 0; g < 4; ++g) {
-      f32x4 q4;
-#pragma unroll
-      for (int k = 0; k < 4; ++k) q4[k] = acc[mt][4 * g + k];
-      *reinterpret_cast<f32x4*>(es + (32 * mt + r) * CP + 8 * g + 4 * h) = q4;
-    }
-  const int c8 = (lane & 3) * 8, pl0 = lane >> 2;
-  const int co = n0 + c8;   // < Cout: Cout is a multiple of 32 (launcher)
-  const int wvu = __builtin_amdgcn_readfirstlane(wv);
-  const EpilogueH& e = a.ep;
-  const bool affine = e.scale != nullptr, film = e.film_mul != nullptr, relu = e.relu != 0;
-  const bool has_bias = e.bias != nullptr, has_res = e.res.p != nullptr, has_pool = e.pool.p != nullptr;
-  const int oyw = ty0 + 4 * wvu;
-  const bool full = (ty0 + 16 <= a.H) && (tx0 + 16 <= a.W);
-
-  f32x8 sc8, sh8, fm8, fa8;
-#pragma unroll
-  for (int k = 0; k < 8; ++k) { sc8[k] = 1.f; sh8[k] = 0.f; fm8[k] = 1.f; fa8[k] = 0.f; }
-  if (affine) {
-    sc8 = *reinterpret_cast<const f32x8*>(e.scale + co);
-    sh8 = *reinterpret_cast<const f32x8*>(e.shift + co);
-  }
-  if (has_bias) {
-    const f32x8 bias8 = *reinterpret_cast<const f32x8*>(e.bias + co);
-    // (acc + bias) s + t as ONE fused multiply-add per value; the constant bias s + t is formed once per item
-#pragma unroll
-    for (int k = 0; k < 8; ++k) sh8[k] = fmaf(bias8[k], sc8[k], sh8[k]);
-  }
-  if (film) {
-    fm8 = *reinterpret_cast<const f32x8*>(e.film_mul + (long)b * e.film_ld + co);
-    fa8 = *reinterpret_cast<const f32x8*>(e.film_add + (long)b * e.film_ld + co);
-  }
-  auto voff = [&](const TViewH& v, int y, int x) { return (long)b * v.sB + (long)y * v.sY + (long)x * v.sX; };
-  auto mk = [&](const __bf16* p) {
-    // the descriptor must be wave-uniform: the pointer depends on the wave index
-    const unsigned long long u = (unsigned long long)p;
-    const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)u), hi = __builtin_amdgcn_readfirstlane((unsigned)(u >> 32));
-    return __builtin_amdgcn_make_buffer_rsrc((void*)(((unsigned long long)hi << 32) | lo), 0, 0x7FFFFFFF, 0x00020000);
-  };
-  const int lo_out = 2 * (pl0 * (int)a.out.sX + co);
-  const int lo_res = has_res ? 2 * (pl0 * (int)e.res.sX + co) : 0;
-  const int lo_pool = has_pool ? 2 * ((pl0 >> 1) * (int)e.pool.sX + co) : 0;
-  const __amdgpu_buffer_rsrc_t r_out = mk(a.out.p + out_goff + voff(a.out, oyw, tx0));
-  const __amdgpu_buffer_rsrc_t r_res = mk(has_res ? e.res.p + voff(e.res, oyw, tx0) : a.out.p);
-  const __amdgpu_buffer_rsrc_t r_pool = mk(has_pool ? e.pool.p + voff(e.pool, oyw >> 1, tx0 >> 1) : a.out.p);
-  const int sY_out = 2 * (int)a.out.sY, sY_res = 2 * (int)e.res.sY, sY_pool = 2 * (int)e.pool.sY;
-  f32x8 vrow;
-#pragma unroll
-  for (int k = 0; k < 8; ++k) vrow[k] = 0.f;
-#pragma unroll
-  for (int p = 0; p < 4; ++p) {
-    // pass p = row p of the wave's 4 x 16 block: the two rows of a 2x2 pool window are consecutive passes, its two
-    // columns 4 lanes apart
-    const bool ok = full || (oyw + p < a.H && tx0 + pl0 < a.W);
-    const f32x4 v0 = *reinterpret_cast<const f32x4*>(es + (p * 16 + pl0) * CP + c8);
-    const f32x4 v1 = *reinterpret_cast<const f32x4*>(es + (p * 16 + pl0) * CP + c8 + 4);
-    f32x8 v;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) { v[k] = v0[k]; v[4 + k] = v1[k]; }
-#pragma unroll
-    for (int k = 0; k < 8; ++k) v[k] = fmaf(v[k], sc8[k], sh8[k]);
-    if (film) {
-#pragma unroll
-      for (int k = 0; k < 8; ++k) v[k] = film_preact(v[k], fm8[k], fa8[k]);
-    }
-    if (relu) {
-#pragma unroll
-      for (int k = 0; k < 8; ++k) v[k] = dg_vmax(v[k], 0.f);
-    }
-    if (has_res) {
-      i32x4 rr = {0, 0, 0, 0};
-      if (ok) rr = __builtin_amdgcn_raw_buffer_load_b128(r_res, lo_res, p * sY_res, 0);
-      const f32x8 rf = __builtin_convertvector(__builtin_bit_cast(bf16x8, rr), f32x8);   // widening: exact
-#pragma unroll
-      for (int k = 0; k < 8; ++k) v[k] += rf[k];
-    }
-    // the one rounding of the storage contract: fp32 -> bf16, round to nearest even (v_cvt_pk_bf16_f32)
-    const bf16x8 o = __builtin_convertvector(v, bf16x8);
-    if (ok) __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(i32x4, o), r_out, lo_out, p * sY_out, 0);
-    if (has_pool) {
-      const f32x8 sv = __builtin_convertvector(o, f32x8);   // the STORED values
-      if ((p & 1) == 0) {
-        vrow = sv;
-      } else {
-        f32x8 m;
-#pragma unroll
-        for (int k = 0; k < 8; ++k) {
-          const float t2 = dg_vmax(vrow[k], sv[k]);
-          m[k] = dg_vmax(t2, __shfl_xor(t2, 4, 64));
-        }
-        const bf16x8 mo = __builtin_convertvector(m, bf16x8);   // exact: m is one of the stored values
-        if (ok && (pl0 & 1) == 0)
-          __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(i32x4, mo), r_pool, lo_pool, (p >> 1) * sY_pool, 0);
-      }
-    }
-  }
-}
-
-template <int KS, int TAPG>
+template <int KS, int TAPG, bool HEAD>
 static int launch_bf16s(const ConvArgsH& a, hipStream_t st) {
   constexpr int TW = 16 + KS - 1;
   constexpr size_t lds_k = (size_t)(TW * TW + TAPG * 32) * 80;
   constexpr size_t lds_e = (size_t)4 * 64 * (32 + 4) * sizeof(float);
   constexpr size_t lds = lds_k > lds_e ? lds_k : lds_e;
+  void (*kern)(const ConvArgsH) = nullptr;
+  if constexpr (HEAD) kern = &igemm_bf16s_head_kernel<KS, TAPG>;
+  else kern = &igemm_bf16s_kernel<KS, TAPG>;
   static DgOncePerDevice once;
   if (once.need()) {
-    HIPCHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&igemm_bf16s_kernel<KS, TAPG>),
-                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    HIPCHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                 (int)lds));
   }
   ConvArgsH b = a;
   b.lgx = cdiv(a.W, 16) * cdiv(a.H, 16) * a.B;
   b.lgy = cdiv(a.Cout, 32) * (a.groups > 1 ? a.groups : 1);
   const long total = (long)b.lgx * b.lgy;
-  hipLaunchKernelGGL((igemm_bf16s_kernel<KS, TAPG>), dim3((unsigned)total), dim3(256), lds, st, b);
+  hipLaunchKernelGGL(kern, dim3((unsigned)total), dim3(256), lds, st, b);
   HIPCHECK(hipGetLastError());
   return DG_OK;
 }
@@ -301,7 +66,10 @@ static bool offsets_fit(const TViewH& v) {
   return !v.p || (v.sX > 0 && v.sY > 0 && v.sB >= 0 && 2 * (4 * v.sY + 16 * v.sX + 32) < 0x7FFFFFFFL);
 }
 
-const char* dg_conv_bf16s_name(int KS) { return KS == 3 ? "igemm_bf16s_kernel<3, 9>" : "igemm_bf16s_kernel<1, 1>"; }
+const char* dg_conv_bf16s_name(int KS, bool head) {
+  if (head) return "igemm_bf16s_head_kernel<3, 9>";
+  return KS == 3 ? "igemm_bf16s_kernel<3, 9>" : "igemm_bf16s_kernel<1, 1>";
+}
 
 int dg_conv_bf16s(int KS, const ConvArgsH& a, hipStream_t st) {
   if (KS != 1 && KS != 3) { dg_set_error("dg_conv_bf16s: kernel size %d (1 or 3)", KS); return DG_ERR_UNSUPPORTED; }
@@ -328,7 +96,21 @@ int dg_conv_bf16s(int KS, const ConvArgsH& a, hipStream_t st) {
   if (a.ep.pool.p && ((a.H | a.W) & 1)) { dg_set_error("dg_conv_bf16s: the fused pool needs even H and W"); return DG_ERR_ARG; }
   const long total = (long)cdiv(a.W, 16) * cdiv(a.H, 16) * a.B * cdiv(a.Cout, 32) * ng;
   if (total > 0x7FFFFFFFL) { dg_set_error("dg_conv_bf16s: %ld work items", total); return DG_ERR_UNSUPPORTED; }
-  return KS == 3 ? launch_bf16s<3, 9>(a, st) : launch_bf16s<1, 1>(a, st);
+  if (a.ep.head_out) {
+    // the fused head needs the 4 lanes of a pixel to hold ALL its channels: one channel tile, one group, 3x3
+    if (KS != 3 || a.Cout != 32 || ng != 1) {
+      dg_set_error("dg_conv_bf16s: the fused head needs a 3x3 convolution to exactly 32 channels, ungrouped (KS %d, Cout %d, groups %d)",
+                   KS, a.Cout, ng);
+      return DG_ERR_UNSUPPORTED;
+    }
+    if (!a.ep.head_w || !a.ep.head_b || (((uintptr_t)a.ep.head_w) & 15)) {
+      dg_set_error("dg_conv_bf16s: the fused head needs its weights (16-byte aligned) and bias");
+      return DG_ERR_ARG;
+    }
+    return launch_bf16s<3, 9, true>(a, st);
+  }
+  if (a.ep.head_skip_out) { dg_set_error("dg_conv_bf16s: head_skip_out without a fused head"); return DG_ERR_ARG; }
+  return KS == 3 ? launch_bf16s<3, 9, false>(a, st) : launch_bf16s<1, 1, false>(a, st);
 }
 
 // ---------------------------------------------------------------------------

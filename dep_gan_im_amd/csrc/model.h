@@ -201,6 +201,11 @@ struct depgan_ctx {
   // depgan_g_forward_bf16s and freed with the context; the fp32 set above is not touched by that path
   std::vector<TViewH> h_in, h_out;
   bool h_ready = false, h_valid = false;
+  // depgan_set_fwd_only_storage(1): the forward-only generator passes of the training closures (critic updates,
+  // netG_no_update) run on that forward and write c->attr; the generator update keeps fp32 storage
+  bool fwd_only_bf16 = false;
+  bool bf16s_head_fused = true;    // those passes: gen_segmentation in gen_17's epilogue (DEPGAN_BF16S_HEAD_FUSED=0: own launch)
+  bool h_17_skipped = false;       // the last bf16-storage pass did not store gen_17 (fused head, no debug capture)
 
   // ---- profiling ----
   bool prof_on = false;
@@ -257,6 +262,14 @@ int wgrad_full(depgan_ctx* c, int KS, TView x, TView dy, int N, int H, int W, in
                float* out, float* raw, int accumulate, int oi, const ColSum* cs = nullptr);
 int net_adam(depgan_ctx* c, Net& n, float gscale = 1.0f);
 int g_forward(depgan_ctx* c, const float* x, const float* z, int n, bool store_u);
+// model_bf16s.hip.  bf16s_check_ctx: what the context must be for the bf16-storage forward (no HIP call);
+// g_forward_bf16s: fused_head = gen_segmentation in gen_17's epilogue, and then gen_17 is stored only if keep_17;
+// g_forward_only: the generator pass of a closure that keeps nothing for a backward pass, batch samples into c->attr,
+// on the storage depgan_set_fwd_only_storage chose
+int bf16s_check_ctx(const depgan_ctx* c, const char* who);
+int bf16s_alloc(depgan_ctx* c);
+int g_forward_bf16s(depgan_ctx* c, const float* x, const float* z, float* out, int n, bool fused_head, bool keep_17);
+int g_forward_only(depgan_ctx* c, const float* x, const float* z);
 int refresh_generator(depgan_ctx* c);
 int refresh_generator_bn(depgan_ctx* c);  // phase-0 BN affines only (after the moving statistics moved)
 int uresnet_build(depgan_ctx* c);

@@ -1039,7 +1039,7 @@ static int critic_enqueue(depgan_ctx* c, int which, const float* y2, const float
   DNet& D = c->d[which];
   const int B = c->cfg.batch, H0 = c->cfg.height, W0 = c->cfg.width;
   const long HW0 = (long)H0 * W0;
-  DGCHECK(g_forward(c, x, z, B, false));
+  DGCHECK(g_forward_only(c, x, z));   // the critic updates do not differentiate G (GT:549, 568)
   {
     ProfScope ps(c, 2, 0.0, "critic inputs");
     DGCHECK(dg_critic_inputs(y2, x, c->cfg.nicg, c->attr.p, ep, c->d_in, B, HW0, which, c->st));
@@ -1119,7 +1119,12 @@ static int g_eval_enqueue(depgan_ctx* c, const float* x, const float* y2, const 
                           float* stats_dev) {
   const int B = c->cfg.batch, H0 = c->cfg.height, W0 = c->cfg.width;
   const long HW0 = (long)H0 * W0, P = (long)B * HW0;
-  DGCHECK(g_forward(c, x, z, B, train));
+  // netG_no_update keeps nothing for a backward pass: on the storage depgan_set_fwd_only_storage chose
+  if (train) {
+    DGCHECK(g_forward(c, x, z, B, true));
+  } else {
+    DGCHECK(g_forward_only(c, x, z));
+  }
   {
     ProfScope ps(c, 2, 0.0, "fake_y2");
     DGCHECK(dg_add_ch0(x, c->cfg.nicg, c->attr.p, c->fake_y2, P, c->st));
@@ -1330,6 +1335,9 @@ int depgan_create(const depgan_config* cfg, depgan_ctx** out) {
     // tests/test_gpu_model.py::test_fused_head_matches_the_separate_launch)
     const char* hf = getenv("DEPGAN_HEAD_FUSED");
     c->head_fused = !(hf && atoi(hf) == 0);
+    // and its bf16-storage counterpart: DEPGAN_BF16S_HEAD_FUSED=0 keeps head_bf16s_kernel in every bf16-storage pass
+    const char* hfs = getenv("DEPGAN_BF16S_HEAD_FUSED");
+    c->bf16s_head_fused = !(hfs && atoi(hfs) == 0);
     // DEPGAN_WINOGRAD=0: every 3x3 convolution on the direct implicit-GEMM kernel (A/B switch of the parity tests and
     // of bench.py's `direct_conv` line)
     const char* wn = getenv("DEPGAN_WINOGRAD");

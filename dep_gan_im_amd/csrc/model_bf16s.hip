@@ -3,6 +3,9 @@
 // the operator entries of the kernels in igemm_bf16s.hip.  The fp32 path (g_forward in model.hip) and its buffers are
 // not touched: this is a second, opt-in walk over the same layer table, the same packed bf16 panels (GLayer::wpf), the
 // same BN affines and the same fp32 noise MLP.
+// Second consumer (depgan_set_fwd_only_storage): the forward-only generator passes of the training closures --
+// g_forward_only, called by critic_enqueue and by g_eval_enqueue(train = false) in model.hip -- run the same walk into
+// c->attr, with gen_segmentation fused into gen_17's epilogue and gen_17 itself stored only under debug capture.
 #include "model.h"
 
 #include <stdio.h>
@@ -30,7 +33,7 @@ static int halloc(depgan_ctx* c, __bf16** p, size_t elems) {
 }
 
 // what the context must be for the bf16-storage forward; no HIP call
-static int bf16s_check_ctx(const depgan_ctx* c, const char* who) {
+int bf16s_check_ctx(const depgan_ctx* c, const char* who) {
   if (!c->cfg.bf16_mfma || !c->cfg.bf16_weights || c->cfg.nc_out != 1) {
     dg_set_error("%s: needs a context created with bf16_mfma = 1 (hence bf16_weights = 1, nc_out = 1); this one has "
                  "bf16_mfma = %d, bf16_weights = %d, nc_out = %d", who, c->cfg.bf16_mfma, c->cfg.bf16_weights,
@@ -56,7 +59,7 @@ static int bf16s_check_ctx(const depgan_ctx* c, const char* who) {
 // The bf16 twin of build_generator's activation set: one buffer per layer output; a convolution that feeds a pool
 // writes into the upper channels of its concat buffer, the transposed convolution of the same level into the lower ones
 // (GT:450/465/479: [deconv | skip]).  The pairing is read off the fp32 views, which are laid out the same way.
-static int bf16s_alloc(depgan_ctx* c) {
+int bf16s_alloc(depgan_ctx* c) {
   if (c->h_ready) return DG_OK;
   const int B = c->cfg.batch;
   const size_t nl = c->gl.size();
@@ -102,24 +105,29 @@ static int bf16s_alloc(depgan_ctx* c) {
 static double bf16s_bytes(const ConvArgsH& a, int KS) {
   const int ng = a.groups > 1 ? a.groups : 1;
   const double px = 2.0 * a.B * a.H * a.W;
-  return px * a.Cin + ng * (px * a.Cout * (1 + (a.ep.res.p ? 1 : 0) + (a.ep.pool.p ? 0.25 : 0)) + 2.0 * KS * KS * a.Cin * a.Cout);
+  const double head = a.ep.head_out ? 4.0 * a.B * a.H * a.W : 0.0;
+  return px * a.Cin + head +
+         ng * (px * a.Cout * (1 + (a.ep.res.p ? 1 : 0) + (a.ep.pool.p ? 0.25 : 0) - (a.ep.head_skip_out ? 1 : 0)) +
+               2.0 * KS * KS * a.Cin * a.Cout);
 }
 
 static int conv_launch_bf16s(depgan_ctx* c, const ConvArgsH& a, int KS) {
   const int ng = a.groups > 1 ? a.groups : 1;
   const double fl = 2.0 * a.B * a.H * a.W * (double)a.Cin * a.Cout * KS * KS * ng;
   char lb[56];
-  snprintf(lb, sizeof(lb), "conv(bf16s) k%d b%d %dx%d %d->%d%s", KS, a.B, a.H, a.W, a.Cin, a.Cout, ng > 1 ? " x4" : "");
-  ProfScope ps(c, 0, fl, lb, bf16s_bytes(a, KS), dg_conv_bf16s_name(KS));
+  snprintf(lb, sizeof(lb), "conv(bf16s) k%d b%d %dx%d %d->%d%s", KS, a.B, a.H, a.W, a.Cin, a.Cout,
+           ng > 1 ? " x4" : (a.ep.head_out ? (a.ep.head_skip_out ? " +head, no store" : " +head") : ""));
+  ProfScope ps(c, 0, fl, lb, bf16s_bytes(a, KS), dg_conv_bf16s_name(KS, a.ep.head_out != nullptr));
   return dg_conv_bf16s(KS, a, c->st);
 }
 
-static int g_forward_bf16s(depgan_ctx* c, const float* x, const float* z, float* out, int n) {
+int g_forward_bf16s(depgan_ctx* c, const float* x, const float* z, float* out, int n, bool fused_head, bool keep_17) {
   {
     ProfScope ps(c, 2, 0.0, "noise mlp fwd");
     DGCHECK(dg_noise_fwd(c->np, z, c->na, n, c->st));
   }
-  bool pooled_by_conv = false;
+  c->h_17_skipped = false;
+  bool pooled_by_conv = false, head_by_conv = false;
   for (size_t i = 0; i < c->gl.size(); ++i) {
     const GLayer& L = c->gl[i];
     if (L.kind == G_CONV && i == 0) {
@@ -152,6 +160,18 @@ static int g_forward_bf16s(depgan_ctx* c, const float* x, const float* z, float*
       if (i + 1 < c->gl.size() && c->gl[i + 1].kind == G_POOL && c->gl[i + 1].skip_of == (int)i && !((L.H | L.W) & 1))
         a.ep.pool = c->h_out[i + 1];
       pooled_by_conv = a.ep.pool.p != nullptr;
+      // gen_segmentation rides in gen_17's epilogue (one channel tile, no pool); a pass that keeps nothing then does not
+      // store gen_17 at all -- the bf16 twin of g_forward's head_skip_out
+      head_by_conv = false;
+      if (fused_head && L.kind == G_CONV && L.Cout == 32 && !a.ep.pool.p && i + 1 < c->gl.size() &&
+          c->gl[i + 1].kind == G_HEAD) {
+        const GLayer& Hd = c->gl[i + 1];
+        a.ep.head_w = Hd.Wt; a.ep.head_b = Hd.b; a.ep.head_out = out;
+        a.ep.head_tanh = 1;
+        a.ep.head_skip_out = keep_17 ? 0 : 1;
+        head_by_conv = true;
+        c->h_17_skipped = !keep_17;
+      }
       DGCHECK(conv_launch_bf16s(c, a, 3));
     } else if (L.kind == G_POOL) {
       if (pooled_by_conv && L.skip_of == (int)i - 1) continue;
@@ -174,6 +194,7 @@ static int g_forward_bf16s(depgan_ctx* c, const float* x, const float* z, float*
       a.w = L.wpf[0];
       DGCHECK(conv_launch_bf16s(c, a, 1));
     } else if (L.kind == G_HEAD) {
+      if (head_by_conv) continue;
       const TViewH in = c->h_in[i];
       const long P = (long)n * L.H * L.W;
       ProfScope ps(c, 2, 2.0 * P * L.Cin, "head fwd(bf16s)", P * (2.0 * L.Cin + 4.0));
@@ -189,10 +210,33 @@ int depgan_g_forward_bf16s(depgan_ctx* c, const float* x, const float* z, float*
   if (n < 1 || n > c->cfg.batch) { dg_set_error("depgan_g_forward_bf16s: n must be in [1, batch]"); return DG_ERR_ARG; }
   DGCHECK(bf16s_alloc(c));
   c->h_valid = false;
-  DGCHECK(g_forward_bf16s(c, x, z, out, n));
+  DGCHECK(g_forward_bf16s(c, x, z, out, n, false, true));   // predict: two launches, gen_17 stored
   c->h_valid = true;
   return DG_OK;
 }
+
+int g_forward_only(depgan_ctx* c, const float* x, const float* z) {
+  const int B = c->cfg.batch;
+  if (!c->fwd_only_bf16) return g_forward(c, x, z, B, false);
+  DGCHECK(bf16s_alloc(c));
+  c->h_valid = false;
+  DGCHECK(g_forward_bf16s(c, x, z, c->attr.p, B, c->bf16s_head_fused, c->dbg_capture));
+  c->h_valid = true;
+  return DG_OK;
+}
+
+int depgan_set_fwd_only_storage(depgan_ctx* c, int storage) {
+  if (!c) { dg_set_error("depgan_set_fwd_only_storage: null context"); return DG_ERR_ARG; }
+  if (storage != 0 && storage != 1) {
+    dg_set_error("depgan_set_fwd_only_storage: storage must be 0 (fp32) or 1 (bf16), got %d", storage);
+    return DG_ERR_ARG;
+  }
+  if (storage == 1) DGCHECK(bf16s_check_ctx(c, "depgan_set_fwd_only_storage"));
+  c->fwd_only_bf16 = storage == 1;
+  return DG_OK;
+}
+
+int depgan_get_fwd_only_storage(depgan_ctx* c) { return (c && c->fwd_only_bf16) ? 1 : 0; }
 
 int depgan_debug_tensor_bf16s(depgan_ctx* c, const char* name, float* host, long cap, int shape[4]) {
   if (!c || !name || !shape) { dg_set_error("debug_tensor_bf16s: null argument"); return DG_ERR_ARG; }
@@ -211,6 +255,11 @@ int depgan_debug_tensor_bf16s(depgan_ctx* c, const char* name, float* host, long
     if (L.name != ln) continue;
     if (L.kind == G_HEAD) {
       dg_set_error("debug_tensor_bf16s: %s is the fp32 output of depgan_g_forward_bf16s, not a bf16 buffer", name);
+      return DG_ERR_ARG;
+    }
+    if (c->h_17_skipped && i + 1 < c->gl.size() && c->gl[i + 1].kind == G_HEAD) {
+      dg_set_error("debug_tensor_bf16s: the last bf16-storage pass was a forward-only pass with the fused head and did "
+                   "not store %s (depgan_debug_capture(ctx, 1) makes those passes store it)", name);
       return DG_ERR_ARG;
     }
     const TViewH v = c->h_out[i];
@@ -244,18 +293,24 @@ static TViewH op_view_h(const void* p, long sB, long sY, long sX) {
 }
 static bool bad_view(const void* p, long sB, long sY, long sX) { return !p || sB < 0 || sY < 1 || sX < 1; }
 
-int depgan_op_conv2d_bf16s(const void* in, long isB, long isY, long isX, const float* w_hwio, const float* bias,
-                           const float* scale, const float* shift, const float* film_mul, const float* film_add,
-                           int film_ld, const void* res, long rsB, long rsY, long rsX, void* out, long osB, long osY,
-                           long osX, void* pool, int B, int H, int W, int Cin, int Cout, int KS, int relu, void* stream) {
+static int op_conv2d_bf16s_impl(const char* who, const void* in, long isB, long isY, long isX, const float* w_hwio,
+                                const float* bias, const float* scale, const float* shift, const float* film_mul,
+                                const float* film_add, int film_ld, const void* res, long rsB, long rsY, long rsX,
+                                void* out, long osB, long osY, long osX, void* pool, int B, int H, int W, int Cin, int Cout,
+                                int KS, int relu, const float* head_w, const float* head_b, float* head_out, int tanh_act,
+                                int skip_out, void* stream) {
   if (bad_view(in, isB, isY, isX) || bad_view(out, osB, osY, osX) || !w_hwio || B < 1 || H < 1 || W < 1 || Cin < 1 ||
       Cout < 1 || (res && bad_view(res, rsB, rsY, rsX))) {
-    dg_set_error("op_conv2d_bf16s: null or non-positive argument");
+    dg_set_error("%s: null or non-positive argument", who);
     return DG_ERR_ARG;
   }
-  if (KS != 1 && KS != 3) { dg_set_error("op_conv2d_bf16s: KS must be 1 or 3"); return DG_ERR_ARG; }
+  if (KS != 1 && KS != 3) { dg_set_error("%s: KS must be 1 or 3", who); return DG_ERR_ARG; }
   const ConvPlan pl = dg_plan_conv_bf16(KS, Cin, Cout);
-  if (pl.bf16 != 1 || (Cin % 8)) { dg_set_error("op_conv2d_bf16s: the bf16 MFMA kernel does not cover %d -> %d", Cin, Cout); return DG_ERR_UNSUPPORTED; }
+  if (pl.bf16 != 1 || (Cin % 8)) { dg_set_error("%s: the bf16 MFMA kernel does not cover %d -> %d", who, Cin, Cout); return DG_ERR_UNSUPPORTED; }
+  if (head_out && (KS != 3 || Cout != 32)) {
+    dg_set_error("%s: the fused head needs a 3x3 convolution to exactly 32 channels (KS %d, Cout %d)", who, KS, Cout);
+    return DG_ERR_UNSUPPORTED;
+  }
   hipStream_t st = (hipStream_t)stream;
   ConvArgsH a;
   memset(&a, 0, sizeof(a));
@@ -267,6 +322,8 @@ int depgan_op_conv2d_bf16s(const void* in, long isB, long isY, long isX, const f
   a.ep.res = res ? op_view_h(res, rsB, rsY, rsX) : null_view_h();
   a.ep.relu = relu;
   a.ep.pool = pool ? make_view_h(reinterpret_cast<__bf16*>(pool), H / 2, W / 2, Cout) : null_view_h();
+  a.ep.head_w = head_w; a.ep.head_b = head_b; a.ep.head_out = head_out;
+  a.ep.head_tanh = tanh_act; a.ep.head_skip_out = head_out ? skip_out : 0;
   float* wp = nullptr;
   HIPCHECK(hipMalloc((void**)&wp, pl.packedFloats * sizeof(float)));
   int rc = dg_pack_weights(pl, w_hwio, Cin, Cout, 0, 0, 0, nullptr, wp, st);
@@ -275,6 +332,27 @@ int depgan_op_conv2d_bf16s(const void* in, long isB, long isY, long isX, const f
   hipStreamSynchronize(st);
   hipFree(wp);
   return rc;
+}
+
+int depgan_op_conv2d_bf16s(const void* in, long isB, long isY, long isX, const float* w_hwio, const float* bias,
+                           const float* scale, const float* shift, const float* film_mul, const float* film_add,
+                           int film_ld, const void* res, long rsB, long rsY, long rsX, void* out, long osB, long osY,
+                           long osX, void* pool, int B, int H, int W, int Cin, int Cout, int KS, int relu, void* stream) {
+  return op_conv2d_bf16s_impl("op_conv2d_bf16s", in, isB, isY, isX, w_hwio, bias, scale, shift, film_mul, film_add, film_ld,
+                              res, rsB, rsY, rsX, out, osB, osY, osX, pool, B, H, W, Cin, Cout, KS, relu, nullptr, nullptr,
+                              nullptr, 0, 0, stream);
+}
+
+int depgan_op_conv2d_head_bf16s(const void* in, long isB, long isY, long isX, const float* w_hwio, const float* bias,
+                                const float* scale, const float* shift, const float* film_mul, const float* film_add,
+                                int film_ld, const void* res, long rsB, long rsY, long rsX, void* out, long osB,
+                                long osY, long osX, void* pool, int B, int H, int W, int Cin, int Cout, int KS, int relu,
+                                const float* head_w, const float* head_b, float* head_out, int tanh_act, int skip_out,
+                                void* stream) {
+  if (!head_w || !head_b || !head_out) { dg_set_error("op_conv2d_head_bf16s: null head argument"); return DG_ERR_ARG; }
+  return op_conv2d_bf16s_impl("op_conv2d_head_bf16s", in, isB, isY, isX, w_hwio, bias, scale, shift, film_mul, film_add,
+                              film_ld, res, rsB, rsY, rsX, out, osB, osY, osX, pool, B, H, W, Cin, Cout, KS, relu, head_w,
+                              head_b, head_out, tanh_act, skip_out, stream);
 }
 
 int depgan_op_deconv2x2_bf16s(const void* in, long isB, long isY, long isX, const float* w_hwoi, const float* bias,

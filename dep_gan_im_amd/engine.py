@@ -269,6 +269,24 @@ class Engine:
                              "this one has bf16_mfma=%d, nc_out=%d" % (self.cfg.bf16_mfma, self.cfg.nc_out))
         return storage
 
+    @property
+    def forward_only_storage(self):
+        """How the FORWARD-ONLY generator passes of the training closures (the one inside every critic update and
+        netG_no_update / the best-of-k evaluations) store their activations: "float32" (default) or "bfloat16"
+        (bf16_mfma engines only; depgan_set_fwd_only_storage).  The generator update keeps float32 storage, so with
+        "bfloat16" netG_no_update(z) and netG_train(z) no longer report identical scalars for the same noise.
+        Independent of forward_storage, which governs g_forward / predict.  Every rank of a data-parallel job must
+        use the same value."""
+        return getattr(self, "_forward_only_storage", "float32")
+
+    @forward_only_storage.setter
+    def forward_only_storage(self, value):
+        value = self._check_storage(value)
+        if getattr(self, "h", None):
+            check(self.lib.depgan_set_fwd_only_storage(self.h, 1 if value == "bfloat16" else 0),
+                  "depgan_set_fwd_only_storage")
+        self._forward_only_storage = value
+
     def g_forward(self, x, z, storage=None):
         """Model.predict of the generator.  storage: None = self.forward_storage; "bfloat16" keeps every inter-layer
         activation as bf16 (forward only; the input and the output stay float32)."""

@@ -139,7 +139,8 @@ class Trainers:
 
 
 def build_trainers(netG, netD_y2, netD_dem, batchSize=16, delta=10.0, lrD=1e-4, lrG=1e-4, IM_TRSH=0.5,
-                   dist=None, device=None, weights_dtype="float32", activations_dtype="float32", f32_split=0):
+                   dist=None, device=None, weights_dtype="float32", activations_dtype="float32", f32_split=0,
+                   forward_only_storage="float32"):
     """Builds the loss graph of GT:523-598 for the three models and returns a
     Trainers object.  The models are bound to one engine: afterwards their
     predict()/get_weights()/save() see the trained weights.
@@ -149,6 +150,11 @@ def build_trainers(netG, netD_y2, netD_dem, batchSize=16, delta=10.0, lrD=1e-4, 
     bf16 and run on the bf16 matrix pipe (v_mfma_f32_32x32x16_bf16), accumulating in fp32.
     f32_split=6 (or 3): opt-in -- fp32 operands of the MFMA convolutions split exactly into three (two) bf16 terms, the six
     (three) largest cross products on the bf16 matrix pipe, fp32 accumulation (include/depgan.h, depgan_config.f32_split).
+    forward_only_storage="bfloat16" (needs activations_dtype="bfloat16"): opt-in -- the generator passes that keep nothing
+    for a backward pass (the one inside every critic update, netG_no_update and the best-of-k evaluations: 20 of the 21
+    generator forwards of one iteration of the reference schedule) store their activations as bf16
+    (Engine.forward_only_storage).  netG_train keeps float32 storage, so netG_no_update(z) and netG_train(z) then differ
+    for the same noise by the size of the bf16 rounding effect; every rank of a data-parallel job must use the same value.
     dist: a dep_gan_im_amd.dist.DataParallel -- the engine becomes one replica of a data-parallel job (rank 0's
     weights are broadcast, every update all-reduces its gradient arena)."""
     if weights_dtype not in ("float32", "bfloat16"):
@@ -157,12 +163,17 @@ def build_trainers(netG, netD_y2, netD_dem, batchSize=16, delta=10.0, lrD=1e-4, 
         raise ValueError("activations_dtype must be 'float32' or 'bfloat16'")
     if activations_dtype == "bfloat16" and weights_dtype != "bfloat16":
         raise ValueError("activations_dtype='bfloat16' needs weights_dtype='bfloat16'")
+    if forward_only_storage not in ("float32", "bfloat16"):
+        raise ValueError("forward_only_storage must be 'float32' or 'bfloat16'")
+    if forward_only_storage == "bfloat16" and activations_dtype != "bfloat16":
+        raise ValueError("forward_only_storage='bfloat16' needs activations_dtype='bfloat16' (the bf16 matrix pipe)")
     H, W, nicg = netG.input_shape
     if tuple(netD_y2.input_shape) != (H, W, 1) or tuple(netD_dem.input_shape) != (H, W, 1):
         raise ValueError("critics must take (%d,%d,1) images" % (H, W))
     eng = Engine(batchSize, H, W, nicg, first_fm=netG.first_fm, im_thresh=IM_TRSH, delta=delta, lrD=lrD, lrG=lrG,
                  beta1=0.0, beta2=0.9, device=device, bf16_weights=(weights_dtype == "bfloat16"),
                  bf16_mfma=(activations_dtype == "bfloat16"), f32_split=f32_split)
+    eng.forward_only_storage = forward_only_storage
     netG._bind(eng, "G")
     netD_y2._bind(eng, "D_y2")
     netD_dem._bind(eng, "D_dem")

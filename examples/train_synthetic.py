@@ -52,6 +52,9 @@ def main():
     ap.add_argument("--out", default="netG_synthetic.npz")
     ap.add_argument("--state", default="train_state.npz", help="full training state (3 networks, Adam, counters)")
     ap.add_argument("--resume", action="store_true")
+    ap.add_argument("--forward-only-storage", choices=("float32", "bfloat16"), default="float32",
+                    help="bfloat16: train in BASELINE config 4 (bf16 weights and matrix pipe) and store the activations of "
+                         "the generator passes that keep nothing for a backward pass (critic updates, best-of-k) as bf16")
     args = ap.parse_args()
 
     import torch
@@ -72,7 +75,9 @@ def main():
     netD_dem = dg.Dis_C2D_FCN1((imageSize, imageSize, 1), seed=2)             # GT:516
     netG = dg.Gen_UNet2D((imageSize, imageSize, nicg), (noiseSize, 1), first_fm_G, 1, seed=3)   # GT:520
     t = dg.build_trainers(netG, netD_y2, netD_dem, batchSize=args.batch, delta=10.0, lrD=1e-4, lrG=1e-4, IM_TRSH=0.178,
-                          dist=dp)
+                          dist=dp, forward_only_storage=args.forward_only_storage,
+                          **({"weights_dtype": "bfloat16", "activations_dtype": "bfloat16"}
+                             if args.forward_only_storage == "bfloat16" else {}))
 
     train_1tp, train_2tp = synthetic_slices(args.slices, imageSize, 0)
     train_1tp, train_2tp = torch.from_numpy(train_1tp).cuda(), torch.from_numpy(train_2tp).cuda()   # resident in HBM

@@ -299,6 +299,33 @@ int depgan_debug_tensor(depgan_ctx* ctx, const char* name, float* host_dst, long
 int depgan_g_forward_bf16s(depgan_ctx* ctx, const float* x_dev, const float* z_dev, float* out_dev, int n);
 int depgan_debug_tensor_bf16s(depgan_ctx* ctx, const char* name, float* host_dst, long cap_floats, int shape[4]);
 
+/* ---- bf16 activation storage for the FORWARD-ONLY generator passes of the training closures.  Opt-in, default 0.
+ * Of the 21 generator forwards of one generator iteration of the reference schedule (5 + 5 critic updates, 10
+ * evaluations, 1 update) 20 keep nothing for a backward pass: the critic updates do not differentiate G (GT:549, 568)
+ * and netG_no_update is the best-of-k evaluation (GT:868-877).  With storage = 1 those passes -- the generator pass
+ * inside depgan_critic_grads / depgan_critic_step / depgan_g_eval / depgan_g_eval_multi and both critic loops and the
+ * k evaluations of depgan_gen_iteration -- run the forward of depgan_g_forward_bf16s (same storage contract) with
+ * gen_segmentation fused into gen_17's epilogue, so that gen_17 is neither stored nor read back
+ * (DEPGAN_BF16S_HEAD_FUSED=0, read by depgan_create, keeps the two launches: A/B).  The generator UPDATE
+ * (depgan_g_grads, depgan_g_step, the update closing depgan_gen_iteration) keeps the fp32-storage forward and the
+ * existing backward; depgan_g_forward, depgan_g_forward_bf16s and the DEP-UResNet entries are not affected.  With
+ * storage = 0 every path computes the bits it computed before this option existed.
+ * Consequence to know: with storage = 1 netG_no_update(z) evaluates the bf16-storage generator and netG_train(z)
+ * reports the fp32-storage one, so the two no longer return identical scalars for the same noise, and the noise
+ * best-of-k picks is the arg-min under the bf16-storage forward.  In a data-parallel job every rank must use the same
+ * value (the mode changes no collective; the arg-min is formed from all-reduced pieces, so the ranks agree anyway).
+ * depgan_set_fwd_only_storage: 0 = fp32 (default), 1 = bf16.  1 is refused with status 3 and a message naming the
+ *   cause, before any launch, for whatever depgan_g_forward_bf16s refuses (no bf16_mfma, nc_out != 1, a layer without
+ *   a bf16 plan); any other value is status 1.  The bf16 buffers are those of depgan_g_forward_bf16s: allocated by the
+ *   first pass that needs them and kept -- 58 MB per sample of batch at 256 x 256 on top of the fp32 set.
+ * Debug surface with storage = 1: "g/out/gen_segmentation" of depgan_debug_tensor is the generator output of the last
+ *   pass whichever storage wrote it; the other fp32 "g/out/<layer>" names describe the last fp32-storage pass.  The bf16
+ *   buffers of the last forward-only pass are read with depgan_debug_tensor_bf16s; "g/out/gen_17" is stored by those
+ *   passes only while depgan_debug_capture is on -- after a pass that skipped the store it is refused with status 1
+ *   and a message that says so (never stale data); every other layer stays readable. */
+int depgan_set_fwd_only_storage(depgan_ctx* ctx, int storage);
+int depgan_get_fwd_only_storage(depgan_ctx* ctx);
+
 /* Operators of that path.  bf16 tensors are void* device pointers with explicit view strides (sample, row, pixel) in
  * ELEMENTS; every bf16 view must be 16-byte aligned (pointer, strides multiples of 8).  Status 1 for null / non-positive
  * arguments (checked before any HIP call), 3 for shapes the kernels do not cover.
@@ -308,12 +335,21 @@ int depgan_debug_tensor_bf16s(depgan_ctx* ctx, const char* name, float* host_dst
  * depgan_op_deconv2x2_bf16s: Conv2DTranspose(2x2, stride 2) with (kh, kw, Cout, Cin) fp32 weights as ONE grouped launch
  *   of the same kernel; `out` is the (2H, 2W) view.
  * depgan_op_edge_conv_bf16s: 3x3, Cin in {1, 2}, Cout in {8, 16, 24, 32}; dense fp32 input (B, H, W, Cin), bf16 output.
- * depgan_op_head_bf16s: out[p] = act(sum_c a[p][c] w[c] + b[0]), dense bf16 a (P, C), fp32 out; act = tanh if tanh_act. */
+ * depgan_op_head_bf16s: out[p] = act(sum_c a[p][c] w[c] + b[0]), dense bf16 a (P, C), fp32 out; act = tanh if tanh_act.
+ * depgan_op_conv2d_head_bf16s: depgan_op_conv2d_bf16s with that head fused into the epilogue (KS = 3, Cout = 32; status
+ *   3 otherwise): head_out (B, H, W) dense fp32 is computed from the STORED (rounded) values in depgan_op_head_bf16s's
+ *   arithmetic and order, so it equals the two calls bit for bit; with skip_out the stores of `out` are not issued. */
 int depgan_op_conv2d_bf16s(const void* in, long isB, long isY, long isX, const float* w_hwio, const float* bias,
                            const float* scale, const float* shift, const float* film_mul, const float* film_add,
                            int film_ld, const void* res, long rsB, long rsY, long rsX, void* out, long osB, long osY,
                            long osX, void* pool, int B, int H, int W, int Cin, int Cout, int KS, int relu,
                            void* hip_stream);
+int depgan_op_conv2d_head_bf16s(const void* in, long isB, long isY, long isX, const float* w_hwio, const float* bias,
+                                const float* scale, const float* shift, const float* film_mul, const float* film_add,
+                                int film_ld, const void* res, long rsB, long rsY, long rsX, void* out, long osB,
+                                long osY, long osX, void* pool, int B, int H, int W, int Cin, int Cout, int KS, int relu,
+                                const float* head_w, const float* head_b, float* head_out, int tanh_act, int skip_out,
+                                void* hip_stream);
 int depgan_op_deconv2x2_bf16s(const void* in, long isB, long isY, long isX, const float* w_hwoi, const float* bias,
                               const float* scale, const float* shift, void* out, long osB, long osY, long osX, int B,
                               int H, int W, int Cin, int Cout, int relu, void* hip_stream);
