@@ -34,6 +34,9 @@ EXPORTS = [
     "depgan_g_forward_bf16s", "depgan_debug_tensor_bf16s", "depgan_op_conv2d_bf16s", "depgan_op_deconv2x2_bf16s",
     "depgan_op_edge_conv_bf16s", "depgan_op_head_bf16s",
     "depgan_set_fwd_only_storage", "depgan_get_fwd_only_storage", "depgan_op_conv2d_head_bf16s",
+    "depgan_set_g_update_storage", "depgan_get_g_update_storage", "depgan_debug_film_decision_bf16s",
+    "depgan_op_conv2d_film_train_bf16s", "depgan_op_conv2d_wgrad_bf16s", "depgan_op_conv2d_bwd_data_bf16s",
+    "depgan_op_unpool_mask_bf16s", "depgan_op_film_bwd_bf16s", "depgan_op_head_bwd_bf16s",
 ]
 
 ABI_VERSION = 3          # DEPGAN_ABI_VERSION of the include/depgan.h this binding was written against
@@ -202,6 +205,17 @@ def load():
     # bf16 storage for the forward-only generator passes of the training closures
     lib.depgan_set_fwd_only_storage.argtypes = [vp, i]
     lib.depgan_get_fwd_only_storage.argtypes = [vp]
+    # bf16 storage for the generator update: setter, debug surface and the operators of its backward
+    lib.depgan_set_g_update_storage.argtypes = [vp, i]
+    lib.depgan_get_g_update_storage.argtypes = [vp]
+    lib.depgan_debug_film_decision_bf16s.argtypes = [vp, C.c_char_p, vp, L, ip]
+    lib.depgan_op_conv2d_film_train_bf16s.argtypes = ([vp, L, L, L] + [vp] * 6 + [i] + [vp, L, L, L] * 2 + [vp, vp] +
+                                                      [i] * 6 + [vp])
+    lib.depgan_op_conv2d_wgrad_bf16s.argtypes = [vp, L, L, L] * 2 + [vp, vp] + [i] * 7 + [vp]
+    lib.depgan_op_conv2d_bwd_data_bf16s.argtypes = [vp, L, L, L] + [vp] + [vp, L, L, L] * 3 + [i] * 6 + [vp]
+    lib.depgan_op_unpool_mask_bf16s.argtypes = [vp, L, L, L] * 4 + [i] * 4 + [vp]
+    lib.depgan_op_film_bwd_bf16s.argtypes = [vp] * 4 + [i] + [vp] * 3 + [i, L, i, vp]
+    lib.depgan_op_head_bwd_bf16s.argtypes = [i, vp, L] + [vp] * 3 + [L, i, vp]
     _lib = lib
     return lib
 

@@ -1,8 +1,16 @@
 // Text of the bf16-storage implicit-GEMM kernel, included by igemm_bf16s.hip once per kernel: the including file defines
 // IGEMM_BF16S_KERNEL (the kernel's name) and IGEMM_BF16S_HEAD (0 / 1: gen_segmentation fused into the epilogue).  Two
 // kernels from one text, so that the plain one compiles exactly as it did before the fused head existed.
+// igemm_bf16s_train.hip includes it a third time with IGEMM_BF16S_TRAIN = 1 and IGEMM_BF16S_ARGS = ConvArgsHT (ConvArgsH
+// plus `u` and `fdec`): the FiLM layers of the generator update, which also store RNE_bf16 of the pre-FiLM tensor and
+// the ReLU decision the epilogue took, one bit per element.  Both default to what the two kernels above are built with.
+#ifndef IGEMM_BF16S_TRAIN
+#define IGEMM_BF16S_TRAIN 0
+#define IGEMM_BF16S_ARGS ConvArgsH
+#define IGEMM_BF16S_TRAIN_DEFAULTED
+#endif
 template <int KS, int TAPG>
-__global__ __launch_bounds__(256, 2) void IGEMM_BF16S_KERNEL(const ConvArgsH a) {
+__global__ __launch_bounds__(256, 2) void IGEMM_BF16S_KERNEL(const IGEMM_BF16S_ARGS a) {
   constexpr bool HEAD = IGEMM_BF16S_HEAD != 0;
   constexpr int NT = 32, MT = 2, CK = 32;
   constexpr int PAD = KS / 2;
@@ -217,6 +225,13 @@ __global__ __launch_bounds__(256, 2) void IGEMM_BF16S_KERNEL(const ConvArgsH a) 
     hrow = e.head_out + ((long)b * a.H + oyw) * a.W + tx0 + pl0;
     skip_out = e.head_skip_out != 0;
   }
+#if IGEMM_BF16S_TRAIN
+  // TRAIN (launcher: FiLM present): the pre-FiLM tensor as bf16 and the decision bits, dense [B][H][W][Cout / 8] bytes
+  const int lo_u = 2 * (pl0 * (int)a.u.sX + co);
+  const __amdgpu_buffer_rsrc_t r_u = mk(a.u.p + voff(a.u, oyw, tx0));
+  const int sY_u = 2 * (int)a.u.sY;
+  unsigned* drow = reinterpret_cast<unsigned*>(a.fdec + (((long)b * a.H + oyw) * a.W + tx0 + pl0) * (a.Cout >> 3) + (n0 >> 3));
+#endif
 #pragma unroll
   for (int p = 0; p < 4; ++p) {
     // pass p = row p of the wave's 4 x 16 block: the two rows of a 2x2 pool window are consecutive passes, its two
@@ -229,10 +244,26 @@ __global__ __launch_bounds__(256, 2) void IGEMM_BF16S_KERNEL(const ConvArgsH a) 
     for (int k = 0; k < 4; ++k) { v[k] = v0[k]; v[4 + k] = v1[k]; }
 #pragma unroll
     for (int k = 0; k < 8; ++k) v[k] = fmaf(v[k], sc8[k], sh8[k]);
+#if IGEMM_BF16S_TRAIN
+    if (ok) __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(i32x4, __builtin_convertvector(v, bf16x8)), r_u, lo_u, p * sY_u, 0);
+#endif
     if (film) {
 #pragma unroll
       for (int k = 0; k < 8; ++k) v[k] = film_preact(v[k], fm8[k], fa8[k]);
     }
+#if IGEMM_BF16S_TRAIN
+    {
+      // the decision of the ReLU below, taken on the very value it clamps: bit k of this lane's byte = (v[k] > 0); the 4
+      // lanes of a pixel hold its 32 channels = one 32-bit word, gathered by two shuffles and stored by lane 0 of the four
+      unsigned m = 0u;
+#pragma unroll
+      for (int k = 0; k < 8; ++k) m |= (v[k] > 0.f ? 1u : 0u) << k;
+      m <<= 8 * (lane & 3);
+      m |= __shfl_xor(m, 1, 64);
+      m |= __shfl_xor(m, 2, 64);
+      if (ok && (lane & 3) == 0) drow[(long)p * a.W * (a.Cout >> 5)] = m;
+    }
+#endif
     if (relu) {
 #pragma unroll
       for (int k = 0; k < 8; ++k) v[k] = dg_vmax(v[k], 0.f);
@@ -280,3 +311,8 @@ __global__ __launch_bounds__(256, 2) void IGEMM_BF16S_KERNEL(const ConvArgsH a) 
     }
   }
 }
+#ifdef IGEMM_BF16S_TRAIN_DEFAULTED
+#undef IGEMM_BF16S_TRAIN
+#undef IGEMM_BF16S_ARGS
+#undef IGEMM_BF16S_TRAIN_DEFAULTED
+#endif

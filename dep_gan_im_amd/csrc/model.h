@@ -10,6 +10,7 @@
 #include "../../include/depgan.h"
 #include "common.h"
 #include "bf16s.h"
+#include "bf16s_train.h"
 #include "deconv_fwd.h"
 #include "noise.h"
 #include "ops.h"
@@ -206,6 +207,13 @@ struct depgan_ctx {
   bool fwd_only_bf16 = false;
   bool bf16s_head_fused = true;    // those passes: gen_segmentation in gen_17's epilogue (DEPGAN_BF16S_HEAD_FUSED=0: own launch)
   bool h_17_skipped = false;       // the last bf16-storage pass did not store gen_17 (fused head, no debug capture)
+  // depgan_set_g_update_storage(1): the generator update runs on the bf16-storage forward too and its backward reads the
+  // bf16 buffers (model_bf16s_train.hip).  Per FiLM layer the pre-FiLM tensor as bf16 and the decision bits the forward
+  // stored; allocated by the first update in the mode, valid after a training forward in the mode
+  bool g_update_bf16 = false;
+  std::vector<TViewH> h_u;
+  std::vector<unsigned char*> h_dec;
+  bool hu_ready = false, hu_valid = false;
 
   // ---- profiling ----
   bool prof_on = false;
@@ -268,8 +276,17 @@ int g_forward(depgan_ctx* c, const float* x, const float* z, int n, bool store_u
 // on the storage depgan_set_fwd_only_storage chose
 int bf16s_check_ctx(const depgan_ctx* c, const char* who);
 int bf16s_alloc(depgan_ctx* c);
-int g_forward_bf16s(depgan_ctx* c, const float* x, const float* z, float* out, int n, bool fused_head, bool keep_17);
+int g_forward_bf16s(depgan_ctx* c, const float* x, const float* z, float* out, int n, bool fused_head, bool keep_17,
+                    bool train = false);
 int g_forward_only(depgan_ctx* c, const float* x, const float* z);
+// model_bf16s_train.hip: the generator update on bf16 activation storage.  g_forward_train_bf16s: batch samples into
+// c->attr, additionally keeping u and the FiLM decisions; g_backward_bf16s: g_backward over the same layer table, gradient
+// arena and raw_all slots, reading the bf16 buffers; g_backward_finish (model.hip): the BN-gamma launch and the noise MLP
+int bf16s_train_alloc(depgan_ctx* c);
+int bf16s_debug_u(depgan_ctx* c, const char* name, float* host, long cap, int shape[4]);
+int g_forward_train_bf16s(depgan_ctx* c, const float* x, const float* z);
+int g_backward_bf16s(depgan_ctx* c, const float* x, const float* z, int n);
+int g_backward_finish(depgan_ctx* c, const float* z, int n);
 int refresh_generator(depgan_ctx* c);
 int refresh_generator_bn(depgan_ctx* c);  // phase-0 BN affines only (after the moving statistics moved)
 int uresnet_build(depgan_ctx* c);

@@ -905,6 +905,11 @@ int g_backward(depgan_ctx* c, const float* x, const float* z, int n) {
       DGCHECK(deconv_bwd_data(c, L, L.dout, n));
     }
   }
+  return g_backward_finish(c, z, n);
+}
+
+// what every generator backward ends with, whatever its activation storage (g_backward_bf16s, model_bf16s_train.hip)
+int g_backward_finish(depgan_ctx* c, const float* z, int n) {
   {
     // BN-gamma gradients of all 24 layers in one launch: d gamma = rstd (sum_k W dWraw + (b - mu) S), S = d beta
     if (!c->g_gamma_jobs) {
@@ -1121,7 +1126,9 @@ static int g_eval_enqueue(depgan_ctx* c, const float* x, const float* y2, const 
   const long HW0 = (long)H0 * W0, P = (long)B * HW0;
   // netG_no_update keeps nothing for a backward pass: on the storage depgan_set_fwd_only_storage chose
   if (train) {
-    DGCHECK(g_forward(c, x, z, B, true));
+    // depgan_set_g_update_storage(1): the update runs on the same bf16-storage forward as the forward-only passes
+    if (c->g_update_bf16) DGCHECK(g_forward_train_bf16s(c, x, z));
+    else DGCHECK(g_forward(c, x, z, B, true));
   } else {
     DGCHECK(g_forward_only(c, x, z));
   }
@@ -1145,7 +1152,8 @@ static int g_eval_enqueue(depgan_ctx* c, const float* x, const float* y2, const 
       ProfScope ps(c, 2, 0.0, "g dpre");
       DGCHECK(dg_g_dpre(x, c->cfg.nicg, y2, c->attr.p, c->g0, c->g0 + P, c->dpre, B, P, c->st));
     }
-    DGCHECK(g_backward(c, x, z, B));
+    if (c->g_update_bf16) DGCHECK(g_backward_bf16s(c, x, z, B));
+    else DGCHECK(g_backward(c, x, z, B));
   }
   return DG_OK;
 }

@@ -6,6 +6,8 @@
 // Second consumer (depgan_set_fwd_only_storage): the forward-only generator passes of the training closures --
 // g_forward_only, called by critic_enqueue and by g_eval_enqueue(train = false) in model.hip -- run the same walk into
 // c->attr, with gen_segmentation fused into gen_17's epilogue and gen_17 itself stored only under debug capture.
+// Third consumer (depgan_set_g_update_storage, model_bf16s_train.hip): the generator update; g_forward_bf16s(train = true)
+// runs the FiLM layers on the sibling kernel that also keeps the pre-FiLM tensor and the ReLU decisions.
 #include "model.h"
 
 #include <stdio.h>
@@ -121,7 +123,8 @@ static int conv_launch_bf16s(depgan_ctx* c, const ConvArgsH& a, int KS) {
   return dg_conv_bf16s(KS, a, c->st);
 }
 
-int g_forward_bf16s(depgan_ctx* c, const float* x, const float* z, float* out, int n, bool fused_head, bool keep_17) {
+int g_forward_bf16s(depgan_ctx* c, const float* x, const float* z, float* out, int n, bool fused_head, bool keep_17,
+                    bool train) {
   {
     ProfScope ps(c, 2, 0.0, "noise mlp fwd");
     DGCHECK(dg_noise_fwd(c->np, z, c->na, n, c->st));
@@ -171,6 +174,20 @@ int g_forward_bf16s(depgan_ctx* c, const float* x, const float* z, float* out, i
         a.ep.head_skip_out = keep_17 ? 0 : 1;
         head_by_conv = true;
         c->h_17_skipped = !keep_17;
+      }
+      if (train && L.kind == G_FILM) {
+        // the generator update: the same launch under the sibling kernel that also keeps RNE_bf16(u) and the FiLM decisions
+        ConvArgsHT t;
+        static_cast<ConvArgsH&>(t) = a;
+        t.u = c->h_u[i];
+        t.fdec = c->h_dec[i];
+        char lb[56];
+        snprintf(lb, sizeof(lb), "conv(bf16s) k3 b%d %dx%d %d->%d +u", n, L.H, L.W, L.Cin, L.Cout);
+        const double px = (double)n * L.H * L.W;
+        ProfScope ps(c, 0, 2.0 * px * L.Cin * L.Cout * 9, lb, bf16s_bytes(a, 3) + px * L.Cout * (2.0 + 0.125),
+                     "igemm_bf16s_train_kernel<3, 9>");
+        DGCHECK(dg_conv_bf16s_train(t, c->st));
+        continue;
       }
       DGCHECK(conv_launch_bf16s(c, a, 3));
     } else if (L.kind == G_POOL) {
@@ -241,8 +258,9 @@ int depgan_get_fwd_only_storage(depgan_ctx* c) { return (c && c->fwd_only_bf16) 
 int depgan_debug_tensor_bf16s(depgan_ctx* c, const char* name, float* host, long cap, int shape[4]) {
   if (!c || !name || !shape) { dg_set_error("debug_tensor_bf16s: null argument"); return DG_ERR_ARG; }
   if (host && cap < 1) { dg_set_error("debug_tensor_bf16s: non-positive capacity"); return DG_ERR_ARG; }
+  if (strncmp(name, "g/u/", 4) == 0) return bf16s_debug_u(c, name, host, cap, shape);
   if (strncmp(name, "g/out/", 6) != 0) {
-    dg_set_error("debug_tensor_bf16s: '%s' is not a g/out/<layer> name", name);
+    dg_set_error("debug_tensor_bf16s: '%s' is not a g/out/<layer> or g/u/<film layer> name", name);
     return DG_ERR_ARG;
   }
   if (!c->h_ready || !c->h_valid) {

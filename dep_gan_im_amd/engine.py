@@ -273,8 +273,9 @@ class Engine:
     def forward_only_storage(self):
         """How the FORWARD-ONLY generator passes of the training closures (the one inside every critic update and
         netG_no_update / the best-of-k evaluations) store their activations: "float32" (default) or "bfloat16"
-        (bf16_mfma engines only; depgan_set_fwd_only_storage).  The generator update keeps float32 storage, so with
-        "bfloat16" netG_no_update(z) and netG_train(z) no longer report identical scalars for the same noise.
+        (bf16_mfma engines only; depgan_set_fwd_only_storage).  The generator update keeps float32 storage unless
+        g_update_storage says otherwise; while it does, netG_no_update(z) and netG_train(z) no longer report identical
+        scalars for the same noise.
         Independent of forward_storage, which governs g_forward / predict.  Every rank of a data-parallel job must
         use the same value."""
         return getattr(self, "_forward_only_storage", "float32")
@@ -286,6 +287,23 @@ class Engine:
             check(self.lib.depgan_set_fwd_only_storage(self.h, 1 if value == "bfloat16" else 0),
                   "depgan_set_fwd_only_storage")
         self._forward_only_storage = value
+
+    @property
+    def g_update_storage(self):
+        """How the generator UPDATE (g_grads, g_step, the update closing gen_iteration) stores the generator's activations:
+        "float32" (default) or "bfloat16" (bf16_mfma engines only; depgan_set_g_update_storage).  With "bfloat16" the
+        update runs the forward of the bf16-storage passes (same output bits) and a backward that reads the bf16 buffers;
+        gradients stay float32.  Independent of forward_only_storage; with both on netG_no_update(z) and netG_train(z)
+        report identical scalars again.  Every rank of a data-parallel job must use the same value."""
+        return getattr(self, "_g_update_storage", "float32")
+
+    @g_update_storage.setter
+    def g_update_storage(self, value):
+        value = self._check_storage(value)
+        if getattr(self, "h", None):
+            check(self.lib.depgan_set_g_update_storage(self.h, 1 if value == "bfloat16" else 0),
+                  "depgan_set_g_update_storage")
+        self._g_update_storage = value
 
     def g_forward(self, x, z, storage=None):
         """Model.predict of the generator.  storage: None = self.forward_storage; "bfloat16" keeps every inter-layer
@@ -480,6 +498,17 @@ class Engine:
         out = np.empty(tuple(shape), np.float32)
         check(self.lib.depgan_debug_tensor(self.h, name.encode(), C.c_void_p(out.ctypes.data), out.size, shape),
               "depgan_debug_tensor")
+        return out
+
+    def debug_film_decision_bf16s(self, layer):
+        """The FiLM ReLU decisions (uint8, 0 / 1, (N, H, W, C)) the last training forward on bfloat16 storage stored for a
+        FiLM layer ("gen_2", ...): what its backward masks with (depgan_debug_film_decision_bf16s)."""
+        shape = (C.c_int * 4)()
+        check(self.lib.depgan_debug_film_decision_bf16s(self.h, layer.encode(), None, 0, shape),
+              "depgan_debug_film_decision_bf16s")
+        out = np.empty(tuple(shape), np.uint8)
+        check(self.lib.depgan_debug_film_decision_bf16s(self.h, layer.encode(), C.c_void_p(out.ctypes.data), out.size, shape),
+              "depgan_debug_film_decision_bf16s")
         return out
 
     def debug_tensor_bf16s(self, name):

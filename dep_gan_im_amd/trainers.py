@@ -140,7 +140,7 @@ class Trainers:
 
 def build_trainers(netG, netD_y2, netD_dem, batchSize=16, delta=10.0, lrD=1e-4, lrG=1e-4, IM_TRSH=0.5,
                    dist=None, device=None, weights_dtype="float32", activations_dtype="float32", f32_split=0,
-                   forward_only_storage="float32"):
+                   forward_only_storage="float32", generator_update_storage="float32"):
     """Builds the loss graph of GT:523-598 for the three models and returns a
     Trainers object.  The models are bound to one engine: afterwards their
     predict()/get_weights()/save() see the trained weights.
@@ -155,6 +155,10 @@ def build_trainers(netG, netD_y2, netD_dem, batchSize=16, delta=10.0, lrD=1e-4, 
     generator forwards of one iteration of the reference schedule) store their activations as bf16
     (Engine.forward_only_storage).  netG_train keeps float32 storage, so netG_no_update(z) and netG_train(z) then differ
     for the same noise by the size of the bf16 rounding effect; every rank of a data-parallel job must use the same value.
+    generator_update_storage="bfloat16" (needs activations_dtype="bfloat16"): opt-in -- the generator update itself runs
+    on bf16 activation storage (Engine.g_update_storage): the forward of the forward-only passes and a backward that reads
+    the bf16 buffers, gradients float32.  With forward_only_storage="bfloat16" as well, netG_no_update(z) and netG_train(z)
+    report identical scalars again.
     dist: a dep_gan_im_amd.dist.DataParallel -- the engine becomes one replica of a data-parallel job (rank 0's
     weights are broadcast, every update all-reduces its gradient arena)."""
     if weights_dtype not in ("float32", "bfloat16"):
@@ -167,6 +171,10 @@ def build_trainers(netG, netD_y2, netD_dem, batchSize=16, delta=10.0, lrD=1e-4, 
         raise ValueError("forward_only_storage must be 'float32' or 'bfloat16'")
     if forward_only_storage == "bfloat16" and activations_dtype != "bfloat16":
         raise ValueError("forward_only_storage='bfloat16' needs activations_dtype='bfloat16' (the bf16 matrix pipe)")
+    if generator_update_storage not in ("float32", "bfloat16"):
+        raise ValueError("generator_update_storage must be 'float32' or 'bfloat16'")
+    if generator_update_storage == "bfloat16" and activations_dtype != "bfloat16":
+        raise ValueError("generator_update_storage='bfloat16' needs activations_dtype='bfloat16' (the bf16 matrix pipe)")
     H, W, nicg = netG.input_shape
     if tuple(netD_y2.input_shape) != (H, W, 1) or tuple(netD_dem.input_shape) != (H, W, 1):
         raise ValueError("critics must take (%d,%d,1) images" % (H, W))
@@ -174,6 +182,7 @@ def build_trainers(netG, netD_y2, netD_dem, batchSize=16, delta=10.0, lrD=1e-4, 
                  beta1=0.0, beta2=0.9, device=device, bf16_weights=(weights_dtype == "bfloat16"),
                  bf16_mfma=(activations_dtype == "bfloat16"), f32_split=f32_split)
     eng.forward_only_storage = forward_only_storage
+    eng.g_update_storage = generator_update_storage
     netG._bind(eng, "G")
     netD_y2._bind(eng, "D_y2")
     netD_dem._bind(eng, "D_dem")

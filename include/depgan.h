@@ -308,9 +308,10 @@ int depgan_debug_tensor_bf16s(depgan_ctx* ctx, const char* name, float* host_dst
  * gen_segmentation fused into gen_17's epilogue, so that gen_17 is neither stored nor read back
  * (DEPGAN_BF16S_HEAD_FUSED=0, read by depgan_create, keeps the two launches: A/B).  The generator UPDATE
  * (depgan_g_grads, depgan_g_step, the update closing depgan_gen_iteration) keeps the fp32-storage forward and the
- * existing backward; depgan_g_forward, depgan_g_forward_bf16s and the DEP-UResNet entries are not affected.  With
+ * existing backward unless depgan_set_g_update_storage(ctx, 1) puts it on the same storage; depgan_g_forward,
+ * depgan_g_forward_bf16s and the DEP-UResNet entries are not affected.  With
  * storage = 0 every path computes the bits it computed before this option existed.
- * Consequence to know: with storage = 1 netG_no_update(z) evaluates the bf16-storage generator and netG_train(z)
+ * Consequence to know (without depgan_set_g_update_storage): with storage = 1 netG_no_update(z) evaluates the bf16-storage generator and netG_train(z)
  * reports the fp32-storage one, so the two no longer return identical scalars for the same noise, and the noise
  * best-of-k picks is the arg-min under the bf16-storage forward.  In a data-parallel job every rank must use the same
  * value (the mode changes no collective; the arg-min is formed from all-reduced pieces, so the ranks agree anyway).
@@ -325,6 +326,69 @@ int depgan_debug_tensor_bf16s(depgan_ctx* ctx, const char* name, float* host_dst
  *   and a message that says so (never stale data); every other layer stays readable. */
 int depgan_set_fwd_only_storage(depgan_ctx* ctx, int storage);
 int depgan_get_fwd_only_storage(depgan_ctx* ctx);
+
+/* ---- bf16 activation storage for the generator UPDATE.  Opt-in, default 0, independent of
+ * depgan_set_fwd_only_storage.  With storage = 1 the training pass of g_eval -- depgan_g_grads, depgan_g_step and the
+ * update closing depgan_gen_iteration -- runs the forward of depgan_g_forward_bf16s (same storage contract, same attr
+ * bits as that call and as the forward-only passes of depgan_set_fwd_only_storage) and a backward that reads every
+ * generator activation from the bf16 buffers: weight-gradient operands staged from bf16 memory, ReLU masks `stored > 0`,
+ * pool arg-max on the stored values.  Gradients (dout / din / du, the gradient arena, the data-parallel all-reduce)
+ * stay fp32; no fp32 copy of a generator activation is written.  The forward additionally keeps, per FiLM layer,
+ * u = RNE_bf16 of the pre-FiLM value (FiLM itself is computed from the unrounded fp32 value, so the output bits do not
+ * change) and the ReLU decision its epilogue took, one bit per element; the FiLM backward uses that stored decision and
+ * never re-derives it from the rounded u.  The gradient is the backward of the stored graph with each storage rounding
+ * treated as the identity (straight-through).  With both modes on, netG_no_update(z) and the pre-update scalars of
+ * netG_train(z) are the same bits again.  With storage = 0 every path computes the bits it computed before.
+ * depgan_set_g_update_storage: 0 = fp32 (default), 1 = bf16; refusals as depgan_set_fwd_only_storage.  Extra memory, on
+ *   top of the bf16 buffers of depgan_g_forward_bf16s: the u buffers, 7.2 M bf16 elements = 14.4 MB per sample of batch
+ *   at 256 x 256, plus 0.9 MB per sample of decision bits; allocated by the first update in the mode and kept.
+ * depgan_debug_tensor_bf16s additionally serves "g/u/<film layer>" (the stored u, widened) after a training forward in
+ *   the mode; before one it is refused with status 1.
+ * depgan_debug_film_decision_bf16s: the stored decisions of a FiLM layer ("gen_2", ...) as one byte (0 / 1) per element,
+ *   (N, H, W, C); host_dst == NULL only reports the shape; status 1 before a training forward in the mode. */
+int depgan_set_g_update_storage(depgan_ctx* ctx, int storage);
+int depgan_get_g_update_storage(depgan_ctx* ctx);
+int depgan_debug_film_decision_bf16s(depgan_ctx* ctx, const char* layer, unsigned char* host_dst, long cap_bytes,
+                                     int shape[4]);
+
+/* Operators of the update on bf16 storage: conventions of the operators below (explicit element strides, stream last,
+ * status 1 for null / non-positive arguments before any HIP call, 3 for shapes the kernels do not cover).
+ * depgan_op_conv2d_film_train_bf16s: depgan_op_conv2d_bf16s (KS = 3, FiLM required) that also stores u_out = RNE_bf16 of
+ *   the pre-FiLM value, dense (B, H, W, Cout) bf16, and dec_bits: bit (c & 7) of byte [pixel (Cout / 8) + c / 8] =
+ *   (FiLM result > 0), B H W Cout / 8 bytes, 4-byte aligned.  `out` has the bits of depgan_op_conv2d_bf16s.
+ * depgan_op_conv2d_wgrad_bf16s: dw[tap][ci][co] (oi = 1: [tap][co][ci]) = sum x[pixel + tap][ci] dy[pixel][co], x a bf16
+ *   view staged as it is, dy an fp32 view rounded to bf16 (RNE) while staged; KS in {1, 3}, Cin % 8 == 0, Cout % 4 == 0;
+ *   colsum (optional, Cout floats) = column sums of the unrounded dy.  Same K order as depgan_op_conv2d_wgrad_bf16:
+ *   bit-equal to it on the widened operand.
+ * depgan_op_conv2d_bwd_data_bf16s: dx = (mask > 0) ? bwd_data(dy, w) + res : 0 with dy fp32 (rounded while staged), res
+ *   fp32 (optional), mask a bf16 view (optional), dx fp32, all (H, W) views of Cin channels except dy (Cout channels).
+ *   deconv = 0: 3x3, w HWIO (Cin, Cout).  deconv = 1: dy is the (2H, 2W) upstream gradient of Conv2DTranspose(2x2,
+ *   stride 2) with (kh, kw, Cout, Cin) weights, contracted as one 1x1 convolution over its four pixel grids.
+ * depgan_op_unpool_mask_bf16s: depgan_op_unpool_mask with a bf16 `a`; C % 8 == 0.  The arg-max of a window is its FIRST
+ *   maximum in the order (0,0), (0,1), (1,0), (1,1), as in the fp32 kernel.
+ * depgan_op_film_bwd_bf16s: dv = dec ? dr : 0; du = dv * fmul; dmul[b][c] = sum_p dv * u; dadd[b][c] = sum_p dv; u dense
+ *   bf16 (B, HW, C), dec_bits as above, dr / du dense fp32; C % 8 == 0, C <= 256.
+ * depgan_op_head_bwd_bf16s: backward = 0: out[c] = sum_p dpre[p] a[p ld + c]; backward = 1: out[p][c] = (a > 0) ?
+ *   dpre[p] w[c] : 0; a bf16 with row stride ld. */
+int depgan_op_conv2d_film_train_bf16s(const void* in, long isB, long isY, long isX, const float* w_hwio, const float* bias,
+                                      const float* scale, const float* shift, const float* film_mul, const float* film_add,
+                                      int film_ld, const void* res, long rsB, long rsY, long rsX, void* out, long osB,
+                                      long osY, long osX, void* u_out, unsigned char* dec_bits, int B, int H, int W, int Cin,
+                                      int Cout, int relu, void* hip_stream);
+int depgan_op_conv2d_wgrad_bf16s(const void* x, long xsB, long xsY, long xsX, const float* dy, long dsB, long dsY, long dsX,
+                                 float* dw, float* colsum, int B, int H, int W, int Cin, int Cout, int KS, int oi,
+                                 void* hip_stream);
+int depgan_op_conv2d_bwd_data_bf16s(const float* dy, long dsB, long dsY, long dsX, const float* w, const float* res,
+                                    long rsB, long rsY, long rsX, const void* mask, long msB, long msY, long msX, float* dx,
+                                    long osB, long osY, long osX, int B, int H, int W, int Cin, int Cout, int deconv,
+                                    void* hip_stream);
+int depgan_op_unpool_mask_bf16s(const float* dpool, long dsB, long dsY, long dsX, const void* a, long asB, long asY, long asX,
+                                const float* skip, long ssB, long ssY, long ssX, float* out, long osB, long osY, long osX,
+                                int B, int Ho, int Wo, int C, void* hip_stream);
+int depgan_op_film_bwd_bf16s(const float* dr, const void* u, const unsigned char* dec_bits, const float* fmul, int film_ld,
+                             float* du, float* dmul, float* dadd, int B, long HW, int C, void* hip_stream);
+int depgan_op_head_bwd_bf16s(int backward, const void* a, long ld, const float* w, const float* dpre, float* out, long P,
+                             int C, void* hip_stream);
 
 /* Operators of that path.  bf16 tensors are void* device pointers with explicit view strides (sample, row, pixel) in
  * ELEMENTS; every bf16 view must be 16-byte aligned (pointer, strides multiples of 8).  Status 1 for null / non-positive
