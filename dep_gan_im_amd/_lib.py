@@ -37,6 +37,7 @@ EXPORTS = [
     "depgan_set_g_update_storage", "depgan_get_g_update_storage", "depgan_debug_film_decision_bf16s",
     "depgan_op_conv2d_film_train_bf16s", "depgan_op_conv2d_wgrad_bf16s", "depgan_op_conv2d_bwd_data_bf16s",
     "depgan_op_unpool_mask_bf16s", "depgan_op_film_bwd_bf16s", "depgan_op_head_bwd_bf16s",
+    "depgan_op_conv2d_fused", "depgan_op_deconv2x2_igemm", "depgan_op_conv2d_wgrad_ex",
 ]
 
 ABI_VERSION = 3          # DEPGAN_ABI_VERSION of the include/depgan.h this binding was written against
@@ -216,6 +217,11 @@ def load():
     lib.depgan_op_unpool_mask_bf16s.argtypes = [vp, L, L, L] * 4 + [i] * 4 + [vp]
     lib.depgan_op_film_bwd_bf16s.argtypes = [vp] * 4 + [i] + [vp] * 3 + [i, L, i, vp]
     lib.depgan_op_head_bwd_bf16s.argtypes = [i, vp, L] + [vp] * 3 + [L, i, vp]
+    # the fp32 convolution kernels with views and the whole fused epilogue (tests/test_gpu_fused_ops.py)
+    lib.depgan_op_conv2d_fused.argtypes = ([vp, L, L, L] + [vp] * 6 + [i] + [vp, L, L, L] * 5 + [vp] * 3 + [i] * 12 +
+                                           [vp])
+    lib.depgan_op_deconv2x2_igemm.argtypes = [i] + [vp, L, L, L] + [vp] * 4 + [vp, L, L, L] * 2 + [i] * 7 + [vp]
+    lib.depgan_op_conv2d_wgrad_ex.argtypes = [vp, L, L, L] * 2 + [vp] * 3 + [i] * 3 + [vp] * 3 + [i] * 7 + [vp]
     _lib = lib
     return lib
 

@@ -270,6 +270,8 @@ int dg_pack_weights(const ConvPlan& pl, const float* src, int srcI, int srcO, in
                     const float* kscale, float* dst, hipStream_t st);
 
 int dg_conv_igemm(const ConvPlan& pl, const ConvArgs& a, hipStream_t st);
+// the argument checks of the MFMA launchers (alignment, fused pool, gathered K, fused head); sets the error text
+int dg_conv_igemm_check(const ConvPlan& pl, const ConvArgs& a);
 // wave-private 3x3 kernel (igemm_wp.hip): no workgroup barrier in steady state; reads the 8-channel-chunk plan's panel
 bool dg_conv_igemm_wp_supported(const ConvPlan& pl, const ConvArgs& a, bool force);
 int dg_conv_igemm_wp(const ConvPlan& pl, const ConvArgs& a, hipStream_t st);

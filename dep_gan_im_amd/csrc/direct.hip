@@ -321,6 +321,11 @@ static int launch_cin12(const ConvArgs& a, hipStream_t st) {
 
 int dg_conv_direct(int KS, const ConvArgs& a_in, hipStream_t st) {
   ConvArgs a = a_in;
+  // epilogue.h has no pooled store and no head, and these kernels no grouped or gathered form: refused, not ignored
+  if (a.ep.pool.p || a.ep.head_out || a.ep.head_skip_out || a.groups > 1 || a.cpt > 0) {
+    dg_set_error("dg_conv_direct: no fused pool, fused head, grouped launch or gathered K on the direct kernels");
+    return DG_ERR_UNSUPPORTED;
+  }
   auto aligned = [](const TView& v) {
     return !v.p || (!(v.sX % 4) && !(v.sY % 4) && !(v.sB % 4) && !(((uintptr_t)v.p) & 15));
   };

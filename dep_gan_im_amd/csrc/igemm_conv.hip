@@ -532,9 +532,8 @@ void dg_conv_igemm_name(const ConvPlan& pl, const ConvArgs& a, char* buf, size_t
   dispatch_variant(pl, a, nullptr, buf, cap);
 }
 
-static int conv_igemm_impl(const ConvPlan& pl, const ConvArgs& a_in, hipStream_t st, bool allow_wp) {
-  ConvArgs a = a_in;
-  const bool is_bf16 = pl.bf16 != 0;
+// Argument checks shared by every MFMA launcher (the wave-private kernel is also launched directly)
+int dg_conv_igemm_check(const ConvPlan& pl, const ConvArgs& a) {
   if (pl.variant < 0) {
     dg_set_error("dg_conv_igemm: no MFMA variant for KS=%d Cin=%d Cout=%d", pl.KS, pl.Cin, pl.Cout);
     return DG_ERR_UNSUPPORTED;
@@ -564,6 +563,13 @@ static int conv_igemm_impl(const ConvPlan& pl, const ConvArgs& a_in, hipStream_t
     dg_set_error("dg_conv_igemm: the fused head needs the fp32 8-channel-chunk 3x3 kernel, 32 output channels, no pool");
     return DG_ERR_ARG;
   }
+  return DG_OK;
+}
+
+static int conv_igemm_impl(const ConvPlan& pl, const ConvArgs& a_in, hipStream_t st, bool allow_wp) {
+  ConvArgs a = a_in;
+  const bool is_bf16 = pl.bf16 != 0;
+  DGCHECK(dg_conv_igemm_check(pl, a));
   if (is_bf16) return dg_conv_igemm_bf16(pl, a, st);
   if (pl.variant == 9) return dg_conv_wino(pl, a, st);   // its panel fits no other kernel
   if (allow_wp && dg_conv_igemm_wp_supported(pl, a, false)) return dg_conv_igemm_wp(pl, a, st);

@@ -229,6 +229,7 @@ bool dg_conv_igemm_wp_supported(const ConvPlan& pl, const ConvArgs& a, bool forc
 
 int dg_conv_igemm_wp(const ConvPlan& pl, const ConvArgs& a_in, hipStream_t st) {
   ConvArgs a = a_in;
+  DGCHECK(dg_conv_igemm_check(pl, a));   // unit tests launch this kernel directly, not through dg_conv_igemm
   const size_t lds = ((size_t)a.Cin * 9 * 32 + (size_t)WP_NW * WP_WAVE_FLOATS) * sizeof(float);
   static DgOncePerDevice once;
   if (once.need())

@@ -225,7 +225,7 @@ struct ProfScope {
   bool live;
   ProfScope(depgan_ctx* c_, int klass, double flops, const char* label = "", double bytes = 0.0,
             const char* kernel = "")
-      : c(c_), live(c_->prof_on) {
+      : c(c_), live(c_ && c_->prof_on) {
     if (!live) return;
     ProfRec r;
     r.klass = klass;

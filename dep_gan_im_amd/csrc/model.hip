@@ -251,12 +251,25 @@ TView strided2(TView v, int di, int dj) {  // pixel grid (2i+di, 2j+dj)
 }
 
 // weight gradient: slabs + reduction (+ optional BN scale / raw copy / OI layout)
-int wgrad_full(depgan_ctx* c, int KS, TView x, TView dy, int N, int H, int W, int Cin, int Cout,
-               const float* scale, float* out, float* raw, int accumulate, int oi, const ColSum* cs) {
+// The workspaces are the caller's (WgradWs): the context's own in the model, a call's own in depgan_op_conv2d_wgrad_ex.
+struct WgradWs {
+  float* part;           // slabs
+  size_t partFloats;
+  float* scratch;        // partial column-sum rows ([nchunks][Cout]) or the scratch of the streaming column-sum pass
+  size_t scratchFloats;
+  bool bf16;             // contraction on the bf16 matrix pipe where wgrad_bf16.hip covers the shape
+  hipStream_t st;
+  depgan_ctx* prof;      // profile records go to this context; null: none
+};
+static int wgrad_run(const WgradWs& ws, int KS, TView x, TView dy, int N, int H, int W, int Cin, int Cout,
+                     const float* scale, float* out, float* raw, int accumulate, int oi, const ColSum* cs) {
+  depgan_ctx* c = ws.prof;
+  float* const scratch = ws.scratch;
+  const size_t cap = ws.scratchFloats;
   WgradArgs a;
   a.x = x;
   a.dy = dy;
-  a.part = c->part;
+  a.part = ws.part;
   a.B = N;
   a.H = H;
   a.W = W;
@@ -272,23 +285,23 @@ int wgrad_full(depgan_ctx* c, int KS, TView x, TView dy, int N, int H, int W, in
   const bool mfma = Cin % 4 == 0 && Cout % 4 == 0 && Cin >= 8;
   // BASELINE configs[3] on the bf16 matrix pipe: the contraction on v_mfma_f32_32x32x16_bf16 (operands rounded while
   // staged, fp32 accumulation); the column sums keep their own streaming pass
-  if (c->cfg.bf16_mfma && mfma && c->wgrad_bf16 && dg_wgrad_bf16_supported(KS, Cin, Cout)) {
-    if (dg_wgrad_bf16_part_floats(KS, N, H, W, Cin, Cout) > c->partFloats) {
+  if (ws.bf16 && mfma && dg_wgrad_bf16_supported(KS, Cin, Cout)) {
+    if (dg_wgrad_bf16_part_floats(KS, N, H, W, Cin, Cout) > ws.partFloats) {
       dg_set_error("wgrad slab workspace too small");
       return DG_ERR_ARG;
     }
     if (cs) {
-      a.colpart = c->scratch;
+      a.colpart = scratch;
       a.colB = cs->B;
     }
     snprintf(lb, sizeof(lb), "wgrad(bf16) k%d b%d %dx%d %d->%d", KS, N, H, W, Cin, Cout);
     {
       ProfScope ps(c, 1, fl, lb);
-      DGCHECK(dg_wgrad_bf16(KS, a, &nch, c->st));
+      DGCHECK(dg_wgrad_bf16(KS, a, &nch, ws.st));
     }
     ProfScope ps(c, 2, 0.0, "slab reduce");
-    return dg_wgrad_finish(c->part, nch, KS * KS, Cin, Cout, scale, out, raw, accumulate, oi, cs ? c->scratch : nullptr,
-                           Cout, cs ? cs->scale : nullptr, cs ? cs->out : nullptr, cs ? cs->raw : nullptr, c->st);
+    return dg_wgrad_finish(ws.part, nch, KS * KS, Cin, Cout, scale, out, raw, accumulate, oi, cs ? scratch : nullptr,
+                           Cout, cs ? cs->scale : nullptr, cs ? cs->out : nullptr, cs ? cs->raw : nullptr, ws.st);
   }
   // Column sums of dy (bias / BN-beta gradients) ride in the MFMA weight-gradient kernel, whose B fragments are the
   // dy values anyway (2 FMAs per 18 MFMAs in one workgroup column; with the register-staged kernel of earlier in the
@@ -296,36 +309,40 @@ int wgrad_full(depgan_ctx* c, int KS, TView x, TView dy, int N, int H, int W, in
   // the separate streaming pass.
   if (cs && !mfma) {
     ProfScope ps(c, 2, 0.0, "colsum");
-    DGCHECK(dg_colsum(dy, cs->B, H, W, Cout, cs->scale, cs->out, cs->raw, 0, c->scratch, c->scratchFloats,
-                      c->st));
+    DGCHECK(dg_colsum(dy, cs->B, H, W, Cout, cs->scale, cs->out, cs->raw, 0, scratch, cap, ws.st));
   }
   if (mfma) {
-    if (dg_wgrad_part_floats(KS, N, H, W, Cin, Cout) > c->partFloats) {
+    if (dg_wgrad_part_floats(KS, N, H, W, Cin, Cout) > ws.partFloats) {
       dg_set_error("wgrad slab workspace too small");
       return DG_ERR_ARG;
     }
     if (cs) {
-      a.colpart = c->scratch;
+      a.colpart = scratch;
       a.colB = cs->B;
     }
     {
       ProfScope ps(c, 1, fl, lb);
-      DGCHECK(dg_wgrad(KS, a, &nch, c->st));
+      DGCHECK(dg_wgrad(KS, a, &nch, ws.st));
     }
     // slab reduction and the column-sum finish in one launch
     ProfScope ps(c, 2, 0.0, "slab reduce");
-    return dg_wgrad_finish(c->part, nch, KS * KS, Cin, Cout, scale, out, raw, accumulate, oi, cs ? c->scratch : nullptr,
-                           Cout, cs ? cs->scale : nullptr, cs ? cs->out : nullptr, cs ? cs->raw : nullptr, c->st);
+    return dg_wgrad_finish(ws.part, nch, KS * KS, Cin, Cout, scale, out, raw, accumulate, oi, cs ? scratch : nullptr,
+                           Cout, cs ? cs->scale : nullptr, cs ? cs->out : nullptr, cs ? cs->raw : nullptr, ws.st);
   } else {
-    if (dg_wgrad_small_part_floats(KS, N, H, W, Cin, Cout) > c->partFloats) {
+    if (dg_wgrad_small_part_floats(KS, N, H, W, Cin, Cout) > ws.partFloats) {
       dg_set_error("wgrad slab workspace too small");
       return DG_ERR_ARG;
     }
     ProfScope ps(c, 2, fl, lb);
-    DGCHECK(dg_wgrad_small(KS, a, &nch, c->st));
+    DGCHECK(dg_wgrad_small(KS, a, &nch, ws.st));
   }
   ProfScope ps(c, 2, 0.0, "slab reduce");
-  return dg_wgrad_reduce(c->part, nch, KS * KS, Cin, Cout, scale, out, raw, accumulate, oi, c->st);
+  return dg_wgrad_reduce(ws.part, nch, KS * KS, Cin, Cout, scale, out, raw, accumulate, oi, ws.st);
+}
+int wgrad_full(depgan_ctx* c, int KS, TView x, TView dy, int N, int H, int W, int Cin, int Cout,
+               const float* scale, float* out, float* raw, int accumulate, int oi, const ColSum* cs) {
+  const WgradWs ws = {c->part, c->partFloats, c->scratch, c->scratchFloats, c->cfg.bf16_mfma && c->wgrad_bf16, c->st, c};
+  return wgrad_run(ws, KS, x, dy, N, H, W, Cin, Cout, scale, out, raw, accumulate, oi, cs);
 }
 
 // ---------------------------------------------------------------------------
@@ -1829,18 +1846,10 @@ int depgan_debug_tensor(depgan_ctx* c, const char* name, float* host, long cap, 
 }
 
 // ---- single operators (unit tests) ----
-static int op_conv(const float* in, const float* w_hwio, const float* bias, float* out, int B, int H, int W, int Cin,
-                   int Cout, int KS, int relu, int path, int bwd, hipStream_t st) {
-  // bwd: compute dx = conv_bwd_data(dy=in (Cout ch), W) -> out (Cin ch)
-  const int ci = bwd ? Cout : Cin, co = bwd ? Cin : Cout;
-  ConvArgs a;
-  memset(&a, 0, sizeof(a));
-  zero_ep(&a.ep);
-  a.in = make_view(const_cast<float*>(in), H, W, ci);
-  a.out = make_view(out, H, W, co);
-  a.B = B; a.H = H; a.W = W; a.Cin = ci; a.Cout = co;
-  a.ep.bias = bias;
-  a.ep.relu = relu;
+// a: views, sizes and epilogue of the launch (bwd: Cin / Cout already in their launch roles); w_hwio (KS, KS, Cin, Cout)
+// of the layer.  Plans, packs and launches on the kernel `path` names; what that kernel does not cover is an error.
+static int op_conv_run(ConvArgs a, const float* w_hwio, int Cin, int Cout, int KS, int path, int bwd, hipStream_t st) {
+  const int ci = a.Cin, co = a.Cout;
   ConvPlan pl = (path == 3) ? dg_plan_conv_bf16(KS, ci, co)
                 : (path == 4 || path == 5) ? dg_plan_conv_split(KS, ci, co, path == 5 ? 3 : 2)
                 : (path == 6) ? dg_plan_conv_items(KS, ci, co, 1L << 30) : dg_plan_conv(KS, ci, co);
@@ -1879,6 +1888,21 @@ static int op_conv(const float* in, const float* w_hwio, const float* bias, floa
     a.wsT = (long)Cin * Cout; a.wsI = 1; a.wsO = Cout; a.flip = 1;
   }
   return dg_conv_direct(KS, a, st);
+}
+
+static int op_conv(const float* in, const float* w_hwio, const float* bias, float* out, int B, int H, int W, int Cin,
+                   int Cout, int KS, int relu, int path, int bwd, hipStream_t st) {
+  // bwd: compute dx = conv_bwd_data(dy=in (Cout ch), W) -> out (Cin ch)
+  const int ci = bwd ? Cout : Cin, co = bwd ? Cin : Cout;
+  ConvArgs a;
+  memset(&a, 0, sizeof(a));
+  zero_ep(&a.ep);
+  a.in = make_view(const_cast<float*>(in), H, W, ci);
+  a.out = make_view(out, H, W, co);
+  a.B = B; a.H = H; a.W = W; a.Cin = ci; a.Cout = co;
+  a.ep.bias = bias;
+  a.ep.relu = relu;
+  return op_conv_run(a, w_hwio, Cin, Cout, KS, path, bwd, st);
 }
 
 // diagnostics: run the MFMA conv with per-workgroup phase stamps (16 x u64 per workgroup) into `stamps`
@@ -2060,6 +2084,203 @@ static int op_alloc(float** p, size_t floats, const char* who) {
   return DG_OK;
 }
 static size_t op_scratch(long scratch_floats, size_t need) { return scratch_floats > 0 ? (size_t)scratch_floats : need; }
+static TView op_view_or_null(const float* p, long sB, long sY, long sX) {
+  return p ? op_view(p, sB, sY, sX) : null_view();
+}
+
+// ---- the fp32 convolution kernels with the whole fused epilogue and strided views (unit tests) ----
+static bool op_view_bad(const float* p, long sB, long sY, long sX) { return !p || sB < 1 || sY < 1 || sX < 1; }
+
+int depgan_op_conv2d_fused(const float* in, long isB, long isY, long isX, const float* w_hwio, const float* bias,
+                           const float* scale, const float* shift, const float* film_mul, const float* film_add,
+                           int film_ld, float* out, long osB, long osY, long osX, float* out_pre, long psB, long psY,
+                           long psX, const float* res, long rsB, long rsY, long rsX, const float* mask, long msB,
+                           long msY, long msX, float* pool, long qsB, long qsY, long qsX, const float* head_w,
+                           const float* head_b, float* head_out, int head_tanh, int head_skip_out, int B, int H, int W,
+                           int Cin, int Cout, int KS, int relu, int accumulate, int path, int bwd, void* stream) {
+  if (op_view_bad(in, isB, isY, isX) || op_view_bad(out, osB, osY, osX) || !w_hwio || B < 1 || H < 1 || W < 1 || Cin < 1 ||
+      Cout < 1 || (KS != 1 && KS != 3 && KS != 5) || (out_pre && op_view_bad(out_pre, psB, psY, psX)) ||
+      (res && op_view_bad(res, rsB, rsY, rsX)) || (mask && op_view_bad(mask, msB, msY, msX)) ||
+      (pool && op_view_bad(pool, qsB, qsY, qsX))) {
+    dg_set_error("op_conv2d_fused: null or non-positive argument");
+    return DG_ERR_ARG;
+  }
+  const int co = bwd ? Cin : Cout;
+  if (!scale != !shift || !film_mul != !film_add || (film_mul && film_ld < co)) {
+    dg_set_error("op_conv2d_fused: scale / shift and film_mul / film_add come in pairs, film_ld >= output channels");
+    return DG_ERR_ARG;
+  }
+  if ((head_w || head_b || head_out) && !(head_w && head_b && head_out)) { dg_set_error("op_conv2d_fused: null head argument"); return DG_ERR_ARG; }
+  if (head_skip_out && !head_out) { dg_set_error("op_conv2d_fused: head_skip_out without a head"); return DG_ERR_ARG; }
+  if (path < 1 || path > 8) { dg_set_error("op_conv2d_fused: path must be 1 ... 8"); return DG_ERR_ARG; }
+  ConvArgs a;
+  memset(&a, 0, sizeof(a));
+  zero_ep(&a.ep);
+  a.in = op_view(in, isB, isY, isX);
+  a.out = op_view(out, osB, osY, osX);
+  a.B = B; a.H = H; a.W = W; a.Cin = bwd ? Cout : Cin; a.Cout = co;
+  Epilogue& e = a.ep;
+  e.bias = bias; e.scale = scale; e.shift = shift;
+  e.film_mul = film_mul; e.film_add = film_add; e.film_ld = film_ld;
+  e.out_pre = op_view_or_null(out_pre, psB, psY, psX);
+  e.res = op_view_or_null(res, rsB, rsY, rsX);
+  e.mask = op_view_or_null(mask, msB, msY, msX);
+  e.pool = op_view_or_null(pool, qsB, qsY, qsX);
+  e.relu = relu; e.accumulate = accumulate;
+  e.head_w = head_w; e.head_b = head_b; e.head_out = head_out;
+  e.head_tanh = head_tanh; e.head_skip_out = head_skip_out;
+  return op_conv_run(a, w_hwio, Cin, Cout, KS, path, bwd ? 1 : 0, (hipStream_t)stream);
+}
+
+// upload and run pack jobs whose destinations interleave (GLayer::wpb_all); synchronises: `jobs` is the caller's
+static int op_pack_jobs(PackJob* jobs, int n, hipStream_t st) {
+  const unsigned nb = dg_pack_layout(jobs, n);
+  PackJob* jd = nullptr;
+  HIPCHECK(hipMalloc((void**)&jd, n * sizeof(PackJob)));
+  hipError_t e = hipMemcpyAsync(jd, jobs, n * sizeof(PackJob), hipMemcpyHostToDevice, st);
+  int rc = DG_OK;
+  if (e != hipSuccess) { dg_set_error("op_pack_jobs: upload failed: %s", hipGetErrorString(e)); rc = DG_ERR_HIP; }
+  if (rc == DG_OK) rc = dg_pack_weights_batch(jd, n, nb, st);
+  hipStreamSynchronize(st);
+  hipFree(jd);
+  return rc;
+}
+
+int depgan_op_deconv2x2_igemm(int form, const float* in, long isB, long isY, long isX, const float* w_hwoi,
+                              const float* bias, const float* scale, const float* shift, float* out, long osB, long osY,
+                              long osX, const float* mask, long msB, long msY, long msX, int B, int H, int W, int Cin,
+                              int Cout, int relu, int path, void* stream) {
+  if (op_view_bad(in, isB, isY, isX) || op_view_bad(out, osB, osY, osX) || !w_hwoi || B < 1 || H < 1 || W < 1 || Cin < 1 ||
+      Cout < 1 || (mask && op_view_bad(mask, msB, msY, msX))) {
+    dg_set_error("op_deconv2x2_igemm: null or non-positive argument");
+    return DG_ERR_ARG;
+  }
+  if (form < 0 || form > 2 || !scale != !shift || (path != 1 && path != 3 && path != 8)) {
+    dg_set_error("op_deconv2x2_igemm: form must be 0, 1 or 2, path 1, 3 or 8, scale and shift come as a pair");
+    return DG_ERR_ARG;
+  }
+  if (form == 0 ? mask != nullptr : (bias || scale || relu)) {
+    dg_set_error("op_deconv2x2_igemm: the forward takes bias / scale / shift / relu, the backward-data forms a mask");
+    return DG_ERR_ARG;
+  }
+  if (path == 8) { dg_set_error("op_deconv2x2_igemm: the Winograd kernel has no 1x1 form"); return DG_ERR_UNSUPPORTED; }
+  auto plan = [&](int ci, int co) { return path == 3 ? dg_plan_conv_bf16(1, ci, co) : dg_plan_conv(1, ci, co); };
+  auto covered = [&](const ConvPlan& p) { return p.variant >= 0 && (path == 3) == (p.bf16 != 0); };
+  hipStream_t st = (hipStream_t)stream;
+  ConvArgs a;
+  memset(&a, 0, sizeof(a));
+  zero_ep(&a.ep);
+  a.B = B; a.H = H; a.W = W;
+  float* wp = nullptr;
+  int rc = DG_OK;
+  if (form == 0) {
+    // as g_forward: four 1x1 convolutions of one input, tap (di, dj) writing the pixel grid (2i+di, 2j+dj), one launch
+    const ConvPlan pf = plan(Cin, Cout);
+    if (!covered(pf)) { dg_set_error("op_deconv2x2_igemm: no MFMA plan for %d -> %d on path %d", Cin, Cout, path); return DG_ERR_UNSUPPORTED; }
+    const TView o = op_view(out, osB, osY, osX);
+    a.in = op_view(in, isB, isY, isX);
+    a.out = strided2(o, 0, 0);
+    a.Cin = Cin; a.Cout = Cout;
+    a.ep.bias = bias; a.ep.scale = scale; a.ep.shift = shift; a.ep.relu = relu;
+    a.groups = 4;
+    HIPCHECK(hipMalloc((void**)&wp, 4 * pf.packedFloats * sizeof(float)));
+    for (int t = 0; t < 4 && rc == DG_OK; ++t) {
+      float* dst = wp + (size_t)t * pf.packedFloats;
+      rc = dg_pack_weights(pf, w_hwoi + (size_t)t * Cout * Cin, Cin, Cout, 1, 0, 0, nullptr, dst, st);
+      a.w_group[t] = dst;
+      a.out_group_off[t] = strided2(o, t / 2, t % 2).p - a.out.p;
+    }
+    a.w = wp;
+    if (rc == DG_OK) rc = dg_conv_igemm(pf, a, st);
+  } else {
+    // as deconv_bwd_data: in = the upstream gradient (B, 2H, 2W, Cout), out = dIn (B, H, W, Cin)
+    const ConvPlan pb = plan(Cout, Cin);
+    if (!covered(pb)) { dg_set_error("op_deconv2x2_igemm: no MFMA plan for %d -> %d on path %d", Cout, Cin, path); return DG_ERR_UNSUPPORTED; }
+    const TView d = op_view(in, isB, isY, isX);
+    a.out = op_view(out, osB, osY, osX);
+    a.Cout = Cin;
+    a.ep.mask = op_view_or_null(mask, msB, msY, msX);
+    if (form == 1) {
+      const ConvPlan pbf = plan(4 * Cout, Cin);
+      if (!(pbf.variant == pb.variant && pbf.bf16 == pb.bf16 && (Cout % pb.CK) == 0 && pbf.packedFloats == 4 * pb.packedFloats)) {
+        dg_set_error("op_deconv2x2_igemm: the gathered 1x1 form does not cover %d -> %d", Cout, Cin);
+        return DG_ERR_UNSUPPORTED;
+      }
+      HIPCHECK(hipMalloc((void**)&wp, pbf.packedFloats * sizeof(float)));
+      // the four per-tap panels interleaved per channel tile, as refresh_generator builds GLayer::wpb_all
+      const size_t blk = (size_t)pb.nCC * pb.NT * pb.CK;   // elements
+      PackJob jobs[4];
+      for (int t = 0; t < 4 && rc == DG_OK; ++t) {
+        float* dst = reinterpret_cast<float*>(reinterpret_cast<char*>(wp) + t * blk * dg_plan_elem_bytes(pb));
+        rc = dg_pack_job(pb, w_hwoi + (size_t)t * Cout * Cin, Cin, Cout, 1, 1, 0, nullptr, dst, 4 * blk, &jobs[t]);
+      }
+      if (rc == DG_OK) rc = op_pack_jobs(jobs, 4, st);
+      a.in = strided2(d, 0, 0);
+      a.Cin = 4 * Cout;
+      a.cpt = Cout / pb.CK;
+      for (int t = 0; t < 4; ++t) a.in_run_off[t] = (long)(t / 2) * d.sY + (long)(t % 2) * d.sX;
+      a.w = wp;
+      if (rc == DG_OK) rc = dg_conv_igemm(pbf, a, st);
+    } else {
+      HIPCHECK(hipMalloc((void**)&wp, 4 * pb.packedFloats * sizeof(float)));
+      a.Cin = Cout;
+      for (int t = 0; t < 4 && rc == DG_OK; ++t) {
+        float* dst = wp + (size_t)t * pb.packedFloats;
+        rc = dg_pack_weights(pb, w_hwoi + (size_t)t * Cout * Cin, Cin, Cout, 1, 1, 0, nullptr, dst, st);
+        if (rc != DG_OK) break;
+        a.in = strided2(d, t / 2, t % 2);
+        a.w = dst;
+        a.ep.accumulate = (t > 0);
+        rc = dg_conv_igemm(pb, a, st);
+      }
+    }
+  }
+  hipStreamSynchronize(st);
+  hipFree(wp);
+  return rc;
+}
+
+int depgan_op_conv2d_wgrad_ex(const float* x, long xsB, long xsY, long xsX, const float* dy, long dsB, long dsY,
+                              long dsX, const float* scale, float* dw, float* raw, int accumulate, int oi,
+                              int colB, const float* colscale, float* colout, float* colraw, int B, int H, int W,
+                              int Cin, int Cout, int KS, int bf16, void* stream) {
+  if (op_view_bad(x, xsB, xsY, xsX) || op_view_bad(dy, dsB, dsY, dsX) || !dw || B < 1 || H < 1 || W < 1 || Cin < 1 || Cout < 1 ||
+      (KS != 1 && KS != 3 && KS != 5)) {
+    dg_set_error("op_conv2d_wgrad_ex: null or non-positive argument");
+    return DG_ERR_ARG;
+  }
+  const bool cols = colout || colraw;
+  if ((bf16 != 0 && bf16 != 1) || (cols ? (colB < 1 || colB > B) : (colB != 0 || colscale != nullptr))) {
+    dg_set_error("op_conv2d_wgrad_ex: bf16 must be 0 or 1; column sums need colout or colraw and 1 <= colB <= B");
+    return DG_ERR_ARG;
+  }
+  const bool mfma = Cin % 4 == 0 && Cout % 4 == 0 && Cin >= 8;
+  if (bf16 && !(mfma && dg_wgrad_bf16_supported(KS, Cin, Cout))) {
+    dg_set_error("op_conv2d_wgrad_ex: the bf16 weight-gradient kernel does not cover %d -> %d", Cin, Cout);
+    return DG_ERR_UNSUPPORTED;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  WgradWs ws;
+  memset(&ws, 0, sizeof(ws));
+  ws.partFloats = bf16 ? dg_wgrad_bf16_part_floats(KS, B, H, W, Cin, Cout)
+                  : mfma ? dg_wgrad_part_floats(KS, B, H, W, Cin, Cout) : dg_wgrad_small_part_floats(KS, B, H, W, Cin, Cout);
+  // one partial column-sum row per slab (MFMA kernels), or the scratch of the streaming pass (edge kernels)
+  ws.scratchFloats = mfma ? ws.partFloats / ((size_t)KS * KS * Cin) : (cols ? dg_colsum_scratch(colB, H, W, Cout) : 0);
+  ws.bf16 = bf16 != 0;
+  ws.st = st;
+  DGCHECK(op_alloc(&ws.part, ws.partFloats, "op_conv2d_wgrad_ex"));
+  int rc = op_alloc(&ws.scratch, ws.scratchFloats, "op_conv2d_wgrad_ex");
+  if (rc == DG_OK) {
+    const ColSum cs = {colB, colscale, colout, colraw};
+    rc = wgrad_run(ws, KS, op_view(x, xsB, xsY, xsX), op_view(dy, dsB, dsY, dsX), B, H, W, Cin, Cout, scale, dw, raw, accumulate,
+                   oi, cols ? &cs : nullptr);
+  }
+  hipStreamSynchronize(st);
+  hipFree(ws.part);
+  hipFree(ws.scratch);
+  return rc;
+}
+
 
 int depgan_op_bn_moments(const float* x, long sB, long sY, long sX, int B, int H, int W, int C, float* mean, float* var,
                          long scratch_floats, void* stream) {
@@ -2174,9 +2395,6 @@ int depgan_op_small_gemm(int form, const float* A, const float* Bm, const float*
 
 // ---- the two-critic step's HBM-bound operators (ops.hip) and the noise MLP (noise.hip), each the dg_* function the
 // model calls; views as above, scratch_floats <= 0 for what the launch needs ----
-static TView op_view_or_null(const float* p, long sB, long sY, long sX) {
-  return p ? op_view(p, sB, sY, sX) : null_view();
-}
 extern "C++" {
 // allocate a reduction scratch of op_scratch(scratch_floats, need) floats, run the call, synchronise, free
 template <typename F>

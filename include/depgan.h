@@ -460,6 +460,47 @@ int depgan_op_deconv2x2(const float* in, const float* w_hwoi, const float* bias,
 int depgan_op_deconv2x2_wgrad(const float* in, const float* dout, float* dw_hwoi, float* colsum, int B, int H, int W,
                               int Cin, int Cout, void* hip_stream);
 
+/* The fp32 convolution kernels as the model launches them: every operand an NHWC view with the float strides
+ * (sB, sY, sX) and channel stride 1, and the whole fused epilogue, applied to the raw contraction acc in this order:
+ *   v = (acc + bias[co]) * scale[co] + shift[co];  out_pre = v;  v = v * film_mul[b][co] + film_add[b][co];
+ *   v = max(v, 0) if relu;  v += res;  v = mask > 0 ? v : 0;  out = accumulate ? out + v : v;
+ *   pool (view of (H/2, W/2) pixels) = 2x2 / stride-2 maximum of out;
+ *   head_out[b][y][x] = act(sum_co out[co] head_w[co] + head_b[0]), act = tanh when head_tanh (dense (B, H, W));
+ *   head_skip_out: out itself is not stored.
+ * Optional operands are NULL (their strides are then ignored); scale / shift and film_mul / film_add come in pairs;
+ * film_mul / film_add are rows of film_ld floats per sample.  w_hwio is (KS, KS, Cin, Cout); bwd = 1 is the
+ * backward-data form: `in` has Cout channels, `out` (and the epilogue operands) Cin.  path as in depgan_op_conv2d:
+ * 1 MFMA, 2 direct, 3 bf16 pipe, 4 / 5 split, 6 8-channel chunks, 7 wave-private, 8 Winograd.  Status 1 for null or
+ * non-positive arguments (before any HIP call) and whatever the launcher's argument checks refuse, 3 for what the kernel
+ * of that path does not cover; nothing is written then. */
+int depgan_op_conv2d_fused(const float* in, long isB, long isY, long isX, const float* w_hwio, const float* bias,
+                           const float* scale, const float* shift, const float* film_mul, const float* film_add,
+                           int film_ld, float* out, long osB, long osY, long osX, float* out_pre, long psB, long psY,
+                           long psX, const float* res, long rsB, long rsY, long rsX, const float* mask, long msB,
+                           long msY, long msX, float* pool, long qsB, long qsY, long qsX, const float* head_w,
+                           const float* head_b, float* head_out, int head_tanh, int head_skip_out, int B, int H, int W,
+                           int Cin, int Cout, int KS, int relu, int accumulate, int path, int bwd, void* hip_stream);
+/* The 2x2 / stride-2 transposed convolution on the implicit-GEMM kernels, w_hwoi the Keras kernel (2, 2, Cout, Cin).
+ * form 0: forward as ONE grouped launch of four 1x1 convolutions: in (B, H, W, Cin) -> out (B, 2H, 2W, Cout), with
+ *         bias / scale+shift / relu; mask must be NULL.
+ * form 1: backward-data as ONE 1x1 convolution whose K axis gathers the four pixel grids of the upstream gradient:
+ *         in = dOut (B, 2H, 2W, Cout) -> out = dIn (B, H, W, Cin), times (mask > 0) when mask (B, H, W, Cin) is given.
+ * form 2: the same as four accumulating 1x1 launches, one per pixel grid.
+ * path 1 (fp32 MFMA), 3 (bf16 pipe) or 8 (Winograd: no 1x1 form, status 3). */
+int depgan_op_deconv2x2_igemm(int form, const float* in, long isB, long isY, long isX, const float* w_hwoi,
+                              const float* bias, const float* scale, const float* shift, float* out, long osB, long osY,
+                              long osX, const float* mask, long msB, long msY, long msX, int B, int H, int W, int Cin,
+                              int Cout, int relu, int path, void* hip_stream);
+/* Weight gradient as the model runs it (slab kernel, then the finishing launch): dw[tap][ci][co] (oi = 1:
+ * [tap][co][ci]) (+)= scale[co] * g, raw (optional) = g, g[tap][ci][co] = sum over pixels of x (shifted by the tap) dy;
+ * x and dy strided views.  Column sums of dy over the samples b < colB when colout or colraw is given:
+ * colout[co] = colscale[co] (or 1) * sum, colraw[co] = sum; without them colB must be 0.  bf16 = 1: the contraction on
+ * the bf16 matrix pipe (status 3 where wgrad_bf16.hip does not cover the shape). */
+int depgan_op_conv2d_wgrad_ex(const float* x, long xsB, long xsY, long xsX, const float* dy, long dsB, long dsY,
+                              long dsX, const float* scale, float* dw, float* raw, int accumulate, int oi, int colB,
+                              const float* colscale, float* colout, float* colraw, int B, int H, int W, int Cin,
+                              int Cout, int KS, int bf16, void* hip_stream);
+
 /* Learning-phase-1 operators (the DEP-UResNet training step's batch-statistics BatchNorm, Dropout, softmax and
  * cross-entropy), each the internal function uresnet.hip calls.  Device pointers; every NHWC view has the float strides
  * (sB, sY, sX) and channel stride 1, so a channel slice of a wider buffer is (p + c0, H*W*Ctot, W*Ctot, Ctot).

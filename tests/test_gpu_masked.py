@@ -219,9 +219,10 @@ def test_gradients_256_under_hip_masks(lib, seed, noisy, trained):
 
 def test_headline_config_backward_batch32_256(lib):
     """BASELINE configs[1] at its own size (batch 32, 256x256x1, fp32): critic("D_y2"), critic("D_dem") and
-    generator("grads") against the oracle on the whole batch -- the launches the benchmark times (8-channel-chunk
-    igemm_conv_kernel<32,3,8,9,true> from 1536 items up, the persistent 5x5 kernels in backward-data and u-forward, the
-    fused transposed-convolution kernels).  The oracle's convolutions run in fp32 here (a float64 batch-32 step is
+    generator("grads") against the oracle on the whole batch -- the launches the benchmark times (the 3x3 layers with
+    even sizes on the Winograd wino_conv_kernel, which the default plan takes before the 8-channel-chunk
+    igemm_conv_kernel<32,3,8,9,true>; the persistent 5x5 kernels in backward-data and u-forward; the fused
+    transposed-convolution kernels).  The oracle's convolutions run in fp32 here (a float64 batch-32 step is
     minutes of CPU) and its parameter-gradient reductions in float64 (oracle/manual.py _es / _rs), under the HIP path's
     decisions; per-tensor bound printed and asserted."""
     from oracle import depgan_oracle as O

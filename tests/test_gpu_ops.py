@@ -1,7 +1,12 @@
 """GPU parity, operator level, through the C ABI: every HIP convolution form
 (MFMA implicit GEMM, direct edge kernels, MFMA / VALU weight gradient) against a
-float64 torch-CPU reference of the same op, including ragged spatial sizes,
-channel counts that exercise every kernel variant and the concat/strided views."""
+float64 torch-CPU reference of the same op, including ragged spatial sizes and
+channel counts that exercise every kernel variant.  The entries used here build dense
+views with bias and ReLU only: this file checks the contraction.  The fused epilogue
+(BN affine, out_pre, FiLM, res, mask, accumulate, pooled store, fused head), strided
+views (concat slices, sample windows, strided pixel grids), the grouped and gathered-K
+launches and the weight gradient's scale / raw / accumulate / OI / column sums are
+checked bit for bit in tests/test_gpu_fused_ops.py."""
 import ctypes as C
 
 import numpy as np
