@@ -15,16 +15,16 @@ struct ConvArgsHT : ConvArgsH {
 int dg_conv_bf16s_train(const ConvArgsHT& a, hipStream_t st);
 static inline size_t dg_film_dec_bytes(int B, int H, int W, int C) { return (size_t)B * H * W * (C / 8); }
 
-// Backward-data (3x3, or 1x1 with ConvArgs::cpt gathering the four grids of a transposed convolution) on
-// igemm_bf16_kernel's main loop -- dy fp32 in HBM, rounded while staged, as in every bf16_mfma context -- whose ReLU mask
+// Backward-data (3x3, or 1x1 with ConvArgs::cpt gathering the four grids of a transposed convolution) on the same
+// included main-loop text as igemm_bf16_kernel (igemm_bf16_main.inc) -- dy fp32 in HBM, rounded while staged, as in every bf16_mfma context -- whose ReLU mask
 // operand is a bf16 view: out = accumulate ? out + v : v, v = (mask_h > 0) ? acc + res : 0.  Of a.ep only res and
 // accumulate are read (everything else must be unset); a.Cout % 32 == 0, a.Cin % 4 == 0.
 int dg_conv_bf16_mh(const ConvPlan& pl, const ConvArgs& a, TViewH mask_h, hipStream_t st);
 const char* dg_conv_bf16_mh_name(int KS);
 
 // Weight gradient on the bf16 pipe, activation operand staged from bf16 memory (16-byte pieces of 8 bf16, no rounding
-// step), dy staged as fp32 and rounded while committed: wgrad_bf16_kernel's tiles, LDS images, chunking, K order and slab
-// format -- bit-equal to dg_wgrad_bf16 on the widened operand.  KS in {1, 3}; Cin % 8 == 0, Cout % 4 == 0.
+// step), dy staged as fp32 and rounded while committed: the same included text as wgrad_bf16_kernel
+// (wgrad_bf16_kernel.inc), hence its tiles, LDS images, chunking, K order and slab format -- bit-equal to dg_wgrad_bf16 on the widened operand.  KS in {1, 3}; Cin % 8 == 0, Cout % 4 == 0.
 struct WgradArgsH {
   TViewH x;
   TView dy;

@@ -4,6 +4,7 @@
 // igemm_bf16s_train.hip includes it a third time with IGEMM_BF16S_TRAIN = 1 and IGEMM_BF16S_ARGS = ConvArgsHT (ConvArgsH
 // plus `u` and `fdec`): the FiLM layers of the generator update, which also store RNE_bf16 of the pre-FiLM tensor and
 // the ReLU decision the epilogue took, one bit per element.  Both default to what the two kernels above are built with.
+// The main loop is the same included text as igemm_bf16_kernel's (igemm_bf16_main.inc with the bf16 operand form).
 #ifndef IGEMM_BF16S_TRAIN
 #define IGEMM_BF16S_TRAIN 0
 #define IGEMM_BF16S_ARGS ConvArgsH
@@ -13,166 +14,15 @@ template <int KS, int TAPG>
 __global__ __launch_bounds__(256, 2) void IGEMM_BF16S_KERNEL(const IGEMM_BF16S_ARGS a) {
   constexpr bool HEAD = IGEMM_BF16S_HEAD != 0;
   constexpr int NT = 32, MT = 2, CK = 32;
-  constexpr int PAD = KS / 2;
-  constexpr int TW = 16 + KS - 1;
-  constexpr int PIXT = TW * TW;
-  constexpr int NTAPS = KS * KS;
-  constexpr int NG = NTAPS / TAPG;
-  constexpr int ROWB = 80;   // bytes per LDS row: 32 bf16 + 16 bytes of padding, as igemm_bf16_kernel
-  constexpr int XV = CK / 8;  // 16-byte pieces (8 bf16) of one pixel's chunk in global memory
-  constexpr int XTOT = PIXT * XV;
-  constexpr int XPIECES = (XTOT + 255) / 256;
-  constexpr int WV = CK / 8;  // 16-byte pieces of one packed weight row
-  constexpr int WTOT = TAPG * NT * WV;
-  constexpr int WPIECES = (WTOT + 255) / 256;
-  static_assert(NTAPS % TAPG == 0, "tap grouping");
-  typedef f32x16 acc_t;
-
-  extern __shared__ __attribute__((aligned(16))) float smem[];
-  char* xs = reinterpret_cast<char*>(smem);      // [PIXT][ROWB]
-  char* ws = xs + PIXT * ROWB;                   // [TAPG][NT][ROWB]
-
-  const int tid = threadIdx.x;
-  const int tilesX = (a.W + 15) >> 4, tilesY = (a.H + 15) >> 4;
-  // work item -> (pixel tile, channel tile): the XCD-aware order of igemm_conv.hip
-  const unsigned nNTall = (unsigned)a.lgy, nPix = (unsigned)a.lgx;
-  const unsigned id = blockIdx.x;
-  int t, ntile;
-  if ((nPix & 7u) == 0) {
-    const unsigned x = id & 7u, sl = id >> 3;
-    ntile = (int)(sl % nNTall);
-    t = (int)(x * (nPix >> 3) + sl / nNTall);
-  } else {
-    t = (int)(id % nPix);
-    ntile = (int)(id / nPix);
-  }
-  const int tx0 = (t % tilesX) * 16;
-  t /= tilesX;
-  const int ty0 = (t % tilesY) * 16;
-  const int b = t / tilesY;
-  const int ngrp = a.groups > 1 ? a.groups : 1;
-  const int nNTg = (int)nNTall / ngrp;
-  const int grp = ntile / nNTg;
-  ntile -= grp * nNTg;
-  const __bf16* wbase = reinterpret_cast<const __bf16*>(a.groups > 1 ? a.w_group[grp] : a.w);
-  const long out_goff = a.groups > 1 ? a.out_group_off[grp] : 0;
-  const int n0 = ntile * NT;
-  const int nCC = (a.Cin + CK - 1) / CK;
-  const int NS = nCC * NG;
-  const __bf16* inb = a.in.p + (long)b * a.in.sB;
-
-  u32x4 xr[XPIECES];
-  u32x4 wr[WPIECES];
-  auto prefetch = [&](int s) {
-    const int cc = s / NG, tg = s - cc * NG;
-    if (tg == 0) {
-#pragma unroll
-      for (int i = 0; i < XPIECES; ++i) {
-        const int q = tid + i * 256;
-        u32x4 v = {0u, 0u, 0u, 0u};
-        if (q < XTOT) {
-          const int pix = q / XV, part = q - pix * XV;
-          const int ly = pix / TW, lx = pix - ly * TW;
-          const int iy = ty0 + ly - PAD, ix = tx0 + lx - PAD;
-          const int c = cc * CK + part * 8;
-          // Cin is a multiple of 8 (launcher): a piece is inside the channels or outside, never across the end
-          if (iy >= 0 && iy < a.H && ix >= 0 && ix < a.W && c < a.Cin)
-            v = *reinterpret_cast<const u32x4*>(inb + (long)iy * a.in.sY + (long)ix * a.in.sX + c);
-        }
-        xr[i] = v;
-      }
-    }
-    const __bf16* wsrc = wbase + ((size_t)((size_t)ntile * nCC + cc) * NTAPS + (size_t)tg * TAPG) * (NT * CK);
-#pragma unroll
-    for (int i = 0; i < WPIECES; ++i) {
-      const int q = tid + i * 256;
-      u32x4 v = {0u, 0u, 0u, 0u};
-      if (q < WTOT) v = *reinterpret_cast<const u32x4*>(wsrc + (size_t)q * 8);
-      wr[i] = v;
-    }
-  };
-  auto commit = [&](int s) {
-    const int tg = s % NG;
-    if (tg == 0) {
-#pragma unroll
-      for (int i = 0; i < XPIECES; ++i) {
-        const int q = tid + i * 256;
-        if (q < XTOT) {
-          const int pix = q / XV, part = q - pix * XV;
-          *reinterpret_cast<u32x4*>(xs + pix * ROWB + part * 16) = xr[i];   // a copy: the operand is bf16 already
-        }
-      }
-    }
-#pragma unroll
-    for (int i = 0; i < WPIECES; ++i) {
-      const int q = tid + i * 256;
-      if (q < WTOT) {
-        const int row = q / WV, part = q - row * WV;
-        *reinterpret_cast<u32x4*>(ws + row * ROWB + part * 16) = wr[i];
-      }
-    }
-  };
-
-  const int lane = tid & 63, wv = tid >> 6;
-  const int r = lane & 31, h = lane >> 5;   // h: which 8 of the 16 k-values of an MFMA this lane carries
-  int apix[MT];
-#pragma unroll
-  for (int mt = 0; mt < MT; ++mt) {
-    const int py = 4 * wv + 2 * mt + (r >> 4), px = r & 15;
-    apix[mt] = (py * TW + px) * ROWB + 16 * h;
-  }
-  const int boff = r * ROWB + 16 * h;
-
-  acc_t acc[MT];
-#pragma unroll
-  for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-    for (int j = 0; j < 16; ++j) acc[mt][j] = 0.f;
-
-  prefetch(0);
-  for (int s = 0; s < NS; ++s) {
-    __syncthreads();
-    commit(s);
-    __syncthreads();
-    if (s + 1 < NS) prefetch(s + 1);
-    const int tg = s % NG;
-#pragma unroll
-    for (int tl = 0; tl < TAPG; ++tl) {
-      const int tap = (TAPG == NTAPS) ? tl : (tg * TAPG + tl);
-      const int ty = tap / KS, tx = tap - ty * KS;
-      const int tapoff = (ty * TW + tx) * ROWB;
-#pragma unroll
-      for (int sub = 0; sub < CK / 16; ++sub) {
-        const bf16x8 bw = *reinterpret_cast<const bf16x8*>(ws + tl * (NT * ROWB) + boff + 32 * sub);
-#pragma unroll
-        for (int mt = 0; mt < MT; ++mt) {
-          const bf16x8 ax = *reinterpret_cast<const bf16x8*>(xs + apix[mt] + tapoff + 32 * sub);
-          // weight fragment first: D[channel][pixel]
-          acc[mt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(bw, ax, acc[mt], 0, 0, 0);
-        }
-      }
-    }
-  }
+#define IGEMM_X_BF16 1
+#include "igemm_bf16_main.inc"
+#undef IGEMM_X_BF16
 
   // ---- epilogue ----
-  // As igemm_epilogue.inc: each wave's 64 x 32 tile goes through LDS (rows of NT + 4 floats) so that a lane owns
-  // consecutive channels of one pixel; here 8 of them = 16 bytes of bf16, 4 lanes per pixel, 16 pixels (one row of the
-  // wave's 4 x 16 block) per pass.  Per view one buffer descriptor on a 64-bit base at pixel (oyw, tx0) of sample b, a
-  // per-lane 32-bit byte offset computed once and a scalar byte offset per pass: offsets stay inside four image rows.
-  __syncthreads();   // every wave is done with its fragment reads; the tile region is free
-  constexpr int CP = NT + 4;
-  float* es = smem + wv * (64 * CP);
-#pragma unroll
-  for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-    for (int g = 0; g < 4; ++g) {
-      f32x4 q4;
-#pragma unroll
-      for (int k = 0; k < 4; ++k) q4[k] = acc[mt][4 * g + k];
-      *reinterpret_cast<f32x4*>(es + (32 * mt + r) * CP + 8 * g + 4 * h) = q4;
-    }
-  const int c8 = (lane & 3) * 8, pl0 = lane >> 2;
-  const int co = n0 + c8;   // < Cout: Cout is a multiple of 32 (launcher)
+  // A lane owns 8 consecutive channels of one pixel = 16 bytes of bf16 (igemm_bf16_acc8.inc).  Per view one buffer
+  // descriptor on a 64-bit base at pixel (oyw, tx0) of sample b, a per-lane 32-bit byte offset computed once and a scalar
+  // byte offset per pass: offsets stay inside four image rows.
+#include "igemm_bf16_acc8.inc"
   const int wvu = __builtin_amdgcn_readfirstlane(wv);
   const EpilogueH& e = a.ep;
   const bool affine = e.scale != nullptr, film = e.film_mul != nullptr, relu = e.relu != 0;

@@ -251,7 +251,33 @@ int talloc(depgan_ctx* c, Tn* t, int N, int H, int W, int C);
 int conv_launch(depgan_ctx* c, const ConvPlan& pl, const ConvArgs& a, int KS);
 void zero_ep(Epilogue* e);
 TView view_offset(TView v, long samples);
-TView strided2(TView v, int di, int dj);
+TView strided2(TView v, int di, int dj);   // pixel grid (2i + di, 2j + dj) of a (2H, 2W) view
+TViewH strided2_h(TViewH v, int di, int dj);
+// backward-data of a 2x2 / stride-2 transposed convolution as ONE 1x1 convolution (dIn[p] = sum_t W_t^T dOut[2p + t]):
+// fills a->in, Cin, cpt and in_run_off so that the K axis gathers the four strided pixel grids of the upstream gradient
+// d, Cout channels each, in chunks of CK
+void deconv_gather_k(ConvArgs* a, TView d, int Cout, int CK);
+// views of the single-operator entries (depgan_op_*): NHWC, strides in elements, channel stride 1
+static inline TView op_view(const float* p, long sB, long sY, long sX) {
+  TView v;
+  v.p = const_cast<float*>(p);
+  v.sB = sB; v.sY = sY; v.sX = sX;
+  return v;
+}
+static inline TView op_view_or_null(const float* p, long sB, long sY, long sX) {
+  return p ? op_view(p, sB, sY, sX) : null_view();
+}
+static inline TViewH op_view_h(const void* p, long sB, long sY, long sX) {
+  TViewH v;
+  v.p = reinterpret_cast<__bf16*>(const_cast<void*>(p));
+  v.sB = sB; v.sY = sY; v.sX = sX;
+  return v;
+}
+static inline TViewH op_view_h_or_null(const void* p, long sB, long sY, long sX) {
+  return p ? op_view_h(p, sB, sY, sX) : null_view_h();
+}
+// what the bf16-storage operator entries refuse (sB = 0, one sample read by every batch index, is a view)
+static inline bool bad_view(const void* p, long sB, long sY, long sX) { return !p || sB < 0 || sY < 1 || sX < 1; }
 int deconv_bwd_data(depgan_ctx* c, GLayer& L, TView dsrc, int n);
 // weight gradient (four taps) + column sums of the upstream gradient of a transposed convolution
 int deconv_wgrad_all(depgan_ctx* c, const GLayer& L, TView dsrc, int n, const float* scale, float* raw,
@@ -284,6 +310,9 @@ int g_forward_only(depgan_ctx* c, const float* x, const float* z);
 // arena and raw_all slots, reading the bf16 buffers; g_backward_finish (model.hip): the BN-gamma launch and the noise MLP
 int bf16s_train_alloc(depgan_ctx* c);
 int bf16s_debug_u(depgan_ctx* c, const char* name, float* host, long cap, int shape[4]);
+// the tail of depgan_debug_tensor_bf16s (model_bf16s.hip): shape of the (batch, H, W, C) bf16 view v and, where host is
+// given, its dense fp32 copy
+int bf16s_debug_copy(depgan_ctx* c, const char* name, TViewH v, int H, int W, int C, float* host, long cap, int shape[4]);
 int g_forward_train_bf16s(depgan_ctx* c, const float* x, const float* z);
 int g_backward_bf16s(depgan_ctx* c, const float* x, const float* z, int n);
 int g_backward_finish(depgan_ctx* c, const float* z, int n);

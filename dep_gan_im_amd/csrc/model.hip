@@ -215,11 +215,7 @@ int deconv_bwd_data(depgan_ctx* c, GLayer& L, TView dsrc, int n) {
   a.B = n; a.H = L.H; a.W = L.W; a.Cout = L.Cin;
   a.ep.mask = L.in_mask;
   if (L.wpb_all) {
-    // dIn[p] = sum_t W_t^T dOut[2p + t]: one 1x1 convolution whose K axis gathers the four strided pixel grids
-    a.in = strided2(dsrc, 0, 0);
-    a.Cin = 4 * L.Cout;
-    a.cpt = L.Cout / L.pb.CK;
-    for (int t = 0; t < 4; ++t) a.in_run_off[t] = (long)(t / 2) * dsrc.sY + (long)(t % 2) * dsrc.sX;
+    deconv_gather_k(&a, dsrc, L.Cout, L.pb.CK);
     a.w = L.wpb_all;
     return conv_launch(c, L.pbf, a, 1);
   }
@@ -248,6 +244,19 @@ TView strided2(TView v, int di, int dj) {  // pixel grid (2i+di, 2j+dj)
   r.sY = 2 * v.sY;
   r.sX = 2 * v.sX;
   return r;
+}
+TViewH strided2_h(TViewH v, int di, int dj) {
+  TViewH r = v;
+  r.p = v.p + di * v.sY + dj * v.sX;
+  r.sY = 2 * v.sY;
+  r.sX = 2 * v.sX;
+  return r;
+}
+void deconv_gather_k(ConvArgs* a, TView d, int Cout, int CK) {
+  a->in = strided2(d, 0, 0);
+  a->Cin = 4 * Cout;
+  a->cpt = Cout / CK;
+  for (int t = 0; t < 4; ++t) a->in_run_off[t] = (long)(t / 2) * d.sY + (long)(t % 2) * d.sX;
 }
 
 // weight gradient: slabs + reduction (+ optional BN scale / raw copy / OI layout)
@@ -2068,14 +2077,6 @@ int depgan_eval_counts(const float* x, int nicg, const double* pred, const float
 
 // ---- learning-phase-1 operators (train_ops.hip), as uresnet.hip calls them; each view is NHWC with the strides
 // (sB, sY, sX) in floats and channel stride 1 ----
-static TView op_view(const float* p, long sB, long sY, long sX) {
-  TView v;
-  v.p = const_cast<float*>(p);
-  v.sB = sB;
-  v.sY = sY;
-  v.sX = sX;
-  return v;
-}
 static int op_alloc(float** p, size_t floats, const char* who) {
   if (hipMalloc((void**)p, (floats ? floats : 1) * sizeof(float)) != hipSuccess) {
     dg_set_error("%s: out of device memory (%zu floats)", who, floats);
@@ -2084,9 +2085,6 @@ static int op_alloc(float** p, size_t floats, const char* who) {
   return DG_OK;
 }
 static size_t op_scratch(long scratch_floats, size_t need) { return scratch_floats > 0 ? (size_t)scratch_floats : need; }
-static TView op_view_or_null(const float* p, long sB, long sY, long sX) {
-  return p ? op_view(p, sB, sY, sX) : null_view();
-}
 
 // ---- the fp32 convolution kernels with the whole fused epilogue and strided views (unit tests) ----
 static bool op_view_bad(const float* p, long sB, long sY, long sX) { return !p || sB < 1 || sY < 1 || sX < 1; }
@@ -2215,10 +2213,7 @@ int depgan_op_deconv2x2_igemm(int form, const float* in, long isB, long isY, lon
         rc = dg_pack_job(pb, w_hwoi + (size_t)t * Cout * Cin, Cin, Cout, 1, 1, 0, nullptr, dst, 4 * blk, &jobs[t]);
       }
       if (rc == DG_OK) rc = op_pack_jobs(jobs, 4, st);
-      a.in = strided2(d, 0, 0);
-      a.Cin = 4 * Cout;
-      a.cpt = Cout / pb.CK;
-      for (int t = 0; t < 4; ++t) a.in_run_off[t] = (long)(t / 2) * d.sY + (long)(t % 2) * d.sX;
+      deconv_gather_k(&a, d, Cout, pb.CK);
       a.w = wp;
       if (rc == DG_OK) rc = dg_conv_igemm(pbf, a, st);
     } else {

@@ -13,14 +13,6 @@
 #include <stdio.h>
 #include <string.h>
 
-static TViewH strided2_h(TViewH v, int di, int dj) {   // pixel grid (2i + di, 2j + dj) of a (2H, 2W) view
-  TViewH o = v;
-  o.p = v.p + di * v.sY + dj * v.sX;
-  o.sY = 2 * v.sY;
-  o.sX = 2 * v.sX;
-  return o;
-}
-
 static int halloc(depgan_ctx* c, __bf16** p, size_t elems) {
   void* q = nullptr;
   const size_t bytes = (elems ? elems : 8) * sizeof(__bf16);
@@ -255,6 +247,23 @@ int depgan_set_fwd_only_storage(depgan_ctx* c, int storage) {
 
 int depgan_get_fwd_only_storage(depgan_ctx* c) { return (c && c->fwd_only_bf16) ? 1 : 0; }
 
+int bf16s_debug_copy(depgan_ctx* c, const char* name, TViewH v, int H, int W, int C, float* host, long cap, int shape[4]) {
+  const int N = c->cfg.batch;
+  shape[0] = N; shape[1] = H; shape[2] = W; shape[3] = C;
+  if (!host) return DG_OK;
+  const long need = (long)N * H * W * C;
+  if (cap < need) { dg_set_error("debug_tensor_bf16s: %s needs %ld floats, the buffer holds %ld", name, need, cap); return DG_ERR_ARG; }
+  float* tmp = nullptr;
+  HIPCHECK(hipMalloc((void**)&tmp, (size_t)need * sizeof(float)));
+  int rc = dg_widen_bf16(v, N, H, W, C, tmp, c->st);
+  hipError_t e = hipStreamSynchronize(c->st);
+  if (rc == DG_OK && e == hipSuccess) e = hipMemcpy(host, tmp, (size_t)need * sizeof(float), hipMemcpyDeviceToHost);
+  hipFree(tmp);
+  if (rc != DG_OK) return rc;
+  if (e != hipSuccess) { dg_set_error("debug_tensor_bf16s: copy of %s failed: %s", name, hipGetErrorString(e)); return DG_ERR_HIP; }
+  return DG_OK;
+}
+
 int depgan_debug_tensor_bf16s(depgan_ctx* c, const char* name, float* host, long cap, int shape[4]) {
   if (!c || !name || !shape) { dg_set_error("debug_tensor_bf16s: null argument"); return DG_ERR_ARG; }
   if (host && cap < 1) { dg_set_error("debug_tensor_bf16s: non-positive capacity"); return DG_ERR_ARG; }
@@ -280,36 +289,15 @@ int depgan_debug_tensor_bf16s(depgan_ctx* c, const char* name, float* host, long
                    "not store %s (depgan_debug_capture(ctx, 1) makes those passes store it)", name);
       return DG_ERR_ARG;
     }
-    const TViewH v = c->h_out[i];
-    const int N = c->cfg.batch, C = L.Cout;
     const int H = L.kind == G_POOL ? L.H / 2 : (L.kind == G_DECONV ? 2 * L.H : L.H);
     const int W = L.kind == G_POOL ? L.W / 2 : (L.kind == G_DECONV ? 2 * L.W : L.W);
-    shape[0] = N; shape[1] = H; shape[2] = W; shape[3] = C;
-    if (!host) return DG_OK;
-    const long need = (long)N * H * W * C;
-    if (cap < need) { dg_set_error("debug_tensor_bf16s: %s needs %ld floats, the buffer holds %ld", name, need, cap); return DG_ERR_ARG; }
-    float* tmp = nullptr;
-    HIPCHECK(hipMalloc((void**)&tmp, (size_t)need * sizeof(float)));
-    int rc = dg_widen_bf16(v, N, H, W, C, tmp, c->st);
-    hipError_t e = hipStreamSynchronize(c->st);
-    if (rc == DG_OK && e == hipSuccess) e = hipMemcpy(host, tmp, (size_t)need * sizeof(float), hipMemcpyDeviceToHost);
-    hipFree(tmp);
-    if (rc != DG_OK) return rc;
-    if (e != hipSuccess) { dg_set_error("debug_tensor_bf16s: copy of %s failed: %s", name, hipGetErrorString(e)); return DG_ERR_HIP; }
-    return DG_OK;
+    return bf16s_debug_copy(c, name, c->h_out[i], H, W, L.Cout, host, cap, shape);
   }
   dg_set_error("debug_tensor_bf16s: unknown tensor '%s'", name);
   return DG_ERR_ARG;
 }
 
 // ---- single operators (unit tests): explicit view strides in ELEMENTS, stream last, checks before any HIP call ----
-static TViewH op_view_h(const void* p, long sB, long sY, long sX) {
-  TViewH v;
-  v.p = reinterpret_cast<__bf16*>(const_cast<void*>(p));
-  v.sB = sB; v.sY = sY; v.sX = sX;
-  return v;
-}
-static bool bad_view(const void* p, long sB, long sY, long sX) { return !p || sB < 0 || sY < 1 || sX < 1; }
 
 static int op_conv2d_bf16s_impl(const char* who, const void* in, long isB, long isY, long isX, const float* w_hwio,
                                 const float* bias, const float* scale, const float* shift, const float* film_mul,
@@ -337,7 +325,7 @@ static int op_conv2d_bf16s_impl(const char* who, const void* in, long isB, long 
   a.B = B; a.H = H; a.W = W; a.Cin = Cin; a.Cout = Cout;
   a.ep.bias = bias; a.ep.scale = scale; a.ep.shift = shift;
   a.ep.film_mul = film_mul; a.ep.film_add = film_add; a.ep.film_ld = film_ld;
-  a.ep.res = res ? op_view_h(res, rsB, rsY, rsX) : null_view_h();
+  a.ep.res = op_view_h_or_null(res, rsB, rsY, rsX);
   a.ep.relu = relu;
   a.ep.pool = pool ? make_view_h(reinterpret_cast<__bf16*>(pool), H / 2, W / 2, Cout) : null_view_h();
   a.ep.head_w = head_w; a.ep.head_b = head_b; a.ep.head_out = head_out;

@@ -161,10 +161,7 @@ int g_backward_bf16s(depgan_ctx* c, const float* x, const float* z, int n) {
       zero_ep(&a.ep);
       a.out = L.din;
       a.B = n; a.H = L.H; a.W = L.W; a.Cout = L.Cin;
-      a.in = strided2(L.dout, 0, 0);
-      a.Cin = 4 * L.Cout;
-      a.cpt = L.Cout / L.pb.CK;
-      for (int t = 0; t < 4; ++t) a.in_run_off[t] = (long)(t / 2) * L.dout.sY + (long)(t % 2) * L.dout.sX;
+      deconv_gather_k(&a, L.dout, L.Cout, L.pb.CK);
       a.w = L.wpb_all;
       DGCHECK(bwd_data_h(c, L.pbf, a, L.in_mask.p ? c->h_in[i] : null_view_h(), 1));
     }
@@ -205,20 +202,7 @@ int bf16s_debug_u(depgan_ctx* c, const char* name, float* host, long cap, int sh
   size_t i = 0;
   const GLayer* L = film_layer(c, "debug_tensor_bf16s", name + 4, &i);
   if (!L) return DG_ERR_ARG;
-  const int N = c->cfg.batch;
-  shape[0] = N; shape[1] = L->H; shape[2] = L->W; shape[3] = L->Cout;
-  if (!host) return DG_OK;
-  const long need = (long)N * L->H * L->W * L->Cout;
-  if (cap < need) { dg_set_error("debug_tensor_bf16s: %s needs %ld floats, the buffer holds %ld", name, need, cap); return DG_ERR_ARG; }
-  float* tmp = nullptr;
-  HIPCHECK(hipMalloc((void**)&tmp, (size_t)need * sizeof(float)));
-  int rc = dg_widen_bf16(c->h_u[i], N, L->H, L->W, L->Cout, tmp, c->st);
-  hipError_t e = hipStreamSynchronize(c->st);
-  if (rc == DG_OK && e == hipSuccess) e = hipMemcpy(host, tmp, (size_t)need * sizeof(float), hipMemcpyDeviceToHost);
-  hipFree(tmp);
-  if (rc != DG_OK) return rc;
-  if (e != hipSuccess) { dg_set_error("debug_tensor_bf16s: copy of %s failed: %s", name, hipGetErrorString(e)); return DG_ERR_HIP; }
-  return DG_OK;
+  return bf16s_debug_copy(c, name, c->h_u[i], L->H, L->W, L->Cout, host, cap, shape);
 }
 
 int depgan_debug_film_decision_bf16s(depgan_ctx* c, const char* layer, unsigned char* host, long cap, int shape[4]) {
@@ -244,27 +228,14 @@ int depgan_debug_film_decision_bf16s(depgan_ctx* c, const char* layer, unsigned 
 }
 
 // ---- single operators (unit tests): explicit view strides in ELEMENTS, stream last, checks before any HIP call ----
-static TViewH opv_h(const void* p, long sB, long sY, long sX) {
-  TViewH v;
-  v.p = reinterpret_cast<__bf16*>(const_cast<void*>(p));
-  v.sB = sB; v.sY = sY; v.sX = sX;
-  return v;
-}
-static TView opv_f(const float* p, long sB, long sY, long sX) {
-  TView v;
-  v.p = const_cast<float*>(p);
-  v.sB = sB; v.sY = sY; v.sX = sX;
-  return v;
-}
-static bool bad_v(const void* p, long sB, long sY, long sX) { return !p || sB < 0 || sY < 1 || sX < 1; }
 
 int depgan_op_conv2d_film_train_bf16s(const void* in, long isB, long isY, long isX, const float* w_hwio, const float* bias,
                                       const float* scale, const float* shift, const float* film_mul, const float* film_add,
                                       int film_ld, const void* res, long rsB, long rsY, long rsX, void* out, long osB,
                                       long osY, long osX, void* u_out, unsigned char* dec_bits, int B, int H, int W, int Cin,
                                       int Cout, int relu, void* stream) {
-  if (bad_v(in, isB, isY, isX) || bad_v(out, osB, osY, osX) || !w_hwio || !film_mul || !film_add || !u_out || !dec_bits ||
-      B < 1 || H < 1 || W < 1 || Cin < 1 || Cout < 1 || (res && bad_v(res, rsB, rsY, rsX))) {
+  if (bad_view(in, isB, isY, isX) || bad_view(out, osB, osY, osX) || !w_hwio || !film_mul || !film_add || !u_out || !dec_bits ||
+      B < 1 || H < 1 || W < 1 || Cin < 1 || Cout < 1 || (res && bad_view(res, rsB, rsY, rsX))) {
     dg_set_error("op_conv2d_film_train_bf16s: null or non-positive argument");
     return DG_ERR_ARG;
   }
@@ -273,12 +244,12 @@ int depgan_op_conv2d_film_train_bf16s(const void* in, long isB, long isY, long i
   hipStream_t st = (hipStream_t)stream;
   ConvArgsHT a;
   memset(&a, 0, sizeof(a));
-  a.in = opv_h(in, isB, isY, isX);
-  a.out = opv_h(out, osB, osY, osX);
+  a.in = op_view_h(in, isB, isY, isX);
+  a.out = op_view_h(out, osB, osY, osX);
   a.B = B; a.H = H; a.W = W; a.Cin = Cin; a.Cout = Cout;
   a.ep.bias = bias; a.ep.scale = scale; a.ep.shift = shift;
   a.ep.film_mul = film_mul; a.ep.film_add = film_add; a.ep.film_ld = film_ld;
-  a.ep.res = res ? opv_h(res, rsB, rsY, rsX) : null_view_h();
+  a.ep.res = op_view_h_or_null(res, rsB, rsY, rsX);
   a.ep.relu = relu;
   a.ep.pool = null_view_h();
   a.u = make_view_h(reinterpret_cast<__bf16*>(u_out), H, W, Cout);
@@ -296,7 +267,7 @@ int depgan_op_conv2d_film_train_bf16s(const void* in, long isB, long isY, long i
 int depgan_op_conv2d_wgrad_bf16s(const void* x, long xsB, long xsY, long xsX, const float* dy, long dsB, long dsY, long dsX,
                                  float* dw, float* colsum, int B, int H, int W, int Cin, int Cout, int KS, int oi,
                                  void* stream) {
-  if (bad_v(x, xsB, xsY, xsX) || bad_v(dy, dsB, dsY, dsX) || !dw || B < 1 || H < 1 || W < 1 || Cin < 1 || Cout < 1) {
+  if (bad_view(x, xsB, xsY, xsX) || bad_view(dy, dsB, dsY, dsX) || !dw || B < 1 || H < 1 || W < 1 || Cin < 1 || Cout < 1) {
     dg_set_error("op_conv2d_wgrad_bf16s: null or non-positive argument");
     return DG_ERR_ARG;
   }
@@ -313,8 +284,8 @@ int depgan_op_conv2d_wgrad_bf16s(const void* x, long xsB, long xsY, long xsX, co
     return DG_ERR_HIP;
   }
   WgradArgsH a;
-  a.x = opv_h(x, xsB, xsY, xsX);
-  a.dy = opv_f(dy, dsB, dsY, dsX);
+  a.x = op_view_h(x, xsB, xsY, xsX);
+  a.dy = op_view(dy, dsB, dsY, dsX);
   a.part = part;
   a.B = B; a.H = H; a.W = W; a.Cin = Cin; a.Cout = Cout;
   a.nTiles = a.tilesPerChunk = 0;
@@ -336,8 +307,8 @@ int depgan_op_conv2d_bwd_data_bf16s(const float* dy, long dsB, long dsY, long ds
                                     long rsB, long rsY, long rsX, const void* mask, long msB, long msY, long msX, float* dx,
                                     long osB, long osY, long osX, int B, int H, int W, int Cin, int Cout, int deconv,
                                     void* stream) {
-  if (bad_v(dy, dsB, dsY, dsX) || bad_v(dx, osB, osY, osX) || !w || B < 1 || H < 1 || W < 1 || Cin < 1 || Cout < 1 ||
-      (res && bad_v(res, rsB, rsY, rsX)) || (mask && bad_v(mask, msB, msY, msX))) {
+  if (bad_view(dy, dsB, dsY, dsX) || bad_view(dx, osB, osY, osX) || !w || B < 1 || H < 1 || W < 1 || Cin < 1 || Cout < 1 ||
+      (res && bad_view(res, rsB, rsY, rsX)) || (mask && bad_view(mask, msB, msY, msX))) {
     dg_set_error("op_conv2d_bwd_data_bf16s: null or non-positive argument");
     return DG_ERR_ARG;
   }
@@ -346,11 +317,11 @@ int depgan_op_conv2d_bwd_data_bf16s(const float* dy, long dsB, long dsY, long ds
   ConvArgs a;
   memset(&a, 0, sizeof(a));
   zero_ep(&a.ep);
-  a.out = opv_f(dx, osB, osY, osX);
+  a.out = op_view(dx, osB, osY, osX);
   a.B = B; a.H = H; a.W = W; a.Cout = Cin;
-  a.ep.res = res ? opv_f(res, rsB, rsY, rsX) : null_view();
-  const TViewH mh = mask ? opv_h(mask, msB, msY, msX) : null_view_h();
-  const TView d = opv_f(dy, dsB, dsY, dsX);
+  a.ep.res = op_view_or_null(res, rsB, rsY, rsX);
+  const TViewH mh = op_view_h_or_null(mask, msB, msY, msX);
+  const TView d = op_view(dy, dsB, dsY, dsX);
   float* wp = nullptr;
   int rc = DG_OK;
   ConvPlan pl;
@@ -384,10 +355,7 @@ int depgan_op_conv2d_bwd_data_bf16s(const float* dy, long dsB, long dsY, long ds
       hipStreamSynchronize(st);
       hipFree(jd);
     }
-    a.in = strided2(d, 0, 0);
-    a.Cin = 4 * Cout;
-    a.cpt = Cout / pb.CK;
-    for (int t = 0; t < 4; ++t) a.in_run_off[t] = (long)(t / 2) * d.sY + (long)(t % 2) * d.sX;
+    deconv_gather_k(&a, d, Cout, pb.CK);
   }
   a.w = wp;
   if (rc == DG_OK) rc = dg_conv_bf16_mh(pl, a, mh, st);
@@ -399,13 +367,13 @@ int depgan_op_conv2d_bwd_data_bf16s(const float* dy, long dsB, long dsY, long ds
 int depgan_op_unpool_mask_bf16s(const float* dpool, long dsB, long dsY, long dsX, const void* a, long asB, long asY, long asX,
                                 const float* skip, long ssB, long ssY, long ssX, float* out, long osB, long osY, long osX,
                                 int B, int Ho, int Wo, int C, void* stream) {
-  if (bad_v(dpool, dsB, dsY, dsX) || bad_v(a, asB, asY, asX) || bad_v(out, osB, osY, osX) || (skip && bad_v(skip, ssB, ssY, ssX)) ||
+  if (bad_view(dpool, dsB, dsY, dsX) || bad_view(a, asB, asY, asX) || bad_view(out, osB, osY, osX) || (skip && bad_view(skip, ssB, ssY, ssX)) ||
       B < 1 || Ho < 1 || Wo < 1 || C < 1) {
     dg_set_error("op_unpool_mask_bf16s: null or non-positive argument");
     return DG_ERR_ARG;
   }
-  return dg_unpool_mask_bf16s(opv_f(dpool, dsB, dsY, dsX), opv_h(a, asB, asY, asX),
-                              skip ? opv_f(skip, ssB, ssY, ssX) : null_view(), opv_f(out, osB, osY, osX), B, Ho, Wo, C,
+  return dg_unpool_mask_bf16s(op_view(dpool, dsB, dsY, dsX), op_view_h(a, asB, asY, asX),
+                              op_view_or_null(skip, ssB, ssY, ssX), op_view(out, osB, osY, osX), B, Ho, Wo, C,
                               (hipStream_t)stream);
 }
 

@@ -435,6 +435,37 @@ def test_backward_data_with_a_bf16_mask(lib, case):
     _gate(dx.cpu().numpy(), full, "bwd-data 3x3 no mask %s" % (case,))
 
 
+# B, H, W, channels of dx, channels of dy: one tile and one chunk; ragged tiles, three channel tiles, four chunks; a K tail
+# (the last chunk is partly outside the channels); eight pixel tiles, so the XCD-aware item order is taken
+@pytest.mark.parametrize("case", [(1, 16, 16, 32, 32), (3, 21, 19, 96, 128), (2, 32, 32, 64, 40), (8, 16, 16, 32, 64)])
+def test_backward_data_equals_the_fp32_mask_kernel_bit_for_bit(lib, case):
+    """igemm_bf16_mh_kernel and igemm_bf16_kernel contract with the same included main loop over the same flipped bf16
+    panel, and without bias, affine, FiLM and ReLU the shared epilogue leaves the accumulator as it is: the two entries
+    agree bit for bit, and a bf16 mask selects those bits or +0.0."""
+    from dep_gan_im_amd import _lib
+    B, H, W, ci, co = case
+    dev = torch.device("cuda:0")
+    rng = np.random.default_rng(7 * ci + co + H)
+    dyd = torch.from_numpy(rng.standard_normal((B, H, W, co)).astype(np.float32)).to(dev)
+    wd = torch.from_numpy((rng.standard_normal((3, 3, ci, co)) / np.sqrt(9 * co)).astype(np.float32)).to(dev)
+    mask = _bf16(rng.standard_normal((B, H, W, ci)) * (rng.uniform(size=(B, H, W, ci)) > 0.3))
+    assert (mask == 0).any() and (mask < 0).any() and (mask > 0).any()
+    mh = _dev_h(mask, dev)
+    ref = torch.full((B, H, W, ci), float("nan"), device=dev)
+    _lib.check(lib.depgan_op_conv2d_bwd_data(P(dyd), P(wd), P(ref), B, H, W, ci, co, 3, 3, None))
+    dx = torch.full((B, H, W, ci), float("nan"), device=dev)
+    _lib.check(lib.depgan_op_conv2d_bwd_data_bf16s(P(dyd), *_st(dyd), P(wd), None, 0, 0, 0, None, 0, 0, 0, P(dx), *_st(dx),
+                                                   B, H, W, ci, co, 0, None))
+    torch.cuda.synchronize()
+    ref = ref.cpu().numpy()
+    assert np.isfinite(ref).all() and same(dx.cpu().numpy(), ref)
+    dx.fill_(float("nan"))
+    _lib.check(lib.depgan_op_conv2d_bwd_data_bf16s(P(dyd), *_st(dyd), P(wd), None, 0, 0, 0, P(mh), *_st(mh), P(dx), *_st(dx),
+                                                   B, H, W, ci, co, 0, None))
+    torch.cuda.synchronize()
+    assert same(dx.cpu().numpy(), np.where(mask > 0, ref, np.float32(0.0)))
+
+
 @pytest.mark.parametrize("case", [(2, 32, 32, 128, 128), (3, 16, 12, 96, 96), (2, 128, 128, 64, 64)])
 def test_backward_data_of_the_transposed_convolution_with_a_bf16_mask(lib, case):
     from dep_gan_im_amd import _lib
