@@ -275,6 +275,11 @@ int dg_conv_igemm_check(const ConvPlan& pl, const ConvArgs& a);
 // wave-private 3x3 kernel (igemm_wp.hip): no workgroup barrier in steady state; reads the 8-channel-chunk plan's panel
 bool dg_conv_igemm_wp_supported(const ConvPlan& pl, const ConvArgs& a, bool force);
 int dg_conv_igemm_wp(const ConvPlan& pl, const ConvArgs& a, hipStream_t st);
+// weight-stationary, wave-private 5x5 kernel (igemm_wp.hip): Cin, Cout in {16, 32}, one channel tile; reads the packed
+// panel of plans 2 / 3 as it is and is bit-identical to igemm_conv_kernel<., 5, ., 25>
+bool dg_conv_igemm_ws5_supported(const ConvPlan& pl, const ConvArgs& a, bool force);
+int dg_conv_igemm_ws5(const ConvPlan& pl, const ConvArgs& a, hipStream_t st);
+const char* dg_conv_igemm_ws5_name(const ConvPlan& pl);
 int dg_conv_igemm_tile(const ConvPlan& pl, const ConvArgs& a, hipStream_t st);
 // the launch for (pl, a) can carry the fused one-channel head (Epilogue::head_*): 32 -> 32, 8-channel-chunk 3x3 kernel
 bool dg_conv_igemm_head_supported(const ConvPlan& pl, const ConvArgs& a);

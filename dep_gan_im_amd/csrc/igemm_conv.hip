@@ -529,6 +529,7 @@ void dg_conv_igemm_name(const ConvPlan& pl, const ConvArgs& a, char* buf, size_t
   if (pl.bf16) { snprintf(buf, cap, pl.variant >= 200 ? "igemm_split_kernel" : "igemm_bf16_kernel"); return; }
   if (pl.variant == 9) { snprintf(buf, cap, "%s", dg_conv_wino_name(a)); return; }
   if (dg_conv_igemm_wp_supported(pl, a, false)) { snprintf(buf, cap, "igemm_wp_kernel<0>"); return; }
+  if (dg_conv_igemm_ws5_supported(pl, a, false)) { snprintf(buf, cap, "%s", dg_conv_igemm_ws5_name(pl)); return; }
   dispatch_variant(pl, a, nullptr, buf, cap);
 }
 
@@ -573,6 +574,7 @@ static int conv_igemm_impl(const ConvPlan& pl, const ConvArgs& a_in, hipStream_t
   if (is_bf16) return dg_conv_igemm_bf16(pl, a, st);
   if (pl.variant == 9) return dg_conv_wino(pl, a, st);   // its panel fits no other kernel
   if (allow_wp && dg_conv_igemm_wp_supported(pl, a, false)) return dg_conv_igemm_wp(pl, a, st);
+  if (allow_wp && dg_conv_igemm_ws5_supported(pl, a, false)) return dg_conv_igemm_ws5(pl, a, st);
   return dispatch_variant(pl, a, st, nullptr, 0);
 }
 

@@ -22,6 +22,25 @@
 // another wave could run meanwhile, exactly as the micro-benchmarks of round 1 said (an fp32 MFMA stream is the vector
 // ALU: nothing issued overlaps with it).  The kernel therefore stays OPT-IN (DEPGAN_IGEMM_WP=1); the default path is the
 // workgroup-tile kernel.
+//
+// The same body, templated on (MF, KS, CK), is the WEIGHT-STATIONARY 5x5 kernel igemm_ws5_kernel<MF, CK> for the critics'
+// 5x5 layers (Cin, Cout in {16, 32}: one channel tile, so the packed panel is the same for every item of a launch and
+// igemm_conv_kernel<., 5, ., 25> re-stages it per item).  Per persistent workgroup the whole panel (25 x Cin x Cout
+// floats: 25.6 / 51.2 / 102.4 KB) goes into LDS once, unpadded, 16-byte slots XOR-swizzled so that the B-fragment reads
+// are conflict-free; a wave's item is a 4 x 16 pixel block x all channels (MF = 16: four v_mfma_f32_16x16x4_f32 tiles;
+// MF = 32: two 32x32x2 tiles), its 8 x 20 halo chunk staged through registers into an unpadded wave-private region (5 KB
+// at CK = 8, 10 KB at CK = 16, the latter swizzled conflict-free).  As many waves as 160 KB admit beside the panel, 12 at
+// the most: 12 / 12 / 11 / 12 for 16->16 / 16->32 / 32->16 / 32->32 (32->16 cannot reach three waves on every SIMD at the
+// plan's 16-channel chunks: 51.2 KB + 12 x 10 KB > 160 KB).  Same panel (plans 2 and 3 of dg_plan_conv), same K order,
+// the plan's chunk width for all four pairs, same epilogue text: bit-identical to the tile kernel
+// (tests/test_gpu_conv5_ws.py).  -Rpass-analysis=kernel-resource-usage: <32, 8> 120 VGPRs, <16, 16> 158 VGPRs, no scratch
+// (the 3x3 instantiation: 114, none).
+// MEASURED (profiles/ws5_experiments.md; tools/ab_ws5.py, against the tile kernel in one process): 16->16 @256^2 -8.5 % at
+// batch 96 (0.707 -> 0.773 of the fp32 matrix peak), -4.4 % at batch 32; 32->32 @128^2 -7.6 % at batch 96 (0.787 -> 0.852),
+// +5.4 % at batch 32 (2.7 items per wave slot); 16->32 @128^2 -9.3 % / -5.0 % with 16 waves (12 waves: -9.1 % / +5.1 %);
+// 32->16 +3 ... +5 % at both batches.  Default where it is faster (dg_conv_igemm_ws5_supported), the tile kernel
+// elsewhere.  Canonical step: 49.83 -> 49.16 ms forced on for all eight launches, 49.66 -> 48.74 ms with that default
+// (medians of five alternating runs; every run with it faster than every run without).  Counters not read yet.
 #include <stdlib.h>
 
 #include "common.h"
@@ -29,34 +48,79 @@
 
 namespace {
 
-constexpr int WP_NW = 16;                   // waves per workgroup
-constexpr int WP_TWX = 18, WP_TWY = 6;      // halo of a 4 x 16 block
-constexpr int WP_PIX = WP_TWX * WP_TWY;     // 108 pixels
-constexpr int WP_CK = 8, WP_CKP = 12;       // channels per chunk; floats per halo pixel row (48 B: conflict-free b128 reads)
-constexpr int WP_WAVE_FLOATS = WP_PIX * WP_CKP;   // 1296 floats = 5184 B >= the 32 x 36-float transpose tile (4608 B)
-constexpr int WP_SLOTS = WP_PIX * 2;        // 16-byte pieces of one halo chunk (two per pixel)
-constexpr int WP_PIECES = (WP_SLOTS + 63) / 64;   // 4 per lane, the last one partial (24 lanes)
+constexpr int WP_NW = 16;                   // waves per workgroup of the 3x3 form
+
+// One text for the 3x3 form (MF = 32, CK = 8) and the weight-stationary 5x5 forms (MF = 32 / CK = 8, MF = 16 / CK = 16).
+// The 3x3 halo keeps its padded 48-byte pixel rows; the 5x5 halos are unpadded (8 x 20 pixels x CK floats: 5 KB / 10 KB
+// per wave -- padded rows would cost the third wave per SIMD).
+template <int MF, int KS, int CK>
+struct WpGeo {
+  static constexpr int NT = MF, MT = 64 / MF, PAD = KS / 2, NTAPS = KS * KS;
+  static constexpr int TWX = 16 + KS - 1, TWY = 4 + KS - 1;   // halo of a 4 x 16 block
+  static constexpr int PIX = TWX * TWY;
+  static constexpr int XV = CK / 4;                           // 16-byte pieces per halo pixel
+  static constexpr int CKP = (KS == 3) ? CK + 4 : CK;         // floats per halo pixel row
+  static constexpr int EPI_FLOATS = (MF == 32 ? 32 : 64) * (NT + 4);   // transpose scratch of the epilogue
+  static constexpr int WAVE_FLOATS = PIX * CKP > EPI_FLOATS ? PIX * CKP : EPI_FLOATS;
+  static constexpr int SLOTS = PIX * XV;
+  static constexpr int PIECES = (SLOTS + 63) / 64;            // per lane; the last one may be partial
+  // 16-byte slot swizzles (slot ^= f): within each 16-lane group of a ds_read_b128 every lane must hit another slot
+  // of the 256-byte bank row.
+  //   panel, 32-byte rows (MF = 32): f = bit 4 of the row for 5x5 (conflict-free); the 3x3 form keeps the bit-2 swizzle
+  //     it was measured with.
+  //   panel, 64-byte rows (MF = 16): f = {0, 2, 3, 1}[row >> 2] (conflict-free).
+  //   halo, 64-byte rows (MF = 16): f = 2 * bit 2 of the pixel index (conflict-free at every tap offset).
+  //   halo, 32-byte rows (MF = 32, 5x5): none -- rows 20 pixels apart admit no conflict-free one-bit swizzle; 2-way, as
+  //     the padded rows of the tile kernel are, and the LDS is not what limits this form (3 reads per 8 MFMAs).
+  static __device__ __forceinline__ int panel_sw(int n) {
+    if (MF == 32) return (n >> (KS == 3 ? 2 : 4)) & 1;
+    return (0x78 >> (2 * (n >> 2))) & 3;
+  }
+  static __device__ __forceinline__ int halo_off(int pix, int part) {   // float offset of piece `part` of halo pixel `pix`
+    if (CK == 16) return pix * CKP + 4 * (part ^ (((pix >> 2) & 1) << 1));
+    return pix * CKP + 4 * part;
+  }
+};
+
+template <int MF> struct WpMfma;
+template <> struct WpMfma<32> {
+  typedef f32x16 acc_t;
+  static constexpr int NREG = 16;
+  static __device__ __forceinline__ acc_t run(float w, float x, acc_t c) { return __builtin_amdgcn_mfma_f32_32x32x2f32(w, x, c, 0, 0, 0); }
+};
+template <> struct WpMfma<16> {
+  typedef f32x4 acc_t;
+  static constexpr int NREG = 4;
+  static __device__ __forceinline__ acc_t run(float w, float x, acc_t c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(w, x, c, 0, 0, 0); }
+};
 
 // ABL: ablation bits for tools/ab_wp.py (0 = the product kernel): 1 no epilogue, 2 no staging after an item's first
 // chunk, 4 no MFMAs
-template <int ABL>
-__global__ __launch_bounds__(WP_NW * 64, 1) void igemm_wp_kernel(const ConvArgs a) {
-  constexpr int MF = 32, NT = 32, MT = 2, KS = 3, TW = WP_TWX;
-  typedef f32x16 acc_t;
+// The number of waves is the launch's (blockDim.x / 64 <= NWMAX): the launcher takes what the LDS budget admits.
+template <int MF, int KS, int CK, int ABL>
+static __device__ __forceinline__ void igemm_wp_body(const ConvArgs& a) {
+  typedef WpGeo<MF, KS, CK> G;
+  constexpr int NT = G::NT, MT = G::MT, TW = G::TWX, PAD = G::PAD, NTAPS = G::NTAPS, CKP = G::CKP;
+  constexpr int PIECES = G::PIECES, SLOTS = G::SLOTS, XV = G::XV;
+  typedef typename WpMfma<MF>::acc_t acc_t;
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const int tid = threadIdx.x;
   const int lane = tid & 63, wv = tid >> 6;
-  const int r = lane & 31, h = lane >> 5;
-  const int nCC = a.Cin / WP_CK;
-  const int panelFloats = nCC * 9 * NT * WP_CK;
+  const int NW = (int)(blockDim.x >> 6);
+  const int r = lane % MF, h = lane / MF;
+  const int nCC = a.Cin / CK;
+  const int panelFloats = nCC * NTAPS * NT * CK;
   float* panel = smem;
-  float* wbuf = smem + panelFloats + wv * WP_WAVE_FLOATS;
+  float* wbuf = smem + panelFloats + wv * G::WAVE_FLOATS;
 
-  // ---- work items: super-tiles of 16 rows x 64 columns (wave w: rows 4 (w & 3), columns 16 (w >> 2)) x channel tile;
-  // ids dealt over the 8 XCDs as in igemm_conv_kernel (an XCD walks a contiguous eighth of the super-tiles, channel
-  // tile fastest).  The grid is a multiple of 8 nNT, so a workgroup's channel tile never changes: one panel.
+  // ---- work items: one wave's 4 x 16 pixel block x channel tile.  Blocks are numbered row-in-band fastest (four
+  // blocks = 16 rows), then along the row, then band, then sample; a group of NW consecutive blocks is what the
+  // workgroup's waves take together (16 waves: 16 rows x 64 columns).  Group ids are dealt over the 8 XCDs as in
+  // igemm_conv_kernel (an XCD walks a contiguous eighth of the groups, channel tile fastest).  The grid is a multiple of
+  // 8 nNT or there is one channel tile, so a workgroup's channel tile never changes: one panel.
   const unsigned nNT = (unsigned)a.lgy, nSup = (unsigned)a.lgx;
-  const int supX = (a.W + 63) >> 6, supY = (a.H + 15) >> 4;
+  const int bxN = (a.W + 15) >> 4, bandsY = (a.H + 15) >> 4;
+  const int nItems = a.B * bandsY * bxN * 4;
   unsigned id = blockIdx.x;
   auto decode = [&](unsigned i, int& st, int& nt) {
     if ((nSup & 7u) == 0) {
@@ -70,110 +134,147 @@ __global__ __launch_bounds__(WP_NW * 64, 1) void igemm_wp_kernel(const ConvArgs 
   };
   int st0, ntile;
   decode(id, st0, ntile);
-  const int n0 = ntile * NT;
 
-  // ---- the panel: [chunk][tap][n][8 floats], 32-byte rows, the two 16-byte halves of row n swapped when bit 2 of n
-  // is set: lanes r and r + 4 of a b128 fragment read then fall into different bank groups (conflict-free, unpadded)
+  // ---- the panel: [chunk][tap][n][CK floats], unpadded rows, the 16-byte pieces of row n swizzled (WpGeo::panel_sw):
+  // the lanes of a b128 fragment read fall into different bank groups
   {
     const float* src = a.w + (size_t)ntile * panelFloats;
     const int nq = panelFloats / 4;
-    for (int q = tid; q < nq; q += WP_NW * 64) {
-      const int row = q >> 1, half = q & 1;
+    for (int q = tid; q < nq; q += (int)blockDim.x) {
+      const int row = q / XV, part = q % XV;
       const f32x4 v = *reinterpret_cast<const f32x4*>(src + (size_t)q * 4);
-      *reinterpret_cast<f32x4*>(panel + row * 8 + 4 * (half ^ ((row >> 2) & 1))) = v;
+      *reinterpret_cast<f32x4*>(panel + row * CK + 4 * (part ^ G::panel_sw(row % NT))) = v;
     }
   }
   __syncthreads();   // the only one: from here on a wave waits for nobody
 
-  // ---- per-lane staging geometry, once per wave: piece i covers halo slot q = lane + 64 i -> pixel q / 2, half q & 1
-  unsigned xgb[WP_PIECES], xlb[WP_PIECES];
-  int xyx[WP_PIECES];
+  // ---- per-lane staging geometry, once per wave: piece i covers halo slot q = lane + 64 i -> pixel q / XV, part q % XV
+  // (the LDS offset of piece i is that of piece 0 plus a constant: 64 / XV pixels further on, where the swizzle repeats)
+  unsigned xgb[PIECES];
+  constexpr int PSTEP = 64 / XV;                      // pixels between a lane's consecutive pieces
+  static_assert(PSTEP % 8 == 0, "the halo swizzle must repeat from piece to piece");
+  const int xpart = lane % XV, xpix0 = lane / XV;
 #pragma unroll
-  for (int i = 0; i < WP_PIECES; ++i) {
-    const int q = min(lane + 64 * i, WP_SLOTS - 1);
-    const int pix = q >> 1, part = q & 1;
+  for (int i = 0; i < PIECES; ++i) {
+    const int pix = min(xpix0 + PSTEP * i, G::PIX - 1);
     const int ly = pix / TW, lx = pix - ly * TW;
-    xgb[i] = 4u * (unsigned)(ly * (int)a.in.sY + lx * (int)a.in.sX + part * 4);
-    xlb[i] = 4u * (unsigned)(pix * WP_CKP + part * 4);
-    xyx[i] = (ly << 16) | (lx << 8) | (part * 4);
+    xgb[i] = 4u * (unsigned)(ly * (int)a.in.sY + lx * (int)a.in.sX + xpart * 4);
   }
-  const bool in_last = lane < (WP_SLOTS - 64 * (WP_PIECES - 1));
+  const unsigned xlb0 = 4u * (unsigned)G::halo_off(xpix0, xpart);
+  const bool in_last = lane < (SLOTS - 64 * (PIECES - 1));
   const unsigned wb0 = (unsigned)(size_t)(__attribute__((address_space(3))) float*)wbuf;
-  // fragment bases: A = pixel (2 mt + (r >> 4), r & 15) of the halo tile, channels 4h..; B = panel row r, swizzled half
+  // fragment bases: A = the lane's pixel of MFMA tile mt (MF = 32: (2 mt + (r >> 4), r & 15); MF = 16: (mt, r)) of the
+  // halo tile, channels 4h..; B = panel row r, swizzled piece
   int apix[MT];
 #pragma unroll
-  for (int mt = 0; mt < MT; ++mt) apix[mt] = ((2 * mt + (r >> 4)) * TW + (r & 15)) * WP_CKP + 4 * h;
-  const int boff = r * 8 + 4 * (h ^ ((r >> 2) & 1));
-  const int wrow = wv & 3, wcol = wv >> 2;
+  for (int mt = 0; mt < MT; ++mt)
+    apix[mt] = (MF == 32) ? ((2 * mt + (r >> 4)) * TW + (r & 15)) * CKP + 4 * h : (mt * TW + r) * CKP + 4 * h;
+  // swizzled halo (CK = 16): the swizzle bit of pixel (mt + ty) TW + r + tx is bit 2 of r + tx, flipped when mt + ty is
+  // odd (TW = 20 = 4 x 5) -- one lane offset per (tx, parity), every other term a constant of the unrolled loop
+  int asw[KS][2];
+#pragma unroll
+  for (int tx = 0; tx < KS; ++tx)
+#pragma unroll
+    for (int par = 0; par < 2; ++par)
+      asw[tx][par] = (CK == 16) ? (r + tx) * CKP + 4 * (h ^ (((((r + tx) >> 2) & 1) ^ par) << 1)) : 0;
+  const int boff = r * CK + 4 * (h ^ G::panel_sw(r));
 
   for (;;) {
     int st, nt_unused;
     decode(id, st, nt_unused);
-    const int sx = st % supX;
-    int t = st / supX;
-    const int sy = t % supY;
-    const int b = t / supY;
-    const int ty0 = sy * 16 + 4 * wrow, tx0 = sx * 64 + 16 * wcol;   // this wave's 4 x 16 block
-    if (ty0 < a.H && tx0 < a.W) {
+    const int item = st * NW + wv;
+    const int wrow = item & 3;
+    int t = item >> 2;
+    const int bxi = t % bxN;
+    t /= bxN;
+    const int sy = t % bandsY;
+    const int b = t / bandsY;
+    const int ty0 = sy * 16 + 4 * wrow, tx0 = bxi * 16;   // this wave's 4 x 16 block
+    if (item < nItems && ty0 < a.H) {
+      // (opaque per item: the epilogue's per-channel pointers are then formed per item instead of living in 64-bit
+      // register pairs across the item loop)
+      int n0 = ntile * NT;
+      asm volatile("" : "+s"(n0));
       const float* inb = a.in.p + (long)b * a.in.sB;
-      const bool interior = ty0 >= 1 && ty0 + 5 <= a.H && tx0 >= 1 && tx0 + 17 <= a.W;
-      const char* halo0 = reinterpret_cast<const char*>(inb + ((long)(ty0 - 1) * a.in.sY + (long)(tx0 - 1) * a.in.sX));
-      f32x4 xr[WP_PIECES];
+      const bool interior = ty0 >= PAD && ty0 + 4 + PAD <= a.H && tx0 >= PAD && tx0 + 16 + PAD <= a.W;
+      const char* halo0 = reinterpret_cast<const char*>(inb + ((long)(ty0 - PAD) * a.in.sY + (long)(tx0 - PAD) * a.in.sX));
+      // only used for interior blocks, whose whole halo lies inside the image
+      // (readfirstlane returns int: through unsigned, or the low word's bit 31 would be sign-extended into the high one)
+      const unsigned long long hu = (unsigned long long)halo0;
+      const unsigned hlo = __builtin_amdgcn_readfirstlane((unsigned)hu), hhi = __builtin_amdgcn_readfirstlane((unsigned)(hu >> 32));
+      const __amdgpu_buffer_rsrc_t halo_rsrc =
+          __builtin_amdgcn_make_buffer_rsrc((void*)(((unsigned long long)hhi << 32) | hlo), 0, 0x7FFFFFFF, 0x00020000);
+      f32x4 xr[PIECES];
       auto prefetch = [&](int cc) {
-        const char* src = halo0 + 4 * (long)cc * WP_CK;
+        const char* src = halo0 + 4 * (long)cc * CK;
         if (interior) {
+          // (uniform base in a buffer descriptor) + (the lane's 32-bit byte offset): as plain pointers the compiler keeps
+          // every offset as a 64-bit pair across the item loop
+          typedef int i32x4 __attribute__((ext_vector_type(4)));
 #pragma unroll
-          for (int i = 0; i < WP_PIECES - 1; ++i) xr[i] = *reinterpret_cast<const f32x4*>(src + xgb[i]);
-          if (in_last) xr[WP_PIECES - 1] = *reinterpret_cast<const f32x4*>(src + xgb[WP_PIECES - 1]);
+          for (int i = 0; i < PIECES - 1; ++i)
+            xr[i] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(halo_rsrc, (int)xgb[i], 4 * cc * CK, 0));
+          if (in_last)
+            xr[PIECES - 1] =
+                __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(halo_rsrc, (int)xgb[PIECES - 1], 4 * cc * CK, 0));
         } else {
+          // border blocks only: the geometry is recomputed here from a value the compiler cannot trace back to the
+          // lane index, so that it is not hoisted out of the item loop into registers the interior path never uses
+          int xp = xpix0;
+          asm volatile("" : "+v"(xp));
 #pragma unroll
-          for (int i = 0; i < WP_PIECES; ++i) {
-            const int iy = ty0 + (xyx[i] >> 16) - 1, ix = tx0 + ((xyx[i] >> 8) & 255) - 1;
-            const bool ok = (i < WP_PIECES - 1 || in_last) && iy >= 0 && iy < a.H && ix >= 0 && ix < a.W;
+          for (int i = 0; i < PIECES; ++i) {
+            const int pix = min(xp + PSTEP * i, G::PIX - 1);
+            const int ly = pix / TW, lx = pix - ly * TW;
+            const int iy = ty0 + ly - PAD, ix = tx0 + lx - PAD;
+            const bool ok = (i < PIECES - 1 || in_last) && iy >= 0 && iy < a.H && ix >= 0 && ix < a.W;
             f32x4 v = {0.f, 0.f, 0.f, 0.f};
-            if (ok) v = *reinterpret_cast<const f32x4*>(src + xgb[i]);
+            if (ok) v = *reinterpret_cast<const f32x4*>(src + 4 * (ly * (int)a.in.sY + lx * (int)a.in.sX + xpart * 4));
             xr[i] = v;
           }
         }
       };
       auto commit = [&]() {
 #pragma unroll
-        for (int i = 0; i < WP_PIECES - 1; ++i)
-          *reinterpret_cast<__attribute__((address_space(3))) f32x4*>((size_t)(wb0 + xlb[i])) = xr[i];
+        for (int i = 0; i < PIECES - 1; ++i)
+          *reinterpret_cast<__attribute__((address_space(3))) f32x4*>((size_t)(wb0 + xlb0 + 4u * PSTEP * CKP * i)) = xr[i];
         if (in_last)
-          *reinterpret_cast<__attribute__((address_space(3))) f32x4*>((size_t)(wb0 + xlb[WP_PIECES - 1])) = xr[WP_PIECES - 1];
+          *reinterpret_cast<__attribute__((address_space(3))) f32x4*>((size_t)(wb0 + xlb0 + 4u * PSTEP * CKP * (PIECES - 1))) =
+              xr[PIECES - 1];
       };
 
       acc_t acc[MT];
 #pragma unroll
       for (int mt = 0; mt < MT; ++mt)
 #pragma unroll
-        for (int j = 0; j < 16; ++j) acc[mt][j] = 0.f;
+        for (int j = 0; j < WpMfma<MF>::NREG; ++j) acc[mt][j] = 0.f;
 
       prefetch(0);
       commit();
       for (int cc = 0; cc < nCC; ++cc) {
         if (!(ABL & 2) && cc + 1 < nCC) prefetch(cc + 1);
-        const float* wp = panel + (size_t)cc * (9 * NT * WP_CK) + boff;
+        const float* wp = panel + (size_t)cc * (NTAPS * NT * CK) + boff;
         f32x4 av[2][MT], bv[2];
         auto load_frag = [&](int tap, f32x4* a_, f32x4& b_) {
           const int ty = tap / KS, tx = tap - ty * KS;
-          const int tapoff = (ty * TW + tx) * WP_CKP;
 #pragma unroll
-          for (int mt = 0; mt < MT; ++mt) a_[mt] = *reinterpret_cast<const f32x4*>(wbuf + apix[mt] + tapoff);
-          b_ = *reinterpret_cast<const f32x4*>(wp + tap * (NT * WP_CK));
+          for (int mt = 0; mt < MT; ++mt) {
+            if (CK == 16) a_[mt] = *reinterpret_cast<const f32x4*>(wbuf + asw[tx][(mt + ty) & 1] + (mt + ty) * TW * CKP);
+            else a_[mt] = *reinterpret_cast<const f32x4*>(wbuf + apix[mt] + (ty * TW + tx) * CKP);
+          }
+          b_ = *reinterpret_cast<const f32x4*>(wp + tap * (NT * CK));
         };
         load_frag(0, av[0], bv[0]);
 #pragma unroll
-        for (int q = 0; q < 9; ++q) {
-          if (q + 1 < 9) load_frag(q + 1, av[(q + 1) & 1], bv[(q + 1) & 1]);
+        for (int q = 0; q < NTAPS; ++q) {
+          if (q + 1 < NTAPS) load_frag(q + 1, av[(q + 1) & 1], bv[(q + 1) & 1]);
           __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
           for (int j = 0; j < 4; ++j)
 #pragma unroll
             for (int mt = 0; mt < MT; ++mt) {
               if (ABL & 4) acc[mt][j] += bv[q & 1][j] * av[q & 1][mt][j];
-              else acc[mt] = __builtin_amdgcn_mfma_f32_32x32x2f32(bv[q & 1][j], av[q & 1][mt][j], acc[mt], 0, 0, 0);
+              else acc[mt] = WpMfma<MF>::run(bv[q & 1][j], av[q & 1][mt][j], acc[mt]);
             }
           __builtin_amdgcn_sched_barrier(0);
         }
@@ -188,13 +289,18 @@ __global__ __launch_bounds__(WP_NW * 64, 1) void igemm_wp_kernel(const ConvArgs 
       } else {
 #define EPI_PRE_SYNC ((void)0)
 #define EPI_ES_BASE wbuf
-#define EPI_PHASED
 #define EPI_OYW ty0
 #define EPI_FULL ((ty0 + 4 <= a.H) && (tx0 + 16 <= a.W))
+        // 32-pixel tiles go through the scratch one after the other (it holds one); the four 16-pixel tiles fit at once
+        if constexpr (MF == 32) {
+#define EPI_PHASED
 #include "igemm_epilogue.inc"
+#undef EPI_PHASED
+        } else {
+#include "igemm_epilogue.inc"
+        }
 #undef EPI_PRE_SYNC
 #undef EPI_ES_BASE
-#undef EPI_PHASED
 #undef EPI_OYW
 #undef EPI_FULL
       }
@@ -204,17 +310,34 @@ __global__ __launch_bounds__(WP_NW * 64, 1) void igemm_wp_kernel(const ConvArgs 
   }
 }
 
+template <int ABL>
+__global__ __launch_bounds__(WP_NW * 64, 1) void igemm_wp_kernel(const ConvArgs a) {
+  igemm_wp_body<32, 3, 8, ABL>(a);
+}
+
+// the weight-stationary 5x5 forms: compiled for up to 16 waves (MF = 32: 120 VGPRs) and 12 waves (MF = 16: 158 VGPRs),
+// no scratch in either
+constexpr int ws5_nwmax(int MF) { return MF == 32 ? 16 : 12; }
+template <int MF, int CK>
+__global__ __launch_bounds__(ws5_nwmax(MF) * 64, 1) void igemm_ws5_kernel(const ConvArgs a) {
+  igemm_wp_body<MF, 5, CK, 0>(a);
+}
+
 }  // namespace
+
+typedef WpGeo<32, 3, 8> Wp3;
+// groups of `nw` wave items (4 x 16 pixel blocks, whole 16-row bands) of a launch: the kernel's logical grid
+static long wp_groups(const ConvArgs& a, int nw) { return cdiv((long)a.B * cdiv(a.H, 16) * cdiv(a.W, 16) * 4, nw); }
 
 // whether the wave-private kernel covers this launch of plan `pl` (the 8-channel-chunk 3x3 plan, whose packed panel it
 // reads as it is)
 // force: the shape test only (unit tests run small launches through it); otherwise also "is it worth it": enough
-// super-tiles for a whole chip of 16-wave workgroups, and DEPGAN_IGEMM_WP=1 (opt-in: measured neutral)
+// groups for a whole chip of 16-wave workgroups, and DEPGAN_IGEMM_WP=1 (opt-in: measured neutral)
 bool dg_conv_igemm_wp_supported(const ConvPlan& pl, const ConvArgs& a, bool force) {
-  if (pl.variant != 8 || pl.bf16 || pl.KS != 3 || pl.CK != WP_CK) return false;
-  if (a.Cin != pl.Cin || (a.Cin % WP_CK) || a.Cin > 64 || (a.Cout % 32) || a.groups > 1 || a.cpt > 0 || a.dbg) return false;
+  if (pl.variant != 8 || pl.bf16 || pl.KS != 3 || pl.CK != 8) return false;
+  if (a.Cin != pl.Cin || (a.Cin % 8) || a.Cin > 64 || (a.Cout % 32) || a.groups > 1 || a.cpt > 0 || a.dbg) return false;
   if (a.ep.head_out) return false;   // the fused head lives in the tile kernel's epilogue only
-  const size_t lds = ((size_t)a.Cin * 9 * 32 + (size_t)WP_NW * WP_WAVE_FLOATS) * sizeof(float);
+  const size_t lds = ((size_t)a.Cin * 9 * 32 + (size_t)WP_NW * Wp3::WAVE_FLOATS) * sizeof(float);
   if (lds > 160 * 1024) return false;
   if (force) return true;
   static int on = -1;
@@ -223,20 +346,20 @@ bool dg_conv_igemm_wp_supported(const ConvPlan& pl, const ConvArgs& a, bool forc
     on = (e && atoi(e) != 0) ? 1 : 0;     // opt-in: measured neutral (see the header of this file)
   }
   if (!on) return false;
-  const long sup = (long)a.B * cdiv(a.H, 16) * cdiv(a.W, 64);
+  const long sup = wp_groups(a, WP_NW);
   return (sup & 7) == 0 && sup * (a.Cout / 32) >= 256;
 }
 
 int dg_conv_igemm_wp(const ConvPlan& pl, const ConvArgs& a_in, hipStream_t st) {
   ConvArgs a = a_in;
   DGCHECK(dg_conv_igemm_check(pl, a));   // unit tests launch this kernel directly, not through dg_conv_igemm
-  const size_t lds = ((size_t)a.Cin * 9 * 32 + (size_t)WP_NW * WP_WAVE_FLOATS) * sizeof(float);
+  const size_t lds = ((size_t)a.Cin * 9 * 32 + (size_t)WP_NW * Wp3::WAVE_FLOATS) * sizeof(float);
   static DgOncePerDevice once;
   if (once.need())
     HIPCHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&igemm_wp_kernel<0>),
                                  hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
   const int nNT = a.Cout / 32;
-  a.lgx = a.B * cdiv(a.H, 16) * cdiv(a.W, 64);
+  a.lgx = (int)wp_groups(a, WP_NW);
   a.lgy = nNT;
   const long total = (long)a.lgx * nNT;
   // one workgroup per CU, rounded down to a multiple of 8 nNT (XCD round-robin x channel tiles: a workgroup keeps its
@@ -244,7 +367,7 @@ int dg_conv_igemm_wp(const ConvPlan& pl, const ConvArgs& a_in, hipStream_t st) {
   long G = dg_cu_count();
   G -= G % (8L * nNT);
   if (G < 8L * nNT) G = 8L * nNT;
-  // (a super-tile count that is not a multiple of 8 takes the plain id -> (super-tile, channel tile) form, in which a
+  // (a group count that is not a multiple of 8 takes the plain id -> (group, channel tile) form, in which a
   // persistent workgroup would change its channel tile: one item per workgroup then -- unit tests only)
   if (G > total || (a.lgx & 7) != 0) G = total;
 #ifdef DEPGAN_WP_ABLATIONS
@@ -275,4 +398,78 @@ int dg_conv_igemm_wp(const ConvPlan& pl, const ConvArgs& a_in, hipStream_t st) {
   hipLaunchKernelGGL((igemm_wp_kernel<0>), dim3((unsigned)G), dim3(WP_NW * 64), lds, st, a);
   HIPCHECK(hipGetLastError());
   return DG_OK;
+}
+
+// ---------------------------------------------------------------------------
+// the weight-stationary 5x5 forms (plans 2 and 3 of dg_plan_conv, whose packed panels they read as they are)
+// ---------------------------------------------------------------------------
+// waves per workgroup: what 160 KB of LDS admit beside the panel, at most the instantiation's register budget
+template <int MF, int CK>
+static int ws5_waves(int Cin) {
+  const long panel = (long)Cin * 25 * MF, wave = WpGeo<MF, 5, CK>::WAVE_FLOATS;
+  long nw = (160L * 1024 / 4 - panel) / wave;
+  // DEPGAN_IGEMM_WS5_WAVES=<n> caps it for A/B runs.  Default 16: only 16->32 has room for more than 12, and there
+  // 16 waves measured equal at batch 96 and 10 % faster at batch 32 (125 against 139 us)
+  static int cap = -1;
+  if (cap < 0) {
+    const char* e = getenv("DEPGAN_IGEMM_WS5_WAVES");
+    cap = (e && atoi(e) >= 4) ? atoi(e) : 16;
+  }
+  if (nw > cap) nw = cap;
+  return (int)(nw < ws5_nwmax(MF) ? nw : ws5_nwmax(MF));
+}
+static int ws5_waves_of(const ConvPlan& pl, int Cin) { return pl.MF == 32 ? ws5_waves<32, 8>(Cin) : ws5_waves<16, 16>(Cin); }
+
+// force: the shape test only (the operator surface, path 9); otherwise also the measured per-shape default and the size
+// threshold, or DEPGAN_IGEMM_WS5=0|1 for all covered shapes (read once)
+bool dg_conv_igemm_ws5_supported(const ConvPlan& pl, const ConvArgs& a, bool force) {
+  if ((pl.variant != 2 && pl.variant != 3) || pl.bf16 || pl.KS != 5) return false;
+  if (pl.CK != (pl.MF == 32 ? 8 : 16)) return false;
+  if (a.Cin != pl.Cin || a.Cout != pl.Cout || a.Cout != pl.MF || (a.Cin != 16 && a.Cin != 32)) return false;
+  if (a.groups > 1 || a.cpt > 0 || a.dbg || a.ep.head_out) return false;
+  if (force) return true;
+  static int mode = -2;
+  if (mode == -2) {
+    const char* e = getenv("DEPGAN_IGEMM_WS5");
+    mode = e ? (atoi(e) != 0 ? 1 : 0) : -1;
+  }
+  if (mode == 0) return false;
+  // fewer wave items than two per wave slot of the chip: the tile kernel's smaller items balance better
+  const long items = (long)a.B * cdiv(a.H, 4) * cdiv(a.W, 16);
+  const long slots = (long)dg_cu_count() * ws5_waves_of(pl, a.Cin);
+  if (items < 2 * slots) return false;
+  if (mode == 1) return true;
+  // the measured per-shape default (profiles/ws5_experiments.md): 16->16 and 16->32 at both batches of the step
+  // (-4 ... -9 %); 32->32 at batch 96 (8 items per slot: -7.6 %) but not at batch 32 (2.7 per slot: +5 %, the 102 KB
+  // panel load in front of three short rounds); 32->16 at neither (+3 ... +5 %: 11 waves, two SIMDs with two)
+  if (a.Cin == 32 && a.Cout == 16) return false;
+  if (a.Cin == 32 && a.Cout == 32) return items >= 4 * slots;
+  return true;
+}
+
+const char* dg_conv_igemm_ws5_name(const ConvPlan& pl) { return pl.MF == 32 ? "igemm_ws5_kernel<32,8>" : "igemm_ws5_kernel<16,16>"; }
+
+template <int MF, int CK>
+static int ws5_launch(ConvArgs& a, hipStream_t st) {
+  const int nw = ws5_waves<MF, CK>(a.Cin);
+  const size_t lds = ((size_t)a.Cin * 25 * MF + (size_t)nw * WpGeo<MF, 5, CK>::WAVE_FLOATS) * sizeof(float);
+  static DgOncePerDevice once;
+  if (once.need())
+    HIPCHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&igemm_ws5_kernel<MF, CK>),
+                                 hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+  a.lgx = (int)wp_groups(a, nw);
+  a.lgy = 1;
+  // one workgroup per CU; a multiple of 8 when the groups are dealt over the XCDs
+  long G = dg_cu_count();
+  if ((a.lgx & 7) == 0) G -= G % 8;
+  if (G > a.lgx || G < 1) G = a.lgx;
+  hipLaunchKernelGGL((igemm_ws5_kernel<MF, CK>), dim3((unsigned)G), dim3(nw * 64), lds, st, a);
+  HIPCHECK(hipGetLastError());
+  return DG_OK;
+}
+
+int dg_conv_igemm_ws5(const ConvPlan& pl, const ConvArgs& a_in, hipStream_t st) {
+  ConvArgs a = a_in;
+  DGCHECK(dg_conv_igemm_check(pl, a));   // the operator surface launches this kernel directly
+  return pl.MF == 32 ? ws5_launch<32, 8>(a, st) : ws5_launch<16, 16>(a, st);
 }

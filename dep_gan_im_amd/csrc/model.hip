@@ -1869,6 +1869,10 @@ static int op_conv_run(ConvArgs a, const float* w_hwio, int Cin, int Cout, int K
   }
   if ((path == 6 || path == 7) && pl.CK != 8) { dg_set_error("op_conv: the 8-channel-chunk variant does not cover this shape"); return DG_ERR_UNSUPPORTED; }
   if (path >= 3 && path <= 5 && !pl.bf16) { dg_set_error("op_conv: the bf16 MFMA kernel does not cover this shape"); return DG_ERR_UNSUPPORTED; }
+  // path 9 names a 5x5 kernel: another KS is a bad argument (status 1, as for a path number that does not exist), what
+  // the 5x5 kernel does not cover is status 3
+  if (path == 9 && KS != 5) { dg_set_error("op_conv: path 9 is the weight-stationary 5x5 kernel, KS must be 5"); return DG_ERR_ARG; }
+  if (path == 9 && !dg_conv_igemm_ws5_supported(pl, a, true)) { dg_set_error("op_conv: the weight-stationary 5x5 kernel does not cover this shape"); return DG_ERR_UNSUPPORTED; }
   if (path == 1 && pl.variant < 0) { dg_set_error("op_conv: MFMA path not available for this shape"); return DG_ERR_UNSUPPORTED; }
   if (path != 2 && pl.variant >= 0) {
     float* wp = nullptr;
@@ -1879,7 +1883,9 @@ static int op_conv_run(ConvArgs a, const float* w_hwio, int Cin, int Cout, int K
       if (path == 7) {
         if (dg_conv_igemm_wp_supported(pl, a, true)) rc = dg_conv_igemm_wp(pl, a, st);
         else { dg_set_error("op_conv: the wave-private kernel does not cover this shape"); rc = DG_ERR_UNSUPPORTED; }
-      } else if (path == 6) {
+      } else if (path == 9) {
+        rc = dg_conv_igemm_ws5(pl, a, st);
+      } else if (path == 6 || path == 1) {
         // the workgroup-tile kernel itself (the reference the wave-private kernel must match bit for bit)
         rc = dg_conv_igemm_tile(pl, a, st);
       } else {
@@ -2110,7 +2116,7 @@ int depgan_op_conv2d_fused(const float* in, long isB, long isY, long isX, const 
   }
   if ((head_w || head_b || head_out) && !(head_w && head_b && head_out)) { dg_set_error("op_conv2d_fused: null head argument"); return DG_ERR_ARG; }
   if (head_skip_out && !head_out) { dg_set_error("op_conv2d_fused: head_skip_out without a head"); return DG_ERR_ARG; }
-  if (path < 1 || path > 8) { dg_set_error("op_conv2d_fused: path must be 1 ... 8"); return DG_ERR_ARG; }
+  if (path < 1 || path > 9) { dg_set_error("op_conv2d_fused: path must be 1 ... 9"); return DG_ERR_ARG; }
   ConvArgs a;
   memset(&a, 0, sizeof(a));
   zero_ep(&a.ep);

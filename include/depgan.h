@@ -428,7 +428,9 @@ int depgan_op_head_bf16s(const void* a, const float* w, const float* b, float* o
  * 4 / 5: fp32 operands split into 2 / 3 bf16 terms, 3 / 6 products on the bf16 pipe (depgan_config.f32_split = 3 / 6),
  * 6: fp32 MFMA with 8-channel chunks, workgroup tiles (large 3x3 launches with more than 64 input channels),
  * 7: the wave-private form of 6 (csrc/igemm_wp.hip: large 3x3 launches with Cin <= 64; bit-identical to 6),
- * 8: Winograd F(2x2,3x3) on the fp32 matrix pipe (csrc/igemm_wino.hip: 3x3, Cin % 8 == 0, Cout % 32 == 0, even H, W) */
+ * 8: Winograd F(2x2,3x3) on the fp32 matrix pipe (csrc/igemm_wino.hip: 3x3, Cin % 8 == 0, Cout % 32 == 0, even H, W),
+ * 9: the weight-stationary, wave-private 5x5 form of 1 (csrc/igemm_wp.hip: 5x5, Cin and Cout in {16, 32}, no fused
+ *    head; any size; bit-identical to 1; status 1 for KS != 5, status 3 for everything else it does not cover) */
 int depgan_op_conv2d(const float* in, const float* w_hwio, const float* bias, float* out, int B, int H, int W,
                      int Cin, int Cout, int KS, int relu, int path, void* hip_stream);
 int depgan_op_conv2d_bwd_data(const float* dy, const float* w_hwio, float* dx, int B, int H, int W, int Cin,
@@ -470,7 +472,7 @@ int depgan_op_deconv2x2_wgrad(const float* in, const float* dout, float* dw_hwoi
  * Optional operands are NULL (their strides are then ignored); scale / shift and film_mul / film_add come in pairs;
  * film_mul / film_add are rows of film_ld floats per sample.  w_hwio is (KS, KS, Cin, Cout); bwd = 1 is the
  * backward-data form: `in` has Cout channels, `out` (and the epilogue operands) Cin.  path as in depgan_op_conv2d:
- * 1 MFMA, 2 direct, 3 bf16 pipe, 4 / 5 split, 6 8-channel chunks, 7 wave-private, 8 Winograd.  Status 1 for null or
+ * 1 MFMA, 2 direct, 3 bf16 pipe, 4 / 5 split, 6 8-channel chunks, 7 wave-private, 8 Winograd, 9 weight-stationary 5x5.  Status 1 for null or
  * non-positive arguments (before any HIP call) and whatever the launcher's argument checks refuse, 3 for what the kernel
  * of that path does not cover; nothing is written then. */
 int depgan_op_conv2d_fused(const float* in, long isB, long isY, long isX, const float* w_hwio, const float* bias,
