@@ -211,7 +211,16 @@ static inline int dg_cu_count() {   // CUs of the current device, asked once per
 }
 
 // ---- conv plans -----------------------------------------------------------
-// How one convolution maps on the MFMA implicit-GEMM kernel.
+// How one convolution maps on the MFMA implicit-GEMM kernels: the kernel family, and within it the instantiation that
+// the fields MF / KS / CK select.
+enum ConvFamily {
+  CONV_DIRECT = 0,  // not MFMA-eligible: the direct kernel on the raw HWIO tensor (no packed panel)
+  CONV_TILE,        // fp32 workgroup-tile kernels (igemm_conv.hip; the wave-private kernels read the same panels)
+  CONV_WINO,        // Winograd F(2x2,3x3) (igemm_wino.hip): panel [nt][chunk][16 frequencies][32][8] of G g G^T
+  CONV_BF16,        // bf16 matrix pipe (igemm_bf16.hip): panels are packed as bf16, the activation operand is rounded
+                    // to bf16 while it is staged, accumulation stays fp32
+  CONV_SPLIT,       // fp32 operands split into `planes` bf16 terms each (igemm_split_kernel)
+};
 struct ConvPlan {
   int KS, Cin, Cout;
   int MF;    // MFMA tile edge: 32 (v_mfma_f32_32x32x2_f32) or 16 (v_mfma_f32_16x16x4_f32)
@@ -219,23 +228,36 @@ struct ConvPlan {
   int CK;    // input channels staged per LDS chunk
   int nNT, nCC;
   size_t packedFloats;  // size of the packed panel in 4-byte units (bf16 plans: two elements per unit)
-  int variant;  // index into the instantiation table, -1 = not MFMA-eligible
-  int bf16;     // 1: bf16 matrix pipe (igemm_bf16.hip): panels are packed as bf16, the activation operand is rounded to
-                // bf16 while it is staged, accumulation stays fp32
+  ConvFamily family;
+  int planes;           // bf16 terms per packed element: 0 for fp32, 1 for bf16, 2 or 3 for split
+  // taps of the packed panel [nt][cc][tap][n][k]: the kernel's, or the 16 Winograd "frequencies"
+  int ntaps() const { return family == CONV_WINO ? 16 : KS * KS; }
+  // split panels: taps per staged group of [nt][cc][tap group][plane][tap][n][k = 16]
+  int tapg() const { return KS == 5 ? 5 : KS * KS; }
 };
+static inline bool dg_plan_mfma(const ConvPlan& pl) { return pl.family != CONV_DIRECT; }
+static inline bool dg_plan_bf16(const ConvPlan& pl) { return pl.family == CONV_BF16; }
+static inline bool dg_plan_split(const ConvPlan& pl) { return pl.family == CONV_SPLIT; }
+static inline bool dg_plan_wino(const ConvPlan& pl) { return pl.family == CONV_WINO; }
+// the 8-channel-chunk 3x3 tile plan (dg_plan_conv_items) and the 5x5 tile plans (32x5x8 and 16x5x16)
+static inline bool dg_plan_tile3_ck8(const ConvPlan& pl) { return pl.family == CONV_TILE && pl.KS == 3 && pl.CK == 8; }
+static inline bool dg_plan_tile5(const ConvPlan& pl) { return pl.family == CONV_TILE && pl.KS == 5; }
+// the plan of a convolution that runs on the direct kernel
+static inline ConvPlan dg_plan_direct() {
+  ConvPlan p = {};
+  p.family = CONV_DIRECT;
+  return p;
+}
 ConvPlan dg_plan_conv(int KS, int Cin, int Cout);
 // ... knowing the number of work items of its launches (chunk size by launch size, see igemm_conv.hip)
 ConvPlan dg_plan_conv_items(int KS, int Cin, int Cout, long items);
 // the bf16 plan where the bf16 kernel covers the shape (Cout % 32 == 0, Cin >= 8), else the fp32 plan
 ConvPlan dg_plan_conv_bf16(int KS, int Cin, int Cout);
-// fp32 operands split into `planes` (2 or 3) bf16 terms each, 3 or 6 products on the bf16 pipe (igemm_split_kernel);
-// the plan's bf16 field then holds the number of planes and its packed layout is
-// [nt][cc][tap group][plane][tap][n][k = 16]
+// fp32 operands split into `planes` (2 or 3) bf16 terms each, 3 or 6 products on the bf16 pipe (igemm_split_kernel)
 ConvPlan dg_plan_conv_split(int KS, int Cin, int Cout, int planes);
 int dg_conv_igemm_bf16(const ConvPlan& pl, const ConvArgs& a, hipStream_t st);
-// byte size of one packed element of a plan
-// bytes of packed storage per element of the plain [nt][cc][tap][n][k] panel (split plans store `bf16` planes of it)
-static inline size_t dg_plan_elem_bytes(const ConvPlan& pl) { return pl.variant >= 200 ? 2 * (size_t)pl.bf16 : (pl.bf16 ? 2 : 4); }
+// bytes of packed storage per element of the plain [nt][cc][tap][n][k] panel (split plans store `planes` planes of it)
+static inline size_t dg_plan_elem_bytes(const ConvPlan& pl) { return pl.planes ? 2 * (size_t)pl.planes : 4; }
 
 // One weight-packing job of a batched launch (dg_pack_weights_batch): what dg_pack_weights takes, plus an optional
 // re-spacing of the channel-tile blocks in the destination (nt_stride elements between consecutive channel tiles;
@@ -276,14 +298,14 @@ int dg_conv_igemm_check(const ConvPlan& pl, const ConvArgs& a);
 bool dg_conv_igemm_wp_supported(const ConvPlan& pl, const ConvArgs& a, bool force);
 int dg_conv_igemm_wp(const ConvPlan& pl, const ConvArgs& a, hipStream_t st);
 // weight-stationary, wave-private 5x5 kernel (igemm_wp.hip): Cin, Cout in {16, 32}, one channel tile; reads the packed
-// panel of plans 2 / 3 as it is and is bit-identical to igemm_conv_kernel<., 5, ., 25>
+// panel of the 5x5 tile plans as it is and is bit-identical to igemm_conv_kernel<., 5, ., 25>
 bool dg_conv_igemm_ws5_supported(const ConvPlan& pl, const ConvArgs& a, bool force);
 int dg_conv_igemm_ws5(const ConvPlan& pl, const ConvArgs& a, hipStream_t st);
 const char* dg_conv_igemm_ws5_name(const ConvPlan& pl);
 int dg_conv_igemm_tile(const ConvPlan& pl, const ConvArgs& a, hipStream_t st);
 // the launch for (pl, a) can carry the fused one-channel head (Epilogue::head_*): 32 -> 32, 8-channel-chunk 3x3 kernel
 bool dg_conv_igemm_head_supported(const ConvPlan& pl, const ConvArgs& a);
-// Winograd F(2x2,3x3) kernel (igemm_wino.hip): plan variant 9, panel [nt][chunk][16 frequencies][32][8] of G g G^T
+// Winograd F(2x2,3x3) kernel (igemm_wino.hip): plan family CONV_WINO, panel [nt][chunk][16 frequencies][32][8] of G g G^T
 ConvPlan dg_plan_conv_wino(int Cin, int Cout);
 bool dg_conv_wino_supported(const ConvPlan& pl, const ConvArgs& a);
 const char* dg_conv_wino_name(const ConvArgs& a);

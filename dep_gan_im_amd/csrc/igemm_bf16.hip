@@ -230,34 +230,34 @@ ConvPlan dg_plan_conv_bf16(int KS, int Cin, int Cout) {
   ConvPlan p = dg_plan_conv(KS, Cin, Cout);
   // layers the bf16 kernel does not cover keep the fp32 matrix pipe (their weights are bf16-valued all the same):
   // Cout not a multiple of 32 (the 16-channel critic layers), edge layers (Cin < 8), odd channel counts
-  if (p.variant < 0 || (Cout % 32) != 0 || Cin < 8 || (Cin % 4) != 0 || !(KS == 1 || KS == 3 || KS == 5)) return p;
-  p.bf16 = 1;
+  if (!dg_plan_mfma(p) || (Cout % 32) != 0 || Cin < 8 || (Cin % 4) != 0 || !(KS == 1 || KS == 3 || KS == 5)) return p;
+  p.family = CONV_BF16;
+  p.planes = 1;
   p.MF = 32;
   p.NT = 32;
   p.CK = 32;
   p.nNT = cdiv(Cout, 32);
   p.nCC = cdiv(Cin, 32);
-  p.variant = KS == 3 ? 100 : (KS == 5 ? 101 : 102);
   const size_t elems = (size_t)p.nNT * p.nCC * KS * KS * p.NT * p.CK;
   p.packedFloats = (elems + 1) / 2;     // bf16 elements, counted in 4-byte units for the allocator
   return p;
 }
 
-// split plans: bf16 = number of planes (2 or 3); Cin a multiple of 4 and >= 8 like the bf16 plans; Cout a multiple of 16 --
+// split plans: 2 or 3 planes; Cin a multiple of 4 and >= 8 like the bf16 plans; Cout a multiple of 16 --
 // a 16-channel layer (the critics' first 5x5 convolutions) runs as half of a 32-channel tile with zero weight rows: twice
 // the MFMAs it needs, still a third of the cycles the fp32 pipe's 16x16x4 form takes for it
 ConvPlan dg_plan_conv_split(int KS, int Cin, int Cout, int planes) {
   ConvPlan p = dg_plan_conv(KS, Cin, Cout);
-  if (p.variant < 0 || (Cout % 16) != 0 || Cin < 8 || (Cin % 4) != 0 || !(KS == 1 || KS == 3 || KS == 5) ||
+  if (!dg_plan_mfma(p) || (Cout % 16) != 0 || Cin < 8 || (Cin % 4) != 0 || !(KS == 1 || KS == 3 || KS == 5) ||
       (planes != 2 && planes != 3))
     return p;
-  p.bf16 = planes;
+  p.family = CONV_SPLIT;
+  p.planes = planes;
   p.MF = 32;
   p.NT = 32;
   p.CK = 16;
   p.nNT = cdiv(Cout, 32);
   p.nCC = cdiv(Cin, 16);
-  p.variant = 200 + (KS == 3 ? 0 : (KS == 5 ? 1 : 2));
   const size_t elems = (size_t)planes * p.nNT * p.nCC * KS * KS * p.NT * p.CK;
   p.packedFloats = (elems + 1) / 2;
   return p;
@@ -307,21 +307,20 @@ static int launch_bf16(const ConvArgs& a, hipStream_t st) {
 }
 
 int dg_conv_igemm_bf16(const ConvPlan& pl, const ConvArgs& a, hipStream_t st) {
-  if (pl.variant >= 200) {
-    const int ks = pl.variant - 200;
-    if (pl.bf16 == 3) {
-      if (ks == 0) return launch_split<3, 9, 3>(a, st);
-      if (ks == 1) return launch_split<5, 5, 3>(a, st);
-      return launch_split<1, 1, 3>(a, st);
-    }
-    if (ks == 0) return launch_split<3, 9, 2>(a, st);
-    if (ks == 1) return launch_split<5, 5, 2>(a, st);
-    return launch_split<1, 1, 2>(a, st);
+  if (dg_plan_split(pl) && pl.planes == 3) switch (pl.KS) {
+    case 3: return launch_split<3, 9, 3>(a, st);
+    case 5: return launch_split<5, 5, 3>(a, st);
+    case 1: return launch_split<1, 1, 3>(a, st);
   }
-  switch (pl.variant) {
-    case 100: return launch_bf16<3, 9>(a, st);
-    case 101: return launch_bf16<5, 5>(a, st);
-    case 102: return launch_bf16<1, 1>(a, st);
+  if (dg_plan_split(pl) && pl.planes == 2) switch (pl.KS) {
+    case 3: return launch_split<3, 9, 2>(a, st);
+    case 5: return launch_split<5, 5, 2>(a, st);
+    case 1: return launch_split<1, 1, 2>(a, st);
+  }
+  if (dg_plan_bf16(pl)) switch (pl.KS) {
+    case 3: return launch_bf16<3, 9>(a, st);
+    case 5: return launch_bf16<5, 5>(a, st);
+    case 1: return launch_bf16<1, 1>(a, st);
   }
   dg_set_error("dg_conv_igemm_bf16: no bf16 variant for KS=%d", pl.KS);
   return DG_ERR_UNSUPPORTED;

@@ -95,7 +95,7 @@ int dg_conv_bf16_mh(const ConvPlan& pl, const ConvArgs& a, TViewH mask_h, hipStr
     dg_set_error("dg_conv_bf16_mh: bad argument");
     return DG_ERR_ARG;
   }
-  if (pl.bf16 != 1 || (pl.variant != 100 && pl.variant != 102) || (a.Cout % 32) || (a.Cin % 4)) {
+  if (!dg_plan_bf16(pl) || (pl.KS != 3 && pl.KS != 1) || (a.Cout % 32) || (a.Cin % 4)) {
     dg_set_error("dg_conv_bf16_mh: needs a bf16 plan of a 3x3 or 1x1 convolution, Cin %% 4 == 0, Cout %% 32 == 0 (%d -> %d)",
                  a.Cin, a.Cout);
     return DG_ERR_UNSUPPORTED;
@@ -114,5 +114,5 @@ int dg_conv_bf16_mh(const ConvPlan& pl, const ConvArgs& a, TViewH mask_h, hipStr
   ConvArgsM m;
   static_cast<ConvArgs&>(m) = a;
   m.mask_h = mask_h;
-  return pl.variant == 100 ? launch_mh<3, 9>(m, st) : launch_mh<1, 1>(m, st);
+  return pl.KS == 3 ? launch_mh<3, 9>(m, st) : launch_mh<1, 1>(m, st);
 }

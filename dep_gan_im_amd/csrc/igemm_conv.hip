@@ -360,39 +360,22 @@ __global__ __launch_bounds__(256, PERS ? 4 : 1) void igemm_conv_head_kernel(cons
 }
 
 // ---------------------------------------------------------------------------
-// variants
+// plans
 // ---------------------------------------------------------------------------
-struct VariantInfo {
-  int MF, KS, CK, TAPG;
-};
-static const VariantInfo kVariants[] = {
-    {32, 3, 16, 9},   // 0
-    {16, 3, 16, 9},   // 1
-    {32, 5, 8, 25},   // 2
-    {16, 5, 16, 25},  // 3
-    {32, 1, 32, 1},   // 4
-    {16, 1, 16, 1},   // 5
-};
-
+// The fp32 tile plan: MF by the channel count, the chunk size by (MF, KS) -- the instantiations of dispatch_tile
 ConvPlan dg_plan_conv(int KS, int Cin, int Cout) {
-  ConvPlan p;
+  ConvPlan p = dg_plan_direct();
   p.KS = KS;
   p.Cin = Cin;
   p.Cout = Cout;
-  p.variant = -1;
-  p.bf16 = 0;
   p.MF = (Cout % 32 == 0) ? 32 : 16;
   p.NT = p.MF;
   p.CK = 16;
-  p.nNT = p.nCC = 0;
-  p.packedFloats = 0;
   if (Cin < 8 || (Cin % 4) != 0 || Cout < 8) return p;  // direct kernel territory
-  for (int i = 0; i < (int)(sizeof(kVariants) / sizeof(kVariants[0])); ++i)
-    if (kVariants[i].MF == p.MF && kVariants[i].KS == KS) {
-      p.variant = i;
-      p.CK = kVariants[i].CK;
-    }
-  if (p.variant < 0) return p;
+  if (KS != 1 && KS != 3 && KS != 5) return p;
+  if (p.MF == 32 && KS == 5) p.CK = 8;
+  if (p.MF == 32 && KS == 1) p.CK = 32;
+  p.family = CONV_TILE;
   p.nNT = cdiv(Cout, p.NT);
   p.nCC = cdiv(Cin, p.CK);
   p.packedFloats = (size_t)p.nNT * p.nCC * KS * KS * p.NT * p.CK;
@@ -408,8 +391,7 @@ ConvPlan dg_plan_conv_items(int KS, int Cin, int Cout, long items) {
   ConvPlan p = dg_plan_conv(KS, Cin, Cout);
   const char* e = getenv("DEPGAN_IGEMM_CK8");
   const bool on = !(e && atoi(e) == 0);
-  if (on && p.variant == 0 && KS == 3 && p.MF == 32 && (Cin % 8) == 0 && items >= 1536) {
-    p.variant = 8;
+  if (on && p.family == CONV_TILE && KS == 3 && p.MF == 32 && (Cin % 8) == 0 && items >= 1536) {
     p.CK = 8;
     p.nCC = cdiv(Cin, p.CK);
     p.packedFloats = (size_t)p.nNT * p.nCC * KS * KS * p.NT * p.CK;
@@ -420,8 +402,8 @@ ConvPlan dg_plan_conv_items(int KS, int Cin, int Cout, long items) {
 // Winograd F(2x2,3x3) plan (igemm_wino.hip): 8-channel chunks, 16 transform-domain panels per chunk
 ConvPlan dg_plan_conv_wino(int Cin, int Cout) {
   ConvPlan p = dg_plan_conv(3, Cin, Cout);
-  if (p.variant != 0 || (Cin % 8) != 0 || (Cout % 32) != 0) { p.variant = -1; return p; }
-  p.variant = 9;
+  if (p.family != CONV_TILE || (Cin % 8) != 0 || (Cout % 32) != 0) { p.family = CONV_DIRECT; return p; }
+  p.family = CONV_WINO;
   p.CK = 8;
   p.nCC = Cin / 8;
   p.packedFloats = (size_t)p.nNT * p.nCC * 16 * p.NT * p.CK;
@@ -452,7 +434,7 @@ static long igemm_grid(int KS, int CK, size_t lds, long total) {
 // name_out != nullptr: only report which instantiation the launch would take (profile records, bench.py's
 // dominant-kernel line: the names rocprofv3 prints), launch nothing
 template <int MF, int KS, int CK, int TAPG>
-static int launch_variant(const ConvArgs& a, hipStream_t st, char* name_out = nullptr, size_t name_cap = 0) {
+static int launch_tile(const ConvArgs& a, hipStream_t st, char* name_out = nullptr, size_t name_cap = 0) {
   constexpr int TW = 16 + KS - 1;
   constexpr size_t lds_k = (size_t)(TW * TW * (CK + 4) + TAPG * MF * (CK + 4)) * sizeof(float);
   constexpr size_t lds_e = (size_t)4 * 64 * (MF + 4) * sizeof(float);  // epilogue transpose
@@ -504,38 +486,38 @@ static int launch_variant(const ConvArgs& a, hipStream_t st, char* name_out = nu
   return DG_OK;
 }
 
-static int dispatch_variant(const ConvPlan& pl, const ConvArgs& a, hipStream_t st, char* name_out, size_t name_cap) {
-  switch (pl.variant) {
-    case 0: return launch_variant<32, 3, 16, 9>(a, st, name_out, name_cap);
-    case 1: return launch_variant<16, 3, 16, 9>(a, st, name_out, name_cap);
-    case 2: return launch_variant<32, 5, 8, 25>(a, st, name_out, name_cap);
-    case 3: return launch_variant<16, 5, 16, 25>(a, st, name_out, name_cap);
-    case 4: return launch_variant<32, 1, 32, 1>(a, st, name_out, name_cap);
-    case 5: return launch_variant<16, 1, 16, 1>(a, st, name_out, name_cap);
-    case 8: return launch_variant<32, 3, 8, 9>(a, st, name_out, name_cap);
-  }
-  dg_set_error("dg_conv_igemm: bad variant %d", pl.variant);
+static int dispatch_tile(const ConvPlan& pl, const ConvArgs& a, hipStream_t st, char* name_out, size_t name_cap) {
+  const bool wide = pl.MF == 32;
+  if (pl.family == CONV_TILE && pl.KS == 3 && !dg_plan_tile3_ck8(pl))
+    return wide ? launch_tile<32, 3, 16, 9>(a, st, name_out, name_cap) : launch_tile<16, 3, 16, 9>(a, st, name_out, name_cap);
+  if (pl.family == CONV_TILE && pl.KS == 5)
+    return wide ? launch_tile<32, 5, 8, 25>(a, st, name_out, name_cap) : launch_tile<16, 5, 16, 25>(a, st, name_out, name_cap);
+  if (pl.family == CONV_TILE && pl.KS == 1)
+    return wide ? launch_tile<32, 1, 32, 1>(a, st, name_out, name_cap) : launch_tile<16, 1, 16, 1>(a, st, name_out, name_cap);
+  if (dg_plan_tile3_ck8(pl)) return launch_tile<32, 3, 8, 9>(a, st, name_out, name_cap);
+  dg_set_error("dg_conv_igemm: no tile kernel for family %d MF=%d KS=%d CK=%d", (int)pl.family, pl.MF, pl.KS, pl.CK);
   return DG_ERR_ARG;
 }
 
 bool dg_conv_igemm_head_supported(const ConvPlan& pl, const ConvArgs& a) {
-  return (pl.variant == 8 || pl.variant == 9) && !pl.bf16 && a.Cout == 32 && a.groups <= 1 && a.ep.pool.p == nullptr && a.cpt <= 0 &&
+  return (dg_plan_tile3_ck8(pl) || dg_plan_wino(pl)) && a.Cout == 32 && a.groups <= 1 && a.ep.pool.p == nullptr && a.cpt <= 0 &&
          !a.ep.accumulate;
 }
 
 void dg_conv_igemm_name(const ConvPlan& pl, const ConvArgs& a, char* buf, size_t cap) {
   if (cap) buf[0] = 0;
-  if (pl.variant < 0) { snprintf(buf, cap, "conv_direct"); return; }
-  if (pl.bf16) { snprintf(buf, cap, pl.variant >= 200 ? "igemm_split_kernel" : "igemm_bf16_kernel"); return; }
-  if (pl.variant == 9) { snprintf(buf, cap, "%s", dg_conv_wino_name(a)); return; }
+  if (!dg_plan_mfma(pl)) { snprintf(buf, cap, "conv_direct"); return; }
+  if (dg_plan_split(pl)) { snprintf(buf, cap, "igemm_split_kernel"); return; }
+  if (dg_plan_bf16(pl)) { snprintf(buf, cap, "igemm_bf16_kernel"); return; }
+  if (dg_plan_wino(pl)) { snprintf(buf, cap, "%s", dg_conv_wino_name(a)); return; }
   if (dg_conv_igemm_wp_supported(pl, a, false)) { snprintf(buf, cap, "igemm_wp_kernel<0>"); return; }
   if (dg_conv_igemm_ws5_supported(pl, a, false)) { snprintf(buf, cap, "%s", dg_conv_igemm_ws5_name(pl)); return; }
-  dispatch_variant(pl, a, nullptr, buf, cap);
+  dispatch_tile(pl, a, nullptr, buf, cap);
 }
 
 // Argument checks shared by every MFMA launcher (the wave-private kernel is also launched directly)
 int dg_conv_igemm_check(const ConvPlan& pl, const ConvArgs& a) {
-  if (pl.variant < 0) {
+  if (!dg_plan_mfma(pl)) {
     dg_set_error("dg_conv_igemm: no MFMA variant for KS=%d Cin=%d Cout=%d", pl.KS, pl.Cin, pl.Cout);
     return DG_ERR_UNSUPPORTED;
   }
@@ -569,13 +551,12 @@ int dg_conv_igemm_check(const ConvPlan& pl, const ConvArgs& a) {
 
 static int conv_igemm_impl(const ConvPlan& pl, const ConvArgs& a_in, hipStream_t st, bool allow_wp) {
   ConvArgs a = a_in;
-  const bool is_bf16 = pl.bf16 != 0;
   DGCHECK(dg_conv_igemm_check(pl, a));
-  if (is_bf16) return dg_conv_igemm_bf16(pl, a, st);
-  if (pl.variant == 9) return dg_conv_wino(pl, a, st);   // its panel fits no other kernel
+  if (dg_plan_bf16(pl) || dg_plan_split(pl)) return dg_conv_igemm_bf16(pl, a, st);
+  if (dg_plan_wino(pl)) return dg_conv_wino(pl, a, st);   // its panel fits no other kernel
   if (allow_wp && dg_conv_igemm_wp_supported(pl, a, false)) return dg_conv_igemm_wp(pl, a, st);
   if (allow_wp && dg_conv_igemm_ws5_supported(pl, a, false)) return dg_conv_igemm_ws5(pl, a, st);
-  return dispatch_variant(pl, a, st, nullptr, 0);
+  return dispatch_tile(pl, a, st, nullptr, 0);
 }
 
 int dg_conv_igemm(const ConvPlan& pl, const ConvArgs& a, hipStream_t st) { return conv_igemm_impl(pl, a, st, true); }
@@ -585,35 +566,7 @@ int dg_conv_igemm_tile(const ConvPlan& pl, const ConvArgs& a, hipStream_t st) { 
 // ---------------------------------------------------------------------------
 // weight packing:  dst[nt][cc][tap][n][k]
 // ---------------------------------------------------------------------------
-__global__ void pack_weights_kernel(const float* __restrict__ src, float* __restrict__ dst, int ntaps, int srcI,
-                                    int srcO, int io, int transpose, int flip, const float* __restrict__ kscale,
-                                    int NT, int CK, int nCC, int Kdim, int Ndim, size_t total, int bf16, int tapg) {
-  for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
-    size_t q = i;
-    const int k = (int)(q % CK);
-    q /= CK;
-    const int n = (int)(q % NT);
-    q /= NT;
-    const int tap = (int)(q % ntaps);
-    q /= ntaps;
-    const int cc = (int)(q % nCC);
-    const int nt = (int)(q / nCC);
-    const int kk = cc * CK + k, nn = nt * NT + n;
-    float v = 0.f;
-    if (kk < Kdim && nn < Ndim) {
-      const int ci = transpose ? nn : kk;  // source I-axis index
-      const int co = transpose ? kk : nn;  // source O-axis index
-      const int ts = flip ? (ntaps - 1 - tap) : tap;
-      const size_t off = (size_t)ts * srcI * srcO + (io ? ((size_t)co * srcI + ci) : ((size_t)ci * srcO + co));
-      v = src[off];
-      if (kscale) v *= kscale[kk];
-    }
-    if (bf16 >= 2) store_split(dst, (size_t)nt * nCC * ntaps * NT * CK * bf16, cc, tap, n, k, v, bf16, tapg, ntaps, NT, CK);
-    else store_packed(dst, i, v, bf16);
-  }
-}
-
-// Batched form: every packed panel of a network in ONE launch (a refresh after an Adam step used to be ~130 launches
+// Every packed panel of a network in ONE launch (a refresh after an Adam step used to be ~130 launches
 // of a few microseconds each for the generator).  Block -> job by binary search over the jobs' first blocks.
 __global__ __launch_bounds__(256) void pack_weights_batch_kernel(const PackJob* __restrict__ jobs, int njobs) {
   int lo = 0, hi = njobs - 1;
@@ -703,16 +656,16 @@ __global__ __launch_bounds__(256) void pack_weights_batch_kernel(const PackJob* 
 int dg_pack_job(const ConvPlan& pl, const float* src, int srcI, int srcO, int io, int transpose, int flip,
                 const float* kscale, float* dst, size_t nt_stride, PackJob* job) {
   const int Kdim = transpose ? srcO : srcI, Ndim = transpose ? srcI : srcO;
-  if (Kdim != pl.Cin || Ndim != pl.Cout || pl.variant < 0 || pl.packedFloats >= (1ull << 30)) {
+  if (Kdim != pl.Cin || Ndim != pl.Cout || !dg_plan_mfma(pl) || pl.packedFloats >= (1ull << 30)) {
     dg_set_error("dg_pack_job: plan (%d->%d) does not match source roles (%d->%d)", pl.Cin, pl.Cout, Kdim, Ndim);
     return DG_ERR_ARG;
   }
   job->src = src; job->dst = dst; job->kscale = kscale;
-  job->wino = (pl.variant == 9) ? 1 : 0;
-  job->ntaps = job->wino ? 16 : pl.KS * pl.KS; job->srcI = srcI; job->srcO = srcO; job->io = io; job->transpose = transpose;
+  job->wino = dg_plan_wino(pl) ? 1 : 0;
+  job->ntaps = pl.ntaps(); job->srcI = srcI; job->srcO = srcO; job->io = io; job->transpose = transpose;
   job->flip = flip; job->NT = pl.NT; job->CK = pl.CK; job->nCC = pl.nCC; job->Kdim = Kdim; job->Ndim = Ndim;
-  job->bf16 = pl.bf16;
-  job->tapg = (pl.variant >= 200) ? (pl.KS == 5 ? 5 : pl.KS * pl.KS) : 0;
+  job->bf16 = pl.planes;
+  job->tapg = dg_plan_split(pl) ? pl.tapg() : 0;
   job->total = (unsigned)((size_t)pl.nNT * pl.nCC * job->ntaps * pl.NT * pl.CK);
   job->per_nt = (unsigned)((size_t)pl.nCC * job->ntaps * pl.NT * pl.CK);
   job->nt_stride = nt_stride ? (unsigned)nt_stride : job->per_nt;
@@ -747,23 +700,15 @@ int dg_pack_weights(const ConvPlan& pl, const float* src, int srcI, int srcO, in
     dg_set_error("dg_pack_weights: plan (%d->%d) does not match source roles (%d->%d)", pl.Cin, pl.Cout, Kdim, Ndim);
     return DG_ERR_ARG;
   }
-  if (pl.variant == 9) {   // Winograd panels exist in the batched kernel only: one job
-    PackJob job;
-    DGCHECK(dg_pack_job(pl, src, srcI, srcO, io, transpose, flip, kscale, dst, 0, &job));
-    const unsigned nb = dg_pack_layout(&job, 1);
-    PackJob* jd = nullptr;
-    HIPCHECK(hipMalloc((void**)&jd, sizeof(PackJob)));
-    hipError_t e = hipMemcpyAsync(jd, &job, sizeof(PackJob), hipMemcpyHostToDevice, st);
-    int rc = (e == hipSuccess) ? dg_pack_weights_batch(jd, 1, nb, st) : DG_ERR_HIP;
-    hipStreamSynchronize(st);   // `job` lives on this stack frame
-    hipFree(jd);
-    return rc;
-  }
-  const size_t total = (size_t)pl.nNT * pl.nCC * pl.KS * pl.KS * pl.NT * pl.CK;
-  const int blocks = (int)((total + 255) / 256 > 1024 ? 1024 : (total + 255) / 256);
-  hipLaunchKernelGGL(pack_weights_kernel, dim3(blocks), dim3(256), 0, st, src, dst, pl.KS * pl.KS, srcI, srcO, io,
-                     transpose, flip, kscale, pl.NT, pl.CK, pl.nCC, Kdim, Ndim, total, pl.bf16,
-                     (pl.variant >= 200) ? (pl.KS == 5 ? 5 : pl.KS * pl.KS) : 0);
-  HIPCHECK(hipGetLastError());
-  return DG_OK;
+  // one job of the batched kernel, the packer every context refreshes its panels with
+  PackJob job;
+  DGCHECK(dg_pack_job(pl, src, srcI, srcO, io, transpose, flip, kscale, dst, 0, &job));
+  const unsigned nb = dg_pack_layout(&job, 1);
+  PackJob* jd = nullptr;
+  HIPCHECK(hipMalloc((void**)&jd, sizeof(PackJob)));
+  hipError_t e = hipMemcpyAsync(jd, &job, sizeof(PackJob), hipMemcpyHostToDevice, st);
+  int rc = (e == hipSuccess) ? dg_pack_weights_batch(jd, 1, nb, st) : DG_ERR_HIP;
+  hipStreamSynchronize(st);   // `job` lives on this stack frame
+  hipFree(jd);
+  return rc;
 }

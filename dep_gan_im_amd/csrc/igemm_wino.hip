@@ -367,7 +367,7 @@ __global__ __launch_bounds__(256, WnCfg<MT>::WGS_PER_CU) void wino_conv_abl_kern
 }  // namespace
 
 bool dg_conv_wino_supported(const ConvPlan& pl, const ConvArgs& a) {
-  if (pl.variant != 9 || pl.bf16 || pl.KS != 3) return false;
+  if (!dg_plan_wino(pl)) return false;
   if (a.Cin != pl.Cin || (a.Cin % WN_CK) || (a.Cout % 32) || a.groups > 1 || a.dbg || ((a.H | a.W) & 1)) return false;
   if (a.cpt > 0 && ((a.Cin % (a.cpt * WN_CK)) != 0 || a.Cin / (a.cpt * WN_CK) > 4)) return false;
   return true;

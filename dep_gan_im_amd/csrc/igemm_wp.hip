@@ -31,7 +31,7 @@
 // MF = 32: two 32x32x2 tiles), its 8 x 20 halo chunk staged through registers into an unpadded wave-private region (5 KB
 // at CK = 8, 10 KB at CK = 16, the latter swizzled conflict-free).  As many waves as 160 KB admit beside the panel, 12 at
 // the most: 12 / 12 / 11 / 12 for 16->16 / 16->32 / 32->16 / 32->32 (32->16 cannot reach three waves on every SIMD at the
-// plan's 16-channel chunks: 51.2 KB + 12 x 10 KB > 160 KB).  Same panel (plans 2 and 3 of dg_plan_conv), same K order,
+// plan's 16-channel chunks: 51.2 KB + 12 x 10 KB > 160 KB).  Same panel (the 5x5 tile plans of dg_plan_conv), same K order,
 // the plan's chunk width for all four pairs, same epilogue text: bit-identical to the tile kernel
 // (tests/test_gpu_conv5_ws.py).  -Rpass-analysis=kernel-resource-usage: <32, 8> 120 VGPRs, <16, 16> 158 VGPRs, no scratch
 // (the 3x3 instantiation: 114, none).
@@ -334,7 +334,7 @@ static long wp_groups(const ConvArgs& a, int nw) { return cdiv((long)a.B * cdiv(
 // force: the shape test only (unit tests run small launches through it); otherwise also "is it worth it": enough
 // groups for a whole chip of 16-wave workgroups, and DEPGAN_IGEMM_WP=1 (opt-in: measured neutral)
 bool dg_conv_igemm_wp_supported(const ConvPlan& pl, const ConvArgs& a, bool force) {
-  if (pl.variant != 8 || pl.bf16 || pl.KS != 3 || pl.CK != 8) return false;
+  if (!dg_plan_tile3_ck8(pl)) return false;
   if (a.Cin != pl.Cin || (a.Cin % 8) || a.Cin > 64 || (a.Cout % 32) || a.groups > 1 || a.cpt > 0 || a.dbg) return false;
   if (a.ep.head_out) return false;   // the fused head lives in the tile kernel's epilogue only
   const size_t lds = ((size_t)a.Cin * 9 * 32 + (size_t)WP_NW * Wp3::WAVE_FLOATS) * sizeof(float);
@@ -401,7 +401,7 @@ int dg_conv_igemm_wp(const ConvPlan& pl, const ConvArgs& a_in, hipStream_t st) {
 }
 
 // ---------------------------------------------------------------------------
-// the weight-stationary 5x5 forms (plans 2 and 3 of dg_plan_conv, whose packed panels they read as they are)
+// the weight-stationary 5x5 forms (the 5x5 tile plans of dg_plan_conv, whose packed panels they read as they are)
 // ---------------------------------------------------------------------------
 // waves per workgroup: what 160 KB of LDS admit beside the panel, at most the instantiation's register budget
 template <int MF, int CK>
@@ -423,7 +423,7 @@ static int ws5_waves_of(const ConvPlan& pl, int Cin) { return pl.MF == 32 ? ws5_
 // force: the shape test only (the operator surface, path 9); otherwise also the measured per-shape default and the size
 // threshold, or DEPGAN_IGEMM_WS5=0|1 for all covered shapes (read once)
 bool dg_conv_igemm_ws5_supported(const ConvPlan& pl, const ConvArgs& a, bool force) {
-  if ((pl.variant != 2 && pl.variant != 3) || pl.bf16 || pl.KS != 5) return false;
+  if (!dg_plan_tile5(pl)) return false;
   if (pl.CK != (pl.MF == 32 ? 8 : 16)) return false;
   if (a.Cin != pl.Cin || a.Cout != pl.Cout || a.Cout != pl.MF || (a.Cin != 16 && a.Cin != 32)) return false;
   if (a.groups > 1 || a.cpt > 0 || a.dbg || a.ep.head_out) return false;

@@ -250,6 +250,50 @@ int dmalloc(depgan_ctx* c, float** p, size_t floats);
 int talloc(depgan_ctx* c, Tn* t, int N, int H, int W, int C);
 int conv_launch(depgan_ctx* c, const ConvPlan& pl, const ConvArgs& a, int KS);
 void zero_ep(Epilogue* e);
+// a launch description with nothing but its views and sizes: every other field zero, a null-view epilogue
+static inline ConvArgs conv_args(TView in, TView out, int B, int H, int W, int Cin, int Cout) {
+  ConvArgs a;
+  memset(&a, 0, sizeof(a));
+  zero_ep(&a.ep);
+  a.in = in;
+  a.out = out;
+  a.B = B; a.H = H; a.W = W; a.Cin = Cin; a.Cout = Cout;
+  return a;
+}
+static inline ConvArgsH conv_args_h(TViewH in, TViewH out, int B, int H, int W, int Cin, int Cout) {
+  ConvArgsH a;
+  memset(&a, 0, sizeof(a));
+  a.in = in;
+  a.out = out;
+  a.B = B; a.H = H; a.W = W; a.Cin = Cin; a.Cout = Cout;
+  return a;
+}
+// the weights of a launch of the (KS, KS, Cin, Cout) layer `raw_hwio`: the packed panel where the plan is an MFMA plan,
+// else the raw tensor behind the direct kernel's strides.  conv_set_weights in the forward roles (K = Cin, N = Cout);
+// conv_set_weights_bwd transposed and flipped (backward-data: K = Cout, N = Cin)
+static inline void conv_set_weights(ConvArgs* a, const ConvPlan& pl, const float* packed, const float* raw_hwio, int Cin,
+                                    int Cout) {
+  if (dg_plan_mfma(pl)) { a->w = packed; return; }
+  a->w = raw_hwio;
+  a->wsT = (long)Cin * Cout; a->wsI = Cout; a->wsO = 1; a->flip = 0;
+}
+static inline void conv_set_weights_bwd(ConvArgs* a, const ConvPlan& pl, const float* packed, const float* raw_hwio,
+                                        int Cin, int Cout) {
+  if (dg_plan_mfma(pl)) { a->w = packed; return; }
+  a->w = raw_hwio;
+  a->wsT = (long)Cin * Cout; a->wsI = 1; a->wsO = Cout; a->flip = 1;
+}
+static inline WgradArgs wgrad_args(TView x, TView dy, float* part, int B, int H, int W, int Cin, int Cout) {
+  WgradArgs a;
+  a.x = x;
+  a.dy = dy;
+  a.part = part;
+  a.B = B; a.H = H; a.W = W; a.Cin = Cin; a.Cout = Cout;
+  a.nTiles = a.tilesPerChunk = 0;
+  a.colpart = nullptr;
+  a.colB = 0;
+  return a;
+}
 TView view_offset(TView v, long samples);
 TView strided2(TView v, int di, int dj);   // pixel grid (2i + di, 2j + dj) of a (2H, 2W) view
 TViewH strided2_h(TViewH v, int di, int dj);
@@ -292,6 +336,19 @@ struct ColSum {
   const float* scale;
   float *out, *raw;
 };
+// the workspaces of one weight gradient are the caller's: the context's own in the model, a call's own in
+// depgan_op_conv2d_wgrad_ex
+struct WgradWs {
+  float* part;           // slabs
+  size_t partFloats;
+  float* scratch;        // partial column-sum rows ([nchunks][Cout]) or the scratch of the streaming column-sum pass
+  size_t scratchFloats;
+  bool bf16;             // contraction on the bf16 matrix pipe where wgrad_bf16.hip covers the shape
+  hipStream_t st;
+  depgan_ctx* prof;      // profile records go to this context; null: none
+};
+int wgrad_run(const WgradWs& ws, int KS, TView x, TView dy, int N, int H, int W, int Cin, int Cout, const float* scale,
+              float* out, float* raw, int accumulate, int oi, const ColSum* cs);
 int wgrad_full(depgan_ctx* c, int KS, TView x, TView dy, int N, int H, int W, int Cin, int Cout, const float* scale,
                float* out, float* raw, int accumulate, int oi, const ColSum* cs = nullptr);
 int net_adam(depgan_ctx* c, Net& n, float gscale = 1.0f);

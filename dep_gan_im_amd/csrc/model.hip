@@ -111,7 +111,7 @@ static ConvPlan plan_conv(const depgan_ctx* c, int KS, int Cin, int Cout, int N 
   // 3x3 layers the Winograd kernel covers (igemm_wino.hip: 4/9 of the MFMAs of the direct form)
   if (c->winograd && KS == 3 && H > 0 && W > 0 && !((H | W) & 1)) {
     const ConvPlan w = dg_plan_conv_wino(Cin, Cout);
-    if (w.variant == 9) return w;
+    if (dg_plan_wino(w)) return w;
   }
   return dg_plan_conv_items(KS, Cin, Cout, items);
 }
@@ -123,10 +123,11 @@ static ConvPlan plan_conv(const depgan_ctx* c, int KS, int Cin, int Cout, int N 
 int conv_launch(depgan_ctx* c, const ConvPlan& pl, const ConvArgs& a, int KS) {
   const int ng = a.groups > 1 ? a.groups : 1;
   const double fl = 2.0 * a.B * a.H * a.W * (double)a.Cin * a.Cout * KS * KS * ng;
-  char lb[56];
-  snprintf(lb, sizeof(lb), "conv%s k%d b%d %dx%d %d->%d%s",
-           pl.variant >= 200 ? (pl.bf16 == 3 ? "(bf16x6)" : "(bf16x3)") : (pl.bf16 ? "(bf16)" : ""), KS, a.B, a.H, a.W, a.Cin,
-           a.Cout, ng > 1 ? " x4" : "");
+  char lb[56], pipe[12] = "";
+  // split plans: the cross products of `planes` bf16 terms per operand that are kept (3 of 2 planes, 6 of 3)
+  if (dg_plan_split(pl)) snprintf(pipe, sizeof(pipe), "(bf16x%d)", pl.planes * (pl.planes + 1) / 2);
+  else if (dg_plan_bf16(pl)) snprintf(pipe, sizeof(pipe), "(bf16)");
+  snprintf(lb, sizeof(lb), "conv%s k%d b%d %dx%d %d->%d%s", pipe, KS, a.B, a.H, a.W, a.Cin, a.Cout, ng > 1 ? " x4" : "");
   // algorithmic bytes: every operand the epilogue names read once, every result written once, weights once
   const double px = 4.0 * a.B * a.H * a.W;
   const double by = px * a.Cin + ng * (px * a.Cout * (1 + (a.ep.res.p ? 1 : 0) + (a.ep.mask.p ? 1 : 0) +
@@ -134,7 +135,7 @@ int conv_launch(depgan_ctx* c, const ConvPlan& pl, const ConvArgs& a, int KS) {
                                                       (a.ep.pool.p ? 0.25 : 0) - (a.ep.head_skip_out ? 1 : 0)) +
                                           4.0 * KS * KS * a.Cin * a.Cout) +
                     (a.ep.head_out ? px + 4.0 * a.Cout : 0.0);
-  if (pl.variant >= 0) {
+  if (dg_plan_mfma(pl)) {
     char kn[48] = "";
     if (c->prof_on) dg_conv_igemm_name(pl, a, kn, sizeof(kn));
     ProfScope ps(c, 0, fl, lb, by, kn);
@@ -208,18 +209,13 @@ int deconv_wgrad_all(depgan_ctx* c, const GLayer& L, TView dsrc, int n, const fl
 }
 
 int deconv_bwd_data(depgan_ctx* c, GLayer& L, TView dsrc, int n) {
-  ConvArgs a;
-  memset(&a, 0, sizeof(a));
-  zero_ep(&a.ep);
-  a.out = L.din;
-  a.B = n; a.H = L.H; a.W = L.W; a.Cout = L.Cin;
+  ConvArgs a = conv_args(null_view(), L.din, n, L.H, L.W, L.Cout, L.Cin);
   a.ep.mask = L.in_mask;
   if (L.wpb_all) {
     deconv_gather_k(&a, dsrc, L.Cout, L.pb.CK);
     a.w = L.wpb_all;
     return conv_launch(c, L.pbf, a, 1);
   }
-  a.Cin = L.Cout;
   for (int t = 0; t < 4; ++t) {
     a.in = strided2(dsrc, t / 2, t % 2);
     a.w = L.wpb[t];
@@ -261,32 +257,12 @@ void deconv_gather_k(ConvArgs* a, TView d, int Cout, int CK) {
 
 // weight gradient: slabs + reduction (+ optional BN scale / raw copy / OI layout)
 // The workspaces are the caller's (WgradWs): the context's own in the model, a call's own in depgan_op_conv2d_wgrad_ex.
-struct WgradWs {
-  float* part;           // slabs
-  size_t partFloats;
-  float* scratch;        // partial column-sum rows ([nchunks][Cout]) or the scratch of the streaming column-sum pass
-  size_t scratchFloats;
-  bool bf16;             // contraction on the bf16 matrix pipe where wgrad_bf16.hip covers the shape
-  hipStream_t st;
-  depgan_ctx* prof;      // profile records go to this context; null: none
-};
-static int wgrad_run(const WgradWs& ws, int KS, TView x, TView dy, int N, int H, int W, int Cin, int Cout,
+int wgrad_run(const WgradWs& ws, int KS, TView x, TView dy, int N, int H, int W, int Cin, int Cout,
                      const float* scale, float* out, float* raw, int accumulate, int oi, const ColSum* cs) {
   depgan_ctx* c = ws.prof;
   float* const scratch = ws.scratch;
   const size_t cap = ws.scratchFloats;
-  WgradArgs a;
-  a.x = x;
-  a.dy = dy;
-  a.part = ws.part;
-  a.B = N;
-  a.H = H;
-  a.W = W;
-  a.Cin = Cin;
-  a.Cout = Cout;
-  a.nTiles = a.tilesPerChunk = 0;
-  a.colpart = nullptr;
-  a.colB = 0;
+  WgradArgs a = wgrad_args(x, dy, ws.part, N, H, W, Cin, Cout);
   int nch = 0;
   const double fl = 2.0 * N * H * W * (double)Cin * Cout * KS * KS;
   char lb[56];
@@ -524,8 +500,8 @@ static int build_generator(depgan_ctx* c) {
     if (e.kind == G_CONV) {
       L.pf = plan_conv(c, 3, L.Cin, L.Cout, 32, H, W);
       L.pb = plan_conv(c, 3, L.Cout, L.Cin, 32, H, W);
-      if (L.pf.variant >= 0) DGCHECK(dmalloc(c, &L.wpf[0], L.pf.packedFloats));
-      if (i > 0 && L.pb.variant >= 0) DGCHECK(dmalloc(c, &L.wpb[0], L.pb.packedFloats));
+      if (dg_plan_mfma(L.pf)) DGCHECK(dmalloc(c, &L.wpf[0], L.pf.packedFloats));
+      if (i > 0 && dg_plan_mfma(L.pb)) DGCHECK(dmalloc(c, &L.wpb[0], L.pb.packedFloats));
       const bool skip = (i + 1 < kNTrunk && kTrunk[i + 1].kind == G_POOL);
       if (skip) {
         Cat& ct = cats[kTrunk[i + 1].name];
@@ -583,7 +559,7 @@ static int build_generator(depgan_ctx* c) {
         DGCHECK(dmalloc(c, &L.wpb[t], L.pb.packedFloats));
       }
       L.pbf = plan_conv(c, 1, 4 * L.Cout, L.Cin);
-      if (L.pb.variant >= 0 && L.pbf.variant == L.pb.variant && L.pbf.bf16 == L.pb.bf16 && (L.Cout % L.pb.CK) == 0 &&
+      if (dg_plan_mfma(L.pb) && L.pbf.family == L.pb.family && L.pbf.planes == L.pb.planes && (L.Cout % L.pb.CK) == 0 &&
           L.pbf.packedFloats == 4 * L.pb.packedFloats)
         DGCHECK(dmalloc(c, &L.wpb_all, L.pbf.packedFloats));
       Cat& ct = cats[e.aux];
@@ -675,8 +651,8 @@ static int build_critics(depgan_ctx* c) {
       D.W[l] = n.p(nm + "/kernel"); D.b[l] = n.p(nm + "/bias");
       D.dW[l] = n.g(nm + "/kernel"); D.db[l] = n.g(nm + "/bias");
       D.wpf[l] = D.wpb[l] = nullptr;
-      if (c->dl[l].pf.variant >= 0) DGCHECK(dmalloc(c, &D.wpf[l], c->dl[l].pf.packedFloats));
-      if (c->dl[l].pb.variant >= 0) DGCHECK(dmalloc(c, &D.wpb[l], c->dl[l].pb.packedFloats));
+      if (dg_plan_mfma(c->dl[l].pf)) DGCHECK(dmalloc(c, &D.wpf[l], c->dl[l].pf.packedFloats));
+      if (dg_plan_mfma(c->dl[l].pb)) DGCHECK(dmalloc(c, &D.wpb[l], c->dl[l].pb.packedFloats));
     }
     D.w9 = n.p("dis_9/kernel"); D.b9 = n.p("dis_9/bias"); D.wd = n.p("dense_1/kernel"); D.bd = n.p("dense_1/bias");
     D.dw9 = n.g("dis_9/kernel"); D.db9 = n.g("dis_9/bias"); D.dwd = n.g("dense_1/kernel"); D.dbd = n.g("dense_1/bias");
@@ -810,12 +786,8 @@ int g_forward(depgan_ctx* c, const float* x, const float* z, int n, bool store_u
   for (size_t i = 0; i < c->gl.size(); ++i) {
     GLayer& L = c->gl[i];
     if (L.kind == G_CONV || L.kind == G_FILM) {
-      ConvArgs a;
-      memset(&a, 0, sizeof(a));
-      zero_ep(&a.ep);
-      a.in = (i == 0) ? make_view(const_cast<float*>(x), L.H, L.W, L.Cin) : L.in;
-      a.out = L.out;
-      a.B = n; a.H = L.H; a.W = L.W; a.Cin = L.Cin; a.Cout = L.Cout;
+      ConvArgs a = conv_args((i == 0) ? make_view(const_cast<float*>(x), L.H, L.W, L.Cin) : L.in, L.out,
+                             n, L.H, L.W, L.Cin, L.Cout);
       a.ep.bias = L.b; a.ep.scale = L.s; a.ep.shift = L.t; a.ep.relu = 1;
       if (L.kind == G_FILM) {
         a.ep.film_mul = c->na.heads + L.col_mul;
@@ -824,15 +796,12 @@ int g_forward(depgan_ctx* c, const float* x, const float* z, int n, bool store_u
         a.ep.res = L.in;
         if (store_u) a.ep.out_pre = L.u.view();
       }
-      if (L.pf.variant >= 0) {
-        a.w = L.wpf[0];
+      conv_set_weights(&a, L.pf, L.wpf[0], L.Wt, L.Cin, L.Cout);
+      if (dg_plan_mfma(L.pf)) {
         // the 2x2 max-pool that follows (gen_1 / gen_3 / gen_5, GT:409/422/435) rides in this launch's epilogue
         if (i + 1 < c->gl.size() && c->gl[i + 1].kind == G_POOL && c->gl[i + 1].skip_of == (int)i &&
             !((L.H | L.W) & 1))
           a.ep.pool = c->gl[i + 1].out;
-      } else {
-        a.w = L.Wt;
-        a.wsT = (long)L.Cin * L.Cout; a.wsI = L.Cout; a.wsO = 1; a.flip = 0;
       }
       pooled_by_conv = a.ep.pool.p != nullptr;
       // gen_segmentation (1x1 to one channel, tanh: GT:494-495) rides in gen_17's epilogue where the layer runs on the
@@ -858,12 +827,7 @@ int g_forward(depgan_ctx* c, const float* x, const float* z, int n, bool store_u
         DGCHECK(deconv_fwd_launch(c, L, L.out, L.b, L.s, L.t, 1, n));
         continue;
       }
-      ConvArgs a;
-      memset(&a, 0, sizeof(a));
-      zero_ep(&a.ep);
-      a.in = L.in;
-      a.out = strided2(L.out, 0, 0);
-      a.B = n; a.H = L.H; a.W = L.W; a.Cin = L.Cin; a.Cout = L.Cout;
+      ConvArgs a = conv_args(L.in, strided2(L.out, 0, 0), n, L.H, L.W, L.Cin, L.Cout);
       a.ep.bias = L.b; a.ep.scale = L.s; a.ep.shift = L.t; a.ep.relu = 1;
       a.groups = 4;
       for (int t = 0; t < 4; ++t) {
@@ -889,13 +853,8 @@ static int g_conv_bn_bwd(depgan_ctx* c, GLayer& L, size_t li, const float* x_use
   // the un-scaled gradient stays in the layer's slot of raw_all: g_backward forms every BN gamma gradient at its end
   DGCHECK(wgrad_full(c, 3, xin, dy, n, L.H, L.W, L.Cin, L.Cout, L.s, L.dW, c->raw_all + (L.dW - c->g.G), 0, 0, &cs));
   if (li == 0) return DG_OK;
-  ConvArgs a;
-  memset(&a, 0, sizeof(a));
-  zero_ep(&a.ep);
-  a.in = dy;
-  a.out = L.din;
+  ConvArgs a = conv_args(dy, L.din, n, L.H, L.W, L.Cout, L.Cin);
   a.w = L.wpb[0];
-  a.B = n; a.H = L.H; a.W = L.W; a.Cin = L.Cout; a.Cout = L.Cin;
   a.ep.res = res;
   a.ep.mask = L.in_mask;
   return conv_launch(c, L.pb, a, 3);
@@ -972,21 +931,13 @@ static int d_forward(depgan_ctx* c, DNet& D, const float* img, long s0, int N) {
   const int H0 = c->cfg.height, W0 = c->cfg.width;
   for (int l = 0; l < 11; ++l) {
     const DLayer& L = c->dl[l];
-    ConvArgs a;
-    memset(&a, 0, sizeof(a));
-    zero_ep(&a.ep);
-    a.in = (l == 0) ? make_view(const_cast<float*>(img), H0, W0, 1) : d_in_view(c, l, s0);
-    a.out = view_offset(c->d_act[l].view(), s0);
-    a.B = N; a.H = L.H; a.W = L.W; a.Cin = L.Cin; a.Cout = L.Cout;
+    ConvArgs a = conv_args((l == 0) ? make_view(const_cast<float*>(img), H0, W0, 1) : d_in_view(c, l, s0),
+                           view_offset(c->d_act[l].view(), s0), N, L.H, L.W, L.Cin, L.Cout);
     a.ep.bias = D.b[l];
     a.ep.relu = 1;
-    if (L.pf.variant >= 0) {
-      a.w = D.wpf[l];
-      if (L.pool && !((L.H | L.W) & 1)) a.ep.pool = view_offset(c->d_pool[l].view(), s0);   // pooled in the epilogue
-    } else {
-      a.w = D.W[l];
-      a.wsT = (long)L.Cin * L.Cout; a.wsI = L.Cout; a.wsO = 1; a.flip = 0;
-    }
+    conv_set_weights(&a, L.pf, D.wpf[l], D.W[l], L.Cin, L.Cout);
+    if (dg_plan_mfma(L.pf) && L.pool && !((L.H | L.W) & 1))
+      a.ep.pool = view_offset(c->d_pool[l].view(), s0);   // pooled in the epilogue
     DGCHECK(conv_launch(c, L.pf, a, L.KS));
     if (L.pool && !a.ep.pool.p) {
       ProfScope ps(c, 2, 0.0, "maxpool");
@@ -1014,12 +965,8 @@ static int d_backward_chain(depgan_ctx* c, DNet& D, long s0, int N, const float*
   for (int l = 10; l >= 1; --l) {
     const DLayer& L = c->dl[l];
     const DLayer& Pv = c->dl[l - 1];
-    ConvArgs a;
-    memset(&a, 0, sizeof(a));
-    zero_ep(&a.ep);
-    a.in = view_offset(c->d_dz[l].view(), s0);
+    ConvArgs a = conv_args(view_offset(c->d_dz[l].view(), s0), null_view(), N, L.H, L.W, L.Cout, L.Cin);
     a.w = D.wpb[l];
-    a.B = N; a.H = L.H; a.W = L.W; a.Cin = L.Cout; a.Cout = L.Cin;
     if (Pv.pool) {
       a.out = view_offset(c->d_dpool[l - 1].view(), s0);
     } else {
@@ -1035,18 +982,11 @@ static int d_backward_chain(depgan_ctx* c, DNet& D, long s0, int N, const float*
   }
   if (img_n > 0) {
     const DLayer& L = c->dl[0];
-    ConvArgs a;
-    memset(&a, 0, sizeof(a));
-    zero_ep(&a.ep);
-    a.in = view_offset(c->d_dz[0].view(), s0 + img_s0);
-    a.out = make_view(g0_out, L.H, L.W, 1);
-    a.B = img_n; a.H = L.H; a.W = L.W; a.Cin = L.Cout; a.Cout = 1;
+    ConvArgs a = conv_args(view_offset(c->d_dz[0].view(), s0 + img_s0), make_view(g0_out, L.H, L.W, 1),
+                           img_n, L.H, L.W, L.Cout, 1);
     // transposed + flipped access of the HWIO kernel (Cin_f = 1): w(tap', k = co_f, n = 0)
-    a.w = D.W[0];
-    a.wsT = (long)L.Cin * L.Cout; a.wsI = 1; a.wsO = L.Cout; a.flip = 1;
-    ConvPlan none = {};
-    none.variant = -1;
-    DGCHECK(conv_launch(c, none, a, L.KS));
+    conv_set_weights_bwd(&a, dg_plan_direct(), nullptr, D.W[0], L.Cin, L.Cout);
+    DGCHECK(conv_launch(c, dg_plan_direct(), a, L.KS));
   }
   return DG_OK;
 }
@@ -1096,23 +1036,12 @@ static int critic_enqueue(depgan_ctx* c, int which, const float* y2, const float
   // u-forward through the masks of the mixed pass, overwriting the mixed slots
   for (int l = 0; l < 11; ++l) {
     const DLayer& L = c->dl[l];
-    ConvArgs a;
-    memset(&a, 0, sizeof(a));
-    zero_ep(&a.ep);
-    a.in = (l == 0) ? make_view(u0, H0, W0, 1) : d_in_view(c, l, 2 * B);
     TView act = view_offset(c->d_act[l].view(), 2 * B);
-    a.out = L.pool ? c->d_ufull.view() : act;
-    if (L.pool) {  // scratch has 16 channels at full size; re-view it for this layer's shape
-      a.out = make_view(c->d_ufull.p, L.H, L.W, L.Cout);
-    }
+    // pooled layers write the scratch (16 channels at full size), re-viewed for this layer's shape
+    ConvArgs a = conv_args((l == 0) ? make_view(u0, H0, W0, 1) : d_in_view(c, l, 2 * B),
+                           L.pool ? make_view(c->d_ufull.p, L.H, L.W, L.Cout) : act, B, L.H, L.W, L.Cin, L.Cout);
     a.ep.mask = act;
-    a.B = B; a.H = L.H; a.W = L.W; a.Cin = L.Cin; a.Cout = L.Cout;
-    if (L.pf.variant >= 0) {
-      a.w = D.wpf[l];
-    } else {
-      a.w = D.W[l];
-      a.wsT = (long)L.Cin * L.Cout; a.wsI = L.Cout; a.wsO = 1; a.flip = 0;
-    }
+    conv_set_weights(&a, L.pf, D.wpf[l], D.W[l], L.Cin, L.Cout);
     DGCHECK(conv_launch(c, L.pf, a, L.KS));
     if (L.pool) {
       ProfScope ps(c, 2, 0.0, "gather pool");
@@ -1852,813 +1781,6 @@ int depgan_debug_tensor(depgan_ctx* c, const char* name, float* host, long cap, 
   hipFree(tmp);
   if (e != hipSuccess) { dg_set_error("debug_tensor: copy of %s failed: %s", name, hipGetErrorString(e)); return DG_ERR_HIP; }
   return DG_OK;
-}
-
-// ---- single operators (unit tests) ----
-// a: views, sizes and epilogue of the launch (bwd: Cin / Cout already in their launch roles); w_hwio (KS, KS, Cin, Cout)
-// of the layer.  Plans, packs and launches on the kernel `path` names; what that kernel does not cover is an error.
-static int op_conv_run(ConvArgs a, const float* w_hwio, int Cin, int Cout, int KS, int path, int bwd, hipStream_t st) {
-  const int ci = a.Cin, co = a.Cout;
-  ConvPlan pl = (path == 3) ? dg_plan_conv_bf16(KS, ci, co)
-                : (path == 4 || path == 5) ? dg_plan_conv_split(KS, ci, co, path == 5 ? 3 : 2)
-                : (path == 6) ? dg_plan_conv_items(KS, ci, co, 1L << 30) : dg_plan_conv(KS, ci, co);
-  if (path == 7) pl = dg_plan_conv_items(KS, ci, co, 1L << 30);
-  if (path == 8) {
-    pl = (KS == 3) ? dg_plan_conv_wino(ci, co) : pl;
-    if (pl.variant != 9 || !dg_conv_wino_supported(pl, a)) { dg_set_error("op_conv: the Winograd kernel does not cover this shape"); return DG_ERR_UNSUPPORTED; }
-  }
-  if ((path == 6 || path == 7) && pl.CK != 8) { dg_set_error("op_conv: the 8-channel-chunk variant does not cover this shape"); return DG_ERR_UNSUPPORTED; }
-  if (path >= 3 && path <= 5 && !pl.bf16) { dg_set_error("op_conv: the bf16 MFMA kernel does not cover this shape"); return DG_ERR_UNSUPPORTED; }
-  // path 9 names a 5x5 kernel: another KS is a bad argument (status 1, as for a path number that does not exist), what
-  // the 5x5 kernel does not cover is status 3
-  if (path == 9 && KS != 5) { dg_set_error("op_conv: path 9 is the weight-stationary 5x5 kernel, KS must be 5"); return DG_ERR_ARG; }
-  if (path == 9 && !dg_conv_igemm_ws5_supported(pl, a, true)) { dg_set_error("op_conv: the weight-stationary 5x5 kernel does not cover this shape"); return DG_ERR_UNSUPPORTED; }
-  if (path == 1 && pl.variant < 0) { dg_set_error("op_conv: MFMA path not available for this shape"); return DG_ERR_UNSUPPORTED; }
-  if (path != 2 && pl.variant >= 0) {
-    float* wp = nullptr;
-    HIPCHECK(hipMalloc((void**)&wp, pl.packedFloats * sizeof(float)));
-    int rc = dg_pack_weights(pl, w_hwio, Cin, Cout, 0, bwd, bwd, nullptr, wp, st);
-    if (rc == DG_OK) {
-      a.w = wp;
-      if (path == 7) {
-        if (dg_conv_igemm_wp_supported(pl, a, true)) rc = dg_conv_igemm_wp(pl, a, st);
-        else { dg_set_error("op_conv: the wave-private kernel does not cover this shape"); rc = DG_ERR_UNSUPPORTED; }
-      } else if (path == 9) {
-        rc = dg_conv_igemm_ws5(pl, a, st);
-      } else if (path == 6 || path == 1) {
-        // the workgroup-tile kernel itself (the reference the wave-private kernel must match bit for bit)
-        rc = dg_conv_igemm_tile(pl, a, st);
-      } else {
-        rc = dg_conv_igemm(pl, a, st);
-      }
-    }
-    hipStreamSynchronize(st);
-    hipFree(wp);
-    return rc;
-  }
-  a.w = w_hwio;
-  if (!bwd) {
-    a.wsT = (long)Cin * Cout; a.wsI = Cout; a.wsO = 1; a.flip = 0;
-  } else {
-    a.wsT = (long)Cin * Cout; a.wsI = 1; a.wsO = Cout; a.flip = 1;
-  }
-  return dg_conv_direct(KS, a, st);
-}
-
-static int op_conv(const float* in, const float* w_hwio, const float* bias, float* out, int B, int H, int W, int Cin,
-                   int Cout, int KS, int relu, int path, int bwd, hipStream_t st) {
-  // bwd: compute dx = conv_bwd_data(dy=in (Cout ch), W) -> out (Cin ch)
-  const int ci = bwd ? Cout : Cin, co = bwd ? Cin : Cout;
-  ConvArgs a;
-  memset(&a, 0, sizeof(a));
-  zero_ep(&a.ep);
-  a.in = make_view(const_cast<float*>(in), H, W, ci);
-  a.out = make_view(out, H, W, co);
-  a.B = B; a.H = H; a.W = W; a.Cin = ci; a.Cout = co;
-  a.ep.bias = bias;
-  a.ep.relu = relu;
-  return op_conv_run(a, w_hwio, Cin, Cout, KS, path, bwd, st);
-}
-
-// diagnostics: run the MFMA conv with per-workgroup phase stamps (16 x u64 per workgroup) into `stamps`
-int depgan_op_conv2d_stamps(const float* in, const float* w_hwio, float* out, int B, int H, int W, int Cin, int Cout,
-                            int KS, unsigned long long* stamps, int reps, void* stream) {
-  hipStream_t st = (hipStream_t)stream;
-  ConvArgs a;
-  memset(&a, 0, sizeof(a));
-  zero_ep(&a.ep);
-  a.in = make_view(const_cast<float*>(in), H, W, Cin);
-  a.out = make_view(out, H, W, Cout);
-  a.B = B; a.H = H; a.W = W; a.Cin = Cin; a.Cout = Cout;
-  a.ep.relu = 1;
-  ConvPlan pl = dg_plan_conv(KS, Cin, Cout);
-  if (pl.variant < 0) { dg_set_error("no MFMA variant"); return DG_ERR_UNSUPPORTED; }
-  float* wp = nullptr;
-  HIPCHECK(hipMalloc((void**)&wp, pl.packedFloats * sizeof(float)));
-  int rc = dg_pack_weights(pl, w_hwio, Cin, Cout, 0, 0, 0, nullptr, wp, st);
-  a.w = wp;
-  for (int i = 0; i < reps && rc == DG_OK; ++i) {
-    a.dbg = (i == reps - 1) ? stamps : nullptr;
-    rc = dg_conv_igemm(pl, a, st);
-  }
-  hipStreamSynchronize(st);
-  hipFree(wp);
-  return rc;
-}
-
-int depgan_op_conv2d(const float* in, const float* w_hwio, const float* bias, float* out, int B, int H, int W,
-                     int Cin, int Cout, int KS, int relu, int path, void* stream) {
-  return op_conv(in, w_hwio, bias, out, B, H, W, Cin, Cout, KS, relu, path, 0, (hipStream_t)stream);
-}
-int depgan_op_conv2d_bwd_data(const float* dy, const float* w_hwio, float* dx, int B, int H, int W, int Cin,
-                              int Cout, int KS, int path, void* stream) {
-  return op_conv(dy, w_hwio, nullptr, dx, B, H, W, Cin, Cout, KS, 0, path, 1, (hipStream_t)stream);
-}
-int depgan_op_conv2d_wgrad(const float* x, const float* dy, float* dw, int B, int H, int W, int Cin, int Cout, int KS,
-                           void* stream) {
-  hipStream_t st = (hipStream_t)stream;
-  const bool big = (Cin % 4 == 0 && Cout % 4 == 0 && Cin >= 8);
-  const size_t pf = big ? dg_wgrad_part_floats(KS, B, H, W, Cin, Cout) : dg_wgrad_small_part_floats(KS, B, H, W, Cin, Cout);
-  float* part = nullptr;
-  HIPCHECK(hipMalloc((void**)&part, pf * sizeof(float)));
-  WgradArgs a;
-  a.x = make_view(const_cast<float*>(x), H, W, Cin);
-  a.dy = make_view(const_cast<float*>(dy), H, W, Cout);
-  a.part = part;
-  a.B = B; a.H = H; a.W = W; a.Cin = Cin; a.Cout = Cout;
-  a.nTiles = a.tilesPerChunk = 0;
-  a.colpart = nullptr;
-  a.colB = 0;
-  int nch = 0;
-  int rc = big ? dg_wgrad(KS, a, &nch, st) : dg_wgrad_small(KS, a, &nch, st);
-  if (rc == DG_OK) rc = dg_wgrad_reduce(part, nch, KS * KS, Cin, Cout, nullptr, dw, nullptr, 0, 0, st);
-  hipStreamSynchronize(st);
-  hipFree(part);
-  return rc;
-}
-int depgan_op_conv2d_wgrad_bf16(const float* x, const float* dy, float* dw, int B, int H, int W, int Cin, int Cout,
-                                int KS, void* stream) {
-  hipStream_t st = (hipStream_t)stream;
-  if (!dg_wgrad_bf16_supported(KS, Cin, Cout)) { dg_set_error("op_wgrad_bf16: shape not covered"); return DG_ERR_UNSUPPORTED; }
-  const size_t pf = dg_wgrad_bf16_part_floats(KS, B, H, W, Cin, Cout);
-  float* part = nullptr;
-  HIPCHECK(hipMalloc((void**)&part, pf * sizeof(float)));
-  WgradArgs a;
-  a.x = make_view(const_cast<float*>(x), H, W, Cin);
-  a.dy = make_view(const_cast<float*>(dy), H, W, Cout);
-  a.part = part;
-  a.B = B; a.H = H; a.W = W; a.Cin = Cin; a.Cout = Cout;
-  a.nTiles = a.tilesPerChunk = 0;
-  a.colpart = nullptr;
-  a.colB = 0;
-  int nch = 0;
-  int rc = dg_wgrad_bf16(KS, a, &nch, st);
-  if (rc == DG_OK) rc = dg_wgrad_reduce(part, nch, KS * KS, Cin, Cout, nullptr, dw, nullptr, 0, 0, st);
-  hipStreamSynchronize(st);
-  hipFree(part);
-  return rc;
-}
-int depgan_op_deconv2x2(const float* in, const float* w_hwoi, const float* bias, const float* scale,
-                        const float* shift, float* out, int B, int H, int W, int Cin, int Cout, int relu,
-                        void* stream) {
-  if (!in || !w_hwoi || !out || B < 1 || H < 1 || W < 1) { dg_set_error("op_deconv2x2: bad argument"); return DG_ERR_ARG; }
-  DeconvArgs d;
-  memset(&d, 0, sizeof(d));
-  d.in = in;
-  d.w = w_hwoi;
-  d.out = make_view(out, 2 * H, 2 * W, Cout);
-  d.bias = bias; d.scale = scale; d.shift = shift; d.relu = relu;
-  d.H = H; d.W = W; d.Cin = Cin; d.Cout = Cout;
-  return dg_deconv_fwd(d, B, (hipStream_t)stream);
-}
-int depgan_op_deconv2x2_wgrad(const float* in, const float* dout, float* dw_hwoi, float* colsum, int B, int H, int W,
-                              int Cin, int Cout, void* stream) {
-  if (!in || !dout || !dw_hwoi || B < 1 || H < 1 || W < 1) { dg_set_error("op_deconv2x2_wgrad: bad argument"); return DG_ERR_ARG; }
-  hipStream_t st = (hipStream_t)stream;
-  DeconvWgradArgs d;
-  memset(&d, 0, sizeof(d));
-  d.in = in;
-  d.dout = make_view(const_cast<float*>(dout), 2 * H, 2 * W, Cout);
-  d.H = H; d.W = W; d.Cin = Cin; d.Cout = Cout;
-  if (!dg_deconv_wgrad_supported(B, H, W, Cin, Cout, make_view(const_cast<float*>(in), H, W, Cin), d.dout)) {
-    dg_set_error("op_deconv2x2_wgrad: shape %dx%dx%d %d->%d not covered by the fused kernel", B, H, W, Cin, Cout);
-    return DG_ERR_UNSUPPORTED;
-  }
-  const size_t pf = dg_deconv_wgrad_part_floats(B, H, W, Cin, Cout);
-  float *part = nullptr, *col = nullptr;
-  HIPCHECK(hipMalloc((void**)&part, pf * sizeof(float)));
-  if (hipMalloc((void**)&col, (pf / ((size_t)Cin * Cout)) * Cout * sizeof(float)) != hipSuccess) {
-    hipFree(part);
-    dg_set_error("op_deconv2x2_wgrad: out of memory");
-    return DG_ERR_HIP;
-  }
-  d.part = part;
-  d.colpart = colsum ? col : nullptr;
-  int nch = 0;
-  int rc = dg_deconv_wgrad(d, B, &nch, st);
-  if (rc == DG_OK)
-    rc = dg_wgrad_finish_rows(part, nch, 4, Cin, Cout, nullptr, dw_hwoi, nullptr, 0, 1, colsum ? col : nullptr, 4 * nch,
-                              Cout, nullptr, colsum, nullptr, st);
-  hipStreamSynchronize(st);
-  hipFree(part);
-  hipFree(col);
-  return rc;
-}
-int depgan_op_maxpool(const float* in, float* out, int B, int Ho, int Wo, int C, void* stream) {
-  return dg_maxpool(make_view(const_cast<float*>(in), 2 * Ho, 2 * Wo, C), make_view(out, Ho, Wo, C), B, Ho, Wo, C,
-                    (hipStream_t)stream);
-}
-
-// ---- evaluation step after the path (GE:616-807): stateless, caller's stream ----
-int depgan_eval_accumulate(const float* pred, const float* mask, double* acc, long n, void* stream) {
-  if (!pred || !acc || n < 0) { dg_set_error("eval_accumulate: null argument"); return DG_ERR_ARG; }
-  return dg_eval_accumulate(pred, mask, acc, (size_t)n, (hipStream_t)stream);
-}
-int depgan_eval_divide(double* acc, long n, double divisor, void* stream) {
-  if (!acc || n < 0) { dg_set_error("eval_divide: null argument"); return DG_ERR_ARG; }
-  return dg_eval_divide(acc, (size_t)n, divisor, (hipStream_t)stream);
-}
-int depgan_eval_counts(const float* x, int nicg, const double* pred, const float* code_real, const float* mask1,
-                       const float* wmh1, const float* mask2, const float* wmh2, const float* prob2, long npix,
-                       double thr, long long out_host[DEPGAN_EVAL_NCOUNT], void* stream) {
-  if (!x || !pred || !out_host || nicg < 1 || npix < 0) { dg_set_error("eval_counts: bad argument"); return DG_ERR_ARG; }
-  hipStream_t st = (hipStream_t)stream;
-  unsigned long long* dev = nullptr;
-  HIPCHECK(hipMalloc((void**)&dev, DEPGAN_EVAL_NCOUNT * sizeof(unsigned long long)));
-  int rc = dg_eval_counts(x, nicg, pred, code_real, mask1, wmh1, mask2, wmh2, prob2, (size_t)npix, thr, dev, st);
-  if (rc == DG_OK) {
-    unsigned long long h[DEPGAN_EVAL_NCOUNT];
-    if (hipMemcpyAsync(h, dev, sizeof(h), hipMemcpyDeviceToHost, st) != hipSuccess ||
-        hipStreamSynchronize(st) != hipSuccess) {
-      dg_set_error("eval_counts: copy back failed");
-      rc = DG_ERR_HIP;
-    } else {
-      for (int k = 0; k < DEPGAN_EVAL_NCOUNT; ++k) out_host[k] = (long long)h[k];
-    }
-  }
-  hipFree(dev);
-  return rc;
-}
-
-
-// ---- learning-phase-1 operators (train_ops.hip), as uresnet.hip calls them; each view is NHWC with the strides
-// (sB, sY, sX) in floats and channel stride 1 ----
-static int op_alloc(float** p, size_t floats, const char* who) {
-  if (hipMalloc((void**)p, (floats ? floats : 1) * sizeof(float)) != hipSuccess) {
-    dg_set_error("%s: out of device memory (%zu floats)", who, floats);
-    return DG_ERR_HIP;
-  }
-  return DG_OK;
-}
-static size_t op_scratch(long scratch_floats, size_t need) { return scratch_floats > 0 ? (size_t)scratch_floats : need; }
-
-// ---- the fp32 convolution kernels with the whole fused epilogue and strided views (unit tests) ----
-static bool op_view_bad(const float* p, long sB, long sY, long sX) { return !p || sB < 1 || sY < 1 || sX < 1; }
-
-int depgan_op_conv2d_fused(const float* in, long isB, long isY, long isX, const float* w_hwio, const float* bias,
-                           const float* scale, const float* shift, const float* film_mul, const float* film_add,
-                           int film_ld, float* out, long osB, long osY, long osX, float* out_pre, long psB, long psY,
-                           long psX, const float* res, long rsB, long rsY, long rsX, const float* mask, long msB,
-                           long msY, long msX, float* pool, long qsB, long qsY, long qsX, const float* head_w,
-                           const float* head_b, float* head_out, int head_tanh, int head_skip_out, int B, int H, int W,
-                           int Cin, int Cout, int KS, int relu, int accumulate, int path, int bwd, void* stream) {
-  if (op_view_bad(in, isB, isY, isX) || op_view_bad(out, osB, osY, osX) || !w_hwio || B < 1 || H < 1 || W < 1 || Cin < 1 ||
-      Cout < 1 || (KS != 1 && KS != 3 && KS != 5) || (out_pre && op_view_bad(out_pre, psB, psY, psX)) ||
-      (res && op_view_bad(res, rsB, rsY, rsX)) || (mask && op_view_bad(mask, msB, msY, msX)) ||
-      (pool && op_view_bad(pool, qsB, qsY, qsX))) {
-    dg_set_error("op_conv2d_fused: null or non-positive argument");
-    return DG_ERR_ARG;
-  }
-  const int co = bwd ? Cin : Cout;
-  if (!scale != !shift || !film_mul != !film_add || (film_mul && film_ld < co)) {
-    dg_set_error("op_conv2d_fused: scale / shift and film_mul / film_add come in pairs, film_ld >= output channels");
-    return DG_ERR_ARG;
-  }
-  if ((head_w || head_b || head_out) && !(head_w && head_b && head_out)) { dg_set_error("op_conv2d_fused: null head argument"); return DG_ERR_ARG; }
-  if (head_skip_out && !head_out) { dg_set_error("op_conv2d_fused: head_skip_out without a head"); return DG_ERR_ARG; }
-  if (path < 1 || path > 9) { dg_set_error("op_conv2d_fused: path must be 1 ... 9"); return DG_ERR_ARG; }
-  ConvArgs a;
-  memset(&a, 0, sizeof(a));
-  zero_ep(&a.ep);
-  a.in = op_view(in, isB, isY, isX);
-  a.out = op_view(out, osB, osY, osX);
-  a.B = B; a.H = H; a.W = W; a.Cin = bwd ? Cout : Cin; a.Cout = co;
-  Epilogue& e = a.ep;
-  e.bias = bias; e.scale = scale; e.shift = shift;
-  e.film_mul = film_mul; e.film_add = film_add; e.film_ld = film_ld;
-  e.out_pre = op_view_or_null(out_pre, psB, psY, psX);
-  e.res = op_view_or_null(res, rsB, rsY, rsX);
-  e.mask = op_view_or_null(mask, msB, msY, msX);
-  e.pool = op_view_or_null(pool, qsB, qsY, qsX);
-  e.relu = relu; e.accumulate = accumulate;
-  e.head_w = head_w; e.head_b = head_b; e.head_out = head_out;
-  e.head_tanh = head_tanh; e.head_skip_out = head_skip_out;
-  return op_conv_run(a, w_hwio, Cin, Cout, KS, path, bwd ? 1 : 0, (hipStream_t)stream);
-}
-
-// upload and run pack jobs whose destinations interleave (GLayer::wpb_all); synchronises: `jobs` is the caller's
-static int op_pack_jobs(PackJob* jobs, int n, hipStream_t st) {
-  const unsigned nb = dg_pack_layout(jobs, n);
-  PackJob* jd = nullptr;
-  HIPCHECK(hipMalloc((void**)&jd, n * sizeof(PackJob)));
-  hipError_t e = hipMemcpyAsync(jd, jobs, n * sizeof(PackJob), hipMemcpyHostToDevice, st);
-  int rc = DG_OK;
-  if (e != hipSuccess) { dg_set_error("op_pack_jobs: upload failed: %s", hipGetErrorString(e)); rc = DG_ERR_HIP; }
-  if (rc == DG_OK) rc = dg_pack_weights_batch(jd, n, nb, st);
-  hipStreamSynchronize(st);
-  hipFree(jd);
-  return rc;
-}
-
-int depgan_op_deconv2x2_igemm(int form, const float* in, long isB, long isY, long isX, const float* w_hwoi,
-                              const float* bias, const float* scale, const float* shift, float* out, long osB, long osY,
-                              long osX, const float* mask, long msB, long msY, long msX, int B, int H, int W, int Cin,
-                              int Cout, int relu, int path, void* stream) {
-  if (op_view_bad(in, isB, isY, isX) || op_view_bad(out, osB, osY, osX) || !w_hwoi || B < 1 || H < 1 || W < 1 || Cin < 1 ||
-      Cout < 1 || (mask && op_view_bad(mask, msB, msY, msX))) {
-    dg_set_error("op_deconv2x2_igemm: null or non-positive argument");
-    return DG_ERR_ARG;
-  }
-  if (form < 0 || form > 2 || !scale != !shift || (path != 1 && path != 3 && path != 8)) {
-    dg_set_error("op_deconv2x2_igemm: form must be 0, 1 or 2, path 1, 3 or 8, scale and shift come as a pair");
-    return DG_ERR_ARG;
-  }
-  if (form == 0 ? mask != nullptr : (bias || scale || relu)) {
-    dg_set_error("op_deconv2x2_igemm: the forward takes bias / scale / shift / relu, the backward-data forms a mask");
-    return DG_ERR_ARG;
-  }
-  if (path == 8) { dg_set_error("op_deconv2x2_igemm: the Winograd kernel has no 1x1 form"); return DG_ERR_UNSUPPORTED; }
-  auto plan = [&](int ci, int co) { return path == 3 ? dg_plan_conv_bf16(1, ci, co) : dg_plan_conv(1, ci, co); };
-  auto covered = [&](const ConvPlan& p) { return p.variant >= 0 && (path == 3) == (p.bf16 != 0); };
-  hipStream_t st = (hipStream_t)stream;
-  ConvArgs a;
-  memset(&a, 0, sizeof(a));
-  zero_ep(&a.ep);
-  a.B = B; a.H = H; a.W = W;
-  float* wp = nullptr;
-  int rc = DG_OK;
-  if (form == 0) {
-    // as g_forward: four 1x1 convolutions of one input, tap (di, dj) writing the pixel grid (2i+di, 2j+dj), one launch
-    const ConvPlan pf = plan(Cin, Cout);
-    if (!covered(pf)) { dg_set_error("op_deconv2x2_igemm: no MFMA plan for %d -> %d on path %d", Cin, Cout, path); return DG_ERR_UNSUPPORTED; }
-    const TView o = op_view(out, osB, osY, osX);
-    a.in = op_view(in, isB, isY, isX);
-    a.out = strided2(o, 0, 0);
-    a.Cin = Cin; a.Cout = Cout;
-    a.ep.bias = bias; a.ep.scale = scale; a.ep.shift = shift; a.ep.relu = relu;
-    a.groups = 4;
-    HIPCHECK(hipMalloc((void**)&wp, 4 * pf.packedFloats * sizeof(float)));
-    for (int t = 0; t < 4 && rc == DG_OK; ++t) {
-      float* dst = wp + (size_t)t * pf.packedFloats;
-      rc = dg_pack_weights(pf, w_hwoi + (size_t)t * Cout * Cin, Cin, Cout, 1, 0, 0, nullptr, dst, st);
-      a.w_group[t] = dst;
-      a.out_group_off[t] = strided2(o, t / 2, t % 2).p - a.out.p;
-    }
-    a.w = wp;
-    if (rc == DG_OK) rc = dg_conv_igemm(pf, a, st);
-  } else {
-    // as deconv_bwd_data: in = the upstream gradient (B, 2H, 2W, Cout), out = dIn (B, H, W, Cin)
-    const ConvPlan pb = plan(Cout, Cin);
-    if (!covered(pb)) { dg_set_error("op_deconv2x2_igemm: no MFMA plan for %d -> %d on path %d", Cout, Cin, path); return DG_ERR_UNSUPPORTED; }
-    const TView d = op_view(in, isB, isY, isX);
-    a.out = op_view(out, osB, osY, osX);
-    a.Cout = Cin;
-    a.ep.mask = op_view_or_null(mask, msB, msY, msX);
-    if (form == 1) {
-      const ConvPlan pbf = plan(4 * Cout, Cin);
-      if (!(pbf.variant == pb.variant && pbf.bf16 == pb.bf16 && (Cout % pb.CK) == 0 && pbf.packedFloats == 4 * pb.packedFloats)) {
-        dg_set_error("op_deconv2x2_igemm: the gathered 1x1 form does not cover %d -> %d", Cout, Cin);
-        return DG_ERR_UNSUPPORTED;
-      }
-      HIPCHECK(hipMalloc((void**)&wp, pbf.packedFloats * sizeof(float)));
-      // the four per-tap panels interleaved per channel tile, as refresh_generator builds GLayer::wpb_all
-      const size_t blk = (size_t)pb.nCC * pb.NT * pb.CK;   // elements
-      PackJob jobs[4];
-      for (int t = 0; t < 4 && rc == DG_OK; ++t) {
-        float* dst = reinterpret_cast<float*>(reinterpret_cast<char*>(wp) + t * blk * dg_plan_elem_bytes(pb));
-        rc = dg_pack_job(pb, w_hwoi + (size_t)t * Cout * Cin, Cin, Cout, 1, 1, 0, nullptr, dst, 4 * blk, &jobs[t]);
-      }
-      if (rc == DG_OK) rc = op_pack_jobs(jobs, 4, st);
-      deconv_gather_k(&a, d, Cout, pb.CK);
-      a.w = wp;
-      if (rc == DG_OK) rc = dg_conv_igemm(pbf, a, st);
-    } else {
-      HIPCHECK(hipMalloc((void**)&wp, 4 * pb.packedFloats * sizeof(float)));
-      a.Cin = Cout;
-      for (int t = 0; t < 4 && rc == DG_OK; ++t) {
-        float* dst = wp + (size_t)t * pb.packedFloats;
-        rc = dg_pack_weights(pb, w_hwoi + (size_t)t * Cout * Cin, Cin, Cout, 1, 1, 0, nullptr, dst, st);
-        if (rc != DG_OK) break;
-        a.in = strided2(d, t / 2, t % 2);
-        a.w = dst;
-        a.ep.accumulate = (t > 0);
-        rc = dg_conv_igemm(pb, a, st);
-      }
-    }
-  }
-  hipStreamSynchronize(st);
-  hipFree(wp);
-  return rc;
-}
-
-int depgan_op_conv2d_wgrad_ex(const float* x, long xsB, long xsY, long xsX, const float* dy, long dsB, long dsY,
-                              long dsX, const float* scale, float* dw, float* raw, int accumulate, int oi,
-                              int colB, const float* colscale, float* colout, float* colraw, int B, int H, int W,
-                              int Cin, int Cout, int KS, int bf16, void* stream) {
-  if (op_view_bad(x, xsB, xsY, xsX) || op_view_bad(dy, dsB, dsY, dsX) || !dw || B < 1 || H < 1 || W < 1 || Cin < 1 || Cout < 1 ||
-      (KS != 1 && KS != 3 && KS != 5)) {
-    dg_set_error("op_conv2d_wgrad_ex: null or non-positive argument");
-    return DG_ERR_ARG;
-  }
-  const bool cols = colout || colraw;
-  if ((bf16 != 0 && bf16 != 1) || (cols ? (colB < 1 || colB > B) : (colB != 0 || colscale != nullptr))) {
-    dg_set_error("op_conv2d_wgrad_ex: bf16 must be 0 or 1; column sums need colout or colraw and 1 <= colB <= B");
-    return DG_ERR_ARG;
-  }
-  const bool mfma = Cin % 4 == 0 && Cout % 4 == 0 && Cin >= 8;
-  if (bf16 && !(mfma && dg_wgrad_bf16_supported(KS, Cin, Cout))) {
-    dg_set_error("op_conv2d_wgrad_ex: the bf16 weight-gradient kernel does not cover %d -> %d", Cin, Cout);
-    return DG_ERR_UNSUPPORTED;
-  }
-  hipStream_t st = (hipStream_t)stream;
-  WgradWs ws;
-  memset(&ws, 0, sizeof(ws));
-  ws.partFloats = bf16 ? dg_wgrad_bf16_part_floats(KS, B, H, W, Cin, Cout)
-                  : mfma ? dg_wgrad_part_floats(KS, B, H, W, Cin, Cout) : dg_wgrad_small_part_floats(KS, B, H, W, Cin, Cout);
-  // one partial column-sum row per slab (MFMA kernels), or the scratch of the streaming pass (edge kernels)
-  ws.scratchFloats = mfma ? ws.partFloats / ((size_t)KS * KS * Cin) : (cols ? dg_colsum_scratch(colB, H, W, Cout) : 0);
-  ws.bf16 = bf16 != 0;
-  ws.st = st;
-  DGCHECK(op_alloc(&ws.part, ws.partFloats, "op_conv2d_wgrad_ex"));
-  int rc = op_alloc(&ws.scratch, ws.scratchFloats, "op_conv2d_wgrad_ex");
-  if (rc == DG_OK) {
-    const ColSum cs = {colB, colscale, colout, colraw};
-    rc = wgrad_run(ws, KS, op_view(x, xsB, xsY, xsX), op_view(dy, dsB, dsY, dsX), B, H, W, Cin, Cout, scale, dw, raw, accumulate,
-                   oi, cols ? &cs : nullptr);
-  }
-  hipStreamSynchronize(st);
-  hipFree(ws.part);
-  hipFree(ws.scratch);
-  return rc;
-}
-
-
-int depgan_op_bn_moments(const float* x, long sB, long sY, long sX, int B, int H, int W, int C, float* mean, float* var,
-                         long scratch_floats, void* stream) {
-  if (!x || !mean || !var || B < 1 || H < 1 || W < 1 || C < 4) { dg_set_error("op_bn_moments: bad argument"); return DG_ERR_ARG; }
-  hipStream_t st = (hipStream_t)stream;
-  const size_t cap = op_scratch(scratch_floats, dg_col_moments_scratch(B, H, W, C));
-  float* scratch = nullptr;
-  DGCHECK(op_alloc(&scratch, cap, "op_bn_moments"));
-  int rc = dg_col_moments(op_view(x, sB, sY, sX), B, H, W, C, mean, var, scratch, cap, st);
-  hipStreamSynchronize(st);
-  hipFree(scratch);
-  return rc;
-}
-
-int depgan_op_bn_backward(const float* dy, const float* raw, float* draw, long sB, long sY, long sX, int B, int H, int W,
-                          int C, const float* gamma, const float* mean, const float* var, float eps, float invN,
-                          float dyscale, float* dgamma, float* dbeta, long scratch_floats, void* stream) {
-  if (!dy || !raw || !draw || !gamma || !mean || !var || !dgamma || !dbeta || B < 1 || H < 1 || W < 1 || C < 4) {
-    dg_set_error("op_bn_backward: bad argument");
-    return DG_ERR_ARG;
-  }
-  hipStream_t st = (hipStream_t)stream;
-  const size_t cap = op_scratch(scratch_floats, dg_colsum_pair_scratch(B, H, W, C));
-  float *scratch = nullptr, *coef = nullptr;
-  DGCHECK(op_alloc(&scratch, cap, "op_bn_backward"));
-  int rc = op_alloc(&coef, (size_t)8 * C, "op_bn_backward");
-  if (rc == DG_OK) {
-    // uresnet.hip: dg_bn_train_prepare (s, t, rstd) in the forward; dg_colsum_pair -> dg_bn_bwd_coeffs -> dg_axpby_ch
-    float *s = coef, *t = coef + C, *rstd = coef + 2 * C, *sums = coef + 3 * C, *cA = coef + 5 * C, *cB = coef + 6 * C,
-          *cC = coef + 7 * C;
-    const TView dyv = op_view(dy, sB, sY, sX), rawv = op_view(raw, sB, sY, sX), dv = op_view(draw, sB, sY, sX);
-    rc = dg_bn_train_prepare(gamma, gamma, mean, var, eps, 0.f, 0.f, nullptr, nullptr, s, t, rstd, C, st);  // t unused
-    if (rc == DG_OK) rc = dg_colsum_pair(dyv, rawv, mean, B, H, W, C, sums, scratch, cap, st);
-    if (rc == DG_OK) rc = dg_bn_bwd_coeffs(sums, mean, rstd, s, invN, dyscale, dgamma, dbeta, cA, cB, cC, C, st);
-    if (rc == DG_OK) rc = dg_axpby_ch(dyv, rawv, dv, B, H, W, C, cA, cB, cC, st);
-  }
-  hipStreamSynchronize(st);
-  hipFree(scratch);
-  hipFree(coef);
-  return rc;
-}
-
-int depgan_op_affine_act(const float* in, float* out, float* out_pre, const float* res, long sB, long sY, long sX,
-                         const float* s, const float* t, const float* film_mul, const float* film_add, int film_ld,
-                         int relu, int B, int H, int W, int C, unsigned drop_seed, float drop_rate, void* stream) {
-  if (!in || !out || !s || !t || (!film_mul != !film_add) || B < 1 || H < 1 || W < 1 || C < 4) {
-    dg_set_error("op_affine_act: bad argument");
-    return DG_ERR_ARG;
-  }
-  AffineActArgs a;
-  memset(&a, 0, sizeof(a));
-  a.in = op_view(in, sB, sY, sX);
-  a.out = op_view(out, sB, sY, sX);
-  a.out_pre = out_pre ? op_view(out_pre, sB, sY, sX) : null_view();
-  a.res = res ? op_view(res, sB, sY, sX) : null_view();
-  a.s = s;
-  a.t = t;
-  a.film_mul = film_mul;
-  a.film_add = film_add;
-  a.film_ld = film_ld;
-  a.relu = relu;
-  a.B = B; a.H = H; a.W = W; a.C = C;
-  a.drop_seed = drop_seed;
-  a.drop_rate = drop_rate;
-  return dg_affine_act(a, (hipStream_t)stream);
-}
-
-int depgan_op_softmax_ce4(const float* logits, const float* onehot, float* probs, float* dz, float* loss_sum, long P,
-                          void* stream) {
-  if (!logits || !probs || P < 1 || (onehot && (!dz || !loss_sum))) { dg_set_error("op_softmax_ce4: bad argument"); return DG_ERR_ARG; }
-  hipStream_t st = (hipStream_t)stream;
-  if (!onehot) return dg_softmax4(logits, probs, P, st);
-  float* scratch = nullptr;
-  DGCHECK(op_alloc(&scratch, 1024, "op_softmax_ce4"));
-  int rc = dg_softmax_ce4(logits, onehot, probs, dz, loss_sum, P, scratch, st);
-  hipStreamSynchronize(st);
-  hipFree(scratch);
-  return rc;
-}
-
-int depgan_op_bn_rows_fwd(const float* x, float* y, int R, int C, int ld, const float* gamma, const float* beta,
-                          float eps, float momentum, float corr, float* moving_mean, float* moving_var, float* mean,
-                          float* rstd, int relu, void* stream) {
-  if (!x || !y || !gamma || !beta || !mean || !rstd || (!moving_mean != !moving_var) || R < 1 || C < 1 || ld < C) {
-    dg_set_error("op_bn_rows_fwd: bad argument");
-    return DG_ERR_ARG;
-  }
-  return dg_bn_rows_fwd(x, y, R, C, ld, gamma, beta, eps, momentum, corr, moving_mean, moving_var, mean, rstd, relu,
-                        (hipStream_t)stream);
-}
-int depgan_op_bn_rows_bwd(const float* dy, const float* x, const float* relu_out, float* dx, int R, int C, int ld,
-                          const float* gamma, const float* mean, const float* rstd, float* dgamma, float* dbeta,
-                          void* stream) {
-  if (!dy || !x || !dx || !gamma || !mean || !rstd || !dgamma || !dbeta || R < 1 || C < 1 || ld < C) {
-    dg_set_error("op_bn_rows_bwd: bad argument");
-    return DG_ERR_ARG;
-  }
-  return dg_bn_rows_bwd(dy, x, relu_out, dx, R, C, ld, gamma, mean, rstd, dgamma, dbeta, (hipStream_t)stream);
-}
-
-int depgan_op_small_gemm(int form, const float* A, const float* Bm, const float* bias, float* Cm, int M, int K, int N,
-                         void* stream) {
-  if (!A || !Bm || !Cm || M < 1 || K < 1 || N < 1) { dg_set_error("op_small_gemm: bad argument"); return DG_ERR_ARG; }
-  hipStream_t st = (hipStream_t)stream;
-  if (form == 0) return dg_small_gemm(A, Bm, bias, Cm, M, K, N, st);
-  if (form == 1) return dg_small_gemm_at(A, Bm, Cm, M, K, N, st);
-  if (form == 2) return dg_small_gemm_bt(A, Bm, Cm, M, K, N, st);
-  dg_set_error("op_small_gemm: form %d is not 0, 1 or 2", form);
-  return DG_ERR_ARG;
-}
-
-
-// ---- the two-critic step's HBM-bound operators (ops.hip) and the noise MLP (noise.hip), each the dg_* function the
-// model calls; views as above, scratch_floats <= 0 for what the launch needs ----
-extern "C++" {
-// allocate a reduction scratch of op_scratch(scratch_floats, need) floats, run the call, synchronise, free
-template <typename F>
-static int op_with_scratch(long scratch_floats, size_t need, const char* who, hipStream_t st, F&& call) {
-  const size_t cap = op_scratch(scratch_floats, need);
-  float* scratch = nullptr;
-  DGCHECK(op_alloc(&scratch, cap, who));
-  const int rc = call(scratch, cap);
-  hipStreamSynchronize(st);
-  hipFree(scratch);
-  return rc;
-}
-// a job table on the device, as the model's upload_table makes it
-template <typename T>
-static int op_upload_jobs(const std::vector<T>& jobs, T** dev, const char* who) {
-  *dev = nullptr;
-  if (hipMalloc((void**)dev, jobs.size() * sizeof(T)) != hipSuccess) { dg_set_error("%s: out of device memory", who); return DG_ERR_HIP; }
-  if (hipMemcpy(*dev, jobs.data(), jobs.size() * sizeof(T), hipMemcpyHostToDevice) != hipSuccess) {
-    dg_set_error("%s: job table upload failed", who);
-    return DG_ERR_HIP;
-  }
-  return DG_OK;
-}
-}  // extern "C++"
-
-int depgan_op_unpool_mask(const float* dpool, long dsB, long dsY, long dsX, const float* a, long asB, long asY, long asX,
-                          const float* skip, long ssB, long ssY, long ssX, float* out, long osB, long osY, long osX,
-                          int B, int Ho, int Wo, int C, void* stream) {
-  if (!dpool || !a || !out || B < 1 || Ho < 1 || Wo < 1 || C < 1) { dg_set_error("op_unpool_mask: bad argument"); return DG_ERR_ARG; }
-  return dg_unpool_mask(op_view(dpool, dsB, dsY, dsX), op_view(a, asB, asY, asX), op_view_or_null(skip, ssB, ssY, ssX),
-                        op_view(out, osB, osY, osX), B, Ho, Wo, C, (hipStream_t)stream);
-}
-int depgan_op_gather_pool(const float* u, long usB, long usY, long usX, const float* a, long asB, long asY, long asX,
-                          float* out, long osB, long osY, long osX, int B, int Ho, int Wo, int C, void* stream) {
-  if (!u || !a || !out || B < 1 || Ho < 1 || Wo < 1 || C < 1) { dg_set_error("op_gather_pool: bad argument"); return DG_ERR_ARG; }
-  return dg_gather_pool(op_view(u, usB, usY, usX), op_view(a, asB, asY, asX), op_view(out, osB, osY, osX), B, Ho, Wo, C,
-                        (hipStream_t)stream);
-}
-
-int depgan_op_head(int backward, const float* a, const float* w, const float* b, const float* dpre, float* out, long P,
-                   int C, int tanh_act, void* stream) {
-  if (!a || !w || !out || P < 1 || C < 1 || (backward ? !dpre : !b)) { dg_set_error("op_head: bad argument"); return DG_ERR_ARG; }
-  if (backward) return dg_head_bwd(dpre, w, a, out, P, C, (hipStream_t)stream);
-  return dg_head_fwd(a, w, b, out, P, C, tanh_act, (hipStream_t)stream);
-}
-
-int depgan_op_critic_tail_fwd(const float* a, const float* w9, const float* b9, const float* wd, const float* bd,
-                              float* t9, float* out, int N, int HW, int C, void* stream) {
-  if (!a || !w9 || !b9 || !wd || !bd || !t9 || !out || N < 1 || HW < 1 || C < 1) {
-    dg_set_error("op_critic_tail_fwd: bad argument");
-    return DG_ERR_ARG;
-  }
-  return dg_critic_tail_fwd(a, w9, b9, wd, bd, t9, out, N, HW, C, (hipStream_t)stream);
-}
-int depgan_op_critic_tail_bwd(const float* a, const float* w9, const float* wd, const float* coefs, int per, float* dz,
-                              int N, int HW, int C, void* stream) {
-  if (!a || !w9 || !wd || !coefs || !dz || per < 1 || N < 1 || HW < 1 || C < 4 || (C % 4)) {
-    dg_set_error("op_critic_tail_bwd: bad argument");
-    return DG_ERR_ARG;
-  }
-  return dg_critic_tail_bwd(a, w9, wd, coefs, per, dz, N, HW, C, (hipStream_t)stream);
-}
-int depgan_op_critic_tail_wgrad(const float* src, const float* w9, const float* b9, const float* wd, const float* coefs,
-                                int per, int add_bias_terms, int accumulate, float* dw9, float* db9, float* dwd,
-                                float* dbd, int N, int HW, int C, long scratch_floats, void* stream) {
-  if (!src || !w9 || !wd || !coefs || !dw9 || !dwd || per < 1 || N < 1 || HW < 1 || C < 1 ||
-      (add_bias_terms && (!b9 || !db9 || !dbd))) {
-    dg_set_error("op_critic_tail_wgrad: bad argument");
-    return DG_ERR_ARG;
-  }
-  hipStream_t st = (hipStream_t)stream;
-  return op_with_scratch(scratch_floats, dg_critic_tail_wgrad_scratch(N, HW, C), "op_critic_tail_wgrad", st,
-                         [&](float* scratch, size_t cap) {
-                           return dg_critic_tail_wgrad(src, w9, b9, wd, coefs, per, add_bias_terms, accumulate, dw9,
-                                                       db9, dwd, dbd, scratch, cap, N, HW, C, st);
-                         });
-}
-
-int depgan_op_colsum(const float* v, long sB, long sY, long sX, int B, int H, int W, int C, const float* scale,
-                     float* out, float* raw, int accumulate, const float* rowmul, long scratch_floats, void* stream) {
-  if (!v || B < 1 || H < 1 || W < 1 || C < 1 || (!out && !raw) || (rowmul && (!out || scale || raw || accumulate))) {
-    dg_set_error("op_colsum: bad argument");
-    return DG_ERR_ARG;
-  }
-  hipStream_t st = (hipStream_t)stream;
-  const TView vv = op_view(v, sB, sY, sX);
-  return op_with_scratch(scratch_floats, dg_colsum_scratch(B, H, W, C), "op_colsum", st, [&](float* scratch, size_t cap) {
-    if (rowmul) return dg_colsum_rowmul(vv, B, H, W, C, rowmul, out, scratch, cap, st);
-    return dg_colsum(vv, B, H, W, C, scale, out, raw, accumulate, scratch, cap, st);
-  });
-}
-int depgan_op_sum(const float* in, long n, float* out, long scratch_floats, void* stream) {
-  if (!in || !out || n < 1) { dg_set_error("op_sum: bad argument"); return DG_ERR_ARG; }
-  hipStream_t st = (hipStream_t)stream;
-  return op_with_scratch(scratch_floats, dg_sum_scratch((size_t)n), "op_sum", st, [&](float* scratch, size_t cap) {
-    return dg_sum(in, (size_t)n, out, scratch, cap, st);
-  });
-}
-
-int depgan_op_critic_inputs(const float* y2, const float* x, int nicg, const float* attr, const float* ep, float* out,
-                            int B, long HW, int which, void* stream) {
-  if (!x || !attr || !out || nicg < 1 || B < 1 || HW < 1 || which < 0 || which > 2 || (which < 2 && (!y2 || !ep))) {
-    dg_set_error("op_critic_inputs: bad argument");
-    return DG_ERR_ARG;
-  }
-  if (which == 2) return dg_add_ch0(x, nicg, attr, out, (long)B * HW, (hipStream_t)stream);
-  return dg_critic_inputs(y2, x, nicg, attr, ep, out, B, HW, which, (hipStream_t)stream);
-}
-
-int depgan_op_gp_u0(const float* g0, float* u0, float* norms, float* gp_out, float delta, int B, long HW,
-                    long scratch_floats, void* stream) {
-  if (!g0 || !u0 || !norms || B < 1 || HW < 1) { dg_set_error("op_gp_u0: bad argument"); return DG_ERR_ARG; }
-  hipStream_t st = (hipStream_t)stream;
-  return op_with_scratch(scratch_floats, dg_gp_u0_scratch(B), "op_gp_u0", st, [&](float* scratch, size_t cap) {
-    return dg_gp_u0(g0, u0, norms, gp_out, delta, B, HW, scratch, cap, st);
-  });
-}
-int depgan_op_critic_stats(const float* d_out, const float* norms, float* out, int B, void* stream) {
-  if (!d_out || !norms || !out || B < 1) { dg_set_error("op_critic_stats: bad argument"); return DG_ERR_ARG; }
-  return dg_critic_stats(d_out, norms, out, B, (hipStream_t)stream);
-}
-
-int depgan_op_gloss_sums(const float* x, int nicg, const float* y2, const float* attr, float thr, float* sums, long P,
-                         long scratch_floats, void* stream) {
-  if (!x || !y2 || !attr || !sums || nicg < 1 || P < 1) { dg_set_error("op_gloss_sums: bad argument"); return DG_ERR_ARG; }
-  hipStream_t st = (hipStream_t)stream;
-  return op_with_scratch(scratch_floats, dg_gloss_sums_scratch(P), "op_gloss_sums", st, [&](float* scratch, size_t cap) {
-    return dg_gloss_sums(x, nicg, y2, attr, thr, sums, P, scratch, cap, st);
-  });
-}
-int depgan_op_g_dpre(const float* x, int nicg, const float* y2, const float* attr, const float* g1, const float* g2,
-                     float* dpre, int B, long P, void* stream) {
-  if (!x || !y2 || !attr || !g1 || !g2 || !dpre || nicg < 1 || B < 1 || P < 1) {
-    dg_set_error("op_g_dpre: bad argument");
-    return DG_ERR_ARG;
-  }
-  return dg_g_dpre(x, nicg, y2, attr, g1, g2, dpre, B, P, (hipStream_t)stream);
-}
-
-int depgan_op_film_bwd(const float* dr, const float* u, const float* fmul, const float* fadd, int film_ld, float* du,
-                       float* dmul, float* dadd, int B, long HW, int C, long scratch_floats, void* stream) {
-  if (!dr || !u || !fmul || !fadd || !du || !dmul || !dadd || film_ld < C || B < 1 || HW < 1 || C < 1) {
-    dg_set_error("op_film_bwd: bad argument");
-    return DG_ERR_ARG;
-  }
-  hipStream_t st = (hipStream_t)stream;
-  return op_with_scratch(scratch_floats, dg_film_bwd_scratch(B, C), "op_film_bwd", st, [&](float* scratch, size_t cap) {
-    return dg_film_bwd(dr, u, fmul, fadd, film_ld, du, dmul, dadd, B, HW, C, scratch, cap, st);
-  });
-}
-
-int depgan_op_bn_prepare_batch(void* const* ptrs, const int* C, int njobs, float eps, void* stream) {
-  if (!ptrs || !C || njobs < 1) { dg_set_error("op_bn_prepare_batch: bad argument"); return DG_ERR_ARG; }
-  std::vector<BnJob> jobs(njobs);
-  for (int j = 0; j < njobs; ++j) {
-    void* const* q = ptrs + 8 * j;
-    for (int k = 0; k < 7; ++k)   // q[7], mean_copy, is optional
-      if (!q[k] || C[j] < 1) { dg_set_error("op_bn_prepare_batch: job %d: bad argument", j); return DG_ERR_ARG; }
-    jobs[j] = {(const float*)q[0], (const float*)q[1], (const float*)q[2], (const float*)q[3], (float*)q[4],
-               (float*)q[5], (float*)q[6], (float*)q[7], C[j]};
-  }
-  hipStream_t st = (hipStream_t)stream;
-  BnJob* dev = nullptr;
-  int rc = op_upload_jobs(jobs, &dev, "op_bn_prepare_batch");
-  if (rc == DG_OK) rc = dg_bn_prepare_batch(dev, njobs, eps, st);
-  hipStreamSynchronize(st);
-  hipFree(dev);
-  return rc;
-}
-
-int depgan_op_bn_gamma_grad_batch(void* const* ptrs, const int* dims, int njobs, void* stream) {
-  if (!ptrs || !dims || njobs < 1) { dg_set_error("op_bn_gamma_grad_batch: bad argument"); return DG_ERR_ARG; }
-  std::vector<GammaJob> jobs(njobs);
-  int nblocks = 0;
-  for (int j = 0; j < njobs; ++j) {
-    void* const* q = ptrs + 7 * j;
-    const int* d = dims + 4 * j;   // K, Cout, oi, Cin
-    for (int k = 0; k < 7; ++k)
-      if (!q[k]) { dg_set_error("op_bn_gamma_grad_batch: job %d: null pointer", j); return DG_ERR_ARG; }
-    if (d[0] < 1 || d[1] < 1 || (d[2] != 0 && d[2] != 1) || (d[2] && (d[3] < 1 || d[0] % d[3]))) {
-      dg_set_error("op_bn_gamma_grad_batch: job %d: bad shape", j);
-      return DG_ERR_ARG;
-    }
-    jobs[j] = {(const float*)q[0], (const float*)q[1], (const float*)q[2], (const float*)q[3], (const float*)q[4],
-               (const float*)q[5], (float*)q[6], d[0], d[1], d[2], d[3], nblocks};
-    nblocks += d[1];   // one block per output channel, jobs back to back (the model's g_gamma_jobs)
-  }
-  hipStream_t st = (hipStream_t)stream;
-  GammaJob* dev = nullptr;
-  int rc = op_upload_jobs(jobs, &dev, "op_bn_gamma_grad_batch");
-  if (rc == DG_OK) rc = dg_bn_gamma_grad_batch(dev, njobs, nblocks, st);
-  hipStreamSynchronize(st);
-  hipFree(dev);
-  return rc;
-}
-
-// NoiseParams / NoiseGrads over packed buffers (include/depgan.h)
-static int op_noise_params(const float* trunk, const float* Wh, const float* hvec, const int* ncol, NoiseParams* P) {
-  if (!trunk || !Wh || !hvec || !ncol) { dg_set_error("op_noise: bad argument"); return DG_ERR_ARG; }
-  P->W0 = trunk; P->b0 = trunk + 32; P->s0 = trunk + 64; P->t0 = trunk + 96; P->mean0 = trunk + 128;
-  P->rstd0 = trunk + 160;
-  P->W1 = trunk + 192; P->b1 = trunk + 1216; P->s1 = trunk + 1248; P->t1 = trunk + 1280; P->mean1 = trunk + 1312;
-  P->rstd1 = trunk + 1344;
-  int col = 0;
-  size_t woff = 0;
-  for (int h = 0; h < NOISE_NHEADS; ++h) {
-    if (ncol[h] < 1) { dg_set_error("op_noise: head %d has %d columns", h, ncol[h]); return DG_ERR_ARG; }
-    P->Wh[h] = Wh + woff;
-    P->bh[h] = hvec + col;
-    P->col0[h] = col;
-    P->ncol[h] = ncol[h];
-    woff += (size_t)1024 * ncol[h];
-    col += ncol[h];
-  }
-  if (col != 1024) { dg_set_error("op_noise: head widths sum to %d, not 1024", col); return DG_ERR_ARG; }
-  P->sh = hvec + 1024; P->th = hvec + 2048; P->meanh = hvec + 3072; P->rstdh = hvec + 4096;
-  return DG_OK;
-}
-static NoiseActs op_noise_acts(float* acts, int B) {
-  const size_t n = (size_t)B * 1024;
-  NoiseActs A;
-  A.h0 = acts; A.a0 = acts + n; A.h1 = acts + 2 * n; A.a1 = acts + 3 * n; A.lin = acts + 4 * n; A.heads = acts + 5 * n;
-  return A;
-}
-
-int depgan_op_noise_fwd(const float* trunk, const float* Wh, const float* hvec, const int* ncol, const float* z,
-                        float* acts, int B, void* stream) {
-  NoiseParams P;
-  DGCHECK(op_noise_params(trunk, Wh, hvec, ncol, &P));
-  if (!z || !acts || B < 1) { dg_set_error("op_noise_fwd: bad argument"); return DG_ERR_ARG; }
-  return dg_noise_fwd(P, z, op_noise_acts(acts, B), B, (hipStream_t)stream);
-}
-int depgan_op_noise_bwd(const float* trunk, const float* Wh, const float* hvec, const int* ncol, const float* z,
-                        float* acts, const float* dheads, float* gtrunk, float* dWh, float* ghvec, int B,
-                        long scratch_floats, void* stream) {
-  NoiseParams P;
-  DGCHECK(op_noise_params(trunk, Wh, hvec, ncol, &P));
-  if (!z || !acts || !dheads || !gtrunk || !dWh || !ghvec || B < 1) { dg_set_error("op_noise_bwd: bad argument"); return DG_ERR_ARG; }
-  NoiseGrads G;
-  G.dW0 = gtrunk; G.db0 = gtrunk + 32; G.dgamma0 = gtrunk + 64; G.dbeta0 = gtrunk + 96;
-  G.dW1 = gtrunk + 128; G.db1 = gtrunk + 1152; G.dgamma1 = gtrunk + 1184; G.dbeta1 = gtrunk + 1216;
-  for (int h = 0; h < NOISE_NHEADS; ++h) {
-    G.dWh[h] = dWh + ((size_t)(P.Wh[h] - Wh));
-    G.dbh[h] = ghvec + P.col0[h];
-    G.dgamma_h[h] = ghvec + 1024 + P.col0[h];
-    G.dbeta_h[h] = ghvec + 2048 + P.col0[h];
-  }
-  hipStream_t st = (hipStream_t)stream;
-  const NoiseActs A = op_noise_acts(acts, B);
-  return op_with_scratch(scratch_floats, dg_noise_bwd_scratch(B), "op_noise_bwd", st, [&](float* scratch, size_t cap) {
-    return dg_noise_bwd(P, G, z, A, dheads, scratch, cap, B, st);
-  });
-}
-
-int depgan_op_best_noise(const float* stats, int k, const float* z_all, long zfloats, int* best, float* z_out,
-                         void* stream) {
-  if (!stats || !z_all || !best || !z_out || k < 1 || zfloats < 1) { dg_set_error("op_best_noise: bad argument"); return DG_ERR_ARG; }
-  return dg_best_noise(stats, k, z_all, zfloats, best, z_out, (hipStream_t)stream);
-}
-
-int depgan_op_round_bf16_masked(const float* src, const unsigned char* mask, float* dst, long n, void* stream) {
-  if (!src || !mask || !dst || n < 1) { dg_set_error("op_round_bf16_masked: bad argument"); return DG_ERR_ARG; }
-  return dg_round_bf16_masked(src, mask, dst, (size_t)n, (hipStream_t)stream);
 }
 
 }  // extern "C"

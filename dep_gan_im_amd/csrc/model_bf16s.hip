@@ -37,7 +37,7 @@ int bf16s_check_ctx(const depgan_ctx* c, const char* who) {
   for (size_t i = 0; i < c->gl.size(); ++i) {
     const GLayer& L = c->gl[i];
     const bool conv = (L.kind == G_CONV && i > 0) || L.kind == G_FILM || L.kind == G_DECONV;
-    if (conv && (L.pf.bf16 != 1 || L.pf.variant < 100 || L.pf.variant >= 200 || !L.wpf[0] || (L.Cin % 8) || (L.Cout % 32))) {
+    if (conv && (!dg_plan_bf16(L.pf) || !L.wpf[0] || (L.Cin % 8) || (L.Cout % 32))) {
       dg_set_error("%s: layer %s (%d -> %d) has no bf16 plan; the storage types are not mixed", who, L.name.c_str(),
                    L.Cin, L.Cout);
       return DG_ERR_UNSUPPORTED;
@@ -138,12 +138,8 @@ int g_forward_bf16s(depgan_ctx* c, const float* x, const float* z, float* out, i
       DGCHECK(dg_edge_conv_bf16s(e, c->st));
       pooled_by_conv = false;
     } else if (L.kind == G_CONV || L.kind == G_FILM) {
-      ConvArgsH a;
-      memset(&a, 0, sizeof(a));
-      a.in = c->h_in[i];
-      a.out = c->h_out[i];
+      ConvArgsH a = conv_args_h(c->h_in[i], c->h_out[i], n, L.H, L.W, L.Cin, L.Cout);
       a.w = L.wpf[0];
-      a.B = n; a.H = L.H; a.W = L.W; a.Cin = L.Cin; a.Cout = L.Cout;
       a.ep.bias = L.b; a.ep.scale = L.s; a.ep.shift = L.t; a.ep.relu = 1;
       if (L.kind == G_FILM) {
         a.ep.film_mul = c->na.heads + L.col_mul;
@@ -189,11 +185,7 @@ int g_forward_bf16s(depgan_ctx* c, const float* x, const float* z, float* out, i
       return DG_ERR_UNSUPPORTED;
     } else if (L.kind == G_DECONV) {
       // four 1x1 convolutions of the same input, tap (di, dj) writing the pixel grid (2i + di, 2j + dj): one grouped launch
-      ConvArgsH a;
-      memset(&a, 0, sizeof(a));
-      a.in = c->h_in[i];
-      a.out = strided2_h(c->h_out[i], 0, 0);
-      a.B = n; a.H = L.H; a.W = L.W; a.Cin = L.Cin; a.Cout = L.Cout;
+      ConvArgsH a = conv_args_h(c->h_in[i], strided2_h(c->h_out[i], 0, 0), n, L.H, L.W, L.Cin, L.Cout);
       a.ep.bias = L.b; a.ep.scale = L.s; a.ep.shift = L.t; a.ep.relu = 1;
       a.groups = 4;
       for (int t = 0; t < 4; ++t) {
@@ -312,17 +304,13 @@ static int op_conv2d_bf16s_impl(const char* who, const void* in, long isB, long 
   }
   if (KS != 1 && KS != 3) { dg_set_error("%s: KS must be 1 or 3", who); return DG_ERR_ARG; }
   const ConvPlan pl = dg_plan_conv_bf16(KS, Cin, Cout);
-  if (pl.bf16 != 1 || (Cin % 8)) { dg_set_error("%s: the bf16 MFMA kernel does not cover %d -> %d", who, Cin, Cout); return DG_ERR_UNSUPPORTED; }
+  if (!dg_plan_bf16(pl) || (Cin % 8)) { dg_set_error("%s: the bf16 MFMA kernel does not cover %d -> %d", who, Cin, Cout); return DG_ERR_UNSUPPORTED; }
   if (head_out && (KS != 3 || Cout != 32)) {
     dg_set_error("%s: the fused head needs a 3x3 convolution to exactly 32 channels (KS %d, Cout %d)", who, KS, Cout);
     return DG_ERR_UNSUPPORTED;
   }
   hipStream_t st = (hipStream_t)stream;
-  ConvArgsH a;
-  memset(&a, 0, sizeof(a));
-  a.in = op_view_h(in, isB, isY, isX);
-  a.out = op_view_h(out, osB, osY, osX);
-  a.B = B; a.H = H; a.W = W; a.Cin = Cin; a.Cout = Cout;
+  ConvArgsH a = conv_args_h(op_view_h(in, isB, isY, isX), op_view_h(out, osB, osY, osX), B, H, W, Cin, Cout);
   a.ep.bias = bias; a.ep.scale = scale; a.ep.shift = shift;
   a.ep.film_mul = film_mul; a.ep.film_add = film_add; a.ep.film_ld = film_ld;
   a.ep.res = op_view_h_or_null(res, rsB, rsY, rsX);
@@ -370,14 +358,10 @@ int depgan_op_deconv2x2_bf16s(const void* in, long isB, long isY, long isX, cons
     return DG_ERR_ARG;
   }
   const ConvPlan pl = dg_plan_conv_bf16(1, Cin, Cout);
-  if (pl.bf16 != 1 || (Cin % 8)) { dg_set_error("op_deconv2x2_bf16s: the bf16 MFMA kernel does not cover %d -> %d", Cin, Cout); return DG_ERR_UNSUPPORTED; }
+  if (!dg_plan_bf16(pl) || (Cin % 8)) { dg_set_error("op_deconv2x2_bf16s: the bf16 MFMA kernel does not cover %d -> %d", Cin, Cout); return DG_ERR_UNSUPPORTED; }
   hipStream_t st = (hipStream_t)stream;
   const TViewH o = op_view_h(out, osB, osY, osX);   // the (2H, 2W) output
-  ConvArgsH a;
-  memset(&a, 0, sizeof(a));
-  a.in = op_view_h(in, isB, isY, isX);
-  a.out = strided2_h(o, 0, 0);
-  a.B = B; a.H = H; a.W = W; a.Cin = Cin; a.Cout = Cout;
+  ConvArgsH a = conv_args_h(op_view_h(in, isB, isY, isX), strided2_h(o, 0, 0), B, H, W, Cin, Cout);
   a.ep.bias = bias; a.ep.scale = scale; a.ep.shift = shift; a.ep.relu = relu;
   a.ep.res = null_view_h();
   a.ep.pool = null_view_h();

@@ -104,13 +104,8 @@ static int conv_bn_bwd_h(depgan_ctx* c, GLayer& L, size_t li, const float* x_use
     return wgrad_full(c, 3, make_view(const_cast<float*>(x_user), L.H, L.W, L.Cin), dy, n, L.H, L.W, L.Cin, L.Cout, L.s,
                       L.dW, raw, 0, 0, &cs);
   DGCHECK(wgrad_full_h(c, 3, c->h_in[li], dy, n, L.H, L.W, L.Cin, L.Cout, L.s, L.dW, raw, 0, &cs));
-  ConvArgs a;
-  memset(&a, 0, sizeof(a));
-  zero_ep(&a.ep);
-  a.in = dy;
-  a.out = L.din;
+  ConvArgs a = conv_args(dy, L.din, n, L.H, L.W, L.Cout, L.Cin);
   a.w = L.wpb[0];
-  a.B = n; a.H = L.H; a.W = L.W; a.Cin = L.Cout; a.Cout = L.Cin;
   a.ep.res = res;
   // the mask of the fp32 path is the layer's own input tensor (the producer's output, or the whole concat buffer)
   return bwd_data_h(c, L.pb, a, L.in_mask.p ? c->h_in[li] : null_view_h(), 3);
@@ -156,11 +151,7 @@ int g_backward_bf16s(depgan_ctx* c, const float* x, const float* z, int n) {
       }
       // backward-data: one 1x1 convolution over the four strided grids of the upstream gradient (deconv_bwd_data)
       if (!L.wpb_all) { dg_set_error("g_backward_bf16s: %s has no gathered backward-data panel", L.name.c_str()); return DG_ERR_UNSUPPORTED; }
-      ConvArgs a;
-      memset(&a, 0, sizeof(a));
-      zero_ep(&a.ep);
-      a.out = L.din;
-      a.B = n; a.H = L.H; a.W = L.W; a.Cout = L.Cin;
+      ConvArgs a = conv_args(null_view(), L.din, n, L.H, L.W, L.Cout, L.Cin);
       deconv_gather_k(&a, L.dout, L.Cout, L.pb.CK);
       a.w = L.wpb_all;
       DGCHECK(bwd_data_h(c, L.pbf, a, L.in_mask.p ? c->h_in[i] : null_view_h(), 1));
@@ -240,13 +231,10 @@ int depgan_op_conv2d_film_train_bf16s(const void* in, long isB, long isY, long i
     return DG_ERR_ARG;
   }
   const ConvPlan pl = dg_plan_conv_bf16(3, Cin, Cout);
-  if (pl.bf16 != 1 || (Cin % 8)) { dg_set_error("op_conv2d_film_train_bf16s: the bf16 MFMA kernel does not cover %d -> %d", Cin, Cout); return DG_ERR_UNSUPPORTED; }
+  if (!dg_plan_bf16(pl) || (Cin % 8)) { dg_set_error("op_conv2d_film_train_bf16s: the bf16 MFMA kernel does not cover %d -> %d", Cin, Cout); return DG_ERR_UNSUPPORTED; }
   hipStream_t st = (hipStream_t)stream;
   ConvArgsHT a;
-  memset(&a, 0, sizeof(a));
-  a.in = op_view_h(in, isB, isY, isX);
-  a.out = op_view_h(out, osB, osY, osX);
-  a.B = B; a.H = H; a.W = W; a.Cin = Cin; a.Cout = Cout;
+  static_cast<ConvArgsH&>(a) = conv_args_h(op_view_h(in, isB, isY, isX), op_view_h(out, osB, osY, osX), B, H, W, Cin, Cout);
   a.ep.bias = bias; a.ep.scale = scale; a.ep.shift = shift;
   a.ep.film_mul = film_mul; a.ep.film_add = film_add; a.ep.film_ld = film_ld;
   a.ep.res = op_view_h_or_null(res, rsB, rsY, rsX);
@@ -314,11 +302,7 @@ int depgan_op_conv2d_bwd_data_bf16s(const float* dy, long dsB, long dsY, long ds
   }
   if (deconv != 0 && deconv != 1) { dg_set_error("op_conv2d_bwd_data_bf16s: deconv must be 0 or 1"); return DG_ERR_ARG; }
   hipStream_t st = (hipStream_t)stream;
-  ConvArgs a;
-  memset(&a, 0, sizeof(a));
-  zero_ep(&a.ep);
-  a.out = op_view(dx, osB, osY, osX);
-  a.B = B; a.H = H; a.W = W; a.Cout = Cin;
+  ConvArgs a = conv_args(null_view(), op_view(dx, osB, osY, osX), B, H, W, Cout, Cin);
   a.ep.res = op_view_or_null(res, rsB, rsY, rsX);
   const TViewH mh = op_view_h_or_null(mask, msB, msY, msX);
   const TView d = op_view(dy, dsB, dsY, dsX);
@@ -327,15 +311,14 @@ int depgan_op_conv2d_bwd_data_bf16s(const float* dy, long dsB, long dsY, long ds
   ConvPlan pl;
   if (!deconv) {
     pl = dg_plan_conv_bf16(3, Cout, Cin);
-    if (pl.bf16 != 1) { dg_set_error("op_conv2d_bwd_data_bf16s: the bf16 MFMA kernel does not cover %d -> %d", Cout, Cin); return DG_ERR_UNSUPPORTED; }
+    if (!dg_plan_bf16(pl)) { dg_set_error("op_conv2d_bwd_data_bf16s: the bf16 MFMA kernel does not cover %d -> %d", Cout, Cin); return DG_ERR_UNSUPPORTED; }
     HIPCHECK(hipMalloc((void**)&wp, pl.packedFloats * sizeof(float)));
     rc = dg_pack_weights(pl, w, Cin, Cout, 0, 1, 1, nullptr, wp, st);
     a.in = d;
-    a.Cin = Cout;
   } else {
     const ConvPlan pb = dg_plan_conv_bf16(1, Cout, Cin);
     pl = dg_plan_conv_bf16(1, 4 * Cout, Cin);
-    if (pb.bf16 != 1 || pl.bf16 != 1 || (Cout % pb.CK) || pl.packedFloats != 4 * pb.packedFloats) {
+    if (!dg_plan_bf16(pb) || !dg_plan_bf16(pl) || (Cout % pb.CK) || pl.packedFloats != 4 * pb.packedFloats) {
       dg_set_error("op_conv2d_bwd_data_bf16s: the gathered 1x1 form does not cover %d -> %d", Cout, Cin);
       return DG_ERR_UNSUPPORTED;
     }

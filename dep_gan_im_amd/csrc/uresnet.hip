@@ -180,19 +180,10 @@ static int u_forward_train(depgan_ctx* c, const float* x, const float* z, int n,
   for (size_t i = 0; i < c->gl.size(); ++i) {
     GLayer& L = c->gl[i];
     if (L.kind == G_CONV || L.kind == G_FILM) {
-      ConvArgs a;
-      memset(&a, 0, sizeof(a));
-      zero_ep(&a.ep);
-      a.in = (i == 0) ? make_view(const_cast<float*>(x), L.H, L.W, L.Cin) : L.in;
-      a.out = L.raw.view();
-      a.B = n; a.H = L.H; a.W = L.W; a.Cin = L.Cin; a.Cout = L.Cout;
+      ConvArgs a = conv_args((i == 0) ? make_view(const_cast<float*>(x), L.H, L.W, L.Cin) : L.in, L.raw.view(),
+                             n, L.H, L.W, L.Cin, L.Cout);
       a.ep.bias = L.b;
-      if (L.pf.variant >= 0) {
-        a.w = L.wpf[0];
-      } else {
-        a.w = L.Wt;
-        a.wsT = (long)L.Cin * L.Cout; a.wsI = L.Cout; a.wsO = 1; a.flip = 0;
-      }
+      conv_set_weights(&a, L.pf, L.wpf[0], L.Wt, L.Cin, L.Cout);
       DGCHECK(conv_launch(c, L.pf, a, 3));
       DGCHECK(u_bn_act(c, L, L.H, L.W, n, drop_seed));
     } else if (L.kind == G_POOL) {
@@ -200,12 +191,7 @@ static int u_forward_train(depgan_ctx* c, const float* x, const float* z, int n,
       DGCHECK(dg_maxpool(c->gl[L.skip_of].out, L.out, n, L.H / 2, L.W / 2, L.Cout, c->st));
     } else if (L.kind == G_DECONV) {
       for (int t = 0; t < 4 && !deconv_fused(c, L, n); ++t) {
-        ConvArgs a;
-        memset(&a, 0, sizeof(a));
-        zero_ep(&a.ep);
-        a.in = L.in;
-        a.out = strided2(L.raw.view(), t / 2, t % 2);
-        a.B = n; a.H = L.H; a.W = L.W; a.Cin = L.Cin; a.Cout = L.Cout;
+        ConvArgs a = conv_args(L.in, strided2(L.raw.view(), t / 2, t % 2), n, L.H, L.W, L.Cin, L.Cout);
         a.ep.bias = L.b;
         a.w = L.wpf[t];
         DGCHECK(conv_launch(c, L.pf, a, 1));
@@ -220,19 +206,10 @@ static int u_forward_train(depgan_ctx* c, const float* x, const float* z, int n,
 // 1x1 head to 4 logits (direct kernel: N = 4 is far below an MFMA tile)
 static int u_head_logits(depgan_ctx* c, int n) {
   GLayer& L = c->gl.back();
-  ConvArgs a;
-  memset(&a, 0, sizeof(a));
-  zero_ep(&a.ep);
-  a.in = L.in;
-  a.out = make_view(c->logits, L.H, L.W, 4);
-  a.B = n; a.H = L.H; a.W = L.W; a.Cin = L.Cin; a.Cout = 4;
+  ConvArgs a = conv_args(L.in, make_view(c->logits, L.H, L.W, 4), n, L.H, L.W, L.Cin, 4);
   a.ep.bias = L.b;
-  a.w = L.Wt;
-  a.wsT = (long)L.Cin * 4; a.wsI = 4; a.wsO = 1;
-  ConvPlan none = {};
-  memset(&none, 0, sizeof(none));
-  none.variant = -1;
-  return conv_launch(c, none, a, 1);
+  conv_set_weights(&a, dg_plan_direct(), nullptr, L.Wt, L.Cin, 4);
+  return conv_launch(c, dg_plan_direct(), a, 1);
 }
 
 // BN backward of one layer: dy (grad at the BN output, ReLU / FiLM already applied) -> dRAW in draw_tmp,
@@ -256,13 +233,8 @@ static int u_conv_bwd(depgan_ctx* c, GLayer& L, size_t li, const float* x_user, 
   const ColSum cs = {n, nullptr, L.db, nullptr};
   DGCHECK(wgrad_full(c, 3, xin, draw, n, L.H, L.W, L.Cin, L.Cout, nullptr, L.dW, nullptr, 0, 0, &cs));
   if (li == 0) return DG_OK;
-  ConvArgs a;
-  memset(&a, 0, sizeof(a));
-  zero_ep(&a.ep);
-  a.in = draw;
-  a.out = L.din;
+  ConvArgs a = conv_args(draw, L.din, n, L.H, L.W, L.Cout, L.Cin);
   a.w = L.wpb[0];
-  a.B = n; a.H = L.H; a.W = L.W; a.Cin = L.Cout; a.Cout = L.Cin;
   a.ep.res = res;
   a.ep.mask = L.in_mask;
   return conv_launch(c, L.pb, a, 3);
@@ -275,19 +247,10 @@ static int u_backward(depgan_ctx* c, const float* x, const float* z, int n) {
       TView dzv = make_view(c->dz, L.H, L.W, 4);
       const ColSum cs = {n, nullptr, L.db, nullptr};
       DGCHECK(wgrad_full(c, 1, L.in, dzv, n, L.H, L.W, L.Cin, 4, nullptr, L.dW, nullptr, 0, 0, &cs));
-      ConvArgs a;
-      memset(&a, 0, sizeof(a));
-      zero_ep(&a.ep);
-      a.in = dzv;
-      a.out = L.din;
-      a.B = n; a.H = L.H; a.W = L.W; a.Cin = 4; a.Cout = L.Cin;
-      a.w = L.Wt;                               // W[ci][co] read as (k = co, n = ci)
-      a.wsT = (long)L.Cin * 4; a.wsI = 1; a.wsO = 4;
+      ConvArgs a = conv_args(dzv, L.din, n, L.H, L.W, 4, L.Cin);
+      conv_set_weights_bwd(&a, dg_plan_direct(), nullptr, L.Wt, L.Cin, 4);   // W[ci][co] read as (k = co, n = ci)
       a.ep.mask = L.in_mask;
-      ConvPlan none = {};
-      memset(&none, 0, sizeof(none));
-      none.variant = -1;
-      DGCHECK(conv_launch(c, none, a, 1));
+      DGCHECK(conv_launch(c, dg_plan_direct(), a, 1));
     } else if (L.kind == G_CONV) {
       const float k = (L.name == kDropLayer && c->last_drop_seed) ? 1.0f / (1.0f - kDropRate) : 1.0f;
       DGCHECK(u_conv_bwd(c, L, (size_t)i, x, L.dout, null_view(), n, k));

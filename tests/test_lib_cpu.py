@@ -177,7 +177,7 @@ def test_every_step_reduction_call_passes_its_scratch_capacity():
     depgan_op_* entries: the scratch they allocate and its capacity), and each declares its capacity argument and a
     *_scratch size helper."""
     model_calls = set()
-    for f in ("model.hip", "uresnet.hip"):
+    for f in ("model.hip", "op_entries.hip", "uresnet.hip"):
         src = open(os.path.join(ROOT, "dep_gan_im_amd", "csrc", f)).read()
         for name, args in re.findall(r"\b(%s)\s*\(([^;]*)\);" % "|".join(SCRATCH_REDUCTIONS), src):
             args = [a.strip() for a in args.replace("\n", " ").split(",")]
