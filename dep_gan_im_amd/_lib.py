@@ -38,6 +38,7 @@ EXPORTS = [
     "depgan_op_conv2d_film_train_bf16s", "depgan_op_conv2d_wgrad_bf16s", "depgan_op_conv2d_bwd_data_bf16s",
     "depgan_op_unpool_mask_bf16s", "depgan_op_film_bwd_bf16s", "depgan_op_head_bwd_bf16s",
     "depgan_op_conv2d_fused", "depgan_op_deconv2x2_igemm", "depgan_op_conv2d_wgrad_ex",
+    "depgan_set_critic16_pipe", "depgan_get_critic16_pipe",
 ]
 
 ABI_VERSION = 3          # DEPGAN_ABI_VERSION of the include/depgan.h this binding was written against
@@ -209,6 +210,8 @@ def load():
     # bf16 storage for the generator update: setter, debug surface and the operators of its backward
     lib.depgan_set_g_update_storage.argtypes = [vp, i]
     lib.depgan_get_g_update_storage.argtypes = [vp]
+    lib.depgan_set_critic16_pipe.argtypes = [vp, i]
+    lib.depgan_get_critic16_pipe.argtypes = [vp]
     lib.depgan_debug_film_decision_bf16s.argtypes = [vp, C.c_char_p, vp, L, ip]
     lib.depgan_op_conv2d_film_train_bf16s.argtypes = ([vp, L, L, L] + [vp] * 6 + [i] + [vp, L, L, L] * 2 + [vp, vp] +
                                                       [i] * 6 + [vp])

@@ -223,7 +223,7 @@ enum ConvFamily {
 };
 struct ConvPlan {
   int KS, Cin, Cout;
-  int MF;    // MFMA tile edge: 32 (v_mfma_f32_32x32x2_f32) or 16 (v_mfma_f32_16x16x4_f32)
+  int MF;    // MFMA tile edge: 32 (v_mfma_f32_32x32x2_f32) or 16 (v_mfma_f32_16x16x4_f32); bf16 plans: 32x32x16 or 16x16x32
   int NT;    // output channels per workgroup
   int CK;    // input channels staged per LDS chunk
   int nNT, nCC;
@@ -253,6 +253,11 @@ ConvPlan dg_plan_conv(int KS, int Cin, int Cout);
 ConvPlan dg_plan_conv_items(int KS, int Cin, int Cout, long items);
 // the bf16 plan where the bf16 kernel covers the shape (Cout % 32 == 0, Cin >= 8), else the fp32 plan
 ConvPlan dg_plan_conv_bf16(int KS, int Cin, int Cout);
+// the 16-output-channel 5x5 form of the bf16 plan (MF = NT = 16, CK = 32): KS == 5, Cout % 16 == 0, Cin >= 8,
+// Cin % 4 == 0; else the fp32 plan.  Opt-in per context (depgan_set_critic16_pipe) and operator path 10
+ConvPlan dg_plan_conv_bf16_n16(int KS, int Cin, int Cout);
+// name of the instantiation dg_conv_igemm_bf16 launches for a CONV_BF16 plan, as rocprofv3 prints it
+const char* dg_conv_igemm_bf16_name(const ConvPlan& pl);
 // fp32 operands split into `planes` (2 or 3) bf16 terms each, 3 or 6 products on the bf16 pipe (igemm_split_kernel)
 ConvPlan dg_plan_conv_split(int KS, int Cin, int Cout, int planes);
 int dg_conv_igemm_bf16(const ConvPlan& pl, const ConvArgs& a, hipStream_t st);

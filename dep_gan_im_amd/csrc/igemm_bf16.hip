@@ -34,6 +34,27 @@ __global__ __launch_bounds__(256, 2) void igemm_bf16_kernel(const ConvArgs a) {
 #include "igemm_epilogue.inc"
 }
 
+// 16 output channels per workgroup (the critics' 16-channel 5x5 layers, dg_plan_conv_bf16_n16): the same text with
+// v_mfma_f32_16x16x32_bf16 -- 16 channels x 16 pixels, K = 32 = the whole chunk in ONE MFMA per tap and pixel tile.  Each
+// wave owns the same 4 x 16 pixels as four 16-pixel tiles (f32x4 accumulators, 16 VGPRs); lane (r = lane & 15,
+// h = lane >> 4) reads the 16 bytes [8h, 8h + 8) of LDS row r for both operands, and with the weight fragment first the
+// result is D[channel][pixel] (col = lane & 15 = pixel, row = 4 (lane >> 4) + reg = channel): the C/D layout of
+// v_mfma_f32_16x16x4_f32, i.e. what the shared epilogue's MF == 16 form expects.  With Cin = 16 half of every MFMA's K is
+// zero padding; the contraction is still a fraction of the HBM time.  The K order is chunk, then
+// tap, whatever TAPG: the bits do not depend on the tap grouping, the occupancy or the number of samples in the launch.
+// TAPG / OCC: taps per weight stage and the workgroups per CU the registers are budgeted for (a measured choice,
+// profiles/critic16_pipe_experiments.md).  No gathered K (the launcher refuses ConvArgs::cpt), no fused head.
+template <int KS, int TAPG, int OCC>
+__global__ __launch_bounds__(256, OCC) void igemm_bf16_n16_kernel(const ConvArgs a) {
+  constexpr int MF = 16, NT = 16, MT = 4, CK = 32;
+#define IGEMM_X_BF16 0
+#define IGEMM_MF 16
+#include "igemm_bf16_main.inc"
+#undef IGEMM_MF
+#undef IGEMM_X_BF16
+#include "igemm_epilogue.inc"
+}
+
 // ---------------------------------------------------------------------------
 // fp32 operands on the bf16 matrix pipe: split products
 // ---------------------------------------------------------------------------
@@ -243,6 +264,24 @@ ConvPlan dg_plan_conv_bf16(int KS, int Cin, int Cout) {
   return p;
 }
 
+// The 16-output-channel 5x5 form of the bf16 plan (igemm_bf16_n16_kernel): Cout a multiple of 16, Cin >= 8 and a multiple
+// of 4; anything else keeps the fp32 plan.  A plan function of its own: dg_plan_conv_bf16 returns what it always did,
+// and a context takes this plan only where it was asked to (depgan_set_critic16_pipe).
+ConvPlan dg_plan_conv_bf16_n16(int KS, int Cin, int Cout) {
+  ConvPlan p = dg_plan_conv(KS, Cin, Cout);
+  if (!dg_plan_mfma(p) || KS != 5 || (Cout % 16) != 0 || Cin < 8 || (Cin % 4) != 0) return p;
+  p.family = CONV_BF16;
+  p.planes = 1;
+  p.MF = 16;
+  p.NT = 16;
+  p.CK = 32;
+  p.nNT = cdiv(Cout, 16);
+  p.nCC = cdiv(Cin, 32);
+  const size_t elems = (size_t)p.nNT * p.nCC * KS * KS * p.NT * p.CK;   // [nt][cc][tap][n = 16][k = 32]
+  p.packedFloats = (elems + 1) / 2;     // bf16 elements, counted in 4-byte units for the allocator
+  return p;
+}
+
 // split plans: 2 or 3 planes; Cin a multiple of 4 and >= 8 like the bf16 plans; Cout a multiple of 16 --
 // a 16-channel layer (the critics' first 5x5 convolutions) runs as half of a 32-channel tile with zero weight rows: twice
 // the MFMAs it needs, still a third of the cycles the fp32 pipe's 16x16x4 form takes for it
@@ -306,7 +345,61 @@ static int launch_bf16(const ConvArgs& a, hipStream_t st) {
   return DG_OK;
 }
 
+// Tap grouping and occupancy of the 16-channel kernel.  Shipped: all 25 taps of a chunk staged at once (64 KB, one
+// barrier pair per chunk), two workgroups per CU.  DEPGAN_BF16_N16_VARIANT=1 / 2 (A/B measurements only) select five taps
+// per stage (38 KB, 163 VGPRs): 1 at the three workgroups per CU that allows, 2 held at two per CU by asking for the
+// shipped variant's LDS size, so that tap grouping and occupancy can be told apart; every variant computes the same bits.
+static int bf16_n16_variant() {
+  static const int v = [] {
+    const char* e = getenv("DEPGAN_BF16_N16_VARIANT");
+    const int x = e ? atoi(e) : 0;
+    return (x == 1 || x == 2) ? x : 0;
+  }();
+  return v;
+}
+
+template <int KS, int TAPG, int OCC, int LDS_TAPS = TAPG>
+static int launch_bf16_n16(const ConvArgs& a, hipStream_t st) {
+  constexpr int TW = 16 + KS - 1;
+  constexpr size_t lds_k = (size_t)(TW * TW + LDS_TAPS * 16) * 80;   // LDS_TAPS > TAPG: unused LDS that limits the occupancy
+  constexpr size_t lds_e = (size_t)4 * 64 * (16 + 4) * sizeof(float);
+  constexpr size_t lds = lds_k > lds_e ? lds_k : lds_e;
+  if (a.cpt > 0 || a.ep.head_out) {
+    dg_set_error("dg_conv_igemm_bf16: the 16-channel kernel has no gathered K and no fused head");
+    return DG_ERR_ARG;
+  }
+  static DgOncePerDevice once;
+  if (once.need()) {
+    HIPCHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&igemm_bf16_n16_kernel<KS, TAPG, OCC>),
+                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  }
+  ConvArgs b = a;
+  b.lgx = cdiv(a.W, 16) * cdiv(a.H, 16) * a.B;
+  b.lgy = cdiv(a.Cout, 16) * (a.groups > 1 ? a.groups : 1);
+  const long total = (long)b.lgx * b.lgy;
+  hipLaunchKernelGGL((igemm_bf16_n16_kernel<KS, TAPG, OCC>), dim3((unsigned)total), dim3(256), lds, st, b);
+  HIPCHECK(hipGetLastError());
+  return DG_OK;
+}
+
+const char* dg_conv_igemm_bf16_name(const ConvPlan& pl) {
+  if (!dg_plan_bf16(pl) || pl.MF != 16) return "igemm_bf16_kernel";
+  switch (bf16_n16_variant()) {
+    case 1:
+    case 2: return "igemm_bf16_n16_kernel<5,5,2>";
+  }
+  return "igemm_bf16_n16_kernel<5,25,2>";
+}
+
 int dg_conv_igemm_bf16(const ConvPlan& pl, const ConvArgs& a, hipStream_t st) {
+  if (dg_plan_bf16(pl) && pl.MF == 16) {
+    if (pl.KS != 5) { dg_set_error("dg_conv_igemm_bf16: the 16-channel kernel is a 5x5 kernel, KS=%d", pl.KS); return DG_ERR_UNSUPPORTED; }
+    switch (bf16_n16_variant()) {
+      case 1: return launch_bf16_n16<5, 5, 2>(a, st);
+      case 2: return launch_bf16_n16<5, 5, 2, 25>(a, st);
+    }
+    return launch_bf16_n16<5, 25, 2>(a, st);
+  }
   if (dg_plan_split(pl) && pl.planes == 3) switch (pl.KS) {
     case 3: return launch_split<3, 9, 3>(a, st);
     case 5: return launch_split<5, 5, 3>(a, st);

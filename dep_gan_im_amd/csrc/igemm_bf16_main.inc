@@ -6,6 +6,14 @@
 // One hook, the form of the activation operand in HBM:
 //   IGEMM_X_BF16 = 0: fp32 (TView), rounded to bf16 (RNE) while the halo tile is committed, K gathered by ConvArgs::cpt
 //   IGEMM_X_BF16 = 1: bf16 (TViewH), copied; Cin is a multiple of 8 (launcher); no gathered K
+// and one for the MFMA shape (not defined = 32):
+//   IGEMM_MF = 32: v_mfma_f32_32x32x16_bf16, 32 channels x 32 pixels (two image rows of the tile), two per 32-channel chunk
+//   IGEMM_MF = 16: v_mfma_f32_16x16x32_bf16, 16 channels x 16 pixels (one image row), one per chunk; included after
+//                  `constexpr int NT = 16, MT = 4, CK = 32;` (igemm_bf16_n16_kernel, the critics' 16-channel 5x5 layers)
+#ifndef IGEMM_MF
+#define IGEMM_MF 32
+#define IGEMM_MF_DEFAULTED
+#endif
   constexpr int PAD = KS / 2;
   constexpr int TW = 16 + KS - 1;
   constexpr int PIXT = TW * TW;
@@ -23,7 +31,13 @@
   constexpr int WTOT = TAPG * NT * WV;
   constexpr int WPIECES = (WTOT + 255) / 256;
   static_assert(NTAPS % TAPG == 0, "tap grouping");
+#if IGEMM_MF == 16
+  typedef f32x4 acc_t;
+  constexpr int NACC = 4, KM = 32;   // accumulator registers, K of one MFMA
+#else
   typedef f32x16 acc_t;
+  constexpr int NACC = 16, KM = 16;
+#endif
 
   extern __shared__ __attribute__((aligned(16))) float smem[];
   char* xs = reinterpret_cast<char*>(smem);      // [PIXT][ROWB]
@@ -148,11 +162,19 @@
   };
 
   const int lane = tid & 63, wv = tid >> 6;
+#if IGEMM_MF == 16
+  const int r = lane & 15, h = lane >> 4;   // h: which 8 of the 32 k-values of an MFMA this lane carries
+#else
   const int r = lane & 31, h = lane >> 5;   // h: which 8 of the 16 k-values of an MFMA this lane carries
+#endif
   int apix[MT];
 #pragma unroll
   for (int mt = 0; mt < MT; ++mt) {
+#if IGEMM_MF == 16
+    const int py = 4 * wv + mt, px = r;
+#else
     const int py = 4 * wv + 2 * mt + (r >> 4), px = r & 15;
+#endif
     apix[mt] = (py * TW + px) * ROWB + 16 * h;
   }
   const int boff = r * ROWB + 16 * h;
@@ -161,7 +183,7 @@
 #pragma unroll
   for (int mt = 0; mt < MT; ++mt)
 #pragma unroll
-    for (int j = 0; j < 16; ++j) acc[mt][j] = 0.f;
+    for (int j = 0; j < NACC; ++j) acc[mt][j] = 0.f;
 
   prefetch(0);
   for (int s = 0; s < NS; ++s) {
@@ -176,14 +198,22 @@
       const int ty = tap / KS, tx = tap - ty * KS;
       const int tapoff = (ty * TW + tx) * ROWB;
 #pragma unroll
-      for (int sub = 0; sub < CK / 16; ++sub) {
-        const bf16x8 bw = *reinterpret_cast<const bf16x8*>(ws + tl * (NT * ROWB) + boff + 32 * sub);
+      for (int sub = 0; sub < CK / KM; ++sub) {
+        const bf16x8 bw = *reinterpret_cast<const bf16x8*>(ws + tl * (NT * ROWB) + boff + 2 * KM * sub);
 #pragma unroll
         for (int mt = 0; mt < MT; ++mt) {
-          const bf16x8 ax = *reinterpret_cast<const bf16x8*>(xs + apix[mt] + tapoff + 32 * sub);
+          const bf16x8 ax = *reinterpret_cast<const bf16x8*>(xs + apix[mt] + tapoff + 2 * KM * sub);
           // weight fragment first: D[channel][pixel], the layout the shared epilogue expects
+#if IGEMM_MF == 16
+          acc[mt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bw, ax, acc[mt], 0, 0, 0);
+#else
           acc[mt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(bw, ax, acc[mt], 0, 0, 0);
+#endif
         }
       }
     }
   }
+#ifdef IGEMM_MF_DEFAULTED
+#undef IGEMM_MF
+#undef IGEMM_MF_DEFAULTED
+#endif

@@ -508,7 +508,7 @@ void dg_conv_igemm_name(const ConvPlan& pl, const ConvArgs& a, char* buf, size_t
   if (cap) buf[0] = 0;
   if (!dg_plan_mfma(pl)) { snprintf(buf, cap, "conv_direct"); return; }
   if (dg_plan_split(pl)) { snprintf(buf, cap, "igemm_split_kernel"); return; }
-  if (dg_plan_bf16(pl)) { snprintf(buf, cap, "igemm_bf16_kernel"); return; }
+  if (dg_plan_bf16(pl)) { snprintf(buf, cap, "%s", dg_conv_igemm_bf16_name(pl)); return; }
   if (dg_plan_wino(pl)) { snprintf(buf, cap, "%s", dg_conv_wino_name(a)); return; }
   if (dg_conv_igemm_wp_supported(pl, a, false)) { snprintf(buf, cap, "igemm_wp_kernel<0>"); return; }
   if (dg_conv_igemm_ws5_supported(pl, a, false)) { snprintf(buf, cap, "%s", dg_conv_igemm_ws5_name(pl)); return; }

@@ -88,6 +88,10 @@ struct DLayer {
   int KS, Cin, Cout, H, W;  // H, W: spatial size at this layer
   bool pool;
   ConvPlan pf, pb;
+  // depgan_set_critic16_pipe: the 16-channel bf16 plans of the launches the bf16 plan above leaves on the fp32 pipe
+  // (dis_0b forward, dis_0b / dis_1a backward-data); has16f / has16b say where one exists (bf16_mfma contexts only)
+  ConvPlan pf16, pb16;
+  bool has16f = false, has16b = false;
 };
 
 struct DNet {
@@ -97,6 +101,8 @@ struct DNet {
   unsigned pack_blocks = 0;
   float* wpf[11];
   float* wpb[11];
+  float* wpf16[11];                // panels of DLayer::pf16 / pb16 (null where the layer has none); packed with the others
+  float* wpb16[11];
   float *W[11], *b[11], *dW[11], *db[11];
   float *w9, *b9, *wd, *bd, *dw9, *db9, *dwd, *dbd;
 };
@@ -214,6 +220,9 @@ struct depgan_ctx {
   std::vector<TViewH> h_u;
   std::vector<unsigned char*> h_dec;
   bool hu_ready = false, hu_valid = false;
+
+  // depgan_set_critic16_pipe(1): the critics' 16-channel 5x5 launches on igemm_bf16_n16_kernel (DLayer::pf16 / pb16)
+  bool critic16_bf16 = false;
 
   // ---- profiling ----
   bool prof_on = false;

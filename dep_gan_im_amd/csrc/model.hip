@@ -612,6 +612,13 @@ static int build_critics(depgan_ctx* c) {
     L.W = W;
     L.pf = plan_conv(c, L.KS, L.Cin, L.Cout, 96, H, W);     // the critics mostly run on [real | fake | mixed]
     L.pb = plan_conv(c, L.KS, L.Cout, L.Cin, 96, H, W);
+    if (c->cfg.bf16_mfma) {
+      // the launches dg_plan_conv_bf16 leaves on the fp32 pipe for their 16 output channels: both plans, both panels
+      L.pf16 = dg_plan_conv_bf16_n16(L.KS, L.Cin, L.Cout);
+      L.pb16 = dg_plan_conv_bf16_n16(L.KS, L.Cout, L.Cin);
+      L.has16f = dg_plan_mfma(L.pf) && !dg_plan_bf16(L.pf) && dg_plan_bf16(L.pf16);
+      L.has16b = l > 0 && dg_plan_mfma(L.pb) && !dg_plan_bf16(L.pb) && dg_plan_bf16(L.pb16);
+    }
     DGCHECK(talloc(c, &c->d_act[l], c->NB3, H, W, L.Cout));
     DGCHECK(talloc(c, &c->d_dz[l], c->NB3, H, W, L.Cout));
     if (L.pool) {
@@ -653,6 +660,9 @@ static int build_critics(depgan_ctx* c) {
       D.wpf[l] = D.wpb[l] = nullptr;
       if (dg_plan_mfma(c->dl[l].pf)) DGCHECK(dmalloc(c, &D.wpf[l], c->dl[l].pf.packedFloats));
       if (dg_plan_mfma(c->dl[l].pb)) DGCHECK(dmalloc(c, &D.wpb[l], c->dl[l].pb.packedFloats));
+      D.wpf16[l] = D.wpb16[l] = nullptr;
+      if (c->dl[l].has16f) DGCHECK(dmalloc(c, &D.wpf16[l], c->dl[l].pf16.packedFloats));
+      if (c->dl[l].has16b) DGCHECK(dmalloc(c, &D.wpb16[l], c->dl[l].pb16.packedFloats));
     }
     D.w9 = n.p("dis_9/kernel"); D.b9 = n.p("dis_9/bias"); D.wd = n.p("dense_1/kernel"); D.bd = n.p("dense_1/bias");
     D.dw9 = n.g("dis_9/kernel"); D.db9 = n.g("dis_9/bias"); D.dwd = n.g("dense_1/kernel"); D.dbd = n.g("dense_1/bias");
@@ -763,6 +773,16 @@ static int refresh_critic(depgan_ctx* c, DNet& D) {
       }
       if (D.wpb[l]) {
         DGCHECK(dg_pack_job(L.pb, D.W[l], L.Cin, L.Cout, 0, 1, 1, nullptr, D.wpb[l], 0, &j));
+        jobs.push_back(j);
+      }
+      // depgan_set_critic16_pipe: both panels of those launches are kept up to date whatever the setting (a few KB in
+      // the same launch), so that switching needs no call and no refresh
+      if (D.wpf16[l]) {
+        DGCHECK(dg_pack_job(L.pf16, D.W[l], L.Cin, L.Cout, 0, 0, 0, nullptr, D.wpf16[l], 0, &j));
+        jobs.push_back(j);
+      }
+      if (D.wpb16[l]) {
+        DGCHECK(dg_pack_job(L.pb16, D.W[l], L.Cin, L.Cout, 0, 1, 1, nullptr, D.wpb16[l], 0, &j));
         jobs.push_back(j);
       }
     }
@@ -927,6 +947,20 @@ static TView d_in_view(depgan_ctx* c, int l, long s0) {  // input tensor of crit
   return view_offset(t.view(), s0);
 }
 
+// plan and panel of critic layer l's forward / backward-data launch under the context's critic16 setting
+static const ConvPlan& d_plan_f(const depgan_ctx* c, int l) {
+  return (c->critic16_bf16 && c->dl[l].has16f) ? c->dl[l].pf16 : c->dl[l].pf;
+}
+static const float* d_panel_f(const depgan_ctx* c, const DNet& D, int l) {
+  return (c->critic16_bf16 && c->dl[l].has16f) ? D.wpf16[l] : D.wpf[l];
+}
+static const ConvPlan& d_plan_b(const depgan_ctx* c, int l) {
+  return (c->critic16_bf16 && c->dl[l].has16b) ? c->dl[l].pb16 : c->dl[l].pb;
+}
+static const float* d_panel_b(const depgan_ctx* c, const DNet& D, int l) {
+  return (c->critic16_bf16 && c->dl[l].has16b) ? D.wpb16[l] : D.wpb[l];
+}
+
 static int d_forward(depgan_ctx* c, DNet& D, const float* img, long s0, int N) {
   const int H0 = c->cfg.height, W0 = c->cfg.width;
   for (int l = 0; l < 11; ++l) {
@@ -935,10 +969,11 @@ static int d_forward(depgan_ctx* c, DNet& D, const float* img, long s0, int N) {
                            view_offset(c->d_act[l].view(), s0), N, L.H, L.W, L.Cin, L.Cout);
     a.ep.bias = D.b[l];
     a.ep.relu = 1;
-    conv_set_weights(&a, L.pf, D.wpf[l], D.W[l], L.Cin, L.Cout);
-    if (dg_plan_mfma(L.pf) && L.pool && !((L.H | L.W) & 1))
+    const ConvPlan& pf = d_plan_f(c, l);
+    conv_set_weights(&a, pf, d_panel_f(c, D, l), D.W[l], L.Cin, L.Cout);
+    if (dg_plan_mfma(pf) && L.pool && !((L.H | L.W) & 1))
       a.ep.pool = view_offset(c->d_pool[l].view(), s0);   // pooled in the epilogue
-    DGCHECK(conv_launch(c, L.pf, a, L.KS));
+    DGCHECK(conv_launch(c, pf, a, L.KS));
     if (L.pool && !a.ep.pool.p) {
       ProfScope ps(c, 2, 0.0, "maxpool");
       DGCHECK(dg_maxpool(a.out, view_offset(c->d_pool[l].view(), s0), N, L.H / 2, L.W / 2, L.Cout, c->st));
@@ -966,14 +1001,14 @@ static int d_backward_chain(depgan_ctx* c, DNet& D, long s0, int N, const float*
     const DLayer& L = c->dl[l];
     const DLayer& Pv = c->dl[l - 1];
     ConvArgs a = conv_args(view_offset(c->d_dz[l].view(), s0), null_view(), N, L.H, L.W, L.Cout, L.Cin);
-    a.w = D.wpb[l];
+    a.w = d_panel_b(c, D, l);
     if (Pv.pool) {
       a.out = view_offset(c->d_dpool[l - 1].view(), s0);
     } else {
       a.out = view_offset(c->d_dz[l - 1].view(), s0);
       a.ep.mask = view_offset(c->d_act[l - 1].view(), s0);
     }
-    DGCHECK(conv_launch(c, L.pb, a, L.KS));
+    DGCHECK(conv_launch(c, d_plan_b(c, l), a, L.KS));
     if (Pv.pool) {
       ProfScope ps(c, 2, 0.0, "unpool+mask");
       DGCHECK(dg_unpool_mask(a.out, view_offset(c->d_act[l - 1].view(), s0), null_view(),
@@ -1041,8 +1076,8 @@ static int critic_enqueue(depgan_ctx* c, int which, const float* y2, const float
     ConvArgs a = conv_args((l == 0) ? make_view(u0, H0, W0, 1) : d_in_view(c, l, 2 * B),
                            L.pool ? make_view(c->d_ufull.p, L.H, L.W, L.Cout) : act, B, L.H, L.W, L.Cin, L.Cout);
     a.ep.mask = act;
-    conv_set_weights(&a, L.pf, D.wpf[l], D.W[l], L.Cin, L.Cout);
-    DGCHECK(conv_launch(c, L.pf, a, L.KS));
+    conv_set_weights(&a, d_plan_f(c, l), d_panel_f(c, D, l), D.W[l], L.Cin, L.Cout);
+    DGCHECK(conv_launch(c, d_plan_f(c, l), a, L.KS));
     if (L.pool) {
       ProfScope ps(c, 2, 0.0, "gather pool");
       DGCHECK(dg_gather_pool(a.out, act, view_offset(c->d_pool[l].view(), 2 * B), B, L.H / 2, L.W / 2, L.Cout,
@@ -1526,6 +1561,24 @@ int depgan_weights_changed(depgan_ctx* c, int net) {
   dg_set_error("unknown net id %d", net);
   return DG_ERR_ARG;
 }
+
+// the critics' 16-channel 5x5 launches on the bf16 pipe (include/depgan.h): a flag the critic launches read; both
+// plans and both panels exist in every bf16_mfma context, so nothing is allocated or packed here
+int depgan_set_critic16_pipe(depgan_ctx* c, int pipe) {
+  if (!c) { dg_set_error("depgan_set_critic16_pipe: null context"); return DG_ERR_ARG; }
+  if (pipe != 0 && pipe != 1) {
+    dg_set_error("depgan_set_critic16_pipe: pipe must be 0 (fp32) or 1 (bf16), got %d", pipe);
+    return DG_ERR_ARG;
+  }
+  if (pipe == 1 && (!c->cfg.bf16_mfma || c->dl.empty())) {
+    dg_set_error("depgan_set_critic16_pipe: the bf16 pipe for the critics' 16-channel layers needs a context created with "
+                 "bf16_mfma = 1 (and critics: nc_out = 1)");
+    return DG_ERR_UNSUPPORTED;
+  }
+  c->critic16_bf16 = pipe == 1;
+  return DG_OK;
+}
+int depgan_get_critic16_pipe(depgan_ctx* c) { return (c && c->critic16_bf16) ? 1 : 0; }
 
 int depgan_g_forward(depgan_ctx* c, const float* x, const float* z, float* out, int n) {
   if (n < 1 || n > c->cfg.batch) { dg_set_error("g_forward: n must be in [1, batch]"); return DG_ERR_ARG; }

@@ -19,6 +19,14 @@ static int op_conv_run(ConvArgs a, const float* w_hwio, int Cin, int Cout, int K
                 : (path == 4 || path == 5) ? dg_plan_conv_split(KS, ci, co, path == 5 ? 3 : 2)
                 : (path == 6) ? dg_plan_conv_items(KS, ci, co, 1L << 30) : dg_plan_conv(KS, ci, co);
   if (path == 7) pl = dg_plan_conv_items(KS, ci, co, 1L << 30);
+  if (path == 10) {
+    // the 16-output-channel 5x5 form of 3: decided before any HIP call, as path 9
+    if (KS != 5) { dg_set_error("op_conv: path 10 is the 16-channel 5x5 bf16 kernel, KS must be 5"); return DG_ERR_ARG; }
+    if (!a.in.p || !a.out.p || !w_hwio) { dg_set_error("op_conv: null operand"); return DG_ERR_ARG; }
+    if (a.ep.head_w || a.ep.head_b || a.ep.head_out) { dg_set_error("op_conv: path 10 has no fused head"); return DG_ERR_ARG; }
+    pl = dg_plan_conv_bf16_n16(KS, ci, co);
+    if (!dg_plan_bf16(pl) || pl.MF != 16) { dg_set_error("op_conv: the 16-channel bf16 kernel does not cover a launch of %d -> %d channels", ci, co); return DG_ERR_UNSUPPORTED; }
+  }
   if (path == 8) {
     pl = (KS == 3) ? dg_plan_conv_wino(ci, co) : pl;
     if (!dg_plan_wino(pl) || !dg_conv_wino_supported(pl, a)) { dg_set_error("op_conv: the Winograd kernel does not cover this shape"); return DG_ERR_UNSUPPORTED; }
@@ -246,7 +254,7 @@ int depgan_op_conv2d_fused(const float* in, long isB, long isY, long isX, const 
   }
   if ((head_w || head_b || head_out) && !(head_w && head_b && head_out)) { dg_set_error("op_conv2d_fused: null head argument"); return DG_ERR_ARG; }
   if (head_skip_out && !head_out) { dg_set_error("op_conv2d_fused: head_skip_out without a head"); return DG_ERR_ARG; }
-  if (path < 1 || path > 9) { dg_set_error("op_conv2d_fused: path must be 1 ... 9"); return DG_ERR_ARG; }
+  if (path < 1 || path > 10) { dg_set_error("op_conv2d_fused: path must be 1 ... 10"); return DG_ERR_ARG; }
   ConvArgs a = conv_args(op_view(in, isB, isY, isX), op_view(out, osB, osY, osX), B, H, W, bwd ? Cout : Cin, co);
   Epilogue& e = a.ep;
   e.bias = bias; e.scale = scale; e.shift = shift;

@@ -305,6 +305,26 @@ class Engine:
                   "depgan_set_g_update_storage")
         self._g_update_storage = value
 
+    @property
+    def critic16_pipe(self):
+        """The matrix pipe of the critics' 16-channel 5x5 launches (dis_0b forward, its u-forward and backward-data,
+        dis_1a backward-data): "float32" (default: the fp32 MFMA kernel, as every bf16_mfma engine ran them before) or
+        "bfloat16" (bf16_mfma engines only; depgan_set_critic16_pipe): both operands rounded to bf16 while staged, fp32
+        accumulation, like every other convolution of such an engine.  Every rank of a data-parallel job must use the
+        same value."""
+        return getattr(self, "_critic16_pipe", "float32")
+
+    @critic16_pipe.setter
+    def critic16_pipe(self, value):
+        if value not in ("float32", "bfloat16"):
+            raise ValueError("critic16_pipe must be 'float32' or 'bfloat16', got %r" % (value,))
+        if value == "bfloat16" and not (self.cfg.bf16_mfma and self.cfg.nc_out in (0, 1)):
+            raise ValueError("critic16_pipe='bfloat16' needs an engine created with bf16_mfma=True (and nc_out=1); "
+                             "this one has bf16_mfma=%d, nc_out=%d" % (self.cfg.bf16_mfma, self.cfg.nc_out))
+        if getattr(self, "h", None):
+            check(self.lib.depgan_set_critic16_pipe(self.h, 1 if value == "bfloat16" else 0), "depgan_set_critic16_pipe")
+        self._critic16_pipe = value
+
     def g_forward(self, x, z, storage=None):
         """Model.predict of the generator.  storage: None = self.forward_storage; "bfloat16" keeps every inter-layer
         activation as bf16 (forward only; the input and the output stay float32)."""

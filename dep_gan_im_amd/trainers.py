@@ -140,7 +140,7 @@ class Trainers:
 
 def build_trainers(netG, netD_y2, netD_dem, batchSize=16, delta=10.0, lrD=1e-4, lrG=1e-4, IM_TRSH=0.5,
                    dist=None, device=None, weights_dtype="float32", activations_dtype="float32", f32_split=0,
-                   forward_only_storage="float32", generator_update_storage="float32"):
+                   forward_only_storage="float32", generator_update_storage="float32", critic16_pipe="float32"):
     """Builds the loss graph of GT:523-598 for the three models and returns a
     Trainers object.  The models are bound to one engine: afterwards their
     predict()/get_weights()/save() see the trained weights.
@@ -159,6 +159,10 @@ def build_trainers(netG, netD_y2, netD_dem, batchSize=16, delta=10.0, lrD=1e-4, 
     on bf16 activation storage (Engine.g_update_storage): the forward of the forward-only passes and a backward that reads
     the bf16 buffers, gradients float32.  With forward_only_storage="bfloat16" as well, netG_no_update(z) and netG_train(z)
     report identical scalars again.
+    critic16_pipe="bfloat16" (needs activations_dtype="bfloat16"): opt-in -- the critics' 16-channel 5x5 launches (dis_0b
+    forward, u-forward and backward-data, dis_1a backward-data), which otherwise stay on the fp32 matrix pipe, run on the
+    bf16 pipe like the rest of such an engine (Engine.critic16_pipe); every rank of a data-parallel job must use the same
+    value.
     dist: a dep_gan_im_amd.dist.DataParallel -- the engine becomes one replica of a data-parallel job (rank 0's
     weights are broadcast, every update all-reduces its gradient arena)."""
     if weights_dtype not in ("float32", "bfloat16"):
@@ -175,6 +179,10 @@ def build_trainers(netG, netD_y2, netD_dem, batchSize=16, delta=10.0, lrD=1e-4, 
         raise ValueError("generator_update_storage must be 'float32' or 'bfloat16'")
     if generator_update_storage == "bfloat16" and activations_dtype != "bfloat16":
         raise ValueError("generator_update_storage='bfloat16' needs activations_dtype='bfloat16' (the bf16 matrix pipe)")
+    if critic16_pipe not in ("float32", "bfloat16"):
+        raise ValueError("critic16_pipe must be 'float32' or 'bfloat16'")
+    if critic16_pipe == "bfloat16" and activations_dtype != "bfloat16":
+        raise ValueError("critic16_pipe='bfloat16' needs activations_dtype='bfloat16' (the bf16 matrix pipe)")
     H, W, nicg = netG.input_shape
     if tuple(netD_y2.input_shape) != (H, W, 1) or tuple(netD_dem.input_shape) != (H, W, 1):
         raise ValueError("critics must take (%d,%d,1) images" % (H, W))
@@ -183,6 +191,7 @@ def build_trainers(netG, netD_y2, netD_dem, batchSize=16, delta=10.0, lrD=1e-4, 
                  bf16_mfma=(activations_dtype == "bfloat16"), f32_split=f32_split)
     eng.forward_only_storage = forward_only_storage
     eng.g_update_storage = generator_update_storage
+    eng.critic16_pipe = critic16_pipe
     netG._bind(eng, "G")
     netD_y2._bind(eng, "D_y2")
     netD_dem._bind(eng, "D_dem")

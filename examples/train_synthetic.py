@@ -58,6 +58,9 @@ def main():
     ap.add_argument("--generator-update-storage", choices=("float32", "bfloat16"), default="float32",
                     help="bfloat16: train in BASELINE config 4 and run the generator update itself on bf16 activation "
                          "storage (forward of the forward-only passes, backward from the bf16 buffers, fp32 gradients)")
+    ap.add_argument("--critic16-pipe", choices=("float32", "bfloat16"), default="float32",
+                    help="bfloat16: train in BASELINE config 4 and run the critics' 16-channel 5x5 launches (dis_0b, the "
+                         "backward-data of dis_1a) on the bf16 matrix pipe too")
     args = ap.parse_args()
 
     import torch
@@ -79,9 +82,10 @@ def main():
     netG = dg.Gen_UNet2D((imageSize, imageSize, nicg), (noiseSize, 1), first_fm_G, 1, seed=3)   # GT:520
     t = dg.build_trainers(netG, netD_y2, netD_dem, batchSize=args.batch, delta=10.0, lrD=1e-4, lrG=1e-4, IM_TRSH=0.178,
                           dist=dp, forward_only_storage=args.forward_only_storage,
-                          generator_update_storage=args.generator_update_storage,
+                          generator_update_storage=args.generator_update_storage, critic16_pipe=args.critic16_pipe,
                           **({"weights_dtype": "bfloat16", "activations_dtype": "bfloat16"}
-                             if "bfloat16" in (args.forward_only_storage, args.generator_update_storage) else {}))
+                             if "bfloat16" in (args.forward_only_storage, args.generator_update_storage, args.critic16_pipe)
+                             else {}))
 
     train_1tp, train_2tp = synthetic_slices(args.slices, imageSize, 0)
     train_1tp, train_2tp = torch.from_numpy(train_1tp).cuda(), torch.from_numpy(train_2tp).cuda()   # resident in HBM

@@ -348,6 +348,27 @@ int depgan_get_fwd_only_storage(depgan_ctx* ctx);
  *   (N, H, W, C); host_dst == NULL only reports the shape; status 1 before a training forward in the mode. */
 int depgan_set_g_update_storage(depgan_ctx* ctx, int storage);
 int depgan_get_g_update_storage(depgan_ctx* ctx);
+
+/* ---- the critics' 16-channel 5x5 layers on the bf16 matrix pipe.  Opt-in, default 0.
+ * A bf16_mfma context runs every convolution with Cout % 32 == 0 on v_mfma_f32_32x32x16_bf16; the launches of the
+ * critics whose output-channel count is 16 stayed on the fp32 pipe (igemm_conv_kernel<16,5,16,25,..>).  With pipe = 1
+ * they run on igemm_bf16_n16_kernel (csrc/igemm_bf16.hip, v_mfma_f32_16x16x32_bf16) under the operand contract of the
+ * other bf16 launches: the fp32 activation view is rounded to bf16 (RNE) while it is staged, the weights are the
+ * context's bf16-valued weights, accumulation and the whole epilogue are fp32, the K order is fixed (chunk, then tap: the
+ * bits repeat from run to run and do not depend on how many samples share the launch).  The launches that move, in both
+ * critics: dis_0b forward (bias, ReLU, fused pool), the penalty's u-forward of dis_0b (mask) and dis_0b backward-data
+ * (5x5, 16 -> 16 at full resolution), and dis_1a backward-data (5x5, 32 -> 16 at half resolution) -- in depgan_d_forward,
+ * depgan_critic_grads / depgan_critic_step, the critic passes of depgan_g_eval / depgan_g_eval_multi / depgan_g_grads /
+ * depgan_g_step, and depgan_gen_iteration.  Not touched: the weight gradients (already on the bf16 pipe), dis_0a (one
+ * input channel) and its backward-data (one output channel), every other layer, the generator.  With pipe = 0 every path
+ * computes the bits it computed before this option existed; switching needs no other call and allocates nothing (both
+ * panels of the four launches are planned and packed by every bf16_mfma context, a few KB).
+ * depgan_set_critic16_pipe: 0 = fp32 (default), 1 = bf16; any other value is status 1; 1 on a context without
+ *   bf16_mfma (or without critics) is status 3 with a message naming the setting, before any launch.
+ * In a data-parallel job every rank must use the same value (the mode changes no collective, but the ranks would
+ * otherwise average gradients of two different critics' arithmetic). */
+int depgan_set_critic16_pipe(depgan_ctx* ctx, int pipe);
+int depgan_get_critic16_pipe(depgan_ctx* ctx);
 int depgan_debug_film_decision_bf16s(depgan_ctx* ctx, const char* layer, unsigned char* host_dst, long cap_bytes,
                                      int shape[4]);
 
@@ -430,7 +451,10 @@ int depgan_op_head_bf16s(const void* a, const float* w, const float* b, float* o
  * 7: the wave-private form of 6 (csrc/igemm_wp.hip: large 3x3 launches with Cin <= 64; bit-identical to 6),
  * 8: Winograd F(2x2,3x3) on the fp32 matrix pipe (csrc/igemm_wino.hip: 3x3, Cin % 8 == 0, Cout % 32 == 0, even H, W),
  * 9: the weight-stationary, wave-private 5x5 form of 1 (csrc/igemm_wp.hip: 5x5, Cin and Cout in {16, 32}, no fused
- *    head; any size; bit-identical to 1; status 1 for KS != 5, status 3 for everything else it does not cover) */
+ *    head; any size; bit-identical to 1; status 1 for KS != 5, status 3 for everything else it does not cover),
+ * 10: the 16-output-channel 5x5 form of 3 (igemm_bf16_n16_kernel: 5x5, output channels of the launch -- Cout, or Cin
+ *    for backward-data -- a multiple of 16, input channels >= 8 and a multiple of 4; status 1 for KS != 5, null operands
+ *    or a fused head, status 3 for every other shape it does not cover; all decided before any HIP call) */
 int depgan_op_conv2d(const float* in, const float* w_hwio, const float* bias, float* out, int B, int H, int W,
                      int Cin, int Cout, int KS, int relu, int path, void* hip_stream);
 int depgan_op_conv2d_bwd_data(const float* dy, const float* w_hwio, float* dx, int B, int H, int W, int Cin,
@@ -472,7 +496,7 @@ int depgan_op_deconv2x2_wgrad(const float* in, const float* dout, float* dw_hwoi
  * Optional operands are NULL (their strides are then ignored); scale / shift and film_mul / film_add come in pairs;
  * film_mul / film_add are rows of film_ld floats per sample.  w_hwio is (KS, KS, Cin, Cout); bwd = 1 is the
  * backward-data form: `in` has Cout channels, `out` (and the epilogue operands) Cin.  path as in depgan_op_conv2d:
- * 1 MFMA, 2 direct, 3 bf16 pipe, 4 / 5 split, 6 8-channel chunks, 7 wave-private, 8 Winograd, 9 weight-stationary 5x5.  Status 1 for null or
+ * 1 MFMA, 2 direct, 3 bf16 pipe, 4 / 5 split, 6 8-channel chunks, 7 wave-private, 8 Winograd, 9 weight-stationary 5x5, 10 bf16 pipe with 16-channel tiles (5x5).  Status 1 for null or
  * non-positive arguments (before any HIP call) and whatever the launcher's argument checks refuse, 3 for what the kernel
  * of that path does not cover; nothing is written then. */
 int depgan_op_conv2d_fused(const float* in, long isB, long isY, long isX, const float* w_hwio, const float* bias,
