@@ -38,7 +38,7 @@ EXPORTS = [
     "depgan_op_conv2d_film_train_bf16s", "depgan_op_conv2d_wgrad_bf16s", "depgan_op_conv2d_bwd_data_bf16s",
     "depgan_op_unpool_mask_bf16s", "depgan_op_film_bwd_bf16s", "depgan_op_head_bwd_bf16s",
     "depgan_op_conv2d_fused", "depgan_op_deconv2x2_igemm", "depgan_op_conv2d_wgrad_ex",
-    "depgan_set_critic16_pipe", "depgan_get_critic16_pipe",
+    "depgan_set_critic16_pipe", "depgan_get_critic16_pipe", "depgan_op_head_softmax_bf16s",
 ]
 
 ABI_VERSION = 3          # DEPGAN_ABI_VERSION of the include/depgan.h this binding was written against
@@ -202,6 +202,7 @@ def load():
     lib.depgan_op_deconv2x2_bf16s.argtypes = [vp, L, L, L] + [vp] * 4 + [vp, L, L, L] + [i] * 6 + [vp]
     lib.depgan_op_edge_conv_bf16s.argtypes = [vp] * 5 + [vp, L, L, L] + [i] * 6 + [vp]
     lib.depgan_op_head_bf16s.argtypes = [vp] * 4 + [L, i, i, vp]
+    lib.depgan_op_head_softmax_bf16s.argtypes = [vp, L] + [vp] * 4 + [L, i, vp]
     lib.depgan_op_conv2d_head_bf16s.argtypes = ([vp, L, L, L] + [vp] * 6 + [i] + [vp, L, L, L] * 2 + [vp] + [i] * 7 +
                                                 [vp] * 3 + [i, i, vp])
     # bf16 storage for the forward-only generator passes of the training closures

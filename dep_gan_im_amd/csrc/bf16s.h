@@ -64,5 +64,12 @@ int dg_edge_conv_bf16s(const EdgeArgsH& a, hipStream_t st);
 int dg_head_bf16s(const __bf16* a, long ld, const float* w, const float* b, float* out, long P, int C, int tanh_act,
                   hipStream_t st);
 
+// gen_segmentation of the DEP-UResNet: z[p][k] = sum_c a[p * ld + c] w[c * K + k] + b[k] in dg_head_bf16s's arithmetic
+// and order per column k, probs[p] = softmax(z[p]) in softmax_ce4_kernel's statements (contraction off around both);
+// bf16 in, fp32 (P, 4) out as 16-byte rows, the logits too where `logits` is given.  K == 4; C as dg_head_bf16s; a, w,
+// probs and logits 16-byte aligned.  Anything else is a status before any launch.
+int dg_head_softmax_bf16s(const __bf16* a, long ld, const float* w, const float* b, float* probs, float* logits, long P,
+                          int C, int K = 4, hipStream_t st = nullptr);
+
 // dense fp32 (N, H, W, C) copy of a bf16 view (exact)
 int dg_widen_bf16(TViewH src, int N, int H, int W, int C, float* dst, hipStream_t st);

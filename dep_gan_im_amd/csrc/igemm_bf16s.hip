@@ -256,6 +256,81 @@ int dg_head_bf16s(const __bf16* a, long ld, const float* w, const float* b, floa
 }
 
 // ---------------------------------------------------------------------------
+// DEP-UResNet head: 1x1 convolution to four logits + softmax over them, bf16 in, fp32 out.  head_bf16s_kernel's lane
+// mapping (C / 8 lanes per pixel, one 16-byte load each, consecutive lanes on consecutive addresses) with four columns of
+// w (C, 4) instead of one: logit k is formed exactly as that kernel forms its output with column k (per 8-channel part
+// v = a0 w0, fmaf over channels 1..7; the same xor butterfly; + b[k]), and the softmax is softmax_ce4_kernel's
+// statements (train_ops.hip, onehot == nullptr) on those four values -- so both halves have an existing kernel to be
+// bit-equal to.  HBM-bound (2 C + 16 bytes per pixel): a grid-stride loop, so that a lane's 32 weights are loaded once;
+// the stride is a multiple of 256, hence of LP, and a lane keeps its part.  Lane 0 of a pixel stores its 16 bytes.
+// ---------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void head_softmax_bf16s_kernel(const __bf16* __restrict__ a, long ld,
+                                                                  const float* __restrict__ w,
+                                                                  const float* __restrict__ b, float* __restrict__ probs,
+                                                                  float* __restrict__ logits, long P, int lgLP) {
+#pragma clang fp contract(off)
+  const int LP = 1 << lgLP;
+  const int part = threadIdx.x & (LP - 1);
+  f32x4 wv[8];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) wv[j] = *reinterpret_cast<const f32x4*>(w + (part * 8 + j) * 4);
+  const long total = P << lgLP;
+  // the trip count is the same for every lane of a block: the shuffles below run with all 64 lanes
+  for (long t0 = blockIdx.x * 256L; t0 < total; t0 += gridDim.x * 256L) {
+    const long p = (t0 + threadIdx.x) >> lgLP;
+    f32x4 z = {0.f, 0.f, 0.f, 0.f};
+    if (p < P) {
+      const f32x8 av = __builtin_convertvector(*reinterpret_cast<const bf16x8*>(a + p * ld + part * 8), f32x8);
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        float v = av[0] * wv[0][k];
+#pragma unroll
+        for (int j = 1; j < 8; ++j) v = fmaf(av[j], wv[j][k], v);
+        z[k] = v;
+      }
+    }
+    for (int o = LP >> 1; o > 0; o >>= 1) {
+#pragma unroll
+      for (int k = 0; k < 4; ++k) z[k] += __shfl_xor(z[k], o, 64);
+    }
+    if (p < P && part == 0) {
+#pragma unroll
+      for (int k = 0; k < 4; ++k) z[k] += b[k];
+      if (logits) *reinterpret_cast<f32x4*>(logits + p * 4) = z;
+      const float m = fmaxf(fmaxf(z[0], z[1]), fmaxf(z[2], z[3]));
+      f32x4 pr;
+      float S0 = 0.f;
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        pr[k] = expf(z[k] - m);
+        S0 += pr[k];
+      }
+#pragma unroll
+      for (int k = 0; k < 4; ++k) pr[k] /= S0;
+      *reinterpret_cast<f32x4*>(probs + p * 4) = pr;
+    }
+  }
+}
+
+int dg_head_softmax_bf16s(const __bf16* a, long ld, const float* w, const float* b, float* probs, float* logits, long P,
+                          int C, int K, hipStream_t st) {
+  if (!a || !w || !b || !probs || P < 1) { dg_set_error("dg_head_softmax_bf16s: bad argument"); return DG_ERR_ARG; }
+  if (K != 4) { dg_set_error("dg_head_softmax_bf16s: %d classes (the softmax is over 4)", K); return DG_ERR_UNSUPPORTED; }
+  const int LP = C / 8;
+  if (C < 8 || (C % 8) || LP > 64 || (LP & (LP - 1))) { dg_set_error("dg_head_softmax_bf16s: C/8 must be a power of two <= 64"); return DG_ERR_ARG; }
+  if (ld < C || (ld % 8) || (((uintptr_t)a) & 15) || (((uintptr_t)w) & 15)) { dg_set_error("dg_head_softmax_bf16s: the input and the weights must be 16-byte aligned, ld a multiple of 8"); return DG_ERR_ARG; }
+  if ((((uintptr_t)probs) & 15) || (((uintptr_t)logits) & 15)) { dg_set_error("dg_head_softmax_bf16s: probs and logits are written as 16-byte rows and must be 16-byte aligned"); return DG_ERR_ARG; }
+  if (P > (0x7FFFFFFFFFFFFFFFL >> 8) / (ld > 64 ? ld : 64)) { dg_set_error("dg_head_softmax_bf16s: %ld pixels", P); return DG_ERR_UNSUPPORTED; }
+  int lg = 0;
+  while ((1 << lg) < LP) ++lg;
+  long blocks = (P * LP + 255) / 256;
+  if (blocks > 2048) blocks = 2048;   // 256 CUs x 8 resident blocks; the loop takes the rest
+  hipLaunchKernelGGL(head_softmax_bf16s_kernel, dim3((unsigned)blocks), dim3(256), 0, st, a, ld, w, b, probs, logits, P, lg);
+  HIPCHECK(hipGetLastError());
+  return DG_OK;
+}
+
+// ---------------------------------------------------------------------------
 // bf16 view -> dense fp32 (exact), 8 channels per thread where the view allows, else one
 // ---------------------------------------------------------------------------
 __global__ void widen_bf16_kernel(TViewH s, long npix, int H, int W, int C, int vec, float* __restrict__ dst) {

@@ -188,7 +188,13 @@ struct depgan_ctx {
   float* fake_y2 = nullptr;        // [B*H*W]
   float last_sums[8];
 
-  // ---- learning-phase-1 path (nc_out == 4) ----
+  // ---- inference context (bf16_mfma = 1 with nc_out = 4): the DEP-UResNet in learning phase 0 on the bf16 pipe ----
+  // predict-only: generator arena, BN affines, noise MLP, forward panels and the fp32 forward activations; no critics, no
+  // gradient tensors, no backward panels, no phase-1 buffers, no weight-gradient slab.  Every training entry refuses it
+  // (infer_refuse) before any launch
+  bool infer_only = false;
+
+  // ---- learning-phase-1 path (nc_out == 4, not the inference context) ----
   bool train_bn = false;
   unsigned last_drop_seed = 0;
   Tn draw_tmp;                     // gradient at the raw conv output (largest layer)
@@ -366,7 +372,9 @@ int g_forward(depgan_ctx* c, const float* x, const float* z, int n, bool store_u
 // g_forward_bf16s: fused_head = gen_segmentation in gen_17's epilogue, and then gen_17 is stored only if keep_17;
 // g_forward_only: the generator pass of a closure that keeps nothing for a backward pass, batch samples into c->attr,
 // on the storage depgan_set_fwd_only_storage chose
-int bf16s_check_ctx(const depgan_ctx* c, const char* who);
+int bf16s_check_ctx(const depgan_ctx* c, const char* who, bool softmax_head = false);
+// DG_ERR_UNSUPPORTED with a text that names the inference context where c is one (no HIP call); DG_OK otherwise
+int infer_refuse(const depgan_ctx* c, const char* who);
 int bf16s_alloc(depgan_ctx* c);
 int g_forward_bf16s(depgan_ctx* c, const float* x, const float* z, float* out, int n, bool fused_head, bool keep_17,
                     bool train = false);

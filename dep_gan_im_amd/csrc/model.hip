@@ -459,6 +459,13 @@ static int build_generator(depgan_ctx* c) {
   for (int i = 0; i < kNTrunk; ++i)
     if (kTrunk[i].kind == G_DECONV) cats[kTrunk[i].aux].co_deconv = kTrunk[i].co * fm;
 
+  // an inference context keeps the forward set only: gradient tensors stay null views, u and the backward panels unallocated
+  const bool fwd_only = c->infer_only;
+  auto galloc = [&](Tn* t, int N, int Hh, int Ww, int Cc) {
+    if (!fwd_only) return talloc(c, t, N, Hh, Ww, Cc);
+    t->p = nullptr; t->H = Hh; t->W = Ww; t->C = Cc;
+    return (int)DG_OK;
+  };
   c->gl.resize(kNTrunk);
   int H = H0, W = W0;
   TView cur = null_view();
@@ -501,20 +508,20 @@ static int build_generator(depgan_ctx* c) {
       L.pf = plan_conv(c, 3, L.Cin, L.Cout, 32, H, W);
       L.pb = plan_conv(c, 3, L.Cout, L.Cin, 32, H, W);
       if (dg_plan_mfma(L.pf)) DGCHECK(dmalloc(c, &L.wpf[0], L.pf.packedFloats));
-      if (i > 0 && dg_plan_mfma(L.pb)) DGCHECK(dmalloc(c, &L.wpb[0], L.pb.packedFloats));
+      if (i > 0 && dg_plan_mfma(L.pb) && !fwd_only) DGCHECK(dmalloc(c, &L.wpb[0], L.pb.packedFloats));
       const bool skip = (i + 1 < kNTrunk && kTrunk[i + 1].kind == G_POOL);
       if (skip) {
         Cat& ct = cats[kTrunk[i + 1].name];
         DGCHECK(talloc(c, &ct.fwd, B, H, W, ct.co_deconv + L.Cout));
-        DGCHECK(talloc(c, &ct.grad, B, H, W, ct.co_deconv + L.Cout));
+        DGCHECK(galloc(&ct.grad, B, H, W, ct.co_deconv + L.Cout));
         L.out = ct.fwd.slice(ct.co_deconv);
         Tn dsk;
-        DGCHECK(talloc(c, &dsk, B, H, W, L.Cout));
+        DGCHECK(galloc(&dsk, B, H, W, L.Cout));
         L.dout = dsk.view();
       } else {
         Tn a, d;
         DGCHECK(talloc(c, &a, B, H, W, L.Cout));
-        DGCHECK(talloc(c, &d, B, H, W, L.Cout));
+        DGCHECK(galloc(&d, B, H, W, L.Cout));
         L.out = a.view();
         L.dout = d.view();
       }
@@ -523,15 +530,15 @@ static int build_generator(depgan_ctx* c) {
       L.pf = plan_conv(c, 3, L.Cin, L.Cout, 32, H, W);
       L.pb = plan_conv(c, 3, L.Cout, L.Cin, 32, H, W);
       DGCHECK(dmalloc(c, &L.wpf[0], L.pf.packedFloats));
-      DGCHECK(dmalloc(c, &L.wpb[0], L.pb.packedFloats));
+      if (!fwd_only) DGCHECK(dmalloc(c, &L.wpb[0], L.pb.packedFloats));
       const std::string key = e.aux;
       const std::string sfx = key.empty() ? "" : ("_" + key);
       L.col_mul = headcol["noise_2_mul" + sfx];
       L.col_add = headcol["noise_2_add" + sfx];
       Tn r, d;
       DGCHECK(talloc(c, &r, B, H, W, L.Cout));
-      DGCHECK(talloc(c, &d, B, H, W, L.Cout));
-      DGCHECK(talloc(c, &L.u, B, H, W, L.Cout));
+      DGCHECK(galloc(&d, B, H, W, L.Cout));
+      DGCHECK(galloc(&L.u, B, H, W, L.Cout));
       L.out = r.view();
       L.dout = d.view();
       if (r.per_sample() > maxFilm) maxFilm = r.per_sample();
@@ -541,12 +548,12 @@ static int build_generator(depgan_ctx* c) {
       Cat& ct = cats[e.name];
       Tn p, dp;
       DGCHECK(talloc(c, &p, B, H / 2, W / 2, Pc.Cout));
-      DGCHECK(talloc(c, &dp, B, H / 2, W / 2, Pc.Cout));
+      DGCHECK(galloc(&dp, B, H / 2, W / 2, Pc.Cout));
       L.Cin = L.Cout = Pc.Cout;
       L.skip_of = i - 1;
       L.out = p.view();
       L.pool_dsrc = dp.view();
-      L.pool_skipgrad = ct.grad.slice(ct.co_deconv);
+      L.pool_skipgrad = fwd_only ? null_view() : ct.grad.slice(ct.co_deconv);
       L.pool_dst = Pc.dout;
       H /= 2;
       W /= 2;
@@ -556,15 +563,15 @@ static int build_generator(depgan_ctx* c) {
       L.pb = plan_conv(c, 1, L.Cout, L.Cin);
       for (int t = 0; t < 4; ++t) {
         DGCHECK(dmalloc(c, &L.wpf[t], L.pf.packedFloats));
-        DGCHECK(dmalloc(c, &L.wpb[t], L.pb.packedFloats));
+        if (!fwd_only) DGCHECK(dmalloc(c, &L.wpb[t], L.pb.packedFloats));
       }
       L.pbf = plan_conv(c, 1, 4 * L.Cout, L.Cin);
-      if (dg_plan_mfma(L.pb) && L.pbf.family == L.pb.family && L.pbf.planes == L.pb.planes && (L.Cout % L.pb.CK) == 0 &&
+      if (!fwd_only && dg_plan_mfma(L.pb) && L.pbf.family == L.pb.family && L.pbf.planes == L.pb.planes && (L.Cout % L.pb.CK) == 0 &&
           L.pbf.packedFloats == 4 * L.pb.packedFloats)
         DGCHECK(dmalloc(c, &L.wpb_all, L.pbf.packedFloats));
       Cat& ct = cats[e.aux];
       L.out = ct.fwd.slice(0);    // (2H, 2W) grid, first Cout channels
-      L.dout = ct.grad.slice(0);
+      L.dout = fwd_only ? null_view() : ct.grad.slice(0);
       H *= 2;
       W *= 2;
       cur = ct.fwd.view();
@@ -576,6 +583,7 @@ static int build_generator(depgan_ctx* c) {
     }
     producer = i;
   }
+  if (fwd_only) return DG_OK;
   DGCHECK(dmalloc(c, &c->du_tmp.p, (size_t)B * maxFilm));
   DGCHECK(dmalloc(c, &c->dpre, (size_t)B * H0 * W0));
   DGCHECK(dmalloc(c, &c->fake_y2, (size_t)B * H0 * W0));
@@ -738,6 +746,7 @@ int refresh_generator(depgan_ctx* c) {
           const float* src = L.Wt + (size_t)t * L.Cout * L.Cin;  // (kh,kw,Cout,Cin)
           DGCHECK(dg_pack_job(L.pf, src, L.Cin, L.Cout, 1, 0, 0, nullptr, L.wpf[t], 0, &j));
           jobs.push_back(j);
+          if (!L.wpb[t]) continue;   // an inference context has no backward panels
           if (L.wpb_all) {
             // panel of channel tile nt, tap t -> [nt][t][chunk][n][k]: the K axis of the fused backward-data launch
             // is (tap, channel); the per-tap panels are written straight into that interleaved layout
@@ -1259,6 +1268,7 @@ static int finish_update(depgan_ctx* c, int net, Net& n, int nstats, int slot_fl
 
 static int critic_impl(depgan_ctx* c, int net, const float* y2, const float* x, const float* z, const float* ep,
                        float out[2], bool update) {
+  DGCHECK(infer_refuse(c, update ? "depgan_critic_step" : "depgan_critic_grads"));
   if (net != DEPGAN_NET_D_Y2 && net != DEPGAN_NET_D_DEM) { dg_set_error("not a critic id"); return DG_ERR_ARG; }
   DGCHECK(critic_enqueue(c, net - 1, y2, x, z, ep));
   DGCHECK(finish_update(c, net, c->d[net - 1].net, 4, 0, update));
@@ -1270,6 +1280,7 @@ static int critic_impl(depgan_ctx* c, int net, const float* y2, const float* x, 
 
 static int g_impl(depgan_ctx* c, const float* x, const float* y2, const float* z, float out[6], bool train,
                   bool update) {
+  DGCHECK(infer_refuse(c, !train ? "depgan_g_eval" : (update ? "depgan_g_step" : "depgan_g_grads")));
   if (c->cfg.nc_out != 1) { dg_set_error("the WGAN-GP closures need nc_out == 1"); return DG_ERR_ARG; }
   float* stats = c->g.G + c->g.nTrain;
   DGCHECK(g_eval_enqueue(c, x, y2, z, train, stats));
@@ -1312,8 +1323,9 @@ int depgan_create(const depgan_config* cfg, depgan_ctx** out) {
     dg_set_error("depgan_create: f32_split must be 0, 3 or 6, without bf16_weights / bf16_mfma, nc_out = 1");
     return DG_ERR_ARG;
   }
-  if (cfg->bf16_mfma && (!cfg->bf16_weights || (cfg->nc_out != 0 && cfg->nc_out != 1))) {
-    dg_set_error("depgan_create: bf16_mfma needs bf16_weights = 1 and the DEP-GAN generator (nc_out = 1)");
+  if (cfg->bf16_mfma && (!cfg->bf16_weights || (cfg->nc_out != 0 && cfg->nc_out != 1 && cfg->nc_out != 4))) {
+    dg_set_error("depgan_create: bf16_mfma needs bf16_weights = 1 and nc_out = 1 (the DEP-GAN generator) or nc_out = 4 "
+                 "(the DEP-UResNet as a predict-only inference context)");
     return DG_ERR_ARG;
   }
   if (cfg->batch < 1 || cfg->height % 16 || cfg->width % 16 || cfg->height < 16 || cfg->width < 16 || cfg->nicg < 1 ||
@@ -1347,12 +1359,16 @@ int depgan_create(const depgan_config* cfg, depgan_ctx** out) {
     delete c;
     return DG_ERR_ARG;
   }
-  c->train_bn = c->cfg.nc_out != 1;
+  // bf16_mfma = 1 with nc_out = 4: the DEP-UResNet in learning phase 0 only (model.h); no phase-1 state
+  c->infer_only = c->cfg.bf16_mfma && c->cfg.nc_out == 4;
+  c->train_bn = c->cfg.nc_out != 1 && !c->infer_only;
   memset(c->last_sums, 0, sizeof(c->last_sums));
   int rc = build_generator(c);
-  if (rc == DG_OK && !c->train_bn) rc = build_critics(c);   // the supervised path has no critics
+  if (rc == DG_OK && !c->train_bn && !c->infer_only) rc = build_critics(c);   // the supervised path has no critics
   if (rc == DG_OK && c->train_bn) rc = uresnet_build(c);
-  if (rc == DG_OK) {
+  // what u_head_logits and the softmax of depgan_g_forward use, and nothing else of uresnet_build
+  if (rc == DG_OK && c->infer_only) rc = dmalloc(c, &c->logits, (size_t)cfg->batch * cfg->height * cfg->width * 4);
+  if (rc == DG_OK && !c->infer_only) {
     // slab workspace: the largest weight-gradient call of either network
     size_t mx = 0;
     const int B = cfg->batch;
@@ -1388,8 +1404,8 @@ int depgan_create(const depgan_config* cfg, depgan_ctx** out) {
     c->partFloats = mx;
     rc = dmalloc(c, &c->part, mx);
   }
-  if (rc == DG_OK) rc = dmalloc(c, &c->raw, (size_t)9 * 256 * 256);
-  if (rc == DG_OK && !c->train_bn) rc = dmalloc(c, &c->raw_all, c->g.nTrain);
+  if (rc == DG_OK && !c->infer_only) rc = dmalloc(c, &c->raw, (size_t)9 * 256 * 256);
+  if (rc == DG_OK && !c->train_bn && !c->infer_only) rc = dmalloc(c, &c->raw_all, c->g.nTrain);
   if (rc == DG_OK) rc = dmalloc(c, &c->Sraw, 256);
   c->scratchFloats = (size_t)(1 << 20) + (size_t)cfg->batch * 20000;
   if (rc == DG_OK) rc = dmalloc(c, &c->scratch, c->scratchFloats);
@@ -1570,6 +1586,7 @@ int depgan_set_critic16_pipe(depgan_ctx* c, int pipe) {
     dg_set_error("depgan_set_critic16_pipe: pipe must be 0 (fp32) or 1 (bf16), got %d", pipe);
     return DG_ERR_ARG;
   }
+  DGCHECK(infer_refuse(c, "depgan_set_critic16_pipe"));
   if (pipe == 1 && (!c->cfg.bf16_mfma || c->dl.empty())) {
     dg_set_error("depgan_set_critic16_pipe: the bf16 pipe for the critics' 16-channel layers needs a context created with "
                  "bf16_mfma = 1 (and critics: nc_out = 1)");
@@ -1590,6 +1607,7 @@ int depgan_g_forward(depgan_ctx* c, const float* x, const float* z, float* out, 
 }
 
 int depgan_d_forward(depgan_ctx* c, int net, const float* img, float* out, int n) {
+  DGCHECK(infer_refuse(c, "depgan_d_forward"));
   if (net != DEPGAN_NET_D_Y2 && net != DEPGAN_NET_D_DEM) { dg_set_error("d_forward: not a critic id"); return DG_ERR_ARG; }
   if (n < 1 || n > c->NB3) { dg_set_error("d_forward: n must be in [1, 3*batch]"); return DG_ERR_ARG; }
   DGCHECK(d_forward(c, c->d[net - 1], img, 0, n));
@@ -1603,6 +1621,7 @@ int depgan_critic_grads(depgan_ctx* c, int net, const float* y2, const float* x,
 }
 
 int depgan_apply_adam(depgan_ctx* c, int net) {
+  DGCHECK(infer_refuse(c, "depgan_apply_adam"));
   Net* n = pick_net(c, net);
   if (!n) return DG_ERR_ARG;
   DGCHECK(net_adam(c, *n));
@@ -1630,6 +1649,7 @@ int depgan_g_eval(depgan_ctx* c, const float* x, const float* y2, const float* z
 }
 // k evaluations into scal_multi (k x 8 pieces), reduced across ranks when a hook is set.  No host synchronisation.
 static int g_eval_multi_enqueue(depgan_ctx* c, const float* x, const float* y2, const float* z_all, int k) {
+  DGCHECK(infer_refuse(c, "depgan_g_eval_multi"));
   if (c->cfg.nc_out != 1) { dg_set_error("the WGAN-GP closures need nc_out == 1"); return DG_ERR_ARG; }
   if (k < 1 || k > DEPGAN_MAX_MULTI) { dg_set_error("best-of-k: k must be in [1, %d]", DEPGAN_MAX_MULTI); return DG_ERR_ARG; }
   const size_t zstride = (size_t)c->cfg.batch * 32;
@@ -1658,6 +1678,7 @@ int depgan_gen_iteration(depgan_ctx* c, const float* x_y2, const float* y2_y2, c
                          int n_y2, const float* x_dem, const float* y2_dem, const float* z_dem, const float* ep_dem,
                          int n_dem, long batch_stride, const float* x_gen, const float* y2_gen, const float* z_gen, int k,
                          float* out_host, int* best_host) {
+  DGCHECK(infer_refuse(c, "depgan_gen_iteration"));
   if (c->cfg.nc_out != 1) { dg_set_error("the WGAN-GP closures need nc_out == 1"); return DG_ERR_ARG; }
   if (n_y2 < 0 || n_dem < 0 || n_y2 + n_dem > DEPGAN_MAX_CRITIC_STEPS || k < 1 || k > DEPGAN_MAX_MULTI || !out_host ||
       !best_host || !x_gen || !y2_gen || !z_gen || batch_stride < 0) {

@@ -8,6 +8,8 @@
 // c->attr, with gen_segmentation fused into gen_17's epilogue and gen_17 itself stored only under debug capture.
 // Third consumer (depgan_set_g_update_storage, model_bf16s_train.hip): the generator update; g_forward_bf16s(train = true)
 // runs the FiLM layers on the sibling kernel that also keeps the pre-FiLM tensor and the ReLU decisions.
+// Fourth consumer (an inference context: bf16_mfma = 1 with nc_out = 4): depgan_g_forward_bf16s of the DEP-UResNet in
+// learning phase 0 -- the same walk, bit for bit, up to gen_17, then dg_head_softmax_bf16s instead of the tanh head.
 #include "model.h"
 
 #include <stdio.h>
@@ -26,11 +28,21 @@ static int halloc(depgan_ctx* c, __bf16** p, size_t elems) {
   return DG_OK;
 }
 
-// what the context must be for the bf16-storage forward; no HIP call
-int bf16s_check_ctx(const depgan_ctx* c, const char* who) {
-  if (!c->cfg.bf16_mfma || !c->cfg.bf16_weights || c->cfg.nc_out != 1) {
-    dg_set_error("%s: needs a context created with bf16_mfma = 1 (hence bf16_weights = 1, nc_out = 1); this one has "
-                 "bf16_mfma = %d, bf16_weights = %d, nc_out = %d", who, c->cfg.bf16_mfma, c->cfg.bf16_weights,
+int infer_refuse(const depgan_ctx* c, const char* who) {
+  if (!c->infer_only) return DG_OK;
+  dg_set_error("%s: this is an inference context (created with bf16_mfma = 1 and nc_out = 4): predict-only, it holds no "
+               "critics, gradients or optimiser scratch; depgan_g_forward and depgan_g_forward_bf16s are its entries",
+               who);
+  return DG_ERR_UNSUPPORTED;
+}
+
+// what the context must be for the bf16-storage forward; no HIP call.  softmax_head: the caller also serves the
+// inference context (nc_out = 4), which only depgan_g_forward_bf16s does
+int bf16s_check_ctx(const depgan_ctx* c, const char* who, bool softmax_head) {
+  if (!c->cfg.bf16_mfma || !c->cfg.bf16_weights || (c->cfg.nc_out != 1 && !(softmax_head && c->infer_only))) {
+    dg_set_error("%s: needs a context created with bf16_mfma = 1 (hence bf16_weights = 1, nc_out = 1%s); this one has "
+                 "bf16_mfma = %d, bf16_weights = %d, nc_out = %d", who,
+                 softmax_head ? ", or nc_out = 4 for the inference context" : "", c->cfg.bf16_mfma, c->cfg.bf16_weights,
                  c->cfg.nc_out);
     return DG_ERR_UNSUPPORTED;
   }
@@ -154,8 +166,8 @@ int g_forward_bf16s(depgan_ctx* c, const float* x, const float* z, float* out, i
       // gen_segmentation rides in gen_17's epilogue (one channel tile, no pool); a pass that keeps nothing then does not
       // store gen_17 at all -- the bf16 twin of g_forward's head_skip_out
       head_by_conv = false;
-      if (fused_head && L.kind == G_CONV && L.Cout == 32 && !a.ep.pool.p && i + 1 < c->gl.size() &&
-          c->gl[i + 1].kind == G_HEAD) {
+      if (fused_head && c->cfg.nc_out == 1 && L.kind == G_CONV && L.Cout == 32 && !a.ep.pool.p &&
+          i + 1 < c->gl.size() && c->gl[i + 1].kind == G_HEAD) {
         const GLayer& Hd = c->gl[i + 1];
         a.ep.head_w = Hd.Wt; a.ep.head_b = Hd.b; a.ep.head_out = out;
         a.ep.head_tanh = 1;
@@ -198,6 +210,12 @@ int g_forward_bf16s(depgan_ctx* c, const float* x, const float* z, float* out, i
       if (head_by_conv) continue;
       const TViewH in = c->h_in[i];
       const long P = (long)n * L.H * L.W;
+      if (c->cfg.nc_out == 4) {
+        // the DEP-UResNet's head: four logits and their softmax from the stored gen_17, never fused into its epilogue
+        ProfScope ps(c, 2, 2.0 * P * L.Cin * 4, "head softmax fwd(bf16s)", P * (2.0 * L.Cin + 16.0));
+        DGCHECK(dg_head_softmax_bf16s(in.p, in.sX, L.Wt, L.b, out, nullptr, P, L.Cin, 4, c->st));
+        continue;
+      }
       ProfScope ps(c, 2, 2.0 * P * L.Cin, "head fwd(bf16s)", P * (2.0 * L.Cin + 4.0));
       DGCHECK(dg_head_bf16s(in.p, in.sX, L.Wt, L.b, out, P, L.Cin, 1, c->st));
     }
@@ -207,7 +225,7 @@ int g_forward_bf16s(depgan_ctx* c, const float* x, const float* z, float* out, i
 
 int depgan_g_forward_bf16s(depgan_ctx* c, const float* x, const float* z, float* out, int n) {
   if (!c || !x || !z || !out) { dg_set_error("depgan_g_forward_bf16s: null argument"); return DG_ERR_ARG; }
-  DGCHECK(bf16s_check_ctx(c, "depgan_g_forward_bf16s"));
+  DGCHECK(bf16s_check_ctx(c, "depgan_g_forward_bf16s", true));
   if (n < 1 || n > c->cfg.batch) { dg_set_error("depgan_g_forward_bf16s: n must be in [1, batch]"); return DG_ERR_ARG; }
   DGCHECK(bf16s_alloc(c));
   c->h_valid = false;
@@ -232,6 +250,7 @@ int depgan_set_fwd_only_storage(depgan_ctx* c, int storage) {
     dg_set_error("depgan_set_fwd_only_storage: storage must be 0 (fp32) or 1 (bf16), got %d", storage);
     return DG_ERR_ARG;
   }
+  DGCHECK(infer_refuse(c, "depgan_set_fwd_only_storage"));
   if (storage == 1) DGCHECK(bf16s_check_ctx(c, "depgan_set_fwd_only_storage"));
   c->fwd_only_bf16 = storage == 1;
   return DG_OK;
@@ -395,6 +414,12 @@ int depgan_op_edge_conv_bf16s(const float* in, const float* w_hwio, const float*
   e.out = op_view_h(out, osB, osY, osX);
   e.B = B; e.H = H; e.W = W; e.Cin = Cin; e.Cout = Cout; e.relu = relu;
   return dg_edge_conv_bf16s(e, (hipStream_t)stream);
+}
+
+int depgan_op_head_softmax_bf16s(const void* a, long ld, const float* w, const float* b, float* probs, float* logits,
+                                 long P, int C, void* stream) {
+  if (!a || !w || !b || !probs || P < 1 || C < 1 || ld < 1) { dg_set_error("op_head_softmax_bf16s: null or non-positive argument"); return DG_ERR_ARG; }
+  return dg_head_softmax_bf16s(reinterpret_cast<const __bf16*>(a), ld, w, b, probs, logits, P, C, 4, (hipStream_t)stream);
 }
 
 int depgan_op_head_bf16s(const void* a, const float* w, const float* b, float* out, long P, int C, int tanh_act,

@@ -166,6 +166,7 @@ int depgan_set_g_update_storage(depgan_ctx* c, int storage) {
     dg_set_error("depgan_set_g_update_storage: storage must be 0 (fp32) or 1 (bf16), got %d", storage);
     return DG_ERR_ARG;
   }
+  DGCHECK(infer_refuse(c, "depgan_set_g_update_storage"));
   if (storage == 1) DGCHECK(bf16s_check_ctx(c, "depgan_set_g_update_storage"));
   c->g_update_bf16 = storage == 1;
   return DG_OK;

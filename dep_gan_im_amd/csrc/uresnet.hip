@@ -283,6 +283,7 @@ static int u_backward(depgan_ctx* c, const float* x, const float* z, int n) {
 // entry points
 // ---------------------------------------------------------------------------
 static int u_check(depgan_ctx* c, const char* who) {
+  DGCHECK(infer_refuse(c, who));
   if (!c->train_bn) {
     dg_set_error("%s: the context was not created with nc_out = 4", who);
     return DG_ERR_ARG;
@@ -344,6 +345,7 @@ int depgan_uresnet_grads(depgan_ctx* c, const float* x, const float* z, const fl
 
 int depgan_uresnet_step(depgan_ctx* c, const float* x, const float* z, const float* labels, int n,
                         unsigned drop_seed, float* loss_host) {
+  DGCHECK(infer_refuse(c, "depgan_uresnet_step"));
   DGCHECK(u_grads(c, x, z, labels, n, drop_seed, loss_host, false));
   return depgan_apply_adam(c, DEPGAN_NET_G);
 }

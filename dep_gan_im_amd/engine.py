@@ -250,11 +250,25 @@ class Engine:
         nid = NET_IDS[net]
         return self.lib.depgan_arena_ptr(self.h, nid, ARENA_GRADS), self.lib.depgan_arena_floats(self.h, nid, ARENA_GRADS)
 
+    # ---- the inference context ----
+    @property
+    def inference_only(self):
+        """True for an engine created with bf16_mfma=True and nc_out=4: the DEP-UResNet in learning phase 0 on the bf16
+        matrix pipe.  g_forward (either storage) and the weight surface work; the context holds no critics, gradients or
+        optimiser scratch, and every training helper raises ValueError without calling the library."""
+        return bool(self.cfg.bf16_mfma and self.cfg.nc_out == 4)
+
+    def _need_trainable(self, what):
+        if self.inference_only:
+            raise ValueError("%s: this engine is an inference context (bf16_mfma=True, nc_out=4), predict-only; train on "
+                             "an Engine(..., nc_out=4) and copy the weights over" % what)
+
     # ---- forward ----
     @property
     def forward_storage(self):
         """How g_forward stores the activations between the generator's layers: "float32" (default) or "bfloat16"
-        (bf16_mfma engines only: BASELINE config 4 with bf16 activations, depgan_g_forward_bf16s)."""
+        (bf16_mfma engines only, the nc_out=4 inference context included: BASELINE config 4 with bf16 activations,
+        depgan_g_forward_bf16s)."""
         return getattr(self, "_forward_storage", "float32")
 
     @forward_storage.setter
@@ -264,9 +278,10 @@ class Engine:
     def _check_storage(self, storage):
         if storage not in ("float32", "bfloat16"):
             raise ValueError("forward storage must be 'float32' or 'bfloat16', got %r" % (storage,))
-        if storage == "bfloat16" and not (self.cfg.bf16_mfma and self.cfg.nc_out in (0, 1)):
-            raise ValueError("bfloat16 activation storage needs an engine created with bf16_mfma=True (and nc_out=1); "
-                             "this one has bf16_mfma=%d, nc_out=%d" % (self.cfg.bf16_mfma, self.cfg.nc_out))
+        if storage == "bfloat16" and not (self.cfg.bf16_mfma and self.cfg.nc_out in (0, 1, 4)):
+            raise ValueError("bfloat16 activation storage needs an engine created with bf16_mfma=True (nc_out=1, or "
+                             "nc_out=4 for the predict-only inference context); this one has bf16_mfma=%d, nc_out=%d"
+                             % (self.cfg.bf16_mfma, self.cfg.nc_out))
         return storage
 
     @property
@@ -283,6 +298,7 @@ class Engine:
     @forward_only_storage.setter
     def forward_only_storage(self, value):
         value = self._check_storage(value)
+        self._need_trainable("forward_only_storage")
         if getattr(self, "h", None):
             check(self.lib.depgan_set_fwd_only_storage(self.h, 1 if value == "bfloat16" else 0),
                   "depgan_set_fwd_only_storage")
@@ -300,6 +316,7 @@ class Engine:
     @g_update_storage.setter
     def g_update_storage(self, value):
         value = self._check_storage(value)
+        self._need_trainable("g_update_storage")
         if getattr(self, "h", None):
             check(self.lib.depgan_set_g_update_storage(self.h, 1 if value == "bfloat16" else 0),
                   "depgan_set_g_update_storage")
@@ -318,6 +335,7 @@ class Engine:
     def critic16_pipe(self, value):
         if value not in ("float32", "bfloat16"):
             raise ValueError("critic16_pipe must be 'float32' or 'bfloat16', got %r" % (value,))
+        self._need_trainable("critic16_pipe")
         if value == "bfloat16" and not (self.cfg.bf16_mfma and self.cfg.nc_out in (0, 1)):
             raise ValueError("critic16_pipe='bfloat16' needs an engine created with bf16_mfma=True (and nc_out=1); "
                              "this one has bf16_mfma=%d, nc_out=%d" % (self.cfg.bf16_mfma, self.cfg.nc_out))
@@ -348,6 +366,7 @@ class Engine:
         return out
 
     def d_forward(self, net, img):
+        self._need_trainable("d_forward")
         torch = _torch()
         img = self._dev(img)
         if img.dim() != 4 or tuple(img.shape[1:]) != (self.height, self.width, 1):
@@ -377,6 +396,7 @@ class Engine:
         return x, y2, z, ep
 
     def critic(self, which, y2, x, z, ep, update=True):
+        self._need_trainable("critic")
         x, y2, z, ep = self._batch_inputs(x, y2, z, ep)
         out = (C.c_float * 2)()
         self._use_current_stream()
@@ -385,6 +405,7 @@ class Engine:
         return [float(out[0]), float(out[1])]
 
     def generator(self, x, y2, z, mode="eval"):
+        self._need_trainable("generator")
         x, y2, z, _ = self._batch_inputs(x, y2, z)
         out = (C.c_float * 6)()
         self._use_current_stream()
@@ -395,6 +416,7 @@ class Engine:
     def generator_eval_multi(self, x, y2, zs):
         """k forward-only loss evaluations on one batch with k noises (GT:868-877), one host sync.
         zs: (k, B, 32, 1) array / tensor or a list of k (B,32,1) noises.  Returns (k x 6 outputs, k x 8 sums)."""
+        self._need_trainable("generator_eval_multi")
         torch = _torch()
         B = self.batch
         x = self._dev(x, (B, self.height, self.width, self.nicg))
@@ -422,6 +444,7 @@ class Engine:
         tensors whose batch j starts at sample j*batch_stride, z (n, B, 32[,1]), ep (n, B[,1,1,1]); n may be 0.
         gen: (x, y2, zs) -- one batch and its k noises (k, B, 32[,1]).
         Returns (critic_y2 outs n x 2, critic_dem outs n x 2, eval outs k x 6, train out 6, best index)."""
+        self._need_trainable("gen_iteration")
         torch = _torch()
         B = self.batch
         stride = B if batch_stride is None else int(batch_stride)
@@ -477,6 +500,7 @@ class Engine:
     def uresnet(self, x, z, labels, mode="step", drop_seed=0):
         """mode 'step' = train_on_batch (UT:602-606), 'grads' = gradients only, 'eval' = phase-0 loss.
         The leading dimension may be shorter than the engine batch (Keras' last batch of an epoch)."""
+        self._need_trainable("uresnet")
         x = self._dev(x)
         n = int(x.shape[0])
         if n < 1 or n > self.batch or tuple(x.shape[1:]) != (self.height, self.width, self.nicg):
@@ -498,6 +522,7 @@ class Engine:
         return float(loss.value)
 
     def apply_adam(self, net):
+        self._need_trainable("apply_adam")
         self._use_current_stream()
         check(self.lib.depgan_apply_adam(self.h, NET_IDS[net]), "depgan_apply_adam")
 

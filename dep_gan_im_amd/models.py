@@ -264,7 +264,8 @@ class GeneratorModel(_Model):
     net = "G"
     name = "Gen_UNet2D"
 
-    def __init__(self, input_shape, noiseZ_shape=(32, 1), first_fm=32, nc_out=1, seed=None, inference_dtype="float32"):
+    def __init__(self, input_shape, noiseZ_shape=(32, 1), first_fm=32, nc_out=1, seed=None, inference_dtype="float32",
+                 _inference_only=False):
         super().__init__(input_shape, seed)
         if tuple(noiseZ_shape) != (32, 1) or first_fm != 32:
             raise ValueError("the HIP path is built for noiseZ_shape=(32,1), first_fm=32 (GT:520)")
@@ -272,10 +273,12 @@ class GeneratorModel(_Model):
             raise ValueError("nc_out must be 1 (DEP-GAN generator, GT:520) or 4 (DEP-UResNet, UT:583)")
         if inference_dtype not in ("float32", "bfloat16"):
             raise ValueError("inference_dtype must be 'float32' or 'bfloat16', got %r" % (inference_dtype,))
-        if inference_dtype == "bfloat16" and nc_out != 1:
-            raise ValueError("inference_dtype='bfloat16' (bf16 activation storage) exists for the DEP-GAN generator "
-                             "(nc_out=1) only")
+        if inference_dtype == "bfloat16" and nc_out != 1 and not _inference_only:
+            raise ValueError("inference_dtype='bfloat16' (bf16 activation storage) with nc_out=%d: the constructor builds "
+                             "trainable models and the softmax variant has no training on the bf16 pipe; train the "
+                             "float32 model and take model.inference_copy('bfloat16') for predict" % nc_out)
         self.inference_dtype = inference_dtype
+        self.inference_only = bool(_inference_only)      # a predict-only copy (inference_copy)
         self.noiseZ_shape, self.first_fm, self.nc_out = tuple(noiseZ_shape), first_fm, nc_out
         if nc_out != 1:
             self.name = "DEP_UResNet"
@@ -295,7 +298,26 @@ class GeneratorModel(_Model):
             return eng
         if self.nc_out == 1:
             return Engine(batch, H, W, nicg)
+        if self.inference_only:
+            # the inference context: the DEP-UResNet in learning phase 0 on the bf16 matrix pipe, bf16 activation storage
+            eng = Engine(batch, H, W, nicg, nc_out=self.nc_out, bf16_mfma=True)
+            eng.forward_storage = "bfloat16"
+            return eng
         return Engine(batch, H, W, nicg, lrG=self._lr, beta1=0.9, beta2=0.999, nc_out=self.nc_out)
+
+    def inference_copy(self, dtype="bfloat16"):
+        """A new predict-only model with this architecture and a copy of the current weights, whose private engine runs
+        predict on the bf16 matrix pipe with bf16 activation storage (for nc_out=4 the inference context of
+        include/depgan.h).  Later changes to this model are not followed.  predict, set_weights, load_weights,
+        get_weights and save_weights work on the copy; compile, fit, train_on_batch, test_on_batch and evaluate raise
+        RuntimeError.  For nc_out=1 the copy predicts what Gen_UNet2D(..., inference_dtype='bfloat16') with these
+        weights predicts.  UE:553-564: evaluate.predict_mean(model.inference_copy(), flair, mask=...)."""
+        if dtype != "bfloat16":
+            raise ValueError("inference_copy: dtype must be 'bfloat16', got %r" % (dtype,))
+        twin = GeneratorModel(self.input_shape, self.noiseZ_shape, self.first_fm, self.nc_out, self._seed, "bfloat16",
+                              _inference_only=True)
+        twin.set_weights(OrderedDict((n, np.array(v, np.float32)) for n, v in self._weights_dict().items()))
+        return twin
 
     def predict(self, inputs, batch_size=32):
         """netG.predict([x, z])  (GT:848, 859; GE:621; UE:  my_network.predict)."""
@@ -317,6 +339,9 @@ class GeneratorModel(_Model):
 
     # ---- supervised surface of the softmax variant (DEP-UResNet, UT:427, 583-618) ----
     def _need_softmax(self, what):
+        if self.inference_only:
+            raise RuntimeError("%s: this model is a predict-only inference copy (inference_copy); train the model it was "
+                               "copied from" % what)
         if self.nc_out == 1:
             raise RuntimeError("%s: the tanh generator is trained through the WGAN-GP closures "
                                "(trainers.build_trainers), not compiled with a loss" % what)

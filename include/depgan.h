@@ -48,7 +48,12 @@ typedef struct depgan_config {
   int bf16_mfma;    /* BASELINE config 4 on the bf16 matrix pipe (needs bf16_weights = 1): the MFMA convolutions AND the
                        weight-gradient contractions round their operands to bf16 (RNE) while staging them and run
                        v_mfma_f32_32x32x16_bf16 with fp32 accumulation; everything between them stays fp32.
-                       0 = fp32 matrix pipe  */
+                       0 = fp32 matrix pipe.
+                       With nc_out = 4 it creates an INFERENCE CONTEXT: the DEP-UResNet in learning phase 0 only
+                       (depgan_g_forward, depgan_g_forward_bf16s, the weight entry points).  It holds no critics,
+                       gradient tensors, phase-1 buffers or weight-gradient slab, and every training entry
+                       (depgan_uresnet_*, depgan_apply_adam, the WGAN-GP closures, depgan_d_forward and the
+                       depgan_set_*_storage / _pipe setters) returns status 3 before any launch  */
   int f32_split;    /* 0 (default): fp32 products on v_mfma_f32_32x32x2_f32.  6 or 3 (opt-in, never the benchmark's
                        headline; excludes bf16_weights / bf16_mfma): every fp32 operand of the MFMA convolutions is split
                        exactly into three (two) bf16 terms and the six (three) largest cross products run on
@@ -293,6 +298,10 @@ int depgan_debug_tensor(depgan_ctx* ctx, const char* name, float* host_dst, long
  *   Needs a context created with bf16_mfma = 1 (hence bf16_weights = 1, nc_out = 1); any other context gets status 3
  *   and a message naming the settings, before any launch.  The bf16 buffers (one per generator layer output, concat
  *   buffers shared) are allocated by the first call, kept, and freed by depgan_destroy.
+ *   On an inference context (bf16_mfma = 1, nc_out = 4) the same walk, bit for bit up to gen_17, ends in
+ *   depgan_op_head_softmax_bf16s of the stored gen_17 and out_dev is (n, H, W, 4) class probabilities; depgan_g_forward
+ *   on such a context (bf16 pipe, fp32 storage, the direct 1x1 head, its own softmax launch) is the same-context A/B
+ *   partner.
  * depgan_debug_tensor_bf16s: "g/out/<layer>" as depgan_debug_tensor resolves it, from the bf16 buffers of the last
  *   depgan_g_forward_bf16s, widened to fp32 (exact): every conv / FiLM / deconv / pool layer, gen_17 included.
  *   ("g/out/gen_segmentation" is the call's own fp32 output and has no bf16 buffer: status 1.) */
@@ -423,7 +432,12 @@ int depgan_op_head_bwd_bf16s(int backward, const void* a, long ld, const float* 
  * depgan_op_head_bf16s: out[p] = act(sum_c a[p][c] w[c] + b[0]), dense bf16 a (P, C), fp32 out; act = tanh if tanh_act.
  * depgan_op_conv2d_head_bf16s: depgan_op_conv2d_bf16s with that head fused into the epilogue (KS = 3, Cout = 32; status
  *   3 otherwise): head_out (B, H, W) dense fp32 is computed from the STORED (rounded) values in depgan_op_head_bf16s's
- *   arithmetic and order, so it equals the two calls bit for bit; with skip_out the stores of `out` are not issued. */
+ *   arithmetic and order, so it equals the two calls bit for bit; with skip_out the stores of `out` are not issued.
+ * depgan_op_head_softmax_bf16s: the DEP-UResNet's head.  z[p][k] = sum_c a[p ld + c] w[c][k] + b[k] for k = 0..3, bf16 a
+ *   with row stride ld >= C elements (ld % 8 == 0), w (C, 4) fp32 (HWIO of a 1x1 kernel), each column in
+ *   depgan_op_head_bf16s's arithmetic and order; probs[p] = softmax(z[p]) in depgan_op_softmax_ce4's arithmetic, dense
+ *   fp32 (P, 4); `logits` (P, 4) receives z where it is not NULL.  a, w, probs and logits 16-byte aligned; C / 8 a power
+ *   of two <= 64. */
 int depgan_op_conv2d_bf16s(const void* in, long isB, long isY, long isX, const float* w_hwio, const float* bias,
                            const float* scale, const float* shift, const float* film_mul, const float* film_add,
                            int film_ld, const void* res, long rsB, long rsY, long rsX, void* out, long osB, long osY,
@@ -443,6 +457,8 @@ int depgan_op_edge_conv_bf16s(const float* in, const float* w_hwio, const float*
                               int Cout, int relu, void* hip_stream);
 int depgan_op_head_bf16s(const void* a, const float* w, const float* b, float* out, long P, int C, int tanh_act,
                          void* hip_stream);
+int depgan_op_head_softmax_bf16s(const void* a, long ld, const float* w, const float* b, float* probs,
+                                 float* logits_or_null, long P, int C, void* hip_stream);
 
 /* ---- single operators (unit-test surface; device pointers) ---- */
 /* path: 0 auto, 1 fp32 MFMA implicit GEMM, 2 direct, 3 bf16 MFMA implicit GEMM (both operands rounded to bf16, RNE),
