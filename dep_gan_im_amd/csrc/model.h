@@ -70,6 +70,11 @@ struct GLayer {
   int col_mul = -1, col_add = -1;
   // tensors
   TView in, out;           // forward views (in has Cin channels, out has Cout)
+  // bf16 activation storage (bf16s_alloc, bf16_mfma contexts): the bf16 twins of in / out, concat buffers shared as in
+  // the fp32 set; FiLM layers of the generator update (bf16s_train_alloc): RNE_bf16(u) and the ReLU decision bits
+  TViewH hin = null_view_h(), hout = null_view_h(), hu = null_view_h();
+  unsigned char* hdec = nullptr;
+  int cat_deconv = -1;     // conv that feeds a pool: index of the transposed convolution that shares its concat buffer
   TView din, dout;         // gradient views (dout = grad wrt out, after the producer's mask)
   TView in_mask;           // mask applied when writing din (null: none)
   Tn u;                    // FiLM pre-activation (kept when training G)
@@ -210,9 +215,8 @@ struct depgan_ctx {
   bool dbg_mixed_valid = false;
 
   // ---- bf16 activation storage of the generator forward (model_bf16s.hip; bf16_mfma contexts) ----
-  // one view per generator layer (concat buffers shared as in the fp32 set), allocated by the first
-  // depgan_g_forward_bf16s and freed with the context; the fp32 set above is not touched by that path
-  std::vector<TViewH> h_in, h_out;
+  // GLayer::hin / hout, one view per generator layer, allocated by the first depgan_g_forward_bf16s and freed with the
+  // context; the fp32 set above is not touched by that path
   bool h_ready = false, h_valid = false;
   // depgan_set_fwd_only_storage(1): the forward-only generator passes of the training closures (critic updates,
   // netG_no_update) run on that forward and write c->attr; the generator update keeps fp32 storage
@@ -221,10 +225,8 @@ struct depgan_ctx {
   bool h_17_skipped = false;       // the last bf16-storage pass did not store gen_17 (fused head, no debug capture)
   // depgan_set_g_update_storage(1): the generator update runs on the bf16-storage forward too and its backward reads the
   // bf16 buffers (model_bf16s_train.hip).  Per FiLM layer the pre-FiLM tensor as bf16 and the decision bits the forward
-  // stored; allocated by the first update in the mode, valid after a training forward in the mode
+  // stored (GLayer::hu / hdec); allocated by the first update in the mode, valid after a training forward in the mode
   bool g_update_bf16 = false;
-  std::vector<TViewH> h_u;
-  std::vector<unsigned char*> h_dec;
   bool hu_ready = false, hu_valid = false;
 
   // depgan_set_critic16_pipe(1): the critics' 16-channel 5x5 launches on igemm_bf16_n16_kernel (DLayer::pf16 / pb16)
@@ -261,7 +263,30 @@ struct ProfScope {
 };
 
 // helpers shared between model.hip and uresnet.hip
+// zero-filled device memory of the context's lifetime (depgan_destroy frees it), sized in bytes.  The status of the
+// hipMalloc or of the fill comes back unworded: dmalloc (floats) and bf16s_alloc (bf16 elements) word their own messages
+hipError_t dalloc_bytes(depgan_ctx* c, void** p, size_t bytes);
 int dmalloc(depgan_ctx* c, float** p, size_t floats);
+// A device temporary of ONE call (never a context's: those go through c->allocs).  alloc reports failure as a status and
+// frees nothing; the destructor waits for the stream the work went to and frees, so every return after alloc is covered
+struct DevTmp {
+  hipStream_t st;
+  void* p = nullptr;
+  explicit DevTmp(hipStream_t st_) : st(st_) {}
+  DevTmp(const DevTmp&) = delete;
+  DevTmp& operator=(const DevTmp&) = delete;
+  ~DevTmp() {
+    if (!p) return;
+    hipStreamSynchronize(st);
+    hipFree(p);
+  }
+  int alloc(size_t bytes) {
+    HIPCHECK(hipMalloc(&p, bytes));
+    return DG_OK;
+  }
+  template <typename T>
+  T* as() const { return static_cast<T*>(p); }
+};
 int talloc(depgan_ctx* c, Tn* t, int N, int H, int W, int C);
 int conv_launch(depgan_ctx* c, const ConvPlan& pl, const ConvArgs& a, int KS);
 void zero_ep(Epilogue* e);
@@ -298,8 +323,10 @@ static inline void conv_set_weights_bwd(ConvArgs* a, const ConvPlan& pl, const f
   a->w = raw_hwio;
   a->wsT = (long)Cin * Cout; a->wsI = 1; a->wsO = Cout; a->flip = 1;
 }
-static inline WgradArgs wgrad_args(TView x, TView dy, float* part, int B, int H, int W, int Cin, int Cout) {
-  WgradArgs a;
+// WgradArgs / WgradArgsH (activation operand in bf16 memory) with no column sums
+template <typename A, typename X>
+static inline A wgrad_args_of(X x, TView dy, float* part, int B, int H, int W, int Cin, int Cout) {
+  A a;
   a.x = x;
   a.dy = dy;
   a.part = part;
@@ -309,9 +336,49 @@ static inline WgradArgs wgrad_args(TView x, TView dy, float* part, int B, int H,
   a.colB = 0;
   return a;
 }
+static inline WgradArgs wgrad_args(TView x, TView dy, float* part, int B, int H, int W, int Cin, int Cout) {
+  return wgrad_args_of<WgradArgs>(x, dy, part, B, H, W, Cin, Cout);
+}
+static inline WgradArgsH wgrad_args_h(TViewH x, TView dy, float* part, int B, int H, int W, int Cin, int Cout) {
+  return wgrad_args_of<WgradArgsH>(x, dy, part, B, H, W, Cin, Cout);
+}
 TView view_offset(TView v, long samples);
-TView strided2(TView v, int di, int dj);   // pixel grid (2i + di, 2j + dj) of a (2H, 2W) view
-TViewH strided2_h(TViewH v, int di, int dj);
+// pixel grid (2i + di, 2j + dj) of a (2H, 2W) view (TView or TViewH)
+template <typename V>
+static inline V strided2(V v, int di, int dj) {
+  v.p += di * v.sY + dj * v.sX;
+  v.sY *= 2;
+  v.sX *= 2;
+  return v;
+}
+// 2x2 / stride-2 transposed convolution = four 1x1 convolutions of the same input, tap (di, dj) = panels[2 di + dj]
+// writing the pixel grid (2i + di, 2j + dj) of the (2H, 2W) view out2: one grouped launch (ConvArgs or ConvArgsH)
+template <typename A, typename V>
+static inline void deconv_groups(A* a, V out2, const float* const panels[4]) {
+  a->out = strided2(out2, 0, 0);
+  a->groups = 4;
+  for (int t = 0; t < 4; ++t) {
+    a->w_group[t] = panels[t];
+    a->out_group_off[t] = strided2(out2, t / 2, t % 2).p - a->out.p;
+  }
+  a->w = panels[0];
+}
+// epilogue of generator layer L in learning phase 0 (Epilogue or EpilogueH): BN affine and ReLU; a FiLM layer also takes
+// its mul / add columns of the noise heads (rows of 1024) and adds `res`, its own input
+template <typename E, typename V>
+static inline void g_layer_epilogue(E* e, const GLayer& L, const float* heads, V res) {
+  e->bias = L.b; e->scale = L.s; e->shift = L.t; e->relu = 1;
+  if (L.kind != G_FILM) return;
+  e->film_mul = heads + L.col_mul;
+  e->film_add = heads + L.col_add;
+  e->film_ld = 1024;
+  e->res = res;
+}
+// layer i + 1 is the 2x2 max-pool of layer i (gen_1 / gen_3 / gen_5, GT:409/422/435) and H, W are even: the pool can
+// ride in the epilogue of layer i's launch
+static inline bool g_pool_follows(const std::vector<GLayer>& gl, size_t i) {
+  return i + 1 < gl.size() && gl[i + 1].kind == G_POOL && gl[i + 1].skip_of == (int)i && !((gl[i].H | gl[i].W) & 1);
+}
 // backward-data of a 2x2 / stride-2 transposed convolution as ONE 1x1 convolution (dIn[p] = sum_t W_t^T dOut[2p + t]):
 // fills a->in, Cin, cpt and in_run_off so that the K axis gathers the four strided pixel grids of the upstream gradient
 // d, Cout channels each, in chunks of CK
@@ -335,8 +402,12 @@ static inline TViewH op_view_h(const void* p, long sB, long sY, long sX) {
 static inline TViewH op_view_h_or_null(const void* p, long sB, long sY, long sX) {
   return p ? op_view_h(p, sB, sY, sX) : null_view_h();
 }
-// what the bf16-storage operator entries refuse (sB = 0, one sample read by every batch index, is a view)
-static inline bool bad_view(const void* p, long sB, long sY, long sX) { return !p || sB < 0 || sY < 1 || sX < 1; }
+// what the operator entries refuse as a view.  The two meanings differ on purpose: the fp32 entries (op_entries.hip) want
+// a batch stride; the bf16-storage entries (op_entries_bf16s.hip) also take sB = 0, one sample read by every batch index
+static inline bool op_view_bad_batched(const void* p, long sB, long sY, long sX) { return !p || sB < 1 || sY < 1 || sX < 1; }
+static inline bool op_view_bad_broadcast(const void* p, long sB, long sY, long sX) { return !p || sB < 0 || sY < 1 || sX < 1; }
+// upload and run pack jobs whose destinations interleave (GLayer::wpb_all); synchronises: `jobs` is the caller's
+int op_pack_jobs(PackJob* jobs, int n, hipStream_t st);
 int deconv_bwd_data(depgan_ctx* c, GLayer& L, TView dsrc, int n);
 // weight gradient (four taps) + column sums of the upstream gradient of a transposed convolution
 int deconv_wgrad_all(depgan_ctx* c, const GLayer& L, TView dsrc, int n, const float* scale, float* raw,

@@ -51,13 +51,15 @@ float* Net::g(const std::string& name) const {
   return G + pi.off;
 }
 
+hipError_t dalloc_bytes(depgan_ctx* c, void** p, size_t bytes) {
+  const hipError_t e = hipMalloc(p, bytes);
+  if (e != hipSuccess) return e;
+  c->allocs.push_back(*p);
+  return hipMemset(*p, 0, bytes);
+}
 int dmalloc(depgan_ctx* c, float** p, size_t floats) {
-  void* q = nullptr;
   if (floats == 0) floats = 4;
-  HIPCHECK(hipMalloc(&q, floats * sizeof(float)));
-  HIPCHECK(hipMemset(q, 0, floats * sizeof(float)));
-  c->allocs.push_back(q);
-  *p = (float*)q;
+  HIPCHECK(dalloc_bytes(c, (void**)p, floats * sizeof(float)));
   return DG_OK;
 }
 int talloc(depgan_ctx* c, Tn* t, int N, int H, int W, int C) {
@@ -233,20 +235,6 @@ void zero_ep(Epilogue* e) {
 TView view_offset(TView v, long samples) {
   v.p += samples * v.sB;
   return v;
-}
-TView strided2(TView v, int di, int dj) {  // pixel grid (2i+di, 2j+dj)
-  TView r = v;
-  r.p = v.p + di * v.sY + dj * v.sX;
-  r.sY = 2 * v.sY;
-  r.sX = 2 * v.sX;
-  return r;
-}
-TViewH strided2_h(TViewH v, int di, int dj) {
-  TViewH r = v;
-  r.p = v.p + di * v.sY + dj * v.sX;
-  r.sY = 2 * v.sY;
-  r.sX = 2 * v.sX;
-  return r;
 }
 void deconv_gather_k(ConvArgs* a, TView d, int Cout, int CK) {
   a->in = strided2(d, 0, 0);
@@ -570,6 +558,9 @@ static int build_generator(depgan_ctx* c) {
           L.pbf.packedFloats == 4 * L.pb.packedFloats)
         DGCHECK(dmalloc(c, &L.wpb_all, L.pbf.packedFloats));
       Cat& ct = cats[e.aux];
+      // e.aux names the pool whose skip convolution wrote the upper channels of this concat buffer
+      for (int j = 0; j < i; ++j)
+        if (kTrunk[j].kind == G_POOL && !strcmp(kTrunk[j].name, e.aux)) c->gl[c->gl[j].skip_of].cat_deconv = i;
       L.out = ct.fwd.slice(0);    // (2H, 2W) grid, first Cout channels
       L.dout = fwd_only ? null_view() : ct.grad.slice(0);
       H *= 2;
@@ -817,21 +808,11 @@ int g_forward(depgan_ctx* c, const float* x, const float* z, int n, bool store_u
     if (L.kind == G_CONV || L.kind == G_FILM) {
       ConvArgs a = conv_args((i == 0) ? make_view(const_cast<float*>(x), L.H, L.W, L.Cin) : L.in, L.out,
                              n, L.H, L.W, L.Cin, L.Cout);
-      a.ep.bias = L.b; a.ep.scale = L.s; a.ep.shift = L.t; a.ep.relu = 1;
-      if (L.kind == G_FILM) {
-        a.ep.film_mul = c->na.heads + L.col_mul;
-        a.ep.film_add = c->na.heads + L.col_add;
-        a.ep.film_ld = 1024;
-        a.ep.res = L.in;
-        if (store_u) a.ep.out_pre = L.u.view();
-      }
+      g_layer_epilogue(&a.ep, L, c->na.heads, L.in);
+      if (L.kind == G_FILM && store_u) a.ep.out_pre = L.u.view();
       conv_set_weights(&a, L.pf, L.wpf[0], L.Wt, L.Cin, L.Cout);
-      if (dg_plan_mfma(L.pf)) {
-        // the 2x2 max-pool that follows (gen_1 / gen_3 / gen_5, GT:409/422/435) rides in this launch's epilogue
-        if (i + 1 < c->gl.size() && c->gl[i + 1].kind == G_POOL && c->gl[i + 1].skip_of == (int)i &&
-            !((L.H | L.W) & 1))
-          a.ep.pool = c->gl[i + 1].out;
-      }
+      // the 2x2 max-pool that follows rides in this launch's epilogue
+      if (dg_plan_mfma(L.pf) && g_pool_follows(c->gl, i)) a.ep.pool = c->gl[i + 1].out;
       pooled_by_conv = a.ep.pool.p != nullptr;
       // gen_segmentation (1x1 to one channel, tanh: GT:494-495) rides in gen_17's epilogue where the layer runs on the
       // 8-channel-chunk kernel; forward-only passes then do not store gen_17's own output at all
@@ -856,14 +837,9 @@ int g_forward(depgan_ctx* c, const float* x, const float* z, int n, bool store_u
         DGCHECK(deconv_fwd_launch(c, L, L.out, L.b, L.s, L.t, 1, n));
         continue;
       }
-      ConvArgs a = conv_args(L.in, strided2(L.out, 0, 0), n, L.H, L.W, L.Cin, L.Cout);
-      a.ep.bias = L.b; a.ep.scale = L.s; a.ep.shift = L.t; a.ep.relu = 1;
-      a.groups = 4;
-      for (int t = 0; t < 4; ++t) {
-        a.w_group[t] = L.wpf[t];
-        a.out_group_off[t] = strided2(L.out, t / 2, t % 2).p - a.out.p;
-      }
-      a.w = L.wpf[0];
+      ConvArgs a = conv_args(L.in, L.out, n, L.H, L.W, L.Cin, L.Cout);
+      g_layer_epilogue(&a.ep, L, c->na.heads, L.in);
+      deconv_groups(&a, L.out, L.wpf);
       DGCHECK(conv_launch(c, L.pf, a, 1));
     } else if (L.kind == G_HEAD && c->cfg.nc_out == 1) {
       if (head_by_conv) continue;
@@ -1847,12 +1823,11 @@ int depgan_debug_tensor(depgan_ctx* c, const char* name, float* host, long cap, 
     return DG_OK;
   }
   // rows of C floats at a pitch of sX floats (a channel slice of a concat buffer) -> dense on the device, then down
-  float* tmp = nullptr;
-  HIPCHECK(hipMalloc((void**)&tmp, (size_t)need * sizeof(float)));
-  hipError_t e = hipMemcpy2D(tmp, (size_t)C * sizeof(float), v.p, (size_t)v.sX * sizeof(float), (size_t)C * sizeof(float),
+  DevTmp tmp(c->st);
+  DGCHECK(tmp.alloc((size_t)need * sizeof(float)));
+  hipError_t e = hipMemcpy2D(tmp.p, (size_t)C * sizeof(float), v.p, (size_t)v.sX * sizeof(float), (size_t)C * sizeof(float),
                              (size_t)N * H * W, hipMemcpyDeviceToDevice);
-  if (e == hipSuccess) e = hipMemcpy(host, tmp, (size_t)need * sizeof(float), hipMemcpyDeviceToHost);
-  hipFree(tmp);
+  if (e == hipSuccess) e = hipMemcpy(host, tmp.p, (size_t)need * sizeof(float), hipMemcpyDeviceToHost);
   if (e != hipSuccess) { dg_set_error("debug_tensor: copy of %s failed: %s", name, hipGetErrorString(e)); return DG_ERR_HIP; }
   return DG_OK;
 }

@@ -1,6 +1,6 @@
 // Generator forward (Model.predict, GT:846-859; the evaluation's ten-noise mean, GE:616-628) of a bf16_mfma context
-// with every inter-layer activation STORED as bf16 (bf16s.h): the drivers, the debug surface and
-// the operator entries of the kernels in igemm_bf16s.hip.  The fp32 path (g_forward in model.hip) and its buffers are
+// with every inter-layer activation STORED as bf16 (bf16s.h): the drivers and the debug surface
+// (the operator entries of the kernels are in op_entries_bf16s.hip).  The fp32 path (g_forward in model.hip) and its buffers are
 // not touched: this is a second, opt-in walk over the same layer table, the same packed bf16 panels (GLayer::wpf), the
 // same BN affines and the same fp32 noise MLP.
 // Second consumer (depgan_set_fwd_only_storage): the forward-only generator passes of the training closures --
@@ -15,16 +15,14 @@
 #include <stdio.h>
 #include <string.h>
 
-static int halloc(depgan_ctx* c, __bf16** p, size_t elems) {
-  void* q = nullptr;
+static int bf16s_malloc(depgan_ctx* c, __bf16** p, size_t elems) {
   const size_t bytes = (elems ? elems : 8) * sizeof(__bf16);
-  if (hipMalloc(&q, bytes) != hipSuccess) {
+  const hipError_t e = dalloc_bytes(c, (void**)p, bytes);
+  if (e == hipErrorOutOfMemory) {
     dg_set_error("depgan_g_forward_bf16s: out of device memory for the bf16 activation buffers (%zu bytes)", bytes);
     return DG_ERR_HIP;
   }
-  c->allocs.push_back(q);
-  HIPCHECK(hipMemset(q, 0, bytes));
-  *p = (__bf16*)q;
+  HIPCHECK(e);
   return DG_OK;
 }
 
@@ -62,47 +60,33 @@ int bf16s_check_ctx(const depgan_ctx* c, const char* who, bool softmax_head) {
   return DG_OK;
 }
 
-// The bf16 twin of build_generator's activation set: one buffer per layer output; a convolution that feeds a pool
-// writes into the upper channels of its concat buffer, the transposed convolution of the same level into the lower ones
-// (GT:450/465/479: [deconv | skip]).  The pairing is read off the fp32 views, which are laid out the same way.
+// The bf16 twin of build_generator's activation set (GLayer::hin / hout): one buffer per layer output; a convolution that
+// feeds a pool writes into the upper channels of its concat buffer, the transposed convolution of the same level
+// (GLayer::cat_deconv) into the lower ones (GT:450/465/479: [deconv | skip])
 int bf16s_alloc(depgan_ctx* c) {
   if (c->h_ready) return DG_OK;
   const int B = c->cfg.batch;
-  const size_t nl = c->gl.size();
-  std::vector<TViewH> hin(nl, null_view_h()), hout(nl, null_view_h());
   TViewH cur = null_view_h();
-  for (size_t i = 0; i < nl; ++i) {
-    const GLayer& L = c->gl[i];
-    hin[i] = cur;
-    if (L.kind == G_CONV && i + 1 < nl && c->gl[i + 1].kind == G_POOL) {
-      // the skip convolution: find the transposed convolution that shares its concat buffer
-      int dc = -1;
-      for (size_t j = i + 1; j < nl; ++j)
-        if (c->gl[j].kind == G_DECONV && c->gl[j].out.sX == L.out.sX && L.out.p == c->gl[j].out.p + c->gl[j].Cout) dc = (int)j;
-      if (dc < 0) { dg_set_error("depgan_g_forward_bf16s: no concat partner for %s", L.name.c_str()); return DG_ERR_UNSUPPORTED; }
-      const int Ctot = c->gl[dc].Cout + L.Cout;
-      __bf16* p = nullptr;
-      DGCHECK(halloc(c, &p, (size_t)B * L.H * L.W * Ctot));
-      hout[i] = make_view_slice_h(p, L.H, L.W, Ctot, c->gl[dc].Cout);
-      hout[dc] = make_view_slice_h(p, L.H, L.W, Ctot, 0);
-      cur = hout[i];
+  for (GLayer& L : c->gl) {
+    L.hin = cur;
+    __bf16* p = nullptr;
+    if (L.kind == G_CONV && L.cat_deconv >= 0) {
+      GLayer& D = c->gl[L.cat_deconv];
+      const int Ctot = D.Cout + L.Cout;
+      DGCHECK(bf16s_malloc(c, &p, (size_t)B * L.H * L.W * Ctot));
+      L.hout = make_view_slice_h(p, L.H, L.W, Ctot, D.Cout);
+      D.hout = make_view_slice_h(p, L.H, L.W, Ctot, 0);
     } else if (L.kind == G_CONV || L.kind == G_FILM) {
-      __bf16* p = nullptr;
-      DGCHECK(halloc(c, &p, (size_t)B * L.H * L.W * L.Cout));
-      hout[i] = make_view_h(p, L.H, L.W, L.Cout);
-      cur = hout[i];
+      DGCHECK(bf16s_malloc(c, &p, (size_t)B * L.H * L.W * L.Cout));
+      L.hout = make_view_h(p, L.H, L.W, L.Cout);
     } else if (L.kind == G_POOL) {
-      __bf16* p = nullptr;
-      DGCHECK(halloc(c, &p, (size_t)B * (L.H / 2) * (L.W / 2) * L.Cout));
-      hout[i] = make_view_h(p, L.H / 2, L.W / 2, L.Cout);
-      cur = hout[i];
-    } else if (L.kind == G_DECONV) {
-      if (!hout[i].p) { dg_set_error("depgan_g_forward_bf16s: %s has no concat buffer", L.name.c_str()); return DG_ERR_UNSUPPORTED; }
-      cur = hout[i];   // slice 0 of the concat buffer = the whole buffer for a consumer that reads all its channels
+      DGCHECK(bf16s_malloc(c, &p, (size_t)B * (L.H / 2) * (L.W / 2) * L.Cout));
+      L.hout = make_view_h(p, L.H / 2, L.W / 2, L.Cout);
     }
+    // a transposed convolution got slice 0 of its concat buffer above: the whole buffer for a consumer that reads all its
+    // channels; the head writes fp32
+    if (L.kind != G_HEAD) cur = L.hout;
   }
-  c->h_in.swap(hin);
-  c->h_out.swap(hout);
   c->h_ready = true;
   return DG_OK;
 }
@@ -141,7 +125,7 @@ int g_forward_bf16s(depgan_ctx* c, const float* x, const float* z, float* out, i
       EdgeArgsH e;
       memset(&e, 0, sizeof(e));
       e.in = x; e.w = L.Wt; e.bias = L.b; e.scale = L.s; e.shift = L.t;
-      e.out = c->h_out[i];
+      e.out = L.hout;
       e.B = n; e.H = L.H; e.W = L.W; e.Cin = L.Cin; e.Cout = L.Cout; e.relu = 1;
       char lb[56];
       snprintf(lb, sizeof(lb), "edge conv(bf16s) b%d %dx%d %d->%d", n, L.H, L.W, L.Cin, L.Cout);
@@ -150,18 +134,11 @@ int g_forward_bf16s(depgan_ctx* c, const float* x, const float* z, float* out, i
       DGCHECK(dg_edge_conv_bf16s(e, c->st));
       pooled_by_conv = false;
     } else if (L.kind == G_CONV || L.kind == G_FILM) {
-      ConvArgsH a = conv_args_h(c->h_in[i], c->h_out[i], n, L.H, L.W, L.Cin, L.Cout);
+      ConvArgsH a = conv_args_h(L.hin, L.hout, n, L.H, L.W, L.Cin, L.Cout);
       a.w = L.wpf[0];
-      a.ep.bias = L.b; a.ep.scale = L.s; a.ep.shift = L.t; a.ep.relu = 1;
-      if (L.kind == G_FILM) {
-        a.ep.film_mul = c->na.heads + L.col_mul;
-        a.ep.film_add = c->na.heads + L.col_add;
-        a.ep.film_ld = 1024;
-        a.ep.res = c->h_in[i];
-      }
-      // the 2x2 max-pool that follows (gen_1 / gen_3 / gen_5) rides in this launch's epilogue
-      if (i + 1 < c->gl.size() && c->gl[i + 1].kind == G_POOL && c->gl[i + 1].skip_of == (int)i && !((L.H | L.W) & 1))
-        a.ep.pool = c->h_out[i + 1];
+      g_layer_epilogue(&a.ep, L, c->na.heads, L.hin);
+      // the 2x2 max-pool that follows rides in this launch's epilogue
+      if (g_pool_follows(c->gl, i)) a.ep.pool = c->gl[i + 1].hout;
       pooled_by_conv = a.ep.pool.p != nullptr;
       // gen_segmentation rides in gen_17's epilogue (one channel tile, no pool); a pass that keeps nothing then does not
       // store gen_17 at all -- the bf16 twin of g_forward's head_skip_out
@@ -179,8 +156,8 @@ int g_forward_bf16s(depgan_ctx* c, const float* x, const float* z, float* out, i
         // the generator update: the same launch under the sibling kernel that also keeps RNE_bf16(u) and the FiLM decisions
         ConvArgsHT t;
         static_cast<ConvArgsH&>(t) = a;
-        t.u = c->h_u[i];
-        t.fdec = c->h_dec[i];
+        t.u = L.hu;
+        t.fdec = L.hdec;
         char lb[56];
         snprintf(lb, sizeof(lb), "conv(bf16s) k3 b%d %dx%d %d->%d +u", n, L.H, L.W, L.Cin, L.Cout);
         const double px = (double)n * L.H * L.W;
@@ -197,18 +174,13 @@ int g_forward_bf16s(depgan_ctx* c, const float* x, const float* z, float* out, i
       return DG_ERR_UNSUPPORTED;
     } else if (L.kind == G_DECONV) {
       // four 1x1 convolutions of the same input, tap (di, dj) writing the pixel grid (2i + di, 2j + dj): one grouped launch
-      ConvArgsH a = conv_args_h(c->h_in[i], strided2_h(c->h_out[i], 0, 0), n, L.H, L.W, L.Cin, L.Cout);
-      a.ep.bias = L.b; a.ep.scale = L.s; a.ep.shift = L.t; a.ep.relu = 1;
-      a.groups = 4;
-      for (int t = 0; t < 4; ++t) {
-        a.w_group[t] = L.wpf[t];
-        a.out_group_off[t] = strided2_h(c->h_out[i], t / 2, t % 2).p - a.out.p;
-      }
-      a.w = L.wpf[0];
+      ConvArgsH a = conv_args_h(L.hin, L.hout, n, L.H, L.W, L.Cin, L.Cout);
+      g_layer_epilogue(&a.ep, L, c->na.heads, L.hin);
+      deconv_groups(&a, L.hout, L.wpf);
       DGCHECK(conv_launch_bf16s(c, a, 1));
     } else if (L.kind == G_HEAD) {
       if (head_by_conv) continue;
-      const TViewH in = c->h_in[i];
+      const TViewH in = L.hin;
       const long P = (long)n * L.H * L.W;
       if (c->cfg.nc_out == 4) {
         // the DEP-UResNet's head: four logits and their softmax from the stored gen_17, never fused into its epilogue
@@ -264,13 +236,11 @@ int bf16s_debug_copy(depgan_ctx* c, const char* name, TViewH v, int H, int W, in
   if (!host) return DG_OK;
   const long need = (long)N * H * W * C;
   if (cap < need) { dg_set_error("debug_tensor_bf16s: %s needs %ld floats, the buffer holds %ld", name, need, cap); return DG_ERR_ARG; }
-  float* tmp = nullptr;
-  HIPCHECK(hipMalloc((void**)&tmp, (size_t)need * sizeof(float)));
-  int rc = dg_widen_bf16(v, N, H, W, C, tmp, c->st);
+  DevTmp tmp(c->st);
+  DGCHECK(tmp.alloc((size_t)need * sizeof(float)));
+  DGCHECK(dg_widen_bf16(v, N, H, W, C, tmp.as<float>(), c->st));
   hipError_t e = hipStreamSynchronize(c->st);
-  if (rc == DG_OK && e == hipSuccess) e = hipMemcpy(host, tmp, (size_t)need * sizeof(float), hipMemcpyDeviceToHost);
-  hipFree(tmp);
-  if (rc != DG_OK) return rc;
+  if (e == hipSuccess) e = hipMemcpy(host, tmp.p, (size_t)need * sizeof(float), hipMemcpyDeviceToHost);
   if (e != hipSuccess) { dg_set_error("debug_tensor_bf16s: copy of %s failed: %s", name, hipGetErrorString(e)); return DG_ERR_HIP; }
   return DG_OK;
 }
@@ -302,128 +272,8 @@ int depgan_debug_tensor_bf16s(depgan_ctx* c, const char* name, float* host, long
     }
     const int H = L.kind == G_POOL ? L.H / 2 : (L.kind == G_DECONV ? 2 * L.H : L.H);
     const int W = L.kind == G_POOL ? L.W / 2 : (L.kind == G_DECONV ? 2 * L.W : L.W);
-    return bf16s_debug_copy(c, name, c->h_out[i], H, W, L.Cout, host, cap, shape);
+    return bf16s_debug_copy(c, name, L.hout, H, W, L.Cout, host, cap, shape);
   }
   dg_set_error("debug_tensor_bf16s: unknown tensor '%s'", name);
   return DG_ERR_ARG;
-}
-
-// ---- single operators (unit tests): explicit view strides in ELEMENTS, stream last, checks before any HIP call ----
-
-static int op_conv2d_bf16s_impl(const char* who, const void* in, long isB, long isY, long isX, const float* w_hwio,
-                                const float* bias, const float* scale, const float* shift, const float* film_mul,
-                                const float* film_add, int film_ld, const void* res, long rsB, long rsY, long rsX,
-                                void* out, long osB, long osY, long osX, void* pool, int B, int H, int W, int Cin, int Cout,
-                                int KS, int relu, const float* head_w, const float* head_b, float* head_out, int tanh_act,
-                                int skip_out, void* stream) {
-  if (bad_view(in, isB, isY, isX) || bad_view(out, osB, osY, osX) || !w_hwio || B < 1 || H < 1 || W < 1 || Cin < 1 ||
-      Cout < 1 || (res && bad_view(res, rsB, rsY, rsX))) {
-    dg_set_error("%s: null or non-positive argument", who);
-    return DG_ERR_ARG;
-  }
-  if (KS != 1 && KS != 3) { dg_set_error("%s: KS must be 1 or 3", who); return DG_ERR_ARG; }
-  const ConvPlan pl = dg_plan_conv_bf16(KS, Cin, Cout);
-  if (!dg_plan_bf16(pl) || (Cin % 8)) { dg_set_error("%s: the bf16 MFMA kernel does not cover %d -> %d", who, Cin, Cout); return DG_ERR_UNSUPPORTED; }
-  if (head_out && (KS != 3 || Cout != 32)) {
-    dg_set_error("%s: the fused head needs a 3x3 convolution to exactly 32 channels (KS %d, Cout %d)", who, KS, Cout);
-    return DG_ERR_UNSUPPORTED;
-  }
-  hipStream_t st = (hipStream_t)stream;
-  ConvArgsH a = conv_args_h(op_view_h(in, isB, isY, isX), op_view_h(out, osB, osY, osX), B, H, W, Cin, Cout);
-  a.ep.bias = bias; a.ep.scale = scale; a.ep.shift = shift;
-  a.ep.film_mul = film_mul; a.ep.film_add = film_add; a.ep.film_ld = film_ld;
-  a.ep.res = op_view_h_or_null(res, rsB, rsY, rsX);
-  a.ep.relu = relu;
-  a.ep.pool = pool ? make_view_h(reinterpret_cast<__bf16*>(pool), H / 2, W / 2, Cout) : null_view_h();
-  a.ep.head_w = head_w; a.ep.head_b = head_b; a.ep.head_out = head_out;
-  a.ep.head_tanh = tanh_act; a.ep.head_skip_out = head_out ? skip_out : 0;
-  float* wp = nullptr;
-  HIPCHECK(hipMalloc((void**)&wp, pl.packedFloats * sizeof(float)));
-  int rc = dg_pack_weights(pl, w_hwio, Cin, Cout, 0, 0, 0, nullptr, wp, st);
-  a.w = wp;
-  if (rc == DG_OK) rc = dg_conv_bf16s(KS, a, st);
-  hipStreamSynchronize(st);
-  hipFree(wp);
-  return rc;
-}
-
-int depgan_op_conv2d_bf16s(const void* in, long isB, long isY, long isX, const float* w_hwio, const float* bias,
-                           const float* scale, const float* shift, const float* film_mul, const float* film_add,
-                           int film_ld, const void* res, long rsB, long rsY, long rsX, void* out, long osB, long osY,
-                           long osX, void* pool, int B, int H, int W, int Cin, int Cout, int KS, int relu, void* stream) {
-  return op_conv2d_bf16s_impl("op_conv2d_bf16s", in, isB, isY, isX, w_hwio, bias, scale, shift, film_mul, film_add, film_ld,
-                              res, rsB, rsY, rsX, out, osB, osY, osX, pool, B, H, W, Cin, Cout, KS, relu, nullptr, nullptr,
-                              nullptr, 0, 0, stream);
-}
-
-int depgan_op_conv2d_head_bf16s(const void* in, long isB, long isY, long isX, const float* w_hwio, const float* bias,
-                                const float* scale, const float* shift, const float* film_mul, const float* film_add,
-                                int film_ld, const void* res, long rsB, long rsY, long rsX, void* out, long osB,
-                                long osY, long osX, void* pool, int B, int H, int W, int Cin, int Cout, int KS, int relu,
-                                const float* head_w, const float* head_b, float* head_out, int tanh_act, int skip_out,
-                                void* stream) {
-  if (!head_w || !head_b || !head_out) { dg_set_error("op_conv2d_head_bf16s: null head argument"); return DG_ERR_ARG; }
-  return op_conv2d_bf16s_impl("op_conv2d_head_bf16s", in, isB, isY, isX, w_hwio, bias, scale, shift, film_mul, film_add,
-                              film_ld, res, rsB, rsY, rsX, out, osB, osY, osX, pool, B, H, W, Cin, Cout, KS, relu, head_w,
-                              head_b, head_out, tanh_act, skip_out, stream);
-}
-
-int depgan_op_deconv2x2_bf16s(const void* in, long isB, long isY, long isX, const float* w_hwoi, const float* bias,
-                              const float* scale, const float* shift, void* out, long osB, long osY, long osX, int B,
-                              int H, int W, int Cin, int Cout, int relu, void* stream) {
-  if (bad_view(in, isB, isY, isX) || bad_view(out, osB, osY, osX) || !w_hwoi || B < 1 || H < 1 || W < 1 || Cin < 1 ||
-      Cout < 1) {
-    dg_set_error("op_deconv2x2_bf16s: null or non-positive argument");
-    return DG_ERR_ARG;
-  }
-  const ConvPlan pl = dg_plan_conv_bf16(1, Cin, Cout);
-  if (!dg_plan_bf16(pl) || (Cin % 8)) { dg_set_error("op_deconv2x2_bf16s: the bf16 MFMA kernel does not cover %d -> %d", Cin, Cout); return DG_ERR_UNSUPPORTED; }
-  hipStream_t st = (hipStream_t)stream;
-  const TViewH o = op_view_h(out, osB, osY, osX);   // the (2H, 2W) output
-  ConvArgsH a = conv_args_h(op_view_h(in, isB, isY, isX), strided2_h(o, 0, 0), B, H, W, Cin, Cout);
-  a.ep.bias = bias; a.ep.scale = scale; a.ep.shift = shift; a.ep.relu = relu;
-  a.ep.res = null_view_h();
-  a.ep.pool = null_view_h();
-  a.groups = 4;
-  float* wp = nullptr;
-  HIPCHECK(hipMalloc((void**)&wp, 4 * pl.packedFloats * sizeof(float)));
-  int rc = DG_OK;
-  for (int t = 0; t < 4 && rc == DG_OK; ++t) {
-    float* dst = wp + (size_t)t * pl.packedFloats;
-    rc = dg_pack_weights(pl, w_hwoi + (size_t)t * Cout * Cin, Cin, Cout, 1, 0, 0, nullptr, dst, st);
-    a.w_group[t] = dst;
-    a.out_group_off[t] = strided2_h(o, t / 2, t % 2).p - a.out.p;
-  }
-  a.w = wp;
-  if (rc == DG_OK) rc = dg_conv_bf16s(1, a, st);
-  hipStreamSynchronize(st);
-  hipFree(wp);
-  return rc;
-}
-
-int depgan_op_edge_conv_bf16s(const float* in, const float* w_hwio, const float* bias, const float* scale,
-                              const float* shift, void* out, long osB, long osY, long osX, int B, int H, int W, int Cin,
-                              int Cout, int relu, void* stream) {
-  if (!in || !w_hwio || bad_view(out, osB, osY, osX) || B < 1 || H < 1 || W < 1 || Cin < 1 || Cout < 1) {
-    dg_set_error("op_edge_conv_bf16s: null or non-positive argument");
-    return DG_ERR_ARG;
-  }
-  EdgeArgsH e;
-  memset(&e, 0, sizeof(e));
-  e.in = in; e.w = w_hwio; e.bias = bias; e.scale = scale; e.shift = shift;
-  e.out = op_view_h(out, osB, osY, osX);
-  e.B = B; e.H = H; e.W = W; e.Cin = Cin; e.Cout = Cout; e.relu = relu;
-  return dg_edge_conv_bf16s(e, (hipStream_t)stream);
-}
-
-int depgan_op_head_softmax_bf16s(const void* a, long ld, const float* w, const float* b, float* probs, float* logits,
-                                 long P, int C, void* stream) {
-  if (!a || !w || !b || !probs || P < 1 || C < 1 || ld < 1) { dg_set_error("op_head_softmax_bf16s: null or non-positive argument"); return DG_ERR_ARG; }
-  return dg_head_softmax_bf16s(reinterpret_cast<const __bf16*>(a), ld, w, b, probs, logits, P, C, 4, (hipStream_t)stream);
-}
-
-int depgan_op_head_bf16s(const void* a, const float* w, const float* b, float* out, long P, int C, int tanh_act,
-                         void* stream) {
-  if (!a || !w || !b || !out || P < 1 || C < 1) { dg_set_error("op_head_bf16s: null or non-positive argument"); return DG_ERR_ARG; }
-  return dg_head_bf16s(reinterpret_cast<const __bf16*>(a), C, w, b, out, P, C, tanh_act, (hipStream_t)stream);
 }

@@ -8,6 +8,15 @@
 #include <stdio.h>
 #include <string.h>
 
+int op_pack_jobs(PackJob* jobs, int n, hipStream_t st) {
+  const unsigned nb = dg_pack_layout(jobs, n);
+  DevTmp jd(st);
+  DGCHECK(jd.alloc(n * sizeof(PackJob)));
+  hipError_t e = hipMemcpyAsync(jd.p, jobs, n * sizeof(PackJob), hipMemcpyHostToDevice, st);
+  if (e != hipSuccess) { dg_set_error("op_pack_jobs: upload failed: %s", hipGetErrorString(e)); return DG_ERR_HIP; }
+  return dg_pack_weights_batch(jd.as<PackJob>(), n, nb, st);
+}
+
 extern "C" {
 
 // ---- single operators (unit tests) ----
@@ -39,26 +48,19 @@ static int op_conv_run(ConvArgs a, const float* w_hwio, int Cin, int Cout, int K
   if (path == 9 && !dg_conv_igemm_ws5_supported(pl, a, true)) { dg_set_error("op_conv: the weight-stationary 5x5 kernel does not cover this shape"); return DG_ERR_UNSUPPORTED; }
   if (path == 1 && !dg_plan_mfma(pl)) { dg_set_error("op_conv: MFMA path not available for this shape"); return DG_ERR_UNSUPPORTED; }
   if (path != 2 && dg_plan_mfma(pl)) {
-    float* wp = nullptr;
-    HIPCHECK(hipMalloc((void**)&wp, pl.packedFloats * sizeof(float)));
-    int rc = dg_pack_weights(pl, w_hwio, Cin, Cout, 0, bwd, bwd, nullptr, wp, st);
-    if (rc == DG_OK) {
-      a.w = wp;
-      if (path == 7) {
-        if (dg_conv_igemm_wp_supported(pl, a, true)) rc = dg_conv_igemm_wp(pl, a, st);
-        else { dg_set_error("op_conv: the wave-private kernel does not cover this shape"); rc = DG_ERR_UNSUPPORTED; }
-      } else if (path == 9) {
-        rc = dg_conv_igemm_ws5(pl, a, st);
-      } else if (path == 6 || path == 1) {
-        // the workgroup-tile kernel itself (the reference the wave-private kernel must match bit for bit)
-        rc = dg_conv_igemm_tile(pl, a, st);
-      } else {
-        rc = dg_conv_igemm(pl, a, st);
-      }
+    DevTmp wp(st);
+    DGCHECK(wp.alloc(pl.packedFloats * sizeof(float)));
+    DGCHECK(dg_pack_weights(pl, w_hwio, Cin, Cout, 0, bwd, bwd, nullptr, wp.as<float>(), st));
+    a.w = wp.as<float>();
+    if (path == 7) {
+      if (dg_conv_igemm_wp_supported(pl, a, true)) return dg_conv_igemm_wp(pl, a, st);
+      dg_set_error("op_conv: the wave-private kernel does not cover this shape");
+      return DG_ERR_UNSUPPORTED;
     }
-    hipStreamSynchronize(st);
-    hipFree(wp);
-    return rc;
+    if (path == 9) return dg_conv_igemm_ws5(pl, a, st);
+    // 6 and 1: the workgroup-tile kernel itself (the reference the wave-private kernel must match bit for bit)
+    if (path == 6 || path == 1) return dg_conv_igemm_tile(pl, a, st);
+    return dg_conv_igemm(pl, a, st);
   }
   if (!bwd) conv_set_weights(&a, dg_plan_direct(), nullptr, w_hwio, Cin, Cout);
   else conv_set_weights_bwd(&a, dg_plan_direct(), nullptr, w_hwio, Cin, Cout);
@@ -83,17 +85,15 @@ int depgan_op_conv2d_stamps(const float* in, const float* w_hwio, float* out, in
   a.ep.relu = 1;
   ConvPlan pl = dg_plan_conv(KS, Cin, Cout);
   if (!dg_plan_mfma(pl)) { dg_set_error("no MFMA variant"); return DG_ERR_UNSUPPORTED; }
-  float* wp = nullptr;
-  HIPCHECK(hipMalloc((void**)&wp, pl.packedFloats * sizeof(float)));
-  int rc = dg_pack_weights(pl, w_hwio, Cin, Cout, 0, 0, 0, nullptr, wp, st);
-  a.w = wp;
-  for (int i = 0; i < reps && rc == DG_OK; ++i) {
+  DevTmp wp(st);
+  DGCHECK(wp.alloc(pl.packedFloats * sizeof(float)));
+  DGCHECK(dg_pack_weights(pl, w_hwio, Cin, Cout, 0, 0, 0, nullptr, wp.as<float>(), st));
+  a.w = wp.as<float>();
+  for (int i = 0; i < reps; ++i) {
     a.dbg = (i == reps - 1) ? stamps : nullptr;
-    rc = dg_conv_igemm(pl, a, st);
+    DGCHECK(dg_conv_igemm(pl, a, st));
   }
-  hipStreamSynchronize(st);
-  hipFree(wp);
-  return rc;
+  return DG_OK;
 }
 
 int depgan_op_conv2d(const float* in, const float* w_hwio, const float* bias, float* out, int B, int H, int W,
@@ -109,32 +109,26 @@ int depgan_op_conv2d_wgrad(const float* x, const float* dy, float* dw, int B, in
   hipStream_t st = (hipStream_t)stream;
   const bool big = (Cin % 4 == 0 && Cout % 4 == 0 && Cin >= 8);
   const size_t pf = big ? dg_wgrad_part_floats(KS, B, H, W, Cin, Cout) : dg_wgrad_small_part_floats(KS, B, H, W, Cin, Cout);
-  float* part = nullptr;
-  HIPCHECK(hipMalloc((void**)&part, pf * sizeof(float)));
-  WgradArgs a = wgrad_args(make_view(const_cast<float*>(x), H, W, Cin), make_view(const_cast<float*>(dy), H, W, Cout), part,
-                           B, H, W, Cin, Cout);
+  DevTmp part(st);
+  DGCHECK(part.alloc(pf * sizeof(float)));
+  WgradArgs a = wgrad_args(make_view(const_cast<float*>(x), H, W, Cin), make_view(const_cast<float*>(dy), H, W, Cout),
+                           part.as<float>(), B, H, W, Cin, Cout);
   int nch = 0;
-  int rc = big ? dg_wgrad(KS, a, &nch, st) : dg_wgrad_small(KS, a, &nch, st);
-  if (rc == DG_OK) rc = dg_wgrad_reduce(part, nch, KS * KS, Cin, Cout, nullptr, dw, nullptr, 0, 0, st);
-  hipStreamSynchronize(st);
-  hipFree(part);
-  return rc;
+  DGCHECK(big ? dg_wgrad(KS, a, &nch, st) : dg_wgrad_small(KS, a, &nch, st));
+  return dg_wgrad_reduce(a.part, nch, KS * KS, Cin, Cout, nullptr, dw, nullptr, 0, 0, st);
 }
 int depgan_op_conv2d_wgrad_bf16(const float* x, const float* dy, float* dw, int B, int H, int W, int Cin, int Cout,
                                 int KS, void* stream) {
   hipStream_t st = (hipStream_t)stream;
   if (!dg_wgrad_bf16_supported(KS, Cin, Cout)) { dg_set_error("op_wgrad_bf16: shape not covered"); return DG_ERR_UNSUPPORTED; }
   const size_t pf = dg_wgrad_bf16_part_floats(KS, B, H, W, Cin, Cout);
-  float* part = nullptr;
-  HIPCHECK(hipMalloc((void**)&part, pf * sizeof(float)));
-  WgradArgs a = wgrad_args(make_view(const_cast<float*>(x), H, W, Cin), make_view(const_cast<float*>(dy), H, W, Cout), part,
-                           B, H, W, Cin, Cout);
+  DevTmp part(st);
+  DGCHECK(part.alloc(pf * sizeof(float)));
+  WgradArgs a = wgrad_args(make_view(const_cast<float*>(x), H, W, Cin), make_view(const_cast<float*>(dy), H, W, Cout),
+                           part.as<float>(), B, H, W, Cin, Cout);
   int nch = 0;
-  int rc = dg_wgrad_bf16(KS, a, &nch, st);
-  if (rc == DG_OK) rc = dg_wgrad_reduce(part, nch, KS * KS, Cin, Cout, nullptr, dw, nullptr, 0, 0, st);
-  hipStreamSynchronize(st);
-  hipFree(part);
-  return rc;
+  DGCHECK(dg_wgrad_bf16(KS, a, &nch, st));
+  return dg_wgrad_reduce(a.part, nch, KS * KS, Cin, Cout, nullptr, dw, nullptr, 0, 0, st);
 }
 int depgan_op_deconv2x2(const float* in, const float* w_hwoi, const float* bias, const float* scale,
                         const float* shift, float* out, int B, int H, int W, int Cin, int Cout, int relu,
@@ -163,24 +157,18 @@ int depgan_op_deconv2x2_wgrad(const float* in, const float* dout, float* dw_hwoi
     return DG_ERR_UNSUPPORTED;
   }
   const size_t pf = dg_deconv_wgrad_part_floats(B, H, W, Cin, Cout);
-  float *part = nullptr, *col = nullptr;
-  HIPCHECK(hipMalloc((void**)&part, pf * sizeof(float)));
-  if (hipMalloc((void**)&col, (pf / ((size_t)Cin * Cout)) * Cout * sizeof(float)) != hipSuccess) {
-    hipFree(part);
+  DevTmp part(st), col(st);
+  DGCHECK(part.alloc(pf * sizeof(float)));
+  if (col.alloc((pf / ((size_t)Cin * Cout)) * Cout * sizeof(float)) != DG_OK) {
     dg_set_error("op_deconv2x2_wgrad: out of memory");
     return DG_ERR_HIP;
   }
-  d.part = part;
-  d.colpart = colsum ? col : nullptr;
+  d.part = part.as<float>();
+  d.colpart = colsum ? col.as<float>() : nullptr;
   int nch = 0;
-  int rc = dg_deconv_wgrad(d, B, &nch, st);
-  if (rc == DG_OK)
-    rc = dg_wgrad_finish_rows(part, nch, 4, Cin, Cout, nullptr, dw_hwoi, nullptr, 0, 1, colsum ? col : nullptr, 4 * nch,
-                              Cout, nullptr, colsum, nullptr, st);
-  hipStreamSynchronize(st);
-  hipFree(part);
-  hipFree(col);
-  return rc;
+  DGCHECK(dg_deconv_wgrad(d, B, &nch, st));
+  return dg_wgrad_finish_rows(d.part, nch, 4, Cin, Cout, nullptr, dw_hwoi, nullptr, 0, 1, d.colpart, 4 * nch, Cout, nullptr,
+                              colsum, nullptr, st);
 }
 int depgan_op_maxpool(const float* in, float* out, int B, int Ho, int Wo, int C, void* stream) {
   return dg_maxpool(make_view(const_cast<float*>(in), 2 * Ho, 2 * Wo, C), make_view(out, Ho, Wo, C), B, Ho, Wo, C,
@@ -201,28 +189,25 @@ int depgan_eval_counts(const float* x, int nicg, const double* pred, const float
                        double thr, long long out_host[DEPGAN_EVAL_NCOUNT], void* stream) {
   if (!x || !pred || !out_host || nicg < 1 || npix < 0) { dg_set_error("eval_counts: bad argument"); return DG_ERR_ARG; }
   hipStream_t st = (hipStream_t)stream;
-  unsigned long long* dev = nullptr;
-  HIPCHECK(hipMalloc((void**)&dev, DEPGAN_EVAL_NCOUNT * sizeof(unsigned long long)));
-  int rc = dg_eval_counts(x, nicg, pred, code_real, mask1, wmh1, mask2, wmh2, prob2, (size_t)npix, thr, dev, st);
-  if (rc == DG_OK) {
-    unsigned long long h[DEPGAN_EVAL_NCOUNT];
-    if (hipMemcpyAsync(h, dev, sizeof(h), hipMemcpyDeviceToHost, st) != hipSuccess ||
-        hipStreamSynchronize(st) != hipSuccess) {
-      dg_set_error("eval_counts: copy back failed");
-      rc = DG_ERR_HIP;
-    } else {
-      for (int k = 0; k < DEPGAN_EVAL_NCOUNT; ++k) out_host[k] = (long long)h[k];
-    }
+  DevTmp dev(st);
+  DGCHECK(dev.alloc(DEPGAN_EVAL_NCOUNT * sizeof(unsigned long long)));
+  DGCHECK(dg_eval_counts(x, nicg, pred, code_real, mask1, wmh1, mask2, wmh2, prob2, (size_t)npix, thr,
+                         dev.as<unsigned long long>(), st));
+  unsigned long long h[DEPGAN_EVAL_NCOUNT];
+  if (hipMemcpyAsync(h, dev.p, sizeof(h), hipMemcpyDeviceToHost, st) != hipSuccess ||
+      hipStreamSynchronize(st) != hipSuccess) {
+    dg_set_error("eval_counts: copy back failed");
+    return DG_ERR_HIP;
   }
-  hipFree(dev);
-  return rc;
+  for (int k = 0; k < DEPGAN_EVAL_NCOUNT; ++k) out_host[k] = (long long)h[k];
+  return DG_OK;
 }
 
 
 // ---- learning-phase-1 operators (train_ops.hip), as uresnet.hip calls them; each view is NHWC with the strides
 // (sB, sY, sX) in floats and channel stride 1 ----
-static int op_alloc(float** p, size_t floats, const char* who) {
-  if (hipMalloc((void**)p, (floats ? floats : 1) * sizeof(float)) != hipSuccess) {
+static int op_alloc(DevTmp* t, size_t floats, const char* who) {
+  if (t->alloc((floats ? floats : 1) * sizeof(float)) != DG_OK) {
     dg_set_error("%s: out of device memory (%zu floats)", who, floats);
     return DG_ERR_HIP;
   }
@@ -231,7 +216,6 @@ static int op_alloc(float** p, size_t floats, const char* who) {
 static size_t op_scratch(long scratch_floats, size_t need) { return scratch_floats > 0 ? (size_t)scratch_floats : need; }
 
 // ---- the fp32 convolution kernels with the whole fused epilogue and strided views (unit tests) ----
-static bool op_view_bad(const float* p, long sB, long sY, long sX) { return !p || sB < 1 || sY < 1 || sX < 1; }
 
 int depgan_op_conv2d_fused(const float* in, long isB, long isY, long isX, const float* w_hwio, const float* bias,
                            const float* scale, const float* shift, const float* film_mul, const float* film_add,
@@ -240,10 +224,10 @@ int depgan_op_conv2d_fused(const float* in, long isB, long isY, long isX, const 
                            long msY, long msX, float* pool, long qsB, long qsY, long qsX, const float* head_w,
                            const float* head_b, float* head_out, int head_tanh, int head_skip_out, int B, int H, int W,
                            int Cin, int Cout, int KS, int relu, int accumulate, int path, int bwd, void* stream) {
-  if (op_view_bad(in, isB, isY, isX) || op_view_bad(out, osB, osY, osX) || !w_hwio || B < 1 || H < 1 || W < 1 || Cin < 1 ||
-      Cout < 1 || (KS != 1 && KS != 3 && KS != 5) || (out_pre && op_view_bad(out_pre, psB, psY, psX)) ||
-      (res && op_view_bad(res, rsB, rsY, rsX)) || (mask && op_view_bad(mask, msB, msY, msX)) ||
-      (pool && op_view_bad(pool, qsB, qsY, qsX))) {
+  if (op_view_bad_batched(in, isB, isY, isX) || op_view_bad_batched(out, osB, osY, osX) || !w_hwio || B < 1 || H < 1 || W < 1 || Cin < 1 ||
+      Cout < 1 || (KS != 1 && KS != 3 && KS != 5) || (out_pre && op_view_bad_batched(out_pre, psB, psY, psX)) ||
+      (res && op_view_bad_batched(res, rsB, rsY, rsX)) || (mask && op_view_bad_batched(mask, msB, msY, msX)) ||
+      (pool && op_view_bad_batched(pool, qsB, qsY, qsX))) {
     dg_set_error("op_conv2d_fused: null or non-positive argument");
     return DG_ERR_ARG;
   }
@@ -269,26 +253,13 @@ int depgan_op_conv2d_fused(const float* in, long isB, long isY, long isX, const 
   return op_conv_run(a, w_hwio, Cin, Cout, KS, path, bwd ? 1 : 0, (hipStream_t)stream);
 }
 
-// upload and run pack jobs whose destinations interleave (GLayer::wpb_all); synchronises: `jobs` is the caller's
-static int op_pack_jobs(PackJob* jobs, int n, hipStream_t st) {
-  const unsigned nb = dg_pack_layout(jobs, n);
-  PackJob* jd = nullptr;
-  HIPCHECK(hipMalloc((void**)&jd, n * sizeof(PackJob)));
-  hipError_t e = hipMemcpyAsync(jd, jobs, n * sizeof(PackJob), hipMemcpyHostToDevice, st);
-  int rc = DG_OK;
-  if (e != hipSuccess) { dg_set_error("op_pack_jobs: upload failed: %s", hipGetErrorString(e)); rc = DG_ERR_HIP; }
-  if (rc == DG_OK) rc = dg_pack_weights_batch(jd, n, nb, st);
-  hipStreamSynchronize(st);
-  hipFree(jd);
-  return rc;
-}
 
 int depgan_op_deconv2x2_igemm(int form, const float* in, long isB, long isY, long isX, const float* w_hwoi,
                               const float* bias, const float* scale, const float* shift, float* out, long osB, long osY,
                               long osX, const float* mask, long msB, long msY, long msX, int B, int H, int W, int Cin,
                               int Cout, int relu, int path, void* stream) {
-  if (op_view_bad(in, isB, isY, isX) || op_view_bad(out, osB, osY, osX) || !w_hwoi || B < 1 || H < 1 || W < 1 || Cin < 1 ||
-      Cout < 1 || (mask && op_view_bad(mask, msB, msY, msX))) {
+  if (op_view_bad_batched(in, isB, isY, isX) || op_view_bad_batched(out, osB, osY, osX) || !w_hwoi || B < 1 || H < 1 || W < 1 || Cin < 1 ||
+      Cout < 1 || (mask && op_view_bad_batched(mask, msB, msY, msX))) {
     dg_set_error("op_deconv2x2_igemm: null or non-positive argument");
     return DG_ERR_ARG;
   }
@@ -305,77 +276,69 @@ int depgan_op_deconv2x2_igemm(int form, const float* in, long isB, long isY, lon
   auto covered = [&](const ConvPlan& p) { return dg_plan_mfma(p) && (path == 3) == dg_plan_bf16(p); };
   hipStream_t st = (hipStream_t)stream;
   ConvArgs a = conv_args(null_view(), null_view(), B, H, W, 0, 0);   // views and channels by form, below
-  float* wp = nullptr;
-  int rc = DG_OK;
+  DevTmp wt(st);
   if (form == 0) {
     // as g_forward: four 1x1 convolutions of one input, tap (di, dj) writing the pixel grid (2i+di, 2j+dj), one launch
     const ConvPlan pf = plan(Cin, Cout);
     if (!covered(pf)) { dg_set_error("op_deconv2x2_igemm: no MFMA plan for %d -> %d on path %d", Cin, Cout, path); return DG_ERR_UNSUPPORTED; }
     const TView o = op_view(out, osB, osY, osX);
     a.in = op_view(in, isB, isY, isX);
-    a.out = strided2(o, 0, 0);
     a.Cin = Cin; a.Cout = Cout;
     a.ep.bias = bias; a.ep.scale = scale; a.ep.shift = shift; a.ep.relu = relu;
-    a.groups = 4;
-    HIPCHECK(hipMalloc((void**)&wp, 4 * pf.packedFloats * sizeof(float)));
-    for (int t = 0; t < 4 && rc == DG_OK; ++t) {
-      float* dst = wp + (size_t)t * pf.packedFloats;
-      rc = dg_pack_weights(pf, w_hwoi + (size_t)t * Cout * Cin, Cin, Cout, 1, 0, 0, nullptr, dst, st);
-      a.w_group[t] = dst;
-      a.out_group_off[t] = strided2(o, t / 2, t % 2).p - a.out.p;
+    DGCHECK(wt.alloc(4 * pf.packedFloats * sizeof(float)));
+    const float* panels[4];
+    for (int t = 0; t < 4; ++t) {
+      float* dst = wt.as<float>() + (size_t)t * pf.packedFloats;
+      DGCHECK(dg_pack_weights(pf, w_hwoi + (size_t)t * Cout * Cin, Cin, Cout, 1, 0, 0, nullptr, dst, st));
+      panels[t] = dst;
     }
-    a.w = wp;
-    if (rc == DG_OK) rc = dg_conv_igemm(pf, a, st);
-  } else {
-    // as deconv_bwd_data: in = the upstream gradient (B, 2H, 2W, Cout), out = dIn (B, H, W, Cin)
-    const ConvPlan pb = plan(Cout, Cin);
-    if (!covered(pb)) { dg_set_error("op_deconv2x2_igemm: no MFMA plan for %d -> %d on path %d", Cout, Cin, path); return DG_ERR_UNSUPPORTED; }
-    const TView d = op_view(in, isB, isY, isX);
-    a.out = op_view(out, osB, osY, osX);
-    a.Cout = Cin;
-    a.ep.mask = op_view_or_null(mask, msB, msY, msX);
-    if (form == 1) {
-      const ConvPlan pbf = plan(4 * Cout, Cin);
-      if (!(pbf.family == pb.family && pbf.planes == pb.planes && (Cout % pb.CK) == 0 && pbf.packedFloats == 4 * pb.packedFloats)) {
-        dg_set_error("op_deconv2x2_igemm: the gathered 1x1 form does not cover %d -> %d", Cout, Cin);
-        return DG_ERR_UNSUPPORTED;
-      }
-      HIPCHECK(hipMalloc((void**)&wp, pbf.packedFloats * sizeof(float)));
-      // the four per-tap panels interleaved per channel tile, as refresh_generator builds GLayer::wpb_all
-      const size_t blk = (size_t)pb.nCC * pb.NT * pb.CK;   // elements
-      PackJob jobs[4];
-      for (int t = 0; t < 4 && rc == DG_OK; ++t) {
-        float* dst = reinterpret_cast<float*>(reinterpret_cast<char*>(wp) + t * blk * dg_plan_elem_bytes(pb));
-        rc = dg_pack_job(pb, w_hwoi + (size_t)t * Cout * Cin, Cin, Cout, 1, 1, 0, nullptr, dst, 4 * blk, &jobs[t]);
-      }
-      if (rc == DG_OK) rc = op_pack_jobs(jobs, 4, st);
-      deconv_gather_k(&a, d, Cout, pb.CK);
-      a.w = wp;
-      if (rc == DG_OK) rc = dg_conv_igemm(pbf, a, st);
-    } else {
-      HIPCHECK(hipMalloc((void**)&wp, 4 * pb.packedFloats * sizeof(float)));
-      a.Cin = Cout;
-      for (int t = 0; t < 4 && rc == DG_OK; ++t) {
-        float* dst = wp + (size_t)t * pb.packedFloats;
-        rc = dg_pack_weights(pb, w_hwoi + (size_t)t * Cout * Cin, Cin, Cout, 1, 1, 0, nullptr, dst, st);
-        if (rc != DG_OK) break;
-        a.in = strided2(d, t / 2, t % 2);
-        a.w = dst;
-        a.ep.accumulate = (t > 0);
-        rc = dg_conv_igemm(pb, a, st);
-      }
-    }
+    deconv_groups(&a, o, panels);
+    return dg_conv_igemm(pf, a, st);
   }
-  hipStreamSynchronize(st);
-  hipFree(wp);
-  return rc;
+  // as deconv_bwd_data: in = the upstream gradient (B, 2H, 2W, Cout), out = dIn (B, H, W, Cin)
+  const ConvPlan pb = plan(Cout, Cin);
+  if (!covered(pb)) { dg_set_error("op_deconv2x2_igemm: no MFMA plan for %d -> %d on path %d", Cout, Cin, path); return DG_ERR_UNSUPPORTED; }
+  const TView d = op_view(in, isB, isY, isX);
+  a.out = op_view(out, osB, osY, osX);
+  a.Cout = Cin;
+  a.ep.mask = op_view_or_null(mask, msB, msY, msX);
+  if (form == 1) {
+    const ConvPlan pbf = plan(4 * Cout, Cin);
+    if (!(pbf.family == pb.family && pbf.planes == pb.planes && (Cout % pb.CK) == 0 && pbf.packedFloats == 4 * pb.packedFloats)) {
+      dg_set_error("op_deconv2x2_igemm: the gathered 1x1 form does not cover %d -> %d", Cout, Cin);
+      return DG_ERR_UNSUPPORTED;
+    }
+    DGCHECK(wt.alloc(pbf.packedFloats * sizeof(float)));
+    // the four per-tap panels interleaved per channel tile, as refresh_generator builds GLayer::wpb_all
+    const size_t blk = (size_t)pb.nCC * pb.NT * pb.CK;   // elements
+    PackJob jobs[4];
+    for (int t = 0; t < 4; ++t) {
+      float* dst = reinterpret_cast<float*>(wt.as<char>() + t * blk * dg_plan_elem_bytes(pb));
+      DGCHECK(dg_pack_job(pb, w_hwoi + (size_t)t * Cout * Cin, Cin, Cout, 1, 1, 0, nullptr, dst, 4 * blk, &jobs[t]));
+    }
+    DGCHECK(op_pack_jobs(jobs, 4, st));
+    deconv_gather_k(&a, d, Cout, pb.CK);
+    a.w = wt.as<float>();
+    return dg_conv_igemm(pbf, a, st);
+  }
+  DGCHECK(wt.alloc(4 * pb.packedFloats * sizeof(float)));
+  a.Cin = Cout;
+  for (int t = 0; t < 4; ++t) {
+    float* dst = wt.as<float>() + (size_t)t * pb.packedFloats;
+    DGCHECK(dg_pack_weights(pb, w_hwoi + (size_t)t * Cout * Cin, Cin, Cout, 1, 1, 0, nullptr, dst, st));
+    a.in = strided2(d, t / 2, t % 2);
+    a.w = dst;
+    a.ep.accumulate = (t > 0);
+    DGCHECK(dg_conv_igemm(pb, a, st));
+  }
+  return DG_OK;
 }
 
 int depgan_op_conv2d_wgrad_ex(const float* x, long xsB, long xsY, long xsX, const float* dy, long dsB, long dsY,
                               long dsX, const float* scale, float* dw, float* raw, int accumulate, int oi,
                               int colB, const float* colscale, float* colout, float* colraw, int B, int H, int W,
                               int Cin, int Cout, int KS, int bf16, void* stream) {
-  if (op_view_bad(x, xsB, xsY, xsX) || op_view_bad(dy, dsB, dsY, dsX) || !dw || B < 1 || H < 1 || W < 1 || Cin < 1 || Cout < 1 ||
+  if (op_view_bad_batched(x, xsB, xsY, xsX) || op_view_bad_batched(dy, dsB, dsY, dsX) || !dw || B < 1 || H < 1 || W < 1 || Cin < 1 || Cout < 1 ||
       (KS != 1 && KS != 3 && KS != 5)) {
     dg_set_error("op_conv2d_wgrad_ex: null or non-positive argument");
     return DG_ERR_ARG;
@@ -399,17 +362,14 @@ int depgan_op_conv2d_wgrad_ex(const float* x, long xsB, long xsY, long xsX, cons
   ws.scratchFloats = mfma ? ws.partFloats / ((size_t)KS * KS * Cin) : (cols ? dg_colsum_scratch(colB, H, W, Cout) : 0);
   ws.bf16 = bf16 != 0;
   ws.st = st;
-  DGCHECK(op_alloc(&ws.part, ws.partFloats, "op_conv2d_wgrad_ex"));
-  int rc = op_alloc(&ws.scratch, ws.scratchFloats, "op_conv2d_wgrad_ex");
-  if (rc == DG_OK) {
-    const ColSum cs = {colB, colscale, colout, colraw};
-    rc = wgrad_run(ws, KS, op_view(x, xsB, xsY, xsX), op_view(dy, dsB, dsY, dsX), B, H, W, Cin, Cout, scale, dw, raw, accumulate,
+  DevTmp part(st), scratch(st);
+  DGCHECK(op_alloc(&part, ws.partFloats, "op_conv2d_wgrad_ex"));
+  DGCHECK(op_alloc(&scratch, ws.scratchFloats, "op_conv2d_wgrad_ex"));
+  ws.part = part.as<float>();
+  ws.scratch = scratch.as<float>();
+  const ColSum cs = {colB, colscale, colout, colraw};
+  return wgrad_run(ws, KS, op_view(x, xsB, xsY, xsX), op_view(dy, dsB, dsY, dsX), B, H, W, Cin, Cout, scale, dw, raw, accumulate,
                    oi, cols ? &cs : nullptr);
-  }
-  hipStreamSynchronize(st);
-  hipFree(ws.part);
-  hipFree(ws.scratch);
-  return rc;
 }
 
 
@@ -418,12 +378,9 @@ int depgan_op_bn_moments(const float* x, long sB, long sY, long sX, int B, int H
   if (!x || !mean || !var || B < 1 || H < 1 || W < 1 || C < 4) { dg_set_error("op_bn_moments: bad argument"); return DG_ERR_ARG; }
   hipStream_t st = (hipStream_t)stream;
   const size_t cap = op_scratch(scratch_floats, dg_col_moments_scratch(B, H, W, C));
-  float* scratch = nullptr;
+  DevTmp scratch(st);
   DGCHECK(op_alloc(&scratch, cap, "op_bn_moments"));
-  int rc = dg_col_moments(op_view(x, sB, sY, sX), B, H, W, C, mean, var, scratch, cap, st);
-  hipStreamSynchronize(st);
-  hipFree(scratch);
-  return rc;
+  return dg_col_moments(op_view(x, sB, sY, sX), B, H, W, C, mean, var, scratch.as<float>(), cap, st);
 }
 
 int depgan_op_bn_backward(const float* dy, const float* raw, float* draw, long sB, long sY, long sX, int B, int H, int W,
@@ -435,23 +392,18 @@ int depgan_op_bn_backward(const float* dy, const float* raw, float* draw, long s
   }
   hipStream_t st = (hipStream_t)stream;
   const size_t cap = op_scratch(scratch_floats, dg_colsum_pair_scratch(B, H, W, C));
-  float *scratch = nullptr, *coef = nullptr;
+  DevTmp scratch(st), coeft(st);
   DGCHECK(op_alloc(&scratch, cap, "op_bn_backward"));
-  int rc = op_alloc(&coef, (size_t)8 * C, "op_bn_backward");
-  if (rc == DG_OK) {
-    // uresnet.hip: dg_bn_train_prepare (s, t, rstd) in the forward; dg_colsum_pair -> dg_bn_bwd_coeffs -> dg_axpby_ch
-    float *s = coef, *t = coef + C, *rstd = coef + 2 * C, *sums = coef + 3 * C, *cA = coef + 5 * C, *cB = coef + 6 * C,
-          *cC = coef + 7 * C;
-    const TView dyv = op_view(dy, sB, sY, sX), rawv = op_view(raw, sB, sY, sX), dv = op_view(draw, sB, sY, sX);
-    rc = dg_bn_train_prepare(gamma, gamma, mean, var, eps, 0.f, 0.f, nullptr, nullptr, s, t, rstd, C, st);  // t unused
-    if (rc == DG_OK) rc = dg_colsum_pair(dyv, rawv, mean, B, H, W, C, sums, scratch, cap, st);
-    if (rc == DG_OK) rc = dg_bn_bwd_coeffs(sums, mean, rstd, s, invN, dyscale, dgamma, dbeta, cA, cB, cC, C, st);
-    if (rc == DG_OK) rc = dg_axpby_ch(dyv, rawv, dv, B, H, W, C, cA, cB, cC, st);
-  }
-  hipStreamSynchronize(st);
-  hipFree(scratch);
-  hipFree(coef);
-  return rc;
+  DGCHECK(op_alloc(&coeft, (size_t)8 * C, "op_bn_backward"));
+  // uresnet.hip: dg_bn_train_prepare (s, t, rstd) in the forward; dg_colsum_pair -> dg_bn_bwd_coeffs -> dg_axpby_ch
+  float* const coef = coeft.as<float>();
+  float *s = coef, *t = coef + C, *rstd = coef + 2 * C, *sums = coef + 3 * C, *cA = coef + 5 * C, *cB = coef + 6 * C,
+        *cC = coef + 7 * C;
+  const TView dyv = op_view(dy, sB, sY, sX), rawv = op_view(raw, sB, sY, sX), dv = op_view(draw, sB, sY, sX);
+  DGCHECK(dg_bn_train_prepare(gamma, gamma, mean, var, eps, 0.f, 0.f, nullptr, nullptr, s, t, rstd, C, st));  // t unused
+  DGCHECK(dg_colsum_pair(dyv, rawv, mean, B, H, W, C, sums, scratch.as<float>(), cap, st));
+  DGCHECK(dg_bn_bwd_coeffs(sums, mean, rstd, s, invN, dyscale, dgamma, dbeta, cA, cB, cC, C, st));
+  return dg_axpby_ch(dyv, rawv, dv, B, H, W, C, cA, cB, cC, st);
 }
 
 int depgan_op_affine_act(const float* in, float* out, float* out_pre, const float* res, long sB, long sY, long sX,
@@ -484,12 +436,9 @@ int depgan_op_softmax_ce4(const float* logits, const float* onehot, float* probs
   if (!logits || !probs || P < 1 || (onehot && (!dz || !loss_sum))) { dg_set_error("op_softmax_ce4: bad argument"); return DG_ERR_ARG; }
   hipStream_t st = (hipStream_t)stream;
   if (!onehot) return dg_softmax4(logits, probs, P, st);
-  float* scratch = nullptr;
+  DevTmp scratch(st);
   DGCHECK(op_alloc(&scratch, 1024, "op_softmax_ce4"));
-  int rc = dg_softmax_ce4(logits, onehot, probs, dz, loss_sum, P, scratch, st);
-  hipStreamSynchronize(st);
-  hipFree(scratch);
-  return rc;
+  return dg_softmax_ce4(logits, onehot, probs, dz, loss_sum, P, scratch.as<float>(), st);
 }
 
 int depgan_op_bn_rows_fwd(const float* x, float* y, int R, int C, int ld, const float* gamma, const float* beta,
@@ -531,19 +480,15 @@ extern "C++" {
 template <typename F>
 static int op_with_scratch(long scratch_floats, size_t need, const char* who, hipStream_t st, F&& call) {
   const size_t cap = op_scratch(scratch_floats, need);
-  float* scratch = nullptr;
+  DevTmp scratch(st);
   DGCHECK(op_alloc(&scratch, cap, who));
-  const int rc = call(scratch, cap);
-  hipStreamSynchronize(st);
-  hipFree(scratch);
-  return rc;
+  return call(scratch.as<float>(), cap);
 }
 // a job table on the device, as the model's upload_table makes it
 template <typename T>
-static int op_upload_jobs(const std::vector<T>& jobs, T** dev, const char* who) {
-  *dev = nullptr;
-  if (hipMalloc((void**)dev, jobs.size() * sizeof(T)) != hipSuccess) { dg_set_error("%s: out of device memory", who); return DG_ERR_HIP; }
-  if (hipMemcpy(*dev, jobs.data(), jobs.size() * sizeof(T), hipMemcpyHostToDevice) != hipSuccess) {
+static int op_upload_jobs(const std::vector<T>& jobs, DevTmp* dev, const char* who) {
+  if (dev->alloc(jobs.size() * sizeof(T)) != DG_OK) { dg_set_error("%s: out of device memory", who); return DG_ERR_HIP; }
+  if (hipMemcpy(dev->p, jobs.data(), jobs.size() * sizeof(T), hipMemcpyHostToDevice) != hipSuccess) {
     dg_set_error("%s: job table upload failed", who);
     return DG_ERR_HIP;
   }
@@ -688,12 +633,9 @@ int depgan_op_bn_prepare_batch(void* const* ptrs, const int* C, int njobs, float
                (float*)q[5], (float*)q[6], (float*)q[7], C[j]};
   }
   hipStream_t st = (hipStream_t)stream;
-  BnJob* dev = nullptr;
-  int rc = op_upload_jobs(jobs, &dev, "op_bn_prepare_batch");
-  if (rc == DG_OK) rc = dg_bn_prepare_batch(dev, njobs, eps, st);
-  hipStreamSynchronize(st);
-  hipFree(dev);
-  return rc;
+  DevTmp dev(st);
+  DGCHECK(op_upload_jobs(jobs, &dev, "op_bn_prepare_batch"));
+  return dg_bn_prepare_batch(dev.as<BnJob>(), njobs, eps, st);
 }
 
 int depgan_op_bn_gamma_grad_batch(void* const* ptrs, const int* dims, int njobs, void* stream) {
@@ -714,12 +656,9 @@ int depgan_op_bn_gamma_grad_batch(void* const* ptrs, const int* dims, int njobs,
     nblocks += d[1];   // one block per output channel, jobs back to back (the model's g_gamma_jobs)
   }
   hipStream_t st = (hipStream_t)stream;
-  GammaJob* dev = nullptr;
-  int rc = op_upload_jobs(jobs, &dev, "op_bn_gamma_grad_batch");
-  if (rc == DG_OK) rc = dg_bn_gamma_grad_batch(dev, njobs, nblocks, st);
-  hipStreamSynchronize(st);
-  hipFree(dev);
-  return rc;
+  DevTmp dev(st);
+  DGCHECK(op_upload_jobs(jobs, &dev, "op_bn_gamma_grad_batch"));
+  return dg_bn_gamma_grad_batch(dev.as<GammaJob>(), njobs, nblocks, st);
 }
 
 // NoiseParams / NoiseGrads over packed buffers (include/depgan.h)
