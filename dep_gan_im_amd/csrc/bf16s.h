@@ -46,6 +46,9 @@ struct ConvArgsH {
 // bf16-in / bf16-out implicit GEMM on v_mfma_f32_32x32x16_bf16, KS in {1, 3}; Cin % 8 == 0, Cout % 32 == 0, every view
 // 16-byte aligned (pointer and strides).  Argument checks come before the launch.
 int dg_conv_bf16s(int KS, const ConvArgsH& a, hipStream_t st);
+// every check of dg_conv_bf16s but the weight panels' pointers, no HIP call: what an entry that packs its weights into a
+// temporary runs first, so that a call it refuses allocates and launches nothing
+int dg_conv_bf16s_check(int KS, const ConvArgsH& a);
 const char* dg_conv_bf16s_name(int KS, bool head = false);
 
 // gen_0: 3x3, Cin in {1, 2}, dense fp32 input, HWIO fp32 weights, affine + ReLU, bf16 output; Cout % 8 == 0, <= 32

@@ -13,6 +13,7 @@ struct ConvArgsHT : ConvArgsH {
   unsigned char* fdec;   // dense, 4-byte aligned, B H W Cout / 8 bytes
 };
 int dg_conv_bf16s_train(const ConvArgsHT& a, hipStream_t st);
+int dg_conv_bf16s_train_check(const ConvArgsHT& a);   // its checks but the weight panel's pointer, no HIP call
 static inline size_t dg_film_dec_bytes(int B, int H, int W, int C) { return (size_t)B * H * W * (C / 8); }
 
 // Backward-data (3x3, or 1x1 with ConvArgs::cpt gathering the four grids of a transposed convolution) on the same

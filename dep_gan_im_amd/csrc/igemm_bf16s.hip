@@ -71,7 +71,7 @@ const char* dg_conv_bf16s_name(int KS, bool head) {
   return KS == 3 ? "igemm_bf16s_kernel<3, 9>" : "igemm_bf16s_kernel<1, 1>";
 }
 
-int dg_conv_bf16s(int KS, const ConvArgsH& a, hipStream_t st) {
+int dg_conv_bf16s_check(int KS, const ConvArgsH& a) {
   if (KS != 1 && KS != 3) { dg_set_error("dg_conv_bf16s: kernel size %d (1 or 3)", KS); return DG_ERR_UNSUPPORTED; }
   if (!a.in.p || !a.out.p || a.B < 1 || a.H < 1 || a.W < 1) { dg_set_error("dg_conv_bf16s: bad argument"); return DG_ERR_ARG; }
   if (a.Cin < 8 || (a.Cin % 8) || a.Cout < 32 || (a.Cout % 32)) {
@@ -81,11 +81,7 @@ int dg_conv_bf16s(int KS, const ConvArgsH& a, hipStream_t st) {
   const int ng = a.groups > 1 ? a.groups : 1;
   if (ng != 1 && ng != 4) { dg_set_error("dg_conv_bf16s: groups must be 0, 1 or 4"); return DG_ERR_ARG; }
   bool al = aligned16_h(a.in) && aligned16_h(a.out) && aligned16_h(a.ep.res) && aligned16_h(a.ep.pool);
-  for (int g = 0; g < ng && ng > 1; ++g) {
-    if (!a.w_group[g]) { dg_set_error("dg_conv_bf16s: null weight panel of group %d", g); return DG_ERR_ARG; }
-    al = al && !(a.out_group_off[g] % 8);
-  }
-  if (ng == 1 && !a.w) { dg_set_error("dg_conv_bf16s: null weight panel"); return DG_ERR_ARG; }
+  for (int g = 0; g < ng && ng > 1; ++g) al = al && !(a.out_group_off[g] % 8);
   if (!al) { dg_set_error("dg_conv_bf16s: every view must be 16-byte aligned (pointer, strides in multiples of 8 elements)"); return DG_ERR_ARG; }
   if (!offsets_fit(a.in) || !offsets_fit(a.out) || !offsets_fit(a.ep.res) || !offsets_fit(a.ep.pool)) {
     dg_set_error("dg_conv_bf16s: view strides out of range");
@@ -107,9 +103,19 @@ int dg_conv_bf16s(int KS, const ConvArgsH& a, hipStream_t st) {
       dg_set_error("dg_conv_bf16s: the fused head needs its weights (16-byte aligned) and bias");
       return DG_ERR_ARG;
     }
-    return launch_bf16s<3, 9, true>(a, st);
+    return DG_OK;
   }
   if (a.ep.head_skip_out) { dg_set_error("dg_conv_bf16s: head_skip_out without a fused head"); return DG_ERR_ARG; }
+  return DG_OK;
+}
+
+int dg_conv_bf16s(int KS, const ConvArgsH& a, hipStream_t st) {
+  DGCHECK(dg_conv_bf16s_check(KS, a));
+  const int ng = a.groups > 1 ? a.groups : 1;
+  for (int g = 0; g < ng && ng > 1; ++g)
+    if (!a.w_group[g]) { dg_set_error("dg_conv_bf16s: null weight panel of group %d", g); return DG_ERR_ARG; }
+  if (ng == 1 && !a.w) { dg_set_error("dg_conv_bf16s: null weight panel"); return DG_ERR_ARG; }
+  if (a.ep.head_out) return launch_bf16s<3, 9, true>(a, st);
   return KS == 3 ? launch_bf16s<3, 9, false>(a, st) : launch_bf16s<1, 1, false>(a, st);
 }
 

@@ -27,8 +27,8 @@ static bool al16(const TViewH& v) {
 }
 static bool fits(const TViewH& v) { return v.sX > 0 && v.sY > 0 && v.sB >= 0 && 2 * (4 * v.sY + 16 * v.sX + 32) < 0x7FFFFFFFL; }
 
-int dg_conv_bf16s_train(const ConvArgsHT& a, hipStream_t st) {
-  if (!a.in.p || !a.out.p || !a.w || !a.u.p || !a.fdec || a.B < 1 || a.H < 1 || a.W < 1) {
+int dg_conv_bf16s_train_check(const ConvArgsHT& a) {
+  if (!a.in.p || !a.out.p || !a.u.p || !a.fdec || a.B < 1 || a.H < 1 || a.W < 1) {
     dg_set_error("dg_conv_bf16s_train: bad argument");
     return DG_ERR_ARG;
   }
@@ -52,6 +52,13 @@ int dg_conv_bf16s_train(const ConvArgsHT& a, hipStream_t st) {
   }
   const long total = (long)cdiv(a.W, 16) * cdiv(a.H, 16) * a.B * cdiv(a.Cout, 32);
   if (total > 0x7FFFFFFFL) { dg_set_error("dg_conv_bf16s_train: %ld work items", total); return DG_ERR_UNSUPPORTED; }
+  return DG_OK;
+}
+
+int dg_conv_bf16s_train(const ConvArgsHT& a, hipStream_t st) {
+  DGCHECK(dg_conv_bf16s_train_check(a));
+  if (!a.w) { dg_set_error("dg_conv_bf16s_train: null weight panel"); return DG_ERR_ARG; }
+  const long total = (long)cdiv(a.W, 16) * cdiv(a.H, 16) * a.B * cdiv(a.Cout, 32);
   constexpr size_t lds_k = (size_t)(18 * 18 + 9 * 32) * 80;
   constexpr size_t lds_e = (size_t)4 * 64 * (32 + 4) * sizeof(float);
   constexpr size_t lds = lds_k > lds_e ? lds_k : lds_e;

@@ -35,6 +35,7 @@ static int op_conv2d_bf16s_impl(const char* who, const void* in, long isB, long 
   a.ep.pool = pool ? make_view_h(reinterpret_cast<__bf16*>(pool), H / 2, W / 2, Cout) : null_view_h();
   a.ep.head_w = head_w; a.ep.head_b = head_b; a.ep.head_out = head_out;
   a.ep.head_tanh = tanh_act; a.ep.head_skip_out = head_out ? skip_out : 0;
+  DGCHECK(dg_conv_bf16s_check(KS, a));   // alignment, pool parity, FiLM pairs: before the temporary and the pack launch
   DevTmp wp(st);
   DGCHECK(wp.alloc(pl.packedFloats * sizeof(float)));
   DGCHECK(dg_pack_weights(pl, w_hwio, Cin, Cout, 0, 0, 0, nullptr, wp.as<float>(), st));
@@ -79,9 +80,11 @@ int depgan_op_deconv2x2_bf16s(const void* in, long isB, long isY, long isX, cons
   a.ep.bias = bias; a.ep.scale = scale; a.ep.shift = shift; a.ep.relu = relu;
   a.ep.res = null_view_h();
   a.ep.pool = null_view_h();
+  const float* panels[4] = {nullptr, nullptr, nullptr, nullptr};
+  deconv_groups(&a, o, panels);          // the groups' output offsets are part of what is checked
+  DGCHECK(dg_conv_bf16s_check(1, a));
   DevTmp wp(st);
   DGCHECK(wp.alloc(4 * pl.packedFloats * sizeof(float)));
-  const float* panels[4];
   for (int t = 0; t < 4; ++t) {
     float* dst = wp.as<float>() + (size_t)t * pl.packedFloats;
     DGCHECK(dg_pack_weights(pl, w_hwoi + (size_t)t * Cout * Cin, Cin, Cout, 1, 0, 0, nullptr, dst, st));
@@ -142,6 +145,7 @@ int depgan_op_conv2d_film_train_bf16s(const void* in, long isB, long isY, long i
   a.ep.pool = null_view_h();
   a.u = make_view_h(reinterpret_cast<__bf16*>(u_out), H, W, Cout);
   a.fdec = dec_bits;
+  DGCHECK(dg_conv_bf16s_train_check(a));
   DevTmp wp(st);
   DGCHECK(wp.alloc(pl.packedFloats * sizeof(float)));
   DGCHECK(dg_pack_weights(pl, w_hwio, Cin, Cout, 0, 0, 0, nullptr, wp.as<float>(), st));

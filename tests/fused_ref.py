@@ -192,3 +192,104 @@ def wgrad(x, dy, k, dtype=torch.float64):
     y = F.conv2d(_nchw(x, dtype), w, padding=k // 2)
     (g,) = torch.autograd.grad(y, w, _nchw(dy, dtype))
     return g.permute(2, 3, 1, 0).contiguous().numpy()
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# bf16 activation STORAGE (depgan_op_*_bf16s): the value in front of the store is known exactly on the exact operands,
+# so the stored bf16 is its round-to-nearest-even -- one bit pattern (tests/test_bf16s_ref_cpu.py proves the pieces,
+# tests/test_gpu_bf16s_exact.py uses them).  Everything below is numpy on the bits of finite float32 values.
+# ---------------------------------------------------------------------------------------------------------------------
+def _u32(a):
+    return np.ascontiguousarray(a, np.float32).view(np.uint32).astype(np.uint64)
+
+
+def _f32(b):
+    return ((b << np.uint64(16)) & np.uint64(0xFFFFFFFF)).astype(np.uint32).view(np.float32)
+
+
+def rne_bf16(a):
+    """float32 -> nearest bf16, ties to even -> float32, by integer arithmetic on the bits (finite values)."""
+    b = _u32(a)
+    return _f32((b + np.uint64(0x7FFF) + ((b >> np.uint64(16)) & np.uint64(1))) >> np.uint64(16))
+
+
+def trunc_bf16(a):
+    """MUTANT: the low 16 bits dropped (round toward zero)."""
+    return _f32(_u32(a) >> np.uint64(16))
+
+
+def half_away_bf16(a):
+    """MUTANT: round to nearest, ties away from zero (sign-magnitude bits: adding to them grows the magnitude)."""
+    return _f32((_u32(a) + np.uint64(0x8000)) >> np.uint64(16))
+
+
+def is_bf16(a):
+    """every value representable in bf16 (low 16 bits of the float32 pattern clear)"""
+    return a is None or not (np.ascontiguousarray(a, np.float32).view(np.uint32) & 0xFFFF).any()
+
+
+MASKS_BF16 = rne_bf16(MASKS)       # {-1, -0.0, 0, RNE_bf16(1e-30), 1}: the mask operand is a bf16 view
+ZERO_FILM_CHANNEL = 3              # make_ops_bf16s: FiLM multiplier and addend forced to 0 on this channel
+
+
+def make_ops_bf16s(kind, rng, *a, **kw):
+    """make_ops (same draws, so the cases of the fp32 files keep their operands), then for the bf16-storage kernels:
+    exact + FiLM: channel ZERO_FILM_CHANNEL gets fmul = fadd = 0 in every sample, next to the (-1.25, 0, 2) make_ops
+    plants -- its FiLM value is exactly 0, its decision 0 and its output the residual; real: x and res rounded to bf16
+    first (they are stored activations)."""
+    o = make_ops(kind, rng, *a, **kw)
+    if kind == "exact":
+        if o.fmul is not None:
+            o.fmul[:, ZERO_FILM_CHANNEL] = 0.0
+            o.fadd[:, ZERO_FILM_CHANNEL] = 0.0
+        if o.mask is not None:
+            o.mask = rne_bf16(o.mask)
+    else:
+        o.x = rne_bf16(o.x)
+        if o.res is not None:
+            o.res = rne_bf16(o.res)
+        if o.mask is not None:
+            o.mask = rne_bf16(o.mask)
+    return o
+
+
+def pack_dec(dec):
+    """(B, H, W, C) booleans -> bytes: bit (c & 7) of byte [pixel * (C / 8) + c / 8] (include/depgan.h)."""
+    return np.packbits(np.ascontiguousarray(dec, bool).reshape(-1, 8), axis=-1, bitorder="little").ravel()
+
+
+def reference_bf16s(o, rnd=rne_bf16):
+    """The contract of the bf16-storage convolutions on EXACT operands (every float64 value of reference(o) is then a
+    float32 value, so the cast in front of `rnd` does not round): out = rnd(exact out), pool = pool2 of the STORED
+    values, head from the stored values, u = rnd(out_pre), dec = (FiLM value > 0) and its packed bytes."""
+    r = reference(o)
+    f32 = lambda a: a.astype(np.float32)   # noqa: E731
+    assert np.array_equal(f32(r["out"]).astype(np.float64), r["out"])
+    out = rnd(f32(r["out"]))
+    q = {"acc": r["acc"], "out_pre": r["out_pre"], "out_exact": r["out"], "out": out, "stages": list(r["stages"]),
+         "u": rnd(f32(r["out_pre"]))}
+    if not (out.shape[1] | out.shape[2]) & 1:
+        q["pool"] = pool2(out)
+    if o.head_w is not None:
+        q["stages"].pop()                  # reference()'s head of the unrounded values is not part of this contract
+        q["head"] = head(out, o)
+        q["stages"].append(q["head"])
+    if o.fmul is not None:
+        v = r["out_pre"] * o.fmul.astype(np.float64)[:, None, None, :] + o.fadd.astype(np.float64)[:, None, None, :]
+        q["dec"] = v > 0
+        q["dec_bits"] = pack_dec(q["dec"])
+    return q
+
+
+def unpool_mask(dpool, a, skip=None, last=False):
+    """depgan_op_unpool_mask(_bf16s): dpool (B, Ho, Wo, C) goes to the FIRST maximum of each 2x2 window of a
+    (B, 2Ho, 2Wo, C) in the order (0,0), (0,1), (1,0), (1,1); then + skip; then * (a > 0).  float64.
+    last: MUTANT taking the last maximum."""
+    B, Ho, Wo, Cc = dpool.shape
+    win = np.asarray(a, np.float64).reshape(B, Ho, 2, Wo, 2, Cc).transpose(0, 1, 3, 5, 2, 4).reshape(B, Ho, Wo, Cc, 4)
+    am = 3 - win[..., ::-1].argmax(-1) if last else win.argmax(-1)      # numpy: the first of equal maxima
+    g = (np.arange(4) == am[..., None]) * np.asarray(dpool, np.float64)[..., None]
+    g = g.reshape(B, Ho, Wo, Cc, 2, 2).transpose(0, 1, 4, 2, 5, 3).reshape(B, 2 * Ho, 2 * Wo, Cc)
+    if skip is not None:
+        g = g + np.asarray(skip, np.float64)
+    return np.where(np.asarray(a) > 0, g, 0.0)
