@@ -247,8 +247,7 @@ class Engine:
 
     def grad_arena(self, net):
         """(device pointer, number of floats) of a network's flat gradient arena (for the RCCL all-reduce)."""
-        nid = NET_IDS[net]
-        return self.lib.depgan_arena_ptr(self.h, nid, ARENA_GRADS), self.lib.depgan_arena_floats(self.h, nid, ARENA_GRADS)
+        return self.arena(net, ARENA_GRADS)
 
     # ---- the inference context ----
     @property
@@ -284,6 +283,13 @@ class Engine:
                              % (self.cfg.bf16_mfma, self.cfg.nc_out))
         return storage
 
+    def _set_mode(self, attr, entry, value):
+        """Tail of the three mode setters: hands an already validated "float32" / "bfloat16" to the library's setter
+        `entry` (0 / 1) and remembers it."""
+        if getattr(self, "h", None):
+            check(getattr(self.lib, entry)(self.h, 1 if value == "bfloat16" else 0), entry)
+        setattr(self, "_" + attr, value)
+
     @property
     def forward_only_storage(self):
         """How the FORWARD-ONLY generator passes of the training closures (the one inside every critic update and
@@ -299,10 +305,7 @@ class Engine:
     def forward_only_storage(self, value):
         value = self._check_storage(value)
         self._need_trainable("forward_only_storage")
-        if getattr(self, "h", None):
-            check(self.lib.depgan_set_fwd_only_storage(self.h, 1 if value == "bfloat16" else 0),
-                  "depgan_set_fwd_only_storage")
-        self._forward_only_storage = value
+        self._set_mode("forward_only_storage", "depgan_set_fwd_only_storage", value)
 
     @property
     def g_update_storage(self):
@@ -317,10 +320,7 @@ class Engine:
     def g_update_storage(self, value):
         value = self._check_storage(value)
         self._need_trainable("g_update_storage")
-        if getattr(self, "h", None):
-            check(self.lib.depgan_set_g_update_storage(self.h, 1 if value == "bfloat16" else 0),
-                  "depgan_set_g_update_storage")
-        self._g_update_storage = value
+        self._set_mode("g_update_storage", "depgan_set_g_update_storage", value)
 
     @property
     def critic16_pipe(self):
@@ -339,9 +339,7 @@ class Engine:
         if value == "bfloat16" and not (self.cfg.bf16_mfma and self.cfg.nc_out in (0, 1)):
             raise ValueError("critic16_pipe='bfloat16' needs an engine created with bf16_mfma=True (and nc_out=1); "
                              "this one has bf16_mfma=%d, nc_out=%d" % (self.cfg.bf16_mfma, self.cfg.nc_out))
-        if getattr(self, "h", None):
-            check(self.lib.depgan_set_critic16_pipe(self.h, 1 if value == "bfloat16" else 0), "depgan_set_critic16_pipe")
-        self._critic16_pipe = value
+        self._set_mode("critic16_pipe", "depgan_set_critic16_pipe", value)
 
     def g_forward(self, x, z, storage=None):
         """Model.predict of the generator.  storage: None = self.forward_storage; "bfloat16" keeps every inter-layer
@@ -382,10 +380,28 @@ class Engine:
         return out
 
     # ---- closures ----
+    def _xy(self, x, y2):
+        """One batch of inputs and targets on the device: (B, H, W, nicg) and (B, H, W, 1)."""
+        B = self.batch
+        return self._dev(x, (B, self.height, self.width, self.nicg)), self._dev(y2, (B, self.height, self.width, 1))
+
+    def _noises(self, zs):
+        """k noises for one batch, (k, B, 32[, 1]) or a list of k (B, 32[, 1]), as a contiguous (k, B*32) device
+        tensor; returns it and k."""
+        B = self.batch
+        if isinstance(zs, (list, tuple)):
+            zs = _torch().stack([self._dev(z).reshape(B, 32) for z in zs])
+        else:
+            zs = self._dev(zs)
+        k = int(zs.shape[0])
+        zs = zs.reshape(k, -1).contiguous()
+        if zs.shape[1] != B * 32:
+            raise ValueError("noises must be (k,%d,32,1)" % B)
+        return zs, k
+
     def _batch_inputs(self, x, y2, z, ep=None):
         B = self.batch
-        x = self._dev(x, (B, self.height, self.width, self.nicg))
-        y2 = self._dev(y2, (B, self.height, self.width, 1))
+        x, y2 = self._xy(x, y2)
         z = self._dev(z).reshape(-1)
         if z.numel() != B * 32:
             raise ValueError("noise must be (%d,32,1)" % B)
@@ -417,18 +433,8 @@ class Engine:
         """k forward-only loss evaluations on one batch with k noises (GT:868-877), one host sync.
         zs: (k, B, 32, 1) array / tensor or a list of k (B,32,1) noises.  Returns (k x 6 outputs, k x 8 sums)."""
         self._need_trainable("generator_eval_multi")
-        torch = _torch()
-        B = self.batch
-        x = self._dev(x, (B, self.height, self.width, self.nicg))
-        y2 = self._dev(y2, (B, self.height, self.width, 1))
-        if isinstance(zs, (list, tuple)):
-            zs = torch.stack([self._dev(z).reshape(B, 32) for z in zs])
-        else:
-            zs = self._dev(zs)
-        k = int(zs.shape[0])
-        zs = zs.reshape(k, -1).contiguous()
-        if zs.shape[1] != B * 32:
-            raise ValueError("noises must be (k,%d,32,1)" % B)
+        x, y2 = self._xy(x, y2)
+        zs, k = self._noises(zs)
         out, sums = (C.c_float * (6 * k))(), (C.c_float * (8 * k))()
         self._use_current_stream()
         self._check(self.lib.depgan_g_eval_multi(self.h, self._p(x), self._p(y2), self._p(zs), k, out, sums),
@@ -445,7 +451,6 @@ class Engine:
         gen: (x, y2, zs) -- one batch and its k noises (k, B, 32[,1]).
         Returns (critic_y2 outs n x 2, critic_dem outs n x 2, eval outs k x 6, train out 6, best index)."""
         self._need_trainable("gen_iteration")
-        torch = _torch()
         B = self.batch
         stride = B if batch_stride is None else int(batch_stride)
 
@@ -469,13 +474,8 @@ class Engine:
         xa, ya, za, ea, na = loop(y2_loop)
         xb, yb, zb, eb, nb = loop(dem_loop)
         xg, yg, zs = gen
-        xg = self._dev(xg, (B, self.height, self.width, self.nicg))
-        yg = self._dev(yg, (B, self.height, self.width, 1))
-        zs = self._dev(zs)
-        k = int(zs.shape[0])
-        zs = zs.reshape(k, -1).contiguous()
-        if zs.shape[1] != B * 32:
-            raise ValueError("noises must be (k,%d,32,1)" % B)
+        xg, yg = self._xy(xg, yg)
+        zs, k = self._noises(zs)
         if na + nb > _lib.MAX_CRITIC_STEPS or not 1 <= k <= _lib.MAX_MULTI:
             raise ValueError("gen_iteration: at most %d critic updates and %d noises" % (_lib.MAX_CRITIC_STEPS,
                                                                                        _lib.MAX_MULTI))
@@ -536,34 +536,26 @@ class Engine:
         """Keep a copy of the mixed pass's activations in every critic closure (depgan_debug_capture)."""
         check(self.lib.depgan_debug_capture(self.h, 1 if on else 0), "depgan_debug_capture")
 
+    def _debug_fetch(self, entry, name, dtype):
+        """Size-then-fill of the debug surface: asks `entry` for the shape (NULL destination), then for the data."""
+        fn, shape = getattr(self.lib, entry), (C.c_int * 4)()
+        check(fn(self.h, name.encode(), None, 0, shape), entry)
+        out = np.empty(tuple(shape), dtype)
+        check(fn(self.h, name.encode(), C.c_void_p(out.ctypes.data), out.size, shape), entry)
+        return out
+
     def debug_tensor(self, name):
         """An internal tensor of the last closure as a dense (N,H,W,C) float32 array (depgan_debug_tensor)."""
-        shape = (C.c_int * 4)()
-        check(self.lib.depgan_debug_tensor(self.h, name.encode(), None, 0, shape), "depgan_debug_tensor")
-        out = np.empty(tuple(shape), np.float32)
-        check(self.lib.depgan_debug_tensor(self.h, name.encode(), C.c_void_p(out.ctypes.data), out.size, shape),
-              "depgan_debug_tensor")
-        return out
+        return self._debug_fetch("depgan_debug_tensor", name, np.float32)
 
     def debug_film_decision_bf16s(self, layer):
         """The FiLM ReLU decisions (uint8, 0 / 1, (N, H, W, C)) the last training forward on bfloat16 storage stored for a
         FiLM layer ("gen_2", ...): what its backward masks with (depgan_debug_film_decision_bf16s)."""
-        shape = (C.c_int * 4)()
-        check(self.lib.depgan_debug_film_decision_bf16s(self.h, layer.encode(), None, 0, shape),
-              "depgan_debug_film_decision_bf16s")
-        out = np.empty(tuple(shape), np.uint8)
-        check(self.lib.depgan_debug_film_decision_bf16s(self.h, layer.encode(), C.c_void_p(out.ctypes.data), out.size, shape),
-              "depgan_debug_film_decision_bf16s")
-        return out
+        return self._debug_fetch("depgan_debug_film_decision_bf16s", layer, np.uint8)
 
     def debug_tensor_bf16s(self, name):
         """"g/out/<layer>" of the last bfloat16-storage g_forward, widened to float32 (depgan_debug_tensor_bf16s)."""
-        shape = (C.c_int * 4)()
-        check(self.lib.depgan_debug_tensor_bf16s(self.h, name.encode(), None, 0, shape), "depgan_debug_tensor_bf16s")
-        out = np.empty(tuple(shape), np.float32)
-        check(self.lib.depgan_debug_tensor_bf16s(self.h, name.encode(), C.c_void_p(out.ctypes.data), out.size, shape),
-              "depgan_debug_tensor_bf16s")
-        return out
+        return self._debug_fetch("depgan_debug_tensor_bf16s", name, np.float32)
 
     # ---- profiling ----
     def profile(self, on):

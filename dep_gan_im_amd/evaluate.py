@@ -28,8 +28,7 @@ import numpy as np
 
 from . import _lib
 
-NCOUNT = 20
-NCOUNT_LABEL = 18
+NCOUNT, NCOUNT_LABEL = _lib.EVAL_NCOUNT, _lib.EVAL_LABEL_NCOUNT      # DEPGAN_EVAL_*NCOUNT of include/depgan.h
 
 
 def _torch():

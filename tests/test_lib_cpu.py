@@ -209,3 +209,76 @@ def test_step_operator_entries_are_exported_and_bound(lib):
         assert name in _lib.EXPORTS, name
         assert hasattr(lib, name), name
         assert getattr(lib, name).argtypes, name + " has no argtypes"
+
+
+# ---- the binding is derived from include/depgan.h (dep_gan_im_amd/_lib.py::parse_header) ----
+
+def _pinned_signatures():
+    """argtypes / restype as the hand-kept table listed them before the binding was derived from the header (typed
+    pointers written as c_void_p), one entry of every declaration form."""
+    import ctypes as C
+    vp, i, L, f, u, s = C.c_void_p, C.c_int, C.c_long, C.c_float, C.c_uint, C.c_char_p
+    return {
+        "depgan_create": (i, [vp, vp]),
+        "depgan_destroy": (None, [vp]),
+        "depgan_param_info": (i, [vp, i, i, s, i, vp, vp, vp, vp]),
+        "depgan_arena_ptr": (vp, [vp, i, i]),
+        "depgan_arena_floats": (L, [vp, i, i]),
+        "depgan_data_prep_scratch_floats": (C.c_size_t, [i] * 3),
+        "depgan_last_error": (s, []),
+        "depgan_set_allreduce": (i, [vp, _lib.ALLREDUCE_FN, vp, i]),
+        "depgan_gen_iteration": (i, [vp, vp, vp, vp, vp, i, vp, vp, vp, vp, i, L, vp, vp, vp, i, vp, vp]),
+        "depgan_eval_counts": (i, [vp, i] + [vp] * 7 + [L, C.c_double, vp, vp]),
+        "depgan_op_affine_act": (i, [vp] * 4 + [L] * 3 + [vp] * 4 + [i] * 6 + [u, f, vp]),
+        "depgan_profile_read": (i, [vp, i, vp, vp, vp]),
+        # 47 parameters: four-word views of in / out / out_pre / res / mask / pool, 9 bare pointers, 13 ints, the stream
+        "depgan_op_conv2d_fused": (i, [vp, L, L, L] + [vp] * 6 + [i] + [vp, L, L, L] * 5 + [vp] * 3 + [i] * 12 + [vp]),
+        "depgan_op_unpool_mask_bf16s": (i, [vp, L, L, L] * 4 + [i] * 4 + [vp]),
+    }
+
+
+def test_derived_binding_matches_the_pinned_signatures(lib):
+    import ctypes as C
+    for name, (restype, argtypes) in _pinned_signatures().items():
+        fn = getattr(lib, name)
+        assert fn.restype is restype, (name, fn.restype)
+        assert list(fn.argtypes) == argtypes, (name, fn.argtypes)
+    hook = _lib.ALLREDUCE_FN
+    assert hook._restype_ is C.c_int and list(hook._argtypes_) == [C.c_void_p, C.c_void_p, C.c_long, C.c_void_p]
+    assert len(lib.depgan_gen_iteration.argtypes) == 18 and len(lib.depgan_op_conv2d_fused.argtypes) == 47
+
+
+def test_every_prototype_is_bound_with_the_header_s_parameter_count(lib):
+    """The count does not come from _lib's parser: names by the regex of test_library_exports_every_declared_symbol,
+    parameters by the commas between the parentheses of the comment-stripped text."""
+    hdr = open(os.path.join(ROOT, "include", "depgan.h")).read()
+    declared = set(re.findall(r"\b(depgan_[a-z0-9_]+)\s*\(", hdr)) - {"depgan_ctx", "depgan_config"}
+    assert set(_lib.EXPORTS) == declared and len(_lib.EXPORTS) == len(declared) >= 111
+    stripped = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
+    for name in sorted(declared):
+        found = re.findall(r"\b%s\s*\(([^()]*)\)\s*;" % name, stripped)
+        assert len(found) == 1, name
+        count = 0 if found[0].strip() == "void" else found[0].count(",") + 1
+        fn = getattr(lib, name)
+        assert fn.argtypes is not None and len(fn.argtypes) == count, (name, count, fn.argtypes)
+
+
+def test_header_parser_refuses_what_it_cannot_map(tmp_path):
+    with pytest.raises(_lib.DepganError, match="depgan_x"):
+        _lib.parse_header("int depgan_x(short a);")
+    with pytest.raises(_lib.DepganError, match="depgan_x"):
+        _lib.parse_header("int depgan_ok(int a);\nint depgan_x(int a")
+    missing = str(tmp_path / "include" / "depgan.h")
+    with pytest.raises(_lib.DepganError, match=re.escape(missing)):
+        _lib.read_header(missing)
+    ok = _lib.parse_header("int depgan_ok(int a);")
+    assert list(ok.prototypes) == ["depgan_ok"]
+
+
+def test_constants_taken_from_the_header_keep_their_values():
+    from dep_gan_im_amd import evaluate
+    assert (_lib.ABI_VERSION, _lib.MAX_MULTI, _lib.MAX_CRITIC_STEPS, _lib.RCCL_ID_BYTES) == (3, 32, 256, 128)
+    assert (evaluate.NCOUNT, evaluate.NCOUNT_LABEL) == (20, 18)
+    assert (_lib.NET_G, _lib.NET_D_Y2, _lib.NET_D_DEM) == (0, 1, 2)
+    assert (_lib.ARENA_PARAMS, _lib.ARENA_NONTRAINABLE, _lib.ARENA_GRADS, _lib.ARENA_ADAM_M, _lib.ARENA_ADAM_V) \
+        == (0, 1, 2, 3, 4)
