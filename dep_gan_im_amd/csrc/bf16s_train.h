@@ -38,6 +38,7 @@ struct WgradArgsH {
 bool dg_wgrad_bf16s_supported(int KS, int Cin, int Cout);
 size_t dg_wgrad_bf16s_part_floats(int KS, int B, int H, int W, int Cin, int Cout);
 int dg_wgrad_bf16s(int KS, const WgradArgsH& a, int* nchunks, hipStream_t st);
+int dg_wgrad_bf16s_plan(int KS, int B, int H, int W, int Cin, int Cout, int out[4]);   // as dg_wgrad_plan (common.h)
 
 // out(2Ho, 2Wo) = ((a > 0) ? skip + (argmax ? dpool : 0) : 0), `a` bf16; the arg-max of a 2x2 window is the FIRST
 // maximum in the order (0,0), (0,1), (1,0), (1,1) -- pool_bwd_kernel's rule.  C % 8 == 0.

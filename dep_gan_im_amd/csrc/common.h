@@ -345,3 +345,10 @@ int dg_wgrad_bf16(int KS, const WgradArgs& a, int* nchunks, hipStream_t st);
 // small-Cin wgrad (VALU), same slab format as dg_wgrad
 size_t dg_wgrad_small_part_floats(int KS, int B, int H, int W, int Cin, int Cout);
 int dg_wgrad_small(int KS, const WgradArgs& a, int* nchunks, hipStream_t st);
+
+// The launch plan each of these launchers computes for a shape, from the launcher's own chunking function and without a
+// launch or an allocation: out = {pixel tiles, tiles per workgroup, chunks (= gridDim.x = partial slabs), gridDim.y}.
+// A shape the launcher refuses returns the launcher's status.
+int dg_wgrad_plan(int KS, int B, int H, int W, int Cin, int Cout, int out[4]);
+int dg_wgrad_small_plan(int KS, int B, int H, int W, int Cin, int Cout, int out[4]);
+int dg_wgrad_bf16_plan(int KS, int B, int H, int W, int Cin, int Cout, int out[4]);

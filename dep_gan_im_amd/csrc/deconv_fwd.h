@@ -36,3 +36,5 @@ bool dg_deconv_wgrad_supported(int B, int H, int W, int Cin, int Cout, TView in,
 size_t dg_deconv_wgrad_part_floats(int B, int H, int W, int Cin, int Cout);
 // launches the kernel; *nchunks = number of partial slabs (and nchunks * 4 partial column rows) for dg_wgrad_finish_rows
 int dg_deconv_wgrad(DeconvWgradArgs a, int B, int* nchunks, hipStream_t st);
+// its plan for dense operands, no launch: out = {k-steps, steps per workgroup, workgroups along x, gridDim.y}
+int dg_deconv_wgrad_plan(int B, int H, int W, int Cin, int Cout, int out[4]);

@@ -210,6 +210,23 @@ size_t dg_deconv_wgrad_part_floats(int B, int H, int W, int Cin, int Cout) {
   return (size_t)(n > 0 ? n : 0) * 4 * Cin * Cout;
 }
 
+// the launch plan of dg_deconv_wgrad for a shape with dense operands, without launching (depgan_debug_wgrad_plan):
+// k-steps, steps per workgroup, workgroups along x, gridDim.y
+int dg_deconv_wgrad_plan(int B, int H, int W, int Cin, int Cout, int out[4]) {
+  if (!dg_deconv_wgrad_supported(B, H, W, Cin, Cout, make_view(nullptr, H, W, Cin), make_view(nullptr, 2 * H, 2 * W, Cout))) {
+    dg_set_error("dg_deconv_wgrad: shape %dx%dx%d %d->%d not covered by the fused kernel", B, H, W, Cin, Cout);
+    return DG_ERR_UNSUPPORTED;
+  }
+  const int ny = Cin == 128 ? 2 : 1;
+  const long total = (long)B * H * W / 4;
+  const int n = pick_chunks(total, ny);
+  out[0] = (int)total;
+  out[1] = (int)(total / n);
+  out[2] = n;
+  out[3] = ny;
+  return DG_OK;
+}
+
 int dg_deconv_wgrad(DeconvWgradArgs a, int B, int* nchunks, hipStream_t st) {
   if (!dg_deconv_wgrad_supported(B, a.H, a.W, a.Cin, a.Cout, make_view(const_cast<float*>(a.in), a.H, a.W, a.Cin),
                                  a.dout)) {

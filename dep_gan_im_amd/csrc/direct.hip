@@ -535,6 +535,21 @@ size_t dg_wgrad_small_part_floats(int KS, int B, int H, int W, int Cin, int Cout
   return (size_t)nch * slab;
 }
 
+// the launch plan of dg_wgrad_small for a shape, without launching (depgan_debug_wgrad_plan)
+int dg_wgrad_small_plan(int KS, int B, int H, int W, int Cin, int Cout, int out[4]) {
+  if (KS * KS * Cin * Cout > 1024 || Cout > 64) {
+    dg_set_error("dg_wgrad_small: taps*Cin*Cout = %d too large", KS * KS * Cin * Cout);
+    return DG_ERR_UNSUPPORTED;
+  }
+  if (KS != 3 && KS != 5) {
+    dg_set_error("dg_wgrad_small: unsupported kernel size %d", KS);
+    return DG_ERR_UNSUPPORTED;
+  }
+  small_chunking(B, H, W, &out[0], &out[1], &out[2]);
+  out[3] = 1;
+  return DG_OK;
+}
+
 int dg_wgrad_small(int KS, const WgradArgs& a_in, int* nchunks, hipStream_t st) {
   WgradArgs a = a_in;
   if (KS * KS * a.Cin * a.Cout > 1024 || a.Cout > 64) {

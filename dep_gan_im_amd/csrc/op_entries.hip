@@ -372,6 +372,23 @@ int depgan_op_conv2d_wgrad_ex(const float* x, long xsB, long xsY, long xsX, cons
                    oi, cols ? &cs : nullptr);
 }
 
+// host only: what the launcher of `kernel` would do with this shape, from the launcher's own chunking function
+int depgan_debug_wgrad_plan(int kernel, int KS, int B, int H, int W, int Cin, int Cout, int out[4]) {
+  if (!out || B < 1 || H < 1 || W < 1 || Cin < 1 || Cout < 1) {
+    dg_set_error("debug_wgrad_plan: null or non-positive argument");
+    return DG_ERR_ARG;
+  }
+  switch (kernel) {
+    case 0: return dg_wgrad_plan(KS, B, H, W, Cin, Cout, out);
+    case 1: return dg_wgrad_small_plan(KS, B, H, W, Cin, Cout, out);
+    case 2: return dg_wgrad_bf16_plan(KS, B, H, W, Cin, Cout, out);
+    case 3: return dg_wgrad_bf16s_plan(KS, B, H, W, Cin, Cout, out);
+    case 4: return dg_deconv_wgrad_plan(B, H, W, Cin, Cout, out);
+  }
+  dg_set_error("debug_wgrad_plan: kernel %d is not one of 0..4", kernel);
+  return DG_ERR_ARG;
+}
+
 
 int depgan_op_bn_moments(const float* x, long sB, long sY, long sX, int B, int H, int W, int C, float* mean, float* var,
                          long scratch_floats, void* stream) {

@@ -407,6 +407,22 @@ size_t dg_wgrad_part_floats(int KS, int B, int H, int W, int Cin, int Cout) {
   return (size_t)nch * slab;
 }
 
+// the launch plan of dg_wgrad for a shape, without launching (depgan_debug_wgrad_plan)
+int dg_wgrad_plan(int KS, int B, int H, int W, int Cin, int Cout, int out[4]) {
+  if ((Cin % 4) || (Cout % 4)) {
+    dg_set_error("dg_wgrad: channels and strides must be multiples of 4 floats (Cin=%d Cout=%d)", Cin, Cout);
+    return DG_ERR_ARG;
+  }
+  if (KS != 1 && KS != 3 && KS != 5) {
+    dg_set_error("dg_wgrad: unsupported kernel size %d", KS);
+    return DG_ERR_UNSUPPORTED;
+  }
+  WVar v;
+  pick_variant(KS, Cin, Cout, &v);
+  chunking(v, B, H, W, Cin, Cout, &out[0], &out[1], &out[2], &out[3]);
+  return DG_OK;
+}
+
 template <int MF, int KS, int TPW, int TH>
 static int launch_wgrad_dma(WgradArgs a, int nchunks, int gridY, hipStream_t st) {
   constexpr size_t lds = WDmaCfg<MF, KS, TPW, TH>::LDS_BYTES;

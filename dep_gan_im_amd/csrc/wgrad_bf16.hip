@@ -48,6 +48,16 @@ size_t dg_wgrad_bf16_part_floats(int KS, int B, int H, int W, int Cin, int Cout)
   return (KS == 1 || KS == 3 || KS == 5) ? part_floats(KS, B, H, W, Cin, Cout) : 0;
 }
 
+// the launch plan of dg_wgrad_bf16 for a shape, without launching (depgan_debug_wgrad_plan)
+int dg_wgrad_bf16_plan(int KS, int B, int H, int W, int Cin, int Cout, int out[4]) {
+  if (!dg_wgrad_bf16_supported(KS, Cin, Cout)) {
+    dg_set_error("dg_wgrad_bf16: unsupported shape (KS=%d Cin=%d Cout=%d)", KS, Cin, Cout);
+    return DG_ERR_UNSUPPORTED;
+  }
+  chunking(KS, B, H, W, Cin, Cout, &out[0], &out[1], &out[2], &out[3]);
+  return DG_OK;
+}
+
 int dg_wgrad_bf16(int KS, const WgradArgs& a, int* nchunks_out, hipStream_t st) {
   if (!dg_wgrad_bf16_supported(KS, a.Cin, a.Cout)) {
     dg_set_error("dg_wgrad_bf16: unsupported shape (KS=%d Cin=%d Cout=%d)", KS, a.Cin, a.Cout);

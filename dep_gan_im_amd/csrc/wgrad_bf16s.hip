@@ -33,6 +33,16 @@ size_t dg_wgrad_bf16s_part_floats(int KS, int B, int H, int W, int Cin, int Cout
   return (KS == 1 || KS == 3) ? part_floats(KS, B, H, W, Cin, Cout) : 0;
 }
 
+// the launch plan of dg_wgrad_bf16s for a shape, without launching (depgan_debug_wgrad_plan)
+int dg_wgrad_bf16s_plan(int KS, int B, int H, int W, int Cin, int Cout, int out[4]) {
+  if (!dg_wgrad_bf16s_supported(KS, Cin, Cout)) {
+    dg_set_error("dg_wgrad_bf16s: unsupported shape (KS=%d Cin=%d Cout=%d)", KS, Cin, Cout);
+    return DG_ERR_UNSUPPORTED;
+  }
+  chunking(KS, B, H, W, Cin, Cout, &out[0], &out[1], &out[2], &out[3]);
+  return DG_OK;
+}
+
 int dg_wgrad_bf16s(int KS, const WgradArgsH& a, int* nchunks_out, hipStream_t st) {
   if (!a.x.p || !a.dy.p || !a.part || !nchunks_out || a.B < 1 || a.H < 1 || a.W < 1) {
     dg_set_error("dg_wgrad_bf16s: bad argument");

@@ -542,6 +542,14 @@ int depgan_op_conv2d_wgrad_ex(const float* x, long xsB, long xsY, long xsX, cons
                               long dsX, const float* scale, float* dw, float* raw, int accumulate, int oi, int colB,
                               const float* colscale, float* colout, float* colraw, int B, int H, int W, int Cin,
                               int Cout, int KS, int bf16, void* hip_stream);
+/* Host only (no launch, no allocation): the launch plan a weight-gradient launcher computes for a shape on the current
+ * device, from the same chunking function the launcher calls.  kernel: 0 fp32 MFMA (wgrad.hip), 1 edge layers
+ * (direct.hip: Cin < 8 or channels that are no multiple of 4), 2 bf16 pipe with fp32 staging (wgrad_bf16.hip), 3 bf16 pipe
+ * with bf16 staging (wgrad_bf16s.hip), 4 transposed convolution (deconv_wgrad.hip; KS is ignored).
+ * out = {pixel tiles, tiles per workgroup, chunks (= partial slabs), gridDim.y}; kernel 4: {k-steps of 4 pixels, k-steps
+ * per workgroup, workgroups along x, gridDim.y}.  A shape the launcher refuses returns the launcher's status; a null
+ * `out`, a non-positive size or an unknown `kernel` status 1. */
+int depgan_debug_wgrad_plan(int kernel, int KS, int B, int H, int W, int Cin, int Cout, int out[4]);
 
 /* Learning-phase-1 operators (the DEP-UResNet training step's batch-statistics BatchNorm, Dropout, softmax and
  * cross-entropy), each the internal function uresnet.hip calls.  Device pointers; every NHWC view has the float strides

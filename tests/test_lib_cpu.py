@@ -211,6 +211,18 @@ def test_step_operator_entries_are_exported_and_bound(lib):
         assert getattr(lib, name).argtypes, name + " has no argtypes"
 
 
+DEBUG_ENTRIES = ["capture", "tensor", "tensor_bf16s", "film_decision_bf16s", "wgrad_plan"]
+
+
+def test_debug_entries_are_exported_and_bound(lib):
+    hdr = open(os.path.join(ROOT, "include", "depgan.h")).read()
+    assert sorted(set(re.findall(r"\bint depgan_debug_(\w+)\(", hdr))) == sorted(DEBUG_ENTRIES)
+    for op in DEBUG_ENTRIES:
+        name = "depgan_debug_" + op
+        assert name in _lib.EXPORTS and hasattr(lib, name), name
+        assert getattr(lib, name).argtypes, name + " has no argtypes"
+
+
 # ---- the binding is derived from include/depgan.h (dep_gan_im_amd/_lib.py::parse_header) ----
 
 def _pinned_signatures():
@@ -234,6 +246,8 @@ def _pinned_signatures():
         # 47 parameters: four-word views of in / out / out_pre / res / mask / pool, 9 bare pointers, 13 ints, the stream
         "depgan_op_conv2d_fused": (i, [vp, L, L, L] + [vp] * 6 + [i] + [vp, L, L, L] * 5 + [vp] * 3 + [i] * 12 + [vp]),
         "depgan_op_unpool_mask_bf16s": (i, [vp, L, L, L] * 4 + [i] * 4 + [vp]),
+        "depgan_debug_tensor": (i, [vp, s, vp, L, vp]),
+        "depgan_debug_wgrad_plan": (i, [i] * 7 + [vp]),      # host only; an `int out[4]` array parameter
     }
 
 
@@ -253,7 +267,7 @@ def test_every_prototype_is_bound_with_the_header_s_parameter_count(lib):
     parameters by the commas between the parentheses of the comment-stripped text."""
     hdr = open(os.path.join(ROOT, "include", "depgan.h")).read()
     declared = set(re.findall(r"\b(depgan_[a-z0-9_]+)\s*\(", hdr)) - {"depgan_ctx", "depgan_config"}
-    assert set(_lib.EXPORTS) == declared and len(_lib.EXPORTS) == len(declared) >= 111
+    assert set(_lib.EXPORTS) == declared and len(_lib.EXPORTS) == len(declared) >= 112
     stripped = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
     for name in sorted(declared):
         found = re.findall(r"\b%s\s*\(([^()]*)\)\s*;" % name, stripped)
