@@ -17,14 +17,16 @@
 //     16 independent GEMMs  M_f[tile][n] = sum_c V_f[tile][c] U_f[c][n]  (32 MT x Cin x 32);
 //   * wave w owns the frequencies a = w (b = 0..3): 4 frequencies x MT row tiles of v_mfma_f32_32x32x2_f32.  Its
 //     weight fragments U_f are nobody else's: from the packed panel [nt][chunk][f][n][8] straight into registers, never
-//     through LDS.  And it transforms exactly the V rows it multiplies: task = (tile, 4 channels) for row a = w, two
-//     halo rows x four columns in, four 16-byte rows of V out -- so V is wave-private and needs no barrier, only the LDS
-//     unit's in-order execution of the wave's own writes and reads;
+//     through LDS.  And it transforms exactly the V values it multiplies, each LANE its own: v_mfma_f32_32x32x2_f32
+//     takes from lane (r = lane & 31, h = lane >> 5) the operand V_f[tile 32 mt + r][channels 4h .. 4h + 3], so transform
+//     task mt of a lane is (tile 32 mt + r, channel half h, row a = w): two halo rows x four columns in, the four
+//     frequencies b = 0..3 x four channels out -- exactly the 16 operand registers of the lane's MFMAs for row tile mt.
+//     V never exists in memory: no LDS write, no read back, no wait between the transform and the MFMAs;
 //   * per chunk of 8 input channels: the raw (8 MT + 2) x 18 x 8 halo is copied global -> LDS by the DMA path
 //     (buffer_load_dwordx4 ... lds: no registers, no ds_write pass, asynchronous; double-buffered, issued a whole chunk
-//     ahead; its completion is the ONE barrier of the chunk), transform (16 packed additions per task), 16 MT MFMAs per
-//     wave with one b128 A-fragment read per four of them.  The raw image and the V planes are XOR-swizzled (rslot,
-//     vslot): the LDS serves a b128 access eight lanes at a time out of 128 bytes of banks;
+//     ahead; its completion is the ONE barrier of the chunk), transform (8 b128 reads of the raw image and 16 packed
+//     additions per task), 16 MT MFMAs per wave out of registers.  The raw image is XOR-swizzled (rslot): the lanes the
+//     LDS serves together on a b128 read are neighbouring tiles of one channel half, 64 bytes apart unswizzled;
 //   * epilogue: each wave reduces its four b's to the two output columns in registers (Z[a][q] = row transform), the
 //     waves exchange Z through LDS, and the fused epilogue of igemm_conv (igemm_epilogue.inc, same text) fetches
 //     v = Z[0] + Z[1] + Z[2] (even rows) or Z[1] - Z[2] - Z[3] (odd rows) where it used to fetch one transposed value.
@@ -56,44 +58,42 @@ struct WnCfg {
   // The raw halo chunk is copied global -> LDS by the DMA path (buffer_load_dwordx4 ... lds: no VGPR destination, no
   // ds_write pass, asynchronous): a wave-instruction writes 64 lanes x 16 B lane-linearly, so the LDS image is the
   // unpadded [pixel][8 channels] one, in whole rounds of 256 pieces.  Which piece a lane FETCHES is free, and that is
-  // where the bank swizzle goes (rslot): logical piece (pixel, half) lives in slot (2 pixel + half) ^ (bit 2 of pixel
-  // << 1), so the transform's reads -- eight lanes = four tiles x two channel halves, 64 B apart -- hit eight different
-  // 16-byte slots of the 128-byte bank window.
+  // where the bank swizzle goes (rslot): logical piece (pixel, half) lives in slot (2 pixel + half) ^ ((column >> 2) & 3)
+  // -- the transform's reads come from lanes that hold neighbouring tiles of ONE channel half, pixels two apart = slots
+  // four apart, and the XOR spreads each run of four such slots over the four positions of its 64 bytes.
   static constexpr int XTOT = PIXT * WN_XV;             // 16-byte pieces of a raw chunk
   static constexpr int NXP = (XTOT + 255) / 256;        // DMA instructions per wave and chunk
   static constexpr int RAW = NXP * 256 * 4;             // floats
-  // one frequency: tiles x 8 channels, unpadded; its 16-byte slots are XOR-swizzled (vslot below): the LDS serves a
-  // b128 access eight lanes at a time out of 128 bytes of banks, so eight consecutive lanes must hit eight different
-  // slots modulo 8 -- lanes r and r + 4 of a fragment read (32-byte rows) and the four a's of a transform write
-  // (whole planes apart) would not (counters: half of the LDS cycles of the unswizzled form were bank conflicts)
-  static constexpr int VPLANE = NTILE * WN_CK;
-  static constexpr int V = 16 * VPLANE;
+  static_assert(XTOT % 4 == 0 && WN_TW % 2 == 0, "rslot permutes inside aligned groups of four slots: halo and padding stay apart");
   static constexpr int ZPLANE = NTILE * WN_CP + 32;     // one (a, q): +128 B so that q = 0 / 1 of a pixel pair differ in bank group
   static constexpr int Z = 8 * ZPLANE;
-  // two raw buffers (one barrier per chunk: a wave may stage chunk c + 1 while another still transforms chunk c)
-  static constexpr size_t LDS = sizeof(float) * (size_t)((2 * RAW + V) > Z ? (2 * RAW + V) : Z);
+  // two raw buffers (one barrier per chunk: a wave may stage chunk c + 1 while another still transforms chunk c); the
+  // Z exchange of the epilogue aliases them and is the larger of the two in both forms (37 KB / 73 KB)
+  static constexpr size_t LDS = sizeof(float) * (size_t)((2 * RAW) > Z ? (2 * RAW) : Z);
   static constexpr int WGS_PER_CU = (MT == 2) ? 2 : 3;
 };
 
+// 16-byte slot of the raw LDS image that holds logical piece (pixel, channel half) of the (rows x 18) halo: the two low
+// bits of the linear slot 2 pixel + half XORed with bits 2..3 of the pixel's column.  A b128 read of the transform
+// (row y, column 2 tx + j, half h over the lanes' tiles tx = 0..7, ty = 0..3) then hits different 16-byte slots of the
+// bank window in every group of lanes the LDS serves together -- eight consecutive lanes modulo 8 slots as well as the
+// 16-lane groups {0-3, 12-15, 20-27}, {4-11, 16-19, 28-31} modulo 16 (enumerated in tests/test_wino_regmap_cpu.py)
+static __device__ __forceinline__ int rslot(int pix, int half) { return (2 * pix + half) ^ (((pix % WN_TW) >> 2) & 3); }
+// its inverse on slot indices: the key depends on slot >> 2 only (18 columns are even), so the same XOR undoes it
+static __device__ __forceinline__ int rslot_inv(int q) { return q ^ ((((q >> 1) % WN_TW) >> 2) & 3); }
+
 // ABL: ablation bits for tools/time_wino.py (0 = the product kernel; the others are compiled with
-// -DDEPGAN_WINO_ABLATIONS only): 1 no epilogue, 2 no input transform, 4 no MFMAs, 8 no raw staging
-// 16-byte slot of the raw LDS image that holds logical piece (pixel, channel half); an involution on slot indices
-static __device__ __forceinline__ int rslot(int pix, int half) { return (2 * pix + half) ^ (((pix >> 2) & 1) << 1); }
-
-// float offset inside a V plane of 16-byte slot (tile T, channel half cg) of the frequencies of transform row a
-static __device__ __forceinline__ int vslot(int T, int cg, int a) { return ((2 * T + cg) ^ ((T >> 2) & 1) ^ (a << 1)) << 2; }
-
+// -DDEPGAN_WINO_ABLATIONS only): 1 no epilogue, 2 no input transform (zero operands), 4 no MFMAs, 8 no raw staging
 template <int MT, bool PERS, bool HEAD, int ABL = 0>
 static __device__ __forceinline__ void wino_body(const ConvArgs& a) {
   typedef WnCfg<MT> C;
   constexpr int MF = 32, NT = 32;
-  constexpr int WN_RAW = C::RAW, WN_VPLANE = C::VPLANE, WN_ZPLANE = C::ZPLANE, WN_XTOT = C::XTOT, NXP = C::NXP;
+  constexpr int WN_RAW = C::RAW, WN_ZPLANE = C::ZPLANE, WN_XTOT = C::XTOT, NXP = C::NXP;
   typedef f32x16 acc_t;
   extern __shared__ __attribute__((aligned(16))) float smem[];
-  // raw halo buffers [(8 MT + 2) x 18][12] x 2 and V [16][WN_VPLANE]; the Z planes of the epilogue alias all three
+  // raw halo buffers [(8 MT + 2) x 18][8] x 2, in whole rounds of 256 pieces; the Z planes of the epilogue alias both
   float* const raw0 = smem;
   float* const raw1 = smem + WN_RAW;
-  float* V = smem + 2 * WN_RAW;
 
   const int tid = threadIdx.x;
   const int lane = tid & 63, wv = tid >> 6;
@@ -103,31 +103,29 @@ static __device__ __forceinline__ void wino_body(const ConvArgs& a) {
   const int nCC = a.Cin / WN_CK;
 
   // ---- per-thread geometry, once per workgroup ----
-  // raw staging: DMA piece i of this thread fills LDS slot q = tid + 256 i with logical piece rslot^-1(q) = rslot of it
-  // (an involution): byte offset from the halo origin, or an out-of-range offset for the padding slots behind the halo
-  // tile (the hardware returns zeros for those, as for out-of-image pixels)
+  // raw staging: DMA piece i of this thread fills LDS slot q = tid + 256 i with logical piece rslot_inv(q): byte offset
+  // from the halo origin, or an out-of-range offset for the padding slots behind the halo tile (the hardware returns
+  // zeros for those, as for out-of-image pixels)
   constexpr int SENT = (int)0x80000000;
   int xvo[NXP], xyx[NXP];
 #pragma unroll
   for (int i = 0; i < NXP; ++i) {
     const int q = tid + i * 256;
-    const int lq = q ^ (((q >> 3) & 1) << 1);
+    const int lq = rslot_inv(q);
     const int pix = lq >> 1, part = lq & 1;
     const int ly = pix / WN_TW, lx = pix - ly * WN_TW;
     xvo[i] = (q < WN_XTOT) ? 4 * (ly * (int)a.in.sY + lx * (int)a.in.sX + part * 4) : SENT;
     xyx[i] = (ly << 8) | lx;
   }
-  // transform task i of a lane: q = lane + 64 i -> channel group q & 1, tile q >> 1, transform row a = wave.
+  // transform task i of a lane: tile 32 i + (lane & 31), channel half lane >> 5, transform row a = wave -- the operand
+  // layout of the MFMA, so the task's results are the lane's own A operands of row tile mt = i.
   // Row a of B^T d needs two of the tile's four halo rows:  a = 0: d0 - d2,  1: d1 + d2,  2: d2 - d1,  3: d1 - d3
   // = x + s y with (x, y) = rows (0,2) (1,2) (2,1) (1,3) and s = +1 for a = 1, else -1.
-  int tA[MT][4], tB[MT][4], tV[MT];
+  int tA[MT][4], tB[MT][4];
   float tS[MT];
 #pragma unroll
   for (int i = 0; i < MT; ++i) {
-    // a wave transforms exactly the frequencies it multiplies (row a = wave): V needs no barrier between the transform
-    // and the MFMAs, only the LDS unit's in-order execution of the wave's own writes and reads
-    const int q = lane + 64 * i;
-    const int cg = q & 1, aa = wv, T = q >> 1;
+    const int cg = h, aa = wv, T = 32 * i + r;
     const int tyi = T >> 3, txi = T & 7;
     const int rA = (aa == 0) ? 0 : (aa == 2 ? 2 : 1), rB = (aa == 3) ? 3 : (aa == 2 ? 1 : 2);
 #pragma unroll
@@ -135,14 +133,10 @@ static __device__ __forceinline__ void wino_body(const ConvArgs& a) {
       tA[i][j] = 4 * rslot((2 * tyi + rA) * WN_TW + 2 * txi + j, cg);
       tB[i][j] = 4 * rslot((2 * tyi + rB) * WN_TW + 2 * txi + j, cg);
     }
-    tV[i] = (4 * aa) * WN_VPLANE + vslot(T, cg, aa);
     tS[i] = (aa == 1) ? 1.f : -1.f;
   }
   const int wbase = __builtin_amdgcn_readfirstlane(wv * 256);   // this wave's float offset inside a 256-piece round
-  // fragments: A = V[f][32 mt + r][4h ..], B = panel[f][r][4h ..]
-  int aoff[MT];
-#pragma unroll
-  for (int mt = 0; mt < MT; ++mt) aoff[mt] = vslot(32 * mt + r, h, wv);
+  // fragments: A = V[f][32 mt + r][4h ..] = vr[mt][f] of the transform, B = panel[f][r][4h ..]
   const int boff = (4 * wv * 32 + r) * WN_CK + 4 * h;
 
   unsigned id = blockIdx.x;
@@ -224,41 +218,46 @@ static __device__ __forceinline__ void wino_body(const ConvArgs& a) {
       // raw[(cc + 1) & 1] was last read by the transform of chunk cc - 1: every wave is past this chunk's barrier
       if (!(ABL & 8) && cc + 1 < nCC) stage_dma(cc + 1, (cc + 1) & 1);
       const float* raw = (cc & 1) ? raw1 : raw0;
-      // ---- input transform: raw -> V ----
+      // ---- input transform: raw -> vr[mt][b] = V[(wave, b)][32 mt + r][4h .. 4h + 3], the lane's own MFMA operands ----
+      // (in channel pairs, the packed fp32 forms of the vector ALU: the pair is (k, k + 1) of one 16-byte read, so nothing
+      // moves between registers -- left to itself the compiler pairs across the columns j and pays 24 moves per task)
+      f32x2 vr[MT][4][2];
+      if (ABL & 2) {
+#pragma unroll
+        for (int i = 0; i < MT; ++i)
+#pragma unroll
+          for (int bb = 0; bb < 4; ++bb) vr[i][bb][0] = vr[i][bb][1] = f32x2{0.f, 0.f};
+      }
 #pragma unroll
       for (int i = 0; i < ((ABL & 2) ? 0 : MT); ++i) {
-        f32x4 tc[4];
+        const f32x2 s2 = {tS[i], tS[i]};
+        f32x2 tc[4][2];
+        // all eight reads of the task in flight before the first addition waits for one (the scheduler's own order is
+        // four round trips of two reads each)
+        f32x4 xs[4], ys[4];
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-          const f32x4 x = *reinterpret_cast<const f32x4*>(raw + tA[i][j]);
-          const f32x4 y = *reinterpret_cast<const f32x4*>(raw + tB[i][j]);
-#pragma unroll
-          for (int k = 0; k < 4; ++k) tc[j][k] = fmaf(y[k], tS[i], x[k]);   // exact: s = +-1
+          xs[j] = *reinterpret_cast<const f32x4*>(raw + tA[i][j]);
+          ys[j] = *reinterpret_cast<const f32x4*>(raw + tB[i][j]);
         }
-        f32x4 v0, v1, v2, v3;
+        __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-        for (int k = 0; k < 4; ++k) {
-          v0[k] = tc[0][k] - tc[2][k];
-          v1[k] = tc[1][k] + tc[2][k];
-          v2[k] = tc[2][k] - tc[1][k];
-          v3[k] = tc[1][k] - tc[3][k];
+        for (int j = 0; j < 4; ++j) {
+          const f32x4 x = xs[j], y = ys[j];
+          tc[j][0] = __builtin_elementwise_fma(f32x2{y[0], y[1]}, s2, f32x2{x[0], x[1]});   // exact: s = +-1
+          tc[j][1] = __builtin_elementwise_fma(f32x2{y[2], y[3]}, s2, f32x2{x[2], x[3]});
         }
-        *reinterpret_cast<f32x4*>(V + tV[i]) = v0;
-        *reinterpret_cast<f32x4*>(V + tV[i] + WN_VPLANE) = v1;
-        *reinterpret_cast<f32x4*>(V + tV[i] + 2 * WN_VPLANE) = v2;
-        *reinterpret_cast<f32x4*>(V + tV[i] + 3 * WN_VPLANE) = v3;
+#pragma unroll
+        for (int p = 0; p < 2; ++p) {
+          vr[i][0][p] = tc[0][p] - tc[2][p];
+          vr[i][1][p] = tc[1][p] + tc[2][p];
+          vr[i][2][p] = tc[2][p] - tc[1][p];
+          vr[i][3][p] = tc[1][p] - tc[3][p];
+        }
       }
-      // ---- 16 GEMMs, this wave's four: 32 MFMAs (V rows of frequency row a = wave: written by this wave just above) ----
-      f32x4 av[2][MT];
-      auto load_a = [&](int f, f32x4* d) {
-#pragma unroll
-        for (int mt = 0; mt < MT; ++mt)
-          d[mt] = *reinterpret_cast<const f32x4*>(V + (4 * wv + f) * WN_VPLANE + aoff[mt]);
-      };
-      load_a(0, av[0]);
+      // ---- 16 GEMMs, this wave's four: 16 MT MFMAs on the operands formed just above ----
 #pragma unroll
       for (int f = 0; f < 4; ++f) {
-        if (f + 1 < 4) load_a(f + 1, av[(f + 1) & 1]);
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
         for (int j = 0; j < 4; ++j)
@@ -267,13 +266,13 @@ static __device__ __forceinline__ void wino_body(const ConvArgs& a) {
             if (!(ABL & 4)) {
               if (FIRST && j == 0) {
                 const acc_t zero = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-                acc[f][mt] = __builtin_amdgcn_mfma_f32_32x32x2f32(bq[f][j], av[f & 1][mt][j], zero, 0, 0, 0);
+                acc[f][mt] = __builtin_amdgcn_mfma_f32_32x32x2f32(bq[f][j], vr[mt][f][j >> 1][j & 1], zero, 0, 0, 0);
               } else {
-                acc[f][mt] = __builtin_amdgcn_mfma_f32_32x32x2f32(bq[f][j], av[f & 1][mt][j], acc[f][mt], 0, 0, 0);
+                acc[f][mt] = __builtin_amdgcn_mfma_f32_32x32x2f32(bq[f][j], vr[mt][f][j >> 1][j & 1], acc[f][mt], 0, 0, 0);
               }
             } else {
               if (FIRST && j == 0) acc[f][mt] = acc_t{};
-              acc[f][mt][j] += bq[f][j] * av[f & 1][mt][j];
+              acc[f][mt][j] += bq[f][j] * vr[mt][f][j >> 1][j & 1];
             }
         __builtin_amdgcn_sched_barrier(0);
       }
@@ -296,7 +295,7 @@ static __device__ __forceinline__ void wino_body(const ConvArgs& a) {
     // ---- output transform, first half (this wave's row a = wv: the four b's -> the two output columns q) ----
     // run from inside the fused epilogue (EPI_STAGE_LATE): after its per-item constant loads have been issued
     auto zstage = [&]() {
-      __syncthreads();   // every wave is done with V: the Z exchange may overwrite raw and V
+      __syncthreads();   // every wave is done with the last chunk's raw image: the Z exchange may overwrite both buffers
       float* zw = smem + (2 * wv) * WN_ZPLANE + r * WN_CP + 4 * h;
 #pragma unroll
       for (int mt = 0; mt < MT; ++mt)

@@ -254,6 +254,26 @@ int depgan_op_conv2d_fused(const float* in, long isB, long isY, long isX, const 
 }
 
 
+int depgan_op_conv3x3_wino_gathered(const float* in, long isB, long isY, long isX, const long* run_off, int runs,
+                                    const float* w_hwio, const float* bias, float* out, long osB, long osY, long osX,
+                                    int B, int H, int W, int Cin, int Cout, void* stream) {
+  if (op_view_bad_batched(in, isB, isY, isX) || op_view_bad_batched(out, osB, osY, osX) || !w_hwio || !run_off || B < 1 || H < 1 ||
+      W < 1 || Cin < 1 || Cout < 1 || runs < 1 || runs > 4) {
+    dg_set_error("op_conv3x3_wino_gathered: null or non-positive argument, or not 1 ... 4 runs");
+    return DG_ERR_ARG;
+  }
+  if (Cin % (runs * 8)) {
+    dg_set_error("op_conv3x3_wino_gathered: %d channels are not %d runs of whole 8-channel chunks", Cin, runs);
+    return DG_ERR_UNSUPPORTED;
+  }
+  ConvArgs a = conv_args(op_view(in, isB, isY, isX), op_view(out, osB, osY, osX), B, H, W, Cin, Cout);
+  a.ep.bias = bias;
+  a.cpt = Cin / (runs * 8);
+  for (int t = 0; t < runs; ++t) a.in_run_off[t] = run_off[t];
+  return op_conv_run(a, w_hwio, Cin, Cout, 3, 8, 0, (hipStream_t)stream);
+}
+
+
 int depgan_op_deconv2x2_igemm(int form, const float* in, long isB, long isY, long isX, const float* w_hwoi,
                               const float* bias, const float* scale, const float* shift, float* out, long osB, long osY,
                               long osX, const float* mask, long msB, long msY, long msX, int B, int H, int W, int Cin,

@@ -522,6 +522,13 @@ int depgan_op_conv2d_fused(const float* in, long isB, long isY, long isX, const 
                            long msY, long msX, float* pool, long qsB, long qsY, long qsX, const float* head_w,
                            const float* head_b, float* head_out, int head_tanh, int head_skip_out, int B, int H, int W,
                            int Cin, int Cout, int KS, int relu, int accumulate, int path, int bwd, void* hip_stream);
+/* The Winograd 3x3 kernel (path 8 above) with a gathered K axis, the launch form ConvArgs::cpt describes: the Cin input
+ * channels are `runs` (1 ... 4) equal runs of whole 8-channel chunks, run t read at in + run_off[t] floats with the
+ * strides of `in` (run_off: HOST array of `runs` offsets, multiples of 4).  w_hwio (3, 3, Cin, Cout) with the runs in
+ * order along Cin; bias optional.  Status 1 for bad arguments, 3 for what the kernel does not cover. */
+int depgan_op_conv3x3_wino_gathered(const float* in, long isB, long isY, long isX, const long* run_off, int runs,
+                                    const float* w_hwio, const float* bias, float* out, long osB, long osY, long osX,
+                                    int B, int H, int W, int Cin, int Cout, void* hip_stream);
 /* The 2x2 / stride-2 transposed convolution on the implicit-GEMM kernels, w_hwoi the Keras kernel (2, 2, Cout, Cin).
  * form 0: forward as ONE grouped launch of four 1x1 convolutions: in (B, H, W, Cin) -> out (B, 2H, 2W, Cout), with
  *         bias / scale+shift / relu; mask must be NULL.
