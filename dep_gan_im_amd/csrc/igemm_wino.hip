@@ -23,10 +23,16 @@
 //     frequencies b = 0..3 x four channels out -- exactly the 16 operand registers of the lane's MFMAs for row tile mt.
 //     V never exists in memory: no LDS write, no read back, no wait between the transform and the MFMAs;
 //   * per chunk of 8 input channels: the raw (8 MT + 2) x 18 x 8 halo is copied global -> LDS by the DMA path
-//     (buffer_load_dwordx4 ... lds: no registers, no ds_write pass, asynchronous; double-buffered, issued a whole chunk
-//     ahead; its completion is the ONE barrier of the chunk), transform (8 b128 reads of the raw image and 16 packed
-//     additions per task), 16 MT MFMAs per wave out of registers.  The raw image is XOR-swizzled (rslot): the lanes the
-//     LDS serves together on a b128 read are neighbouring tiles of one channel half, 64 bytes apart unswizzled;
+//     (buffer_load_dwordx4 ... lds: no registers, no ds_write pass, asynchronous) into a ring of NBUF raw buffers (two:
+//     three measured the same, profiles/wino_ring_experiments.md): the first NBUF - 1 chunks of an item are issued back
+//     to back, chunk c + NBUF - 1 behind the barrier of chunk c -- the ONE barrier of the chunk, a bare s_barrier in
+//     front of which a wave waits for its own pieces of chunk c only (s_waitcnt vmcnt(N), N = the younger DMA
+//     instructions + the four weight-fragment loads: vector-memory instructions complete in order).  The fragment loads are asm statements, waited for by count in front of the
+//     first MFMA: the compiler, which next to a DMA in flight waits vmcnt(0) for every load it knows of and in front
+//     of every __syncthreads(), sees no load in the chunk loop and drains nothing.  Then the transform (8 b128 reads
+//     of the raw image and 16 packed additions per task) and 16 MT MFMAs per wave out of registers.  The raw image is
+//     XOR-swizzled (rslot): the lanes the LDS serves together on a b128 read are neighbouring tiles of one channel
+//     half, 64 bytes apart unswizzled;
 //   * epilogue: each wave reduces its four b's to the two output columns in registers (Z[a][q] = row transform), the
 //     waves exchange Z through LDS, and the fused epilogue of igemm_conv (igemm_epilogue.inc, same text) fetches
 //     v = Z[0] + Z[1] + Z[2] (even rows) or Z[1] - Z[2] - Z[3] (odd rows) where it used to fetch one transposed value.
@@ -67,11 +73,37 @@ struct WnCfg {
   static_assert(XTOT % 4 == 0 && WN_TW % 2 == 0, "rslot permutes inside aligned groups of four slots: halo and padding stay apart");
   static constexpr int ZPLANE = NTILE * WN_CP + 32;     // one (a, q): +128 B so that q = 0 / 1 of a pixel pair differ in bank group
   static constexpr int Z = 8 * ZPLANE;
-  // two raw buffers (one barrier per chunk: a wave may stage chunk c + 1 while another still transforms chunk c); the
-  // Z exchange of the epilogue aliases them and is the larger of the two in both forms (37 KB / 73 KB)
-  static constexpr size_t LDS = sizeof(float) * (size_t)((2 * RAW) > Z ? (2 * RAW) : Z);
+  // a ring of NBUF raw buffers (one barrier per chunk: after the barrier of chunk c a wave stages chunk c + NBUF - 1 into
+  // the buffer the transform of chunk c - 1 read last).  Two: the weight-fragment wait in front of the MFMAs completes,
+  // in order, every DMA issued before this chunk's barrier, so only ONE chunk is ever in flight behind it, and three
+  // buffers measured no faster than two (profiles/wino_ring_experiments.md); 3 and, at 8-row tiles, 4 are valid values.
+  // The Z exchange of the epilogue aliases the ring and is the larger of the two in both forms (37.9 KB / 73 KB against
+  // 24 / 36 KB for three buffers), so the ring costs no LDS and the workgroups per CU stay what the registers allow
+  static constexpr int NBUF = 2;
+  static_assert(NBUF >= 2 && NBUF * RAW <= Z, "the raw ring must fit under the Z exchange: LDS and workgroups per CU unchanged");
+  static_assert((NBUF - 1) * NXP + 4 < 64, "counted waits: vmcnt is a 6-bit field");
+  static constexpr size_t LDS = sizeof(float) * (size_t)Z;
   static constexpr int WGS_PER_CU = (MT == 2) ? 2 : 3;
 };
+
+// s_waitcnt vmcnt(N) with N a compile-time count of vector-memory instructions that may stay in flight.  Explicit, with a
+// memory clobber: the compiler knows neither that the DMA writes LDS nor (the weight fragments are loaded in an asm
+// statement) that these loads exist
+template <int N>
+static __device__ __forceinline__ void wn_wait_vm() {
+  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
+}
+// the same for a run-time number y <= Y of younger chunks (NX instructions each) plus the four fragment loads: a
+// wave-uniform branch to the immediate
+template <int NX, int Y>
+static __device__ __forceinline__ void wn_wait_younger(int y) {
+  if constexpr (Y == 0) {
+    wn_wait_vm<4>();
+  } else {
+    if (y >= Y) wn_wait_vm<NX * Y + 4>();
+    else wn_wait_younger<NX, Y - 1>(y);
+  }
+}
 
 // 16-byte slot of the raw LDS image that holds logical piece (pixel, channel half) of the (rows x 18) halo: the two low
 // bits of the linear slot 2 pixel + half XORed with bits 2..3 of the pixel's column.  A b128 read of the transform
@@ -88,12 +120,12 @@ template <int MT, bool PERS, bool HEAD, int ABL = 0>
 static __device__ __forceinline__ void wino_body(const ConvArgs& a) {
   typedef WnCfg<MT> C;
   constexpr int MF = 32, NT = 32;
-  constexpr int WN_RAW = C::RAW, WN_ZPLANE = C::ZPLANE, WN_XTOT = C::XTOT, NXP = C::NXP;
+  constexpr int WN_RAW = C::RAW, WN_ZPLANE = C::ZPLANE, WN_XTOT = C::XTOT, NXP = C::NXP, NBUF = C::NBUF;
+  constexpr int NXI = (ABL & 8) ? 0 : NXP;   // DMA instructions a wave really issues per chunk
   typedef f32x16 acc_t;
   extern __shared__ __attribute__((aligned(16))) float smem[];
-  // raw halo buffers [(8 MT + 2) x 18][8] x 2, in whole rounds of 256 pieces; the Z planes of the epilogue alias both
-  float* const raw0 = smem;
-  float* const raw1 = smem + WN_RAW;
+  // raw halo buffers [(8 MT + 2) x 18][8] x NBUF at smem + slot * RAW, in whole rounds of 256 pieces; the Z planes of the
+  // epilogue alias all of them
 
   const int tid = threadIdx.x;
   const int lane = tid & 63, wv = tid >> 6;
@@ -130,8 +162,8 @@ static __device__ __forceinline__ void wino_body(const ConvArgs& a) {
     const int rA = (aa == 0) ? 0 : (aa == 2 ? 2 : 1), rB = (aa == 3) ? 3 : (aa == 2 ? 1 : 2);
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-      tA[i][j] = 4 * rslot((2 * tyi + rA) * WN_TW + 2 * txi + j, cg);
-      tB[i][j] = 4 * rslot((2 * tyi + rB) * WN_TW + 2 * txi + j, cg);
+      tA[i][j] = 16 * rslot((2 * tyi + rA) * WN_TW + 2 * txi + j, cg);   // bytes; the ring slot is added as a scalar
+      tB[i][j] = 16 * rslot((2 * tyi + rB) * WN_TW + 2 * txi + j, cg);
     }
     tS[i] = (aa == 1) ? 1.f : -1.f;
   }
@@ -175,9 +207,9 @@ static __device__ __forceinline__ void wino_body(const ConvArgs& a) {
     const __amdgpu_buffer_rsrc_t rx =
         __builtin_amdgcn_make_buffer_rsrc((void*)(((unsigned long long)xhi << 32) | xlo), 0, 0x7FFFFFFF, 0x00020000);
     const int xso0 = 4 * (b * (int)a.in.sB + ty0 * (int)a.in.sY + tx0 * (int)a.in.sX);
-    auto stage_dma = [&](int cc, int buf) {   // chunk cc -> raw buffer buf
+    auto stage_dma = [&](int cc, int buf) {   // chunk cc -> ring slot buf
       const int xso = xso0 + 4 * (int)coff(cc);
-      float* xs = (buf ? raw1 : raw0) + wbase;
+      float* xs = smem + buf * WN_RAW + wbase;
       if (interior) {
 #pragma unroll
         for (int i = 0; i < NXP; ++i) {
@@ -203,21 +235,48 @@ static __device__ __forceinline__ void wino_body(const ConvArgs& a) {
     acc_t acc[4][MT];
 
     const float* wnt = a.w + (size_t)ntile * nCC * (16 * NT * WN_CK) + boff;
-    if (!(ABL & 8)) stage_dma(0, 0);
-    auto chunk = [&](const int cc, auto first_tag) {
-      constexpr bool FIRST = decltype(first_tag)::value;
-      // this wave's weight fragments of the chunk: four frequencies x (32 channels x 8) -- in flight during the transform
-      f32x4 bq[4];
+    // the first NBUF - 1 chunks of the item, back to back (no DMA of the previous item is in flight: its last chunk
+    // waited for everything, and the end-of-item barrier is behind us)
+    if (!(ABL & 8)) {
 #pragma unroll
-      for (int f = 0; f < 4; ++f)
-        bq[f] = *reinterpret_cast<const f32x4*>(wnt + (size_t)cc * (16 * NT * WN_CK) + f * (NT * WN_CK));
-      // this wave's DMA pieces of chunk cc (issued a whole chunk ago) and its weight fragments have landed ... (the
-      // compiler does not know that the DMA writes LDS: the wait is explicit)
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      __syncthreads();   // ... and so have everybody else's -- the only barrier of the chunk
-      // raw[(cc + 1) & 1] was last read by the transform of chunk cc - 1: every wave is past this chunk's barrier
-      if (!(ABL & 8) && cc + 1 < nCC) stage_dma(cc + 1, (cc + 1) & 1);
-      const float* raw = (cc & 1) ? raw1 : raw0;
+      for (int k = 0; k < NBUF - 1; ++k)
+        if (k < nCC) stage_dma(k, k);
+    }
+    // slot: ring slot of chunk cc (cc % NBUF).  One text for every ring position (a text per slot and tail position --
+    // immediate LDS offsets, no branch at the waits -- spilled over a hundred registers in the 16-row form): the waits
+    // branch, wave-uniformly, to their immediates
+    auto chunk = [&](const int cc, const int slot, auto first_tag) {
+      constexpr bool FIRST = decltype(first_tag)::value;
+      const bool issue = cc + NBUF - 1 < nCC;   // chunk cc + NBUF - 1 exists: staged behind this chunk's barrier
+      // this wave's weight fragments of the chunk: four frequencies x (32 channels x 8), in flight across the barrier and
+      // the transform.  Loaded in an asm statement: next to a DMA in flight the compiler waits vmcnt(0) for the result of
+      // any load it knows of, which would drain the ring in front of the MFMAs; these four are counted by hand
+      f32x4 bq[4];
+      {
+        const float* wp = wnt + (size_t)cc * (16 * NT * WN_CK);
+        static_assert(3 * NT * WN_CK * sizeof(float) < 4096, "immediate offsets of the fragment loads");
+        asm volatile(
+            "global_load_dwordx4 %0, %4, off\n\t"
+            "global_load_dwordx4 %1, %4, off offset:1024\n\t"
+            "global_load_dwordx4 %2, %4, off offset:2048\n\t"
+            "global_load_dwordx4 %3, %4, off offset:3072"
+            : "=&v"(bq[0]), "=&v"(bq[1]), "=&v"(bq[2]), "=&v"(bq[3])
+            : "v"(wp)
+            : "memory");
+        static_assert(NT * WN_CK * sizeof(float) == 1024, "the offsets above");
+      }
+      // this wave's DMA pieces of chunk cc have landed: vector-memory instructions complete in order, and younger than
+      // them are the DMAs of the chunks cc + 1 ... (NBUF - 2 of them, fewer at the end of an item) and the four loads
+      // above.  (The compiler does not know that the DMA writes LDS: the wait is explicit)
+      wn_wait_younger<NXI, NBUF - 2>(nCC - 1 - cc);
+      // ... and so have everybody else's -- the only barrier of the chunk.  The bare instruction: __syncthreads() fences,
+      // and the fence drains vmcnt while a DMA is in flight.  Nothing else needs the fence: a wave's LDS reads of chunk
+      // cc - 1 have returned before its MFMAs of that chunk took them
+      __builtin_amdgcn_s_barrier();
+      asm volatile("" ::: "memory");
+      // slot (cc + NBUF - 1) % NBUF was last read by the transform of chunk cc - 1: every wave is past this chunk's barrier
+      if (issue && !(ABL & 8)) stage_dma(cc + NBUF - 1, slot ? slot - 1 : NBUF - 1);
+      const char* raw = reinterpret_cast<const char*>(smem + slot * WN_RAW);
       // ---- input transform: raw -> vr[mt][b] = V[(wave, b)][32 mt + r][4h .. 4h + 3], the lane's own MFMA operands ----
       // (in channel pairs, the packed fp32 forms of the vector ALU: the pair is (k, k + 1) of one 16-byte read, so nothing
       // moves between registers -- left to itself the compiler pairs across the columns j and pays 24 moves per task)
@@ -255,6 +314,19 @@ static __device__ __forceinline__ void wino_body(const ConvArgs& a) {
           vr[i][3][p] = tc[1][p] - tc[3][p];
         }
       }
+      // the weight fragments have landed, their latency spent under the barrier and the transform.  In-order completion:
+      // this also completes every DMA issued before them; only the one issued behind this chunk's barrier stays in flight.
+      // The transform's results are operands of an empty statement in front of the wait (its additions stay above it,
+      // where the branch would otherwise let them sink to their first use), the fragments of one behind it (nothing that
+      // reads them moves above it)
+#pragma unroll
+      for (int i = 0; i < MT; ++i)
+        asm volatile("" : "+v"(vr[i][0][0]), "+v"(vr[i][0][1]), "+v"(vr[i][1][0]), "+v"(vr[i][1][1]), "+v"(vr[i][2][0]),
+                          "+v"(vr[i][2][1]), "+v"(vr[i][3][0]), "+v"(vr[i][3][1]));
+      __builtin_amdgcn_sched_barrier(0);
+      if (issue) wn_wait_vm<NXI>();
+      else wn_wait_vm<0>();
+      asm volatile("" : "+v"(bq[0]), "+v"(bq[1]), "+v"(bq[2]), "+v"(bq[3])::"memory");
       // ---- 16 GEMMs, this wave's four: 16 MT MFMAs on the operands formed just above ----
 #pragma unroll
       for (int f = 0; f < 4; ++f) {
@@ -277,8 +349,8 @@ static __device__ __forceinline__ void wino_body(const ConvArgs& a) {
         __builtin_amdgcn_sched_barrier(0);
       }
     };
-    chunk(0, std::true_type{});
-    for (int cc = 1; cc < nCC; ++cc) chunk(cc, std::false_type{});
+    chunk(0, 0, std::true_type{});
+    for (int cc = 1, s = 1 % NBUF; cc < nCC; ++cc, s = (s + 1 == NBUF) ? 0 : s + 1) chunk(cc, s, std::false_type{});
 
     if (ABL & 1) {   // keep the accumulators alive with one store that never happens
       float sacc = 0.f;
@@ -295,7 +367,9 @@ static __device__ __forceinline__ void wino_body(const ConvArgs& a) {
     // ---- output transform, first half (this wave's row a = wv: the four b's -> the two output columns q) ----
     // run from inside the fused epilogue (EPI_STAGE_LATE): after its per-item constant loads have been issued
     auto zstage = [&]() {
-      __syncthreads();   // every wave is done with the last chunk's raw image: the Z exchange may overwrite both buffers
+      // every wave is done with the last chunk's raw image, and no DMA is in flight (the last chunk issued none and
+      // waited for all): the Z exchange may overwrite the ring
+      __syncthreads();
       float* zw = smem + (2 * wv) * WN_ZPLANE + r * WN_CP + 4 * h;
 #pragma unroll
       for (int mt = 0; mt < MT; ++mt)
