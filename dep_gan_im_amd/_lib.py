@@ -92,6 +92,7 @@ ABI_VERSION = 3          # the ABI engine.py's call sites were written against; 
 MAX_MULTI, MAX_CRITIC_STEPS = _K["DEPGAN_MAX_MULTI"], _K["DEPGAN_MAX_CRITIC_STEPS"]
 RCCL_ID_BYTES = _K["DEPGAN_RCCL_ID_BYTES"]
 EVAL_NCOUNT, EVAL_LABEL_NCOUNT = _K["DEPGAN_EVAL_NCOUNT"], _K["DEPGAN_EVAL_LABEL_NCOUNT"]
+MAX_HEAD_CLASSES = _K["DEPGAN_MAX_HEAD_CLASSES"]     # a softmax head has 2 .. this many classes
 NET_G, NET_D_Y2, NET_D_DEM = (_K["DEPGAN_NET_" + n] for n in ("G", "D_Y2", "D_DEM"))
 ARENA_PARAMS, ARENA_NONTRAINABLE, ARENA_GRADS, ARENA_ADAM_M, ARENA_ADAM_V = (
     _K["DEPGAN_ARENA_" + n] for n in ("PARAMS", "NONTRAINABLE", "GRADS", "ADAM_M", "ADAM_V"))

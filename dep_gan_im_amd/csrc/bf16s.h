@@ -68,9 +68,10 @@ int dg_head_bf16s(const __bf16* a, long ld, const float* w, const float* b, floa
                   hipStream_t st);
 
 // gen_segmentation of the DEP-UResNet: z[p][k] = sum_c a[p * ld + c] w[c * K + k] + b[k] in dg_head_bf16s's arithmetic
-// and order per column k, probs[p] = softmax(z[p]) in softmax_ce4_kernel's statements (contraction off around both);
-// bf16 in, fp32 (P, 4) out as 16-byte rows, the logits too where `logits` is given.  K == 4; C as dg_head_bf16s; a, w,
-// probs and logits 16-byte aligned.  Anything else is a status before any launch.
+// and order per column k, probs[p] = softmax(z[p]) in softmax_ce_kernel's statements for K classes (softmax_row.h;
+// contraction off around both); bf16 in, dense fp32 (P, K) out, the logits too where `logits` is given.  K = 2..8; C as
+// dg_head_bf16s; a 16-byte aligned; w, probs and logits 16-byte aligned where K % 4 == 0 (16-byte rows), else 4-byte.
+// Anything else is a status before any launch.
 int dg_head_softmax_bf16s(const __bf16* a, long ld, const float* w, const float* b, float* probs, float* logits, long P,
                           int C, int K = 4, hipStream_t st = nullptr);
 

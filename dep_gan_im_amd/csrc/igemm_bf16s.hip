@@ -18,6 +18,7 @@
 
 #include "bf16s.h"
 #include "epilogue.h"
+#include "softmax_row.h"
 
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef float f32x8 __attribute__((ext_vector_type(8), aligned(16)));   // loaded from 16-byte aligned tables
@@ -262,33 +263,38 @@ int dg_head_bf16s(const __bf16* a, long ld, const float* w, const float* b, floa
 }
 
 // ---------------------------------------------------------------------------
-// DEP-UResNet head: 1x1 convolution to four logits + softmax over them, bf16 in, fp32 out.  head_bf16s_kernel's lane
-// mapping (C / 8 lanes per pixel, one 16-byte load each, consecutive lanes on consecutive addresses) with four columns of
-// w (C, 4) instead of one: logit k is formed exactly as that kernel forms its output with column k (per 8-channel part
-// v = a0 w0, fmaf over channels 1..7; the same xor butterfly; + b[k]), and the softmax is softmax_ce4_kernel's
-// statements (train_ops.hip, onehot == nullptr) on those four values -- so both halves have an existing kernel to be
-// bit-equal to.  HBM-bound (2 C + 16 bytes per pixel): a grid-stride loop, so that a lane's 32 weights are loaded once;
-// the stride is a multiple of 256, hence of LP, and a lane keeps its part.  Lane 0 of a pixel stores its 16 bytes.
+// DEP-UResNet head: 1x1 convolution to K = 2..8 class logits + softmax over them, bf16 in, fp32 out.
+// head_bf16s_kernel's lane mapping (C / 8 lanes per pixel, one 16-byte load each, consecutive lanes on consecutive
+// addresses) with K columns of w (C, K) instead of one: logit k is formed exactly as that kernel forms its output with
+// column k (per 8-channel part v = a0 w0, fmaf over channels 1..7; the same xor butterfly; + b[k]), and the softmax is
+// dg_softmax_row (softmax_row.h), the text softmax_ce_kernel runs -- so both halves have an existing kernel to be
+// bit-equal to.  HBM-bound (2 C + 4 K bytes per pixel): a grid-stride loop, so that a lane's 8 K weights are loaded once;
+// the stride is a multiple of 256, hence of LP, and a lane keeps its part.  Lane 0 of a pixel stores its row.
+// One body; the reference's four classes keep the kernel name the resource checks know, the other counts are
+// instantiations of head_softmax_k_bf16s_kernel.
 // ---------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void head_softmax_bf16s_kernel(const __bf16* __restrict__ a, long ld,
-                                                                  const float* __restrict__ w,
-                                                                  const float* __restrict__ b, float* __restrict__ probs,
-                                                                  float* __restrict__ logits, long P, int lgLP) {
+template <int K>
+__device__ __forceinline__ void head_softmax_bf16s_body(const __bf16* __restrict__ a, long ld,
+                                                        const float* __restrict__ w, const float* __restrict__ b,
+                                                        float* __restrict__ probs, float* __restrict__ logits, long P,
+                                                        int lgLP) {
 #pragma clang fp contract(off)
   const int LP = 1 << lgLP;
   const int part = threadIdx.x & (LP - 1);
-  f32x4 wv[8];
+  float wv[8][K];
 #pragma unroll
-  for (int j = 0; j < 8; ++j) wv[j] = *reinterpret_cast<const f32x4*>(w + (part * 8 + j) * 4);
+  for (int j = 0; j < 8; ++j) dg_row_load<K>(w + (part * 8 + j) * K, wv[j]);
   const long total = P << lgLP;
   // the trip count is the same for every lane of a block: the shuffles below run with all 64 lanes
   for (long t0 = blockIdx.x * 256L; t0 < total; t0 += gridDim.x * 256L) {
     const long p = (t0 + threadIdx.x) >> lgLP;
-    f32x4 z = {0.f, 0.f, 0.f, 0.f};
+    float z[K];
+#pragma unroll
+    for (int k = 0; k < K; ++k) z[k] = 0.f;
     if (p < P) {
       const f32x8 av = __builtin_convertvector(*reinterpret_cast<const bf16x8*>(a + p * ld + part * 8), f32x8);
 #pragma unroll
-      for (int k = 0; k < 4; ++k) {
+      for (int k = 0; k < K; ++k) {
         float v = av[0] * wv[0][k];
 #pragma unroll
         for (int j = 1; j < 8; ++j) v = fmaf(av[j], wv[j][k], v);
@@ -297,41 +303,60 @@ __global__ __launch_bounds__(256) void head_softmax_bf16s_kernel(const __bf16* _
     }
     for (int o = LP >> 1; o > 0; o >>= 1) {
 #pragma unroll
-      for (int k = 0; k < 4; ++k) z[k] += __shfl_xor(z[k], o, 64);
+      for (int k = 0; k < K; ++k) z[k] += __shfl_xor(z[k], o, 64);
     }
     if (p < P && part == 0) {
 #pragma unroll
-      for (int k = 0; k < 4; ++k) z[k] += b[k];
-      if (logits) *reinterpret_cast<f32x4*>(logits + p * 4) = z;
-      const float m = fmaxf(fmaxf(z[0], z[1]), fmaxf(z[2], z[3]));
-      f32x4 pr;
-      float S0 = 0.f;
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        pr[k] = expf(z[k] - m);
-        S0 += pr[k];
-      }
-#pragma unroll
-      for (int k = 0; k < 4; ++k) pr[k] /= S0;
-      *reinterpret_cast<f32x4*>(probs + p * 4) = pr;
+      for (int k = 0; k < K; ++k) z[k] += b[k];
+      if (logits) dg_row_store<K>(logits + p * K, z);
+      float pr[K];
+      dg_softmax_row<K>(z, pr);
+      dg_row_store<K>(probs + p * K, pr);
     }
   }
+}
+__global__ __launch_bounds__(256) void head_softmax_bf16s_kernel(const __bf16* __restrict__ a, long ld,
+                                                                  const float* __restrict__ w,
+                                                                  const float* __restrict__ b, float* __restrict__ probs,
+                                                                  float* __restrict__ logits, long P, int lgLP) {
+  head_softmax_bf16s_body<4>(a, ld, w, b, probs, logits, P, lgLP);
+}
+template <int K>
+__global__ __launch_bounds__(256) void head_softmax_k_bf16s_kernel(const __bf16* __restrict__ a, long ld,
+                                                                    const float* __restrict__ w,
+                                                                    const float* __restrict__ b,
+                                                                    float* __restrict__ probs,
+                                                                    float* __restrict__ logits, long P, int lgLP) {
+  head_softmax_bf16s_body<K>(a, ld, w, b, probs, logits, P, lgLP);
 }
 
 int dg_head_softmax_bf16s(const __bf16* a, long ld, const float* w, const float* b, float* probs, float* logits, long P,
                           int C, int K, hipStream_t st) {
   if (!a || !w || !b || !probs || P < 1) { dg_set_error("dg_head_softmax_bf16s: bad argument"); return DG_ERR_ARG; }
-  if (K != 4) { dg_set_error("dg_head_softmax_bf16s: %d classes (the softmax is over 4)", K); return DG_ERR_UNSUPPORTED; }
+  if (K < DG_MIN_CLASSES || K > DG_MAX_CLASSES) {
+    dg_set_error("dg_head_softmax_bf16s: %d classes (the head covers %d to %d)", K, DG_MIN_CLASSES, DG_MAX_CLASSES);
+    return DG_ERR_UNSUPPORTED;
+  }
   const int LP = C / 8;
   if (C < 8 || (C % 8) || LP > 64 || (LP & (LP - 1))) { dg_set_error("dg_head_softmax_bf16s: C/8 must be a power of two <= 64"); return DG_ERR_ARG; }
-  if (ld < C || (ld % 8) || (((uintptr_t)a) & 15) || (((uintptr_t)w) & 15)) { dg_set_error("dg_head_softmax_bf16s: the input and the weights must be 16-byte aligned, ld a multiple of 8"); return DG_ERR_ARG; }
-  if ((((uintptr_t)probs) & 15) || (((uintptr_t)logits) & 15)) { dg_set_error("dg_head_softmax_bf16s: probs and logits are written as 16-byte rows and must be 16-byte aligned"); return DG_ERR_ARG; }
+  if (ld < C || (ld % 8) || (((uintptr_t)a) & 15)) { dg_set_error("dg_head_softmax_bf16s: the input must be 16-byte aligned, ld a multiple of 8"); return DG_ERR_ARG; }
+  // rows of K floats: 16-byte accesses where K % 4 == 0, else float by float
+  const uintptr_t al = (K % 4 == 0) ? 15 : 3;
+  if ((((uintptr_t)w) | ((uintptr_t)probs) | ((uintptr_t)logits)) & al) {
+    dg_set_error("dg_head_softmax_bf16s: the weights, probs and logits must be %d-byte aligned for %d classes", (int)al + 1, K);
+    return DG_ERR_ARG;
+  }
   if (P > (0x7FFFFFFFFFFFFFFFL >> 8) / (ld > 64 ? ld : 64)) { dg_set_error("dg_head_softmax_bf16s: %ld pixels", P); return DG_ERR_UNSUPPORTED; }
   int lg = 0;
   while ((1 << lg) < LP) ++lg;
   long blocks = (P * LP + 255) / 256;
   if (blocks > 2048) blocks = 2048;   // 256 CUs x 8 resident blocks; the loop takes the rest
-  hipLaunchKernelGGL(head_softmax_bf16s_kernel, dim3((unsigned)blocks), dim3(256), 0, st, a, ld, w, b, probs, logits, P, lg);
+  switch (K) {
+    case 4: hipLaunchKernelGGL(head_softmax_bf16s_kernel, dim3((unsigned)blocks), dim3(256), 0, st, a, ld, w, b, probs, logits, P, lg); break;
+#define DG_HS(N) case N: hipLaunchKernelGGL(head_softmax_k_bf16s_kernel<N>, dim3((unsigned)blocks), dim3(256), 0, st, a, ld, w, b, probs, logits, P, lg); break;
+    DG_HS(2) DG_HS(3) DG_HS(5) DG_HS(6) DG_HS(7) DG_HS(8)
+#undef DG_HS
+  }
   HIPCHECK(hipGetLastError());
   return DG_OK;
 }

@@ -193,13 +193,13 @@ struct depgan_ctx {
   float* fake_y2 = nullptr;        // [B*H*W]
   float last_sums[8];
 
-  // ---- inference context (bf16_mfma = 1 with nc_out = 4): the DEP-UResNet in learning phase 0 on the bf16 pipe ----
+  // ---- inference context (bf16_mfma = 1 with nc_out >= 2): the DEP-UResNet in learning phase 0 on the bf16 pipe ----
   // predict-only: generator arena, BN affines, noise MLP, forward panels and the fp32 forward activations; no critics, no
   // gradient tensors, no backward panels, no phase-1 buffers, no weight-gradient slab.  Every training entry refuses it
   // (infer_refuse) before any launch
   bool infer_only = false;
 
-  // ---- learning-phase-1 path (nc_out == 4, not the inference context) ----
+  // ---- learning-phase-1 path (nc_out >= 2, not the inference context) ----
   bool train_bn = false;
   unsigned last_drop_seed = 0;
   Tn draw_tmp;                     // gradient at the raw conv output (largest layer)

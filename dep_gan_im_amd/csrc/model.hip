@@ -1299,9 +1299,9 @@ int depgan_create(const depgan_config* cfg, depgan_ctx** out) {
     dg_set_error("depgan_create: f32_split must be 0, 3 or 6, without bf16_weights / bf16_mfma, nc_out = 1");
     return DG_ERR_ARG;
   }
-  if (cfg->bf16_mfma && (!cfg->bf16_weights || (cfg->nc_out != 0 && cfg->nc_out != 1 && cfg->nc_out != 4))) {
-    dg_set_error("depgan_create: bf16_mfma needs bf16_weights = 1 and nc_out = 1 (the DEP-GAN generator) or nc_out = 4 "
-                 "(the DEP-UResNet as a predict-only inference context)");
+  if (cfg->bf16_mfma && !cfg->bf16_weights) {
+    dg_set_error("depgan_create: bf16_mfma needs bf16_weights = 1 and nc_out = 1 (the DEP-GAN generator) or nc_out in "
+                 "[2, %d] (the DEP-UResNet as a predict-only inference context)", DEPGAN_MAX_HEAD_CLASSES);
     return DG_ERR_ARG;
   }
   if (cfg->batch < 1 || cfg->height % 16 || cfg->width % 16 || cfg->height < 16 || cfg->width < 16 || cfg->nicg < 1 ||
@@ -1329,21 +1329,23 @@ int depgan_create(const depgan_config* cfg, depgan_ctx** out) {
     const char* wn = getenv("DEPGAN_WINOGRAD");
     c->winograd = !(wn && atoi(wn) == 0);
   }
-  if (c->cfg.nc_out <= 0) c->cfg.nc_out = 1;
-  if (c->cfg.nc_out != 1 && c->cfg.nc_out != 4) {
-    dg_set_error("depgan_create: nc_out must be 1 (DEP-GAN) or 4 (DEP-UResNet)");
+  if (c->cfg.nc_out == 0) c->cfg.nc_out = 1;
+  if (c->cfg.nc_out < 1 || c->cfg.nc_out > DEPGAN_MAX_HEAD_CLASSES) {
+    dg_set_error("depgan_create: nc_out must be 1 (DEP-GAN) or in [2, %d] (DEP-UResNet classes), not %d",
+                 DEPGAN_MAX_HEAD_CLASSES, c->cfg.nc_out);
     delete c;
     return DG_ERR_ARG;
   }
-  // bf16_mfma = 1 with nc_out = 4: the DEP-UResNet in learning phase 0 only (model.h); no phase-1 state
-  c->infer_only = c->cfg.bf16_mfma && c->cfg.nc_out == 4;
+  // bf16_mfma = 1 with nc_out >= 2: the DEP-UResNet in learning phase 0 only (model.h); no phase-1 state
+  c->infer_only = c->cfg.bf16_mfma && c->cfg.nc_out >= 2;
   c->train_bn = c->cfg.nc_out != 1 && !c->infer_only;
   memset(c->last_sums, 0, sizeof(c->last_sums));
   int rc = build_generator(c);
   if (rc == DG_OK && !c->train_bn && !c->infer_only) rc = build_critics(c);   // the supervised path has no critics
   if (rc == DG_OK && c->train_bn) rc = uresnet_build(c);
   // what u_head_logits and the softmax of depgan_g_forward use, and nothing else of uresnet_build
-  if (rc == DG_OK && c->infer_only) rc = dmalloc(c, &c->logits, (size_t)cfg->batch * cfg->height * cfg->width * 4);
+  if (rc == DG_OK && c->infer_only)
+    rc = dmalloc(c, &c->logits, (size_t)cfg->batch * cfg->height * cfg->width * c->cfg.nc_out);
   if (rc == DG_OK && !c->infer_only) {
     // slab workspace: the largest weight-gradient call of either network
     size_t mx = 0;
@@ -1359,7 +1361,7 @@ int depgan_create(const depgan_config* cfg, depgan_ctx** out) {
           if (fb > f) f = fb;
         }
       }
-      else if (L.kind == G_DECONV || (L.kind == G_HEAD && c->train_bn))
+      else if (L.kind == G_DECONV || (L.kind == G_HEAD && c->train_bn && L.Cout == 4))   // other counts: dg_head_k_wgrad
         f = dg_wgrad_part_floats(1, B, L.H, L.W, L.Cin, L.Cout);
       if (L.kind == G_DECONV && dg_deconv_wgrad_supported(B, L.H, L.W, L.Cin, L.Cout, L.in, L.dout)) {
         const size_t f4 = dg_deconv_wgrad_part_floats(B, L.H, L.W, L.Cin, L.Cout);   // four taps in one slab

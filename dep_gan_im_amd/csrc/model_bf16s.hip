@@ -8,7 +8,7 @@
 // c->attr, with gen_segmentation fused into gen_17's epilogue and gen_17 itself stored only under debug capture.
 // Third consumer (depgan_set_g_update_storage, model_bf16s_train.hip): the generator update; g_forward_bf16s(train = true)
 // runs the FiLM layers on the sibling kernel that also keeps the pre-FiLM tensor and the ReLU decisions.
-// Fourth consumer (an inference context: bf16_mfma = 1 with nc_out = 4): depgan_g_forward_bf16s of the DEP-UResNet in
+// Fourth consumer (an inference context: bf16_mfma = 1 with nc_out >= 2): depgan_g_forward_bf16s of the DEP-UResNet in
 // learning phase 0 -- the same walk, bit for bit, up to gen_17, then dg_head_softmax_bf16s instead of the tanh head.
 #include "model.h"
 
@@ -28,19 +28,19 @@ static int bf16s_malloc(depgan_ctx* c, __bf16** p, size_t elems) {
 
 int infer_refuse(const depgan_ctx* c, const char* who) {
   if (!c->infer_only) return DG_OK;
-  dg_set_error("%s: this is an inference context (created with bf16_mfma = 1 and nc_out = 4): predict-only, it holds no "
+  dg_set_error("%s: this is an inference context (created with bf16_mfma = 1 and nc_out >= 2): predict-only, it holds no "
                "critics, gradients or optimiser scratch; depgan_g_forward and depgan_g_forward_bf16s are its entries",
                who);
   return DG_ERR_UNSUPPORTED;
 }
 
 // what the context must be for the bf16-storage forward; no HIP call.  softmax_head: the caller also serves the
-// inference context (nc_out = 4), which only depgan_g_forward_bf16s does
+// inference context (nc_out >= 2), which only depgan_g_forward_bf16s does
 int bf16s_check_ctx(const depgan_ctx* c, const char* who, bool softmax_head) {
   if (!c->cfg.bf16_mfma || !c->cfg.bf16_weights || (c->cfg.nc_out != 1 && !(softmax_head && c->infer_only))) {
     dg_set_error("%s: needs a context created with bf16_mfma = 1 (hence bf16_weights = 1, nc_out = 1%s); this one has "
                  "bf16_mfma = %d, bf16_weights = %d, nc_out = %d", who,
-                 softmax_head ? ", or nc_out = 4 for the inference context" : "", c->cfg.bf16_mfma, c->cfg.bf16_weights,
+                 softmax_head ? ", or nc_out >= 2 for the inference context" : "", c->cfg.bf16_mfma, c->cfg.bf16_weights,
                  c->cfg.nc_out);
     return DG_ERR_UNSUPPORTED;
   }
@@ -182,10 +182,10 @@ int g_forward_bf16s(depgan_ctx* c, const float* x, const float* z, float* out, i
       if (head_by_conv) continue;
       const TViewH in = L.hin;
       const long P = (long)n * L.H * L.W;
-      if (c->cfg.nc_out == 4) {
-        // the DEP-UResNet's head: four logits and their softmax from the stored gen_17, never fused into its epilogue
+      if (c->cfg.nc_out >= 2) {
+        // the DEP-UResNet's head: the class logits and their softmax from the stored gen_17, never fused into its epilogue
         ProfScope ps(c, 2, 2.0 * P * L.Cin * 4, "head softmax fwd(bf16s)", P * (2.0 * L.Cin + 16.0));
-        DGCHECK(dg_head_softmax_bf16s(in.p, in.sX, L.Wt, L.b, out, nullptr, P, L.Cin, 4, c->st));
+        DGCHECK(dg_head_softmax_bf16s(in.p, in.sX, L.Wt, L.b, out, nullptr, P, L.Cin, c->cfg.nc_out, c->st));
         continue;
       }
       ProfScope ps(c, 2, 2.0 * P * L.Cin, "head fwd(bf16s)", P * (2.0 * L.Cin + 4.0));

@@ -468,14 +468,31 @@ int depgan_op_affine_act(const float* in, float* out, float* out_pre, const floa
   return dg_affine_act(a, (hipStream_t)stream);
 }
 
+int depgan_op_softmax_ce(const float* logits, const float* onehot, const unsigned char* codes, float* probs, float* dz,
+                         float* loss_sum, long P, int C, void* stream) {
+  DGCHECK(dg_softmax_ce_check(logits, onehot, codes, probs, dz, loss_sum, P, C));
+  hipStream_t st = (hipStream_t)stream;
+  if (!onehot && !codes) return dg_softmax_ce(logits, nullptr, nullptr, probs, nullptr, nullptr, nullptr, P, C, nullptr, st);
+  // 2048 floats of reduction scratch, then the counter of out-of-range codes
+  DevTmp scratch(st);
+  DGCHECK(op_alloc(&scratch, 2048 + 4, "op_softmax_ce"));
+  unsigned* bad = reinterpret_cast<unsigned*>(scratch.as<float>() + 2048);
+  DGCHECK(dg_softmax_ce(logits, onehot, codes, probs, dz, loss_sum, bad, P, C, scratch.as<float>(), st));
+  if (!codes) return DG_OK;
+  unsigned h = 0;
+  if (hipMemcpyAsync(&h, bad, sizeof(h), hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) {
+    dg_set_error("op_softmax_ce: copy back failed");
+    return DG_ERR_HIP;
+  }
+  if (h) {
+    dg_set_error("op_softmax_ce: %u of %ld class codes are outside [0, %d)", h, P, C);
+    return DG_ERR_ARG;
+  }
+  return DG_OK;
+}
 int depgan_op_softmax_ce4(const float* logits, const float* onehot, float* probs, float* dz, float* loss_sum, long P,
                           void* stream) {
-  if (!logits || !probs || P < 1 || (onehot && (!dz || !loss_sum))) { dg_set_error("op_softmax_ce4: bad argument"); return DG_ERR_ARG; }
-  hipStream_t st = (hipStream_t)stream;
-  if (!onehot) return dg_softmax4(logits, probs, P, st);
-  DevTmp scratch(st);
-  DGCHECK(op_alloc(&scratch, 1024, "op_softmax_ce4"));
-  return dg_softmax_ce4(logits, onehot, probs, dz, loss_sum, P, scratch.as<float>(), st);
+  return depgan_op_softmax_ce(logits, onehot, nullptr, probs, dz, loss_sum, P, 4, stream);
 }
 
 int depgan_op_bn_rows_fwd(const float* x, float* y, int R, int C, int ld, const float* gamma, const float* beta,

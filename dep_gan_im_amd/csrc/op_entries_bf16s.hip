@@ -109,10 +109,18 @@ int depgan_op_edge_conv_bf16s(const float* in, const float* w_hwio, const float*
   return dg_edge_conv_bf16s(e, (hipStream_t)stream);
 }
 
+int depgan_op_head_softmax_k_bf16s(const void* a, long ld, const float* w, const float* b, float* probs, float* logits,
+                                   long P, int C, int K, void* stream) {
+  if (!a || !w || !b || !probs || P < 1 || C < 1 || ld < 1) { dg_set_error("op_head_softmax_bf16s: null or non-positive argument"); return DG_ERR_ARG; }
+  if (K < 2 || K > DEPGAN_MAX_HEAD_CLASSES) {
+    dg_set_error("op_head_softmax_k_bf16s: %d classes (2 to %d)", K, DEPGAN_MAX_HEAD_CLASSES);
+    return DG_ERR_ARG;
+  }
+  return dg_head_softmax_bf16s(reinterpret_cast<const __bf16*>(a), ld, w, b, probs, logits, P, C, K, (hipStream_t)stream);
+}
 int depgan_op_head_softmax_bf16s(const void* a, long ld, const float* w, const float* b, float* probs, float* logits,
                                  long P, int C, void* stream) {
-  if (!a || !w || !b || !probs || P < 1 || C < 1 || ld < 1) { dg_set_error("op_head_softmax_bf16s: null or non-positive argument"); return DG_ERR_ARG; }
-  return dg_head_softmax_bf16s(reinterpret_cast<const __bf16*>(a), ld, w, b, probs, logits, P, C, 4, (hipStream_t)stream);
+  return depgan_op_head_softmax_k_bf16s(a, ld, w, b, probs, logits, P, C, 4, stream);
 }
 
 int depgan_op_head_bf16s(const void* a, const float* w, const float* b, float* out, long P, int C, int tanh_act,

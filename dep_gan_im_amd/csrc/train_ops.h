@@ -41,11 +41,30 @@ int dg_bn_bwd_coeffs(const float* sums, const float* mean, const float* rstd, co
 int dg_axpby_ch(TView d, TView x, TView out, int B, int H, int W, int C, const float* A, const float* Bc,
                 const float* Cc, hipStream_t st);
 
-// softmax + keras categorical cross-entropy on 4-class logits: probs out, dz = dLoss/dlogits (loss = mean over
-// pixels), loss_sum[0] = sum over pixels of the per-pixel loss.    scratch: 1024 floats
-int dg_softmax_ce4(const float* logits, const float* onehot, float* probs, float* dz, float* loss_sum, long P,
-                   float* scratch, hipStream_t st);
-int dg_softmax4(const float* logits, float* probs, long P, hipStream_t st);
+// softmax + keras categorical cross-entropy on dense (P, C) logits, C = 2..8: probs out; with labels also
+// dz = dLoss/dlogits (loss = mean over pixels) and loss_sum[0] = sum over pixels of the per-pixel loss.  Labels are a
+// float32 one-hot row (onehot) or one class code per pixel (codes), never both; neither: probabilities only.  With
+// codes, bad_count[0] receives the number of pixels whose code is >= C (they add no loss and no gradient); with onehot
+// it receives 0 where it is given.  scratch: 2048 floats (unused without labels).  Rows are accessed 16 bytes at a time
+// where C % 4 == 0 (16-byte aligned operands), else float by float.
+int dg_softmax_ce(const float* logits, const float* onehot, const unsigned char* codes, float* probs, float* dz,
+                  float* loss_sum, unsigned* bad_count, long P, int C, float* scratch, hipStream_t st);
+// its argument checks alone (no HIP call): what an entry asks before it allocates
+int dg_softmax_ce_check(const float* logits, const float* onehot, const unsigned char* codes, const float* probs,
+                        const float* dz, const float* loss_sum, long P, int C);
+
+// the 1x1 head to K = 2..8 class logits on dense (P, K) rows; a, mask and din are pixel rows of C channels at strides
+// ld* (multiples of 4 floats, 16-byte aligned), w is (C, K) dense, C / 4 a power of two <= 64
+int dg_head_k_fwd(const float* a, long ld, const float* w, const float* b, float* logits, long P, int C, int K,
+                  hipStream_t st);
+// din[p][c] = (mask[p][c] > 0 or no mask) ? sum_k dz[p][k] w[c][k] : 0
+int dg_head_k_bwd(const float* dz, const float* w, const float* mask, long ldm, float* din, long ldd, long P, int C,
+                  int K, hipStream_t st);
+// dW[c][k] = sum_p a[p][c] dz[p][k], db[k] = sum_p dz[p][k]; two fixed-order stages through
+// dg_head_k_wgrad_scratch(P, C, K) floats of scratch (at most 1024 (C K + K)); DG_ERR_ARG when scratch_floats is less
+int dg_head_k_wgrad(const float* a, long lda, const float* dz, float* dW, float* db, long P, int C, int K,
+                    float* scratch, size_t scratch_floats, hipStream_t st);
+size_t dg_head_k_wgrad_scratch(long P, int C, int K);
 
 // ---- noise MLP in training mode: BN over the rows of small [R][C] matrices ----
 // y = relu?( gamma*(x-mean)*rstd + beta ), stats over the R rows; also updates the moving stats

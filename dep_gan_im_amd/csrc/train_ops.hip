@@ -2,6 +2,7 @@
 // axis, block reductions through LDS, deterministic second passes.
 #include "train_ops.h"
 #include "epilogue.h"
+#include "softmax_row.h"
 
 __device__ __forceinline__ float t_wave_sum(float v) {
 #pragma unroll
@@ -447,31 +448,52 @@ int dg_axpby_ch(TView d, TView x, TView out, int B, int H, int W, int C, const f
 // ---------------------------------------------------------------------------
 // softmax + categorical cross-entropy (keras, probabilities path)
 // ---------------------------------------------------------------------------
-__global__ void softmax_ce4_kernel(const float* __restrict__ logits, const float* __restrict__ onehot,
-                                   float* __restrict__ probs, float* __restrict__ dz, float* __restrict__ part,
-                                   long P, float invN) {
+// One kernel for every class count C = 2..8 and every label source: LBL_ONEHOT reads a float32 one-hot row,
+// LBL_CODES forms t[k] = (k == code) in registers from one byte and then runs the same statements (so the two agree
+// value for value), LBL_NONE stops after the probabilities.  A code is only ever compared, never used as an index:
+// any byte is safe; a code >= C gives an all-zero t (no loss, no gradient from that pixel) and is counted.
+// Evaluation order (softmax_row.h): maximum and S over pairs folded left to right -- for C = 4 that is the pairwise
+// max and S = (p0 + p1) + (p2 + p3); S0, the loss, dot and pg run over k = 0..C-1 left to right.
+enum { LBL_NONE = 0, LBL_ONEHOT = 1, LBL_CODES = 2 };
+
+__device__ __forceinline__ unsigned t_block_sum_u(unsigned v, unsigned* shu4) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) shu4[threadIdx.x >> 6] = v;
+  __syncthreads();
+  return (shu4[0] + shu4[1]) + (shu4[2] + shu4[3]);
+}
+
+template <int C, int LBL>
+__global__ void softmax_ce_kernel(const float* __restrict__ logits, const float* __restrict__ onehot,
+                                  const unsigned char* __restrict__ codes, float* __restrict__ probs,
+                                  float* __restrict__ dz, float* __restrict__ part, unsigned* __restrict__ bad_part,
+                                  long P, float invN) {
   __shared__ float sh4[4];
+  __shared__ unsigned shu4[4];
   float lsum = 0.f;
+  unsigned nbad = 0;
   for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < (size_t)P; i += (size_t)gridDim.x * blockDim.x) {
-    const f32x4 z = *reinterpret_cast<const f32x4*>(logits + i * 4);
-    const float m = fmaxf(fmaxf(z[0], z[1]), fmaxf(z[2], z[3]));
-    f32x4 p;
-    float S0 = 0.f;
+    float z[C], p[C];
+    dg_row_load<C>(logits + i * C, z);
+    dg_softmax_row<C>(z, p);
+    dg_row_store<C>(probs + i * C, p);
+    if (LBL != LBL_NONE) {
+      float t[C];
+      if (LBL == LBL_ONEHOT) {
+        dg_row_load<C>(onehot + i * C, t);
+      } else {
+        const int code = codes[i];
 #pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      p[k] = expf(z[k] - m);
-      S0 += p[k];
-    }
-#pragma unroll
-    for (int k = 0; k < 4; ++k) p[k] /= S0;
-    *reinterpret_cast<f32x4*>(probs + i * 4) = p;
-    if (onehot) {
-      const f32x4 t = *reinterpret_cast<const f32x4*>(onehot + i * 4);
-      const float S = (p[0] + p[1]) + (p[2] + p[3]);
-      f32x4 gq;
+        for (int k = 0; k < C; ++k) t[k] = (k == code) ? 1.0f : 0.0f;
+        nbad += (code >= C) ? 1u : 0u;
+      }
+      const float S = dg_row_pairsum<C>(p);
+      float gq[C];
       float dot = 0.f;
 #pragma unroll
-      for (int k = 0; k < 4; ++k) {
+      for (int k = 0; k < C; ++k) {
         const float q = p[k] / S;
         const float r = fminf(fmaxf(q, 1e-7f), 1.0f - 1e-7f);
         lsum -= t[k] * logf(r);
@@ -481,47 +503,338 @@ __global__ void softmax_ce4_kernel(const float* __restrict__ logits, const float
         dot += gq[k] * p[k];
       }
       // q = p/S: dL/dp_j = gq_j/S - dot/S^2 ; softmax: dL/dz_k = p_k (dL/dp_k - sum_j p_j dL/dp_j)
-      f32x4 gp;
+      float gp[C];
       float pg = 0.f;
 #pragma unroll
-      for (int k = 0; k < 4; ++k) {
+      for (int k = 0; k < C; ++k) {
         gp[k] = gq[k] / S - dot / (S * S);
         pg += p[k] * gp[k];
       }
-      f32x4 o;
+      float o[C];
 #pragma unroll
-      for (int k = 0; k < 4; ++k) o[k] = p[k] * (gp[k] - pg);
-      *reinterpret_cast<f32x4*>(dz + i * 4) = o;
+      for (int k = 0; k < C; ++k) o[k] = p[k] * (gp[k] - pg);
+      dg_row_store<C>(dz + i * C, o);
     }
   }
-  if (onehot) {
+  if (LBL != LBL_NONE) {
     lsum = t_block_sum(lsum, sh4);
     if (threadIdx.x == 0) part[blockIdx.x] = lsum;
   }
+  if (LBL == LBL_CODES) {
+    nbad = t_block_sum_u(nbad, shu4);
+    if (threadIdx.x == 0) bad_part[blockIdx.x] = nbad;
+  }
 }
-__global__ void sum_small_kernel(const float* __restrict__ part, int nb, float* __restrict__ out) {
+// second stage, one block: the block partials in index order; bad_out[0] = the out-of-range codes (0 without bad_part)
+__global__ void sum_small_kernel(const float* __restrict__ part, int nb, float* __restrict__ out,
+                                 const unsigned* __restrict__ bad_part, unsigned* __restrict__ bad_out) {
   __shared__ float sh4[4];
+  __shared__ unsigned shu4[4];
   float acc = 0.f;
   for (int i = threadIdx.x; i < nb; i += blockDim.x) acc += part[i];
   acc = t_block_sum(acc, sh4);
   if (threadIdx.x == 0) out[0] = acc;
+  if (bad_out) {
+    unsigned nbad = 0;
+    if (bad_part)
+      for (int i = threadIdx.x; i < nb; i += blockDim.x) nbad += bad_part[i];
+    nbad = t_block_sum_u(nbad, shu4);
+    if (threadIdx.x == 0) bad_out[0] = nbad;
+  }
 }
-int dg_softmax_ce4(const float* logits, const float* onehot, float* probs, float* dz, float* loss_sum, long P,
-                   float* scratch, hipStream_t st) {
+
+template <int C>
+static void softmax_ce_launch(int lbl, int nb, hipStream_t st, const float* logits, const float* onehot,
+                              const unsigned char* codes, float* probs, float* dz, float* part, unsigned* bad_part,
+                              long P, float invN) {
+  if (lbl == LBL_ONEHOT)
+    hipLaunchKernelGGL((softmax_ce_kernel<C, LBL_ONEHOT>), dim3(nb), dim3(256), 0, st, logits, onehot, codes, probs, dz,
+                       part, bad_part, P, invN);
+  else if (lbl == LBL_CODES)
+    hipLaunchKernelGGL((softmax_ce_kernel<C, LBL_CODES>), dim3(nb), dim3(256), 0, st, logits, onehot, codes, probs, dz,
+                       part, bad_part, P, invN);
+  else
+    hipLaunchKernelGGL((softmax_ce_kernel<C, LBL_NONE>), dim3(nb), dim3(256), 0, st, logits, onehot, codes, probs, dz,
+                       part, bad_part, P, invN);
+}
+
+int dg_softmax_ce_check(const float* logits, const float* onehot, const unsigned char* codes, const float* probs,
+                        const float* dz, const float* loss_sum, long P, int C) {
+  if (!logits || !probs || P < 1) { dg_set_error("dg_softmax_ce: null logits or probs, or P < 1"); return DG_ERR_ARG; }
+  if (C < DG_MIN_CLASSES || C > DG_MAX_CLASSES) {
+    dg_set_error("dg_softmax_ce: %d classes (the kernel covers %d to %d)", C, DG_MIN_CLASSES, DG_MAX_CLASSES);
+    return DG_ERR_ARG;
+  }
+  if (onehot && codes) { dg_set_error("dg_softmax_ce: one-hot labels and class codes are both given"); return DG_ERR_ARG; }
+  if ((onehot || codes) && (!dz || !loss_sum)) { dg_set_error("dg_softmax_ce: labels without dz or loss_sum"); return DG_ERR_ARG; }
+  // rows are read and written 16 bytes at a time where C is a multiple of 4, else float by float
+  const uintptr_t al = (C % 4 == 0) ? 15 : 3;
+  if ((((uintptr_t)logits | (uintptr_t)probs | (uintptr_t)onehot | (uintptr_t)dz) & al) || ((uintptr_t)loss_sum & 3)) {
+    dg_set_error("dg_softmax_ce: logits, probs, onehot and dz must be %d-byte aligned for %d classes", (int)al + 1, C);
+    return DG_ERR_ARG;
+  }
+  return DG_OK;
+}
+
+int dg_softmax_ce(const float* logits, const float* onehot, const unsigned char* codes, float* probs, float* dz,
+                  float* loss_sum, unsigned* bad_count, long P, int C, float* scratch, hipStream_t st) {
+  DGCHECK(dg_softmax_ce_check(logits, onehot, codes, probs, dz, loss_sum, P, C));
+  const int lbl = onehot ? LBL_ONEHOT : (codes ? LBL_CODES : LBL_NONE);
+  if (lbl != LBL_NONE && !scratch) { dg_set_error("dg_softmax_ce: labels without scratch"); return DG_ERR_ARG; }
+  if (lbl == LBL_CODES && !bad_count) { dg_set_error("dg_softmax_ce: class codes without a counter"); return DG_ERR_ARG; }
   const int nb = t_nblk((size_t)P, 1024);
-  hipLaunchKernelGGL(softmax_ce4_kernel, dim3(nb), dim3(256), 0, st, logits, onehot, probs, dz, scratch, P,
-                     1.0f / (float)P);
+  float* part = scratch;
+  unsigned* bad_part = scratch ? reinterpret_cast<unsigned*>(scratch + 1024) : nullptr;
+  const float invN = (lbl == LBL_NONE) ? 0.f : 1.0f / (float)P;
+  switch (C) {
+#define DG_SM(N) case N: softmax_ce_launch<N>(lbl, nb, st, logits, onehot, codes, probs, dz, part, bad_part, P, invN); break;
+    DG_SM(2) DG_SM(3) DG_SM(4) DG_SM(5) DG_SM(6) DG_SM(7) DG_SM(8)
+#undef DG_SM
+  }
   HIPCHECK(hipGetLastError());
-  hipLaunchKernelGGL(sum_small_kernel, dim3(1), dim3(256), 0, st, scratch, nb, loss_sum);
+  if (lbl == LBL_NONE) return DG_OK;
+  hipLaunchKernelGGL(sum_small_kernel, dim3(1), dim3(256), 0, st, part, nb, loss_sum,
+                     lbl == LBL_CODES ? bad_part : nullptr, bad_count);
   HIPCHECK(hipGetLastError());
   return DG_OK;
 }
-int dg_softmax4(const float* logits, float* probs, long P, hipStream_t st) {
-  hipLaunchKernelGGL(softmax_ce4_kernel, dim3(t_nblk((size_t)P, 1024)), dim3(256), 0, st, logits, nullptr, probs,
-                     nullptr, nullptr, P, 0.f);
+
+// ---------------------------------------------------------------------------
+// the 1x1 head to K class logits for K other than 4 (K = 4 keeps the direct-convolution and MFMA weight-gradient
+// launches of uresnet.hip): dense rows of K floats, HBM-bound, K a template parameter so that a row stays in registers
+// ---------------------------------------------------------------------------
+// Forward.  head_fwd_kernel's lane mapping (C / 4 lanes per pixel, one 16-byte load each) with K columns of w (C, K):
+// per 4-channel part v = a0 w0, fmaf over channels 1..3; xor butterfly over the parts; + b[k].  The grid stride is a
+// multiple of 256, hence of the lanes per pixel: a lane keeps its part and loads its 4 K weights once.
+template <int K>
+__global__ __launch_bounds__(256) void head_k_fwd_kernel(const float* __restrict__ a, long ld,
+                                                          const float* __restrict__ w, const float* __restrict__ b,
+                                                          float* __restrict__ logits, long P, int lgLP) {
+#pragma clang fp contract(off)
+  const int LP = 1 << lgLP;
+  const int part = threadIdx.x & (LP - 1);
+  float wv[4][K];
+#pragma unroll
+  for (int j = 0; j < 4; ++j)
+#pragma unroll
+    for (int k = 0; k < K; ++k) wv[j][k] = w[(part * 4 + j) * K + k];
+  const long total = P << lgLP;
+  // the trip count is the same for every lane of a block: the shuffles below run with all 64 lanes
+  for (long t0 = blockIdx.x * 256L; t0 < total; t0 += gridDim.x * 256L) {
+    const long p = (t0 + threadIdx.x) >> lgLP;
+    float z[K];
+#pragma unroll
+    for (int k = 0; k < K; ++k) z[k] = 0.f;
+    if (p < P) {
+      const f32x4 av = *reinterpret_cast<const f32x4*>(a + p * ld + part * 4);
+#pragma unroll
+      for (int k = 0; k < K; ++k) {
+        float v = av[0] * wv[0][k];
+#pragma unroll
+        for (int j = 1; j < 4; ++j) v = fmaf(av[j], wv[j][k], v);
+        z[k] = v;
+      }
+    }
+    for (int o = LP >> 1; o > 0; o >>= 1) {
+#pragma unroll
+      for (int k = 0; k < K; ++k) z[k] += __shfl_xor(z[k], o, 64);
+    }
+    if (p < P && part == 0) {
+#pragma unroll
+      for (int k = 0; k < K; ++k) z[k] += b[k];
+      dg_row_store<K>(logits + p * K, z);
+    }
+  }
+}
+
+// Backward-data onto the head's input under its ReLU mask: din[p][c] = (a[p][c] > 0) ? sum_k dz[p][k] w[c][k] : 0,
+// the sum as d0 w0 then fmaf over k = 1..K-1.  Thread = one pixel x 4 channels, lane mapping as above.
+template <int K>
+__global__ __launch_bounds__(256) void head_k_bwd_kernel(const float* __restrict__ dz, const float* __restrict__ w,
+                                                          const float* __restrict__ a, long lda,
+                                                          float* __restrict__ din, long ldd, long P, int lgLP) {
+#pragma clang fp contract(off)
+  const int LP = 1 << lgLP;
+  const int part = threadIdx.x & (LP - 1);
+  float wv[4][K];
+#pragma unroll
+  for (int j = 0; j < 4; ++j)
+#pragma unroll
+    for (int k = 0; k < K; ++k) wv[j][k] = w[(part * 4 + j) * K + k];
+  const long total = P << lgLP;
+  for (long t = blockIdx.x * 256L + threadIdx.x; t < total; t += gridDim.x * 256L) {
+    const long p = t >> lgLP;
+    float d[K];
+    dg_row_load<K>(dz + p * K, d);
+    f32x4 o;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      float v = d[0] * wv[j][0];
+#pragma unroll
+      for (int k = 1; k < K; ++k) v = fmaf(d[k], wv[j][k], v);
+      o[j] = v;
+    }
+    if (a) {
+      const f32x4 av = *reinterpret_cast<const f32x4*>(a + p * lda + part * 4);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) o[j] = (av[j] > 0.f) ? o[j] : 0.f;
+    }
+    *reinterpret_cast<f32x4*>(din + p * ldd + part * 4) = o;
+  }
+}
+
+// Weight and bias gradient, two stages, fixed order, no atomics.  Stage 1: block b covers pixels [b ppb, (b+1) ppb);
+// thread (pixel row pp, part lp) walks its pixels in order, 4 K accumulators dW[c][k] += a[p][c] dz[p][k] (fmaf) and,
+// in part 0, K bias sums; the 256 / LP pixel rows are then added in index order through LDS -> part[b][C K + K].
+template <int K>
+__global__ __launch_bounds__(256) void head_k_wgrad_partial(const float* __restrict__ a, long lda,
+                                                             const float* __restrict__ dz, long P, int lgLP, int ppb,
+                                                             float* __restrict__ part) {
+  extern __shared__ __attribute__((aligned(16))) float sh[];   // [256][4 K], then [256 / LP][K]
+  const int LP = 1 << lgLP, PP = 256 >> lgLP;
+  const int lp = threadIdx.x & (LP - 1), pp = threadIdx.x >> lgLP;
+  float* shb = sh + 256 * 4 * K;
+  const long q0 = (long)blockIdx.x * ppb, q1 = min(q0 + ppb, P);
+  float acc[4][K], bs[K];
+#pragma unroll
+  for (int k = 0; k < K; ++k) {
+    bs[k] = 0.f;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) acc[j][k] = 0.f;
+  }
+  for (long q = q0 + pp; q < q1; q += PP) {
+    float d[K];
+    dg_row_load<K>(dz + q * K, d);
+    const f32x4 av = *reinterpret_cast<const f32x4*>(a + q * lda + lp * 4);
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+#pragma unroll
+      for (int k = 0; k < K; ++k) acc[j][k] = fmaf(av[j], d[k], acc[j][k]);
+    if (lp == 0) {
+#pragma unroll
+      for (int k = 0; k < K; ++k) bs[k] += d[k];
+    }
+  }
+#pragma unroll
+  for (int j = 0; j < 4; ++j)
+#pragma unroll
+    for (int k = 0; k < K; ++k) sh[threadIdx.x * 4 * K + j * K + k] = acc[j][k];
+  if (lp == 0) {
+#pragma unroll
+    for (int k = 0; k < K; ++k) shb[pp * K + k] = bs[k];
+  }
+  __syncthreads();
+  const int nw = LP * 4 * K, nout = nw + K;
+  for (int idx = threadIdx.x; idx < nout; idx += 256) {
+    float s = 0.f;
+    if (idx < nw) {
+      const int c = idx / K, k = idx - c * K;
+      const int l = c >> 2, j = c & 3;
+      for (int r = 0; r < PP; ++r) s += sh[((r << lgLP) + l) * 4 * K + j * K + k];
+    } else {
+      for (int r = 0; r < PP; ++r) s += shb[r * K + (idx - nw)];
+    }
+    part[(size_t)blockIdx.x * nout + idx] = s;
+  }
+}
+// Stage 2: one block per gradient entry, the nb block partials strided over the threads and a fixed-order block sum.
+// Entries [0, nw) are dW (C, K) dense -- the (1, 1, C, K) arena tensor -- and [nw, nw + K) are db.
+__global__ void head_k_wgrad_final(const float* __restrict__ part, int nb, int nout, int nw, float* __restrict__ dW,
+                                   float* __restrict__ db) {
+  __shared__ float sh4[4];
+  const int e = blockIdx.x;
+  float s = 0.f;
+  for (int b = threadIdx.x; b < nb; b += blockDim.x) s += part[(size_t)b * nout + e];
+  s = t_block_sum(s, sh4);
+  if (threadIdx.x == 0) {
+    if (e < nw) dW[e] = s; else db[e - nw] = s;
+  }
+}
+
+static int head_k_check(const char* who, long P, int C, int K, int* lg) {
+  const int LP = C / 4;
+  if (P < 1 || K < DG_MIN_CLASSES || K > DG_MAX_CLASSES) {
+    dg_set_error("%s: P >= 1 and %d to %d classes (got %ld, %d)", who, DG_MIN_CLASSES, DG_MAX_CLASSES, P, K);
+    return DG_ERR_ARG;
+  }
+  if (C < 4 || (C % 4) || LP > 64 || (LP & (LP - 1))) { dg_set_error("%s: C/4 must be a power of two <= 64", who); return DG_ERR_ARG; }
+  if (P > (0x7FFFFFFFFFFFFFFFL >> 8) / 256) { dg_set_error("%s: %ld pixels", who, P); return DG_ERR_UNSUPPORTED; }
+  *lg = 0;
+  while ((1 << *lg) < LP) ++*lg;
+  return DG_OK;
+}
+static unsigned head_k_blocks(long P, int lg) {
+  const long b = ((P << lg) + 255) / 256;
+  return (unsigned)(b > 2048 ? 2048 : b);   // 256 CUs x 8 resident blocks; the loop takes the rest
+}
+#define DG_HEAD_K(CALL)                                                                                    \
+  switch (K) {                                                                                             \
+    case 2: CALL(2); break; case 3: CALL(3); break; case 4: CALL(4); break; case 5: CALL(5); break;        \
+    case 6: CALL(6); break; case 7: CALL(7); break; case 8: CALL(8); break;                                \
+  }
+
+int dg_head_k_fwd(const float* a, long ld, const float* w, const float* b, float* logits, long P, int C, int K,
+                  hipStream_t st) {
+  int lg;
+  DGCHECK(head_k_check("dg_head_k_fwd", P, C, K, &lg));
+  if (!a || !w || !b || !logits || ld < C || (ld % 4) || (((uintptr_t)a) & 15) || (((uintptr_t)logits) & (K % 4 ? 3 : 15))) {
+    dg_set_error("dg_head_k_fwd: null, misaligned or short-strided operand");
+    return DG_ERR_ARG;
+  }
+#define DG_CALL(N) hipLaunchKernelGGL(head_k_fwd_kernel<N>, dim3(head_k_blocks(P, lg)), dim3(256), 0, st, a, ld, w, b, logits, P, lg)
+  DG_HEAD_K(DG_CALL)
+#undef DG_CALL
   HIPCHECK(hipGetLastError());
   return DG_OK;
 }
+
+int dg_head_k_bwd(const float* dz, const float* w, const float* mask, long ldm, float* din, long ldd, long P, int C,
+                  int K, hipStream_t st) {
+  int lg;
+  DGCHECK(head_k_check("dg_head_k_bwd", P, C, K, &lg));
+  if (!dz || !w || !din || ldd < C || (ldd % 4) || (((uintptr_t)din) & 15) || (((uintptr_t)dz) & (K % 4 ? 3 : 15)) ||
+      (mask && (ldm < C || (ldm % 4) || (((uintptr_t)mask) & 15)))) {
+    dg_set_error("dg_head_k_bwd: null, misaligned or short-strided operand");
+    return DG_ERR_ARG;
+  }
+#define DG_CALL(N) hipLaunchKernelGGL(head_k_bwd_kernel<N>, dim3(head_k_blocks(P, lg)), dim3(256), 0, st, dz, w, mask, ldm, din, ldd, P, lg)
+  DG_HEAD_K(DG_CALL)
+#undef DG_CALL
+  HIPCHECK(hipGetLastError());
+  return DG_OK;
+}
+
+size_t dg_head_k_wgrad_scratch(long P, int C, int K) {
+  int nb, ppb;
+  t_pix_grid(P, &nb, &ppb);
+  return (size_t)nb * ((size_t)C * K + K);
+}
+int dg_head_k_wgrad(const float* a, long lda, const float* dz, float* dW, float* db, long P, int C, int K,
+                    float* scratch, size_t scratch_floats, hipStream_t st) {
+  int lg;
+  DGCHECK(head_k_check("dg_head_k_wgrad", P, C, K, &lg));
+  if (!a || !dz || !dW || !db || !scratch || lda < C || (lda % 4) || (((uintptr_t)a) & 15) ||
+      (((uintptr_t)dz) & (K % 4 ? 3 : 15))) {
+    dg_set_error("dg_head_k_wgrad: null, misaligned or short-strided operand");
+    return DG_ERR_ARG;
+  }
+  if (dg_head_k_wgrad_scratch(P, C, K) > scratch_floats) {
+    dg_set_error("dg_head_k_wgrad: scratch holds %zu floats, %zu needed", scratch_floats, dg_head_k_wgrad_scratch(P, C, K));
+    return DG_ERR_ARG;
+  }
+  int nb, ppb;
+  t_pix_grid(P, &nb, &ppb);
+  const int nw = C * K, nout = nw + K;
+  const size_t lds = (size_t)(256 * 4 * K + (256 >> lg) * K) * sizeof(float);
+#define DG_CALL(N) hipLaunchKernelGGL(head_k_wgrad_partial<N>, dim3(nb), dim3(256), lds, st, a, lda, dz, P, lg, ppb, scratch)
+  DG_HEAD_K(DG_CALL)
+#undef DG_CALL
+  HIPCHECK(hipGetLastError());
+  hipLaunchKernelGGL(head_k_wgrad_final, dim3(nout), dim3(256), 0, st, scratch, nb, nout, nw, dW, db);
+  HIPCHECK(hipGetLastError());
+  return DG_OK;
+}
+#undef DG_HEAD_K
 
 // ---------------------------------------------------------------------------
 // BN over the rows of small matrices (noise MLP), thread = column

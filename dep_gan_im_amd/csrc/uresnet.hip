@@ -1,5 +1,6 @@
 // DEP-UResNet supervised path: the same U-ResNet as the DEP-GAN generator with a
-// 4-class softmax head, trained by my_network.fit / train_on_batch in Keras learning phase 1
+// softmax head over nc_out = 2..8 classes (the reference's n_label = 4, UT:573), trained by my_network.fit /
+// train_on_batch in Keras learning phase 1
 // (DEP-UResNet-wNoises-training-4fold.py "UT":355-427 model, 583-606 compile + fit).
 //
 // What phase 1 changes relative to the GAN closures (which never feed the learning phase):
@@ -64,8 +65,8 @@ int uresnet_build(depgan_ctx* c) {
   }
   DGCHECK(dmalloc(c, &c->draw_tmp.p, (size_t)B * maxOut));
   const size_t P = (size_t)B * c->cfg.height * c->cfg.width;
-  DGCHECK(dmalloc(c, &c->logits, P * 4));
-  DGCHECK(dmalloc(c, &c->dz, P * 4));
+  DGCHECK(dmalloc(c, &c->logits, P * c->cfg.nc_out));
+  DGCHECK(dmalloc(c, &c->dz, P * c->cfg.nc_out));
   DGCHECK(dmalloc(c, &c->loss_dev, 4));
   DGCHECK(dmalloc(c, &c->ones1k, 1024));
   DGCHECK(dmalloc(c, &c->zeros1k, 1024));
@@ -203,9 +204,18 @@ static int u_forward_train(depgan_ctx* c, const float* x, const float* z, int n,
   return DG_OK;
 }
 
-// 1x1 head to 4 logits (direct kernel: N = 4 is far below an MFMA tile)
+// the head's input, its gradient and its mask as pixel rows: dg_head_k_* take no (sB, sY, sX) views
+static bool u_flat(const TView& t, int H, int W) { return t.sY == (long)W * t.sX && t.sB == (long)H * t.sY; }
+
+// 1x1 head to the class logits, dense (P, nc_out).  4 classes: the direct kernel (N = 4 is far below an MFMA tile);
+// any other count: dg_head_k_fwd
 static int u_head_logits(depgan_ctx* c, int n) {
   GLayer& L = c->gl.back();
+  if (L.Cout != 4) {
+    ProfScope ps(c, 2, 0.0, "head fwd (classes)");
+    if (!u_flat(L.in, L.H, L.W)) { dg_set_error("uresnet: the head's input is not pixel-contiguous"); return DG_ERR_UNSUPPORTED; }
+    return dg_head_k_fwd(L.in.p, L.in.sX, L.Wt, L.b, c->logits, (long)n * L.H * L.W, L.Cin, L.Cout, c->st);
+  }
   ConvArgs a = conv_args(L.in, make_view(c->logits, L.H, L.W, 4), n, L.H, L.W, L.Cin, 4);
   a.ep.bias = L.b;
   conv_set_weights(&a, dg_plan_direct(), nullptr, L.Wt, L.Cin, 4);
@@ -243,7 +253,17 @@ static int u_conv_bwd(depgan_ctx* c, GLayer& L, size_t li, const float* x_user, 
 static int u_backward(depgan_ctx* c, const float* x, const float* z, int n) {
   for (int i = (int)c->gl.size() - 1; i >= 0; --i) {
     GLayer& L = c->gl[i];
-    if (L.kind == G_HEAD) {
+    if (L.kind == G_HEAD && L.Cout != 4) {
+      ProfScope ps(c, 2, 0.0, "head bwd (classes)");
+      const long P = (long)n * L.H * L.W;
+      if (!u_flat(L.in, L.H, L.W) || !u_flat(L.din, L.H, L.W) || (L.in_mask.p && !u_flat(L.in_mask, L.H, L.W))) {
+        dg_set_error("uresnet: the head's input, gradient or mask is not pixel-contiguous");
+        return DG_ERR_UNSUPPORTED;
+      }
+      DGCHECK(dg_head_k_wgrad(L.in.p, L.in.sX, c->dz, L.dW, L.db, P, L.Cin, L.Cout, c->scratch, c->scratchFloats,
+                              c->st));
+      DGCHECK(dg_head_k_bwd(c->dz, L.Wt, L.in_mask.p, L.in_mask.sX, L.din.p, L.din.sX, P, L.Cin, L.Cout, c->st));
+    } else if (L.kind == G_HEAD) {
       TView dzv = make_view(c->dz, L.H, L.W, 4);
       const ColSum cs = {n, nullptr, L.db, nullptr};
       DGCHECK(wgrad_full(c, 1, L.in, dzv, n, L.H, L.W, L.Cin, 4, nullptr, L.dW, nullptr, 0, 0, &cs));
@@ -285,7 +305,7 @@ static int u_backward(depgan_ctx* c, const float* x, const float* z, int n) {
 static int u_check(depgan_ctx* c, const char* who) {
   DGCHECK(infer_refuse(c, who));
   if (!c->train_bn) {
-    dg_set_error("%s: the context was not created with nc_out = 4", who);
+    dg_set_error("%s: the context was not created with nc_out >= 2", who);
     return DG_ERR_ARG;
   }
   return DG_OK;
@@ -301,66 +321,108 @@ int uresnet_predict(depgan_ctx* c, const float* x, const float* z, float* out, i
   DGCHECK(u_forward_infer(c, x, z, n));
   const long P = (long)n * c->cfg.height * c->cfg.width;
   ProfScope ps(c, 2, 0.0, "softmax");
-  return dg_softmax4(c->logits, out, P, c->st);
+  return dg_softmax_ce(c->logits, nullptr, nullptr, out, nullptr, nullptr, nullptr, P, c->cfg.nc_out, nullptr, c->st);
 }
 
-static int u_loss_to_host(depgan_ctx* c, long P, float* loss_host) {
-  float s = 0.f;
-  HIPCHECK(hipMemcpyAsync(&s, c->loss_dev, sizeof(float), hipMemcpyDeviceToHost, c->st));
+// the labels of one call: a float32 one-hot tensor (n, H, W, nc_out) or one class code per pixel (n, H, W)
+struct ULabels {
+  const float* onehot;
+  const unsigned char* codes;
+};
+
+// loss_dev[0] = summed loss, loss_dev[1] = the count of class codes outside [0, nc_out) as an unsigned
+static int u_softmax_ce(depgan_ctx* c, ULabels lab, long P) {
+  ProfScope ps(c, 2, 0.0, "softmax + cross-entropy");
+  return dg_softmax_ce(c->logits, lab.onehot, lab.codes, c->attr.p, c->dz, c->loss_dev,
+                       reinterpret_cast<unsigned*>(c->loss_dev + 1), P, c->cfg.nc_out, c->scratch, c->st);
+}
+
+// the one synchronisation of a call: the summed loss and the count of out-of-range class codes come back together
+static int u_loss_to_host(depgan_ctx* c, const char* who, long P, float* loss_host) {
+  float h[2] = {0.f, 0.f};
+  HIPCHECK(hipMemcpyAsync(h, c->loss_dev, sizeof(h), hipMemcpyDeviceToHost, c->st));
   HIPCHECK(hipStreamSynchronize(c->st));
-  c->last_sums[0] = s;
+  unsigned bad;
+  memcpy(&bad, &h[1], sizeof(bad));
+  c->last_sums[0] = h[0];
   c->last_sums[1] = (float)P;
-  if (loss_host) *loss_host = s / (float)P;
+  if (loss_host) *loss_host = h[0] / (float)P;
+  if (bad) {
+    dg_set_error("%s: %u of %ld class codes are outside [0, %d)", who, bad, P, c->cfg.nc_out);
+    return DG_ERR_ARG;
+  }
   return DG_OK;
 }
 
-static int u_grads(depgan_ctx* c, const float* x, const float* z, const float* labels, int n, unsigned drop_seed,
-                   float* loss_host, bool refresh_bn) {
-  DGCHECK(u_check(c, "uresnet_grads"));
+static int u_grads(depgan_ctx* c, const char* who, const float* x, const float* z, ULabels lab, int n,
+                   unsigned drop_seed, float* loss_host, bool refresh_bn) {
+  DGCHECK(u_check(c, who));
   if (n < 1 || n > c->cfg.batch) {
     dg_set_error("uresnet: n must be in [1, batch]");
     return DG_ERR_ARG;
   }
+  if (!lab.onehot && !lab.codes) { dg_set_error("%s: null labels", who); return DG_ERR_ARG; }
   const long P = (long)n * c->cfg.height * c->cfg.width;
   c->last_drop_seed = drop_seed;
   DGCHECK(u_forward_train(c, x, z, n, drop_seed));
   DGCHECK(u_head_logits(c, n));
-  {
-    ProfScope ps(c, 2, 0.0, "softmax + cross-entropy");
-    DGCHECK(dg_softmax_ce4(c->logits, labels, c->attr.p, c->dz, c->loss_dev, P, c->scratch, c->st));
-  }
+  DGCHECK(u_softmax_ce(c, lab, P));
   DGCHECK(u_backward(c, x, z, n));
   // the forward pass moved the BN moving statistics: the phase-0 affines are stale (the step variant
   // refreshes everything after Adam anyway)
   if (refresh_bn) DGCHECK(refresh_generator_bn(c));
-  return u_loss_to_host(c, P, loss_host);
+  const int rc = u_loss_to_host(c, who, P, loss_host);
+  // a refused step applies no Adam, so nothing after it refreshes the phase-0 affines of the statistics that moved
+  if (rc != DG_OK && !refresh_bn) refresh_generator_bn(c);
+  return rc;
+}
+
+static int u_step(depgan_ctx* c, const char* who, const float* x, const float* z, ULabels lab, int n,
+                  unsigned drop_seed, float* loss_host) {
+  DGCHECK(infer_refuse(c, who));
+  // an out-of-range class code comes back here as status 1, after the loss fetch: no Adam update, the step counter
+  // stays; the phase-1 forward has moved the BN moving statistics by then, as depgan_uresnet_grads always does
+  DGCHECK(u_grads(c, who, x, z, lab, n, drop_seed, loss_host, false));
+  return depgan_apply_adam(c, DEPGAN_NET_G);
+}
+
+static int u_eval(depgan_ctx* c, const char* who, const float* x, const float* z, ULabels lab, int n,
+                  float* loss_host) {
+  DGCHECK(u_check(c, who));
+  if (n < 1 || n > c->cfg.batch) { dg_set_error("uresnet_eval: n must be in [1, batch]"); return DG_ERR_ARG; }
+  if (!lab.onehot && !lab.codes) { dg_set_error("%s: null labels", who); return DG_ERR_ARG; }
+  const long P = (long)n * c->cfg.height * c->cfg.width;
+  DGCHECK(u_forward_infer(c, x, z, n));
+  DGCHECK(u_softmax_ce(c, lab, P));
+  return u_loss_to_host(c, who, P, loss_host);
 }
 
 extern "C" {
 
 int depgan_uresnet_grads(depgan_ctx* c, const float* x, const float* z, const float* labels, int n,
                          unsigned drop_seed, float* loss_host) {
-  return u_grads(c, x, z, labels, n, drop_seed, loss_host, true);
+  return u_grads(c, "uresnet_grads", x, z, ULabels{labels, nullptr}, n, drop_seed, loss_host, true);
 }
-
 int depgan_uresnet_step(depgan_ctx* c, const float* x, const float* z, const float* labels, int n,
                         unsigned drop_seed, float* loss_host) {
-  DGCHECK(infer_refuse(c, "depgan_uresnet_step"));
-  DGCHECK(u_grads(c, x, z, labels, n, drop_seed, loss_host, false));
-  return depgan_apply_adam(c, DEPGAN_NET_G);
+  return u_step(c, "depgan_uresnet_step", x, z, ULabels{labels, nullptr}, n, drop_seed, loss_host);
 }
-
 int depgan_uresnet_eval(depgan_ctx* c, const float* x, const float* z, const float* labels, int n,
                         float* loss_host) {
-  DGCHECK(u_check(c, "uresnet_eval"));
-  if (n < 1 || n > c->cfg.batch) { dg_set_error("uresnet_eval: n must be in [1, batch]"); return DG_ERR_ARG; }
-  const long P = (long)n * c->cfg.height * c->cfg.width;
-  DGCHECK(u_forward_infer(c, x, z, n));
-  {
-    ProfScope ps(c, 2, 0.0, "softmax + cross-entropy");
-    DGCHECK(dg_softmax_ce4(c->logits, labels, c->attr.p, c->dz, c->loss_dev, P, c->scratch, c->st));
-  }
-  return u_loss_to_host(c, P, loss_host);
+  return u_eval(c, "uresnet_eval", x, z, ULabels{labels, nullptr}, n, loss_host);
+}
+
+int depgan_uresnet_grads_sparse(depgan_ctx* c, const float* x, const float* z, const unsigned char* codes, int n,
+                                unsigned drop_seed, float* loss_host) {
+  return u_grads(c, "uresnet_grads_sparse", x, z, ULabels{nullptr, codes}, n, drop_seed, loss_host, true);
+}
+int depgan_uresnet_step_sparse(depgan_ctx* c, const float* x, const float* z, const unsigned char* codes, int n,
+                               unsigned drop_seed, float* loss_host) {
+  return u_step(c, "depgan_uresnet_step_sparse", x, z, ULabels{nullptr, codes}, n, drop_seed, loss_host);
+}
+int depgan_uresnet_eval_sparse(depgan_ctx* c, const float* x, const float* z, const unsigned char* codes, int n,
+                               float* loss_host) {
+  return u_eval(c, "uresnet_eval_sparse", x, z, ULabels{nullptr, codes}, n, loss_host);
 }
 
 }  // extern "C"

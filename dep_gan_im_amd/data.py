@@ -318,7 +318,8 @@ def load_uresnet_training_set(subjects, device=None, prefetch=2, progress=None):
     """UT:474-531: every subject whose FLAIR file exists, stacked along the slice axis.
     subjects: list of UResNetFiles (uresnet_file_lists).  Returns (flair (N, X, Y, 1), coded (N, X, Y, 1)) on `device`:
     the z-scored brain FLAIR and brain_wsc_1tp = coded*icv1 [*(1 - sl1)].  split_and_shuffle takes them as they are;
-    to_one_hot makes the labels.  A reader thread keeps `prefetch` decoded subjects ahead of the GPU."""
+    to_one_hot makes the labels, to_codes their 1-byte form for loss='sparse_categorical_crossentropy'.  A reader thread
+    keeps `prefetch` decoded subjects ahead of the GPU."""
     import torch
     dev = torch.device(device if device is not None else "cuda:0")
     todo = [s for s in subjects if os.path.isfile(s.flair_1tp)]
@@ -358,6 +359,33 @@ def to_one_hot(coded, n_class=4, device=None):
     _lib.check(lib.depgan_labels_to_onehot(_p(t), t.numel(), int(n_class), _p(out), _stream(dev, None)),
                "depgan_labels_to_onehot")
     return out
+
+
+def to_codes(coded, n_class=4, device=None):
+    """The 1-byte counterpart of to_one_hot: coded.astype(int) (truncation toward zero, UT:563) as class indices.
+    coded: (N, X, Y, 1) or (N, X, Y) array / tensor.  Returns (N, X, Y) uint8 on the GPU, the layout
+    Gen_UNet2D(..., nc_out=n_class).compile(loss='sparse_categorical_crossentropy').fit reads: 1 byte per pixel where
+    the one-hot tensor has 4 * n_class.  A value outside [0, n_class) raises DepganError, as in to_one_hot."""
+    if isinstance(n_class, bool) or not isinstance(n_class, (int, np.integer)) or not 1 <= int(n_class) <= 127:
+        raise ValueError("n_class must be an integer in [1, 127], got %r" % (n_class,))
+    shape = tuple(int(d) for d in (coded.shape if hasattr(coded, "shape") else np.shape(coded)))
+    if len(shape) == 4 and shape[3] == 1:
+        shape = shape[:3]
+    if len(shape) != 3:
+        raise ValueError("coded must be (N, X, Y, 1) or (N, X, Y), got shape %s" % (shape,))
+    import torch
+    if isinstance(coded, torch.Tensor):
+        dev = coded.device if device is None and coded.is_cuda else torch.device(device or "cuda:0")
+        t = coded.to(device=dev, dtype=torch.float32).reshape(shape)
+    else:
+        dev = torch.device(device if device is not None else "cuda:0")
+        t = torch.from_numpy(np.ascontiguousarray(np.asarray(coded), dtype=np.float32)).to(dev).reshape(shape)
+    ok = (t > -1.0) & (t < float(n_class))                 # trunc(v) in [0, n_class); False for NaN
+    bad = int((~ok).sum())
+    if bad:
+        raise _lib.DepganError("to_codes: %d of %d values truncate to a class outside [0, %d)"
+                               % (bad, t.numel(), int(n_class)))
+    return t.to(torch.uint8).contiguous()                  # float -> integer conversion truncates toward zero
 
 
 def data_prep_save(image_data):

@@ -25,6 +25,20 @@ def _torch():
     return torch
 
 
+def require_class_indices(labels):
+    """ValueError unless `labels` (NumPy array or tensor) has an integer dtype or is float with integral values: what
+    the sparse loss accepts.  Reads the array only; no library call."""
+    torch = _torch()
+    tens = isinstance(labels, torch.Tensor)
+    a = labels if tens else np.asarray(labels)
+    if (a.is_floating_point() if tens else a.dtype.kind == "f"):
+        if not bool((a == (torch if tens else np).trunc(a)).all()):                    # NaN and inf fail here too
+            raise ValueError("sparse labels must hold integral values (class indices)")
+    elif not tens and a.dtype.kind not in "iub":
+        raise ValueError("sparse labels must be an integer or float array, got dtype %s" % a.dtype)
+    return a
+
+
 class Engine:
     def __init__(self, batch, height=256, width=256, nicg=1, first_fm=32, im_thresh=0.5, delta=10.0, lrD=1e-4,
                  lrG=1e-4, beta1=0.0, beta2=0.9, adam_eps=1e-7, device=None, nc_out=1, bf16_weights=False,
@@ -252,21 +266,21 @@ class Engine:
     # ---- the inference context ----
     @property
     def inference_only(self):
-        """True for an engine created with bf16_mfma=True and nc_out=4: the DEP-UResNet in learning phase 0 on the bf16
+        """True for an engine created with bf16_mfma=True and nc_out>=2: the DEP-UResNet in learning phase 0 on the bf16
         matrix pipe.  g_forward (either storage) and the weight surface work; the context holds no critics, gradients or
         optimiser scratch, and every training helper raises ValueError without calling the library."""
-        return bool(self.cfg.bf16_mfma and self.cfg.nc_out == 4)
+        return bool(self.cfg.bf16_mfma and self.cfg.nc_out >= 2)
 
     def _need_trainable(self, what):
         if self.inference_only:
-            raise ValueError("%s: this engine is an inference context (bf16_mfma=True, nc_out=4), predict-only; train on "
-                             "an Engine(..., nc_out=4) and copy the weights over" % what)
+            raise ValueError("%s: this engine is an inference context (bf16_mfma=True, nc_out>=2), predict-only; train "
+                             "on an Engine(..., nc_out=%d) and copy the weights over" % (what, self.cfg.nc_out))
 
     # ---- forward ----
     @property
     def forward_storage(self):
         """How g_forward stores the activations between the generator's layers: "float32" (default) or "bfloat16"
-        (bf16_mfma engines only, the nc_out=4 inference context included: BASELINE config 4 with bf16 activations,
+        (bf16_mfma engines only, the nc_out>=2 inference context included: BASELINE config 4 with bf16 activations,
         depgan_g_forward_bf16s)."""
         return getattr(self, "_forward_storage", "float32")
 
@@ -277,9 +291,9 @@ class Engine:
     def _check_storage(self, storage):
         if storage not in ("float32", "bfloat16"):
             raise ValueError("forward storage must be 'float32' or 'bfloat16', got %r" % (storage,))
-        if storage == "bfloat16" and not (self.cfg.bf16_mfma and self.cfg.nc_out in (0, 1, 4)):
+        if storage == "bfloat16" and not (self.cfg.bf16_mfma and 0 <= self.cfg.nc_out <= _lib.MAX_HEAD_CLASSES):
             raise ValueError("bfloat16 activation storage needs an engine created with bf16_mfma=True (nc_out=1, or "
-                             "nc_out=4 for the predict-only inference context); this one has bf16_mfma=%d, nc_out=%d"
+                             "nc_out>=2 for the predict-only inference context); this one has bf16_mfma=%d, nc_out=%d"
                              % (self.cfg.bf16_mfma, self.cfg.nc_out))
         return storage
 
@@ -496,29 +510,61 @@ class Engine:
         o += 6 * k
         return cy, cd, ev, v[o:o + 6], int(best.value)
 
-    # ---- DEP-UResNet supervised path (nc_out = 4) ----
+    # ---- DEP-UResNet supervised path (nc_out >= 2) ----
+    def _codes(self, labels):
+        """(n, H, W) or (n, H, W, 1) class indices of any integer dtype, or float with integral values, as the contiguous
+        uint8 CUDA tensor the *_sparse entries read (NumPy arrays are narrowed on the host: 1 byte per pixel crosses the
+        bus).  A float that is not integral is a ValueError; a value outside [0, 255] becomes 255, which no class count
+        reaches, so the library reports it with the other out-of-range codes."""
+        torch = _torch()
+        tens = isinstance(labels, torch.Tensor)
+        a = labels if tens else np.asarray(labels)
+        if a.ndim == 4:
+            a = a[..., 0]
+        u8 = torch.uint8 if tens else np.uint8
+        if a.dtype != u8:
+            xp = torch if tens else np
+            a = require_class_indices(a)
+            if a.dtype == (torch.bool if tens else np.bool_):
+                a = a.to(u8) if tens else a.astype(u8)
+            else:
+                bad = (a < 0) | (a > 255)
+                a = xp.where(bad, xp.full_like(a, 255), a)
+                a = a.to(u8) if tens else a.astype(u8)
+        t = a if tens else torch.from_numpy(np.ascontiguousarray(a))
+        return t.to(self.device).contiguous()
+
     def uresnet(self, x, z, labels, mode="step", drop_seed=0):
         """mode 'step' = train_on_batch (UT:602-606), 'grads' = gradients only, 'eval' = phase-0 loss.
-        The leading dimension may be shorter than the engine batch (Keras' last batch of an epoch)."""
+        The leading dimension may be shorter than the engine batch (Keras' last batch of an epoch).
+        labels: one-hot (n, H, W, nc_out), cast to float32 like Keras' feed (depgan_uresnet_*), or class indices
+        (n, H, W) / (n, H, W, 1) of an integer dtype or float with integral values (depgan_uresnet_*_sparse, as uint8):
+        the shape picks the entry."""
         self._need_trainable("uresnet")
         x = self._dev(x)
         n = int(x.shape[0])
         if n < 1 or n > self.batch or tuple(x.shape[1:]) != (self.height, self.width, self.nicg):
             raise ValueError("images must be (n<=%d,%d,%d,%d), got %s" % (self.batch, self.height, self.width,
                                                                           self.nicg, tuple(x.shape)))
-        labels = self._dev(labels, (n, self.height, self.width, self.nc_out))
+        lshape = tuple(int(d) for d in (labels.shape if hasattr(labels, "shape") else np.shape(labels)))
+        sparse = self.nc_out != 1 and lshape in ((n, self.height, self.width), (n, self.height, self.width, 1))
+        if sparse:
+            labels = self._codes(labels)
+        else:
+            labels = self._dev(labels, (n, self.height, self.width, self.nc_out))
+        sfx = "_sparse" if sparse else ""
         z = self._dev(z).reshape(-1)
         if z.numel() != n * 32:
             raise ValueError("noise must be (%d,32,1)" % n)
         loss = C.c_float()
         self._use_current_stream()
         if mode == "eval":
-            check(self.lib.depgan_uresnet_eval(self.h, self._p(x), self._p(z), self._p(labels), n, C.byref(loss)),
-                  "depgan_uresnet_eval")
+            fn = getattr(self.lib, "depgan_uresnet_eval" + sfx)
+            check(fn(self.h, self._p(x), self._p(z), self._p(labels), n, C.byref(loss)), "depgan_uresnet_eval" + sfx)
         else:
-            fn = {"step": self.lib.depgan_uresnet_step, "grads": self.lib.depgan_uresnet_grads}[mode]
+            fn = getattr(self.lib, {"step": "depgan_uresnet_step", "grads": "depgan_uresnet_grads"}[mode] + sfx)
             check(fn(self.h, self._p(x), self._p(z), self._p(labels), n, C.c_uint(int(drop_seed) & 0xFFFFFFFF),
-                     C.byref(loss)), "depgan_uresnet_" + mode)
+                     C.byref(loss)), "depgan_uresnet_" + mode + sfx)
         return float(loss.value)
 
     def apply_adam(self, net):

@@ -175,7 +175,8 @@ def dem_metrics(x, pred, code_real, mask1, wmh1, mask2, wmh2, prob2, voxel_volum
 def label_census(pred, code_real=None, mask1=None, wmh1=None, mask2=None, wmh2=None, device=None,
                  return_labels=False):
     """The 18 integer counts of depgan_eval_label_counts (include/depgan.h) as a Python list.
-    pred: (..., C) float64 class probabilities (predict_mean of a 4-channel model); the other arrays have one value
+    pred: (..., C) float64 class probabilities (predict_mean of a C-channel model, any C; the counts themselves read the
+    reference's 4 codes); the other arrays have one value
     per pixel and may be None.  With return_labels the argmax label map (pred.shape[:-1], int8 CUDA tensor) comes too."""
     torch = _torch()
     lib = _lib.load()
@@ -199,8 +200,16 @@ def label_census(pred, code_real=None, mask1=None, wmh1=None, mask2=None, wmh2=N
     return (counts, labels) if return_labels else counts
 
 
-def label_metrics_from_census(c, voxel_volume):
-    """UE's scalar algebra on the label census (UE:572-700); vol_dsc has GE's 18-entry row order."""
+_FOUR_CODES = ("the DEP-UResNet metrics implement the reference's 4-code change map (UE:566-700); a prediction with %d "
+               "classes has no such reading -- predict_mean and label_census(..., return_labels=True) serve any class "
+               "count")
+
+
+def label_metrics_from_census(c, voxel_volume, n_class=4):
+    """UE's scalar algebra on the label census (UE:572-700); vol_dsc has GE's 18-entry row order.  The census must come
+    from a 4-class prediction (n_class says what it came from): any other count is a ValueError."""
+    if int(n_class) != 4:
+        raise ValueError(_FOUR_CODES % int(n_class))
     vol_1tp__ml = c[0] * voxel_volume / 1000                                          # UE:575-581
     vol_2tp__ml = c[1] * voxel_volume / 1000                                          # UE:584-591
     vol_out__ml = c[2] * voxel_volume / 1000                                          # UE:594-602
@@ -231,7 +240,11 @@ def label_metrics_from_census(c, voxel_volume):
 
 def uresnet_metrics(pred, code_real, mask1, wmh1, mask2, wmh2, voxel_volume):
     """All per-subject figures of UE:566-700 for one volume of slices; "labels" holds the label map (int8 CUDA
-    tensor, UE:570 convert_from_1hot) for save_uresnet_maps."""
+    tensor, UE:570 convert_from_1hot) for save_uresnet_maps.  pred must have the reference's 4 channels: any other count is
+    a ValueError."""
+    n_class = int(pred.shape[-1]) if len(getattr(pred, "shape", ())) else 0
+    if n_class != 4:
+        raise ValueError(_FOUR_CODES % n_class)
     c, labels = label_census(pred, code_real, mask1, wmh1, mask2, wmh2, return_labels=True)
     m = label_metrics_from_census(c, voxel_volume)
     m["labels"] = labels

@@ -17,7 +17,8 @@ from collections import OrderedDict
 
 import numpy as np
 
-from .engine import Engine
+from ._lib import MAX_HEAD_CLASSES
+from .engine import Engine, require_class_indices
 
 
 class WeightRef:
@@ -253,6 +254,9 @@ def _gen_static_table(nicg, fm, nc_out):
     return T
 
 
+_LOSSES = ("categorical_crossentropy", "sparse_categorical_crossentropy")
+
+
 class History:
     """keras.callbacks.History: .history['loss'] / ['val_loss'] per epoch (UT:609-618)."""
 
@@ -269,8 +273,10 @@ class GeneratorModel(_Model):
         super().__init__(input_shape, seed)
         if tuple(noiseZ_shape) != (32, 1) or first_fm != 32:
             raise ValueError("the HIP path is built for noiseZ_shape=(32,1), first_fm=32 (GT:520)")
-        if nc_out not in (1, 4):
-            raise ValueError("nc_out must be 1 (DEP-GAN generator, GT:520) or 4 (DEP-UResNet, UT:583)")
+        if isinstance(nc_out, bool) or not isinstance(nc_out, (int, np.integer)) or not 1 <= nc_out <= MAX_HEAD_CLASSES:
+            raise ValueError("nc_out must be 1 (DEP-GAN generator, GT:520) or the DEP-UResNet's class count in [2, %d] "
+                             "(the reference has 4, UT:573, 583), got %r" % (MAX_HEAD_CLASSES, nc_out))
+        nc_out = int(nc_out)
         if inference_dtype not in ("float32", "bfloat16"):
             raise ValueError("inference_dtype must be 'float32' or 'bfloat16', got %r" % (inference_dtype,))
         if inference_dtype == "bfloat16" and nc_out != 1 and not _inference_only:
@@ -284,6 +290,7 @@ class GeneratorModel(_Model):
             self.name = "DEP_UResNet"
         # Gen_UNet2D compiles the softmax variant itself: Adam(lr=1e-4), categorical cross-entropy (UT:427)
         self._lr = 1e-4
+        self._loss = "categorical_crossentropy"
         self._drop_rng = np.random.RandomState(seed)
 
     def _static_table(self):
@@ -307,7 +314,7 @@ class GeneratorModel(_Model):
 
     def inference_copy(self, dtype="bfloat16"):
         """A new predict-only model with this architecture and a copy of the current weights, whose private engine runs
-        predict on the bf16 matrix pipe with bf16 activation storage (for nc_out=4 the inference context of
+        predict on the bf16 matrix pipe with bf16 activation storage (for nc_out>=2 the inference context of
         include/depgan.h).  Later changes to this model are not followed.  predict, set_weights, load_weights,
         get_weights and save_weights work on the copy; compile, fit, train_on_batch, test_on_batch and evaluate raise
         RuntimeError.  For nc_out=1 the copy predicts what Gen_UNet2D(..., inference_dtype='bfloat16') with these
@@ -347,10 +354,16 @@ class GeneratorModel(_Model):
                                "(trainers.build_trainers), not compiled with a loss" % what)
 
     def compile(self, optimizer="adam", loss="categorical_crossentropy", lr=None, **_):
-        """model.compile(optimizer=Adam(lr=1e-4), loss='categorical_crossentropy')  (UT:427)."""
+        """model.compile(optimizer=Adam(lr=1e-4), loss='categorical_crossentropy')  (UT:427).
+        loss='sparse_categorical_crossentropy' is the same loss on integer labels: train_on_batch, test_on_batch,
+        evaluate, fit and its validation_data then take class indices (n, H, W) or (n, H, W, 1) -- any integer dtype, or
+        float with integral values (data.to_codes makes them, 1 byte per pixel) -- instead of the one-hot
+        (n, H, W, nc_out) tensor, and compute bit for bit what the one-hot encoding of those labels gives."""
         self._need_softmax("compile")
-        if loss != "categorical_crossentropy":
-            raise ValueError("only loss='categorical_crossentropy' is built (UT:427)")
+        if loss not in _LOSSES:
+            raise ValueError("loss must be 'categorical_crossentropy' (UT:427) or 'sparse_categorical_crossentropy', "
+                             "got %r" % (loss,))
+        self._loss = loss
         if lr is None:
             lr = getattr(optimizer, "lr", None)
         if lr is not None:
@@ -359,6 +372,21 @@ class GeneratorModel(_Model):
             self._lr = float(lr)
         return self
 
+    def _check_labels(self, labels, n, what):
+        """The labels' shape against the compiled loss, before anything reaches the library."""
+        H, W, _ = self.input_shape
+        shape = tuple(int(d) for d in (labels.shape if hasattr(labels, "shape") else np.shape(labels)))
+        if self._loss == "sparse_categorical_crossentropy":
+            want = ((n, H, W), (n, H, W, 1))
+            text = "class indices of shape (%d, %d, %d) or (%d, %d, %d, 1)" % (n, H, W, n, H, W)
+        else:
+            want = ((n, H, W, self.nc_out),)
+            text = "one-hot labels of shape (%d, %d, %d, %d)" % (n, H, W, self.nc_out)
+        if shape not in want:
+            raise ValueError("%s: loss=%r takes %s, got shape %s" % (what, self._loss, text, shape))
+        if self._loss == "sparse_categorical_crossentropy":
+            require_class_indices(labels)
+
     def _next_drop_seed(self):
         return int(self._drop_rng.randint(1, 2 ** 31 - 1))
 
@@ -366,18 +394,21 @@ class GeneratorModel(_Model):
         """One learning-phase-1 Adam step; returns the batch loss."""
         self._need_softmax("train_on_batch")
         x, z = inputs
+        self._check_labels(labels, len(x), "train_on_batch")
         eng = self._ensure_engine(len(x))
         return eng.uresnet(x, z, labels, "step", self._next_drop_seed() if drop_seed is None else drop_seed)
 
     def test_on_batch(self, inputs, labels):
         self._need_softmax("test_on_batch")
         x, z = inputs
+        self._check_labels(labels, len(x), "test_on_batch")
         return self._ensure_engine(len(x)).uresnet(x, z, labels, "eval")
 
     def evaluate(self, inputs, labels, batch_size=32, verbose=0):
         """Sample-weighted mean of the phase-0 loss over batches (keras Model.evaluate)."""
         self._need_softmax("evaluate")
         x, z = inputs
+        self._check_labels(labels, len(x), "evaluate")
         eng = self._ensure_engine(min(batch_size, len(x)))
         bs = min(batch_size, eng.batch)
         tot = 0.0
@@ -396,6 +427,9 @@ class GeneratorModel(_Model):
         n = len(x)
         if len(z) != n or len(labels) != n:
             raise ValueError("fit: images, noise and labels must have the same length")
+        self._check_labels(labels, n, "fit")
+        if validation_data is not None:
+            self._check_labels(validation_data[1], len(validation_data[0][0]), "fit(validation_data)")
         eng = self._ensure_engine(min(batch_size, n))
         bs = min(batch_size, eng.batch)
         hist = {"loss": []}

@@ -41,15 +41,17 @@ typedef struct depgan_config {
   float delta;      /* WGAN-GP weight (GT:37)                                          */
   float lrD, lrG;   /* GT:44-45                                                        */
   float beta1, beta2, adam_eps; /* Adam(beta_1=0, beta_2=0.9), K.epsilon() (GT:549)    */
-  int nc_out;       /* generator head channels: 1 = DEP-GAN (tanh, GT:520); 4 = DEP-UResNet (softmax, UT:583).
-                       0 is read as 1.                                                    */
+  int nc_out;       /* generator head channels: 1 = DEP-GAN (tanh, GT:520); 2..DEPGAN_MAX_HEAD_CLASSES = DEP-UResNet
+                       with that many classes (softmax; the reference's n_label = 4, UT:573, 583).  0 is read as 1;
+                       anything else is refused.  The bound of 8 lets a pixel's logits, probabilities and gradient
+                       live in registers as two float4.                                   */
   int bf16_weights; /* BASELINE config 4: 1 = every "/kernel" tensor is rounded to bf16 (RNE) before use, products
                        accumulate in fp32, the fp32 master copy and the Adam state stay fp32; 0 = fp32 weights */
   int bf16_mfma;    /* BASELINE config 4 on the bf16 matrix pipe (needs bf16_weights = 1): the MFMA convolutions AND the
                        weight-gradient contractions round their operands to bf16 (RNE) while staging them and run
                        v_mfma_f32_32x32x16_bf16 with fp32 accumulation; everything between them stays fp32.
                        0 = fp32 matrix pipe.
-                       With nc_out = 4 it creates an INFERENCE CONTEXT: the DEP-UResNet in learning phase 0 only
+                       With nc_out >= 2 it creates an INFERENCE CONTEXT: the DEP-UResNet in learning phase 0 only
                        (depgan_g_forward, depgan_g_forward_bf16s, the weight entry points).  It holds no critics,
                        gradient tensors, phase-1 buffers or weight-gradient slab, and every training entry
                        (depgan_uresnet_*, depgan_apply_adam, the WGAN-GP closures, depgan_d_forward and the
@@ -60,6 +62,7 @@ typedef struct depgan_config {
                        v_mfma_f32_32x32x16_bf16 with fp32 accumulation -- dropped terms are below 2^-24 (2^-16) of
                        |x||w|, i.e. fp32-grade (6) or TF32-grade-plus (3) products at 2.7x (5.3x) the fp32 matrix rate */
 } depgan_config;
+#define DEPGAN_MAX_HEAD_CLASSES 8
 
 enum { DEPGAN_NET_G = 0, DEPGAN_NET_D_Y2 = 1, DEPGAN_NET_D_DEM = 2 };
 enum { DEPGAN_ARENA_PARAMS = 0, DEPGAN_ARENA_NONTRAINABLE = 1, DEPGAN_ARENA_GRADS = 2,
@@ -161,10 +164,11 @@ int depgan_gen_iteration(depgan_ctx* ctx, const float* x_y2, const float* y2_y2,
                          int n_dem, long batch_stride, const float* x_gen, const float* y2_gen, const float* z_gen, int k,
                          float* out_host, int* best_host);
 
-/* DEP-UResNet supervised path (DEP-UResNet-wNoises-training-4fold.py "UT"; contexts created with nc_out = 4):
+/* DEP-UResNet supervised path (DEP-UResNet-wNoises-training-4fold.py "UT"; contexts created with nc_out = C in
+ * 2..DEPGAN_MAX_HEAD_CLASSES and bf16_mfma = 0):
  * my_network.fit / train_on_batch (UT:427, 602-606) = learning phase 1: batch-statistics BatchNorm with
  * moving-average updates, Dropout(0.25) after conv_10 (UT:388; drop_seed 0 disables it), softmax +
- * categorical cross-entropy, Adam(beta1, beta2 of the config).  labels: one-hot (n,H,W,4) fp32.
+ * categorical cross-entropy, Adam(beta1, beta2 of the config).  labels: one-hot (n,H,W,C) fp32.
  * n: samples in this call (1..batch; the last batch of a keras epoch may be short); loss_host: mean loss.
  * depgan_uresnet_grads leaves the gradients in the G arena and, like any phase-1 forward pass, moves
  * the BN moving statistics; depgan_uresnet_step also applies Adam.                                   */
@@ -175,6 +179,20 @@ int depgan_uresnet_step(depgan_ctx* ctx, const float* x_dev, const float* z_dev,
 /* validation loss in learning phase 0 (UT:606); n in 1..batch */
 int depgan_uresnet_eval(depgan_ctx* ctx, const float* x_dev, const float* z_dev, const float* labels_dev, int n,
                         float* loss_host);
+/* The same three entries with integer labels (keras sparse_categorical_crossentropy): codes_dev is (n,H,W) unsigned
+ * char, one class index per pixel, 1 byte where the one-hot tensor has 4 C.  The cross-entropy kernel forms the one-hot
+ * row in registers and runs the one-hot statements, so every result equals, bit for bit, that of the one-hot entry fed
+ * the one-hot encoding of the codes.  A code is only compared, never used as an index: any byte value is safe.  Pixels
+ * whose code is outside [0, C) add neither loss nor gradient and are counted on the device; the count comes back with
+ * the loss (the one synchronisation these entries have), and if it is not zero the entry returns status 1 with a
+ * message that gives it.  depgan_uresnet_step_sparse then applies NO Adam update and leaves the Adam step counter
+ * alone; the phase-1 forward has by then moved the BatchNorm moving statistics, as depgan_uresnet_grads always does. */
+int depgan_uresnet_grads_sparse(depgan_ctx* ctx, const float* x_dev, const float* z_dev, const unsigned char* codes_dev,
+                                int n, unsigned drop_seed, float* loss_host);
+int depgan_uresnet_step_sparse(depgan_ctx* ctx, const float* x_dev, const float* z_dev, const unsigned char* codes_dev,
+                               int n, unsigned drop_seed, float* loss_host);
+int depgan_uresnet_eval_sparse(depgan_ctx* ctx, const float* x_dev, const float* z_dev, const unsigned char* codes_dev,
+                               int n, float* loss_host);
 
 /* Un-normalised pieces of the last critic / generator evaluation, for exact
  * data-parallel reporting: critic: [sum D(real), sum D(fake), sum (norm-1)^2, n];
@@ -298,8 +316,8 @@ int depgan_debug_tensor(depgan_ctx* ctx, const char* name, float* host_dst, long
  *   Needs a context created with bf16_mfma = 1 (hence bf16_weights = 1, nc_out = 1); any other context gets status 3
  *   and a message naming the settings, before any launch.  The bf16 buffers (one per generator layer output, concat
  *   buffers shared) are allocated by the first call, kept, and freed by depgan_destroy.
- *   On an inference context (bf16_mfma = 1, nc_out = 4) the same walk, bit for bit up to gen_17, ends in
- *   depgan_op_head_softmax_bf16s of the stored gen_17 and out_dev is (n, H, W, 4) class probabilities; depgan_g_forward
+ *   On an inference context (bf16_mfma = 1, nc_out = K >= 2) the same walk, bit for bit up to gen_17, ends in
+ *   depgan_op_head_softmax_k_bf16s of the stored gen_17 and out_dev is (n, H, W, K) class probabilities; depgan_g_forward
  *   on such a context (bf16 pipe, fp32 storage, the direct 1x1 head, its own softmax launch) is the same-context A/B
  *   partner.
  * depgan_debug_tensor_bf16s: "g/out/<layer>" as depgan_debug_tensor resolves it, from the bf16 buffers of the last
@@ -437,7 +455,11 @@ int depgan_op_head_bwd_bf16s(int backward, const void* a, long ld, const float* 
  *   with row stride ld >= C elements (ld % 8 == 0), w (C, 4) fp32 (HWIO of a 1x1 kernel), each column in
  *   depgan_op_head_bf16s's arithmetic and order; probs[p] = softmax(z[p]) in depgan_op_softmax_ce4's arithmetic, dense
  *   fp32 (P, 4); `logits` (P, 4) receives z where it is not NULL.  a, w, probs and logits 16-byte aligned; C / 8 a power
- *   of two <= 64. */
+ *   of two <= 64.  It is depgan_op_head_softmax_k_bf16s with K = 4.
+ * depgan_op_head_softmax_k_bf16s: that head for K = 2..DEPGAN_MAX_HEAD_CLASSES classes: w (C, K), b (K), probs and
+ *   logits dense (P, K); each logit column in depgan_op_head_bf16s's arithmetic and order, the softmax in
+ *   depgan_op_softmax_ce's arithmetic for K classes.  a 16-byte aligned; w, probs and logits 16-byte aligned where
+ *   K % 4 == 0, else 4-byte. */
 int depgan_op_conv2d_bf16s(const void* in, long isB, long isY, long isX, const float* w_hwio, const float* bias,
                            const float* scale, const float* shift, const float* film_mul, const float* film_add,
                            int film_ld, const void* res, long rsB, long rsY, long rsX, void* out, long osB, long osY,
@@ -459,6 +481,8 @@ int depgan_op_head_bf16s(const void* a, const float* w, const float* b, float* o
                          void* hip_stream);
 int depgan_op_head_softmax_bf16s(const void* a, long ld, const float* w, const float* b, float* probs,
                                  float* logits_or_null, long P, int C, void* hip_stream);
+int depgan_op_head_softmax_k_bf16s(const void* a, long ld, const float* w, const float* b, float* probs,
+                                   float* logits_or_null, long P, int C, int K, void* hip_stream);
 
 /* ---- single operators (unit-test surface; device pointers) ---- */
 /* path: 0 auto, 1 fp32 MFMA implicit GEMM, 2 direct, 3 bf16 MFMA implicit GEMM (both operands rounded to bf16, RNE),
@@ -576,9 +600,21 @@ int depgan_op_bn_backward(const float* dy, const float* raw, float* draw, long s
 int depgan_op_affine_act(const float* in, float* out, float* out_pre, const float* res, long sB, long sY, long sX,
                          const float* s, const float* t, const float* film_mul, const float* film_add, int film_ld,
                          int relu, int B, int H, int W, int C, unsigned drop_seed, float drop_rate, void* hip_stream);
-/* softmax over 4 logits per pixel; with onehot: dz = d(mean keras cross-entropy)/dlogits, loss_sum[0] = summed loss */
+/* softmax over 4 logits per pixel; with onehot: dz = d(mean keras cross-entropy)/dlogits, loss_sum[0] = summed loss.
+ * It is depgan_op_softmax_ce with C = 4 and no codes. */
 int depgan_op_softmax_ce4(const float* logits, const float* onehot, float* probs, float* dz, float* loss_sum, long P,
                           void* hip_stream);
+/* softmax over C = 2..DEPGAN_MAX_HEAD_CLASSES logits per pixel, dense rows (P, C).  Labels: `onehot` (P, C) fp32 or
+ * `codes` (P) unsigned char class indices, at most one of them; both NULL: probabilities only (dz, loss_sum unused).
+ * With labels dz = d(mean keras cross-entropy)/dlogits and loss_sum[0] = summed loss; the call with codes equals the
+ * call with their one-hot encoding bit for bit (the kernel forms t[j] = (j == code) in registers and runs the same
+ * statements).  Order of evaluation: the row maximum and the renormalising sum S over the pairs (0,1), (2,3), ...
+ * folded left to right, an odd last element last; every other sum over k = 0..C-1 left to right.  A code is only
+ * compared, so any byte is safe; pixels with a code >= C add no loss and no gradient, and if there are any the entry
+ * returns status 1 with their count (with codes it synchronises the stream for that).  logits, onehot, probs and dz
+ * 16-byte aligned where C % 4 == 0, else 4-byte. */
+int depgan_op_softmax_ce(const float* logits, const float* onehot, const unsigned char* codes, float* probs, float* dz,
+                         float* loss_sum, long P, int C, void* hip_stream);
 /* BatchNorm over the R rows of an [R][ld] matrix (first C columns), moving statistics updated when given:
  * moving = momentum*moving + (1 - momentum)*(mean, var*corr) */
 int depgan_op_bn_rows_fwd(const float* x, float* y, int R, int C, int ld, const float* gamma, const float* beta,
