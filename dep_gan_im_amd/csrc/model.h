@@ -204,6 +204,10 @@ struct depgan_ctx {
   unsigned last_drop_seed = 0;
   Tn draw_tmp;                     // gradient at the raw conv output (largest layer)
   float *logits = nullptr, *dz = nullptr, *loss_dev = nullptr;
+  // depgan_uresnet_set_census(1): every depgan_uresnet_* call also counts (true class, predicted class) pairs; the
+  // table of the last such call, row = true class, row-major nc_out x nc_out
+  bool census = false, census_valid = false;
+  long long last_census[DEPGAN_MAX_HEAD_CLASSES * DEPGAN_MAX_HEAD_CLASSES];
   float *ones1k = nullptr, *zeros1k = nullptr;
   float *n_mean0 = nullptr, *n_rstd0 = nullptr, *n_mean1 = nullptr, *n_rstd1 = nullptr, *n_meanh = nullptr,
         *n_rstdh = nullptr;

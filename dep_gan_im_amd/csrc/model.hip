@@ -1779,6 +1779,11 @@ int depgan_debug_tensor(depgan_ctx* c, const char* name, float* host, long cap, 
     float* p = nm == "g/heads" ? c->na.heads : (nm == "g/noise_a0" ? c->na.a0 : c->na.a1);
     v = make_view(p, 1, 1, 1024);
     N = B; H = 1; W = 1; C = 1024;
+  } else if (nm == "g/probs") {
+    // the softmax of the last depgan_uresnet_* call (training: the phase-1 probabilities the loss was taken from)
+    if (c->cfg.nc_out < 2) { dg_set_error("debug_tensor: g/probs needs a context with a softmax head (nc_out >= 2)"); return DG_ERR_ARG; }
+    v = c->attr.view();
+    N = B; H = c->cfg.height; W = c->cfg.width; C = c->cfg.nc_out;
   } else if (starts("g/out/") || starts("g/u/")) {
     const bool want_u = starts("g/u/");
     const std::string ln = want_u ? rest("g/u/") : rest("g/out/");

@@ -490,6 +490,35 @@ int depgan_op_softmax_ce(const float* logits, const float* onehot, const unsigne
   }
   return DG_OK;
 }
+int depgan_op_softmax_ce_census(const float* logits, const float* onehot, const unsigned char* codes, float* probs,
+                                float* dz, float* loss_sum, long long* census_host, long P, int C, void* stream) {
+  if (!census_host) { dg_set_error("op_softmax_ce_census: null census_host"); return DG_ERR_ARG; }
+  if (!onehot && !codes) { dg_set_error("op_softmax_ce_census: a census needs labels (onehot or codes)"); return DG_ERR_ARG; }
+  DGCHECK(dg_softmax_ce_check(logits, onehot, codes, probs, dz, loss_sum, P, C));
+  hipStream_t st = (hipStream_t)stream;
+  // the reduction scratch, then the counter of out-of-range codes (padded to 8 bytes) and the C*C 64-bit counts
+  const size_t cap = (dg_softmax_ce_census_scratch(P, C) + 1) & ~(size_t)1;      // even: the counts behind it are 8-byte aligned
+  DevTmp scratch(st);
+  DGCHECK(op_alloc(&scratch, cap + 2 + 2 * (size_t)C * C, "op_softmax_ce_census"));
+  unsigned* bad = reinterpret_cast<unsigned*>(scratch.as<float>() + cap);
+  unsigned long long* cen = reinterpret_cast<unsigned long long*>(scratch.as<float>() + cap + 2);
+  DGCHECK(dg_softmax_ce_census(logits, onehot, codes, probs, dz, loss_sum, bad, cen, P, C, scratch.as<float>(), cap, st));
+  struct {
+    unsigned bad, pad;
+    long long census[DEPGAN_MAX_HEAD_CLASSES * DEPGAN_MAX_HEAD_CLASSES];
+  } h;
+  if (hipMemcpyAsync(&h, bad, 8 + (size_t)C * C * sizeof(long long), hipMemcpyDeviceToHost, st) != hipSuccess ||
+      hipStreamSynchronize(st) != hipSuccess) {
+    dg_set_error("op_softmax_ce_census: copy back failed");
+    return DG_ERR_HIP;
+  }
+  memcpy(census_host, h.census, (size_t)C * C * sizeof(long long));
+  if (h.bad) {
+    dg_set_error("op_softmax_ce_census: %u of %ld class codes are outside [0, %d)", h.bad, P, C);
+    return DG_ERR_ARG;
+  }
+  return DG_OK;
+}
 int depgan_op_softmax_ce4(const float* logits, const float* onehot, float* probs, float* dz, float* loss_sum, long P,
                           void* stream) {
   return depgan_op_softmax_ce(logits, onehot, nullptr, probs, dz, loss_sum, P, 4, stream);

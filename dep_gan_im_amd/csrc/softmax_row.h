@@ -60,6 +60,21 @@ __device__ __forceinline__ float dg_row_pairsum(const float (&p)[C]) {
   return s;
 }
 
+// first index of the row's maximum: k = 0..C-1 left to right, replaced on a strict >, so a tie keeps the lower index
+// (np.argmax of the same floats; a NaN never wins a comparison here, where np.argmax would return it)
+template <int C>
+__device__ __forceinline__ int dg_row_argmax(const float (&r)[C]) {
+  int a = 0;
+  float m = r[0];
+#pragma unroll
+  for (int k = 1; k < C; ++k)
+    if (r[k] > m) {
+      m = r[k];
+      a = k;
+    }
+  return a;
+}
+
 // p = softmax(z): maximum in dg_row_max's order, e_k = expf(z_k - m), S0 = ((0 + e_0) + e_1) + ... left to right,
 // p_k = e_k / S0
 template <int C>

@@ -49,6 +49,17 @@ int dg_axpby_ch(TView d, TView x, TView out, int B, int H, int W, int C, const f
 // where C % 4 == 0 (16-byte aligned operands), else float by float.
 int dg_softmax_ce(const float* logits, const float* onehot, const unsigned char* codes, float* probs, float* dz,
                   float* loss_sum, unsigned* bad_count, long P, int C, float* scratch, hipStream_t st);
+// dg_softmax_ce with labels plus the class census of the same pass: census[tc * C + pc] (C*C 64-bit device counts,
+// 8-byte aligned) = the pixels of true class tc predicted as pc.  pc = the first index of the maximum of the stored
+// probability row (k = 0..C-1, strict >: np.argmax of probs); tc = the code, or the first index of the maximum of the
+// one-hot row (an all-zero row is class 0).  A pixel whose code is >= C is in no bin: sum(census) + bad_count == P.
+// probs, dz and loss_sum have the bits dg_softmax_ce gives.  Two stages, no atomics, nothing to zero between calls; the
+// block tables follow the 2048 floats of the other partials: dg_softmax_ce_census_scratch(P, C) floats of scratch
+// (at most 2048 + 1024 C C), DG_ERR_ARG when scratch_floats is less.  bad_count is required (0 with onehot).
+size_t dg_softmax_ce_census_scratch(long P, int C);
+int dg_softmax_ce_census(const float* logits, const float* onehot, const unsigned char* codes, float* probs, float* dz,
+                         float* loss_sum, unsigned* bad_count, unsigned long long* census, long P, int C, float* scratch,
+                         size_t scratch_floats, hipStream_t st);
 // its argument checks alone (no HIP call): what an entry asks before it allocates
 int dg_softmax_ce_check(const float* logits, const float* onehot, const unsigned char* codes, const float* probs,
                         const float* dz, const float* loss_sum, long P, int C);

@@ -454,6 +454,14 @@ int dg_axpby_ch(TView d, TView x, TView out, int B, int H, int W, int C, const f
 // any byte is safe; a code >= C gives an all-zero t (no loss, no gradient from that pixel) and is counted.
 // Evaluation order (softmax_row.h): maximum and S over pairs folded left to right -- for C = 4 that is the pairwise
 // max and S = (p0 + p1) + (p2 + p3); S0, the loss, dot and pg run over k = 0..C-1 left to right.
+//
+// CENSUS (labels present): every pixel also adds 1 to bin [tc][pc] of a C x C table, tc = the code (LBL_CODES; a code
+// >= C joins no bin, it is in nbad) or the first arg-max of the label row (LBL_ONEHOT; an all-zero row is class 0),
+// pc = the first arg-max of p as stored.  Integers only: no float statement reads anything the census writes, and the
+// CENSUS = false instantiations compile to the instructions they were.  In a block the table is kept per wave, with no
+// atomics and no LDS traffic in the loop: one ballot per true class and one per predicted class (2 C compares), then
+// lane l, the owner of bin l = k * C + j, adds popcount(ballot_t[k] & ballot_p[j]) to its one counter.  The four
+// waves' tables meet in LDS after the loop and C*C lanes store the block's partial.
 enum { LBL_NONE = 0, LBL_ONEHOT = 1, LBL_CODES = 2 };
 
 __device__ __forceinline__ unsigned t_block_sum_u(unsigned v, unsigned* shu4) {
@@ -465,55 +473,79 @@ __device__ __forceinline__ unsigned t_block_sum_u(unsigned v, unsigned* shu4) {
   return (shu4[0] + shu4[1]) + (shu4[2] + shu4[3]);
 }
 
-template <int C, int LBL>
+template <int C, int LBL, bool CENSUS>
 __global__ void softmax_ce_kernel(const float* __restrict__ logits, const float* __restrict__ onehot,
                                   const unsigned char* __restrict__ codes, float* __restrict__ probs,
                                   float* __restrict__ dz, float* __restrict__ part, unsigned* __restrict__ bad_part,
-                                  long P, float invN) {
+                                  unsigned* __restrict__ cen_part, long P, float invN) {
+  static_assert(!CENSUS || LBL != LBL_NONE, "a census needs labels");
   __shared__ float sh4[4];
   __shared__ unsigned shu4[4];
   float lsum = 0.f;
   unsigned nbad = 0;
-  for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < (size_t)P; i += (size_t)gridDim.x * blockDim.x) {
-    float z[C], p[C];
-    dg_row_load<C>(logits + i * C, z);
-    dg_softmax_row<C>(z, p);
-    dg_row_store<C>(probs + i * C, p);
-    if (LBL != LBL_NONE) {
-      float t[C];
-      if (LBL == LBL_ONEHOT) {
-        dg_row_load<C>(onehot + i * C, t);
-      } else {
-        const int code = codes[i];
+  // CENSUS: lane l of a wave owns bin l (true class l / C, predicted class l % C) of the wave's table
+  const int bin_t = CENSUS ? (int)(threadIdx.x & 63) / C : 0, bin_p = CENSUS ? (int)(threadIdx.x & 63) % C : 0;
+  unsigned cen = 0;
+  // CENSUS keeps the whole wave in the loop until its last lane is done (a ballot must meet every bin's owner)
+  for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; CENSUS ? (__any(i < (size_t)P) != 0) : (i < (size_t)P);
+       i += (size_t)gridDim.x * blockDim.x) {
+    int tc = -1, pc = -1;
+    if (!CENSUS || i < (size_t)P) {
+      float z[C], p[C];
+      dg_row_load<C>(logits + i * C, z);
+      dg_softmax_row<C>(z, p);
+      dg_row_store<C>(probs + i * C, p);
+      if (LBL != LBL_NONE) {
+        float t[C];
+        if (LBL == LBL_ONEHOT) {
+          dg_row_load<C>(onehot + i * C, t);
+          if (CENSUS) tc = dg_row_argmax<C>(t);
+        } else {
+          const int code = codes[i];
 #pragma unroll
-        for (int k = 0; k < C; ++k) t[k] = (k == code) ? 1.0f : 0.0f;
-        nbad += (code >= C) ? 1u : 0u;
+          for (int k = 0; k < C; ++k) t[k] = (k == code) ? 1.0f : 0.0f;
+          nbad += (code >= C) ? 1u : 0u;
+          if (CENSUS) tc = (code < C) ? code : -1;
+        }
+        const float S = dg_row_pairsum<C>(p);
+        float gq[C];
+        float dot = 0.f;
+#pragma unroll
+        for (int k = 0; k < C; ++k) {
+          const float q = p[k] / S;
+          const float r = fminf(fmaxf(q, 1e-7f), 1.0f - 1e-7f);
+          lsum -= t[k] * logf(r);
+          // clip's gradient passes on the closed interval, bounds included (TF clip_by_value, torch.clamp)
+          const bool in = (q >= 1e-7f) && (q <= 1.0f - 1e-7f);
+          gq[k] = in ? (-t[k] * invN / q) : 0.f;    // dL/dq
+          dot += gq[k] * p[k];
+        }
+        // q = p/S: dL/dp_j = gq_j/S - dot/S^2 ; softmax: dL/dz_k = p_k (dL/dp_k - sum_j p_j dL/dp_j)
+        float gp[C];
+        float pg = 0.f;
+#pragma unroll
+        for (int k = 0; k < C; ++k) {
+          gp[k] = gq[k] / S - dot / (S * S);
+          pg += p[k] * gp[k];
+        }
+        float o[C];
+#pragma unroll
+        for (int k = 0; k < C; ++k) o[k] = p[k] * (gp[k] - pg);
+        dg_row_store<C>(dz + i * C, o);
+        if (CENSUS) pc = dg_row_argmax<C>(p);
       }
-      const float S = dg_row_pairsum<C>(p);
-      float gq[C];
-      float dot = 0.f;
+    }
+    if (CENSUS) {
+      // the ballots of the lane's own row and column, selected out of the C + C; a lane without a pixel, or with a code
+      // >= C, has tc = -1 and is in no ballot; lanes C*C.. own no bin (bin_t >= C)
+      unsigned long long mt = 0, mp = 0;
 #pragma unroll
       for (int k = 0; k < C; ++k) {
-        const float q = p[k] / S;
-        const float r = fminf(fmaxf(q, 1e-7f), 1.0f - 1e-7f);
-        lsum -= t[k] * logf(r);
-        // clip's gradient passes on the closed interval, bounds included (TF clip_by_value, torch.clamp)
-        const bool in = (q >= 1e-7f) && (q <= 1.0f - 1e-7f);
-        gq[k] = in ? (-t[k] * invN / q) : 0.f;    // dL/dq
-        dot += gq[k] * p[k];
+        const unsigned long long bt = __ballot(tc == k), bp = __ballot(pc == k);
+        mt = (bin_t == k) ? bt : mt;
+        mp = (bin_p == k) ? bp : mp;
       }
-      // q = p/S: dL/dp_j = gq_j/S - dot/S^2 ; softmax: dL/dz_k = p_k (dL/dp_k - sum_j p_j dL/dp_j)
-      float gp[C];
-      float pg = 0.f;
-#pragma unroll
-      for (int k = 0; k < C; ++k) {
-        gp[k] = gq[k] / S - dot / (S * S);
-        pg += p[k] * gp[k];
-      }
-      float o[C];
-#pragma unroll
-      for (int k = 0; k < C; ++k) o[k] = p[k] * (gp[k] - pg);
-      dg_row_store<C>(dz + i * C, o);
+      cen += (unsigned)__popcll(mt & mp);
     }
   }
   if (LBL != LBL_NONE) {
@@ -524,10 +556,22 @@ __global__ void softmax_ce_kernel(const float* __restrict__ logits, const float*
     nbad = t_block_sum_u(nbad, shu4);
     if (threadIdx.x == 0) bad_part[blockIdx.x] = nbad;
   }
+  if (CENSUS) {
+    __shared__ unsigned shc[4][64];
+    shc[threadIdx.x >> 6][threadIdx.x & 63] = cen;
+    __syncthreads();
+    const int b = threadIdx.x;
+    if (b < C * C) cen_part[(size_t)blockIdx.x * (C * C) + b] = (shc[0][b] + shc[1][b]) + (shc[2][b] + shc[3][b]);
+  }
 }
-// second stage, one block: the block partials in index order; bad_out[0] = the out-of-range codes (0 without bad_part)
+// second stage, one block: the block partials in index order; bad_out[0] = the out-of-range codes (0 without bad_part).
+// CENSUS: cen_out[b] = the sum over the nb blocks of bin b of their CC-entry tables, as 64-bit counts (wave g takes the
+// blocks g, g + 4, ..., lane b the bin; integer sums, any order gives the same table)
+template <bool CENSUS>
 __global__ void sum_small_kernel(const float* __restrict__ part, int nb, float* __restrict__ out,
-                                 const unsigned* __restrict__ bad_part, unsigned* __restrict__ bad_out) {
+                                 const unsigned* __restrict__ bad_part, unsigned* __restrict__ bad_out,
+                                 const unsigned* __restrict__ cen_part, unsigned long long* __restrict__ cen_out,
+                                 int CC) {
   __shared__ float sh4[4];
   __shared__ unsigned shu4[4];
   float acc = 0.f;
@@ -541,21 +585,37 @@ __global__ void sum_small_kernel(const float* __restrict__ part, int nb, float* 
     nbad = t_block_sum_u(nbad, shu4);
     if (threadIdx.x == 0) bad_out[0] = nbad;
   }
+  if (CENSUS) {
+    __shared__ unsigned long long shc[4][DG_MAX_CLASSES * DG_MAX_CLASSES];
+    const int g = threadIdx.x >> 6, b = threadIdx.x & 63;
+    unsigned long long a = 0;
+    if (b < CC)
+      for (int i = g; i < nb; i += 4) a += cen_part[(size_t)i * CC + b];
+    shc[g][b] = a;
+    __syncthreads();
+    if (g == 0 && b < CC) cen_out[b] = (shc[0][b] + shc[1][b]) + (shc[2][b] + shc[3][b]);
+  }
 }
 
 template <int C>
-static void softmax_ce_launch(int lbl, int nb, hipStream_t st, const float* logits, const float* onehot,
+static void softmax_ce_launch(int lbl, bool census, int nb, hipStream_t st, const float* logits, const float* onehot,
                               const unsigned char* codes, float* probs, float* dz, float* part, unsigned* bad_part,
-                              long P, float invN) {
-  if (lbl == LBL_ONEHOT)
-    hipLaunchKernelGGL((softmax_ce_kernel<C, LBL_ONEHOT>), dim3(nb), dim3(256), 0, st, logits, onehot, codes, probs, dz,
-                       part, bad_part, P, invN);
+                              unsigned* cen_part, long P, float invN) {
+  if (lbl == LBL_ONEHOT && census)
+    hipLaunchKernelGGL((softmax_ce_kernel<C, LBL_ONEHOT, true>), dim3(nb), dim3(256), 0, st, logits, onehot, codes, probs,
+                       dz, part, bad_part, cen_part, P, invN);
+  else if (lbl == LBL_CODES && census)
+    hipLaunchKernelGGL((softmax_ce_kernel<C, LBL_CODES, true>), dim3(nb), dim3(256), 0, st, logits, onehot, codes, probs,
+                       dz, part, bad_part, cen_part, P, invN);
+  else if (lbl == LBL_ONEHOT)
+    hipLaunchKernelGGL((softmax_ce_kernel<C, LBL_ONEHOT, false>), dim3(nb), dim3(256), 0, st, logits, onehot, codes, probs,
+                       dz, part, bad_part, cen_part, P, invN);
   else if (lbl == LBL_CODES)
-    hipLaunchKernelGGL((softmax_ce_kernel<C, LBL_CODES>), dim3(nb), dim3(256), 0, st, logits, onehot, codes, probs, dz,
-                       part, bad_part, P, invN);
+    hipLaunchKernelGGL((softmax_ce_kernel<C, LBL_CODES, false>), dim3(nb), dim3(256), 0, st, logits, onehot, codes, probs,
+                       dz, part, bad_part, cen_part, P, invN);
   else
-    hipLaunchKernelGGL((softmax_ce_kernel<C, LBL_NONE>), dim3(nb), dim3(256), 0, st, logits, onehot, codes, probs, dz,
-                       part, bad_part, P, invN);
+    hipLaunchKernelGGL((softmax_ce_kernel<C, LBL_NONE, false>), dim3(nb), dim3(256), 0, st, logits, onehot, codes, probs,
+                       dz, part, bad_part, cen_part, P, invN);
 }
 
 int dg_softmax_ce_check(const float* logits, const float* onehot, const unsigned char* codes, const float* probs,
@@ -576,27 +636,56 @@ int dg_softmax_ce_check(const float* logits, const float* onehot, const unsigned
   return DG_OK;
 }
 
-int dg_softmax_ce(const float* logits, const float* onehot, const unsigned char* codes, float* probs, float* dz,
-                  float* loss_sum, unsigned* bad_count, long P, int C, float* scratch, hipStream_t st) {
-  DGCHECK(dg_softmax_ce_check(logits, onehot, codes, probs, dz, loss_sum, P, C));
+// census: null, or C*C device counts; the block tables then follow the 2048 floats of the other partials
+static int softmax_ce_run(const float* logits, const float* onehot, const unsigned char* codes, float* probs, float* dz,
+                          float* loss_sum, unsigned* bad_count, unsigned long long* census, long P, int C, float* scratch,
+                          hipStream_t st) {
   const int lbl = onehot ? LBL_ONEHOT : (codes ? LBL_CODES : LBL_NONE);
   if (lbl != LBL_NONE && !scratch) { dg_set_error("dg_softmax_ce: labels without scratch"); return DG_ERR_ARG; }
   if (lbl == LBL_CODES && !bad_count) { dg_set_error("dg_softmax_ce: class codes without a counter"); return DG_ERR_ARG; }
   const int nb = t_nblk((size_t)P, 1024);
   float* part = scratch;
   unsigned* bad_part = scratch ? reinterpret_cast<unsigned*>(scratch + 1024) : nullptr;
+  unsigned* cen_part = census ? reinterpret_cast<unsigned*>(scratch + 2048) : nullptr;
   const float invN = (lbl == LBL_NONE) ? 0.f : 1.0f / (float)P;
   switch (C) {
-#define DG_SM(N) case N: softmax_ce_launch<N>(lbl, nb, st, logits, onehot, codes, probs, dz, part, bad_part, P, invN); break;
+#define DG_SM(N) case N: softmax_ce_launch<N>(lbl, census != nullptr, nb, st, logits, onehot, codes, probs, dz, part, bad_part, cen_part, P, invN); break;
     DG_SM(2) DG_SM(3) DG_SM(4) DG_SM(5) DG_SM(6) DG_SM(7) DG_SM(8)
 #undef DG_SM
   }
   HIPCHECK(hipGetLastError());
   if (lbl == LBL_NONE) return DG_OK;
-  hipLaunchKernelGGL(sum_small_kernel, dim3(1), dim3(256), 0, st, part, nb, loss_sum,
-                     lbl == LBL_CODES ? bad_part : nullptr, bad_count);
+  if (census)
+    hipLaunchKernelGGL(sum_small_kernel<true>, dim3(1), dim3(256), 0, st, part, nb, loss_sum,
+                       lbl == LBL_CODES ? bad_part : nullptr, bad_count, cen_part, census, C * C);
+  else
+    hipLaunchKernelGGL(sum_small_kernel<false>, dim3(1), dim3(256), 0, st, part, nb, loss_sum,
+                       lbl == LBL_CODES ? bad_part : nullptr, bad_count, nullptr, nullptr, 0);
   HIPCHECK(hipGetLastError());
   return DG_OK;
+}
+
+int dg_softmax_ce(const float* logits, const float* onehot, const unsigned char* codes, float* probs, float* dz,
+                  float* loss_sum, unsigned* bad_count, long P, int C, float* scratch, hipStream_t st) {
+  DGCHECK(dg_softmax_ce_check(logits, onehot, codes, probs, dz, loss_sum, P, C));
+  return softmax_ce_run(logits, onehot, codes, probs, dz, loss_sum, bad_count, nullptr, P, C, scratch, st);
+}
+
+size_t dg_softmax_ce_census_scratch(long P, int C) { return 2048 + (size_t)t_nblk((size_t)P, 1024) * C * C; }
+
+int dg_softmax_ce_census(const float* logits, const float* onehot, const unsigned char* codes, float* probs, float* dz,
+                         float* loss_sum, unsigned* bad_count, unsigned long long* census, long P, int C, float* scratch,
+                         size_t scratch_floats, hipStream_t st) {
+  DGCHECK(dg_softmax_ce_check(logits, onehot, codes, probs, dz, loss_sum, P, C));
+  if (!onehot && !codes) { dg_set_error("dg_softmax_ce_census: a census needs labels"); return DG_ERR_ARG; }
+  if (!census || ((uintptr_t)census & 7)) { dg_set_error("dg_softmax_ce_census: null or misaligned census"); return DG_ERR_ARG; }
+  if (!bad_count) { dg_set_error("dg_softmax_ce_census: no counter of out-of-range codes"); return DG_ERR_ARG; }
+  const size_t need = dg_softmax_ce_census_scratch(P, C);
+  if (!scratch || scratch_floats < need) {
+    dg_set_error("dg_softmax_ce_census: scratch of %zu floats, the launch needs %zu", scratch ? scratch_floats : (size_t)0, need);
+    return DG_ERR_ARG;
+  }
+  return softmax_ce_run(logits, onehot, codes, probs, dz, loss_sum, bad_count, census, P, C, scratch, st);
 }
 
 // ---------------------------------------------------------------------------

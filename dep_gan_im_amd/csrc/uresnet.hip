@@ -15,6 +15,7 @@
 //            backward: sums (dy, dy*RAW) -> dgamma, dbeta and the three coefficients of
 //                           dRAW = A*dy + B*RAW + C ; then the same wgrad / bwd-data kernels as the GAN path
 //                           on dRAW with unscaled weights.
+#include <stddef.h>
 #include <string.h>
 
 #include <string>
@@ -67,7 +68,8 @@ int uresnet_build(depgan_ctx* c) {
   const size_t P = (size_t)B * c->cfg.height * c->cfg.width;
   DGCHECK(dmalloc(c, &c->logits, P * c->cfg.nc_out));
   DGCHECK(dmalloc(c, &c->dz, P * c->cfg.nc_out));
-  DGCHECK(dmalloc(c, &c->loss_dev, 4));
+  // [0] summed loss, [1] out-of-range codes (unsigned), then the census: nc_out^2 64-bit counts from float 2 on
+  DGCHECK(dmalloc(c, &c->loss_dev, 4 + 2 * DEPGAN_MAX_HEAD_CLASSES * DEPGAN_MAX_HEAD_CLASSES));
   DGCHECK(dmalloc(c, &c->ones1k, 1024));
   DGCHECK(dmalloc(c, &c->zeros1k, 1024));
   {
@@ -330,23 +332,41 @@ struct ULabels {
   const unsigned char* codes;
 };
 
-// loss_dev[0] = summed loss, loss_dev[1] = the count of class codes outside [0, nc_out) as an unsigned
+// loss_dev[0] = summed loss, loss_dev[1] = the count of class codes outside [0, nc_out) as an unsigned; with the census
+// on (depgan_uresnet_set_census) the nc_out x nc_out table of the same pass follows as 64-bit counts
 static int u_softmax_ce(depgan_ctx* c, ULabels lab, long P) {
   ProfScope ps(c, 2, 0.0, "softmax + cross-entropy");
-  return dg_softmax_ce(c->logits, lab.onehot, lab.codes, c->attr.p, c->dz, c->loss_dev,
-                       reinterpret_cast<unsigned*>(c->loss_dev + 1), P, c->cfg.nc_out, c->scratch, c->st);
+  unsigned* bad = reinterpret_cast<unsigned*>(c->loss_dev + 1);
+  if (c->census)
+    return dg_softmax_ce_census(c->logits, lab.onehot, lab.codes, c->attr.p, c->dz, c->loss_dev, bad,
+                                reinterpret_cast<unsigned long long*>(c->loss_dev + 2), P, c->cfg.nc_out, c->scratch,
+                                c->scratchFloats, c->st);
+  return dg_softmax_ce(c->logits, lab.onehot, lab.codes, c->attr.p, c->dz, c->loss_dev, bad, P, c->cfg.nc_out, c->scratch,
+                       c->st);
 }
 
-// the one synchronisation of a call: the summed loss and the count of out-of-range class codes come back together
+// the one synchronisation of a call: the summed loss, the count of out-of-range class codes and, with the census on, its
+// table come back in one copy
 static int u_loss_to_host(depgan_ctx* c, const char* who, long P, float* loss_host) {
-  float h[2] = {0.f, 0.f};
-  HIPCHECK(hipMemcpyAsync(h, c->loss_dev, sizeof(h), hipMemcpyDeviceToHost, c->st));
+  struct {
+    float loss;
+    unsigned bad;
+    long long census[DEPGAN_MAX_HEAD_CLASSES * DEPGAN_MAX_HEAD_CLASSES];
+  } h;
+  static_assert(offsetof(decltype(h), census) == 2 * sizeof(float), "the census follows the two scalars of loss_dev");
+  h.loss = 0.f;
+  h.bad = 0;
+  const size_t ncen = c->census ? (size_t)c->cfg.nc_out * c->cfg.nc_out : 0;
+  HIPCHECK(hipMemcpyAsync(&h, c->loss_dev, 2 * sizeof(float) + ncen * sizeof(long long), hipMemcpyDeviceToHost, c->st));
   HIPCHECK(hipStreamSynchronize(c->st));
-  unsigned bad;
-  memcpy(&bad, &h[1], sizeof(bad));
-  c->last_sums[0] = h[0];
+  const unsigned bad = h.bad;
+  if (ncen) {
+    memcpy(c->last_census, h.census, ncen * sizeof(long long));
+    c->census_valid = true;
+  }
+  c->last_sums[0] = h.loss;
   c->last_sums[1] = (float)P;
-  if (loss_host) *loss_host = h[0] / (float)P;
+  if (loss_host) *loss_host = h.loss / (float)P;
   if (bad) {
     dg_set_error("%s: %u of %ld class codes are outside [0, %d)", who, bad, P, c->cfg.nc_out);
     return DG_ERR_ARG;
@@ -398,6 +418,31 @@ static int u_eval(depgan_ctx* c, const char* who, const float* x, const float* z
 }
 
 extern "C" {
+
+int depgan_uresnet_set_census(depgan_ctx* c, int on) {
+  if (!c) { dg_set_error("depgan_uresnet_set_census: null context"); return DG_ERR_ARG; }
+  if (on != 0 && on != 1) { dg_set_error("depgan_uresnet_set_census: on must be 0 or 1, got %d", on); return DG_ERR_ARG; }
+  if (on) {
+    DGCHECK(u_check(c, "depgan_uresnet_set_census"));
+  }
+  c->census = on != 0;
+  if (!on) c->census_valid = false;
+  return DG_OK;
+}
+int depgan_uresnet_get_census(depgan_ctx* c) { return (c && c->census) ? 1 : 0; }
+int depgan_uresnet_last_census(depgan_ctx* c, long long out_host[DEPGAN_MAX_HEAD_CLASSES * DEPGAN_MAX_HEAD_CLASSES],
+                               int* classes) {
+  if (!c || !out_host) { dg_set_error("depgan_uresnet_last_census: null argument"); return DG_ERR_ARG; }
+  if (!c->census || !c->census_valid) {
+    dg_set_error("depgan_uresnet_last_census: no depgan_uresnet_* call has run with the census on "
+                 "(depgan_uresnet_set_census)");
+    return DG_ERR_ARG;
+  }
+  const int C = c->cfg.nc_out;
+  memcpy(out_host, c->last_census, (size_t)C * C * sizeof(long long));
+  if (classes) *classes = C;
+  return DG_OK;
+}
 
 int depgan_uresnet_grads(depgan_ctx* c, const float* x, const float* z, const float* labels, int n,
                          unsigned drop_seed, float* loss_host) {

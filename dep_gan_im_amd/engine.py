@@ -567,6 +567,26 @@ class Engine:
                      C.byref(loss)), "depgan_uresnet_" + mode + sfx)
         return float(loss.value)
 
+    def set_census(self, on=True):
+        """depgan_uresnet_set_census: with it on every uresnet() call also counts the (true class, predicted class) pixel
+        pairs in the loss kernel; the loss and the gradients keep their bits.  ValueError on an inference context."""
+        if on:
+            self._need_trainable("set_census")
+        check(self.lib.depgan_uresnet_set_census(self.h, 1 if on else 0), "depgan_uresnet_set_census")
+
+    @property
+    def census(self):
+        return bool(self.lib.depgan_uresnet_get_census(self.h))
+
+    def uresnet_census(self):
+        """The (nc_out, nc_out) np.int64 confusion matrix of the last uresnet() call, row = true class, column = the
+        arg-max of the probabilities (first index on a tie).  'step' and 'grads' count the phase-1 predictions the loss
+        was taken from (batch statistics, dropout, before the update: what Keras' training metrics see), 'eval' the
+        phase-0 ones.  It came back with that call's loss; this reads host memory (depgan_uresnet_last_census)."""
+        out, k = (C.c_longlong * (_lib.MAX_HEAD_CLASSES ** 2))(), C.c_int()
+        check(self.lib.depgan_uresnet_last_census(self.h, out, C.byref(k)), "depgan_uresnet_last_census")
+        return np.array(out[:k.value * k.value], np.int64).reshape(k.value, k.value)
+
     def apply_adam(self, net):
         self._need_trainable("apply_adam")
         self._use_current_stream()

@@ -132,6 +132,37 @@ def _dice(both, real, fake, smooth=1e-7):
     return (both * 2.0 + smooth) / (smooth + real + fake)                             # GE:746-748
 
 
+def confusion_metrics(cm, smooth=1e-7):
+    """Accuracy, Dice and IoU from a confusion matrix: cm (C, C) integers, cm[t, p] = pixels of true class t predicted as
+    class p -- Engine.uresnet_census() of one call, or the sum of such tables over the batches of an epoch.  Pure NumPy.
+
+    Per class k: both = cm[k, k], real = row sum k, fake = column sum k; dice[k] = _dice(both, real, fake), the
+    reference's (2 both + smooth) / (smooth + real + fake), so a 4-class table gives UE:636-652 for codes 1 to 3;
+    iou[k] = (both + smooth) / (real + fake - both + smooth); precision = both / fake and recall = both / real (NaN
+    for a class never predicted / without support); support = real.  accuracy = trace / sum.  mean_dice and mean_iou
+    run over the foreground classes 1..C-1 (four classes: the reference's avg_all_dice, UE:697).
+
+    A table summed over batches gives Keras' sample-weighted accuracy exactly (every sample has H*W pixels) and the
+    GLOBAL Dice of the pixels it covers, which is not the mean of the batches' Dice figures.  An empty table is a
+    ValueError."""
+    cm = np.asarray(cm)
+    if cm.ndim != 2 or cm.shape[0] != cm.shape[1] or cm.shape[0] < 2 or cm.dtype.kind not in "iu":
+        raise ValueError("confusion_metrics: cm must be a (C, C) integer table with C >= 2, got %s %s"
+                         % (cm.dtype, cm.shape))
+    cm = cm.astype(np.int64)
+    total = int(cm.sum())
+    if total <= 0 or int(cm.min()) < 0:
+        raise ValueError("confusion_metrics: the table is empty (no pixel was counted) or holds a negative count")
+    both, real, fake = np.diag(cm), cm.sum(axis=1), cm.sum(axis=0)
+    dice = np.array([_dice(int(b), int(r), int(f), smooth) for b, r, f in zip(both, real, fake)], np.float64)
+    iou = (both + smooth) / (real + fake - both + smooth)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        precision, recall = both / fake.astype(np.float64), both / real.astype(np.float64)
+    return {"accuracy": float(both.sum()) / total, "dice": dice, "iou": iou, "precision": precision, "recall": recall,
+            "support": real, "mean_dice": sum(dice[1:].tolist()) / (len(dice) - 1.0),     # left to right, as UE:697
+            "mean_iou": sum(iou[1:].tolist()) / (len(iou) - 1.0)}
+
+
 def metrics_from_census(c, voxel_volume):
     """The reference's scalar algebra on the census (GE:640-808)."""
     vol_1tp__ml = c[0] * voxel_volume / 1000                                          # GE:640-641

@@ -255,13 +255,19 @@ def _gen_static_table(nicg, fm, nc_out):
 
 
 _LOSSES = ("categorical_crossentropy", "sparse_categorical_crossentropy")
+# compile(metrics=[...]): the name as given is the history key; what it reads out of evaluate.confusion_metrics
+_METRICS = {"acc": "accuracy", "accuracy": "accuracy", "dice": "mean_dice", "iou": "mean_iou"}
 
 
 class History:
-    """keras.callbacks.History: .history['loss'] / ['val_loss'] per epoch (UT:609-618)."""
+    """keras.callbacks.History: .history['loss'] / ['val_loss'] per epoch (UT:609-618).  With compile(metrics=[...])
+    also .history[name] / ['val_' + name], and .census = {'train': [...], 'val': [...]}: per epoch the confusion matrix
+    (np.int64 (C, C), row = true class) summed over the epoch's training batches / over the validation data."""
 
-    def __init__(self, history):
+    def __init__(self, history, census=None):
         self.history = history
+        if census is not None:
+            self.census = census
 
 
 class GeneratorModel(_Model):
@@ -291,6 +297,7 @@ class GeneratorModel(_Model):
         # Gen_UNet2D compiles the softmax variant itself: Adam(lr=1e-4), categorical cross-entropy (UT:427)
         self._lr = 1e-4
         self._loss = "categorical_crossentropy"
+        self._metrics = []
         self._drop_rng = np.random.RandomState(seed)
 
     def _static_table(self):
@@ -311,6 +318,11 @@ class GeneratorModel(_Model):
             eng.forward_storage = "bfloat16"
             return eng
         return Engine(batch, H, W, nicg, lrG=self._lr, beta1=0.9, beta2=0.999, nc_out=self.nc_out)
+
+    def _bind(self, engine, net):
+        super()._bind(engine, net)
+        if self._metrics:
+            engine.set_census(True)
 
     def inference_copy(self, dtype="bfloat16"):
         """A new predict-only model with this architecture and a copy of the current weights, whose private engine runs
@@ -353,8 +365,16 @@ class GeneratorModel(_Model):
             raise RuntimeError("%s: the tanh generator is trained through the WGAN-GP closures "
                                "(trainers.build_trainers), not compiled with a loss" % what)
 
-    def compile(self, optimizer="adam", loss="categorical_crossentropy", lr=None, **_):
+    def compile(self, optimizer="adam", loss="categorical_crossentropy", lr=None, metrics=None, **_):
         """model.compile(optimizer=Adam(lr=1e-4), loss='categorical_crossentropy')  (UT:427).
+        metrics: names out of 'acc' / 'accuracy' (pixel accuracy: Keras' categorical_accuracy, arg-max against arg-max),
+        'dice' and 'iou' (the means over the foreground classes 1..nc_out-1, evaluate.confusion_metrics).  They come from
+        the confusion matrix the loss kernel counts on the device (Engine.set_census), so they cost no second pass and
+        change no loss or gradient bit.  train_on_batch / test_on_batch / evaluate then return [loss, m1, ...] in the
+        order given and fit records history[name] and history['val_' + name]; a training value is that of the phase-1
+        predictions made before the update, as in Keras.  Per epoch the figures come from the table summed over the
+        epoch's batches: Keras' sample-weighted accuracy exactly (every sample has H*W pixels), and the global Dice /
+        IoU of the epoch rather than a mean of batch figures.  Without metrics nothing changes.
         loss='sparse_categorical_crossentropy' is the same loss on integer labels: train_on_batch, test_on_batch,
         evaluate, fit and its validation_data then take class indices (n, H, W) or (n, H, W, 1) -- any integer dtype, or
         float with integral values (data.to_codes makes them, 1 byte per pixel) -- instead of the one-hot
@@ -363,6 +383,16 @@ class GeneratorModel(_Model):
         if loss not in _LOSSES:
             raise ValueError("loss must be 'categorical_crossentropy' (UT:427) or 'sparse_categorical_crossentropy', "
                              "got %r" % (loss,))
+        if metrics is not None:
+            if isinstance(metrics, str):
+                metrics = [metrics]
+            bad = [m for m in metrics if not isinstance(m, str) or m not in _METRICS]
+            if bad or len(set(metrics)) != len(metrics):
+                raise ValueError("metrics must be distinct names out of %s, got %r" % (sorted(_METRICS), list(metrics)))
+            metrics = list(metrics)
+            if self._engine is not None:
+                self._engine.set_census(bool(metrics))
+            self._metrics = metrics
         self._loss = loss
         if lr is None:
             lr = getattr(optimizer, "lr", None)
@@ -390,38 +420,60 @@ class GeneratorModel(_Model):
     def _next_drop_seed(self):
         return int(self._drop_rng.randint(1, 2 ** 31 - 1))
 
+    def _metric_values(self, cm):
+        """The compiled metrics of one confusion matrix, in the order given to compile."""
+        from .evaluate import confusion_metrics
+        m = confusion_metrics(cm)
+        return [m[_METRICS[name]] for name in self._metrics]
+
+    def _with_metrics(self, eng, loss):
+        return [loss] + self._metric_values(eng.uresnet_census()) if self._metrics else loss
+
     def train_on_batch(self, inputs, labels, drop_seed=None):
-        """One learning-phase-1 Adam step; returns the batch loss."""
+        """One learning-phase-1 Adam step; returns the batch loss, or [loss, m1, ...] with compile(metrics=[...])."""
         self._need_softmax("train_on_batch")
         x, z = inputs
         self._check_labels(labels, len(x), "train_on_batch")
         eng = self._ensure_engine(len(x))
-        return eng.uresnet(x, z, labels, "step", self._next_drop_seed() if drop_seed is None else drop_seed)
+        return self._with_metrics(eng, eng.uresnet(x, z, labels, "step",
+                                                   self._next_drop_seed() if drop_seed is None else drop_seed))
 
     def test_on_batch(self, inputs, labels):
         self._need_softmax("test_on_batch")
         x, z = inputs
         self._check_labels(labels, len(x), "test_on_batch")
-        return self._ensure_engine(len(x)).uresnet(x, z, labels, "eval")
+        eng = self._ensure_engine(len(x))
+        return self._with_metrics(eng, eng.uresnet(x, z, labels, "eval"))
 
-    def evaluate(self, inputs, labels, batch_size=32, verbose=0):
-        """Sample-weighted mean of the phase-0 loss over batches (keras Model.evaluate)."""
-        self._need_softmax("evaluate")
-        x, z = inputs
-        self._check_labels(labels, len(x), "evaluate")
+    def _evaluate(self, x, z, labels, batch_size):
+        """(sample-weighted mean phase-0 loss, the confusion matrix summed over the batches or None without metrics)"""
         eng = self._ensure_engine(min(batch_size, len(x)))
         bs = min(batch_size, eng.batch)
-        tot = 0.0
+        tot, cm = 0.0, None
         for i in range(0, len(x), bs):
             m = min(bs, len(x) - i)
             tot += m * eng.uresnet(x[i:i + m], z[i:i + m], labels[i:i + m], "eval")
-        return tot / len(x)
+            if self._metrics:
+                cm = eng.uresnet_census() if cm is None else cm + eng.uresnet_census()
+        return tot / len(x), cm
+
+    def evaluate(self, inputs, labels, batch_size=32, verbose=0):
+        """Sample-weighted mean of the phase-0 loss over batches (keras Model.evaluate); with compile(metrics=[...])
+        [loss, m1, ...], the metrics from the confusion matrix summed over the batches."""
+        self._need_softmax("evaluate")
+        x, z = inputs
+        self._check_labels(labels, len(x), "evaluate")
+        loss, cm = self._evaluate(x, z, labels, batch_size)
+        return [loss] + self._metric_values(cm) if self._metrics else loss
 
     def fit(self, inputs, labels, epochs=1, batch_size=32, shuffle=True, validation_data=None, verbose=1,
             print_fn=print):
         """my_network.fit([flair, noise], onehot, epochs=1, batch_size=nb_samples, shuffle=..., validation_data=...)
         (UT:602-606).  Batches in index order (after an optional np.random shuffle, as keras does), a short last
-        batch, per-epoch loss = sample-weighted mean of the batch losses; returns an object with .history."""
+        batch, per-epoch loss = sample-weighted mean of the batch losses; returns an object with .history.  With
+        compile(metrics=[...]) each epoch also records every metric of the confusion matrix summed over its training
+        batches and, with validation data, over that data (History.census keeps the tables; the progress line shows
+        them)."""
         self._need_softmax("fit")
         x, z = inputs
         n = len(x)
@@ -433,25 +485,43 @@ class GeneratorModel(_Model):
         eng = self._ensure_engine(min(batch_size, n))
         bs = min(batch_size, eng.batch)
         hist = {"loss": []}
+        hist.update((name, []) for name in self._metrics)
         if validation_data is not None:
             hist["val_loss"] = []
+            hist.update(("val_" + name, []) for name in self._metrics)
+        census = {"train": [], "val": []} if self._metrics else None
         for ep in range(epochs):
             order = np.arange(n)
             if shuffle:
                 np.random.shuffle(order)
-            tot = 0.0
+            tot, cm = 0.0, None
             for i in range(0, n, bs):
                 idx = order[i:i + bs]
                 tot += len(idx) * eng.uresnet(x[idx], z[idx], labels[idx], "step", self._next_drop_seed())
+                if self._metrics:
+                    cm = eng.uresnet_census() if cm is None else cm + eng.uresnet_census()
             hist["loss"].append(tot / n)
             msg = "Epoch %d/%d - loss: %.4f" % (ep + 1, epochs, hist["loss"][-1])
+            if self._metrics:
+                census["train"].append(cm)
+                for name, v in zip(self._metrics, self._metric_values(cm)):
+                    hist[name].append(v)
+                    msg += " - %s: %.4f" % (name, v)
             if validation_data is not None:
                 (vx, vz), vy = validation_data
-                hist["val_loss"].append(self.evaluate([vx, vz], vy, batch_size=bs))
+                vloss, vcm = self._evaluate(vx, vz, vy, bs)
+                hist["val_loss"].append(vloss)
                 msg += " - val_loss: %.4f" % hist["val_loss"][-1]
+                if self._metrics:
+                    census["val"].append(vcm)
+                    for name, v in zip(self._metrics, self._metric_values(vcm)):
+                        hist["val_" + name].append(v)
+                        msg += " - val_%s: %.4f" % (name, v)
+            if self._metrics and verbose:
+                msg += " - census train %s" % cm.tolist() + (" val %s" % vcm.tolist() if validation_data is not None else "")
             if verbose:
                 print_fn(msg)
-        return History(hist)
+        return History(hist, census)
 
     def get_config(self):
         return {"name": self.name, "input_shape": self.input_shape, "noiseZ_shape": self.noiseZ_shape,

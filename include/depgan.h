@@ -194,6 +194,27 @@ int depgan_uresnet_step_sparse(depgan_ctx* ctx, const float* x_dev, const float*
 int depgan_uresnet_eval_sparse(depgan_ctx* ctx, const float* x_dev, const float* z_dev, const unsigned char* codes_dev,
                                int n, float* loss_host);
 
+/* The class census of the supervised path: accuracy, Dice and IoU of a batch from the pass that computes its loss.
+ * depgan_uresnet_set_census(ctx, 1): from now on every depgan_uresnet_{grads,step,eval}{,_sparse} call also counts, in
+ *   the softmax + cross-entropy kernel itself, the pixels of every (true class, predicted class) pair -- the definitions
+ *   of depgan_op_softmax_ce_census: predicted = first arg-max of the probabilities (a tie goes to the lower index),
+ *   true = the code, or the first arg-max of the one-hot row.  Default 0.  The loss, the gradients and every other result
+ *   are bit for bit what they are with the census off.  on = 1 is refused before any launch on a context without the
+ *   trainable softmax head: status 3 on an inference context, status 1 for nc_out = 1; a value other than 0 or 1 is
+ *   status 1.  depgan_uresnet_get_census returns the setting.
+ * depgan_uresnet_last_census: host only.  out_host[tc * C + pc] (C = nc_out, reported in *classes when not NULL; the
+ *   first C*C entries are valid) = the table of the last depgan_uresnet_* call made with the census on.  It came back in
+ *   the same copy and synchronisation as that call's loss.  Status 1 before any such call and after set_census(0).
+ *   What a call counts: grads / step count the phase-1 predictions the loss is taken from -- batch-statistics BatchNorm
+ *   and Dropout included, made BEFORE the Adam update -- which is what Keras' training metrics see; eval counts the
+ *   phase-0 predictions, the arg-max of depgan_g_forward on the same inputs.  A pixel whose code is outside [0, C) is in
+ *   no bin: the table sums to n*H*W minus the count the refused call reports, and a sparse step refused for such codes
+ *   still leaves its table here. */
+int depgan_uresnet_set_census(depgan_ctx* ctx, int on);
+int depgan_uresnet_get_census(depgan_ctx* ctx);
+int depgan_uresnet_last_census(depgan_ctx* ctx, long long out_host[DEPGAN_MAX_HEAD_CLASSES * DEPGAN_MAX_HEAD_CLASSES],
+                               int* classes);
+
 /* Un-normalised pieces of the last critic / generator evaluation, for exact
  * data-parallel reporting: critic: [sum D(real), sum D(fake), sum (norm-1)^2, n];
  * generator: [sum D_y2(fake), sum D_dem(attr), sum |attr-real_dem|, sum wr, sum wf, sum wr*wf, n, n*H*W]. */
@@ -294,6 +315,8 @@ int depgan_eval_label_counts(const double* pred_dev, int C, const float* code_re
  *     "g/out/<layer>"   output of a generator trunk layer of the last generator pass: conv / FiLM block / deconv
  *                       (post-ReLU), "skip1..3" (the pooled tensor), "gen_segmentation" (tanh output)
  *     "g/u/<layer>"     BatchNorm output of a FiLM block's convolution (GT:402; kept by training passes only)
+ *     "g/probs"         the (N, H, W, nc_out) probabilities the softmax of the last depgan_uresnet_* call wrote (a training
+ *                       call: the phase-1 probabilities its loss and census were taken from); status 1 for nc_out = 1
  *     "g/heads"         the 14 noise-MLP head outputs, (N, 1, 1, 1024) in creation order (GT:363-395)
  *     "g/noise_a0", "g/noise_a1"   post-ReLU trunk activations of the noise MLP (GT:358-359), (N, 1, 1, 1024)
  *     "d/act/<layer>"   post-ReLU activations of critic layer dis_0a .. dis_8 of the last critic passes, 3*batch
@@ -615,6 +638,17 @@ int depgan_op_softmax_ce4(const float* logits, const float* onehot, float* probs
  * 16-byte aligned where C % 4 == 0, else 4-byte. */
 int depgan_op_softmax_ce(const float* logits, const float* onehot, const unsigned char* codes, float* probs, float* dz,
                          float* loss_sum, long P, int C, void* hip_stream);
+/* depgan_op_softmax_ce with labels, plus the class census of the same pass: census_host (host, C*C entries, row-major)
+ * receives census[tc * C + pc] = the pixels of true class tc predicted as pc.  pc = the first index of the maximum of
+ * the probability row as stored in probs (scan k = 0..C-1, replace on a strict >: np.argmax of probs; a tie goes to
+ * the lower index).  tc = the code, or with `onehot` the first index of the maximum of the label row (Keras'
+ * categorical_accuracy: argmax(y_true); an all-zero row is class 0).  A pixel whose code is >= C is in no bin, so
+ * sum(census) + (the count in the message) == P; the entry then returns status 1 as depgan_op_softmax_ce does, with
+ * the table written.  probs, dz and loss_sum are bit for bit those of depgan_op_softmax_ce.  The counts are integers
+ * summed in two stages without atomics: exact, and independent of what the buffers held before.  Labels are required:
+ * a null census_host, or neither onehot nor codes, is status 1 before any HIP call.  Synchronises the stream. */
+int depgan_op_softmax_ce_census(const float* logits, const float* onehot, const unsigned char* codes, float* probs,
+                                float* dz, float* loss_sum, long long* census_host, long P, int C, void* hip_stream);
 /* BatchNorm over the R rows of an [R][ld] matrix (first C columns), moving statistics updated when given:
  * moving = momentum*moving + (1 - momentum)*(mean, var*corr) */
 int depgan_op_bn_rows_fwd(const float* x, float* y, int R, int C, int ld, const float* gamma, const float* beta,
