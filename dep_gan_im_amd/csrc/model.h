@@ -208,6 +208,13 @@ struct depgan_ctx {
   // table of the last such call, row = true class, row-major nc_out x nc_out
   bool census = false, census_valid = false;
   long long last_census[DEPGAN_MAX_HEAD_CLASSES * DEPGAN_MAX_HEAD_CLASSES];
+  // depgan_uresnet_set_loss_weights: the loss-weight mode (off by default).  lw_w: nc_out class weights, lw_ignore: the
+  // ignore code (-1: none, read with class codes only); lw_counts: the label pre-pass counts of the last call made with
+  // the mode on ([0] den, [1] ignored, [2] out of range, [3 + k] class k), which came back with that call's loss
+  bool lw_on = false, lw_valid = false;
+  float lw_w[DEPGAN_MAX_HEAD_CLASSES];
+  int lw_ignore = -1;
+  long long lw_counts[DEPGAN_LABEL_NCOUNT];
   float *ones1k = nullptr, *zeros1k = nullptr;
   float *n_mean0 = nullptr, *n_rstd0 = nullptr, *n_mean1 = nullptr, *n_rstd1 = nullptr, *n_meanh = nullptr,
         *n_rstdh = nullptr;

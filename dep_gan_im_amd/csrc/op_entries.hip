@@ -519,6 +519,60 @@ int depgan_op_softmax_ce_census(const float* logits, const float* onehot, const 
   }
   return DG_OK;
 }
+int depgan_op_softmax_ce_weighted(const float* logits, const float* onehot, const unsigned char* codes,
+                                  const float* w_host, int n, int ignore_code, float* probs, float* dz, float* loss_sum,
+                                  long long* census_host, long long* counts_host, long P, int C, void* stream) {
+  if (!w_host || !counts_host) { dg_set_error("op_softmax_ce_weighted: null w_host or counts_host"); return DG_ERR_ARG; }
+  if (!onehot && !codes) { dg_set_error("op_softmax_ce_weighted: loss weights need labels (onehot or codes)"); return DG_ERR_ARG; }
+  DGCHECK(dg_loss_weights_check("op_softmax_ce_weighted", w_host, n, C, ignore_code));
+  DGCHECK(dg_softmax_ce_check(logits, onehot, codes, probs, dz, loss_sum, P, C));
+  hipStream_t st = (hipStream_t)stream;
+  // the reduction scratch, then what comes back: the counter of out-of-range codes (padded to 8 bytes), the C*C census
+  // and the C + 3 label counts
+  const size_t cap = (dg_softmax_ce_weighted_scratch(P, C, census_host != nullptr) + 1) & ~(size_t)1;
+  struct {
+    unsigned bad, pad;
+    long long census[DEPGAN_MAX_HEAD_CLASSES * DEPGAN_MAX_HEAD_CLASSES];
+    long long counts[DEPGAN_LABEL_NCOUNT];
+  } h;
+  DevTmp scratch(st);
+  DGCHECK(op_alloc(&scratch, cap + sizeof(h) / sizeof(float), "op_softmax_ce_weighted"));
+  unsigned* bad = reinterpret_cast<unsigned*>(scratch.as<float>() + cap);
+  unsigned long long* cen = reinterpret_cast<unsigned long long*>(scratch.as<float>() + cap + 2);
+  unsigned long long* cnt = cen + DEPGAN_MAX_HEAD_CLASSES * DEPGAN_MAX_HEAD_CLASSES;
+  DGCHECK(dg_softmax_ce_weighted(logits, onehot, codes, probs, dz, loss_sum, bad, census_host ? cen : nullptr, cnt, w_host,
+                                 ignore_code, P, C, scratch.as<float>(), cap, st));
+  // the census region is written only with census_host: the part of h it covers is then not read
+  if (hipMemcpyAsync(&h, bad, sizeof(h), hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) {
+    dg_set_error("op_softmax_ce_weighted: copy back failed");
+    return DG_ERR_HIP;
+  }
+  if (census_host) memcpy(census_host, h.census, (size_t)C * C * sizeof(long long));
+  memcpy(counts_host, h.counts, (size_t)(C + 3) * sizeof(long long));
+  if (h.bad) {
+    dg_set_error("op_softmax_ce_weighted: %u of %ld class codes are outside [0, %d)", h.bad, P, C);
+    return DG_ERR_ARG;
+  }
+  return DG_OK;
+}
+int depgan_op_label_counts(const float* onehot, const unsigned char* codes, long P, int C, int ignore_code,
+                           long long* out_host, void* stream) {
+  if (!out_host) { dg_set_error("op_label_counts: null out_host"); return DG_ERR_ARG; }
+  DGCHECK(dg_loss_weights_check("op_label_counts", nullptr, C, C, ignore_code));
+  if (P < 1 || (!onehot == !codes)) { dg_set_error("op_label_counts: P < 1, or not exactly one of onehot and codes"); return DG_ERR_ARG; }
+  hipStream_t st = (hipStream_t)stream;
+  const size_t cap = (dg_label_counts_scratch(P, C) + 1) & ~(size_t)1;
+  DevTmp scratch(st);
+  DGCHECK(op_alloc(&scratch, cap + 2 * DEPGAN_LABEL_NCOUNT, "op_label_counts"));
+  unsigned long long* cnt = reinterpret_cast<unsigned long long*>(scratch.as<float>() + cap);
+  DGCHECK(dg_label_counts(onehot, codes, P, C, nullptr, ignore_code, cnt, scratch.as<float>(), cap, st));
+  if (hipMemcpyAsync(out_host, cnt, (size_t)(C + 3) * sizeof(long long), hipMemcpyDeviceToHost, st) != hipSuccess ||
+      hipStreamSynchronize(st) != hipSuccess) {
+    dg_set_error("op_label_counts: copy back failed");
+    return DG_ERR_HIP;
+  }
+  return DG_OK;
+}
 int depgan_op_softmax_ce4(const float* logits, const float* onehot, float* probs, float* dz, float* loss_sum, long P,
                           void* stream) {
   return depgan_op_softmax_ce(logits, onehot, nullptr, probs, dz, loss_sum, P, 4, stream);

@@ -75,6 +75,15 @@ __device__ __forceinline__ int dg_row_argmax(const float (&r)[C]) {
   return a;
 }
 
+// whether any entry of the row is not zero (a NaN is not zero)
+template <int C>
+__device__ __forceinline__ bool dg_row_any(const float (&r)[C]) {
+  bool any = false;
+#pragma unroll
+  for (int k = 0; k < C; ++k) any = any || (r[k] != 0.f);
+  return any;
+}
+
 // p = softmax(z): maximum in dg_row_max's order, e_k = expf(z_k - m), S0 = ((0 + e_0) + e_1) + ... left to right,
 // p_k = e_k / S0
 template <int C>

@@ -60,6 +60,27 @@ size_t dg_softmax_ce_census_scratch(long P, int C);
 int dg_softmax_ce_census(const float* logits, const float* onehot, const unsigned char* codes, float* probs, float* dz,
                          float* loss_sum, unsigned* bad_count, unsigned long long* census, long P, int C, float* scratch,
                          size_t scratch_floats, hipStream_t st);
+// The loss-weight mode.  cw: C host class weights, finite and >= 0 with at least one > 0 (null: unit weights);
+// ignore_code: -1 for none, else a byte value whose pixels have t = 0 and are not counted as out of range (read with
+// codes only: with one-hot labels the ignored pixel is the all-zero row).
+// dg_loss_weights_check validates both without a HIP call (n must equal C where w is given).
+// dg_label_counts: the label pre-pass alone.  counts (C + 3 64-bit device counts, 8-byte aligned) receives
+// [0] den = the pixels with weight w = sum_k cw[k] t[k] != 0, [1] the pixels without a true class (the ignore code, an
+// all-zero one-hot row), [2] the codes >= C that are not the ignore code, [3 + k] the pixels of true class k (the code,
+// or the first arg-max of the row).  Two stages, no atomics, nothing to zero; dg_label_counts_scratch(P, C) floats.
+// dg_softmax_ce_weighted: that pass, then dg_softmax_ce (census == null) or dg_softmax_ce_census on the label row
+// cw[k] t[k] with 1 / den for 1 / P (0 for den = 0), den read on the device from counts[0]; loss_sum[0] = the weighted
+// sum, the mean is loss_sum / den.  Under it a pixel without a true class joins no census bin.  With unit weights and
+// nothing ignored every output has dg_softmax_ce's bits.  dg_softmax_ce_weighted_scratch(P, C, census) floats.
+int dg_loss_weights_check(const char* who, const float* w, int n, int C, int ignore_code);
+size_t dg_label_counts_scratch(long P, int C);
+int dg_label_counts(const float* onehot, const unsigned char* codes, long P, int C, const float* cw, int ignore_code,
+                    unsigned long long* counts, float* scratch, size_t scratch_floats, hipStream_t st);
+size_t dg_softmax_ce_weighted_scratch(long P, int C, bool census);
+int dg_softmax_ce_weighted(const float* logits, const float* onehot, const unsigned char* codes, float* probs, float* dz,
+                           float* loss_sum, unsigned* bad_count, unsigned long long* census,
+                           unsigned long long* counts, const float* cw, int ignore_code, long P, int C, float* scratch,
+                           size_t scratch_floats, hipStream_t st);
 // its argument checks alone (no HIP call): what an entry asks before it allocates
 int dg_softmax_ce_check(const float* logits, const float* onehot, const unsigned char* codes, const float* probs,
                         const float* dz, const float* loss_sum, long P, int C);

@@ -1,6 +1,9 @@
 // Learning-phase-1 operators (see train_ops.h).  All HBM-bound: 16-byte accesses over the channel
 // axis, block reductions through LDS, deterministic second passes.
 #include "train_ops.h"
+
+#include <float.h>
+
 #include "epilogue.h"
 #include "softmax_row.h"
 
@@ -462,7 +465,24 @@ int dg_axpby_ch(TView d, TView x, TView out, int B, int H, int W, int C, const f
 // atomics and no LDS traffic in the loop: one ballot per true class and one per predicted class (2 C compares), then
 // lane l, the owner of bin l = k * C + j, adds popcount(ballot_t[k] & ballot_p[j]) to its one counter.  The four
 // waves' tables meet in LDS after the loop and C*C lanes store the block's partial.
+//
+// WEIGHTED (labels present; dg_softmax_ce_weighted): the label row becomes cw[k] * t[k] before the statements above run
+// on it, a code equal to wa.ignore gives t = 0 without being counted in nbad, and 1/N becomes 1/den, den = the count of
+// pixels with a non-zero weight that label_count_kernel left in wa.den (invDen = 0 for den = 0: no division by zero, an
+// all-zero dz).  With unit weights, no ignored pixel and den = P every float is the one the WEIGHTED = false
+// instantiation computes (1 * t = t, and 1.0f / (float)den is the host's 1.0f / (float)P).  A pixel with t = 0 --
+// ignored, or of a zero-weight class -- has a dz row of zeros and still gets its probabilities.  CENSUS under WEIGHTED:
+// a pixel without a true class (the ignore code, an all-zero one-hot row) joins no bin.  The WEIGHTED = false
+// instantiations ignore wa, their last argument, and compile to the instructions they were.
 enum { LBL_NONE = 0, LBL_ONEHOT = 1, LBL_CODES = 2 };
+
+// the loss-weight mode's kernel arguments, by value: C class weights (the rest 0), the ignore code (-1: none) and the
+// device count of weighted pixels
+struct SmWeights {
+  float cw[DG_MAX_CLASSES];
+  int ignore;
+  const unsigned long long* den;
+};
 
 __device__ __forceinline__ unsigned t_block_sum_u(unsigned v, unsigned* shu4) {
 #pragma unroll
@@ -473,12 +493,17 @@ __device__ __forceinline__ unsigned t_block_sum_u(unsigned v, unsigned* shu4) {
   return (shu4[0] + shu4[1]) + (shu4[2] + shu4[3]);
 }
 
-template <int C, int LBL, bool CENSUS>
+template <int C, int LBL, bool CENSUS, bool WEIGHTED>
 __global__ void softmax_ce_kernel(const float* __restrict__ logits, const float* __restrict__ onehot,
                                   const unsigned char* __restrict__ codes, float* __restrict__ probs,
                                   float* __restrict__ dz, float* __restrict__ part, unsigned* __restrict__ bad_part,
-                                  unsigned* __restrict__ cen_part, long P, float invN) {
+                                  unsigned* __restrict__ cen_part, long P, float invN, SmWeights wa) {
   static_assert(!CENSUS || LBL != LBL_NONE, "a census needs labels");
+  static_assert(!WEIGHTED || LBL != LBL_NONE, "loss weights need labels");
+  if (WEIGHTED) {
+    const unsigned long long den = *wa.den;
+    invN = den ? 1.0f / (float)den : 0.f;
+  }
   __shared__ float sh4[4];
   __shared__ unsigned shu4[4];
   float lsum = 0.f;
@@ -500,12 +525,18 @@ __global__ void softmax_ce_kernel(const float* __restrict__ logits, const float*
         if (LBL == LBL_ONEHOT) {
           dg_row_load<C>(onehot + i * C, t);
           if (CENSUS) tc = dg_row_argmax<C>(t);
+          if (CENSUS && WEIGHTED) tc = dg_row_any<C>(t) ? tc : -1;
         } else {
-          const int code = codes[i];
+          // WEIGHTED: the ignore code becomes -1, which equals no k: t = 0, in no bin and not in nbad
+          const int code = (WEIGHTED && codes[i] == wa.ignore) ? -1 : codes[i];
 #pragma unroll
           for (int k = 0; k < C; ++k) t[k] = (k == code) ? 1.0f : 0.0f;
           nbad += (code >= C) ? 1u : 0u;
           if (CENSUS) tc = (code < C) ? code : -1;
+        }
+        if (WEIGHTED) {
+#pragma unroll
+          for (int k = 0; k < C; ++k) t[k] = wa.cw[k] * t[k];
         }
         const float S = dg_row_pairsum<C>(p);
         float gq[C];
@@ -600,22 +631,21 @@ __global__ void sum_small_kernel(const float* __restrict__ part, int nb, float* 
 template <int C>
 static void softmax_ce_launch(int lbl, bool census, int nb, hipStream_t st, const float* logits, const float* onehot,
                               const unsigned char* codes, float* probs, float* dz, float* part, unsigned* bad_part,
-                              unsigned* cen_part, long P, float invN) {
-  if (lbl == LBL_ONEHOT && census)
-    hipLaunchKernelGGL((softmax_ce_kernel<C, LBL_ONEHOT, true>), dim3(nb), dim3(256), 0, st, logits, onehot, codes, probs,
-                       dz, part, bad_part, cen_part, P, invN);
-  else if (lbl == LBL_CODES && census)
-    hipLaunchKernelGGL((softmax_ce_kernel<C, LBL_CODES, true>), dim3(nb), dim3(256), 0, st, logits, onehot, codes, probs,
-                       dz, part, bad_part, cen_part, P, invN);
-  else if (lbl == LBL_ONEHOT)
-    hipLaunchKernelGGL((softmax_ce_kernel<C, LBL_ONEHOT, false>), dim3(nb), dim3(256), 0, st, logits, onehot, codes, probs,
-                       dz, part, bad_part, cen_part, P, invN);
-  else if (lbl == LBL_CODES)
-    hipLaunchKernelGGL((softmax_ce_kernel<C, LBL_CODES, false>), dim3(nb), dim3(256), 0, st, logits, onehot, codes, probs,
-                       dz, part, bad_part, cen_part, P, invN);
-  else
-    hipLaunchKernelGGL((softmax_ce_kernel<C, LBL_NONE, false>), dim3(nb), dim3(256), 0, st, logits, onehot, codes, probs,
-                       dz, part, bad_part, cen_part, P, invN);
+                              unsigned* cen_part, long P, float invN, const SmWeights* weights) {
+  const SmWeights wa = weights ? *weights : SmWeights{};
+#define DG_SM_GO(LBL, CEN, WGT)                                                                                        \
+  hipLaunchKernelGGL((softmax_ce_kernel<C, LBL, CEN, WGT>), dim3(nb), dim3(256), 0, st, logits, onehot, codes, probs, dz, \
+                     part, bad_part, cen_part, P, invN, wa)
+  if (weights && lbl == LBL_ONEHOT && census) DG_SM_GO(LBL_ONEHOT, true, true);
+  else if (weights && lbl == LBL_CODES && census) DG_SM_GO(LBL_CODES, true, true);
+  else if (weights && lbl == LBL_ONEHOT) DG_SM_GO(LBL_ONEHOT, false, true);
+  else if (weights && lbl == LBL_CODES) DG_SM_GO(LBL_CODES, false, true);
+  else if (lbl == LBL_ONEHOT && census) DG_SM_GO(LBL_ONEHOT, true, false);
+  else if (lbl == LBL_CODES && census) DG_SM_GO(LBL_CODES, true, false);
+  else if (lbl == LBL_ONEHOT) DG_SM_GO(LBL_ONEHOT, false, false);
+  else if (lbl == LBL_CODES) DG_SM_GO(LBL_CODES, false, false);
+  else DG_SM_GO(LBL_NONE, false, false);
+#undef DG_SM_GO
 }
 
 int dg_softmax_ce_check(const float* logits, const float* onehot, const unsigned char* codes, const float* probs,
@@ -636,10 +666,11 @@ int dg_softmax_ce_check(const float* logits, const float* onehot, const unsigned
   return DG_OK;
 }
 
-// census: null, or C*C device counts; the block tables then follow the 2048 floats of the other partials
+// census: null, or C*C device counts; the block tables then follow the 2048 floats of the other partials.  weights:
+// null, or the loss-weight mode's arguments (weights->den already holds the count when this launch runs)
 static int softmax_ce_run(const float* logits, const float* onehot, const unsigned char* codes, float* probs, float* dz,
                           float* loss_sum, unsigned* bad_count, unsigned long long* census, long P, int C, float* scratch,
-                          hipStream_t st) {
+                          hipStream_t st, const SmWeights* weights = nullptr) {
   const int lbl = onehot ? LBL_ONEHOT : (codes ? LBL_CODES : LBL_NONE);
   if (lbl != LBL_NONE && !scratch) { dg_set_error("dg_softmax_ce: labels without scratch"); return DG_ERR_ARG; }
   if (lbl == LBL_CODES && !bad_count) { dg_set_error("dg_softmax_ce: class codes without a counter"); return DG_ERR_ARG; }
@@ -649,7 +680,7 @@ static int softmax_ce_run(const float* logits, const float* onehot, const unsign
   unsigned* cen_part = census ? reinterpret_cast<unsigned*>(scratch + 2048) : nullptr;
   const float invN = (lbl == LBL_NONE) ? 0.f : 1.0f / (float)P;
   switch (C) {
-#define DG_SM(N) case N: softmax_ce_launch<N>(lbl, census != nullptr, nb, st, logits, onehot, codes, probs, dz, part, bad_part, cen_part, P, invN); break;
+#define DG_SM(N) case N: softmax_ce_launch<N>(lbl, census != nullptr, nb, st, logits, onehot, codes, probs, dz, part, bad_part, cen_part, P, invN, weights); break;
     DG_SM(2) DG_SM(3) DG_SM(4) DG_SM(5) DG_SM(6) DG_SM(7) DG_SM(8)
 #undef DG_SM
   }
@@ -686,6 +717,177 @@ int dg_softmax_ce_census(const float* logits, const float* onehot, const unsigne
     return DG_ERR_ARG;
   }
   return softmax_ce_run(logits, onehot, codes, probs, dz, loss_sum, bad_count, census, P, C, scratch, st);
+}
+
+// ---------------------------------------------------------------------------
+// the loss-weight mode: label pre-pass and weighted cross-entropy
+// ---------------------------------------------------------------------------
+// The gradient needs 1 / den inside the pass that writes dz, so den exists before that pass starts: this kernel reads
+// the labels alone (1 byte per pixel, or a one-hot row) and counts, per pixel, C + 3 predicates -- slot 0: the pixel's
+// weight w = sum_k cw[k] t[k] (left to right) is not 0 (den); slot 1: no true class (the ignore code, an all-zero
+// one-hot row); slot 2: a code >= C that is not the ignore code; slot 3 + k: true class k (the code, or the first
+// arg-max of the row: the census rule).  The census's conventions: no atomics, one ballot per slot, lane j of a wave
+// adds the popcount of slot j's ballot to its one counter, the four waves meet in LDS, C + 3 lanes store the block's
+// partial, and a one-block second stage sums the at most 1024 partials into 64-bit counts.
+template <int C, int LBL>
+__global__ void label_count_kernel(const float* __restrict__ onehot, const unsigned char* __restrict__ codes,
+                                   SmWeights wa, unsigned* __restrict__ cnt_part, long P) {
+  static_assert(LBL == LBL_ONEHOT || LBL == LBL_CODES, "a label count needs labels");
+  constexpr int NS = C + 3;
+  const int lane = (int)(threadIdx.x & 63);
+  unsigned cnt = 0;
+  for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; __any(i < (size_t)P) != 0;
+       i += (size_t)gridDim.x * blockDim.x) {
+    int tc = -1;
+    bool has_w = false, ign = false, bad = false;
+    if (i < (size_t)P) {
+      float w = 0.f;
+      if (LBL == LBL_ONEHOT) {
+        float t[C];
+        dg_row_load<C>(onehot + i * C, t);
+        ign = !dg_row_any<C>(t);
+        tc = ign ? -1 : dg_row_argmax<C>(t);
+#pragma unroll
+        for (int k = 0; k < C; ++k) w += wa.cw[k] * t[k];
+      } else {
+        const int raw = codes[i];
+        ign = raw == wa.ignore;
+        bad = !ign && raw >= C;
+        tc = (ign || bad) ? -1 : raw;
+#pragma unroll
+        for (int k = 0; k < C; ++k) w = (k == tc) ? wa.cw[k] : w;
+      }
+      has_w = w != 0.f;
+    }
+    unsigned long long m = 0;
+    const unsigned long long b0 = __ballot(has_w), b1 = __ballot(ign), b2 = __ballot(bad);
+    m = (lane == 0) ? b0 : m;
+    m = (lane == 1) ? b1 : m;
+    m = (lane == 2) ? b2 : m;
+#pragma unroll
+    for (int k = 0; k < C; ++k) {
+      const unsigned long long bk = __ballot(tc == k);
+      m = (lane == 3 + k) ? bk : m;
+    }
+    cnt += (unsigned)__popcll(m);
+  }
+  __shared__ unsigned shc[4][16];
+  if (lane < NS) shc[threadIdx.x >> 6][lane] = cnt;
+  __syncthreads();
+  const int b = threadIdx.x;
+  if (b < NS) cnt_part[(size_t)blockIdx.x * NS + b] = (shc[0][b] + shc[1][b]) + (shc[2][b] + shc[3][b]);
+}
+// second stage, one block of 256: out[j] = the sum over the nb blocks of slot j (wave g takes the blocks g, g + 4, ...,
+// lane j the slot; integer sums, any order gives the same counts)
+__global__ void label_count_sum_kernel(const unsigned* __restrict__ cnt_part, int nb, int NS,
+                                       unsigned long long* __restrict__ out) {
+  __shared__ unsigned long long shc[4][16];
+  const int g = threadIdx.x >> 6, b = threadIdx.x & 63;
+  unsigned long long a = 0;
+  if (b < NS)
+    for (int i = g; i < nb; i += 4) a += cnt_part[(size_t)i * NS + b];
+  if (b < NS) shc[g][b] = a;
+  __syncthreads();
+  if (g == 0 && b < NS) out[b] = (shc[0][b] + shc[1][b]) + (shc[2][b] + shc[3][b]);
+}
+
+int dg_loss_weights_check(const char* who, const float* w, int n, int C, int ignore_code) {
+  if (C < DG_MIN_CLASSES || C > DG_MAX_CLASSES) {
+    dg_set_error("%s: %d classes (the kernel covers %d to %d)", who, C, DG_MIN_CLASSES, DG_MAX_CLASSES);
+    return DG_ERR_ARG;
+  }
+  if (ignore_code < -1 || ignore_code > 255) {
+    dg_set_error("%s: ignore code %d (-1 for none, else a byte value 0..255)", who, ignore_code);
+    return DG_ERR_ARG;
+  }
+  if (!w) return DG_OK;
+  if (n != C) { dg_set_error("%s: %d class weights for %d classes", who, n, C); return DG_ERR_ARG; }
+  bool any = false;
+  for (int k = 0; k < C; ++k) {
+    if (!(w[k] >= 0.f) || w[k] > FLT_MAX) {
+      dg_set_error("%s: class weight %d is %g (every weight is finite and >= 0)", who, k, (double)w[k]);
+      return DG_ERR_ARG;
+    }
+    any = any || w[k] > 0.f;
+  }
+  if (!any) { dg_set_error("%s: every class weight is 0 (at least one must be > 0)", who); return DG_ERR_ARG; }
+  return DG_OK;
+}
+
+static SmWeights sm_weights(const float* cw, int C, int ignore_code, const unsigned long long* den) {
+  SmWeights wa;
+  for (int k = 0; k < DG_MAX_CLASSES; ++k) wa.cw[k] = (k < C) ? (cw ? cw[k] : 1.0f) : 0.f;
+  wa.ignore = ignore_code;
+  wa.den = den;
+  return wa;
+}
+
+size_t dg_label_counts_scratch(long P, int C) { return (size_t)t_nblk((size_t)P, 1024) * (C + 3); }
+
+static int label_counts_run(const float* onehot, const unsigned char* codes, long P, int C, const SmWeights& wa,
+                            unsigned long long* counts, float* scratch, hipStream_t st) {
+  const int nb = t_nblk((size_t)P, 1024);
+  unsigned* cnt_part = reinterpret_cast<unsigned*>(scratch);
+  switch (C) {
+#define DG_LC(N)                                                                                                       \
+  case N:                                                                                                              \
+    if (onehot) hipLaunchKernelGGL((label_count_kernel<N, LBL_ONEHOT>), dim3(nb), dim3(256), 0, st, onehot, codes, wa, cnt_part, P); \
+    else hipLaunchKernelGGL((label_count_kernel<N, LBL_CODES>), dim3(nb), dim3(256), 0, st, onehot, codes, wa, cnt_part, P); \
+    break;
+    DG_LC(2) DG_LC(3) DG_LC(4) DG_LC(5) DG_LC(6) DG_LC(7) DG_LC(8)
+#undef DG_LC
+  }
+  HIPCHECK(hipGetLastError());
+  hipLaunchKernelGGL(label_count_sum_kernel, dim3(1), dim3(256), 0, st, cnt_part, nb, C + 3, counts);
+  HIPCHECK(hipGetLastError());
+  return DG_OK;
+}
+
+static int label_counts_check(const char* who, const float* onehot, const unsigned char* codes, long P, int C,
+                              const unsigned long long* counts, const float* scratch, size_t scratch_floats) {
+  if (P < 1 || (!onehot == !codes)) { dg_set_error("%s: P < 1, or not exactly one of onehot and codes", who); return DG_ERR_ARG; }
+  if (onehot && ((uintptr_t)onehot & ((C % 4 == 0) ? 15 : 3))) { dg_set_error("%s: misaligned onehot", who); return DG_ERR_ARG; }
+  if (!counts || ((uintptr_t)counts & 7)) { dg_set_error("%s: null or misaligned counts", who); return DG_ERR_ARG; }
+  const size_t need = dg_label_counts_scratch(P, C);
+  if (!scratch || scratch_floats < need) {
+    dg_set_error("%s: scratch of %zu floats, the label pass needs %zu", who, scratch ? scratch_floats : (size_t)0, need);
+    return DG_ERR_ARG;
+  }
+  return DG_OK;
+}
+
+int dg_label_counts(const float* onehot, const unsigned char* codes, long P, int C, const float* cw, int ignore_code,
+                    unsigned long long* counts, float* scratch, size_t scratch_floats, hipStream_t st) {
+  DGCHECK(dg_loss_weights_check("dg_label_counts", cw, C, C, ignore_code));
+  DGCHECK(label_counts_check("dg_label_counts", onehot, codes, P, C, counts, scratch, scratch_floats));
+  return label_counts_run(onehot, codes, P, C, sm_weights(cw, C, ignore_code, nullptr), counts, scratch, st);
+}
+
+size_t dg_softmax_ce_weighted_scratch(long P, int C, bool census) {
+  const size_t a = census ? dg_softmax_ce_census_scratch(P, C) : 2048, b = dg_label_counts_scratch(P, C);
+  return a > b ? a : b;
+}
+
+int dg_softmax_ce_weighted(const float* logits, const float* onehot, const unsigned char* codes, float* probs, float* dz,
+                           float* loss_sum, unsigned* bad_count, unsigned long long* census,
+                           unsigned long long* counts, const float* cw, int ignore_code, long P, int C, float* scratch,
+                           size_t scratch_floats, hipStream_t st) {
+  DGCHECK(dg_loss_weights_check("dg_softmax_ce_weighted", cw, C, C, ignore_code));
+  DGCHECK(dg_softmax_ce_check(logits, onehot, codes, probs, dz, loss_sum, P, C));
+  if (!onehot && !codes) { dg_set_error("dg_softmax_ce_weighted: loss weights need labels"); return DG_ERR_ARG; }
+  if (census && ((uintptr_t)census & 7)) { dg_set_error("dg_softmax_ce_weighted: misaligned census"); return DG_ERR_ARG; }
+  if (!bad_count) { dg_set_error("dg_softmax_ce_weighted: no counter of out-of-range codes"); return DG_ERR_ARG; }
+  const size_t need = dg_softmax_ce_weighted_scratch(P, C, census != nullptr);
+  if (!scratch || scratch_floats < need) {
+    dg_set_error("dg_softmax_ce_weighted: scratch of %zu floats, the launches need %zu", scratch ? scratch_floats : (size_t)0, need);
+    return DG_ERR_ARG;
+  }
+  DGCHECK(label_counts_check("dg_softmax_ce_weighted", onehot, codes, P, C, counts, scratch, scratch_floats));
+  const SmWeights wa = sm_weights(cw, C, ignore_code, counts);
+  // the label pass's partials and the cross-entropy pass's share the scratch: the second stage of the first has read them
+  // before the second pass, behind it on the stream, writes
+  DGCHECK(label_counts_run(onehot, codes, P, C, wa, counts, scratch, st));
+  return softmax_ce_run(logits, onehot, codes, probs, dz, loss_sum, bad_count, census, P, C, scratch, st, &wa);
 }
 
 // ---------------------------------------------------------------------------

@@ -43,6 +43,15 @@ static UNoiseBn noise_bn(Net& g, const std::string& nm) {
   return b;
 }
 
+// loss_dev as the host reads it
+struct ULossHost {
+  float loss;
+  unsigned bad;
+  long long census[DEPGAN_MAX_HEAD_CLASSES * DEPGAN_MAX_HEAD_CLASSES];
+  long long counts[DEPGAN_LABEL_NCOUNT];
+};
+static_assert(offsetof(ULossHost, census) == 2 * sizeof(float), "the census follows the two scalars of loss_dev");
+
 int uresnet_build(depgan_ctx* c) {
   const int B = c->cfg.batch;
   size_t maxOut = 0, nsmall = 0;
@@ -68,8 +77,9 @@ int uresnet_build(depgan_ctx* c) {
   const size_t P = (size_t)B * c->cfg.height * c->cfg.width;
   DGCHECK(dmalloc(c, &c->logits, P * c->cfg.nc_out));
   DGCHECK(dmalloc(c, &c->dz, P * c->cfg.nc_out));
-  // [0] summed loss, [1] out-of-range codes (unsigned), then the census: nc_out^2 64-bit counts from float 2 on
-  DGCHECK(dmalloc(c, &c->loss_dev, 4 + 2 * DEPGAN_MAX_HEAD_CLASSES * DEPGAN_MAX_HEAD_CLASSES));
+  // [0] summed loss, [1] out-of-range codes (unsigned), then the census: nc_out^2 64-bit counts from float 2 on; behind
+  // the largest census the DEPGAN_LABEL_NCOUNT 64-bit label counts of the loss-weight mode (ULossHost is the layout)
+  DGCHECK(dmalloc(c, &c->loss_dev, sizeof(ULossHost) / sizeof(float)));
   DGCHECK(dmalloc(c, &c->ones1k, 1024));
   DGCHECK(dmalloc(c, &c->zeros1k, 1024));
   {
@@ -333,10 +343,17 @@ struct ULabels {
 };
 
 // loss_dev[0] = summed loss, loss_dev[1] = the count of class codes outside [0, nc_out) as an unsigned; with the census
-// on (depgan_uresnet_set_census) the nc_out x nc_out table of the same pass follows as 64-bit counts
+// on (depgan_uresnet_set_census) the nc_out x nc_out table of the same pass follows as 64-bit counts.  In the
+// loss-weight mode the label pre-pass runs first and leaves its counts, den first, behind the census
 static int u_softmax_ce(depgan_ctx* c, ULabels lab, long P) {
   ProfScope ps(c, 2, 0.0, "softmax + cross-entropy");
   unsigned* bad = reinterpret_cast<unsigned*>(c->loss_dev + 1);
+  if (c->lw_on)
+    return dg_softmax_ce_weighted(c->logits, lab.onehot, lab.codes, c->attr.p, c->dz, c->loss_dev, bad,
+                                  c->census ? reinterpret_cast<unsigned long long*>(c->loss_dev + 2) : nullptr,
+                                  reinterpret_cast<unsigned long long*>(c->loss_dev + offsetof(ULossHost, counts) / sizeof(float)),
+                                  c->lw_w, lab.codes ? c->lw_ignore : -1, P, c->cfg.nc_out, c->scratch, c->scratchFloats,
+                                  c->st);
   if (c->census)
     return dg_softmax_ce_census(c->logits, lab.onehot, lab.codes, c->attr.p, c->dz, c->loss_dev, bad,
                                 reinterpret_cast<unsigned long long*>(c->loss_dev + 2), P, c->cfg.nc_out, c->scratch,
@@ -348,25 +365,30 @@ static int u_softmax_ce(depgan_ctx* c, ULabels lab, long P) {
 // the one synchronisation of a call: the summed loss, the count of out-of-range class codes and, with the census on, its
 // table come back in one copy
 static int u_loss_to_host(depgan_ctx* c, const char* who, long P, float* loss_host) {
-  struct {
-    float loss;
-    unsigned bad;
-    long long census[DEPGAN_MAX_HEAD_CLASSES * DEPGAN_MAX_HEAD_CLASSES];
-  } h;
-  static_assert(offsetof(decltype(h), census) == 2 * sizeof(float), "the census follows the two scalars of loss_dev");
+  ULossHost h;
   h.loss = 0.f;
   h.bad = 0;
   const size_t ncen = c->census ? (size_t)c->cfg.nc_out * c->cfg.nc_out : 0;
-  HIPCHECK(hipMemcpyAsync(&h, c->loss_dev, 2 * sizeof(float) + ncen * sizeof(long long), hipMemcpyDeviceToHost, c->st));
+  // the loss-weight mode: the label counts sit behind the largest census, the copy takes everything up to them
+  const size_t bytes = c->lw_on ? offsetof(ULossHost, counts) + (size_t)(c->cfg.nc_out + 3) * sizeof(long long)
+                                : 2 * sizeof(float) + ncen * sizeof(long long);
+  HIPCHECK(hipMemcpyAsync(&h, c->loss_dev, bytes, hipMemcpyDeviceToHost, c->st));
   HIPCHECK(hipStreamSynchronize(c->st));
   const unsigned bad = h.bad;
   if (ncen) {
     memcpy(c->last_census, h.census, ncen * sizeof(long long));
     c->census_valid = true;
   }
+  // the mean's denominator: every pixel, or in the loss-weight mode the pixels with a non-zero weight (0.0 for none)
+  float den = (float)P;
+  if (c->lw_on) {
+    memcpy(c->lw_counts, h.counts, (size_t)(c->cfg.nc_out + 3) * sizeof(long long));
+    c->lw_valid = true;
+    den = (float)(unsigned long long)h.counts[0];
+  }
   c->last_sums[0] = h.loss;
-  c->last_sums[1] = (float)P;
-  if (loss_host) *loss_host = h.loss / (float)P;
+  c->last_sums[1] = den;
+  if (loss_host) *loss_host = (den != 0.f) ? h.loss / den : 0.f;
   if (bad) {
     dg_set_error("%s: %u of %ld class codes are outside [0, %d)", who, bad, P, c->cfg.nc_out);
     return DG_ERR_ARG;
@@ -403,6 +425,9 @@ static int u_step(depgan_ctx* c, const char* who, const float* x, const float* z
   // an out-of-range class code comes back here as status 1, after the loss fetch: no Adam update, the step counter
   // stays; the phase-1 forward has moved the BN moving statistics by then, as depgan_uresnet_grads always does
   DGCHECK(u_grads(c, who, x, z, lab, n, drop_seed, loss_host, false));
+  // the loss-weight mode with no weighted pixel in the batch: loss 0.0 and an all-zero dz, status 0; no Adam update and
+  // the step counter stays, the path of a refused sparse step (the moving statistics have moved)
+  if (c->lw_on && c->lw_counts[0] == 0) return refresh_generator_bn(c);
   return depgan_apply_adam(c, DEPGAN_NET_G);
 }
 
@@ -441,6 +466,38 @@ int depgan_uresnet_last_census(depgan_ctx* c, long long out_host[DEPGAN_MAX_HEAD
   const int C = c->cfg.nc_out;
   memcpy(out_host, c->last_census, (size_t)C * C * sizeof(long long));
   if (classes) *classes = C;
+  return DG_OK;
+}
+
+int depgan_uresnet_set_loss_weights(depgan_ctx* c, const float* w_host, int n, int ignore_code) {
+  if (!c) { dg_set_error("depgan_uresnet_set_loss_weights: null context"); return DG_ERR_ARG; }
+  if (!w_host) {
+    c->lw_on = c->lw_valid = false;
+    return DG_OK;
+  }
+  DGCHECK(u_check(c, "depgan_uresnet_set_loss_weights"));
+  DGCHECK(dg_loss_weights_check("depgan_uresnet_set_loss_weights", w_host, n, c->cfg.nc_out, ignore_code));
+  memcpy(c->lw_w, w_host, (size_t)n * sizeof(float));
+  c->lw_ignore = ignore_code;
+  c->lw_on = true;
+  c->lw_valid = false;
+  return DG_OK;
+}
+int depgan_uresnet_get_loss_weights(depgan_ctx* c, float w_host[DEPGAN_MAX_HEAD_CLASSES], int* ignore_code) {
+  if (!c || !c->lw_on) return 0;
+  if (w_host) memcpy(w_host, c->lw_w, (size_t)c->cfg.nc_out * sizeof(float));
+  if (ignore_code) *ignore_code = c->lw_ignore;
+  return 1;
+}
+int depgan_uresnet_last_label_counts(depgan_ctx* c, long long out_host[DEPGAN_LABEL_NCOUNT], int* classes) {
+  if (!c || !out_host) { dg_set_error("depgan_uresnet_last_label_counts: null argument"); return DG_ERR_ARG; }
+  if (!c->lw_on || !c->lw_valid) {
+    dg_set_error("depgan_uresnet_last_label_counts: no depgan_uresnet_* call has run in the loss-weight mode "
+                 "(depgan_uresnet_set_loss_weights)");
+    return DG_ERR_ARG;
+  }
+  memcpy(out_host, c->lw_counts, (size_t)(c->cfg.nc_out + 3) * sizeof(long long));
+  if (classes) *classes = c->cfg.nc_out;
   return DG_OK;
 }
 

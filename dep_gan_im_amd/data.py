@@ -335,11 +335,21 @@ def load_uresnet_training_set(subjects, device=None, prefetch=2, progress=None):
     return torch.cat(fs, 0), torch.cat(cs, 0)
 
 
-def to_one_hot(coded, n_class=4, device=None):
+def _check_ignore_label(ignore_label):
+    if ignore_label is None:
+        return None
+    if isinstance(ignore_label, bool) or not isinstance(ignore_label, (int, np.integer)) or not 0 <= ignore_label <= 255:
+        raise ValueError("ignore_label must be an integer in [0, 255], got %r" % (ignore_label,))
+    return int(ignore_label)
+
+
+def to_one_hot(coded, n_class=4, device=None, ignore_label=None):
     """UT:563-568: coded.astype(int) (truncation toward zero), then convert_to_1hot(., n_class) and np.squeeze.
     coded: (N, X, Y, 1) or (N, X, Y) array / tensor.  Returns (N, X, Y, n_class) float32 on the GPU, the layout
     Gen_UNet2D(..., nc_out=4).fit reads.  A value outside [0, n_class) raises DepganError (NumPy would wrap a
-    negative index)."""
+    negative index).  ignore_label: the value that truncates to it becomes an all-zero row, the ignored pixel of the
+    loss-weight mode (compile(class_weight=...)); every other out-of-range value is refused as before."""
+    ignore_label = _check_ignore_label(ignore_label)
     if isinstance(n_class, bool) or not isinstance(n_class, (int, np.integer)) or not 1 <= int(n_class) <= 127:
         raise ValueError("n_class must be an integer in [1, 127], got %r" % (n_class,))
     shape = tuple(int(d) for d in (coded.shape if hasattr(coded, "shape") else np.shape(coded)))
@@ -355,17 +365,25 @@ def to_one_hot(coded, n_class=4, device=None):
     else:
         dev = torch.device(device if device is not None else "cuda:0")
         t = torch.from_numpy(np.ascontiguousarray(np.asarray(coded), dtype=np.float32)).to(dev)
+    ign = None
+    if ignore_label is not None:
+        ign = torch.trunc(t) == float(ignore_label)
+        t = torch.where(ign, torch.zeros_like(t), t)
     out = torch.empty(shape + (int(n_class),), dtype=torch.float32, device=dev)
     _lib.check(lib.depgan_labels_to_onehot(_p(t), t.numel(), int(n_class), _p(out), _stream(dev, None)),
                "depgan_labels_to_onehot")
+    if ign is not None:
+        out[ign.reshape(shape)] = 0.0
     return out
 
 
-def to_codes(coded, n_class=4, device=None):
+def to_codes(coded, n_class=4, device=None, ignore_label=None):
     """The 1-byte counterpart of to_one_hot: coded.astype(int) (truncation toward zero, UT:563) as class indices.
     coded: (N, X, Y, 1) or (N, X, Y) array / tensor.  Returns (N, X, Y) uint8 on the GPU, the layout
     Gen_UNet2D(..., nc_out=n_class).compile(loss='sparse_categorical_crossentropy').fit reads: 1 byte per pixel where
-    the one-hot tensor has 4 * n_class.  A value outside [0, n_class) raises DepganError, as in to_one_hot."""
+    the one-hot tensor has 4 * n_class.  A value outside [0, n_class) raises DepganError, as in to_one_hot.
+    ignore_label: the value that truncates to it passes through as that byte (compile(ignore_label=...))."""
+    ignore_label = _check_ignore_label(ignore_label)
     if isinstance(n_class, bool) or not isinstance(n_class, (int, np.integer)) or not 1 <= int(n_class) <= 127:
         raise ValueError("n_class must be an integer in [1, 127], got %r" % (n_class,))
     shape = tuple(int(d) for d in (coded.shape if hasattr(coded, "shape") else np.shape(coded)))
@@ -381,11 +399,87 @@ def to_codes(coded, n_class=4, device=None):
         dev = torch.device(device if device is not None else "cuda:0")
         t = torch.from_numpy(np.ascontiguousarray(np.asarray(coded), dtype=np.float32)).to(dev).reshape(shape)
     ok = (t > -1.0) & (t < float(n_class))                 # trunc(v) in [0, n_class); False for NaN
+    if ignore_label is not None:
+        ok = ok | (torch.trunc(t) == float(ignore_label))
     bad = int((~ok).sum())
     if bad:
         raise _lib.DepganError("to_codes: %d of %d values truncate to a class outside [0, %d)"
                                % (bad, t.numel(), int(n_class)))
     return t.to(torch.uint8).contiguous()                  # float -> integer conversion truncates toward zero
+
+
+def class_counts(labels, n_class, ignore_label=None, device=None, chunk=1 << 26, one_hot=None):
+    """Pixels per class of a label set, counted on the device by the loss's label pre-pass (depgan_op_label_counts).
+    labels: one-hot (..., n_class) float32, or class indices of any shape (uint8, or anything Engine-style narrowing to a
+    byte accepts: integer dtypes and integral floats; a value outside [0, 255] counts as out of range), NumPy or tensor,
+    of any size: it goes through in chunks of `chunk` pixels.  The true class of a one-hot row is its first arg-max and
+    an all-zero row is ignored.  one_hot: None takes a floating array whose last dimension is n_class for one-hot rows
+    and anything else for class indices; True / False says it.  Returns a dict: 'classes' (np.int64, n_class), 'ignored', 'bad' (codes >= n_class that
+    are not ignore_label) and 'total'.  n_class in 2..8."""
+    ignore_label = _check_ignore_label(ignore_label)
+    if isinstance(n_class, bool) or not isinstance(n_class, (int, np.integer)) or not 2 <= int(n_class) <= _lib.MAX_HEAD_CLASSES:
+        raise ValueError("n_class must be an integer in [2, %d], got %r" % (_lib.MAX_HEAD_CLASSES, n_class))
+    import torch
+    K = int(n_class)
+    lib = _lib.load()
+    tens = isinstance(labels, torch.Tensor)
+    a = labels if tens else np.asarray(labels)
+    dev = a.device if tens and a.is_cuda and device is None else torch.device(device if device is not None else "cuda:0")
+    floating = a.is_floating_point() if tens else a.dtype.kind == "f"
+    onehot = (floating and a.ndim >= 2 and int(a.shape[-1]) == K) if one_hot is None else bool(one_hot)
+    if onehot and (a.ndim < 2 or int(a.shape[-1]) != K):
+        raise ValueError("class_counts: one-hot labels must end in a dimension of n_class = %d, got shape %s" % (K, tuple(a.shape)))
+    if onehot:
+        flat = a.reshape(-1, K)
+    else:
+        flat = a.reshape(-1)
+    P = int(flat.shape[0])
+    if P < 1:
+        raise ValueError("class_counts: no labels")
+    tot = np.zeros(K + 3, np.int64)
+    out = (C.c_longlong * _lib._K["DEPGAN_LABEL_NCOUNT"])()
+    for i in range(0, P, int(chunk)):
+        part = flat[i:i + int(chunk)]
+        if onehot:
+            t = (part if tens else torch.from_numpy(np.ascontiguousarray(part, dtype=np.float32)))
+            t = t.to(device=dev, dtype=torch.float32).contiguous()
+            args = (_p(t), None)
+        else:
+            if part.dtype != (torch.uint8 if tens else np.uint8):
+                xp = torch if tens else np
+                if floating and not bool((part == xp.trunc(part)).all()):
+                    raise ValueError("class_counts: class indices must hold integral values")
+                badv = (part < 0) | (part > 255)
+                part = xp.where(badv, xp.full_like(part, 254 if ignore_label == 255 else 255), part)
+                part = part.to(torch.uint8) if tens else part.astype(np.uint8)
+            t = (part if tens else torch.from_numpy(np.ascontiguousarray(part))).to(dev).contiguous()
+            args = (None, _p(t))
+        _lib.check(lib.depgan_op_label_counts(args[0], args[1], int(t.shape[0]), K,
+                                              -1 if ignore_label is None else ignore_label, out, _stream(dev, None)),
+                   "depgan_op_label_counts")
+        tot += np.array(out[:K + 3], np.int64)
+    return {"classes": tot[3:].copy(), "ignored": int(tot[1]), "bad": int(tot[2]), "total": P}
+
+
+def balanced_class_weights(counts, rule="inverse"):
+    """Class weights from pixel counts per class (class_counts(...)['classes']); host only.
+    rule 'inverse': total / (C * n_k), scikit-learn's 'balanced'; rule 'median': median(n) / n_k over the classes that
+    occur, median-frequency balancing.  A class that never occurs gets weight 0 (it cannot meet the loss); an input
+    without any pixel is a ValueError, since all-zero weights are no valid setting.  Returns np.float64 (C,)."""
+    if rule not in ("inverse", "median"):
+        raise ValueError("rule must be 'inverse' or 'median', got %r" % (rule,))
+    n = np.asarray(counts["classes"] if isinstance(counts, dict) else counts, np.float64).reshape(-1)
+    if n.size < 1 or not np.all(np.isfinite(n)) or np.any(n < 0):
+        raise ValueError("counts must be finite and >= 0, got %r" % (n.tolist(),))
+    seen = n > 0
+    if not seen.any():
+        raise ValueError("balanced_class_weights: no class occurs (every count is 0)")
+    w = np.zeros(n.size, np.float64)
+    if rule == "inverse":
+        w[seen] = n.sum() / (n.size * n[seen])
+    else:
+        w[seen] = np.median(n[seen]) / n[seen]
+    return w
 
 
 def data_prep_save(image_data):

@@ -64,6 +64,7 @@ class Engine:
         self.h = h
         self._use_current_stream()
         self._tables = {}
+        self._ignore_label = None     # set_loss_weights: the label value that takes a pixel out of the loss
         self._ar_cb = None       # keeps the ctypes callback of set_allreduce alive
         self.world = 1
         self._forward_storage = "float32"
@@ -515,7 +516,9 @@ class Engine:
         """(n, H, W) or (n, H, W, 1) class indices of any integer dtype, or float with integral values, as the contiguous
         uint8 CUDA tensor the *_sparse entries read (NumPy arrays are narrowed on the host: 1 byte per pixel crosses the
         bus).  A float that is not integral is a ValueError; a value outside [0, 255] becomes 255, which no class count
-        reaches, so the library reports it with the other out-of-range codes."""
+        reaches, so the library reports it with the other out-of-range codes.  With an ignore label set
+        (set_loss_weights) the value equal to it reaches the device as that byte, and a value outside [0, 255] becomes
+        a byte that is neither a class nor the ignore label (254 when the ignore label is 255)."""
         torch = _torch()
         tens = isinstance(labels, torch.Tensor)
         a = labels if tens else np.asarray(labels)
@@ -529,7 +532,7 @@ class Engine:
                 a = a.to(u8) if tens else a.astype(u8)
             else:
                 bad = (a < 0) | (a > 255)
-                a = xp.where(bad, xp.full_like(a, 255), a)
+                a = xp.where(bad, xp.full_like(a, 254 if self._ignore_label == 255 else 255), a)
                 a = a.to(u8) if tens else a.astype(u8)
         t = a if tens else torch.from_numpy(np.ascontiguousarray(a))
         return t.to(self.device).contiguous()
@@ -586,6 +589,42 @@ class Engine:
         out, k = (C.c_longlong * (_lib.MAX_HEAD_CLASSES ** 2))(), C.c_int()
         check(self.lib.depgan_uresnet_last_census(self.h, out, C.byref(k)), "depgan_uresnet_last_census")
         return np.array(out[:k.value * k.value], np.int64).reshape(k.value, k.value)
+
+    def set_loss_weights(self, class_weight=None, ignore_label=None):
+        """depgan_uresnet_set_loss_weights: the loss-weight mode of every uresnet() call.  class_weight: nc_out floats,
+        finite and >= 0 with at least one > 0 (None with an ignore_label: unit weights); ignore_label: None, or a label
+        value 0..255 whose pixels add no loss and no gradient and are not counted as out of range (class codes only: with
+        one-hot labels an ignored pixel is an all-zero row).  The loss is the weighted sum over the number of pixels with
+        a non-zero weight (Keras 2's weighted-objective rule).  Both None turns the mode off (the default)."""
+        if class_weight is None and ignore_label is None:
+            check(self.lib.depgan_uresnet_set_loss_weights(self.h, None, 0, -1), "depgan_uresnet_set_loss_weights")
+            self._ignore_label = None
+            return
+        self._need_trainable("set_loss_weights")
+        w = np.ones(self.nc_out, np.float32) if class_weight is None else np.asarray(class_weight, np.float32).reshape(-1)
+        if ignore_label is not None and (int(ignore_label) != ignore_label or not 0 <= int(ignore_label) <= 255):
+            raise ValueError("ignore_label must be an integer in [0, 255], got %r" % (ignore_label,))
+        arr = (C.c_float * len(w))(*[float(v) for v in w])
+        check(self.lib.depgan_uresnet_set_loss_weights(self.h, arr, len(w), -1 if ignore_label is None else int(ignore_label)),
+              "depgan_uresnet_set_loss_weights")
+        self._ignore_label = None if ignore_label is None else int(ignore_label)
+
+    @property
+    def loss_weights(self):
+        """None with the loss-weight mode off, else (np.float32 class weights, ignore label or None)."""
+        w, ign = (C.c_float * _lib.MAX_HEAD_CLASSES)(), C.c_int()
+        if not self.lib.depgan_uresnet_get_loss_weights(self.h, w, C.byref(ign)):
+            return None
+        return np.array(w[:self.nc_out], np.float32), (None if ign.value < 0 else ign.value)
+
+    def uresnet_label_counts(self):
+        """The label pre-pass counts of the last uresnet() call made in the loss-weight mode, as a dict: 'den' (pixels
+        with a non-zero weight, the loss's denominator), 'ignored' (pixels without a true class), 'bad' (out-of-range
+        codes) and 'classes' (np.int64 pixel count per true class).  Host memory (depgan_uresnet_last_label_counts)."""
+        out, k = (C.c_longlong * _lib._K["DEPGAN_LABEL_NCOUNT"])(), C.c_int()
+        check(self.lib.depgan_uresnet_last_label_counts(self.h, out, C.byref(k)), "depgan_uresnet_last_label_counts")
+        return {"den": int(out[0]), "ignored": int(out[1]), "bad": int(out[2]),
+                "classes": np.array(out[3:3 + k.value], np.int64)}
 
     def apply_adam(self, net):
         self._need_trainable("apply_adam")

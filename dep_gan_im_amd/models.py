@@ -298,6 +298,7 @@ class GeneratorModel(_Model):
         self._lr = 1e-4
         self._loss = "categorical_crossentropy"
         self._metrics = []
+        self._class_weight, self._ignore_label = None, None      # compile(class_weight=, ignore_label=)
         self._drop_rng = np.random.RandomState(seed)
 
     def _static_table(self):
@@ -323,6 +324,8 @@ class GeneratorModel(_Model):
         super()._bind(engine, net)
         if self._metrics:
             engine.set_census(True)
+        if self._class_weight is not None or self._ignore_label is not None:
+            engine.set_loss_weights(self._class_weight, self._ignore_label)
 
     def inference_copy(self, dtype="bfloat16"):
         """A new predict-only model with this architecture and a copy of the current weights, whose private engine runs
@@ -365,7 +368,37 @@ class GeneratorModel(_Model):
             raise RuntimeError("%s: the tanh generator is trained through the WGAN-GP closures "
                                "(trainers.build_trainers), not compiled with a loss" % what)
 
-    def compile(self, optimizer="adam", loss="categorical_crossentropy", lr=None, metrics=None, **_):
+    def _loss_weight_args(self, loss, class_weight, ignore_label):
+        """compile's class_weight / ignore_label as (np.float32 weights or None, int or None); ValueError otherwise.
+        Needs no engine."""
+        C = self.nc_out
+        if ignore_label is not None:
+            if loss != "sparse_categorical_crossentropy":
+                raise ValueError("ignore_label needs loss='sparse_categorical_crossentropy' (class indices); with one-hot "
+                                 "labels encode ignored pixels as all-zero rows (data.to_one_hot(..., ignore_label=...))")
+            if isinstance(ignore_label, bool) or not isinstance(ignore_label, (int, np.integer)) or not 0 <= ignore_label <= 255:
+                raise ValueError("ignore_label must be an integer in [0, 255], got %r" % (ignore_label,))
+            ignore_label = int(ignore_label)
+        if class_weight is None:
+            return None, ignore_label
+        if isinstance(class_weight, dict):
+            bad = [k for k in class_weight if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 0 <= k < C]
+            if bad:
+                raise ValueError("class_weight: keys must be class indices in [0, %d), got %r" % (C, bad))
+            w = np.ones(C, np.float64)
+            for k, v in class_weight.items():
+                w[int(k)] = float(v)
+        else:
+            w = np.asarray(class_weight, np.float64).reshape(-1)
+            if w.size != C:
+                raise ValueError("class_weight must hold nc_out = %d weights, got %d" % (C, w.size))
+        w32 = w.astype(np.float32)
+        if not np.all(np.isfinite(w32)) or np.any(w32 < 0) or not np.any(w32 > 0):
+            raise ValueError("class_weight: every weight must be finite and >= 0, and at least one > 0, got %r" % (w.tolist(),))
+        return w32, ignore_label
+
+    def compile(self, optimizer="adam", loss="categorical_crossentropy", lr=None, metrics=None, class_weight=None,
+                ignore_label=None, **_):
         """model.compile(optimizer=Adam(lr=1e-4), loss='categorical_crossentropy')  (UT:427).
         metrics: names out of 'acc' / 'accuracy' (pixel accuracy: Keras' categorical_accuracy, arg-max against arg-max),
         'dice' and 'iou' (the means over the foreground classes 1..nc_out-1, evaluate.confusion_metrics).  They come from
@@ -378,11 +411,22 @@ class GeneratorModel(_Model):
         loss='sparse_categorical_crossentropy' is the same loss on integer labels: train_on_batch, test_on_batch,
         evaluate, fit and its validation_data then take class indices (n, H, W) or (n, H, W, 1) -- any integer dtype, or
         float with integral values (data.to_codes makes them, 1 byte per pixel) -- instead of the one-hot
-        (n, H, W, nc_out) tensor, and compute bit for bit what the one-hot encoding of those labels gives."""
+        (n, H, W, nc_out) tensor, and compute bit for bit what the one-hot encoding of those labels gives.
+        class_weight: nc_out floats, or a dict {class: weight} with the missing classes at 1.0 (Keras refuses
+        class_weight for targets of 3 or more dimensions; data.balanced_class_weights makes them from pixel counts).
+        ignore_label: a label value 0..255 whose pixels add no loss and no gradient (sparse loss only; with one-hot labels
+        an all-zero row is the ignored pixel); alone it means unit weights.  Either turns the loss-weight mode on
+        (Engine.set_loss_weights): the loss of train_on_batch, test_on_batch, evaluate, fit and its validation data is
+        the weighted sum over the number of pixels with a non-zero weight, and the metrics leave ignored pixels out.
+        compile() without them turns the mode off; then every result is what it was without the mode."""
         self._need_softmax("compile")
         if loss not in _LOSSES:
             raise ValueError("loss must be 'categorical_crossentropy' (UT:427) or 'sparse_categorical_crossentropy', "
                              "got %r" % (loss,))
+        was_on = self._class_weight is not None or self._ignore_label is not None
+        self._class_weight, self._ignore_label = self._loss_weight_args(loss, class_weight, ignore_label)
+        if self._engine is not None and (was_on or self._class_weight is not None or self._ignore_label is not None):
+            self._engine.set_loss_weights(self._class_weight, self._ignore_label)
         if metrics is not None:
             if isinstance(metrics, str):
                 metrics = [metrics]

@@ -215,6 +215,37 @@ int depgan_uresnet_get_census(depgan_ctx* ctx);
 int depgan_uresnet_last_census(depgan_ctx* ctx, long long out_host[DEPGAN_MAX_HEAD_CLASSES * DEPGAN_MAX_HEAD_CLASSES],
                                int* classes);
 
+/* The loss-weight mode of the supervised path: per-class loss weights and a label that takes a pixel out of the loss.
+ * depgan_uresnet_set_loss_weights(ctx, w_host, n, ignore_code): w_host = nc_out class weights cw[k] on the host, each
+ *   finite and >= 0, at least one > 0, n == nc_out; ignore_code = -1 for none, else a byte value 0..255 (it may be
+ *   >= nc_out, or a real class).  Anything else is status 1 with a message, before any HIP call; status 3 on an inference
+ *   context, status 1 for nc_out = 1 (as depgan_uresnet_set_census).  w_host == NULL turns the mode off (the default):
+ *   every entry then computes, bit for bit, what it computed before this mode existed.
+ * With the mode on, all six depgan_uresnet_{grads,step,eval}{,_sparse} entries use, per pixel with label row t (the
+ *   one-hot row, or t[k] = (k == code) formed in registers):
+ *     a code equal to ignore_code has t = 0 and is NOT counted as out of range; any other code >= nc_out is counted and
+ *     refused as before; with one-hot labels the ignored pixel is the all-zero row (the ignore code is not read);
+ *     pixel weight w_i = sum_k cw[k] t[k] (left to right); den = the number of pixels with w_i != 0, an exact integer
+ *     counted by a label pre-pass on the device; loss = -sum_i sum_k cw[k] t[k] log r_k / den, q and r as in
+ *     depgan_op_softmax_ce; dL/dq_k = -cw[k] t[k] (1/den) / q_k on the closed clip interval.
+ *   This is Keras 2's weighted-objective rule (the weighted sum over the count of non-zero weights), not a division by
+ *   sum w_i.  Ignored pixels and pixels of a zero-weight class add no loss and no gradient (their dz row is 0), are not
+ *   in den, and still get their probabilities.  den == 0: loss 0.0, dz all zero, status 0; depgan_uresnet_step{,_sparse}
+ *   then applies NO Adam update and leaves the step counter alone (the moving statistics have moved).  *loss_host =
+ *   sum / den and depgan_last_sums[1] = den.  Census: a pixel without a true class (the ignore code, an all-zero one-hot
+ *   row) joins no bin, a zero-weight class keeps its bin: sum(table) + out-of-range + ignored == n*H*W.
+ * depgan_uresnet_get_loss_weights: returns 1 and fills w_host (nc_out entries) and *ignore_code (either may be NULL)
+ *   when the mode is on, else returns 0.
+ * depgan_uresnet_last_label_counts: host only.  out_host = the pre-pass counts of the last depgan_uresnet_* call made
+ *   with the mode on, which came back in the same copy and synchronisation as its loss: [0] den, [1] pixels without a
+ *   true class, [2] out-of-range codes, [3 + k] pixels of true class k (the code, or the first arg-max of the one-hot
+ *   row); the first nc_out + 3 entries are valid, nc_out reported in *classes when not NULL.  Status 1 before any such
+ *   call and after the mode was set again. */
+#define DEPGAN_LABEL_NCOUNT 11 /* 3 + DEPGAN_MAX_HEAD_CLASSES */
+int depgan_uresnet_set_loss_weights(depgan_ctx* ctx, const float* w_host, int n, int ignore_code);
+int depgan_uresnet_get_loss_weights(depgan_ctx* ctx, float w_host[DEPGAN_MAX_HEAD_CLASSES], int* ignore_code);
+int depgan_uresnet_last_label_counts(depgan_ctx* ctx, long long out_host[DEPGAN_LABEL_NCOUNT], int* classes);
+
 /* Un-normalised pieces of the last critic / generator evaluation, for exact
  * data-parallel reporting: critic: [sum D(real), sum D(fake), sum (norm-1)^2, n];
  * generator: [sum D_y2(fake), sum D_dem(attr), sum |attr-real_dem|, sum wr, sum wf, sum wr*wf, n, n*H*W]. */
@@ -649,6 +680,23 @@ int depgan_op_softmax_ce(const float* logits, const float* onehot, const unsigne
  * a null census_host, or neither onehot nor codes, is status 1 before any HIP call.  Synchronises the stream. */
 int depgan_op_softmax_ce_census(const float* logits, const float* onehot, const unsigned char* codes, float* probs,
                                 float* dz, float* loss_sum, long long* census_host, long P, int C, void* hip_stream);
+/* depgan_op_softmax_ce_census in the loss-weight mode (depgan_uresnet_set_loss_weights states the rule): w_host = n == C
+ * host class weights, ignore_code = -1 or a byte value (read with codes only; with onehot the ignored pixel is the
+ * all-zero row).  A label pre-pass counts den first; counts_host (host, required) receives its C + 3 counts in the
+ * layout of depgan_uresnet_last_label_counts, counts_host[0] = den.  dz carries 1 / den (0 for den = 0) and
+ * loss_sum[0] is the weighted sum: the mean is loss_sum / den.  census_host is optional (NULL: no census); under the
+ * mode a pixel without a true class joins no bin.  With unit weights and nothing ignored probs, dz and loss_sum are bit
+ * for bit those of depgan_op_softmax_ce and den == P.  A negative, NaN or infinite weight, all-zero weights, n != C or
+ * an ignore code outside [-1, 255] is status 1 before any HIP call.  A code >= C that is not the ignore code is counted
+ * and reported as depgan_op_softmax_ce does (status 1, everything written).  Synchronises the stream. */
+int depgan_op_softmax_ce_weighted(const float* logits, const float* onehot, const unsigned char* codes,
+                                  const float* w_host, int n, int ignore_code, float* probs, float* dz, float* loss_sum,
+                                  long long* census_host, long long* counts_host, long P, int C, void* hip_stream);
+/* The label pre-pass alone, with unit weights: out_host (host, C + 3 entries) in the layout of
+ * depgan_uresnet_last_label_counts for P pixels given as onehot (P, C) fp32 or codes (P) unsigned char, exactly one of
+ * them.  Integers summed in two stages without atomics.  Synchronises the stream. */
+int depgan_op_label_counts(const float* onehot, const unsigned char* codes, long P, int C, int ignore_code,
+                           long long* out_host, void* hip_stream);
 /* BatchNorm over the R rows of an [R][ld] matrix (first C columns), moving statistics updated when given:
  * moving = momentum*moving + (1 - momentum)*(mean, var*corr) */
 int depgan_op_bn_rows_fwd(const float* x, float* y, int R, int C, int ld, const float* gamma, const float* beta,
