@@ -215,6 +215,14 @@ struct depgan_ctx {
   float lw_w[DEPGAN_MAX_HEAD_CLASSES];
   int lw_ignore = -1;
   long long lw_counts[DEPGAN_LABEL_NCOUNT];
+  // depgan_uresnet_set_dice_loss: the soft Dice loss (DEPGAN_DICE_OFF by default).  dice_c: the nc_out class coefficients
+  // of the class form; dice_sums / dice_last: I_k, P_k, T_k (3 nc_out, packed) and the Dice term of the last call made
+  // with the mode on, which came back with that call's loss
+  int dice_form = 0;
+  bool dice_valid = false;
+  float dice_ce_coef = 1.f, dice_coef = 1.f, dice_smooth = 0.f, dice_last = 0.f;
+  float dice_c[DEPGAN_MAX_HEAD_CLASSES];
+  double dice_sums[3 * DEPGAN_MAX_HEAD_CLASSES];
   float *ones1k = nullptr, *zeros1k = nullptr;
   float *n_mean0 = nullptr, *n_rstd0 = nullptr, *n_mean1 = nullptr, *n_rstd1 = nullptr, *n_meanh = nullptr,
         *n_rstdh = nullptr;

@@ -573,6 +573,30 @@ int depgan_op_label_counts(const float* onehot, const unsigned char* codes, long
   }
   return DG_OK;
 }
+int depgan_op_dice_loss(const float* probs, const float* onehot, const unsigned char* codes, int ignore_code, int form,
+                        const float* class_coef_host, int n, float smooth, float ce_coef, float dice_coef, float* dz,
+                        double* sums_host, float* loss_host, long P, int C, void* stream) {
+  if (!dz || !sums_host || !loss_host) { dg_set_error("op_dice_loss: null dz_inout, sums_host or loss_host"); return DG_ERR_ARG; }
+  DGCHECK(dg_dice_check("op_dice_loss", form, ce_coef, dice_coef, smooth, class_coef_host, n, C));
+  DGCHECK(dg_dice_operands_check("op_dice_loss", probs, onehot, codes, ignore_code, dz, P, C));
+  hipStream_t st = (hipStream_t)stream;
+  // the reduction scratch, then what the coefficient stage leaves
+  const size_t cap = (dg_dice_scratch(P, C) + 1) & ~(size_t)1;
+  DevTmp scratch(st);
+  DGCHECK(op_alloc(&scratch, cap + sizeof(DgDiceDev) / sizeof(float), "op_dice_loss"));
+  DgDiceDev* out = reinterpret_cast<DgDiceDev*>(scratch.as<float>() + cap);
+  DGCHECK(dg_dice_loss(probs, onehot, codes, ignore_code, form, class_coef_host, smooth, ce_coef, dice_coef, dz, out, P, C,
+                       scratch.as<float>(), cap, st));
+  DgDiceDev h;
+  if (hipMemcpyAsync(&h, out, offsetof(DgDiceDev, A), hipMemcpyDeviceToHost, st) != hipSuccess ||
+      hipStreamSynchronize(st) != hipSuccess) {
+    dg_set_error("op_dice_loss: copy back failed");
+    return DG_ERR_HIP;
+  }
+  memcpy(sums_host, h.sums, (size_t)3 * C * sizeof(double));
+  *loss_host = h.loss;
+  return DG_OK;
+}
 int depgan_op_softmax_ce4(const float* logits, const float* onehot, float* probs, float* dz, float* loss_sum, long P,
                           void* stream) {
   return depgan_op_softmax_ce(logits, onehot, nullptr, probs, dz, loss_sum, P, 4, stream);

@@ -2,6 +2,7 @@
 // batch-statistics BatchNorm forward / backward, Dropout, softmax + categorical cross-entropy.
 #pragma once
 #include "common.h"
+#include "../../include/depgan.h"
 
 // per-channel batch mean and biased variance of an NHWC view (one pass, shifted sums; C % 4 == 0, C <= 1024).
 // scratch: dg_col_moments_scratch(B, H, W, C) floats (at most 3 * 1024 * C); DG_ERR_ARG when scratch_floats is less
@@ -84,6 +85,31 @@ int dg_softmax_ce_weighted(const float* logits, const float* onehot, const unsig
 // its argument checks alone (no HIP call): what an entry asks before it allocates
 int dg_softmax_ce_check(const float* logits, const float* onehot, const unsigned char* codes, const float* probs,
                         const float* dz, const float* loss_sum, long P, int C);
+
+// The soft Dice loss (dice_loss.hip; include/depgan.h, depgan_uresnet_set_dice_loss, states the rule).  It runs behind the
+// cross-entropy on the same stream, on the probabilities AS STORED: sums I_k = sum m t_k p_k, P_k = sum m p_k,
+// T_k = sum m t_k over the pixels that take part (m), per-class scalars A_k, B_k with dL/dp_k = m (A_k t_k + B_k), and
+// dz = ce_coef dz + dice_coef p_k (g_k - sum_j p_j g_j).  What the coefficient stage leaves on the device:
+struct DgDiceDev {
+  double sums[3 * DEPGAN_MAX_HEAD_CLASSES];   // I_0..I_{C-1}, P_0..P_{C-1}, T_0..T_{C-1} (3 C entries, packed)
+  float loss, pad;                            // the Dice term, rounded once from the double result
+  float A[DEPGAN_MAX_HEAD_CLASSES], B[DEPGAN_MAX_HEAD_CLASSES];
+};
+// dg_dice_check validates the setting without a HIP call: form DEPGAN_DICE_FLAT / _CLASS, ce_coef finite >= 0, dice_coef
+// and smooth finite > 0, coef null or (class form only) n == C finite values >= 0 with at least one > 0.
+// dg_dice_loss: coef null = 1 / C each.  ignore_code: -1 = every pixel takes part; with codes the pixels of that code
+// stay out (a code >= C always does), with onehot any value >= 0 keeps the all-zero rows out.  dz null: the sums, the
+// coefficients and the loss only (no gradient pass).  ce_coef == 0: dz is written without being read.  Two-stage sums,
+// no atomics, the partials added in index order in double; dg_dice_scratch(P, C) floats of scratch (at most 1024 * 3 C).
+int dg_dice_check(const char* who, int form, float ce_coef, float dice_coef, float smooth, const float* coef, int n,
+                  int C);
+// the operands' checks alone (no HIP call): what an entry asks before it allocates
+int dg_dice_operands_check(const char* who, const float* probs, const float* onehot, const unsigned char* codes,
+                           int ignore_code, const float* dz, long P, int C);
+size_t dg_dice_scratch(long P, int C);
+int dg_dice_loss(const float* probs, const float* onehot, const unsigned char* codes, int ignore_code, int form,
+                 const float* coef, float smooth, float ce_coef, float dice_coef, float* dz, DgDiceDev* out, long P, int C,
+                 float* scratch, size_t scratch_floats, hipStream_t st);
 
 // the 1x1 head to K = 2..8 class logits on dense (P, K) rows; a, mask and din are pixel rows of C channels at strides
 // ld* (multiples of 4 floats, 16-byte aligned), w is (C, K) dense, C / 4 a power of two <= 64

@@ -49,8 +49,10 @@ struct ULossHost {
   unsigned bad;
   long long census[DEPGAN_MAX_HEAD_CLASSES * DEPGAN_MAX_HEAD_CLASSES];
   long long counts[DEPGAN_LABEL_NCOUNT];
+  DgDiceDev dice;   // the Dice mode: the 3 C sums and the Dice term (the copy stops in front of A and B)
 };
 static_assert(offsetof(ULossHost, census) == 2 * sizeof(float), "the census follows the two scalars of loss_dev");
+static_assert(offsetof(ULossHost, dice) % 8 == 0, "the Dice sums are doubles");
 
 int uresnet_build(depgan_ctx* c) {
   const int B = c->cfg.batch;
@@ -78,7 +80,8 @@ int uresnet_build(depgan_ctx* c) {
   DGCHECK(dmalloc(c, &c->logits, P * c->cfg.nc_out));
   DGCHECK(dmalloc(c, &c->dz, P * c->cfg.nc_out));
   // [0] summed loss, [1] out-of-range codes (unsigned), then the census: nc_out^2 64-bit counts from float 2 on; behind
-  // the largest census the DEPGAN_LABEL_NCOUNT 64-bit label counts of the loss-weight mode (ULossHost is the layout)
+  // the largest census the DEPGAN_LABEL_NCOUNT 64-bit label counts of the loss-weight mode, then what the Dice mode's
+  // coefficient stage leaves (ULossHost is the layout)
   DGCHECK(dmalloc(c, &c->loss_dev, sizeof(ULossHost) / sizeof(float)));
   DGCHECK(dmalloc(c, &c->ones1k, 1024));
   DGCHECK(dmalloc(c, &c->zeros1k, 1024));
@@ -345,7 +348,7 @@ struct ULabels {
 // loss_dev[0] = summed loss, loss_dev[1] = the count of class codes outside [0, nc_out) as an unsigned; with the census
 // on (depgan_uresnet_set_census) the nc_out x nc_out table of the same pass follows as 64-bit counts.  In the
 // loss-weight mode the label pre-pass runs first and leaves its counts, den first, behind the census
-static int u_softmax_ce(depgan_ctx* c, ULabels lab, long P) {
+static int u_softmax_ce_only(depgan_ctx* c, ULabels lab, long P) {
   ProfScope ps(c, 2, 0.0, "softmax + cross-entropy");
   unsigned* bad = reinterpret_cast<unsigned*>(c->loss_dev + 1);
   if (c->lw_on)
@@ -362,6 +365,21 @@ static int u_softmax_ce(depgan_ctx* c, ULabels lab, long P) {
                        c->st);
 }
 
+// The Dice mode: its three launches follow the cross-entropy on the stream and reuse the scratch (the cross-entropy's
+// second stage has read its partials by then).  A pixel takes part unless the loss-weight mode says it has no true class:
+// the ignore code with codes, the all-zero row with one-hot labels.  grad = false (eval): no gradient pass
+static int u_softmax_ce(depgan_ctx* c, ULabels lab, long P, bool grad) {
+  DGCHECK(u_softmax_ce_only(c, lab, P));
+  if (c->dice_form == DEPGAN_DICE_OFF) return DG_OK;
+  ProfScope ps(c, 2, 0.0, "dice loss");
+  const int ignore = !c->lw_on ? -1 : (lab.codes ? c->lw_ignore : 0);
+  return dg_dice_loss(c->attr.p, lab.onehot, lab.codes, ignore, c->dice_form,
+                      c->dice_form == DEPGAN_DICE_CLASS ? c->dice_c : nullptr, c->dice_smooth, c->dice_ce_coef,
+                      c->dice_coef, grad ? c->dz : nullptr,
+                      reinterpret_cast<DgDiceDev*>(c->loss_dev + offsetof(ULossHost, dice) / sizeof(float)), P,
+                      c->cfg.nc_out, c->scratch, c->scratchFloats, c->st);
+}
+
 // the one synchronisation of a call: the summed loss, the count of out-of-range class codes and, with the census on, its
 // table come back in one copy
 static int u_loss_to_host(depgan_ctx* c, const char* who, long P, float* loss_host) {
@@ -370,8 +388,11 @@ static int u_loss_to_host(depgan_ctx* c, const char* who, long P, float* loss_ho
   h.bad = 0;
   const size_t ncen = c->census ? (size_t)c->cfg.nc_out * c->cfg.nc_out : 0;
   // the loss-weight mode: the label counts sit behind the largest census, the copy takes everything up to them
-  const size_t bytes = c->lw_on ? offsetof(ULossHost, counts) + (size_t)(c->cfg.nc_out + 3) * sizeof(long long)
-                                : 2 * sizeof(float) + ncen * sizeof(long long);
+  // the Dice mode: its sums and its loss sit behind the label counts, the copy takes everything up to them
+  const bool dice = c->dice_form != DEPGAN_DICE_OFF;
+  const size_t bytes = dice      ? offsetof(ULossHost, dice) + offsetof(DgDiceDev, A)
+                       : c->lw_on ? offsetof(ULossHost, counts) + (size_t)(c->cfg.nc_out + 3) * sizeof(long long)
+                                  : 2 * sizeof(float) + ncen * sizeof(long long);
   HIPCHECK(hipMemcpyAsync(&h, c->loss_dev, bytes, hipMemcpyDeviceToHost, c->st));
   HIPCHECK(hipStreamSynchronize(c->st));
   const unsigned bad = h.bad;
@@ -388,7 +409,14 @@ static int u_loss_to_host(depgan_ctx* c, const char* who, long P, float* loss_ho
   }
   c->last_sums[0] = h.loss;
   c->last_sums[1] = den;
-  if (loss_host) *loss_host = (den != 0.f) ? h.loss / den : 0.f;
+  float loss = (den != 0.f) ? h.loss / den : 0.f;
+  if (dice) {
+    memcpy(c->dice_sums, h.dice.sums, (size_t)3 * c->cfg.nc_out * sizeof(double));
+    c->dice_last = h.dice.loss;
+    c->dice_valid = true;
+    loss = c->dice_ce_coef * loss + c->dice_coef * h.dice.loss;
+  }
+  if (loss_host) *loss_host = loss;
   if (bad) {
     dg_set_error("%s: %u of %ld class codes are outside [0, %d)", who, bad, P, c->cfg.nc_out);
     return DG_ERR_ARG;
@@ -408,7 +436,7 @@ static int u_grads(depgan_ctx* c, const char* who, const float* x, const float* 
   c->last_drop_seed = drop_seed;
   DGCHECK(u_forward_train(c, x, z, n, drop_seed));
   DGCHECK(u_head_logits(c, n));
-  DGCHECK(u_softmax_ce(c, lab, P));
+  DGCHECK(u_softmax_ce(c, lab, P, true));
   DGCHECK(u_backward(c, x, z, n));
   // the forward pass moved the BN moving statistics: the phase-0 affines are stale (the step variant
   // refreshes everything after Adam anyway)
@@ -427,7 +455,12 @@ static int u_step(depgan_ctx* c, const char* who, const float* x, const float* z
   DGCHECK(u_grads(c, who, x, z, lab, n, drop_seed, loss_host, false));
   // the loss-weight mode with no weighted pixel in the batch: loss 0.0 and an all-zero dz, status 0; no Adam update and
   // the step counter stays, the path of a refused sparse step (the moving statistics have moved)
-  if (c->lw_on && c->lw_counts[0] == 0) return refresh_generator_bn(c);
+  // With the Dice mode on the same holds once no pixel takes part in the Dice term either: every pixel is without a true
+  // class (then den == 0 too); pixels of zero-weight classes still carry a Dice gradient, and that batch is updated
+  const long P = (long)n * c->cfg.height * c->cfg.width;
+  const bool ce_empty = c->lw_on && c->lw_counts[0] == 0;
+  const bool dice_empty = c->lw_on && c->lw_counts[1] + c->lw_counts[2] == P;
+  if (c->dice_form == DEPGAN_DICE_OFF ? ce_empty : dice_empty) return refresh_generator_bn(c);
   return depgan_apply_adam(c, DEPGAN_NET_G);
 }
 
@@ -438,7 +471,7 @@ static int u_eval(depgan_ctx* c, const char* who, const float* x, const float* z
   if (!lab.onehot && !lab.codes) { dg_set_error("%s: null labels", who); return DG_ERR_ARG; }
   const long P = (long)n * c->cfg.height * c->cfg.width;
   DGCHECK(u_forward_infer(c, x, z, n));
-  DGCHECK(u_softmax_ce(c, lab, P));
+  DGCHECK(u_softmax_ce(c, lab, P, false));
   return u_loss_to_host(c, who, P, loss_host);
 }
 
@@ -498,6 +531,49 @@ int depgan_uresnet_last_label_counts(depgan_ctx* c, long long out_host[DEPGAN_LA
   }
   memcpy(out_host, c->lw_counts, (size_t)(c->cfg.nc_out + 3) * sizeof(long long));
   if (classes) *classes = c->cfg.nc_out;
+  return DG_OK;
+}
+
+int depgan_uresnet_set_dice_loss(depgan_ctx* c, int form, float ce_coef, float dice_coef, float smooth,
+                                 const float* class_coef_host, int n) {
+  if (!c) { dg_set_error("depgan_uresnet_set_dice_loss: null context"); return DG_ERR_ARG; }
+  if (form == DEPGAN_DICE_OFF) {
+    c->dice_form = DEPGAN_DICE_OFF;
+    c->dice_valid = false;
+    return DG_OK;
+  }
+  DGCHECK(u_check(c, "depgan_uresnet_set_dice_loss"));
+  const int C = c->cfg.nc_out;
+  DGCHECK(dg_dice_check("depgan_uresnet_set_dice_loss", form, ce_coef, dice_coef, smooth, class_coef_host, n, C));
+  for (int k = 0; k < C; ++k) c->dice_c[k] = class_coef_host ? class_coef_host[k] : 1.0f / (float)C;
+  c->dice_form = form;
+  c->dice_ce_coef = ce_coef;
+  c->dice_coef = dice_coef;
+  c->dice_smooth = smooth;
+  c->dice_valid = false;
+  return DG_OK;
+}
+int depgan_uresnet_get_dice_loss(depgan_ctx* c, float* ce_coef, float* dice_coef, float* smooth,
+                                 float class_coef_host[DEPGAN_MAX_HEAD_CLASSES]) {
+  if (!c || c->dice_form == DEPGAN_DICE_OFF) return DEPGAN_DICE_OFF;
+  if (ce_coef) *ce_coef = c->dice_ce_coef;
+  if (dice_coef) *dice_coef = c->dice_coef;
+  if (smooth) *smooth = c->dice_smooth;
+  if (class_coef_host && c->dice_form == DEPGAN_DICE_CLASS)
+    memcpy(class_coef_host, c->dice_c, (size_t)c->cfg.nc_out * sizeof(float));
+  return c->dice_form;
+}
+int depgan_uresnet_last_dice_sums(depgan_ctx* c, double out_host[3 * DEPGAN_MAX_HEAD_CLASSES], int* classes,
+                                  float* dice_loss) {
+  if (!c || !out_host) { dg_set_error("depgan_uresnet_last_dice_sums: null argument"); return DG_ERR_ARG; }
+  if (c->dice_form == DEPGAN_DICE_OFF || !c->dice_valid) {
+    dg_set_error("depgan_uresnet_last_dice_sums: no depgan_uresnet_* call has run with the Dice loss on "
+                 "(depgan_uresnet_set_dice_loss)");
+    return DG_ERR_ARG;
+  }
+  memcpy(out_host, c->dice_sums, (size_t)3 * c->cfg.nc_out * sizeof(double));
+  if (classes) *classes = c->cfg.nc_out;
+  if (dice_loss) *dice_loss = c->dice_last;
   return DG_OK;
 }
 

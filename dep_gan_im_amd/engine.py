@@ -18,6 +18,7 @@ from ._lib import (ARENA_ADAM_M, ARENA_ADAM_V, ARENA_GRADS, ARENA_NONTRAINABLE, 
                    NET_D_Y2, NET_G, Config, check, load)
 
 NET_IDS = {"G": NET_G, "D_y2": NET_D_Y2, "D_dem": NET_D_DEM}
+_DICE_FORMS = {"flat": _lib._K["DEPGAN_DICE_FLAT"], "class": _lib._K["DEPGAN_DICE_CLASS"]}
 
 
 def _torch():
@@ -625,6 +626,48 @@ class Engine:
         check(self.lib.depgan_uresnet_last_label_counts(self.h, out, C.byref(k)), "depgan_uresnet_last_label_counts")
         return {"den": int(out[0]), "ignored": int(out[1]), "bad": int(out[2]),
                 "classes": np.array(out[3:3 + k.value], np.int64)}
+
+    def set_dice_loss(self, form=None, ce_weight=1.0, dice_weight=1.0, smooth=1e-7, class_coef=None):
+        """depgan_uresnet_set_dice_loss: the soft Dice loss of every uresnet() call, alone or added to the cross-entropy.
+        form: None (off, the default), 'flat' (the reference's dice_coef_loss over everything flattened, UT:110-121) or
+        'class' (sum_k c_k (1 - Dice_k), class_coef = the nc_out coefficients c_k, None for 1 / nc_out each).  The loss
+        of a call is ce_weight * cross-entropy + dice_weight * Dice; ce_weight >= 0, dice_weight > 0, smooth > 0.  With
+        the loss-weight mode on, pixels without a true class (the ignore label, an all-zero one-hot row) take no part."""
+        if form is None:
+            check(self.lib.depgan_uresnet_set_dice_loss(self.h, 0, 1.0, 1.0, 0.0, None, 0), "depgan_uresnet_set_dice_loss")
+            return
+        self._need_trainable("set_dice_loss")
+        if form not in _DICE_FORMS:
+            raise ValueError("form must be None, 'flat' or 'class', got %r" % (form,))
+        arr, n = None, 0
+        if class_coef is not None:
+            c = np.asarray(class_coef, np.float32).reshape(-1)
+            arr, n = (C.c_float * len(c))(*[float(v) for v in c]), len(c)
+        check(self.lib.depgan_uresnet_set_dice_loss(self.h, _DICE_FORMS[form], float(ce_weight), float(dice_weight),
+                                                    float(smooth), arr, n), "depgan_uresnet_set_dice_loss")
+
+    @property
+    def dice_loss(self):
+        """None with the Dice loss off, else a dict: 'form', 'ce_weight', 'dice_weight', 'smooth' and 'class_coef'
+        (np.float32, the class form's coefficients; None for the flat form)."""
+        ce, dw, sm, cc = C.c_float(), C.c_float(), C.c_float(), (C.c_float * _lib.MAX_HEAD_CLASSES)()
+        form = self.lib.depgan_uresnet_get_dice_loss(self.h, C.byref(ce), C.byref(dw), C.byref(sm), cc)
+        if not form:
+            return None
+        name = [k for k, v in _DICE_FORMS.items() if v == form][0]
+        return {"form": name, "ce_weight": ce.value, "dice_weight": dw.value, "smooth": sm.value,
+                "class_coef": np.array(cc[:self.nc_out], np.float32) if name == "class" else None}
+
+    def uresnet_dice_sums(self):
+        """The Dice sums of the last uresnet() call made with the Dice loss on, as a dict of np.float64 arrays (nc_out):
+        'intersection' (I_k = sum t_k p_k), 'pred' (P_k = sum p_k), 'true' (T_k = sum t_k) over the pixels that took
+        part, and 'loss', the Dice term.  evaluate.soft_dice turns them into per-class soft Dice.  They came back with
+        that call's loss; this reads host memory (depgan_uresnet_last_dice_sums)."""
+        out, k, loss = (C.c_double * (3 * _lib.MAX_HEAD_CLASSES))(), C.c_int(), C.c_float()
+        check(self.lib.depgan_uresnet_last_dice_sums(self.h, out, C.byref(k), C.byref(loss)), "depgan_uresnet_last_dice_sums")
+        n = k.value
+        return {"intersection": np.array(out[:n], np.float64), "pred": np.array(out[n:2 * n], np.float64),
+                "true": np.array(out[2 * n:3 * n], np.float64), "loss": float(loss.value)}
 
     def apply_adam(self, net):
         self._need_trainable("apply_adam")

@@ -163,6 +163,21 @@ def confusion_metrics(cm, smooth=1e-7):
             "mean_iou": sum(iou[1:].tolist()) / (len(iou) - 1.0)}
 
 
+def soft_dice(sums, smooth=1e-7):
+    """Per-class soft Dice from the sums of a call made with the Dice loss on (Engine.uresnet_dice_sums(): a dict with
+    'intersection' I_k = sum t_k p_k, 'pred' P_k = sum p_k and 'true' T_k = sum t_k over the pixels that took part).
+    Returns {'dice': (2 I_k + smooth) / (T_k + P_k + smooth) per class (np.float64), 'flat': the reference's dice_coef
+    over everything flattened (UT:110-117), 'mean_dice': the mean over the foreground classes 1..C-1}.  Pure NumPy."""
+    I, P, T = (np.asarray(sums[k], np.float64).reshape(-1) for k in ("intersection", "pred", "true"))
+    if not (I.size == P.size == T.size >= 2):
+        raise ValueError("soft_dice: intersection, pred and true must hold one value per class (at least 2 classes)")
+    if not smooth > 0:
+        raise ValueError("soft_dice: smooth must be > 0, got %r" % (smooth,))
+    dice = (2.0 * I + smooth) / (T + P + smooth)
+    return {"dice": dice, "flat": float((2.0 * I.sum() + smooth) / (T.sum() + P.sum() + smooth)),
+            "mean_dice": sum(dice[1:].tolist()) / (len(dice) - 1.0)}
+
+
 def metrics_from_census(c, voxel_volume):
     """The reference's scalar algebra on the census (GE:640-808)."""
     vol_1tp__ml = c[0] * voxel_volume / 1000                                          # GE:640-641

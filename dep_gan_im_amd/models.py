@@ -255,6 +255,8 @@ def _gen_static_table(nicg, fm, nc_out):
 
 
 _LOSSES = ("categorical_crossentropy", "sparse_categorical_crossentropy")
+# the reference's own loss name (UT:120): one-hot labels, the flat Dice form alone, smooth 1e-7
+_DICE_LOSS = "dice_coef_loss"
 # compile(metrics=[...]): the name as given is the history key; what it reads out of evaluate.confusion_metrics
 _METRICS = {"acc": "accuracy", "accuracy": "accuracy", "dice": "mean_dice", "iou": "mean_iou"}
 
@@ -299,6 +301,7 @@ class GeneratorModel(_Model):
         self._loss = "categorical_crossentropy"
         self._metrics = []
         self._class_weight, self._ignore_label = None, None      # compile(class_weight=, ignore_label=)
+        self._dice = None                                        # compile(dice_loss=...): Engine.set_dice_loss's arguments
         self._drop_rng = np.random.RandomState(seed)
 
     def _static_table(self):
@@ -326,6 +329,8 @@ class GeneratorModel(_Model):
             engine.set_census(True)
         if self._class_weight is not None or self._ignore_label is not None:
             engine.set_loss_weights(self._class_weight, self._ignore_label)
+        if self._dice is not None:
+            engine.set_dice_loss(**self._dice)
 
     def inference_copy(self, dtype="bfloat16"):
         """A new predict-only model with this architecture and a copy of the current weights, whose private engine runs
@@ -397,8 +402,54 @@ class GeneratorModel(_Model):
             raise ValueError("class_weight: every weight must be finite and >= 0, and at least one > 0, got %r" % (w.tolist(),))
         return w32, ignore_label
 
+    def _dice_args(self, loss, dice_loss, dice_weight, ce_weight, dice_smooth, dice_classes):
+        """compile's Dice arguments as the keyword arguments of Engine.set_dice_loss, or None with the mode off;
+        ValueError otherwise.  Needs no engine."""
+        C = self.nc_out
+        if loss == _DICE_LOSS:
+            if dice_loss not in (None, "flat") or dice_classes is not None:
+                raise ValueError("loss='dice_coef_loss' is the flat form alone: leave dice_loss and dice_classes out")
+            dice_loss, ce_weight = "flat", 0.0
+        if dice_loss is None:
+            if dice_classes is not None:
+                raise ValueError("dice_classes needs dice_loss='class'")
+            return None
+        if dice_loss not in ("flat", "class"):
+            raise ValueError("dice_loss must be None, 'flat' or 'class', got %r" % (dice_loss,))
+
+        def number(v, name, positive):
+            if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)):
+                raise ValueError("%s must be a number, got %r" % (name, v))
+            v32 = float(np.float32(v))
+            if not np.isfinite(v32) or (v32 <= 0 if positive else v32 < 0):
+                raise ValueError("%s must be finite and %s 0 (as float32), got %r" % (name, ">" if positive else ">=", v))
+            return float(v)
+        out = {"form": dice_loss, "ce_weight": number(ce_weight, "ce_weight", False),
+               "dice_weight": number(dice_weight, "dice_weight", True), "smooth": number(dice_smooth, "dice_smooth", True),
+               "class_coef": None}
+        if dice_classes is None:
+            return out
+        if dice_loss == "flat":
+            raise ValueError("dice_classes: the flat form has no class coefficients (dice_loss='class' takes them)")
+        if isinstance(dice_classes, str):
+            if dice_classes != "foreground":
+                raise ValueError("dice_classes must be None, 'foreground' or %d coefficients, got %r" % (C, dice_classes))
+            c = np.full(C, 1.0 / (C - 1), np.float64)
+            c[0] = 0.0
+        else:
+            c = np.asarray(dice_classes, np.float64).reshape(-1)
+            if c.size != C:
+                raise ValueError("dice_classes must hold nc_out = %d coefficients, got %d" % (C, c.size))
+        c32 = c.astype(np.float32)
+        if not np.all(np.isfinite(c32)) or np.any(c32 < 0) or not np.any(c32 > 0):
+            raise ValueError("dice_classes: every coefficient must be finite and >= 0, and at least one > 0, got %r"
+                             % (c.tolist(),))
+        out["class_coef"] = c32
+        return out
+
     def compile(self, optimizer="adam", loss="categorical_crossentropy", lr=None, metrics=None, class_weight=None,
-                ignore_label=None, **_):
+                ignore_label=None, dice_loss=None, dice_weight=1.0, ce_weight=1.0, dice_smooth=1e-7, dice_classes=None,
+                **_):
         """model.compile(optimizer=Adam(lr=1e-4), loss='categorical_crossentropy')  (UT:427).
         metrics: names out of 'acc' / 'accuracy' (pixel accuracy: Keras' categorical_accuracy, arg-max against arg-max),
         'dice' and 'iou' (the means over the foreground classes 1..nc_out-1, evaluate.confusion_metrics).  They come from
@@ -418,13 +469,24 @@ class GeneratorModel(_Model):
         an all-zero row is the ignored pixel); alone it means unit weights.  Either turns the loss-weight mode on
         (Engine.set_loss_weights): the loss of train_on_batch, test_on_batch, evaluate, fit and its validation data is
         the weighted sum over the number of pixels with a non-zero weight, and the metrics leave ignored pixels out.
-        compile() without them turns the mode off; then every result is what it was without the mode."""
+        compile() without them turns the mode off; then every result is what it was without the mode.
+        dice_loss: None, 'flat' (the reference's dice_coef_loss, UT:110-121: one Dice over everything flattened) or
+        'class' (sum_k c_k (1 - Dice_k) with dice_classes = None for c_k = 1 / nc_out, 'foreground' for c_0 = 0 and
+        1 / (nc_out - 1) elsewhere -- the Dice metrics=['dice'] reports -- or nc_out coefficients >= 0).  The loss is then
+        ce_weight * cross-entropy + dice_weight * Dice on the softmax probabilities (Engine.set_dice_loss); `loss` still
+        selects the label format and the cross-entropy, and class_weight acts on the cross-entropy alone, while ignored
+        pixels are left out of both.  loss='dice_coef_loss' is the reference's name for one-hot labels, the flat form,
+        ce_weight = 0 and smooth 1e-7.  compile() without these arguments turns the Dice loss off."""
         self._need_softmax("compile")
-        if loss not in _LOSSES:
-            raise ValueError("loss must be 'categorical_crossentropy' (UT:427) or 'sparse_categorical_crossentropy', "
-                             "got %r" % (loss,))
+        if loss not in _LOSSES + (_DICE_LOSS,):
+            raise ValueError("loss must be 'categorical_crossentropy' (UT:427), 'sparse_categorical_crossentropy' or "
+                             "'dice_coef_loss' (UT:120), got %r" % (loss,))
+        dice = self._dice_args(loss, dice_loss, dice_weight, ce_weight, dice_smooth, dice_classes)
         was_on = self._class_weight is not None or self._ignore_label is not None
         self._class_weight, self._ignore_label = self._loss_weight_args(loss, class_weight, ignore_label)
+        if self._engine is not None and (self._dice is not None or dice is not None):
+            self._engine.set_dice_loss(**(dice or {"form": None}))
+        self._dice = dice
         if self._engine is not None and (was_on or self._class_weight is not None or self._ignore_label is not None):
             self._engine.set_loss_weights(self._class_weight, self._ignore_label)
         if metrics is not None:

@@ -246,6 +246,52 @@ int depgan_uresnet_set_loss_weights(depgan_ctx* ctx, const float* w_host, int n,
 int depgan_uresnet_get_loss_weights(depgan_ctx* ctx, float w_host[DEPGAN_MAX_HEAD_CLASSES], int* ignore_code);
 int depgan_uresnet_last_label_counts(depgan_ctx* ctx, long long out_host[DEPGAN_LABEL_NCOUNT], int* classes);
 
+/* The soft Dice loss of the supervised path, alone or added to the cross-entropy (the reference's dice_coef_loss,
+ * UT:110-121, and a per-class form).  With p the softmax probabilities AS STORED (not the renormalised, clipped q of the
+ * cross-entropy), t the label row (the one-hot row, or t[k] = (k == code) formed in registers), m = 1 for a pixel that
+ * takes part and 0 otherwise, s = smooth, over the pixels of the call:
+ *     I_k = sum_i m t_k p_k      P_k = sum_i m p_k      T_k = sum_i m t_k
+ *   DEPGAN_DICE_FLAT:   L = 1 - (2 sum_k I_k + s) / (sum_k T_k + sum_k P_k + s)
+ *   DEPGAN_DICE_CLASS:  L = sum_k c_k (1 - D_k),  D_k = (2 I_k + s) / (T_k + P_k + s),  class coefficients c_k >= 0
+ *     (c_k = 1/C: one minus the mean class Dice; c_0 = 0, c_k = 1/(C-1): the foreground Dice).
+ *   The loss of a call is ce_coef * CE + dice_coef * L, CE = what the context computes without this mode (the plain mean,
+ *   or the loss-weight mode's sum / den); the gradient is the same combination.
+ * Which pixels take part: with the loss-weight mode off, every pixel.  With it on, a pixel without a true class (the
+ *   ignore code, an all-zero one-hot row) has m = 0: it is in none of the sums and gets no Dice gradient.  A code >= nc_out
+ *   that is not the ignore code has m = 0 too; it is counted and the call refused as without this mode.  The class weights
+ *   of the loss-weight mode act on the cross-entropy alone.  No pixel takes part: L = 0.0 with a zero gradient, and
+ *   depgan_uresnet_step{,_sparse} applies NO Adam update and leaves the step counter alone (then the cross-entropy has
+ *   den == 0 as well).  A batch with den == 0 whose pixels of zero-weight classes take part in L is updated as usual.
+ * depgan_uresnet_set_dice_loss(ctx, form, ce_coef, dice_coef, smooth, class_coef_host, n): form = DEPGAN_DICE_OFF (the
+ *   default; the other arguments are not read) restores, bit for bit, what every entry computed before this mode existed.
+ *   Otherwise ce_coef finite and >= 0, dice_coef finite and > 0, smooth finite and > 0 (so no denominator is 0);
+ *   class_coef_host = NULL (1/nc_out each), or n == nc_out host values, finite and >= 0 with at least one > 0; it must
+ *   be NULL for the flat form.  Anything else is status 1 with a message, before any HIP call; status 3 on an inference
+ *   context, status 1 for nc_out = 1 (as depgan_uresnet_set_census).
+ * With the mode on all six depgan_uresnet_{grads,step,eval}{,_sparse} entries run, behind the cross-entropy kernel on the
+ *   same stream: a reduction pass over the stored probabilities and the labels (block partials, no atomics), a one-block
+ *   stage that adds the partials in index order in double and forms L and the per-class scalars of
+ *   dL/dp_k = m (A_k t_k + B_k) -- class form A_k = -2 c_k / Den_k, B_k = c_k Num_k / Den_k^2; flat form the same with the
+ *   global Num, Den and c_k = 1 -- and (grads, step) a pass that writes dz = ce_coef dz + dice_coef p_k (g_k - sum_j p_j g_j),
+ *   sums over k left to right.  With ce_coef == 0 that pass does not read dz.  *loss_host = ce_coef * CE + dice_coef * L,
+ *   formed on the host from the call's one copy; depgan_last_sums[0..1] keep the cross-entropy's sum and denominator.
+ *   The census is untouched.
+ * depgan_uresnet_get_dice_loss: returns the form (0 with the mode off) and, where the pointers are not NULL, the
+ *   coefficients, smooth and the nc_out class coefficients in use (for the flat form they are not written).
+ * depgan_uresnet_last_dice_sums: host only.  out_host = I_0..I_{C-1}, P_0..P_{C-1}, T_0..T_{C-1} (the first 3 C entries,
+ *   C = nc_out reported in *classes when not NULL) and *dice_loss = L of the last depgan_uresnet_* call made with the
+ *   mode on; they came back in the same copy and synchronisation as that call's loss.  Status 1 before any such call
+ *   and after the mode was set again. */
+#define DEPGAN_DICE_OFF 0
+#define DEPGAN_DICE_FLAT 1
+#define DEPGAN_DICE_CLASS 2
+int depgan_uresnet_set_dice_loss(depgan_ctx* ctx, int form, float ce_coef, float dice_coef, float smooth,
+                                 const float* class_coef_host, int n);
+int depgan_uresnet_get_dice_loss(depgan_ctx* ctx, float* ce_coef, float* dice_coef, float* smooth,
+                                 float class_coef_host[DEPGAN_MAX_HEAD_CLASSES]);
+int depgan_uresnet_last_dice_sums(depgan_ctx* ctx, double out_host[3 * DEPGAN_MAX_HEAD_CLASSES], int* classes,
+                                  float* dice_loss);
+
 /* Un-normalised pieces of the last critic / generator evaluation, for exact
  * data-parallel reporting: critic: [sum D(real), sum D(fake), sum (norm-1)^2, n];
  * generator: [sum D_y2(fake), sum D_dem(attr), sum |attr-real_dem|, sum wr, sum wf, sum wr*wf, n, n*H*W]. */
@@ -697,6 +743,17 @@ int depgan_op_softmax_ce_weighted(const float* logits, const float* onehot, cons
  * them.  Integers summed in two stages without atomics.  Synchronises the stream. */
 int depgan_op_label_counts(const float* onehot, const unsigned char* codes, long P, int C, int ignore_code,
                            long long* out_host, void* hip_stream);
+/* The soft Dice loss at operator level (depgan_uresnet_set_dice_loss states the rule): probs (P, C) fp32 device
+ * probabilities as depgan_op_softmax_ce stored them; labels onehot (P, C) fp32 or codes (P) unsigned char, exactly one
+ * of them.  ignore_code = -1: every pixel takes part; with codes the pixels of that code stay out (a code >= C always
+ * does, and is not counted here); with onehot and ignore_code >= 0 an all-zero row is the pixel that stays out.
+ * form, smooth, ce_coef, dice_coef and class_coef_host / n as depgan_uresnet_set_dice_loss takes them.  dz_inout (P, C)
+ * device: dz = ce_coef dz + dice_coef dL/dz; with ce_coef == 0 it is written without being read.  sums_host (host,
+ * 3 C doubles: I, P, T) and loss_host (host, the Dice term L) are required.  The entry allocates its own scratch and
+ * synchronises the stream.  A bad argument is status 1 before any HIP call. */
+int depgan_op_dice_loss(const float* probs, const float* onehot, const unsigned char* codes, int ignore_code, int form,
+                        const float* class_coef_host, int n, float smooth, float ce_coef, float dice_coef,
+                        float* dz_inout, double* sums_host, float* loss_host, long P, int C, void* hip_stream);
 /* BatchNorm over the R rows of an [R][ld] matrix (first C columns), moving statistics updated when given:
  * moving = momentum*moving + (1 - momentum)*(mean, var*corr) */
 int depgan_op_bn_rows_fwd(const float* x, float* y, int R, int C, int ld, const float* gamma, const float* beta,
