@@ -482,6 +482,193 @@ def balanced_class_weights(counts, rule="inverse"):
     return w
 
 
+# ---- training-time augmentation (depgan_data_augment, csrc/augment.hip) ----
+
+AUG_NPARAM = _lib._K["DEPGAN_AUG_NPARAM"]
+_BORDERS = {"edge": 0, "constant": 1}
+_ROT90 = np.array(((1.0, 0.0), (0.0, 1.0), (-1.0, 0.0), (0.0, -1.0)))   # (cos, sin) of 0, 90, 180, 270 degrees, exactly
+
+
+def _affine_rows(H, W, deg, s, dy, dx, flip_lr, flip_ud, gain, offset):
+    """affine_params for arrays of n values each: (n, 8) float32, composed in float64 and rounded once."""
+    q = np.floor(deg / 90.0)
+    exact = (deg == q * 90.0)[:, None]                # a multiple of 90 degrees: exact sines
+    rad = np.deg2rad(deg)
+    cs, sn = np.where(exact, _ROT90[q.astype(np.int64) % 4], np.stack([np.cos(rad), np.sin(rad)], 1)).T
+    fy, fx = np.where(flip_ud, -1.0, 1.0), np.where(flip_lr, -1.0, 1.0)
+    m00, m01, m10, m11 = fy * cs / s, fy * sn / s, -fx * sn / s, fx * cs / s
+    cy, cx = (H - 1) / 2.0, (W - 1) / 2.0
+    rows = np.stack([m00, m01, cy - m00 * (cy + dy) - m01 * (cx + dx),
+                     m10, m11, cx - m10 * (cy + dy) - m11 * (cx + dx), gain, offset], 1)
+    return (rows + 0.0).astype(np.float32)          # + 0.0: no negative zero among the coefficients
+
+
+def affine_params(H, W, rotate_deg=0.0, scale=1.0, shift=(0.0, 0.0), flip_lr=False, flip_ud=False, gain=1.0,
+                  offset=0.0):
+    """One parameter row of `augment`: a00 a01 a02 a10 a11 a12 gain offset (np.float32, 8 values), the map from an
+    output pixel (oy, ox) to its source coordinate sy = a00*oy + a01*ox + a02, sx = a10*oy + a11*ox + a12, taken about
+    the image centre ((H-1)/2, (W-1)/2).  The picture turns by rotate_deg counter-clockwise as displayed (90 on a
+    square image is np.rot90), grows by `scale`, moves by shift = (rows down, columns right) and is mirrored left-right
+    / up-down; gain and offset act on the intensities, out = gain*v + offset.  Composed in float64 and rounded once to
+    float32; a multiple of 90 degrees uses exact sines, and with all defaults the row is exactly [1,0,0,0,1,0,1,0]."""
+    H, W = int(H), int(W)
+    if H < 1 or W < 1:
+        raise ValueError("affine_params: H and W must be >= 1, got %r x %r" % (H, W))
+    vals = np.array([[float(v)] for v in (rotate_deg, scale, shift[0], shift[1], gain, offset)], np.float64)
+    if not np.all(np.isfinite(vals)) or vals[1, 0] <= 0:
+        raise ValueError("affine_params: arguments must be finite and scale > 0")
+    deg, s, dy, dx, gain, offset = vals
+    return _affine_rows(H, W, deg, s, dy, dx, np.array([bool(flip_lr)]), np.array([bool(flip_ud)]), gain, offset)[0]
+
+
+def _aug_labels(labels, n_src, H, W, dev):
+    """labels of `augment` -> (contiguous device tensor or None, lab_kind, C, shape of one output sample)."""
+    import torch
+    if labels is None:
+        return None, 0, 0, None
+    shape = tuple(int(d) for d in labels.shape) if hasattr(labels, "shape") else np.shape(labels)
+    if shape in ((n_src, H, W), (n_src, H, W, 1)):
+        tens = isinstance(labels, torch.Tensor)
+        a = labels if tens else np.asarray(labels)
+        u8 = torch.uint8 if tens else np.uint8
+        if a.dtype != u8:
+            from .engine import require_class_indices
+            a = require_class_indices(a)
+            if a.dtype != (torch.bool if tens else np.bool_) and bool(((a < 0) | (a > 255)).any()):
+                raise ValueError("augment: class codes must lie in [0, 255]")
+            a = a.to(u8) if tens else a.astype(u8)
+        t = (a if tens else torch.from_numpy(np.ascontiguousarray(a))).to(dev).contiguous()
+        return t, 1, 0, shape[1:]
+    if len(shape) == 4 and shape[:3] == (n_src, H, W) and 2 <= shape[3] <= _lib.MAX_HEAD_CLASSES:
+        if isinstance(labels, torch.Tensor):
+            t = labels.to(device=dev, dtype=torch.float32).contiguous()
+        else:
+            t = torch.from_numpy(np.ascontiguousarray(np.asarray(labels), dtype=np.float32)).to(dev)
+        return t, 2, shape[3], shape[1:]
+    raise ValueError("augment: labels must be class codes (%d, %d, %d[, 1]) or one-hot (%d, %d, %d, 2..%d), got shape %s"
+                     % (n_src, H, W, n_src, H, W, _lib.MAX_HEAD_CLASSES, shape))
+
+
+def augment(x, labels=None, params=None, index=None, border="edge", x_fill=0.0, label_fill=0, device=None,
+            stream=None):
+    """The batch gather, an affine warp and an intensity change in one launch (depgan_data_augment).
+    x: (n_src, H, W, nicg) float32 images, nicg 1 or 2; labels: None, class codes (n_src, H, W) or (n_src, H, W, 1)
+    (uint8, or integral values in [0, 255] of another dtype), or one-hot (n_src, H, W, C) float32; NumPy arrays or
+    tensors (a tensor on the device is read where it is).  params: (n, 8) float32 rows of `affine_params`, one per
+    output sample, or a single row for all of them.  index: the n source slices, output sample i is made from
+    x[index[i]] (None: from x[i]); a host index outside [0, n_src) is a ValueError, a device index is not read back
+    (an entry outside the range gives a sample of the fill values).  Images are sampled bilinearly, labels by the
+    nearest pixel, so a label row is always a copy of a source row.  border 'edge' repeats the edge pixels; 'constant'
+    puts x_fill and label_fill outside the image (one-hot: the row with 1.0 at label_fill, all zeros when
+    label_fill < 0 -- the ignored pixel of compile(class_weight=...)).  Returns new device tensors (x_out, labels_out)
+    of n samples; labels_out is None without labels.  Every value is bit for bit what the float32 formula of
+    include/depgan.h gives in NumPy (tests/augment_ref.py)."""
+    import torch
+    lib = _lib.load()
+    if border not in _BORDERS:
+        raise ValueError("augment: border must be 'edge' or 'constant', got %r" % (border,))
+    shape = tuple(int(d) for d in (x.shape if hasattr(x, "shape") else np.shape(x)))
+    if len(shape) != 4 or min(shape) < 1 or shape[3] not in (1, 2):
+        raise ValueError("augment: images must be (n_src, H, W, 1 or 2), got shape %s" % (shape,))
+    n_src, H, W, nicg = shape
+    if isinstance(x, torch.Tensor):
+        dev = x.device if device is None and x.is_cuda else torch.device(device or "cuda:0")
+        xs = x.to(device=dev, dtype=torch.float32).contiguous()
+    else:
+        dev = torch.device(device if device is not None else "cuda:0")
+        xs = torch.from_numpy(np.ascontiguousarray(np.asarray(x), dtype=np.float32)).to(dev)
+    ls, kind, Cc, lshape = _aug_labels(labels, n_src, H, W, dev)
+    if isinstance(label_fill, bool) or not isinstance(label_fill, (int, np.integer)):
+        raise ValueError("augment: label_fill must be an integer, got %r" % (label_fill,))
+    if (kind == 1 and not 0 <= label_fill <= 255) or (kind == 2 and label_fill >= Cc):
+        raise ValueError("augment: label_fill = %d does not fit the labels" % label_fill)
+    idx = None
+    if index is not None:
+        if isinstance(index, torch.Tensor) and index.is_cuda:
+            idx = index.to(device=dev, dtype=torch.int64).reshape(-1).contiguous()
+        else:
+            h = np.asarray(index.numpy() if isinstance(index, torch.Tensor) else index)
+            if h.ndim != 1 or h.dtype.kind not in "iu":
+                raise ValueError("augment: index must be a 1-D integer array")
+            if h.size and (int(h.min()) < 0 or int(h.max()) >= n_src):
+                raise ValueError("augment: index outside [0, %d)" % n_src)
+            idx = torch.from_numpy(np.ascontiguousarray(h, dtype=np.int64)).to(dev)
+    n = n_src if idx is None else int(idx.numel())
+    if n < 1:
+        raise ValueError("augment: no output samples")
+    if params is None:
+        params = affine_params(H, W)
+    if isinstance(params, torch.Tensor):
+        ps = params.to(device=dev, dtype=torch.float32)
+    else:
+        ps = torch.from_numpy(np.ascontiguousarray(np.asarray(params), dtype=np.float32)).to(dev)
+    if tuple(ps.shape) == (AUG_NPARAM,):
+        ps = ps.reshape(1, AUG_NPARAM).expand(n, AUG_NPARAM)
+    if tuple(ps.shape) != (n, AUG_NPARAM):
+        raise ValueError("augment: params must be (%d, %d) or (%d,), got shape %s" % (n, AUG_NPARAM, AUG_NPARAM,
+                                                                                   tuple(ps.shape)))
+    ps = ps.contiguous()
+    x_out = torch.empty((n, H, W, nicg), dtype=torch.float32, device=dev)
+    l_out = None if kind == 0 else torch.empty((n,) + tuple(lshape), dtype=ls.dtype, device=dev)
+    _lib.check(lib.depgan_data_augment(_p(xs), nicg, _p(ls), kind, Cc, _p(idx), n_src, _p(ps), n, H, W,
+                                       _BORDERS[border], float(x_fill), int(label_fill), _p(x_out), _p(l_out),
+                                       _stream(dev, stream)), "depgan_data_augment")
+    return x_out, l_out
+
+
+class Augmenter:
+    """Random affine and intensity augmentation of training batches, drawn per sample and applied by `augment`.
+    rotate: degrees, uniform in +-rotate.  scale: (low, high), uniform.  shift: pixels, uniform in +-shift on both axes.
+    flip_lr / flip_ud: mirror with probability 1/2.  gain, offset: (low, high), uniform; out = gain*v + offset.
+    border, x_fill, label_fill: as in `augment`; with compile(ignore_label=k), border='constant' and label_fill=k keep
+    the pixels a warp brings in from outside the image out of the loss.  seed: of the instance's own
+    np.random.default_rng -- np.random is never touched, so the shuffle of fit is what it is without augmentation.
+    GeneratorModel.fit(..., augment=Augmenter(...)) uses it; a hand-written loop calls it: xb, lb = aug(x, labels, idx)."""
+
+    def __init__(self, rotate=0.0, scale=(1.0, 1.0), shift=0.0, flip_lr=False, flip_ud=False, gain=(1.0, 1.0),
+                 offset=(0.0, 0.0), border="edge", x_fill=0.0, label_fill=0, seed=None):
+        def pair(v, name, positive=False):
+            lo, hi = (float(v[0]), float(v[1])) if np.ndim(v) == 1 and len(v) == 2 else (np.nan, np.nan)
+            if not (np.isfinite(lo) and np.isfinite(hi) and lo <= hi) or (positive and lo <= 0):
+                raise ValueError("Augmenter: %s must be a finite (low, high) pair%s, got %r"
+                                 % (name, " above 0" if positive else "", v))
+            return lo, hi
+        self.rotate, self.shift = float(rotate), float(shift)
+        if not (np.isfinite(self.rotate) and self.rotate >= 0 and np.isfinite(self.shift) and self.shift >= 0):
+            raise ValueError("Augmenter: rotate and shift must be finite and >= 0")
+        self.scale, self.gain, self.offset = pair(scale, "scale", True), pair(gain, "gain"), pair(offset, "offset")
+        self.flip_lr, self.flip_ud = bool(flip_lr), bool(flip_ud)
+        if border not in _BORDERS:
+            raise ValueError("Augmenter: border must be 'edge' or 'constant', got %r" % (border,))
+        self.border, self.x_fill, self.label_fill = border, float(x_fill), label_fill
+        self.rng = np.random.default_rng(seed)
+
+    @property
+    def identity(self):
+        """True when no range can move anything: every draw is the identity row."""
+        return (self.rotate == 0 and self.shift == 0 and self.scale == (1.0, 1.0) and self.gain == (1.0, 1.0)
+                and self.offset == (0.0, 0.0) and not self.flip_lr and not self.flip_ud)
+
+    def draw(self, n, H, W):
+        """(n, 8) float32 parameter rows for n samples of H x W pixels.  Every quantity is drawn for every call, in a
+        fixed order, so the stream of a seed does not depend on which ranges are open."""
+        n = int(n)
+        r = self.rng
+        rot = r.uniform(-self.rotate, self.rotate, n)
+        sc = r.uniform(self.scale[0], self.scale[1], n)
+        dy, dx = r.uniform(-self.shift, self.shift, n), r.uniform(-self.shift, self.shift, n)
+        lr, ud = r.random(n) < 0.5, r.random(n) < 0.5
+        g = r.uniform(self.gain[0], self.gain[1], n)
+        o = r.uniform(self.offset[0], self.offset[1], n)
+        return _affine_rows(int(H), int(W), rot, sc, dy, dx, lr & self.flip_lr, ud & self.flip_ud, g, o)
+
+    def __call__(self, x, labels=None, index=None, device=None):
+        """Draws one row per output sample and applies it: (x_out, labels_out) device tensors, as `augment`."""
+        n = int(x.shape[0]) if index is None else int(len(index))
+        return augment(x, labels, self.draw(n, int(x.shape[1]), int(x.shape[2])), index, self.border, self.x_fill,
+                       self.label_fill, device)
+
+
 def data_prep_save(image_data):
     """GT:121-127: (Z, X, Y, 1) network output -> the orientation the reference saves to NIfTI."""
     a = np.squeeze(np.asarray(image_data))

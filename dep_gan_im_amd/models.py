@@ -573,13 +573,22 @@ class GeneratorModel(_Model):
         return [loss] + self._metric_values(cm) if self._metrics else loss
 
     def fit(self, inputs, labels, epochs=1, batch_size=32, shuffle=True, validation_data=None, verbose=1,
-            print_fn=print):
+            print_fn=print, augment=None):
         """my_network.fit([flair, noise], onehot, epochs=1, batch_size=nb_samples, shuffle=..., validation_data=...)
         (UT:602-606).  Batches in index order (after an optional np.random shuffle, as keras does), a short last
         batch, per-epoch loss = sample-weighted mean of the batch losses; returns an object with .history.  With
         compile(metrics=[...]) each epoch also records every metric of the confusion matrix summed over its training
         batches and, with validation data, over that data (History.census keeps the tables; the progress line shows
-        them)."""
+        them).
+        augment: a data.Augmenter.  Every training batch is then made by one depgan_data_augment launch: a random affine
+        warp of the images (bilinear) and their labels (nearest), and a gain / offset on the intensities, drawn per
+        sample from the Augmenter's own generator (np.random, and with it the shuffle, is not touched).  When the
+        images (float32) and the labels (uint8 class codes, or float32 one-hot rows) are tensors on the engine's device,
+        the launch also does the batch gather: it reads the epoch's order[i:i+bs] as its index and x[idx] / labels[idx]
+        are never formed.  Otherwise the batch is sliced as without it, uploaded and augmented.  The noise is gathered
+        as before and validation data is never augmented.  With compile(ignore_label=k),
+        Augmenter(border='constant', label_fill=k) keeps the pixels a warp brings in from outside the image out of the
+        loss (one-hot labels: label_fill=-1, the all-zero row).  None (the default) leaves every batch as it was."""
         self._need_softmax("fit")
         x, z = inputs
         n = len(x)
@@ -596,6 +605,16 @@ class GeneratorModel(_Model):
             hist["val_loss"] = []
             hist.update(("val_" + name, []) for name in self._metrics)
         census = {"train": [], "val": []} if self._metrics else None
+        if augment is not None:
+            import torch
+            from .data import Augmenter
+            if not isinstance(augment, Augmenter):
+                raise TypeError("fit: augment must be a data.Augmenter or None, got %r" % (augment,))
+            # resident: the launch gathers straight from the set, no x[idx] / labels[idx] copy in front of it
+            resident = (isinstance(x, torch.Tensor) and isinstance(labels, torch.Tensor) and x.device == eng.device
+                        and labels.device == eng.device and x.dtype == torch.float32
+                        and labels.dtype == (torch.uint8 if self._loss == "sparse_categorical_crossentropy"
+                                             else torch.float32))
         for ep in range(epochs):
             order = np.arange(n)
             if shuffle:
@@ -603,7 +622,13 @@ class GeneratorModel(_Model):
             tot, cm = 0.0, None
             for i in range(0, n, bs):
                 idx = order[i:i + bs]
-                tot += len(idx) * eng.uresnet(x[idx], z[idx], labels[idx], "step", self._next_drop_seed())
+                if augment is None:
+                    xb, lb = x[idx], labels[idx]
+                elif resident:
+                    xb, lb = augment(x, labels, idx, device=eng.device)
+                else:
+                    xb, lb = augment(x[idx], labels[idx], device=eng.device)
+                tot += len(idx) * eng.uresnet(xb, z[idx], lb, "step", self._next_drop_seed())
                 if self._metrics:
                     cm = eng.uresnet_census() if cm is None else cm + eng.uresnet_census()
             hist["loss"].append(tot / n)

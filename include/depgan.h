@@ -374,6 +374,34 @@ int depgan_data_prep_zscore(const float* f1_dev, const float* icv1_dev, const fl
 int depgan_data_mask_slices(const float* vol_dev, const float* m_a_dev, const float* sl_dev, int X, int Y, int Z,
                             float* out_dev, void* stream);
 int depgan_labels_to_onehot(const float* coded_dev, long npix, int C, float* onehot_out_dev, void* stream);
+
+/* ---- training-time augmentation of a resident slice set: the batch gather, an affine warp and an intensity change in
+ * one launch (csrc/augment.hip).  Stateless; device pointers; enqueued on `stream`.
+ *   x_src (n_src, H, W, nicg) float32, nicg 1..2.  lab_kind 0: no labels (lab_src / lab_out are not read);
+ *   1: class codes, uint8 (n_src, H, W);  2: one-hot float32 (n_src, H, W, C), C = 2..DEPGAN_MAX_HEAD_CLASSES.
+ *   index_dev[i] (n longs) is the source slice of output sample i; NULL means i (then n_src >= n).  A value outside
+ *   [0, n_src) gives a sample made of the fill values alone (x_fill as it is, no gain / offset; the label fill below)
+ *   and reads nothing of the sources.
+ *   params_dev (n, DEPGAN_AUG_NPARAM) float32, row i = a00 a01 a02 a10 a11 a12 gain offset.  For output pixel (oy, ox):
+ *     sy = (a00*oy + a01*ox) + a02          sx = (a10*oy + a11*ox) + a12
+ *     y0 = floorf(sy); fy = sy - y0         x0 = floorf(sx); fx = sx - x0
+ *     top = v(y0,x0)*(1-fx) + v(y0,x0+1)*fx       bot = v(y0+1,x0)*(1-fx) + v(y0+1,x0+1)*fx
+ *     out = gain*(top*(1-fy) + bot*fy) + offset                            per channel
+ *     label: row (floorf(sy+0.5f), floorf(sx+0.5f)) of the source labels, copied bit for bit
+ *   every operation a single float32 operation in that order (y0+1 and x0+1 are float32 sums too), so a NumPy float32
+ *   restatement gives the same bits.  Any coordinate is accepted, +-inf and NaN included: a tap is compared with the
+ *   image and clamped into it before it becomes an index.
+ *   border 0 (edge): tap indices are clamped into the image.  border 1 (constant): an image tap outside the image is
+ *   x_fill (gain and offset then apply as for any pixel); a label outside it is label_fill for codes (0..255), and for
+ *   one-hot the row with 1.0 at label_fill (< C), or the all-zero row -- the ignored pixel of
+ *   depgan_uresnet_set_loss_weights -- when label_fill < 0.
+ *   Writes x_out (n, H, W, nicg) and lab_out (n, H, W) uint8 / (n, H, W, C) float32.  Status 1: n, H, W or n_src < 1,
+ *   nicg, lab_kind, border, C or label_fill outside the ranges above, a required pointer NULL, index_dev NULL with
+ *   n_src < n, or an output range that overlaps a source range or the other output.  H, W <= 2^24, H*W < 2^31. */
+#define DEPGAN_AUG_NPARAM 8
+int depgan_data_augment(const float* x_src, int nicg, const void* lab_src, int lab_kind, int C, const long* index_dev,
+                        long n_src, const float* params_dev, int n, int H, int W, int border, float x_fill,
+                        int label_fill, float* x_out, void* lab_out, void* stream);
 int depgan_eval_accumulate_channels(const float* pred_dev, const float* mask_dev, double* acc_dev, long npix, int C,
                                     void* stream);
 int depgan_eval_label_counts(const double* pred_dev, int C, const float* code_real_dev, const float* mask1_dev,
