@@ -215,6 +215,10 @@ struct depgan_ctx {
   float lw_w[DEPGAN_MAX_HEAD_CLASSES];
   int lw_ignore = -1;
   long long lw_counts[DEPGAN_LABEL_NCOUNT];
+  // depgan_uresnet_set_focal: the focal mode (off by default: both 0).  With it on the cross-entropy runs the weighted
+  // path -- lw_w / lw_ignore when lw_on, else unit weights and no ignore code -- and lw_counts / lw_valid are filled
+  bool focal_on = false;
+  float focal_gamma = 0.f, focal_eps = 0.f;
   // depgan_uresnet_set_dice_loss: the soft Dice loss (DEPGAN_DICE_OFF by default).  dice_c: the nc_out class coefficients
   // of the class form; dice_sums / dice_last: I_k, P_k, T_k (3 nc_out, packed) and the Dice term of the last call made
   // with the mode on, which came back with that call's loss

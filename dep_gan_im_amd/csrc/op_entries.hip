@@ -519,14 +519,12 @@ int depgan_op_softmax_ce_census(const float* logits, const float* onehot, const 
   }
   return DG_OK;
 }
-int depgan_op_softmax_ce_weighted(const float* logits, const float* onehot, const unsigned char* codes,
-                                  const float* w_host, int n, int ignore_code, float* probs, float* dz, float* loss_sum,
-                                  long long* census_host, long long* counts_host, long P, int C, void* stream) {
-  if (!w_host || !counts_host) { dg_set_error("op_softmax_ce_weighted: null w_host or counts_host"); return DG_ERR_ARG; }
-  if (!onehot && !codes) { dg_set_error("op_softmax_ce_weighted: loss weights need labels (onehot or codes)"); return DG_ERR_ARG; }
-  DGCHECK(dg_loss_weights_check("op_softmax_ce_weighted", w_host, n, C, ignore_code));
-  DGCHECK(dg_softmax_ce_check(logits, onehot, codes, probs, dz, loss_sum, P, C));
-  hipStream_t st = (hipStream_t)stream;
+// depgan_op_softmax_ce_weighted and depgan_op_softmax_ce_focal behind their own refusals: focal null = the loss-weight
+// mode alone, else {gamma, label_smoothing}
+static int op_softmax_ce_weighted_run(const char* who, const float* logits, const float* onehot,
+                                      const unsigned char* codes, const float* w_host, int ignore_code,
+                                      const float* focal, float* probs, float* dz, float* loss_sum,
+                                      long long* census_host, long long* counts_host, long P, int C, hipStream_t st) {
   // the reduction scratch, then what comes back: the counter of out-of-range codes (padded to 8 bytes), the C*C census
   // and the C + 3 label counts
   const size_t cap = (dg_softmax_ce_weighted_scratch(P, C, census_host != nullptr) + 1) & ~(size_t)1;
@@ -536,24 +534,51 @@ int depgan_op_softmax_ce_weighted(const float* logits, const float* onehot, cons
     long long counts[DEPGAN_LABEL_NCOUNT];
   } h;
   DevTmp scratch(st);
-  DGCHECK(op_alloc(&scratch, cap + sizeof(h) / sizeof(float), "op_softmax_ce_weighted"));
+  DGCHECK(op_alloc(&scratch, cap + sizeof(h) / sizeof(float), who));
   unsigned* bad = reinterpret_cast<unsigned*>(scratch.as<float>() + cap);
   unsigned long long* cen = reinterpret_cast<unsigned long long*>(scratch.as<float>() + cap + 2);
   unsigned long long* cnt = cen + DEPGAN_MAX_HEAD_CLASSES * DEPGAN_MAX_HEAD_CLASSES;
-  DGCHECK(dg_softmax_ce_weighted(logits, onehot, codes, probs, dz, loss_sum, bad, census_host ? cen : nullptr, cnt, w_host,
-                                 ignore_code, P, C, scratch.as<float>(), cap, st));
+  if (focal)
+    DGCHECK(dg_softmax_ce_focal(logits, onehot, codes, probs, dz, loss_sum, bad, census_host ? cen : nullptr, cnt, w_host,
+                                ignore_code, focal[0], focal[1], P, C, scratch.as<float>(), cap, st));
+  else
+    DGCHECK(dg_softmax_ce_weighted(logits, onehot, codes, probs, dz, loss_sum, bad, census_host ? cen : nullptr, cnt,
+                                   w_host, ignore_code, P, C, scratch.as<float>(), cap, st));
   // the census region is written only with census_host: the part of h it covers is then not read
   if (hipMemcpyAsync(&h, bad, sizeof(h), hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) {
-    dg_set_error("op_softmax_ce_weighted: copy back failed");
+    dg_set_error("%s: copy back failed", who);
     return DG_ERR_HIP;
   }
   if (census_host) memcpy(census_host, h.census, (size_t)C * C * sizeof(long long));
   memcpy(counts_host, h.counts, (size_t)(C + 3) * sizeof(long long));
   if (h.bad) {
-    dg_set_error("op_softmax_ce_weighted: %u of %ld class codes are outside [0, %d)", h.bad, P, C);
+    dg_set_error("%s: %u of %ld class codes are outside [0, %d)", who, h.bad, P, C);
     return DG_ERR_ARG;
   }
   return DG_OK;
+}
+int depgan_op_softmax_ce_weighted(const float* logits, const float* onehot, const unsigned char* codes,
+                                  const float* w_host, int n, int ignore_code, float* probs, float* dz, float* loss_sum,
+                                  long long* census_host, long long* counts_host, long P, int C, void* stream) {
+  if (!w_host || !counts_host) { dg_set_error("op_softmax_ce_weighted: null w_host or counts_host"); return DG_ERR_ARG; }
+  if (!onehot && !codes) { dg_set_error("op_softmax_ce_weighted: loss weights need labels (onehot or codes)"); return DG_ERR_ARG; }
+  DGCHECK(dg_loss_weights_check("op_softmax_ce_weighted", w_host, n, C, ignore_code));
+  DGCHECK(dg_softmax_ce_check(logits, onehot, codes, probs, dz, loss_sum, P, C));
+  return op_softmax_ce_weighted_run("op_softmax_ce_weighted", logits, onehot, codes, w_host, ignore_code, nullptr, probs,
+                                    dz, loss_sum, census_host, counts_host, P, C, (hipStream_t)stream);
+}
+int depgan_op_softmax_ce_focal(const float* logits, const float* onehot, const unsigned char* codes, const float* w_host,
+                               int n, int ignore_code, float gamma, float label_smoothing, float* probs, float* dz,
+                               float* loss_sum, long long* census_host, long long* counts_host, long P, int C,
+                               void* stream) {
+  if (!counts_host) { dg_set_error("op_softmax_ce_focal: null counts_host"); return DG_ERR_ARG; }
+  if (!onehot && !codes) { dg_set_error("op_softmax_ce_focal: the focal loss needs labels (onehot or codes)"); return DG_ERR_ARG; }
+  DGCHECK(dg_focal_check("op_softmax_ce_focal", gamma, label_smoothing));
+  DGCHECK(dg_loss_weights_check("op_softmax_ce_focal", w_host, n, C, ignore_code));
+  DGCHECK(dg_softmax_ce_check(logits, onehot, codes, probs, dz, loss_sum, P, C));
+  const float focal[2] = {gamma, label_smoothing};
+  return op_softmax_ce_weighted_run("op_softmax_ce_focal", logits, onehot, codes, w_host, ignore_code, focal, probs, dz,
+                                    loss_sum, census_host, counts_host, P, C, (hipStream_t)stream);
 }
 int depgan_op_label_counts(const float* onehot, const unsigned char* codes, long P, int C, int ignore_code,
                            long long* out_host, void* stream) {

@@ -82,6 +82,17 @@ int dg_softmax_ce_weighted(const float* logits, const float* onehot, const unsig
                            float* loss_sum, unsigned* bad_count, unsigned long long* census,
                            unsigned long long* counts, const float* cw, int ignore_code, long P, int C, float* scratch,
                            size_t scratch_floats, hipStream_t st);
+// The focal mode (include/depgan.h, depgan_uresnet_set_focal, states the rule): dg_softmax_ce_weighted with the focal
+// cross-entropy and label smoothing in the same kernel text -- gamma finite and >= 0, label_smoothing in [0, 1)
+// (dg_focal_check validates both without a HIP call).  cw null: unit weights.  The pre-pass, den, the ignore code, the
+// census, the stored probabilities and the scratch (dg_softmax_ce_weighted_scratch) are the loss-weight mode's.  gamma =
+// 0 with label_smoothing = 0 is allowed here and runs the focal statements; a caller that wants the plain bits calls
+// dg_softmax_ce_weighted or dg_softmax_ce instead.
+int dg_focal_check(const char* who, float gamma, float label_smoothing);
+int dg_softmax_ce_focal(const float* logits, const float* onehot, const unsigned char* codes, float* probs, float* dz,
+                        float* loss_sum, unsigned* bad_count, unsigned long long* census, unsigned long long* counts,
+                        const float* cw, int ignore_code, float gamma, float label_smoothing, long P, int C,
+                        float* scratch, size_t scratch_floats, hipStream_t st);
 // its argument checks alone (no HIP call): what an entry asks before it allocates
 int dg_softmax_ce_check(const float* logits, const float* onehot, const unsigned char* codes, const float* probs,
                         const float* dz, const float* loss_sum, long P, int C);

@@ -473,7 +473,17 @@ int dg_axpby_ch(TView d, TView x, TView out, int B, int H, int W, int C, const f
 // instantiation computes (1 * t = t, and 1.0f / (float)den is the host's 1.0f / (float)P).  A pixel with t = 0 --
 // ignored, or of a zero-weight class -- has a dz row of zeros and still gets its probabilities.  CENSUS under WEIGHTED:
 // a pixel without a true class (the ignore code, an all-zero one-hot row) joins no bin.  The WEIGHTED = false
-// instantiations ignore wa, their last argument, and compile to the instructions they were.
+// instantiations ignore wa and compile to the instructions they were.
+//
+// FOCAL (with WEIGHTED only; dg_softmax_ce_focal): the focal cross-entropy with label smoothing of include/depgan.h
+// (depgan_uresnet_set_focal).  The label row stays unweighted until the pixel weight w = sum_k cw[k] t[k] (left to right,
+// the pre-pass's statement) and has = any t[k] != 0 are formed from it; then ts[k] = w ((1 - eps) t[k] + (has ? eps / C
+// : 0)) takes the row's place, the loss term is -ts[k] (1 - r)^gamma log r and dL/dq_k = -ts[k] (1/den) ((1 - r)^gamma / q
+// - gamma (1 - r)^(gamma - 1) log r) on the closed clip interval.  1 - r is formed directly (>= 2^-23 inside the clip);
+// the power is 1, 1 - r or (1 - r)^2 for gamma = 0, 1, 2 (a uniform branch: gamma is a kernel argument) and
+// exp2f(gamma log2f(1 - r)) otherwise, (1 - r)^(gamma - 1) the power over 1 - r.  Everything behind dL/dq, the census and
+// the stored probabilities are the text above.  The FOCAL = false instantiations read neither gamma nor eps, the last
+// two arguments, and compile to the instructions they were.
 enum { LBL_NONE = 0, LBL_ONEHOT = 1, LBL_CODES = 2 };
 
 // the loss-weight mode's kernel arguments, by value: C class weights (the rest 0), the ignore code (-1: none) and the
@@ -493,13 +503,32 @@ __device__ __forceinline__ unsigned t_block_sum_u(unsigned v, unsigned* shu4) {
   return (shu4[0] + shu4[1]) + (shu4[2] + shu4[3]);
 }
 
-template <int C, int LBL, bool CENSUS, bool WEIGHTED>
+// pw = x^gamma and pm1 = x^(gamma - 1) for x = 1 - r in [2^-23, 1) and gamma >= 0
+__device__ __forceinline__ void t_focal_pow(float x, float gamma, float& pw, float& pm1) {
+  if (gamma == 0.f) {
+    pw = 1.0f;
+    pm1 = 1.0f / x;     // multiplied by gamma = 0 where it is used
+  } else if (gamma == 1.0f) {
+    pw = x;
+    pm1 = 1.0f;
+  } else if (gamma == 2.0f) {
+    pw = x * x;
+    pm1 = x;
+  } else {
+    pw = exp2f(gamma * log2f(x));
+    pm1 = pw / x;
+  }
+}
+
+template <int C, int LBL, bool CENSUS, bool WEIGHTED, bool FOCAL>
 __global__ void softmax_ce_kernel(const float* __restrict__ logits, const float* __restrict__ onehot,
                                   const unsigned char* __restrict__ codes, float* __restrict__ probs,
                                   float* __restrict__ dz, float* __restrict__ part, unsigned* __restrict__ bad_part,
-                                  unsigned* __restrict__ cen_part, long P, float invN, SmWeights wa) {
+                                  unsigned* __restrict__ cen_part, long P, float invN, SmWeights wa, float gamma,
+                                  float eps) {
   static_assert(!CENSUS || LBL != LBL_NONE, "a census needs labels");
   static_assert(!WEIGHTED || LBL != LBL_NONE, "loss weights need labels");
+  static_assert(!FOCAL || WEIGHTED, "the focal mode runs the weighted path");
   if (WEIGHTED) {
     const unsigned long long den = *wa.den;
     invN = den ? 1.0f / (float)den : 0.f;
@@ -534,9 +563,18 @@ __global__ void softmax_ce_kernel(const float* __restrict__ logits, const float*
           nbad += (code >= C) ? 1u : 0u;
           if (CENSUS) tc = (code < C) ? code : -1;
         }
-        if (WEIGHTED) {
+        if (WEIGHTED && !FOCAL) {
 #pragma unroll
           for (int k = 0; k < C; ++k) t[k] = wa.cw[k] * t[k];
+        }
+        if (FOCAL) {
+          // ts = w ((1 - eps) t + (has ? eps / C : 0)): a row without a true class stays 0, a zero-weight class too
+          float w = 0.f;
+#pragma unroll
+          for (int k = 0; k < C; ++k) w += wa.cw[k] * t[k];
+          const float u = dg_row_any<C>(t) ? eps / (float)C : 0.f;
+#pragma unroll
+          for (int k = 0; k < C; ++k) t[k] = w * ((1.0f - eps) * t[k] + u);
         }
         const float S = dg_row_pairsum<C>(p);
         float gq[C];
@@ -545,10 +583,18 @@ __global__ void softmax_ce_kernel(const float* __restrict__ logits, const float*
         for (int k = 0; k < C; ++k) {
           const float q = p[k] / S;
           const float r = fminf(fmaxf(q, 1e-7f), 1.0f - 1e-7f);
-          lsum -= t[k] * logf(r);
           // clip's gradient passes on the closed interval, bounds included (TF clip_by_value, torch.clamp)
           const bool in = (q >= 1e-7f) && (q <= 1.0f - 1e-7f);
-          gq[k] = in ? (-t[k] * invN / q) : 0.f;    // dL/dq
+          if (FOCAL) {
+            const float lg = logf(r);
+            float pw, pm1;
+            t_focal_pow(1.0f - r, gamma, pw, pm1);
+            lsum -= t[k] * pw * lg;
+            gq[k] = in ? (-t[k] * invN * (pw / q - gamma * pm1 * lg)) : 0.f;
+          } else {
+            lsum -= t[k] * logf(r);
+            gq[k] = in ? (-t[k] * invN / q) : 0.f;    // dL/dq
+          }
           dot += gq[k] * p[k];
         }
         // q = p/S: dL/dp_j = gq_j/S - dot/S^2 ; softmax: dL/dz_k = p_k (dL/dp_k - sum_j p_j dL/dp_j)
@@ -628,23 +674,33 @@ __global__ void sum_small_kernel(const float* __restrict__ part, int nb, float* 
   }
 }
 
+// what the focal mode adds to the weighted launch, by value
+struct SmFocal {
+  float gamma, eps;
+};
+
 template <int C>
 static void softmax_ce_launch(int lbl, bool census, int nb, hipStream_t st, const float* logits, const float* onehot,
                               const unsigned char* codes, float* probs, float* dz, float* part, unsigned* bad_part,
-                              unsigned* cen_part, long P, float invN, const SmWeights* weights) {
+                              unsigned* cen_part, long P, float invN, const SmWeights* weights, const SmFocal* focal) {
   const SmWeights wa = weights ? *weights : SmWeights{};
-#define DG_SM_GO(LBL, CEN, WGT)                                                                                        \
-  hipLaunchKernelGGL((softmax_ce_kernel<C, LBL, CEN, WGT>), dim3(nb), dim3(256), 0, st, logits, onehot, codes, probs, dz, \
-                     part, bad_part, cen_part, P, invN, wa)
-  if (weights && lbl == LBL_ONEHOT && census) DG_SM_GO(LBL_ONEHOT, true, true);
-  else if (weights && lbl == LBL_CODES && census) DG_SM_GO(LBL_CODES, true, true);
-  else if (weights && lbl == LBL_ONEHOT) DG_SM_GO(LBL_ONEHOT, false, true);
-  else if (weights && lbl == LBL_CODES) DG_SM_GO(LBL_CODES, false, true);
-  else if (lbl == LBL_ONEHOT && census) DG_SM_GO(LBL_ONEHOT, true, false);
-  else if (lbl == LBL_CODES && census) DG_SM_GO(LBL_CODES, true, false);
-  else if (lbl == LBL_ONEHOT) DG_SM_GO(LBL_ONEHOT, false, false);
-  else if (lbl == LBL_CODES) DG_SM_GO(LBL_CODES, false, false);
-  else DG_SM_GO(LBL_NONE, false, false);
+  const SmFocal fa = focal ? *focal : SmFocal{0.f, 0.f};
+#define DG_SM_GO(LBL, CEN, WGT, FOC)                                                                                   \
+  hipLaunchKernelGGL((softmax_ce_kernel<C, LBL, CEN, WGT, FOC>), dim3(nb), dim3(256), 0, st, logits, onehot, codes, probs, \
+                     dz, part, bad_part, cen_part, P, invN, wa, fa.gamma, fa.eps)
+  if (focal && lbl == LBL_ONEHOT && census) DG_SM_GO(LBL_ONEHOT, true, true, true);
+  else if (focal && lbl == LBL_CODES && census) DG_SM_GO(LBL_CODES, true, true, true);
+  else if (focal && lbl == LBL_ONEHOT) DG_SM_GO(LBL_ONEHOT, false, true, true);
+  else if (focal && lbl == LBL_CODES) DG_SM_GO(LBL_CODES, false, true, true);
+  else if (weights && lbl == LBL_ONEHOT && census) DG_SM_GO(LBL_ONEHOT, true, true, false);
+  else if (weights && lbl == LBL_CODES && census) DG_SM_GO(LBL_CODES, true, true, false);
+  else if (weights && lbl == LBL_ONEHOT) DG_SM_GO(LBL_ONEHOT, false, true, false);
+  else if (weights && lbl == LBL_CODES) DG_SM_GO(LBL_CODES, false, true, false);
+  else if (lbl == LBL_ONEHOT && census) DG_SM_GO(LBL_ONEHOT, true, false, false);
+  else if (lbl == LBL_CODES && census) DG_SM_GO(LBL_CODES, true, false, false);
+  else if (lbl == LBL_ONEHOT) DG_SM_GO(LBL_ONEHOT, false, false, false);
+  else if (lbl == LBL_CODES) DG_SM_GO(LBL_CODES, false, false, false);
+  else DG_SM_GO(LBL_NONE, false, false, false);
 #undef DG_SM_GO
 }
 
@@ -667,10 +723,11 @@ int dg_softmax_ce_check(const float* logits, const float* onehot, const unsigned
 }
 
 // census: null, or C*C device counts; the block tables then follow the 2048 floats of the other partials.  weights:
-// null, or the loss-weight mode's arguments (weights->den already holds the count when this launch runs)
+// null, or the loss-weight mode's arguments (weights->den already holds the count when this launch runs).  focal: null,
+// or the focal mode's two floats (with weights only)
 static int softmax_ce_run(const float* logits, const float* onehot, const unsigned char* codes, float* probs, float* dz,
                           float* loss_sum, unsigned* bad_count, unsigned long long* census, long P, int C, float* scratch,
-                          hipStream_t st, const SmWeights* weights = nullptr) {
+                          hipStream_t st, const SmWeights* weights = nullptr, const SmFocal* focal = nullptr) {
   const int lbl = onehot ? LBL_ONEHOT : (codes ? LBL_CODES : LBL_NONE);
   if (lbl != LBL_NONE && !scratch) { dg_set_error("dg_softmax_ce: labels without scratch"); return DG_ERR_ARG; }
   if (lbl == LBL_CODES && !bad_count) { dg_set_error("dg_softmax_ce: class codes without a counter"); return DG_ERR_ARG; }
@@ -680,7 +737,7 @@ static int softmax_ce_run(const float* logits, const float* onehot, const unsign
   unsigned* cen_part = census ? reinterpret_cast<unsigned*>(scratch + 2048) : nullptr;
   const float invN = (lbl == LBL_NONE) ? 0.f : 1.0f / (float)P;
   switch (C) {
-#define DG_SM(N) case N: softmax_ce_launch<N>(lbl, census != nullptr, nb, st, logits, onehot, codes, probs, dz, part, bad_part, cen_part, P, invN, weights); break;
+#define DG_SM(N) case N: softmax_ce_launch<N>(lbl, census != nullptr, nb, st, logits, onehot, codes, probs, dz, part, bad_part, cen_part, P, invN, weights, focal); break;
     DG_SM(2) DG_SM(3) DG_SM(4) DG_SM(5) DG_SM(6) DG_SM(7) DG_SM(8)
 #undef DG_SM
   }
@@ -868,26 +925,58 @@ size_t dg_softmax_ce_weighted_scratch(long P, int C, bool census) {
   return a > b ? a : b;
 }
 
-int dg_softmax_ce_weighted(const float* logits, const float* onehot, const unsigned char* codes, float* probs, float* dz,
-                           float* loss_sum, unsigned* bad_count, unsigned long long* census,
-                           unsigned long long* counts, const float* cw, int ignore_code, long P, int C, float* scratch,
-                           size_t scratch_floats, hipStream_t st) {
-  DGCHECK(dg_loss_weights_check("dg_softmax_ce_weighted", cw, C, C, ignore_code));
+// the weighted and the focal entry: one set of checks, one pre-pass, one launch (focal null: the loss-weight mode alone)
+static int softmax_ce_weighted_run(const char* who, const float* logits, const float* onehot, const unsigned char* codes,
+                                   float* probs, float* dz, float* loss_sum, unsigned* bad_count,
+                                   unsigned long long* census, unsigned long long* counts, const float* cw,
+                                   int ignore_code, const SmFocal* focal, long P, int C, float* scratch,
+                                   size_t scratch_floats, hipStream_t st) {
+  DGCHECK(dg_loss_weights_check(who, cw, C, C, ignore_code));
   DGCHECK(dg_softmax_ce_check(logits, onehot, codes, probs, dz, loss_sum, P, C));
-  if (!onehot && !codes) { dg_set_error("dg_softmax_ce_weighted: loss weights need labels"); return DG_ERR_ARG; }
-  if (census && ((uintptr_t)census & 7)) { dg_set_error("dg_softmax_ce_weighted: misaligned census"); return DG_ERR_ARG; }
-  if (!bad_count) { dg_set_error("dg_softmax_ce_weighted: no counter of out-of-range codes"); return DG_ERR_ARG; }
+  if (!onehot && !codes) { dg_set_error("%s: loss weights need labels", who); return DG_ERR_ARG; }
+  if (census && ((uintptr_t)census & 7)) { dg_set_error("%s: misaligned census", who); return DG_ERR_ARG; }
+  if (!bad_count) { dg_set_error("%s: no counter of out-of-range codes", who); return DG_ERR_ARG; }
   const size_t need = dg_softmax_ce_weighted_scratch(P, C, census != nullptr);
   if (!scratch || scratch_floats < need) {
-    dg_set_error("dg_softmax_ce_weighted: scratch of %zu floats, the launches need %zu", scratch ? scratch_floats : (size_t)0, need);
+    dg_set_error("%s: scratch of %zu floats, the launches need %zu", who, scratch ? scratch_floats : (size_t)0, need);
     return DG_ERR_ARG;
   }
-  DGCHECK(label_counts_check("dg_softmax_ce_weighted", onehot, codes, P, C, counts, scratch, scratch_floats));
+  DGCHECK(label_counts_check(who, onehot, codes, P, C, counts, scratch, scratch_floats));
   const SmWeights wa = sm_weights(cw, C, ignore_code, counts);
   // the label pass's partials and the cross-entropy pass's share the scratch: the second stage of the first has read them
   // before the second pass, behind it on the stream, writes
   DGCHECK(label_counts_run(onehot, codes, P, C, wa, counts, scratch, st));
-  return softmax_ce_run(logits, onehot, codes, probs, dz, loss_sum, bad_count, census, P, C, scratch, st, &wa);
+  return softmax_ce_run(logits, onehot, codes, probs, dz, loss_sum, bad_count, census, P, C, scratch, st, &wa, focal);
+}
+
+int dg_softmax_ce_weighted(const float* logits, const float* onehot, const unsigned char* codes, float* probs, float* dz,
+                           float* loss_sum, unsigned* bad_count, unsigned long long* census,
+                           unsigned long long* counts, const float* cw, int ignore_code, long P, int C, float* scratch,
+                           size_t scratch_floats, hipStream_t st) {
+  return softmax_ce_weighted_run("dg_softmax_ce_weighted", logits, onehot, codes, probs, dz, loss_sum, bad_count, census,
+                                 counts, cw, ignore_code, nullptr, P, C, scratch, scratch_floats, st);
+}
+
+int dg_focal_check(const char* who, float gamma, float label_smoothing) {
+  if (!(gamma >= 0.f) || gamma > FLT_MAX) {
+    dg_set_error("%s: focal gamma %g (finite and >= 0)", who, (double)gamma);
+    return DG_ERR_ARG;
+  }
+  if (!(label_smoothing >= 0.f) || !(label_smoothing < 1.0f)) {
+    dg_set_error("%s: label smoothing %g (in [0, 1))", who, (double)label_smoothing);
+    return DG_ERR_ARG;
+  }
+  return DG_OK;
+}
+
+int dg_softmax_ce_focal(const float* logits, const float* onehot, const unsigned char* codes, float* probs, float* dz,
+                        float* loss_sum, unsigned* bad_count, unsigned long long* census, unsigned long long* counts,
+                        const float* cw, int ignore_code, float gamma, float label_smoothing, long P, int C,
+                        float* scratch, size_t scratch_floats, hipStream_t st) {
+  DGCHECK(dg_focal_check("dg_softmax_ce_focal", gamma, label_smoothing));
+  const SmFocal fa{gamma, label_smoothing};
+  return softmax_ce_weighted_run("dg_softmax_ce_focal", logits, onehot, codes, probs, dz, loss_sum, bad_count, census,
+                                 counts, cw, ignore_code, &fa, P, C, scratch, scratch_floats, st);
 }
 
 // ---------------------------------------------------------------------------

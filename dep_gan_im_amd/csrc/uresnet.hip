@@ -347,10 +347,17 @@ struct ULabels {
 
 // loss_dev[0] = summed loss, loss_dev[1] = the count of class codes outside [0, nc_out) as an unsigned; with the census
 // on (depgan_uresnet_set_census) the nc_out x nc_out table of the same pass follows as 64-bit counts.  In the
-// loss-weight mode the label pre-pass runs first and leaves its counts, den first, behind the census
+// loss-weight mode and in the focal mode the label pre-pass runs first and leaves its counts, den first, behind the census
 static int u_softmax_ce_only(depgan_ctx* c, ULabels lab, long P) {
   ProfScope ps(c, 2, 0.0, "softmax + cross-entropy");
   unsigned* bad = reinterpret_cast<unsigned*>(c->loss_dev + 1);
+  // the focal mode runs the weighted path: the loss-weight mode's weights and ignore code, or unit weights and none
+  if (c->focal_on)
+    return dg_softmax_ce_focal(c->logits, lab.onehot, lab.codes, c->attr.p, c->dz, c->loss_dev, bad,
+                               c->census ? reinterpret_cast<unsigned long long*>(c->loss_dev + 2) : nullptr,
+                               reinterpret_cast<unsigned long long*>(c->loss_dev + offsetof(ULossHost, counts) / sizeof(float)),
+                               c->lw_on ? c->lw_w : nullptr, (c->lw_on && lab.codes) ? c->lw_ignore : -1, c->focal_gamma,
+                               c->focal_eps, P, c->cfg.nc_out, c->scratch, c->scratchFloats, c->st);
   if (c->lw_on)
     return dg_softmax_ce_weighted(c->logits, lab.onehot, lab.codes, c->attr.p, c->dz, c->loss_dev, bad,
                                   c->census ? reinterpret_cast<unsigned long long*>(c->loss_dev + 2) : nullptr,
@@ -390,8 +397,9 @@ static int u_loss_to_host(depgan_ctx* c, const char* who, long P, float* loss_ho
   // the loss-weight mode: the label counts sit behind the largest census, the copy takes everything up to them
   // the Dice mode: its sums and its loss sit behind the label counts, the copy takes everything up to them
   const bool dice = c->dice_form != DEPGAN_DICE_OFF;
+  const bool weighted = c->lw_on || c->focal_on;   // the weighted path ran: the loss-weight mode or the focal mode
   const size_t bytes = dice      ? offsetof(ULossHost, dice) + offsetof(DgDiceDev, A)
-                       : c->lw_on ? offsetof(ULossHost, counts) + (size_t)(c->cfg.nc_out + 3) * sizeof(long long)
+                       : weighted ? offsetof(ULossHost, counts) + (size_t)(c->cfg.nc_out + 3) * sizeof(long long)
                                   : 2 * sizeof(float) + ncen * sizeof(long long);
   HIPCHECK(hipMemcpyAsync(&h, c->loss_dev, bytes, hipMemcpyDeviceToHost, c->st));
   HIPCHECK(hipStreamSynchronize(c->st));
@@ -400,9 +408,9 @@ static int u_loss_to_host(depgan_ctx* c, const char* who, long P, float* loss_ho
     memcpy(c->last_census, h.census, ncen * sizeof(long long));
     c->census_valid = true;
   }
-  // the mean's denominator: every pixel, or in the loss-weight mode the pixels with a non-zero weight (0.0 for none)
+  // the mean's denominator: every pixel, or on the weighted path the pixels with a non-zero weight (0.0 for none)
   float den = (float)P;
-  if (c->lw_on) {
+  if (weighted) {
     memcpy(c->lw_counts, h.counts, (size_t)(c->cfg.nc_out + 3) * sizeof(long long));
     c->lw_valid = true;
     den = (float)(unsigned long long)h.counts[0];
@@ -453,12 +461,12 @@ static int u_step(depgan_ctx* c, const char* who, const float* x, const float* z
   // an out-of-range class code comes back here as status 1, after the loss fetch: no Adam update, the step counter
   // stays; the phase-1 forward has moved the BN moving statistics by then, as depgan_uresnet_grads always does
   DGCHECK(u_grads(c, who, x, z, lab, n, drop_seed, loss_host, false));
-  // the loss-weight mode with no weighted pixel in the batch: loss 0.0 and an all-zero dz, status 0; no Adam update and
+  // the loss-weight mode or the focal mode with no weighted pixel in the batch: loss 0.0 and an all-zero dz, status 0; no Adam update and
   // the step counter stays, the path of a refused sparse step (the moving statistics have moved)
   // With the Dice mode on the same holds once no pixel takes part in the Dice term either: every pixel is without a true
   // class (then den == 0 too); pixels of zero-weight classes still carry a Dice gradient, and that batch is updated
   const long P = (long)n * c->cfg.height * c->cfg.width;
-  const bool ce_empty = c->lw_on && c->lw_counts[0] == 0;
+  const bool ce_empty = (c->lw_on || c->focal_on) && c->lw_counts[0] == 0;
   const bool dice_empty = c->lw_on && c->lw_counts[1] + c->lw_counts[2] == P;
   if (c->dice_form == DEPGAN_DICE_OFF ? ce_empty : dice_empty) return refresh_generator_bn(c);
   return depgan_apply_adam(c, DEPGAN_NET_G);
@@ -524,14 +532,35 @@ int depgan_uresnet_get_loss_weights(depgan_ctx* c, float w_host[DEPGAN_MAX_HEAD_
 }
 int depgan_uresnet_last_label_counts(depgan_ctx* c, long long out_host[DEPGAN_LABEL_NCOUNT], int* classes) {
   if (!c || !out_host) { dg_set_error("depgan_uresnet_last_label_counts: null argument"); return DG_ERR_ARG; }
-  if (!c->lw_on || !c->lw_valid) {
+  if (!(c->lw_on || c->focal_on) || !c->lw_valid) {
     dg_set_error("depgan_uresnet_last_label_counts: no depgan_uresnet_* call has run in the loss-weight mode "
-                 "(depgan_uresnet_set_loss_weights)");
+                 "(depgan_uresnet_set_loss_weights) or the focal mode (depgan_uresnet_set_focal)");
     return DG_ERR_ARG;
   }
   memcpy(out_host, c->lw_counts, (size_t)(c->cfg.nc_out + 3) * sizeof(long long));
   if (classes) *classes = c->cfg.nc_out;
   return DG_OK;
+}
+
+int depgan_uresnet_set_focal(depgan_ctx* c, float gamma, float label_smoothing) {
+  if (!c) { dg_set_error("depgan_uresnet_set_focal: null context"); return DG_ERR_ARG; }
+  DGCHECK(dg_focal_check("depgan_uresnet_set_focal", gamma, label_smoothing));
+  const bool on = gamma != 0.f || label_smoothing != 0.f;
+  if (on) {
+    DGCHECK(u_check(c, "depgan_uresnet_set_focal"));
+  }
+  c->focal_on = on;
+  c->focal_gamma = on ? gamma : 0.f;
+  c->focal_eps = on ? label_smoothing : 0.f;
+  // the counts on the host are those of a call made under the setting in force
+  c->lw_valid = false;
+  return DG_OK;
+}
+int depgan_uresnet_get_focal(depgan_ctx* c, float* gamma, float* label_smoothing) {
+  if (!c || !c->focal_on) return 0;
+  if (gamma) *gamma = c->focal_gamma;
+  if (label_smoothing) *label_smoothing = c->focal_eps;
+  return 1;
 }
 
 int depgan_uresnet_set_dice_loss(depgan_ctx* c, int form, float ce_coef, float dice_coef, float smooth,

@@ -619,13 +619,35 @@ class Engine:
         return np.array(w[:self.nc_out], np.float32), (None if ign.value < 0 else ign.value)
 
     def uresnet_label_counts(self):
-        """The label pre-pass counts of the last uresnet() call made in the loss-weight mode, as a dict: 'den' (pixels
+        """The label pre-pass counts of the last uresnet() call made in the loss-weight mode or the focal mode, as a dict: 'den' (pixels
         with a non-zero weight, the loss's denominator), 'ignored' (pixels without a true class), 'bad' (out-of-range
         codes) and 'classes' (np.int64 pixel count per true class).  Host memory (depgan_uresnet_last_label_counts)."""
         out, k = (C.c_longlong * _lib._K["DEPGAN_LABEL_NCOUNT"])(), C.c_int()
         check(self.lib.depgan_uresnet_last_label_counts(self.h, out, C.byref(k)), "depgan_uresnet_last_label_counts")
         return {"den": int(out[0]), "ignored": int(out[1]), "bad": int(out[2]),
                 "classes": np.array(out[3:3 + k.value], np.int64)}
+
+    def set_focal(self, gamma=0.0, label_smoothing=0.0):
+        """depgan_uresnet_set_focal: the focal mode of every uresnet() call.  gamma: the focal exponent, finite and >= 0
+        (each pixel's cross-entropy term is scaled by (1 - r)^gamma); label_smoothing: finite and in [0, 1) (the label
+        row becomes (1 - eps) t + eps / nc_out on pixels with a true class).  Both act inside the loss kernel, on top of
+        the class weights and the ignore label of set_loss_weights.  The loss is the sum over the number of pixels with
+        a non-zero weight, as in the loss-weight mode: with one-hot labels an all-zero row is then an ignored pixel.
+        Both 0 turns the mode off (the default)."""
+        for v, name in ((gamma, "gamma"), (label_smoothing, "label_smoothing")):
+            if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)):
+                raise ValueError("%s must be a number, got %r" % (name, v))
+        if float(gamma) != 0.0 or float(label_smoothing) != 0.0:
+            self._need_trainable("set_focal")
+        check(self.lib.depgan_uresnet_set_focal(self.h, float(gamma), float(label_smoothing)), "depgan_uresnet_set_focal")
+
+    @property
+    def focal(self):
+        """None with the focal mode off, else (gamma, label_smoothing) as the library holds them (float32 values)."""
+        g, e = C.c_float(), C.c_float()
+        if not self.lib.depgan_uresnet_get_focal(self.h, C.byref(g), C.byref(e)):
+            return None
+        return g.value, e.value
 
     def set_dice_loss(self, form=None, ce_weight=1.0, dice_weight=1.0, smooth=1e-7, class_coef=None):
         """depgan_uresnet_set_dice_loss: the soft Dice loss of every uresnet() call, alone or added to the cross-entropy.

@@ -302,6 +302,7 @@ class GeneratorModel(_Model):
         self._metrics = []
         self._class_weight, self._ignore_label = None, None      # compile(class_weight=, ignore_label=)
         self._dice = None                                        # compile(dice_loss=...): Engine.set_dice_loss's arguments
+        self._focal = None                                       # compile(focal_gamma=, label_smoothing=), None when off
         self._drop_rng = np.random.RandomState(seed)
 
     def _static_table(self):
@@ -331,6 +332,8 @@ class GeneratorModel(_Model):
             engine.set_loss_weights(self._class_weight, self._ignore_label)
         if self._dice is not None:
             engine.set_dice_loss(**self._dice)
+        if self._focal is not None:
+            engine.set_focal(*self._focal)
 
     def inference_copy(self, dtype="bfloat16"):
         """A new predict-only model with this architecture and a copy of the current weights, whose private engine runs
@@ -402,6 +405,20 @@ class GeneratorModel(_Model):
             raise ValueError("class_weight: every weight must be finite and >= 0, and at least one > 0, got %r" % (w.tolist(),))
         return w32, ignore_label
 
+    def _focal_args(self, focal_gamma, label_smoothing):
+        """compile's focal_gamma / label_smoothing as (gamma, eps) floats, or None with the mode off (both 0);
+        ValueError otherwise.  Needs no engine."""
+        out = []
+        for v, name in ((focal_gamma, "focal_gamma"), (label_smoothing, "label_smoothing")):
+            if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)):
+                raise ValueError("%s must be a number, got %r" % (name, v))
+            v32 = float(np.float32(v))
+            if not np.isfinite(v32) or v32 < 0 or (name == "label_smoothing" and v32 >= 1):
+                raise ValueError("%s must be finite and %s (as float32), got %r"
+                                 % (name, "in [0, 1)" if name == "label_smoothing" else ">= 0", v))
+            out.append(float(v))
+        return None if out[0] == 0.0 and out[1] == 0.0 else tuple(out)
+
     def _dice_args(self, loss, dice_loss, dice_weight, ce_weight, dice_smooth, dice_classes):
         """compile's Dice arguments as the keyword arguments of Engine.set_dice_loss, or None with the mode off;
         ValueError otherwise.  Needs no engine."""
@@ -449,7 +466,7 @@ class GeneratorModel(_Model):
 
     def compile(self, optimizer="adam", loss="categorical_crossentropy", lr=None, metrics=None, class_weight=None,
                 ignore_label=None, dice_loss=None, dice_weight=1.0, ce_weight=1.0, dice_smooth=1e-7, dice_classes=None,
-                **_):
+                focal_gamma=0.0, label_smoothing=0.0, **_):
         """model.compile(optimizer=Adam(lr=1e-4), loss='categorical_crossentropy')  (UT:427).
         metrics: names out of 'acc' / 'accuracy' (pixel accuracy: Keras' categorical_accuracy, arg-max against arg-max),
         'dice' and 'iou' (the means over the foreground classes 1..nc_out-1, evaluate.confusion_metrics).  They come from
@@ -476,12 +493,22 @@ class GeneratorModel(_Model):
         ce_weight * cross-entropy + dice_weight * Dice on the softmax probabilities (Engine.set_dice_loss); `loss` still
         selects the label format and the cross-entropy, and class_weight acts on the cross-entropy alone, while ignored
         pixels are left out of both.  loss='dice_coef_loss' is the reference's name for one-hot labels, the flat form,
-        ce_weight = 0 and smooth 1e-7.  compile() without these arguments turns the Dice loss off."""
+        ce_weight = 0 and smooth 1e-7.  compile() without these arguments turns the Dice loss off.
+        focal_gamma: the focal loss's exponent, finite and >= 0 (Keras' CategoricalFocalCrossentropy without its alpha:
+        class_weight is the alpha): each pixel's cross-entropy term is scaled by (1 - r)^gamma, so easy pixels stop
+        dominating the gradient.  label_smoothing: finite and in [0, 1), Keras' argument of that name: the label row of
+        a pixel with a true class becomes (1 - eps) t + eps / nc_out.  Either turns the focal mode on
+        (Engine.set_focal), inside the loss kernel; both work with both label formats, with class_weight / ignore_label,
+        metrics (which keep reading the original labels) and dice_loss (the Dice term reads the original labels; with
+        ce_weight = 0 they change nothing but the reported cross-entropy sums).  The loss is then the sum over the
+        number of pixels with a non-zero weight, as with class_weight: with one-hot labels an all-zero row is an
+        ignored pixel.  compile() without them turns the mode off; then every result is what it was without the mode."""
         self._need_softmax("compile")
         if loss not in _LOSSES + (_DICE_LOSS,):
             raise ValueError("loss must be 'categorical_crossentropy' (UT:427), 'sparse_categorical_crossentropy' or "
                              "'dice_coef_loss' (UT:120), got %r" % (loss,))
         dice = self._dice_args(loss, dice_loss, dice_weight, ce_weight, dice_smooth, dice_classes)
+        focal = self._focal_args(focal_gamma, label_smoothing)
         was_on = self._class_weight is not None or self._ignore_label is not None
         self._class_weight, self._ignore_label = self._loss_weight_args(loss, class_weight, ignore_label)
         if self._engine is not None and (self._dice is not None or dice is not None):
@@ -489,6 +516,9 @@ class GeneratorModel(_Model):
         self._dice = dice
         if self._engine is not None and (was_on or self._class_weight is not None or self._ignore_label is not None):
             self._engine.set_loss_weights(self._class_weight, self._ignore_label)
+        if self._engine is not None and (self._focal is not None or focal is not None):
+            self._engine.set_focal(*(focal or (0.0, 0.0)))
+        self._focal = focal
         if metrics is not None:
             if isinstance(metrics, str):
                 metrics = [metrics]

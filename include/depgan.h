@@ -237,7 +237,7 @@ int depgan_uresnet_last_census(depgan_ctx* ctx, long long out_host[DEPGAN_MAX_HE
  * depgan_uresnet_get_loss_weights: returns 1 and fills w_host (nc_out entries) and *ignore_code (either may be NULL)
  *   when the mode is on, else returns 0.
  * depgan_uresnet_last_label_counts: host only.  out_host = the pre-pass counts of the last depgan_uresnet_* call made
- *   with the mode on, which came back in the same copy and synchronisation as its loss: [0] den, [1] pixels without a
+ *   with the mode (or the focal mode, depgan_uresnet_set_focal) on, which came back in the same copy and synchronisation as its loss: [0] den, [1] pixels without a
  *   true class, [2] out-of-range codes, [3 + k] pixels of true class k (the code, or the first arg-max of the one-hot
  *   row); the first nc_out + 3 entries are valid, nc_out reported in *classes when not NULL.  Status 1 before any such
  *   call and after the mode was set again. */
@@ -291,6 +291,48 @@ int depgan_uresnet_get_dice_loss(depgan_ctx* ctx, float* ce_coef, float* dice_co
                                  float class_coef_host[DEPGAN_MAX_HEAD_CLASSES]);
 int depgan_uresnet_last_dice_sums(depgan_ctx* ctx, double out_host[3 * DEPGAN_MAX_HEAD_CLASSES], int* classes,
                                   float* dice_loss);
+
+/* The focal mode of the supervised path: focal cross-entropy (Lin et al.; Keras' CategoricalFocalCrossentropy) and label
+ * smoothing (the label_smoothing= of Keras' CategoricalCrossentropy), two per-pixel shapings of the cross-entropy itself,
+ * computed in the one softmax + cross-entropy kernel.
+ * depgan_uresnet_set_focal(ctx, gamma, label_smoothing): gamma finite and >= 0, label_smoothing (eps below) finite and in
+ *   [0, 1); anything else is status 1 with a message, before any HIP call; status 3 on an inference context, status 1 for
+ *   nc_out = 1 (as depgan_uresnet_set_census).  gamma == 0 together with label_smoothing == 0 turns the mode off (the
+ *   default): every entry then launches exactly the kernels it launched before this mode existed, bit for bit.
+ * With the mode on, all six depgan_uresnet_{grads,step,eval}{,_sparse} entries use, per pixel with label row t (the
+ *   one-hot row, or t[k] = (k == code) formed in registers; the ignore code and an all-zero row give t = 0), class
+ *   weights cw (the loss-weight mode's, all 1 when that mode is off), C = nc_out, and q, r = clip(q, 1e-7, 1 - 1e-7) and
+ *   the closed-interval clip gradient as in depgan_op_softmax_ce:
+ *     w_i  = sum_k cw[k] t[k]                       (left to right: the pre-pass's pixel weight)
+ *     has  = any t[k] != 0                          (on the row before weighting)
+ *     ts_k = w_i ((1 - eps) t[k] + (has ? eps / C : 0))
+ *     L_i  = -sum_k ts_k (1 - r_k)^gamma log r_k
+ *     dL/dq_k = -ts_k (1/den) [ (1 - r_k)^gamma / q_k - gamma (1 - r_k)^(gamma - 1) log r_k ]  on the closed clip
+ *               interval, else 0
+ *     loss = sum_i L_i / den
+ *   Everything behind dL/dq -- q = p / S, the softmax Jacobian, the dz row store -- is the plain kernel's text.  For
+ *   one-hot rows and eps = 0, ts_k = cw[k] t[k]; smoothing is defined on rows with a true class only, and a pixel of a
+ *   zero-weight class has w_i = 0 and stays out of loss, gradient and den.  1 - r is formed directly in float32 (inside
+ *   the clip 1 - r >= 2^-23); the power is 1, 1 - r and (1 - r)(1 - r) for gamma = 0, 1 and 2 and
+ *   exp2f(gamma log2f(1 - r)) otherwise, and (1 - r)^(gamma - 1) is the power over 1 - r.
+ * The denominator.  den, the label pre-pass and the ignore code are the loss-weight mode's: den = the number of pixels with
+ *   w_i != 0.  The focal mode always runs that weighted path; with the loss-weight mode off it does so with unit weights
+ *   and no ignore code.  So den == n*H*W whenever every pixel has a label, but -- THE DIFFERENCE from the plain mean over
+ *   n*H*W of the mode off -- an all-zero one-hot row is then an ignored pixel, outside den and outside the census;
+ *   den == 0 gives loss 0.0, an all-zero dz, status 0, and depgan_uresnet_step{,_sparse} applies NO Adam update and
+ *   leaves the step counter alone.  *loss_host = sum / den, depgan_last_sums[0..1] = the sum and den, and
+ *   depgan_uresnet_last_label_counts is valid after a call made with this mode or the loss-weight mode on.
+ * What the mode leaves alone: the probabilities stored are bit for bit the plain kernel's; the census's true class is the
+ *   arg-max of the original label row (or the code), never of the smoothed row; the Dice mode reads the original labels
+ *   and the stored probabilities and combines with this cross-entropy through ce_coef, and whether a pixel takes part in
+ *   the Dice term follows the loss-weight mode's setting alone.  Still one copy and one synchronisation per call.
+ * What is exact and what is bounded: class codes against their one-hot encoding, census on against off, power-of-two
+ *   class weights and den = P / 2 scale dz exactly; against a float64 evaluation of the rule the kernel keeps the plain
+ *   kernel's bounds (probabilities 1e-6, dz 1e-5 max|dz|, the loss sum 1e-5 relative).
+ * depgan_uresnet_get_focal: returns 1 and fills *gamma and *label_smoothing (either may be NULL) when the mode is on,
+ *   else returns 0. */
+int depgan_uresnet_set_focal(depgan_ctx* ctx, float gamma, float label_smoothing);
+int depgan_uresnet_get_focal(depgan_ctx* ctx, float* gamma, float* label_smoothing);
 
 /* Un-normalised pieces of the last critic / generator evaluation, for exact
  * data-parallel reporting: critic: [sum D(real), sum D(fake), sum (norm-1)^2, n];
@@ -766,6 +808,16 @@ int depgan_op_softmax_ce_census(const float* logits, const float* onehot, const 
 int depgan_op_softmax_ce_weighted(const float* logits, const float* onehot, const unsigned char* codes,
                                   const float* w_host, int n, int ignore_code, float* probs, float* dz, float* loss_sum,
                                   long long* census_host, long long* counts_host, long P, int C, void* hip_stream);
+/* depgan_op_softmax_ce_weighted in the focal mode (depgan_uresnet_set_focal states the rule): gamma finite and >= 0,
+ * label_smoothing in [0, 1); w_host == NULL means unit weights (n is then not read).  A NaN, infinite or negative gamma,
+ * a label_smoothing outside [0, 1) and everything depgan_op_softmax_ce_weighted refuses is status 1 before any HIP call,
+ * the outputs untouched.  gamma == 0 with label_smoothing == 0 is allowed here and runs the focal statements on the
+ * weighted path: den, the counts, the census and probs are those of depgan_op_softmax_ce_weighted, dz and loss_sum agree
+ * with it to rounding.  probs are bit for bit those of depgan_op_softmax_ce.  Synchronises the stream. */
+int depgan_op_softmax_ce_focal(const float* logits, const float* onehot, const unsigned char* codes, const float* w_host,
+                               int n, int ignore_code, float gamma, float label_smoothing, float* probs, float* dz,
+                               float* loss_sum, long long* census_host, long long* counts_host, long P, int C,
+                               void* hip_stream);
 /* The label pre-pass alone, with unit weights: out_host (host, C + 3 entries) in the layout of
  * depgan_uresnet_last_label_counts for P pixels given as onehot (P, C) fp32 or codes (P) unsigned char, exactly one of
  * them.  Integers summed in two stages without atomics.  Synchronises the stream. */
