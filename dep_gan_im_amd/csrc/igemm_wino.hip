@@ -30,7 +30,14 @@
 //     instructions + the four weight-fragment loads: vector-memory instructions complete in order).  The fragment loads are asm statements, waited for by count in front of the
 //     first MFMA: the compiler, which next to a DMA in flight waits vmcnt(0) for every load it knows of and in front
 //     of every __syncthreads(), sees no load in the chunk loop and drains nothing.  Then the transform (8 b128 reads
-//     of the raw image and 16 packed additions per task) and 16 MT MFMAs per wave out of registers.  The raw image is
+//     of the raw image and 16 packed additions per task) and 16 MT MFMAs per wave out of registers.  The chunk loop is
+//     straight-line: with two buffers a chunk differs from its neighbour only in being the first (zero C operand), in
+//     its ring slot and in being the last (no DMA behind the barrier, vmcnt(0) in front of the MFMAs), so the steady
+//     state is unrolled by two with the slot an immediate (the offset: field of the ds_read_b128, a constant m0 of the
+//     DMA), both waits immediates, one scalar addition each for the DMA's offset and the fragment base (a scalar
+//     pointer; the lane's part is a fixed 32-bit offset), one compare and one branch per two chunks; whether a DMA
+//     piece lies in the image is decided once per item (interior and border items issue the same instructions), and
+//     gathered K is a kernel of its own (profiles/wino_straightline_experiments.md).  The raw image is
 //     XOR-swizzled (rslot): the lanes the LDS serves together on a b128 read are neighbouring tiles of one channel
 //     half, 64 bytes apart unswizzled;
 //   * epilogue: each wave reduces its four b's to the two output columns in registers (Z[a][q] = row transform), the
@@ -76,7 +83,8 @@ struct WnCfg {
   // a ring of NBUF raw buffers (one barrier per chunk: after the barrier of chunk c a wave stages chunk c + NBUF - 1 into
   // the buffer the transform of chunk c - 1 read last).  Two: the weight-fragment wait in front of the MFMAs completes,
   // in order, every DMA issued before this chunk's barrier, so only ONE chunk is ever in flight behind it, and three
-  // buffers measured no faster than two (profiles/wino_ring_experiments.md); 3 and, at 8-row tiles, 4 are valid values.
+  // buffers measured no faster than two (profiles/wino_ring_experiments.md).  The chunk walk of wino_body is written for
+  // two: the ring slot of a chunk is a compile-time tag of its body (profiles/wino_straightline_experiments.md).
   // The Z exchange of the epilogue aliases the ring and is the larger of the two in both forms (37.9 KB / 73 KB against
   // 24 / 36 KB for three buffers), so the ring costs no LDS and the workgroups per CU stay what the registers allow
   static constexpr int NBUF = 2;
@@ -93,17 +101,9 @@ template <int N>
 static __device__ __forceinline__ void wn_wait_vm() {
   asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
 }
-// the same for a run-time number y <= Y of younger chunks (NX instructions each) plus the four fragment loads: a
-// wave-uniform branch to the immediate
-template <int NX, int Y>
-static __device__ __forceinline__ void wn_wait_younger(int y) {
-  if constexpr (Y == 0) {
-    wn_wait_vm<4>();
-  } else {
-    if (y >= Y) wn_wait_vm<NX * Y + 4>();
-    else wn_wait_younger<NX, Y - 1>(y);
-  }
-}
+// compile-time ring slot of a chunk body
+template <int S>
+using WnSlot = std::integral_constant<int, S>;
 
 // 16-byte slot of the raw LDS image that holds logical piece (pixel, channel half) of the (rows x 18) halo: the two low
 // bits of the linear slot 2 pixel + half XORed with bits 2..3 of the pixel's column.  A b128 read of the transform
@@ -116,7 +116,8 @@ static __device__ __forceinline__ int rslot_inv(int q) { return q ^ ((((q >> 1) 
 
 // ABL: ablation bits for tools/time_wino.py (0 = the product kernel; the others are compiled with
 // -DDEPGAN_WINO_ABLATIONS only): 1 no epilogue, 2 no input transform (zero operands), 4 no MFMAs, 8 no raw staging
-template <int MT, bool PERS, bool HEAD, int ABL = 0>
+// GATH: gathered K (ConvArgs::cpt > 0), an instantiation of its own: the plain kernels carry no test for it
+template <int MT, bool PERS, bool HEAD, bool GATH = false, int ABL = 0>
 static __device__ __forceinline__ void wino_body(const ConvArgs& a) {
   typedef WnCfg<MT> C;
   constexpr int MF = 32, NT = 32;
@@ -162,14 +163,14 @@ static __device__ __forceinline__ void wino_body(const ConvArgs& a) {
     const int rA = (aa == 0) ? 0 : (aa == 2 ? 2 : 1), rB = (aa == 3) ? 3 : (aa == 2 ? 1 : 2);
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-      tA[i][j] = 16 * rslot((2 * tyi + rA) * WN_TW + 2 * txi + j, cg);   // bytes; the ring slot is added as a scalar
+      tA[i][j] = 16 * rslot((2 * tyi + rA) * WN_TW + 2 * txi + j, cg);   // bytes; the ring slot is an immediate offset
       tB[i][j] = 16 * rslot((2 * tyi + rB) * WN_TW + 2 * txi + j, cg);
     }
     tS[i] = (aa == 1) ? 1.f : -1.f;
   }
   const int wbase = __builtin_amdgcn_readfirstlane(wv * 256);   // this wave's float offset inside a 256-piece round
   // fragments: A = V[f][32 mt + r][4h ..] = vr[mt][f] of the transform, B = panel[f][r][4h ..]
-  const int boff = (4 * wv * 32 + r) * WN_CK + 4 * h;
+  const int wvo = 4 * ((4 * wv * 32 + r) * WN_CK + 4 * h);   // bytes
 
   unsigned id = blockIdx.x;
   do {
@@ -188,16 +189,6 @@ static __device__ __forceinline__ void wino_body(const ConvArgs& a) {
     const int b = t / tilesY;
     const long out_goff = 0;
     const int n0 = ntile * NT;
-    const float* inb = a.in.p + (long)b * a.in.sB;
-    const bool interior = ty0 >= 1 && ty0 + C::TH + 1 <= a.H && tx0 >= 1 && tx0 + 17 <= a.W;
-    const char* halo0 = reinterpret_cast<const char*>(inb + ((long)(ty0 - 1) * a.in.sY + (long)(tx0 - 1) * a.in.sX));
-    auto coff = [&](int cc) -> long {
-      if (a.cpt > 0) {
-        const int run = cc / a.cpt;
-        return a.in_run_off[run] + (long)(cc - run * a.cpt) * WN_CK;
-      }
-      return (long)cc * WN_CK;
-    };
     // descriptor at the pixel one row and one column before the image origin: every in-image piece has a non-negative
     // offset from it
     const float* const xorg = a.in.p - ((long)a.in.sY + (long)a.in.sX);
@@ -206,27 +197,42 @@ static __device__ __forceinline__ void wino_body(const ConvArgs& a) {
     const unsigned xlo = __builtin_amdgcn_readfirstlane((unsigned)xu), xhi = __builtin_amdgcn_readfirstlane((unsigned)(xu >> 32));
     const __amdgpu_buffer_rsrc_t rx =
         __builtin_amdgcn_make_buffer_rsrc((void*)(((unsigned long long)xhi << 32) | xlo), 0, 0x7FFFFFFF, 0x00020000);
-    const int xso0 = 4 * (b * (int)a.in.sB + ty0 * (int)a.in.sY + tx0 * (int)a.in.sX);
-    auto stage_dma = [&](int cc, int buf) {   // chunk cc -> ring slot buf
-      const int xso = xso0 + 4 * (int)coff(cc);
-      float* xs = smem + buf * WN_RAW + wbase;
-      if (interior) {
+    // in the image or not is decided once per item and piece: the chunk loop issues the same NXP DMA instructions for
+    // interior and border items, with no test (the hardware returns zeros for the sentinel, as for the padding slots)
+    int xvi[NXP];
 #pragma unroll
-        for (int i = 0; i < NXP; ++i) {
-          // (a plain int local: with a type-dependent argument such as xvo[i] hipcc drops the host-side instantiation
-          // of the kernel without a diagnostic)
-          const int vo = xvo[i];
-          __builtin_amdgcn_raw_ptr_buffer_load_lds(rx, (__attribute__((address_space(3))) void*)(xs + i * 1024), 16, vo,
-                                                   xso, 0, 0);
+    for (int i = 0; i < NXP; ++i) {
+      const int iy = ty0 + (xyx[i] >> 8) - 1, ix = tx0 + (xyx[i] & 255) - 1;
+      xvi[i] = ((unsigned)iy < (unsigned)a.H && (unsigned)ix < (unsigned)a.W) ? xvo[i] : SENT;
+    }
+    // scalar byte offset of the chunk staged next; one addition per chunk.  Gathered K (ConvArgs::cpt): run t of cpt chunks
+    // starts at in_run_off[t], formed when the run starts
+    const int xso0 = 4 * (b * (int)a.in.sB + ty0 * (int)a.in.sY + tx0 * (int)a.in.sX);
+    int xso = GATH ? xso0 + 4 * (int)a.in_run_off[0] : xso0;
+    int grun = 0, gleft = GATH ? a.cpt : 0;
+    auto next_chunk = [&]() {
+      if constexpr (GATH) {
+        if (--gleft == 0) {
+          ++grun;
+          gleft = a.cpt;
+          xso = xso0 + 4 * (int)a.in_run_off[grun];
+        } else {
+          xso += 4 * WN_CK;
         }
       } else {
+        xso += 4 * WN_CK;
+      }
+    };
+    auto stage_dma = [&](auto buf_tag) {   // the chunk at xso -> ring slot BUF (a constant m0 per slot and piece)
+      constexpr int BUF = decltype(buf_tag)::value;
+      float* xs = smem + BUF * WN_RAW + wbase;
 #pragma unroll
-        for (int i = 0; i < NXP; ++i) {
-          const int iy = ty0 + (xyx[i] >> 8) - 1, ix = tx0 + (xyx[i] & 255) - 1;
-          const int vo = (iy >= 0 && iy < a.H && ix >= 0 && ix < a.W) ? xvo[i] : SENT;
-          __builtin_amdgcn_raw_ptr_buffer_load_lds(rx, (__attribute__((address_space(3))) void*)(xs + i * 1024), 16, vo,
-                                                   xso, 0, 0);
-        }
+      for (int i = 0; i < NXP; ++i) {
+        // (a plain int local: with a type-dependent argument such as xvi[i] hipcc drops the host-side instantiation
+        // of the kernel without a diagnostic)
+        const int vo = xvi[i];
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(rx, (__attribute__((address_space(3))) void*)(xs + i * 1024), 16, vo,
+                                                 xso, 0, 0);
       }
     };
 
@@ -234,49 +240,59 @@ static __device__ __forceinline__ void wino_body(const ConvArgs& a) {
     // vector moves per item less on a pipe where every vector instruction costs its issue time next to the MFMAs
     acc_t acc[4][MT];
 
-    const float* wnt = a.w + (size_t)ntile * nCC * (16 * NT * WN_CK) + boff;
-    // the first NBUF - 1 chunks of the item, back to back (no DMA of the previous item is in flight: its last chunk
-    // waited for everything, and the end-of-item barrier is behind us)
-    if (!(ABL & 8)) {
-#pragma unroll
-      for (int k = 0; k < NBUF - 1; ++k)
-        if (k < nCC) stage_dma(k, k);
-    }
-    // slot: ring slot of chunk cc (cc % NBUF).  One text for every ring position (a text per slot and tail position --
-    // immediate LDS offsets, no branch at the waits -- spilled over a hundred registers in the 16-row form): the waits
-    // branch, wave-uniformly, to their immediates
-    auto chunk = [&](const int cc, const int slot, auto first_tag) {
+    // this wave's weight fragments: a scalar base that advances by one chunk's panel, and the lane's byte offset in it
+    const float* wsp = a.w + (size_t)ntile * nCC * (16 * NT * WN_CK);
+    // the first chunk of the item (no DMA of the previous item is in flight: its last chunk waited for everything, and
+    // the end-of-item barrier is behind us)
+    if (!(ABL & 8)) stage_dma(WnSlot<0>{});
+    // One text, instantiated per (first chunk, ring slot, last chunk): with two buffers nothing else varies from chunk
+    // to chunk, so in the steady state the slot is an immediate offset of the transform's reads and a constant m0 of the
+    // DMA, both waits are immediates and nothing in the body branches.  slot_tag -1: the slot is rt_slot; last_tag 1 /
+    // 0: the item's last chunk or not, -1: rt_last says (both once per item)
+    int rt_slot = 0;
+    bool rt_last = false;
+    auto chunk = [&](auto first_tag, auto slot_tag, auto last_tag) {
       constexpr bool FIRST = decltype(first_tag)::value;
-      const bool issue = cc + NBUF - 1 < nCC;   // chunk cc + NBUF - 1 exists: staged behind this chunk's barrier
+      constexpr int SLOT = decltype(slot_tag)::value, LASTT = decltype(last_tag)::value;
+      constexpr bool LAST = LASTT == 1;
+      static_assert(NBUF == 2 && (SLOT == 0 || SLOT == 1 || SLOT == -1), "the walk below is written for two buffers");
       // this wave's weight fragments of the chunk: four frequencies x (32 channels x 8), in flight across the barrier and
       // the transform.  Loaded in an asm statement: next to a DMA in flight the compiler waits vmcnt(0) for the result of
       // any load it knows of, which would drain the ring in front of the MFMAs; these four are counted by hand
       f32x4 bq[4];
       {
-        const float* wp = wnt + (size_t)cc * (16 * NT * WN_CK);
         static_assert(3 * NT * WN_CK * sizeof(float) < 4096, "immediate offsets of the fragment loads");
         asm volatile(
-            "global_load_dwordx4 %0, %4, off\n\t"
-            "global_load_dwordx4 %1, %4, off offset:1024\n\t"
-            "global_load_dwordx4 %2, %4, off offset:2048\n\t"
-            "global_load_dwordx4 %3, %4, off offset:3072"
+            "global_load_dwordx4 %0, %4, %5\n\t"
+            "global_load_dwordx4 %1, %4, %5 offset:1024\n\t"
+            "global_load_dwordx4 %2, %4, %5 offset:2048\n\t"
+            "global_load_dwordx4 %3, %4, %5 offset:3072"
             : "=&v"(bq[0]), "=&v"(bq[1]), "=&v"(bq[2]), "=&v"(bq[3])
-            : "v"(wp)
+            : "v"(wvo), "s"(wsp)
             : "memory");
         static_assert(NT * WN_CK * sizeof(float) == 1024, "the offsets above");
+        wsp += 16 * NT * WN_CK;
       }
-      // this wave's DMA pieces of chunk cc have landed: vector-memory instructions complete in order, and younger than
-      // them are the DMAs of the chunks cc + 1 ... (NBUF - 2 of them, fewer at the end of an item) and the four loads
-      // above.  (The compiler does not know that the DMA writes LDS: the wait is explicit)
-      wn_wait_younger<NXI, NBUF - 2>(nCC - 1 - cc);
+      // this wave's DMA pieces of this chunk have landed: vector-memory instructions complete in order, and younger than
+      // them are only the four loads above (the next chunk is issued behind the barrier).  (The compiler does not know
+      // that the DMA writes LDS: the wait is explicit)
+      wn_wait_vm<4>();
       // ... and so have everybody else's -- the only barrier of the chunk.  The bare instruction: __syncthreads() fences,
-      // and the fence drains vmcnt while a DMA is in flight.  Nothing else needs the fence: a wave's LDS reads of chunk
-      // cc - 1 have returned before its MFMAs of that chunk took them
+      // and the fence drains vmcnt while a DMA is in flight.  Nothing else needs the fence: a wave's LDS reads of the
+      // previous chunk have returned before its MFMAs of that chunk took them
       __builtin_amdgcn_s_barrier();
       asm volatile("" ::: "memory");
-      // slot (cc + NBUF - 1) % NBUF was last read by the transform of chunk cc - 1: every wave is past this chunk's barrier
-      if (issue && !(ABL & 8)) stage_dma(cc + NBUF - 1, slot ? slot - 1 : NBUF - 1);
-      const char* raw = reinterpret_cast<const char*>(smem + slot * WN_RAW);
+      // the other slot was last read by the transform of the previous chunk: every wave is past this chunk's barrier
+      if constexpr (LASTT == 0) {
+        next_chunk();
+        if (!(ABL & 8)) stage_dma(WnSlot<1 - SLOT>{});
+      } else if constexpr (LASTT == -1) {
+        if (!rt_last) {
+          next_chunk();
+          if (!(ABL & 8)) stage_dma(WnSlot<1 - SLOT>{});
+        }
+      }
+      const char* raw = reinterpret_cast<const char*>(smem + (SLOT < 0 ? rt_slot : SLOT) * WN_RAW);
       // ---- input transform: raw -> vr[mt][b] = V[(wave, b)][32 mt + r][4h .. 4h + 3], the lane's own MFMA operands ----
       // (in channel pairs, the packed fp32 forms of the vector ALU: the pair is (k, k + 1) of one 16-byte read, so nothing
       // moves between registers -- left to itself the compiler pairs across the columns j and pays 24 moves per task)
@@ -317,15 +333,19 @@ static __device__ __forceinline__ void wino_body(const ConvArgs& a) {
       // the weight fragments have landed, their latency spent under the barrier and the transform.  In-order completion:
       // this also completes every DMA issued before them; only the one issued behind this chunk's barrier stays in flight.
       // The transform's results are operands of an empty statement in front of the wait (its additions stay above it,
-      // where the branch would otherwise let them sink to their first use), the fragments of one behind it (nothing that
+      // where they would otherwise be free to sink to their first use), the fragments of one behind it (nothing that
       // reads them moves above it)
 #pragma unroll
       for (int i = 0; i < MT; ++i)
         asm volatile("" : "+v"(vr[i][0][0]), "+v"(vr[i][0][1]), "+v"(vr[i][1][0]), "+v"(vr[i][1][1]), "+v"(vr[i][2][0]),
                           "+v"(vr[i][2][1]), "+v"(vr[i][3][0]), "+v"(vr[i][3][1]));
       __builtin_amdgcn_sched_barrier(0);
-      if (issue) wn_wait_vm<NXI>();
-      else wn_wait_vm<0>();
+      if constexpr (LASTT == -1) {
+        if (rt_last) wn_wait_vm<0>();
+        else wn_wait_vm<NXI>();
+      } else {
+        wn_wait_vm<LAST ? 0 : NXI>();
+      }
       asm volatile("" : "+v"(bq[0]), "+v"(bq[1]), "+v"(bq[2]), "+v"(bq[3])::"memory");
       // ---- 16 GEMMs, this wave's four: 16 MT MFMAs on the operands formed just above ----
 #pragma unroll
@@ -349,8 +369,30 @@ static __device__ __forceinline__ void wino_body(const ConvArgs& a) {
         __builtin_amdgcn_sched_barrier(0);
       }
     };
-    chunk(0, 0, std::true_type{});
-    for (int cc = 1, s = 1 % NBUF; cc < nCC; ++cc, s = (s + 1 == NBUF) ? 0 : s + 1) chunk(cc, s, std::false_type{});
+    // the item's walk: the first chunk (slot 0; whether it is also the last is a run-time test, once per item); the
+    // steady state two chunks a round (slot 1, slot 0: one counter, one branch); one more slot-1 chunk if the count is
+    // odd; the last chunk, which issues no DMA and waits for everything, with its slot a run-time scalar.  Every step
+    // updates the accumulators in place on ONE path: with a body per parity on either side of an if / else the
+    // compiler keeps two sets of accumulators and spills (35 ... 250 registers, profiles/wino_straightline_experiments.md)
+    {
+      const std::true_type yes;
+      const std::false_type no;
+      const WnSlot<1> last;
+      const WnSlot<0> more;
+      const WnSlot<-1> rt;
+      rt_last = nCC == 1;
+      chunk(yes, WnSlot<0>{}, rt);
+      if (nCC > 1) {
+#pragma unroll 1
+        for (int k = (nCC - 2) >> 1; k > 0; --k) {
+          chunk(no, WnSlot<1>{}, more);
+          chunk(no, WnSlot<0>{}, more);
+        }
+        if (nCC & 1) chunk(no, WnSlot<1>{}, more);
+        rt_slot = (nCC - 1) & 1;
+        chunk(no, rt, last);
+      }
+    }
 
     if (ABL & 1) {   // keep the accumulators alive with one store that never happens
       float sacc = 0.f;
@@ -430,10 +472,14 @@ template <bool PERS>
 __global__ __launch_bounds__(256, 2) void wino_conv_head_kernel(const ConvArgs a) {
   wino_body<2, PERS, true>(a);
 }
+template <int MT, bool PERS>
+__global__ __launch_bounds__(256, WnCfg<MT>::WGS_PER_CU) void wino_conv_gathered_kernel(const ConvArgs a) {
+  wino_body<MT, PERS, false, true>(a);
+}
 #ifdef DEPGAN_WINO_ABLATIONS
 template <int MT, int ABL>
 __global__ __launch_bounds__(256, WnCfg<MT>::WGS_PER_CU) void wino_conv_abl_kernel(const ConvArgs a) {
-  wino_body<MT, true, false, ABL>(a);
+  wino_body<MT, true, false, false, ABL>(a);
 }
 #endif
 
@@ -479,6 +525,10 @@ const char* dg_conv_wino_name(const ConvArgs& a_in) {
   const int mt = wino_mt(a);
   if (mt == 2) wino_geometry<2>(a, &total, &G, &pers); else wino_geometry<1>(a, &total, &G, &pers);
   if (a.ep.head_out) return pers ? "wino_conv_head_kernel<true>" : "wino_conv_head_kernel<false>";
+  if (a.cpt > 0) {
+    if (mt == 2) return pers ? "wino_conv_gathered_kernel<2,true>" : "wino_conv_gathered_kernel<2,false>";
+    return pers ? "wino_conv_gathered_kernel<1,true>" : "wino_conv_gathered_kernel<1,false>";
+  }
   if (mt == 2) return pers ? "wino_conv_kernel<2,true>" : "wino_conv_kernel<2,false>";
   return pers ? "wino_conv_kernel<1,true>" : "wino_conv_kernel<1,false>";
 }
@@ -495,6 +545,10 @@ static int wino_launch(ConvArgs a, hipStream_t st) {
                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS));
     HIPCHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&wino_conv_kernel<MT, true>),
                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS));
+    HIPCHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&wino_conv_gathered_kernel<MT, false>),
+                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS));
+    HIPCHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&wino_conv_gathered_kernel<MT, true>),
+                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS));
     if (MT == 2) {
       HIPCHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&wino_conv_head_kernel<false>),
                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS));
@@ -505,7 +559,7 @@ static int wino_launch(ConvArgs a, hipStream_t st) {
 #ifdef DEPGAN_WINO_ABLATIONS
   if (const char* e = getenv("DEPGAN_WINO_ABL")) {
     const int abl = atoi(e);
-    if (abl && pers && !a.ep.head_out) {
+    if (abl && pers && !a.ep.head_out && a.cpt <= 0) {
 #define WN_ABL_CASE(N)                                                                                              \
   case N:                                                                                                           \
     HIPCHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&wino_conv_abl_kernel<MT, N>),                       \
@@ -522,12 +576,15 @@ static int wino_launch(ConvArgs a, hipStream_t st) {
   }
 #endif
   if (a.ep.head_out) {
-    if (MT != 2 || a.Cout != 32 || a.ep.pool.p) {
-      dg_set_error("dg_conv_wino: the fused head needs 32 output channels and no fused pool");
+    if (MT != 2 || a.Cout != 32 || a.ep.pool.p || a.cpt > 0) {
+      dg_set_error("dg_conv_wino: the fused head needs 32 output channels, no fused pool and no gathered K");
       return DG_ERR_ARG;
     }
     if (pers) hipLaunchKernelGGL((wino_conv_head_kernel<true>), dim3((unsigned)G), dim3(256), LDS, st, a);
     else hipLaunchKernelGGL((wino_conv_head_kernel<false>), dim3((unsigned)G), dim3(256), LDS, st, a);
+  } else if (a.cpt > 0) {
+    if (pers) hipLaunchKernelGGL((wino_conv_gathered_kernel<MT, true>), dim3((unsigned)G), dim3(256), LDS, st, a);
+    else hipLaunchKernelGGL((wino_conv_gathered_kernel<MT, false>), dim3((unsigned)G), dim3(256), LDS, st, a);
   } else {
     if (pers) hipLaunchKernelGGL((wino_conv_kernel<MT, true>), dim3((unsigned)G), dim3(256), LDS, st, a);
     else hipLaunchKernelGGL((wino_conv_kernel<MT, false>), dim3((unsigned)G), dim3(256), LDS, st, a);
