@@ -627,6 +627,34 @@ int depgan_op_softmax_ce4(const float* logits, const float* onehot, float* probs
   return depgan_op_softmax_ce(logits, onehot, nullptr, probs, dz, loss_sum, P, 4, stream);
 }
 
+// the fp32 head to K = 2..8 class logits (uresnet.hip's calls for a class count other than 4)
+int depgan_op_head_k_fwd(const float* a, long ld, const float* w, const float* b, float* logits, long P, int C, int K,
+                         void* stream) {
+  return dg_head_k_fwd(a, ld, w, b, logits, P, C, K, (hipStream_t)stream);
+}
+int depgan_op_head_k_bwd(const float* dz, const float* w, const float* mask, long ldm, float* din, long ldd, long P, int C,
+                         int K, void* stream) {
+  return dg_head_k_bwd(dz, w, mask, ldm, din, ldd, P, C, K, (hipStream_t)stream);
+}
+int depgan_op_head_k_wgrad(const float* a, long lda, const float* dz, float* dW, float* db, long P, int C, int K,
+                           long scratch_floats, void* stream) {
+  // the scratch size is only defined for sizes the launcher takes; everything else is the launcher's to refuse
+  if (!a || !dz || !dW || !db || P < 1 || C < 1 || K < 1 || C > 4096 || K > 4096) {
+    dg_set_error("op_head_k_wgrad: bad argument");
+    return DG_ERR_ARG;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  const size_t cap = op_scratch(scratch_floats, dg_head_k_wgrad_scratch(P, C, K));
+  DevTmp scratch(st);
+  DGCHECK(op_alloc(&scratch, cap, "op_head_k_wgrad"));
+  // NaN in every partial: the two stages must write what they read
+  if (hipMemsetAsync(scratch.p, 0xFF, cap * sizeof(float), st) != hipSuccess) {
+    dg_set_error("op_head_k_wgrad: scratch fill failed");
+    return DG_ERR_HIP;
+  }
+  return dg_head_k_wgrad(a, lda, dz, dW, db, P, C, K, scratch.as<float>(), cap, st);
+}
+
 int depgan_op_bn_rows_fwd(const float* x, float* y, int R, int C, int ld, const float* gamma, const float* beta,
                           float eps, float momentum, float corr, float* moving_mean, float* moving_var, float* mean,
                           float* rstd, int relu, void* stream) {

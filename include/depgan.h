@@ -834,6 +834,27 @@ int depgan_op_label_counts(const float* onehot, const unsigned char* codes, long
 int depgan_op_dice_loss(const float* probs, const float* onehot, const unsigned char* codes, int ignore_code, int form,
                         const float* class_coef_host, int n, float smooth, float ce_coef, float dice_coef,
                         float* dz_inout, double* sums_host, float* loss_host, long P, int C, void* hip_stream);
+/* The fp32 1x1 head to K = 2..DEPGAN_MAX_HEAD_CLASSES class logits over P pixel rows, as the DEP-UResNet training step
+ * runs it for a class count other than 4.  Rows of C floats with a row stride in floats (ld >= C, ld % 4 == 0), so a
+ * channel window of a wider buffer is (p + c0, Ctot) with c0 % 4 == 0; C / 4 a power of two <= 64; w (C, K), logits and
+ * dz (P, K) dense.  Row bases 16-byte aligned; logits and dz 16-byte aligned where K % 4 == 0, else 4-byte.  Anything
+ * else, a null operand, P < 1 or a K outside the range is status 1 before any launch, the outputs untouched.
+ * Forward: logits[p][k] = sum_c a[p][c] w[c][k] + b[k].  Order: per 4-channel part a0 w0 then fmaf over channels 1..3,
+ * an xor butterfly over the C / 4 parts, + b[k] last. */
+int depgan_op_head_k_fwd(const float* a, long ld, const float* w, const float* b, float* logits, long P, int C, int K,
+                         void* hip_stream);
+/* Backward-data under the ReLU mask of the head's input: din[p][c] = (mask[p][c] > 0) ? sum_k dz[p][k] w[c][k] : +0,
+ * the sum as dz0 w0 then fmaf over k = 1..K-1; mask optional (NULL: no mask, ldm unused); mask and din have their own
+ * row strides.  Only the C floats of each of the P rows of din are written. */
+int depgan_op_head_k_bwd(const float* dz, const float* w, const float* mask, long ldm, float* din, long ldd, long P, int C,
+                         int K, void* hip_stream);
+/* Weight and bias gradient: dW[c][k] = sum_p a[p][c] dz[p][k] (C, K) dense and db[k] = sum_p dz[p][k], in two stages of
+ * fixed order without atomics, so a call repeats bit for bit.  The partials go through a scratch of nb (C K + K) floats,
+ * nb <= 1024 the pixel blocks of the launch; the entry allocates it and fills it with NaN first, so the result cannot
+ * depend on what it held.  scratch_floats as above: <= 0 for what the launch needs, a capacity below that is status 1.
+ * Synchronises the stream. */
+int depgan_op_head_k_wgrad(const float* a, long lda, const float* dz, float* dW, float* db, long P, int C, int K,
+                           long scratch_floats, void* hip_stream);
 /* BatchNorm over the R rows of an [R][ld] matrix (first C columns), moving statistics updated when given:
  * moving = momentum*moving + (1 - momentum)*(mean, var*corr) */
 int depgan_op_bn_rows_fwd(const float* x, float* y, int R, int C, int ld, const float* gamma, const float* beta,
