@@ -315,6 +315,17 @@ ConvPlan dg_plan_conv_wino(int Cin, int Cout);
 bool dg_conv_wino_supported(const ConvPlan& pl, const ConvArgs& a);
 const char* dg_conv_wino_name(const ConvArgs& a);
 int dg_conv_wino(const ConvPlan& pl, const ConvArgs& a, hipStream_t st);
+// Epilogue classes of the Winograd kernel: instantiations whose epilogue flags are compile-time constants, one per flag
+// set the model launches (the table in igemm_wino.hip).  The flag set of an Epilogue as a bit mask (DEPGAN_EPF_* of
+// include/depgan.h), and the pure host function both the launcher and dg_conv_wino_name select with: form 0 the 8-row
+// kernel, 1 the fused-head kernel, 2 the 16-row kernel without head, 3 gathered K.  Class 0 is the generic kernel (run-time
+// flags): any set outside the table, forms 2 and 3, and everything while the process-wide switch is off.
+enum { DG_EPF_BIAS = 1, DG_EPF_AFFINE = 2, DG_EPF_FILM = 4, DG_EPF_RELU = 8, DG_EPF_PRE = 16, DG_EPF_RES = 32,
+       DG_EPF_MASK = 64, DG_EPF_POOL = 128, DG_EPF_ACCUM = 256, DG_EPF_HEAD = 512, DG_EPF_ALL = 1023 };
+unsigned dg_epilogue_flags(const Epilogue& e);
+int dg_wino_epi_class(unsigned flags, int form);
+void dg_set_epi_classes(int on);
+int dg_get_epi_classes();
 // name of the kernel instantiation dg_conv_igemm launches for (pl, a), as rocprofv3 prints it
 void dg_conv_igemm_name(const ConvPlan& pl, const ConvArgs& a, char* buf, size_t cap);
 int dg_conv_direct(int KS, const ConvArgs& a, hipStream_t st);

@@ -14,6 +14,10 @@
 //   EPI_NPASS      passes of 8 pixels x 32 channels the wave's block takes (default 8 = 4 x 16 pixels)
 //   EPI_FETCH(v, py, px)  statement producing the four channels c4 .. c4+3 of pixel (py, px) of the wave's 4 x 16 block
 //                  in v (default: one 16-byte read of the transposed tile)
+//   EPI_CLASS      a type with constexpr bool members fixed, bias, affine, film, relu, pre, res, msk, pool, head:
+//                  fixed = true makes the epilogue's flags those compile-time constants (accumulate: false) instead of
+//                  run-time tests on a.ep -- the launcher must then pass exactly that flag set (igemm_wino.hip);
+//                  fixed = false, or the hook undefined (default): every flag is read from a.ep
 #ifndef EPI_PRE_SYNC
 #define EPI_PRE_SYNC __syncthreads()
 #define EPI_PRE_SYNC_DEFAULTED
@@ -67,9 +71,22 @@
   const int wvu = __builtin_amdgcn_readfirstlane(wv);
 #endif
   const Epilogue& e = a.ep;
+#ifdef EPI_CLASS
+  // the launcher chose this instantiation for exactly this flag set (EPI_CLASS::fixed; otherwise the class is the
+  // generic one and reads the flags as below): the tests on absent operands, their descriptors, lane offsets and strides
+  // fold away at compile time.  The statements are the same text, so every class computes the generic kernel's bits
+  typedef EPI_CLASS EpiC;
+  constexpr bool EPI_CT = EpiC::fixed;
+  const bool affine = EPI_CT ? EpiC::affine : (e.scale != nullptr), film = EPI_CT ? EpiC::film : (e.film_mul != nullptr),
+             relu = EPI_CT ? EpiC::relu : (e.relu != 0), accum = EPI_CT ? false : (e.accumulate != 0);
+  const bool has_bias = EPI_CT ? EpiC::bias : (e.bias != nullptr), has_pre = EPI_CT ? EpiC::pre : (e.out_pre.p != nullptr),
+             has_res = EPI_CT ? EpiC::res : (e.res.p != nullptr), has_msk = EPI_CT ? EpiC::msk : (e.mask.p != nullptr),
+             has_pool = EPI_CT ? EpiC::pool : (e.pool.p != nullptr);
+#else
   const bool affine = e.scale != nullptr, film = e.film_mul != nullptr, relu = e.relu != 0, accum = e.accumulate != 0;
   const bool has_bias = e.bias != nullptr, has_pre = e.out_pre.p != nullptr, has_res = e.res.p != nullptr,
              has_msk = e.mask.p != nullptr, has_pool = e.pool.p != nullptr;
+#endif
 #ifdef EPI_OYW
   const int oyw = EPI_OYW;
 #else
@@ -127,7 +144,11 @@
     // fused 1x1 head to one channel: the 8 lanes of a pixel hold its 32 channels (4 each) -- a 4-FMA partial dot product,
     // an all-reduce over the 8 lanes in three DPP steps, and lane (pass index) of each pixel group keeps the sum of its
     // pass, so that after the eight passes every lane owns one pixel: ONE activation and ONE store per lane and item
+#ifdef EPI_CLASS
+    const bool has_head = EPI_HEAD && (EPI_CT ? EpiC::head : (e.head_out != nullptr));
+#else
     const bool has_head = EPI_HEAD && e.head_out != nullptr;
+#endif
     f32x4 hw4 = {0.f, 0.f, 0.f, 0.f};
     if (has_head) hw4 = *reinterpret_cast<const f32x4*>(e.head_w + co);
     const bool skip_out = has_head && e.head_skip_out != 0;

@@ -114,10 +114,46 @@ static __device__ __forceinline__ int rslot(int pix, int half) { return (2 * pix
 // its inverse on slot indices: the key depends on slot >> 2 only (18 columns are even), so the same XOR undoes it
 static __device__ __forceinline__ int rslot_inv(int q) { return q ^ ((((q >> 1) % WN_TW) >> 2) & 3); }
 
+// Epilogue classes (profiles/epi_classes_experiments.md).  The fused epilogue tests nine flags of ConvArgs::ep per item
+// and again in every pass, and forms descriptors, lane offsets and strides of operands that are absent: next to the 64
+// MFMAs of a short-K item that is most of what a wave executes outside its chunks, and it costs the persistent kernel 66
+// spilled SGPRs.  An instantiation whose flags are constants carries only the statements of its flag set (the same text:
+// igemm_epilogue.inc, EPI_CLASS).  The table is closed: exactly the flag sets the model launches on this kernel
+// (model.hip: g_forward with g_layer_epilogue -- a pool only ever follows a plain conv layer, never a FiLM layer --,
+// g_conv_bn_bwd, d_forward, d_backward_chain, the u-forward of critic_enqueue).  Class 0 is the generic kernel, which
+// everything else takes: accumulate, the phase-1 bias-only launches, what the operator entries combine.
+constexpr unsigned WN_BAR = DG_EPF_BIAS | DG_EPF_AFFINE | DG_EPF_RELU;    // convolution + BatchNorm affine + ReLU
+constexpr unsigned WN_FILM = WN_BAR | DG_EPF_FILM | DG_EPF_RES;           // the generator's FiLM layer
+constexpr int WN_NCLASS = 11, WN_HEAD_CLASS = 10;                          // 1 .. 9: the 8-row kernel; 10: the fused head
+constexpr unsigned kWnClassMask[WN_NCLASS] = {
+    0,                                                   //  0 generic (run-time flags)
+    WN_BAR,                                              //  1 generator conv
+    WN_BAR | DG_EPF_POOL,                                //  2   ... with the fused pool (gen_1 / gen_3 / gen_5)
+    WN_FILM,                                             //  3 FiLM layer, forward-only passes
+    WN_FILM | DG_EPF_PRE,                                //  4   ... storing u for the backward
+    DG_EPF_RES | DG_EPF_MASK,                            //  5 generator backward-data: gradient join + ReLU mask
+    DG_EPF_MASK,                                         //  6 backward-data with a mask; the critics' u-forward
+    0,                                                   //  7 backward-data into a pooled layer: nothing
+    DG_EPF_BIAS | DG_EPF_RELU,                           //  8 critic 3x3 forward
+    DG_EPF_BIAS | DG_EPF_RELU | DG_EPF_POOL,             //  9   ... with the fused pool
+    WN_BAR | DG_EPF_HEAD,                                // 10 gen_17 with the fused one-channel head (stored or skipped)
+};
+#define WN_CLASSES8(X) X(1) X(2) X(3) X(4) X(5) X(6) X(7) X(8) X(9)
+template <int EC>
+struct WnEpi {
+  static_assert(EC >= 0 && EC < WN_NCLASS, "epilogue class");
+  static constexpr unsigned M = kWnClassMask[EC];
+  static constexpr bool fixed = EC != 0;
+  static constexpr bool bias = M & DG_EPF_BIAS, affine = M & DG_EPF_AFFINE, film = M & DG_EPF_FILM, relu = M & DG_EPF_RELU,
+                        pre = M & DG_EPF_PRE, res = M & DG_EPF_RES, msk = M & DG_EPF_MASK, pool = M & DG_EPF_POOL,
+                        head = M & DG_EPF_HEAD;
+};
+
 // ABL: ablation bits for tools/time_wino.py (0 = the product kernel; the others are compiled with
 // -DDEPGAN_WINO_ABLATIONS only): 1 no epilogue, 2 no input transform (zero operands), 4 no MFMAs, 8 no raw staging
 // GATH: gathered K (ConvArgs::cpt > 0), an instantiation of its own: the plain kernels carry no test for it
-template <int MT, bool PERS, bool HEAD, bool GATH = false, int ABL = 0>
+// EC: epilogue class (0: the flags of a.ep are read at run time)
+template <int MT, bool PERS, bool HEAD, bool GATH = false, int ABL = 0, int EC = 0>
 static __device__ __forceinline__ void wino_body(const ConvArgs& a) {
   typedef WnCfg<MT> C;
   constexpr int MF = 32, NT = 32;
@@ -448,7 +484,9 @@ static __device__ __forceinline__ void wino_body(const ConvArgs& a) {
     _Pragma("unroll") for (int k_ = 0; k_ < 4; ++k_) v[k_] = ((py)&1) ? (za[k_] - zb1[k_]) - zc[k_] : (za[k_] + zb1[k_]) + zc[k_]; \
   }
 #define EPI_HEAD HEAD
+#define EPI_CLASS WnEpi<EC>
 #include "igemm_epilogue.inc"
+#undef EPI_CLASS
 #undef EPI_HEAD
 #undef EPI_FETCH
 #undef EPI_FULL
@@ -464,13 +502,13 @@ static __device__ __forceinline__ void wino_body(const ConvArgs& a) {
   } while (PERS && (id += gridDim.x) < nPix * nNTall);
 }
 
-template <int MT, bool PERS>
+template <int MT, bool PERS, int EC>
 __global__ __launch_bounds__(256, WnCfg<MT>::WGS_PER_CU) void wino_conv_kernel(const ConvArgs a) {
-  wino_body<MT, PERS, false>(a);
+  wino_body<MT, PERS, false, false, 0, EC>(a);
 }
-template <bool PERS>
+template <bool PERS, int EC>
 __global__ __launch_bounds__(256, 2) void wino_conv_head_kernel(const ConvArgs a) {
-  wino_body<2, PERS, true>(a);
+  wino_body<2, PERS, true, false, 0, EC>(a);
 }
 template <int MT, bool PERS>
 __global__ __launch_bounds__(256, WnCfg<MT>::WGS_PER_CU) void wino_conv_gathered_kernel(const ConvArgs a) {
@@ -483,7 +521,60 @@ __global__ __launch_bounds__(256, WnCfg<MT>::WGS_PER_CU) void wino_conv_abl_kern
 }
 #endif
 
+// Every instantiation a launch can take, with the name rocprofv3 prints for it: wino_pick() is the one place that maps
+// a launch to an entry, so the name dg_conv_wino_name reports is the kernel wino_launch starts
+struct WnKern {
+  const void* fn;
+  const char* name;
+};
+#define WN_K8(EC)                                                                                       \
+  {{reinterpret_cast<const void*>(&wino_conv_kernel<1, false, EC>), "wino_conv_kernel<1,false," #EC ">"}, \
+   {reinterpret_cast<const void*>(&wino_conv_kernel<1, true, EC>), "wino_conv_kernel<1,true," #EC ">"}},
+const WnKern kWn8[WN_HEAD_CLASS][2] = {WN_K8(0) WN_CLASSES8(WN_K8)};   // [class][persistent]
+#undef WN_K8
+const WnKern kWn16[2] = {{reinterpret_cast<const void*>(&wino_conv_kernel<2, false, 0>), "wino_conv_kernel<2,false,0>"},
+                         {reinterpret_cast<const void*>(&wino_conv_kernel<2, true, 0>), "wino_conv_kernel<2,true,0>"}};
+const WnKern kWnHead[2][2] = {   // [generic / head class][persistent]
+    {{reinterpret_cast<const void*>(&wino_conv_head_kernel<false, 0>), "wino_conv_head_kernel<false,0>"},
+     {reinterpret_cast<const void*>(&wino_conv_head_kernel<true, 0>), "wino_conv_head_kernel<true,0>"}},
+    {{reinterpret_cast<const void*>(&wino_conv_head_kernel<false, WN_HEAD_CLASS>), "wino_conv_head_kernel<false,10>"},
+     {reinterpret_cast<const void*>(&wino_conv_head_kernel<true, WN_HEAD_CLASS>), "wino_conv_head_kernel<true,10>"}}};
+static_assert(WN_HEAD_CLASS == 10, "the names above");
+const WnKern kWnGath[2][2] = {   // [MT - 1][persistent]
+    {{reinterpret_cast<const void*>(&wino_conv_gathered_kernel<1, false>), "wino_conv_gathered_kernel<1,false>"},
+     {reinterpret_cast<const void*>(&wino_conv_gathered_kernel<1, true>), "wino_conv_gathered_kernel<1,true>"}},
+    {{reinterpret_cast<const void*>(&wino_conv_gathered_kernel<2, false>), "wino_conv_gathered_kernel<2,false>"},
+     {reinterpret_cast<const void*>(&wino_conv_gathered_kernel<2, true>), "wino_conv_gathered_kernel<2,true>"}}};
+
+// DEPGAN_EPI_CLASSES=0: every launch takes the generic kernel (A/B); depgan_set_epilogue_classes overrides it
+int g_epi_classes = -1;
+
 }  // namespace
+
+void dg_set_epi_classes(int on) { g_epi_classes = on ? 1 : 0; }
+int dg_get_epi_classes() {
+  if (g_epi_classes < 0) {
+    const char* e = getenv("DEPGAN_EPI_CLASSES");
+    g_epi_classes = (e && atoi(e) == 0) ? 0 : 1;
+  }
+  return g_epi_classes;
+}
+
+unsigned dg_epilogue_flags(const Epilogue& e) {
+  return (e.bias ? DG_EPF_BIAS : 0u) | (e.scale ? DG_EPF_AFFINE : 0u) | (e.film_mul ? DG_EPF_FILM : 0u) |
+         (e.relu ? DG_EPF_RELU : 0u) | (e.out_pre.p ? DG_EPF_PRE : 0u) | (e.res.p ? DG_EPF_RES : 0u) |
+         (e.mask.p ? DG_EPF_MASK : 0u) | (e.pool.p ? DG_EPF_POOL : 0u) | (e.accumulate ? DG_EPF_ACCUM : 0u) |
+         (e.head_out ? DG_EPF_HEAD : 0u);
+}
+
+int dg_wino_epi_class(unsigned flags, int form) {
+  if (!dg_get_epi_classes()) return 0;
+  if (form == 1) return flags == kWnClassMask[WN_HEAD_CLASS] ? WN_HEAD_CLASS : 0;
+  if (form != 0) return 0;
+  for (int i = 1; i < WN_HEAD_CLASS; ++i)
+    if (kWnClassMask[i] == flags) return i;
+  return 0;
+}
 
 bool dg_conv_wino_supported(const ConvPlan& pl, const ConvArgs& a) {
   if (!dg_plan_wino(pl)) return false;
@@ -518,19 +609,23 @@ static void wino_geometry(ConvArgs& a, long* total, long* G, bool* pers) {
   *G = *pers ? cap : *total;
 }
 
+// the instantiation of a launch: its form, then the epilogue class of its flag set
+static const WnKern* wino_pick(const ConvArgs& a, int mt, bool pers) {
+  const int form = a.ep.head_out ? 1 : (a.cpt > 0 ? 3 : (mt == 2 ? 2 : 0));
+  const int ec = dg_wino_epi_class(dg_epilogue_flags(a.ep), form);
+  if (form == 1) return &kWnHead[ec ? 1 : 0][pers];
+  if (form == 3) return &kWnGath[mt - 1][pers];
+  if (form == 2) return &kWn16[pers];
+  return &kWn8[ec][pers];
+}
+
 const char* dg_conv_wino_name(const ConvArgs& a_in) {
   ConvArgs a = a_in;
   long total, G;
   bool pers;
   const int mt = wino_mt(a);
   if (mt == 2) wino_geometry<2>(a, &total, &G, &pers); else wino_geometry<1>(a, &total, &G, &pers);
-  if (a.ep.head_out) return pers ? "wino_conv_head_kernel<true>" : "wino_conv_head_kernel<false>";
-  if (a.cpt > 0) {
-    if (mt == 2) return pers ? "wino_conv_gathered_kernel<2,true>" : "wino_conv_gathered_kernel<2,false>";
-    return pers ? "wino_conv_gathered_kernel<1,true>" : "wino_conv_gathered_kernel<1,false>";
-  }
-  if (mt == 2) return pers ? "wino_conv_kernel<2,true>" : "wino_conv_kernel<2,false>";
-  return pers ? "wino_conv_kernel<1,true>" : "wino_conv_kernel<1,false>";
+  return wino_pick(a, mt, pers)->name;
 }
 
 template <int MT>
@@ -541,20 +636,15 @@ static int wino_launch(ConvArgs a, hipStream_t st) {
   constexpr size_t LDS = WnCfg<MT>::LDS;
   static DgOncePerDevice once;
   if (once.need()) {
-    HIPCHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&wino_conv_kernel<MT, false>),
-                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS));
-    HIPCHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&wino_conv_kernel<MT, true>),
-                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS));
-    HIPCHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&wino_conv_gathered_kernel<MT, false>),
-                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS));
-    HIPCHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&wino_conv_gathered_kernel<MT, true>),
-                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS));
-    if (MT == 2) {
-      HIPCHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&wino_conv_head_kernel<false>),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS));
-      HIPCHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&wino_conv_head_kernel<true>),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS));
-    }
+    // every instantiation of this MT, its epilogue classes included
+    const WnKern* const own = (MT == 2) ? &kWn16[0] : &kWn8[0][0];
+    const int nown = (MT == 2) ? 2 : 2 * WN_HEAD_CLASS;
+    for (int i = 0; i < nown; ++i)
+      HIPCHECK(hipFuncSetAttribute(own[i].fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS));
+    for (int i = 0; i < 2; ++i)
+      HIPCHECK(hipFuncSetAttribute(kWnGath[MT - 1][i].fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS));
+    for (int i = 0; MT == 2 && i < 4; ++i)
+      HIPCHECK(hipFuncSetAttribute(kWnHead[i >> 1][i & 1].fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS));
   }
 #ifdef DEPGAN_WINO_ABLATIONS
   if (const char* e = getenv("DEPGAN_WINO_ABL")) {
@@ -580,15 +670,9 @@ static int wino_launch(ConvArgs a, hipStream_t st) {
       dg_set_error("dg_conv_wino: the fused head needs 32 output channels, no fused pool and no gathered K");
       return DG_ERR_ARG;
     }
-    if (pers) hipLaunchKernelGGL((wino_conv_head_kernel<true>), dim3((unsigned)G), dim3(256), LDS, st, a);
-    else hipLaunchKernelGGL((wino_conv_head_kernel<false>), dim3((unsigned)G), dim3(256), LDS, st, a);
-  } else if (a.cpt > 0) {
-    if (pers) hipLaunchKernelGGL((wino_conv_gathered_kernel<MT, true>), dim3((unsigned)G), dim3(256), LDS, st, a);
-    else hipLaunchKernelGGL((wino_conv_gathered_kernel<MT, false>), dim3((unsigned)G), dim3(256), LDS, st, a);
-  } else {
-    if (pers) hipLaunchKernelGGL((wino_conv_kernel<MT, true>), dim3((unsigned)G), dim3(256), LDS, st, a);
-    else hipLaunchKernelGGL((wino_conv_kernel<MT, false>), dim3((unsigned)G), dim3(256), LDS, st, a);
   }
+  void* kargs[] = {&a};
+  HIPCHECK(hipLaunchKernel(wino_pick(a, MT, pers)->fn, dim3((unsigned)G), dim3(256), kargs, LDS, st));
   HIPCHECK(hipGetLastError());
   return DG_OK;
 }

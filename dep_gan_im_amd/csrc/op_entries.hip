@@ -274,6 +274,53 @@ int depgan_op_conv3x3_wino_gathered(const float* in, long isB, long isY, long is
 }
 
 
+// ---- epilogue classes of the Winograd kernel (igemm_wino.hip): the switch, the selector, the name of a launch ----
+static_assert(DEPGAN_EPF_BIAS == DG_EPF_BIAS && DEPGAN_EPF_AFFINE == DG_EPF_AFFINE && DEPGAN_EPF_FILM == DG_EPF_FILM &&
+              DEPGAN_EPF_RELU == DG_EPF_RELU && DEPGAN_EPF_PRE == DG_EPF_PRE && DEPGAN_EPF_RES == DG_EPF_RES &&
+              DEPGAN_EPF_MASK == DG_EPF_MASK && DEPGAN_EPF_POOL == DG_EPF_POOL && DEPGAN_EPF_ACCUM == DG_EPF_ACCUM &&
+              DEPGAN_EPF_HEAD == DG_EPF_HEAD && DEPGAN_EPF_ALL == DG_EPF_ALL, "include/depgan.h and common.h");
+int depgan_set_epilogue_classes(int on) {
+  if (on != 0 && on != 1) { dg_set_error("set_epilogue_classes: 0 or 1, not %d", on); return DG_ERR_ARG; }
+  dg_set_epi_classes(on);
+  return DG_OK;
+}
+int depgan_get_epilogue_classes(void) { return dg_get_epi_classes(); }
+int depgan_wino_epilogue_class(unsigned flags, int form) {
+  if ((flags & ~(unsigned)DG_EPF_ALL) || form < 0 || form > 3) {
+    dg_set_error("wino_epilogue_class: flags 0x%x outside DEPGAN_EPF_ALL or form %d outside 0 ... 3", flags, form);
+    return -1;
+  }
+  return dg_wino_epi_class(flags, form);
+}
+int depgan_op_conv3x3_wino_kernel_name(unsigned flags, int B, int H, int W, int Cin, int Cout, char* buf, int cap) {
+  if ((flags & ~(unsigned)DG_EPF_ALL) || B < 1 || H < 1 || W < 1 || Cin < 1 || Cout < 1 || !buf || cap < 1) {
+    dg_set_error("op_conv3x3_wino_kernel_name: null or non-positive argument, or flags outside DEPGAN_EPF_ALL");
+    return DG_ERR_ARG;
+  }
+  // only which operands are present matters to the selection: every present one points at this float
+  static float present;
+  const TView pv = make_view(&present, H, W, Cout);
+  ConvArgs a = conv_args(make_view(&present, H, W, Cin), pv, B, H, W, Cin, Cout);
+  Epilogue& e = a.ep;
+  if (flags & DG_EPF_BIAS) e.bias = &present;
+  if (flags & DG_EPF_AFFINE) e.scale = e.shift = &present;
+  if (flags & DG_EPF_FILM) { e.film_mul = e.film_add = &present; e.film_ld = Cout; }
+  e.relu = (flags & DG_EPF_RELU) ? 1 : 0;
+  if (flags & DG_EPF_PRE) e.out_pre = pv;
+  if (flags & DG_EPF_RES) e.res = pv;
+  if (flags & DG_EPF_MASK) e.mask = pv;
+  if (flags & DG_EPF_POOL) e.pool = pv;
+  e.accumulate = (flags & DG_EPF_ACCUM) ? 1 : 0;
+  if (flags & DG_EPF_HEAD) { e.head_w = e.head_b = &present; e.head_out = &present; }
+  const ConvPlan pl = dg_plan_conv_wino(Cin, Cout);
+  if (!dg_plan_wino(pl) || !dg_conv_wino_supported(pl, a)) {
+    dg_set_error("op_conv3x3_wino_kernel_name: the Winograd kernel does not cover this shape");
+    return DG_ERR_UNSUPPORTED;
+  }
+  snprintf(buf, (size_t)cap, "%s", dg_conv_wino_name(a));
+  return DG_OK;
+}
+
 int depgan_op_deconv2x2_igemm(int form, const float* in, long isB, long isY, long isX, const float* w_hwoi,
                               const float* bias, const float* scale, const float* shift, float* out, long osB, long osY,
                               long osX, const float* mask, long msB, long msY, long msX, int B, int H, int W, int Cin,

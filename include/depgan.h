@@ -723,6 +723,38 @@ int depgan_op_conv2d_fused(const float* in, long isB, long isY, long isX, const 
 int depgan_op_conv3x3_wino_gathered(const float* in, long isB, long isY, long isX, const long* run_off, int runs,
                                     const float* w_hwio, const float* bias, float* out, long osB, long osY, long osX,
                                     int B, int H, int W, int Cin, int Cout, void* hip_stream);
+/* Epilogue classes of the Winograd 3x3 kernel: for each flag set of the fused epilogue that the model launches, an
+ * instantiation that carries the flags as compile-time constants (same statements, same bits as the generic kernel,
+ * fewer instructions per work item).  A flag set is a mask of DEPGAN_EPF_* -- which optional operands of
+ * depgan_op_conv2d_fused are present, in its order: bias, scale/shift, film_mul/film_add, relu, out_pre, res, mask, pool,
+ * accumulate, head_out.
+ * depgan_set_epilogue_classes(on): process-wide A/B switch, 1 (default) = launches take the class of their flag set,
+ *   0 = every launch takes the generic kernel; any other value is status 1.  The environment variable
+ *   DEPGAN_EPI_CLASSES=0 sets the initial state to 0.  depgan_get_epilogue_classes() returns the state.
+ * depgan_wino_epilogue_class(flags, form): host only, no HIP call: the class id a launch with this flag set takes.
+ *   form 0: the 8-row kernel (wino_conv_kernel<1,...>), 1: the fused-head kernel, 2: the 16-row kernel without head,
+ *   3: gathered K.  0 = the generic kernel: sets outside the table, forms 2 and 3, everything while the switch is off.
+ *   -1 (and a message) for flags outside DEPGAN_EPF_ALL or a form outside 0 ... 3.
+ * depgan_op_conv3x3_wino_kernel_name: the kernel instantiation (as rocprofv3 prints it, e.g. "wino_conv_kernel<1,true,1>":
+ *   8-row tiles, persistent grid, class 1) that depgan_op_conv2d_fused on path 8 launches for a (B, H, W, Cin) -> Cout
+ *   convolution with this flag set on the current device, from the same selection function the launcher calls; written
+ *   to buf (cap bytes, NUL-terminated).  Launches nothing.  Status 1 for bad arguments, 3 for a shape the kernel does
+ *   not cover. */
+#define DEPGAN_EPF_BIAS 1
+#define DEPGAN_EPF_AFFINE 2
+#define DEPGAN_EPF_FILM 4
+#define DEPGAN_EPF_RELU 8
+#define DEPGAN_EPF_PRE 16
+#define DEPGAN_EPF_RES 32
+#define DEPGAN_EPF_MASK 64
+#define DEPGAN_EPF_POOL 128
+#define DEPGAN_EPF_ACCUM 256
+#define DEPGAN_EPF_HEAD 512
+#define DEPGAN_EPF_ALL 1023
+int depgan_set_epilogue_classes(int on);
+int depgan_get_epilogue_classes(void);
+int depgan_wino_epilogue_class(unsigned flags, int form);
+int depgan_op_conv3x3_wino_kernel_name(unsigned flags, int B, int H, int W, int Cin, int Cout, char* buf, int cap);
 /* The 2x2 / stride-2 transposed convolution on the implicit-GEMM kernels, w_hwoi the Keras kernel (2, 2, Cout, Cin).
  * form 0: forward as ONE grouped launch of four 1x1 convolutions: in (B, H, W, Cin) -> out (B, 2H, 2W, Cout), with
  *         bias / scale+shift / relu; mask must be NULL.
