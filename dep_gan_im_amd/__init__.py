@@ -17,3 +17,4 @@ from .trainers import Trainers, build_trainers  # noqa: F401
 from .engine import Engine  # noqa: F401
 from . import evaluate  # noqa: F401,E402
 from . import data, nifti  # noqa: F401,E402
+from . import callbacks  # noqa: F401,E402

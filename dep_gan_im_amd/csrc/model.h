@@ -34,6 +34,13 @@ struct Net {
   unsigned char* qmask = nullptr;   // 1 where Pq is rounded
   long adam_t = 0;
   float lr = 1e-4f;
+  // depgan_set_optimizer (all 0: net_adam launches the plain kernel).  decay_bits: bit i set where element i of the
+  // arena belongs to a "/kernel" tensor; gnorm: 3 doubles on the device, the squared norm, the norm and the scale of the
+  // last clipped update (both allocated by the first call that turns an option on)
+  float clipnorm = 0.f, clipvalue = 0.f, weight_decay = 0.f;
+  unsigned* decay_bits = nullptr;
+  double* gnorm = nullptr;
+  bool gnorm_valid = false;
   void add(const std::string& name, std::vector<int> shape, bool trainable);
   float* p(const std::string& name) const;   // parameter pointer the kernels read (either arena; Pq when quantised)
   float* g(const std::string& name) const;   // gradient pointer (trainable only)

@@ -7,6 +7,7 @@
 #include "train_ops.h"
 
 #include <dlfcn.h>
+#include <float.h>
 #include <math.h>
 #include <stdlib.h>
 #include <stdarg.h>
@@ -1016,8 +1017,40 @@ int net_adam(depgan_ctx* c, Net& n, float gscale) {
   const double b1 = c->cfg.beta1, b2 = c->cfg.beta2;
   const double t = (double)n.adam_t;
   const double lr_t = n.lr * sqrt(1.0 - pow(b2, t)) / (1.0 - pow(b1, t));
-  ProfScope ps(c, 2, 0.0, "adam");
-  return dg_adam(n.P, n.G, n.M, n.V, n.nTrain, (float)lr_t, (float)b1, (float)b2, c->cfg.adam_eps, gscale, c->st);
+  if (n.clipnorm == 0.f && n.clipvalue == 0.f && n.weight_decay == 0.f) {
+    ProfScope ps(c, 2, 0.0, "adam");
+    return dg_adam(n.P, n.G, n.M, n.V, n.nTrain, (float)lr_t, (float)b1, (float)b2, c->cfg.adam_eps, gscale, c->st);
+  }
+  // the norm of what the update applies (under data parallelism the averaged gradient: gscale = 1 / world), read by the
+  // option kernel on the device.  A norm that is not finite leaves the arenas alone; adam_t has advanced all the same
+  if (n.clipnorm > 0.f) {
+    ProfScope ps(c, 2, 0.0, "grad sqnorm");
+    DGCHECK(dg_grad_sqnorm(n.G, n.nTrain, gscale, c->scratch, c->scratchFloats, n.gnorm, c->st));
+    n.gnorm_valid = true;
+  }
+  ProfScope ps(c, 2, 0.0, "adam opts");
+  return dg_adam_opts(n.P, n.G, n.M, n.V, n.nTrain, (float)lr_t, n.lr, (float)b1, (float)b2, c->cfg.adam_eps, gscale,
+                      n.clipnorm, n.clipvalue, n.weight_decay, n.decay_bits, n.gnorm, c->st);
+}
+
+// the decay bits and the norm slot of a network, at the first depgan_set_optimizer call that turns an option on
+static int net_opt_alloc(depgan_ctx* c, Net& n) {
+  if (n.gnorm) return DG_OK;
+  const size_t words = (n.nTrain + 31) / 32 + 1;
+  std::vector<unsigned> bits(words, 0u);
+  for (const PInfo& pi : n.params) {
+    const std::string& nm = pi.name;
+    if (pi.trainable && nm.size() > 7 && nm.compare(nm.size() - 7, 7, "/kernel") == 0)
+      for (size_t i = pi.off; i < pi.off + pi.size; ++i) bits[i >> 5] |= 1u << (i & 31);
+  }
+  void* b = nullptr;
+  HIPCHECK(dalloc_bytes(c, &b, words * sizeof(unsigned)));
+  HIPCHECK(hipMemcpy(b, bits.data(), words * sizeof(unsigned), hipMemcpyHostToDevice));
+  void* g = nullptr;
+  HIPCHECK(dalloc_bytes(c, &g, 4 * sizeof(double)));
+  n.decay_bits = (unsigned*)b;
+  n.gnorm = (double*)g;
+  return DG_OK;
 }
 
 // ---------------------------------------------------------------------------
@@ -1614,6 +1647,64 @@ int depgan_set_adam_step(depgan_ctx* c, int net, long t) {
   Net* n = pick_net(c, net);
   if (!n || t < 0) { dg_set_error("set_adam_step: bad argument"); return DG_ERR_ARG; }
   n->adam_t = t;
+  return DG_OK;
+}
+
+int depgan_set_lr(depgan_ctx* c, int net, float lr) {
+  if (!(lr > 0.f) || lr > FLT_MAX) { dg_set_error("depgan_set_lr: lr is %g (finite and > 0)", (double)lr); return DG_ERR_ARG; }
+  Net* n = c ? pick_net(c, net) : nullptr;
+  if (!n) { dg_set_error("depgan_set_lr: null context or unknown network %d", net); return DG_ERR_ARG; }
+  n->lr = lr;
+  return DG_OK;
+}
+int depgan_get_lr(depgan_ctx* c, int net, float* lr) {
+  Net* n = c ? pick_net(c, net) : nullptr;
+  if (!n || !lr) { dg_set_error("depgan_get_lr: null argument or unknown network %d", net); return DG_ERR_ARG; }
+  *lr = n->lr;
+  return DG_OK;
+}
+
+int depgan_set_optimizer(depgan_ctx* c, int net, float clipnorm, float clipvalue, float weight_decay) {
+  const float vals[3] = {clipnorm, clipvalue, weight_decay};
+  const char* names[3] = {"clipnorm", "clipvalue", "weight_decay"};
+  for (int k = 0; k < 3; ++k)
+    if (!(vals[k] >= 0.f) || vals[k] > FLT_MAX) {
+      dg_set_error("depgan_set_optimizer: %s is %g (finite and >= 0; 0 is off)", names[k], (double)vals[k]);
+      return DG_ERR_ARG;
+    }
+  if (!c) { dg_set_error("depgan_set_optimizer: null context"); return DG_ERR_ARG; }
+  DGCHECK(infer_refuse(c, "depgan_set_optimizer"));
+  Net* n = pick_net(c, net);
+  if (!n) { dg_set_error("depgan_set_optimizer: unknown network %d", net); return DG_ERR_ARG; }
+  if (clipnorm != 0.f || clipvalue != 0.f || weight_decay != 0.f) {
+    if (!n->G) { dg_set_error("depgan_set_optimizer: this context does not train network %d", net); return DG_ERR_ARG; }
+    DGCHECK(net_opt_alloc(c, *n));
+  }
+  n->clipnorm = clipnorm;
+  n->clipvalue = clipvalue;
+  n->weight_decay = weight_decay;
+  return DG_OK;
+}
+int depgan_get_optimizer(depgan_ctx* c, int net, float* clipnorm, float* clipvalue, float* weight_decay) {
+  Net* n = c ? pick_net(c, net) : nullptr;
+  if (!n) return 0;
+  if (clipnorm) *clipnorm = n->clipnorm;
+  if (clipvalue) *clipvalue = n->clipvalue;
+  if (weight_decay) *weight_decay = n->weight_decay;
+  return (n->clipnorm != 0.f || n->clipvalue != 0.f || n->weight_decay != 0.f) ? 1 : 0;
+}
+int depgan_last_grad_norm(depgan_ctx* c, int net, double* norm, float* scale) {
+  Net* n = c ? pick_net(c, net) : nullptr;
+  if (!n) { dg_set_error("depgan_last_grad_norm: null context or unknown network %d", net); return DG_ERR_ARG; }
+  if (!n->gnorm_valid) {
+    dg_set_error("depgan_last_grad_norm: no update of network %d has run with clipnorm on (depgan_set_optimizer)", net);
+    return DG_ERR_ARG;
+  }
+  double h[3];
+  HIPCHECK(hipMemcpyAsync(h, n->gnorm, sizeof(h), hipMemcpyDeviceToHost, c->st));
+  HIPCHECK(hipStreamSynchronize(c->st));
+  if (norm) *norm = h[1];
+  if (scale) *scale = (float)h[2];
   return DG_OK;
 }
 

@@ -991,4 +991,64 @@ int depgan_op_round_bf16_masked(const float* src, const unsigned char* mask, flo
   return dg_round_bf16_masked(src, mask, dst, (size_t)n, (hipStream_t)stream);
 }
 
+int depgan_op_grad_sqnorm(const float* g, long n, float gscale, double* out_host, void* stream) {
+  if (!g || n < 1 || !out_host) { dg_set_error("op_grad_sqnorm: bad argument"); return DG_ERR_ARG; }
+  hipStream_t st = (hipStream_t)stream;
+  DevTmp out(st);
+  if (out.alloc(sizeof(double)) != DG_OK) { dg_set_error("op_grad_sqnorm: out of device memory"); return DG_ERR_HIP; }
+  DGCHECK(op_with_scratch(0, dg_grad_sqnorm_scratch((size_t)n), "op_grad_sqnorm", st, [&](float* scratch, size_t cap) {
+    return dg_grad_sqnorm(g, (size_t)n, gscale, scratch, cap, out.as<double>(), st);
+  }));
+  HIPCHECK(hipMemcpyAsync(out_host, out.p, sizeof(double), hipMemcpyDeviceToHost, st));
+  HIPCHECK(hipStreamSynchronize(st));
+  return DG_OK;
+}
+
+int depgan_op_adam_opts(float* p, const float* g, float* m, float* v, long n, float lr_t, float lr, float b1, float b2,
+                        float eps, float gscale, float clipnorm, float clipvalue, float weight_decay,
+                        const long* seg_end_host, const int* seg_decay_host, int nseg, double* norm_host, void* stream) {
+  if (!p || !g || !m || !v || n < 1 || !(clipnorm >= 0.f) || !(clipvalue >= 0.f) || !(weight_decay >= 0.f) ||
+      nseg < 0 || (nseg > 0 && (!seg_end_host || !seg_decay_host)) || (clipnorm > 0.f && !norm_host)) {
+    dg_set_error("op_adam_opts: bad argument");
+    return DG_ERR_ARG;
+  }
+  // the segments tile [0, n): ends ascending, the last one n
+  long at = 0;
+  for (int s = 0; s < nseg; ++s) {
+    if (seg_end_host[s] <= at || seg_end_host[s] > n) { dg_set_error("op_adam_opts: segment ends must ascend within (0, n]"); return DG_ERR_ARG; }
+    at = seg_end_host[s];
+  }
+  if (nseg > 0 && at != n) { dg_set_error("op_adam_opts: the last segment must end at n"); return DG_ERR_ARG; }
+  hipStream_t st = (hipStream_t)stream;
+  const size_t words = ((size_t)n + 31) / 32;
+  std::vector<unsigned> bits(words, 0u);
+  at = 0;
+  for (int s = 0; s < nseg; ++s) {
+    if (seg_decay_host[s])
+      for (long i = at; i < seg_end_host[s]; ++i) bits[(size_t)i >> 5] |= 1u << (i & 31);
+    at = seg_end_host[s];
+  }
+  DevTmp dbits(st), nrm(st);
+  if (dbits.alloc(words * sizeof(unsigned)) != DG_OK || nrm.alloc(4 * sizeof(double)) != DG_OK) {
+    dg_set_error("op_adam_opts: out of device memory");
+    return DG_ERR_HIP;
+  }
+  HIPCHECK(hipMemcpyAsync(dbits.p, bits.data(), words * sizeof(unsigned), hipMemcpyHostToDevice, st));
+  HIPCHECK(hipMemsetAsync(nrm.p, 0, 4 * sizeof(double), st));
+  if (clipnorm > 0.f)
+    DGCHECK(op_with_scratch(0, dg_grad_sqnorm_scratch((size_t)n), "op_adam_opts", st, [&](float* scratch, size_t cap) {
+      return dg_grad_sqnorm(g, (size_t)n, gscale, scratch, cap, nrm.as<double>(), st);
+    }));
+  DGCHECK(dg_adam_opts(p, g, m, v, (size_t)n, lr_t, lr, b1, b2, eps, gscale, clipnorm, clipvalue, weight_decay,
+                       dbits.as<unsigned>(), nrm.as<double>(), st));
+  double h[3] = {0.0, 0.0, 1.0};
+  if (clipnorm > 0.f) HIPCHECK(hipMemcpyAsync(h, nrm.p, sizeof(h), hipMemcpyDeviceToHost, st));
+  HIPCHECK(hipStreamSynchronize(st));
+  if (norm_host) {
+    norm_host[0] = h[1];
+    norm_host[1] = h[2];
+  }
+  return DG_OK;
+}
+
 }  // extern "C"

@@ -108,6 +108,20 @@ int dg_bn_gamma_grad(const float* W, const float* dWraw, int K, int Cout, int oi
 // gscale multiplies the gradient first (1/world after a summing all-reduce; 1 otherwise)
 int dg_adam(float* p, const float* g, float* m, float* v, size_t n, float lr_t, float b1, float b2, float eps,
             float gscale, hipStream_t st);
+// out_dev[0] = sum_i ((double)(g[i] * gscale))^2, one double in device memory; deterministic (the grid depends on n
+// alone, no atomics).  g 16-byte aligned, scratch and out_dev 8-byte aligned.
+// scratch: dg_grad_sqnorm_scratch(n) floats (one double per block, at most 1024 blocks); DG_ERR_ARG when less
+int dg_grad_sqnorm(const float* g, size_t n, float gscale, float* scratch, size_t scratch_floats, double* out_dev,
+                   hipStream_t st);
+size_t dg_grad_sqnorm_scratch(size_t n);
+// dg_adam with options, one launch.  clipnorm > 0: Keras 2's global-norm clip from the squared norm in nrm[0] (device,
+// 3 doubles: dg_grad_sqnorm's result in, [1] the norm and [2] the scale used out; a squared norm that is not finite
+// leaves p, m and v as they were and reports scale 0).  clipvalue > 0: the scaled gradient clamped to +-clipvalue.
+// weight_decay > 0: p <- p - (lr * weight_decay) p first, where bit i of decay_bits ((n + 31) / 32 words) is set.
+// 0 turns an option off; nrm / decay_bits may be null while theirs is off.
+int dg_adam_opts(float* p, const float* g, float* m, float* v, size_t n, float lr_t, float lr, float b1, float b2,
+                 float eps, float gscale, float clipnorm, float clipvalue, float weight_decay,
+                 const unsigned* decay_bits, double* nrm, hipStream_t st);
 
 int dg_scale_copy(const float* in, float* out, size_t n, float s, hipStream_t st);
 int dg_mean_groups(const float* in, float* out, int groups, int per, hipStream_t st);

@@ -2,6 +2,7 @@
 // over the contiguous channel axis, reductions as wave-shuffle -> LDS -> a
 // second deterministic pass (no float atomics).
 #include "ops.h"
+#include <float.h>
 #include <hip/hip_bf16.h>
 #include "epilogue.h"
 
@@ -867,6 +868,116 @@ __global__ void adam_kernel(float* __restrict__ p, const float* __restrict__ g, 
 int dg_adam(float* p, const float* g, float* m, float* v, size_t n, float lr_t, float b1, float b2, float eps,
             float gscale, hipStream_t st) {
   hipLaunchKernelGGL(adam_kernel, dim3(nblk(n, 2048)), dim3(256), 0, st, p, g, m, v, n, lr_t, b1, b2, eps, gscale);
+  HIPCHECK(hipGetLastError());
+  return DG_OK;
+}
+
+// Squared global norm of the scaled gradient, sum_i ((double)(g[i] * gscale))^2.  Two stages, no atomics: a grid-stride
+// pass over 16-byte quads with one double partial per block, then one block that adds the partials in index order.  The
+// product g[i] * gscale is the float the Adam kernels form; its square is exact in double, so only the additions round.
+// The grid depends on n alone, and with it the order of every addition.
+static inline int sqnorm_nblk(size_t n) {
+  size_t b = ((n >> 2) + 255) / 256;
+  return (int)(b > 1024 ? 1024 : (b < 1 ? 1 : b));
+}
+__global__ __launch_bounds__(256) void grad_sqnorm_partial(const float* __restrict__ g, size_t n, float gscale,
+                                                           double* __restrict__ part) {
+  __shared__ double sh4[4];
+  const size_t nv = n >> 2;
+  double acc = 0.0;
+  for (size_t q = blockIdx.x * (size_t)256 + threadIdx.x; q < nv; q += (size_t)gridDim.x * 256) {
+    const f32x4 a = *reinterpret_cast<const f32x4*>(g + 4 * q);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const double x = (double)(a[k] * gscale);
+      acc += x * x;
+    }
+  }
+  // the n % 4 elements behind the last quad
+  if (blockIdx.x == 0 && threadIdx.x == 0)
+    for (size_t i = nv << 2; i < n; ++i) {
+      const double x = (double)(g[i] * gscale);
+      acc += x * x;
+    }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) acc += __shfl_down(acc, o, 64);
+  if ((threadIdx.x & 63) == 0) sh4[threadIdx.x >> 6] = acc;
+  __syncthreads();
+  if (threadIdx.x == 0) part[blockIdx.x] = (sh4[0] + sh4[1]) + (sh4[2] + sh4[3]);
+}
+__global__ __launch_bounds__(256) void grad_sqnorm_final(const double* __restrict__ part, int nb,
+                                                         double* __restrict__ out) {
+  __shared__ double sh[1024];
+  for (int e = threadIdx.x; e < nb; e += 256) sh[e] = part[e];
+  __syncthreads();
+  if (threadIdx.x != 0) return;
+  double a = 0.0;
+  for (int b = 0; b < nb; ++b) a += sh[b];
+  out[0] = a;
+}
+size_t dg_grad_sqnorm_scratch(size_t n) { return (size_t)sqnorm_nblk(n) * 2; }
+int dg_grad_sqnorm(const float* g, size_t n, float gscale, float* scratch, size_t scratch_floats, double* out_dev,
+                   hipStream_t st) {
+  if (!g || n < 1 || !out_dev || ((uintptr_t)g & 15) || ((uintptr_t)out_dev & 7) || ((uintptr_t)scratch & 7)) {
+    dg_set_error("dg_grad_sqnorm: null or misaligned argument (g 16-byte, scratch and out 8-byte aligned), or n < 1");
+    return DG_ERR_ARG;
+  }
+  if (!scratch || !scratch_ok("dg_grad_sqnorm", dg_grad_sqnorm_scratch(n), scratch_floats)) return DG_ERR_ARG;
+  const int nb = sqnorm_nblk(n);
+  double* part = reinterpret_cast<double*>(scratch);
+  hipLaunchKernelGGL(grad_sqnorm_partial, dim3(nb), dim3(256), 0, st, g, n, gscale, part);
+  HIPCHECK(hipGetLastError());
+  hipLaunchKernelGGL(grad_sqnorm_final, dim3(1), dim3(256), 0, st, part, nb, out_dev);
+  HIPCHECK(hipGetLastError());
+  return DG_OK;
+}
+
+// Adam with options, one launch over the arena.  Everything it shares with adam_kernel keeps that kernel's expressions
+// and their order, so an option that does not act (a scale of 1, a clip above every |g|, an element that is not
+// decayed) leaves the plain kernel's bits.
+//   clipnorm > 0:  nrm[0] holds the squared norm (dg_grad_sqnorm on the same g and gscale).  norm = sqrt(nrm[0]) in
+//                  double, s = norm >= clipnorm ? (float)(clipnorm / norm) : 1, gi = g[i] * gscale * s.  A squared norm
+//                  that is not finite ends every thread before it writes: the test is on one value the whole grid reads.
+//                  Thread 0 leaves norm in nrm[1] and s in nrm[2] (0 for the refused update).
+//   clipvalue > 0: gi clamped to [-clipvalue, clipvalue] after the scaling (a NaN stays a NaN).
+//   lrwd > 0:      p <- p - lrwd p before the Adam displacement where bit i of decay_bits is set (lrwd = lr * wd).
+__global__ void adam_opts_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                 float* __restrict__ v, size_t n, float lr_t, float b1, float b2, float eps,
+                                 float gscale, float clipnorm, float clipvalue, float lrwd,
+                                 const unsigned* __restrict__ decay_bits, double* __restrict__ nrm) {
+  float s = 1.0f;
+  if (clipnorm > 0.f) {
+    const double sq = nrm[0];
+    const double norm = sqrt(sq);
+    const bool finite = sq <= DBL_MAX;   // false for a NaN too; a sum of squares is never negative
+    if (finite) s = (norm >= (double)clipnorm) ? (float)((double)clipnorm / norm) : 1.0f;
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+      nrm[1] = norm;
+      nrm[2] = finite ? (double)s : 0.0;
+    }
+    if (!finite) return;
+  }
+  for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+    float gi = g[i] * gscale * s;
+    if (clipvalue > 0.f) gi = gi < -clipvalue ? -clipvalue : (gi > clipvalue ? clipvalue : gi);
+    float pi = p[i];
+    if (lrwd > 0.f && ((decay_bits[i >> 5] >> (i & 31)) & 1u)) pi = __fmaf_rn(-lrwd, pi, pi);
+    const float mi = b1 * m[i] + (1.0f - b1) * gi;
+    const float vi = b2 * v[i] + (1.0f - b2) * gi * gi;
+    m[i] = mi;
+    v[i] = vi;
+    p[i] = pi - lr_t * mi / (sqrtf(vi) + eps);
+  }
+}
+int dg_adam_opts(float* p, const float* g, float* m, float* v, size_t n, float lr_t, float lr, float b1, float b2,
+                 float eps, float gscale, float clipnorm, float clipvalue, float weight_decay,
+                 const unsigned* decay_bits, double* nrm, hipStream_t st) {
+  if ((clipnorm > 0.f && (!nrm || ((uintptr_t)nrm & 7))) || (weight_decay > 0.f && !decay_bits)) {
+    dg_set_error("dg_adam_opts: clipnorm without the norm's device slot, or weight_decay without the decay bits");
+    return DG_ERR_ARG;
+  }
+  hipLaunchKernelGGL(adam_opts_kernel, dim3(nblk(n, 2048)), dim3(256), 0, st, p, g, m, v, n, lr_t, b1, b2, eps, gscale,
+                     clipnorm, clipvalue, lr * weight_decay, decay_bits, nrm);
   HIPCHECK(hipGetLastError());
   return DG_OK;
 }

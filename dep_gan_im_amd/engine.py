@@ -696,6 +696,61 @@ class Engine:
         self._use_current_stream()
         check(self.lib.depgan_apply_adam(self.h, NET_IDS[net]), "depgan_apply_adam")
 
+    # ---- optimiser options (depgan_set_lr, depgan_set_optimizer) ----
+    @staticmethod
+    def _opt_number(v, name, positive):
+        """`v` as a float that is finite and > 0 (`positive`) or >= 0 once rounded to float32; ValueError otherwise.
+        None stands for 0 (off) where 0 is allowed.  No library call."""
+        if v is None and not positive:
+            return 0.0
+        if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)):
+            raise ValueError("%s must be a number, got %r" % (name, v))
+        with np.errstate(over="ignore"):
+            v32 = float(np.float32(v))
+        if not np.isfinite(v32) or (v32 <= 0 if positive else v32 < 0):
+            raise ValueError("%s must be finite and %s 0 (as float32), got %r" % (name, ">" if positive else ">=", v))
+        return float(v)
+
+    def set_lr(self, net, lr):
+        """depgan_set_lr: the learning rate of one network's Adam, from the next update on (host only)."""
+        check(self.lib.depgan_set_lr(self.h, NET_IDS[net], self._opt_number(lr, "lr", True)), "depgan_set_lr")
+
+    def lr(self, net):
+        """The learning rate the next update of `net` uses, as the library holds it (a float32 value)."""
+        v = C.c_float()
+        check(self.lib.depgan_get_lr(self.h, NET_IDS[net], C.byref(v)), "depgan_get_lr")
+        return v.value
+
+    def set_optimizer(self, net, clipnorm=0, clipvalue=0, weight_decay=0):
+        """depgan_set_optimizer: options of every Adam update of `net`, each finite and >= 0 with 0 (or None) = off.
+        clipnorm: the gradient is scaled by clipnorm / norm when its global L2 norm (over all tensors, taken on the
+        device in front of the update) reaches clipnorm -- standalone Keras 2's clipnorm; an update whose norm is not
+        finite changes no weight and no Adam moment, though adam_step still counts it.  clipvalue: every gradient
+        element is then clamped to +-clipvalue.  weight_decay: decoupled decay (AdamW), p <- p - lr * weight_decay * p
+        before the Adam displacement, on the "/kernel" tensors only (never biases or BatchNorm gamma / beta).  All off
+        (the default) is the plain update, bit for bit."""
+        vals = [self._opt_number(v, n, False) for v, n in ((clipnorm, "clipnorm"), (clipvalue, "clipvalue"),
+                                                           (weight_decay, "weight_decay"))]
+        if any(vals):
+            self._need_trainable("set_optimizer")
+        check(self.lib.depgan_set_optimizer(self.h, NET_IDS[net], *vals), "depgan_set_optimizer")
+
+    def optimizer(self, net):
+        """None with every option off, else a dict of 'clipnorm', 'clipvalue' and 'weight_decay' (float32 values)."""
+        a, b, w = C.c_float(), C.c_float(), C.c_float()
+        if not self.lib.depgan_get_optimizer(self.h, NET_IDS[net], C.byref(a), C.byref(b), C.byref(w)):
+            return None
+        return {"clipnorm": a.value, "clipvalue": b.value, "weight_decay": w.value}
+
+    def grad_norm(self, net):
+        """(norm, scale) of the last update of `net` made with clipnorm on: the global L2 norm of the gradient the
+        update applied (float64, summed on the device) and the float32 factor it was scaled by (1.0: not clipped; 0.0:
+        the norm was not finite and the update was skipped).  Waits for the stream (depgan_last_grad_norm)."""
+        norm, scale = C.c_double(), C.c_float()
+        check(self.lib.depgan_last_grad_norm(self.h, NET_IDS[net], C.byref(norm), C.byref(scale)),
+              "depgan_last_grad_norm")
+        return norm.value, scale.value
+
     def last_sums(self):
         out = (C.c_float * 8)()
         check(self.lib.depgan_last_sums(self.h, out), "depgan_last_sums")

@@ -303,6 +303,8 @@ class GeneratorModel(_Model):
         self._class_weight, self._ignore_label = None, None      # compile(class_weight=, ignore_label=)
         self._dice = None                                        # compile(dice_loss=...): Engine.set_dice_loss's arguments
         self._focal = None                                       # compile(focal_gamma=, label_smoothing=), None when off
+        self._opt = None                                         # compile(clipnorm=, clipvalue=, weight_decay=), None when off
+        self.stop_training = False                               # a fit callback sets it to end fit after the epoch
         self._drop_rng = np.random.RandomState(seed)
 
     def _static_table(self):
@@ -334,6 +336,8 @@ class GeneratorModel(_Model):
             engine.set_dice_loss(**self._dice)
         if self._focal is not None:
             engine.set_focal(*self._focal)
+        if self._opt is not None:
+            engine.set_optimizer(net, **self._opt)
 
     def inference_copy(self, dtype="bfloat16"):
         """A new predict-only model with this architecture and a copy of the current weights, whose private engine runs
@@ -419,6 +423,17 @@ class GeneratorModel(_Model):
             out.append(float(v))
         return None if out[0] == 0.0 and out[1] == 0.0 else tuple(out)
 
+    def _opt_args(self, optimizer, clipnorm, clipvalue, weight_decay):
+        """compile's clipnorm / clipvalue / weight_decay (an argument wins over the optimizer object's attribute of that
+        name) as the keyword arguments of Engine.set_optimizer, or None with all of them off; ValueError otherwise.
+        Needs no engine."""
+        out = {}
+        for name, v in (("clipnorm", clipnorm), ("clipvalue", clipvalue), ("weight_decay", weight_decay)):
+            if v is None:
+                v = getattr(optimizer, name, None)
+            out[name] = Engine._opt_number(v, name, False)
+        return out if any(out.values()) else None
+
     def _dice_args(self, loss, dice_loss, dice_weight, ce_weight, dice_smooth, dice_classes):
         """compile's Dice arguments as the keyword arguments of Engine.set_dice_loss, or None with the mode off;
         ValueError otherwise.  Needs no engine."""
@@ -466,7 +481,7 @@ class GeneratorModel(_Model):
 
     def compile(self, optimizer="adam", loss="categorical_crossentropy", lr=None, metrics=None, class_weight=None,
                 ignore_label=None, dice_loss=None, dice_weight=1.0, ce_weight=1.0, dice_smooth=1e-7, dice_classes=None,
-                focal_gamma=0.0, label_smoothing=0.0, **_):
+                focal_gamma=0.0, label_smoothing=0.0, clipnorm=None, clipvalue=None, weight_decay=None, **_):
         """model.compile(optimizer=Adam(lr=1e-4), loss='categorical_crossentropy')  (UT:427).
         metrics: names out of 'acc' / 'accuracy' (pixel accuracy: Keras' categorical_accuracy, arg-max against arg-max),
         'dice' and 'iou' (the means over the foreground classes 1..nc_out-1, evaluate.confusion_metrics).  They come from
@@ -502,13 +517,21 @@ class GeneratorModel(_Model):
         metrics (which keep reading the original labels) and dice_loss (the Dice term reads the original labels; with
         ce_weight = 0 they change nothing but the reported cross-entropy sums).  The loss is then the sum over the
         number of pixels with a non-zero weight, as with class_weight: with one-hot labels an all-zero row is an
-        ignored pixel.  compile() without them turns the mode off; then every result is what it was without the mode."""
+        ignored pixel.  compile() without them turns the mode off; then every result is what it was without the mode.
+        clipnorm, clipvalue, weight_decay: options of the Adam update (Engine.set_optimizer), each finite and >= 0 with
+        None or 0 = off; they are also read from attributes of those names on an `optimizer` object, as lr is.  clipnorm
+        scales the whole gradient by clipnorm / norm once its global L2 norm reaches clipnorm (standalone Keras 2's
+        clipnorm; Engine.grad_norm reads the norm back), clipvalue then clamps every element, weight_decay is AdamW's
+        decoupled decay on the kernels (not biases, not BatchNorm).  All of it runs inside the update's own launches
+        on the device.  compile() without them is the plain Adam update, bit for bit.  The rate itself can change at
+        any time: model.set_lr(lr), or fit(callbacks=[...]) with dep_gan_im_amd.callbacks."""
         self._need_softmax("compile")
         if loss not in _LOSSES + (_DICE_LOSS,):
             raise ValueError("loss must be 'categorical_crossentropy' (UT:427), 'sparse_categorical_crossentropy' or "
                              "'dice_coef_loss' (UT:120), got %r" % (loss,))
         dice = self._dice_args(loss, dice_loss, dice_weight, ce_weight, dice_smooth, dice_classes)
         focal = self._focal_args(focal_gamma, label_smoothing)
+        opt = self._opt_args(optimizer, clipnorm, clipvalue, weight_decay)
         was_on = self._class_weight is not None or self._ignore_label is not None
         self._class_weight, self._ignore_label = self._loss_weight_args(loss, class_weight, ignore_label)
         if self._engine is not None and (self._dice is not None or dice is not None):
@@ -519,6 +542,9 @@ class GeneratorModel(_Model):
         if self._engine is not None and (self._focal is not None or focal is not None):
             self._engine.set_focal(*(focal or (0.0, 0.0)))
         self._focal = focal
+        if self._engine is not None and (self._opt is not None or opt is not None):
+            self._engine.set_optimizer(self.net, **(opt or {}))
+        self._opt = opt
         if metrics is not None:
             if isinstance(metrics, str):
                 metrics = [metrics]
@@ -537,6 +563,21 @@ class GeneratorModel(_Model):
                 raise RuntimeError("compile(lr=...) must come before the first fit / train_on_batch / predict")
             self._lr = float(lr)
         return self
+
+    @property
+    def lr(self):
+        """The learning rate the next update uses: compile's until an engine exists, then the engine's own (a float32
+        value), which set_lr and the callbacks of fit change."""
+        return self._lr if self._engine is None else self._engine.lr(self.net)
+
+    def set_lr(self, lr):
+        """Sets the learning rate, before or after the first use; on an engine it takes effect at the next update
+        (Engine.set_lr).  Finite and > 0."""
+        self._need_softmax("set_lr")
+        lr = Engine._opt_number(lr, "lr", True)
+        if self._engine is not None:
+            self._engine.set_lr(self.net, lr)
+        self._lr = lr
 
     def _check_labels(self, labels, n, what):
         """The labels' shape against the compiled loss, before anything reaches the library."""
@@ -603,7 +644,7 @@ class GeneratorModel(_Model):
         return [loss] + self._metric_values(cm) if self._metrics else loss
 
     def fit(self, inputs, labels, epochs=1, batch_size=32, shuffle=True, validation_data=None, verbose=1,
-            print_fn=print, augment=None):
+            print_fn=print, augment=None, callbacks=None):
         """my_network.fit([flair, noise], onehot, epochs=1, batch_size=nb_samples, shuffle=..., validation_data=...)
         (UT:602-606).  Batches in index order (after an optional np.random shuffle, as keras does), a short last
         batch, per-epoch loss = sample-weighted mean of the batch losses; returns an object with .history.  With
@@ -618,7 +659,12 @@ class GeneratorModel(_Model):
         are never formed.  Otherwise the batch is sliced as without it, uploaded and augmented.  The noise is gathered
         as before and validation data is never augmented.  With compile(ignore_label=k),
         Augmenter(border='constant', label_fill=k) keeps the pixels a warp brings in from outside the image out of the
-        loss (one-hot labels: label_fill=-1, the all-zero row).  None (the default) leaves every batch as it was."""
+        loss (one-hot labels: label_fill=-1, the all-zero row).  None (the default) leaves every batch as it was.
+        callbacks: a list of dep_gan_im_amd.callbacks objects (ReduceLROnPlateau, EarlyStopping, LearningRateScheduler,
+        ModelCheckpoint, or anything with their hooks).  Each gets on_train_begin(), per epoch on_epoch_begin(epoch)
+        and on_epoch_end(epoch, logs) with logs = the epoch's history entries plus 'lr', and on_train_end().
+        history['lr'] then records the rate every epoch trained with and the progress line shows it; a callback that
+        sets model.stop_training = True ends fit after that epoch.  None (the default) changes nothing."""
         self._need_softmax("fit")
         x, z = inputs
         n = len(x)
@@ -635,6 +681,14 @@ class GeneratorModel(_Model):
             hist["val_loss"] = []
             hist.update(("val_" + name, []) for name in self._metrics)
         census = {"train": [], "val": []} if self._metrics else None
+        callbacks = list(callbacks) if callbacks is not None else None
+        if callbacks is not None:
+            hist["lr"] = []
+            self.stop_training = False
+            for cb in callbacks:
+                if hasattr(cb, "set_model"):
+                    cb.set_model(self)
+                cb.on_train_begin()
         if augment is not None:
             import torch
             from .data import Augmenter
@@ -646,6 +700,8 @@ class GeneratorModel(_Model):
                         and labels.dtype == (torch.uint8 if self._loss == "sparse_categorical_crossentropy"
                                              else torch.float32))
         for ep in range(epochs):
+            for cb in callbacks or ():
+                cb.on_epoch_begin(ep)
             order = np.arange(n)
             if shuffle:
                 np.random.shuffle(order)
@@ -680,8 +736,19 @@ class GeneratorModel(_Model):
                         msg += " - val_%s: %.4f" % (name, v)
             if self._metrics and verbose:
                 msg += " - census train %s" % cm.tolist() + (" val %s" % vcm.tolist() if validation_data is not None else "")
+            if callbacks is not None:
+                hist["lr"].append(float(self.lr))
+                msg += " - lr: %.4g" % hist["lr"][-1]
             if verbose:
                 print_fn(msg)
+            if callbacks is not None:
+                logs = {k: v[-1] for k, v in hist.items()}
+                for cb in callbacks:
+                    cb.on_epoch_end(ep, logs)
+                if self.stop_training:
+                    break
+        for cb in callbacks or ():
+            cb.on_train_end()
         return History(hist, census)
 
     def get_config(self):

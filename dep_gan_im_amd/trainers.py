@@ -88,6 +88,9 @@ class Trainers:
         return out
 
     def save_state(self, path, schedule_state=None, extra=None):
+        """state_dict as an .npz.  The optimiser options (Engine.set_lr, Engine.set_optimizer: a changed learning rate,
+        clipnorm, clipvalue, weight_decay) are not recorded: they are configuration, like the lr the engine was created
+        with, and a resumed run sets them again."""
         np.savez(path, **self.state_dict(schedule_state, extra))
 
     @staticmethod

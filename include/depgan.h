@@ -146,6 +146,34 @@ int depgan_apply_adam(depgan_ctx* ctx, int net);
 long depgan_get_adam_step(depgan_ctx* ctx, int net);
 int depgan_set_adam_step(depgan_ctx* ctx, int net, long t);
 
+/* Optimiser options of one network (DEPGAN_NET_*), off by default.  With none set every update launches the plain Adam
+ * kernel with the arguments it always had.
+ * depgan_set_lr / depgan_get_lr: the learning rate the network was created with (lrG / lrD), settable at any time; it
+ *   takes effect at the next update.  Host only.  lr finite and > 0, else status 1.
+ * depgan_set_optimizer(ctx, net, clipnorm, clipvalue, weight_decay): each finite and >= 0, 0 = off; a negative, NaN or
+ *   infinite value is status 1 before any HIP call, an inference context status 3.  All three 0 is the plain path again.
+ *   Every update of the network (depgan_apply_adam, depgan_uresnet_step*, the critic and generator steps,
+ *   depgan_gen_iteration) then runs, on the gradient g' = g * gscale the plain update uses (gscale = 1 / world after a
+ *   summing all-reduce, so the globally averaged gradient):
+ *     clipnorm = c:     norm = sqrt(sum_i (double)g'_i^2), a deterministic two-stage reduction enqueued in front of the
+ *                       update; s = norm >= c ? (float)(c / norm) : 1; g'' = g' * s (standalone Keras 2's clipnorm: one
+ *                       global norm).  The update kernel reads the norm on the device, no host synchronisation is
+ *                       added.  If the squared norm is not finite (a NaN or an infinity in the gradient) the update
+ *                       writes nothing: parameters and both Adam moments keep their bits.  The step counter
+ *                       (depgan_get_adam_step) has advanced all the same.
+ *     clipvalue = a:    g'' = min(max(g'', -a), a), after the norm scaling.
+ *     weight_decay = w: decoupled decay (AdamW): p <- p - (lr * w) p before the Adam displacement, with the plain lr
+ *                       (not the bias-corrected one), on the tensors whose name ends in "/kernel" (convolution,
+ *                       transposed-convolution and dense kernels); biases and BatchNorm gamma / beta are never decayed.
+ *   depgan_get_optimizer returns 1 and the three values with an option on, 0 (and zeros) otherwise.
+ * depgan_last_grad_norm: norm and s of the network's last update made with clipnorm on (s = 0: the update was refused,
+ *   norm is then not finite).  Synchronises the stream.  Status 1 before any such update. */
+int depgan_set_lr(depgan_ctx* ctx, int net, float lr);
+int depgan_get_lr(depgan_ctx* ctx, int net, float* lr);
+int depgan_set_optimizer(depgan_ctx* ctx, int net, float clipnorm, float clipvalue, float weight_decay);
+int depgan_get_optimizer(depgan_ctx* ctx, int net, float* clipnorm, float* clipvalue, float* weight_decay);
+int depgan_last_grad_norm(depgan_ctx* ctx, int net, double* norm, float* scale);
+
 /* One generator iteration of the reference schedule (GT:791-829, 868-878) with ONE host synchronisation:
  *   n_y2  critic-Y2 updates  on the batches  x_y2 + j*stride, y2_y2 + j*stride_y   (j = 0 .. n_y2-1)   GT:802-814
  *   n_dem critic-DEM updates on the batches  x_dem + j*stride, ...                                        GT:817-829
@@ -971,6 +999,19 @@ int depgan_op_best_noise(const float* stats, int k, const float* z_all, long zfl
                          void* hip_stream);
 /* dst[i] = mask[i] ? float(bfloat16(src[i])) : src[i] */
 int depgan_op_round_bf16_masked(const float* src, const unsigned char* mask, float* dst, long n, void* hip_stream);
+/* The kernels behind depgan_set_optimizer on caller-owned device arrays; both allocate their scratch and synchronise.
+ * depgan_op_grad_sqnorm: *out_host = sum_i ((double)(g[i] * gscale))^2 (g 16-byte aligned), bit-identical from run to run.
+ * depgan_op_adam_opts: one update of p, m, v (n floats each) by the option kernel, whatever the options (all 0 runs it with
+ *   nothing acting, which gives the plain kernel's bits).  lr_t is the bias-corrected rate, lr the plain one (it only
+ *   scales weight_decay).  seg_end_host (nseg ascending element ends, the last one n) and seg_decay_host (nseg flags)
+ *   say which elements weight_decay acts on; nseg = 0: none.  With clipnorm > 0 the squared norm is taken from g first
+ *   and norm_host[0] = the norm, norm_host[1] = the scale used (0: the norm was not finite and nothing was written);
+ *   otherwise norm_host (optional) gets 0 and 1. */
+int depgan_op_grad_sqnorm(const float* g, long n, float gscale, double* out_host, void* hip_stream);
+int depgan_op_adam_opts(float* p, const float* g, float* m, float* v, long n, float lr_t, float lr, float b1, float b2,
+                        float eps, float gscale, float clipnorm, float clipvalue, float weight_decay,
+                        const long* seg_end_host, const int* seg_decay_host, int nseg, double* norm_host,
+                        void* hip_stream);
 
 #ifdef __cplusplus
 }
