@@ -521,6 +521,30 @@ def affine_params(H, W, rotate_deg=0.0, scale=1.0, shift=(0.0, 0.0), flip_lr=Fal
     return _affine_rows(H, W, deg, s, dy, dx, np.array([bool(flip_lr)]), np.array([bool(flip_ud)]), gain, offset)[0]
 
 
+def affine_inverse(rows):
+    """The inverse maps of parameter rows: (..., 8) float32 rows of `affine_params` / `Augmenter.draw` in, rows of the
+    same shape out.  A row maps an output pixel p to its source coordinate A p + b; its inverse maps q to
+    A^-1 q - A^-1 b, so `augment` with a row followed by `augment` with its inverse brings a picture back to its frame
+    (evaluate.predict_stats(tta=...) averages predictions that way).  The 2x2 inverse and the offset are computed in
+    float64 from the float32 row and rounded once; the inverse of a flip, a quarter turn or an integer shift is exact.
+    Elements 6 and 7 (gain, offset) become 1 and 0: an intensity change is not inverted.  A singular or non-finite row
+    is a ValueError.  Pure NumPy."""
+    r = np.asarray(rows, np.float32)
+    if r.ndim < 1 or r.shape[-1] != AUG_NPARAM:
+        raise ValueError("affine_inverse: rows must be (..., %d), got shape %s" % (AUG_NPARAM, r.shape))
+    a00, a01, b0, a10, a11, b1 = (r[..., k].astype(np.float64) for k in range(6))
+    det = a00 * a11 - a01 * a10
+    if not np.all(np.isfinite(r[..., :6])) or not np.all(np.isfinite(det)) or np.any(det == 0):
+        raise ValueError("affine_inverse: a row is singular or not finite")
+    i00, i01, i10, i11 = a11 / det, -a01 / det, -a10 / det, a00 / det
+    one = np.ones_like(det)
+    out = np.stack([i00, i01, -(i00 * b0 + i01 * b1), i10, i11, -(i10 * b0 + i11 * b1), one, 0.0 * one], -1)
+    out = (out + 0.0).astype(np.float32)              # + 0.0: no negative zero among the coefficients
+    if not np.all(np.isfinite(out)):
+        raise ValueError("affine_inverse: a row is singular or not finite")
+    return out
+
+
 def _aug_labels(labels, n_src, H, W, dev):
     """labels of `augment` -> (contiguous device tensor or None, lab_kind, C, shape of one output sample)."""
     import torch

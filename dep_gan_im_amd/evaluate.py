@@ -19,6 +19,12 @@ The DEP-UResNet evaluation (DEP-UResNet_testing_4fold.py "UE":553-717) works on 
 
 The label map is np.argmax over the float64 channel means (first index on a tie), and the volumes and Dice figures
 come from an 18-count integer census of it (`depgan_eval_label_counts`).
+
+What the noise draws say beyond their mean -- per-pixel variance, entropy, mutual information, votes -- and test-time
+augmentation, for both models (csrc/eval_stats.hip):
+
+    stats = predict_stats(my_network, brain_flair_1tp, n_repeat=10, mask=icv_and_sl_mask_2tp, tta=None)
+    save_uncertainty_maps(dirOutData, name, stats, affine)
 """
 from __future__ import annotations
 
@@ -104,6 +110,102 @@ def _predict_mean_channels(netG, x, n_repeat, mask, noise_size, rng, batch_size)
                    "depgan_eval_accumulate_channels")                                 # UE:559-560
     _lib.check(lib.depgan_eval_divide(_p(acc), acc.numel(), float(n_repeat), stream), "depgan_eval_divide")  # UE:564
     return acc
+
+
+_STAT_BORDERS = {"edge": 0, "valid": 1}      # border of depgan_eval_accumulate_stats
+MAX_DRAWS = 255                              # votes and count are uint8
+
+
+def _stats_arguments(x, n_repeat, mask, tta, border, ddof):
+    """The host-side checks of predict_stats, before anything touches the device.
+    Returns (n, H, W, rows): rows is None, the Augmenter, or the (n_repeat, n, 8) float32 array of parameter rows."""
+    from .data import AUG_NPARAM, Augmenter
+    if isinstance(n_repeat, bool) or not isinstance(n_repeat, (int, np.integer)) or not 1 <= n_repeat <= MAX_DRAWS:
+        raise ValueError("predict_stats: n_repeat must be an integer in 1..%d, got %r" % (MAX_DRAWS, n_repeat))
+    if border not in _STAT_BORDERS:
+        raise ValueError("predict_stats: border must be 'edge' or 'valid', got %r" % (border,))
+    if isinstance(ddof, bool) or ddof not in (0, 1):
+        raise ValueError("predict_stats: ddof must be 0 or 1, got %r" % (ddof,))
+    shape = tuple(int(d) for d in (x.shape if hasattr(x, "shape") else np.shape(x)))
+    if len(shape) != 4 or min(shape) < 1:
+        raise ValueError("predict_stats: x must be (n, H, W, nicg), got shape %s" % (shape,))
+    n, H, W = shape[:3]
+    if mask is not None:
+        mshape = tuple(int(d) for d in (mask.shape if hasattr(mask, "shape") else np.shape(mask)))
+        if int(np.prod(mshape)) != n * H * W:
+            raise ValueError("predict_stats: mask must have one value per output pixel")
+    rows = None
+    if isinstance(tta, Augmenter):
+        if tta.gain != (1.0, 1.0) or tta.offset != (0.0, 0.0):
+            raise ValueError("predict_stats: a test-time Augmenter must have gain == (1, 1) and offset == (0, 0): an "
+                             "intensity change has no inverse on a probability")
+        rows = tta
+    elif tta is not None:
+        rows = np.asarray(tta.detach().cpu().numpy() if hasattr(tta, "detach") else tta, np.float32)
+        if rows.shape != (n_repeat, n, AUG_NPARAM):
+            raise ValueError("predict_stats: tta must be a data.Augmenter or parameter rows (%d, %d, %d), got shape %s"
+                             % (n_repeat, n, AUG_NPARAM, rows.shape))
+    return n, H, W, rows
+
+
+def predict_stats(netG, x, n_repeat=10, mask=None, noise_size=32, rng=None, batch_size=32, tta=None, border="valid",
+                  ddof=0):
+    """What the n_repeat noise draws of predict_mean say beyond their mean, and test-time augmentation.
+    x: (n, H, W, nicg); mask: (n, H, W) or None.  Returns a dict of device tensors:
+      'mean', 'var'                                 float64 (n, H, W, C), or (n, H, W) for a one-channel model: the mean
+                                                    and the variance (ddof 0 or 1) of the masked predictions
+      'entropy', 'expected_entropy', 'mutual_info'  float64 (n, H, W), C >= 2: the entropy of the mean row, the mean of
+                                                    the draws' entropies, and their difference, the BALD term (nats)
+      'votes'                                       uint8 (n, H, W, C), C >= 2: how many draws had their maximum there
+      'count'                                       uint8 (n, H, W): how many draws took part at the pixel
+    The noise is drawn from `rng` exactly as predict_mean draws it, so with tta=None and the same rng state 'mean' is
+    predict_mean's result bit for bit; the forward is eng.g_forward, so an inference_copy("bfloat16") works unchanged.
+    tta: a data.Augmenter (gain and offset closed, else ValueError; it draws n rows per repeat from its own generator)
+    or an array (n_repeat, n, 8) of parameter rows.  Repeat r predicts on data.augment(x, params=rows[r]) and is
+    accumulated in the original frame through data.affine_inverse(rows[r]); the mask applies in the original frame.
+    border 'edge' clamps the taps of that resampling, and every draw counts everywhere; 'valid' lets a draw take part
+    only where every tap that carries weight lies inside its prediction, so 'count' can fall below n_repeat near the
+    corners (a pixel no draw reached holds 0.0 everywhere).  At most 255 draws."""
+    n, H, W, rows = _stats_arguments(x, n_repeat, mask, tta, border, ddof)
+    from . import data as D
+    torch = _torch()
+    lib = _lib.load()
+    rng = rng if rng is not None else np.random
+    eng = netG._ensure_engine(min(batch_size, n))
+    dev = eng.device
+    if (H, W) != (eng.height, eng.width):
+        raise ValueError("predict_stats: x is %d x %d, the model works on %d x %d" % (H, W, eng.height, eng.width))
+    C_out = int(getattr(eng, "nc_out", 1))
+    xd = _dev(x, dev)
+    md = _dev(mask, dev)
+    npix = n * H * W
+    f64 = dict(dtype=torch.float64, device=dev)
+    shape = (n, H, W, C_out) if C_out > 1 else (n, H, W)
+    acc, sq = torch.zeros(shape, **f64), torch.zeros(shape, **f64)
+    count = torch.zeros((n, H, W), dtype=torch.uint8, device=dev)
+    ent = votes = entropy = mi = None
+    if C_out > 1:
+        ent, entropy, mi = torch.zeros((n, H, W), **f64), torch.empty((n, H, W), **f64), torch.empty((n, H, W), **f64)
+        votes = torch.zeros((n, H, W, C_out), dtype=torch.uint8, device=dev)
+    stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+    for r in range(n_repeat):
+        noise = rng.normal(size=(n, noise_size, 1)).astype("float32")               # as predict_mean
+        xw, inv = xd, None
+        if rows is not None:
+            fwd = rows.draw(n, H, W) if isinstance(rows, D.Augmenter) else rows[r]
+            inv = torch.from_numpy(D.affine_inverse(fwd)).to(dev)                     # ValueError before the forward
+            xw, _ = D.augment(xd, params=fwd, border=getattr(tta, "border", "edge"), x_fill=getattr(tta, "x_fill", 0.0))
+        pred = eng.g_forward(xw, noise)
+        _lib.check(lib.depgan_eval_accumulate_stats(_p(pred), _p(md), _p(inv), _STAT_BORDERS[border], n, H, W, C_out,
+                                                    _p(acc), _p(sq), _p(ent), _p(votes), _p(count), stream),
+                   "depgan_eval_accumulate_stats")
+    _lib.check(lib.depgan_eval_finish_stats(_p(acc), _p(sq), _p(ent), _p(count) if rows is not None else None,
+                                            _p(entropy), _p(mi), npix, C_out, int(n_repeat), int(ddof), stream),
+               "depgan_eval_finish_stats")
+    out = {"mean": acc, "var": sq, "count": count}
+    if C_out > 1:
+        out.update({"entropy": entropy, "expected_entropy": ent, "mutual_info": mi, "votes": votes})
+    return out
 
 
 def census(x, pred, code_real=None, mask1=None, wmh1=None, mask2=None, wmh2=None, prob2=None, thr=0.5, device=None):
@@ -316,4 +418,34 @@ def save_uresnet_maps(directory, name, labels, prob_mean, affine):
         pred_prob = prob[:, :, :, c].reshape((N, H, W, 1))                                               # UE:712-713
         paths.append(os.path.join(directory, name + "_prb_map_c" + str(c) + ".nii.gz"))
         nifti.save(paths[-1], data_prep_save(pred_prob).astype("float32"), affine)                      # UE:715-717
+    return paths
+
+
+def save_uncertainty_maps(directory, name, stats, affine):
+    """The uncertainty maps of predict_stats as float32 NIfTI volumes, each through data_prep_save like the maps of
+    save_uresnet_maps: <name>_unc_entropy.nii.gz and <name>_unc_mutual_info.nii.gz (a model with C >= 2 channels) and
+    the variance, <name>_unc_var_c<c>.nii.gz per channel or <name>_unc_var.nii.gz for a one-channel model.
+    stats: the dict predict_stats returned (device tensors or arrays).  Returns the paths written."""
+    import os
+    from . import nifti
+    from .data import data_prep_save
+
+    def host(a):
+        return a.detach().cpu().numpy() if hasattr(a, "detach") else np.asarray(a)
+
+    paths = []
+
+    def save(suffix, a):
+        paths.append(os.path.join(directory, name + "_unc_" + suffix + ".nii.gz"))
+        nifti.save(paths[-1], data_prep_save(a[..., None]).astype("float32"), affine)
+
+    for key in ("entropy", "mutual_info"):
+        if stats.get(key) is not None:
+            save(key, host(stats[key]))
+    var = host(stats["var"])
+    if var.ndim == 3:
+        save("var", var)
+    else:
+        for c in range(var.shape[3]):
+            save("var_c" + str(c), var[:, :, :, c])
     return paths

@@ -478,6 +478,59 @@ int depgan_eval_label_counts(const double* pred_dev, int C, const float* code_re
                              const float* wmh1_dev, const float* mask2_dev, const float* wmh2_dev, long npix,
                              signed char* labels_out_dev, long long out_host[DEPGAN_EVAL_LABEL_NCOUNT], void* stream);
 
+/* ---- per-draw statistics of the stochastic predictions and test-time augmentation (csrc/eval_stats.hip) ----
+ * What the n_repeat noise draws say beyond their mean.  Stateless; device pointers; enqueued on `stream`; the host does
+ * not synchronise; no atomics (a thread owns its pixel's state).  Every float and double operation below is one
+ * correctly rounded operation in the stated order, so a NumPy restatement (tests/eval_stats_ref.py) gives the same bits
+ * wherever no log is involved.
+ * depgan_eval_accumulate_stats: one call per noise draw, in the place of depgan_eval_accumulate[_channels].
+ *   pred_dev (n, H, W, C) float32, this draw's prediction, C = 1..DEPGAN_MAX_HEAD_CLASSES; mask_dev (n, H, W) float32
+ *   or NULL; params_dev (n, DEPGAN_AUG_NPARAM) float32 or NULL.  State, zeroed by the caller before the first draw,
+ *   each pointer optional (NULL = not kept) except sum_dev: sum_dev, sumsq_dev (npix, C) double, ent_sum_dev (npix)
+ *   double, votes_dev (npix, C) uint8, count_dev (npix) uint8, npix = n*H*W.  The caller makes at most 255 draws.
+ *   For output pixel t = (i, oy, ox) and channel c:
+ *     u_c: without params_dev, pred[t, c].  With params_dev (test-time augmentation) row i is an output-to-source map
+ *       in depgan_data_augment's convention -- the output is the original frame, the source is the prediction made on
+ *       the warped input -- and sy, sx, y0, x0, fy, fx, the four taps and u_c = top*(1-fy) + bot*fy are that entry's
+ *       float32 statements applied to the C channels of sample i.  The gain / offset statement is not applied;
+ *       elements 6 and 7 of the row are ignored.  A tap is compared with the sample and clamped into it as a float
+ *       before it becomes an index, so nothing outside the sample is read, whatever the coordinate.
+ *       border 0 (edge): taps are clamped and every draw counts.  border 1 (valid): the draw takes part at this pixel
+ *       only if every tap that carries weight lies inside, in0(y0) && in0(x0) && (fy == 0 || in(y0+1)) &&
+ *       (fx == 0 || in(x0+1)) -- exact maps (flips, quarter turns, integer shifts) keep their last row and column --
+ *       and otherwise NOTHING of the state is touched for this pixel.  Without params_dev border is not used.
+ *     v_c = u_c * mask[t] in float32 (v_c = u_c when mask_dev is NULL), as depgan_eval_accumulate_channels
+ *     sum[t, c]   = sum[t, c] + (double)v_c                        (that entry's statement and bits)
+ *     sumsq[t, c] = sumsq[t, c] + (double)v_c * (double)v_c        (the product is exact; only the add rounds)
+ *     ent_sum[t]  = ent_sum[t] + h,  h = ((0 - t_0) - t_1) - ... in channel order,
+ *                   t_c = v_c > 0 ? (double)v_c * log((double)v_c) : 0.0   (natural log in double)
+ *     votes[t, argmax_c v_c] += 1   -- the first maximum wins and a NaN counts as the maximum, the rule of
+ *                   depgan_eval_label_counts; a pixel the mask zeroed votes for class 0
+ *     count[t]    += 1
+ *   Status 1, nothing launched: n, H, W < 1, C outside 1..DEPGAN_MAX_HEAD_CLASSES, border not 0 / 1, pred_dev or
+ *   sum_dev NULL, ent_sum_dev or votes_dev with C < 2, H or W > 2^24 or H*W >= 2^31, or a state range that overlaps
+ *   pred, mask, params or another state range.
+ * depgan_eval_finish_stats: one call after the last draw, elementwise per pixel, all arithmetic in double, every
+ *   operation rounded on its own.  R = n_draws (1..255), or count[t] where count_dev is given; a pixel with R = 0 gets
+ *   0.0 in every output.  In place:
+ *     mean = sum / R                                          over sum_dev; with count_dev NULL depgan_eval_divide's bits
+ *     var  = max(sumsq / R - mean*mean, 0) * (R / (R - ddof)) over sumsq_dev (may be NULL); ddof 0 or 1; 0 where
+ *            R - ddof = 0; max(d, 0) = d < 0 ? 0 : d, so a NaN stays one
+ *     expected_entropy = ent_sum / R                          over ent_sum_dev (may be NULL)
+ *   and into new arrays (npix) double, each may be NULL:
+ *     entropy     = the h statement above applied to the mean row
+ *     mutual_info = max(entropy - expected_entropy, 0), the BALD term (needs ent_sum_dev); it is non-negative
+ *                   mathematically, the clamp only removes rounding
+ *   Status 1, nothing launched: sum_dev NULL, npix < 1, C outside 1..DEPGAN_MAX_HEAD_CLASSES, n_draws outside 1..255,
+ *   ddof not 0 / 1, ent_sum_dev, entropy_dev or mutual_info_dev with C < 2, mutual_info_dev without ent_sum_dev, or
+ *   two ranges that overlap. */
+int depgan_eval_accumulate_stats(const float* pred_dev, const float* mask_dev, const float* params_dev, int border,
+                                 int n, int H, int W, int C, double* sum_dev, double* sumsq_dev, double* ent_sum_dev,
+                                 unsigned char* votes_dev, unsigned char* count_dev, void* stream);
+int depgan_eval_finish_stats(double* sum_dev, double* sumsq_dev, double* ent_sum_dev, const unsigned char* count_dev,
+                             double* entropy_dev, double* mutual_info_dev, long npix, int C, int n_draws, int ddof,
+                             void* stream);
+
 /* ---- parity-test surface: the tensors a training closure left behind ----
  * The step functions are piecewise linear in the ReLU signs and max-pool arg-maxes of the forward passes (GT:256-309
  * activations, GT:322-335 pools; the gradient penalty of GT:543-549 differentiates through them twice).  A parity
