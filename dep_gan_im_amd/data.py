@@ -699,3 +699,32 @@ def data_prep_save(image_data):
     a = np.swapaxes(a, 0, 2)
     a = np.rot90(a)
     return a[::-1, ...]
+
+
+def data_prep(image_data):
+    """GT:106-118: an (X, Y, Z) volume as loaded -> the (Z, X, Y, 1) float32 slices the networks work on.  Pure NumPy;
+    the device route is prep_subject / mask_slices, which leave their slices in this order."""
+    a = np.asarray(image_data)
+    if a.ndim != 3:
+        raise ValueError("data_prep: expected a 3-D volume, got shape %s" % (a.shape,))
+    return np.array([a[:, :, z] for z in range(a.shape[2])], dtype="float32")[..., None]
+
+
+def prepared_spacing(pixdim):
+    """Voxel spacing of the prepared slices.  pixdim: the pixdim[1:4] of a loaded NIfTI (nifti.load(path).header
+    ["pixdim"][1:4]), the spacing along the file's three axes.  Returns (sz, sy, sx) as floats, the spacing along the
+    axes of the (n, H, W) slices data_prep leaves -- what evaluate.surface_distances takes as `spacing`.  The order is
+    read off data_prep itself: a volume whose voxels hold their own file index goes through it, and the file axis
+    whose index changes along a prepared axis is that axis' source.  Pure NumPy."""
+    p = np.asarray(pixdim, np.float64).reshape(-1)
+    if p.size != 3 or not np.isfinite(p).all() or not (p > 0).all():
+        raise ValueError("prepared_spacing: pixdim must hold three finite positive spacings, got %r" % (pixdim,))
+    index = np.indices((2, 3, 4))                       # index[a][i, j, k] = the voxel's index along file axis a
+    moved = [data_prep(index[a])[..., 0] for a in range(3)]
+    out = []
+    for axis in range(3):                               # prepared axis: which file index changes along it?
+        src = [a for a in range(3) if np.diff(moved[a], axis=axis).any()]
+        if len(src) != 1:
+            raise AssertionError("data_prep no longer permutes the axes of its volume")
+        out.append(float(p[src[0]]))
+    return tuple(out)

@@ -25,6 +25,11 @@ augmentation, for both models (csrc/eval_stats.hip):
 
     stats = predict_stats(my_network, brain_flair_1tp, n_repeat=10, mask=icv_and_sl_mask_2tp, tta=None)
     save_uncertainty_maps(dirOutData, name, stats, affine)
+
+How far the predicted boundaries lie from the true ones -- Hausdorff distance, its 95th percentile, average symmetric
+surface distance -- per class, from an exact distance map formed on the device (csrc/surface_dist.hip):
+
+    surf = label_surface_metrics(m["labels"], brain_cod_2tp, classes=(1, 2, 3), spacing=data.prepared_spacing(pixdim))
 """
 from __future__ import annotations
 
@@ -449,3 +454,197 @@ def save_uncertainty_maps(directory, name, stats, affine):
         for c in range(var.shape[3]):
             save("var_c" + str(c), var[:, :, :, c])
     return paths
+
+
+# ---- surface distances: HD, HD95, ASSD from an exact on-device distance map (csrc/surface_dist.hip) ----
+
+SURFACE_KEYS = ("n_surface_a", "n_surface_b", "hd_ab", "hd_ba", "hd", "msd_ab", "msd_ba", "assd", "hd95_ab", "hd95_ba",
+                "hd95", "hd95_pooled")
+
+
+def _shape3(a, what):
+    shape = tuple(int(d) for d in (a.shape if hasattr(a, "shape") else np.shape(a)))
+    if len(shape) != 3 or min(shape) < 1:
+        raise ValueError("%s must be a three-dimensional (n, H, W) array, got shape %s" % (what, shape))
+    return shape
+
+
+def _spacing_weights(spacing, who):
+    """(wz, wy, wx), the squared spacings depgan_eval_edt_sq takes; ValueError unless three finite positive numbers."""
+    try:
+        s = [float(v) for v in spacing]
+    except (TypeError, ValueError):
+        s = []
+    w = [v * v for v in s]
+    if len(s) != 3 or not all(np.isfinite(v) and v > 0 for v in s + w):
+        raise ValueError("%s: spacing must hold three finite positive numbers (sz, sy, sx), got %r" % (who, spacing))
+    return tuple(w)
+
+
+def _set_u8(a, device):
+    """(n, H, W) uint8 device tensor, 1 where `a` is non-zero (any dtype, host or device)."""
+    torch = _torch()
+    t = a if isinstance(a, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(a) != 0))
+    return (t.to(device) != 0).to(torch.uint8).contiguous()
+
+
+def _surface_device(*arrays):
+    torch = _torch()
+    for a in arrays:
+        if isinstance(a, torch.Tensor) and a.is_cuda:
+            return a.device
+    return torch.device("cuda:%d" % torch.cuda.current_device())
+
+
+def _edt_sq(lib, set_u8, w, stream):
+    """float64 device tensor: depgan_eval_edt_sq of a (n, H, W) uint8 device tensor"""
+    torch = _torch()
+    D, H, W = (int(d) for d in set_u8.shape)
+    d2 = torch.empty((D, H, W), dtype=torch.float64, device=set_u8.device)
+    scratch = torch.empty((max(1, int(lib.depgan_eval_edt_scratch_bytes(D, H, W)) // 8),), dtype=torch.float64,
+                          device=set_u8.device)
+    _lib.check(lib.depgan_eval_edt_sq(_p(set_u8), D, H, W, w[0], w[1], w[2], _p(d2), _p(scratch), stream),
+               "depgan_eval_edt_sq")
+    return d2
+
+
+def distance_transform(mask, spacing=(1, 1, 1), squared=False):
+    """The exact Euclidean distance from every voxel to the nearest non-zero voxel of `mask`, in units of `spacing` =
+    (sz, sy, sx) (data.prepared_spacing): a float64 device tensor (n, H, W).  mask: (n, H, W), any dtype, host or
+    device; non-zero means set.  squared: the squared distance, which is what the kernels form (include/depgan.h:
+    every product and sum of dz^2 sz^2 + dy^2 sy^2 + dx^2 sx^2 rounded once); otherwise its square root.  A mask
+    without a set voxel gives +inf everywhere.  Note the sense: scipy.ndimage.distance_transform_edt(~mask, spacing)."""
+    _shape3(mask, "distance_transform: mask")
+    w = _spacing_weights(spacing, "distance_transform")
+    torch = _torch()
+    lib = _lib.load()
+    dev = _surface_device(mask)
+    stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+    d2 = _edt_sq(lib, _set_u8(mask, dev), w, stream)
+    return d2 if squared else torch.sqrt(d2)
+
+
+def _percentile_index(n, q):
+    """NumPy's linear-interpolation statement for np.percentile(a, q) of n sorted values: (lower index, upper index,
+    weight of the upper one)."""
+    virtual = (n - 1) * np.true_divide(q, 100.0)
+    if virtual >= n - 1:                                 # at or above the last index: the maximum
+        return n - 1, n - 1, 0.0
+    lo = int(np.floor(virtual))
+    return lo, lo + 1, float(virtual - np.floor(virtual))
+
+
+def _lerp(a, b, t):
+    """NumPy's _lerp: a + (b - a) t, taken from the other end for t >= 0.5"""
+    d = b - a
+    return a + d * t if t < 0.5 else b - d * (1.0 - t)
+
+
+def surface_distances(a, b, spacing=(1, 1, 1), in_plane=False, percentile=95.0):
+    """Distances between the surfaces of two binary volumes a and b, (n, H, W), any dtype, host or device, non-zero =
+    set; `spacing` = (sz, sy, sx) of the slices (data.prepared_spacing).  A surface voxel is a set voxel with a face
+    neighbour that is unset or outside the volume -- the 6 neighbours in the volume, or with in_plane the 4 in the
+    slice (the WMH challenge's convention for thick slices).  With s_ab the distances from a's surface voxels to the
+    nearest surface voxel of b and s_ba the reverse, returns a dict of Python numbers:
+      n_surface_a, n_surface_b   the surface voxel counts
+      hd_ab, hd_ba, hd           the directed maxima and their maximum, the Hausdorff distance
+      msd_ab, msd_ba, assd       the directed means and (msd_ab + msd_ba) / 2, medpy's assd
+      hd95_ab, hd95_ba, hd95     np.percentile(s, percentile) (linear interpolation) per direction and the maximum of
+                                 the two, the WMH challenge's figure
+      hd95_pooled                the percentile of the two sets concatenated, medpy's hd95
+    If either surface is empty every distance figure is nan and the counts say why; nothing raises.
+    The masks, the exact distance maps (depgan_eval_edt_sq), the sums and the sort stay on the device; a handful of
+    scalars travel back."""
+    shape = _shape3(a, "surface_distances: a")
+    if _shape3(b, "surface_distances: b") != shape:
+        raise ValueError("surface_distances: a and b must have the same shape, got %s and %s"
+                         % (shape, _shape3(b, "surface_distances: b")))
+    w = _spacing_weights(spacing, "surface_distances")
+    try:
+        q = float(percentile)
+    except (TypeError, ValueError):
+        q = float("nan")
+    if not 0.0 <= q <= 100.0:
+        raise ValueError("surface_distances: percentile must lie in [0, 100], got %r" % (percentile,))
+    torch = _torch()
+    lib = _lib.load()
+    dev = _surface_device(a, b)
+    stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+    D, H, W = shape
+    n = D * H * W
+    partial = torch.empty((max(1, int(lib.depgan_eval_surface_sums_scratch_bytes(n)) // 8),), dtype=torch.float64,
+                          device=dev)
+    surf, d2 = [], []
+    for vol in (a, b):
+        s = torch.empty(shape, dtype=torch.uint8, device=dev)
+        _lib.check(lib.depgan_eval_surface_mask(_p(_set_u8(vol, dev)), D, H, W, 1 if in_plane else 0, _p(s), stream),
+                   "depgan_eval_surface_mask")
+        surf.append(s)
+        d2.append(_edt_sq(lib, s, w, stream))             # the distance to THIS surface
+    sums = []
+    for own, other in ((0, 1), (1, 0)):                   # s_ab: a's surface voxels in b's map; then s_ba
+        out = (C.c_double * 4)()
+        _lib.check(lib.depgan_eval_surface_sums(_p(d2[other]), _p(surf[own]), n, _p(partial), out, stream),
+                   "depgan_eval_surface_sums")
+        sums.append([float(v) for v in out])
+    na, nb = int(sums[0][0]), int(sums[1][0])
+    res = {k: float("nan") for k in SURFACE_KEYS}
+    res["n_surface_a"], res["n_surface_b"] = na, nb
+    if na == 0 or nb == 0:
+        return res
+    res["hd_ab"], res["hd_ba"] = float(np.sqrt(sums[0][1])), float(np.sqrt(sums[1][1]))
+    res["hd"] = max(res["hd_ab"], res["hd_ba"])
+    res["msd_ab"], res["msd_ba"] = sums[0][2] / na, sums[1][2] / nb
+    res["assd"] = (res["msd_ab"] + res["msd_ba"]) / 2
+    # the percentile: the squared distances at the surface voxels, sorted on the device; the square root is monotone,
+    # so the order statistics of the distances are the square roots of these
+    s_ab = torch.masked_select(d2[1], surf[0] != 0)
+    s_ba = torch.masked_select(d2[0], surf[1] != 0)
+    picks, where = [], []
+    for v in (s_ab, s_ba, torch.cat([s_ab, s_ba])):
+        lo, hi, t = _percentile_index(int(v.numel()), q)
+        picks.append(torch.sort(v).values[[lo, hi]])
+        where.append(t)
+    stats = np.sqrt(torch.cat(picks).cpu().numpy())
+    for i, key in enumerate(("hd95_ab", "hd95_ba", "hd95_pooled")):
+        res[key] = float(_lerp(stats[2 * i], stats[2 * i + 1], where[i]))
+    res["hd95"] = max(res["hd95_ab"], res["hd95_ba"])
+    return res
+
+
+def label_surface_metrics(labels, code_real, classes=(1, 2, 3), spacing=(1, 1, 1), mask=None, in_plane=False):
+    """surface_distances per class: {k: surface_distances(labels == k, code_real == k, spacing, in_plane)} for k in
+    `classes` (any class count).  labels: the int8 label map of uresnet_metrics(...)["labels"]; code_real: the float32
+    code volume; both (n, H, W) (a trailing axis of length 1 is dropped), host or device.  mask (same shape, optional):
+    both maps are zeroed where it is zero first."""
+    classes = [int(k) for k in classes]
+    if not classes:
+        raise ValueError("label_surface_metrics: classes is empty")
+    torch = _torch()
+
+    def vol(v, what):
+        shape = tuple(int(d) for d in (v.shape if hasattr(v, "shape") else np.shape(v)))
+        if len(shape) == 4 and shape[3] == 1:
+            v = v.reshape(shape[:3])
+        _shape3(v, "label_surface_metrics: " + what)
+        return v
+
+    labels, code_real = vol(labels, "labels"), vol(code_real, "code_real")
+    if tuple(labels.shape) != tuple(code_real.shape):
+        raise ValueError("label_surface_metrics: labels and code_real must have the same shape, got %s and %s"
+                         % (tuple(labels.shape), tuple(code_real.shape)))
+    if mask is not None:
+        mask = vol(mask, "mask")
+        if tuple(mask.shape) != tuple(labels.shape):
+            raise ValueError("label_surface_metrics: mask must have the shape of labels")
+    _spacing_weights(spacing, "label_surface_metrics")
+    dev = _surface_device(labels, code_real, mask)
+
+    def up(v):
+        return v.to(dev) if isinstance(v, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(v)).to(dev)
+
+    lab, real = up(labels), up(code_real)
+    if mask is not None:
+        keep = up(mask) != 0
+        lab, real = lab * keep.to(lab.dtype), real * keep.to(real.dtype)
+    return {k: surface_distances(lab == k, real == k, spacing, in_plane) for k in classes}

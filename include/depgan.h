@@ -531,6 +531,36 @@ int depgan_eval_finish_stats(double* sum_dev, double* sumsq_dev, double* ent_sum
                              double* entropy_dev, double* mutual_info_dev, long npix, int C, int n_draws, int ddof,
                              void* stream);
 
+/* ---- surface distances from an exact distance map (csrc/surface_dist.hip; evaluate.surface_distances) ----
+ * Stateless; device pointers; enqueued on `stream`; no atomics.  A volume is (D, H, W) bytes with W contiguous -- what
+ * (n, H, W) slices are -- and non-zero means set.  1 <= D, H, W <= 4096 and D*H*W < 2^31.
+ * depgan_eval_surface_mask: surf[v] = 1 where set[v] != 0 and at least one face neighbour is unset or lies outside the
+ *   volume, else 0.  in_plane 0: the 6 neighbours in the volume (a & ~binary_erosion(a, 6-connected, border_value=0));
+ *   in_plane 1: the 4 in the slice (slices are several times thicker than pixels; the WMH challenge's convention).
+ * depgan_eval_edt_sq: d2[v] (double) = the exact squared Euclidean distance from v to the nearest set voxel, the minimum
+ *   over the set voxels of fl(fl(fl(dx^2 wx) + fl(dy^2 wy)) + fl(dz^2 wz)) with the integer squares converted exactly
+ *   and every product and sum rounded once; wz, wy, wx are the SQUARED voxel spacings.  Computed as three separable
+ *   passes (rows, then H, then D), which gives these bits because rounding is monotone; a minimum does not depend on
+ *   its order, so a call repeats bit for bit.  A voxel that is set gets 0, a volume without a set voxel +inf everywhere.
+ *   scratch: depgan_eval_edt_scratch_bytes(D, H, W) device bytes (0 for a volume outside the limits), 8-byte aligned
+ *   like d2.  The host does not synchronise.
+ * depgan_eval_surface_sums: over the n voxels with surf != 0, out_host = {their count, the maximum of d2 (0 when there
+ *   is none; d2 >= 0), the sum of sqrt(d2) (a correctly rounded square root per voxel), the number of them whose d2 is
+ *   +inf}.  One partial per block, then one block adds the partials in index order: the bits repeat from run to run.
+ *   The two counts are integers held in doubles (exact below 2^53).  partial: depgan_eval_surface_sums_scratch_bytes(n)
+ *   device bytes (0 unless 1 <= n < 2^31), 8-byte aligned.  Synchronises `stream`.
+ * Status 1, nothing launched: a dimension below 1 or above 4096, D*H*W >= 2^31 (n outside 1 .. 2^31 - 1), a pointer
+ *   NULL or misaligned, a weight that is not finite or not > 0, in_plane not 0 / 1, or an output or scratch range that
+ *   overlaps an input range or another output. */
+int depgan_eval_surface_mask(const unsigned char* set, int D, int H, int W, int in_plane, unsigned char* surf,
+                             void* stream);
+size_t depgan_eval_edt_scratch_bytes(int D, int H, int W);
+int depgan_eval_edt_sq(const unsigned char* set, int D, int H, int W, double wz, double wy, double wx, double* d2,
+                       void* scratch, void* stream);
+size_t depgan_eval_surface_sums_scratch_bytes(long n);
+int depgan_eval_surface_sums(const double* d2, const unsigned char* surf, long n, double* partial, double out_host[4],
+                             void* stream);
+
 /* ---- parity-test surface: the tensors a training closure left behind ----
  * The step functions are piecewise linear in the ReLU signs and max-pool arg-maxes of the forward passes (GT:256-309
  * activations, GT:322-335 pools; the gradient penalty of GT:543-549 differentiates through them twice).  A parity
