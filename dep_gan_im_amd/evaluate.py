@@ -30,6 +30,11 @@ How far the predicted boundaries lie from the true ones -- Hausdorff distance, i
 surface distance -- per class, from an exact distance map formed on the device (csrc/surface_dist.hip):
 
     surf = label_surface_metrics(m["labels"], brain_cod_2tp, classes=(1, 2, 3), spacing=data.prepared_spacing(pixdim))
+
+Which lesions were found at all -- lesion-wise recall, precision, F1 and the absolute volume difference -- per class, from
+connected components labelled on the device (csrc/components.hip):
+
+    les = label_lesion_metrics(m["labels"], brain_cod_2tp, classes=(1, 2, 3), voxel_volume=voxel_volume)
 """
 from __future__ import annotations
 
@@ -648,3 +653,222 @@ def label_surface_metrics(labels, code_real, classes=(1, 2, 3), spacing=(1, 1, 1
         keep = up(mask) != 0
         lab, real = lab * keep.to(lab.dtype), real * keep.to(real.dtype)
     return {k: surface_distances(lab == k, real == k, spacing, in_plane) for k in classes}
+
+
+# ---- lesion-wise detection: connected components labelled on the device (csrc/components.hip) ----
+
+LESION_KEYS = ("n_truth", "n_pred", "n_truth_detected", "n_pred_true", "recall", "precision", "f1", "voxels_truth",
+               "voxels_pred", "avd_percent")
+
+
+def _cc_args(who, connectivity=1, in_plane=False, min_voxels=1, voxel_volume=None):
+    """(connectivity, in_plane as 0 / 1, min_voxels, voxel_volume or None); ValueError for anything else."""
+    if isinstance(connectivity, bool) or connectivity not in (1, 2, 3):
+        raise ValueError("%s: connectivity must be 1, 2 or 3 (scipy's generate_binary_structure rank), got %r"
+                         % (who, connectivity))
+    if isinstance(in_plane, (bool, np.bool_)):
+        in_plane = int(in_plane)
+    if isinstance(in_plane, (float, str)) or in_plane not in (0, 1):
+        raise ValueError("%s: in_plane must be False or True, got %r" % (who, in_plane))
+    try:
+        mv = int(min_voxels)
+        whole = not isinstance(min_voxels, (bool, str)) and mv == min_voxels
+    except (TypeError, ValueError, OverflowError):
+        mv, whole = 0, False
+    if not whole:
+        raise ValueError("%s: min_voxels must be an integer, got %r" % (who, min_voxels))
+    if voxel_volume is not None:
+        try:
+            voxel_volume = float(voxel_volume)
+        except (TypeError, ValueError):
+            voxel_volume = float("nan")
+        if not (np.isfinite(voxel_volume) and voxel_volume > 0):
+            raise ValueError("%s: voxel_volume must be a finite positive number, got %r" % (who, voxel_volume))
+    return int(connectivity), int(in_plane), mv, voxel_volume
+
+
+def _cc_label(lib, set_u8, connectivity, in_plane, stream):
+    """(int32 device tensor, N): depgan_eval_cc_label of a (n, H, W) uint8 device tensor"""
+    torch = _torch()
+    D, H, W = (int(d) for d in set_u8.shape)
+    labels = torch.empty((D, H, W), dtype=torch.int32, device=set_u8.device)
+    scratch = torch.empty((max(1, int(lib.depgan_eval_cc_scratch_bytes(D, H, W)) // 8),), dtype=torch.int64,
+                          device=set_u8.device)
+    n_out = (C.c_longlong * 1)()
+    _lib.check(lib.depgan_eval_cc_label(_p(set_u8), D, H, W, connectivity, in_plane, _p(labels), _p(scratch), n_out,
+                                        stream), "depgan_eval_cc_label")
+    return labels, int(n_out[0])
+
+
+def _cc_tables(lib, labels, n, other_u8, stream):
+    """(size, hits): depgan_eval_cc_overlap of an int32 device tensor with components 1..n"""
+    torch = _torch()
+    size = torch.empty((n,), dtype=torch.int32, device=labels.device)
+    hits = torch.empty((n,), dtype=torch.int32, device=labels.device)
+    _lib.check(lib.depgan_eval_cc_overlap(_p(labels), _p(other_u8), int(labels.numel()), n, _p(size) if n else None,
+                                          _p(hits) if n else None, stream), "depgan_eval_cc_overlap")
+    return size, hits
+
+
+def _cc_stream(dev):
+    return C.c_void_p(_torch().cuda.current_stream(dev).cuda_stream)
+
+
+def connected_components(mask, connectivity=1, in_plane=False):
+    """The connected components of the non-zero voxels of `mask`, (n, H, W), any dtype, host or device: (labels, N) with
+    labels an int32 device tensor (n, H, W), 0 where mask is zero and 1..N elsewhere, and N a Python int.  Components
+    are numbered in the order of their first voxel in index order, which is scipy.ndimage.label's numbering.
+    connectivity is scipy's rank, generate_binary_structure(3, connectivity): 1 (scipy's default) joins the 6 face
+    neighbours, 2 the 18 that share a face or an edge, 3 all 26.  With in_plane the neighbours lie in the slice only:
+    4 at rank 1, 8 at ranks 2 and 3 (slices several times thicker than pixels, as in surface_distances)."""
+    _shape3(mask, "connected_components: mask")
+    connectivity, in_plane, _, _ = _cc_args("connected_components", connectivity, in_plane)
+    lib = _lib.load()
+    dev = _surface_device(mask)
+    return _cc_label(lib, _set_u8(mask, dev), connectivity, in_plane, _cc_stream(dev))
+
+
+def component_sizes(labels, n, other=None):
+    """(size, hits), int32 device tensors of length n, for a label volume of connected_components: size[k - 1] is the
+    voxel count of component k and hits[k - 1] the number of its voxels where `other` (same shape, any dtype, host or
+    device) is non-zero; all zero when other is None.  A label outside 1..n is not counted."""
+    shape = _shape3(labels, "component_sizes: labels")
+    try:
+        whole = not isinstance(n, bool) and int(n) == n
+    except (TypeError, ValueError, OverflowError):
+        whole = False
+    if not whole or not 0 <= int(n) <= shape[0] * shape[1] * shape[2]:
+        raise ValueError("component_sizes: n must be an integer from 0 to the number of voxels, got %r" % (n,))
+    if other is not None and _shape3(other, "component_sizes: other") != shape:
+        raise ValueError("component_sizes: other must have the shape of labels, got %s and %s"
+                         % (_shape3(other, "component_sizes: other"), shape))
+    torch = _torch()
+    lib = _lib.load()
+    dev = _surface_device(labels, other)
+    lab = labels if isinstance(labels, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(labels))
+    lab = lab.to(device=dev, dtype=torch.int32).contiguous()
+    return _cc_tables(lib, lab, int(n), None if other is None else _set_u8(other, dev), _cc_stream(dev))
+
+
+def _keep_large(labels, size, min_voxels):
+    """(uint8 mask of the voxels whose component has at least min_voxels voxels, bool table of those components)"""
+    torch = _torch()
+    keep = size >= min_voxels
+    table = torch.cat([keep.new_zeros((1,)), keep])                  # label 0, the background, is never kept
+    return table[labels.long()].to(torch.uint8), keep
+
+
+def remove_small_components(mask, min_voxels, connectivity=1, in_plane=False):
+    """`mask` (n, H, W), any dtype, host or device, as a uint8 device tensor of 0 / 1 with every connected component of
+    fewer than min_voxels voxels cleared; min_voxels <= 1 returns the binarised mask.  connectivity and in_plane as in
+    connected_components."""
+    _shape3(mask, "remove_small_components: mask")
+    connectivity, in_plane, min_voxels, _ = _cc_args("remove_small_components", connectivity, in_plane, min_voxels)
+    dev = _surface_device(mask)
+    set_u8 = _set_u8(mask, dev)
+    if min_voxels <= 1:
+        return set_u8
+    lib = _lib.load()
+    stream = _cc_stream(dev)
+    labels, n = _cc_label(lib, set_u8, connectivity, in_plane, stream)
+    size, _ = _cc_tables(lib, labels, n, None, stream)
+    return _keep_large(labels, size, min_voxels)[0]
+
+
+def _ratio(a, b):
+    return a / b if b else float("nan")
+
+
+def lesion_detection(pred, truth, connectivity=3, in_plane=False, min_voxels=1, voxel_volume=None):
+    """Lesion-wise detection figures of two binary volumes, (n, H, W), any dtype, host or device, non-zero = set.  A
+    lesion is a connected component; connectivity and in_plane as in connected_components.  The default, rank 3, is the
+    WMH challenge's fully connected filter; rank 1 is scipy.ndimage.label's default.  Returns a dict of Python numbers
+      n_truth, n_pred                the lesion counts
+      n_truth_detected               truth lesions with at least one voxel set in pred
+      n_pred_true                    predicted lesions with at least one voxel set in truth
+      recall, precision, f1          n_truth_detected / n_truth, n_pred_true / n_pred and 2 P R / (P + R)
+      voxels_truth, voxels_pred      the set voxels
+      avd_percent                    100 |voxels_pred - voxels_truth| / voxels_truth, the absolute volume difference
+    followed by sizes_truth and sizes_pred, the lesion sizes as device tensors in label order: int32 voxel counts, or
+    with voxel_volume float64 in its unit.  min_voxels > 1 first clears every component of fewer voxels from each
+    volume; the lesion lists and the masks the overlaps are taken against are the cleaned ones.  A ratio whose
+    denominator is 0 is nan and the counts say why; f1 is nan if either ratio is, and 0.0 if both are 0.  Nothing
+    raises.  The labels and tables stay on the device; eight integers travel back."""
+    shape = _shape3(pred, "lesion_detection: pred")
+    if _shape3(truth, "lesion_detection: truth") != shape:
+        raise ValueError("lesion_detection: pred and truth must have the same shape, got %s and %s"
+                         % (shape, _shape3(truth, "lesion_detection: truth")))
+    connectivity, in_plane, min_voxels, voxel_volume = _cc_args("lesion_detection", connectivity, in_plane, min_voxels,
+                                                                voxel_volume)
+    torch = _torch()
+    lib = _lib.load()
+    dev = _surface_device(pred, truth)
+    stream = _cc_stream(dev)
+    masks = [_set_u8(truth, dev), _set_u8(pred, dev)]
+    labelled = [_cc_label(lib, m, connectivity, in_plane, stream) for m in masks]
+    keep = [None, None]
+    if min_voxels > 1:
+        for i, (lab, n) in enumerate(labelled):
+            masks[i], keep[i] = _keep_large(lab, _cc_tables(lib, lab, n, None, stream)[0], min_voxels)
+    sizes, counts = [], []
+    for i, (lab, n) in enumerate(labelled):
+        size, hits = _cc_tables(lib, lab, n, masks[1 - i], stream)
+        if keep[i] is not None:
+            size, hits = size[keep[i]], hits[keep[i]]
+        sizes.append(size)
+        counts += [torch.tensor(size.numel(), device=dev), (hits > 0).sum(), size.sum()]
+    nt, ntd, vt, npd, npt, vp = (int(v) for v in torch.stack([c.to(torch.int64) for c in counts]).cpu())
+    recall, precision = _ratio(ntd, nt), _ratio(npt, npd)
+    if np.isnan(recall) or np.isnan(precision):
+        f1 = float("nan")
+    else:
+        f1 = 2 * precision * recall / (precision + recall) if precision + recall else 0.0
+    res = {"n_truth": nt, "n_pred": npd, "n_truth_detected": ntd, "n_pred_true": npt, "recall": recall,
+           "precision": precision, "f1": f1, "voxels_truth": vt, "voxels_pred": vp,
+           "avd_percent": _ratio(100.0 * abs(vp - vt), vt)}
+    if voxel_volume is not None:
+        sizes = [s.to(torch.float64) * voxel_volume for s in sizes]
+    res["sizes_truth"], res["sizes_pred"] = sizes
+    return res
+
+
+def label_lesion_metrics(labels, code_real, classes=(1, 2, 3), mask=None, **kw):
+    """lesion_detection per class: {k: lesion_detection(labels == k, code_real == k, **kw)} for k in `classes` (any
+    class count), kw = connectivity, in_plane, min_voxels, voxel_volume.  labels: the int8 label map of
+    uresnet_metrics(...)["labels"], the prediction; code_real: the float32 code volume, the truth; both (n, H, W) (a
+    trailing axis of length 1 is dropped), host or device.  mask (same shape, optional): both maps are zeroed where it
+    is zero first."""
+    classes = [int(k) for k in classes]
+    if not classes:
+        raise ValueError("label_lesion_metrics: classes is empty")
+    torch = _torch()
+
+    def vol(v, what):
+        shape = tuple(int(d) for d in (v.shape if hasattr(v, "shape") else np.shape(v)))
+        if len(shape) == 4 and shape[3] == 1:
+            v = v.reshape(shape[:3])
+        _shape3(v, "label_lesion_metrics: " + what)
+        return v
+
+    labels, code_real = vol(labels, "labels"), vol(code_real, "code_real")
+    if tuple(labels.shape) != tuple(code_real.shape):
+        raise ValueError("label_lesion_metrics: labels and code_real must have the same shape, got %s and %s"
+                         % (tuple(labels.shape), tuple(code_real.shape)))
+    if mask is not None:
+        mask = vol(mask, "mask")
+        if tuple(mask.shape) != tuple(labels.shape):
+            raise ValueError("label_lesion_metrics: mask must have the shape of labels")
+    if set(kw) - {"connectivity", "in_plane", "min_voxels", "voxel_volume"}:
+        raise ValueError("label_lesion_metrics: unknown argument %s" % sorted(kw))
+    _cc_args("label_lesion_metrics", kw.get("connectivity", 3), kw.get("in_plane", False), kw.get("min_voxels", 1),
+             kw.get("voxel_volume"))
+    dev = _surface_device(labels, code_real, mask)
+
+    def up(v):
+        return v.to(dev) if isinstance(v, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(v)).to(dev)
+
+    lab, real = up(labels), up(code_real)
+    if mask is not None:
+        keep = up(mask) != 0
+        lab, real = lab * keep.to(lab.dtype), real * keep.to(real.dtype)
+    return {k: lesion_detection(lab == k, real == k, **kw) for k in classes}

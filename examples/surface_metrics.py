@@ -1,5 +1,5 @@
 """DEP-UResNet evaluation of one synthetic subject: the reference's volumes and Dice figures, then how far the
-predicted lesion boundaries lie from the true ones (needs a GPU).
+predicted lesion boundaries lie from the true ones, and which lesions were found at all (needs a GPU).
 
     python examples/surface_metrics.py [--slices 8] [--size 64]
 
@@ -31,10 +31,14 @@ def main():
     m = evaluate.uresnet_metrics(prob, code, ones, code > 0, ones, code > 0, float(np.prod(pixdim)))
     surf = evaluate.label_surface_metrics(m["labels"], code, classes=(1, 2, 3), spacing=data.prepared_spacing(pixdim),
                                           in_plane=True)
+    les = evaluate.label_lesion_metrics(m["labels"], code, classes=(1, 2, 3), voxel_volume=float(np.prod(pixdim)))
     print("dice 1..3: %s" % [round(d, 4) for d in m["dice"][:3]])
     for k, f in surf.items():
         print("class %d: hd %.3f mm  hd95 %.3f mm  assd %.3f mm  (%d / %d surface voxels)"
               % (k, f["hd"], f["hd95"], f["assd"], f["n_surface_a"], f["n_surface_b"]))
+        g = les[k]
+        print("         lesions %d true / %d predicted: recall %.3f  precision %.3f  f1 %.3f  avd %.2f %%"
+              % (g["n_truth"], g["n_pred"], g["recall"], g["precision"], g["f1"], g["avd_percent"]))
 
 
 if __name__ == "__main__":

@@ -561,6 +561,36 @@ size_t depgan_eval_surface_sums_scratch_bytes(long n);
 int depgan_eval_surface_sums(const double* d2, const unsigned char* surf, long n, double* partial, double out_host[4],
                              void* stream);
 
+/* ---- connected components (csrc/components.hip; evaluate.connected_components, lesion_detection) ----
+ * Stateless; device pointers; enqueued on `stream`.  Volumes as above: (D, H, W) bytes with W contiguous, non-zero means
+ * set, 1 <= D, H, W <= 4096 and D*H*W < 2^31.
+ * depgan_eval_cc_label: labels[v] (int32) = 0 where set[v] is 0, else the number 1..N of v's component; N goes to
+ *   n_out_host[0].  connectivity is scipy's rank, generate_binary_structure(3, connectivity): with in_plane 0, 1 is the 6
+ *   face neighbours, 2 the 18 (faces and edges), 3 the 26; with in_plane 1 the neighbours lie in the slice only, 1 is 4
+ *   and 2 and 3 are 8 (slices several times thicker than pixels, as depgan_eval_surface_mask's flag).  Canonical
+ *   numbering: components are numbered in the order of their smallest linear index, which is scipy.ndimage.label's
+ *   numbering, so every output is an integer with one right answer.  Label-equivalence union-find in six launches,
+ *   whatever the content (no loop on the host that relaunches until nothing changes): run starts per row, unions over
+ *   the backward half-neighbourhood by atomicMin on roots, compress, count roots per block, prefix sum, renumber.
+ *   parent[x] <= x always holds, so every chase descends strictly and every retry of a union starts from a strictly
+ *   smaller index: the loops are bounded by construction and no thread waits for another.  The root of a tree is its
+ *   smallest index in whatever order the atomics land, so a call repeats bit for bit.
+ *   scratch: depgan_eval_cc_scratch_bytes(D, H, W) device bytes (0 for a volume outside the limits), 8-byte aligned;
+ *   labels 4-byte aligned.  Synchronises `stream`.
+ * depgan_eval_cc_overlap: zeroes and fills two tables of n_comp ints over the n voxels of `labels`: size[k - 1] = the
+ *   voxel count of component k, hits[k - 1] = the number of its voxels where other_or_null is non-zero (all 0 when it is
+ *   NULL).  Integer atomic adds, one per run of equal labels in a wave: order-independent.  A label outside 1..n_comp is
+ *   not counted.  n_comp = 0 is allowed and launches nothing (size and hits may then be NULL).  The host does not
+ *   synchronise.
+ * Status 1, nothing launched, every buffer untouched: a dimension below 1 or above 4096, D*H*W >= 2^31 (n outside
+ *   1 .. 2^31 - 1), n_comp outside 0..n, connectivity not 1 / 2 / 3, in_plane not 0 / 1, a pointer NULL or misaligned, or
+ *   an output or scratch range that overlaps an input range or another output. */
+size_t depgan_eval_cc_scratch_bytes(int D, int H, int W);
+int depgan_eval_cc_label(const unsigned char* set, int D, int H, int W, int connectivity, int in_plane, int* labels,
+                         void* scratch, long long n_out_host[1], void* stream);
+int depgan_eval_cc_overlap(const int* labels, const unsigned char* other_or_null, long n, int n_comp, int* size,
+                           int* hits, void* stream);
+
 /* ---- parity-test surface: the tensors a training closure left behind ----
  * The step functions are piecewise linear in the ReLU signs and max-pool arg-maxes of the forward passes (GT:256-309
  * activations, GT:322-335 pools; the gradient penalty of GT:543-549 differentiates through them twice).  A parity
