@@ -44,7 +44,9 @@
 //     waves exchange Z through LDS, and the fused epilogue of igemm_conv (igemm_epilogue.inc, same text) fetches
 //     v = Z[0] + Z[1] + Z[2] (even rows) or Z[1] - Z[2] - Z[3] (odd rows) where it used to fetch one transposed value.
 // Covers KS = 3, stride 1, 'same' padding, Cin % 8 == 0, Cout % 32 == 0, even H and W; gathered K (ConvArgs::cpt) as in
-// igemm_conv; no groups.  Everything else stays on igemm_conv_kernel.
+// igemm_conv; no groups; an input view whose halo tile (18 rows, 18 pixels, the channel row and the largest run offset)
+// spans less than 2 GiB -- the sample stride is free (64-bit descriptor base per item).  Everything else stays on
+// igemm_conv_kernel.
 #include <stdlib.h>
 
 #include <type_traits>
@@ -225,9 +227,12 @@ static __device__ __forceinline__ void wino_body(const ConvArgs& a) {
     const int b = t / tilesY;
     const long out_goff = 0;
     const int n0 = ntile * NT;
-    // descriptor at the pixel one row and one column before the image origin: every in-image piece has a non-negative
-    // offset from it
-    const float* const xorg = a.in.p - ((long)a.in.sY + (long)a.in.sX);
+    // descriptor at the pixel one row and one column before the item's tile origin, formed in 64 bits per item (b, ty0
+    // and tx0 are wave-uniform: scalar work): every in-image piece has a non-negative offset from it, and what stays in
+    // the 32-bit vector and scalar offsets is one halo tile plus the channel row (dg_conv_wino_supported bounds it) --
+    // a sample may lie any distance from the view's origin.  (sY and sX fit an int, the same bound: their products
+    // are 32 x 32 -> 64-bit scalar multiplications)
+    const float* const xorg = a.in.p + ((long)b * a.in.sB + (long)(ty0 - 1) * (int)a.in.sY + (long)(tx0 - 1) * (int)a.in.sX);
     const unsigned long long xu = (unsigned long long)xorg;
     // (unsigned locals: readfirstlane returns int, and a low half with bit 31 set would sign-extend into the high one)
     const unsigned xlo = __builtin_amdgcn_readfirstlane((unsigned)xu), xhi = __builtin_amdgcn_readfirstlane((unsigned)(xu >> 32));
@@ -241,17 +246,16 @@ static __device__ __forceinline__ void wino_body(const ConvArgs& a) {
       const int iy = ty0 + (xyx[i] >> 8) - 1, ix = tx0 + (xyx[i] & 255) - 1;
       xvi[i] = ((unsigned)iy < (unsigned)a.H && (unsigned)ix < (unsigned)a.W) ? xvo[i] : SENT;
     }
-    // scalar byte offset of the chunk staged next; one addition per chunk.  Gathered K (ConvArgs::cpt): run t of cpt chunks
-    // starts at in_run_off[t], formed when the run starts
-    const int xso0 = 4 * (b * (int)a.in.sB + ty0 * (int)a.in.sY + tx0 * (int)a.in.sX);
-    int xso = GATH ? xso0 + 4 * (int)a.in_run_off[0] : xso0;
+    // scalar byte offset of the chunk staged next, from the item's descriptor base: the channel, one addition per chunk.
+    // Gathered K (ConvArgs::cpt): run t of cpt chunks starts at in_run_off[t], formed when the run starts
+    int xso = GATH ? 4 * (int)a.in_run_off[0] : 0;
     int grun = 0, gleft = GATH ? a.cpt : 0;
     auto next_chunk = [&]() {
       if constexpr (GATH) {
         if (--gleft == 0) {
           ++grun;
           gleft = a.cpt;
-          xso = xso0 + 4 * (int)a.in_run_off[grun];
+          xso = 4 * (int)a.in_run_off[grun];
         } else {
           xso += 4 * WN_CK;
         }
@@ -580,6 +584,17 @@ bool dg_conv_wino_supported(const ConvPlan& pl, const ConvArgs& a) {
   if (!dg_plan_wino(pl)) return false;
   if (a.Cin != pl.Cin || (a.Cin % WN_CK) || (a.Cout % 32) || a.groups > 1 || a.dbg || ((a.H | a.W) & 1)) return false;
   if (a.cpt > 0 && ((a.Cin % (a.cpt * WN_CK)) != 0 || a.Cin / (a.cpt * WN_CK) > 4)) return false;
+  // Input addressing: a 64-bit descriptor base per item (sample and tile origin), 32-bit byte offsets inside it.  What
+  // the offsets span is one halo tile plus the channel row and the largest run offset; the 16-row form bounds both
+  // forms.  No layout of the model comes near 2 GiB here; the sample stride is not part of it
+  long run = 0;
+  for (int t = 0; a.cpt > 0 && t < a.Cin / (a.cpt * WN_CK); ++t) {
+    if (a.in_run_off[t] < 0) return false;
+    run = a.in_run_off[t] > run ? a.in_run_off[t] : run;
+  }
+  constexpr long lim = 1L << 29;   // 2^31 bytes in floats; each term below it first, so that the sum cannot overflow
+  if (a.in.sY < 0 || a.in.sX < 0 || a.in.sY >= lim || a.in.sX >= lim || run >= lim) return false;
+  if ((WnCfg<2>::TH + 2) * a.in.sY + WN_TW * a.in.sX + a.Cin + run >= lim) return false;
   return true;
 }
 
@@ -679,7 +694,7 @@ static int wino_launch(ConvArgs a, hipStream_t st) {
 
 int dg_conv_wino(const ConvPlan& pl, const ConvArgs& a, hipStream_t st) {
   if (!dg_conv_wino_supported(pl, a)) {
-    dg_set_error("dg_conv_wino: shape not covered (3x3, Cin %% 8, Cout %% 32, even H and W, no groups)");
+    dg_set_error("dg_conv_wino: shape not covered (3x3, Cin %% 8, Cout %% 32, even H and W, no groups, a halo tile of the input view within 2 GiB)");
     return DG_ERR_UNSUPPORTED;
   }
   return wino_mt(a) == 2 ? wino_launch<2>(a, st) : wino_launch<1>(a, st);
