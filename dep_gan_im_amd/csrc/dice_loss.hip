@@ -208,13 +208,13 @@ int dg_dice_check(const char* who, int form, float ce_coef, float dice_coef, flo
   return DG_OK;
 }
 
-int dg_dice_operands_check(const char* who, const float* probs, const float* onehot, const unsigned char* codes,
-                           int ignore_code, const float* dz, long P, int C) {
+int dg_dice_operands_check(const char* who, const float* probs, DgLabels lab, int ignore_code, const float* dz, long P,
+                           int C) {
   if (C < DG_MIN_CLASSES || C > DG_MAX_CLASSES) {
     dg_set_error("%s: %d classes (the kernels cover %d to %d)", who, C, DG_MIN_CLASSES, DG_MAX_CLASSES);
     return DG_ERR_ARG;
   }
-  if (!probs || P < 1 || (!onehot == !codes)) {
+  if (!probs || P < 1 || (!lab.onehot == !lab.codes)) {
     dg_set_error("%s: null probs, P < 1, or not exactly one of onehot and codes", who);
     return DG_ERR_ARG;
   }
@@ -224,7 +224,7 @@ int dg_dice_operands_check(const char* who, const float* probs, const float* one
   }
   // rows are read and written 16 bytes at a time where C is a multiple of 4, else float by float
   const uintptr_t al = (C % 4 == 0) ? 15 : 3;
-  if (((uintptr_t)probs | (uintptr_t)onehot | (uintptr_t)dz) & al) {
+  if (((uintptr_t)probs | (uintptr_t)lab.onehot | (uintptr_t)dz) & al) {
     dg_set_error("%s: probs, onehot and dz must be %d-byte aligned for %d classes", who, (int)al + 1, C);
     return DG_ERR_ARG;
   }
@@ -253,11 +253,11 @@ static void dice_launch(bool onehot_lbl, bool read_dz, int nb, hipStream_t st, c
 #undef DG_DICE_GRAD
 }
 
-int dg_dice_loss(const float* probs, const float* onehot, const unsigned char* codes, int ignore_code, int form,
-                 const float* coef, float smooth, float ce_coef, float dice_coef, float* dz, DgDiceDev* out, long P, int C,
-                 float* scratch, size_t scratch_floats, hipStream_t st) {
-  DGCHECK(dg_dice_check("dg_dice_loss", form, ce_coef, dice_coef, smooth, coef, C, C));
-  DGCHECK(dg_dice_operands_check("dg_dice_loss", probs, onehot, codes, ignore_code, dz, P, C));
+int dg_dice_loss(const float* probs, DgLabels lab, int ignore_code, const DgDiceSetting& set, float* dz, DgDiceDev* out,
+                 long P, int C, float* scratch, size_t scratch_floats, hipStream_t st) {
+  DGCHECK(dg_dice_check("dg_dice_loss", set.form, set.ce_coef, set.dice_coef, set.smooth,
+                        set.form == DEPGAN_DICE_CLASS ? set.c : nullptr, C, C));
+  DGCHECK(dg_dice_operands_check("dg_dice_loss", probs, lab, ignore_code, dz, P, C));
   if (!out || ((uintptr_t)out & 7)) { dg_set_error("dg_dice_loss: null or misaligned out"); return DG_ERR_ARG; }
   const size_t need = dg_dice_scratch(P, C);
   if (!scratch || scratch_floats < need) {
@@ -265,13 +265,13 @@ int dg_dice_loss(const float* probs, const float* onehot, const unsigned char* c
     return DG_ERR_ARG;
   }
   DiceCoef dc;
-  dc.form = form;
-  dc.smooth = smooth;
-  for (int k = 0; k < DG_MAX_CLASSES; ++k) dc.c[k] = (k < C) ? (coef ? coef[k] : 1.0f / (float)C) : 0.f;
+  dc.form = set.form;
+  dc.smooth = set.smooth;
+  for (int k = 0; k < DG_MAX_CLASSES; ++k) dc.c[k] = (k < C) ? set.c[k] : 0.f;
   const int nb = dice_nblk((size_t)P);
-  const bool read_dz = ce_coef != 0.f;
+  const bool read_dz = set.ce_coef != 0.f;
   switch (C) {
-#define DG_DICE(N) case N: dice_launch<N>(onehot != nullptr, read_dz, nb, st, probs, onehot, codes, ignore_code, scratch, dc, out, ce_coef, dice_coef, dz, P); break;
+#define DG_DICE(N) case N: dice_launch<N>(lab.onehot != nullptr, read_dz, nb, st, probs, lab.onehot, lab.codes, ignore_code, scratch, dc, out, set.ce_coef, set.dice_coef, dz, P); break;
     DG_DICE(2) DG_DICE(3) DG_DICE(4) DG_DICE(5) DG_DICE(6) DG_DICE(7) DG_DICE(8)
 #undef DG_DICE
   }

@@ -14,6 +14,7 @@
 #include "deconv_fwd.h"
 #include "noise.h"
 #include "ops.h"
+#include "train_ops.h"
 
 struct PInfo {
   std::string name;
@@ -211,29 +212,24 @@ struct depgan_ctx {
   unsigned last_drop_seed = 0;
   Tn draw_tmp;                     // gradient at the raw conv output (largest layer)
   float *logits = nullptr, *dz = nullptr, *loss_dev = nullptr;
-  // depgan_uresnet_set_census(1): every depgan_uresnet_* call also counts (true class, predicted class) pairs; the
-  // table of the last such call, row = true class, row-major nc_out x nc_out
-  bool census = false, census_valid = false;
-  long long last_census[DEPGAN_MAX_HEAD_CLASSES * DEPGAN_MAX_HEAD_CLASSES];
-  // depgan_uresnet_set_loss_weights: the loss-weight mode (off by default).  lw_w: nc_out class weights, lw_ignore: the
-  // ignore code (-1: none, read with class codes only); lw_counts: the label pre-pass counts of the last call made with
-  // the mode on ([0] den, [1] ignored, [2] out of range, [3 + k] class k), which came back with that call's loss
-  bool lw_on = false, lw_valid = false;
-  float lw_w[DEPGAN_MAX_HEAD_CLASSES];
-  int lw_ignore = -1;
-  long long lw_counts[DEPGAN_LABEL_NCOUNT];
-  // depgan_uresnet_set_focal: the focal mode (off by default: both 0).  With it on the cross-entropy runs the weighted
-  // path -- lw_w / lw_ignore when lw_on, else unit weights and no ignore code -- and lw_counts / lw_valid are filled
-  bool focal_on = false;
-  float focal_gamma = 0.f, focal_eps = 0.f;
-  // depgan_uresnet_set_dice_loss: the soft Dice loss (DEPGAN_DICE_OFF by default).  dice_c: the nc_out class coefficients
-  // of the class form; dice_sums / dice_last: I_k, P_k, T_k (3 nc_out, packed) and the Dice term of the last call made
-  // with the mode on, which came back with that call's loss
-  int dice_form = 0;
-  bool dice_valid = false;
-  float dice_ce_coef = 1.f, dice_coef = 1.f, dice_smooth = 0.f, dice_last = 0.f;
-  float dice_c[DEPGAN_MAX_HEAD_CLASSES];
-  double dice_sums[3 * DEPGAN_MAX_HEAD_CLASSES];
+  // the supervised loss as the depgan_uresnet_set_* entries left it (everything off by default): the census, the
+  // loss-weight mode and the focal mode in ce (train_ops.h states each), the soft Dice loss beside it
+  struct {
+    DgCeSetting ce;
+    DgDiceSetting dice;
+  } loss;
+  // what came back with the loss of the last depgan_uresnet_* call made under that setting: the census table (row =
+  // true class, row-major nc_out x nc_out), the label pre-pass counts of the weighted path ([0] den, [1] ignored, [2]
+  // out of range, [3 + k] class k), and the Dice sums I_k, P_k, T_k (3 nc_out, packed) with the Dice term.  Cleared:
+  // census_valid when the census is switched off; counts_valid and dice_valid when their mode is set anew or switched
+  // off, counts_valid also by every depgan_uresnet_set_focal
+  struct {
+    bool census_valid = false, counts_valid = false, dice_valid = false;
+    long long census[DEPGAN_MAX_HEAD_CLASSES * DEPGAN_MAX_HEAD_CLASSES];
+    long long counts[DEPGAN_LABEL_NCOUNT];
+    double dice_sums[3 * DEPGAN_MAX_HEAD_CLASSES];
+    float dice_loss = 0.f;
+  } last;
   float *ones1k = nullptr, *zeros1k = nullptr;
   float *n_mean0 = nullptr, *n_rstd0 = nullptr, *n_mean1 = nullptr, *n_rstd1 = nullptr, *n_meanh = nullptr,
         *n_rstdh = nullptr;

@@ -4,7 +4,6 @@
 // update (GT:574-598; A7-A9) and Keras Adam (A10).  The algebra follows
 // oracle/manual.py step for step.
 #include "model.h"
-#include "train_ops.h"
 
 #include <dlfcn.h>
 #include <float.h>

@@ -1,7 +1,6 @@
 // The single-operator entries (depgan_op_*): the unit-test surface of the kernels.  Each plans, packs and launches on
 // its own stream and workspace; nothing here touches a context's state.
 #include "model.h"
-#include "train_ops.h"
 
 #include <math.h>
 #include <stdlib.h>
@@ -515,94 +514,69 @@ int depgan_op_affine_act(const float* in, float* out, float* out_pre, const floa
   return dg_affine_act(a, (hipStream_t)stream);
 }
 
-int depgan_op_softmax_ce(const float* logits, const float* onehot, const unsigned char* codes, float* probs, float* dz,
-                         float* loss_sum, long P, int C, void* stream) {
-  DGCHECK(dg_softmax_ce_check(logits, onehot, codes, probs, dz, loss_sum, P, C));
-  hipStream_t st = (hipStream_t)stream;
-  if (!onehot && !codes) return dg_softmax_ce(logits, nullptr, nullptr, probs, nullptr, nullptr, nullptr, P, C, nullptr, st);
-  // 2048 floats of reduction scratch, then the counter of out-of-range codes
-  DevTmp scratch(st);
-  DGCHECK(op_alloc(&scratch, 2048 + 4, "op_softmax_ce"));
-  unsigned* bad = reinterpret_cast<unsigned*>(scratch.as<float>() + 2048);
-  DGCHECK(dg_softmax_ce(logits, onehot, codes, probs, dz, loss_sum, bad, P, C, scratch.as<float>(), st));
-  if (!codes) return DG_OK;
-  unsigned h = 0;
-  if (hipMemcpyAsync(&h, bad, sizeof(h), hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) {
-    dg_set_error("op_softmax_ce: copy back failed");
-    return DG_ERR_HIP;
+// The softmax + cross-entropy entries behind their own refusals: `a` holds the caller's operands and the setting.  This
+// adds the reduction scratch and, behind it, the one device tail (DgCeDev; the caller's loss_sum stands for its loss
+// slot), launches, copies back what the setting wrote, and reports the class codes outside [0, C).  census_host /
+// counts_host: where the census and the label counts go (null where the setting has none)
+static int op_softmax_ce_run(const char* who, SoftmaxCeArgs a, long long* census_host, long long* counts_host,
+                             hipStream_t st) {
+  const long P = a.P;
+  const int C = a.C;
+  const bool labels = a.lab.onehot || a.lab.codes;
+  const size_t cap = (dg_softmax_ce_scratch(P, C, a.set) + 1) & ~(size_t)1;   // even: the tail is 8-byte aligned
+  DgCeDev h;
+  const auto bind = [&](float* scratch, DgCeDev* tail) {
+    if (!labels) return;
+    a.scratch = scratch;
+    a.scratch_floats = cap;
+    a.bad_count = &tail->bad;
+    a.census = tail->census;
+    a.counts = tail->counts;
+  };
+  // the refusals come before anything is allocated: the host's copy of the tail, never read through, stands in
+  bind(reinterpret_cast<float*>(&h), &h);
+  DGCHECK(dg_softmax_ce_check(who, a));
+  DevTmp dev(st);
+  DgCeDev* tail = nullptr;
+  if (labels) {
+    DGCHECK(op_alloc(&dev, cap + sizeof(DgCeDev) / sizeof(float), who));
+    tail = reinterpret_cast<DgCeDev*>(dev.as<float>() + cap);
+    bind(dev.as<float>(), tail);
   }
-  if (h) {
-    dg_set_error("op_softmax_ce: %u of %ld class codes are outside [0, %d)", h, P, C);
-    return DG_ERR_ARG;
-  }
-  return DG_OK;
-}
-int depgan_op_softmax_ce_census(const float* logits, const float* onehot, const unsigned char* codes, float* probs,
-                                float* dz, float* loss_sum, long long* census_host, long P, int C, void* stream) {
-  if (!census_host) { dg_set_error("op_softmax_ce_census: null census_host"); return DG_ERR_ARG; }
-  if (!onehot && !codes) { dg_set_error("op_softmax_ce_census: a census needs labels (onehot or codes)"); return DG_ERR_ARG; }
-  DGCHECK(dg_softmax_ce_check(logits, onehot, codes, probs, dz, loss_sum, P, C));
-  hipStream_t st = (hipStream_t)stream;
-  // the reduction scratch, then the counter of out-of-range codes (padded to 8 bytes) and the C*C 64-bit counts
-  const size_t cap = (dg_softmax_ce_census_scratch(P, C) + 1) & ~(size_t)1;      // even: the counts behind it are 8-byte aligned
-  DevTmp scratch(st);
-  DGCHECK(op_alloc(&scratch, cap + 2 + 2 * (size_t)C * C, "op_softmax_ce_census"));
-  unsigned* bad = reinterpret_cast<unsigned*>(scratch.as<float>() + cap);
-  unsigned long long* cen = reinterpret_cast<unsigned long long*>(scratch.as<float>() + cap + 2);
-  DGCHECK(dg_softmax_ce_census(logits, onehot, codes, probs, dz, loss_sum, bad, cen, P, C, scratch.as<float>(), cap, st));
-  struct {
-    unsigned bad, pad;
-    long long census[DEPGAN_MAX_HEAD_CLASSES * DEPGAN_MAX_HEAD_CLASSES];
-  } h;
-  if (hipMemcpyAsync(&h, bad, 8 + (size_t)C * C * sizeof(long long), hipMemcpyDeviceToHost, st) != hipSuccess ||
+  DGCHECK(dg_softmax_ce(a, st));
+  // one-hot labels on the plain path: no code can be out of range, nothing to fetch, no synchronisation
+  if (!a.lab.codes && !census_host && !counts_host) return DG_OK;
+  if (hipMemcpyAsync(&h, tail, DgCeDev::bytes(C, a.set), hipMemcpyDeviceToHost, st) != hipSuccess ||
       hipStreamSynchronize(st) != hipSuccess) {
-    dg_set_error("op_softmax_ce_census: copy back failed");
-    return DG_ERR_HIP;
-  }
-  memcpy(census_host, h.census, (size_t)C * C * sizeof(long long));
-  if (h.bad) {
-    dg_set_error("op_softmax_ce_census: %u of %ld class codes are outside [0, %d)", h.bad, P, C);
-    return DG_ERR_ARG;
-  }
-  return DG_OK;
-}
-// depgan_op_softmax_ce_weighted and depgan_op_softmax_ce_focal behind their own refusals: focal null = the loss-weight
-// mode alone, else {gamma, label_smoothing}
-static int op_softmax_ce_weighted_run(const char* who, const float* logits, const float* onehot,
-                                      const unsigned char* codes, const float* w_host, int ignore_code,
-                                      const float* focal, float* probs, float* dz, float* loss_sum,
-                                      long long* census_host, long long* counts_host, long P, int C, hipStream_t st) {
-  // the reduction scratch, then what comes back: the counter of out-of-range codes (padded to 8 bytes), the C*C census
-  // and the C + 3 label counts
-  const size_t cap = (dg_softmax_ce_weighted_scratch(P, C, census_host != nullptr) + 1) & ~(size_t)1;
-  struct {
-    unsigned bad, pad;
-    long long census[DEPGAN_MAX_HEAD_CLASSES * DEPGAN_MAX_HEAD_CLASSES];
-    long long counts[DEPGAN_LABEL_NCOUNT];
-  } h;
-  DevTmp scratch(st);
-  DGCHECK(op_alloc(&scratch, cap + sizeof(h) / sizeof(float), who));
-  unsigned* bad = reinterpret_cast<unsigned*>(scratch.as<float>() + cap);
-  unsigned long long* cen = reinterpret_cast<unsigned long long*>(scratch.as<float>() + cap + 2);
-  unsigned long long* cnt = cen + DEPGAN_MAX_HEAD_CLASSES * DEPGAN_MAX_HEAD_CLASSES;
-  if (focal)
-    DGCHECK(dg_softmax_ce_focal(logits, onehot, codes, probs, dz, loss_sum, bad, census_host ? cen : nullptr, cnt, w_host,
-                                ignore_code, focal[0], focal[1], P, C, scratch.as<float>(), cap, st));
-  else
-    DGCHECK(dg_softmax_ce_weighted(logits, onehot, codes, probs, dz, loss_sum, bad, census_host ? cen : nullptr, cnt,
-                                   w_host, ignore_code, P, C, scratch.as<float>(), cap, st));
-  // the census region is written only with census_host: the part of h it covers is then not read
-  if (hipMemcpyAsync(&h, bad, sizeof(h), hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) {
     dg_set_error("%s: copy back failed", who);
     return DG_ERR_HIP;
   }
   if (census_host) memcpy(census_host, h.census, (size_t)C * C * sizeof(long long));
-  memcpy(counts_host, h.counts, (size_t)(C + 3) * sizeof(long long));
+  if (counts_host) memcpy(counts_host, h.counts, (size_t)(C + 3) * sizeof(long long));
   if (h.bad) {
     dg_set_error("%s: %u of %ld class codes are outside [0, %d)", who, h.bad, P, C);
     return DG_ERR_ARG;
   }
   return DG_OK;
+}
+// the operands every entry passes on
+static SoftmaxCeArgs op_softmax_ce_args(const float* logits, const float* onehot, const unsigned char* codes,
+                                        float* probs, float* dz, float* loss_sum, long P, int C) {
+  return SoftmaxCeArgs{logits, {onehot, codes}, probs, dz, loss_sum, nullptr, nullptr, nullptr, DgCeSetting{}, P, C,
+                       nullptr, 0};
+}
+int depgan_op_softmax_ce(const float* logits, const float* onehot, const unsigned char* codes, float* probs, float* dz,
+                         float* loss_sum, long P, int C, void* stream) {
+  const SoftmaxCeArgs a = op_softmax_ce_args(logits, onehot, codes, probs, dz, loss_sum, P, C);
+  return op_softmax_ce_run("op_softmax_ce", a, nullptr, nullptr, (hipStream_t)stream);
+}
+int depgan_op_softmax_ce_census(const float* logits, const float* onehot, const unsigned char* codes, float* probs,
+                                float* dz, float* loss_sum, long long* census_host, long P, int C, void* stream) {
+  if (!census_host) { dg_set_error("op_softmax_ce_census: null census_host"); return DG_ERR_ARG; }
+  if (!onehot && !codes) { dg_set_error("op_softmax_ce_census: a census needs labels (onehot or codes)"); return DG_ERR_ARG; }
+  SoftmaxCeArgs a = op_softmax_ce_args(logits, onehot, codes, probs, dz, loss_sum, P, C);
+  a.set.census = true;
+  return op_softmax_ce_run("op_softmax_ce_census", a, census_host, nullptr, (hipStream_t)stream);
 }
 int depgan_op_softmax_ce_weighted(const float* logits, const float* onehot, const unsigned char* codes,
                                   const float* w_host, int n, int ignore_code, float* probs, float* dz, float* loss_sum,
@@ -610,9 +584,10 @@ int depgan_op_softmax_ce_weighted(const float* logits, const float* onehot, cons
   if (!w_host || !counts_host) { dg_set_error("op_softmax_ce_weighted: null w_host or counts_host"); return DG_ERR_ARG; }
   if (!onehot && !codes) { dg_set_error("op_softmax_ce_weighted: loss weights need labels (onehot or codes)"); return DG_ERR_ARG; }
   DGCHECK(dg_loss_weights_check("op_softmax_ce_weighted", w_host, n, C, ignore_code));
-  DGCHECK(dg_softmax_ce_check(logits, onehot, codes, probs, dz, loss_sum, P, C));
-  return op_softmax_ce_weighted_run("op_softmax_ce_weighted", logits, onehot, codes, w_host, ignore_code, nullptr, probs,
-                                    dz, loss_sum, census_host, counts_host, P, C, (hipStream_t)stream);
+  SoftmaxCeArgs a = op_softmax_ce_args(logits, onehot, codes, probs, dz, loss_sum, P, C);
+  a.set.census = census_host != nullptr;
+  a.set.set_weights(w_host, C, ignore_code);
+  return op_softmax_ce_run("op_softmax_ce_weighted", a, census_host, counts_host, (hipStream_t)stream);
 }
 int depgan_op_softmax_ce_focal(const float* logits, const float* onehot, const unsigned char* codes, const float* w_host,
                                int n, int ignore_code, float gamma, float label_smoothing, float* probs, float* dz,
@@ -622,10 +597,13 @@ int depgan_op_softmax_ce_focal(const float* logits, const float* onehot, const u
   if (!onehot && !codes) { dg_set_error("op_softmax_ce_focal: the focal loss needs labels (onehot or codes)"); return DG_ERR_ARG; }
   DGCHECK(dg_focal_check("op_softmax_ce_focal", gamma, label_smoothing));
   DGCHECK(dg_loss_weights_check("op_softmax_ce_focal", w_host, n, C, ignore_code));
-  DGCHECK(dg_softmax_ce_check(logits, onehot, codes, probs, dz, loss_sum, P, C));
-  const float focal[2] = {gamma, label_smoothing};
-  return op_softmax_ce_weighted_run("op_softmax_ce_focal", logits, onehot, codes, w_host, ignore_code, focal, probs, dz,
-                                    loss_sum, census_host, counts_host, P, C, (hipStream_t)stream);
+  SoftmaxCeArgs a = op_softmax_ce_args(logits, onehot, codes, probs, dz, loss_sum, P, C);
+  a.set.census = census_host != nullptr;
+  a.set.set_weights(w_host, C, ignore_code);   // null: unit weights, the ignore code still holds
+  a.set.focal = true;
+  a.set.gamma = gamma;
+  a.set.eps = label_smoothing;
+  return op_softmax_ce_run("op_softmax_ce_focal", a, census_host, counts_host, (hipStream_t)stream);
 }
 int depgan_op_label_counts(const float* onehot, const unsigned char* codes, long P, int C, int ignore_code,
                            long long* out_host, void* stream) {
@@ -650,15 +628,17 @@ int depgan_op_dice_loss(const float* probs, const float* onehot, const unsigned 
                         double* sums_host, float* loss_host, long P, int C, void* stream) {
   if (!dz || !sums_host || !loss_host) { dg_set_error("op_dice_loss: null dz_inout, sums_host or loss_host"); return DG_ERR_ARG; }
   DGCHECK(dg_dice_check("op_dice_loss", form, ce_coef, dice_coef, smooth, class_coef_host, n, C));
-  DGCHECK(dg_dice_operands_check("op_dice_loss", probs, onehot, codes, ignore_code, dz, P, C));
+  const DgLabels lab{onehot, codes};
+  DGCHECK(dg_dice_operands_check("op_dice_loss", probs, lab, ignore_code, dz, P, C));
   hipStream_t st = (hipStream_t)stream;
+  DgDiceSetting set;
+  set.set(form, ce_coef, dice_coef, smooth, class_coef_host, C);
   // the reduction scratch, then what the coefficient stage leaves
   const size_t cap = (dg_dice_scratch(P, C) + 1) & ~(size_t)1;
   DevTmp scratch(st);
   DGCHECK(op_alloc(&scratch, cap + sizeof(DgDiceDev) / sizeof(float), "op_dice_loss"));
   DgDiceDev* out = reinterpret_cast<DgDiceDev*>(scratch.as<float>() + cap);
-  DGCHECK(dg_dice_loss(probs, onehot, codes, ignore_code, form, class_coef_host, smooth, ce_coef, dice_coef, dz, out, P, C,
-                       scratch.as<float>(), cap, st));
+  DGCHECK(dg_dice_loss(probs, lab, ignore_code, set, dz, out, P, C, scratch.as<float>(), cap, st));
   DgDiceDev h;
   if (hipMemcpyAsync(&h, out, offsetof(DgDiceDev, A), hipMemcpyDeviceToHost, st) != hipSuccess ||
       hipStreamSynchronize(st) != hipSuccess) {

@@ -1,5 +1,5 @@
 // One pixel's class row in registers: C = 2..8 logits, probabilities or gradient entries (DEPGAN_MAX_HEAD_CLASSES = 8
-// keeps a row within two float4).  Shared by softmax_ce_kernel (train_ops.hip) and head_softmax_bf16s_kernel
+// keeps a row within two float4).  Shared by softmax_ce_kernel (softmax_ce.hip) and head_softmax_bf16s_kernel
 // (igemm_bf16s.hip), so the two softmaxes are one text.
 #pragma once
 #include "common.h"

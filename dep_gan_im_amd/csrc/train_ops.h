@@ -42,60 +42,84 @@ int dg_bn_bwd_coeffs(const float* sums, const float* mean, const float* rstd, co
 int dg_axpby_ch(TView d, TView x, TView out, int B, int H, int W, int C, const float* A, const float* Bc,
                 const float* Cc, hipStream_t st);
 
-// softmax + keras categorical cross-entropy on dense (P, C) logits, C = 2..8: probs out; with labels also
-// dz = dLoss/dlogits (loss = mean over pixels) and loss_sum[0] = sum over pixels of the per-pixel loss.  Labels are a
-// float32 one-hot row (onehot) or one class code per pixel (codes), never both; neither: probabilities only.  With
-// codes, bad_count[0] receives the number of pixels whose code is >= C (they add no loss and no gradient); with onehot
-// it receives 0 where it is given.  scratch: 2048 floats (unused without labels).  Rows are accessed 16 bytes at a time
-// where C % 4 == 0 (16-byte aligned operands), else float by float.
-int dg_softmax_ce(const float* logits, const float* onehot, const unsigned char* codes, float* probs, float* dz,
-                  float* loss_sum, unsigned* bad_count, long P, int C, float* scratch, hipStream_t st);
-// dg_softmax_ce with labels plus the class census of the same pass: census[tc * C + pc] (C*C 64-bit device counts,
-// 8-byte aligned) = the pixels of true class tc predicted as pc.  pc = the first index of the maximum of the stored
-// probability row (k = 0..C-1, strict >: np.argmax of probs); tc = the code, or the first index of the maximum of the
-// one-hot row (an all-zero row is class 0).  A pixel whose code is >= C is in no bin: sum(census) + bad_count == P.
-// probs, dz and loss_sum have the bits dg_softmax_ce gives.  Two stages, no atomics, nothing to zero between calls; the
-// block tables follow the 2048 floats of the other partials: dg_softmax_ce_census_scratch(P, C) floats of scratch
-// (at most 2048 + 1024 C C), DG_ERR_ARG when scratch_floats is less.  bad_count is required (0 with onehot).
-size_t dg_softmax_ce_census_scratch(long P, int C);
-int dg_softmax_ce_census(const float* logits, const float* onehot, const unsigned char* codes, float* probs, float* dz,
-                         float* loss_sum, unsigned* bad_count, unsigned long long* census, long P, int C, float* scratch,
-                         size_t scratch_floats, hipStream_t st);
-// The loss-weight mode.  cw: C host class weights, finite and >= 0 with at least one > 0 (null: unit weights);
-// ignore_code: -1 for none, else a byte value whose pixels have t = 0 and are not counted as out of range (read with
-// codes only: with one-hot labels the ignored pixel is the all-zero row).
-// dg_loss_weights_check validates both without a HIP call (n must equal C where w is given).
-// dg_label_counts: the label pre-pass alone.  counts (C + 3 64-bit device counts, 8-byte aligned) receives
-// [0] den = the pixels with weight w = sum_k cw[k] t[k] != 0, [1] the pixels without a true class (the ignore code, an
-// all-zero one-hot row), [2] the codes >= C that are not the ignore code, [3 + k] the pixels of true class k (the code,
-// or the first arg-max of the row).  Two stages, no atomics, nothing to zero; dg_label_counts_scratch(P, C) floats.
-// dg_softmax_ce_weighted: that pass, then dg_softmax_ce (census == null) or dg_softmax_ce_census on the label row
-// cw[k] t[k] with 1 / den for 1 / P (0 for den = 0), den read on the device from counts[0]; loss_sum[0] = the weighted
-// sum, the mean is loss_sum / den.  Under it a pixel without a true class joins no census bin.  With unit weights and
-// nothing ignored every output has dg_softmax_ce's bits.  dg_softmax_ce_weighted_scratch(P, C, census) floats.
+// ---- the supervised loss (softmax_ce.hip, dice_loss.hip) ----
+// the labels of one call: a float32 one-hot row per pixel (onehot) or one class code per pixel (codes), never both
+struct DgLabels {
+  const float* onehot;
+  const unsigned char* codes;
+};
+// The cross-entropy setting, on the host.  census: also count (true class, predicted class) pairs.  weighted: the
+// loss-weight mode -- cw: C class weights, finite and >= 0 with at least one > 0; ignore: -1 for none, else a byte value
+// whose pixels have t = 0 and are not counted as out of range (read with codes only: with one-hot labels the ignored
+// pixel is the all-zero row).  focal: the focal mode (include/depgan.h, depgan_uresnet_set_focal, states the rule) with
+// gamma finite and >= 0 and label smoothing eps in [0, 1); it runs the weighted path, with unit weights and no ignore
+// code unless weighted is on too.  gamma = 0 with eps = 0 is allowed and runs the focal statements.
+struct DgCeSetting {
+  bool census = false, weighted = false, focal = false;
+  float cw[DEPGAN_MAX_HEAD_CLASSES];
+  int ignore = -1;
+  float gamma = 0.f, eps = 0.f;
+  bool weighted_path() const { return weighted || focal; }   // the label pre-pass runs and leaves counts
+  // the loss-weight mode on: C weights (null: unit weights) and the ignore code
+  void set_weights(const float* w, int C, int ignore_code) {
+    for (int k = 0; k < C; ++k) cw[k] = w ? w[k] : 1.0f;
+    ignore = ignore_code;
+    weighted = true;
+  }
+};
+// What a labelled launch leaves on the device beside probs and dz, as the host reads it: the summed loss (entries that
+// take a loss_sum of their own leave the slot unused), bad = the codes >= C that are not the ignore code (0 with
+// onehot), census[tc * C + pc] = the pixels of true class tc predicted as pc, and the label pre-pass counts: [0] den =
+// the pixels with weight w = sum_k cw[k] t[k] != 0, [1] the pixels without a true class (the ignore code, an all-zero
+// one-hot row), [2] the codes >= C that are not the ignore code, [3 + k] the pixels of true class k (the code, or the
+// first arg-max of the row).  pc = the first index of the maximum of the stored probability row (np.argmax of probs);
+// tc = the code, or the first arg-max of the one-hot row (an all-zero row is class 0; on the weighted path it joins no
+// bin).  A pixel whose code is >= C is in no bin: sum(census) + bad + (weighted path: pixels without a true class) == P.
+struct DgCeDev {
+  float loss;
+  unsigned bad;
+  unsigned long long census[DEPGAN_MAX_HEAD_CLASSES * DEPGAN_MAX_HEAD_CLASSES];
+  unsigned long long counts[DEPGAN_LABEL_NCOUNT];
+  // the leading bytes a launch under s writes: what a copy back to the host takes
+  static size_t bytes(int C, const DgCeSetting& s) {
+    if (s.weighted_path()) return offsetof(DgCeDev, counts) + (size_t)(C + 3) * sizeof(long long);
+    return offsetof(DgCeDev, census) + (s.census ? (size_t)C * C : 0) * sizeof(long long);
+  }
+};
+// softmax + keras categorical cross-entropy on dense (P, C) logits, C = 2..8: probs out; with labels also dz =
+// dLoss/dlogits (loss = mean over pixels) and loss_sum[0] = sum over pixels of the per-pixel loss.  Without labels:
+// probabilities only -- nothing else is written, no scratch is needed and every setting is off.  bad_count: required
+// with codes, with a census and on the weighted path, else optional.  census (C*C counts) with set.census, counts
+// (C + 3) with set.weighted_path(), both 8-byte aligned.  On the weighted path the label pre-pass runs first and the
+// loss runs on the label row cw[k] t[k] with 1 / den for 1 / P (0 for den = 0), den read on the device from counts[0];
+// loss_sum[0] = the weighted sum, the mean is loss_sum / den; with unit weights and nothing ignored every output has
+// the plain path's bits.  The scratch holds the partials of both passes in turn.  Two stages,
+// no atomics, nothing to zero between calls; the pre-pass shares the scratch: dg_softmax_ce_scratch(P, C, set) floats =
+// max(2048 + the census's block tables, the pre-pass's block tables), at most 2048 + 1024 C C.  Rows are accessed 16
+// bytes at a time where C % 4 == 0 (16-byte aligned operands), else float by float.
+struct SoftmaxCeArgs {
+  const float* logits;
+  DgLabels lab;
+  float *probs, *dz, *loss_sum;
+  unsigned* bad_count;
+  unsigned long long *census, *counts;
+  DgCeSetting set;
+  long P;
+  int C;
+  float* scratch;
+  size_t scratch_floats;
+};
+size_t dg_softmax_ce_scratch(long P, int C, const DgCeSetting& set);
+// every refusal of dg_softmax_ce, without a HIP call and without reading through a pointer: DG_ERR_ARG and a message
+int dg_softmax_ce_check(const char* who, const SoftmaxCeArgs& a);
+int dg_softmax_ce(const SoftmaxCeArgs& a, hipStream_t st);
+// dg_loss_weights_check and dg_focal_check validate a setting's values without a HIP call (n must equal C where w is
+// given).  dg_label_counts: the label pre-pass alone (cw null: unit weights); dg_label_counts_scratch(P, C) floats.
 int dg_loss_weights_check(const char* who, const float* w, int n, int C, int ignore_code);
+int dg_focal_check(const char* who, float gamma, float label_smoothing);
 size_t dg_label_counts_scratch(long P, int C);
 int dg_label_counts(const float* onehot, const unsigned char* codes, long P, int C, const float* cw, int ignore_code,
                     unsigned long long* counts, float* scratch, size_t scratch_floats, hipStream_t st);
-size_t dg_softmax_ce_weighted_scratch(long P, int C, bool census);
-int dg_softmax_ce_weighted(const float* logits, const float* onehot, const unsigned char* codes, float* probs, float* dz,
-                           float* loss_sum, unsigned* bad_count, unsigned long long* census,
-                           unsigned long long* counts, const float* cw, int ignore_code, long P, int C, float* scratch,
-                           size_t scratch_floats, hipStream_t st);
-// The focal mode (include/depgan.h, depgan_uresnet_set_focal, states the rule): dg_softmax_ce_weighted with the focal
-// cross-entropy and label smoothing in the same kernel text -- gamma finite and >= 0, label_smoothing in [0, 1)
-// (dg_focal_check validates both without a HIP call).  cw null: unit weights.  The pre-pass, den, the ignore code, the
-// census, the stored probabilities and the scratch (dg_softmax_ce_weighted_scratch) are the loss-weight mode's.  gamma =
-// 0 with label_smoothing = 0 is allowed here and runs the focal statements; a caller that wants the plain bits calls
-// dg_softmax_ce_weighted or dg_softmax_ce instead.
-int dg_focal_check(const char* who, float gamma, float label_smoothing);
-int dg_softmax_ce_focal(const float* logits, const float* onehot, const unsigned char* codes, float* probs, float* dz,
-                        float* loss_sum, unsigned* bad_count, unsigned long long* census, unsigned long long* counts,
-                        const float* cw, int ignore_code, float gamma, float label_smoothing, long P, int C,
-                        float* scratch, size_t scratch_floats, hipStream_t st);
-// its argument checks alone (no HIP call): what an entry asks before it allocates
-int dg_softmax_ce_check(const float* logits, const float* onehot, const unsigned char* codes, const float* probs,
-                        const float* dz, const float* loss_sum, long P, int C);
 
 // The soft Dice loss (dice_loss.hip; include/depgan.h, depgan_uresnet_set_dice_loss, states the rule).  It runs behind the
 // cross-entropy on the same stream, on the probabilities AS STORED: sums I_k = sum m t_k p_k, P_k = sum m p_k,
@@ -106,21 +130,31 @@ struct DgDiceDev {
   float loss, pad;                            // the Dice term, rounded once from the double result
   float A[DEPGAN_MAX_HEAD_CLASSES], B[DEPGAN_MAX_HEAD_CLASSES];
 };
-// dg_dice_check validates the setting without a HIP call: form DEPGAN_DICE_FLAT / _CLASS, ce_coef finite >= 0, dice_coef
-// and smooth finite > 0, coef null or (class form only) n == C finite values >= 0 with at least one > 0.
-// dg_dice_loss: coef null = 1 / C each.  ignore_code: -1 = every pixel takes part; with codes the pixels of that code
-// stay out (a code >= C always does), with onehot any value >= 0 keeps the all-zero rows out.  dz null: the sums, the
-// coefficients and the loss only (no gradient pass).  ce_coef == 0: dz is written without being read.  Two-stage sums,
-// no atomics, the partials added in index order in double; dg_dice_scratch(P, C) floats of scratch (at most 1024 * 3 C).
+// The Dice setting, on the host: form DEPGAN_DICE_OFF / _FLAT / _CLASS, ce_coef finite >= 0, dice_coef and smooth finite
+// > 0, c: the class form's C coefficients (finite, >= 0, at least one > 0).
+struct DgDiceSetting {
+  int form = DEPGAN_DICE_OFF;
+  float ce_coef = 1.f, dice_coef = 1.f, smooth = 0.f;
+  float c[DEPGAN_MAX_HEAD_CLASSES];
+  // coef null: 1 / C each
+  void set(int form_, float ce, float dice, float smooth_, const float* coef, int C) {
+    form = form_, ce_coef = ce, dice_coef = dice, smooth = smooth_;
+    for (int k = 0; k < C; ++k) c[k] = coef ? coef[k] : 1.0f / (float)C;
+  }
+};
+// dg_dice_check validates the values of a setting without a HIP call: coef null or (class form only) n == C values.
+// dg_dice_loss: ignore_code: -1 = every pixel takes part; with codes the pixels of that code stay out (a code >= C
+// always does), with onehot any value >= 0 keeps the all-zero rows out.  dz null: the sums, the coefficients and the
+// loss only (no gradient pass).  ce_coef == 0: dz is written without being read.  Two-stage sums, no atomics, the
+// partials added in index order in double; dg_dice_scratch(P, C) floats of scratch (at most 1024 * 3 C).
 int dg_dice_check(const char* who, int form, float ce_coef, float dice_coef, float smooth, const float* coef, int n,
                   int C);
 // the operands' checks alone (no HIP call): what an entry asks before it allocates
-int dg_dice_operands_check(const char* who, const float* probs, const float* onehot, const unsigned char* codes,
-                           int ignore_code, const float* dz, long P, int C);
+int dg_dice_operands_check(const char* who, const float* probs, DgLabels lab, int ignore_code, const float* dz, long P,
+                           int C);
 size_t dg_dice_scratch(long P, int C);
-int dg_dice_loss(const float* probs, const float* onehot, const unsigned char* codes, int ignore_code, int form,
-                 const float* coef, float smooth, float ce_coef, float dice_coef, float* dz, DgDiceDev* out, long P, int C,
-                 float* scratch, size_t scratch_floats, hipStream_t st);
+int dg_dice_loss(const float* probs, DgLabels lab, int ignore_code, const DgDiceSetting& set, float* dz, DgDiceDev* out,
+                 long P, int C, float* scratch, size_t scratch_floats, hipStream_t st);
 
 // the 1x1 head to K = 2..8 class logits on dense (P, K) rows; a, mask and din are pixel rows of C channels at strides
 // ld* (multiples of 4 floats, 16-byte aligned), w is (C, K) dense, C / 4 a power of two <= 64

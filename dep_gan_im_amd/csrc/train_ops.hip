@@ -2,27 +2,9 @@
 // axis, block reductions through LDS, deterministic second passes.
 #include "train_ops.h"
 
-#include <float.h>
-
+#include "block_sum.h"
 #include "epilogue.h"
 #include "softmax_row.h"
-
-__device__ __forceinline__ float t_wave_sum(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-  return v;
-}
-__device__ __forceinline__ float t_block_sum(float v, float* sh4) {
-  v = t_wave_sum(v);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) sh4[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return (sh4[0] + sh4[1]) + (sh4[2] + sh4[3]);
-}
-static inline int t_nblk(size_t n, int cap) {
-  size_t b = (n + 255) / 256;
-  return (int)(b > (size_t)cap ? cap : (b < 1 ? 1 : b));
-}
 
 // MODE 0: (sum x, -)   MODE 1: (sum (x-m)^2, -)   MODE 2: (sum d, sum d*(x-m))   [v = d, w = x]
 // FLAT: both views are pixel-contiguous (sY == W*sX, sB == H*sY), so pixel q sits at q*sX: no divisions in the loop.
@@ -446,537 +428,6 @@ int dg_axpby_ch(TView d, TView x, TView out, int B, int H, int W, int C, const f
                        A, Bc, Cc);
   HIPCHECK(hipGetLastError());
   return DG_OK;
-}
-
-// ---------------------------------------------------------------------------
-// softmax + categorical cross-entropy (keras, probabilities path)
-// ---------------------------------------------------------------------------
-// One kernel for every class count C = 2..8 and every label source: LBL_ONEHOT reads a float32 one-hot row,
-// LBL_CODES forms t[k] = (k == code) in registers from one byte and then runs the same statements (so the two agree
-// value for value), LBL_NONE stops after the probabilities.  A code is only ever compared, never used as an index:
-// any byte is safe; a code >= C gives an all-zero t (no loss, no gradient from that pixel) and is counted.
-// Evaluation order (softmax_row.h): maximum and S over pairs folded left to right -- for C = 4 that is the pairwise
-// max and S = (p0 + p1) + (p2 + p3); S0, the loss, dot and pg run over k = 0..C-1 left to right.
-//
-// CENSUS (labels present): every pixel also adds 1 to bin [tc][pc] of a C x C table, tc = the code (LBL_CODES; a code
-// >= C joins no bin, it is in nbad) or the first arg-max of the label row (LBL_ONEHOT; an all-zero row is class 0),
-// pc = the first arg-max of p as stored.  Integers only: no float statement reads anything the census writes, and the
-// CENSUS = false instantiations compile to the instructions they were.  In a block the table is kept per wave, with no
-// atomics and no LDS traffic in the loop: one ballot per true class and one per predicted class (2 C compares), then
-// lane l, the owner of bin l = k * C + j, adds popcount(ballot_t[k] & ballot_p[j]) to its one counter.  The four
-// waves' tables meet in LDS after the loop and C*C lanes store the block's partial.
-//
-// WEIGHTED (labels present; dg_softmax_ce_weighted): the label row becomes cw[k] * t[k] before the statements above run
-// on it, a code equal to wa.ignore gives t = 0 without being counted in nbad, and 1/N becomes 1/den, den = the count of
-// pixels with a non-zero weight that label_count_kernel left in wa.den (invDen = 0 for den = 0: no division by zero, an
-// all-zero dz).  With unit weights, no ignored pixel and den = P every float is the one the WEIGHTED = false
-// instantiation computes (1 * t = t, and 1.0f / (float)den is the host's 1.0f / (float)P).  A pixel with t = 0 --
-// ignored, or of a zero-weight class -- has a dz row of zeros and still gets its probabilities.  CENSUS under WEIGHTED:
-// a pixel without a true class (the ignore code, an all-zero one-hot row) joins no bin.  The WEIGHTED = false
-// instantiations ignore wa and compile to the instructions they were.
-//
-// FOCAL (with WEIGHTED only; dg_softmax_ce_focal): the focal cross-entropy with label smoothing of include/depgan.h
-// (depgan_uresnet_set_focal).  The label row stays unweighted until the pixel weight w = sum_k cw[k] t[k] (left to right,
-// the pre-pass's statement) and has = any t[k] != 0 are formed from it; then ts[k] = w ((1 - eps) t[k] + (has ? eps / C
-// : 0)) takes the row's place, the loss term is -ts[k] (1 - r)^gamma log r and dL/dq_k = -ts[k] (1/den) ((1 - r)^gamma / q
-// - gamma (1 - r)^(gamma - 1) log r) on the closed clip interval.  1 - r is formed directly (>= 2^-23 inside the clip);
-// the power is 1, 1 - r or (1 - r)^2 for gamma = 0, 1, 2 (a uniform branch: gamma is a kernel argument) and
-// exp2f(gamma log2f(1 - r)) otherwise, (1 - r)^(gamma - 1) the power over 1 - r.  Everything behind dL/dq, the census and
-// the stored probabilities are the text above.  The FOCAL = false instantiations read neither gamma nor eps, the last
-// two arguments, and compile to the instructions they were.
-enum { LBL_NONE = 0, LBL_ONEHOT = 1, LBL_CODES = 2 };
-
-// the loss-weight mode's kernel arguments, by value: C class weights (the rest 0), the ignore code (-1: none) and the
-// device count of weighted pixels
-struct SmWeights {
-  float cw[DG_MAX_CLASSES];
-  int ignore;
-  const unsigned long long* den;
-};
-
-__device__ __forceinline__ unsigned t_block_sum_u(unsigned v, unsigned* shu4) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) shu4[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return (shu4[0] + shu4[1]) + (shu4[2] + shu4[3]);
-}
-
-// pw = x^gamma and pm1 = x^(gamma - 1) for x = 1 - r in [2^-23, 1) and gamma >= 0
-__device__ __forceinline__ void t_focal_pow(float x, float gamma, float& pw, float& pm1) {
-  if (gamma == 0.f) {
-    pw = 1.0f;
-    pm1 = 1.0f / x;     // multiplied by gamma = 0 where it is used
-  } else if (gamma == 1.0f) {
-    pw = x;
-    pm1 = 1.0f;
-  } else if (gamma == 2.0f) {
-    pw = x * x;
-    pm1 = x;
-  } else {
-    pw = exp2f(gamma * log2f(x));
-    pm1 = pw / x;
-  }
-}
-
-template <int C, int LBL, bool CENSUS, bool WEIGHTED, bool FOCAL>
-__global__ void softmax_ce_kernel(const float* __restrict__ logits, const float* __restrict__ onehot,
-                                  const unsigned char* __restrict__ codes, float* __restrict__ probs,
-                                  float* __restrict__ dz, float* __restrict__ part, unsigned* __restrict__ bad_part,
-                                  unsigned* __restrict__ cen_part, long P, float invN, SmWeights wa, float gamma,
-                                  float eps) {
-  static_assert(!CENSUS || LBL != LBL_NONE, "a census needs labels");
-  static_assert(!WEIGHTED || LBL != LBL_NONE, "loss weights need labels");
-  static_assert(!FOCAL || WEIGHTED, "the focal mode runs the weighted path");
-  if (WEIGHTED) {
-    const unsigned long long den = *wa.den;
-    invN = den ? 1.0f / (float)den : 0.f;
-  }
-  __shared__ float sh4[4];
-  __shared__ unsigned shu4[4];
-  float lsum = 0.f;
-  unsigned nbad = 0;
-  // CENSUS: lane l of a wave owns bin l (true class l / C, predicted class l % C) of the wave's table
-  const int bin_t = CENSUS ? (int)(threadIdx.x & 63) / C : 0, bin_p = CENSUS ? (int)(threadIdx.x & 63) % C : 0;
-  unsigned cen = 0;
-  // CENSUS keeps the whole wave in the loop until its last lane is done (a ballot must meet every bin's owner)
-  for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; CENSUS ? (__any(i < (size_t)P) != 0) : (i < (size_t)P);
-       i += (size_t)gridDim.x * blockDim.x) {
-    int tc = -1, pc = -1;
-    if (!CENSUS || i < (size_t)P) {
-      float z[C], p[C];
-      dg_row_load<C>(logits + i * C, z);
-      dg_softmax_row<C>(z, p);
-      dg_row_store<C>(probs + i * C, p);
-      if (LBL != LBL_NONE) {
-        float t[C];
-        if (LBL == LBL_ONEHOT) {
-          dg_row_load<C>(onehot + i * C, t);
-          if (CENSUS) tc = dg_row_argmax<C>(t);
-          if (CENSUS && WEIGHTED) tc = dg_row_any<C>(t) ? tc : -1;
-        } else {
-          // WEIGHTED: the ignore code becomes -1, which equals no k: t = 0, in no bin and not in nbad
-          const int code = (WEIGHTED && codes[i] == wa.ignore) ? -1 : codes[i];
-#pragma unroll
-          for (int k = 0; k < C; ++k) t[k] = (k == code) ? 1.0f : 0.0f;
-          nbad += (code >= C) ? 1u : 0u;
-          if (CENSUS) tc = (code < C) ? code : -1;
-        }
-        if (WEIGHTED && !FOCAL) {
-#pragma unroll
-          for (int k = 0; k < C; ++k) t[k] = wa.cw[k] * t[k];
-        }
-        if (FOCAL) {
-          // ts = w ((1 - eps) t + (has ? eps / C : 0)): a row without a true class stays 0, a zero-weight class too
-          float w = 0.f;
-#pragma unroll
-          for (int k = 0; k < C; ++k) w += wa.cw[k] * t[k];
-          const float u = dg_row_any<C>(t) ? eps / (float)C : 0.f;
-#pragma unroll
-          for (int k = 0; k < C; ++k) t[k] = w * ((1.0f - eps) * t[k] + u);
-        }
-        const float S = dg_row_pairsum<C>(p);
-        float gq[C];
-        float dot = 0.f;
-#pragma unroll
-        for (int k = 0; k < C; ++k) {
-          const float q = p[k] / S;
-          const float r = fminf(fmaxf(q, 1e-7f), 1.0f - 1e-7f);
-          // clip's gradient passes on the closed interval, bounds included (TF clip_by_value, torch.clamp)
-          const bool in = (q >= 1e-7f) && (q <= 1.0f - 1e-7f);
-          if (FOCAL) {
-            const float lg = logf(r);
-            float pw, pm1;
-            t_focal_pow(1.0f - r, gamma, pw, pm1);
-            lsum -= t[k] * pw * lg;
-            gq[k] = in ? (-t[k] * invN * (pw / q - gamma * pm1 * lg)) : 0.f;
-          } else {
-            lsum -= t[k] * logf(r);
-            gq[k] = in ? (-t[k] * invN / q) : 0.f;    // dL/dq
-          }
-          dot += gq[k] * p[k];
-        }
-        // q = p/S: dL/dp_j = gq_j/S - dot/S^2 ; softmax: dL/dz_k = p_k (dL/dp_k - sum_j p_j dL/dp_j)
-        float gp[C];
-        float pg = 0.f;
-#pragma unroll
-        for (int k = 0; k < C; ++k) {
-          gp[k] = gq[k] / S - dot / (S * S);
-          pg += p[k] * gp[k];
-        }
-        float o[C];
-#pragma unroll
-        for (int k = 0; k < C; ++k) o[k] = p[k] * (gp[k] - pg);
-        dg_row_store<C>(dz + i * C, o);
-        if (CENSUS) pc = dg_row_argmax<C>(p);
-      }
-    }
-    if (CENSUS) {
-      // the ballots of the lane's own row and column, selected out of the C + C; a lane without a pixel, or with a code
-      // >= C, has tc = -1 and is in no ballot; lanes C*C.. own no bin (bin_t >= C)
-      unsigned long long mt = 0, mp = 0;
-#pragma unroll
-      for (int k = 0; k < C; ++k) {
-        const unsigned long long bt = __ballot(tc == k), bp = __ballot(pc == k);
-        mt = (bin_t == k) ? bt : mt;
-        mp = (bin_p == k) ? bp : mp;
-      }
-      cen += (unsigned)__popcll(mt & mp);
-    }
-  }
-  if (LBL != LBL_NONE) {
-    lsum = t_block_sum(lsum, sh4);
-    if (threadIdx.x == 0) part[blockIdx.x] = lsum;
-  }
-  if (LBL == LBL_CODES) {
-    nbad = t_block_sum_u(nbad, shu4);
-    if (threadIdx.x == 0) bad_part[blockIdx.x] = nbad;
-  }
-  if (CENSUS) {
-    __shared__ unsigned shc[4][64];
-    shc[threadIdx.x >> 6][threadIdx.x & 63] = cen;
-    __syncthreads();
-    const int b = threadIdx.x;
-    if (b < C * C) cen_part[(size_t)blockIdx.x * (C * C) + b] = (shc[0][b] + shc[1][b]) + (shc[2][b] + shc[3][b]);
-  }
-}
-// second stage, one block: the block partials in index order; bad_out[0] = the out-of-range codes (0 without bad_part).
-// CENSUS: cen_out[b] = the sum over the nb blocks of bin b of their CC-entry tables, as 64-bit counts (wave g takes the
-// blocks g, g + 4, ..., lane b the bin; integer sums, any order gives the same table)
-template <bool CENSUS>
-__global__ void sum_small_kernel(const float* __restrict__ part, int nb, float* __restrict__ out,
-                                 const unsigned* __restrict__ bad_part, unsigned* __restrict__ bad_out,
-                                 const unsigned* __restrict__ cen_part, unsigned long long* __restrict__ cen_out,
-                                 int CC) {
-  __shared__ float sh4[4];
-  __shared__ unsigned shu4[4];
-  float acc = 0.f;
-  for (int i = threadIdx.x; i < nb; i += blockDim.x) acc += part[i];
-  acc = t_block_sum(acc, sh4);
-  if (threadIdx.x == 0) out[0] = acc;
-  if (bad_out) {
-    unsigned nbad = 0;
-    if (bad_part)
-      for (int i = threadIdx.x; i < nb; i += blockDim.x) nbad += bad_part[i];
-    nbad = t_block_sum_u(nbad, shu4);
-    if (threadIdx.x == 0) bad_out[0] = nbad;
-  }
-  if (CENSUS) {
-    __shared__ unsigned long long shc[4][DG_MAX_CLASSES * DG_MAX_CLASSES];
-    const int g = threadIdx.x >> 6, b = threadIdx.x & 63;
-    unsigned long long a = 0;
-    if (b < CC)
-      for (int i = g; i < nb; i += 4) a += cen_part[(size_t)i * CC + b];
-    shc[g][b] = a;
-    __syncthreads();
-    if (g == 0 && b < CC) cen_out[b] = (shc[0][b] + shc[1][b]) + (shc[2][b] + shc[3][b]);
-  }
-}
-
-// what the focal mode adds to the weighted launch, by value
-struct SmFocal {
-  float gamma, eps;
-};
-
-template <int C>
-static void softmax_ce_launch(int lbl, bool census, int nb, hipStream_t st, const float* logits, const float* onehot,
-                              const unsigned char* codes, float* probs, float* dz, float* part, unsigned* bad_part,
-                              unsigned* cen_part, long P, float invN, const SmWeights* weights, const SmFocal* focal) {
-  const SmWeights wa = weights ? *weights : SmWeights{};
-  const SmFocal fa = focal ? *focal : SmFocal{0.f, 0.f};
-#define DG_SM_GO(LBL, CEN, WGT, FOC)                                                                                   \
-  hipLaunchKernelGGL((softmax_ce_kernel<C, LBL, CEN, WGT, FOC>), dim3(nb), dim3(256), 0, st, logits, onehot, codes, probs, \
-                     dz, part, bad_part, cen_part, P, invN, wa, fa.gamma, fa.eps)
-  if (focal && lbl == LBL_ONEHOT && census) DG_SM_GO(LBL_ONEHOT, true, true, true);
-  else if (focal && lbl == LBL_CODES && census) DG_SM_GO(LBL_CODES, true, true, true);
-  else if (focal && lbl == LBL_ONEHOT) DG_SM_GO(LBL_ONEHOT, false, true, true);
-  else if (focal && lbl == LBL_CODES) DG_SM_GO(LBL_CODES, false, true, true);
-  else if (weights && lbl == LBL_ONEHOT && census) DG_SM_GO(LBL_ONEHOT, true, true, false);
-  else if (weights && lbl == LBL_CODES && census) DG_SM_GO(LBL_CODES, true, true, false);
-  else if (weights && lbl == LBL_ONEHOT) DG_SM_GO(LBL_ONEHOT, false, true, false);
-  else if (weights && lbl == LBL_CODES) DG_SM_GO(LBL_CODES, false, true, false);
-  else if (lbl == LBL_ONEHOT && census) DG_SM_GO(LBL_ONEHOT, true, false, false);
-  else if (lbl == LBL_CODES && census) DG_SM_GO(LBL_CODES, true, false, false);
-  else if (lbl == LBL_ONEHOT) DG_SM_GO(LBL_ONEHOT, false, false, false);
-  else if (lbl == LBL_CODES) DG_SM_GO(LBL_CODES, false, false, false);
-  else DG_SM_GO(LBL_NONE, false, false, false);
-#undef DG_SM_GO
-}
-
-int dg_softmax_ce_check(const float* logits, const float* onehot, const unsigned char* codes, const float* probs,
-                        const float* dz, const float* loss_sum, long P, int C) {
-  if (!logits || !probs || P < 1) { dg_set_error("dg_softmax_ce: null logits or probs, or P < 1"); return DG_ERR_ARG; }
-  if (C < DG_MIN_CLASSES || C > DG_MAX_CLASSES) {
-    dg_set_error("dg_softmax_ce: %d classes (the kernel covers %d to %d)", C, DG_MIN_CLASSES, DG_MAX_CLASSES);
-    return DG_ERR_ARG;
-  }
-  if (onehot && codes) { dg_set_error("dg_softmax_ce: one-hot labels and class codes are both given"); return DG_ERR_ARG; }
-  if ((onehot || codes) && (!dz || !loss_sum)) { dg_set_error("dg_softmax_ce: labels without dz or loss_sum"); return DG_ERR_ARG; }
-  // rows are read and written 16 bytes at a time where C is a multiple of 4, else float by float
-  const uintptr_t al = (C % 4 == 0) ? 15 : 3;
-  if ((((uintptr_t)logits | (uintptr_t)probs | (uintptr_t)onehot | (uintptr_t)dz) & al) || ((uintptr_t)loss_sum & 3)) {
-    dg_set_error("dg_softmax_ce: logits, probs, onehot and dz must be %d-byte aligned for %d classes", (int)al + 1, C);
-    return DG_ERR_ARG;
-  }
-  return DG_OK;
-}
-
-// census: null, or C*C device counts; the block tables then follow the 2048 floats of the other partials.  weights:
-// null, or the loss-weight mode's arguments (weights->den already holds the count when this launch runs).  focal: null,
-// or the focal mode's two floats (with weights only)
-static int softmax_ce_run(const float* logits, const float* onehot, const unsigned char* codes, float* probs, float* dz,
-                          float* loss_sum, unsigned* bad_count, unsigned long long* census, long P, int C, float* scratch,
-                          hipStream_t st, const SmWeights* weights = nullptr, const SmFocal* focal = nullptr) {
-  const int lbl = onehot ? LBL_ONEHOT : (codes ? LBL_CODES : LBL_NONE);
-  if (lbl != LBL_NONE && !scratch) { dg_set_error("dg_softmax_ce: labels without scratch"); return DG_ERR_ARG; }
-  if (lbl == LBL_CODES && !bad_count) { dg_set_error("dg_softmax_ce: class codes without a counter"); return DG_ERR_ARG; }
-  const int nb = t_nblk((size_t)P, 1024);
-  float* part = scratch;
-  unsigned* bad_part = scratch ? reinterpret_cast<unsigned*>(scratch + 1024) : nullptr;
-  unsigned* cen_part = census ? reinterpret_cast<unsigned*>(scratch + 2048) : nullptr;
-  const float invN = (lbl == LBL_NONE) ? 0.f : 1.0f / (float)P;
-  switch (C) {
-#define DG_SM(N) case N: softmax_ce_launch<N>(lbl, census != nullptr, nb, st, logits, onehot, codes, probs, dz, part, bad_part, cen_part, P, invN, weights, focal); break;
-    DG_SM(2) DG_SM(3) DG_SM(4) DG_SM(5) DG_SM(6) DG_SM(7) DG_SM(8)
-#undef DG_SM
-  }
-  HIPCHECK(hipGetLastError());
-  if (lbl == LBL_NONE) return DG_OK;
-  if (census)
-    hipLaunchKernelGGL(sum_small_kernel<true>, dim3(1), dim3(256), 0, st, part, nb, loss_sum,
-                       lbl == LBL_CODES ? bad_part : nullptr, bad_count, cen_part, census, C * C);
-  else
-    hipLaunchKernelGGL(sum_small_kernel<false>, dim3(1), dim3(256), 0, st, part, nb, loss_sum,
-                       lbl == LBL_CODES ? bad_part : nullptr, bad_count, nullptr, nullptr, 0);
-  HIPCHECK(hipGetLastError());
-  return DG_OK;
-}
-
-int dg_softmax_ce(const float* logits, const float* onehot, const unsigned char* codes, float* probs, float* dz,
-                  float* loss_sum, unsigned* bad_count, long P, int C, float* scratch, hipStream_t st) {
-  DGCHECK(dg_softmax_ce_check(logits, onehot, codes, probs, dz, loss_sum, P, C));
-  return softmax_ce_run(logits, onehot, codes, probs, dz, loss_sum, bad_count, nullptr, P, C, scratch, st);
-}
-
-size_t dg_softmax_ce_census_scratch(long P, int C) { return 2048 + (size_t)t_nblk((size_t)P, 1024) * C * C; }
-
-int dg_softmax_ce_census(const float* logits, const float* onehot, const unsigned char* codes, float* probs, float* dz,
-                         float* loss_sum, unsigned* bad_count, unsigned long long* census, long P, int C, float* scratch,
-                         size_t scratch_floats, hipStream_t st) {
-  DGCHECK(dg_softmax_ce_check(logits, onehot, codes, probs, dz, loss_sum, P, C));
-  if (!onehot && !codes) { dg_set_error("dg_softmax_ce_census: a census needs labels"); return DG_ERR_ARG; }
-  if (!census || ((uintptr_t)census & 7)) { dg_set_error("dg_softmax_ce_census: null or misaligned census"); return DG_ERR_ARG; }
-  if (!bad_count) { dg_set_error("dg_softmax_ce_census: no counter of out-of-range codes"); return DG_ERR_ARG; }
-  const size_t need = dg_softmax_ce_census_scratch(P, C);
-  if (!scratch || scratch_floats < need) {
-    dg_set_error("dg_softmax_ce_census: scratch of %zu floats, the launch needs %zu", scratch ? scratch_floats : (size_t)0, need);
-    return DG_ERR_ARG;
-  }
-  return softmax_ce_run(logits, onehot, codes, probs, dz, loss_sum, bad_count, census, P, C, scratch, st);
-}
-
-// ---------------------------------------------------------------------------
-// the loss-weight mode: label pre-pass and weighted cross-entropy
-// ---------------------------------------------------------------------------
-// The gradient needs 1 / den inside the pass that writes dz, so den exists before that pass starts: this kernel reads
-// the labels alone (1 byte per pixel, or a one-hot row) and counts, per pixel, C + 3 predicates -- slot 0: the pixel's
-// weight w = sum_k cw[k] t[k] (left to right) is not 0 (den); slot 1: no true class (the ignore code, an all-zero
-// one-hot row); slot 2: a code >= C that is not the ignore code; slot 3 + k: true class k (the code, or the first
-// arg-max of the row: the census rule).  The census's conventions: no atomics, one ballot per slot, lane j of a wave
-// adds the popcount of slot j's ballot to its one counter, the four waves meet in LDS, C + 3 lanes store the block's
-// partial, and a one-block second stage sums the at most 1024 partials into 64-bit counts.
-template <int C, int LBL>
-__global__ void label_count_kernel(const float* __restrict__ onehot, const unsigned char* __restrict__ codes,
-                                   SmWeights wa, unsigned* __restrict__ cnt_part, long P) {
-  static_assert(LBL == LBL_ONEHOT || LBL == LBL_CODES, "a label count needs labels");
-  constexpr int NS = C + 3;
-  const int lane = (int)(threadIdx.x & 63);
-  unsigned cnt = 0;
-  for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; __any(i < (size_t)P) != 0;
-       i += (size_t)gridDim.x * blockDim.x) {
-    int tc = -1;
-    bool has_w = false, ign = false, bad = false;
-    if (i < (size_t)P) {
-      float w = 0.f;
-      if (LBL == LBL_ONEHOT) {
-        float t[C];
-        dg_row_load<C>(onehot + i * C, t);
-        ign = !dg_row_any<C>(t);
-        tc = ign ? -1 : dg_row_argmax<C>(t);
-#pragma unroll
-        for (int k = 0; k < C; ++k) w += wa.cw[k] * t[k];
-      } else {
-        const int raw = codes[i];
-        ign = raw == wa.ignore;
-        bad = !ign && raw >= C;
-        tc = (ign || bad) ? -1 : raw;
-#pragma unroll
-        for (int k = 0; k < C; ++k) w = (k == tc) ? wa.cw[k] : w;
-      }
-      has_w = w != 0.f;
-    }
-    unsigned long long m = 0;
-    const unsigned long long b0 = __ballot(has_w), b1 = __ballot(ign), b2 = __ballot(bad);
-    m = (lane == 0) ? b0 : m;
-    m = (lane == 1) ? b1 : m;
-    m = (lane == 2) ? b2 : m;
-#pragma unroll
-    for (int k = 0; k < C; ++k) {
-      const unsigned long long bk = __ballot(tc == k);
-      m = (lane == 3 + k) ? bk : m;
-    }
-    cnt += (unsigned)__popcll(m);
-  }
-  __shared__ unsigned shc[4][16];
-  if (lane < NS) shc[threadIdx.x >> 6][lane] = cnt;
-  __syncthreads();
-  const int b = threadIdx.x;
-  if (b < NS) cnt_part[(size_t)blockIdx.x * NS + b] = (shc[0][b] + shc[1][b]) + (shc[2][b] + shc[3][b]);
-}
-// second stage, one block of 256: out[j] = the sum over the nb blocks of slot j (wave g takes the blocks g, g + 4, ...,
-// lane j the slot; integer sums, any order gives the same counts)
-__global__ void label_count_sum_kernel(const unsigned* __restrict__ cnt_part, int nb, int NS,
-                                       unsigned long long* __restrict__ out) {
-  __shared__ unsigned long long shc[4][16];
-  const int g = threadIdx.x >> 6, b = threadIdx.x & 63;
-  unsigned long long a = 0;
-  if (b < NS)
-    for (int i = g; i < nb; i += 4) a += cnt_part[(size_t)i * NS + b];
-  if (b < NS) shc[g][b] = a;
-  __syncthreads();
-  if (g == 0 && b < NS) out[b] = (shc[0][b] + shc[1][b]) + (shc[2][b] + shc[3][b]);
-}
-
-int dg_loss_weights_check(const char* who, const float* w, int n, int C, int ignore_code) {
-  if (C < DG_MIN_CLASSES || C > DG_MAX_CLASSES) {
-    dg_set_error("%s: %d classes (the kernel covers %d to %d)", who, C, DG_MIN_CLASSES, DG_MAX_CLASSES);
-    return DG_ERR_ARG;
-  }
-  if (ignore_code < -1 || ignore_code > 255) {
-    dg_set_error("%s: ignore code %d (-1 for none, else a byte value 0..255)", who, ignore_code);
-    return DG_ERR_ARG;
-  }
-  if (!w) return DG_OK;
-  if (n != C) { dg_set_error("%s: %d class weights for %d classes", who, n, C); return DG_ERR_ARG; }
-  bool any = false;
-  for (int k = 0; k < C; ++k) {
-    if (!(w[k] >= 0.f) || w[k] > FLT_MAX) {
-      dg_set_error("%s: class weight %d is %g (every weight is finite and >= 0)", who, k, (double)w[k]);
-      return DG_ERR_ARG;
-    }
-    any = any || w[k] > 0.f;
-  }
-  if (!any) { dg_set_error("%s: every class weight is 0 (at least one must be > 0)", who); return DG_ERR_ARG; }
-  return DG_OK;
-}
-
-static SmWeights sm_weights(const float* cw, int C, int ignore_code, const unsigned long long* den) {
-  SmWeights wa;
-  for (int k = 0; k < DG_MAX_CLASSES; ++k) wa.cw[k] = (k < C) ? (cw ? cw[k] : 1.0f) : 0.f;
-  wa.ignore = ignore_code;
-  wa.den = den;
-  return wa;
-}
-
-size_t dg_label_counts_scratch(long P, int C) { return (size_t)t_nblk((size_t)P, 1024) * (C + 3); }
-
-static int label_counts_run(const float* onehot, const unsigned char* codes, long P, int C, const SmWeights& wa,
-                            unsigned long long* counts, float* scratch, hipStream_t st) {
-  const int nb = t_nblk((size_t)P, 1024);
-  unsigned* cnt_part = reinterpret_cast<unsigned*>(scratch);
-  switch (C) {
-#define DG_LC(N)                                                                                                       \
-  case N:                                                                                                              \
-    if (onehot) hipLaunchKernelGGL((label_count_kernel<N, LBL_ONEHOT>), dim3(nb), dim3(256), 0, st, onehot, codes, wa, cnt_part, P); \
-    else hipLaunchKernelGGL((label_count_kernel<N, LBL_CODES>), dim3(nb), dim3(256), 0, st, onehot, codes, wa, cnt_part, P); \
-    break;
-    DG_LC(2) DG_LC(3) DG_LC(4) DG_LC(5) DG_LC(6) DG_LC(7) DG_LC(8)
-#undef DG_LC
-  }
-  HIPCHECK(hipGetLastError());
-  hipLaunchKernelGGL(label_count_sum_kernel, dim3(1), dim3(256), 0, st, cnt_part, nb, C + 3, counts);
-  HIPCHECK(hipGetLastError());
-  return DG_OK;
-}
-
-static int label_counts_check(const char* who, const float* onehot, const unsigned char* codes, long P, int C,
-                              const unsigned long long* counts, const float* scratch, size_t scratch_floats) {
-  if (P < 1 || (!onehot == !codes)) { dg_set_error("%s: P < 1, or not exactly one of onehot and codes", who); return DG_ERR_ARG; }
-  if (onehot && ((uintptr_t)onehot & ((C % 4 == 0) ? 15 : 3))) { dg_set_error("%s: misaligned onehot", who); return DG_ERR_ARG; }
-  if (!counts || ((uintptr_t)counts & 7)) { dg_set_error("%s: null or misaligned counts", who); return DG_ERR_ARG; }
-  const size_t need = dg_label_counts_scratch(P, C);
-  if (!scratch || scratch_floats < need) {
-    dg_set_error("%s: scratch of %zu floats, the label pass needs %zu", who, scratch ? scratch_floats : (size_t)0, need);
-    return DG_ERR_ARG;
-  }
-  return DG_OK;
-}
-
-int dg_label_counts(const float* onehot, const unsigned char* codes, long P, int C, const float* cw, int ignore_code,
-                    unsigned long long* counts, float* scratch, size_t scratch_floats, hipStream_t st) {
-  DGCHECK(dg_loss_weights_check("dg_label_counts", cw, C, C, ignore_code));
-  DGCHECK(label_counts_check("dg_label_counts", onehot, codes, P, C, counts, scratch, scratch_floats));
-  return label_counts_run(onehot, codes, P, C, sm_weights(cw, C, ignore_code, nullptr), counts, scratch, st);
-}
-
-size_t dg_softmax_ce_weighted_scratch(long P, int C, bool census) {
-  const size_t a = census ? dg_softmax_ce_census_scratch(P, C) : 2048, b = dg_label_counts_scratch(P, C);
-  return a > b ? a : b;
-}
-
-// the weighted and the focal entry: one set of checks, one pre-pass, one launch (focal null: the loss-weight mode alone)
-static int softmax_ce_weighted_run(const char* who, const float* logits, const float* onehot, const unsigned char* codes,
-                                   float* probs, float* dz, float* loss_sum, unsigned* bad_count,
-                                   unsigned long long* census, unsigned long long* counts, const float* cw,
-                                   int ignore_code, const SmFocal* focal, long P, int C, float* scratch,
-                                   size_t scratch_floats, hipStream_t st) {
-  DGCHECK(dg_loss_weights_check(who, cw, C, C, ignore_code));
-  DGCHECK(dg_softmax_ce_check(logits, onehot, codes, probs, dz, loss_sum, P, C));
-  if (!onehot && !codes) { dg_set_error("%s: loss weights need labels", who); return DG_ERR_ARG; }
-  if (census && ((uintptr_t)census & 7)) { dg_set_error("%s: misaligned census", who); return DG_ERR_ARG; }
-  if (!bad_count) { dg_set_error("%s: no counter of out-of-range codes", who); return DG_ERR_ARG; }
-  const size_t need = dg_softmax_ce_weighted_scratch(P, C, census != nullptr);
-  if (!scratch || scratch_floats < need) {
-    dg_set_error("%s: scratch of %zu floats, the launches need %zu", who, scratch ? scratch_floats : (size_t)0, need);
-    return DG_ERR_ARG;
-  }
-  DGCHECK(label_counts_check(who, onehot, codes, P, C, counts, scratch, scratch_floats));
-  const SmWeights wa = sm_weights(cw, C, ignore_code, counts);
-  // the label pass's partials and the cross-entropy pass's share the scratch: the second stage of the first has read them
-  // before the second pass, behind it on the stream, writes
-  DGCHECK(label_counts_run(onehot, codes, P, C, wa, counts, scratch, st));
-  return softmax_ce_run(logits, onehot, codes, probs, dz, loss_sum, bad_count, census, P, C, scratch, st, &wa, focal);
-}
-
-int dg_softmax_ce_weighted(const float* logits, const float* onehot, const unsigned char* codes, float* probs, float* dz,
-                           float* loss_sum, unsigned* bad_count, unsigned long long* census,
-                           unsigned long long* counts, const float* cw, int ignore_code, long P, int C, float* scratch,
-                           size_t scratch_floats, hipStream_t st) {
-  return softmax_ce_weighted_run("dg_softmax_ce_weighted", logits, onehot, codes, probs, dz, loss_sum, bad_count, census,
-                                 counts, cw, ignore_code, nullptr, P, C, scratch, scratch_floats, st);
-}
-
-int dg_focal_check(const char* who, float gamma, float label_smoothing) {
-  if (!(gamma >= 0.f) || gamma > FLT_MAX) {
-    dg_set_error("%s: focal gamma %g (finite and >= 0)", who, (double)gamma);
-    return DG_ERR_ARG;
-  }
-  if (!(label_smoothing >= 0.f) || !(label_smoothing < 1.0f)) {
-    dg_set_error("%s: label smoothing %g (in [0, 1))", who, (double)label_smoothing);
-    return DG_ERR_ARG;
-  }
-  return DG_OK;
-}
-
-int dg_softmax_ce_focal(const float* logits, const float* onehot, const unsigned char* codes, float* probs, float* dz,
-                        float* loss_sum, unsigned* bad_count, unsigned long long* census, unsigned long long* counts,
-                        const float* cw, int ignore_code, float gamma, float label_smoothing, long P, int C,
-                        float* scratch, size_t scratch_floats, hipStream_t st) {
-  DGCHECK(dg_focal_check("dg_softmax_ce_focal", gamma, label_smoothing));
-  const SmFocal fa{gamma, label_smoothing};
-  return softmax_ce_weighted_run("dg_softmax_ce_focal", logits, onehot, codes, probs, dz, loss_sum, bad_count, census,
-                                 counts, cw, ignore_code, &fa, P, C, scratch, scratch_floats, st);
 }
 
 // ---------------------------------------------------------------------------

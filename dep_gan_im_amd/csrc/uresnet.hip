@@ -21,7 +21,6 @@
 #include <string>
 
 #include "model.h"
-#include "train_ops.h"
 
 static const float kBnEps = 1e-3f, kBnMomentum = 0.99f, kDropRate = 0.25f;
 static const char* kDropLayer = "gen_10";
@@ -43,15 +42,11 @@ static UNoiseBn noise_bn(Net& g, const std::string& nm) {
   return b;
 }
 
-// loss_dev as the host reads it
+// loss_dev, on the device and as the host reads it
 struct ULossHost {
-  float loss;
-  unsigned bad;
-  long long census[DEPGAN_MAX_HEAD_CLASSES * DEPGAN_MAX_HEAD_CLASSES];
-  long long counts[DEPGAN_LABEL_NCOUNT];
+  DgCeDev ce;
   DgDiceDev dice;   // the Dice mode: the 3 C sums and the Dice term (the copy stops in front of A and B)
 };
-static_assert(offsetof(ULossHost, census) == 2 * sizeof(float), "the census follows the two scalars of loss_dev");
 static_assert(offsetof(ULossHost, dice) % 8 == 0, "the Dice sums are doubles");
 
 int uresnet_build(depgan_ctx* c) {
@@ -79,9 +74,7 @@ int uresnet_build(depgan_ctx* c) {
   const size_t P = (size_t)B * c->cfg.height * c->cfg.width;
   DGCHECK(dmalloc(c, &c->logits, P * c->cfg.nc_out));
   DGCHECK(dmalloc(c, &c->dz, P * c->cfg.nc_out));
-  // [0] summed loss, [1] out-of-range codes (unsigned), then the census: nc_out^2 64-bit counts from float 2 on; behind
-  // the largest census the DEPGAN_LABEL_NCOUNT 64-bit label counts of the loss-weight mode, then what the Dice mode's
-  // coefficient stage leaves (ULossHost is the layout)
+  // what the loss launches leave for the host: DgCeDev, then what the Dice mode's coefficient stage leaves
   DGCHECK(dmalloc(c, &c->loss_dev, sizeof(ULossHost) / sizeof(float)));
   DGCHECK(dmalloc(c, &c->ones1k, 1024));
   DGCHECK(dmalloc(c, &c->zeros1k, 1024));
@@ -336,103 +329,80 @@ int uresnet_predict(depgan_ctx* c, const float* x, const float* z, float* out, i
   DGCHECK(u_forward_infer(c, x, z, n));
   const long P = (long)n * c->cfg.height * c->cfg.width;
   ProfScope ps(c, 2, 0.0, "softmax");
-  return dg_softmax_ce(c->logits, nullptr, nullptr, out, nullptr, nullptr, nullptr, P, c->cfg.nc_out, nullptr, c->st);
+  SoftmaxCeArgs a{};
+  a.logits = c->logits;
+  a.probs = out;
+  a.P = P;
+  a.C = c->cfg.nc_out;
+  return dg_softmax_ce(a, c->st);
 }
 
-// the labels of one call: a float32 one-hot tensor (n, H, W, nc_out) or one class code per pixel (n, H, W)
-struct ULabels {
-  const float* onehot;
-  const unsigned char* codes;
-};
-
-// loss_dev[0] = summed loss, loss_dev[1] = the count of class codes outside [0, nc_out) as an unsigned; with the census
-// on (depgan_uresnet_set_census) the nc_out x nc_out table of the same pass follows as 64-bit counts.  In the
-// loss-weight mode and in the focal mode the label pre-pass runs first and leaves its counts, den first, behind the census
-static int u_softmax_ce_only(depgan_ctx* c, ULabels lab, long P) {
+// The cross-entropy of one call under the context's setting; what it leaves for the host goes to loss_dev (ULossHost)
+static int u_softmax_ce_only(depgan_ctx* c, DgLabels lab, long P) {
   ProfScope ps(c, 2, 0.0, "softmax + cross-entropy");
-  unsigned* bad = reinterpret_cast<unsigned*>(c->loss_dev + 1);
-  // the focal mode runs the weighted path: the loss-weight mode's weights and ignore code, or unit weights and none
-  if (c->focal_on)
-    return dg_softmax_ce_focal(c->logits, lab.onehot, lab.codes, c->attr.p, c->dz, c->loss_dev, bad,
-                               c->census ? reinterpret_cast<unsigned long long*>(c->loss_dev + 2) : nullptr,
-                               reinterpret_cast<unsigned long long*>(c->loss_dev + offsetof(ULossHost, counts) / sizeof(float)),
-                               c->lw_on ? c->lw_w : nullptr, (c->lw_on && lab.codes) ? c->lw_ignore : -1, c->focal_gamma,
-                               c->focal_eps, P, c->cfg.nc_out, c->scratch, c->scratchFloats, c->st);
-  if (c->lw_on)
-    return dg_softmax_ce_weighted(c->logits, lab.onehot, lab.codes, c->attr.p, c->dz, c->loss_dev, bad,
-                                  c->census ? reinterpret_cast<unsigned long long*>(c->loss_dev + 2) : nullptr,
-                                  reinterpret_cast<unsigned long long*>(c->loss_dev + offsetof(ULossHost, counts) / sizeof(float)),
-                                  c->lw_w, lab.codes ? c->lw_ignore : -1, P, c->cfg.nc_out, c->scratch, c->scratchFloats,
-                                  c->st);
-  if (c->census)
-    return dg_softmax_ce_census(c->logits, lab.onehot, lab.codes, c->attr.p, c->dz, c->loss_dev, bad,
-                                reinterpret_cast<unsigned long long*>(c->loss_dev + 2), P, c->cfg.nc_out, c->scratch,
-                                c->scratchFloats, c->st);
-  return dg_softmax_ce(c->logits, lab.onehot, lab.codes, c->attr.p, c->dz, c->loss_dev, bad, P, c->cfg.nc_out, c->scratch,
-                       c->st);
+  DgCeDev* dev = &reinterpret_cast<ULossHost*>(c->loss_dev)->ce;
+  const SoftmaxCeArgs a = {c->logits, lab, c->attr.p, c->dz, &dev->loss, &dev->bad, dev->census, dev->counts, c->loss.ce,
+                           P, c->cfg.nc_out, c->scratch, c->scratchFloats};
+  return dg_softmax_ce(a, c->st);
 }
 
 // The Dice mode: its three launches follow the cross-entropy on the stream and reuse the scratch (the cross-entropy's
 // second stage has read its partials by then).  A pixel takes part unless the loss-weight mode says it has no true class:
 // the ignore code with codes, the all-zero row with one-hot labels.  grad = false (eval): no gradient pass
-static int u_softmax_ce(depgan_ctx* c, ULabels lab, long P, bool grad) {
+static int u_softmax_ce(depgan_ctx* c, DgLabels lab, long P, bool grad) {
   DGCHECK(u_softmax_ce_only(c, lab, P));
-  if (c->dice_form == DEPGAN_DICE_OFF) return DG_OK;
+  if (c->loss.dice.form == DEPGAN_DICE_OFF) return DG_OK;
   ProfScope ps(c, 2, 0.0, "dice loss");
-  const int ignore = !c->lw_on ? -1 : (lab.codes ? c->lw_ignore : 0);
-  return dg_dice_loss(c->attr.p, lab.onehot, lab.codes, ignore, c->dice_form,
-                      c->dice_form == DEPGAN_DICE_CLASS ? c->dice_c : nullptr, c->dice_smooth, c->dice_ce_coef,
-                      c->dice_coef, grad ? c->dz : nullptr,
-                      reinterpret_cast<DgDiceDev*>(c->loss_dev + offsetof(ULossHost, dice) / sizeof(float)), P,
-                      c->cfg.nc_out, c->scratch, c->scratchFloats, c->st);
+  const DgCeSetting& ce = c->loss.ce;
+  const int ignore = !ce.weighted ? -1 : (lab.codes ? ce.ignore : 0);
+  return dg_dice_loss(c->attr.p, lab, ignore, c->loss.dice, grad ? c->dz : nullptr,
+                      &reinterpret_cast<ULossHost*>(c->loss_dev)->dice, P, c->cfg.nc_out, c->scratch, c->scratchFloats,
+                      c->st);
 }
 
-// the one synchronisation of a call: the summed loss, the count of out-of-range class codes and, with the census on, its
-// table come back in one copy
+// the one synchronisation of a call: what the launches under the setting left in loss_dev comes back in one copy -- the
+// summed loss and the count of out-of-range class codes, the census, the label counts behind the largest census, and
+// the Dice sums and term behind those
 static int u_loss_to_host(depgan_ctx* c, const char* who, long P, float* loss_host) {
+  const DgCeSetting& ce = c->loss.ce;
+  const DgDiceSetting& dice = c->loss.dice;
+  const int C = c->cfg.nc_out;
   ULossHost h;
-  h.loss = 0.f;
-  h.bad = 0;
-  const size_t ncen = c->census ? (size_t)c->cfg.nc_out * c->cfg.nc_out : 0;
-  // the loss-weight mode: the label counts sit behind the largest census, the copy takes everything up to them
-  // the Dice mode: its sums and its loss sit behind the label counts, the copy takes everything up to them
-  const bool dice = c->dice_form != DEPGAN_DICE_OFF;
-  const bool weighted = c->lw_on || c->focal_on;   // the weighted path ran: the loss-weight mode or the focal mode
-  const size_t bytes = dice      ? offsetof(ULossHost, dice) + offsetof(DgDiceDev, A)
-                       : weighted ? offsetof(ULossHost, counts) + (size_t)(c->cfg.nc_out + 3) * sizeof(long long)
-                                  : 2 * sizeof(float) + ncen * sizeof(long long);
+  h.ce.loss = 0.f;
+  h.ce.bad = 0;
+  const size_t bytes = dice.form != DEPGAN_DICE_OFF ? offsetof(ULossHost, dice) + offsetof(DgDiceDev, A)
+                                                    : DgCeDev::bytes(C, ce);
   HIPCHECK(hipMemcpyAsync(&h, c->loss_dev, bytes, hipMemcpyDeviceToHost, c->st));
   HIPCHECK(hipStreamSynchronize(c->st));
-  const unsigned bad = h.bad;
-  if (ncen) {
-    memcpy(c->last_census, h.census, ncen * sizeof(long long));
-    c->census_valid = true;
+  if (ce.census) {
+    memcpy(c->last.census, h.ce.census, (size_t)C * C * sizeof(long long));
+    c->last.census_valid = true;
   }
   // the mean's denominator: every pixel, or on the weighted path the pixels with a non-zero weight (0.0 for none)
   float den = (float)P;
-  if (weighted) {
-    memcpy(c->lw_counts, h.counts, (size_t)(c->cfg.nc_out + 3) * sizeof(long long));
-    c->lw_valid = true;
-    den = (float)(unsigned long long)h.counts[0];
+  if (ce.weighted_path()) {
+    memcpy(c->last.counts, h.ce.counts, (size_t)(C + 3) * sizeof(long long));
+    c->last.counts_valid = true;
+    den = (float)h.ce.counts[0];
   }
-  c->last_sums[0] = h.loss;
+  c->last_sums[0] = h.ce.loss;
   c->last_sums[1] = den;
-  float loss = (den != 0.f) ? h.loss / den : 0.f;
-  if (dice) {
-    memcpy(c->dice_sums, h.dice.sums, (size_t)3 * c->cfg.nc_out * sizeof(double));
-    c->dice_last = h.dice.loss;
-    c->dice_valid = true;
-    loss = c->dice_ce_coef * loss + c->dice_coef * h.dice.loss;
+  float loss = (den != 0.f) ? h.ce.loss / den : 0.f;
+  if (dice.form != DEPGAN_DICE_OFF) {
+    memcpy(c->last.dice_sums, h.dice.sums, (size_t)3 * C * sizeof(double));
+    c->last.dice_loss = h.dice.loss;
+    c->last.dice_valid = true;
+    loss = dice.ce_coef * loss + dice.dice_coef * h.dice.loss;
   }
   if (loss_host) *loss_host = loss;
-  if (bad) {
-    dg_set_error("%s: %u of %ld class codes are outside [0, %d)", who, bad, P, c->cfg.nc_out);
+  if (h.ce.bad) {
+    dg_set_error("%s: %u of %ld class codes are outside [0, %d)", who, h.ce.bad, P, C);
     return DG_ERR_ARG;
   }
   return DG_OK;
 }
 
-static int u_grads(depgan_ctx* c, const char* who, const float* x, const float* z, ULabels lab, int n,
+static int u_grads(depgan_ctx* c, const char* who, const float* x, const float* z, DgLabels lab, int n,
                    unsigned drop_seed, float* loss_host, bool refresh_bn) {
   DGCHECK(u_check(c, who));
   if (n < 1 || n > c->cfg.batch) {
@@ -455,7 +425,7 @@ static int u_grads(depgan_ctx* c, const char* who, const float* x, const float* 
   return rc;
 }
 
-static int u_step(depgan_ctx* c, const char* who, const float* x, const float* z, ULabels lab, int n,
+static int u_step(depgan_ctx* c, const char* who, const float* x, const float* z, DgLabels lab, int n,
                   unsigned drop_seed, float* loss_host) {
   DGCHECK(infer_refuse(c, who));
   // an out-of-range class code comes back here as status 1, after the loss fetch: no Adam update, the step counter
@@ -466,13 +436,13 @@ static int u_step(depgan_ctx* c, const char* who, const float* x, const float* z
   // With the Dice mode on the same holds once no pixel takes part in the Dice term either: every pixel is without a true
   // class (then den == 0 too); pixels of zero-weight classes still carry a Dice gradient, and that batch is updated
   const long P = (long)n * c->cfg.height * c->cfg.width;
-  const bool ce_empty = (c->lw_on || c->focal_on) && c->lw_counts[0] == 0;
-  const bool dice_empty = c->lw_on && c->lw_counts[1] + c->lw_counts[2] == P;
-  if (c->dice_form == DEPGAN_DICE_OFF ? ce_empty : dice_empty) return refresh_generator_bn(c);
+  const bool ce_empty = c->loss.ce.weighted_path() && c->last.counts[0] == 0;
+  const bool dice_empty = c->loss.ce.weighted && c->last.counts[1] + c->last.counts[2] == P;
+  if (c->loss.dice.form == DEPGAN_DICE_OFF ? ce_empty : dice_empty) return refresh_generator_bn(c);
   return depgan_apply_adam(c, DEPGAN_NET_G);
 }
 
-static int u_eval(depgan_ctx* c, const char* who, const float* x, const float* z, ULabels lab, int n,
+static int u_eval(depgan_ctx* c, const char* who, const float* x, const float* z, DgLabels lab, int n,
                   float* loss_host) {
   DGCHECK(u_check(c, who));
   if (n < 1 || n > c->cfg.batch) { dg_set_error("uresnet_eval: n must be in [1, batch]"); return DG_ERR_ARG; }
@@ -491,21 +461,21 @@ int depgan_uresnet_set_census(depgan_ctx* c, int on) {
   if (on) {
     DGCHECK(u_check(c, "depgan_uresnet_set_census"));
   }
-  c->census = on != 0;
-  if (!on) c->census_valid = false;
+  c->loss.ce.census = on != 0;
+  if (!on) c->last.census_valid = false;
   return DG_OK;
 }
-int depgan_uresnet_get_census(depgan_ctx* c) { return (c && c->census) ? 1 : 0; }
+int depgan_uresnet_get_census(depgan_ctx* c) { return (c && c->loss.ce.census) ? 1 : 0; }
 int depgan_uresnet_last_census(depgan_ctx* c, long long out_host[DEPGAN_MAX_HEAD_CLASSES * DEPGAN_MAX_HEAD_CLASSES],
                                int* classes) {
   if (!c || !out_host) { dg_set_error("depgan_uresnet_last_census: null argument"); return DG_ERR_ARG; }
-  if (!c->census || !c->census_valid) {
+  if (!c->loss.ce.census || !c->last.census_valid) {
     dg_set_error("depgan_uresnet_last_census: no depgan_uresnet_* call has run with the census on "
                  "(depgan_uresnet_set_census)");
     return DG_ERR_ARG;
   }
   const int C = c->cfg.nc_out;
-  memcpy(out_host, c->last_census, (size_t)C * C * sizeof(long long));
+  memcpy(out_host, c->last.census, (size_t)C * C * sizeof(long long));
   if (classes) *classes = C;
   return DG_OK;
 }
@@ -513,31 +483,29 @@ int depgan_uresnet_last_census(depgan_ctx* c, long long out_host[DEPGAN_MAX_HEAD
 int depgan_uresnet_set_loss_weights(depgan_ctx* c, const float* w_host, int n, int ignore_code) {
   if (!c) { dg_set_error("depgan_uresnet_set_loss_weights: null context"); return DG_ERR_ARG; }
   if (!w_host) {
-    c->lw_on = c->lw_valid = false;
+    c->loss.ce.weighted = c->last.counts_valid = false;
     return DG_OK;
   }
   DGCHECK(u_check(c, "depgan_uresnet_set_loss_weights"));
   DGCHECK(dg_loss_weights_check("depgan_uresnet_set_loss_weights", w_host, n, c->cfg.nc_out, ignore_code));
-  memcpy(c->lw_w, w_host, (size_t)n * sizeof(float));
-  c->lw_ignore = ignore_code;
-  c->lw_on = true;
-  c->lw_valid = false;
+  c->loss.ce.set_weights(w_host, n, ignore_code);
+  c->last.counts_valid = false;
   return DG_OK;
 }
 int depgan_uresnet_get_loss_weights(depgan_ctx* c, float w_host[DEPGAN_MAX_HEAD_CLASSES], int* ignore_code) {
-  if (!c || !c->lw_on) return 0;
-  if (w_host) memcpy(w_host, c->lw_w, (size_t)c->cfg.nc_out * sizeof(float));
-  if (ignore_code) *ignore_code = c->lw_ignore;
+  if (!c || !c->loss.ce.weighted) return 0;
+  if (w_host) memcpy(w_host, c->loss.ce.cw, (size_t)c->cfg.nc_out * sizeof(float));
+  if (ignore_code) *ignore_code = c->loss.ce.ignore;
   return 1;
 }
 int depgan_uresnet_last_label_counts(depgan_ctx* c, long long out_host[DEPGAN_LABEL_NCOUNT], int* classes) {
   if (!c || !out_host) { dg_set_error("depgan_uresnet_last_label_counts: null argument"); return DG_ERR_ARG; }
-  if (!(c->lw_on || c->focal_on) || !c->lw_valid) {
+  if (!c->loss.ce.weighted_path() || !c->last.counts_valid) {
     dg_set_error("depgan_uresnet_last_label_counts: no depgan_uresnet_* call has run in the loss-weight mode "
                  "(depgan_uresnet_set_loss_weights) or the focal mode (depgan_uresnet_set_focal)");
     return DG_ERR_ARG;
   }
-  memcpy(out_host, c->lw_counts, (size_t)(c->cfg.nc_out + 3) * sizeof(long long));
+  memcpy(out_host, c->last.counts, (size_t)(c->cfg.nc_out + 3) * sizeof(long long));
   if (classes) *classes = c->cfg.nc_out;
   return DG_OK;
 }
@@ -549,17 +517,17 @@ int depgan_uresnet_set_focal(depgan_ctx* c, float gamma, float label_smoothing) 
   if (on) {
     DGCHECK(u_check(c, "depgan_uresnet_set_focal"));
   }
-  c->focal_on = on;
-  c->focal_gamma = on ? gamma : 0.f;
-  c->focal_eps = on ? label_smoothing : 0.f;
+  c->loss.ce.focal = on;
+  c->loss.ce.gamma = on ? gamma : 0.f;
+  c->loss.ce.eps = on ? label_smoothing : 0.f;
   // the counts on the host are those of a call made under the setting in force
-  c->lw_valid = false;
+  c->last.counts_valid = false;
   return DG_OK;
 }
 int depgan_uresnet_get_focal(depgan_ctx* c, float* gamma, float* label_smoothing) {
-  if (!c || !c->focal_on) return 0;
-  if (gamma) *gamma = c->focal_gamma;
-  if (label_smoothing) *label_smoothing = c->focal_eps;
+  if (!c || !c->loss.ce.focal) return 0;
+  if (gamma) *gamma = c->loss.ce.gamma;
+  if (label_smoothing) *label_smoothing = c->loss.ce.eps;
   return 1;
 }
 
@@ -567,69 +535,65 @@ int depgan_uresnet_set_dice_loss(depgan_ctx* c, int form, float ce_coef, float d
                                  const float* class_coef_host, int n) {
   if (!c) { dg_set_error("depgan_uresnet_set_dice_loss: null context"); return DG_ERR_ARG; }
   if (form == DEPGAN_DICE_OFF) {
-    c->dice_form = DEPGAN_DICE_OFF;
-    c->dice_valid = false;
+    c->loss.dice.form = DEPGAN_DICE_OFF;
+    c->last.dice_valid = false;
     return DG_OK;
   }
   DGCHECK(u_check(c, "depgan_uresnet_set_dice_loss"));
   const int C = c->cfg.nc_out;
   DGCHECK(dg_dice_check("depgan_uresnet_set_dice_loss", form, ce_coef, dice_coef, smooth, class_coef_host, n, C));
-  for (int k = 0; k < C; ++k) c->dice_c[k] = class_coef_host ? class_coef_host[k] : 1.0f / (float)C;
-  c->dice_form = form;
-  c->dice_ce_coef = ce_coef;
-  c->dice_coef = dice_coef;
-  c->dice_smooth = smooth;
-  c->dice_valid = false;
+  c->loss.dice.set(form, ce_coef, dice_coef, smooth, class_coef_host, C);
+  c->last.dice_valid = false;
   return DG_OK;
 }
 int depgan_uresnet_get_dice_loss(depgan_ctx* c, float* ce_coef, float* dice_coef, float* smooth,
                                  float class_coef_host[DEPGAN_MAX_HEAD_CLASSES]) {
-  if (!c || c->dice_form == DEPGAN_DICE_OFF) return DEPGAN_DICE_OFF;
-  if (ce_coef) *ce_coef = c->dice_ce_coef;
-  if (dice_coef) *dice_coef = c->dice_coef;
-  if (smooth) *smooth = c->dice_smooth;
-  if (class_coef_host && c->dice_form == DEPGAN_DICE_CLASS)
-    memcpy(class_coef_host, c->dice_c, (size_t)c->cfg.nc_out * sizeof(float));
-  return c->dice_form;
+  if (!c || c->loss.dice.form == DEPGAN_DICE_OFF) return DEPGAN_DICE_OFF;
+  const DgDiceSetting& d = c->loss.dice;
+  if (ce_coef) *ce_coef = d.ce_coef;
+  if (dice_coef) *dice_coef = d.dice_coef;
+  if (smooth) *smooth = d.smooth;
+  if (class_coef_host && d.form == DEPGAN_DICE_CLASS) memcpy(class_coef_host, d.c, (size_t)c->cfg.nc_out * sizeof(float));
+  return d.form;
 }
 int depgan_uresnet_last_dice_sums(depgan_ctx* c, double out_host[3 * DEPGAN_MAX_HEAD_CLASSES], int* classes,
                                   float* dice_loss) {
   if (!c || !out_host) { dg_set_error("depgan_uresnet_last_dice_sums: null argument"); return DG_ERR_ARG; }
-  if (c->dice_form == DEPGAN_DICE_OFF || !c->dice_valid) {
+  if (c->loss.dice.form == DEPGAN_DICE_OFF || !c->last.dice_valid) {
     dg_set_error("depgan_uresnet_last_dice_sums: no depgan_uresnet_* call has run with the Dice loss on "
                  "(depgan_uresnet_set_dice_loss)");
     return DG_ERR_ARG;
   }
-  memcpy(out_host, c->dice_sums, (size_t)3 * c->cfg.nc_out * sizeof(double));
+  memcpy(out_host, c->last.dice_sums, (size_t)3 * c->cfg.nc_out * sizeof(double));
   if (classes) *classes = c->cfg.nc_out;
-  if (dice_loss) *dice_loss = c->dice_last;
+  if (dice_loss) *dice_loss = c->last.dice_loss;
   return DG_OK;
 }
 
 int depgan_uresnet_grads(depgan_ctx* c, const float* x, const float* z, const float* labels, int n,
                          unsigned drop_seed, float* loss_host) {
-  return u_grads(c, "uresnet_grads", x, z, ULabels{labels, nullptr}, n, drop_seed, loss_host, true);
+  return u_grads(c, "uresnet_grads", x, z, DgLabels{labels, nullptr}, n, drop_seed, loss_host, true);
 }
 int depgan_uresnet_step(depgan_ctx* c, const float* x, const float* z, const float* labels, int n,
                         unsigned drop_seed, float* loss_host) {
-  return u_step(c, "depgan_uresnet_step", x, z, ULabels{labels, nullptr}, n, drop_seed, loss_host);
+  return u_step(c, "depgan_uresnet_step", x, z, DgLabels{labels, nullptr}, n, drop_seed, loss_host);
 }
 int depgan_uresnet_eval(depgan_ctx* c, const float* x, const float* z, const float* labels, int n,
                         float* loss_host) {
-  return u_eval(c, "uresnet_eval", x, z, ULabels{labels, nullptr}, n, loss_host);
+  return u_eval(c, "uresnet_eval", x, z, DgLabels{labels, nullptr}, n, loss_host);
 }
 
 int depgan_uresnet_grads_sparse(depgan_ctx* c, const float* x, const float* z, const unsigned char* codes, int n,
                                 unsigned drop_seed, float* loss_host) {
-  return u_grads(c, "uresnet_grads_sparse", x, z, ULabels{nullptr, codes}, n, drop_seed, loss_host, true);
+  return u_grads(c, "uresnet_grads_sparse", x, z, DgLabels{nullptr, codes}, n, drop_seed, loss_host, true);
 }
 int depgan_uresnet_step_sparse(depgan_ctx* c, const float* x, const float* z, const unsigned char* codes, int n,
                                unsigned drop_seed, float* loss_host) {
-  return u_step(c, "depgan_uresnet_step_sparse", x, z, ULabels{nullptr, codes}, n, drop_seed, loss_host);
+  return u_step(c, "depgan_uresnet_step_sparse", x, z, DgLabels{nullptr, codes}, n, drop_seed, loss_host);
 }
 int depgan_uresnet_eval_sparse(depgan_ctx* c, const float* x, const float* z, const unsigned char* codes, int n,
                                float* loss_host) {
-  return u_eval(c, "uresnet_eval_sparse", x, z, ULabels{nullptr, codes}, n, loss_host);
+  return u_eval(c, "uresnet_eval_sparse", x, z, DgLabels{nullptr, codes}, n, loss_host);
 }
 
 }  // extern "C"
