@@ -292,6 +292,11 @@ struct ProfScope {
 // zero-filled device memory of the context's lifetime (depgan_destroy frees it), sized in bytes.  The status of the
 // hipMalloc or of the fill comes back unworded: dmalloc (floats) and bf16s_alloc (bf16 elements) word their own messages
 hipError_t dalloc_bytes(depgan_ctx* c, void** p, size_t bytes);
+// The fill of dalloc_bytes is a hipMemset on the null stream, which does not wait for the host, and the context's stream
+// may be a non-blocking one that the null stream does not order itself against.  Every entry that allocates context
+// memory (depgan_create and the lazy allocators) ends with this wait, once, so that on its return every fill and table
+// upload is complete on the device whatever stream the first kernel or the caller's upload runs on.
+int dalloc_fills_done();
 int dmalloc(depgan_ctx* c, float** p, size_t floats);
 // A device temporary of ONE call (never a context's: those go through c->allocs).  alloc reports failure as a status and
 // frees nothing; the destructor waits for the stream the work went to and frees, so every return after alloc is covered

@@ -57,6 +57,10 @@ hipError_t dalloc_bytes(depgan_ctx* c, void** p, size_t bytes) {
   c->allocs.push_back(*p);
   return hipMemset(*p, 0, bytes);
 }
+int dalloc_fills_done() {
+  HIPCHECK(hipStreamSynchronize(nullptr));
+  return DG_OK;
+}
 int dmalloc(depgan_ctx* c, float** p, size_t floats) {
   if (floats == 0) floats = 4;
   HIPCHECK(dalloc_bytes(c, (void**)p, floats * sizeof(float)));
@@ -1049,7 +1053,7 @@ static int net_opt_alloc(depgan_ctx* c, Net& n) {
   HIPCHECK(dalloc_bytes(c, &g, 4 * sizeof(double)));
   n.decay_bits = (unsigned*)b;
   n.gnorm = (double*)g;
-  return DG_OK;
+  return dalloc_fills_done();
 }
 
 // ---------------------------------------------------------------------------
@@ -1072,7 +1076,11 @@ static int critic_enqueue(depgan_ctx* c, int which, const float* y2, const float
     // parity-test surface: the mixed pass's activations, before the penalty's u-forward overwrites them in place
     for (int l = 0; l < 11; ++l) {
       const size_t per = c->d_act[l].per_sample();
-      if (!c->dbg_mixed[l]) DGCHECK(dmalloc(c, &c->dbg_mixed[l], (size_t)B * per));
+      if (!c->dbg_mixed[l]) {
+        // first capture only: the fill must not land behind the copy below when c->st is a non-blocking stream
+        DGCHECK(dmalloc(c, &c->dbg_mixed[l], (size_t)B * per));
+        DGCHECK(dalloc_fills_done());
+      }
       HIPCHECK(hipMemcpyAsync(c->dbg_mixed[l], c->d_act[l].p + (size_t)2 * B * per, (size_t)B * per * sizeof(float),
                               hipMemcpyDeviceToDevice, c->st));
     }
@@ -1432,6 +1440,7 @@ int depgan_create(const depgan_config* cfg, depgan_ctx** out) {
     rc = DG_ERR_HIP;
   }
   if (rc == DG_OK) c->best_host = reinterpret_cast<int*>(c->host_stats + HOST_STATS_FLOATS);
+  if (rc == DG_OK) rc = dalloc_fills_done();   // every zero-fill and table upload above is complete on return
   if (rc != DG_OK) {
     depgan_destroy(c);
     return rc;

@@ -88,7 +88,7 @@ int bf16s_alloc(depgan_ctx* c) {
     if (L.kind != G_HEAD) cur = L.hout;
   }
   c->h_ready = true;
-  return DG_OK;
+  return dalloc_fills_done();
 }
 
 // algorithmic bytes of one bf16-storage convolution launch: activations at 2 bytes per element, bf16 panels

@@ -31,7 +31,7 @@ int bf16s_train_alloc(depgan_ctx* c) {
     L.hdec = (unsigned char*)pd;
   }
   c->hu_ready = true;
-  return DG_OK;
+  return dalloc_fills_done();
 }
 
 int g_forward_train_bf16s(depgan_ctx* c, const float* x, const float* z) {

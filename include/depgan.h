@@ -74,7 +74,22 @@ const char* depgan_last_error(void);
  * Weights start zeroed: load them with depgan_arena_ptr + depgan_weights_changed. */
 int depgan_create(const depgan_config* cfg, depgan_ctx** out);
 void depgan_destroy(depgan_ctx* ctx);
-/* all work is enqueued on this hipStream_t (default: the null stream) */
+/* all work is enqueued on this hipStream_t (default: the null stream).  The stream contract ("Streams"):
+ *   - Every kernel, memset and copy of a context entry goes to the stream set here; every stateless entry that takes a
+ *     `stream` / `hip_stream` argument puts all its work on that stream.  Nothing is enqueued on the null stream and no
+ *     entry waits for it, so a stream created non-blocking (hipStreamNonBlocking, torch.cuda.Stream()) is supported:
+ *     operands need only be valid in that stream's order, not on the host's clock.
+ *   - An entry that returns host values (losses, counts, a status that depends on device data) synchronises that stream
+ *     and no other; an entry that returns none does not wait for the device at all.
+ *   - Allocation is the one exception and it is closed on return: depgan_create and every entry that allocates context
+ *     memory lazily (depgan_set_fwd_only_storage / depgan_set_g_update_storage and the first pass under them,
+ *     depgan_g_forward_bf16s, depgan_set_optimizer, the first capture under depgan_debug_capture) zero-fill on the null
+ *     stream and wait for it once before they return.
+ *     On return every zero-fill and table upload is complete on the device, whatever stream the next kernel -- or the
+ *     caller's own upload through depgan_arena_ptr -- runs on.
+ *   - depgan_set_stream itself enqueues nothing and waits for nothing.  Ordering across a switch is the caller's job:
+ *     work already enqueued on the old stream must be finished (or the new stream made to wait for it) before an entry
+ *     on the new stream touches the context. */
 int depgan_set_stream(depgan_ctx* ctx, void* hip_stream);
 
 /* Data parallelism (the reference is single-GPU, GT:13).  The library stays free of any communication
