@@ -36,7 +36,6 @@ struct WgradArgsH {
   int colB;
 };
 bool dg_wgrad_bf16s_supported(int KS, int Cin, int Cout);
-size_t dg_wgrad_bf16s_part_floats(int KS, int B, int H, int W, int Cin, int Cout);
 int dg_wgrad_bf16s(int KS, const WgradArgsH& a, int* nchunks, hipStream_t st);
 int dg_wgrad_bf16s_plan(int KS, int B, int H, int W, int Cin, int Cout, int out[4]);   // as dg_wgrad_plan (common.h)
 

@@ -330,9 +330,8 @@ int dg_get_epi_classes();
 void dg_conv_igemm_name(const ConvPlan& pl, const ConvArgs& a, char* buf, size_t cap);
 int dg_conv_direct(int KS, const ConvArgs& a, hipStream_t st);
 
-// wgrad: returns number of chunks used through *nchunks; part must hold
-// dg_wgrad_part_floats() floats.
-size_t dg_wgrad_part_floats(int KS, int B, int H, int W, int Cin, int Cout);
+// wgrad: returns number of chunks used through *nchunks; part must hold nchunks slabs of KS * KS * Cin * Cout floats
+// (DgWgradChoice::part_floats).
 int dg_wgrad(int KS, const WgradArgs& a, int* nchunks, hipStream_t st);
 // out[(tap,ci,co)] (+)= scale[co] * sum_chunks part ; raw (optional) gets the unscaled sum.
 // oi=1 writes [tap][co][ci] (Conv2DTranspose kernel layout) instead of [tap][ci][co].
@@ -344,17 +343,13 @@ int dg_wgrad_finish(const float* part, int nchunks, int ntaps, int Cin, int Cout
 int dg_wgrad_finish_rows(const float* part, int nchunks, int ntaps, int Cin, int Cout, const float* scale, float* out,
                          float* raw, int accumulate, int oi, const float* colpart, int colrows, int colC,
                          const float* colscale, float* colout, float* colraw, hipStream_t st);
-int dg_wgrad_reduce(const float* part, int nchunks, int ntaps, int Cin, int Cout, const float* scale, float* out,
-                    float* raw, int accumulate, int oi, hipStream_t st);
 
 // bf16 matrix pipe (wgrad_bf16.hip, BASELINE configs[3]): operands rounded to bf16 while staged, fp32 accumulation;
 // same slab format, column-sum rows ([nchunks][Cout], samples b < colB) and finish launch as dg_wgrad
 bool dg_wgrad_bf16_supported(int KS, int Cin, int Cout);
-size_t dg_wgrad_bf16_part_floats(int KS, int B, int H, int W, int Cin, int Cout);
 int dg_wgrad_bf16(int KS, const WgradArgs& a, int* nchunks, hipStream_t st);
 
 // small-Cin wgrad (VALU), same slab format as dg_wgrad
-size_t dg_wgrad_small_part_floats(int KS, int B, int H, int W, int Cin, int Cout);
 int dg_wgrad_small(int KS, const WgradArgs& a, int* nchunks, hipStream_t st);
 
 // The launch plan each of these launchers computes for a shape, from the launcher's own chunking function and without a
@@ -363,3 +358,23 @@ int dg_wgrad_small(int KS, const WgradArgs& a, int* nchunks, hipStream_t st);
 int dg_wgrad_plan(int KS, int B, int H, int W, int Cin, int Cout, int out[4]);
 int dg_wgrad_small_plan(int KS, int B, int H, int W, int Cin, int Cout, int out[4]);
 int dg_wgrad_bf16_plan(int KS, int B, int H, int W, int Cin, int Cout, int out[4]);
+
+// THE rule that says which slab kernel a weight gradient takes and what the launch needs (wgrad_select.hip; host only,
+// no HIP call).  With mfma = Cin % 4 == 0 && Cout % 4 == 0 && Cin >= 8:
+//   x_bf16 (activation operand in bf16 memory)        DG_WG_BF16S where dg_wgrad_bf16s_supported, else DG_ERR_UNSUPPORTED
+//   bf16_pipe && mfma && dg_wgrad_bf16_supported      DG_WG_BF16
+//   mfma                                              DG_WG_F32
+//   otherwise                                         DG_WG_EDGE
+// nchunks is the chosen launcher's own plan (its refusal is returned), part_floats = nchunks slabs of KS KS Cin Cout
+// floats, col_rows the partial column-sum rows of Cout floats the kernel writes when asked for column sums: nchunks for
+// the three MFMA kernels, 0 for the edge kernel, whose column sums are the streaming dg_colsum pass.
+// The numbering is that of depgan_debug_wgrad_plan; DG_WG_DECONV (deconv_wgrad.hip) is never chosen here.
+enum DgWgradKernel { DG_WG_F32 = 0, DG_WG_EDGE = 1, DG_WG_BF16 = 2, DG_WG_BF16S = 3, DG_WG_DECONV = 4 };
+struct DgWgradChoice {
+  int kernel, nchunks;
+  size_t part_floats;
+  int col_rows;
+};
+int dg_wgrad_choose(int KS, int B, int H, int W, int Cin, int Cout, bool bf16_pipe, bool x_bf16, DgWgradChoice* out);
+// the *_plan of slab kernel `kernel` (DG_WG_F32 .. DG_WG_BF16S)
+int dg_wgrad_plan_of(int kernel, int KS, int B, int H, int W, int Cin, int Cout, int out[4]);

@@ -357,7 +357,7 @@ int dg_conv_direct(int KS, const ConvArgs& a_in, hipStream_t st) {
 
 // ---------------------------------------------------------------------------
 // weight gradient for the small-Cin edge layers (gen_0, dis_0a): same slab
-// format as the MFMA wgrad so dg_wgrad_reduce finishes it.
+// format as the MFMA wgrad so dg_wgrad_finish finishes it.
 // ---------------------------------------------------------------------------
 template <int KS>
 __global__ __launch_bounds__(256) void wgrad_small_kernel(const WgradArgs a) {
@@ -526,13 +526,6 @@ static void small_chunking(int B, int H, int W, int* nTiles, int* tpc, int* nch)
   if (want > *nTiles) want = *nTiles;
   *tpc = cdiv(*nTiles, want);
   *nch = cdiv(*nTiles, *tpc);
-}
-
-size_t dg_wgrad_small_part_floats(int KS, int B, int H, int W, int Cin, int Cout) {
-  int nTiles, tpc, nch;
-  small_chunking(B, H, W, &nTiles, &tpc, &nch);
-  const size_t slab = (size_t)KS * KS * Cin * Cout;
-  return (size_t)nch * slab;
 }
 
 // the launch plan of dg_wgrad_small for a shape, without launching (depgan_debug_wgrad_plan)

@@ -5,6 +5,7 @@
 
 #include <map>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/depgan.h"
@@ -367,12 +368,6 @@ static inline A wgrad_args_of(X x, TView dy, float* part, int B, int H, int W, i
   a.colB = 0;
   return a;
 }
-static inline WgradArgs wgrad_args(TView x, TView dy, float* part, int B, int H, int W, int Cin, int Cout) {
-  return wgrad_args_of<WgradArgs>(x, dy, part, B, H, W, Cin, Cout);
-}
-static inline WgradArgsH wgrad_args_h(TViewH x, TView dy, float* part, int B, int H, int W, int Cin, int Cout) {
-  return wgrad_args_of<WgradArgsH>(x, dy, part, B, H, W, Cin, Cout);
-}
 TView view_offset(TView v, long samples);
 // pixel grid (2i + di, 2j + dj) of a (2H, 2W) view (TView or TViewH)
 template <typename V>
@@ -440,8 +435,10 @@ static inline bool op_view_bad_broadcast(const void* p, long sB, long sY, long s
 // upload and run pack jobs whose destinations interleave (GLayer::wpb_all); synchronises: `jobs` is the caller's
 int op_pack_jobs(PackJob* jobs, int n, hipStream_t st);
 int deconv_bwd_data(depgan_ctx* c, GLayer& L, TView dsrc, int n);
-// weight gradient (four taps) + column sums of the upstream gradient of a transposed convolution
-int deconv_wgrad_all(depgan_ctx* c, const GLayer& L, TView dsrc, int n, const float* scale, float* raw,
+// weight gradient (four taps) + column sums of the upstream gradient of a transposed convolution whose input is the
+// view x (XV = TView: L.in; TViewH: L.hin, the bf16 activation storage)
+template <typename XV>
+int deconv_wgrad_all(depgan_ctx* c, const GLayer& L, XV x, TView dsrc, int n, const float* scale, float* raw,
                      const float* colscale, float* colout, float* colraw);
 // forward of a transposed convolution on the fused four-tap kernel (deconv_fwd.hip) where it covers the layer
 bool deconv_fused(const depgan_ctx* c, const GLayer& L, int n);
@@ -453,21 +450,35 @@ struct ColSum {
   const float* scale;
   float *out, *raw;
 };
-// the workspaces of one weight gradient are the caller's: the context's own in the model, a call's own in
-// depgan_op_conv2d_wgrad_ex
+// the workspaces of one weight gradient are the caller's: the context's own in the model, a call's own in the
+// depgan_op_conv2d_wgrad* entries
 struct WgradWs {
   float* part;           // slabs
   size_t partFloats;
-  float* scratch;        // partial column-sum rows ([nchunks][Cout]) or the scratch of the streaming column-sum pass
+  float* scratch;        // partial column-sum rows ([col_rows][Cout]) or the scratch of the streaming column-sum pass
   size_t scratchFloats;
   bool bf16;             // contraction on the bf16 matrix pipe where wgrad_bf16.hip covers the shape
   hipStream_t st;
   depgan_ctx* prof;      // profile records go to this context; null: none
 };
-int wgrad_run(const WgradWs& ws, int KS, TView x, TView dy, int N, int H, int W, int Cin, int Cout, const float* scale,
+// THE weight-gradient driver, the only code that launches a slab kernel and its finish: the kernel dg_wgrad_choose names
+// for the shape, ws.bf16 and the storage of x (XV = TView: fp32; TViewH: bf16), the capacity checks (status 1 before any
+// launch), the streaming column-sum pass where the kernel has no column rows, the launch, the finish
+template <typename XV>
+int wgrad_run(const WgradWs& ws, int KS, XV x, TView dy, int N, int H, int W, int Cin, int Cout, const float* scale,
               float* out, float* raw, int accumulate, int oi, const ColSum* cs);
-int wgrad_full(depgan_ctx* c, int KS, TView x, TView dy, int N, int H, int W, int Cin, int Cout, const float* scale,
-               float* out, float* raw, int accumulate, int oi, const ColSum* cs = nullptr);
+// ... on the context's workspaces and stream, with its profile records
+template <typename XV>
+static inline int wgrad_full(depgan_ctx* c, int KS, XV x, TView dy, int N, int H, int W, int Cin, int Cout,
+                             const float* scale, float* out, float* raw, int accumulate, int oi,
+                             const ColSum* cs = nullptr) {
+  const WgradWs ws = {c->part, c->partFloats, c->scratch, c->scratchFloats, c->cfg.bf16_mfma && c->wgrad_bf16, c->st, c};
+  return wgrad_run(ws, KS, x, dy, N, H, W, Cin, Cout, scale, out, raw, accumulate, oi, cs);
+}
+// ... of an operator entry, after its own argument checks: DevTmp workspaces of the call, sized from the choice
+template <typename XV>
+int op_wgrad(const char* who, int KS, XV x, TView dy, int B, int H, int W, int Cin, int Cout, bool bf16,
+             const float* scale, float* dw, float* raw, int accumulate, int oi, const ColSum* cs, hipStream_t st);
 int net_adam(depgan_ctx* c, Net& n, float gscale = 1.0f);
 int g_forward(depgan_ctx* c, const float* x, const float* z, int n, bool store_u);
 // model_bf16s.hip.  bf16s_check_ctx: what the context must be for the bf16-storage forward (no HIP call);

@@ -177,29 +177,31 @@ int deconv_fwd_launch(depgan_ctx* c, const GLayer& L, TView out, const float* bi
 // Weight gradient of a transposed convolution (all four taps) and the column sums of its upstream gradient:
 // dW = scale . sum, raw (optional) = the unscaled sum, db = colscale . colsum, draw_col (optional) = colsum.
 // One fused launch + one reduction where deconv_wgrad.hip covers the layer, else the column-sum pass and four
-// per-tap launches of the general kernel.
-int deconv_wgrad_all(depgan_ctx* c, const GLayer& L, TView dsrc, int n, const float* scale, float* raw,
+// per-tap launches of the general kernel.  The fused kernel reads fp32 operands and runs in fp32 contexts only.
+template <typename XV>
+int deconv_wgrad_all(depgan_ctx* c, const GLayer& L, XV x, TView dsrc, int n, const float* scale, float* raw,
                      const float* colscale, float* colout, float* colraw) {
-  if (!c->cfg.bf16_mfma && !c->cfg.f32_split &&
-      dg_deconv_wgrad_supported(n, L.H, L.W, L.Cin, L.Cout, L.in, dsrc) &&
-      dg_deconv_wgrad_part_floats(n, L.H, L.W, L.Cin, L.Cout) <= c->partFloats) {
-    DeconvWgradArgs d;
-    memset(&d, 0, sizeof(d));
-    d.in = L.in.p;
-    d.dout = dsrc;
-    d.part = c->part;
-    d.colpart = c->scratch;
-    d.H = L.H; d.W = L.W; d.Cin = L.Cin; d.Cout = L.Cout;
-    int nch = 0;
-    {
-      char lb[56];
-      snprintf(lb, sizeof(lb), "wgrad k1 b%d %dx%d %d->%d x4", n, L.H, L.W, L.Cin, L.Cout);
-      ProfScope ps(c, 1, 2.0 * n * L.H * L.W * (double)L.Cin * L.Cout * 4, lb);
-      DGCHECK(dg_deconv_wgrad(d, n, &nch, c->st));
+  if constexpr (std::is_same<XV, TView>::value) {
+    if (!c->cfg.bf16_mfma && !c->cfg.f32_split && dg_deconv_wgrad_supported(n, L.H, L.W, L.Cin, L.Cout, x, dsrc) &&
+        dg_deconv_wgrad_part_floats(n, L.H, L.W, L.Cin, L.Cout) <= c->partFloats) {
+      DeconvWgradArgs d;
+      memset(&d, 0, sizeof(d));
+      d.in = x.p;
+      d.dout = dsrc;
+      d.part = c->part;
+      d.colpart = c->scratch;
+      d.H = L.H; d.W = L.W; d.Cin = L.Cin; d.Cout = L.Cout;
+      int nch = 0;
+      {
+        char lb[56];
+        snprintf(lb, sizeof(lb), "wgrad k1 b%d %dx%d %d->%d x4", n, L.H, L.W, L.Cin, L.Cout);
+        ProfScope ps(c, 1, 2.0 * n * L.H * L.W * (double)L.Cin * L.Cout * 4, lb);
+        DGCHECK(dg_deconv_wgrad(d, n, &nch, c->st));
+      }
+      ProfScope ps(c, 2, 0.0, "slab reduce");
+      return dg_wgrad_finish_rows(c->part, nch, 4, L.Cin, L.Cout, scale, L.dW, raw, 0, 1, c->scratch, 4 * nch, L.Cout,
+                                  colscale, colout, colraw, c->st);
     }
-    ProfScope ps(c, 2, 0.0, "slab reduce");
-    return dg_wgrad_finish_rows(c->part, nch, 4, L.Cin, L.Cout, scale, L.dW, raw, 0, 1, c->scratch, 4 * nch, L.Cout,
-                                colscale, colout, colraw, c->st);
   }
   {
     ProfScope ps(c, 2, 0.0, "colsum");
@@ -208,11 +210,15 @@ int deconv_wgrad_all(depgan_ctx* c, const GLayer& L, TView dsrc, int n, const fl
   }
   for (int t = 0; t < 4; ++t) {
     const size_t o = (size_t)t * L.Cout * L.Cin;
-    DGCHECK(wgrad_full(c, 1, L.in, strided2(dsrc, t / 2, t % 2), n, L.H, L.W, L.Cin, L.Cout, scale, L.dW + o,
+    DGCHECK(wgrad_full(c, 1, x, strided2(dsrc, t / 2, t % 2), n, L.H, L.W, L.Cin, L.Cout, scale, L.dW + o,
                        raw ? raw + o : nullptr, 0, 1));
   }
   return DG_OK;
 }
+template int deconv_wgrad_all<TView>(depgan_ctx*, const GLayer&, TView, TView, int, const float*, float*, const float*,
+                                     float*, float*);
+template int deconv_wgrad_all<TViewH>(depgan_ctx*, const GLayer&, TViewH, TView, int, const float*, float*,
+                                      const float*, float*, float*);
 
 int deconv_bwd_data(depgan_ctx* c, GLayer& L, TView dsrc, int n) {
   ConvArgs a = conv_args(null_view(), L.din, n, L.H, L.W, L.Cout, L.Cin);
@@ -248,79 +254,67 @@ void deconv_gather_k(ConvArgs* a, TView d, int Cout, int CK) {
 }
 
 // weight gradient: slabs + reduction (+ optional BN scale / raw copy / OI layout)
-// The workspaces are the caller's (WgradWs): the context's own in the model, a call's own in depgan_op_conv2d_wgrad_ex.
-int wgrad_run(const WgradWs& ws, int KS, TView x, TView dy, int N, int H, int W, int Cin, int Cout,
-                     const float* scale, float* out, float* raw, int accumulate, int oi, const ColSum* cs) {
+// The workspaces are the caller's (WgradWs): the context's own in the model, a call's own in the operator entries.
+static int wgrad_launch(int kernel, int KS, const WgradArgs& a, int* nch, hipStream_t st) {
+  if (kernel == DG_WG_F32) return dg_wgrad(KS, a, nch, st);
+  if (kernel == DG_WG_EDGE) return dg_wgrad_small(KS, a, nch, st);
+  // BASELINE configs[3] on the bf16 matrix pipe: the contraction on v_mfma_f32_32x32x16_bf16 (operands rounded while
+  // staged, fp32 accumulation)
+  return dg_wgrad_bf16(KS, a, nch, st);
+}
+static int wgrad_launch(int, int KS, const WgradArgsH& a, int* nch, hipStream_t st) { return dg_wgrad_bf16s(KS, a, nch, st); }
+
+template <typename XV>
+int wgrad_run(const WgradWs& ws, int KS, XV x, TView dy, int N, int H, int W, int Cin, int Cout, const float* scale,
+              float* out, float* raw, int accumulate, int oi, const ColSum* cs) {
+  constexpr bool x_bf16 = std::is_same<XV, TViewH>::value;
+  typedef typename std::conditional<x_bf16, WgradArgsH, WgradArgs>::type Args;
   depgan_ctx* c = ws.prof;
   float* const scratch = ws.scratch;
   const size_t cap = ws.scratchFloats;
-  WgradArgs a = wgrad_args(x, dy, ws.part, N, H, W, Cin, Cout);
-  int nch = 0;
-  const double fl = 2.0 * N * H * W * (double)Cin * Cout * KS * KS;
-  char lb[56];
-  snprintf(lb, sizeof(lb), "wgrad k%d b%d %dx%d %d->%d", KS, N, H, W, Cin, Cout);
-  const bool mfma = Cin % 4 == 0 && Cout % 4 == 0 && Cin >= 8;
-  // BASELINE configs[3] on the bf16 matrix pipe: the contraction on v_mfma_f32_32x32x16_bf16 (operands rounded while
-  // staged, fp32 accumulation); the column sums keep their own streaming pass
-  if (ws.bf16 && mfma && dg_wgrad_bf16_supported(KS, Cin, Cout)) {
-    if (dg_wgrad_bf16_part_floats(KS, N, H, W, Cin, Cout) > ws.partFloats) {
-      dg_set_error("wgrad slab workspace too small");
-      return DG_ERR_ARG;
-    }
-    if (cs) {
-      a.colpart = scratch;
-      a.colB = cs->B;
-    }
-    snprintf(lb, sizeof(lb), "wgrad(bf16) k%d b%d %dx%d %d->%d", KS, N, H, W, Cin, Cout);
-    {
-      ProfScope ps(c, 1, fl, lb);
-      DGCHECK(dg_wgrad_bf16(KS, a, &nch, ws.st));
-    }
-    ProfScope ps(c, 2, 0.0, "slab reduce");
-    return dg_wgrad_finish(ws.part, nch, KS * KS, Cin, Cout, scale, out, raw, accumulate, oi, cs ? scratch : nullptr,
-                           Cout, cs ? cs->scale : nullptr, cs ? cs->out : nullptr, cs ? cs->raw : nullptr, ws.st);
+  DgWgradChoice ch;
+  DGCHECK(dg_wgrad_choose(KS, N, H, W, Cin, Cout, ws.bf16, x_bf16, &ch));
+  if (ch.part_floats > ws.partFloats) {
+    dg_set_error("wgrad slab workspace too small");
+    return DG_ERR_ARG;
   }
-  // Column sums of dy (bias / BN-beta gradients) ride in the MFMA weight-gradient kernel, whose B fragments are the
+  // Column sums of dy (bias / BN-beta gradients) ride in the MFMA weight-gradient kernels, whose B fragments are the
   // dy values anyway (2 FMAs per 18 MFMAs in one workgroup column; with the register-staged kernel of earlier in the
-  // round the same idea cost 10 % -- it sat at the VGPR limit of two workgroups per CU).  The edge-layer kernels keep
-  // the separate streaming pass.
-  if (cs && !mfma) {
+  // round the same idea cost 10 % -- it sat at the VGPR limit of two workgroups per CU): one partial row per slab.
+  // The edge-layer kernels keep the separate streaming pass.
+  const bool rows = cs && ch.col_rows;
+  if (rows && (size_t)ch.col_rows * Cout > cap) {
+    dg_set_error("wgrad column-sum workspace too small (%d rows of %d floats, capacity %zu)", ch.col_rows, Cout, cap);
+    return DG_ERR_ARG;
+  }
+  if (cs && !rows) {
     ProfScope ps(c, 2, 0.0, "colsum");
     DGCHECK(dg_colsum(dy, cs->B, H, W, Cout, cs->scale, cs->out, cs->raw, 0, scratch, cap, ws.st));
   }
-  if (mfma) {
-    if (dg_wgrad_part_floats(KS, N, H, W, Cin, Cout) > ws.partFloats) {
-      dg_set_error("wgrad slab workspace too small");
-      return DG_ERR_ARG;
-    }
-    if (cs) {
-      a.colpart = scratch;
-      a.colB = cs->B;
-    }
-    {
-      ProfScope ps(c, 1, fl, lb);
-      DGCHECK(dg_wgrad(KS, a, &nch, ws.st));
-    }
-    // slab reduction and the column-sum finish in one launch
-    ProfScope ps(c, 2, 0.0, "slab reduce");
-    return dg_wgrad_finish(ws.part, nch, KS * KS, Cin, Cout, scale, out, raw, accumulate, oi, cs ? scratch : nullptr,
-                           Cout, cs ? cs->scale : nullptr, cs ? cs->out : nullptr, cs ? cs->raw : nullptr, ws.st);
-  } else {
-    if (dg_wgrad_small_part_floats(KS, N, H, W, Cin, Cout) > ws.partFloats) {
-      dg_set_error("wgrad slab workspace too small");
-      return DG_ERR_ARG;
-    }
-    ProfScope ps(c, 2, fl, lb);
-    DGCHECK(dg_wgrad_small(KS, a, &nch, ws.st));
+  Args a = wgrad_args_of<Args>(x, dy, ws.part, N, H, W, Cin, Cout);
+  if (rows) {
+    a.colpart = scratch;
+    a.colB = cs->B;
   }
+  int nch = 0;
+  {
+    static const char* const tag[] = {"wgrad", "wgrad", "wgrad(bf16)", "wgrad(bf16s)"};
+    char lb[56];
+    snprintf(lb, sizeof(lb), "%s k%d b%d %dx%d %d->%d", tag[ch.kernel], KS, N, H, W, Cin, Cout);
+    const double px = (double)N * H * W;
+    ProfScope ps(c, ch.kernel == DG_WG_EDGE ? 2 : 1, 2.0 * px * Cin * Cout * KS * KS, lb,
+                 x_bf16 ? px * (2.0 * Cin + 4.0 * Cout) : 0.0);
+    DGCHECK(wgrad_launch(ch.kernel, KS, a, &nch, ws.st));
+  }
+  // slab reduction and (MFMA kernels) the column-sum finish in one launch
   ProfScope ps(c, 2, 0.0, "slab reduce");
-  return dg_wgrad_reduce(ws.part, nch, KS * KS, Cin, Cout, scale, out, raw, accumulate, oi, ws.st);
+  return dg_wgrad_finish(ws.part, nch, KS * KS, Cin, Cout, scale, out, raw, accumulate, oi, rows ? scratch : nullptr,
+                         Cout, rows ? cs->scale : nullptr, rows ? cs->out : nullptr, rows ? cs->raw : nullptr, ws.st);
 }
-int wgrad_full(depgan_ctx* c, int KS, TView x, TView dy, int N, int H, int W, int Cin, int Cout,
-               const float* scale, float* out, float* raw, int accumulate, int oi, const ColSum* cs) {
-  const WgradWs ws = {c->part, c->partFloats, c->scratch, c->scratchFloats, c->cfg.bf16_mfma && c->wgrad_bf16, c->st, c};
-  return wgrad_run(ws, KS, x, dy, N, H, W, Cin, Cout, scale, out, raw, accumulate, oi, cs);
-}
+template int wgrad_run<TView>(const WgradWs&, int, TView, TView, int, int, int, int, int, const float*, float*, float*,
+                              int, int, const ColSum*);
+template int wgrad_run<TViewH>(const WgradWs&, int, TViewH, TView, int, int, int, int, int, const float*, float*,
+                               float*, int, int, const ColSum*);
 
 // ---------------------------------------------------------------------------
 // generator construction (GT:349-498)
@@ -895,7 +889,7 @@ int g_backward(depgan_ctx* c, const float* x, const float* z, int n) {
       DGCHECK(dg_unpool_mask(L.pool_dsrc, c->gl[L.skip_of].out, L.pool_skipgrad, L.pool_dst, n, L.H / 2, L.W / 2,
                              L.Cout, c->st));
     } else if (L.kind == G_DECONV) {
-      DGCHECK(deconv_wgrad_all(c, L, L.dout, n, L.s, c->raw_all + (L.dW - c->g.G), L.s, L.db, L.dbeta));
+      DGCHECK(deconv_wgrad_all(c, L, L.in, L.dout, n, L.s, c->raw_all + (L.dW - c->g.G), L.s, L.db, L.dbeta));
       DGCHECK(deconv_bwd_data(c, L, L.dout, n));
     }
   }
@@ -1387,38 +1381,34 @@ int depgan_create(const depgan_config* cfg, depgan_ctx** out) {
   if (rc == DG_OK && c->infer_only)
     rc = dmalloc(c, &c->logits, (size_t)cfg->batch * cfg->height * cfg->width * c->cfg.nc_out);
   if (rc == DG_OK && !c->infer_only) {
-    // slab workspace: the largest weight-gradient call of either network
+    // slab workspace: the largest weight-gradient call the backward passes make (g_backward, g_backward_bf16s,
+    // u_backward, critic_enqueue), each in every form dg_wgrad_choose can name for this context at run time: fp32 always,
+    // the bf16 pipe in a bf16_mfma context (DEPGAN_WGRAD_BF16 switches it), x in bf16 storage where the generator update
+    // can run on it (depgan_set_g_update_storage: layers past the first).  A form the rule refuses launches nothing.
     size_t mx = 0;
     const int B = cfg->batch;
+    const bool pipe = cfg->bf16_mfma != 0, store = pipe && c->cfg.nc_out == 1;
+    auto call = [&](int KS, int N, const auto& L, bool x_bf16) {
+      auto form = [&](bool bf16_pipe, bool xh) {
+        DgWgradChoice ch;
+        if (dg_wgrad_choose(KS, N, L.H, L.W, L.Cin, L.Cout, bf16_pipe, xh, &ch) == DG_OK && ch.part_floats > mx)
+          mx = ch.part_floats;
+      };
+      form(false, false);
+      if (pipe) form(true, false);
+      if (x_bf16) form(false, true);
+    };
     for (size_t i = 0; i < c->gl.size(); ++i) {
       const GLayer& L = c->gl[i];
-      size_t f = 0;
-      if (L.kind == G_CONV || L.kind == G_FILM) {
-        f = (L.Cin >= 8) ? dg_wgrad_part_floats(3, B, L.H, L.W, L.Cin, L.Cout)
-                         : dg_wgrad_small_part_floats(3, B, L.H, L.W, L.Cin, L.Cout);
-        if (cfg->bf16_mfma && L.Cin >= 8 && dg_wgrad_bf16_supported(3, L.Cin, L.Cout)) {
-          const size_t fb = dg_wgrad_bf16_part_floats(3, B, L.H, L.W, L.Cin, L.Cout);
-          if (fb > f) f = fb;
-        }
-      }
-      else if (L.kind == G_DECONV || (L.kind == G_HEAD && c->train_bn && L.Cout == 4))   // other counts: dg_head_k_wgrad
-        f = dg_wgrad_part_floats(1, B, L.H, L.W, L.Cin, L.Cout);
+      if (L.kind == G_CONV || L.kind == G_FILM) call(3, B, L, store && i > 0);
+      else if (L.kind == G_DECONV) call(1, B, L, store);   // deconv_wgrad_all, one tap at a time ...
+      else if (L.kind == G_HEAD && c->train_bn && L.Cout == 4) call(1, B, L, false);   // other counts: dg_head_k_wgrad
       if (L.kind == G_DECONV && dg_deconv_wgrad_supported(B, L.H, L.W, L.Cin, L.Cout, L.in, L.dout)) {
-        const size_t f4 = dg_deconv_wgrad_part_floats(B, L.H, L.W, L.Cin, L.Cout);   // four taps in one slab
-        if (f4 > f) f = f4;
+        const size_t f4 = dg_deconv_wgrad_part_floats(B, L.H, L.W, L.Cin, L.Cout);   // ... or four taps in one slab
+        if (f4 > mx) mx = f4;
       }
-      if (f > mx) mx = f;
     }
-    for (size_t l = 0; l < c->dl.size(); ++l) {
-      const DLayer& L = c->dl[l];
-      size_t f = (L.Cin >= 8) ? dg_wgrad_part_floats(L.KS, 3 * B, L.H, L.W, L.Cin, L.Cout)
-                              : dg_wgrad_small_part_floats(L.KS, 3 * B, L.H, L.W, L.Cin, L.Cout);
-      if (cfg->bf16_mfma && L.Cin >= 8 && dg_wgrad_bf16_supported(L.KS, L.Cin, L.Cout)) {
-        const size_t fb = dg_wgrad_bf16_part_floats(L.KS, 3 * B, L.H, L.W, L.Cin, L.Cout);
-        if (fb > f) f = fb;
-      }
-      if (f > mx) mx = f;
-    }
+    for (const DLayer& L : c->dl) call(L.KS, 3 * B, L, false);
     c->partFloats = mx;
     rc = dmalloc(c, &c->part, mx);
   }

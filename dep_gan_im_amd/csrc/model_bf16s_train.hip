@@ -45,33 +45,6 @@ int g_forward_train_bf16s(depgan_ctx* c, const float* x, const float* z) {
   return DG_OK;
 }
 
-// weight gradient with the activation operand in bf16 memory: slabs + the finish launch of wgrad_full
-static int wgrad_full_h(depgan_ctx* c, int KS, TViewH x, TView dy, int N, int H, int W, int Cin, int Cout,
-                        const float* scale, float* out, float* raw, int oi, const ColSum* cs) {
-  if (!dg_wgrad_bf16s_supported(KS, Cin, Cout)) {
-    dg_set_error("g_backward_bf16s: no bf16-staged weight gradient for k%d %d -> %d", KS, Cin, Cout);
-    return DG_ERR_UNSUPPORTED;
-  }
-  if (dg_wgrad_bf16s_part_floats(KS, N, H, W, Cin, Cout) > c->partFloats) {
-    dg_set_error("wgrad slab workspace too small");
-    return DG_ERR_ARG;
-  }
-  WgradArgsH a = wgrad_args_h(x, dy, c->part, N, H, W, Cin, Cout);
-  a.colpart = cs ? c->scratch : nullptr;
-  a.colB = cs ? cs->B : 0;
-  int nch = 0;
-  char lb[56];
-  snprintf(lb, sizeof(lb), "wgrad(bf16s) k%d b%d %dx%d %d->%d", KS, N, H, W, Cin, Cout);
-  {
-    const double px = (double)N * H * W;
-    ProfScope ps(c, 1, 2.0 * px * Cin * Cout * KS * KS, lb, px * (2.0 * Cin + 4.0 * Cout));
-    DGCHECK(dg_wgrad_bf16s(KS, a, &nch, c->st));
-  }
-  ProfScope ps(c, 2, 0.0, "slab reduce");
-  return dg_wgrad_finish(c->part, nch, KS * KS, Cin, Cout, scale, out, raw, 0, oi, cs ? c->scratch : nullptr, Cout,
-                         cs ? cs->scale : nullptr, cs ? cs->out : nullptr, cs ? cs->raw : nullptr, c->st);
-}
-
 static int bwd_data_h(depgan_ctx* c, const ConvPlan& pl, const ConvArgs& a, TViewH mask, int KS) {
   char lb[56];
   snprintf(lb, sizeof(lb), "conv(bf16,mask bf16) k%d b%d %dx%d %d->%d", KS, a.B, a.H, a.W, a.Cin, a.Cout);
@@ -83,14 +56,15 @@ static int bwd_data_h(depgan_ctx* c, const ConvPlan& pl, const ConvArgs& a, TVie
   return dg_conv_bf16_mh(pl, a, mask, c->st);
 }
 
-// conv + phase-0 BN backward given dy (g_conv_bn_bwd of model.hip); layer 0 reads the fp32 network input
+// conv + phase-0 BN backward given dy (g_conv_bn_bwd of model.hip); layer 0 reads the fp32 network input, every other
+// layer its bf16 input: the storage of x picks the weight-gradient kernel (dg_wgrad_choose)
 static int conv_bn_bwd_h(depgan_ctx* c, GLayer& L, size_t li, const float* x_user, TView dy, TView res, int n) {
   const ColSum cs = {n, L.s, L.db, L.dbeta};
   float* raw = c->raw_all + (L.dW - c->g.G);
   if (li == 0)
     return wgrad_full(c, 3, make_view(const_cast<float*>(x_user), L.H, L.W, L.Cin), dy, n, L.H, L.W, L.Cin, L.Cout, L.s,
                       L.dW, raw, 0, 0, &cs);
-  DGCHECK(wgrad_full_h(c, 3, L.hin, dy, n, L.H, L.W, L.Cin, L.Cout, L.s, L.dW, raw, 0, &cs));
+  DGCHECK(wgrad_full(c, 3, L.hin, dy, n, L.H, L.W, L.Cin, L.Cout, L.s, L.dW, raw, 0, 0, &cs));
   ConvArgs a = conv_args(dy, L.din, n, L.H, L.W, L.Cout, L.Cin);
   a.w = L.wpb[0];
   a.ep.res = res;
@@ -126,16 +100,7 @@ int g_backward_bf16s(depgan_ctx* c, const float* x, const float* z, int n) {
                                    L.Cout, c->st));
     } else if (L.kind == G_DECONV) {
       // weight gradient: the column sums of the fp32 upstream gradient, then one 1x1 launch per tap (HWOI)
-      {
-        ProfScope ps(c, 2, 0.0, "colsum");
-        DGCHECK(dg_colsum(L.dout, n, 2 * L.H, 2 * L.W, L.Cout, L.s, L.db, L.dbeta, 0, c->scratch, c->scratchFloats, c->st));
-      }
-      float* raw = c->raw_all + (L.dW - c->g.G);
-      for (int t = 0; t < 4; ++t) {
-        const size_t o = (size_t)t * L.Cout * L.Cin;
-        DGCHECK(wgrad_full_h(c, 1, L.hin, strided2(L.dout, t / 2, t % 2), n, L.H, L.W, L.Cin, L.Cout, L.s, L.dW + o,
-                             raw + o, 1, nullptr));
-      }
+      DGCHECK(deconv_wgrad_all(c, L, L.hin, L.dout, n, L.s, c->raw_all + (L.dW - c->g.G), L.s, L.db, L.dbeta));
       // backward-data: one 1x1 convolution over the four strided grids of the upstream gradient (deconv_bwd_data)
       if (!L.wpb_all) { dg_set_error("g_backward_bf16s: %s has no gathered backward-data panel", L.name.c_str()); return DG_ERR_UNSUPPORTED; }
       ConvArgs a = conv_args(null_view(), L.din, n, L.H, L.W, L.Cout, L.Cin);

@@ -16,6 +16,37 @@ int op_pack_jobs(PackJob* jobs, int n, hipStream_t st) {
   return dg_pack_weights_batch(jd.as<PackJob>(), n, nb, st);
 }
 
+static int op_alloc(DevTmp* t, size_t floats, const char* who) {
+  if (t->alloc((floats ? floats : 1) * sizeof(float)) != DG_OK) {
+    dg_set_error("%s: out of device memory (%zu floats)", who, floats);
+    return DG_ERR_HIP;
+  }
+  return DG_OK;
+}
+
+// The weight gradient of an operator entry as the model runs it (wgrad_run), on workspaces of this call sized from the
+// choice: the slabs, and for column sums one partial row per col_rows or the scratch of the streaming pass.
+template <typename XV>
+int op_wgrad(const char* who, int KS, XV x, TView dy, int B, int H, int W, int Cin, int Cout, bool bf16,
+             const float* scale, float* dw, float* raw, int accumulate, int oi, const ColSum* cs, hipStream_t st) {
+  DgWgradChoice ch;
+  DGCHECK(dg_wgrad_choose(KS, B, H, W, Cin, Cout, bf16, std::is_same<XV, TViewH>::value, &ch));
+  WgradWs ws;
+  memset(&ws, 0, sizeof(ws));
+  ws.partFloats = ch.part_floats;
+  ws.scratchFloats = !cs ? 0 : ch.col_rows ? (size_t)ch.col_rows * Cout : dg_colsum_scratch(cs->B, H, W, Cout);
+  ws.bf16 = bf16;
+  ws.st = st;
+  DevTmp part(st), scratch(st);
+  DGCHECK(op_alloc(&part, ws.partFloats, who));
+  DGCHECK(op_alloc(&scratch, ws.scratchFloats, who));
+  ws.part = part.as<float>();
+  ws.scratch = scratch.as<float>();
+  return wgrad_run(ws, KS, x, dy, B, H, W, Cin, Cout, scale, dw, raw, accumulate, oi, cs);
+}
+template int op_wgrad<TViewH>(const char*, int, TViewH, TView, int, int, int, int, int, bool, const float*, float*, float*,
+                              int, int, const ColSum*, hipStream_t);   // op_entries_bf16s.hip
+
 extern "C" {
 
 // ---- single operators (unit tests) ----
@@ -105,29 +136,16 @@ int depgan_op_conv2d_bwd_data(const float* dy, const float* w_hwio, float* dx, i
 }
 int depgan_op_conv2d_wgrad(const float* x, const float* dy, float* dw, int B, int H, int W, int Cin, int Cout, int KS,
                            void* stream) {
-  hipStream_t st = (hipStream_t)stream;
-  const bool big = (Cin % 4 == 0 && Cout % 4 == 0 && Cin >= 8);
-  const size_t pf = big ? dg_wgrad_part_floats(KS, B, H, W, Cin, Cout) : dg_wgrad_small_part_floats(KS, B, H, W, Cin, Cout);
-  DevTmp part(st);
-  DGCHECK(part.alloc(pf * sizeof(float)));
-  WgradArgs a = wgrad_args(make_view(const_cast<float*>(x), H, W, Cin), make_view(const_cast<float*>(dy), H, W, Cout),
-                           part.as<float>(), B, H, W, Cin, Cout);
-  int nch = 0;
-  DGCHECK(big ? dg_wgrad(KS, a, &nch, st) : dg_wgrad_small(KS, a, &nch, st));
-  return dg_wgrad_reduce(a.part, nch, KS * KS, Cin, Cout, nullptr, dw, nullptr, 0, 0, st);
+  return op_wgrad("op_conv2d_wgrad", KS, make_view(const_cast<float*>(x), H, W, Cin),
+                  make_view(const_cast<float*>(dy), H, W, Cout), B, H, W, Cin, Cout, false, nullptr, dw, nullptr, 0, 0,
+                  nullptr, (hipStream_t)stream);
 }
 int depgan_op_conv2d_wgrad_bf16(const float* x, const float* dy, float* dw, int B, int H, int W, int Cin, int Cout,
                                 int KS, void* stream) {
-  hipStream_t st = (hipStream_t)stream;
   if (!dg_wgrad_bf16_supported(KS, Cin, Cout)) { dg_set_error("op_wgrad_bf16: shape not covered"); return DG_ERR_UNSUPPORTED; }
-  const size_t pf = dg_wgrad_bf16_part_floats(KS, B, H, W, Cin, Cout);
-  DevTmp part(st);
-  DGCHECK(part.alloc(pf * sizeof(float)));
-  WgradArgs a = wgrad_args(make_view(const_cast<float*>(x), H, W, Cin), make_view(const_cast<float*>(dy), H, W, Cout),
-                           part.as<float>(), B, H, W, Cin, Cout);
-  int nch = 0;
-  DGCHECK(dg_wgrad_bf16(KS, a, &nch, st));
-  return dg_wgrad_reduce(a.part, nch, KS * KS, Cin, Cout, nullptr, dw, nullptr, 0, 0, st);
+  return op_wgrad("op_conv2d_wgrad_bf16", KS, make_view(const_cast<float*>(x), H, W, Cin),
+                  make_view(const_cast<float*>(dy), H, W, Cout), B, H, W, Cin, Cout, true, nullptr, dw, nullptr, 0, 0,
+                  nullptr, (hipStream_t)stream);
 }
 int depgan_op_deconv2x2(const float* in, const float* w_hwoi, const float* bias, const float* scale,
                         const float* shift, float* out, int B, int H, int W, int Cin, int Cout, int relu,
@@ -205,13 +223,6 @@ int depgan_eval_counts(const float* x, int nicg, const double* pred, const float
 
 // ---- learning-phase-1 operators (train_ops.hip), as uresnet.hip calls them; each view is NHWC with the strides
 // (sB, sY, sX) in floats and channel stride 1 ----
-static int op_alloc(DevTmp* t, size_t floats, const char* who) {
-  if (t->alloc((floats ? floats : 1) * sizeof(float)) != DG_OK) {
-    dg_set_error("%s: out of device memory (%zu floats)", who, floats);
-    return DG_ERR_HIP;
-  }
-  return DG_OK;
-}
 static size_t op_scratch(long scratch_floats, size_t need) { return scratch_floats > 0 ? (size_t)scratch_floats : need; }
 
 // ---- the fp32 convolution kernels with the whole fused epilogue and strided views (unit tests) ----
@@ -414,28 +425,13 @@ int depgan_op_conv2d_wgrad_ex(const float* x, long xsB, long xsY, long xsX, cons
     dg_set_error("op_conv2d_wgrad_ex: bf16 must be 0 or 1; column sums need colout or colraw and 1 <= colB <= B");
     return DG_ERR_ARG;
   }
-  const bool mfma = Cin % 4 == 0 && Cout % 4 == 0 && Cin >= 8;
-  if (bf16 && !(mfma && dg_wgrad_bf16_supported(KS, Cin, Cout))) {
+  if (bf16 && !dg_wgrad_bf16_supported(KS, Cin, Cout)) {
     dg_set_error("op_conv2d_wgrad_ex: the bf16 weight-gradient kernel does not cover %d -> %d", Cin, Cout);
     return DG_ERR_UNSUPPORTED;
   }
-  hipStream_t st = (hipStream_t)stream;
-  WgradWs ws;
-  memset(&ws, 0, sizeof(ws));
-  ws.partFloats = bf16 ? dg_wgrad_bf16_part_floats(KS, B, H, W, Cin, Cout)
-                  : mfma ? dg_wgrad_part_floats(KS, B, H, W, Cin, Cout) : dg_wgrad_small_part_floats(KS, B, H, W, Cin, Cout);
-  // one partial column-sum row per slab (MFMA kernels), or the scratch of the streaming pass (edge kernels)
-  ws.scratchFloats = mfma ? ws.partFloats / ((size_t)KS * KS * Cin) : (cols ? dg_colsum_scratch(colB, H, W, Cout) : 0);
-  ws.bf16 = bf16 != 0;
-  ws.st = st;
-  DevTmp part(st), scratch(st);
-  DGCHECK(op_alloc(&part, ws.partFloats, "op_conv2d_wgrad_ex"));
-  DGCHECK(op_alloc(&scratch, ws.scratchFloats, "op_conv2d_wgrad_ex"));
-  ws.part = part.as<float>();
-  ws.scratch = scratch.as<float>();
   const ColSum cs = {colB, colscale, colout, colraw};
-  return wgrad_run(ws, KS, op_view(x, xsB, xsY, xsX), op_view(dy, dsB, dsY, dsX), B, H, W, Cin, Cout, scale, dw, raw, accumulate,
-                   oi, cols ? &cs : nullptr);
+  return op_wgrad("op_conv2d_wgrad_ex", KS, op_view(x, xsB, xsY, xsX), op_view(dy, dsB, dsY, dsX), B, H, W, Cin, Cout,
+                  bf16 != 0, scale, dw, raw, accumulate, oi, cols ? &cs : nullptr, (hipStream_t)stream);
 }
 
 // host only: what the launcher of `kernel` would do with this shape, from the launcher's own chunking function
@@ -444,15 +440,23 @@ int depgan_debug_wgrad_plan(int kernel, int KS, int B, int H, int W, int Cin, in
     dg_set_error("debug_wgrad_plan: null or non-positive argument");
     return DG_ERR_ARG;
   }
-  switch (kernel) {
-    case 0: return dg_wgrad_plan(KS, B, H, W, Cin, Cout, out);
-    case 1: return dg_wgrad_small_plan(KS, B, H, W, Cin, Cout, out);
-    case 2: return dg_wgrad_bf16_plan(KS, B, H, W, Cin, Cout, out);
-    case 3: return dg_wgrad_bf16s_plan(KS, B, H, W, Cin, Cout, out);
-    case 4: return dg_deconv_wgrad_plan(B, H, W, Cin, Cout, out);
-  }
+  if (kernel == DG_WG_DECONV) return dg_deconv_wgrad_plan(B, H, W, Cin, Cout, out);
+  if (kernel >= DG_WG_F32 && kernel <= DG_WG_BF16S) return dg_wgrad_plan_of(kernel, KS, B, H, W, Cin, Cout, out);
   dg_set_error("debug_wgrad_plan: kernel %d is not one of 0..4", kernel);
   return DG_ERR_ARG;
+}
+
+// host only: the kernel wgrad_run launches for this shape, pipe and storage of x, and what the launch needs
+int depgan_debug_wgrad_choice(int KS, int B, int H, int W, int Cin, int Cout, int bf16_pipe, int x_bf16, long out[4]) {
+  if (!out || B < 1 || H < 1 || W < 1 || Cin < 1 || Cout < 1 || (bf16_pipe != 0 && bf16_pipe != 1) ||
+      (x_bf16 != 0 && x_bf16 != 1)) {
+    dg_set_error("debug_wgrad_choice: null or non-positive argument, or a flag that is not 0 or 1");
+    return DG_ERR_ARG;
+  }
+  DgWgradChoice ch;
+  DGCHECK(dg_wgrad_choose(KS, B, H, W, Cin, Cout, bf16_pipe != 0, x_bf16 != 0, &ch));
+  out[0] = ch.kernel; out[1] = ch.nchunks; out[2] = (long)ch.part_floats; out[3] = ch.col_rows;
+  return DG_OK;
 }
 
 

@@ -170,22 +170,9 @@ int depgan_op_conv2d_wgrad_bf16s(const void* x, long xsB, long xsY, long xsX, co
   }
   if (KS != 1 && KS != 3) { dg_set_error("op_conv2d_wgrad_bf16s: KS must be 1 or 3"); return DG_ERR_ARG; }
   if (!dg_wgrad_bf16s_supported(KS, Cin, Cout)) { dg_set_error("op_conv2d_wgrad_bf16s: shape not covered (%d -> %d)", Cin, Cout); return DG_ERR_UNSUPPORTED; }
-  hipStream_t st = (hipStream_t)stream;
-  const size_t pf = dg_wgrad_bf16s_part_floats(KS, B, H, W, Cin, Cout);
-  const size_t cf = pf / ((size_t)KS * KS * Cin * Cout) * Cout;
-  DevTmp part(st), colt(st);
-  DGCHECK(part.alloc(pf * sizeof(float)));
-  if (colsum && colt.alloc(cf * sizeof(float)) != DG_OK) {
-    dg_set_error("op_conv2d_wgrad_bf16s: out of memory");
-    return DG_ERR_HIP;
-  }
-  float* const col = colt.as<float>();
-  WgradArgsH a = wgrad_args_h(op_view_h(x, xsB, xsY, xsX), op_view(dy, dsB, dsY, dsX), part.as<float>(), B, H, W, Cin, Cout);
-  a.colpart = col;
-  a.colB = col ? B : 0;
-  int nch = 0;
-  DGCHECK(dg_wgrad_bf16s(KS, a, &nch, st));
-  return dg_wgrad_finish(a.part, nch, KS * KS, Cin, Cout, nullptr, dw, nullptr, 0, oi, col, Cout, nullptr, colsum, nullptr, st);
+  const ColSum cs = {B, nullptr, colsum, nullptr};   // over all samples: the entry knows no other form
+  return op_wgrad("op_conv2d_wgrad_bf16s", KS, op_view_h(x, xsB, xsY, xsX), op_view(dy, dsB, dsY, dsX), B, H, W, Cin, Cout,
+                  true, nullptr, dw, nullptr, 0, oi, colsum ? &cs : nullptr, (hipStream_t)stream);
 }
 
 // KS = 3: dx = mask(conv_bwd_data(dy, w_hwio) + res); KS = 1 with deconv = 1: dy is the (2H, 2W) upstream gradient of a

@@ -299,7 +299,7 @@ static int u_backward(depgan_ctx* c, const float* x, const float* z, int n) {
       const int Ho = 2 * L.H, Wo = 2 * L.W;
       TView draw;
       DGCHECK(u_bn_bwd(c, L, L.dout, Ho, Wo, n, 1.0f, &draw));
-      DGCHECK(deconv_wgrad_all(c, L, draw, n, nullptr, nullptr, nullptr, L.db, nullptr));
+      DGCHECK(deconv_wgrad_all(c, L, L.in, draw, n, nullptr, nullptr, nullptr, L.db, nullptr));
       DGCHECK(deconv_bwd_data(c, L, draw, n));
     }
   }

@@ -398,15 +398,6 @@ static void chunking(const WVar& v, int B, int H, int W, int Cin, int Cout, int*
   *nchunks = cdiv(*nTiles, *tilesPerChunk);
 }
 
-size_t dg_wgrad_part_floats(int KS, int B, int H, int W, int Cin, int Cout) {
-  WVar v;
-  pick_variant(KS, Cin, Cout, &v);
-  int nTiles, tpc, nch, gy;
-  chunking(v, B, H, W, Cin, Cout, &nTiles, &tpc, &nch, &gy);
-  const size_t slab = (size_t)KS * KS * Cin * Cout;
-  return (size_t)nch * slab;
-}
-
 // the launch plan of dg_wgrad for a shape, without launching (depgan_debug_wgrad_plan)
 int dg_wgrad_plan(int KS, int B, int H, int W, int Cin, int Cout, int out[4]) {
   if ((Cin % 4) || (Cout % 4)) {
@@ -569,10 +560,4 @@ int dg_wgrad_finish_rows(const float* part, int nchunks, int ntaps, int Cin, int
                        out, raw, accumulate, oi, nbr, cf);
   HIPCHECK(hipGetLastError());
   return DG_OK;
-}
-
-int dg_wgrad_reduce(const float* part, int nchunks, int ntaps, int Cin, int Cout, const float* scale, float* out,
-                    float* raw, int accumulate, int oi, hipStream_t st) {
-  return dg_wgrad_finish(part, nchunks, ntaps, Cin, Cout, scale, out, raw, accumulate, oi, nullptr, 0, nullptr, nullptr,
-                         nullptr, st);
 }

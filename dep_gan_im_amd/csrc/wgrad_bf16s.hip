@@ -29,10 +29,6 @@ bool dg_wgrad_bf16s_supported(int KS, int Cin, int Cout) {
   return (KS == 1 || KS == 3) && Cin >= 8 && (Cin % 8) == 0 && (Cout % 4) == 0;
 }
 
-size_t dg_wgrad_bf16s_part_floats(int KS, int B, int H, int W, int Cin, int Cout) {
-  return (KS == 1 || KS == 3) ? part_floats(KS, B, H, W, Cin, Cout) : 0;
-}
-
 // the launch plan of dg_wgrad_bf16s for a shape, without launching (depgan_debug_wgrad_plan)
 int dg_wgrad_bf16s_plan(int KS, int B, int H, int W, int Cin, int Cout, int out[4]) {
   if (!dg_wgrad_bf16s_supported(KS, Cin, Cout)) {

@@ -939,6 +939,17 @@ int depgan_op_conv2d_wgrad_ex(const float* x, long xsB, long xsY, long xsX, cons
  * per workgroup, workgroups along x, gridDim.y}.  A shape the launcher refuses returns the launcher's status; a null
  * `out`, a non-positive size or an unknown `kernel` status 1. */
 int depgan_debug_wgrad_plan(int kernel, int KS, int B, int H, int W, int Cin, int Cout, int out[4]);
+/* Host only (no launch, no allocation): the slab kernel every weight gradient of the library takes for a shape -- the
+ * model's and the depgan_op_conv2d_wgrad* entries' -- with bf16_pipe = 1 where the contraction may run on the bf16 matrix
+ * pipe and x_bf16 = 1 where the activation operand lies in bf16 memory.  With mfma = Cin % 4 == 0 && Cout % 4 == 0 &&
+ * Cin >= 8: x_bf16 takes kernel 3 or is refused with status 3 (the storage types are not mixed); else bf16_pipe && mfma
+ * takes kernel 2 where wgrad_bf16.hip covers the shape; else mfma takes kernel 0; else kernel 1.
+ * out = {kernel (the numbering above), chunks (out[2] of depgan_debug_wgrad_plan for that kernel), floats of the slab
+ * workspace (chunks * KS * KS * Cin * Cout), partial column-sum rows of Cout floats the launch writes when column sums
+ * are asked for (chunks; 0 for kernel 1, whose column sums are a streaming pass of their own)}.  A shape the chosen
+ * launcher refuses returns the launcher's status; a null `out`, a non-positive size or a flag that is not 0 or 1
+ * status 1.  A refusal writes nothing. */
+int depgan_debug_wgrad_choice(int KS, int B, int H, int W, int Cin, int Cout, int bf16_pipe, int x_bf16, long out[4]);
 
 /* Learning-phase-1 operators (the DEP-UResNet training step's batch-statistics BatchNorm, Dropout, softmax and
  * cross-entropy), each the internal function uresnet.hip calls.  Device pointers; every NHWC view has the float strides
