@@ -148,6 +148,25 @@ class LearningRateScheduler(Callback):
             print("Epoch %05d: LearningRateScheduler setting learning rate to %g." % (epoch + 1, float(lr)))
 
 
+class BoundaryWeightScheduler(Callback):
+    """At the start of every epoch boundary_weight <- schedule(epoch, boundary_weight), for a model compiled with
+    boundary_loss=True: the boundary term is used with a weight that starts small and rises.  fit records the weight
+    every epoch trained with in history['boundary_weight']."""
+
+    def __init__(self, schedule, verbose=0):
+        self.schedule, self.verbose = schedule, verbose
+
+    def on_epoch_begin(self, epoch):
+        if self.model.boundary_weight is None:
+            raise ValueError("BoundaryWeightScheduler: the model was not compiled with boundary_loss=True")
+        w = self.schedule(epoch, float(self.model.boundary_weight))
+        if isinstance(w, bool) or not isinstance(w, (int, float, np.integer, np.floating)):
+            raise ValueError('The output of the "schedule" function should be float.')
+        self.model.set_boundary_weight(float(w))
+        if self.verbose:
+            print("Epoch %05d: BoundaryWeightScheduler setting boundary weight to %g." % (epoch + 1, float(w)))
+
+
 class ModelCheckpoint(Callback):
     """keras.callbacks.ModelCheckpoint through model.save_weights: after every epoch, or with save_best_only after the
     epochs whose monitor is the best so far.  `path` may hold {epoch} (counted from 1) and the names in logs."""

@@ -218,7 +218,14 @@ struct depgan_ctx {
   struct {
     DgCeSetting ce;
     DgDiceSetting dice;
+    DgBoundarySetting boundary;
   } loss;
+  // the boundary mode's buffers, allocated when the mode is first set and never inside a step: phi (batch, H, W, nc_out),
+  // the row pass's 16-bit maps and the loss pass's block partials
+  float* bl_phi = nullptr;
+  void* bl_rows = nullptr;
+  size_t bl_rows_bytes = 0;
+  double* bl_part = nullptr;
   // what came back with the loss of the last depgan_uresnet_* call made under that setting: the census table (row =
   // true class, row-major nc_out x nc_out), the label pre-pass counts of the weighted path ([0] den, [1] ignored, [2]
   // out of range, [3 + k] class k), and the Dice sums I_k, P_k, T_k (3 nc_out, packed) with the Dice term.  Cleared:
@@ -230,6 +237,9 @@ struct depgan_ctx {
     long long counts[DEPGAN_LABEL_NCOUNT];
     double dice_sums[3 * DEPGAN_MAX_HEAD_CLASSES];
     float dice_loss = 0.f;
+    // the boundary mode: L_B and M of the last call made with it on; cleared when the mode is set anew or switched off
+    bool boundary_valid = false;
+    double boundary_loss = 0.0, boundary_M = 0.0;
   } last;
   float *ones1k = nullptr, *zeros1k = nullptr;
   float *n_mean0 = nullptr, *n_rstd0 = nullptr, *n_mean1 = nullptr, *n_rstd1 = nullptr, *n_meanh = nullptr,

@@ -653,6 +653,64 @@ int depgan_op_dice_loss(const float* probs, const float* onehot, const unsigned 
   *loss_host = h.loss;
   return DG_OK;
 }
+int depgan_op_signed_distance(const float* onehot, const unsigned char* codes, int ignore_code, int n, int H, int W, int C,
+                              const int* class_on_host, double sy, double sx, double inside_offset, float* phi_out,
+                              void* stream) {
+  DGCHECK(dg_signed_distance_check("op_signed_distance", n, H, W, C, sy, sx, inside_offset));
+  if (!phi_out || ((uintptr_t)phi_out & 3) || (!onehot == !codes) || ((uintptr_t)onehot & 3)) {
+    dg_set_error("op_signed_distance: null or misaligned phi_out, or not exactly one of onehot and codes (4-byte aligned)");
+    return DG_ERR_ARG;
+  }
+  if (ignore_code < -1 || ignore_code > 255) {
+    dg_set_error("op_signed_distance: ignore code %d (-1 for none, else a byte value 0..255)", ignore_code);
+    return DG_ERR_ARG;
+  }
+  unsigned mask = 0;
+  for (int k = 0; k < C; ++k) mask |= ((!class_on_host || class_on_host[k]) ? 1u : 0u) << k;
+  if (!mask) { dg_set_error("op_signed_distance: every class is switched off"); return DG_ERR_ARG; }
+  hipStream_t st = (hipStream_t)stream;
+  const size_t bytes = dg_signed_distance_scratch_bytes(n, H, W, C);
+  DevTmp scratch(st);
+  DGCHECK(op_alloc(&scratch, (bytes + 3) / 4, "op_signed_distance"));
+  return dg_signed_distance(DgLabels{onehot, codes}, ignore_code, n, H, W, C, mask, sy, sx, inside_offset, phi_out,
+                            scratch.p, bytes, st);
+}
+int depgan_op_boundary_loss(const float* probs, const float* phi, const float* onehot, const unsigned char* codes,
+                            int ignore_code, const float* class_coef_host, int ncoef, float boundary_coef,
+                            float* dz_inout, double* loss_host, long P, int C, void* stream) {
+  if (!loss_host) { dg_set_error("op_boundary_loss: null loss_host"); return DG_ERR_ARG; }
+  DGCHECK(dg_boundary_check("op_boundary_loss", boundary_coef, class_coef_host, ncoef, C));
+  const DgLabels lab{onehot, codes};
+  DGCHECK(dg_boundary_operands_check("op_boundary_loss", probs, phi, lab, ignore_code, dz_inout, P, C));
+  hipStream_t st = (hipStream_t)stream;
+  float coef[DEPGAN_MAX_HEAD_CLASSES];
+  for (int k = 0; k < C; ++k) coef[k] = class_coef_host ? class_coef_host[k] : 1.0f / (float)C;
+  // the block partials (doubles), what the finish stage leaves, then -- with an ignore code -- the label pre-pass's
+  // counts and its scratch: M = P - the pixels without a true class - the codes out of range.  Without one M = P
+  const size_t part = dg_boundary_scratch(P) * 2, outf = sizeof(DgBoundaryDev) / sizeof(float);
+  const size_t cntf = 2 * DEPGAN_LABEL_NCOUNT, lcf = ignore_code >= 0 ? dg_label_counts_scratch(P, C) : 0;
+  DevTmp scratch(st);
+  DGCHECK(op_alloc(&scratch, part + outf + cntf + lcf, "op_boundary_loss"));
+  double* partials = scratch.as<double>();
+  DgBoundaryDev* out = reinterpret_cast<DgBoundaryDev*>(scratch.as<float>() + part);
+  unsigned long long* counts = nullptr;
+  if (ignore_code >= 0) {
+    counts = reinterpret_cast<unsigned long long*>(scratch.as<float>() + part + outf);
+    DGCHECK(dg_label_counts(onehot, codes, P, C, nullptr, ignore_code, counts, scratch.as<float>() + part + outf + cntf,
+                            lcf, st));
+  }
+  DGCHECK(dg_boundary_loss(probs, phi, lab, ignore_code, coef, boundary_coef, counts, dz_inout, out, P, C, partials,
+                           dg_boundary_scratch(P), st));
+  DgBoundaryDev h;
+  if (hipMemcpyAsync(&h, out, sizeof(h), hipMemcpyDeviceToHost, st) != hipSuccess ||
+      hipStreamSynchronize(st) != hipSuccess) {
+    dg_set_error("op_boundary_loss: copy back failed");
+    return DG_ERR_HIP;
+  }
+  loss_host[0] = h.loss;
+  loss_host[1] = h.M;
+  return DG_OK;
+}
 int depgan_op_softmax_ce4(const float* logits, const float* onehot, float* probs, float* dz, float* loss_sum, long P,
                           void* stream) {
   return depgan_op_softmax_ce(logits, onehot, nullptr, probs, dz, loss_sum, P, 4, stream);

@@ -156,6 +156,47 @@ size_t dg_dice_scratch(long P, int C);
 int dg_dice_loss(const float* probs, DgLabels lab, int ignore_code, const DgDiceSetting& set, float* dz, DgDiceDev* out,
                  long P, int C, float* scratch, size_t scratch_floats, hipStream_t st);
 
+// The boundary loss (boundary_loss.hip; include/depgan.h, depgan_uresnet_set_boundary_loss, states the rule).  It runs
+// behind the cross-entropy and the Dice mode on the same stream: the signed distance maps of the call's labels, then one
+// pass over the stored probabilities that adds its gradient to dz.  The setting, on the host: c: C class coefficients
+// (finite, >= 0, at least one > 0; a class with c_k == 0 gets no map), coef = boundary_coef finite >= 0, the spacings
+// finite > 0 and inside_offset in [0, min(sy, sx)].
+struct DgBoundarySetting {
+  bool on = false;
+  float coef = 1.f;
+  float c[DEPGAN_MAX_HEAD_CLASSES];
+  double sy = 1.0, sx = 1.0, inside_offset = 0.0;
+  unsigned class_mask(int C) const {
+    unsigned m = 0;
+    for (int k = 0; k < C; ++k) m |= (c[k] != 0.f ? 1u : 0u) << k;
+    return m;
+  }
+};
+// what the finish stage leaves on the device: L_B = sum / M (0.0 for M = 0) and M, the pixels that take part
+struct DgBoundaryDev {
+  double loss, M;
+};
+// the values of a setting, without a HIP call: coef null or n == C values
+int dg_boundary_check(const char* who, float boundary_coef, const float* coef, int n, int C);
+// the geometry of a signed distance call, without a HIP call: n >= 1, H and W in 1..4096, n H W < 2^31, n H and the
+// 64 x 16 tiles of all n C maps each < 2^24 (the two grids), C in 2..8
+int dg_signed_distance_check(const char* who, long n, int H, int W, int C, double sy, double sx, double inside_offset);
+// phi (n, H, W, C) float32 of n label slices: the classes of class_mask get their map, the others 0.  ignore_code as
+// dg_dice_loss takes it.  Two launches whatever n; dg_signed_distance_scratch_bytes(n, H, W, classes) of scratch, where
+// `classes` is at least the number of bits set in class_mask (2-byte aligned).
+size_t dg_signed_distance_scratch_bytes(long n, int H, int W, int C);
+int dg_signed_distance(DgLabels lab, int ignore_code, long n, int H, int W, int C, unsigned class_mask, double sy,
+                       double sx, double inside_offset, float* phi, void* scratch, size_t scratch_bytes, hipStream_t st);
+// L_B and, with dz, dz += boundary_coef p (g - sum p g).  counts: null for M = P, else the label pre-pass counts
+// (DgCeDev::counts) on the device, M = P - counts[1] - counts[2].  dg_boundary_scratch(P) doubles of scratch (at most
+// 1024), 8-byte aligned.  One partial per block, added in index order by one block: no atomics, nothing to zero.
+int dg_boundary_operands_check(const char* who, const float* probs, const float* phi, DgLabels lab, int ignore_code,
+                               const float* dz, long P, int C);
+size_t dg_boundary_scratch(long P);
+int dg_boundary_loss(const float* probs, const float* phi, DgLabels lab, int ignore_code, const float* class_coef,
+                     float boundary_coef, const unsigned long long* counts, float* dz, DgBoundaryDev* out, long P, int C,
+                     double* scratch, size_t scratch_doubles, hipStream_t st);
+
 // the 1x1 head to K = 2..8 class logits on dense (P, K) rows; a, mask and din are pixel rows of C channels at strides
 // ld* (multiples of 4 floats, 16-byte aligned), w is (C, K) dense, C / 4 a power of two <= 64
 int dg_head_k_fwd(const float* a, long ld, const float* w, const float* b, float* logits, long P, int C, int K,

@@ -46,8 +46,10 @@ static UNoiseBn noise_bn(Net& g, const std::string& nm) {
 struct ULossHost {
   DgCeDev ce;
   DgDiceDev dice;   // the Dice mode: the 3 C sums and the Dice term (the copy stops in front of A and B)
+  DgBoundaryDev bl; // the boundary mode: L_B and M (the copy then runs to the end of the struct)
 };
 static_assert(offsetof(ULossHost, dice) % 8 == 0, "the Dice sums are doubles");
+static_assert(offsetof(ULossHost, bl) % 8 == 0, "L_B and M are doubles");
 
 int uresnet_build(depgan_ctx* c) {
   const int B = c->cfg.batch;
@@ -351,13 +353,26 @@ static int u_softmax_ce_only(depgan_ctx* c, DgLabels lab, long P) {
 // the ignore code with codes, the all-zero row with one-hot labels.  grad = false (eval): no gradient pass
 static int u_softmax_ce(depgan_ctx* c, DgLabels lab, long P, bool grad) {
   DGCHECK(u_softmax_ce_only(c, lab, P));
-  if (c->loss.dice.form == DEPGAN_DICE_OFF) return DG_OK;
-  ProfScope ps(c, 2, 0.0, "dice loss");
   const DgCeSetting& ce = c->loss.ce;
   const int ignore = !ce.weighted ? -1 : (lab.codes ? ce.ignore : 0);
-  return dg_dice_loss(c->attr.p, lab, ignore, c->loss.dice, grad ? c->dz : nullptr,
-                      &reinterpret_cast<ULossHost*>(c->loss_dev)->dice, P, c->cfg.nc_out, c->scratch, c->scratchFloats,
-                      c->st);
+  ULossHost* dev = reinterpret_cast<ULossHost*>(c->loss_dev);
+  if (c->loss.dice.form != DEPGAN_DICE_OFF) {
+    ProfScope ps(c, 2, 0.0, "dice loss");
+    DGCHECK(dg_dice_loss(c->attr.p, lab, ignore, c->loss.dice, grad ? c->dz : nullptr, &dev->dice, P, c->cfg.nc_out,
+                         c->scratch, c->scratchFloats, c->st));
+  }
+  // The boundary mode, last: the signed distance maps of this call's labels (two launches whatever n), then one pass
+  // that adds its gradient to what the cross-entropy and the Dice mode left in dz, and the one-block sum.  The same
+  // pixels take part as in the Dice term; M is read on the device from the label pre-pass's counts
+  if (!c->loss.boundary.on) return DG_OK;
+  ProfScope ps(c, 2, 0.0, "boundary loss");
+  const DgBoundarySetting& b = c->loss.boundary;
+  const int C = c->cfg.nc_out;
+  DGCHECK(dg_signed_distance(lab, ignore, P / ((long)c->cfg.height * c->cfg.width), c->cfg.height, c->cfg.width, C,
+                             b.class_mask(C), b.sy, b.sx, b.inside_offset, c->bl_phi, c->bl_rows, c->bl_rows_bytes,
+                             c->st));
+  return dg_boundary_loss(c->attr.p, c->bl_phi, lab, ignore, b.c, b.coef, ce.weighted ? dev->ce.counts : nullptr,
+                          grad ? c->dz : nullptr, &dev->bl, P, C, c->bl_part, dg_boundary_scratch(P), c->st);
 }
 
 // the one synchronisation of a call: what the launches under the setting left in loss_dev comes back in one copy -- the
@@ -370,8 +385,10 @@ static int u_loss_to_host(depgan_ctx* c, const char* who, long P, float* loss_ho
   ULossHost h;
   h.ce.loss = 0.f;
   h.ce.bad = 0;
-  const size_t bytes = dice.form != DEPGAN_DICE_OFF ? offsetof(ULossHost, dice) + offsetof(DgDiceDev, A)
-                                                    : DgCeDev::bytes(C, ce);
+  const DgBoundarySetting& bl = c->loss.boundary;
+  const size_t bytes = bl.on ? sizeof(ULossHost)
+                             : dice.form != DEPGAN_DICE_OFF ? offsetof(ULossHost, dice) + offsetof(DgDiceDev, A)
+                                                            : DgCeDev::bytes(C, ce);
   HIPCHECK(hipMemcpyAsync(&h, c->loss_dev, bytes, hipMemcpyDeviceToHost, c->st));
   HIPCHECK(hipStreamSynchronize(c->st));
   if (ce.census) {
@@ -393,6 +410,12 @@ static int u_loss_to_host(depgan_ctx* c, const char* who, long P, float* loss_ho
     c->last.dice_loss = h.dice.loss;
     c->last.dice_valid = true;
     loss = dice.ce_coef * loss + dice.dice_coef * h.dice.loss;
+  }
+  if (bl.on) {
+    c->last.boundary_loss = h.bl.loss;
+    c->last.boundary_M = h.bl.M;
+    c->last.boundary_valid = true;
+    loss = loss + bl.coef * (float)h.bl.loss;
   }
   if (loss_host) *loss_host = loss;
   if (h.ce.bad) {
@@ -438,7 +461,9 @@ static int u_step(depgan_ctx* c, const char* who, const float* x, const float* z
   const long P = (long)n * c->cfg.height * c->cfg.width;
   const bool ce_empty = c->loss.ce.weighted_path() && c->last.counts[0] == 0;
   const bool dice_empty = c->loss.ce.weighted && c->last.counts[1] + c->last.counts[2] == P;
-  if (c->loss.dice.form == DEPGAN_DICE_OFF ? ce_empty : dice_empty) return refresh_generator_bn(c);
+  // The boundary mode follows the Dice mode's rule: its term has a gradient wherever a pixel takes part
+  const bool regional_only = c->loss.dice.form == DEPGAN_DICE_OFF && !c->loss.boundary.on;
+  if (regional_only ? ce_empty : dice_empty) return refresh_generator_bn(c);
   return depgan_apply_adam(c, DEPGAN_NET_G);
 }
 
@@ -567,6 +592,76 @@ int depgan_uresnet_last_dice_sums(depgan_ctx* c, double out_host[3 * DEPGAN_MAX_
   memcpy(out_host, c->last.dice_sums, (size_t)3 * c->cfg.nc_out * sizeof(double));
   if (classes) *classes = c->cfg.nc_out;
   if (dice_loss) *dice_loss = c->last.dice_loss;
+  return DG_OK;
+}
+
+int depgan_uresnet_set_boundary_loss(depgan_ctx* c, int on, float boundary_coef, const float* class_coef_host, int n,
+                                     double sy, double sx, double inside_offset) {
+  const char* who = "depgan_uresnet_set_boundary_loss";
+  if (!c) { dg_set_error("%s: null context", who); return DG_ERR_ARG; }
+  if (on != 0 && on != 1) { dg_set_error("%s: on must be 0 or 1, got %d", who, on); return DG_ERR_ARG; }
+  if (!on) {
+    c->loss.boundary.on = c->last.boundary_valid = false;
+    return DG_OK;
+  }
+  DGCHECK(u_check(c, who));
+  const int C = c->cfg.nc_out, B = c->cfg.batch, H = c->cfg.height, W = c->cfg.width;
+  DGCHECK(dg_boundary_check(who, boundary_coef, class_coef_host, n, C));
+  DGCHECK(dg_signed_distance_check(who, B, H, W, C, sy, sx, inside_offset));
+  // the buffers, once: phi, the row pass's maps for every class (so that other coefficients need no other buffer) and
+  // the block partials.  Setting the mode again finds them and allocates nothing.  Each pointer is kept as it is
+  // obtained (dalloc_bytes registers it with the context only on success), so a call that runs out of memory half way
+  // leaves what it got to the next call instead of allocating it twice
+  if (!c->bl_phi || !c->bl_rows || !c->bl_part) {
+    const size_t rbytes = dg_signed_distance_scratch_bytes(B, H, W, C);
+    hipError_t e = hipSuccess;
+    void* p = nullptr;
+    if (!c->bl_phi && (e = dalloc_bytes(c, &p, (size_t)B * H * W * C * sizeof(float))) == hipSuccess) c->bl_phi = (float*)p;
+    if (e == hipSuccess && !c->bl_rows && (e = dalloc_bytes(c, &p, rbytes)) == hipSuccess) {
+      c->bl_rows = p;
+      c->bl_rows_bytes = rbytes;
+    }
+    if (e == hipSuccess && !c->bl_part &&
+        (e = dalloc_bytes(c, &p, dg_boundary_scratch((long)B * H * W) * sizeof(double))) == hipSuccess)
+      c->bl_part = (double*)p;
+    if (e == hipErrorOutOfMemory) {
+      dg_set_error("%s: out of device memory for the signed distance maps (%zu bytes)", who,
+                   (size_t)B * H * W * C * sizeof(float) + rbytes);
+      return DG_ERR_HIP;
+    }
+    HIPCHECK(e);
+    DGCHECK(dalloc_fills_done());
+  }
+  DgBoundarySetting& b = c->loss.boundary;
+  b.on = true;
+  b.coef = boundary_coef;
+  for (int k = 0; k < C; ++k) b.c[k] = class_coef_host ? class_coef_host[k] : 1.0f / (float)C;
+  b.sy = sy;
+  b.sx = sx;
+  b.inside_offset = inside_offset;
+  c->last.boundary_valid = false;
+  return DG_OK;
+}
+int depgan_uresnet_get_boundary_loss(depgan_ctx* c, float* boundary_coef, float class_coef_host[DEPGAN_MAX_HEAD_CLASSES],
+                                     double* sy, double* sx, double* inside_offset) {
+  if (!c || !c->loss.boundary.on) return 0;
+  const DgBoundarySetting& b = c->loss.boundary;
+  if (boundary_coef) *boundary_coef = b.coef;
+  if (class_coef_host) memcpy(class_coef_host, b.c, (size_t)c->cfg.nc_out * sizeof(float));
+  if (sy) *sy = b.sy;
+  if (sx) *sx = b.sx;
+  if (inside_offset) *inside_offset = b.inside_offset;
+  return 1;
+}
+int depgan_uresnet_last_boundary_loss(depgan_ctx* c, double* boundary_loss, long long* taking_part) {
+  if (!c || !boundary_loss) { dg_set_error("depgan_uresnet_last_boundary_loss: null argument"); return DG_ERR_ARG; }
+  if (!c->loss.boundary.on || !c->last.boundary_valid) {
+    dg_set_error("depgan_uresnet_last_boundary_loss: no depgan_uresnet_* call has run with the boundary loss on "
+                 "(depgan_uresnet_set_boundary_loss)");
+    return DG_ERR_ARG;
+  }
+  *boundary_loss = c->last.boundary_loss;
+  if (taking_part) *taking_part = (long long)c->last.boundary_M;
   return DG_OK;
 }
 

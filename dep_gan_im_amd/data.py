@@ -461,6 +461,85 @@ def class_counts(labels, n_class, ignore_label=None, device=None, chunk=1 << 26,
     return {"classes": tot[3:].copy(), "ignored": int(tot[1]), "bad": int(tot[2]), "total": P}
 
 
+def _signed_distance_args(shape, floating, n_class, spacing, ignore_label, inside_offset, classes):
+    """The checks of signed_distance_maps, before anything touches the library: returns (n, H, W, one-hot?, (sy, sx),
+    the ignore code or -1, the offset, the per-class switches or None)."""
+    ignore_label = _check_ignore_label(ignore_label)
+    if isinstance(n_class, bool) or not isinstance(n_class, (int, np.integer)) or not 2 <= int(n_class) <= _lib.MAX_HEAD_CLASSES:
+        raise ValueError("n_class must be an integer in [2, %d], got %r" % (_lib.MAX_HEAD_CLASSES, n_class))
+    K = int(n_class)
+    onehot = floating and len(shape) == 4 and shape[3] == K
+    if not onehot and len(shape) == 4 and shape[3] == 1:
+        shape = shape[:3]
+    if len(shape) != (4 if onehot else 3):
+        raise ValueError("labels must be class indices (n, H, W) or (n, H, W, 1), or float one-hot rows (n, H, W, %d), "
+                         "got shape %s" % (K, shape))
+    n, H, W = shape[:3]
+    if n < 1 or not 1 <= H <= 4096 or not 1 <= W <= 4096 or n * H * W >= 1 << 31:
+        raise ValueError("labels: n >= 1 slices of 1..4096 pixels a side and fewer than 2^31 pixels in all, got %s" % (shape,))
+    try:
+        sp = tuple(spacing)
+    except TypeError:
+        sp = ()
+    if len(sp) != 2 or any(isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) for v in sp) \
+            or not all(np.isfinite(float(v)) and float(v) > 0 for v in sp):
+        raise ValueError("spacing must be (sy, sx), two finite numbers > 0, got %r" % (spacing,))
+    sp = (float(sp[0]), float(sp[1]))
+    if isinstance(inside_offset, bool) or not isinstance(inside_offset, (int, float, np.integer, np.floating)) \
+            or not 0.0 <= float(inside_offset) <= min(sp):
+        raise ValueError("inside_offset must be a number in [0, min(spacing)] = [0, %g], got %r" % (min(sp), inside_offset))
+    on = None
+    if classes is not None:
+        ks = [k for k in classes]
+        if not ks or any(isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 0 <= k < K for k in ks):
+            raise ValueError("classes must be None or a non-empty list of class indices in [0, %d), got %r" % (K, classes))
+        on = [1 if k in ks else 0 for k in range(K)]
+    return n, H, W, onehot, sp, -1 if ignore_label is None else ignore_label, float(inside_offset), on
+
+
+def signed_distance_maps(labels, n_class, spacing=(1, 1), ignore_label=None, inside_offset=0.0, classes=None, device=None):
+    """The signed distance maps the boundary loss integrates against (compile(boundary_loss=True) computes them itself
+    for every batch; this serves inspection and loops of one's own): depgan_op_signed_distance.
+    labels: class indices (n, H, W) or (n, H, W, 1) (uint8, or any integer dtype or integral floats narrowed to a byte),
+    or float one-hot rows (n, H, W, n_class), NumPy or tensor.  Per slice and class k, with S the pixels whose true class
+    is k (the code, or the first arg-max of the row): phi = +distance to S outside it and -(distance to the complement -
+    inside_offset) inside, exact Euclidean distances at pixel spacing (sy, sx), 0 where the class is absent from the slice
+    or fills it.  ignore_label: pixels of that code -- or, for one-hot rows and any ignore_label, all-zero rows -- belong
+    to no class.  classes: None, or the class indices that get a map (the others are 0).  Slices never see each other.
+    Returns (n, H, W, n_class) float32 on the GPU."""
+    import torch
+    tens = isinstance(labels, torch.Tensor)
+    a = labels if tens else np.asarray(labels)
+    floating = a.is_floating_point() if tens else a.dtype.kind == "f"
+    n, H, W, onehot, sp, ign, off, on = _signed_distance_args(tuple(int(d) for d in a.shape), floating, n_class, spacing,
+                                                              ignore_label, inside_offset, classes)
+    K = int(n_class)
+    if not onehot:
+        a = a.reshape(n, H, W)
+        if a.dtype != (torch.uint8 if tens else np.uint8):
+            xp = torch if tens else np
+            if floating and not bool((a == xp.trunc(a)).all()):
+                raise ValueError("signed_distance_maps: class indices must hold integral values")
+            badv = (a < 0) | (a > 255)
+            a = xp.where(badv, xp.full_like(a, 254 if ign == 255 else 255), a)
+            a = a.to(torch.uint8) if tens else a.astype(np.uint8)
+    lib = _lib.load()
+    dev = a.device if tens and a.is_cuda and device is None else torch.device(device if device is not None else "cuda:0")
+    if onehot:
+        t = (a if tens else torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32))).to(device=dev, dtype=torch.float32)
+        keep = t.contiguous()
+        args = (_p(keep), None)
+    else:
+        keep = (a if tens else torch.from_numpy(np.ascontiguousarray(a))).to(dev).contiguous()
+        args = (None, _p(keep))
+    out = torch.empty((n, H, W, K), dtype=torch.float32, device=dev)
+    sw = None if on is None else (C.c_int * K)(*on)
+    _lib.check(lib.depgan_op_signed_distance(args[0], args[1], ign, n, H, W, K, sw, sp[0], sp[1], off, _p(out),
+                                             _stream(dev, None)), "depgan_op_signed_distance")
+    del keep
+    return out
+
+
 def balanced_class_weights(counts, rule="inverse"):
     """Class weights from pixel counts per class (class_counts(...)['classes']); host only.
     rule 'inverse': total / (C * n_k), scikit-learn's 'balanced'; rule 'median': median(n) / n_k over the classes that

@@ -691,6 +691,46 @@ class Engine:
         return {"intersection": np.array(out[:n], np.float64), "pred": np.array(out[n:2 * n], np.float64),
                 "true": np.array(out[2 * n:3 * n], np.float64), "loss": float(loss.value)}
 
+    def set_boundary_loss(self, on=True, weight=1.0, class_coef=None, spacing=(1.0, 1.0), inside_offset=0.0):
+        """depgan_uresnet_set_boundary_loss: the boundary loss of every uresnet() call (Kervadec et al.): the softmax
+        probabilities integrated against the signed distance map of the call's labels, weight * L_B added to what the
+        cross-entropy and the Dice mode compute.  class_coef: the nc_out coefficients c_k >= 0 (None: 1 / nc_out each; a
+        class with 0 gets no map); spacing = (sy, sx) > 0; inside_offset in [0, min(spacing)] (0: the symmetric map).
+        L_B is negative at a perfect prediction.  The first call allocates the maps; calling again with another weight
+        allocates nothing, so a schedule may do it before every epoch.  on=False turns the mode off (the default)."""
+        if not on:
+            check(self.lib.depgan_uresnet_set_boundary_loss(self.h, 0, 0.0, None, 0, 1.0, 1.0, 0.0),
+                  "depgan_uresnet_set_boundary_loss")
+            return
+        self._need_trainable("set_boundary_loss")
+        arr, n = None, 0
+        if class_coef is not None:
+            c = np.asarray(class_coef, np.float32).reshape(-1)
+            arr, n = (C.c_float * len(c))(*[float(v) for v in c]), len(c)
+        sy, sx = (float(v) for v in spacing)
+        check(self.lib.depgan_uresnet_set_boundary_loss(self.h, 1, float(weight), arr, n, sy, sx, float(inside_offset)),
+              "depgan_uresnet_set_boundary_loss")
+
+    @property
+    def boundary_loss(self):
+        """None with the boundary loss off, else a dict: 'weight', 'class_coef' (np.float32), 'spacing' (sy, sx) and
+        'inside_offset' as the library holds them."""
+        w, cc = C.c_float(), (C.c_float * _lib.MAX_HEAD_CLASSES)()
+        sy, sx, off = C.c_double(), C.c_double(), C.c_double()
+        if not self.lib.depgan_uresnet_get_boundary_loss(self.h, C.byref(w), cc, C.byref(sy), C.byref(sx), C.byref(off)):
+            return None
+        return {"weight": w.value, "class_coef": np.array(cc[:self.nc_out], np.float32),
+                "spacing": (sy.value, sx.value), "inside_offset": off.value}
+
+    def uresnet_boundary_loss(self):
+        """(L_B, M) of the last uresnet() call made with the boundary loss on: the boundary term before its weight, and
+        the number of pixels that took part.  They came back with that call's loss; this reads host memory
+        (depgan_uresnet_last_boundary_loss)."""
+        lb, m = C.c_double(), C.c_longlong()
+        check(self.lib.depgan_uresnet_last_boundary_loss(self.h, C.byref(lb), C.byref(m)),
+              "depgan_uresnet_last_boundary_loss")
+        return float(lb.value), int(m.value)
+
     def apply_adam(self, net):
         self._need_trainable("apply_adam")
         self._use_current_stream()

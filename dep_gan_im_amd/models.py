@@ -303,6 +303,7 @@ class GeneratorModel(_Model):
         self._class_weight, self._ignore_label = None, None      # compile(class_weight=, ignore_label=)
         self._dice = None                                        # compile(dice_loss=...): Engine.set_dice_loss's arguments
         self._focal = None                                       # compile(focal_gamma=, label_smoothing=), None when off
+        self._boundary = None                                    # compile(boundary_loss=True, ...): Engine.set_boundary_loss's arguments
         self._opt = None                                         # compile(clipnorm=, clipvalue=, weight_decay=), None when off
         self.stop_training = False                               # a fit callback sets it to end fit after the epoch
         self._drop_rng = np.random.RandomState(seed)
@@ -336,6 +337,8 @@ class GeneratorModel(_Model):
             engine.set_dice_loss(**self._dice)
         if self._focal is not None:
             engine.set_focal(*self._focal)
+        if self._boundary is not None:
+            engine.set_boundary_loss(**self._boundary)
         if self._opt is not None:
             engine.set_optimizer(net, **self._opt)
 
@@ -479,9 +482,79 @@ class GeneratorModel(_Model):
         out["class_coef"] = c32
         return out
 
+    def _boundary_args(self, boundary_loss, boundary_weight, boundary_classes, boundary_spacing, boundary_inside_offset):
+        """compile's boundary arguments as the keyword arguments of Engine.set_boundary_loss, or None with the mode
+        off; ValueError otherwise.  Needs no engine."""
+        C = self.nc_out
+        if not isinstance(boundary_loss, (bool, np.bool_)):
+            raise ValueError("boundary_loss must be True or False, got %r" % (boundary_loss,))
+        if not boundary_loss:
+            if boundary_classes is not None:
+                raise ValueError("boundary_classes needs boundary_loss=True")
+            return None
+        H, W, _ = self.input_shape
+        if not (1 <= H <= 4096 and 1 <= W <= 4096):
+            raise ValueError("boundary_loss: the distance transform takes images of 1..4096 pixels a side, got %dx%d" % (H, W))
+        if boundary_weight is None:
+            raise ValueError("boundary_weight must be a number, got None")
+        weight = Engine._opt_number(boundary_weight, "boundary_weight", False)
+        try:
+            sp = tuple(boundary_spacing)
+        except TypeError:
+            sp = ()
+        if len(sp) != 2 or any(isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) for v in sp) \
+                or not all(np.isfinite(float(v)) and float(v) > 0 for v in sp):
+            raise ValueError("boundary_spacing must be (sy, sx), two finite numbers > 0, got %r" % (boundary_spacing,))
+        sp = (float(sp[0]), float(sp[1]))
+        off = boundary_inside_offset
+        if isinstance(off, bool) or not isinstance(off, (int, float, np.integer, np.floating)) \
+                or not 0.0 <= float(off) <= min(sp):
+            raise ValueError("boundary_inside_offset must be a number in [0, min(boundary_spacing)] = [0, %g], got %r"
+                             % (min(sp), off))
+        out = {"weight": weight, "class_coef": None, "spacing": sp, "inside_offset": float(off)}
+        if boundary_classes is None:
+            return out
+        if isinstance(boundary_classes, str):
+            if boundary_classes != "foreground":
+                raise ValueError("boundary_classes must be None, 'foreground' or %d coefficients, got %r"
+                                 % (C, boundary_classes))
+            c = np.full(C, 1.0 / (C - 1), np.float64)
+            c[0] = 0.0
+        else:
+            c = np.asarray(boundary_classes, np.float64).reshape(-1)
+            if c.size != C:
+                raise ValueError("boundary_classes must hold nc_out = %d coefficients, got %d" % (C, c.size))
+        c32 = c.astype(np.float32)
+        if not np.all(np.isfinite(c32)) or np.any(c32 < 0) or not np.any(c32 > 0):
+            raise ValueError("boundary_classes: every coefficient must be finite and >= 0, and at least one > 0, got %r"
+                             % (c.tolist(),))
+        out["class_coef"] = c32
+        return out
+
+    @property
+    def boundary_weight(self):
+        """The weight of the boundary term in the loss, None with compile(boundary_loss=False)."""
+        return None if self._boundary is None else self._boundary["weight"]
+
+    def set_boundary_weight(self, weight):
+        """Sets the weight of the boundary term, before or after the first use (finite and >= 0); on an engine it holds
+        from the next call on and allocates nothing (Engine.set_boundary_loss).  The schedule the loss is used with
+        starts small and rises: callbacks.BoundaryWeightScheduler calls this before every epoch."""
+        self._need_softmax("set_boundary_weight")
+        if self._boundary is None:
+            raise RuntimeError("set_boundary_weight: the model was not compiled with boundary_loss=True")
+        if weight is None:
+            raise ValueError("boundary_weight must be a number, got None")
+        weight = Engine._opt_number(weight, "boundary_weight", False)
+        if self._engine is not None:
+            self._engine.set_boundary_loss(**dict(self._boundary, weight=weight))
+        self._boundary = dict(self._boundary, weight=weight)
+
     def compile(self, optimizer="adam", loss="categorical_crossentropy", lr=None, metrics=None, class_weight=None,
                 ignore_label=None, dice_loss=None, dice_weight=1.0, ce_weight=1.0, dice_smooth=1e-7, dice_classes=None,
-                focal_gamma=0.0, label_smoothing=0.0, clipnorm=None, clipvalue=None, weight_decay=None, **_):
+                focal_gamma=0.0, label_smoothing=0.0, clipnorm=None, clipvalue=None, weight_decay=None,
+                boundary_loss=False, boundary_weight=1.0, boundary_classes=None, boundary_spacing=(1.0, 1.0),
+                boundary_inside_offset=0.0, **_):
         """model.compile(optimizer=Adam(lr=1e-4), loss='categorical_crossentropy')  (UT:427).
         metrics: names out of 'acc' / 'accuracy' (pixel accuracy: Keras' categorical_accuracy, arg-max against arg-max),
         'dice' and 'iou' (the means over the foreground classes 1..nc_out-1, evaluate.confusion_metrics).  They come from
@@ -524,7 +597,17 @@ class GeneratorModel(_Model):
         clipnorm; Engine.grad_norm reads the norm back), clipvalue then clamps every element, weight_decay is AdamW's
         decoupled decay on the kernels (not biases, not BatchNorm).  All of it runs inside the update's own launches
         on the device.  compile() without them is the plain Adam update, bit for bit.  The rate itself can change at
-        any time: model.set_lr(lr), or fit(callbacks=[...]) with dep_gan_im_amd.callbacks."""
+        any time: model.set_lr(lr), or fit(callbacks=[...]) with dep_gan_im_amd.callbacks.
+        boundary_loss=True adds boundary_weight * L_B to the loss (Kervadec et al.; Engine.set_boundary_loss): the
+        softmax probabilities integrated against the signed distance map of each label slice, which the library computes
+        on the device for every batch, so it follows fit(augment=...).  boundary_classes: None (1 / nc_out each),
+        'foreground' (class 0 out, 1 / (nc_out - 1) elsewhere) or nc_out coefficients >= 0; boundary_spacing = (sy, sx)
+        pixel spacings > 0; boundary_inside_offset in [0, min(spacing)] (0: the symmetric map).  L_B is negative at a
+        perfect prediction, so the loss reported may be negative.  It works with both label formats, class_weight /
+        ignore_label (ignored pixels take no part and belong to no class), dice_loss, focal_gamma / label_smoothing and
+        metrics.  The term is used with a weight that starts small and rises: model.set_boundary_weight(w), or
+        callbacks.BoundaryWeightScheduler in fit, which then records history['boundary_weight'].  compile() without
+        boundary_loss turns the mode off; then every result is what it was without it."""
         self._need_softmax("compile")
         if loss not in _LOSSES + (_DICE_LOSS,):
             raise ValueError("loss must be 'categorical_crossentropy' (UT:427), 'sparse_categorical_crossentropy' or "
@@ -532,6 +615,8 @@ class GeneratorModel(_Model):
         dice = self._dice_args(loss, dice_loss, dice_weight, ce_weight, dice_smooth, dice_classes)
         focal = self._focal_args(focal_gamma, label_smoothing)
         opt = self._opt_args(optimizer, clipnorm, clipvalue, weight_decay)
+        boundary = self._boundary_args(boundary_loss, boundary_weight, boundary_classes, boundary_spacing,
+                                       boundary_inside_offset)
         was_on = self._class_weight is not None or self._ignore_label is not None
         self._class_weight, self._ignore_label = self._loss_weight_args(loss, class_weight, ignore_label)
         if self._engine is not None and (self._dice is not None or dice is not None):
@@ -542,6 +627,9 @@ class GeneratorModel(_Model):
         if self._engine is not None and (self._focal is not None or focal is not None):
             self._engine.set_focal(*(focal or (0.0, 0.0)))
         self._focal = focal
+        if self._engine is not None and (self._boundary is not None or boundary is not None):
+            self._engine.set_boundary_loss(**(boundary or {"on": False}))
+        self._boundary = boundary
         if self._engine is not None and (self._opt is not None or opt is not None):
             self._engine.set_optimizer(self.net, **(opt or {}))
         self._opt = opt
@@ -684,6 +772,8 @@ class GeneratorModel(_Model):
         callbacks = list(callbacks) if callbacks is not None else None
         if callbacks is not None:
             hist["lr"] = []
+            if self._boundary is not None:
+                hist["boundary_weight"] = []
             self.stop_training = False
             for cb in callbacks:
                 if hasattr(cb, "set_model"):
@@ -739,6 +829,9 @@ class GeneratorModel(_Model):
             if callbacks is not None:
                 hist["lr"].append(float(self.lr))
                 msg += " - lr: %.4g" % hist["lr"][-1]
+                if self._boundary is not None:
+                    hist["boundary_weight"].append(float(self.boundary_weight))
+                    msg += " - boundary_weight: %.4g" % hist["boundary_weight"][-1]
             if verbose:
                 print_fn(msg)
             if callbacks is not None:

@@ -335,6 +335,52 @@ int depgan_uresnet_get_dice_loss(depgan_ctx* ctx, float* ce_coef, float* dice_co
 int depgan_uresnet_last_dice_sums(depgan_ctx* ctx, double out_host[3 * DEPGAN_MAX_HEAD_CLASSES], int* classes,
                                   float* dice_loss);
 
+/* The boundary loss of the supervised path (Kervadec et al., "Boundary loss for highly unbalanced segmentation"): the
+ * softmax probabilities AS STORED integrated against the signed distance map of the labels, added to whatever the
+ * cross-entropy and the Dice mode compute.  Over a call's n label slices (H, W):
+ *   True class of a pixel: the census's -- the code, or the first arg-max of the one-hot row.  With the loss-weight mode
+ *     on, a pixel of the ignore code or with an all-zero row has no true class: it takes no part (m = 0) and is a member
+ *     of no class.  A code >= nc_out has none either; it is counted and the call refused as without this mode.
+ *   Distance: for class k and slice s let S be the pixels of slice s whose true class is k.  For x in S, d(x) is the
+ *     distance to the nearest pixel of slice s not in S; for x not in S, to the nearest pixel in S.  d2 = d^2 is exactly
+ *     what depgan_eval_edt_sq defines on that slice as a (1, H, W) volume with wy = sy^2, wx = sx^2:
+ *     fl(fl(dx^2 wx) + fl(dy^2 wy)) minimised over the candidate pixels, in double.  Slices never see each other.
+ *   phi_k(x) = float32(sqrt(d2)) outside S and float32(-(sqrt(d2) - inside_offset)) inside, root and subtraction in
+ *     double, one rounding to float32; an infinite d2 (the class absent from the slice, or filling it) gives 0.
+ *     inside_offset in [0, min(sy, sx)]: 0 is the symmetric map, 1 at unit spacing the map of the published code.
+ *   L_B = (1/M) sum_x m(x) sum_k c_k phi_k(x) p_k(x), M = the number of pixels that take part, c_k >= 0.
+ *     L_B IS NEGATIVE at a perfect prediction (the mass sits where phi < 0) and positive for mass far outside: it is a
+ *     term to add to a regional loss, never a loss with a minimum of 0.
+ *   g_k = m c_k phi_k / M, dz_j += boundary_coef p_j (g_j - sum_k p_k g_k), sums over k left to right, added to what
+ *     the cross-entropy and the Dice mode left in dz.  The loss of a call is (what the context computes without this
+ *     mode) + boundary_coef * L_B.
+ *   M == 0: the term is 0.0, dz is untouched and depgan_uresnet_step{,_sparse} applies NO Adam update and leaves the
+ *     step counter alone, by the Dice mode's rule for an empty batch (every pixel without a true class).
+ * depgan_uresnet_set_boundary_loss(ctx, on, boundary_coef, class_coef_host, n, sy, sx, inside_offset): on = 0 (the
+ *   default; the other arguments are not read) restores, bit for bit, what every entry computed before this mode
+ *   existed: nothing of it is launched.  on = 1: boundary_coef finite and >= 0; class_coef_host = NULL (1/nc_out each) or
+ *   n == nc_out host values, finite and >= 0 with at least one > 0 (a class with c_k = 0 gets no map); sy, sx finite and
+ *   > 0; inside_offset in [0, min(sy, sx)]; height and width within depgan_eval_edt_sq's 1..4096.  Anything else is
+ *   status 1 with a message before any launch, the setting and every buffer as they were; status 3 on an inference
+ *   context, status 1 for nc_out = 1.  The first call with on = 1 allocates phi (batch*H*W*nc_out floats) and the
+ *   distance pass's scratch (2 bytes per pixel and class); no later call and no step allocates, so a schedule may set
+ *   another boundary_coef before every epoch.
+ * With the mode on all six depgan_uresnet_{grads,step,eval}{,_sparse} entries run, behind the cross-entropy and the Dice
+ *   launches: a row pass and a column pass over all slices and switched-on classes (two launches whatever n), one pass
+ *   that reads p, phi, the labels and dz and writes dz and one double partial per block, and one block that adds the
+ *   partials in index order.  No atomics, nothing to zero between calls.  M is read on the device from the label
+ *   pre-pass (M = n*H*W with the loss-weight mode off); L_B and M come back in the call's one copy.  eval runs the
+ *   distance pass and the sum, not the gradient write.
+ * depgan_uresnet_get_boundary_loss: returns 1 and fills what is not NULL when the mode is on, else returns 0.
+ * depgan_uresnet_last_boundary_loss: host only; L_B and M of the last depgan_uresnet_* call made with the mode on.
+ *   Status 1 before any such call and after the mode was set again. */
+int depgan_uresnet_set_boundary_loss(depgan_ctx* ctx, int on, float boundary_coef, const float* class_coef_host, int n,
+                                     double sy, double sx, double inside_offset);
+int depgan_uresnet_get_boundary_loss(depgan_ctx* ctx, float* boundary_coef,
+                                     float class_coef_host[DEPGAN_MAX_HEAD_CLASSES], double* sy, double* sx,
+                                     double* inside_offset);
+int depgan_uresnet_last_boundary_loss(depgan_ctx* ctx, double* boundary_loss, long long* taking_part);
+
 /* The focal mode of the supervised path: focal cross-entropy (Lin et al.; Keras' CategoricalFocalCrossentropy) and label
  * smoothing (the label_smoothing= of Keras' CategoricalCrossentropy), two per-pixel shapings of the cross-entropy itself,
  * computed in the one softmax + cross-entropy kernel.
@@ -1033,6 +1079,31 @@ int depgan_op_label_counts(const float* onehot, const unsigned char* codes, long
 int depgan_op_dice_loss(const float* probs, const float* onehot, const unsigned char* codes, int ignore_code, int form,
                         const float* class_coef_host, int n, float smooth, float ce_coef, float dice_coef,
                         float* dz_inout, double* sums_host, float* loss_host, long P, int C, void* hip_stream);
+/* The signed distance maps of the boundary loss at operator level (depgan_uresnet_set_boundary_loss states the rule):
+ * n label slices (H, W) as onehot (n, H, W, C) fp32 or codes (n, H, W) unsigned char, exactly one of them, on the device.
+ * ignore_code as depgan_op_dice_loss takes it (-1: every pixel has a true class -- an all-zero one-hot row is class 0,
+ * the first arg-max; >= 0: that code, or an all-zero row, has none); a code >= C has none.  class_on_host: NULL (every
+ * class), or C host ints, non-zero = the class gets its map; at least one.  phi_out (n, H, W, C) fp32 device: phi of the
+ * switched-on classes, 0.0 for the others; every element is written.  sy, sx finite and > 0, inside_offset in
+ * [0, min(sy, sx)], H and W in 1..4096, n >= 1, n*H*W < 2^31, C in 2..DEPGAN_MAX_HEAD_CLASSES, phi_out and onehot 4-byte
+ * aligned; anything else is status 1 before any HIP call.  Two launches whatever n; the entry allocates its own scratch
+ * (2 bytes per pixel and class) and waits for the stream before it frees it.  n*H and the number of 64 x 16 tiles over
+ * all slices and classes must each stay below 2^24 (one workgroup each). */
+int depgan_op_signed_distance(const float* onehot, const unsigned char* codes, int ignore_code, int n, int H, int W, int C,
+                              const int* class_on_host, double sy, double sx, double inside_offset, float* phi_out,
+                              void* hip_stream);
+/* The boundary loss at operator level: probs (P, C) as depgan_op_softmax_ce stored them, phi (P, C) as
+ * depgan_op_signed_distance wrote it, labels and ignore_code as above (they decide m alone).  M = P with
+ * ignore_code = -1 (a code >= C then has m = 0 but stays in M: the context refuses such a batch); otherwise
+ * M = P - the pixels without a true class - the codes >= C, counted by the label pre-pass on the device.
+ * class_coef_host: NULL (1/C each) or ncoef == C host values, finite and >= 0, at least one > 0; boundary_coef finite and
+ * >= 0.  dz_inout (P, C) device or NULL: dz += boundary_coef dL_B/dz on the pixels that take part (the others are not
+ * written); NULL gives the loss only.  loss_host (host, 2 doubles): L_B and M; M == 0 gives L_B = 0.0 and an untouched
+ * dz.  probs, phi, onehot and dz 16-byte aligned where C % 4 == 0, else 4-byte; 1 <= P < 2^31.  Anything else is status 1
+ * before any HIP call.  The entry allocates its own scratch and synchronises the stream. */
+int depgan_op_boundary_loss(const float* probs, const float* phi, const float* onehot, const unsigned char* codes,
+                            int ignore_code, const float* class_coef_host, int ncoef, float boundary_coef,
+                            float* dz_inout, double* loss_host, long P, int C, void* hip_stream);
 /* The fp32 1x1 head to K = 2..DEPGAN_MAX_HEAD_CLASSES class logits over P pixel rows, as the DEP-UResNet training step
  * runs it for a class count other than 4.  Rows of C floats with a row stride in floats (ld >= C, ld % 4 == 0), so a
  * channel window of a wider buffer is (p + c0, Ctot) with c0 % 4 == 0; C / 4 a power of two <= 64; w (C, K), logits and
