@@ -5,8 +5,7 @@
 //   bl_rows_kernel    one workgroup per (slice, row): the true class of every pixel of the row (the census rule), then
 //                     per switched-on class k the distance in pixels to the nearest pixel of the row whose membership
 //                     of S_k = {true class == k} differs from the pixel's own, 15 bits (BL_NONE: the row is all of one
-//                     membership), bit 15 = the pixel is in S_k.  A row is a sequence of runs of one membership: the
-//                     distance is to the end of the pixel's own run, from a two-sided scan over the run starts.
+//                     membership), bit 15 = the pixel is in S_k
 //   bl_cols_kernel    along H, per (slice, class): d2[y] = min_y' fl(a(y') + fl((y - y')^2 wy)) over the rows y' whose
 //                     nearest pixel of the OTHER membership than pixel y's lies at a(y') = fl(g^2 wx) -- 0 where the
 //                     pixel of row y' in this column is of the other membership itself, g's value where it is of the
@@ -14,31 +13,24 @@
 //   bl_loss_kernel    L_B's block partials and (GRAD) dz += boundary_coef p (g - sum p g)
 //   bl_finish_kernel  one block adds the partials in index order, divides by M
 //
-// The distance arithmetic restates surface_dist.hip's (edt_rows_kernel, edt_axis_kernel): the same expression tree per
-// candidate, fl(fl(dx^2 wx) + fl(dy^2 wy)), and a minimum of doubles does not depend on its order, so d2 is bit for bit
-// what depgan_eval_edt_sq gives on the slice as a (1, H, W) volume.  No atomics anywhere, nothing to zero between calls.
+// The scan and the sweep are edt.h's, the text depgan_eval_edt_sq runs, so d2 is bit for bit what that entry gives on
+// the slice as a (1, H, W) volume.  No atomics anywhere, nothing to zero between calls.
 #include "train_ops.h"
 
 #include <float.h>
-#include <math.h>
 
-#include "softmax_row.h"
+#include "block_sum.h"
+#include "edt.h"
+#include "labels.h"
 
-// As in surface_dist.hip: every double operation below is rounded on its own.  Plain operators on purpose -- the pragma
-// governs the operations of this text, not those of the HIP headers' inline __dmul_rn / __dadd_rn.
+// every double operation of this file is rounded on its own too (edt.h has the reasons)
 #pragma clang fp contract(off)
 
 namespace {
 
-constexpr int BL_MAX_DIM = 4096;                  // depgan_eval_edt_sq's limit
 constexpr unsigned short BL_NONE = 0x7FFF, BL_IN = 0x8000;
-constexpr int BL_COLS = 64, BL_CHUNK = 32, BL_ROWS_PER_THREAD = 4, BL_TILE_ROWS = 16;
-static_assert(BL_ROWS_PER_THREAD == 4 && BL_CHUNK % 4 == 0 && BL_TILE_ROWS == 4 * BL_ROWS_PER_THREAD,
-              "bl_cols_kernel: four waves of four rows, candidate rows in steps of four");
 constexpr int BL_MAX_BLOCKS = 1024;
 constexpr unsigned char BL_NO_CLASS = 0xFF;
-
-enum { BLBL_ONEHOT = 1, BLBL_CODES = 2 };
 
 // the switched-on classes of a call, by value: k[0..n) ascending
 struct BlClasses {
@@ -46,25 +38,21 @@ struct BlClasses {
   unsigned char k[DG_MAX_CLASSES];
 };
 
-// grid n * H, block 256, workgroup = one row of one slice.  Thread t owns the run [t * run, (t + 1) * run) of the row,
-// run = ceil(W / 256) <= 16, as in edt_rows_kernel.  A flag stands at x > 0 where the membership of x differs from that
-// of x - 1; with L(x) the last flag at or before x and R(x) the first flag after x, the nearest pixel of the other
-// membership lies at x - L(x) + 1 to the left and R(x) - x to the right.
-// g is (n, classes.n, H, W); ignore as dg_dice_loss takes it (codes: that code has no class; onehot: >= 0 keeps the
-// all-zero rows without one, < 0 gives them class 0, the first arg-max).  A code >= C has no class.
+// grid n * H, block 256, workgroup = one row of one slice: per switched-on class the scan of edt.h over the row's
+// changes of membership.  g is (n, classes.n, H, W); ignore as dg_dice_loss takes it (codes: that code has no class;
+// onehot: >= 0 keeps the all-zero rows without one, < 0 gives them class 0, the first arg-max).  A code >= C has no
+// class.  The decode stays here and not in labels.h: C is a runtime value in this kernel, and it wants the class.
 template <int LBL>
 __global__ __launch_bounds__(256) void bl_rows_kernel(const float* __restrict__ onehot,
                                                       const unsigned char* __restrict__ codes, int ignore,
                                                       unsigned short* __restrict__ g, int H, int W, int C,
                                                       BlClasses cls) {
-  __shared__ unsigned char tc[BL_MAX_DIM];
-  __shared__ int last_s[256], first_s[256];
-  const int t = threadIdx.x;
+  __shared__ unsigned char tc[DG_EDT_MAX_DIM];
   const size_t row = blockIdx.x;                        // slice * H + y
   const size_t base = row * (size_t)W;
-  for (int x = t; x < W; x += 256) {
+  for (int x = threadIdx.x; x < W; x += 256) {
     int cl;
-    if (LBL == BLBL_ONEHOT) {
+    if (LBL == LBL_ONEHOT) {
       const float* r = onehot + (base + x) * (size_t)C;
       float m = r[0];
       bool any = m != 0.f;
@@ -85,74 +73,28 @@ __global__ __launch_bounds__(256) void bl_rows_kernel(const float* __restrict__ 
     tc[x] = (unsigned char)cl;
   }
   __syncthreads();
-  const int NONE = 1 << 20;                             // beyond any distance
-  const int run = (W + 255) / 256;
-  const int x0 = t * run, x1 = min(W, x0 + run);        // x0 may lie beyond W: an empty run
   const size_t slice = row / (size_t)H, y = row - slice * (size_t)H;
   for (int ka = 0; ka < cls.n; ++ka) {
     const int k = cls.k[ka];
-    int last = -NONE, first = NONE;
-    for (int x = max(x0, 1); x < x1; ++x)
-      if ((tc[x] == k) != (tc[x - 1] == k)) {
-        last = x;
-        if (first == NONE) first = x;
-      }
-    last_s[t] = last;
-    first_s[t] = first;
-    __syncthreads();
-    // inclusive prefix maximum of last_s, inclusive suffix minimum of first_s
-    for (int o = 1; o < 256; o <<= 1) {
-      const int a = t >= o ? last_s[t - o] : -NONE;
-      const int b = t + o < 256 ? first_s[t + o] : NONE;
-      __syncthreads();
-      last_s[t] = max(last_s[t], a);
-      first_s[t] = min(first_s[t], b);
-      __syncthreads();
-    }
-    int left[16];                                       // run <= 16 (W <= 4096)
-    int cur = t > 0 ? last_s[t - 1] : -NONE;
-#pragma unroll
-    for (int i = 0; i < 16; ++i) {
-      const int x = x0 + i;
-      if (x < x1) {
-        if (x > 0 && (tc[x] == k) != (tc[x - 1] == k)) cur = x;
-        left[i] = x - cur + 1;
-      }
-    }
-    cur = t < 255 ? first_s[t + 1] : NONE;
     unsigned short* grow = g + ((slice * (size_t)cls.n + (size_t)ka) * (size_t)H + y) * (size_t)W;
-#pragma unroll
-    for (int i = 15; i >= 0; --i) {
-      const int x = x0 + i;
-      if (x < x1) {
-        const int d = min(left[i], cur - x);
-        const unsigned short in = tc[x] == k ? BL_IN : (unsigned short)0;
-        grow[x] = (unsigned short)((d >= BL_MAX_DIM ? (int)BL_NONE : d) | in);
-        if (x > 0 && (tc[x] == k) != (tc[x - 1] == k)) cur = x;
-      }
-    }
-    __syncthreads();                                    // last_s / first_s are read above, written by the next class
+    dg_edt_row_scan<true>(
+        W, [&](int x) { return (tc[x] == k) != (tc[x - 1] == k); },
+        [&](int x, int d) {
+          const unsigned short in = tc[x] == k ? BL_IN : (unsigned short)0;
+          grow[x] = (unsigned short)((d >= DG_EDT_MAX_DIM ? (int)BL_NONE : d) | in);
+        });
+    __syncthreads();                                    // the scan's summaries are written again by the next class
   }
 }
 
-// One v_min_f64 (edt_min of surface_dist.hip, and its reasons): no operand here is a NaN -- a staged value is >= 0 or
-// +inf, a term is >= 0 and finite.
-__device__ __forceinline__ double bl_min(double a, double b) {
-  double o;
-  asm("v_min_f64 %0, %1, %2" : "=v"(o) : "v"(a), "v"(b));
-  return o;
-}
-
-// grid ceil(W / 64) * ceil(H / 16) * n * classes.n (column tile fastest), block 256.  A workgroup of four waves owns 64
-// columns x 16 output rows of one (slice, class), four rows per thread in registers, and walks the candidate rows in
-// chunks of BL_CHUNK staged in LDS twice: so[r'] = the squared row distance to the nearest pixel NOT in S (0 where the
-// pixel is not in S itself), si[r'] = to the nearest pixel in S.  An output pixel in S reads so, one outside reads si;
-// rows past H and dead columns hold +inf in both.  The axis terms shift along as in edt_axis_kernel.
-// phi is (n, H, W, C).  The workgroups of the first switched-on class also write 0 to the switched-off classes.
+// grid ceil(W / 64) * ceil(H / 16) * n * classes.n (column tile fastest), block 256: the sweep of edt.h over one
+// (slice, class) with two staged values per candidate row, a = the squared row distance to the nearest pixel NOT in S
+// (0 where the pixel is not in S itself) and b = to the nearest pixel in S.  An output pixel in S reads a, one outside
+// reads b.  phi is (n, H, W, C).  The workgroups of the first switched-on class also write 0 to the switched-off
+// classes.
 __global__ __launch_bounds__(256) void bl_cols_kernel(const unsigned short* __restrict__ g, float* __restrict__ phi,
                                                       int H, int W, int C, BlClasses cls, int col_tiles, int row_tiles,
                                                       double wx, double wy, double inside_offset) {
-  __shared__ double so[BL_CHUNK][BL_COLS], si[BL_CHUNK][BL_COLS];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   unsigned bid = blockIdx.x;
   const int ct = (int)(bid % (unsigned)col_tiles);
@@ -161,67 +103,32 @@ __global__ __launch_bounds__(256) void bl_cols_kernel(const unsigned short* __re
   const unsigned map = bid / (unsigned)row_tiles;        // slice * cls.n + ka
   const unsigned slice = map / (unsigned)cls.n;
   const int ka = (int)(map - slice * (unsigned)cls.n);
-  const int col = ct * BL_COLS + lane;
+  const int col = ct * DG_EDT_COLS + lane;
   const bool live = col < W;
   const size_t base = (size_t)map * (size_t)H * (size_t)W;
-  const int r0 = rt * BL_TILE_ROWS + wave * BL_ROWS_PER_THREAD;
+  const int r0 = rt * DG_EDT_TILE_ROWS + wave * DG_EDT_ROWS_PER_THREAD;
   const double inf = INFINITY;
-  double best[BL_ROWS_PER_THREAD];
-  bool in[BL_ROWS_PER_THREAD];
+  double best[DG_EDT_ROWS_PER_THREAD];
+  bool in[DG_EDT_ROWS_PER_THREAD];
 #pragma unroll
-  for (int k = 0; k < BL_ROWS_PER_THREAD; ++k) {
-    best[k] = inf;
+  for (int k = 0; k < DG_EDT_ROWS_PER_THREAD; ++k)
     in[k] = live && r0 + k < H && (g[base + (size_t)(r0 + k) * (size_t)W + (size_t)col] & BL_IN) != 0;
-  }
-  for (int c0 = 0; c0 < H; c0 += BL_CHUNK) {
-    const int cn = min(BL_CHUNK, H - c0);
-    const int cn4 = (cn + 3) & ~3;                         // <= BL_CHUNK, a multiple of 4
-    __syncthreads();                                       // the previous chunk has been read
-    for (int r = wave; r < cn4; r += 4) {
-      double ao = inf, ai = inf;
-      if (live && r < cn) {
-        const unsigned short gv = g[base + (size_t)(c0 + r) * (size_t)W + (size_t)col];
-        const int d = gv & BL_NONE;
-        double a = inf;
-        if (d != BL_NONE) {
-          const double gd = (double)d;
-          a = (gd * gd) * wx;                               // gd * gd is exact
-        }
-        const bool is_in = (gv & BL_IN) != 0;
-        ao = is_in ? a : 0.0;
-        ai = is_in ? 0.0 : a;
-      }
-      so[r][lane] = ao;
-      si[r][lane] = ai;
+  dg_edt_axis_sweep<32, true>(H, r0, live, wy, in, [&](int r, double& ao, double& ai) {
+    const unsigned short gv = g[base + (size_t)r * (size_t)W + (size_t)col];
+    const int d = gv & BL_NONE;
+    double a = inf;
+    if (d != BL_NONE) {
+      const double gd = (double)d;
+      a = (gd * gd) * wx;                                   // gd * gd is exact
     }
-    __syncthreads();
-    double e = (double)(r0 - c0);                           // r_0 - r'
-    double t0 = (e * e) * wy;
-    double t1 = ((e + 1.0) * (e + 1.0)) * wy;
-    double t2 = ((e + 2.0) * (e + 2.0)) * wy;
-    double t3 = ((e + 3.0) * (e + 3.0)) * wy;
-#define BL_STEP(R, T0, T1, T2, T3)                           \
-  {                                                          \
-    const double ao = so[r + R][lane], ai = si[r + R][lane]; \
-    best[0] = bl_min(best[0], (in[0] ? ao : ai) + T0);       \
-    best[1] = bl_min(best[1], (in[1] ? ao : ai) + T1);       \
-    best[2] = bl_min(best[2], (in[2] ? ao : ai) + T2);       \
-    best[3] = bl_min(best[3], (in[3] ? ao : ai) + T3);       \
-    e = e - 1.0;                                             \
-    T3 = (e * e) * wy;                                       \
-  }
-    for (int r = 0; r < cn4; r += 4) {                      // rows cn .. cn4 - 1 hold +inf
-      BL_STEP(0, t0, t1, t2, t3)
-      BL_STEP(1, t3, t0, t1, t2)
-      BL_STEP(2, t2, t3, t0, t1)
-      BL_STEP(3, t1, t2, t3, t0)
-    }
-#undef BL_STEP
-  }
+    const bool is_in = (gv & BL_IN) != 0;
+    ao = is_in ? a : 0.0;
+    ai = is_in ? 0.0 : a;
+  }, best);
   if (!live) return;
   const int kclass = cls.k[ka];
 #pragma unroll
-  for (int k = 0; k < BL_ROWS_PER_THREAD; ++k) {
+  for (int k = 0; k < DG_EDT_ROWS_PER_THREAD; ++k) {
     if (r0 + k >= H) continue;
     const double d2 = best[k];
     float v = 0.f;
@@ -246,20 +153,6 @@ struct BlCoef {
   float c[DG_MAX_CLASSES];
   float boundary_coef;
 };
-
-// whether pixel i takes part (m), as dice_label_row of dice_loss.hip decides it
-template <int C, int LBL>
-__device__ __forceinline__ bool bl_takes_part(const float* __restrict__ onehot, const unsigned char* __restrict__ codes,
-                                              size_t i, int ignore) {
-  if (LBL == BLBL_ONEHOT) {
-    if (ignore < 0) return true;
-    float t[C];
-    dg_row_load<C>(onehot + i * C, t);
-    return dg_row_any<C>(t);
-  }
-  const int raw = codes[i];
-  return !(raw == ignore || raw >= C);
-}
 
 // M of a call: every pixel, or P less the pixels without a true class and the codes out of range, as the label pre-pass
 // counted them (DgCeDev::counts)
@@ -286,7 +179,8 @@ __global__ __launch_bounds__(256) void bl_loss_kernel(const float* __restrict__ 
   }
   double acc = 0.0;
   for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < (size_t)P; i += (size_t)gridDim.x * blockDim.x) {
-    if (!bl_takes_part<C, LBL>(onehot, codes, i, ignore)) continue;
+    float t[C];                                             // not read: membership alone
+    if (!dg_label_row<C, LBL, true>(onehot, codes, i, ignore, t)) continue;
     float p[C], w[C];
     dg_row_load<C>(probs + i * C, p);
     dg_row_load<C>(phi + i * C, w);
@@ -335,13 +229,6 @@ __global__ __launch_bounds__(256) void bl_finish_kernel(const double* __restrict
   out->M = M;
 }
 
-int bl_nblk(size_t n) {
-  const size_t b = (n + 255) / 256;
-  return (int)(b > (size_t)BL_MAX_BLOCKS ? (size_t)BL_MAX_BLOCKS : (b < 1 ? 1 : b));
-}
-
-size_t round8(size_t b) { return (b + 7) & ~(size_t)7; }
-
 template <int C>
 void bl_loss_launch(bool onehot_lbl, int nb, hipStream_t st, const float* probs, const float* phi, const float* onehot,
                     const unsigned char* codes, int ignore, const BlCoef& co, const unsigned long long* counts,
@@ -349,50 +236,30 @@ void bl_loss_launch(bool onehot_lbl, int nb, hipStream_t st, const float* probs,
 #define DG_BL(LBL, GR)                                                                                              \
   hipLaunchKernelGGL((bl_loss_kernel<C, LBL, GR>), dim3(nb), dim3(256), 0, st, probs, phi, onehot, codes, ignore, co, \
                      counts, dz, part, P)
-  if (onehot_lbl && dz) DG_BL(BLBL_ONEHOT, true);
-  else if (onehot_lbl) DG_BL(BLBL_ONEHOT, false);
-  else if (dz) DG_BL(BLBL_CODES, true);
-  else DG_BL(BLBL_CODES, false);
+  DG_FOR_LABELS_AND_FLAG(onehot_lbl, dz != nullptr, DG_BL);
 #undef DG_BL
 }
 
 }  // namespace
 
 int dg_boundary_check(const char* who, float boundary_coef, const float* coef, int n, int C) {
-  if (C < DG_MIN_CLASSES || C > DG_MAX_CLASSES) {
-    dg_set_error("%s: %d classes (the kernels cover %d to %d)", who, C, DG_MIN_CLASSES, DG_MAX_CLASSES);
-    return DG_ERR_ARG;
-  }
+  DGCHECK(dg_class_count_check(who, C));
   if (!(boundary_coef >= 0.f) || boundary_coef > FLT_MAX) {
     dg_set_error("%s: boundary_coef is %g (finite and >= 0)", who, (double)boundary_coef);
     return DG_ERR_ARG;
   }
-  if (!coef) return DG_OK;
-  if (n != C) { dg_set_error("%s: %d class coefficients for %d classes", who, n, C); return DG_ERR_ARG; }
-  bool any = false;
-  for (int k = 0; k < C; ++k) {
-    if (!(coef[k] >= 0.f) || coef[k] > FLT_MAX) {
-      dg_set_error("%s: class coefficient %d is %g (every coefficient is finite and >= 0)", who, k, (double)coef[k]);
-      return DG_ERR_ARG;
-    }
-    any = any || coef[k] > 0.f;
-  }
-  if (!any) { dg_set_error("%s: every class coefficient is 0 (at least one must be > 0)", who); return DG_ERR_ARG; }
-  return DG_OK;
+  return coef ? dg_class_coef_check(who, coef, n, C) : DG_OK;
 }
 
 int dg_signed_distance_check(const char* who, long n, int H, int W, int C, double sy, double sx, double inside_offset) {
-  if (C < DG_MIN_CLASSES || C > DG_MAX_CLASSES) {
-    dg_set_error("%s: %d classes (the kernels cover %d to %d)", who, C, DG_MIN_CLASSES, DG_MAX_CLASSES);
-    return DG_ERR_ARG;
-  }
-  if (n < 1 || H < 1 || W < 1 || H > BL_MAX_DIM || W > BL_MAX_DIM || n * (long)H * W >= (1L << 31)) {
+  DGCHECK(dg_class_count_check(who, C));
+  if (n < 1 || H < 1 || W < 1 || H > DG_EDT_MAX_DIM || W > DG_EDT_MAX_DIM || n * (long)H * W >= (1L << 31)) {
     dg_set_error("%s: n=%ld H=%d W=%d (n >= 1, H and W in 1..%d as the distance transform takes them, n*H*W < 2^31)",
-                 who, n, H, W, BL_MAX_DIM);
+                 who, n, H, W, DG_EDT_MAX_DIM);
     return DG_ERR_ARG;
   }
   // one workgroup of 256 per row (row pass) and per 64 x 16 tile of a map (column pass): a grid stays below 2^32 threads
-  const long tiles = (long)cdiv(W, BL_COLS) * cdiv(H, BL_TILE_ROWS) * n * C;
+  const long tiles = (long)cdiv(W, DG_EDT_COLS) * cdiv(H, DG_EDT_TILE_ROWS) * n * C;
   if (n * (long)H >= (1L << 24) || tiles >= (1L << 24)) {
     dg_set_error("%s: n=%ld slices of %d x %d with %d classes: n*H (%ld) and the 64 x 16 tiles of all maps (%ld) must "
                  "each stay below 2^24, one workgroup each", who, n, H, W, C, n * (long)H, tiles);
@@ -411,7 +278,7 @@ int dg_signed_distance_check(const char* who, long n, int H, int W, int C, doubl
 }
 
 size_t dg_signed_distance_scratch_bytes(long n, int H, int W, int C) {
-  return round8((size_t)n * (size_t)H * (size_t)W * (size_t)C * sizeof(unsigned short));
+  return dg_edt_round8((size_t)n * (size_t)H * (size_t)W * (size_t)C * sizeof(unsigned short));
 }
 
 int dg_signed_distance(DgLabels lab, int ignore_code, long n, int H, int W, int C, unsigned class_mask, double sy,
@@ -441,12 +308,12 @@ int dg_signed_distance(DgLabels lab, int ignore_code, long n, int H, int W, int 
   unsigned short* g = (unsigned short*)scratch;
   const dim3 grows((unsigned)(n * H));
   if (lab.onehot)
-    hipLaunchKernelGGL(bl_rows_kernel<BLBL_ONEHOT>, grows, dim3(256), 0, st, lab.onehot, lab.codes, ignore_code, g, H, W,
+    hipLaunchKernelGGL(bl_rows_kernel<LBL_ONEHOT>, grows, dim3(256), 0, st, lab.onehot, lab.codes, ignore_code, g, H, W,
                        C, cls);
   else
-    hipLaunchKernelGGL(bl_rows_kernel<BLBL_CODES>, grows, dim3(256), 0, st, lab.onehot, lab.codes, ignore_code, g, H, W,
+    hipLaunchKernelGGL(bl_rows_kernel<LBL_CODES>, grows, dim3(256), 0, st, lab.onehot, lab.codes, ignore_code, g, H, W,
                        C, cls);
-  const int col_tiles = cdiv(W, BL_COLS), row_tiles = cdiv(H, BL_TILE_ROWS);
+  const int col_tiles = cdiv(W, DG_EDT_COLS), row_tiles = cdiv(H, DG_EDT_TILE_ROWS);
   const long tiles = (long)col_tiles * row_tiles * n * cls.n;
   // the squared spacings as evaluate.surface_distances forms its weights
   hipLaunchKernelGGL(bl_cols_kernel, dim3((unsigned)tiles), dim3(256), 0, st, (const unsigned short*)g, phi, H, W, C,
@@ -455,40 +322,18 @@ int dg_signed_distance(DgLabels lab, int ignore_code, long n, int H, int W, int 
   return DG_OK;
 }
 
-size_t dg_boundary_scratch(long P) { return (size_t)bl_nblk((size_t)P); }
-
-int dg_boundary_operands_check(const char* who, const float* probs, const float* phi, DgLabels lab, int ignore_code,
-                               const float* dz, long P, int C) {
-  if (C < DG_MIN_CLASSES || C > DG_MAX_CLASSES) {
-    dg_set_error("%s: %d classes (the kernels cover %d to %d)", who, C, DG_MIN_CLASSES, DG_MAX_CLASSES);
-    return DG_ERR_ARG;
-  }
-  if (!probs || !phi || P < 1 || P >= (1L << 31) || (!lab.onehot == !lab.codes)) {
-    dg_set_error("%s: null probs or phi, P outside [1, 2^31), or not exactly one of onehot and codes", who);
-    return DG_ERR_ARG;
-  }
-  if (ignore_code < -1 || ignore_code > 255) {
-    dg_set_error("%s: ignore code %d (-1 for none, else a byte value 0..255)", who, ignore_code);
-    return DG_ERR_ARG;
-  }
-  const uintptr_t al = (C % 4 == 0) ? 15 : 3;
-  if (((uintptr_t)probs | (uintptr_t)phi | (uintptr_t)lab.onehot | (uintptr_t)dz) & al) {
-    dg_set_error("%s: probs, phi, onehot and dz must be %d-byte aligned for %d classes", who, (int)al + 1, C);
-    return DG_ERR_ARG;
-  }
-  return DG_OK;
-}
+size_t dg_boundary_scratch(long P) { return (size_t)t_nblk((size_t)P, BL_MAX_BLOCKS); }
 
 int dg_boundary_loss(const float* probs, const float* phi, DgLabels lab, int ignore_code, const float* class_coef,
                      float boundary_coef, const unsigned long long* counts, float* dz, DgBoundaryDev* out, long P, int C,
                      double* scratch, size_t scratch_doubles, hipStream_t st) {
   DGCHECK(dg_boundary_check("dg_boundary_loss", boundary_coef, class_coef, C, C));
-  DGCHECK(dg_boundary_operands_check("dg_boundary_loss", probs, phi, lab, ignore_code, dz, P, C));
+  DGCHECK(dg_loss_operands_check("dg_boundary_loss", probs, "phi", phi, lab, ignore_code, dz, P, true, C));
   if (!class_coef || !out || ((uintptr_t)out & 7) || ((uintptr_t)counts & 7)) {
     dg_set_error("dg_boundary_loss: null class_coef, or null or misaligned out or counts");
     return DG_ERR_ARG;
   }
-  const int nb = bl_nblk((size_t)P);
+  const int nb = t_nblk((size_t)P, BL_MAX_BLOCKS);
   if (!scratch || ((uintptr_t)scratch & 7) || scratch_doubles < (size_t)nb) {
     dg_set_error("dg_boundary_loss: scratch of %zu doubles, the launches need %d", scratch ? scratch_doubles : (size_t)0, nb);
     return DG_ERR_ARG;
@@ -496,11 +341,11 @@ int dg_boundary_loss(const float* probs, const float* phi, DgLabels lab, int ign
   BlCoef co;
   for (int k = 0; k < DG_MAX_CLASSES; ++k) co.c[k] = k < C ? class_coef[k] : 0.f;
   co.boundary_coef = boundary_coef;
-  switch (C) {
-#define DG_BLC(N) case N: bl_loss_launch<N>(lab.onehot != nullptr, nb, st, probs, phi, lab.onehot, lab.codes, ignore_code, co, counts, dz, scratch, P); break;
-    DG_BLC(2) DG_BLC(3) DG_BLC(4) DG_BLC(5) DG_BLC(6) DG_BLC(7) DG_BLC(8)
+#define DG_BLC(N)                                                                                              \
+  bl_loss_launch<N>(lab.onehot != nullptr, nb, st, probs, phi, lab.onehot, lab.codes, ignore_code, co, counts, dz, \
+                    scratch, P)
+  DG_FOR_CLASS_COUNT(C, DG_BLC)
 #undef DG_BLC
-  }
   hipLaunchKernelGGL(bl_finish_kernel, dim3(1), dim3(256), 0, st, (const double*)scratch, nb, counts, P, out);
   HIPCHECK(hipGetLastError());
   return DG_OK;

@@ -7,32 +7,8 @@
 
 #include <float.h>
 
-#include "softmax_row.h"
-
-enum { DLBL_ONEHOT = 1, DLBL_CODES = 2 };
-
-static inline int dice_nblk(size_t n) {
-  size_t b = (n + 255) / 256;
-  return (int)(b > 1024 ? 1024 : (b < 1 ? 1 : b));
-}
-
-// One pixel's label row and whether the pixel takes part (m).  DLBL_CODES: t[k] = (k == code) formed in registers, a
-// code is only compared, never used as an index; the ignore code and any code >= C stay out.  DLBL_ONEHOT: the row as
-// given; with ignore >= 0 an all-zero row stays out.  The statements that follow are the same for both sources, so codes
-// and their one-hot encoding agree bit for bit.
-template <int C, int LBL>
-__device__ __forceinline__ bool dice_label_row(const float* __restrict__ onehot, const unsigned char* __restrict__ codes,
-                                               size_t i, int ignore, float (&t)[C]) {
-  if (LBL == DLBL_ONEHOT) {
-    dg_row_load<C>(onehot + i * C, t);
-    return ignore < 0 || dg_row_any<C>(t);
-  }
-  const int raw = codes[i];
-  const int code = (raw == ignore || raw >= C) ? -1 : raw;
-#pragma unroll
-  for (int k = 0; k < C; ++k) t[k] = (k == code) ? 1.0f : 0.0f;
-  return code >= 0;
-}
+#include "block_sum.h"
+#include "labels.h"
 
 // Stage 1.  Per thread 3 C float accumulators over its grid-stride pixels -- I_k += t_k p_k, P_k += p_k, T_k += t_k for
 // the pixels that take part -- then wave shuffles, the four waves through LDS, and one partial of 3 C floats per block:
@@ -46,7 +22,7 @@ __global__ __launch_bounds__(256) void dice_sums_kernel(const float* __restrict_
   for (int j = 0; j < 3 * C; ++j) acc[j] = 0.f;
   for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < (size_t)P; i += (size_t)gridDim.x * blockDim.x) {
     float p[C], t[C];
-    const bool m = dice_label_row<C, LBL>(onehot, codes, i, ignore, t);
+    const bool m = dg_label_row<C, LBL>(onehot, codes, i, ignore, t);
     dg_row_load<C>(probs + i * C, p);
     if (m) {
 #pragma unroll
@@ -148,7 +124,7 @@ __global__ __launch_bounds__(256) void dice_grad_kernel(const float* __restrict_
   }
   for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < (size_t)P; i += (size_t)gridDim.x * blockDim.x) {
     float p[C], t[C], g[C], o[C];
-    const bool m = dice_label_row<C, LBL>(onehot, codes, i, ignore, t);
+    const bool m = dg_label_row<C, LBL>(onehot, codes, i, ignore, t);
     dg_row_load<C>(probs + i * C, p);
     float pg = 0.f;
 #pragma unroll
@@ -168,12 +144,52 @@ __global__ __launch_bounds__(256) void dice_grad_kernel(const float* __restrict_
   }
 }
 
-int dg_dice_check(const char* who, int form, float ce_coef, float dice_coef, float smooth, const float* coef, int n,
-                  int C) {
+int dg_class_count_check(const char* who, int C) {
   if (C < DG_MIN_CLASSES || C > DG_MAX_CLASSES) {
     dg_set_error("%s: %d classes (the kernels cover %d to %d)", who, C, DG_MIN_CLASSES, DG_MAX_CLASSES);
     return DG_ERR_ARG;
   }
+  return DG_OK;
+}
+
+int dg_class_coef_check(const char* who, const float* coef, int n, int C) {
+  if (n != C) { dg_set_error("%s: %d class coefficients for %d classes", who, n, C); return DG_ERR_ARG; }
+  bool any = false;
+  for (int k = 0; k < C; ++k) {
+    if (!(coef[k] >= 0.f) || coef[k] > FLT_MAX) {
+      dg_set_error("%s: class coefficient %d is %g (every coefficient is finite and >= 0)", who, k, (double)coef[k]);
+      return DG_ERR_ARG;
+    }
+    any = any || coef[k] > 0.f;
+  }
+  if (!any) { dg_set_error("%s: every class coefficient is 0 (at least one must be > 0)", who); return DG_ERR_ARG; }
+  return DG_OK;
+}
+
+int dg_loss_operands_check(const char* who, const float* probs, const char* extra_name, const float* extra, DgLabels lab,
+                           int ignore_code, const float* dz, long P, bool p_below_2_31, int C) {
+  DGCHECK(dg_class_count_check(who, C));
+  if (!probs || (extra_name && !extra) || P < 1 || (p_below_2_31 && P >= (1L << 31)) || (!lab.onehot == !lab.codes)) {
+    dg_set_error("%s: null probs%s%s, P %s, or not exactly one of onehot and codes", who, extra_name ? " or " : "",
+                 extra_name ? extra_name : "", p_below_2_31 ? "outside [1, 2^31)" : "< 1");
+    return DG_ERR_ARG;
+  }
+  if (ignore_code < -1 || ignore_code > 255) {
+    dg_set_error("%s: ignore code %d (-1 for none, else a byte value 0..255)", who, ignore_code);
+    return DG_ERR_ARG;
+  }
+  const uintptr_t al = dg_row_align_mask(C);
+  if (((uintptr_t)probs | (uintptr_t)extra | (uintptr_t)lab.onehot | (uintptr_t)dz) & al) {
+    dg_set_error("%s: probs, %s%sonehot and dz must be %d-byte aligned for %d classes", who,
+                 extra_name ? extra_name : "", extra_name ? ", " : "", (int)al + 1, C);
+    return DG_ERR_ARG;
+  }
+  return DG_OK;
+}
+
+int dg_dice_check(const char* who, int form, float ce_coef, float dice_coef, float smooth, const float* coef, int n,
+                  int C) {
+  DGCHECK(dg_class_count_check(who, C));
   if (form != DEPGAN_DICE_FLAT && form != DEPGAN_DICE_CLASS) {
     dg_set_error("%s: form %d (DEPGAN_DICE_FLAT = 1 or DEPGAN_DICE_CLASS = 2)", who, form);
     return DG_ERR_ARG;
@@ -195,61 +211,25 @@ int dg_dice_check(const char* who, int form, float ce_coef, float dice_coef, flo
     dg_set_error("%s: the flat form takes no class coefficients", who);
     return DG_ERR_ARG;
   }
-  if (n != C) { dg_set_error("%s: %d class coefficients for %d classes", who, n, C); return DG_ERR_ARG; }
-  bool any = false;
-  for (int k = 0; k < C; ++k) {
-    if (!(coef[k] >= 0.f) || coef[k] > FLT_MAX) {
-      dg_set_error("%s: class coefficient %d is %g (every coefficient is finite and >= 0)", who, k, (double)coef[k]);
-      return DG_ERR_ARG;
-    }
-    any = any || coef[k] > 0.f;
-  }
-  if (!any) { dg_set_error("%s: every class coefficient is 0 (at least one must be > 0)", who); return DG_ERR_ARG; }
-  return DG_OK;
+  return dg_class_coef_check(who, coef, n, C);
 }
 
-int dg_dice_operands_check(const char* who, const float* probs, DgLabels lab, int ignore_code, const float* dz, long P,
-                           int C) {
-  if (C < DG_MIN_CLASSES || C > DG_MAX_CLASSES) {
-    dg_set_error("%s: %d classes (the kernels cover %d to %d)", who, C, DG_MIN_CLASSES, DG_MAX_CLASSES);
-    return DG_ERR_ARG;
-  }
-  if (!probs || P < 1 || (!lab.onehot == !lab.codes)) {
-    dg_set_error("%s: null probs, P < 1, or not exactly one of onehot and codes", who);
-    return DG_ERR_ARG;
-  }
-  if (ignore_code < -1 || ignore_code > 255) {
-    dg_set_error("%s: ignore code %d (-1 for none, else a byte value 0..255)", who, ignore_code);
-    return DG_ERR_ARG;
-  }
-  // rows are read and written 16 bytes at a time where C is a multiple of 4, else float by float
-  const uintptr_t al = (C % 4 == 0) ? 15 : 3;
-  if (((uintptr_t)probs | (uintptr_t)lab.onehot | (uintptr_t)dz) & al) {
-    dg_set_error("%s: probs, onehot and dz must be %d-byte aligned for %d classes", who, (int)al + 1, C);
-    return DG_ERR_ARG;
-  }
-  return DG_OK;
-}
-
-size_t dg_dice_scratch(long P, int C) { return (size_t)dice_nblk((size_t)P) * 3 * C; }
+size_t dg_dice_scratch(long P, int C) { return (size_t)t_nblk((size_t)P, 1024) * 3 * C; }
 
 template <int C>
 static void dice_launch(bool onehot_lbl, bool read_dz, int nb, hipStream_t st, const float* probs, const float* onehot,
                         const unsigned char* codes, int ignore, float* part, const DiceCoef& dc, DgDiceDev* out,
                         float ce_coef, float dice_coef, float* dz, long P) {
   if (onehot_lbl)
-    hipLaunchKernelGGL((dice_sums_kernel<C, DLBL_ONEHOT>), dim3(nb), dim3(256), 0, st, probs, onehot, codes, ignore, part, P);
+    hipLaunchKernelGGL((dice_sums_kernel<C, LBL_ONEHOT>), dim3(nb), dim3(256), 0, st, probs, onehot, codes, ignore, part, P);
   else
-    hipLaunchKernelGGL((dice_sums_kernel<C, DLBL_CODES>), dim3(nb), dim3(256), 0, st, probs, onehot, codes, ignore, part, P);
+    hipLaunchKernelGGL((dice_sums_kernel<C, LBL_CODES>), dim3(nb), dim3(256), 0, st, probs, onehot, codes, ignore, part, P);
   hipLaunchKernelGGL(dice_coeffs_kernel, dim3(1), dim3(256), 0, st, part, nb, C, dc, out);
   if (!dz) return;
 #define DG_DICE_GRAD(LBL, RD)                                                                                          \
   hipLaunchKernelGGL((dice_grad_kernel<C, LBL, RD>), dim3(nb), dim3(256), 0, st, probs, onehot, codes, ignore, out,    \
                      ce_coef, dice_coef, dz, P)
-  if (onehot_lbl && read_dz) DG_DICE_GRAD(DLBL_ONEHOT, true);
-  else if (onehot_lbl) DG_DICE_GRAD(DLBL_ONEHOT, false);
-  else if (read_dz) DG_DICE_GRAD(DLBL_CODES, true);
-  else DG_DICE_GRAD(DLBL_CODES, false);
+  DG_FOR_LABELS_AND_FLAG(onehot_lbl, read_dz, DG_DICE_GRAD);
 #undef DG_DICE_GRAD
 }
 
@@ -257,7 +237,7 @@ int dg_dice_loss(const float* probs, DgLabels lab, int ignore_code, const DgDice
                  long P, int C, float* scratch, size_t scratch_floats, hipStream_t st) {
   DGCHECK(dg_dice_check("dg_dice_loss", set.form, set.ce_coef, set.dice_coef, set.smooth,
                         set.form == DEPGAN_DICE_CLASS ? set.c : nullptr, C, C));
-  DGCHECK(dg_dice_operands_check("dg_dice_loss", probs, lab, ignore_code, dz, P, C));
+  DGCHECK(dg_loss_operands_check("dg_dice_loss", probs, nullptr, nullptr, lab, ignore_code, dz, P, false, C));
   if (!out || ((uintptr_t)out & 7)) { dg_set_error("dg_dice_loss: null or misaligned out"); return DG_ERR_ARG; }
   const size_t need = dg_dice_scratch(P, C);
   if (!scratch || scratch_floats < need) {
@@ -268,13 +248,13 @@ int dg_dice_loss(const float* probs, DgLabels lab, int ignore_code, const DgDice
   dc.form = set.form;
   dc.smooth = set.smooth;
   for (int k = 0; k < DG_MAX_CLASSES; ++k) dc.c[k] = (k < C) ? set.c[k] : 0.f;
-  const int nb = dice_nblk((size_t)P);
+  const int nb = t_nblk((size_t)P, 1024);
   const bool read_dz = set.ce_coef != 0.f;
-  switch (C) {
-#define DG_DICE(N) case N: dice_launch<N>(lab.onehot != nullptr, read_dz, nb, st, probs, lab.onehot, lab.codes, ignore_code, scratch, dc, out, set.ce_coef, set.dice_coef, dz, P); break;
-    DG_DICE(2) DG_DICE(3) DG_DICE(4) DG_DICE(5) DG_DICE(6) DG_DICE(7) DG_DICE(8)
+#define DG_DICE(N)                                                                                                \
+  dice_launch<N>(lab.onehot != nullptr, read_dz, nb, st, probs, lab.onehot, lab.codes, ignore_code, scratch, dc, out, \
+                 set.ce_coef, set.dice_coef, dz, P)
+  DG_FOR_CLASS_COUNT(C, DG_DICE)
 #undef DG_DICE
-  }
   HIPCHECK(hipGetLastError());
   return DG_OK;
 }

@@ -633,7 +633,7 @@ int depgan_op_dice_loss(const float* probs, const float* onehot, const unsigned 
   if (!dz || !sums_host || !loss_host) { dg_set_error("op_dice_loss: null dz_inout, sums_host or loss_host"); return DG_ERR_ARG; }
   DGCHECK(dg_dice_check("op_dice_loss", form, ce_coef, dice_coef, smooth, class_coef_host, n, C));
   const DgLabels lab{onehot, codes};
-  DGCHECK(dg_dice_operands_check("op_dice_loss", probs, lab, ignore_code, dz, P, C));
+  DGCHECK(dg_loss_operands_check("op_dice_loss", probs, nullptr, nullptr, lab, ignore_code, dz, P, false, C));
   hipStream_t st = (hipStream_t)stream;
   DgDiceSetting set;
   set.set(form, ce_coef, dice_coef, smooth, class_coef_host, C);
@@ -681,7 +681,7 @@ int depgan_op_boundary_loss(const float* probs, const float* phi, const float* o
   if (!loss_host) { dg_set_error("op_boundary_loss: null loss_host"); return DG_ERR_ARG; }
   DGCHECK(dg_boundary_check("op_boundary_loss", boundary_coef, class_coef_host, ncoef, C));
   const DgLabels lab{onehot, codes};
-  DGCHECK(dg_boundary_operands_check("op_boundary_loss", probs, phi, lab, ignore_code, dz_inout, P, C));
+  DGCHECK(dg_loss_operands_check("op_boundary_loss", probs, "phi", phi, lab, ignore_code, dz_inout, P, true, C));
   hipStream_t st = (hipStream_t)stream;
   float coef[DEPGAN_MAX_HEAD_CLASSES];
   for (int k = 0; k < C; ++k) coef[k] = class_coef_host ? class_coef_host[k] : 1.0f / (float)C;

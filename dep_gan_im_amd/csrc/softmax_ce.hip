@@ -5,7 +5,7 @@
 #include <float.h>
 
 #include "block_sum.h"
-#include "softmax_row.h"
+#include "labels.h"
 
 // ---------------------------------------------------------------------------
 // softmax + categorical cross-entropy (keras, probabilities path)
@@ -42,8 +42,7 @@
 // the power is 1, 1 - r or (1 - r)^2 for gamma = 0, 1, 2 (a uniform branch: gamma is a kernel argument) and
 // exp2f(gamma log2f(1 - r)) otherwise, (1 - r)^(gamma - 1) the power over 1 - r.  Everything behind dL/dq, the census and
 // the stored probabilities are the text above.  The FOCAL = false instantiations read neither gamma nor eps, the last
-// two arguments, and compile to the instructions they were.
-enum { LBL_NONE = 0, LBL_ONEHOT = 1, LBL_CODES = 2 };
+// two arguments, and compile to the instructions they were.  The LBL_* values are labels.h's.
 
 // the loss-weight mode's kernel arguments, by value: C class weights (the rest 0), the ignore code (-1: none) and the
 // device count of weighted pixels
@@ -342,15 +341,11 @@ static int label_counts_run(const float* onehot, const unsigned char* codes, lon
                             unsigned long long* counts, float* scratch, hipStream_t st) {
   const int nb = t_nblk((size_t)P, 1024);
   unsigned* cnt_part = reinterpret_cast<unsigned*>(scratch);
-  switch (C) {
 #define DG_LC(N)                                                                                                       \
-  case N:                                                                                                              \
-    if (onehot) hipLaunchKernelGGL((label_count_kernel<N, LBL_ONEHOT>), dim3(nb), dim3(256), 0, st, onehot, codes, wa, cnt_part, P); \
-    else hipLaunchKernelGGL((label_count_kernel<N, LBL_CODES>), dim3(nb), dim3(256), 0, st, onehot, codes, wa, cnt_part, P); \
-    break;
-    DG_LC(2) DG_LC(3) DG_LC(4) DG_LC(5) DG_LC(6) DG_LC(7) DG_LC(8)
+  if (onehot) hipLaunchKernelGGL((label_count_kernel<N, LBL_ONEHOT>), dim3(nb), dim3(256), 0, st, onehot, codes, wa, cnt_part, P); \
+  else hipLaunchKernelGGL((label_count_kernel<N, LBL_CODES>), dim3(nb), dim3(256), 0, st, onehot, codes, wa, cnt_part, P)
+  DG_FOR_CLASS_COUNT(C, DG_LC)
 #undef DG_LC
-  }
   HIPCHECK(hipGetLastError());
   hipLaunchKernelGGL(label_count_sum_kernel, dim3(1), dim3(256), 0, st, cnt_part, nb, C + 3, counts);
   HIPCHECK(hipGetLastError());
@@ -360,7 +355,7 @@ static int label_counts_run(const float* onehot, const unsigned char* codes, lon
 static int label_counts_check(const char* who, const float* onehot, const unsigned char* codes, long P, int C,
                               const unsigned long long* counts, const float* scratch, size_t scratch_floats) {
   if (P < 1 || (!onehot == !codes)) { dg_set_error("%s: P < 1, or not exactly one of onehot and codes", who); return DG_ERR_ARG; }
-  if (onehot && ((uintptr_t)onehot & ((C % 4 == 0) ? 15 : 3))) { dg_set_error("%s: misaligned onehot", who); return DG_ERR_ARG; }
+  if (onehot && ((uintptr_t)onehot & dg_row_align_mask(C))) { dg_set_error("%s: misaligned onehot", who); return DG_ERR_ARG; }
   if (!counts || ((uintptr_t)counts & 7)) { dg_set_error("%s: null or misaligned counts", who); return DG_ERR_ARG; }
   const size_t need = dg_label_counts_scratch(P, C);
   if (!scratch || scratch_floats < need) {
@@ -436,7 +431,7 @@ int dg_softmax_ce_check(const char* who, const SoftmaxCeArgs& a) {
   const bool labels = a.lab.onehot || a.lab.codes;
   if (labels && (!a.dz || !a.loss_sum)) { dg_set_error("%s: labels without dz or loss_sum", who); return DG_ERR_ARG; }
   // rows are read and written 16 bytes at a time where C is a multiple of 4, else float by float
-  const uintptr_t al = (C % 4 == 0) ? 15 : 3;
+  const uintptr_t al = dg_row_align_mask(C);
   if ((((uintptr_t)a.logits | (uintptr_t)a.probs | (uintptr_t)a.lab.onehot | (uintptr_t)a.dz) & al) ||
       ((uintptr_t)a.loss_sum & 3)) {
     dg_set_error("%s: logits, probs, onehot and dz must be %d-byte aligned for %d classes", who, (int)al + 1, C);
@@ -480,11 +475,9 @@ int dg_softmax_ce(const SoftmaxCeArgs& a, hipStream_t st) {
   unsigned* cen_part = s.census ? reinterpret_cast<unsigned*>(a.scratch + 2048) : nullptr;
   const float invN = (lbl == LBL_NONE) ? 0.f : 1.0f / (float)a.P;
   SmKernel kernel = nullptr;
-  switch (C) {
-#define DG_SM(N) case N: kernel = sm_pick<N>(lbl, s.census, mode); break;
-    DG_SM(2) DG_SM(3) DG_SM(4) DG_SM(5) DG_SM(6) DG_SM(7) DG_SM(8)
+#define DG_SM(N) kernel = sm_pick<N>(lbl, s.census, mode)
+  DG_FOR_CLASS_COUNT(C, DG_SM)
 #undef DG_SM
-  }
   hipLaunchKernelGGL(kernel, dim3(nb), dim3(256), 0, st, a.logits, a.lab.onehot, a.lab.codes, a.probs, a.dz, part,
                      bad_part, cen_part, a.P, invN, wa, s.focal ? s.gamma : 0.f, s.focal ? s.eps : 0.f);
   HIPCHECK(hipGetLastError());

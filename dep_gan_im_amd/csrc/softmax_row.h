@@ -10,7 +10,8 @@
 static_assert(DG_MAX_CLASSES <= 8, "a class row lives in registers as two float4");
 
 // dense rows of C floats: 16-byte accesses where C is a multiple of 4 (the row start is then 16-byte aligned whenever
-// the base is), else one float at a time
+// the base is), else one float at a time.  dg_row_align_mask: the address bits a host check wants clear for that
+static inline uintptr_t dg_row_align_mask(int C) { return (C % 4 == 0) ? 15 : 3; }
 template <int C>
 __device__ __forceinline__ void dg_row_load(const float* __restrict__ p, float (&r)[C]) {
   if constexpr (C % 4 == 0) {

@@ -5,42 +5,26 @@
 //   surface_mask_kernel      surf[v] = set[v] != 0 && a face neighbour (6 in the volume, or 4 in the slice) is unset or
 //                            lies outside the volume
 //   edt_rows_kernel          pass 1, one workgroup per row: g[x] = distance in voxels to the nearest set voxel of the
-//                            row (two-sided scan), 16-bit, EDT_NONE for a row without one
+//                            row, 16-bit, EDT_NONE for a row without one
 //   edt_axis_kernel<true>    pass 2, along H:  F[y]  = min_y' fl(fl(g[y']^2 wx) + fl((y - y')^2 wy))
 //   edt_axis_kernel<false>   pass 3, along D:  d2[z] = min_z' fl(F[z'] + fl((z - z')^2 wz))
 //   surface_sums_kernel, surface_sums_finish_kernel
 //                            count, max d2, sum sqrt(d2) and the number of infinite d2 over the voxels with surf != 0:
 //                            one partial per block, then one block adds the partials in index order
 //
-// Rounding is monotone, so the minimum over the set voxels of fl(fl(fl(dx^2 wx) + fl(dy^2 wy)) + fl(dz^2 wz)) equals
-// the three nested minima bit for bit; a minimum of doubles does not depend on its order, so nothing here does.  The
-// integer squares are exact in double (< 2^24).  No atomics.
-//
-// Passes 2 and 3 are one kernel over a (batch, rows, columns) view with the columns contiguous: (D, H, W) for pass 2
-// and (1, D, H*W) for pass 3.  Lanes run along the columns, so every global access is coalesced.  A workgroup of four
-// waves owns 64 columns x 16 output rows (four rows per thread, in registers) and walks all candidate rows in chunks
-// of 64 staged in LDS as doubles (32 KiB, so four workgroups fit the 160 KiB of a CU); a staged value serves the
-// thread's four outputs, and the four axis terms of a thread shift along as the candidate row advances (the term depends
-// on the row difference alone), so a candidate costs one add and one minimum.  Work is O(rows) per voxel.
-#include "common.h"
-
-#include <math.h>
+// The scan of pass 1, the sweep of passes 2 and 3 and the reasons why the nested minima are exact are edt.h's.  This
+// file owns what a pass reads and writes: passes 2 and 3 are one kernel over a (batch, rows, columns) view with the
+// columns contiguous, (D, H, W) for pass 2 and (1, D, H*W) for pass 3.
+#include "edt.h"
 
 #include "../../include/depgan.h"
 
-// Every double operation below is rounded on its own, as the NumPy restatement's statements are.  The arithmetic is
-// written with plain operators on purpose: the pragma governs the operations of THIS text, while __dmul_rn / __dadd_rn
-// are inline functions of the HIP headers and carry the headers' contraction mode, so a __dmul_rn fed into a __dadd_rn
-// compiles to one v_fma_f64 (seen in this file's first version: one rounding instead of two, an ulp off).
+// every double operation of this file is rounded on its own too (edt.h has the reasons)
 #pragma clang fp contract(off)
 
 namespace {
 
-constexpr int EDT_MAX_DIM = 4096;
 constexpr unsigned short EDT_NONE = 0xFFFF;      // pass 1: the row has no set voxel (a distance is at most 4095)
-constexpr int EDT_COLS = 64, EDT_CHUNK = 64, EDT_ROWS_PER_THREAD = 4, EDT_TILE_ROWS = 16;
-static_assert(EDT_ROWS_PER_THREAD == 4 && EDT_CHUNK % 4 == 0 && EDT_TILE_ROWS == 4 * EDT_ROWS_PER_THREAD,
-              "edt_axis_kernel: four waves of four rows, candidate rows in steps of four");
 constexpr int SUMS_MAX_BLOCKS = 1024, SUMS_PER_THREAD = 8;
 
 // grid ceil(n / 256), block 256, thread = voxel.  HW = H * W; n = D * H * W < 2^31.
@@ -62,67 +46,17 @@ __global__ __launch_bounds__(256) void surface_mask_kernel(const unsigned char* 
   surf[v] = s ? 1 : 0;
 }
 
-// grid D * H, block 256, workgroup = row.  Thread t owns the run [t * run, (t + 1) * run) of the row, run =
-// ceil(W / 256) <= 16: the last set voxel at or before the run's end and the first at or after its start come from a
-// scan over the 256 run summaries, the rest is the two-sided scan inside the run.
+// grid D * H, block 256, workgroup = row: the scan of edt.h over the row's bytes, a set voxel being a hit
 __global__ __launch_bounds__(256) void edt_rows_kernel(const unsigned char* __restrict__ set,
                                                        unsigned short* __restrict__ g, int W) {
-  __shared__ unsigned char row[EDT_MAX_DIM];
-  __shared__ int last_s[256], first_s[256];
-  const int t = threadIdx.x;
+  __shared__ unsigned char row[DG_EDT_MAX_DIM];
   const size_t base = (size_t)blockIdx.x * W;
-  for (int x = t; x < W; x += 256) row[x] = set[base + x];
+  for (int x = threadIdx.x; x < W; x += 256) row[x] = set[base + x];
   __syncthreads();
-  const int NONE = 1 << 20;                           // beyond any distance: |x - (+-NONE)| > 4095
-  const int run = (W + 255) / 256;
-  const int x0 = t * run, x1 = min(W, x0 + run);      // x0 may lie beyond W: an empty run
-  int last = -NONE, first = NONE;
-  for (int x = x0; x < x1; ++x)
-    if (row[x]) {
-      last = x;
-      if (first == NONE) first = x;
-    }
-  last_s[t] = last;
-  first_s[t] = first;
-  __syncthreads();
-  // inclusive prefix maximum of last_s, inclusive suffix minimum of first_s
-  for (int o = 1; o < 256; o <<= 1) {
-    const int a = t >= o ? last_s[t - o] : -NONE;
-    const int b = t + o < 256 ? first_s[t + o] : NONE;
-    __syncthreads();
-    last_s[t] = max(last_s[t], a);
-    first_s[t] = min(first_s[t], b);
-    __syncthreads();
-  }
-  int left[16];                                       // run <= 16 (W <= 4096)
-  int cur = t > 0 ? last_s[t - 1] : -NONE;
-#pragma unroll
-  for (int i = 0; i < 16; ++i) {
-    const int x = x0 + i;
-    if (x < x1) {
-      if (row[x]) cur = x;
-      left[i] = x - cur;
-    }
-  }
-  cur = t < 255 ? first_s[t + 1] : NONE;
-#pragma unroll
-  for (int i = 15; i >= 0; --i) {
-    const int x = x0 + i;
-    if (x < x1) {
-      if (row[x]) cur = x;
-      const int d = min(left[i], cur - x);
-      g[base + x] = d >= EDT_MAX_DIM ? EDT_NONE : (unsigned short)d;
-    }
-  }
-}
-
-// One v_min_f64.  fmin() compiles to three: IEEE minNum first canonicalises every operand it cannot prove free of
-// signalling NaNs (dg_vmax of common.h).  No operand here is a NaN: a staged value is >= 0 or +inf and a term is >= 0
-// (the weights are finite and > 0, checked by the entry), so no inf - inf and no 0 * inf arises.
-__device__ __forceinline__ double edt_min(double a, double b) {
-  double o;
-  asm("v_min_f64 %0, %1, %2" : "=v"(o) : "v"(a), "v"(b));
-  return o;
+  unsigned short* grow = g + base;
+  dg_edt_row_scan<false>(
+      W, [&](int x) { return row[x] != 0; },
+      [&](int x, int d) { grow[x] = d >= DG_EDT_MAX_DIM ? EDT_NONE : (unsigned short)d; });
 }
 
 // grid (ceil(ncols / 64), ceil(nrows / 16), batch), block 256.  src is (batch, nrows, ncols): the 16-bit row distances
@@ -131,66 +65,28 @@ __device__ __forceinline__ double edt_min(double a, double b) {
 template <bool FROM_G>
 __global__ __launch_bounds__(256) void edt_axis_kernel(const void* __restrict__ src, double* __restrict__ dst,
                                                        int nrows, int ncols, double w_src, double w_axis) {
-  __shared__ double stage[EDT_CHUNK][EDT_COLS];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const unsigned col = blockIdx.x * (unsigned)EDT_COLS + (unsigned)lane;       // < 2^31 + 64: ncols < 2^31
+  const unsigned col = blockIdx.x * (unsigned)DG_EDT_COLS + (unsigned)lane;    // < 2^31 + 64: ncols < 2^31
   const bool live = col < (unsigned)ncols;
   const size_t base = (size_t)blockIdx.z * (size_t)nrows * (size_t)ncols;
-  const int r0 = (int)blockIdx.y * EDT_TILE_ROWS + wave * EDT_ROWS_PER_THREAD;
-  const double inf = INFINITY;
-  double best[EDT_ROWS_PER_THREAD];
-#pragma unroll
-  for (int k = 0; k < EDT_ROWS_PER_THREAD; ++k) best[k] = inf;
-  for (int c0 = 0; c0 < nrows; c0 += EDT_CHUNK) {
-    const int cn = min(EDT_CHUNK, nrows - c0);
-    const int cn4 = (cn + 3) & ~3;                         // <= EDT_CHUNK, a multiple of 4
-    __syncthreads();                                       // the previous chunk has been read
-    for (int r = wave; r < cn4; r += 4) {
-      double a = inf;
-      if (live && r < cn) {
-        const size_t at = base + (size_t)(c0 + r) * (size_t)ncols + (size_t)col;
-        if (FROM_G) {
-          const unsigned short gv = ((const unsigned short*)src)[at];
-          if (gv != EDT_NONE) {
-            const double gd = (double)gv;
-            a = (gd * gd) * w_src;                          // gd * gd is exact
-          }
-        } else {
-          a = ((const double*)src)[at];
-        }
+  const int r0 = (int)blockIdx.y * DG_EDT_TILE_ROWS + wave * DG_EDT_ROWS_PER_THREAD;
+  double best[DG_EDT_ROWS_PER_THREAD];
+  const bool in[DG_EDT_ROWS_PER_THREAD] = {};
+  dg_edt_axis_sweep<64, false>(nrows, r0, live, w_axis, in, [&](int r, double& a, double&) {
+    const size_t at = base + (size_t)r * (size_t)ncols + (size_t)col;
+    if (FROM_G) {
+      const unsigned short gv = ((const unsigned short*)src)[at];
+      if (gv != EDT_NONE) {
+        const double gd = (double)gv;
+        a = (gd * gd) * w_src;                              // gd * gd is exact
       }
-      stage[r][lane] = a;
+    } else {
+      a = ((const double*)src)[at];
     }
-    __syncthreads();
-    // The axis term of output row r_k against candidate row r' depends on r_k - r' alone, so stepping r' by one
-    // shifts the thread's four terms along and needs one new one, fl((r_0 - r')^2 w_axis), the square exact.  Four
-    // steps bring the names back to where they were, so the shift costs no moves.
-    double e = (double)(r0 - c0);                           // r_0 - r'
-    double t0 = (e * e) * w_axis;
-    double t1 = ((e + 1.0) * (e + 1.0)) * w_axis;
-    double t2 = ((e + 2.0) * (e + 2.0)) * w_axis;
-    double t3 = ((e + 3.0) * (e + 3.0)) * w_axis;
-#define EDT_STEP(R, T0, T1, T2, T3)        \
-  {                                        \
-    const double a = stage[r + R][lane];   \
-    best[0] = edt_min(best[0], a + T0);    \
-    best[1] = edt_min(best[1], a + T1);    \
-    best[2] = edt_min(best[2], a + T2);    \
-    best[3] = edt_min(best[3], a + T3);    \
-    e = e - 1.0;                           \
-    T3 = (e * e) * w_axis;                 \
-  }
-    for (int r = 0; r < cn4; r += 4) {                      // rows cn .. cn4 - 1 hold +inf
-      EDT_STEP(0, t0, t1, t2, t3)
-      EDT_STEP(1, t3, t0, t1, t2)
-      EDT_STEP(2, t2, t3, t0, t1)
-      EDT_STEP(3, t1, t2, t3, t0)
-    }
-#undef EDT_STEP
-  }
+  }, best);
   if (live) {
 #pragma unroll
-    for (int k = 0; k < EDT_ROWS_PER_THREAD; ++k)
+    for (int k = 0; k < DG_EDT_ROWS_PER_THREAD; ++k)
       if (r0 + k < nrows) dst[base + (size_t)(r0 + k) * (size_t)ncols + (size_t)col] = best[k];
   }
 }
@@ -259,15 +155,13 @@ bool overlaps(const void* a, size_t na, const void* b, size_t nb) {
   return a0 < b0 + nb && b0 < a0 + na;
 }
 
-// D, H, W in 1..4096 and D*H*W < 2^31
+// D, H, W in 1..DG_EDT_MAX_DIM and D*H*W < 2^31
 bool volume_ok(int D, int H, int W) {
-  if (D < 1 || H < 1 || W < 1 || D > EDT_MAX_DIM || H > EDT_MAX_DIM || W > EDT_MAX_DIM) return false;
+  if (D < 1 || H < 1 || W < 1 || D > DG_EDT_MAX_DIM || H > DG_EDT_MAX_DIM || W > DG_EDT_MAX_DIM) return false;
   return (long)D * H * W < (1L << 31);
 }
 
 bool weight_ok(double w) { return isfinite(w) && w > 0.0; }
-
-size_t round8(size_t b) { return (b + 7) & ~(size_t)7; }
 
 }  // namespace
 
@@ -277,7 +171,7 @@ int depgan_eval_surface_mask(const unsigned char* set, int D, int H, int W, int 
                              void* stream) {
   if (!volume_ok(D, H, W) || !set || !surf || (in_plane != 0 && in_plane != 1)) {
     dg_set_error("eval_surface_mask: bad argument (D=%d H=%d W=%d in_plane=%d; dimensions 1..%d, D*H*W < 2^31)", D, H,
-                 W, in_plane, EDT_MAX_DIM);
+                 W, in_plane, DG_EDT_MAX_DIM);
     return DG_ERR_ARG;
   }
   const size_t n = (size_t)D * H * W;
@@ -294,14 +188,14 @@ int depgan_eval_surface_mask(const unsigned char* set, int D, int H, int W, int 
 size_t depgan_eval_edt_scratch_bytes(int D, int H, int W) {
   if (!volume_ok(D, H, W)) return 0;
   const size_t n = (size_t)D * H * W;
-  return n * sizeof(double) + round8(n * sizeof(unsigned short));     // F, then g
+  return n * sizeof(double) + dg_edt_round8(n * sizeof(unsigned short));     // F, then g
 }
 
 int depgan_eval_edt_sq(const unsigned char* set, int D, int H, int W, double wz, double wy, double wx, double* d2,
                        void* scratch, void* stream) {
   if (!volume_ok(D, H, W) || !set || !d2 || !scratch || ((uintptr_t)scratch & 7) || ((uintptr_t)d2 & 7)) {
     dg_set_error("eval_edt_sq: bad argument (D=%d H=%d W=%d; dimensions 1..%d, D*H*W < 2^31; set, d2 and scratch "
-                 "given, d2 and scratch 8-byte aligned)", D, H, W, EDT_MAX_DIM);
+                 "given, d2 and scratch 8-byte aligned)", D, H, W, DG_EDT_MAX_DIM);
     return DG_ERR_ARG;
   }
   if (!weight_ok(wz) || !weight_ok(wy) || !weight_ok(wx)) {
@@ -319,11 +213,11 @@ int depgan_eval_edt_sq(const unsigned char* set, int D, int H, int W, double wz,
   unsigned short* g = (unsigned short*)((char*)scratch + n * sizeof(double));
   hipLaunchKernelGGL(edt_rows_kernel, dim3((unsigned)(D * H)), dim3(256), 0, st, set, g, W);
   // a single slice has no third pass: fl(F + fl(0 wz)) = F
-  const dim3 g2((unsigned)cdiv(W, EDT_COLS), (unsigned)cdiv(H, EDT_TILE_ROWS), (unsigned)D);
+  const dim3 g2((unsigned)cdiv(W, DG_EDT_COLS), (unsigned)cdiv(H, DG_EDT_TILE_ROWS), (unsigned)D);
   hipLaunchKernelGGL(edt_axis_kernel<true>, g2, dim3(256), 0, st, (const void*)g, D == 1 ? d2 : F, H, W, wx, wy);
   if (D > 1) {
     const long HW = (long)H * W;
-    const dim3 g3((unsigned)cdiv(HW, EDT_COLS), (unsigned)cdiv(D, EDT_TILE_ROWS), 1);
+    const dim3 g3((unsigned)cdiv(HW, DG_EDT_COLS), (unsigned)cdiv(D, DG_EDT_TILE_ROWS), 1);
     hipLaunchKernelGGL(edt_axis_kernel<false>, g3, dim3(256), 0, st, (const void*)F, d2, D, (int)HW, 0.0, wz);
   }
   HIPCHECK(hipGetLastError());

@@ -149,9 +149,14 @@ struct DgDiceSetting {
 // partials added in index order in double; dg_dice_scratch(P, C) floats of scratch (at most 1024 * 3 C).
 int dg_dice_check(const char* who, int form, float ce_coef, float dice_coef, float smooth, const float* coef, int n,
                   int C);
-// the operands' checks alone (no HIP call): what an entry asks before it allocates
-int dg_dice_operands_check(const char* who, const float* probs, DgLabels lab, int ignore_code, const float* dz, long P,
-                           int C);
+// What the losses behind the cross-entropy share, each without a HIP call: C in DG_MIN_CLASSES..DG_MAX_CLASSES; n == C
+// class coefficients, each finite and >= 0, at least one > 0; and the operands' checks alone, what an entry asks before
+// it allocates -- probs, the labels, the ignore code, P >= 1 (p_below_2_31: and < 2^31), one more operand where
+// extra_name names it (the boundary loss's phi), and the alignment of every row pointer for C classes.
+int dg_class_count_check(const char* who, int C);
+int dg_class_coef_check(const char* who, const float* coef, int n, int C);
+int dg_loss_operands_check(const char* who, const float* probs, const char* extra_name, const float* extra, DgLabels lab,
+                           int ignore_code, const float* dz, long P, bool p_below_2_31, int C);
 size_t dg_dice_scratch(long P, int C);
 int dg_dice_loss(const float* probs, DgLabels lab, int ignore_code, const DgDiceSetting& set, float* dz, DgDiceDev* out,
                  long P, int C, float* scratch, size_t scratch_floats, hipStream_t st);
@@ -178,8 +183,8 @@ struct DgBoundaryDev {
 };
 // the values of a setting, without a HIP call: coef null or n == C values
 int dg_boundary_check(const char* who, float boundary_coef, const float* coef, int n, int C);
-// the geometry of a signed distance call, without a HIP call: n >= 1, H and W in 1..4096, n H W < 2^31, n H and the
-// 64 x 16 tiles of all n C maps each < 2^24 (the two grids), C in 2..8
+// the geometry of a signed distance call, without a HIP call: n >= 1, H and W within edt.h's limit, n H W < 2^31, n H
+// and the 64 x 16 tiles of all n C maps each < 2^24 (the two grids), C in 2..8
 int dg_signed_distance_check(const char* who, long n, int H, int W, int C, double sy, double sx, double inside_offset);
 // phi (n, H, W, C) float32 of n label slices: the classes of class_mask get their map, the others 0.  ignore_code as
 // dg_dice_loss takes it.  Two launches whatever n; dg_signed_distance_scratch_bytes(n, H, W, classes) of scratch, where
@@ -190,8 +195,6 @@ int dg_signed_distance(DgLabels lab, int ignore_code, long n, int H, int W, int 
 // L_B and, with dz, dz += boundary_coef p (g - sum p g).  counts: null for M = P, else the label pre-pass counts
 // (DgCeDev::counts) on the device, M = P - counts[1] - counts[2].  dg_boundary_scratch(P) doubles of scratch (at most
 // 1024), 8-byte aligned.  One partial per block, added in index order by one block: no atomics, nothing to zero.
-int dg_boundary_operands_check(const char* who, const float* probs, const float* phi, DgLabels lab, int ignore_code,
-                               const float* dz, long P, int C);
 size_t dg_boundary_scratch(long P);
 int dg_boundary_loss(const float* probs, const float* phi, DgLabels lab, int ignore_code, const float* class_coef,
                      float boundary_coef, const unsigned long long* counts, float* dz, DgBoundaryDev* out, long P, int C,

@@ -6,7 +6,8 @@ elements per thread, a column past the staging chunk); contents empty, full, a c
 zero: slices do not leak), one pixel in opposite corners, a checkerboard, random at densities 0.01 and 0.5; C = 2, 3, 4,
 8, spacings (1, 1), (0.9375, 0.9375), (0.977, 1.013), inside_offset 0 and the spacing's minimum, a class switched off.
 Class 1 follows the content, the other pixels are spread over the other classes, so every class has a map to check.
-Exact too: codes against one-hot rows, an ignore code against all-zero rows, a second call into the same buffers.
+Exact too: codes against one-hot rows, an ignore code against all-zero rows, a second call into the same buffers, and
+phi of one class against depgan_eval_edt_sq run on every slice (the two entries share one distance-transform text).
 
 The loss and dz against float64 formed from the device's own stored probabilities and phi, P = 1 (one thread), 255 (a
 ragged block), 3219 (a ragged grid of 13 blocks) and 262181 (37 pixels past the 1024-block cap, where the grid-stride loop
@@ -93,6 +94,39 @@ def test_phi_equals_the_restatement_bit_for_bit(lib, shape):
                 assert np.any(phi[0, :, :, 1] != 0)
             if on is not None:
                 assert all(np.all(phi[..., k] == 0) for k in range(Cc) if not on[k])
+
+
+def _edt_sq_slice(lib, member, wy, wx):
+    """depgan_eval_edt_sq on one (H, W) slice as a (1, H, W) volume: float64 squared distances to the nearest member."""
+    H, W = member.shape
+    s = torch.from_numpy(np.ascontiguousarray(member, np.uint8)).cuda()
+    d2 = torch.full((H, W), float("nan"), dtype=torch.float64, device="cuda:0")
+    scratch = torch.empty((lib.depgan_eval_edt_scratch_bytes(1, H, W) // 8,), dtype=torch.float64, device="cuda:0")
+    assert lib.depgan_eval_edt_sq(P_(s), 1, H, W, 1.0, wy, wx, P_(d2), P_(scratch), None) == 0, lib.depgan_last_error()
+    torch.cuda.synchronize()
+    return d2.cpu().numpy()
+
+
+@pytest.mark.parametrize("shape", SHAPES, ids=lambda s: "x".join(map(str, s)))
+def test_phi_is_the_surface_distance_transform_of_the_slice(lib, shape):
+    """The invariant the shared distance-transform text exists for: phi of class 1 is, in every pixel of every slice,
+    the square root of what depgan_eval_edt_sq gives for S = {label == 1} (outside S) or for its complement (inside S,
+    negated and shifted by inside_offset), rounded once to float32, and 0 where that distance is infinite.  IEEE sqrt
+    is correctly rounded on both sides, so the comparison is on bits."""
+    n, H, W = shape
+    for content in ("empty", "full", "corners", "checker", "random0.01", "random0.5"):
+        codes = _labels(shape, content, 2)
+        for (sy, sx), off in (((1.0, 1.0), 0.0), ((0.977, 1.013), 0.977)):
+            rc, phi = _phi(lib, codes, 2, (sy, sx), off, on=(0, 1))
+            assert rc == 0, lib.depgan_last_error()
+            assert np.all(phi[..., 0] == 0)
+            for z in range(n):
+                S = codes[z] == 1
+                out = np.sqrt(_edt_sq_slice(lib, S, sy * sy, sx * sx)).astype(np.float32)
+                ins = (-(np.sqrt(_edt_sq_slice(lib, ~S, sy * sy, sx * sx)) - off)).astype(np.float32)
+                want = np.where(S, ins, out)
+                want[~np.isfinite(want)] = 0.0
+                np.testing.assert_array_equal(_u32(phi[z, :, :, 1]), _u32(want), err_msg=str((content, sy, sx, off, z)))
 
 
 @pytest.mark.parametrize("Cc", [2, 3, 4, 8])
