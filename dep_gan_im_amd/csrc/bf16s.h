@@ -49,7 +49,14 @@ int dg_conv_bf16s(int KS, const ConvArgsH& a, hipStream_t st);
 // every check of dg_conv_bf16s but the weight panels' pointers, no HIP call: what an entry that packs its weights into a
 // temporary runs first, so that a call it refuses allocates and launches nothing
 int dg_conv_bf16s_check(int KS, const ConvArgsH& a);
-const char* dg_conv_bf16s_name(int KS, bool head = false);
+// the entry dg_conv_bf16s launches (its name is what the profiles print)
+const DgKernel* dg_conv_bf16s_kernel(int KS, bool head = false);
+// dynamic LDS of the kernels built from igemm_bf16s_kernel.inc / igemm_bf16_main.inc: the halo tile and the staged taps of
+// 32 weight rows, in 80-byte rows, or the epilogue transpose where that is larger
+constexpr int dg_bf16s_lds(int KS, int TAPG) {
+  const size_t k = (size_t)((16 + KS - 1) * (16 + KS - 1) + TAPG * 32) * 80, e = (size_t)4 * 64 * (32 + 4) * sizeof(float);
+  return (int)(k > e ? k : e);
+}
 
 // gen_0: 3x3, Cin in {1, 2}, dense fp32 input, HWIO fp32 weights, affine + ReLU, bf16 output; Cout % 8 == 0, <= 32
 struct EdgeArgsH {

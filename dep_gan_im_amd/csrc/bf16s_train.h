@@ -14,6 +14,7 @@ struct ConvArgsHT : ConvArgsH {
 };
 int dg_conv_bf16s_train(const ConvArgsHT& a, hipStream_t st);
 int dg_conv_bf16s_train_check(const ConvArgsHT& a);   // its checks but the weight panel's pointer, no HIP call
+const DgKernel* dg_conv_bf16s_train_kernel();            // the entry it launches
 static inline size_t dg_film_dec_bytes(int B, int H, int W, int C) { return (size_t)B * H * W * (C / 8); }
 
 // Backward-data (3x3, or 1x1 with ConvArgs::cpt gathering the four grids of a transposed convolution) on the same
@@ -21,7 +22,7 @@ static inline size_t dg_film_dec_bytes(int B, int H, int W, int C) { return (siz
 // operand is a bf16 view: out = accumulate ? out + v : v, v = (mask_h > 0) ? acc + res : 0.  Of a.ep only res and
 // accumulate are read (everything else must be unset); a.Cout % 32 == 0, a.Cin % 4 == 0.
 int dg_conv_bf16_mh(const ConvPlan& pl, const ConvArgs& a, TViewH mask_h, hipStream_t st);
-const char* dg_conv_bf16_mh_name(int KS);
+const DgKernel* dg_conv_bf16_mh_kernel(int KS);   // the entry it launches
 
 // Weight gradient on the bf16 pipe, activation operand staged from bf16 memory (16-byte pieces of 8 bf16, no rounding
 // step), dy staged as fp32 and rounded while committed: the same included text as wgrad_bf16_kernel

@@ -199,6 +199,30 @@ struct DgOncePerDevice {   // `if (once.need()) { set attribute ... }`; a device
     return true;
   }
 };
+// One kernel instantiation a launcher can take: its address, the name rocprofv3 prints for it, and the
+// MaxDynamicSharedMemorySize it needs (0 = none).  The attribute belongs to the ENTRY, not to a launch: the wave-private
+// kernels launch with LDS sizes that depend on Cin and the wave count, and all of them must fit what was set once.
+// Every conv launcher keeps a static table of these; the launch and the reported name read the same entry.
+struct DgKernel {
+  const void* fn;
+  const char* name;
+  int attr_lds;
+  mutable DgOncePerDevice once = {};
+};
+// the attribute, once per (device, entry)
+static inline int dg_kernel_ready(const DgKernel& k) {
+  if (k.attr_lds && k.once.need()) HIPCHECK(hipFuncSetAttribute(k.fn, hipFuncAttributeMaxDynamicSharedMemorySize, k.attr_lds));
+  return DG_OK;
+}
+// args: the kernel's one by-value argument struct
+static inline int dg_launch(const DgKernel& k, unsigned grid, unsigned block, size_t lds, const void* args, hipStream_t st,
+                            unsigned grid_y = 1) {
+  DGCHECK(dg_kernel_ready(k));
+  void* kargs[] = {const_cast<void*>(args)};
+  HIPCHECK(hipLaunchKernel(k.fn, dim3(grid, grid_y), dim3(block), kargs, lds, st));
+  HIPCHECK(hipGetLastError());
+  return DG_OK;
+}
 static inline int dg_cu_count() {   // CUs of the current device, asked once per device (the query is slower than a launch)
   static int cus[DG_MAX_DEVICES] = {};
   const int d = dg_device_slot();
@@ -256,11 +280,8 @@ ConvPlan dg_plan_conv_bf16(int KS, int Cin, int Cout);
 // the 16-output-channel 5x5 form of the bf16 plan (MF = NT = 16, CK = 32): KS == 5, Cout % 16 == 0, Cin >= 8,
 // Cin % 4 == 0; else the fp32 plan.  Opt-in per context (depgan_set_critic16_pipe) and operator path 10
 ConvPlan dg_plan_conv_bf16_n16(int KS, int Cin, int Cout);
-// name of the instantiation dg_conv_igemm_bf16 launches for a CONV_BF16 plan, as rocprofv3 prints it
-const char* dg_conv_igemm_bf16_name(const ConvPlan& pl);
 // fp32 operands split into `planes` (2 or 3) bf16 terms each, 3 or 6 products on the bf16 pipe (igemm_split_kernel)
 ConvPlan dg_plan_conv_split(int KS, int Cin, int Cout, int planes);
-int dg_conv_igemm_bf16(const ConvPlan& pl, const ConvArgs& a, hipStream_t st);
 // bytes of packed storage per element of the plain [nt][cc][tap][n][k] panel (split plans store `planes` planes of it)
 static inline size_t dg_plan_elem_bytes(const ConvPlan& pl) { return pl.planes ? 2 * (size_t)pl.planes : 4; }
 
@@ -296,28 +317,52 @@ int dg_pack_weights_batch(const PackJob* jobs_dev, int njobs, unsigned nblocks, 
 int dg_pack_weights(const ConvPlan& pl, const float* src, int srcI, int srcO, int io, int transpose, int flip,
                     const float* kscale, float* dst, hipStream_t st);
 
+// ---- one prepared convolution launch (conv_select.hip) ----
+// THE rule that says which kernel a convolution takes (dg_conv_prepare; host only, no launch, no allocation):
+//   a plan that is not MFMA                 the direct kernels (direct.hip), profile class 2
+//   else dg_conv_igemm_check, then by plan  CONV_BF16 / CONV_SPLIT (igemm_bf16.hip), CONV_WINO (igemm_wino.hip)
+//   CONV_TILE                               wave-private 3x3 (opt-in), weight-stationary 5x5, else the tile instantiation
+// `routes` says which of the CONV_TILE kernels may be taken: all of them (the model), the tile kernels only (the reference
+// the others must match bit for bit), or ONE of the wave-private families without the tile bit -- forced: the shape test
+// alone decides, and a launch it does not cover is refused.
+enum { DG_ROUTE_TILE = 1, DG_ROUTE_WP = 2, DG_ROUTE_WS5 = 4, DG_ROUTE_ALL = 7 };
+struct DgConvLaunch {
+  const DgKernel* k;
+  unsigned grid, grid_y, block;
+  size_t lds;
+  int klass;    // profile class: 0 MFMA, 2 direct
+  ConvArgs a;   // lgx, lgy and vec4 filled
+};
+// the plan of one convolution of a context in the given mode: split or bf16 matrix pipe where configured and covered, else
+// fp32 -- Winograd for the 3x3 layers it covers, else the tile plan with its chunk size by launch size.  N, H, W: the
+// batch and spatial size the layer is planned for (0: unknown, as for the 1x1 layers)
+ConvPlan dg_conv_plan(int f32_split, int bf16_mfma, int winograd, int KS, int Cin, int Cout, int N, int H, int W);
+int dg_conv_prepare(const ConvPlan& pl, const ConvArgs& a, int KS, unsigned routes, DgConvLaunch* out);
+int dg_conv_run(const DgConvLaunch& L, hipStream_t st);
+// prepare and run with every route open: what the model launches for (pl, a)
 int dg_conv_igemm(const ConvPlan& pl, const ConvArgs& a, hipStream_t st);
+// Each family's own part of dg_conv_prepare: the entry of its table and the geometry of the launch
+int dg_conv_direct_prepare(int KS, const ConvArgs& a, DgConvLaunch* out);
+int dg_conv_tile_prepare(const ConvPlan& pl, const ConvArgs& a, DgConvLaunch* out);
+int dg_conv_bf16_prepare(const ConvPlan& pl, const ConvArgs& a, DgConvLaunch* out);
+int dg_conv_wino_prepare(const ConvPlan& pl, const ConvArgs& a, DgConvLaunch* out);
+int dg_conv_wp_prepare(const ConvPlan& pl, const ConvArgs& a, DgConvLaunch* out);
+int dg_conv_ws5_prepare(const ConvPlan& pl, const ConvArgs& a, DgConvLaunch* out);
 // the argument checks of the MFMA launchers (alignment, fused pool, gathered K, fused head); sets the error text
 int dg_conv_igemm_check(const ConvPlan& pl, const ConvArgs& a);
 // wave-private 3x3 kernel (igemm_wp.hip): no workgroup barrier in steady state; reads the 8-channel-chunk plan's panel
 bool dg_conv_igemm_wp_supported(const ConvPlan& pl, const ConvArgs& a, bool force);
-int dg_conv_igemm_wp(const ConvPlan& pl, const ConvArgs& a, hipStream_t st);
 // weight-stationary, wave-private 5x5 kernel (igemm_wp.hip): Cin, Cout in {16, 32}, one channel tile; reads the packed
 // panel of the 5x5 tile plans as it is and is bit-identical to igemm_conv_kernel<., 5, ., 25>
 bool dg_conv_igemm_ws5_supported(const ConvPlan& pl, const ConvArgs& a, bool force);
-int dg_conv_igemm_ws5(const ConvPlan& pl, const ConvArgs& a, hipStream_t st);
-const char* dg_conv_igemm_ws5_name(const ConvPlan& pl);
-int dg_conv_igemm_tile(const ConvPlan& pl, const ConvArgs& a, hipStream_t st);
 // the launch for (pl, a) can carry the fused one-channel head (Epilogue::head_*): 32 -> 32, 8-channel-chunk 3x3 kernel
 bool dg_conv_igemm_head_supported(const ConvPlan& pl, const ConvArgs& a);
 // Winograd F(2x2,3x3) kernel (igemm_wino.hip): plan family CONV_WINO, panel [nt][chunk][16 frequencies][32][8] of G g G^T
 ConvPlan dg_plan_conv_wino(int Cin, int Cout);
 bool dg_conv_wino_supported(const ConvPlan& pl, const ConvArgs& a);
-const char* dg_conv_wino_name(const ConvArgs& a);
-int dg_conv_wino(const ConvPlan& pl, const ConvArgs& a, hipStream_t st);
 // Epilogue classes of the Winograd kernel: instantiations whose epilogue flags are compile-time constants, one per flag
 // set the model launches (the table in igemm_wino.hip).  The flag set of an Epilogue as a bit mask (DEPGAN_EPF_* of
-// include/depgan.h), and the pure host function both the launcher and dg_conv_wino_name select with: form 0 the 8-row
+// include/depgan.h), and the pure host function dg_conv_wino_prepare selects with: form 0 the 8-row
 // kernel, 1 the fused-head kernel, 2 the 16-row kernel without head, 3 gathered K.  Class 0 is the generic kernel (run-time
 // flags): any set outside the table, forms 2 and 3, and everything while the process-wide switch is off.
 enum { DG_EPF_BIAS = 1, DG_EPF_AFFINE = 2, DG_EPF_FILM = 4, DG_EPF_RELU = 8, DG_EPF_PRE = 16, DG_EPF_RES = 32,
@@ -326,9 +371,6 @@ unsigned dg_epilogue_flags(const Epilogue& e);
 int dg_wino_epi_class(unsigned flags, int form);
 void dg_set_epi_classes(int on);
 int dg_get_epi_classes();
-// name of the kernel instantiation dg_conv_igemm launches for (pl, a), as rocprofv3 prints it
-void dg_conv_igemm_name(const ConvPlan& pl, const ConvArgs& a, char* buf, size_t cap);
-int dg_conv_direct(int KS, const ConvArgs& a, hipStream_t st);
 
 // wgrad: returns number of chunks used through *nchunks; part must hold nchunks slabs of KS * KS * Cin * Cout floats
 // (DgWgradChoice::part_floats).

@@ -292,37 +292,34 @@ __global__ __launch_bounds__(256, 1) void deconv_fwd_kernel(DeconvArgs a) {
 #endif
 }
 
-template <int CIN, int MT, bool WIDE>
-int launch_w(const DeconvArgs& a, int ny, hipStream_t st) {
-  using C = DCfg<CIN, MT>;
-  static int per_cu_dev[DG_MAX_DEVICES] = {};   // occupancy and the LDS attribute belong to the device
-  const int slot = dg_device_slot();
-  int per_cu = slot >= 0 ? per_cu_dev[slot] : 0;
+// Every instantiation, [Cin: 64, 96, 128][W >= 32]; the profiles know them all as "deconv_fwd_kernel"
+#define DECONV_K(CIN, MT, WIDE) {reinterpret_cast<const void*>(&deconv_fwd_kernel<CIN, MT, WIDE>), "deconv_fwd_kernel", DCfg<CIN, MT>::LDS_BYTES}
+const DgKernel kDeconv[3][2] = {{DECONV_K(64, 2, false), DECONV_K(64, 2, true)},
+                                {DECONV_K(96, 3, false), DECONV_K(96, 3, true)},
+                                {DECONV_K(128, 2, false), DECONV_K(128, 2, true)}};
+#undef DECONV_K
+
+int launch(const DgKernel& k, const DeconvArgs& a, int ny, hipStream_t st) {
+  static int per_cu_dev[6][DG_MAX_DEVICES] = {};   // occupancy belongs to the device
+  const int slot = dg_device_slot(), e = (int)(&k - &kDeconv[0][0]);
+  int per_cu = slot >= 0 ? per_cu_dev[e][slot] : 0;
   if (!per_cu) {
-    HIPCHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&deconv_fwd_kernel<CIN, MT, WIDE>),
-                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)C::LDS_BYTES));
+    DGCHECK(dg_kernel_ready(k));
     int occ = 0;
-    HIPCHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, deconv_fwd_kernel<CIN, MT, WIDE>, 256, C::LDS_BYTES));
+    HIPCHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, k.fn, 256, (size_t)k.attr_lds));
     if (occ < 1) occ = 1;
-    if (const char* e = getenv("DEPGAN_DECONV_PER_CU")) {
-      const int v = atoi(e);
+    if (const char* env = getenv("DEPGAN_DECONV_PER_CU")) {
+      const int v = atoi(env);
       if (v >= 1 && v < occ) occ = v;
     }
     per_cu = occ;
-    if (slot >= 0) per_cu_dev[slot] = occ;
+    if (slot >= 0) per_cu_dev[e][slot] = occ;
   }
   const int cus = dg_cu_count();
   int gx = cus * per_cu / ny;
   if (gx > a.nTiles) gx = a.nTiles;
   if (gx < 1) gx = 1;
-  hipLaunchKernelGGL((deconv_fwd_kernel<CIN, MT, WIDE>), dim3(gx, ny), dim3(256), C::LDS_BYTES, st, a);
-  HIPCHECK(hipGetLastError());
-  return DG_OK;
-}
-
-template <int CIN, int MT>
-int launch(const DeconvArgs& a, int ny, hipStream_t st) {
-  return a.W >= 32 ? launch_w<CIN, MT, true>(a, ny, st) : launch_w<CIN, MT, false>(a, ny, st);
+  return dg_launch(k, (unsigned)gx, 256, (size_t)k.attr_lds, &a, st, (unsigned)ny);
 }
 
 int mt_for(int Cin) { return Cin == 96 ? 3 : 2; }
@@ -334,6 +331,8 @@ int ilog2_exact(int v) {
 }
 
 }  // namespace
+
+const DgKernel* dg_deconv_fwd_kernel(int Cin, int W) { return &kDeconv[Cin == 64 ? 0 : (Cin == 96 ? 1 : 2)][W >= 32]; }
 
 bool dg_deconv_fwd_supported(int B, int H, int W, int Cin, int Cout, TView in, TView out) {
   if (const char* e = getenv("DEPGAN_DECONV_FUSED"))
@@ -368,7 +367,5 @@ int dg_deconv_fwd(DeconvArgs a, int B, hipStream_t st) {
   a.lgH = ilog2_exact(a.H);
   const int MT = mt_for(a.Cin);
   const int ny = 4 * a.Cout / (128 * MT);
-  if (a.Cin == 64) return launch<64, 2>(a, ny, st);
-  if (a.Cin == 96) return launch<96, 3>(a, ny, st);
-  return launch<128, 2>(a, ny, st);
+  return launch(*dg_deconv_fwd_kernel(a.Cin, a.W), a, ny, st);
 }

@@ -113,21 +113,6 @@ __global__ __launch_bounds__(256) void conv_direct_kernel(const ConvArgs a) {
   }
 }
 
-template <int KS, int COG, int G>
-static int launch_direct(const ConvArgs& a, hipStream_t st) {
-  constexpr int TW = 16 + KS - 1;
-  constexpr size_t lds = (size_t)(8 * TW * TW + KS * KS * 8 * COG * G) * sizeof(float);
-  static DgOncePerDevice once;
-  if (once.need()) {
-    HIPCHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_direct_kernel<KS, COG, G>),
-                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  }
-  dim3 grid((unsigned)(cdiv(a.W, 16) * cdiv(a.H, 16) * a.B), (unsigned)cdiv(a.Cout, COG * G));
-  hipLaunchKernelGGL((conv_direct_kernel<KS, COG, G>), grid, dim3(256), lds, st, a);
-  HIPCHECK(hipGetLastError());
-  return DG_OK;
-}
-
 // ---------------------------------------------------------------------------
 // Cout = 1 (backward-data of dis_0a onto the image, the dD/dx of GT:543): one output channel leaves nothing to
 // amortise an input value over except neighbouring pixels, and the generic kernel above spends two LDS reads per FMA.
@@ -220,21 +205,6 @@ __global__ __launch_bounds__(256) void conv_cout1_kernel(const ConvArgs a) {
   }
 }
 
-template <int KS>
-static int launch_cout1(const ConvArgs& a, hipStream_t st) {
-  constexpr int TW = 32 + KS - 1;
-  constexpr size_t lds = (size_t)(8 * TW * 40 + 8 * KS * 8) * sizeof(float);
-  static DgOncePerDevice once;
-  if (once.need()) {
-    HIPCHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_cout1_kernel<KS>),
-                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  }
-  dim3 grid((unsigned)(cdiv(a.W, 32) * cdiv(a.H, 32) * a.B));
-  hipLaunchKernelGGL((conv_cout1_kernel<KS>), grid, dim3(256), lds, st, a);
-  HIPCHECK(hipGetLastError());
-  return DG_OK;
-}
-
 // ---------------------------------------------------------------------------
 // Cin = 1 or 2 (gen_0 GT:398, dis_0a GT:319 and its gradient-penalty u-forward): the output write is the only HBM
 // traffic that matters and the work is KS^2 Cin FMAs per output value.  Thread = 4 consecutive pixels x 4 consecutive
@@ -310,20 +280,33 @@ __global__ __launch_bounds__(256) void conv_cin12_kernel(const ConvArgs a) {
   }
 }
 
-template <int KS, int G>
-static int launch_cin12(const ConvArgs& a, hipStream_t st) {
-  constexpr int ROWS = 256 / G / 4;
-  dim3 grid((unsigned)(cdiv(a.W, 16) * cdiv(a.H, ROWS) * a.B));
-  hipLaunchKernelGGL((conv_cin12_kernel<KS, G>), grid, dim3(256), 0, st, a);
-  HIPCHECK(hipGetLastError());
-  return DG_OK;
-}
+// Every direct instantiation; the profiles know them all as "conv_direct"
+#define DIRECT_FN(...) reinterpret_cast<const void*>(&__VA_ARGS__)
+#define DIRECT_K(KS, COG, G) \
+  {DIRECT_FN(conv_direct_kernel<KS, COG, G>), "conv_direct", (int)((8 * (16 + KS - 1) * (16 + KS - 1) + KS * KS * 8 * COG * G) * sizeof(float))}
+#define COUT1_K(KS) {DIRECT_FN(conv_cout1_kernel<KS>), "conv_direct", (int)((8 * (32 + KS - 1) * 40 + 8 * KS * 8) * sizeof(float))}
+static const DgKernel kDirect[3][3] = {   // [KS / 2][output channels per workgroup: 1, 16, 32]
+    {DIRECT_K(1, 1, 1), DIRECT_K(1, 4, 4), DIRECT_K(1, 4, 8)},
+    {DIRECT_K(3, 1, 1), DIRECT_K(3, 4, 4), DIRECT_K(3, 4, 8)},
+    {DIRECT_K(5, 1, 1), DIRECT_K(5, 4, 4), DIRECT_K(5, 4, 8)}};
+static const DgKernel kCout1[2] = {COUT1_K(3), COUT1_K(5)};   // [KS == 5]
+static const DgKernel kCin12[2][2] = {                        // [KS == 5][Cout == 32]; static LDS only
+    {{DIRECT_FN(conv_cin12_kernel<3, 4>), "conv_direct", 0}, {DIRECT_FN(conv_cin12_kernel<3, 8>), "conv_direct", 0}},
+    {{DIRECT_FN(conv_cin12_kernel<5, 4>), "conv_direct", 0}, {DIRECT_FN(conv_cin12_kernel<5, 8>), "conv_direct", 0}}};
+#undef COUT1_K
+#undef DIRECT_K
+#undef DIRECT_FN
 
-int dg_conv_direct(int KS, const ConvArgs& a_in, hipStream_t st) {
-  ConvArgs a = a_in;
+int dg_conv_direct_prepare(int KS, const ConvArgs& a_in, DgConvLaunch* L) {
+  L->a = a_in;
+  ConvArgs& a = L->a;
   // epilogue.h has no pooled store and no head, and these kernels no grouped or gathered form: refused, not ignored
   if (a.ep.pool.p || a.ep.head_out || a.ep.head_skip_out || a.groups > 1 || a.cpt > 0) {
     dg_set_error("dg_conv_direct: no fused pool, fused head, grouped launch or gathered K on the direct kernels");
+    return DG_ERR_UNSUPPORTED;
+  }
+  if (KS != 1 && KS != 3 && KS != 5) {
+    dg_set_error("dg_conv_direct: unsupported kernel size %d", KS);
     return DG_ERR_UNSUPPORTED;
   }
   auto aligned = [](const TView& v) {
@@ -332,28 +315,23 @@ int dg_conv_direct(int KS, const ConvArgs& a_in, hipStream_t st) {
   a.vec4 = (a.Cout % 4 == 0) && aligned(a.out) && aligned(a.ep.res) && aligned(a.ep.mask) && aligned(a.ep.out_pre) &&
            (!a.ep.film_mul || a.ep.film_ld % 4 == 0);
   const int sel = (a.Cout == 1) ? 0 : ((a.Cout <= 16) ? 1 : 2);
+  L->klass = 2;
+  L->block = 256;
   if (a.Cin <= 2 && a.vec4 && (a.Cout == 16 || a.Cout == 32) && (KS == 3 || KS == 5)) {
-    if (KS == 3) return (a.Cout == 16) ? launch_cin12<3, 4>(a, st) : launch_cin12<3, 8>(a, st);
-    return (a.Cout == 16) ? launch_cin12<5, 4>(a, st) : launch_cin12<5, 8>(a, st);
+    L->k = &kCin12[KS == 5][a.Cout == 32];
+    L->grid = (unsigned)(cdiv(a.W, 16) * cdiv(a.H, a.Cout == 32 ? 8 : 16) * a.B);   // 256 / (Cout / 4) / 4 rows per block
+  } else if (sel == 0 && a.Cin >= 4 && KS != 1) {
+    L->k = &kCout1[KS == 5];
+    L->grid = (unsigned)(cdiv(a.W, 32) * cdiv(a.H, 32) * a.B);
+  } else {
+    L->k = &kDirect[KS / 2][sel];
+    L->grid = (unsigned)(cdiv(a.W, 16) * cdiv(a.H, 16) * a.B);
+    L->grid_y = (unsigned)cdiv(a.Cout, sel == 0 ? 1 : 16 * sel);
   }
-  if (KS == 3) {
-    if (sel == 0) return (a.Cin >= 4) ? launch_cout1<3>(a, st) : launch_direct<3, 1, 1>(a, st);
-    if (sel == 1) return launch_direct<3, 4, 4>(a, st);
-    return launch_direct<3, 4, 8>(a, st);
-  }
-  if (KS == 5) {
-    if (sel == 0) return (a.Cin >= 4) ? launch_cout1<5>(a, st) : launch_direct<5, 1, 1>(a, st);
-    if (sel == 1) return launch_direct<5, 4, 4>(a, st);
-    return launch_direct<5, 4, 8>(a, st);
-  }
-  if (KS == 1) {
-    if (sel == 0) return launch_direct<1, 1, 1>(a, st);
-    if (sel == 1) return launch_direct<1, 4, 4>(a, st);
-    return launch_direct<1, 4, 8>(a, st);
-  }
-  dg_set_error("dg_conv_direct: unsupported kernel size %d", KS);
-  return DG_ERR_UNSUPPORTED;
+  L->lds = (size_t)L->k->attr_lds;
+  return DG_OK;
 }
+
 
 // ---------------------------------------------------------------------------
 // weight gradient for the small-Cin edge layers (gen_0, dis_0a): same slab

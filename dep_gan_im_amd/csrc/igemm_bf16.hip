@@ -302,49 +302,6 @@ ConvPlan dg_plan_conv_split(int KS, int Cin, int Cout, int planes) {
   return p;
 }
 
-template <int KS, int TAPG, int NPL>
-static int launch_split(const ConvArgs& a, hipStream_t st) {
-  constexpr int TW = 16 + KS - 1;
-  constexpr size_t lds_k = (size_t)NPL * (TW * TW + TAPG * 32) * SPLIT_ROWB(NPL);
-  constexpr size_t lds_e = (size_t)4 * 64 * (32 + 4) * sizeof(float);
-  constexpr size_t lds = lds_k > lds_e ? lds_k : lds_e;
-  static DgOncePerDevice once;
-  if (once.need()) {
-    HIPCHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&igemm_split_kernel<KS, TAPG, NPL>),
-                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  }
-  ConvArgs b = a;
-  b.lgx = cdiv(a.W, 16) * cdiv(a.H, 16) * a.B;
-  b.lgy = cdiv(a.Cout, 32) * (a.groups > 1 ? a.groups : 1);
-  const long total = (long)b.lgx * b.lgy;
-  const long per_cu = (long)((160 * 1024) / lds) > 0 ? (long)((160 * 1024) / lds) : 1;
-  const long cap = 256L * (per_cu > 2 ? 2 : per_cu);
-  const long G = total < cap ? total : cap;        // persistent: every workgroup resident
-  hipLaunchKernelGGL((igemm_split_kernel<KS, TAPG, NPL>), dim3((unsigned)G), dim3(256), lds, st, b);
-  HIPCHECK(hipGetLastError());
-  return DG_OK;
-}
-
-template <int KS, int TAPG>
-static int launch_bf16(const ConvArgs& a, hipStream_t st) {
-  constexpr int TW = 16 + KS - 1;
-  constexpr size_t lds_k = (size_t)(TW * TW + TAPG * 32) * 80;
-  constexpr size_t lds_e = (size_t)4 * 64 * (32 + 4) * sizeof(float);
-  constexpr size_t lds = lds_k > lds_e ? lds_k : lds_e;
-  static DgOncePerDevice once;
-  if (once.need()) {
-    HIPCHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&igemm_bf16_kernel<KS, TAPG>),
-                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  }
-  ConvArgs b = a;
-  b.lgx = cdiv(a.W, 16) * cdiv(a.H, 16) * a.B;
-  b.lgy = cdiv(a.Cout, 32) * (a.groups > 1 ? a.groups : 1);
-  const long total = (long)b.lgx * b.lgy;
-  hipLaunchKernelGGL((igemm_bf16_kernel<KS, TAPG>), dim3((unsigned)total), dim3(256), lds, st, b);
-  HIPCHECK(hipGetLastError());
-  return DG_OK;
-}
-
 // Tap grouping and occupancy of the 16-channel kernel.  Shipped: all 25 taps of a chunk staged at once (64 KB, one
 // barrier pair per chunk), two workgroups per CU.  DEPGAN_BF16_N16_VARIANT=1 / 2 (A/B measurements only) select five taps
 // per stage (38 KB, 163 VGPRs): 1 at the three workgroups per CU that allows, 2 held at two per CU by asking for the
@@ -358,63 +315,54 @@ static int bf16_n16_variant() {
   return v;
 }
 
-template <int KS, int TAPG, int OCC, int LDS_TAPS = TAPG>
-static int launch_bf16_n16(const ConvArgs& a, hipStream_t st) {
-  constexpr int TW = 16 + KS - 1;
-  constexpr size_t lds_k = (size_t)(TW * TW + LDS_TAPS * 16) * 80;   // LDS_TAPS > TAPG: unused LDS that limits the occupancy
-  constexpr size_t lds_e = (size_t)4 * 64 * (16 + 4) * sizeof(float);
-  constexpr size_t lds = lds_k > lds_e ? lds_k : lds_e;
-  if (a.cpt > 0 || a.ep.head_out) {
+// LDS of a launch: the halo tile and `taps` staged taps of NT weight rows, in rows of `rowb` bytes, for each plane -- or
+// the epilogue transpose where that is larger.  Every kernel of this file launches with its entry's attribute.
+constexpr int pipe_lds(int KS, int taps, int NT, size_t rowb, int planes = 1) {
+  const size_t k = (size_t)planes * ((16 + KS - 1) * (16 + KS - 1) + taps * NT) * rowb;
+  const size_t e = (size_t)4 * 64 * (NT + 4) * sizeof(float);
+  return (int)(k > e ? k : e);
+}
+#define PIPE_FN(...) reinterpret_cast<const void*>(&__VA_ARGS__)
+#define SPLIT_K(KS, TAPG, NPL) {PIPE_FN(igemm_split_kernel<KS, TAPG, NPL>), "igemm_split_kernel", pipe_lds(KS, TAPG, 32, SPLIT_ROWB(NPL), NPL)}
+#define BF16_K(KS, TAPG) {PIPE_FN(igemm_bf16_kernel<KS, TAPG>), "igemm_bf16_kernel", pipe_lds(KS, TAPG, 32, 80)}
+static const DgKernel kSplit[2][3] = {{SPLIT_K(1, 1, 2), SPLIT_K(3, 9, 2), SPLIT_K(5, 5, 2)},    // [planes - 2][KS / 2]
+                                      {SPLIT_K(1, 1, 3), SPLIT_K(3, 9, 3), SPLIT_K(5, 5, 3)}};
+static const DgKernel kBf16[3] = {BF16_K(1, 1), BF16_K(3, 9), BF16_K(5, 5)};                     // [KS / 2]
+static const DgKernel kBf16N16[3] = {                                                            // [bf16_n16_variant()]
+    {PIPE_FN(igemm_bf16_n16_kernel<5, 25, 2>), "igemm_bf16_n16_kernel<5,25,2>", pipe_lds(5, 25, 16, 80)},
+    {PIPE_FN(igemm_bf16_n16_kernel<5, 5, 2>), "igemm_bf16_n16_kernel<5,5,2>", pipe_lds(5, 5, 16, 80)},
+    {PIPE_FN(igemm_bf16_n16_kernel<5, 5, 2>), "igemm_bf16_n16_kernel<5,5,2>", pipe_lds(5, 25, 16, 80)}};   // unused LDS that limits the occupancy
+#undef BF16_K
+#undef SPLIT_K
+#undef PIPE_FN
+
+int dg_conv_bf16_prepare(const ConvPlan& pl, const ConvArgs& a, DgConvLaunch* L) {
+  const bool n16 = dg_plan_bf16(pl) && pl.MF == 16;
+  if (n16 && pl.KS != 5) { dg_set_error("dg_conv_igemm_bf16: the 16-channel kernel is a 5x5 kernel, KS=%d", pl.KS); return DG_ERR_UNSUPPORTED; }
+  if (n16 && (a.cpt > 0 || a.ep.head_out)) {
     dg_set_error("dg_conv_igemm_bf16: the 16-channel kernel has no gathered K and no fused head");
     return DG_ERR_ARG;
   }
-  static DgOncePerDevice once;
-  if (once.need()) {
-    HIPCHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&igemm_bf16_n16_kernel<KS, TAPG, OCC>),
-                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  const bool ks_ok = pl.KS == 1 || pl.KS == 3 || pl.KS == 5;
+  L->k = n16 ? &kBf16N16[bf16_n16_variant()]
+         : !ks_ok ? nullptr
+         : (dg_plan_split(pl) && (pl.planes == 2 || pl.planes == 3)) ? &kSplit[pl.planes - 2][pl.KS / 2]
+         : dg_plan_bf16(pl) ? &kBf16[pl.KS / 2] : nullptr;
+  if (!L->k) {
+    dg_set_error("dg_conv_igemm_bf16: no bf16 variant for KS=%d", pl.KS);
+    return DG_ERR_UNSUPPORTED;
   }
-  ConvArgs b = a;
-  b.lgx = cdiv(a.W, 16) * cdiv(a.H, 16) * a.B;
-  b.lgy = cdiv(a.Cout, 16) * (a.groups > 1 ? a.groups : 1);
-  const long total = (long)b.lgx * b.lgy;
-  hipLaunchKernelGGL((igemm_bf16_n16_kernel<KS, TAPG, OCC>), dim3((unsigned)total), dim3(256), lds, st, b);
-  HIPCHECK(hipGetLastError());
+  L->a = a;
+  L->a.lgx = cdiv(a.W, 16) * cdiv(a.H, 16) * a.B;
+  L->a.lgy = cdiv(a.Cout, n16 ? 16 : 32) * (a.groups > 1 ? a.groups : 1);
+  long G = (long)L->a.lgx * L->a.lgy;
+  L->lds = (size_t)L->k->attr_lds;
+  if (dg_plan_split(pl)) {   // persistent: every workgroup resident
+    const long per_cu = (long)((160 * 1024) / L->lds) > 0 ? (long)((160 * 1024) / L->lds) : 1;
+    const long cap = 256L * (per_cu > 2 ? 2 : per_cu);
+    if (G > cap) G = cap;
+  }
+  L->grid = (unsigned)G;
+  L->block = 256;
   return DG_OK;
-}
-
-const char* dg_conv_igemm_bf16_name(const ConvPlan& pl) {
-  if (!dg_plan_bf16(pl) || pl.MF != 16) return "igemm_bf16_kernel";
-  switch (bf16_n16_variant()) {
-    case 1:
-    case 2: return "igemm_bf16_n16_kernel<5,5,2>";
-  }
-  return "igemm_bf16_n16_kernel<5,25,2>";
-}
-
-int dg_conv_igemm_bf16(const ConvPlan& pl, const ConvArgs& a, hipStream_t st) {
-  if (dg_plan_bf16(pl) && pl.MF == 16) {
-    if (pl.KS != 5) { dg_set_error("dg_conv_igemm_bf16: the 16-channel kernel is a 5x5 kernel, KS=%d", pl.KS); return DG_ERR_UNSUPPORTED; }
-    switch (bf16_n16_variant()) {
-      case 1: return launch_bf16_n16<5, 5, 2>(a, st);
-      case 2: return launch_bf16_n16<5, 5, 2, 25>(a, st);
-    }
-    return launch_bf16_n16<5, 25, 2>(a, st);
-  }
-  if (dg_plan_split(pl) && pl.planes == 3) switch (pl.KS) {
-    case 3: return launch_split<3, 9, 3>(a, st);
-    case 5: return launch_split<5, 5, 3>(a, st);
-    case 1: return launch_split<1, 1, 3>(a, st);
-  }
-  if (dg_plan_split(pl) && pl.planes == 2) switch (pl.KS) {
-    case 3: return launch_split<3, 9, 2>(a, st);
-    case 5: return launch_split<5, 5, 2>(a, st);
-    case 1: return launch_split<1, 1, 2>(a, st);
-  }
-  if (dg_plan_bf16(pl)) switch (pl.KS) {
-    case 3: return launch_bf16<3, 9>(a, st);
-    case 5: return launch_bf16<5, 5>(a, st);
-    case 1: return launch_bf16<1, 1>(a, st);
-  }
-  dg_set_error("dg_conv_igemm_bf16: no bf16 variant for KS=%d", pl.KS);
-  return DG_ERR_UNSUPPORTED;
 }

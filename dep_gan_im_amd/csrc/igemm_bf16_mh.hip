@@ -65,28 +65,11 @@ __global__ __launch_bounds__(256, 2) void igemm_bf16_mh_kernel(const ConvArgsM a
   }
 }
 
-template <int KS, int TAPG>
-static int launch_mh(const ConvArgsM& a, hipStream_t st) {
-  constexpr int TW = 16 + KS - 1;
-  constexpr size_t lds_k = (size_t)(TW * TW + TAPG * 32) * 80;
-  constexpr size_t lds_e = (size_t)4 * 64 * (32 + 4) * sizeof(float);
-  constexpr size_t lds = lds_k > lds_e ? lds_k : lds_e;
-  static DgOncePerDevice once;
-  if (once.need()) {
-    HIPCHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&igemm_bf16_mh_kernel<KS, TAPG>),
-                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  }
-  ConvArgsM b = a;
-  b.lgx = cdiv(a.W, 16) * cdiv(a.H, 16) * a.B;
-  b.lgy = cdiv(a.Cout, 32);
-  const long total = (long)b.lgx * b.lgy;
-  if (total > 0x7FFFFFFFL) { dg_set_error("dg_conv_bf16_mh: %ld work items", total); return DG_ERR_UNSUPPORTED; }
-  hipLaunchKernelGGL((igemm_bf16_mh_kernel<KS, TAPG>), dim3((unsigned)total), dim3(256), lds, st, b);
-  HIPCHECK(hipGetLastError());
-  return DG_OK;
-}
-
-const char* dg_conv_bf16_mh_name(int KS) { return KS == 3 ? "igemm_bf16_mh_kernel<3, 9>" : "igemm_bf16_mh_kernel<1, 1>"; }
+// one kernel per KS: the launch and the profile's name read the same entry
+#define MH_K(KS, TAPG) {reinterpret_cast<const void*>(&igemm_bf16_mh_kernel<KS, TAPG>), "igemm_bf16_mh_kernel<" #KS ", " #TAPG ">", dg_bf16s_lds(KS, TAPG)}
+static const DgKernel kMh[2] = {MH_K(1, 1), MH_K(3, 9)};
+#undef MH_K
+const DgKernel* dg_conv_bf16_mh_kernel(int KS) { return &kMh[KS == 3]; }
 
 static bool al16f(const TView& v) { return !(v.sX % 4) && !(v.sY % 4) && !(v.sB % 4) && !(((uintptr_t)v.p) & 15); }
 
@@ -114,5 +97,10 @@ int dg_conv_bf16_mh(const ConvPlan& pl, const ConvArgs& a, TViewH mask_h, hipStr
   ConvArgsM m;
   static_cast<ConvArgs&>(m) = a;
   m.mask_h = mask_h;
-  return pl.KS == 3 ? launch_mh<3, 9>(m, st) : launch_mh<1, 1>(m, st);
+  m.lgx = cdiv(a.W, 16) * cdiv(a.H, 16) * a.B;
+  m.lgy = cdiv(a.Cout, 32);
+  const long total = (long)m.lgx * m.lgy;
+  if (total > 0x7FFFFFFFL) { dg_set_error("dg_conv_bf16_mh: %ld work items", total); return DG_ERR_UNSUPPORTED; }
+  const DgKernel* k = dg_conv_bf16_mh_kernel(pl.KS);
+  return dg_launch(*k, (unsigned)total, 256, (size_t)k->attr_lds, &m, st);
 }

@@ -36,28 +36,12 @@ typedef int i32x4 __attribute__((ext_vector_type(4)));
 #undef IGEMM_BF16S_KERNEL
 #undef IGEMM_BF16S_HEAD
 
-template <int KS, int TAPG, bool HEAD>
-static int launch_bf16s(const ConvArgsH& a, hipStream_t st) {
-  constexpr int TW = 16 + KS - 1;
-  constexpr size_t lds_k = (size_t)(TW * TW + TAPG * 32) * 80;
-  constexpr size_t lds_e = (size_t)4 * 64 * (32 + 4) * sizeof(float);
-  constexpr size_t lds = lds_k > lds_e ? lds_k : lds_e;
-  void (*kern)(const ConvArgsH) = nullptr;
-  if constexpr (HEAD) kern = &igemm_bf16s_head_kernel<KS, TAPG>;
-  else kern = &igemm_bf16s_kernel<KS, TAPG>;
-  static DgOncePerDevice once;
-  if (once.need()) {
-    HIPCHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                 (int)lds));
-  }
-  ConvArgsH b = a;
-  b.lgx = cdiv(a.W, 16) * cdiv(a.H, 16) * a.B;
-  b.lgy = cdiv(a.Cout, 32) * (a.groups > 1 ? a.groups : 1);
-  const long total = (long)b.lgx * b.lgy;
-  hipLaunchKernelGGL(kern, dim3((unsigned)total), dim3(256), lds, st, b);
-  HIPCHECK(hipGetLastError());
-  return DG_OK;
-}
+// one kernel per KS, and the 3x3 one with the fused head: the launch and the profile's name read the same entry
+#define BF16S_K(KERN, KS, TAPG) {reinterpret_cast<const void*>(&KERN<KS, TAPG>), #KERN "<" #KS ", " #TAPG ">", dg_bf16s_lds(KS, TAPG)}
+static const DgKernel kBf16s[3] = {BF16S_K(igemm_bf16s_kernel, 1, 1), BF16S_K(igemm_bf16s_kernel, 3, 9),
+                                   BF16S_K(igemm_bf16s_head_kernel, 3, 9)};
+#undef BF16S_K
+const DgKernel* dg_conv_bf16s_kernel(int KS, bool head) { return &kBf16s[head ? 2 : (KS == 3 ? 1 : 0)]; }
 
 static bool aligned16_h(const TViewH& v) {
   return !v.p || (!(v.sX % 8) && !(v.sY % 8) && !(v.sB % 8) && !(((uintptr_t)v.p) & 15));
@@ -65,11 +49,6 @@ static bool aligned16_h(const TViewH& v) {
 // the epilogue's per-lane and per-pass byte offsets (up to four rows and sixteen pixels from the wave's origin) are ints
 static bool offsets_fit(const TViewH& v) {
   return !v.p || (v.sX > 0 && v.sY > 0 && v.sB >= 0 && 2 * (4 * v.sY + 16 * v.sX + 32) < 0x7FFFFFFFL);
-}
-
-const char* dg_conv_bf16s_name(int KS, bool head) {
-  if (head) return "igemm_bf16s_head_kernel<3, 9>";
-  return KS == 3 ? "igemm_bf16s_kernel<3, 9>" : "igemm_bf16s_kernel<1, 1>";
 }
 
 int dg_conv_bf16s_check(int KS, const ConvArgsH& a) {
@@ -116,8 +95,11 @@ int dg_conv_bf16s(int KS, const ConvArgsH& a, hipStream_t st) {
   for (int g = 0; g < ng && ng > 1; ++g)
     if (!a.w_group[g]) { dg_set_error("dg_conv_bf16s: null weight panel of group %d", g); return DG_ERR_ARG; }
   if (ng == 1 && !a.w) { dg_set_error("dg_conv_bf16s: null weight panel"); return DG_ERR_ARG; }
-  if (a.ep.head_out) return launch_bf16s<3, 9, true>(a, st);
-  return KS == 3 ? launch_bf16s<3, 9, false>(a, st) : launch_bf16s<1, 1, false>(a, st);
+  ConvArgsH b = a;
+  b.lgx = cdiv(a.W, 16) * cdiv(a.H, 16) * a.B;
+  b.lgy = cdiv(a.Cout, 32) * ng;
+  const DgKernel* k = dg_conv_bf16s_kernel(KS, a.ep.head_out != nullptr);
+  return dg_launch(*k, (unsigned)((long)b.lgx * b.lgy), 256, (size_t)k->attr_lds, &b, st);
 }
 
 // ---------------------------------------------------------------------------

@@ -362,7 +362,7 @@ __global__ __launch_bounds__(256, PERS ? 4 : 1) void igemm_conv_head_kernel(cons
 // ---------------------------------------------------------------------------
 // plans
 // ---------------------------------------------------------------------------
-// The fp32 tile plan: MF by the channel count, the chunk size by (MF, KS) -- the instantiations of dispatch_tile
+// The fp32 tile plan: MF by the channel count, the chunk size by (MF, KS) -- the instantiations of kTile
 ConvPlan dg_plan_conv(int KS, int Cin, int Cout) {
   ConvPlan p = dg_plan_direct();
   p.KS = KS;
@@ -431,88 +431,58 @@ static long igemm_grid(int KS, int CK, size_t lds, long total) {
   return (per_cu > 0 && total > cap) ? cap : total;
 }
 
-// name_out != nullptr: only report which instantiation the launch would take (profile records, bench.py's
-// dominant-kernel line: the names rocprofv3 prints), launch nothing
-template <int MF, int KS, int CK, int TAPG>
-static int launch_tile(const ConvArgs& a, hipStream_t st, char* name_out = nullptr, size_t name_cap = 0) {
-  constexpr int TW = 16 + KS - 1;
-  constexpr size_t lds_k = (size_t)(TW * TW * (CK + 4) + TAPG * MF * (CK + 4)) * sizeof(float);
-  constexpr size_t lds_e = (size_t)4 * 64 * (MF + 4) * sizeof(float);  // epilogue transpose
-  constexpr size_t lds = lds_k > lds_e ? lds_k : lds_e;
-  ConvArgs b = a;
-  b.lgx = cdiv(a.W, 16) * cdiv(a.H, 16) * a.B;
-  b.lgy = cdiv(a.Cout, MF) * (a.groups > 1 ? a.groups : 1);
-  const long total = (long)b.lgx * b.lgy;
-  const long G = igemm_grid(KS, CK, lds, total);
-  constexpr bool CAN_HEAD = (MF == 32 && KS == 3 && CK == 8 && TAPG == 9);
+// Every tile instantiation, keyed by the plan fields that select it; k[1] is the persistent form
+constexpr size_t tile_lds(int MF, int KS, int CK, int TAPG) {
+  const size_t lds_k = (size_t)((16 + KS - 1) * (16 + KS - 1) * (CK + 4) + TAPG * MF * (CK + 4)) * sizeof(float);
+  const size_t lds_e = (size_t)4 * 64 * (MF + 4) * sizeof(float);  // epilogue transpose
+  return lds_k > lds_e ? lds_k : lds_e;
+}
+struct TileInst {
+  int MF, KS, CK;
+  DgKernel k[2];
+};
+#define TILE_K(MF, KS, CK, TAPG, PERS)                                                \
+  {reinterpret_cast<const void*>(&igemm_conv_kernel<MF, KS, CK, TAPG, PERS>),         \
+   "igemm_conv_kernel<" #MF "," #KS "," #CK "," #TAPG "," #PERS ">", (int)tile_lds(MF, KS, CK, TAPG)}
+#define TILE_INST(MF, KS, CK, TAPG) {MF, KS, CK, {TILE_K(MF, KS, CK, TAPG, false), TILE_K(MF, KS, CK, TAPG, true)}}
+static const TileInst kTile[] = {TILE_INST(32, 3, 16, 9), TILE_INST(16, 3, 16, 9), TILE_INST(32, 5, 8, 25),
+                                 TILE_INST(16, 5, 16, 25), TILE_INST(32, 1, 32, 1), TILE_INST(16, 1, 16, 1),
+                                 TILE_INST(32, 3, 8, 9)};
+#undef TILE_INST
+#undef TILE_K
+// the 8-channel-chunk 3x3 instantiation with the fused head
+static const DgKernel kTileHead[2] = {
+    {reinterpret_cast<const void*>(&igemm_conv_head_kernel<false>), "igemm_conv_head_kernel<false>", (int)tile_lds(32, 3, 8, 9)},
+    {reinterpret_cast<const void*>(&igemm_conv_head_kernel<true>), "igemm_conv_head_kernel<true>", (int)tile_lds(32, 3, 8, 9)}};
+
+int dg_conv_tile_prepare(const ConvPlan& pl, const ConvArgs& a, DgConvLaunch* L) {
+  const TileInst* t = nullptr;
+  for (const TileInst& i : kTile)
+    if (pl.family == CONV_TILE && i.MF == pl.MF && i.KS == pl.KS && i.CK == pl.CK) t = &i;
+  if (!t) {
+    dg_set_error("dg_conv_igemm: no tile kernel for family %d MF=%d KS=%d CK=%d", (int)pl.family, pl.MF, pl.KS, pl.CK);
+    return DG_ERR_ARG;
+  }
   const bool head = a.ep.head_out != nullptr;
-  if (head && (!CAN_HEAD || a.Cout != 32 || a.groups > 1 || a.ep.pool.p != nullptr)) {
+  if (head && (!dg_plan_tile3_ck8(pl) || a.Cout != 32 || a.groups > 1 || a.ep.pool.p != nullptr)) {
     dg_set_error("dg_conv_igemm: the fused head needs the 8-channel-chunk 3x3 kernel and 32 output channels");
     return DG_ERR_ARG;
   }
-  if (name_out) {
-    if (head) snprintf(name_out, name_cap, "igemm_conv_head_kernel<%s>", G < total ? "true" : "false");
-    else snprintf(name_out, name_cap, "igemm_conv_kernel<%d,%d,%d,%d,%s>", MF, KS, CK, TAPG, G < total ? "true" : "false");
-    return DG_OK;
-  }
-  if constexpr (CAN_HEAD) {
-    if (head) {
-      static DgOncePerDevice once_h;
-      if (once_h.need()) {
-        HIPCHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&igemm_conv_head_kernel<false>),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        HIPCHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&igemm_conv_head_kernel<true>),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-      }
-      if (G < total) hipLaunchKernelGGL((igemm_conv_head_kernel<true>), dim3((unsigned)G), dim3(256), lds, st, b);
-      else hipLaunchKernelGGL((igemm_conv_head_kernel<false>), dim3((unsigned)G), dim3(256), lds, st, b);
-      HIPCHECK(hipGetLastError());
-      return DG_OK;
-    }
-  }
-  // the dynamic-LDS attribute is per device: a process may hold contexts on several GPUs (Engine(device=...))
-  static DgOncePerDevice once;
-  if (once.need()) {
-    HIPCHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&igemm_conv_kernel<MF, KS, CK, TAPG, false>),
-                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    HIPCHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&igemm_conv_kernel<MF, KS, CK, TAPG, true>),
-                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  }
-  if (G < total)
-    hipLaunchKernelGGL((igemm_conv_kernel<MF, KS, CK, TAPG, true>), dim3((unsigned)G), dim3(256), lds, st, b);
-  else
-    hipLaunchKernelGGL((igemm_conv_kernel<MF, KS, CK, TAPG, false>), dim3((unsigned)G), dim3(256), lds, st, b);
-  HIPCHECK(hipGetLastError());
+  L->a = a;
+  L->a.lgx = cdiv(a.W, 16) * cdiv(a.H, 16) * a.B;
+  L->a.lgy = cdiv(a.Cout, t->MF) * (a.groups > 1 ? a.groups : 1);
+  const long total = (long)L->a.lgx * L->a.lgy;
+  L->lds = (size_t)t->k[0].attr_lds;
+  const long G = igemm_grid(t->KS, t->CK, L->lds, total);
+  L->k = head ? &kTileHead[G < total] : &t->k[G < total];
+  L->grid = (unsigned)G;
+  L->block = 256;
   return DG_OK;
-}
-
-static int dispatch_tile(const ConvPlan& pl, const ConvArgs& a, hipStream_t st, char* name_out, size_t name_cap) {
-  const bool wide = pl.MF == 32;
-  if (pl.family == CONV_TILE && pl.KS == 3 && !dg_plan_tile3_ck8(pl))
-    return wide ? launch_tile<32, 3, 16, 9>(a, st, name_out, name_cap) : launch_tile<16, 3, 16, 9>(a, st, name_out, name_cap);
-  if (pl.family == CONV_TILE && pl.KS == 5)
-    return wide ? launch_tile<32, 5, 8, 25>(a, st, name_out, name_cap) : launch_tile<16, 5, 16, 25>(a, st, name_out, name_cap);
-  if (pl.family == CONV_TILE && pl.KS == 1)
-    return wide ? launch_tile<32, 1, 32, 1>(a, st, name_out, name_cap) : launch_tile<16, 1, 16, 1>(a, st, name_out, name_cap);
-  if (dg_plan_tile3_ck8(pl)) return launch_tile<32, 3, 8, 9>(a, st, name_out, name_cap);
-  dg_set_error("dg_conv_igemm: no tile kernel for family %d MF=%d KS=%d CK=%d", (int)pl.family, pl.MF, pl.KS, pl.CK);
-  return DG_ERR_ARG;
 }
 
 bool dg_conv_igemm_head_supported(const ConvPlan& pl, const ConvArgs& a) {
   return (dg_plan_tile3_ck8(pl) || dg_plan_wino(pl)) && a.Cout == 32 && a.groups <= 1 && a.ep.pool.p == nullptr && a.cpt <= 0 &&
          !a.ep.accumulate;
-}
-
-void dg_conv_igemm_name(const ConvPlan& pl, const ConvArgs& a, char* buf, size_t cap) {
-  if (cap) buf[0] = 0;
-  if (!dg_plan_mfma(pl)) { snprintf(buf, cap, "conv_direct"); return; }
-  if (dg_plan_split(pl)) { snprintf(buf, cap, "igemm_split_kernel"); return; }
-  if (dg_plan_bf16(pl)) { snprintf(buf, cap, "%s", dg_conv_igemm_bf16_name(pl)); return; }
-  if (dg_plan_wino(pl)) { snprintf(buf, cap, "%s", dg_conv_wino_name(a)); return; }
-  if (dg_conv_igemm_wp_supported(pl, a, false)) { snprintf(buf, cap, "igemm_wp_kernel<0>"); return; }
-  if (dg_conv_igemm_ws5_supported(pl, a, false)) { snprintf(buf, cap, "%s", dg_conv_igemm_ws5_name(pl)); return; }
-  dispatch_tile(pl, a, nullptr, buf, cap);
 }
 
 // Argument checks shared by every MFMA launcher (the wave-private kernel is also launched directly)
@@ -548,20 +518,6 @@ int dg_conv_igemm_check(const ConvPlan& pl, const ConvArgs& a) {
   }
   return DG_OK;
 }
-
-static int conv_igemm_impl(const ConvPlan& pl, const ConvArgs& a_in, hipStream_t st, bool allow_wp) {
-  ConvArgs a = a_in;
-  DGCHECK(dg_conv_igemm_check(pl, a));
-  if (dg_plan_bf16(pl) || dg_plan_split(pl)) return dg_conv_igemm_bf16(pl, a, st);
-  if (dg_plan_wino(pl)) return dg_conv_wino(pl, a, st);   // its panel fits no other kernel
-  if (allow_wp && dg_conv_igemm_wp_supported(pl, a, false)) return dg_conv_igemm_wp(pl, a, st);
-  if (allow_wp && dg_conv_igemm_ws5_supported(pl, a, false)) return dg_conv_igemm_ws5(pl, a, st);
-  return dispatch_tile(pl, a, st, nullptr, 0);
-}
-
-int dg_conv_igemm(const ConvPlan& pl, const ConvArgs& a, hipStream_t st) { return conv_igemm_impl(pl, a, st, true); }
-// the workgroup-tile kernels only (unit tests: the reference the wave-private kernel must match bit for bit)
-int dg_conv_igemm_tile(const ConvPlan& pl, const ConvArgs& a, hipStream_t st) { return conv_igemm_impl(pl, a, st, false); }
 
 // ---------------------------------------------------------------------------
 // weight packing:  dst[nt][cc][tap][n][k]

@@ -525,30 +525,37 @@ __global__ __launch_bounds__(256, WnCfg<MT>::WGS_PER_CU) void wino_conv_abl_kern
 }
 #endif
 
-// Every instantiation a launch can take, with the name rocprofv3 prints for it: wino_pick() is the one place that maps
-// a launch to an entry, so the name dg_conv_wino_name reports is the kernel wino_launch starts
-struct WnKern {
-  const void* fn;
-  const char* name;
-};
-#define WN_K8(EC)                                                                                       \
-  {{reinterpret_cast<const void*>(&wino_conv_kernel<1, false, EC>), "wino_conv_kernel<1,false," #EC ">"}, \
-   {reinterpret_cast<const void*>(&wino_conv_kernel<1, true, EC>), "wino_conv_kernel<1,true," #EC ">"}},
-const WnKern kWn8[WN_HEAD_CLASS][2] = {WN_K8(0) WN_CLASSES8(WN_K8)};   // [class][persistent]
+// Every instantiation a launch can take, with the name rocprofv3 prints for it and its LDS size: wino_pick() is the one
+// place that maps a launch to an entry
+#define WN_FN(...) reinterpret_cast<const void*>(&__VA_ARGS__)
+#define WN_K8(EC)                                                                                \
+  {{WN_FN(wino_conv_kernel<1, false, EC>), "wino_conv_kernel<1,false," #EC ">", WnCfg<1>::LDS}, \
+   {WN_FN(wino_conv_kernel<1, true, EC>), "wino_conv_kernel<1,true," #EC ">", WnCfg<1>::LDS}},
+const DgKernel kWn8[WN_HEAD_CLASS][2] = {WN_K8(0) WN_CLASSES8(WN_K8)};   // [class][persistent]
 #undef WN_K8
-const WnKern kWn16[2] = {{reinterpret_cast<const void*>(&wino_conv_kernel<2, false, 0>), "wino_conv_kernel<2,false,0>"},
-                         {reinterpret_cast<const void*>(&wino_conv_kernel<2, true, 0>), "wino_conv_kernel<2,true,0>"}};
-const WnKern kWnHead[2][2] = {   // [generic / head class][persistent]
-    {{reinterpret_cast<const void*>(&wino_conv_head_kernel<false, 0>), "wino_conv_head_kernel<false,0>"},
-     {reinterpret_cast<const void*>(&wino_conv_head_kernel<true, 0>), "wino_conv_head_kernel<true,0>"}},
-    {{reinterpret_cast<const void*>(&wino_conv_head_kernel<false, WN_HEAD_CLASS>), "wino_conv_head_kernel<false,10>"},
-     {reinterpret_cast<const void*>(&wino_conv_head_kernel<true, WN_HEAD_CLASS>), "wino_conv_head_kernel<true,10>"}}};
+const DgKernel kWn16[2] = {{WN_FN(wino_conv_kernel<2, false, 0>), "wino_conv_kernel<2,false,0>", WnCfg<2>::LDS},
+                           {WN_FN(wino_conv_kernel<2, true, 0>), "wino_conv_kernel<2,true,0>", WnCfg<2>::LDS}};
+const DgKernel kWnHead[2][2] = {   // [generic / head class][persistent]
+    {{WN_FN(wino_conv_head_kernel<false, 0>), "wino_conv_head_kernel<false,0>", WnCfg<2>::LDS},
+     {WN_FN(wino_conv_head_kernel<true, 0>), "wino_conv_head_kernel<true,0>", WnCfg<2>::LDS}},
+    {{WN_FN(wino_conv_head_kernel<false, WN_HEAD_CLASS>), "wino_conv_head_kernel<false,10>", WnCfg<2>::LDS},
+     {WN_FN(wino_conv_head_kernel<true, WN_HEAD_CLASS>), "wino_conv_head_kernel<true,10>", WnCfg<2>::LDS}}};
 static_assert(WN_HEAD_CLASS == 10, "the names above");
-const WnKern kWnGath[2][2] = {   // [MT - 1][persistent]
-    {{reinterpret_cast<const void*>(&wino_conv_gathered_kernel<1, false>), "wino_conv_gathered_kernel<1,false>"},
-     {reinterpret_cast<const void*>(&wino_conv_gathered_kernel<1, true>), "wino_conv_gathered_kernel<1,true>"}},
-    {{reinterpret_cast<const void*>(&wino_conv_gathered_kernel<2, false>), "wino_conv_gathered_kernel<2,false>"},
-     {reinterpret_cast<const void*>(&wino_conv_gathered_kernel<2, true>), "wino_conv_gathered_kernel<2,true>"}}};
+const DgKernel kWnGath[2][2] = {   // [MT - 1][persistent]
+    {{WN_FN(wino_conv_gathered_kernel<1, false>), "wino_conv_gathered_kernel<1,false>", WnCfg<1>::LDS},
+     {WN_FN(wino_conv_gathered_kernel<1, true>), "wino_conv_gathered_kernel<1,true>", WnCfg<1>::LDS}},
+    {{WN_FN(wino_conv_gathered_kernel<2, false>), "wino_conv_gathered_kernel<2,false>", WnCfg<2>::LDS},
+     {WN_FN(wino_conv_gathered_kernel<2, true>), "wino_conv_gathered_kernel<2,true>", WnCfg<2>::LDS}}};
+#ifdef DEPGAN_WINO_ABLATIONS
+// tools/build_wino_abl.sh: DEPGAN_WINO_ABL=<N> takes the ablated persistent instantiation N of either form
+constexpr int kWnAblN[] = {1, 2, 3, 4, 8, 10, 11};
+#define WN_ABL(MT, N) {WN_FN(wino_conv_abl_kernel<MT, N>), "wino_conv_abl_kernel<" #MT "," #N ">", WnCfg<MT>::LDS},
+#define WN_ABLS(MT) {WN_ABL(MT, 1) WN_ABL(MT, 2) WN_ABL(MT, 3) WN_ABL(MT, 4) WN_ABL(MT, 8) WN_ABL(MT, 10) WN_ABL(MT, 11)}
+const DgKernel kWnAbl[2][7] = {WN_ABLS(1), WN_ABLS(2)};   // [MT - 1][index in kWnAblN]
+#undef WN_ABLS
+#undef WN_ABL
+#endif
+#undef WN_FN
 
 // DEPGAN_EPI_CLASSES=0: every launch takes the generic kernel (A/B); depgan_set_epilogue_classes overrides it
 int g_epi_classes = -1;
@@ -613,19 +620,8 @@ static int wino_mt(const ConvArgs& a) {
   return 1;
 }
 
-template <int MT>
-static void wino_geometry(ConvArgs& a, long* total, long* G, bool* pers) {
-  a.lgx = cdiv(a.W, 16) * cdiv(a.H, WnCfg<MT>::TH) * a.B;
-  a.lgy = a.Cout / 32;
-  *total = (long)a.lgx * a.lgy;
-  // resident workgroups per CU by LDS and registers; persistent when there are more items than that
-  const long cap = (long)WnCfg<MT>::WGS_PER_CU * dg_cu_count();
-  *pers = *total > cap;
-  *G = *pers ? cap : *total;
-}
-
 // the instantiation of a launch: its form, then the epilogue class of its flag set
-static const WnKern* wino_pick(const ConvArgs& a, int mt, bool pers) {
+static const DgKernel* wino_pick(const ConvArgs& a, int mt, bool pers) {
   const int form = a.ep.head_out ? 1 : (a.cpt > 0 ? 3 : (mt == 2 ? 2 : 0));
   const int ec = dg_wino_epi_class(dg_epilogue_flags(a.ep), form);
   if (form == 1) return &kWnHead[ec ? 1 : 0][pers];
@@ -634,68 +630,37 @@ static const WnKern* wino_pick(const ConvArgs& a, int mt, bool pers) {
   return &kWn8[ec][pers];
 }
 
-const char* dg_conv_wino_name(const ConvArgs& a_in) {
-  ConvArgs a = a_in;
-  long total, G;
-  bool pers;
-  const int mt = wino_mt(a);
-  if (mt == 2) wino_geometry<2>(a, &total, &G, &pers); else wino_geometry<1>(a, &total, &G, &pers);
-  return wino_pick(a, mt, pers)->name;
-}
-
-template <int MT>
-static int wino_launch(ConvArgs a, hipStream_t st) {
-  long total, G;
-  bool pers;
-  wino_geometry<MT>(a, &total, &G, &pers);
-  constexpr size_t LDS = WnCfg<MT>::LDS;
-  static DgOncePerDevice once;
-  if (once.need()) {
-    // every instantiation of this MT, its epilogue classes included
-    const WnKern* const own = (MT == 2) ? &kWn16[0] : &kWn8[0][0];
-    const int nown = (MT == 2) ? 2 : 2 * WN_HEAD_CLASS;
-    for (int i = 0; i < nown; ++i)
-      HIPCHECK(hipFuncSetAttribute(own[i].fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS));
-    for (int i = 0; i < 2; ++i)
-      HIPCHECK(hipFuncSetAttribute(kWnGath[MT - 1][i].fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS));
-    for (int i = 0; MT == 2 && i < 4; ++i)
-      HIPCHECK(hipFuncSetAttribute(kWnHead[i >> 1][i & 1].fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS));
-  }
-#ifdef DEPGAN_WINO_ABLATIONS
-  if (const char* e = getenv("DEPGAN_WINO_ABL")) {
-    const int abl = atoi(e);
-    if (abl && pers && !a.ep.head_out && a.cpt <= 0) {
-#define WN_ABL_CASE(N)                                                                                              \
-  case N:                                                                                                           \
-    HIPCHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&wino_conv_abl_kernel<MT, N>),                       \
-                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS));                            \
-    hipLaunchKernelGGL((wino_conv_abl_kernel<MT, N>), dim3((unsigned)G), dim3(256), LDS, st, a);                    \
-    break;
-      switch (abl) {
-        WN_ABL_CASE(1) WN_ABL_CASE(2) WN_ABL_CASE(3) WN_ABL_CASE(4) WN_ABL_CASE(8) WN_ABL_CASE(10) WN_ABL_CASE(11)
-        default: dg_set_error("DEPGAN_WINO_ABL=%d not instantiated", abl); return DG_ERR_ARG;
-      }
-      HIPCHECK(hipGetLastError());
-      return DG_OK;
-    }
-  }
-#endif
-  if (a.ep.head_out) {
-    if (MT != 2 || a.Cout != 32 || a.ep.pool.p || a.cpt > 0) {
-      dg_set_error("dg_conv_wino: the fused head needs 32 output channels, no fused pool and no gathered K");
-      return DG_ERR_ARG;
-    }
-  }
-  void* kargs[] = {&a};
-  HIPCHECK(hipLaunchKernel(wino_pick(a, MT, pers)->fn, dim3((unsigned)G), dim3(256), kargs, LDS, st));
-  HIPCHECK(hipGetLastError());
-  return DG_OK;
-}
-
-int dg_conv_wino(const ConvPlan& pl, const ConvArgs& a, hipStream_t st) {
+int dg_conv_wino_prepare(const ConvPlan& pl, const ConvArgs& a, DgConvLaunch* L) {
   if (!dg_conv_wino_supported(pl, a)) {
     dg_set_error("dg_conv_wino: shape not covered (3x3, Cin %% 8, Cout %% 32, even H and W, no groups, a halo tile of the input view within 2 GiB)");
     return DG_ERR_UNSUPPORTED;
   }
-  return wino_mt(a) == 2 ? wino_launch<2>(a, st) : wino_launch<1>(a, st);
+  const int mt = wino_mt(a);
+  if (a.ep.head_out && (a.Cout != 32 || a.ep.pool.p || a.cpt > 0)) {
+    dg_set_error("dg_conv_wino: the fused head needs 32 output channels, no fused pool and no gathered K");
+    return DG_ERR_ARG;
+  }
+  L->a = a;
+  L->a.lgx = cdiv(a.W, 16) * cdiv(a.H, mt == 2 ? WnCfg<2>::TH : WnCfg<1>::TH) * a.B;
+  L->a.lgy = a.Cout / 32;
+  const long total = (long)L->a.lgx * L->a.lgy;
+  // resident workgroups per CU by LDS and registers; persistent when there are more items than that
+  const long cap = (long)(mt == 2 ? WnCfg<2>::WGS_PER_CU : WnCfg<1>::WGS_PER_CU) * dg_cu_count();
+  const bool pers = total > cap;
+  L->k = wino_pick(a, mt, pers);
+#ifdef DEPGAN_WINO_ABLATIONS
+  if (const char* e = getenv("DEPGAN_WINO_ABL")) {
+    const int abl = atoi(e);
+    if (abl && pers && !a.ep.head_out && a.cpt <= 0) {
+      L->k = nullptr;
+      for (int i = 0; i < 7; ++i)
+        if (kWnAblN[i] == abl) L->k = &kWnAbl[mt - 1][i];
+      if (!L->k) { dg_set_error("DEPGAN_WINO_ABL=%d not instantiated", abl); return DG_ERR_ARG; }
+    }
+  }
+#endif
+  L->grid = (unsigned)(pers ? cap : total);
+  L->block = 256;
+  L->lds = (size_t)L->k->attr_lds;
+  return DG_OK;
 }

@@ -350,18 +350,22 @@ bool dg_conv_igemm_wp_supported(const ConvPlan& pl, const ConvArgs& a, bool forc
   return (sup & 7) == 0 && sup * (a.Cout / 32) >= 256;
 }
 
-int dg_conv_igemm_wp(const ConvPlan& pl, const ConvArgs& a_in, hipStream_t st) {
-  ConvArgs a = a_in;
-  DGCHECK(dg_conv_igemm_check(pl, a));   // unit tests launch this kernel directly, not through dg_conv_igemm
-  const size_t lds = ((size_t)a.Cin * 9 * 32 + (size_t)WP_NW * Wp3::WAVE_FLOATS) * sizeof(float);
-  static DgOncePerDevice once;
-  if (once.need())
-    HIPCHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&igemm_wp_kernel<0>),
-                                 hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+// 160 KB for every entry of this file: their launches' LDS sizes depend on Cin and on the wave count
+#define WP_K(N) {reinterpret_cast<const void*>(&igemm_wp_kernel<N>), "igemm_wp_kernel<" #N ">", 160 * 1024},
+static const DgKernel kWp[] = {
+    WP_K(0)
+#ifdef DEPGAN_WP_ABLATIONS
+    WP_K(1) WP_K(2) WP_K(3) WP_K(4)   // tools/ab_wp_ablation.sh: DEPGAN_WP_ABL selects an ablated instantiation
+#endif
+};
+#undef WP_K
+
+int dg_conv_wp_prepare(const ConvPlan&, const ConvArgs& a, DgConvLaunch* L) {
   const int nNT = a.Cout / 32;
-  a.lgx = (int)wp_groups(a, WP_NW);
-  a.lgy = nNT;
-  const long total = (long)a.lgx * nNT;
+  L->a = a;
+  L->a.lgx = (int)wp_groups(a, WP_NW);
+  L->a.lgy = nNT;
+  const long total = (long)L->a.lgx * nNT;
   // one workgroup per CU, rounded down to a multiple of 8 nNT (XCD round-robin x channel tiles: a workgroup keeps its
   // channel tile and thereby its panel for all its items)
   long G = dg_cu_count();
@@ -369,34 +373,20 @@ int dg_conv_igemm_wp(const ConvPlan& pl, const ConvArgs& a_in, hipStream_t st) {
   if (G < 8L * nNT) G = 8L * nNT;
   // (a group count that is not a multiple of 8 takes the plain id -> (group, channel tile) form, in which a
   // persistent workgroup would change its channel tile: one item per workgroup then -- unit tests only)
-  if (G > total || (a.lgx & 7) != 0) G = total;
+  if (G > total || (L->a.lgx & 7) != 0) G = total;
+  int abl = 0;
 #ifdef DEPGAN_WP_ABLATIONS
-  // tools/ab_wp_ablation.sh (build with -DDEPGAN_WP_ABLATIONS): DEPGAN_WP_ABL selects an ablated instantiation
-  static int abl = -1;
-  if (abl < 0) {
+  static int abl_env = -1;
+  if (abl_env < 0) {
     const char* e = getenv("DEPGAN_WP_ABL");
-    abl = e ? atoi(e) : 0;
+    abl_env = e ? atoi(e) : 0;
   }
-  if (abl) {
-    static DgOncePerDevice once2;
-    if (once2.need()) {
-      HIPCHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&igemm_wp_kernel<1>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-      HIPCHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&igemm_wp_kernel<2>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-      HIPCHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&igemm_wp_kernel<3>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-      HIPCHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&igemm_wp_kernel<4>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    }
-    switch (abl) {
-      case 1: hipLaunchKernelGGL((igemm_wp_kernel<1>), dim3((unsigned)G), dim3(WP_NW * 64), lds, st, a); break;
-      case 2: hipLaunchKernelGGL((igemm_wp_kernel<2>), dim3((unsigned)G), dim3(WP_NW * 64), lds, st, a); break;
-      case 3: hipLaunchKernelGGL((igemm_wp_kernel<3>), dim3((unsigned)G), dim3(WP_NW * 64), lds, st, a); break;
-      default: hipLaunchKernelGGL((igemm_wp_kernel<4>), dim3((unsigned)G), dim3(WP_NW * 64), lds, st, a); break;
-    }
-    HIPCHECK(hipGetLastError());
-    return DG_OK;
-  }
+  abl = abl_env ? (abl_env >= 1 && abl_env <= 3 ? abl_env : 4) : 0;
 #endif
-  hipLaunchKernelGGL((igemm_wp_kernel<0>), dim3((unsigned)G), dim3(WP_NW * 64), lds, st, a);
-  HIPCHECK(hipGetLastError());
+  L->k = &kWp[abl];
+  L->grid = (unsigned)G;
+  L->block = WP_NW * 64;
+  L->lds = ((size_t)a.Cin * 9 * 32 + (size_t)WP_NW * Wp3::WAVE_FLOATS) * sizeof(float);
   return DG_OK;
 }
 
@@ -447,29 +437,24 @@ bool dg_conv_igemm_ws5_supported(const ConvPlan& pl, const ConvArgs& a, bool for
   return true;
 }
 
-const char* dg_conv_igemm_ws5_name(const ConvPlan& pl) { return pl.MF == 32 ? "igemm_ws5_kernel<32,8>" : "igemm_ws5_kernel<16,16>"; }
+static const DgKernel kWs5[2] = {   // [MF == 16]
+    {reinterpret_cast<const void*>(&igemm_ws5_kernel<32, 8>), "igemm_ws5_kernel<32,8>", 160 * 1024},
+    {reinterpret_cast<const void*>(&igemm_ws5_kernel<16, 16>), "igemm_ws5_kernel<16,16>", 160 * 1024}};
 
-template <int MF, int CK>
-static int ws5_launch(ConvArgs& a, hipStream_t st) {
-  const int nw = ws5_waves<MF, CK>(a.Cin);
-  const size_t lds = ((size_t)a.Cin * 25 * MF + (size_t)nw * WpGeo<MF, 5, CK>::WAVE_FLOATS) * sizeof(float);
-  static DgOncePerDevice once;
-  if (once.need())
-    HIPCHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&igemm_ws5_kernel<MF, CK>),
-                                 hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-  a.lgx = (int)wp_groups(a, nw);
-  a.lgy = 1;
+int dg_conv_ws5_prepare(const ConvPlan& pl, const ConvArgs& a, DgConvLaunch* L) {
+  const bool wide = pl.MF == 32;
+  const int nw = ws5_waves_of(pl, a.Cin);
+  const size_t wave = wide ? WpGeo<32, 5, 8>::WAVE_FLOATS : WpGeo<16, 5, 16>::WAVE_FLOATS;
+  L->a = a;
+  L->a.lgx = (int)wp_groups(a, nw);
+  L->a.lgy = 1;
   // one workgroup per CU; a multiple of 8 when the groups are dealt over the XCDs
   long G = dg_cu_count();
-  if ((a.lgx & 7) == 0) G -= G % 8;
-  if (G > a.lgx || G < 1) G = a.lgx;
-  hipLaunchKernelGGL((igemm_ws5_kernel<MF, CK>), dim3((unsigned)G), dim3(nw * 64), lds, st, a);
-  HIPCHECK(hipGetLastError());
+  if ((L->a.lgx & 7) == 0) G -= G % 8;
+  if (G > L->a.lgx || G < 1) G = L->a.lgx;
+  L->k = &kWs5[wide ? 0 : 1];
+  L->grid = (unsigned)G;
+  L->block = (unsigned)nw * 64;
+  L->lds = ((size_t)a.Cin * 25 * pl.MF + (size_t)nw * wave) * sizeof(float);
   return DG_OK;
-}
-
-int dg_conv_igemm_ws5(const ConvPlan& pl, const ConvArgs& a_in, hipStream_t st) {
-  ConvArgs a = a_in;
-  DGCHECK(dg_conv_igemm_check(pl, a));   // the operator surface launches this kernel directly
-  return pl.MF == 32 ? ws5_launch<32, 8>(a, st) : ws5_launch<16, 16>(a, st);
 }

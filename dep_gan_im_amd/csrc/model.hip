@@ -111,15 +111,7 @@ static int net_requantize(depgan_ctx* c, Net& n) {
 // the summation order, and a sample's result must not depend on how many samples share its batch
 // (test_bench_size_properties_batch32_256 checks batch 32 against four batches of 8 bit for bit).
 static ConvPlan plan_conv(const depgan_ctx* c, int KS, int Cin, int Cout, int N = 0, int H = 0, int W = 0) {
-  if (c->cfg.f32_split) return dg_plan_conv_split(KS, Cin, Cout, c->cfg.f32_split == 6 ? 3 : 2);
-  if (c->cfg.bf16_mfma) return dg_plan_conv_bf16(KS, Cin, Cout);
-  const long items = (long)N * cdiv(H, 16) * cdiv(W, 16) * cdiv(Cout, 32);
-  // 3x3 layers the Winograd kernel covers (igemm_wino.hip: 4/9 of the MFMAs of the direct form)
-  if (c->winograd && KS == 3 && H > 0 && W > 0 && !((H | W) & 1)) {
-    const ConvPlan w = dg_plan_conv_wino(Cin, Cout);
-    if (dg_plan_wino(w)) return w;
-  }
-  return dg_plan_conv_items(KS, Cin, Cout, items);
+  return dg_conv_plan(c->cfg.f32_split, c->cfg.bf16_mfma, c->winograd, KS, Cin, Cout, N, H, W);
 }
 
 // ---------------------------------------------------------------------------
@@ -141,14 +133,11 @@ int conv_launch(depgan_ctx* c, const ConvPlan& pl, const ConvArgs& a, int KS) {
                                                       (a.ep.pool.p ? 0.25 : 0) - (a.ep.head_skip_out ? 1 : 0)) +
                                           4.0 * KS * KS * a.Cin * a.Cout) +
                     (a.ep.head_out ? px + 4.0 * a.Cout : 0.0);
-  if (dg_plan_mfma(pl)) {
-    char kn[48] = "";
-    if (c->prof_on) dg_conv_igemm_name(pl, a, kn, sizeof(kn));
-    ProfScope ps(c, 0, fl, lb, by, kn);
-    return dg_conv_igemm(pl, a, c->st);
-  }
-  ProfScope ps(c, 2, fl, lb);
-  return dg_conv_direct(KS, a, c->st);
+  // one walk of the chain: the profile's kernel name is the entry the launch takes
+  DgConvLaunch L;
+  DGCHECK(dg_conv_prepare(pl, a, KS, DG_ROUTE_ALL, &L));
+  ProfScope ps(c, L.klass, fl, lb, L.klass == 0 ? by : 0.0, L.klass == 0 ? L.k->name : "");
+  return dg_conv_run(L, c->st);
 }
 
 // Forward of a transposed convolution on the fused four-tap kernel (deconv_fwd.hip): fp32 contexts only -- the bf16 /
@@ -170,7 +159,7 @@ int deconv_fwd_launch(depgan_ctx* c, const GLayer& L, TView out, const float* bi
   snprintf(lb, sizeof(lb), "conv k1 b%d %dx%d %d->%d x4", n, L.H, L.W, L.Cin, L.Cout);
   const double px = 4.0 * n * L.H * L.W;
   ProfScope ps(c, 0, 2.0 * n * L.H * L.W * (double)L.Cin * L.Cout * 4, lb,
-               px * L.Cin + 4 * (px * L.Cout + 4.0 * L.Cin * L.Cout), "deconv_fwd_kernel");
+               px * L.Cin + 4 * (px * L.Cout + 4.0 * L.Cin * L.Cout), dg_deconv_fwd_kernel(L.Cin, L.W)->name);
   return dg_deconv_fwd(d, n, c->st);
 }
 

@@ -107,7 +107,7 @@ static int conv_launch_bf16s(depgan_ctx* c, const ConvArgsH& a, int KS) {
   char lb[56];
   snprintf(lb, sizeof(lb), "conv(bf16s) k%d b%d %dx%d %d->%d%s", KS, a.B, a.H, a.W, a.Cin, a.Cout,
            ng > 1 ? " x4" : (a.ep.head_out ? (a.ep.head_skip_out ? " +head, no store" : " +head") : ""));
-  ProfScope ps(c, 0, fl, lb, bf16s_bytes(a, KS), dg_conv_bf16s_name(KS, a.ep.head_out != nullptr));
+  ProfScope ps(c, 0, fl, lb, bf16s_bytes(a, KS), dg_conv_bf16s_kernel(KS, a.ep.head_out != nullptr)->name);
   return dg_conv_bf16s(KS, a, c->st);
 }
 
@@ -162,7 +162,7 @@ int g_forward_bf16s(depgan_ctx* c, const float* x, const float* z, float* out, i
         snprintf(lb, sizeof(lb), "conv(bf16s) k3 b%d %dx%d %d->%d +u", n, L.H, L.W, L.Cin, L.Cout);
         const double px = (double)n * L.H * L.W;
         ProfScope ps(c, 0, 2.0 * px * L.Cin * L.Cout * 9, lb, bf16s_bytes(a, 3) + px * L.Cout * (2.0 + 0.125),
-                     "igemm_bf16s_train_kernel<3, 9>");
+                     dg_conv_bf16s_train_kernel()->name);
         DGCHECK(dg_conv_bf16s_train(t, c->st));
         continue;
       }

@@ -52,7 +52,7 @@ static int bwd_data_h(depgan_ctx* c, const ConvPlan& pl, const ConvArgs& a, TVie
   ProfScope ps(c, 0, 2.0 * px * a.Cin * a.Cout * KS * KS, lb,
                px * (4.0 * a.Cin + a.Cout * (4.0 + (a.ep.res.p ? 4.0 : 0.0) + (mask.p ? 2.0 : 0.0))) +
                    2.0 * KS * KS * a.Cin * a.Cout,
-               dg_conv_bf16_mh_name(KS));
+               dg_conv_bf16_mh_kernel(KS)->name);
   return dg_conv_bf16_mh(pl, a, mask, c->st);
 }
 

@@ -52,50 +52,69 @@ extern "C" {
 // ---- single operators (unit tests) ----
 // a: views, sizes and epilogue of the launch (bwd: Cin / Cout already in their launch roles); w_hwio (KS, KS, Cin, Cout)
 // of the layer.  Plans, packs and launches on the kernel `path` names; what that kernel does not cover is an error.
+// What an operator path means: the plan function it takes, the routes of the chain it leaves open (dg_conv_prepare),
+// and below the refusals that belong to it.  0 (and any other number) is the model's choice for the fp32 tile plan.
+static ConvPlan op_conv_plan(int path, int KS, int ci, int co) {
+  switch (path) {
+    case 2: return dg_plan_direct();
+    case 3: return dg_plan_conv_bf16(KS, ci, co);
+    case 4: case 5: return dg_plan_conv_split(KS, ci, co, path == 5 ? 3 : 2);
+    case 6: case 7: return dg_plan_conv_items(KS, ci, co, 1L << 30);
+    case 8: return KS == 3 ? dg_plan_conv_wino(ci, co) : dg_plan_conv(KS, ci, co);
+    case 10: return dg_plan_conv_bf16_n16(KS, ci, co);
+  }
+  return dg_plan_conv(KS, ci, co);
+}
+static unsigned op_conv_routes(int path) {
+  // 6 and 1: the workgroup-tile kernel itself (the reference the wave-private kernels must match bit for bit)
+  return (path == 1 || path == 6) ? DG_ROUTE_TILE : path == 7 ? DG_ROUTE_WP : path == 9 ? DG_ROUTE_WS5 : DG_ROUTE_ALL;
+}
+#define OP_REFUSE(status, ...) do { dg_set_error(__VA_ARGS__); return status; } while (0)
 static int op_conv_run(ConvArgs a, const float* w_hwio, int Cin, int Cout, int KS, int path, int bwd, hipStream_t st) {
   const int ci = a.Cin, co = a.Cout;
-  ConvPlan pl = (path == 3) ? dg_plan_conv_bf16(KS, ci, co)
-                : (path == 4 || path == 5) ? dg_plan_conv_split(KS, ci, co, path == 5 ? 3 : 2)
-                : (path == 6) ? dg_plan_conv_items(KS, ci, co, 1L << 30) : dg_plan_conv(KS, ci, co);
-  if (path == 7) pl = dg_plan_conv_items(KS, ci, co, 1L << 30);
-  if (path == 10) {
-    // the 16-output-channel 5x5 form of 3: decided before any HIP call, as path 9
-    if (KS != 5) { dg_set_error("op_conv: path 10 is the 16-channel 5x5 bf16 kernel, KS must be 5"); return DG_ERR_ARG; }
-    if (!a.in.p || !a.out.p || !w_hwio) { dg_set_error("op_conv: null operand"); return DG_ERR_ARG; }
-    if (a.ep.head_w || a.ep.head_b || a.ep.head_out) { dg_set_error("op_conv: path 10 has no fused head"); return DG_ERR_ARG; }
-    pl = dg_plan_conv_bf16_n16(KS, ci, co);
-    if (!dg_plan_bf16(pl) || pl.MF != 16) { dg_set_error("op_conv: the 16-channel bf16 kernel does not cover a launch of %d -> %d channels", ci, co); return DG_ERR_UNSUPPORTED; }
+  const ConvPlan pl = op_conv_plan(path, KS, ci, co);
+  switch (path) {   // decided before any HIP call
+    case 10:
+      if (KS != 5) OP_REFUSE(DG_ERR_ARG, "op_conv: path 10 is the 16-channel 5x5 bf16 kernel, KS must be 5");
+      if (!a.in.p || !a.out.p || !w_hwio) OP_REFUSE(DG_ERR_ARG, "op_conv: null operand");
+      if (a.ep.head_w || a.ep.head_b || a.ep.head_out) OP_REFUSE(DG_ERR_ARG, "op_conv: path 10 has no fused head");
+      if (!dg_plan_bf16(pl) || pl.MF != 16) OP_REFUSE(DG_ERR_UNSUPPORTED, "op_conv: the 16-channel bf16 kernel does not cover a launch of %d -> %d channels", ci, co);
+      break;
+    case 8:
+      if (!dg_plan_wino(pl) || !dg_conv_wino_supported(pl, a)) OP_REFUSE(DG_ERR_UNSUPPORTED, "op_conv: the Winograd kernel does not cover this shape");
+      break;
+    case 6: case 7:
+      if (pl.CK != 8) OP_REFUSE(DG_ERR_UNSUPPORTED, "op_conv: the 8-channel-chunk variant does not cover this shape");
+      break;
+    case 3: case 4: case 5:
+      if (!pl.planes) OP_REFUSE(DG_ERR_UNSUPPORTED, "op_conv: the bf16 MFMA kernel does not cover this shape");
+      break;
+    case 9:
+      // path 9 names a 5x5 kernel: another KS is a bad argument (status 1, as for a path number that does not exist),
+      // what the 5x5 kernel does not cover is status 3
+      if (KS != 5) OP_REFUSE(DG_ERR_ARG, "op_conv: path 9 is the weight-stationary 5x5 kernel, KS must be 5");
+      if (!dg_conv_igemm_ws5_supported(pl, a, true)) OP_REFUSE(DG_ERR_UNSUPPORTED, "op_conv: the weight-stationary 5x5 kernel does not cover this shape");
+      break;
+    case 1:
+      if (!dg_plan_mfma(pl)) OP_REFUSE(DG_ERR_UNSUPPORTED, "op_conv: MFMA path not available for this shape");
+      break;
   }
-  if (path == 8) {
-    pl = (KS == 3) ? dg_plan_conv_wino(ci, co) : pl;
-    if (!dg_plan_wino(pl) || !dg_conv_wino_supported(pl, a)) { dg_set_error("op_conv: the Winograd kernel does not cover this shape"); return DG_ERR_UNSUPPORTED; }
-  }
-  if ((path == 6 || path == 7) && pl.CK != 8) { dg_set_error("op_conv: the 8-channel-chunk variant does not cover this shape"); return DG_ERR_UNSUPPORTED; }
-  if (path >= 3 && path <= 5 && !pl.planes) { dg_set_error("op_conv: the bf16 MFMA kernel does not cover this shape"); return DG_ERR_UNSUPPORTED; }
-  // path 9 names a 5x5 kernel: another KS is a bad argument (status 1, as for a path number that does not exist), what
-  // the 5x5 kernel does not cover is status 3
-  if (path == 9 && KS != 5) { dg_set_error("op_conv: path 9 is the weight-stationary 5x5 kernel, KS must be 5"); return DG_ERR_ARG; }
-  if (path == 9 && !dg_conv_igemm_ws5_supported(pl, a, true)) { dg_set_error("op_conv: the weight-stationary 5x5 kernel does not cover this shape"); return DG_ERR_UNSUPPORTED; }
-  if (path == 1 && !dg_plan_mfma(pl)) { dg_set_error("op_conv: MFMA path not available for this shape"); return DG_ERR_UNSUPPORTED; }
-  if (path != 2 && dg_plan_mfma(pl)) {
-    DevTmp wp(st);
+  DevTmp wp(st);
+  if (dg_plan_mfma(pl)) {
     DGCHECK(wp.alloc(pl.packedFloats * sizeof(float)));
     DGCHECK(dg_pack_weights(pl, w_hwio, Cin, Cout, 0, bwd, bwd, nullptr, wp.as<float>(), st));
     a.w = wp.as<float>();
-    if (path == 7) {
-      if (dg_conv_igemm_wp_supported(pl, a, true)) return dg_conv_igemm_wp(pl, a, st);
-      dg_set_error("op_conv: the wave-private kernel does not cover this shape");
-      return DG_ERR_UNSUPPORTED;
-    }
-    if (path == 9) return dg_conv_igemm_ws5(pl, a, st);
-    // 6 and 1: the workgroup-tile kernel itself (the reference the wave-private kernel must match bit for bit)
-    if (path == 6 || path == 1) return dg_conv_igemm_tile(pl, a, st);
-    return dg_conv_igemm(pl, a, st);
+    if (path == 7 && !dg_conv_igemm_wp_supported(pl, a, true)) OP_REFUSE(DG_ERR_UNSUPPORTED, "op_conv: the wave-private kernel does not cover this shape");
+  } else if (!bwd) {
+    conv_set_weights(&a, pl, nullptr, w_hwio, Cin, Cout);
+  } else {
+    conv_set_weights_bwd(&a, pl, nullptr, w_hwio, Cin, Cout);
   }
-  if (!bwd) conv_set_weights(&a, dg_plan_direct(), nullptr, w_hwio, Cin, Cout);
-  else conv_set_weights_bwd(&a, dg_plan_direct(), nullptr, w_hwio, Cin, Cout);
-  return dg_conv_direct(KS, a, st);
+  DgConvLaunch L;
+  DGCHECK(dg_conv_prepare(pl, a, KS, op_conv_routes(path), &L));
+  return dg_conv_run(L, st);
 }
+#undef OP_REFUSE
 
 static int op_conv(const float* in, const float* w_hwio, const float* bias, float* out, int B, int H, int W, int Cin,
                    int Cout, int KS, int relu, int path, int bwd, hipStream_t st) {
@@ -302,32 +321,72 @@ int depgan_wino_epilogue_class(unsigned flags, int form) {
   }
   return dg_wino_epi_class(flags, form);
 }
-int depgan_op_conv3x3_wino_kernel_name(unsigned flags, int B, int H, int W, int Cin, int Cout, char* buf, int cap) {
-  if ((flags & ~(unsigned)DG_EPF_ALL) || B < 1 || H < 1 || W < 1 || Cin < 1 || Cout < 1 || !buf || cap < 1) {
-    dg_set_error("op_conv3x3_wino_kernel_name: null or non-positive argument, or flags outside DEPGAN_EPF_ALL");
-    return DG_ERR_ARG;
-  }
-  // only which operands are present matters to the selection: every present one points at this float
-  static float present;
-  const TView pv = make_view(&present, H, W, Cout);
-  ConvArgs a = conv_args(make_view(&present, H, W, Cin), pv, B, H, W, Cin, Cout);
+// A launch description for the host-only entries below.  Only which operands are present matters to the selection:
+// every present one points at these floats
+static ConvArgs op_flag_args(unsigned flags, int B, int H, int W, int Cin, int Cout) {
+  alignas(16) static float present[4];
+  const TView pv = make_view(present, H, W, Cout);
+  ConvArgs a = conv_args(make_view(present, H, W, Cin), pv, B, H, W, Cin, Cout);
   Epilogue& e = a.ep;
-  if (flags & DG_EPF_BIAS) e.bias = &present;
-  if (flags & DG_EPF_AFFINE) e.scale = e.shift = &present;
-  if (flags & DG_EPF_FILM) { e.film_mul = e.film_add = &present; e.film_ld = Cout; }
+  if (flags & DG_EPF_BIAS) e.bias = present;
+  if (flags & DG_EPF_AFFINE) e.scale = e.shift = present;
+  if (flags & DG_EPF_FILM) { e.film_mul = e.film_add = present; e.film_ld = Cout; }
   e.relu = (flags & DG_EPF_RELU) ? 1 : 0;
   if (flags & DG_EPF_PRE) e.out_pre = pv;
   if (flags & DG_EPF_RES) e.res = pv;
   if (flags & DG_EPF_MASK) e.mask = pv;
   if (flags & DG_EPF_POOL) e.pool = pv;
   e.accumulate = (flags & DG_EPF_ACCUM) ? 1 : 0;
-  if (flags & DG_EPF_HEAD) { e.head_w = e.head_b = &present; e.head_out = &present; }
+  if (flags & DG_EPF_HEAD) { e.head_w = e.head_b = present; e.head_out = present; }
+  a.w = present;
+  return a;
+}
+
+int depgan_op_conv3x3_wino_kernel_name(unsigned flags, int B, int H, int W, int Cin, int Cout, char* buf, int cap) {
+  if ((flags & ~(unsigned)DG_EPF_ALL) || B < 1 || H < 1 || W < 1 || Cin < 1 || Cout < 1 || !buf || cap < 1) {
+    dg_set_error("op_conv3x3_wino_kernel_name: null or non-positive argument, or flags outside DEPGAN_EPF_ALL");
+    return DG_ERR_ARG;
+  }
+  const ConvArgs a = op_flag_args(flags, B, H, W, Cin, Cout);
   const ConvPlan pl = dg_plan_conv_wino(Cin, Cout);
   if (!dg_plan_wino(pl) || !dg_conv_wino_supported(pl, a)) {
     dg_set_error("op_conv3x3_wino_kernel_name: the Winograd kernel does not cover this shape");
     return DG_ERR_UNSUPPORTED;
   }
-  snprintf(buf, (size_t)cap, "%s", dg_conv_wino_name(a));
+  DgConvLaunch L;
+  DGCHECK(dg_conv_prepare(pl, a, 3, DG_ROUTE_ALL, &L));
+  snprintf(buf, (size_t)cap, "%s", L.k->name);
+  return DG_OK;
+}
+
+// host only: the launch conv_launch prepares for a layer planned as a context in the given mode plans it
+int depgan_debug_conv_choice(int f32_split, int bf16_mfma, int winograd, int KS, int planN, int B, int H, int W, int Cin,
+                             int Cout, unsigned epilogue_flags, int groups, int runs, char* name, int cap, long out[5]) {
+  if ((f32_split != 0 && f32_split != 3 && f32_split != 6) || (bf16_mfma != 0 && bf16_mfma != 1) ||
+      (winograd != 0 && winograd != 1) || planN < 0 || B < 1 || H < 1 || W < 1 || Cin < 1 || Cout < 1 ||
+      (epilogue_flags & ~(unsigned)DG_EPF_ALL) || (groups != 0 && groups != 1 && groups != 4) || runs < 0 || runs > 4 ||
+      !name || cap < 1 || !out) {
+    dg_set_error("debug_conv_choice: null or non-positive argument, a mode flag that is not one of its values, flags outside "
+                 "DEPGAN_EPF_ALL, groups not 0, 1 or 4, or runs outside 0 ... 4");
+    return DG_ERR_ARG;
+  }
+  const ConvPlan pl = dg_conv_plan(f32_split, bf16_mfma, winograd, KS, Cin, Cout, planN, H, W);
+  ConvArgs a = op_flag_args(epilogue_flags, B, H, W, Cin, Cout);
+  a.groups = groups;
+  for (int g = 0; g < groups; ++g) a.w_group[g] = a.w;
+  if (runs > 0) {
+    if (!dg_plan_mfma(pl) || Cin % (runs * pl.CK)) {
+      dg_set_error("debug_conv_choice: %d channels are not %d runs of whole chunks of this plan", Cin, runs);
+      return DG_ERR_UNSUPPORTED;
+    }
+    a.cpt = Cin / (runs * pl.CK);
+    for (int t = 0; t < runs; ++t) a.in_run_off[t] = 4L * t;
+  }
+  DgConvLaunch L;
+  DGCHECK(dg_conv_prepare(pl, a, KS, DG_ROUTE_ALL, &L));
+  snprintf(name, (size_t)cap, "%s", L.k->name);
+  out[0] = (long)L.grid * L.grid_y; out[1] = L.block; out[2] = (long)L.lds; out[3] = L.k->attr_lds;
+  out[4] = L.a.lgx > 0 && out[0] < (long)L.a.lgx * L.a.lgy;
   return DG_OK;
 }
 

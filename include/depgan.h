@@ -996,6 +996,21 @@ int depgan_debug_wgrad_plan(int kernel, int KS, int B, int H, int W, int Cin, in
  * launcher refuses returns the launcher's status; a null `out`, a non-positive size or a flag that is not 0 or 1
  * status 1.  A refusal writes nothing. */
 int depgan_debug_wgrad_choice(int KS, int B, int H, int W, int Cin, int Cout, int bf16_pipe, int x_bf16, long out[4]);
+/* Host only (no launch, no allocation): the kernel and the launch geometry the model takes for one convolution -- the
+ * layer planned as a context in the given mode plans it (f32_split 0, 3 or 6; bf16_mfma and winograd 0 or 1; planN the
+ * batch the layer is planned for, 0 where the plan does not depend on it), launched at batch B with the operands that
+ * epilogue_flags (DEPGAN_EPF_* bits) names.  groups = 4: the grouped launch of a transposed convolution's four taps;
+ * runs > 0: gathered K, Cin in `runs` runs of whole chunks.  The chain is the library's one statement of the choice:
+ * the direct kernels for a shape without an MFMA plan, else bf16 / split, Winograd, the wave-private 3x3 kernel
+ * (opt-in), the weight-stationary 5x5 kernel, the tile instantiation by (MF, KS, CK) and its fused-head variant.
+ * name receives the kernel's name as the profiles print it; out = {workgroups, threads per workgroup, dynamic LDS bytes
+ * of the launch, MaxDynamicSharedMemorySize the kernel is given once per device (0: none), 1 where the workgroups
+ * walk more than one item each}.  A null pointer, a non-positive size, a mode flag that is not one of its values or
+ * flags outside DEPGAN_EPF_ALL return status 1; a launch the chosen kernel refuses returns the launcher's status (a
+ * fused head on a shape that has none: 1; runs that are no whole chunks, a fused pool on the direct kernels: 3).
+ * A refusal writes nothing. */
+int depgan_debug_conv_choice(int f32_split, int bf16_mfma, int winograd, int KS, int planN, int B, int H, int W, int Cin,
+                             int Cout, unsigned epilogue_flags, int groups, int runs, char* name, int cap, long out[5]);
 
 /* Learning-phase-1 operators (the DEP-UResNet training step's batch-statistics BatchNorm, Dropout, softmax and
  * cross-entropy), each the internal function uresnet.hip calls.  Device pointers; every NHWC view has the float strides

@@ -15,7 +15,7 @@ strays poisons the result), what surrounds a written window is a sentinel that m
 Everything stays inside its allocation.
 
 What each path accepts, from dg_conv_igemm_check / launch_variant / dg_conv_igemm_head_supported (igemm_conv.hip),
-dg_conv_wino_supported (igemm_wino.hip), dg_conv_igemm_wp_supported (igemm_wp.hip) and dg_conv_direct (direct.hip);
+dg_conv_wino_supported (igemm_wino.hip), dg_conv_igemm_wp_supported (igemm_wp.hip) and dg_conv_direct_prepare (direct.hip);
 "-" = refused with a non-zero status and nothing written (test_refused_cells_...):
 
   path                          bias affine out_pre FiLM relu res mask accumulate pool head  shapes

@@ -211,7 +211,7 @@ def test_step_operator_entries_are_exported_and_bound(lib):
         assert getattr(lib, name).argtypes, name + " has no argtypes"
 
 
-DEBUG_ENTRIES = ["capture", "tensor", "tensor_bf16s", "film_decision_bf16s", "wgrad_plan", "wgrad_choice"]
+DEBUG_ENTRIES = ["capture", "tensor", "tensor_bf16s", "film_decision_bf16s", "wgrad_plan", "wgrad_choice", "conv_choice"]
 
 
 def test_debug_entries_are_exported_and_bound(lib):
