@@ -129,6 +129,10 @@ struct ConvArgs {
   // 2x2 / stride-2 transposed convolution as ONE 1x1 convolution over the four strided pixel grids of its upstream
   // gradient (K = 4 Cout).  The run length cpt * CK must divide into whole chunks (no channel tail inside a run).
   int cpt;
+  // the 5x5 kernels only (igemm_ws5_kernel, the persistent igemm_conv_kernel<., 5, ., 25, true>): the epilogue class of
+  // this launch's flag set (dg_conv5_epi_class), filled by the launcher; 0 = the body that reads the flags at run time.
+  // (In the four bytes that padded cpt: no other field moves and the struct keeps its size.)
+  int epi_class;
   long in_run_off[4];
 };
 
@@ -371,6 +375,43 @@ unsigned dg_epilogue_flags(const Epilogue& e);
 int dg_wino_epi_class(unsigned flags, int form);
 void dg_set_epi_classes(int on);
 int dg_get_epi_classes();
+// Epilogue classes of the 5x5 kernels (igemm_ws5_kernel<32,8> / <16,16>, igemm_conv_kernel<32,5,8,25,true> /
+// <16,5,16,25,true>; profiles/conv5_classes_experiments.md).  Their names, grids and LDS sizes are pinned, so a class is
+// not an instantiation of the kernel but a body INSIDE it: once per wave, before the item loop, ConvArgs::epi_class
+// selects the item loop compiled for that flag set (the EPI_CLASS hook of igemm_epilogue.inc); class 0 is the loop that
+// reads the flags at run time, which every other flag set takes, and everything while the process-wide switch is off.
+// The table is closed: the flag sets the model launches on these kernels (model.hip: d_forward, d_backward_chain, the
+// u-forward of critic_enqueue).
+constexpr int DG_CONV5_NCLASS = 5;
+constexpr unsigned kConv5ClassMask[DG_CONV5_NCLASS] = {
+    0,                                          // 0 generic (run-time flags)
+    DG_EPF_BIAS | DG_EPF_RELU,                  // 1 critic 5x5 forward
+    DG_EPF_BIAS | DG_EPF_RELU | DG_EPF_POOL,    // 2   ... with the fused pool
+    DG_EPF_MASK,                                // 3 backward-data with a ReLU mask; the critics' u-forward
+    0,                                          // 4 backward-data into a pooled layer: nothing
+};
+template <int EC>
+struct Conv5Epi {
+  static_assert(EC >= 0 && EC < DG_CONV5_NCLASS, "epilogue class");
+  static constexpr unsigned M = kConv5ClassMask[EC];
+  static constexpr bool fixed = EC != 0;
+  static constexpr bool bias = M & DG_EPF_BIAS, affine = M & DG_EPF_AFFINE, film = M & DG_EPF_FILM, relu = M & DG_EPF_RELU,
+                        pre = M & DG_EPF_PRE, res = M & DG_EPF_RES, msk = M & DG_EPF_MASK, pool = M & DG_EPF_POOL,
+                        head = M & DG_EPF_HEAD;
+};
+// pure host function: the class id of a flag set (a mask of DG_EPF_*), 0 while the switch is off
+int dg_conv5_epi_class(unsigned flags);
+#ifdef __HIPCC__
+// The kernel's one by-value ConvArgs, read again from the kernel-argument segment through a pointer the compiler cannot
+// trace: the scalar loads of whatever fields the caller goes on to use stay where this is called (once per item, in
+// front of the epilogue) instead of being hoisted to the kernel's entry, where the whole struct then has to live in
+// SGPRs -- or, spilled, in VGPR lanes -- across the item loop.  Only for kernels whose sole argument is the ConvArgs.
+static __device__ __forceinline__ void dg_reload_conv_args(ConvArgs* dst) {
+  auto kp = __builtin_amdgcn_kernarg_segment_ptr();   // constant address space: the loads below are scalar
+  asm volatile("" : "+s"(kp));
+  __builtin_memcpy(dst, (const void*)kp, sizeof(ConvArgs));
+}
+#endif
 
 // wgrad: returns number of chunks used through *nchunks; part must hold nchunks slabs of KS * KS * Cin * Cout floats
 // (DgWgradChoice::part_floats).

@@ -14,6 +14,15 @@ ConvPlan dg_conv_plan(int f32_split, int bf16_mfma, int winograd, int KS, int Ci
   return dg_plan_conv_items(KS, Cin, Cout, (long)N * cdiv(H, 16) * cdiv(W, 16) * cdiv(Cout, 32));
 }
 
+// The epilogue class of a 5x5 launch (common.h, kConv5ClassMask): a pure function of the flag set and the switch.  The
+// empty set is class 4, not the run-time-flag body, whose mask is only a placeholder
+int dg_conv5_epi_class(unsigned flags) {
+  if (!dg_get_epi_classes()) return 0;
+  for (int i = 1; i < DG_CONV5_NCLASS; ++i)
+    if (kConv5ClassMask[i] == flags) return i;
+  return 0;
+}
+
 int dg_conv_prepare(const ConvPlan& pl, const ConvArgs& a, int KS, unsigned routes, DgConvLaunch* out) {
   out->grid_y = 1;
   out->klass = 0;

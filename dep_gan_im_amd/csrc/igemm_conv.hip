@@ -17,6 +17,19 @@
 // identically for A and B, which a contraction does not care about.
 // Global loads for stage s+1 are issued into registers before the MFMAs of
 // stage s and written to LDS after them (one register set, T14-style).
+//
+// Epilogue classes of the persistent 5x5 forms (igemm_conv_kernel<32,5,8,25,true> / <16,5,16,25,true>;
+// profiles/conv5_classes_experiments.md): the kernel holds five item loops, selected once by ConvArgs::epi_class
+// (dg_conv5_epi_class: {bias, relu}, {bias, relu, pool}, {mask}, {} -- the flag sets of the critics' layers).  A class
+// loop carries its flag set as constants (EPI_CLASS of igemm_epilogue.inc) and is a plain launch by the launcher's word
+// (one group, contiguous K in whole chunks, no phase stamps), so it holds none of those tests and arguments either:
+// 0 ... 16 spilled SGPRs per loop where the parent's one loop spilled 126 / 144.  Class 0 is the loop that reads everything
+// at run time; it takes every other launch, and reads the epilogue's fields again per item instead of keeping them across
+// the loop (73 / 103 spilled SGPRs, no scratch; +1.4 % on a launch that takes it, which the step has none of).  Same
+// statements, same loads: bit-identical (tests/test_gpu_conv5_classes.py); name, grid, block and LDS size do not depend
+// on the class.  32->16 @128^2 batch 96, per wave: SALU 4363 -> 3560, VALU without MFMAs 4710 -> 2873, wave cycles -3.1 %;
+// the launches of the step that take these kernels -3.1 ... -5.4 %.  Every other instantiation compiles to the
+// instructions it compiled to before.
 #include <stdlib.h>
 
 #include "common.h"
@@ -68,7 +81,8 @@ struct Mfma<16> {
 // run one item per workgroup.
 // HEAD: the epilogue carries the fused one-channel 1x1 head (Epilogue::head_*); its own __global__ wrapper below so
 // that the plain instantiations keep their code and their names in the profiles.
-template <int MF, int KS, int CK, int TAPG, bool PERS, bool HEAD>
+// EC: epilogue class of the persistent 5x5 forms (common.h, Conv5Epi); 0 everywhere else: the flags of a.ep at run time
+template <int MF, int KS, int CK, int TAPG, bool PERS, bool HEAD, int EC = 0>
 static __device__ __forceinline__ void igemm_conv_body(const ConvArgs& a) {
   constexpr int NT = MF;
   constexpr int PAD = KS / 2;
@@ -93,8 +107,11 @@ static __device__ __forceinline__ void igemm_conv_body(const ConvArgs& a) {
   float* xs = smem;                // [PIXT][CKP]
   float* ws = smem + PIXT * CKP;   // [TAPG][NT][CKP]
 
+  // A launch with an epilogue class is a PLAIN one (dg_conv_tile_prepare sees to it): one group, contiguous K in whole
+  // chunks, no phase stamps -- its body carries neither their tests nor their arguments
+  constexpr bool PLAIN = EC != 0;
   const int tid = threadIdx.x;
-  unsigned long long* dbg = a.dbg ? a.dbg + (size_t)blockIdx.x * 16 : nullptr;
+  unsigned long long* dbg = (!PLAIN && a.dbg) ? a.dbg + (size_t)blockIdx.x * 16 : nullptr;
   if (dbg && tid == 0) {
     dbg[0] = __builtin_amdgcn_s_memtime();
     dbg[6] = __builtin_amdgcn_s_memrealtime();
@@ -154,12 +171,13 @@ static __device__ __forceinline__ void igemm_conv_body(const ConvArgs& a) {
   const int ty0 = (t % tilesY) * 16;
   const int b = t / tilesY;
   // grouped launch: the channel-tile index also enumerates the groups (taps of a transposed convolution)
-  const int ngrp = a.groups > 1 ? a.groups : 1;
+  const bool grouped = !PLAIN && a.groups > 1;
+  const int ngrp = grouped ? a.groups : 1;
   const int nNTg = (int)nNTall / ngrp;
   const int grp = ntile / nNTg;
   ntile -= grp * nNTg;
-  const float* wbase = a.groups > 1 ? a.w_group[grp] : a.w;
-  const long out_goff = a.groups > 1 ? a.out_group_off[grp] : 0;
+  const float* wbase = grouped ? a.w_group[grp] : a.w;
+  const long out_goff = grouped ? a.out_group_off[grp] : 0;
   const int n0 = ntile * NT;
   const int nCC = (a.Cin + CK - 1) / CK;
   const int NS = nCC * NG;
@@ -172,7 +190,7 @@ static __device__ __forceinline__ void igemm_conv_body(const ConvArgs& a) {
   const char* halo0 = reinterpret_cast<const char*>(inb + ((long)(ty0 - PAD) * a.in.sY + (long)(tx0 - PAD) * a.in.sX));
   // first input channel (float offset from the pixel) of channel chunk cc; see ConvArgs::cpt for the gathered form
   auto coff = [&](int cc) -> long {
-    if (a.cpt > 0) {
+    if (!PLAIN && a.cpt > 0) {
       const int run = cc / a.cpt;
       return a.in_run_off[run] + (long)(cc - run * a.cpt) * CK;
     }
@@ -183,7 +201,7 @@ static __device__ __forceinline__ void igemm_conv_body(const ConvArgs& a) {
     if (PERS) {
       if (tg == 0) {
         const char* src = halo0 + 4 * coff(cc);   // only dereferenced through in-image offsets
-        if (interior && (cc + 1) * CK <= a.Cin) {
+        if (interior && (PLAIN || (cc + 1) * CK <= a.Cin)) {
 #pragma unroll
           for (int i = 0; i < XFULL; ++i) xr[i] = *reinterpret_cast<const f32x4*>(src + xgb[i]);
           if (XPART) {
@@ -194,7 +212,7 @@ static __device__ __forceinline__ void igemm_conv_body(const ConvArgs& a) {
           for (int i = 0; i < XPIECES; ++i) {
             const int iy = ty0 + (xyx[i] >> 16) - PAD, ix = tx0 + ((xyx[i] >> 8) & 255) - PAD;
             const bool ok = (i < XFULL || in_last) && iy >= 0 && iy < a.H && ix >= 0 && ix < a.W &&
-                            (cc * CK + (xyx[i] & 255)) < a.Cin;
+                            (PLAIN || (cc * CK + (xyx[i] & 255)) < a.Cin);
             f32x4 v = {0.f, 0.f, 0.f, 0.f};
             if (ok) v = *reinterpret_cast<const f32x4*>(src + xgb[i]);
             xr[i] = v;
@@ -337,9 +355,27 @@ static __device__ __forceinline__ void igemm_conv_body(const ConvArgs& a) {
   }
 
   if (dbg && tid == 0) dbg[4] = __builtin_amdgcn_s_memtime();
+  {
+    // The run-time-flag body of the persistent 5x5 forms reads the epilogue's fields again per item
+    // (dg_reload_conv_args): held across the item loop they were 126 / 144 spilled SGPRs, whose VGPR lanes cost
+    // <16,5,16,25,true> its third wave per SIMD -- and a kernel is allocated the registers of its widest body.  The sizes
+    // the item loop keeps anyway are taken from it.
+    constexpr bool RELOAD = PERS && KS == 5 && EC == 0;
+    ConvArgs a_item;
+    if constexpr (RELOAD) {
+      dg_reload_conv_args(&a_item);
+      a_item.H = a.H; a_item.W = a.W; a_item.Cout = a.Cout;
+    }
+    const ConvArgs& a_epi = RELOAD ? a_item : a;
+    {
+      const ConvArgs& a = a_epi;
 #define EPI_HEAD HEAD
+#define EPI_CLASS Conv5Epi<EC>
 #include "igemm_epilogue.inc"
+#undef EPI_CLASS
 #undef EPI_HEAD
+    }
+  }
   if (dbg && tid == 0) {
     dbg[5] = __builtin_amdgcn_s_memtime();
     dbg[6] = __builtin_amdgcn_s_memrealtime() - dbg[6];
@@ -348,9 +384,22 @@ static __device__ __forceinline__ void igemm_conv_body(const ConvArgs& a) {
   } while (PERS && (id += gridDim.x) < nPix * nNTall);
 }
 
+// The persistent 5x5 forms hold one item loop per epilogue class inside the one kernel (its name, grid and LDS size are
+// pinned): the class id is uniform over the launch, read once, and the loop it selects carries its flag set as
+// compile-time constants.  Every other instantiation is the one body it always was.
 template <int MF, int KS, int CK, int TAPG, bool PERS>
 __global__ __launch_bounds__(256, (PERS && KS == 3) ? (CK == 8 ? 4 : 3) : 1) void igemm_conv_kernel(const ConvArgs a) {
-  igemm_conv_body<MF, KS, CK, TAPG, PERS, false>(a);
+  if constexpr (PERS && KS == 5) {
+    switch (a.epi_class) {
+      case 1: igemm_conv_body<MF, KS, CK, TAPG, PERS, false, 1>(a); break;
+      case 2: igemm_conv_body<MF, KS, CK, TAPG, PERS, false, 2>(a); break;
+      case 3: igemm_conv_body<MF, KS, CK, TAPG, PERS, false, 3>(a); break;
+      case 4: igemm_conv_body<MF, KS, CK, TAPG, PERS, false, 4>(a); break;
+      default: igemm_conv_body<MF, KS, CK, TAPG, PERS, false, 0>(a); break;
+    }
+  } else {
+    igemm_conv_body<MF, KS, CK, TAPG, PERS, false>(a);
+  }
 }
 
 // gen_17 + gen_segmentation in one launch (32 -> 32 3x3, then 32 -> 1 and tanh): the 8-channel-chunk kernel
@@ -469,6 +518,9 @@ int dg_conv_tile_prepare(const ConvPlan& pl, const ConvArgs& a, DgConvLaunch* L)
     return DG_ERR_ARG;
   }
   L->a = a;
+  // (a class launch is a plain one, see igemm_conv_body)
+  const bool plain = a.groups <= 1 && a.cpt <= 0 && !a.dbg && (a.Cin % t->CK) == 0;
+  L->a.epi_class = (t->KS == 5 && plain) ? dg_conv5_epi_class(dg_epilogue_flags(a.ep)) : 0;
   L->a.lgx = cdiv(a.W, 16) * cdiv(a.H, 16) * a.B;
   L->a.lgy = cdiv(a.Cout, t->MF) * (a.groups > 1 ? a.groups : 1);
   const long total = (long)L->a.lgx * L->a.lgy;

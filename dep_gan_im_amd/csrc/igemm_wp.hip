@@ -33,14 +33,22 @@
 // the most: 12 / 12 / 11 / 12 for 16->16 / 16->32 / 32->16 / 32->32 (32->16 cannot reach three waves on every SIMD at the
 // plan's 16-channel chunks: 51.2 KB + 12 x 10 KB > 160 KB).  Same panel (the 5x5 tile plans of dg_plan_conv), same K order,
 // the plan's chunk width for all four pairs, same epilogue text: bit-identical to the tile kernel
-// (tests/test_gpu_conv5_ws.py).  -Rpass-analysis=kernel-resource-usage: <32, 8> 120 VGPRs, <16, 16> 158 VGPRs, no scratch
+// (tests/test_gpu_conv5_ws.py).  -Rpass-analysis=kernel-resource-usage: <32, 8> 124 VGPRs, <16, 16> 162 VGPRs, no scratch
 // (the 3x3 instantiation: 114, none).
 // MEASURED (profiles/ws5_experiments.md; tools/ab_ws5.py, against the tile kernel in one process): 16->16 @256^2 -8.5 % at
 // batch 96 (0.707 -> 0.773 of the fp32 matrix peak), -4.4 % at batch 32; 32->32 @128^2 -7.6 % at batch 96 (0.787 -> 0.852),
 // +5.4 % at batch 32 (2.7 items per wave slot); 16->32 @128^2 -9.3 % / -5.0 % with 16 waves (12 waves: -9.1 % / +5.1 %);
 // 32->16 +3 ... +5 % at both batches.  Default where it is faster (dg_conv_igemm_ws5_supported), the tile kernel
 // elsewhere.  Canonical step: 49.83 -> 49.16 ms forced on for all eight launches, 49.66 -> 48.74 ms with that default
-// (medians of five alternating runs; every run with it faster than every run without).  Counters not read yet.
+// (medians of five alternating runs; every run with it faster than every run without).
+// EPILOGUE CLASSES (profiles/conv5_classes_experiments.md): igemm_ws5_kernel holds five item loops, selected once per wave by
+// ConvArgs::epi_class (dg_conv5_epi_class: {bias, relu}, {bias, relu, pool}, {mask}, {} -- the flag sets of the critics'
+// layers; 0 = the loop that reads the flags at run time, which is the parent's and keeps its registers and its speed).
+// A class loop carries its flag set as constants (EPI_CLASS of igemm_epilogue.inc): no test, descriptor, lane offset or
+// stride of an absent operand, and none of the 65 / 105 SGPRs the run-time loop spills.  Same statements, same loads:
+// bit-identical (tests/test_gpu_conv5_classes.py).  The kernel's name, grid, block and LDS size do not depend on the class.
+// Counters, 16->16 @256^2 batch 96, per wave (32 items): SALU 4474 -> 2833, VALU without MFMAs 11492 -> 7897, wave
+// cycles -3.9 %; the eight launches -1.7 ... -5.1 %.
 #include <stdlib.h>
 
 #include "common.h"
@@ -97,7 +105,8 @@ template <> struct WpMfma<16> {
 // ABL: ablation bits for tools/ab_wp.py (0 = the product kernel): 1 no epilogue, 2 no staging after an item's first
 // chunk, 4 no MFMAs
 // The number of waves is the launch's (blockDim.x / 64 <= NWMAX): the launcher takes what the LDS budget admits.
-template <int MF, int KS, int CK, int ABL>
+// EC: epilogue class of the 5x5 forms (common.h, Conv5Epi; the 3x3 form is class 0 as it always was)
+template <int MF, int KS, int CK, int ABL, int EC = 0>
 static __device__ __forceinline__ void igemm_wp_body(const ConvArgs& a) {
   typedef WpGeo<MF, KS, CK> G;
   constexpr int NT = G::NT, MT = G::MT, TW = G::TWX, PAD = G::PAD, NTAPS = G::NTAPS, CKP = G::CKP;
@@ -291,6 +300,7 @@ static __device__ __forceinline__ void igemm_wp_body(const ConvArgs& a) {
 #define EPI_ES_BASE wbuf
 #define EPI_OYW ty0
 #define EPI_FULL ((ty0 + 4 <= a.H) && (tx0 + 16 <= a.W))
+#define EPI_CLASS Conv5Epi<EC>
         // 32-pixel tiles go through the scratch one after the other (it holds one); the four 16-pixel tiles fit at once
         if constexpr (MF == 32) {
 #define EPI_PHASED
@@ -299,6 +309,7 @@ static __device__ __forceinline__ void igemm_wp_body(const ConvArgs& a) {
         } else {
 #include "igemm_epilogue.inc"
         }
+#undef EPI_CLASS
 #undef EPI_PRE_SYNC
 #undef EPI_ES_BASE
 #undef EPI_OYW
@@ -315,12 +326,20 @@ __global__ __launch_bounds__(WP_NW * 64, 1) void igemm_wp_kernel(const ConvArgs 
   igemm_wp_body<32, 3, 8, ABL>(a);
 }
 
-// the weight-stationary 5x5 forms: compiled for up to 16 waves (MF = 32: 120 VGPRs) and 12 waves (MF = 16: 158 VGPRs),
+// the weight-stationary 5x5 forms: compiled for up to 16 waves (MF = 32: 124 VGPRs) and 12 waves (MF = 16: 162 VGPRs),
 // no scratch in either
 constexpr int ws5_nwmax(int MF) { return MF == 32 ? 16 : 12; }
+// One item loop per epilogue class inside the one kernel (its name, grid and LDS size are pinned): the class id is
+// wave-uniform, read once, and the loop it selects carries its flag set as compile-time constants
 template <int MF, int CK>
 __global__ __launch_bounds__(ws5_nwmax(MF) * 64, 1) void igemm_ws5_kernel(const ConvArgs a) {
-  igemm_wp_body<MF, 5, CK, 0>(a);
+  switch (a.epi_class) {
+    case 1: igemm_wp_body<MF, 5, CK, 0, 1>(a); break;
+    case 2: igemm_wp_body<MF, 5, CK, 0, 2>(a); break;
+    case 3: igemm_wp_body<MF, 5, CK, 0, 3>(a); break;
+    case 4: igemm_wp_body<MF, 5, CK, 0, 4>(a); break;
+    default: igemm_wp_body<MF, 5, CK, 0, 0>(a); break;
+  }
 }
 
 }  // namespace
@@ -446,6 +465,7 @@ int dg_conv_ws5_prepare(const ConvPlan& pl, const ConvArgs& a, DgConvLaunch* L) 
   const int nw = ws5_waves_of(pl, a.Cin);
   const size_t wave = wide ? WpGeo<32, 5, 8>::WAVE_FLOATS : WpGeo<16, 5, 16>::WAVE_FLOATS;
   L->a = a;
+  L->a.epi_class = dg_conv5_epi_class(dg_epilogue_flags(a.ep));
   L->a.lgx = (int)wp_groups(a, nw);
   L->a.lgy = 1;
   // one workgroup per CU; a multiple of 8 when the groups are dealt over the XCDs

@@ -321,6 +321,13 @@ int depgan_wino_epilogue_class(unsigned flags, int form) {
   }
   return dg_wino_epi_class(flags, form);
 }
+int depgan_conv5_epilogue_class(unsigned flags) {
+  if (flags & ~(unsigned)DG_EPF_ALL) {
+    dg_set_error("conv5_epilogue_class: flags 0x%x outside DEPGAN_EPF_ALL", flags);
+    return -1;
+  }
+  return dg_conv5_epi_class(flags);
+}
 // A launch description for the host-only entries below.  Only which operands are present matters to the selection:
 // every present one points at these floats
 static ConvArgs op_flag_args(unsigned flags, int B, int H, int W, int Cin, int Cout) {

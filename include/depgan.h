@@ -941,7 +941,13 @@ int depgan_op_conv3x3_wino_gathered(const float* in, long isB, long isY, long is
  *   8-row tiles, persistent grid, class 1) that depgan_op_conv2d_fused on path 8 launches for a (B, H, W, Cin) -> Cout
  *   convolution with this flag set on the current device, from the same selection function the launcher calls; written
  *   to buf (cap bytes, NUL-terminated).  Launches nothing.  Status 1 for bad arguments, 3 for a shape the kernel does
- *   not cover. */
+ *   not cover.
+ * The 5x5 kernels (paths 1 and 9 with KS = 5: igemm_ws5_kernel and the persistent igemm_conv_kernel<.,5,.,25,true>) have
+ * classes too, selected INSIDE the kernel: the kernel's name, grid and LDS size are the same for every class, and the
+ * same switch sends every launch through the run-time-flag body.
+ * depgan_conv5_epilogue_class(flags): host only, no HIP call: 1 {bias, relu}, 2 {bias, relu, pool}, 3 {mask}, 4 {} (no
+ *   flag); 0 = the run-time-flag body: every other set, and everything while the switch is off.  -1 (and a message) for
+ *   flags outside DEPGAN_EPF_ALL. */
 #define DEPGAN_EPF_BIAS 1
 #define DEPGAN_EPF_AFFINE 2
 #define DEPGAN_EPF_FILM 4
@@ -956,6 +962,7 @@ int depgan_op_conv3x3_wino_gathered(const float* in, long isB, long isY, long is
 int depgan_set_epilogue_classes(int on);
 int depgan_get_epilogue_classes(void);
 int depgan_wino_epilogue_class(unsigned flags, int form);
+int depgan_conv5_epilogue_class(unsigned flags);
 int depgan_op_conv3x3_wino_kernel_name(unsigned flags, int B, int H, int W, int Cin, int Cout, char* buf, int cap);
 /* The 2x2 / stride-2 transposed convolution on the implicit-GEMM kernels, w_hwoi the Keras kernel (2, 2, Cout, Cin).
  * form 0: forward as ONE grouped launch of four 1x1 convolutions: in (B, H, W, Cin) -> out (B, 2H, 2W, Cout), with
