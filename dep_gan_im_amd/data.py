@@ -564,6 +564,7 @@ def balanced_class_weights(counts, rule="inverse"):
 # ---- training-time augmentation (depgan_data_augment, csrc/augment.hip) ----
 
 AUG_NPARAM = _lib._K["DEPGAN_AUG_NPARAM"]
+AUG_MAX_GRID = _lib._K["DEPGAN_AUG_MAX_GRID"]        # a control grid of `augment` has 4 .. this many points per axis
 _BORDERS = {"edge": 0, "constant": 1}
 _ROT90 = np.array(((1.0, 0.0), (0.0, 1.0), (-1.0, 0.0), (0.0, -1.0)))   # (cos, sin) of 0, 90, 180, 270 degrees, exactly
 
@@ -652,8 +653,20 @@ def _aug_labels(labels, n_src, H, W, dev):
                      % (n_src, H, W, n_src, H, W, _lib.MAX_HEAD_CLASSES, shape))
 
 
+def _aug_fields_shape(fields, n):
+    """The host-side check of the control grids of `augment`: (n, 3, gh, gw), or (3, gh, gw) for every sample, with
+    gh and gw in [4, AUG_MAX_GRID].  Returns (gh, gw)."""
+    shape = tuple(int(d) for d in fields.shape) if hasattr(fields, "shape") else np.shape(fields)
+    if len(shape) not in (3, 4) or shape[-3] != 3 or (len(shape) == 4 and shape[0] != n):
+        raise ValueError("augment: fields must be (%d, 3, gh, gw) or (3, gh, gw), got shape %s" % (n, shape))
+    gh, gw = shape[-2:]
+    if not (4 <= gh <= AUG_MAX_GRID and 4 <= gw <= AUG_MAX_GRID):
+        raise ValueError("augment: a control grid has 4 to %d points per axis, got %d x %d" % (AUG_MAX_GRID, gh, gw))
+    return gh, gw
+
+
 def augment(x, labels=None, params=None, index=None, border="edge", x_fill=0.0, label_fill=0, device=None,
-            stream=None):
+            stream=None, fields=None, return_fields=False):
     """The batch gather, an affine warp and an intensity change in one launch (depgan_data_augment).
     x: (n_src, H, W, nicg) float32 images, nicg 1 or 2; labels: None, class codes (n_src, H, W) or (n_src, H, W, 1)
     (uint8, or integral values in [0, 255] of another dtype), or one-hot (n_src, H, W, C) float32; NumPy arrays or
@@ -665,7 +678,15 @@ def augment(x, labels=None, params=None, index=None, border="edge", x_fill=0.0, 
     puts x_fill and label_fill outside the image (one-hot: the row with 1.0 at label_fill, all zeros when
     label_fill < 0 -- the ignored pixel of compile(class_weight=...)).  Returns new device tensors (x_out, labels_out)
     of n samples; labels_out is None without labels.  Every value is bit for bit what the float32 formula of
-    include/depgan.h gives in NumPy (tests/augment_ref.py)."""
+    include/depgan.h gives in NumPy (tests/augment_ref.py).
+    fields: None, or control grids (n, 3, gh, gw) float32, one set per output sample, or (3, gh, gw) for all of them,
+    gh and gw in [4, AUG_MAX_GRID]; a NumPy array or a tensor.  The same single launch (depgan_data_augment_fields)
+    then evaluates each plane as a cubic B-spline over the image and adds plane 0 to the source row and plane 1 to the
+    source column of every output pixel (an elastic deformation, in source pixels) and multiplies the interpolated
+    intensity by 1 + plane 2 before the gain (a bias field); labels follow the displacement and do not see the bias.
+    All-zero grids give the bits of fields=None; tests/elastic_ref.py is the NumPy restatement.  return_fields=True
+    (only with fields) returns (x_out, labels_out, dense) with dense (n, H, W, 3) float32, the three planes at every
+    output pixel."""
     import torch
     lib = _lib.load()
     if border not in _BORDERS:
@@ -674,6 +695,12 @@ def augment(x, labels=None, params=None, index=None, border="edge", x_fill=0.0, 
     if len(shape) != 4 or min(shape) < 1 or shape[3] not in (1, 2):
         raise ValueError("augment: images must be (n_src, H, W, 1 or 2), got shape %s" % (shape,))
     n_src, H, W, nicg = shape
+    if fields is None:
+        if return_fields:
+            raise ValueError("augment: return_fields needs fields")
+    else:
+        count = int(index.numel()) if isinstance(index, torch.Tensor) else int(np.size(index))
+        gh, gw = _aug_fields_shape(fields, n_src if index is None else count)
     if isinstance(x, torch.Tensor):
         dev = x.device if device is None and x.is_cuda else torch.device(device or "cuda:0")
         xs = x.to(device=dev, dtype=torch.float32).contiguous()
@@ -713,10 +740,22 @@ def augment(x, labels=None, params=None, index=None, border="edge", x_fill=0.0, 
     ps = ps.contiguous()
     x_out = torch.empty((n, H, W, nicg), dtype=torch.float32, device=dev)
     l_out = None if kind == 0 else torch.empty((n,) + tuple(lshape), dtype=ls.dtype, device=dev)
-    _lib.check(lib.depgan_data_augment(_p(xs), nicg, _p(ls), kind, Cc, _p(idx), n_src, _p(ps), n, H, W,
-                                       _BORDERS[border], float(x_fill), int(label_fill), _p(x_out), _p(l_out),
-                                       _stream(dev, stream)), "depgan_data_augment")
-    return x_out, l_out
+    if fields is None:
+        _lib.check(lib.depgan_data_augment(_p(xs), nicg, _p(ls), kind, Cc, _p(idx), n_src, _p(ps), n, H, W,
+                                           _BORDERS[border], float(x_fill), int(label_fill), _p(x_out), _p(l_out),
+                                           _stream(dev, stream)), "depgan_data_augment")
+        return x_out, l_out
+    if isinstance(fields, torch.Tensor):
+        fs = fields.to(device=dev, dtype=torch.float32)
+    else:
+        fs = torch.from_numpy(np.ascontiguousarray(np.asarray(fields), dtype=np.float32)).to(dev)
+    fs = (fs.expand(n, 3, gh, gw) if fs.dim() == 3 else fs).contiguous()
+    dense = torch.empty((n, H, W, 3), dtype=torch.float32, device=dev) if return_fields else None
+    _lib.check(lib.depgan_data_augment_fields(_p(xs), nicg, _p(ls), kind, Cc, _p(idx), n_src, _p(ps), _p(fs), gh, gw, n,
+                                              H, W, _BORDERS[border], float(x_fill), int(label_fill), _p(x_out),
+                                              _p(l_out), _p(dense), _stream(dev, stream)),
+               "depgan_data_augment_fields")
+    return (x_out, l_out, dense) if return_fields else (x_out, l_out)
 
 
 class Augmenter:
@@ -726,10 +765,20 @@ class Augmenter:
     border, x_fill, label_fill: as in `augment`; with compile(ignore_label=k), border='constant' and label_fill=k keep
     the pixels a warp brings in from outside the image out of the loss.  seed: of the instance's own
     np.random.default_rng -- np.random is never touched, so the shuffle of fit is what it is without augmentation.
+    elastic: an elastic deformation; the control displacements of both axes are uniform in +-elastic source pixels.
+    bias: a smooth multiplicative intensity field (the bias field of an MR coil), out = gain*(v*(1 + b)) + offset; the
+    control values are uniform in +-bias, 0 <= bias < 1, and the spline of them stays inside +-bias (its weights are
+    non-negative and sum to 1), so 1 + b stays positive.  field_grid: (gh, gw) control points per axis, 4 to
+    AUG_MAX_GRID, evaluated as a cubic B-spline over the image (`augment`, fields).  The grids are drawn only when one
+    of the two is open, then all three planes, and from a generator of their own spawned from the seed: the parameter
+    rows of a seed are the same with the fields open or closed, and without these arguments nothing changes in any bit
+    or draw.  Displacements above about half a control-cell width, (H-1)/(gh-3) pixels, can fold the map (two output
+    pixels showing the same source pixel in reversed order); they are not refused.
     GeneratorModel.fit(..., augment=Augmenter(...)) uses it; a hand-written loop calls it: xb, lb = aug(x, labels, idx)."""
 
     def __init__(self, rotate=0.0, scale=(1.0, 1.0), shift=0.0, flip_lr=False, flip_ud=False, gain=(1.0, 1.0),
-                 offset=(0.0, 0.0), border="edge", x_fill=0.0, label_fill=0, seed=None):
+                 offset=(0.0, 0.0), border="edge", x_fill=0.0, label_fill=0, seed=None, elastic=0.0, bias=0.0,
+                 field_grid=(7, 7)):
         def pair(v, name, positive=False):
             lo, hi = (float(v[0]), float(v[1])) if np.ndim(v) == 1 and len(v) == 2 else (np.nan, np.nan)
             if not (np.isfinite(lo) and np.isfinite(hi) and lo <= hi) or (positive and lo <= 0):
@@ -745,12 +794,28 @@ class Augmenter:
             raise ValueError("Augmenter: border must be 'edge' or 'constant', got %r" % (border,))
         self.border, self.x_fill, self.label_fill = border, float(x_fill), label_fill
         self.rng = np.random.default_rng(seed)
+        self.elastic, self.bias = float(elastic), float(bias)
+        if not (np.isfinite(self.elastic) and self.elastic >= 0 and 0 <= self.bias < 1):
+            raise ValueError("Augmenter: elastic must be finite and >= 0 and bias in [0, 1), got %r and %r"
+                             % (elastic, bias))
+        grid = tuple(field_grid) if np.ndim(field_grid) == 1 and len(field_grid) == 2 else ()
+        if not (grid and all(isinstance(g, (int, np.integer)) and not isinstance(g, bool) and 4 <= g <= AUG_MAX_GRID
+                             for g in grid)):
+            raise ValueError("Augmenter: field_grid must be two integers in [4, %d], got %r"
+                             % (AUG_MAX_GRID, field_grid))
+        self.field_grid = (int(grid[0]), int(grid[1]))
+        self.field_rng = np.random.default_rng(np.random.SeedSequence(seed).spawn(1)[0])
+
+    @property
+    def fields_open(self):
+        """True when the elastic or the bias range is open: every call then draws control grids."""
+        return self.elastic > 0 or self.bias > 0
 
     @property
     def identity(self):
-        """True when no range can move anything: every draw is the identity row."""
+        """True when no range can move anything: every draw is the identity row and no field is drawn."""
         return (self.rotate == 0 and self.shift == 0 and self.scale == (1.0, 1.0) and self.gain == (1.0, 1.0)
-                and self.offset == (0.0, 0.0) and not self.flip_lr and not self.flip_ud)
+                and self.offset == (0.0, 0.0) and not self.flip_lr and not self.flip_ud and not self.fields_open)
 
     def draw(self, n, H, W):
         """(n, 8) float32 parameter rows for n samples of H x W pixels.  Every quantity is drawn for every call, in a
@@ -765,11 +830,23 @@ class Augmenter:
         o = r.uniform(self.offset[0], self.offset[1], n)
         return _affine_rows(int(H), int(W), rot, sc, dy, dx, lr & self.flip_lr, ud & self.flip_ud, g, o)
 
+    def draw_fields(self, n):
+        """(n, 3, gh, gw) float32 control grids for n samples: the row and the column displacements, uniform in
+        +-elastic, and the bias, uniform in +-bias, from the field generator (the parameter rows' stream is not
+        touched)."""
+        gh, gw = self.field_grid
+        r = self.field_rng
+        d = r.uniform(-self.elastic, self.elastic, (int(n), 2, gh, gw))
+        b = r.uniform(-self.bias, self.bias, (int(n), 1, gh, gw))
+        return np.concatenate([d, b], 1).astype(np.float32)
+
     def __call__(self, x, labels=None, index=None, device=None):
-        """Draws one row per output sample and applies it: (x_out, labels_out) device tensors, as `augment`."""
+        """Draws one row per output sample -- and, with elastic or bias open, one set of control grids -- and applies
+        them in one launch: (x_out, labels_out) device tensors, as `augment`."""
         n = int(x.shape[0]) if index is None else int(len(index))
-        return augment(x, labels, self.draw(n, int(x.shape[1]), int(x.shape[2])), index, self.border, self.x_fill,
-                       self.label_fill, device)
+        rows = self.draw(n, int(x.shape[1]), int(x.shape[2]))
+        return augment(x, labels, rows, index, self.border, self.x_fill, self.label_fill, device,
+                       fields=self.draw_fields(n) if self.fields_open else None)
 
 
 def data_prep_save(image_data):

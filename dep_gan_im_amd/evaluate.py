@@ -149,6 +149,9 @@ def _stats_arguments(x, n_repeat, mask, tta, border, ddof):
         if tta.gain != (1.0, 1.0) or tta.offset != (0.0, 0.0):
             raise ValueError("predict_stats: a test-time Augmenter must have gain == (1, 1) and offset == (0, 0): an "
                              "intensity change has no inverse on a probability")
+        if tta.fields_open:
+            raise ValueError("predict_stats: a test-time Augmenter must have elastic == 0 and bias == 0: an elastic "
+                             "map has no inverse row to resample the prediction through")
         rows = tta
     elif tta is not None:
         rows = np.asarray(tta.detach().cpu().numpy() if hasattr(tta, "detach") else tta, np.float32)
@@ -170,9 +173,9 @@ def predict_stats(netG, x, n_repeat=10, mask=None, noise_size=32, rng=None, batc
       'count'                                       uint8 (n, H, W): how many draws took part at the pixel
     The noise is drawn from `rng` exactly as predict_mean draws it, so with tta=None and the same rng state 'mean' is
     predict_mean's result bit for bit; the forward is eng.g_forward, so an inference_copy("bfloat16") works unchanged.
-    tta: a data.Augmenter (gain and offset closed, else ValueError; it draws n rows per repeat from its own generator)
-    or an array (n_repeat, n, 8) of parameter rows.  Repeat r predicts on data.augment(x, params=rows[r]) and is
-    accumulated in the original frame through data.affine_inverse(rows[r]); the mask applies in the original frame.
+    tta: a data.Augmenter (gain, offset, elastic and bias closed, else ValueError; it draws n rows per repeat from its
+    own generator) or an array (n_repeat, n, 8) of parameter rows.  Repeat r predicts on data.augment(x, params=rows[r])
+    and is accumulated in the original frame through data.affine_inverse(rows[r]); the mask applies in the original frame.
     border 'edge' clamps the taps of that resampling, and every draw counts everywhere; 'valid' lets a draw take part
     only where every tap that carries weight lies inside its prediction, so 'count' can fall below n_repeat near the
     corners (a pixel no draw reached holds 0.0 everywhere).  At most 255 draws."""

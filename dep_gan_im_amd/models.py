@@ -741,7 +741,10 @@ class GeneratorModel(_Model):
         them).
         augment: a data.Augmenter.  Every training batch is then made by one depgan_data_augment launch: a random affine
         warp of the images (bilinear) and their labels (nearest), and a gain / offset on the intensities, drawn per
-        sample from the Augmenter's own generator (np.random, and with it the shuffle, is not touched).  When the
+        sample from the Augmenter's own generator (np.random, and with it the shuffle, is not touched).  With
+        Augmenter(elastic=..., bias=...) the same launch (depgan_data_augment_fields) also bends every sample by a
+        smooth random displacement and multiplies it by a smooth random bias field, from control grids drawn per
+        sample.  When the
         images (float32) and the labels (uint8 class codes, or float32 one-hot rows) are tensors on the engine's device,
         the launch also does the batch gather: it reads the epoch's order[i:i+bs] as its index and x[idx] / labels[idx]
         are never formed.  Otherwise the batch is sliced as without it, uploaded and augmented.  The noise is gathered

@@ -533,6 +533,36 @@ int depgan_labels_to_onehot(const float* coded_dev, long npix, int C, float* one
 int depgan_data_augment(const float* x_src, int nicg, const void* lab_src, int lab_kind, int C, const long* index_dev,
                         long n_src, const float* params_dev, int n, int H, int W, int border, float x_fill,
                         int label_fill, float* x_out, void* lab_out, void* stream);
+/* depgan_data_augment_fields: depgan_data_augment with an elastic deformation and a smooth multiplicative intensity
+ * (bias) field per output sample, in the same single launch.  Every argument of depgan_data_augment means what it means
+ * there, and:
+ *   fields_dev (n, 3, gh, gw) float32, a control grid per output sample i (not per source slice): plane 0 the row
+ *   displacement dy in source pixels, plane 1 the column displacement dx, plane 2 the bias b.  gh, gw in
+ *   [4, DEPGAN_AUG_MAX_GRID].  Each plane C is evaluated at every output pixel as a uniform cubic B-spline whose
+ *   control cells span the image, (gh-3) x (gw-3) of them:
+ *     ky = (float)((double)(gh-3) / (double)(H-1))   (0 when H == 1), kx likewise from gw and W   -- host, rounded once
+ *     u  = (float)oy * ky;  c = fminf(floorf(u), (float)(gh-4));  t = u - c       (c_x, t_x the same from ox, kx, gw)
+ *     t2 = t*t;  t3 = t2*t;  g = 1 - t
+ *     B0 = (g*g)*g;  B1 = (3*t3 - 6*t2) + 4;  B2 = ((3*t2 - 3*t3) + 3*t) + 1;  B3 = t3        (six times the weights)
+ *     r[j] = ((B0y*C[c_y][j] + B1y*C[c_y+1][j]) + B2y*C[c_y+2][j]) + B3y*C[c_y+3][j]          j = c_x .. c_x+3
+ *     f    = (((B0x*r[c_x] + B1x*r[c_x+1]) + B2x*r[c_x+2]) + B3x*r[c_x+3]) * (1.0f/36.0f)
+ *   and with f_dy, f_dx, f_b the three planes' values and sy, sx of depgan_data_augment:
+ *     sy' = sy + f_dy          sx' = sx + f_dx
+ *     the bilinear taps and weights and the nearest label pixel are depgan_data_augment's statements on sy', sx'
+ *     out = gain*((top*(1-fy) + bot*fy) * (1 + f_b)) + offset                  per channel; labels do not see b
+ *   every operation a single float32 operation in that order, so a NumPy float32 restatement gives the same bits
+ *   (tests/elastic_ref.py), whichever way the kernel shares the r[j] among its lanes.  An all-zero grid gives
+ *   depgan_data_augment's bits (x + 0, v * 1).  A field value may be anything, +-inf, NaN and 1e30 included: a tap is
+ *   compared with the image and clamped into it as a float before it becomes an index, as for any coordinate.
+ *   dense_out: NULL, or (n, H, W, 3) float32 that receives f_dy, f_dx, f_b of every output pixel; a sample whose
+ *   index is outside [0, n_src) gets zeros there (and the fill values in x_out / lab_out, as above).
+ *   Status 1: as depgan_data_augment, fields_dev NULL, gh or gw outside [4, DEPGAN_AUG_MAX_GRID], or an output range
+ *   (x_out, lab_out, dense_out) that overlaps a source range (fields_dev among them) or another output. */
+#define DEPGAN_AUG_MAX_GRID 32
+int depgan_data_augment_fields(const float* x_src, int nicg, const void* lab_src, int lab_kind, int C,
+                               const long* index_dev, long n_src, const float* params_dev, const float* fields_dev,
+                               int gh, int gw, int n, int H, int W, int border, float x_fill, int label_fill,
+                               float* x_out, void* lab_out, float* dense_out, void* stream);
 int depgan_eval_accumulate_channels(const float* pred_dev, const float* mask_dev, double* acc_dev, long npix, int C,
                                     void* stream);
 int depgan_eval_label_counts(const double* pred_dev, int C, const float* code_real_dev, const float* mask1_dev,
