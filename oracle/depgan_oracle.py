@@ -150,9 +150,11 @@ def init_generator(seed, nicg=1, fm=32, nc_out=1, randomize_bn=True, bias_std=0.
     return P
 
 
-def init_critic(seed, bias_std=0.0, img=256):
-    """Parameters of Dis_C2D_FCN1((img,img,1)), GT:316-345 (img=256 in the
-    reference; smaller img only for fast tests: Flatten is (img/16)^2 long)."""
+def init_critic(seed, bias_std=0.0, img=256, width=None):
+    """Parameters of Dis_C2D_FCN1((H,W,1)), GT:316-345 (256 x 256 in the reference; other sizes only for fast tests:
+    Flatten is (H/16)*(W/16) long).  img: the side of a square image, or the height with `width` given, or an (H, W)
+    pair.  The draws do not depend on how the size was spelled: a square size gives the same parameters as ever."""
+    H, W = (int(img[0]), int(img[1])) if isinstance(img, (tuple, list)) else (int(img), int(img if width is None else width))
     rng = np.random.default_rng(seed)
     P = OrderedDict()
     for name, k, ci, co, _ in DIS_TRUNK:
@@ -160,7 +162,7 @@ def init_critic(seed, bias_std=0.0, img=256):
         P["conv2d_" + name + "/bias"] = (bias_std * rng.standard_normal(co)).astype(np.float32)
     P["dis_9/kernel"] = _he_normal(rng, (1, 1, 256, 1), 256)          # GT:339
     P["dis_9/bias"] = (bias_std * rng.standard_normal(1)).astype(np.float32)
-    nflat = (img // 16) ** 2
+    nflat = (H // 16) * (W // 16)
     P["dense_1/kernel"] = _he_normal(rng, (nflat, 1), nflat)          # GT:342
     P["dense_1/bias"] = (bias_std * rng.standard_normal(1)).astype(np.float32)
     return P

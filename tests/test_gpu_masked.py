@@ -19,12 +19,18 @@ pytestmark = pytest.mark.gpu
 D_LAYERS = ["dis_0a", "dis_0b", "dis_1a", "dis_1b", "dis_2", "dis_3", "dis_4", "dis_5", "dis_6", "dis_7", "dis_8"]
 
 
+def hw(img):
+    """(H, W) of an image size given as the side of a square or as an (H, W) pair"""
+    return (int(img[0]), int(img[1])) if isinstance(img, (tuple, list)) else (int(img), int(img))
+
+
 def setup(img, B, seed, noisy=True, trained_regime=False, nicg=1):
     from oracle import depgan_oracle as O
+    H, W = hw(img)
     PG = O.init_generator(seed, nicg=nicg, bias_std=0.05)
-    PD1 = O.init_critic(seed + 1, bias_std=0.05, img=img)
-    PD2 = O.init_critic(seed + 2, bias_std=0.05, img=img)
-    x, y2, z, ep = O.synth_batch(seed + 5, B, img, img, nicg=nicg)
+    PD1 = O.init_critic(seed + 1, bias_std=0.05, img=(H, W))
+    PD2 = O.init_critic(seed + 2, bias_std=0.05, img=(H, W))
+    x, y2, z, ep = O.synth_batch(seed + 5, B, H, W, nicg=nicg)
     if noisy:
         rng = np.random.default_rng(seed)
         x = (x + 0.02 * rng.uniform(size=x.shape)).astype(np.float32)
@@ -38,7 +44,7 @@ def setup(img, B, seed, noisy=True, trained_regime=False, nicg=1):
 
 def engine(img, B, PG, PD1, PD2, **kw):
     from dep_gan_im_amd import Engine
-    eng = Engine(B, img, img, PG["conv2d_gen_0/kernel"].shape[2], **kw)
+    eng = Engine(B, *hw(img), PG["conv2d_gen_0/kernel"].shape[2], **kw)
     for n, P in (("G", PG), ("D_y2", PD1), ("D_dem", PD2)):
         eng.set_weights(n, P)
     eng.debug_capture(True)
