@@ -1895,6 +1895,24 @@ int depgan_debug_tensor(depgan_ctx* c, const char* name, float* host, long cap, 
       H = c->dl[l].H; W = c->dl[l].W; C = c->dl[l].Cout;
       break;
     }
+  } else if (starts("d/dz/") || starts("d/pool/")) {
+    const bool pool = starts("d/pool/");
+    const std::string ln = pool ? rest("d/pool/") : rest("d/dz/");
+    for (size_t l = 0; l < c->dl.size(); ++l) {
+      if (c->dl[l].name != ln) continue;
+      if (pool && !c->dl[l].pool) break;     // not a pooled layer: unknown
+      v = pool ? c->d_pool[l].view() : c->d_dz[l].view();
+      N = c->NB3; C = c->dl[l].Cout;
+      H = pool ? c->dl[l].H / 2 : c->dl[l].H;
+      W = pool ? c->dl[l].W / 2 : c->dl[l].W;
+      break;
+    }
+  } else if ((nm == "d/in" || nm == "d/g0") && !c->dl.empty()) {
+    // d/in: [real | fake | mixed]; a critic closure leaves u0 in the mixed slots.  d/g0: the image gradients
+    const bool in = nm == "d/in";
+    H = c->cfg.height; W = c->cfg.width; C = 1;
+    v = make_view(in ? c->d_in : c->g0, H, W, 1);
+    N = in ? c->NB3 : 2 * B;
   }
   if (!v.p || N == 0) { dg_set_error("debug_tensor: unknown tensor '%s'", name); return DG_ERR_ARG; }
   shape[0] = N; shape[1] = H; shape[2] = W; shape[3] = C;

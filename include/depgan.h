@@ -702,6 +702,15 @@ int depgan_eval_cc_overlap(const int* labels, const unsigned char* other_or_null
  *                       sample slots [real | fake | mixed] (a generator pass leaves D_y2(fake_y2) in slots [0, batch) and
  *                       D_dem(attr) in [batch, 2 batch))
  *     "d/mixed/<layer>" the captured copy of the mixed pass (batch samples; needs depgan_debug_capture)
+ *     "d/dz/<layer>"    gradient at the conv output of critic layer <layer> (after the ReLU mask), (3*batch, H_l, W_l,
+ *                       Cout_l), slots as "d/act/"; a critic closure leaves g_z (upstream 1) in the mixed slots
+ *     "d/pool/<layer>"  pooled output of a pooling critic layer (dis_0b, dis_1b, dis_3, dis_5), (3*batch, H_l/2, W_l/2,
+ *                       Cout_l); after a critic closure the mixed slots hold the penalty's u gathered at the arg-max
+ *                       (the mixed slots of "d/act/" of the non-pooling layers hold u as well).  Any other layer: status 1
+ *     "d/in"            the critic input batch (3*batch, H, W, 1) [real | fake | mixed]; after a critic closure the mixed
+ *                       slots hold u0 (GT:544-545); a generator pass does not write it
+ *     "d/g0"            image gradients (2*batch, H, W, 1): after a critic closure only the first batch samples are
+ *                       defined (d D(mixed) / d mixed); after a generator training closure D_y2's half, then D_dem's
  * Status 1 for an unknown name, a tensor that was not captured, or cap_floats too small. */
 int depgan_debug_capture(depgan_ctx* ctx, int on);
 int depgan_debug_tensor(depgan_ctx* ctx, const char* name, float* host_dst, long cap_floats, int shape[4]);

@@ -393,7 +393,8 @@ CLOSURES = (("netG_no_update", "g"), ("netD_y2_train", "d"), ("netD_dem_train", 
 def test_model_against_the_oracle_under_the_mode_s_rounding_rule(lib, monkeypatch):
     """Inputs, sequence of closures and tolerances of test_config4_bf16_matrix_pipe (64 x 64 x 2, batch 2, seed 57).
     Mode on is held to them against the oracle under the patched rule; mode off against the unpatched oracle is printed
-    next to it (it is asserted by that test)."""
+    next to it (it is asserted by that test).  The critic gradients at the end are printed, not gated: they are held
+    launch by launch, against float64 of the operands each launch stored, by tests/test_gpu_critic_links.py."""
     import dep_gan_im_amd as dg
     from oracle import depgan_oracle as O
     img, B, seed = 64, 2, 57

@@ -470,7 +470,9 @@ def test_config4_bf16_matrix_pipe(lib):
     oracle 3.3e-2 of the output range, rounding effect itself 2.9e-2; critic 1.7e-3 vs 1.1e-3).  So the forward values
     are pinned at THAT level -- no farther from the rounded oracle than twice the rounding's own effect, mean error a
     tenth of it -- and, as SURVEY 8d says, the loss scalars of the four closures (3e-2; 1e-2 without the count-based M3
-    as long as both sides still hold the same weights).  Masters move by one Adam step."""
+    as long as both sides still hold the same weights).  Masters move by one Adam step.  The critic gradient, "not
+    comparable that tightly" against the oracle below, is held launch by launch -- every launch of the closure against
+    float64 of the operands it stored -- by tests/test_gpu_critic_links.py."""
     import dep_gan_im_amd as dg
     from oracle import depgan_oracle as O
     img, B, seed = 64, 2, 57
