@@ -17,7 +17,7 @@ LIB = os.path.join(HERE, "libdepgan.so")
 SOURCES = ["igemm_conv.hip", "conv_select.hip", "igemm_wp.hip", "igemm_wino.hip", "igemm_bf16.hip", "igemm_bf16s.hip", "deconv_fwd.hip", "deconv_wgrad.hip", "wgrad.hip", "wgrad_bf16.hip", "wgrad_select.hip", "direct.hip", "ops.hip", "noise.hip", "train_ops.hip", "softmax_ce.hip", "model.hip", "op_entries.hip", "op_entries_bf16s.hip", "model_bf16s.hip", "model_bf16s_train.hip",
            "igemm_bf16s_train.hip", "igemm_bf16_mh.hip", "wgrad_bf16s.hip", "ops_bf16s.hip",
            "uresnet.hip", "dice_loss.hip", "boundary_loss.hip", "data.hip", "eval_uresnet.hip", "augment.hip", "eval_stats.hip",
-           "surface_dist.hip", "components.hip"]
+           "surface_dist.hip", "components.hip", "calibration.hip"]
 ARCH = "gfx950"
 
 

@@ -35,6 +35,12 @@ Which lesions were found at all -- lesion-wise recall, precision, F1 and the abs
 connected components labelled on the device (csrc/components.hip):
 
     les = label_lesion_metrics(m["labels"], brain_cod_2tp, classes=(1, 2, 3), voxel_volume=voxel_volume)
+
+Whether the probabilities can be believed -- ECE, MCE, Brier score, NLL, the reliability diagram -- and the temperature
+that calibrates them, from an integer census and three double sums formed on the device (csrc/calibration.hip):
+
+    cal = calibration_metrics(calibration_census(stats["mean"], data.to_codes(brain_cod_2tp), bins=15))
+    fit = fit_temperature(stats["mean"], codes);  prob_T = apply_temperature(stats["mean"], fit["T"])
 """
 from __future__ import annotations
 
@@ -875,3 +881,289 @@ def label_lesion_metrics(labels, code_real, classes=(1, 2, 3), mask=None, **kw):
         keep = up(mask) != 0
         lab, real = lab * keep.to(lab.dtype), real * keep.to(real.dtype)
     return {k: lesion_detection(lab == k, real == k, **kw) for k in classes}
+
+
+# ---- calibration: can the probabilities be believed?  (csrc/calibration.hip) ----
+
+CAL_MAX_BINS, CAL_FIX_SHIFT = _lib._K["DEPGAN_CAL_MAX_BINS"], _lib._K["DEPGAN_CAL_FIX_SHIFT"]
+CAL_SCALARS = ("n", "n_nan", "n_bad", "n_floored")
+
+
+def _float_kind(a, who):
+    """0 for float32, 1 for float64 (a NumPy array or a tensor); ValueError for anything else."""
+    name = str(getattr(a, "dtype", "")).rpartition(".")[2]
+    if name not in ("float32", "float64"):
+        raise ValueError("%s: prob must be float32 or float64, got %s" % (who, getattr(a, "dtype", type(a).__name__)))
+    return 0 if name == "float32" else 1
+
+
+def _cal_args(who, prob, labels=None, ignore_label=None, mask=None, eps=1e-7, eps_positive=False, need_labels=True):
+    """The argument checks the calibration functions share, before anything touches the device.  Returns
+    (shape of prob, prob_kind, ignore code or -1, eps)."""
+    shape = tuple(int(d) for d in getattr(prob, "shape", ()))
+    if len(shape) != 4 or min(shape) < 1 or not 2 <= shape[3] <= _lib.MAX_HEAD_CLASSES:
+        raise ValueError("%s: prob must be (n, H, W, C) with C in 2..%d, got shape %s"
+                         % (who, _lib.MAX_HEAD_CLASSES, shape))
+    kind = _float_kind(prob, who)
+    if shape[0] * shape[1] * shape[2] >= 2 ** 31:
+        raise ValueError("%s: prob has 2^31 pixels or more" % who)
+    if need_labels:
+        lshape = tuple(int(d) for d in getattr(labels, "shape", ()))
+        if lshape != shape[:3] or str(getattr(labels, "dtype", "")).rpartition(".")[2] != "uint8":
+            raise ValueError("%s: labels must be uint8 class codes of shape %s (data.to_codes), got %s %s"
+                             % (who, shape[:3], getattr(labels, "dtype", type(labels).__name__), lshape))
+        if mask is not None and tuple(int(d) for d in getattr(mask, "shape", ())) != shape[:3]:
+            raise ValueError("%s: mask must have the shape of labels, %s" % (who, shape[:3]))
+    if ignore_label is None:
+        ignore = -1
+    elif isinstance(ignore_label, bool) or not isinstance(ignore_label, (int, np.integer)) or not 0 <= ignore_label <= 255:
+        raise ValueError("%s: ignore_label must be None or an integer in 0..255, got %r" % (who, ignore_label))
+    else:
+        ignore = int(ignore_label)
+    try:
+        e = float(eps)
+    except (TypeError, ValueError):
+        e = float("nan")
+    if not (0.0 <= e < 1.0) or (eps_positive and e == 0.0):
+        raise ValueError("%s: eps must lie in %s0, 1), got %r" % (who, "(" if eps_positive else "[", eps))
+    return shape, kind, ignore, e
+
+
+def _cal_tensor(a, dev, dtype):
+    """contiguous, 16-byte aligned device tensor of `a` (host or device), or None"""
+    torch = _torch()
+    if a is None:
+        return None
+    t = a if isinstance(a, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(a))
+    t = t.to(device=dev, dtype=dtype).contiguous()
+    return t.clone() if t.data_ptr() % 16 else t
+
+
+def _cal_device(prob, kind, labels, mask):
+    """the operands on the device.  The mask is judged in its own dtype: the entries get (mask != 0) as float32, so a
+    float64 value that float32 would flush to zero keeps its pixel, as NumPy's `mask != 0` does."""
+    torch = _torch()
+    dev = _surface_device(prob, labels, mask)
+    if mask is not None:
+        mask = mask != 0 if isinstance(mask, torch.Tensor) else np.asarray(mask) != 0
+    return (dev, _cal_tensor(prob, dev, torch.float64 if kind else torch.float32), _cal_tensor(labels, dev, torch.uint8),
+            _cal_tensor(mask, dev, torch.float32), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+
+
+def _cal_scratch(lib, dev, npix, Cc, bins):
+    return _torch().empty((max(1, int(lib.depgan_eval_calibration_scratch_bytes(npix, Cc, bins)) // 8),),
+                          dtype=_torch().float64, device=dev)
+
+
+def calibration_census(prob, labels, bins=15, ignore_label=None, mask=None, eps=1e-7):
+    """The integer tables every calibration figure is formed from, counted on the device in one pass over the pixels
+    (depgan_eval_calibration_census; include/depgan.h states every operation).  prob: (n, H, W, C) float32 (predict) or
+    float64 (predict_mean, predict_stats(...)['mean']); labels: (n, H, W) uint8 class codes (data.to_codes); mask:
+    (n, H, W) or None, a pixel with a zero mask takes no part; ignore_label: a code whose pixels take no part; a row with
+    a NaN takes no part and is counted in n_nan.  All host or device.  `bins` equal-width bins, 1..64.  Returns a dict of
+    NumPy int64 arrays and Python numbers:
+      top_count, top_correct, top_conf_q       (bins): per bin of the top-label confidence its pixels, those of them whose
+                                               arg-max (first maximum) is the true class, and the sum of their
+                                               confidences in units of 2^-32
+      class_count, class_pos, class_prob_q     (C, bins): per class k and bin of p_k the pixels, those of class k, and the
+                                               sum of p_k in units of 2^-32
+      n, n_nan, n_bad, n_floored               pixels that take part, rows with a NaN, codes >= C (always 0: such a code
+                                               raises), pixels whose true-class probability is below eps
+      brier_sum, nll_sum                       sums over the pixels of sum_c (p_c - t_c)^2 and of -log(max(p_true, eps))
+      bins, n_class, eps
+    calibration_metrics turns them into ECE, MCE, Brier, NLL and the reliability diagram."""
+    who = "calibration_census"
+    shape, kind, ignore, eps = _cal_args(who, prob, labels, ignore_label, mask, eps)
+    if isinstance(bins, bool) or not isinstance(bins, (int, np.integer)) or not 1 <= bins <= CAL_MAX_BINS:
+        raise ValueError("%s: bins must be an integer in 1..%d, got %r" % (who, CAL_MAX_BINS, bins))
+    bins, Cc, npix = int(bins), shape[3], shape[0] * shape[1] * shape[2]
+    lib = _lib.load()
+    dev, p, lab, m, stream = _cal_device(prob, kind, labels, mask)
+    scratch = _cal_scratch(lib, dev, npix, Cc, bins)
+    counts = np.zeros((1 + Cc) * bins * 3 + len(CAL_SCALARS), np.int64)
+    sums = np.zeros(2, np.float64)
+    _lib.check(lib.depgan_eval_calibration_census(_p(p), kind, Cc, _p(lab), ignore, _p(m), npix, bins, eps, _p(scratch),
+                                                  C.c_void_p(counts.ctypes.data), C.c_void_p(sums.ctypes.data), stream),
+               "depgan_eval_calibration_census")
+    return census_from_tables(counts, sums, Cc, bins, eps)
+
+
+def census_from_tables(counts, sums, n_class, bins, eps):
+    """The dict of calibration_census from the entry's two host tables (counts: (1 + C) * bins * 3 + 4 int64)."""
+    tab = np.asarray(counts[:(1 + n_class) * bins * 3], np.int64).reshape(1 + n_class, bins, 3)
+    res = {"top_count": tab[0, :, 0].copy(), "top_correct": tab[0, :, 1].copy(), "top_conf_q": tab[0, :, 2].copy(),
+           "class_count": tab[1:, :, 0].copy(), "class_pos": tab[1:, :, 1].copy(), "class_prob_q": tab[1:, :, 2].copy()}
+    res.update((k, int(v)) for k, v in zip(CAL_SCALARS, counts[-len(CAL_SCALARS):]))
+    res.update(brier_sum=float(sums[0]), nll_sum=float(sums[1]), bins=int(bins), n_class=int(n_class), eps=float(eps))
+    if res["n_bad"] > 0:
+        raise ValueError("calibration_census: %d labels are not below the class count %d (and are not the ignore label)"
+                         % (res["n_bad"], n_class))
+    return res
+
+
+def _bin_means(count, hits, q):
+    """(share of hits, mean confidence) per bin, nan for an empty bin; any leading axes"""
+    count = np.asarray(count, np.float64)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        return np.asarray(hits, np.float64) / count, np.asarray(q, np.float64) / 2.0 ** CAL_FIX_SHIFT / count
+
+
+def calibration_metrics(census):
+    """Calibration figures from the tables of calibration_census; pure NumPy, nothing raises.
+      ece                 sum_b n_b / N |acc_b - conf_b| over the top-label bins: the expected calibration error
+      mce                 the largest |acc_b - conf_b| of a non-empty bin
+      classwise_ece       (C): sum_b n_kb / N |pos_kb / n_kb - mean p_k in bin b| per class k, one against the rest;
+      classwise_ece_mean  their mean
+      brier, nll          brier_sum / N, nll_sum / N
+      accuracy, mean_confidence   of the top label; their difference is the over-confidence
+      bin_count, bin_accuracy, bin_confidence   (bins): the reliability diagram, nan in an empty bin
+    An empty bin contributes 0.  N = 0 gives nan figures; n, n_nan and n_floored are passed on and say why.  A bin's
+    confidence is within 2^-33 of the mean of its values (the fixed point of the device sum)."""
+    n = int(census["n"])
+    acc, conf = _bin_means(census["top_count"], census["top_correct"], census["top_conf_q"])
+    pos, pk = _bin_means(census["class_count"], census["class_pos"], census["class_prob_q"])
+    res = {"n": n, "n_nan": int(census["n_nan"]), "n_floored": int(census["n_floored"]),
+           "bin_count": np.asarray(census["top_count"], np.int64), "bin_accuracy": acc, "bin_confidence": conf}
+    nan = float("nan")
+    if n == 0:
+        res.update(ece=nan, mce=nan, classwise_ece=np.full(len(pos), nan), classwise_ece_mean=nan, brier=nan, nll=nan,
+                   accuracy=nan, mean_confidence=nan)
+        return res
+    gap = np.where(res["bin_count"] > 0, np.abs(acc - conf), 0.0)
+    cgap = np.where(np.asarray(census["class_count"]) > 0, np.abs(pos - pk), 0.0)
+    res["ece"] = float(np.sum(res["bin_count"] / n * gap))
+    res["mce"] = float(np.max(gap))
+    res["classwise_ece"] = np.sum(np.asarray(census["class_count"], np.float64) / n * cgap, axis=1)
+    res["classwise_ece_mean"] = float(np.mean(res["classwise_ece"]))
+    res["brier"], res["nll"] = float(census["brier_sum"]) / n, float(census["nll_sum"]) / n
+    res["accuracy"] = float(np.sum(np.asarray(census["top_correct"], np.int64))) / n
+    res["mean_confidence"] = float(int(np.sum(np.asarray(census["top_conf_q"], np.int64)))) / 2.0 ** CAL_FIX_SHIFT / n
+    return res
+
+
+def _temperature_args(who, bounds, tol, max_iter):
+    try:
+        lo, hi = (float(v) for v in bounds)
+    except (TypeError, ValueError):
+        lo = hi = float("nan")
+    if not (0.0 < lo < hi < float("inf")):
+        raise ValueError("%s: bounds must be two temperatures 0 < T_min < T_max, got %r" % (who, bounds))
+    try:
+        tol = float(tol)
+    except (TypeError, ValueError):
+        tol = float("nan")
+    if not (0.0 < tol < float("inf")):
+        raise ValueError("%s: tol must be a finite positive number, got %r" % (who, tol))
+    if isinstance(max_iter, bool) or not isinstance(max_iter, (int, np.integer)) or max_iter < 1:
+        raise ValueError("%s: max_iter must be a positive integer, got %r" % (who, max_iter))
+    return (lo, hi), tol, int(max_iter)
+
+
+def solve_temperature(sums, bounds=(0.05, 20.0), tol=1e-6, max_iter=50):
+    """The solver of fit_temperature on any sums function: sums(beta) -> (N, sum L, sum L', sum L'') as
+    depgan_eval_temperature_sums states them.  L is convex in beta = 1 / T, so Newton's method on beta is safeguarded by
+    a bracket: a step that leaves the bracket goes to the far bound if that has not been looked at yet, else to the
+    middle.  Stops when |sum L'| / N <= tol (converged), at a bound whose slope still points outwards (at_bound), or
+    after max_iter evaluations besides the one at T = 1.  Returns the dict of fit_temperature."""
+    (t_lo, t_hi), tol, max_iter = _temperature_args("solve_temperature", bounds, tol, max_iter)
+    lo, hi = 1.0 / t_hi, 1.0 / t_lo
+    n, L, g, h = (float(v) for v in sums(1.0))
+    calls = 1
+    nan = float("nan")
+    res = {"T": nan, "beta": nan, "nll_before": nan, "nll_after": nan, "iterations": calls, "converged": False,
+           "at_bound": False, "n": int(n)}
+    if not n > 0:
+        return res
+    res["nll_before"] = L / n
+    beta = min(max(1.0, lo), hi)
+    if beta != 1.0:
+        n, L, g, h = (float(v) for v in sums(beta))
+        calls += 1
+    a, b, a_seen, b_seen = lo, hi, False, False
+    while True:
+        slope = g / n
+        if abs(slope) <= tol:
+            res["converged"] = True
+            break
+        if (slope < 0 and beta >= hi) or (slope > 0 and beta <= lo):
+            res["at_bound"] = True
+            break
+        if calls > max_iter:
+            break
+        if slope < 0:
+            a, a_seen = beta, True
+        else:
+            b, b_seen = beta, True
+        cand = beta - g / h if h > 0 and np.isfinite(h) else nan
+        if not a < cand < b:
+            cand = b if slope < 0 and not b_seen else a if slope > 0 and not a_seen else 0.5 * (a + b)
+        beta = cand
+        n, L, g, h = (float(v) for v in sums(beta))
+        calls += 1
+    res.update(T=1.0 / beta, beta=beta, nll_after=L / n, iterations=calls)
+    return res
+
+
+def fit_temperature(prob, labels, ignore_label=None, mask=None, eps=1e-7, bounds=(0.05, 20.0), tol=1e-6, max_iter=50):
+    """The temperature T that minimises the negative log-likelihood of softmax(log(max(prob, eps)) / T) against the
+    labels (temperature scaling, Guo et al. 2017), over the pixels that take part (calibration_census's rule).  Arguments
+    as calibration_census; bounds = (T_min, T_max).  One device pass and one synchronisation per iteration
+    (depgan_eval_temperature_sums returns the loss and its first two derivatives in beta = 1 / T); the probabilities stay
+    on the device.  Before the first pass the labels are checked once on the device (a few elementwise launches over the
+    codes and one synchronisation for the count): a code >= C that is not the ignore label raises ValueError, as in
+    calibration_census.  Returns {'T', 'beta', 'nll_before' (at T = 1), 'nll_after', 'iterations' (device passes),
+    'converged' (|dNLL/dbeta| <= tol), 'at_bound' (the minimum lies outside the bounds; T is the bound), 'n'}.  With no
+    pixel taking part the figures are nan."""
+    who = "fit_temperature"
+    shape, kind, ignore, eps = _cal_args(who, prob, labels, ignore_label, mask, eps, eps_positive=True)
+    _temperature_args(who, bounds, tol, max_iter)
+    Cc, npix = shape[3], shape[0] * shape[1] * shape[2]
+    torch = _torch()
+    lib = _lib.load()
+    dev, p, lab, m, stream = _cal_device(prob, kind, labels, mask)
+    bad = lab >= Cc                  # uint8 against a Python int below 256: no wrap-around
+    if ignore >= 0:                  # -1 means no ignore label; it is never compared with the uint8 codes
+        bad &= lab != ignore
+    if m is not None:
+        bad &= m != 0
+    n_bad = int(bad.sum())
+    if n_bad:
+        raise ValueError("%s: %d labels are not below the class count %d (and are not the ignore label)" % (who, n_bad, Cc))
+    scratch = _cal_scratch(lib, dev, npix, Cc, 1)
+
+    def sums(beta):
+        out = (C.c_double * 4)()
+        _lib.check(lib.depgan_eval_temperature_sums(_p(p), kind, Cc, _p(lab), ignore, _p(m), npix, float(beta), eps,
+                                                    _p(scratch), out, stream), "depgan_eval_temperature_sums")
+        return tuple(float(v) for v in out)
+
+    return solve_temperature(sums, bounds, tol, max_iter)
+
+
+def apply_temperature(prob, T, eps=1e-7, out=None):
+    """softmax(log(max(prob, eps)) / T) per pixel, formed in double and rounded once: a device tensor of the shape and
+    kind (float32 / float64) of prob, which may be host or device.  out: a contiguous device tensor of that shape and
+    kind to write into -- prob itself scales in place.  Enqueued on the current stream; nothing synchronises."""
+    who = "apply_temperature"
+    shape, kind, _, eps = _cal_args(who, prob, eps=eps, need_labels=False)
+    try:
+        beta = 1.0 / float(T)
+    except (TypeError, ValueError, ZeroDivisionError):
+        beta = float("nan")
+    if not (0.0 < beta < float("inf")):
+        raise ValueError("%s: T must be a finite positive temperature, got %r" % (who, T))
+    torch = _torch()
+    dtype = torch.float64 if kind else torch.float32
+    if out is not None:
+        if not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == dtype and tuple(out.shape) == shape
+                and out.is_contiguous() and out.data_ptr() % 16 == 0):
+            raise ValueError("%s: out must be a contiguous device tensor of the shape and kind of prob" % who)
+    lib = _lib.load()
+    dev = out.device if out is not None else _surface_device(prob)
+    p = out if out is prob else _cal_tensor(prob, dev, dtype)
+    if out is None:
+        out = torch.empty(shape, dtype=dtype, device=dev)
+    stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+    _lib.check(lib.depgan_eval_apply_temperature(_p(p), kind, shape[3], beta, eps, _p(out), shape[0] * shape[1] * shape[2],
+                                                 stream), "depgan_eval_apply_temperature")
+    return out

@@ -682,6 +682,79 @@ int depgan_eval_cc_label(const unsigned char* set, int D, int H, int W, int conn
 int depgan_eval_cc_overlap(const int* labels, const unsigned char* other_or_null, long n, int n_comp, int* size,
                            int* hits, void* stream);
 
+/* ---- calibration of the class probabilities (csrc/calibration.hip; evaluate.calibration_census, fit_temperature,
+ * apply_temperature) ----
+ * Can the probabilities be believed?  Stateless; device pointers except the *_host outputs; enqueued on `stream`; no
+ * global atomics.  Every double operation below is one correctly rounded operation in the stated order.
+ * Shared conventions: prob is (npix, C) row-contiguous and 16-byte aligned, float32 for prob_kind 0 (predict) and float64
+ * for prob_kind 1 (predict_mean, stats['mean']), C = 2..DEPGAN_MAX_HEAD_CLASSES.  lab is (npix) uint8 class codes,
+ * ignore_label -1 (none) or 0..255, mask (npix) float32 or NULL.  Every element is converted to double first (exact), so
+ * one rule serves both kinds.  A pixel is classified by the first statement that applies:
+ *     mask[x] == 0 (mask given), or lab[x] == ignore_label      takes no part and is counted nowhere
+ *     lab[x] >= C                                               n_bad; takes no part; its row is not read
+ *     an element of its row is a NaN                            n_nan; takes no part
+ *     otherwise                                                 TAKES PART; tc = lab[x] is its true class
+ *   max(a, b) below is a < b ? b : a, so a NaN stays one.
+ * depgan_eval_calibration_census: with
+ *     b(v) = (int)min(max(v * bins, 0.0), bins - 1)              the product, the clamps and the truncation in double;
+ *                                                                bins = 1..DEPGAN_CAL_MAX_BINS; v = k/bins sits in bin k
+ *                                                                where the product is exact, 1.0 in bin bins - 1
+ *     q(v) = (long long)rint(v * 2^DEPGAN_CAL_FIX_SHIFT)         the product is exact (a power of two), one rounding to
+ *                                                                integer, ties to even; q(1) = 2^32
+ *   over the pixels that take part:
+ *     top label   conf = the first maximum of the row, pred = its index (depgan_eval_label_counts' tie rule, the lower
+ *                 index wins); table 0, bin b(conf): count += 1, hits += (pred == tc), sum_q += q(conf)
+ *     class k     (one against the rest) table 1 + k, bin b(p_k): count += 1, hits += (tc == k), sum_q += q(p_k)
+ *     scalars     N += 1; n_floored += (r < eps), r = p_tc; n_nan and n_bad as above
+ *     Brier       bs = 0; for c = 0..C-1: d = p_c - (c == tc ? 1.0 : 0.0); bs = bs + d * d.  The sum of bs.
+ *     NLL         l = 0.0 - log(max(r, eps)), natural log in double.  The sum of l.  With eps = 0 nothing is floored and
+ *                 r = 0 gives +inf: stated, not hidden.
+ *   counts_out_host: (1 + C) * bins * 3 + 4 long long -- element ((j * bins + b) * 3 + f) is field f (0 count, 1 hits,
+ *     2 sum_q) of bin b of table j, then {N, n_nan, n_bad, n_floored}.  sums_out_host: {Brier sum, NLL sum}.
+ *   Everything in counts_out_host is an integer sum: it does not depend on the order of addition, repeats bit for bit,
+ *   and a NumPy restatement gives the same bits (tests/calibration_ref.py).  A bin's mean confidence
+ *   sum_q / (count * 2^32) is within 2^-33 of the mean of its values: |q(v) / 2^32 - v| <= 2^-33 per value (half a unit
+ *   of the fixed point), the integer sum adds nothing, and a mean of errors is no larger than the largest.  sum_q is
+ *   exact in 64 bits: |q| <= 2^32 for elements in [0, 1] and npix < 2^31.  Elements are expected in [0, 1]; any finite
+ *   element is binned by the clamp, and |v| >= 2^31 or an infinite v leaves sum_q unspecified.
+ *   The two double sums: a thread adds its pixels in grid-stride order, a fixed tree over the block's 256 threads, one
+ *   partial per block, and one block adds the partials in index order.  The grid is a function of npix alone
+ *   (min(ceil(npix / 1024), 1024) blocks), so the bits repeat from call to call.  No float atomics.
+ *   Integers: a wave peels its distinct bins with ballots and adds once per distinct bin to the block's table in LDS
+ *   (integer LDS adds); a block stores its table to scratch with plain stores; a finishing launch adds the tables.
+ *   scratch: depgan_eval_calibration_scratch_bytes(npix, C, bins) device bytes (0 outside the limits), 8-byte aligned.
+ *   Synchronises `stream` and copies the two tables to the host, as depgan_eval_surface_sums does.
+ * depgan_eval_temperature_sums: over the pixels that take part, out_host = {N, sum L, sum L', sum L''} (N an integer
+ *   held in a double) of the loss of the temperature-scaled probabilities at beta = 1 / T, eps in (0, 1):
+ *     z_c = log(max(p_c, eps));  s_c = beta * z_c
+ *     m = the maximum of s (folded left to right);  e_c = exp(s_c - m);  S = ((e_0 + e_1) + ...) in channel order
+ *     lse = m + log(S);  pi_c = e_c / S
+ *     A = sum_c pi_c * z_c;  B = sum_c pi_c * (z_c * z_c)        from 0.0, in channel order
+ *     L = lse - s_tc;  L' = A - z_tc;  L'' = B - A * A
+ *   L' and L'' are the first and second derivative of L in beta; L is convex in beta (L'' is a variance), which is why
+ *   the entry is stated in beta and not in T.  The partial pattern of the two double sums above.  scratch:
+ *   depgan_eval_calibration_scratch_bytes(npix, C, 1) bytes suffice.  Synchronises `stream`.
+ * depgan_eval_apply_temperature: every pixel (no labels): z, s, m, S and lse as above with eps in [0, 1), then
+ *     out_c = exp(s_c - lse)     in double, rounded once to the kind of prob
+ *   out (the kind, shape and alignment of prob) may be prob itself or a disjoint range: a thread reads its whole row
+ *   before it writes it.  Does not synchronise.
+ * Status 1, nothing launched, every buffer untouched: npix outside 1 .. 2^31 - 1, C outside 2..DEPGAN_MAX_HEAD_CLASSES,
+ *   bins outside 1..DEPGAN_CAL_MAX_BINS, prob_kind not 0 / 1, ignore_label outside -1..255, eps not in [0, 1) (not in
+ *   (0, 1) for depgan_eval_temperature_sums), beta not finite or <= 0, a required pointer NULL, prob or out not 16-byte,
+ *   mask not 4-byte or scratch not 8-byte aligned, scratch overlapping prob, lab or mask, or out overlapping prob
+ *   without being prob. */
+#define DEPGAN_CAL_MAX_BINS 64
+#define DEPGAN_CAL_FIX_SHIFT 32
+size_t depgan_eval_calibration_scratch_bytes(long npix, int C, int bins);
+int depgan_eval_calibration_census(const void* prob, int prob_kind, int C, const unsigned char* lab, int ignore_label,
+                                   const float* mask, long npix, int bins, double eps, void* scratch,
+                                   long long* counts_out_host, double* sums_out_host, void* stream);
+int depgan_eval_temperature_sums(const void* prob, int prob_kind, int C, const unsigned char* lab, int ignore_label,
+                                 const float* mask, long npix, double beta, double eps, void* scratch,
+                                 double out_host[4], void* stream);
+int depgan_eval_apply_temperature(const void* prob, int prob_kind, int C, double beta, double eps, void* out, long npix,
+                                  void* stream);
+
 /* ---- parity-test surface: the tensors a training closure left behind ----
  * The step functions are piecewise linear in the ReLU signs and max-pool arg-maxes of the forward passes (GT:256-309
  * activations, GT:322-335 pools; the gradient penalty of GT:543-549 differentiates through them twice).  A parity
