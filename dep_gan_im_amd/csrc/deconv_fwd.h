@@ -20,6 +20,8 @@ struct DeconvArgs {
 // H and W powers of two with W >= 8, B H W % 32 == 0) and DEPGAN_DECONV_FUSED is not 0
 bool dg_deconv_fwd_supported(int B, int H, int W, int Cin, int Cout, TView in, TView out);
 int dg_deconv_fwd(DeconvArgs a, int B, hipStream_t st);
+// its geometry for dense operands, no launch: out = {32-pixel tiles, gridDim.x, gridDim.y, workgroups per CU counted on}
+int dg_deconv_fwd_plan(int B, int H, int W, int Cin, int Cout, long out[4]);
 // the entry it launches for a covered layer (its name is what the profiles print)
 const DgKernel* dg_deconv_fwd_kernel(int Cin, int W);
 

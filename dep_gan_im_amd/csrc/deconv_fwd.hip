@@ -299,8 +299,19 @@ const DgKernel kDeconv[3][2] = {{DECONV_K(64, 2, false), DECONV_K(64, 2, true)},
                                 {DECONV_K(128, 2, false), DECONV_K(128, 2, true)}};
 #undef DECONV_K
 
-int launch(const DgKernel& k, const DeconvArgs& a, int ny, hipStream_t st) {
+int mt_for(int Cin) { return Cin == 96 ? 3 : 2; }
+
+// the launch geometry of a covered shape: the one place that decides it (dg_deconv_fwd launches it, dg_deconv_fwd_plan
+// reports it)
+struct DeconvGeom {
+  const DgKernel* k;
+  int nTiles, gx, ny, per_cu;
+};
+int prepare(int B, int H, int W, int Cin, int Cout, DeconvGeom* g) {
   static int per_cu_dev[6][DG_MAX_DEVICES] = {};   // occupancy belongs to the device
+  const DgKernel& k = *dg_deconv_fwd_kernel(Cin, W);
+  const int ny = 4 * Cout / (128 * mt_for(Cin));
+  const int nTiles = (int)((long)B * H * W / 32);
   const int slot = dg_device_slot(), e = (int)(&k - &kDeconv[0][0]);
   int per_cu = slot >= 0 ? per_cu_dev[e][slot] : 0;
   if (!per_cu) {
@@ -317,12 +328,12 @@ int launch(const DgKernel& k, const DeconvArgs& a, int ny, hipStream_t st) {
   }
   const int cus = dg_cu_count();
   int gx = cus * per_cu / ny;
-  if (gx > a.nTiles) gx = a.nTiles;
+  if (gx > nTiles) gx = nTiles;
   if (gx < 1) gx = 1;
-  return dg_launch(k, (unsigned)gx, 256, (size_t)k.attr_lds, &a, st, (unsigned)ny);
+  *g = {&k, nTiles, gx, ny, per_cu};
+  return DG_OK;
 }
 
-int mt_for(int Cin) { return Cin == 96 ? 3 : 2; }
 int ilog2_exact(int v) {
   if (v <= 0 || (v & (v - 1))) return -1;
   int l = 0;
@@ -348,6 +359,9 @@ bool dg_deconv_fwd_supported(int B, int H, int W, int Cin, int Cout, TView in, T
   if (in.sX != Cin || in.sY != (long)W * Cin || in.sB != (long)H * W * Cin) return false;
   if (((uintptr_t)in.p | (uintptr_t)out.p) & 15) return false;
   if ((out.sX | out.sY | out.sB) & 3) return false;
+  // the same bound for a view whose samples overlap or whose strides run backwards: the last float the launch stores
+  if (out.sX < Cout || out.sY < 0 || out.sB < 0 || out.sY > 0x7FFFFFFFL || out.sX > 0x7FFFFFFFL) return false;
+  if ((long)(B - 1) * out.sB + (2L * H - 1) * out.sY + (2L * W - 1) * out.sX + Cout > 0x7FFFFFFFL) return false;
   return true;
 }
 
@@ -362,10 +376,22 @@ int dg_deconv_fwd(DeconvArgs a, int B, hipStream_t st) {
     dg_set_error("dg_deconv_fwd: weights / bias / scale / shift must be 16-byte aligned (scale needs shift)");
     return DG_ERR_ARG;
   }
-  a.nTiles = (int)((long)B * a.H * a.W / 32);
+  DeconvGeom g;
+  DGCHECK(prepare(B, a.H, a.W, a.Cin, a.Cout, &g));
+  a.nTiles = g.nTiles;
   a.lgW = ilog2_exact(a.W);
   a.lgH = ilog2_exact(a.H);
-  const int MT = mt_for(a.Cin);
-  const int ny = 4 * a.Cout / (128 * MT);
-  return launch(*dg_deconv_fwd_kernel(a.Cin, a.W), a, ny, st);
+  return dg_launch(*g.k, (unsigned)g.gx, 256, (size_t)g.k->attr_lds, &a, st, (unsigned)g.ny);
+}
+
+int dg_deconv_fwd_plan(int B, int H, int W, int Cin, int Cout, long out[4]) {
+  if (!dg_deconv_fwd_supported(B, H, W, Cin, Cout, make_view(nullptr, H, W, Cin), make_view(nullptr, 2 * H, 2 * W, Cout))) {
+    dg_set_error("dg_deconv_fwd: shape %dx%dx%d %d->%d not covered by the fused transposed-convolution kernel", B, H, W,
+                 Cin, Cout);
+    return DG_ERR_UNSUPPORTED;
+  }
+  DeconvGeom g;
+  DGCHECK(prepare(B, H, W, Cin, Cout, &g));
+  out[0] = g.nTiles; out[1] = g.gx; out[2] = g.ny; out[3] = g.per_cu;
+  return DG_OK;
 }

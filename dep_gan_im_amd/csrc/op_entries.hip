@@ -166,18 +166,35 @@ int depgan_op_conv2d_wgrad_bf16(const float* x, const float* dy, float* dw, int 
                   make_view(const_cast<float*>(dy), H, W, Cout), B, H, W, Cin, Cout, true, nullptr, dw, nullptr, 0, 0,
                   nullptr, (hipStream_t)stream);
 }
-int depgan_op_deconv2x2(const float* in, const float* w_hwoi, const float* bias, const float* scale,
-                        const float* shift, float* out, int B, int H, int W, int Cin, int Cout, int relu,
-                        void* stream) {
-  if (!in || !w_hwoi || !out || B < 1 || H < 1 || W < 1) { dg_set_error("op_deconv2x2: bad argument"); return DG_ERR_ARG; }
+static int op_deconv2x2(const float* in, const float* w_hwoi, const float* bias, const float* scale, const float* shift,
+                        TView out, int B, int H, int W, int Cin, int Cout, int relu, void* stream) {
+  if (!in || !w_hwoi || !out.p || B < 1 || H < 1 || W < 1) { dg_set_error("op_deconv2x2: bad argument"); return DG_ERR_ARG; }
   DeconvArgs d;
   memset(&d, 0, sizeof(d));
   d.in = in;
   d.w = w_hwoi;
-  d.out = make_view(out, 2 * H, 2 * W, Cout);
+  d.out = out;
   d.bias = bias; d.scale = scale; d.shift = shift; d.relu = relu;
   d.H = H; d.W = W; d.Cin = Cin; d.Cout = Cout;
   return dg_deconv_fwd(d, B, (hipStream_t)stream);
+}
+int depgan_op_deconv2x2(const float* in, const float* w_hwoi, const float* bias, const float* scale,
+                        const float* shift, float* out, int B, int H, int W, int Cin, int Cout, int relu,
+                        void* stream) {
+  return op_deconv2x2(in, w_hwoi, bias, scale, shift, make_view(out, 2 * H, 2 * W, Cout), B, H, W, Cin, Cout, relu, stream);
+}
+int depgan_op_deconv2x2_ex(const float* in, const float* w_hwoi, const float* bias, const float* scale,
+                           const float* shift, float* out, long osB, long osY, long osX, int B, int H, int W, int Cin,
+                           int Cout, int relu, void* stream) {
+  return op_deconv2x2(in, w_hwoi, bias, scale, shift, op_view(out, osB, osY, osX), B, H, W, Cin, Cout, relu, stream);
+}
+// host only: the geometry dg_deconv_fwd launches a dense layer of this shape with
+int depgan_debug_deconv_fwd_plan(int B, int H, int W, int Cin, int Cout, long out[4]) {
+  if (!out || B < 1 || H < 1 || W < 1 || Cin < 1 || Cout < 1) {
+    dg_set_error("debug_deconv_fwd_plan: null or non-positive argument");
+    return DG_ERR_ARG;
+  }
+  return dg_deconv_fwd_plan(B, H, W, Cin, Cout, out);
 }
 int depgan_op_deconv2x2_wgrad(const float* in, const float* dout, float* dw_hwoi, float* colsum, int B, int H, int W,
                               int Cin, int Cout, void* stream) {

@@ -1003,6 +1003,21 @@ int depgan_op_maxpool(const float* in, float* out, int B, int Ho, int Wo, int C,
 int depgan_op_deconv2x2(const float* in, const float* w_hwoi, const float* bias, const float* scale,
                         const float* shift, float* out, int B, int H, int W, int Cin, int Cout, int relu,
                         void* hip_stream);
+/* The same launch with the output given as a view: out points at sample 0, row 0, column 0, channel 0 of the (2H, 2W)
+ * output grid and osB / osY / osX are its float strides between samples, rows and pixels -- the channel slice of a concat
+ * buffer the model stores into (osX > Cout).  Status 3 when the kernel does not cover the launch: the shapes above, an
+ * out that is not 16-byte aligned, a stride that is no multiple of 4, or B * osB above 2^31 - 1 (the kernel addresses the
+ * output with 32-bit float offsets).  A refusal launches and writes nothing. */
+int depgan_op_deconv2x2_ex(const float* in, const float* w_hwoi, const float* bias, const float* scale,
+                           const float* shift, float* out, long osB, long osY, long osX, int B, int H, int W, int Cin,
+                           int Cout, int relu, void* hip_stream);
+/* Host only (no launch, no allocation): the geometry the launcher of the fused forward kernel takes for a dense launch of
+ * this shape on the current device, from the function the launcher itself calls.
+ * out = {32-pixel tiles, gridDim.x, gridDim.y, workgroups per CU the launcher counts on}: gridDim.x =
+ * min(CUs * workgroups per CU / gridDim.y, tiles), and workgroup x walks the tiles x, x + gridDim.x, ...
+ * Status 3 for a shape the kernel does not cover, status 1 for a null `out` or a non-positive size.  A refusal writes
+ * nothing. */
+int depgan_debug_deconv_fwd_plan(int B, int H, int W, int Cin, int Cout, long out[4]);
 
 /* Weight gradient of the same layer on the fused kernel (four taps + the column sums of dout in one launch):
  * dw_hwoi[di][dj][co][ci] = sum_p dout[b][2i+di][2j+dj][co] in[b][i][j][ci]; colsum[co] (optional) = sum of dout over

@@ -29,7 +29,8 @@ Operators whose views share ONE stride triple (depgan_op_bn_backward, depgan_op_
 far allocation at once, interleaved at that stride.  Entries that take dense tensors only (depgan_op_deconv2x2,
 depgan_op_conv2d_wgrad_bf16, depgan_op_maxpool) cannot be handed a far view; the bf16 weight gradient is reached through
 depgan_op_conv2d_wgrad_ex(bf16 = 1) and depgan_op_conv2d_wgrad_bf16s.  dg_deconv_fwd_supported refuses B * sB > 2^31 - 1
-floats by itself.
+floats by itself: depgan_op_deconv2x2_ex, the same kernel with a strided output, cannot span 2 GiB either -- its views and
+that refusal are tests/test_gpu_deconv_tiles.py.
 """
 import ctypes as C
 import functools

@@ -271,7 +271,10 @@ def test_bf16_mfma_conv_weight_gradient(lib, case):
 
 
 DECONV_CASES = [  # B,H,W,Cin,Cout,affine: the three instantiations (64 / 96 / 128 input channels), two channel
-    # halves per pixel tile (Cout = 128), image rows shorter than a 32-pixel tile, H != W
+    # halves per pixel tile (Cout = 128), image rows shorter than a 32-pixel tile, H != W.  These launches have 4 to 64
+    # tiles, fewer than the kernel has workgroups: every workgroup runs ONE tile, i.e. the first-tile body and the tail
+    # store only.  The steady-state body of the persistent loop (two and more tiles per workgroup, uneven trip counts)
+    # and strided output views are tests/test_gpu_deconv_tiles.py.
     (2, 32, 32, 64, 64, True), (1, 16, 64, 96, 96, True), (2, 16, 16, 128, 128, True), (4, 8, 8, 64, 64, False),
     (1, 4, 32, 64, 128, False), (3, 32, 16, 96, 96, False), (2, 16, 8, 128, 64, True),
 ]

@@ -24,6 +24,10 @@ ROWS = []          # (case id, entry name, builder(lib) -> Case)
 EXCLUDED = {
     "depgan_op_conv2d_stamps": "a timing aid: its output is per-workgroup clock stamps, which no two runs share",
 }
+# Entries that report a launcher's plan and enqueue nothing: they take no stream, so they are no rows of this table.
+# tests/test_stream_table_cpu.py holds the list against the header (none of them has a stream parameter or a row).
+HOST_ONLY = ["depgan_debug_wgrad_plan", "depgan_debug_wgrad_choice", "depgan_debug_conv_choice",
+             "depgan_debug_deconv_fwd_plan"]
 
 
 def row(fn, tag=""):
@@ -111,6 +115,16 @@ def _(lib):
     r = rng_of("deconv2x2")
     return Case("depgan_op_deconv2x2", [In(f32(r, B, H, W, ci)), In(f32(r, 2, 2, co, ci)), In(f32(r, co)), In(f32(r, co)),
                                         In(f32(r, co)), F(B * 4 * H * W * co), B, H, W, ci, co, 1, STREAM], sync=False)
+
+
+@row("depgan_op_deconv2x2_ex")
+def _(lib):
+    B, H, W, ci, co = DECONV
+    Ct = co + 32                           # the first co channels of a wider concat buffer
+    r = rng_of("deconv2x2_ex")
+    return Case("depgan_op_deconv2x2_ex", [In(f32(r, B, H, W, ci)), In(f32(r, 2, 2, co, ci)), In(f32(r, co)), In(f32(r, co)),
+                                           In(f32(r, co)), F(B * 4 * H * W * Ct), *dense(2 * H, 2 * W, Ct), B, H, W, ci, co, 1,
+                                           STREAM], sync=False)
 
 
 @row("depgan_op_deconv2x2_wgrad")

@@ -211,7 +211,8 @@ def test_step_operator_entries_are_exported_and_bound(lib):
         assert getattr(lib, name).argtypes, name + " has no argtypes"
 
 
-DEBUG_ENTRIES = ["capture", "tensor", "tensor_bf16s", "film_decision_bf16s", "wgrad_plan", "wgrad_choice", "conv_choice"]
+DEBUG_ENTRIES = ["capture", "tensor", "tensor_bf16s", "film_decision_bf16s", "wgrad_plan", "wgrad_choice", "conv_choice",
+                 "deconv_fwd_plan"]
 
 
 def test_debug_entries_are_exported_and_bound(lib):
@@ -248,6 +249,10 @@ def _pinned_signatures():
         "depgan_op_unpool_mask_bf16s": (i, [vp, L, L, L] * 4 + [i] * 4 + [vp]),
         "depgan_debug_tensor": (i, [vp, s, vp, L, vp]),
         "depgan_debug_wgrad_plan": (i, [i] * 7 + [vp]),      # host only; an `int out[4]` array parameter
+        "depgan_debug_deconv_fwd_plan": (i, [i] * 5 + [vp]),  # host only; a `long out[4]` array parameter
+        # depgan_op_deconv2x2 with the output as a view: six pointers, three strides, six ints, the stream
+        "depgan_op_deconv2x2_ex": (i, [vp] * 6 + [L] * 3 + [i] * 6 + [vp]),
+        "depgan_op_deconv2x2": (i, [vp] * 6 + [i] * 6 + [vp]),
     }
 
 
@@ -267,7 +272,7 @@ def test_every_prototype_is_bound_with_the_header_s_parameter_count(lib):
     parameters by the commas between the parentheses of the comment-stripped text."""
     hdr = open(os.path.join(ROOT, "include", "depgan.h")).read()
     declared = set(re.findall(r"\b(depgan_[a-z0-9_]+)\s*\(", hdr)) - {"depgan_ctx", "depgan_config"}
-    assert set(_lib.EXPORTS) == declared and len(_lib.EXPORTS) == len(declared) >= 112
+    assert set(_lib.EXPORTS) == declared and len(_lib.EXPORTS) == len(declared) >= 174
     stripped = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
     for name in sorted(declared):
         found = re.findall(r"\b%s\s*\(([^()]*)\)\s*;" % name, stripped)

@@ -52,6 +52,18 @@ def test_every_row_names_an_existing_entry_that_takes_a_stream():
     assert set(ops.NEGATIVE_CONTROL) <= set(ids)
 
 
+def test_host_only_plan_entries_take_no_stream_and_have_no_row():
+    """the entries that report a launcher's plan (`Host only` in the header) enqueue nothing: no stream parameter, no row;
+    every depgan_debug_*_plan / *_choice prototype of the header stands in the list"""
+    entries, rows = set(stream_entries()), {fn for _, fn, _ in ops.ROWS}
+    assert len(set(ops.HOST_ONLY)) == len(ops.HOST_ONLY) >= 4
+    for fn in ops.HOST_ONLY:
+        assert fn in _lib.EXPORTS and fn not in entries and fn not in rows and fn not in ops.EXCLUDED, fn
+    plans = [n for n in _lib.EXPORTS if re.fullmatch(r"depgan_debug_\w+_(plan|choice)", n)]
+    assert sorted(plans) == sorted(ops.HOST_ONLY)
+    assert "depgan_debug_deconv_fwd_plan" in plans and "depgan_op_deconv2x2_ex" in rows
+
+
 def test_every_row_has_the_entrys_parameter_count_and_one_stream(lib):
     """the builders run on the host (they ask the library for scratch sizes, host-only calls): the argument list of every
     row has the length of the header's prototype and exactly one stream"""
